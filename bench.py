@@ -483,6 +483,32 @@ def tie_band_mismatches(ref_score, got_rank, pos, mask, band):
     return int(((got_rank < best) | (got_rank > worst)).sum())
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """`--dump-outputs DIR`: each array as DIR/<name>.npy, float32 (float64 stays float64), so that two builds can be compared
+    output for output.  An array that would take the whole DUMP_BYTES budget or more is replaced by a fixed, seeded sample of
+    its flattened entries (sorted), their flat indices written beside it as <name>_index.npy (float64, exact).  Returns
+    {name: what was written} for the JSON line."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu()
+        a = (a.double() if a.dtype == torch.float64 else a.float()).numpy()
+        rec = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        if a.nbytes >= DUMP_BYTES // len(arrays):
+            k = (DUMP_BYTES // len(arrays) - 4096) // (a.itemsize + 8)   # (sample + its float64 indices + two .npy headers)
+            index = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            np.save(os.path.join(directory, name + "_index.npy"), index.astype(np.float64))
+            rec["sample"] = "%d of %d entries, seed 0: flat indices in %s_index.npy" % (k, a.size, name)
+            a = a.reshape(-1)[index]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+        written[name] = rec
+    return written
+
+
 def stub_main(args):
     """`--stub-cpu`: the program of an N-rank run with everything GPU-bound replaced by a stub -- what can be checked of the
     1 / 2 / 4 / 8-GPU half of the metric where no multi-GPU box exists.  Same control flow as main(): self-launch under
@@ -507,7 +533,9 @@ def stub_main(args):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         with _stdout_to_stderr():      # (gloo's connection banner is written to stdout by C code; stdout carries ONE line)
             dist.init_process_group("gloo")
-            dist.barrier()
+            # (monitored_barrier: gloo's CPU barrier.  dist.barrier() asks torch for the machine's accelerator first, which
+            # starts the GPU runtime in every stub rank wherever a GPU exists -- the dry run must leave the GPU alone)
+            dist.monitored_barrier()
     from ultra_amd import distributed as udist
     from ultra_amd import host_order, synthetic, tasks
     from ultra_amd.graph import PipelinedForward
@@ -547,13 +575,13 @@ def stub_main(args):
     for i in range(args.warmup):
         one_step(i)
     if world > 1:
-        dist.barrier()
+        dist.monitored_barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
         last = one_step(args.warmup + i)
     piped.join()
     if world > 1:
-        dist.barrier()
+        dist.monitored_barrier()
     elapsed = time.perf_counter() - t0
     el = torch.tensor([elapsed], dtype=torch.float64)
     per_rank = None
@@ -593,10 +621,13 @@ def stub_main(args):
                       "batch_per_gpu": bs, "triples_per_step_per_gpu": bs * N, "rccl_world_size": world if gather else 1,
                       "collective_backend": "gloo (CPU dry run)" if gather else None, "per_rank": per_rank,
                       "parallelism": "query-shard x%d + all-gather of scores" % world if world > 1 else "single process"}}
+    if rank == 0 and args.dump_outputs:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "step": args.warmup + args.steps - 1,
+                               "arrays": dump_outputs(args.dump_outputs, {"scores": last} if args.steps > 0 else {})}
     if rank == 0:
         print(json.dumps(out), flush=True)
     if gather:
-        dist.barrier()
+        dist.monitored_barrier()
         dist.destroy_process_group()
 
 
@@ -634,6 +665,11 @@ def main():
                     help="dry run of the N-rank program WITHOUT GPUs (tests/test_bench_cpu.py): the launcher path, the gloo "
                          "process group, the shared readout order, the per-step all-gather behind each pipeline slot, the "
                          "barrier-fenced max-over-ranks clock and the JSON line, around a stub scorer on CPU -- not a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in the last of the K timed steps of the first "
+                         "run -- the (bs, num_nodes) scores; with several ranks the all-gathered (ranks * bs, num_nodes) rows -- to "
+                         "DIR/scores.npy (float32; the inputs are seeded: the same arguments give the same inputs, so two builds "
+                         "compare output for output)")
     ap.add_argument("--pmc-target", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--trace-target", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -774,7 +810,9 @@ def main():
 
     pre_warm = [max(args.pre_warm, 0)]      # (consumed by the first timed run)
 
-    def timed_run(forward, gather):
+    def timed_run(forward, gather, keep=None):
+        """W warm-up + K timed steps; returns the K steps' seconds.  keep: a dict that receives a copy of the last timed step's
+        result as "scores" (taken after the clock stops: a captured forward's output buffer is reused by its next replay)."""
         def one_step(step):
             # (bs, N) scores; with `gather` one RCCL all-gather per step, enqueued right behind the forward on its stream:
             # (world * bs, N)
@@ -802,12 +840,16 @@ def main():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for i in range(args.steps):
-                one_step(args.warmup + i)
+                last = one_step(args.warmup + i)
             torch.cuda.synchronize()
             if world > 1:
                 dist.barrier()
             torch.cuda.synchronize()
-            return time.perf_counter() - t0
+            elapsed_ = time.perf_counter() - t0
+            if keep is not None and args.steps > 0:
+                keep["scores"] = last.detach().clone()
+                torch.cuda.synchronize()
+            return elapsed_
 
     roofline = None
     if rank == 0 and world == 1 and not launched and not args.no_roofline:
@@ -815,7 +857,8 @@ def main():
         # region: it is independent of it, and the GPU then enters the timed steps from sustained work rather than from idle
         roofline = measure_roofline(dev, use_pmc=not args.no_pmc, in_flight=1 if args.no_graph else args.in_flight)
     forward = make_forward()
-    elapsed = timed_run(forward, world > 1 or launched)
+    dumped = {} if args.dump_outputs and rank == 0 else None
+    elapsed = timed_run(forward, world > 1 or launched, keep=dumped)
     # the same K steps again, `--repeats` runs in all: box-to-box and run-to-run spread is of the size of a small kernel gain,
     # so the line carries the median and the extremes beside the first run's figure
     runs = [elapsed] + [timed_run(forward, world > 1 or launched) for _ in range(max(args.repeats, 1) - 1)]
@@ -885,6 +928,9 @@ def main():
                    "per_rank": per_rank,
                    "parallelism": "query-shard x%d + RCCL all-gather of scores" % world if world > 1 else "single GPU"},
     }
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "step": args.warmup + args.steps - 1,
+                               "arrays": dump_outputs(args.dump_outputs, dumped)}
 
     if rank == 0 and not args.no_roofline:
         # (counter passes only at N = 1: they re-run the kernels in a child process on this rank's GPU)

@@ -1,4 +1,6 @@
 """Shared test utilities: seeded graphs and a host emulation of the kernel's plan walk."""
+import os
+
 import numpy as np
 import torch
 
@@ -141,3 +143,30 @@ def assert_sum_close(got, want, edge_index, edge_type, edge_weight, relation, in
     diff = (got - want).abs()
     bad = diff > bound
     assert not bad.any(), "max excess %g at %s" % ((diff - bound).max().item(), bad.nonzero()[0].tolist())
+
+
+REFERENCE_TU = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_tu.pt.xz")
+
+
+def load_reference_tu():
+    """What the reference's own compiled rspmm.cpp TU (oracle/_ref) returned, recorded by tests/golden/gen_reference_tu.py."""
+    import io
+    import lzma
+    with open(REFERENCE_TU, "rb") as f:
+        return torch.load(io.BytesIO(lzma.decompress(f.read())))
+
+
+def fingerprint(*tensors):
+    """SHA-256 of the dtypes, shapes and bits of `tensors`: pins operands and bit-exact results in the recorded vectors."""
+    import hashlib
+    h = hashlib.sha256()
+    for t in tensors:
+        t = t.detach().cpu().contiguous()
+        h.update(("%s%s" % (t.dtype, tuple(t.shape))).encode())
+        h.update(t.numpy().tobytes())
+    return h.hexdigest()
+
+
+def sample_index(k, numel, size=256):
+    """Fixed, scattered flat indices of a sample of call k's output: distinct while 1000003 (prime) does not divide numel."""
+    return (torch.arange(min(size, numel)) * 1000003 + 7919 * k) % numel

@@ -81,8 +81,8 @@ def test_missing_library_fails_loudly(tmp_path, monkeypatch):
 
 def test_torch_binding_has_the_reference_extension_surface():
     """The pybind11 module `rspmm` (csrc/torch_binding/rspmm.cpp, a shim over the C ABI) exports the names of
-    /root/reference/ultra/rspmm/source/rspmm.cpp:256-283 with the same Tensor signatures -- checked against the
-    reference's own compiled module (oracle/_ref) where that is present -- so the unchanged wrapper
+    the reference's rspmm.cpp:256-283 with the same Tensor signatures -- checked against those of the reference's own
+    compiled module (oracle/_ref), recorded in tests/golden/reference_tu_signatures.json -- so the unchanged wrapper
     ultra/rspmm/rspmm.py can load it.  No GPU needed: the engine library is opened lazily, CPU calls raise."""
     import torch
     from ultra_amd import build
@@ -99,14 +99,15 @@ def test_torch_binding_has_the_reference_extension_surface():
                     assert doc.count("torch.Tensor") >= n_arg, doc
                     assert doc.split("->")[1].strip().replace("Tuple", "tuple") == ret, doc
                     sig[name] = doc.split("(", 1)[1]
-    from oracle import build_ref
-    if build_ref.available():
-        ref = build_ref.load()
-        ref_names = sorted(n for n in dir(ref) if n.startswith("rspmm_"))
-        assert ref_names == sorted(n for n in sig if n.endswith("_cpu"))          # built without CUDA_OP: the 12 cpu exports
-        for n in ref_names:
-            assert getattr(ref, n).__doc__.splitlines()[0].split("(", 1)[1].replace("Tuple", "tuple") == sig[n].replace("Tuple", "tuple")
-            assert sig[n] == sig[n.replace("_cpu", "_cuda")]
+    import json
+    # the reference's compiled module's exports and their pybind11 signatures, recorded by tests/golden/gen_reference_tu.py
+    with open(os.path.join(ROOT, "tests", "golden", "reference_tu_signatures.json")) as f:
+        ref = json.load(f)
+    ref_names = sorted(ref)
+    assert ref_names == sorted(n for n in sig if n.endswith("_cpu"))          # built without CUDA_OP: the 12 cpu exports
+    for n in ref_names:
+        assert ref[n].split("(", 1)[1].replace("Tuple", "tuple") == sig[n].replace("Tuple", "tuple")
+        assert sig[n] == sig[n.replace("_cpu", "_cuda")]
     x = torch.zeros(3, 4)
     with pytest.raises(RuntimeError, match="no CPU path"):
         mod.rspmm_add_mul_forward_cpu(torch.zeros(2, 0, dtype=torch.long), torch.zeros(0, dtype=torch.long), torch.zeros(0), x, x)

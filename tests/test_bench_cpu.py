@@ -44,3 +44,25 @@ def test_stub_ranks_print_one_line_of_the_contract(world):
 def test_stub_refuses_a_world_size_that_contradicts_gpus():
     r = _run(["--gpus", "2"], env={"WORLD_SIZE": "1", "RANK": "0", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29999"})
     assert r.returncode != 0 and "does not match" in (r.stderr + r.stdout)
+
+
+def test_stub_dump_outputs_is_the_last_timed_step_and_reproducible(tmp_path):
+    """--dump-outputs DIR: the last timed step's result as DIR/scores.npy (float32); the same arguments give the same array,
+    another --steps another step's batch."""
+    import numpy as np
+    dumps = {}
+    for tag, steps in (("a", 4), ("b", 4), ("c", 5)):
+        r = _run(["--steps", str(steps), "--warmup", "2", "--dump-outputs", str(tmp_path / tag)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][0])
+        assert d["steps"] == steps and d["dump_outputs"]["step"] == 2 + steps - 1
+        assert d["dump_outputs"]["arrays"]["scores"] == {"shape": [d["config"]["batch_per_gpu"], 512], "dtype": "float32"}
+        dumps[tag] = np.load(str(tmp_path / tag / "scores.npy"))
+        assert dumps[tag].dtype == np.float32 and dumps[tag].shape == (d["config"]["batch_per_gpu"], 512)
+    assert np.array_equal(dumps["a"], dumps["b"])
+    assert not np.array_equal(dumps["a"], dumps["c"])
+    # two ranks: the all-gathered rows of the last step
+    r = _run(["--gpus", "2", "--steps", "4", "--warmup", "2", "--dump-outputs", str(tmp_path / "w2")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][0])
+    assert np.load(str(tmp_path / "w2" / "scores.npy")).shape == (2 * d["config"]["batch_per_gpu"], 512)

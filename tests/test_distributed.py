@@ -35,6 +35,10 @@ def _free_port():
     return port
 
 
+# The ranks below stay on CPU: they synchronise with dist.monitored_barrier() (gloo's CPU barrier) because dist.barrier()
+# asks torch for the machine's accelerator first, which starts the GPU runtime in every rank wherever a GPU exists.
+
+
 def _worker(rank, world, port, out_dir):
     sys.path.insert(0, ROOT)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -54,7 +58,7 @@ def _worker(rank, world, port, out_dir):
     shards = udist.all_gather_shards(torch.arange(lo, hi).repeat_interleave(2).view(-1, 1) * torch.tensor([[1, 10]]), 7, rows_per_item=2)
     torch.save(dict(res=res, gathered=gathered, var=var, shards=shards, shard=udist.shard_range(37)),
                os.path.join(out_dir, "r%d.pt" % rank))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -102,7 +106,7 @@ def _world8_worker(rank, world, port, out_dir):
     # the per-step collective of the benchmark at this world size: every rank's (bs, N) score rows, rank-major
     gathered = udist.all_gather_scores(torch.full((2, 3), float(rank)))
     torch.save(dict(res=res, shard=(lo, hi), gathered=gathered), os.path.join(out_dir, "w%d.pt" % rank))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -167,7 +171,7 @@ def _order_worker(rank, world, port, out_dir):
     pf.join()
     torch.save(dict(before=before, shared=shared, after=after, gathered=torch.stack(gathered), source=host_order.readout_stages(128)[1]),
                os.path.join(out_dir, "o%d.pt" % rank))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 

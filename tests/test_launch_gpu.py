@@ -68,6 +68,38 @@ def test_bench_scores_real_triples_from_files():
     assert out["cpu_baseline"]["kind"] == "port" and out["cpu_baseline"]["value"] > 0
 
 
+def test_bench_dump_outputs_are_the_last_timed_steps_scores(tmp_path):
+    """bench.py --dump-outputs DIR: DIR/scores.npy holds what the timed path (captured forwards, three in flight) returned in
+    its last timed step -- the scores of step W + K - 1's batch, as the model scores that batch eagerly."""
+    import numpy as np
+    from ultra_amd import models, synthetic, tasks
+    W, K = 2, 5
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(K), "--warmup", str(W), "--repeats", "2",
+           "--no-cpu-baseline", "--no-roofline", "--no-secondary", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert out["steps"] == K and out["dump_outputs"]["step"] == W + K - 1
+    got = torch.from_numpy(np.load(str(tmp_path / "scores.npy")))
+    assert got.dtype == torch.float32 and out["config"]["launch"].startswith("hipGraph")
+
+    dev = torch.device("cuda:0")
+    data = synthetic.make_kg(**synthetic.SHAPES["fb15k237"], seed=1234)
+    model = models.Ultra(**synthetic.default_model_cfg())
+    model.load_state_dict(torch.load(os.path.join(ROOT, "tests", "golden", "ultra_3g_model.pt")))
+    model = model.to(dev).eval()
+    gdata = data.to(dev)
+    bs, triples = out["config"]["batch_per_gpu"], data.target_triples
+
+    def scores(step):           # bench.py's batch_for(step) at world size 1
+        lo = (step * bs) % (triples.shape[0] - bs)
+        with torch.no_grad():
+            return model(gdata, tasks.all_negative(data, triples[lo:lo + bs])[0].to(dev)).cpu()
+    assert got.shape == (bs, data.num_nodes)
+    torch.testing.assert_close(got, scores(W + K - 1), rtol=0, atol=1e-6)
+    assert (got - scores(W + K - 2)).abs().max().item() > 1e-3         # not the step before
+
+
 def test_bench_refuses_more_gpus_than_visible():
     n = torch.cuda.device_count() + 1
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "1", "--warmup", "0"],

@@ -1,11 +1,13 @@
 """Pins the model-level oracle (oracle/ultra_oracle_model.py) to the reference: golden scores recorded
-from the unchanged reference modules + shipped checkpoints (tests/golden/gen_golden.py).  CPU only."""
+from the unchanged reference modules + shipped checkpoints (tests/golden/gen_golden.py), and every rspmm call of the
+forward against the reference TU's recorded output at that call (tests/golden/gen_reference_tu.py).  CPU only."""
 import os
 
 import pytest
 import torch
 
-from oracle import build_ref, ultra_oracle_model
+from oracle import rspmm_oracle, ultra_oracle_model
+from tests import helpers
 from ultra_amd import synthetic
 from ultra_amd.data import Data
 
@@ -23,17 +25,37 @@ def load_golden(ckpt, aggr):
     return g, state, data, synthetic.default_model_cfg(aggregate_func=aggr)
 
 
+def recorded_tu_checker(calls):
+    """An rspmm_fn for ultra_forward: the C oracle's result of each call, checked on a seeded sample of its entries against
+    what the reference's own rspmm.cpp TU (oracle/_ref) returned at the same call of the same forward
+    (tests/golden/reference_tu.pt.xz, gen_reference_tu.py)."""
+    seen = []
+
+    def fn(edge_index, edge_type, edge_weight, relation, input, sum="add", mul="mul"):
+        out = rspmm_oracle.generalized_rspmm(edge_index, edge_type, edge_weight, relation, input, sum=sum, mul=mul)
+        rec = calls[len(seen)]
+        assert (rec["shape"], rec["sum"], rec["mul"]) == (tuple(out.shape), sum, mul), "call %d" % len(seen)
+        # same tolerance as the scores: the inputs of a call went through this host's torch CPU ops
+        got = out.reshape(-1)[helpers.sample_index(len(seen), out.numel())]
+        torch.testing.assert_close(got, rec["value"], rtol=1e-4, atol=2e-5)
+        seen.append(rec)
+        return out
+    return fn, seen
+
+
 @pytest.mark.parametrize("ckpt,aggr", MODELS)
 @pytest.mark.parametrize("kernel", ["c_oracle", "reference_tu"])
 def test_oracle_model_matches_reference_scores(ckpt, aggr, kernel):
     g, state, data, cfg = load_golden(ckpt, aggr)
-    fn = None
-    if kernel == "reference_tu":
-        if not build_ref.available():
-            pytest.skip("oracle/_ref not built")
-        fn = ultra_oracle_model.reference_rspmm_fn()
+    recorded = helpers.load_reference_tu()["model_calls"] if kernel == "reference_tu" else None
     for key_batch, key_pred in (("t_batch", "t_pred"), ("h_batch", "h_pred"), ("neg_batch", "neg_pred")):
+        fn = None
+        if recorded is not None:
+            calls = recorded[(ckpt, aggr, key_batch)]
+            fn, seen = recorded_tu_checker(calls)
         got = ultra_oracle_model.ultra_forward(state, cfg, data, g[key_batch], rspmm_fn=fn)
+        if recorded is not None:
+            assert len(seen) == len(calls) > 0
         assert got.shape == g[key_pred].shape
         # same algorithm, same dtype, different BLAS blocking / summation order only
         torch.testing.assert_close(got, g[key_pred], rtol=1e-4, atol=2e-5)
