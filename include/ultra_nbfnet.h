@@ -247,6 +247,27 @@ int32_t ultra_relation_graph_emit(const void *adj_dev, const int64_t *row_offset
                                   int64_t *edge_index_out_dev, int64_t *edge_type_out_dev, void *stream);
 int32_t ultra_relation_graph_dense_adjacency(const void *adj_dev, int64_t num_relation, void *a_ex_out_dev, void *stream);
 
+/*
+ * One layer of the path beam search behind BaseNBFNet.visualize (/root/reference/ultra/base_nbfnet.py:173-232), with the
+ * reference's semantics under stable sorts and exact top-k keys:
+ *   candidates of destination v: (e, b) for every in-edge e of v whose source is not `tail`, ascending edge id, then
+ *   beam b < num_beam; value m = dist_in[src(e), b] + edge_grad[e] (one fp32 add); prev_rank = the smallest j with
+ *   isclose(m(e, b), m(e, j)) (torch's default isclose); a candidate with the same (src, dst, type, prev_rank) as the one
+ *   directly before it is dropped; the top num_beam survivors by value (descending, ties to the earlier candidate, -inf
+ *   last) are kept, padded with the last one kept; a destination without candidates gets -inf and (0, 0, 0, 0).
+ * Graph: a destination-major CSR whose slots keep ascending edge id within every row -- row_ptr (num_node + 1) int64,
+ * csr_src / csr_type / csr_eid (num_edge) int32 -- and hub_rows (num_hub) int64: exactly the rows with more than
+ * ULTRA_BEAM_HUB_DEGREE slots (served by a workgroup each).  edge_grad (num_edge) fp32 by edge id; dist_in / dist_out
+ * (num_node, num_beam) fp32; back_edge_out (num_node, num_beam, 4) int64 [src, dst, type, prev_rank].  All device pointers;
+ * one writer per output row, no atomics.  num_beam outside [1, ULTRA_BEAM_MAX]: ULTRA_ERR_UNSUPPORTED.
+ */
+#define ULTRA_BEAM_MAX 64
+#define ULTRA_BEAM_HUB_DEGREE 256
+int32_t ultra_beam_search_layer(const int64_t *row_ptr, const int32_t *csr_src, const int32_t *csr_type, const int32_t *csr_eid,
+                                const int64_t *hub_rows, int64_t num_hub, int64_t num_node, int64_t num_edge,
+                                const void *edge_grad, const void *dist_in, int64_t tail, int32_t num_beam, void *dist_out,
+                                int64_t *back_edge_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

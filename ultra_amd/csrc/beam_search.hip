@@ -1,0 +1,319 @@
+// One layer of the path beam search of BaseNBFNet.visualize (reference: ultra/base_nbfnet.py:173-232), with the
+// semantics of DESIGN.md §9 -- the reference's with stable sorts and exact top-k keys:
+//
+//   candidates of destination v: (e, b) for every in-edge e of v whose source is not t, ascending edge id, then beam b;
+//   m(e, b)      = dist_in[src(e), b] + grad[e]                                     (one fp32 add)
+//   prev_rank    = smallest j with isclose(m(e, b), m(e, j)) (torch's default isclose on fp32), 0 if none
+//   dropped      : same (src, dst, type, prev_rank) as the candidate directly before it (before any removal)
+//   kept         : the top K survivors by value, descending, ties to the earlier candidate; -inf ranks last and ties;
+//                  fewer than K survivors: padded with the last one kept; none: -inf and (0, 0, 0, 0).
+//
+// Input: a destination-major CSR whose slots keep ascending edge id within each row (built once per graph by the host
+// layer: a stable sort by destination).  One wave per row scans its candidates in order, keeping the running top K in
+// lanes 0..K-1 (lane = rank): each edge's K candidates are merged by counting ranks (a permutation of the union, so the
+// kept entries land in distinct LDS slots) -- no atomics, one writer per destination, deterministic.  Rows of in-degree
+// above ULTRA_BEAM_HUB_DEGREE go to a second kernel: one workgroup of 16 waves per row, each wave scanning a contiguous
+// slice, then wave 0 merging the 16 partial lists in slice order (ties to the earlier slice = the earlier candidate).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "../../include/ultra_nbfnet.h"
+#include "../../include/ultra_rspmm.h"
+#include "plan.hpp"
+#include "device_scope.hpp"
+
+namespace ultra {
+
+constexpr int BEAM_ROW_WAVES = 4;     // rows per workgroup of the row kernel
+constexpr int BEAM_HUB_WAVES = 16;    // waves per hub row
+
+// torch.isclose(a, b) with rtol = 1e-5, atol = 1e-8 on fp32 (ATen: close = a == b | isfinite(|a - b|) & |a - b| <= atol + |rtol * b|)
+__device__ __forceinline__ bool beam_isclose(float a, float b) {
+    if (a == b) return true;
+    const float err = fabsf(a - b);
+    const float allowed = 1e-8f + fabsf(1e-5f * b);
+    return isfinite(err) && err <= allowed;
+}
+
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+struct BeamLds {
+    float v[64];
+    int src[64];
+    int ty[64];
+    int pr[64];
+};
+
+// running top-K of one wave: lane i < cnt holds the i-th best entry
+struct BeamState {
+    float v;
+    int src, ty, pr;
+    int cnt;    // wave-uniform
+};
+
+// Merge K new entries (lane b: value m, valid flag; ties among them go to the lower lane) into the state (whose entries all
+// precede the new ones in candidate order, so they win ties).
+__device__ __forceinline__ void beam_merge(BeamState &st, float m, bool valid, int src, int ty, int pr, int K, int lane,
+                                           BeamLds &lds) {
+    const unsigned long long vmask = __ballot(valid);
+    if (vmask == 0ull) return;
+    if (st.cnt == K) {
+        const float last = __shfl(st.v, K - 1);
+        if (!__any(valid && m > last)) return;     // nothing beats the K-th entry (ties stay with the state)
+    }
+    int rank_s = lane, rank_n = 0;
+    for (int j = 0; j < K; ++j) {
+        const float mj = __shfl(m, j);
+        const float sj = __shfl(st.v, j);
+        const bool vj = (vmask >> j) & 1ull;
+        if (vj && mj > st.v) ++rank_s;
+        if (j < st.cnt && sj >= m) ++rank_n;
+        if (vj && j != lane && (mj > m || (mj == m && j < lane))) ++rank_n;
+    }
+    if (lane < st.cnt && rank_s < K) {
+        lds.v[rank_s] = st.v;
+        lds.src[rank_s] = st.src;
+        lds.ty[rank_s] = st.ty;
+        lds.pr[rank_s] = st.pr;
+    }
+    if (valid && rank_n < K) {
+        lds.v[rank_n] = m;
+        lds.src[rank_n] = src;
+        lds.ty[rank_n] = ty;
+        lds.pr[rank_n] = pr;
+    }
+    const int total = st.cnt + __popcll(vmask);
+    st.cnt = total < K ? total : K;
+    wave_lds_sync();
+    if (lane < st.cnt) {
+        st.v = lds.v[lane];
+        st.src = lds.src[lane];
+        st.ty = lds.ty[lane];
+        st.pr = lds.pr[lane];
+    }
+    wave_lds_sync();
+}
+
+// prev_rank of lane b's candidate among the K candidates of one edge
+__device__ __forceinline__ int beam_prev_rank(float m, int K) {
+    int pr = 0;
+    bool found = false;
+    for (int j = 0; j < K; ++j) {
+        const float mj = __shfl(m, j);
+        if (!found && beam_isclose(m, mj)) {
+            pr = j;
+            found = true;
+        }
+    }
+    return pr;
+}
+
+struct BeamArgs {
+    const int64_t *row_ptr;
+    const int32_t *src;
+    const int32_t *type;
+    const int32_t *eid;
+    const float *grad;
+    const float *dist_in;
+    float *dist_out;
+    int64_t *back_out;
+    const int64_t *hub_rows;
+    int64_t num_node;
+    int64_t tail;
+    int32_t K;
+};
+
+// Scan slots [pb, pe) of row v into `st`.  The carry (the candidate directly before slot pb's first one) is computed from
+// the row's slots before pb.
+__device__ void beam_scan(const BeamArgs &a, int64_t v, int64_t row_begin, int64_t pb, int64_t pe, BeamState &st, int lane,
+                          BeamLds &lds) {
+    const int K = a.K;
+    const int t = (int)a.tail;
+    bool has_prev = false;
+    int prev_src = 0, prev_ty = 0, prev_pr = 0;
+    {
+        int64_t q = pb - 1;
+        while (q >= row_begin && a.src[q] == t) --q;
+        if (q >= row_begin) {
+            const int s = a.src[q];
+            const float gv = a.grad[a.eid[q]];
+            const float m = lane < K ? a.dist_in[(int64_t)s * K + lane] + gv : -INFINITY;
+            const int pr = beam_prev_rank(m, K);
+            has_prev = true;
+            prev_src = s;
+            prev_ty = a.type[q];
+            prev_pr = __shfl(pr, K - 1);
+        }
+    }
+    for (int64_t c0 = pb; c0 < pe; c0 += 64) {
+        // the chunk's slots, one per lane (coalesced), handed out with shuffles
+        const int64_t n = pe - c0 < 64 ? pe - c0 : 64;
+        int my_src = t, my_ty = 0;
+        float my_g = 0.f;
+        if (lane < n) {
+            my_src = a.src[c0 + lane];
+            my_ty = a.type[c0 + lane];
+            my_g = a.grad[a.eid[c0 + lane]];
+        }
+        int s_next = __shfl(my_src, 0);
+        float d_next = (lane < K && s_next != t) ? a.dist_in[(int64_t)s_next * K + lane] : -INFINITY;
+        for (int c = 0; c < (int)n; ++c) {
+            const int s = s_next;
+            const float d = d_next;
+            if (c + 1 < (int)n) {       // the next edge's beams in flight while this one is merged
+                s_next = __shfl(my_src, c + 1);
+                d_next = (lane < K && s_next != t) ? a.dist_in[(int64_t)s_next * K + lane] : -INFINITY;
+            }
+            if (s == t) continue;       // no path leaves t once it has arrived there (base_nbfnet.py:178-183)
+            const int ty = __shfl(my_ty, c);
+            const float gv = __shfl(my_g, c);
+            const float m = lane < K ? d + gv : -INFINITY;
+            const int pr = beam_prev_rank(m, K);
+            const int pr_before = __shfl_up(pr, 1);
+            bool dup;
+            if (lane == 0)
+                dup = has_prev && prev_src == s && prev_ty == ty && prev_pr == pr;
+            else
+                dup = pr == pr_before;
+            const bool valid = lane < K && !dup;
+            has_prev = true;
+            prev_src = s;
+            prev_ty = ty;
+            prev_pr = __shfl(pr, K - 1);
+            beam_merge(st, m, valid, s, ty, pr, K, lane, lds);
+        }
+    }
+    (void)v;
+}
+
+__device__ __forceinline__ void beam_write(const BeamArgs &a, int64_t v, const BeamState &st, int lane) {
+    const int K = a.K;
+    const int last = st.cnt > 0 ? st.cnt - 1 : 0;
+    const float pv = __shfl(st.v, last);
+    const int psrc = __shfl(st.src, last), pty = __shfl(st.ty, last), ppr = __shfl(st.pr, last);
+    if (lane >= K) return;
+    float val;
+    int64_t s, d, ty, pr;
+    if (st.cnt == 0) {
+        val = -INFINITY;
+        s = d = ty = pr = 0;
+    } else if (lane < st.cnt) {
+        val = st.v;
+        s = st.src;
+        d = v;
+        ty = st.ty;
+        pr = st.pr;
+    } else {
+        val = pv;
+        s = psrc;
+        d = v;
+        ty = pty;
+        pr = ppr;
+    }
+    const int64_t o = v * K + lane;
+    a.dist_out[o] = val;
+    int64_t *be = a.back_out + o * 4;
+    be[0] = s;
+    be[1] = d;
+    be[2] = ty;
+    be[3] = pr;
+}
+
+__global__ void __launch_bounds__(64 * BEAM_ROW_WAVES) beam_row_kernel(BeamArgs a) {
+    __shared__ BeamLds lds[BEAM_ROW_WAVES];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t v = (int64_t)blockIdx.x * BEAM_ROW_WAVES + wave;
+    if (v >= a.num_node) return;
+    const int64_t rb = a.row_ptr[v], re = a.row_ptr[v + 1];
+    if (re - rb > ULTRA_BEAM_HUB_DEGREE) return;       // beam_hub_kernel's row
+    BeamState st;
+    st.v = -INFINITY;
+    st.src = st.ty = st.pr = 0;
+    st.cnt = 0;
+    beam_scan(a, v, rb, rb, re, st, lane, lds[wave]);
+    beam_write(a, v, st, lane);
+}
+
+__global__ void __launch_bounds__(64 * BEAM_HUB_WAVES) beam_hub_kernel(BeamArgs a) {
+    __shared__ BeamLds scratch[BEAM_HUB_WAVES];
+    __shared__ BeamLds part[BEAM_HUB_WAVES];
+    __shared__ int part_cnt[BEAM_HUB_WAVES];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t v = a.hub_rows[blockIdx.x];
+    const int64_t rb = a.row_ptr[v], re = a.row_ptr[v + 1];
+    const int64_t per = (re - rb + BEAM_HUB_WAVES - 1) / BEAM_HUB_WAVES;
+    const int64_t pb = rb + per * wave < re ? rb + per * wave : re;
+    const int64_t pe = pb + per < re ? pb + per : re;
+    BeamState st;
+    st.v = -INFINITY;
+    st.src = st.ty = st.pr = 0;
+    st.cnt = 0;
+    beam_scan(a, v, rb, pb, pe, st, lane, scratch[wave]);
+    if (lane < 64) {
+        part[wave].v[lane] = st.v;
+        part[wave].src[lane] = st.src;
+        part[wave].ty[lane] = st.ty;
+        part[wave].pr[lane] = st.pr;
+    }
+    if (lane == 0) part_cnt[wave] = st.cnt;
+    __syncthreads();
+    if (wave != 0) return;
+    for (int w = 1; w < BEAM_HUB_WAVES; ++w) {
+        const int n = part_cnt[w];
+        const bool valid = lane < n;
+        beam_merge(st, part[w].v[lane], valid, part[w].src[lane], part[w].ty[lane], part[w].pr[lane], a.K, lane, scratch[0]);
+    }
+    beam_write(a, v, st, lane);
+}
+
+}  // namespace ultra
+
+extern "C" int32_t ultra_beam_search_layer(const int64_t *row_ptr, const int32_t *csr_src, const int32_t *csr_type,
+                                           const int32_t *csr_eid, const int64_t *hub_rows, int64_t num_hub,
+                                           int64_t num_node, int64_t num_edge, const void *edge_grad, const void *dist_in,
+                                           int64_t tail, int32_t num_beam, void *dist_out, int64_t *back_edge_out,
+                                           void *stream) {
+    if (num_beam < 1 || num_beam > ULTRA_BEAM_MAX) {
+        ultra::set_error("ultra_beam_search_layer: num_beam must be in [1, 64]");
+        return ULTRA_ERR_UNSUPPORTED;
+    }
+    if (!row_ptr || !dist_out || !back_edge_out || !dist_in || num_node <= 0 || num_edge < 0 || num_hub < 0
+        || num_node >= INT32_MAX || num_edge >= INT32_MAX || (num_hub > 0 && !hub_rows)
+        || (num_edge > 0 && (!csr_src || !csr_type || !csr_eid || !edge_grad)) || tail < 0 || tail >= num_node) {
+        ultra::set_error("ultra_beam_search_layer: NULL operand, empty graph or tail out of range");
+        return ULTRA_ERR_INVALID;
+    }
+    ULTRA_DEVICE_SCOPE(stream, dist_out);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    ultra::BeamArgs a;
+    a.row_ptr = row_ptr;
+    a.src = csr_src;
+    a.type = csr_type;
+    a.eid = csr_eid;
+    a.grad = (const float *)edge_grad;
+    a.dist_in = (const float *)dist_in;
+    a.dist_out = (float *)dist_out;
+    a.back_out = back_edge_out;
+    a.hub_rows = hub_rows;
+    a.num_node = num_node;
+    a.tail = tail;
+    a.K = num_beam;
+    (void)hipGetLastError();   // drop any stale error left by other users of the runtime
+    const unsigned grid = (unsigned)((num_node + ultra::BEAM_ROW_WAVES - 1) / ultra::BEAM_ROW_WAVES);
+    hipLaunchKernelGGL(ultra::beam_row_kernel, dim3(grid), dim3(64 * ultra::BEAM_ROW_WAVES), 0, s, a);
+    if (num_hub > 0)
+        hipLaunchKernelGGL(ultra::beam_hub_kernel, dim3((unsigned)num_hub), dim3(64 * ultra::BEAM_HUB_WAVES), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        ultra::set_error(std::string("beam search launch: ") + hipGetErrorString(e));
+        return ULTRA_ERR_HIP;
+    }
+    return ULTRA_OK;
+}

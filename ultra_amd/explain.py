@@ -1,0 +1,142 @@
+"""Path explanations of link predictions: BaseNBFNet.visualize's beam search (reference: ultra/base_nbfnet.py:156-263).
+
+visualize takes the gradient of one triple's score with respect to every layer's edge weights, beam-searches the
+highest-weight paths from head to tail through those gradients and returns the top paths with their average edge weight.
+Here every layer of the beam search is one call of ultra_beam_search_layer (csrc/beam_search.hip) over a
+destination-major CSR of the graph that is built once per graph and cached, and the backtracking of topk_average_length
+runs as device gathers with one copy to the host at the end.
+
+Semantics: the reference's with stable sorts and exact top-k keys.  The reference itself is
+order-dependent -- its ties follow whatever its unstable sorts produce, and its scatter_topk merges values closer than
+about 4 (max - min) N 2^-23 -- so it is not a bit-exact target.
+"""
+import ctypes
+from collections import OrderedDict, namedtuple
+
+import torch
+
+from . import _lib
+from ._lib import check, lib
+
+BeamCSR = namedtuple("BeamCSR", "row_ptr src type eid hub_rows num_hub num_node num_edge")
+
+_CSR_CACHE = OrderedDict()
+_CSR_CACHE_SIZE = 8
+
+
+def beam_csr(edge_index, edge_type, num_node):
+    """The destination-major CSR of a graph for the beam search (cached like rspmm.get_plan): a stable sort by destination
+    on the device, so the slots of every row keep ascending edge id; rows above ULTRA_BEAM_HUB_DEGREE listed apart."""
+    key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), tuple(edge_index.stride()),
+           edge_type.data_ptr(), edge_type._version, str(edge_index.device), int(num_node))
+    hit = _CSR_CACHE.get(key)
+    if hit is not None:
+        _CSR_CACHE.move_to_end(key)
+        return hit[0]
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_type.shape != (edge_index.shape[1],):
+        raise ValueError("Expected `edge_index` of shape (2, num_edge) and `edge_type` of shape (num_edge,)")
+    if not edge_index.is_cuda:
+        raise RuntimeError("the beam search runs on the GPU: pass the graph on a CUDA device")
+    num_edge = edge_index.shape[1]
+    if num_node <= 0 or num_node >= 2 ** 31 or num_edge >= 2 ** 31:
+        raise ValueError("the beam search takes 0 < num_node < 2^31 and num_edge < 2^31")
+    if num_edge and (int(edge_index.min()) < 0 or int(edge_index.max()) >= num_node):
+        raise ValueError("edge_index holds node ids outside [0, num_node)")
+    src, dst = edge_index[0], edge_index[1]
+    order = torch.sort(dst, stable=True).indices
+    deg = torch.bincount(dst, minlength=num_node)
+    row_ptr = torch.zeros(num_node + 1, dtype=torch.int64, device=dst.device)
+    torch.cumsum(deg, 0, out=row_ptr[1:])
+    hub_rows = torch.nonzero(deg > _lib.BEAM_HUB_DEGREE).flatten().to(torch.int64).contiguous()
+    csr = BeamCSR(row_ptr, src[order].to(torch.int32).contiguous(), edge_type[order].to(torch.int32).contiguous(),
+                  order.to(torch.int32).contiguous(), hub_rows, int(hub_rows.numel()), int(num_node), int(num_edge))
+    _CSR_CACHE[key] = (csr, edge_index, edge_type)     # (the tensors stay alive with the entry: no recycled data_ptr aliases it)
+    while len(_CSR_CACHE) > _CSR_CACHE_SIZE:
+        _CSR_CACHE.popitem(last=False)
+    return csr
+
+
+def clear_csr_cache():
+    _CSR_CACHE.clear()
+
+
+def beam_search_layer(csr, edge_grad, dist_in, tail, num_beam):
+    """One layer (ultra_beam_search_layer): (num_node, num_beam) fp32 distances and (num_node, num_beam, 4) int64 back
+    edges [src, dst, type, prev_rank], on the current stream of the operands' device."""
+    if not isinstance(num_beam, int) or not 1 <= num_beam <= _lib.BEAM_MAX:
+        raise ValueError("num_beam must be an int in [1, %d], got %r" % (_lib.BEAM_MAX, num_beam))
+    if edge_grad.dtype != torch.float32 or dist_in.dtype != torch.float32:
+        raise TypeError("the beam search takes fp32 edge gradients and distances, got %s / %s" % (edge_grad.dtype, dist_in.dtype))
+    if tuple(edge_grad.shape) != (csr.num_edge,):
+        raise ValueError("Expected edge gradients of shape (%d,), got %s" % (csr.num_edge, tuple(edge_grad.shape)))
+    if tuple(dist_in.shape) != (csr.num_node, num_beam):
+        raise ValueError("Expected distances of shape (%d, %d), got %s" % (csr.num_node, num_beam, tuple(dist_in.shape)))
+    if not (edge_grad.is_cuda and dist_in.is_cuda and edge_grad.device == csr.row_ptr.device == dist_in.device):
+        raise RuntimeError("edge gradients, distances and graph must be on one CUDA device")
+    tail = int(tail)
+    if not 0 <= tail < csr.num_node:
+        raise ValueError("tail %d outside [0, %d)" % (tail, csr.num_node))
+    edge_grad, dist_in = edge_grad.contiguous(), dist_in.contiguous()
+    dist = torch.empty((csr.num_node, num_beam), dtype=torch.float32, device=dist_in.device)
+    back = torch.empty((csr.num_node, num_beam, 4), dtype=torch.int64, device=dist_in.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dist_in.device).cuda_stream)
+    check(lib.ultra_beam_search_layer(csr.row_ptr.data_ptr(), csr.src.data_ptr(), csr.type.data_ptr(), csr.eid.data_ptr(),
+                                      csr.hub_rows.data_ptr() if csr.num_hub else None, csr.num_hub, csr.num_node,
+                                      csr.num_edge, edge_grad.data_ptr(), dist_in.data_ptr(), tail, num_beam,
+                                      dist.data_ptr(), back.data_ptr(), stream))
+    return dist, back
+
+
+def beam_search_distance(data, edge_grads, h_index, t_index, num_beam=10):
+    """base_nbfnet.py:173-232: per layer, the top `num_beam` distances of every node from h and their back edges."""
+    h, t = _scalar_index(h_index, "h_index"), _scalar_index(t_index, "t_index")
+    csr = beam_csr(data.edge_index, data.edge_type, data.num_nodes)
+    dev = data.edge_index.device
+    dist = torch.full((data.num_nodes, num_beam), float("-inf"), device=dev)
+    dist[h, 0] = 0
+    distances, back_edges = [], []
+    with torch.no_grad():
+        for edge_grad in edge_grads:
+            dist, back = beam_search_layer(csr, edge_grad, dist, t, num_beam)
+            # every message of the layer -inf: the whole layer is -inf and zeros (base_nbfnet.py:220).  A finite message
+            # always leaves a finite distance behind, so "no finite distance" is that condition.
+            back.mul_(torch.isfinite(dist).any())
+            distances.append(dist)
+            back_edges.append(back)
+    return distances, back_edges
+
+
+def topk_average_length(distances, back_edges, t_index, k=10):
+    """base_nbfnet.py:234-263: backtrack the best `k` entries of t's row of every layer into paths [(h, t, r), ...] and
+    weigh each with distance / length; the best `k` paths overall.  The backtracking is a chain of device gathers, copied
+    to the host once."""
+    t = _scalar_index(t_index, "t_index")
+    records = []
+    for i in range(len(distances)):
+        distance, order = distances[i][t].flatten().sort(descending=True, stable=True)
+        distance, order = distance[:k], order[:k]
+        steps = [back_edges[i][t].index_select(0, order)]                 # (n, 4) edges into t
+        for j in range(i - 1, -1, -1):
+            prev = steps[-1]
+            steps.append(back_edges[j][prev[:, 0], prev[:, 3]])
+        records.append((distance, torch.stack(steps)))                    # (i + 1, n, 4), last edge first
+    host = [(d.cpu().tolist(), s.cpu()) for d, s in records]
+    paths, average_lengths = [], []
+    for i, (dist, steps) in enumerate(host):
+        for n, d in enumerate(dist):
+            if d == float("-inf"):
+                break
+            path = [tuple(int(x) for x in steps[j, n, :3]) for j in range(i, -1, -1)]
+            paths.append(path)
+            average_lengths.append(d / len(path))
+    if paths:
+        average_lengths, paths = zip(*sorted(zip(average_lengths, paths), reverse=True)[:k])
+    return paths, average_lengths
+
+
+def _scalar_index(index, name):
+    if torch.is_tensor(index):
+        if index.numel() != 1:
+            raise ValueError("%s: one triple at a time (base_nbfnet.py:156), got %d indices" % (name, index.numel()))
+        return int(index.reshape(()))
+    return int(index)

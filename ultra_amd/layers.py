@@ -85,6 +85,20 @@ def _scatter(src, index, dim_size, reduce):
     raise ValueError("Unknown aggregation function `%s`" % reduce)
 
 
+_FLIPPED = {}
+
+
+def _flipped_edges(edge_index):
+    """edge_index with its two rows swapped, one tensor per graph (so the plan cache, keyed on the tensor, hits)."""
+    key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), str(edge_index.device))
+    hit = _FLIPPED.get(key)
+    if hit is None:
+        if len(_FLIPPED) >= 8:
+            _FLIPPED.clear()
+        hit = _FLIPPED[key] = (edge_index.flip(0).contiguous(), edge_index)
+    return hit[0]
+
+
 class GeneralizedRelationalConv(nn.Module):
 
     eps = 1e-6
@@ -221,6 +235,24 @@ class GeneralizedRelationalConv(nn.Module):
                                          kwargs["edge_type"], edge_weight, edge_index[1], num_node,
                                          onehot_rows=onehot_rows, edge_keep=edge_keep)
         return self.update(out, kwargs["input"], residual=residual)
+
+    def edge_grad_layer(self, input, query, boundary, edge_index, edge_type, num_node, edge_weight, residual=False,
+                        relation=None):
+        """The layer on the unfused path's direction (messages from edge_index[0] into edge_index[1], layers.py:135-181) with
+        differentiable edge weights, through the plan-based rspmm over the flipped graph: d output / d edge_weight comes from
+        ultra_rspmm_backward's weight gradient.  What BaseNBFNet.visualize asks for; sum / DistMult, fp32 on the GPU only
+        (None otherwise: the caller keeps the unfused route)."""
+        if not (self.aggregate_func == "sum" and self.message_func == "distmult" and input.is_cuda
+                and input.dtype == torch.float32 and input.dim() == 3 and input.shape[0] == 1):
+            return None
+        if relation is None:
+            relation = self._relation_for(query, len(query))
+        if isinstance(boundary, PointBoundary):
+            boundary = boundary.dense()
+        plan = rspmm.get_plan(_flipped_edges(edge_index), edge_type, num_node, relation.shape[1], exact_order=False)
+        # (one sample: the 2-D (N, d) operands of the reference kernel's layout)
+        update = rspmm.plan_rspmm(plan, relation[0], input[0], edge_weight, sum="add", mul="mul", boundary=boundary[0])
+        return self.update(update.unsqueeze(0), input, residual=residual)
 
     def point_boundary_trains(self):
         """The differentiable rspmm takes the boundary condition in closed form for the sum aggregate (rspmm._PlanRSPMM,

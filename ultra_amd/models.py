@@ -4,15 +4,16 @@ Drop-in for the reference's ultra/models.py + ultra/base_nbfnet.py (hot-path par
 names, constructor arguments, forward signatures and state-dict keys, so
 `model.load_state_dict(torch.load(ckpt)["model"])` works unchanged (script/run.py:257-258).
 `data` is duck-typed: .edge_index, .edge_type, .num_nodes, .num_relations, .relation_graph.
-Interpretability tooling of BaseNBFNet (visualize / beam search, base_nbfnet.py:156-336) is out of scope.
+EntityNBFNet.visualize / beam_search_distance / topk_average_length (base_nbfnet.py:156-263) explain one prediction with
+its top paths: ultra_amd.explain (HIP beam search); Ultra.visualize is the same from the full model.
 """
 import copy
 from collections.abc import Sequence
 
 import torch
-from torch import nn
+from torch import autograd, nn
 
-from . import dense, layers, rspmm, tasks
+from . import dense, explain, layers, rspmm, tasks
 
 
 # inference fast path of EntityNBFNet.forward: fused batch prologue + readout from the raw batch (A/B switch for tests)
@@ -115,12 +116,23 @@ class BaseNBFNet(nn.Module):
         new_r_index = torch.where(is_t_neg, r_index, r_index + num_direct_rel)
         return new_h_index, new_t_index, new_r_index
 
+    # ---- explanations (base_nbfnet.py:173-263): the beam search over every layer's edge gradients, ultra_amd.explain ----
+    @torch.no_grad()
+    def beam_search_distance(self, data, edge_grads, h_index, t_index, num_beam=10):
+        return explain.beam_search_distance(data, edge_grads, h_index, t_index, num_beam)
+
+    def topk_average_length(self, distances, back_edges, t_index, k=10):
+        return explain.topk_average_length(distances, back_edges, t_index, k)
+
     def _propagate_layers(self, data, layer_input, query, boundary, separate_grad=False, relations=None,
-                          edge_weight=None, onehot_rows=None, edge_keep=False, prefilled=None, last_rows=None):
+                          edge_weight=None, onehot_rows=None, edge_keep=False, prefilled=None, last_rows=None,
+                          edge_grad_route=False):
         """The Bellman-Ford loop shared by every model (models.py:72-80, 150-163, 233-246).
         `relations`: optional per-layer relation features computed up front (EntityNBFNet batches the six
         relation_projection MLPs, which all read the same relation representations).
-        `boundary` may be a layers.PointBoundary (then `layer_input` is ignored: layer 0 reads the boundary condition)."""
+        `boundary` may be a layers.PointBoundary (then `layer_input` is ignored: layer 0 reads the boundary condition).
+        `edge_grad_route` (with separate_grad; visualize only): the layers that can take their edge-weight gradient from the
+        plan-based differentiable rspmm do (layers.edge_grad_layer), the others keep the unfused route."""
         size = (data.num_nodes, data.num_nodes)
         self._last_hidden_on_rows = False
         # edge_weight None = all ones (only materialised when its gradient is asked for); a 0/1 vector = edge dropout
@@ -151,10 +163,24 @@ class BaseNBFNet(nn.Module):
         for i, layer in enumerate(self.layers):
             if i < first:
                 continue
-            if separate_grad:
+            if separate_grad and edge_grad_route:
+                # models.py:150-152: every layer's weights are a clone of the previous layer's, so d score / d weight of layer
+                # i sums the direct gradients of layers i .. L-1 -- the reference's edge gradients for visualize
+                first_weight = edge_weights[-1] if edge_weights else torch.ones(data.num_edges, device=layer_input.device)
+                edge_weight = first_weight.clone().requires_grad_()
+            elif separate_grad:
                 edge_weight = torch.ones(data.num_edges, device=layer_input.device).requires_grad_()
             # residual connection (models.py:158-160) is fused into the layer's update kernel
             residual = self.short_cut and layer.output_dim == layer_input.shape[-1]
+            if separate_grad and edge_grad_route:
+                hidden = layer.edge_grad_layer(layer_input, query, boundary, data.edge_index, data.edge_type, data.num_nodes,
+                                               edge_weight, residual=residual,
+                                               relation=None if relations is None else relations[i])
+                if hidden is not None:
+                    hiddens.append(hidden)
+                    edge_weights.append(edge_weight)
+                    layer_input = hidden
+                    continue
             if last_rows is not None and i == len(self.layers) - 1 and i > 0 and not separate_grad:
                 # the caller reads the last hidden state at `last_rows` only: that layer on those rows' in-edges alone.
                 # hiddens[-1] is then (batch, n_list, d), flagged by self._last_hidden_on_rows
@@ -283,7 +309,7 @@ class EntityNBFNet(BaseNBFNet):
         return out, side
 
     def _bellmanford_hidden(self, data, h_index, r_index, separate_grad=False, edge_weight=None, edge_keep=False, prefilled=None,
-                            last_rows=None):
+                            last_rows=None, edge_grad_route=False):
         batch_size = len(r_index)
         # query = representation of each sample's query relation, scattered to its head node
         fused = (dense.boundary_supported(h_index, self.query) and self.query.dim() == 3
@@ -310,7 +336,7 @@ class EntityNBFNet(BaseNBFNet):
         hiddens, edge_weights = self._propagate_layers(data, boundary, query, boundary, separate_grad,
                                                        relations=self._project_relations_batched(),
                                                        edge_weight=edge_weight, onehot_rows=h_index, edge_keep=edge_keep,
-                                                       prefilled=prefilled, last_rows=last_rows)
+                                                       prefilled=prefilled, last_rows=last_rows, edge_grad_route=edge_grad_route)
         return hiddens, edge_weights, query
 
     def _project_relations_batched(self):
@@ -374,6 +400,32 @@ class EntityNBFNet(BaseNBFNet):
             "node_feature": output,
             "edge_weights": edge_weights,
         }
+
+    def edge_grads(self, data, batch):
+        """d score(h, t, r) / d edge_weight for every layer (base_nbfnet.py:156-167): the relation representations must be
+        installed (self.query, as forward() does).  sum / DistMult layers take their gradient from the plan-based rspmm,
+        the others from the unfused route.  Returns (edge_grads, score)."""
+        assert batch.shape == (1, 3)
+        h_index, t_index, r_index = batch.unbind(-1)
+        last_hidden_on_rows = getattr(self, "_last_hidden_on_rows", False)
+        with torch.enable_grad():
+            hiddens, edge_weights, query = self._bellmanford_hidden(data, h_index, r_index, separate_grad=True,
+                                                                    edge_grad_route=True)
+            picked = [h[:, t_index] for h in (hiddens if self.concat_hidden else hiddens[-1:])]     # (1, 1, d) each
+            feature = torch.cat(picked + [query.unsqueeze(1)], dim=-1).squeeze(0)
+            score = self.mlp(feature).squeeze(-1)
+            edge_grads = autograd.grad(score, edge_weights)
+        self._last_hidden_on_rows = last_hidden_on_rows
+        return list(edge_grads), score.detach()
+
+    def visualize(self, data, batch):
+        """base_nbfnet.py:156-171: the top `path_topk` paths from h to t of one triple (1, 3) -- lists of (h, t, r) -- and
+        their average edge weights, from a beam of `num_beam` over every layer's edge gradients."""
+        assert batch.shape == (1, 3)
+        h_index, t_index, r_index = batch.unbind(-1)
+        edge_grads, _ = self.edge_grads(data, batch)
+        distances, back_edges = self.beam_search_distance(data, edge_grads, h_index, t_index, self.num_beam)
+        return self.topk_average_length(distances, back_edges, t_index, self.path_topk)
 
     def prologue_supported(self, batch):
         """The inference fast path of forward(): one prologue kernel instead of the index arithmetic of models.py:190-197."""
@@ -559,6 +611,28 @@ class Ultra(nn.Module):
             self.drop_relation_cache()       # another graph, or the weights moved: the table is stale
             return None
         return table.index_select(0, query_rels)
+
+    def visualize(self, data, batch):
+        """EntityNBFNet.visualize of one triple (1, 3) from the full model: the query relation's representations from the
+        relation model (models.py:20-21), installed in the entity model the way its forward() does, then its paths and
+        weights.  The model is left as it was: parameters, training flag, the entity model's installed representations and
+        the relation cache."""
+        assert batch.shape == (1, 3)
+        ent = self.entity_model
+        saved = (getattr(ent, "query", None), [getattr(l, "relation", None) for l in ent.layers])
+        try:
+            with torch.no_grad():
+                rel = self._cached_relations(data, batch[:, 2])
+                if rel is None:
+                    rel = self.relation_model(data.relation_graph, query=batch[:, 2])
+            ent.query = rel
+            for layer in ent.layers:
+                layer.relation = rel
+            return ent.visualize(data, batch)
+        finally:
+            ent.query = saved[0]
+            for layer, r in zip(ent.layers, saved[1]):
+                layer.relation = r
 
     def forward(self, data, batch):
         # batch: (bs, 1 + num_negs, 3); the relation is shared by every triple of a row
