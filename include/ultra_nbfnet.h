@@ -268,6 +268,28 @@ int32_t ultra_beam_search_layer(const int64_t *row_ptr, const int32_t *csr_src, 
                                 const void *edge_grad, const void *dist_in, int64_t tail, int32_t num_beam, void *dist_out,
                                 int64_t *back_edge_out, void *stream);
 
+/* ---- complex logical queries (UltraQuery) ----
+ * ultra_symbolic_traversal: SymbolicTraversal.forward (ultraquery.py:280-298),
+ *   t[b, v] = max(0, max{ h[b, u] : edge u -> v of type r_index[b] })   (0 where no such edge)
+ * over a CSR keyed by (tail, relation): row_ptr (num_node + 1) int64; csr_src / csr_type (num_edge) int32, the in-edges of
+ * every row sorted by relation.  r_index (batch) int64; h, t (batch, num_node) contiguous, fp32 (dtype 0) or fp64 (1).
+ * Exact: the same bits as any other order of the max.
+ *
+ * ultra_answer_ranking: batch_evaluate (query_utils.py:284-325) under the stable descending order (u ahead of v iff
+ * p_u > p_v, or p_u == p_v and u < v; NaN above every number).  pred (batch, num_node) fp32 contiguous; keep
+ * (num_node) uint8 or NULL (a node with keep 0 scores -inf); answers: per query its easy answers by ascending id, then its hard ones (disjoint), at
+ * [ans_ptr[b], ans_ptr[b + 1]); hard_ptr (batch) int64: where query b's hard ranks start in `ranking`; num_easy (batch)
+ * int64.  A query with more than ULTRA_RANKING_LDS_ANSWERS answers (rounded up to a power of two P) works in
+ * ws + ws_off[b] (4-byte words; 4 P words per such query).  Outputs: answer_ranking (sum of answers) int64, the 0-based
+ * unfiltered position of every answer in list order; ranking (sum of hard answers) int64, 1 + #{non-answers ahead}.
+ */
+#define ULTRA_RANKING_LDS_ANSWERS 2048
+int32_t ultra_symbolic_traversal(const int64_t *row_ptr, const int32_t *csr_src, const int32_t *csr_type, int64_t num_node,
+                                 const int64_t *r_index, int64_t batch, int32_t dtype, const void *h, void *t, void *stream);
+int32_t ultra_answer_ranking(const void *pred, const uint8_t *keep, const int64_t *answers, const int64_t *ans_ptr,
+                             const int64_t *hard_ptr, const int64_t *num_easy, const int64_t *ws_off, void *ws, int64_t batch,
+                             int64_t num_node, int64_t *answer_ranking, int64_t *ranking, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

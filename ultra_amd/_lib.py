@@ -33,6 +33,7 @@ LAYER_REFERENCE_ORDER = 8
 DENSE_MAX_IN_ROW = 1024
 BEAM_MAX = 64                # ULTRA_BEAM_MAX
 BEAM_HUB_DEGREE = 256        # ULTRA_BEAM_HUB_DEGREE
+RANKING_LDS_ANSWERS = 2048   # ULTRA_RANKING_LDS_ANSWERS
 ARR_DENSE = 7
 ARR_DENSE_ORDER = 8
 
@@ -115,6 +116,8 @@ def _load():
     lib.ultra_stream_copy.argtypes = [vp, vp, i64, vp]
     lib.ultra_filtered_rank.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp, vp]
     lib.ultra_beam_search_layer.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, i64, i32, vp, vp, vp]
+    lib.ultra_symbolic_traversal.argtypes = [vp, vp, vp, i64, vp, i64, i32, vp, vp, vp]
+    lib.ultra_answer_ranking.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp]
     lib.ultra_strict_negatives.argtypes = [vp, i64, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp]
     lib.ultra_ranking_loss.argtypes = [vp, i64, i64, ctypes.c_float, ctypes.c_float, vp, vp, vp]
     lib.ultra_readout_train_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp]
