@@ -246,6 +246,18 @@ int32_t ultra_relation_graph_bits(const int64_t *edge_index_dev, const int64_t *
 int32_t ultra_relation_graph_emit(const void *adj_dev, const int64_t *row_offsets_dev, int64_t num_relation, int64_t total_edges,
                                   int64_t *edge_index_out_dev, int64_t *edge_type_out_dev, void *stream);
 int32_t ultra_relation_graph_dense_adjacency(const void *adj_dev, int64_t num_relation, void *a_ex_out_dev, void *stream);
+/*
+ * ultra_relation_graph_bits_keep:  ultra_relation_graph_bits of the graph without the edges whose keep (num_edge fp32) is 0
+ *   (the relation graph of a projection's graph after traversal dropout, ultraquery.py:217-219).
+ * ultra_relation_graph_edge_keep:  for the edges (rel_edge_index (2, num_rel_edge), rel_edge_type) of a relation graph,
+ *   keep_out[i] = 1 where adj (bits of any graph, e.g. the dropped one) holds the edge, else 0 -- the dropped relation graph as a
+ *   0/1 vector over the static one's edges.
+ */
+int32_t ultra_relation_graph_bits_keep(const int64_t *edge_index_dev, const int64_t *edge_type_dev, const float *keep_dev,
+                                       int64_t num_edge, int64_t num_node, int64_t num_relation, void *hbits_dev, void *tbits_dev,
+                                       void *adj_dev, int64_t *row_counts_dev, void *stream);
+int32_t ultra_relation_graph_edge_keep(const void *adj_dev, int64_t num_relation, const int64_t *rel_edge_index_dev,
+                                       const int64_t *rel_edge_type_dev, int64_t num_rel_edge, float *keep_out_dev, void *stream);
 
 /*
  * One layer of the path beam search behind BaseNBFNet.visualize (/root/reference/ultra/base_nbfnet.py:173-232), with the
@@ -286,9 +298,40 @@ int32_t ultra_beam_search_layer(const int64_t *row_ptr, const int32_t *csr_src, 
 #define ULTRA_RANKING_LDS_ANSWERS 2048
 int32_t ultra_symbolic_traversal(const int64_t *row_ptr, const int32_t *csr_src, const int32_t *csr_type, int64_t num_node,
                                  const int64_t *r_index, int64_t batch, int32_t dtype, const void *h, void *t, void *stream);
+int32_t ultra_symbolic_traversal_keep(const int64_t *row_ptr, const int32_t *csr_src, const int32_t *csr_type,
+                                      const float *keep_slot, int64_t num_node, const int64_t *r_index, int64_t batch, int32_t dtype,
+                                      const void *h, void *t, void *stream);
 int32_t ultra_answer_ranking(const void *pred, const uint8_t *keep, const int64_t *answers, const int64_t *ans_ptr,
                              const int64_t *hard_ptr, const int64_t *num_easy, const int64_t *ws_off, void *ws, int64_t batch,
                              int64_t num_node, int64_t *answer_ranking, int64_t *ranking, void *stream);
+
+/* ---- training UltraQuery ----
+ * ultra_symbolic_traversal_keep: ultra_symbolic_traversal on the graph without its dropped edges; keep_slot (num_edge) fp32 in
+ *   the CSR's slot order, 0 = absent.
+ *
+ * ultra_traversal_dropout: UltraQuery.traversal_dropout (ultraquery.py:34-83) as a keep vector over the static edge list.
+ *   edge_index (2, num_edge) / edge_type (num_edge) int64; deg_out / deg_in (num_node) int32 degrees of the full graph;
+ *   r_index (batch) int64 relations, sym (batch, num_node) fp32 (dtype 0) or fp64 (1) symbolic sets;
+ *   inv(r) = r ^ 1 (inverse_rel_plus_one) or r -+ num_relation / 2;
+ *     k(e) = #{b : r_b == type(e), sym[b, src(e)] != 0} + #{b : inv(r_b) == type(e), sym[b, dst(e)] != 0}
+ *     keep[e] = 0 iff not (deg_out[src] <= 1 or deg_in[dst] <= 1) and ((k > 0 and u1[e] <= q[k]) or (more > 0 and u2[e] <= more))
+ *   q (2 batch + 1) fp32, q[k] = 1 - (1 - ratio)^k; u1, u2 (num_edge) fp32 uniforms (u2 may be NULL when more_dropout <= 0);
+ *   masks: scratch of 2 * num_relation * ultra_traversal_dropout_mask_words(batch) 32-bit words; keep (num_edge) fp32 out;
+ *   k_out (num_edge) int32 out or NULL.  No atomics: the same bits on every run.
+ *
+ * ultra_query_loss: the query loss of run_query.py:94-114 and d loss / d pred in one launch.  pred, grad (rows, n) fp32,
+ *   target (rows, n) uint8 (easy answers).  Positives weigh 1 / num_pos; negatives softmax(pred / temperature) over the
+ *   row's negatives (a constant) or 1 / num_neg (temperature 0); loss = mean_b(sum l w / sum w), l = BCE with logits.
+ *   work: rows + 1 32-bit words, the last one ZERO on entry (left zero).  Fixed summation order: reproducible.
+ */
+int64_t ultra_traversal_dropout_mask_words(int64_t batch);
+int32_t ultra_traversal_dropout(const int64_t *edge_index, const int64_t *edge_type, int64_t num_edge, int64_t num_node,
+                                int64_t num_relation, int32_t inverse_rel_plus_one, const int32_t *deg_out, const int32_t *deg_in,
+                                const int64_t *r_index, int64_t batch, int32_t dtype, const void *sym, const float *q,
+                                const float *u1, const float *u2, float more_dropout, void *masks, float *keep, int32_t *k_out,
+                                void *stream);
+int32_t ultra_query_loss(const void *pred, const uint8_t *target, int64_t rows, int64_t n, float temperature, void *work,
+                         void *loss, void *grad, void *stream);
 
 #ifdef __cplusplus
 }

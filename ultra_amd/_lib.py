@@ -141,6 +141,14 @@ def _load():
     lib.ultra_relation_graph_bits.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]
     lib.ultra_relation_graph_emit.argtypes = [vp, vp, i64, i64, vp, vp, vp]
     lib.ultra_relation_graph_dense_adjacency.argtypes = [vp, i64, vp, vp]
+    lib.ultra_relation_graph_bits_keep.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]
+    lib.ultra_relation_graph_edge_keep.argtypes = [vp, i64, vp, vp, i64, vp, vp]
+    lib.ultra_symbolic_traversal_keep.argtypes = [vp, vp, vp, vp, i64, vp, i64, i32, vp, vp, vp]
+    lib.ultra_traversal_dropout_mask_words.argtypes = [i64]
+    lib.ultra_traversal_dropout_mask_words.restype = i64
+    lib.ultra_traversal_dropout.argtypes = [vp, vp, i64, i64, i64, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, ctypes.c_float,
+                                            vp, vp, vp, vp]
+    lib.ultra_query_loss.argtypes = [vp, vp, i64, i64, ctypes.c_float, vp, vp, vp, vp]
     lib.ultra_set_tuning.argtypes = [ctypes.POINTER(Tuning)]
     lib.ultra_get_tuning.argtypes = [ctypes.POINTER(Tuning)]
     for s in ("add", "min", "max"):

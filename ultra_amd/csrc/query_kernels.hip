@@ -33,10 +33,12 @@ constexpr int TRAVERSAL_LANE_MAX = 16;       // longest segment one lane scans a
 constexpr int RANKING_THREADS = 256;
 constexpr int RANKING_LDS_ANSWERS = ULTRA_RANKING_LDS_ANSWERS;
 
-template <typename T>
+// KEEP (training, traversal dropout): slots with keep_slot[s] == 0 are absent edges
+template <typename T, bool KEEP = false>
 __global__ void __launch_bounds__(TRAVERSAL_THREADS) symbolic_traversal_kernel(
     const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ csr_src, const int32_t *__restrict__ csr_type,
-    const int64_t *__restrict__ r_index, const T *__restrict__ h, long long num_node, T *__restrict__ t) {
+    const int64_t *__restrict__ r_index, const T *__restrict__ h, long long num_node, T *__restrict__ t,
+    const float *__restrict__ keep_slot) {
     const long long b = blockIdx.y;
     const long long v = (long long)blockIdx.x * TRAVERSAL_THREADS + threadIdx.x;
     const int32_t r = (int32_t)r_index[b];
@@ -62,6 +64,7 @@ __global__ void __launch_bounds__(TRAVERSAL_THREADS) symbolic_traversal_kernel(
     const bool alone = hi - lo <= TRAVERSAL_LANE_MAX;
     if (alone)
         for (long long s = lo; s < hi; ++s) {
+            if (KEEP && keep_slot[s] == 0.f) continue;
             const T x = hb[csr_src[s]];
             best = x > best ? x : best;
         }
@@ -74,6 +77,7 @@ __global__ void __launch_bounds__(TRAVERSAL_THREADS) symbolic_traversal_kernel(
         const long long slo = __shfl(lo, owner), shi = __shfl(hi, owner);
         T m = T(0);
         for (long long s = slo + lane; s < shi; s += 64) {
+            if (KEEP && keep_slot[s] == 0.f) continue;
             const T x = hb[csr_src[s]];
             m = x > m ? x : m;
         }
@@ -226,10 +230,40 @@ extern "C" int32_t ultra_symbolic_traversal(const int64_t *row_ptr, const int32_
     (void)hipGetLastError();
     if (dtype == 0)
         hipLaunchKernelGGL(ultra::symbolic_traversal_kernel<float>, grid, dim3(ultra::TRAVERSAL_THREADS), 0, s, row_ptr,
-                           csr_src, csr_type, r_index, (const float *)h, (long long)num_node, (float *)t);
+                           csr_src, csr_type, r_index, (const float *)h, (long long)num_node, (float *)t, nullptr);
     else
         hipLaunchKernelGGL(ultra::symbolic_traversal_kernel<double>, grid, dim3(ultra::TRAVERSAL_THREADS), 0, s, row_ptr,
-                           csr_src, csr_type, r_index, (const double *)h, (long long)num_node, (double *)t);
+                           csr_src, csr_type, r_index, (const double *)h, (long long)num_node, (double *)t, nullptr);
+    if (hipGetLastError() != hipSuccess) {
+        ultra::set_error("symbolic_traversal_kernel launch failed");
+        return ULTRA_ERR_HIP;
+    }
+    return ULTRA_OK;
+}
+
+// the same on the graph without its dropped edges: keep_slot (num_edge) fp32 in CSR slot order, 0 = absent (training)
+extern "C" int32_t ultra_symbolic_traversal_keep(const int64_t *row_ptr, const int32_t *csr_src, const int32_t *csr_type,
+                                                 const float *keep_slot, int64_t num_node, const int64_t *r_index, int64_t batch,
+                                                 int32_t dtype, const void *h, void *t, void *stream) {
+    ULTRA_DEVICE_SCOPE(stream, h);
+    if (!row_ptr || !keep_slot || !r_index || !h || !t || num_node <= 0 || batch < 0 || batch > 65535 || num_node >= (1LL << 31)) {
+        ultra::set_error("ultra_symbolic_traversal_keep: NULL operand or batch / num_node out of range");
+        return ULTRA_ERR_INVALID;
+    }
+    if (dtype != 0 && dtype != 1) {
+        ultra::set_error("ultra_symbolic_traversal_keep: dtype must be fp32 (0) or fp64 (1)");
+        return ULTRA_ERR_UNSUPPORTED;
+    }
+    if (batch == 0) return ULTRA_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((num_node + ultra::TRAVERSAL_THREADS - 1) / ultra::TRAVERSAL_THREADS), (unsigned)batch);
+    (void)hipGetLastError();
+    if (dtype == 0)
+        hipLaunchKernelGGL((ultra::symbolic_traversal_kernel<float, true>), grid, dim3(ultra::TRAVERSAL_THREADS), 0, s, row_ptr,
+                           csr_src, csr_type, r_index, (const float *)h, (long long)num_node, (float *)t, keep_slot);
+    else
+        hipLaunchKernelGGL((ultra::symbolic_traversal_kernel<double, true>), grid, dim3(ultra::TRAVERSAL_THREADS), 0, s, row_ptr,
+                           csr_src, csr_type, r_index, (const double *)h, (long long)num_node, (double *)t, keep_slot);
     if (hipGetLastError() != hipSuccess) {
         ultra::set_error("symbolic_traversal_kernel launch failed");
         return ULTRA_ERR_HIP;

@@ -24,10 +24,13 @@
 
 namespace ultra {
 
+// KEEP: only the edges with keep[e] != 0 count (the relation graph of a graph whose other edges are dropped)
+template <bool KEEP>
 __global__ void __launch_bounds__(256) incidence_bits_kernel(const int64_t *__restrict__ edge_index, const int64_t *__restrict__ edge_type,
                                                              long long num_edge, int words, uint32_t *__restrict__ hbits,
-                                                             uint32_t *__restrict__ tbits) {
+                                                             uint32_t *__restrict__ tbits, const float *__restrict__ keep) {
     for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < num_edge; e += (long long)gridDim.x * blockDim.x) {
+        if (KEEP && keep[e] == 0.f) continue;
         const long long h = edge_index[e], t = edge_index[num_edge + e], r = edge_type[e];
         const uint32_t bit = 1u << (r & 31);
         uint32_t *hw = hbits + h * words + (r >> 5), *tw = tbits + t * words + (r >> 5);
@@ -132,19 +135,32 @@ __global__ void __launch_bounds__(256) dense_order_adjacency_kernel(const uint32
     a_ex[idx] = make_uint4(out[0], out[1], out[2], out[3]);
 }
 
+// keep[i] = bit r2 of row r1 of matrix type[i], for the edges (r1, r2, type) of a relation graph: which of them a relation graph
+// built from a subset of the entity edges still holds (it can only lose edges)
+__global__ void __launch_bounds__(256) relation_edge_keep_kernel(const uint32_t *__restrict__ adj, int num_rel, int words,
+                                                                 const int64_t *__restrict__ rel_edge_index,
+                                                                 const int64_t *__restrict__ rel_edge_type, long long num_rel_edge,
+                                                                 float *__restrict__ keep) {
+    const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (i >= num_rel_edge) return;
+    const long long r1 = rel_edge_index[i], r2 = rel_edge_index[num_rel_edge + i], type = rel_edge_type[i];
+    bool on = false;
+    if (r1 >= 0 && r1 < num_rel && r2 >= 0 && r2 < num_rel && type >= 0 && type < 4)
+        on = (adj[((size_t)type * num_rel + r1) * words + (r2 >> 5)] >> (r2 & 31)) & 1u;
+    keep[i] = on ? 1.f : 0.f;
+}
+
 }  // namespace ultra
 
 using namespace ultra;
 
-extern "C" {
-
-int32_t ultra_relation_graph_bits(const int64_t *edge_index_dev, const int64_t *edge_type_dev, int64_t num_edge, int64_t num_node,
-                                  int64_t num_relation, void *hbits_dev, void *tbits_dev, void *adj_dev, int64_t *row_counts_dev,
-                                  void *stream) {
+static int32_t relation_graph_bits(const int64_t *edge_index_dev, const int64_t *edge_type_dev, const float *keep_dev, int64_t num_edge,
+                                   int64_t num_node, int64_t num_relation, void *hbits_dev, void *tbits_dev, void *adj_dev,
+                                   int64_t *row_counts_dev, void *stream) {
     ULTRA_DEVICE_SCOPE(stream, edge_index_dev);
     if (num_edge < 0 || num_node < 0 || num_relation <= 0 || (num_edge > 0 && (!edge_index_dev || !edge_type_dev)) || !hbits_dev ||
         !tbits_dev || !adj_dev || !row_counts_dev) {
-        set_error("ultra_relation_graph_bits: bad argument");
+        set_error(keep_dev ? "ultra_relation_graph_bits_keep: bad argument" : "ultra_relation_graph_bits: bad argument");
         return ULTRA_ERR_INVALID;
     }
     if (num_relation > (1 << 20)) {
@@ -154,9 +170,13 @@ int32_t ultra_relation_graph_bits(const int64_t *edge_index_dev, const int64_t *
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int words = (int)((num_relation + 31) / 32);
     (void)hipGetLastError();
-    if (num_edge > 0)
-        hipLaunchKernelGGL(incidence_bits_kernel, dim3((unsigned)std::min<int64_t>((num_edge + 255) / 256, 4096)), dim3(256), 0, s,
-                           edge_index_dev, edge_type_dev, (long long)num_edge, words, (uint32_t *)hbits_dev, (uint32_t *)tbits_dev);
+    const dim3 grid((unsigned)std::min<int64_t>((num_edge + 255) / 256, 4096));
+    if (num_edge > 0 && keep_dev)
+        hipLaunchKernelGGL(incidence_bits_kernel<true>, grid, dim3(256), 0, s, edge_index_dev, edge_type_dev, (long long)num_edge, words,
+                           (uint32_t *)hbits_dev, (uint32_t *)tbits_dev, keep_dev);
+    else if (num_edge > 0)
+        hipLaunchKernelGGL(incidence_bits_kernel<false>, grid, dim3(256), 0, s, edge_index_dev, edge_type_dev, (long long)num_edge, words,
+                           (uint32_t *)hbits_dev, (uint32_t *)tbits_dev, nullptr);
     if (num_node > 0)
         hipLaunchKernelGGL(pair_mark_kernel, dim3((unsigned)std::min<int64_t>((num_node + 3) / 4, 8192)), dim3(256), 0, s,
                            (const uint32_t *)hbits_dev, (const uint32_t *)tbits_dev, (long long)num_node, (int)num_relation, words,
@@ -169,6 +189,26 @@ int32_t ultra_relation_graph_bits(const int64_t *edge_index_dev, const int64_t *
         return ULTRA_ERR_HIP;
     }
     return ULTRA_OK;
+}
+
+extern "C" {
+
+int32_t ultra_relation_graph_bits(const int64_t *edge_index_dev, const int64_t *edge_type_dev, int64_t num_edge, int64_t num_node,
+                                  int64_t num_relation, void *hbits_dev, void *tbits_dev, void *adj_dev, int64_t *row_counts_dev,
+                                  void *stream) {
+    return relation_graph_bits(edge_index_dev, edge_type_dev, nullptr, num_edge, num_node, num_relation, hbits_dev, tbits_dev, adj_dev,
+                               row_counts_dev, stream);
+}
+
+int32_t ultra_relation_graph_bits_keep(const int64_t *edge_index_dev, const int64_t *edge_type_dev, const float *keep_dev,
+                                       int64_t num_edge, int64_t num_node, int64_t num_relation, void *hbits_dev, void *tbits_dev,
+                                       void *adj_dev, int64_t *row_counts_dev, void *stream) {
+    if (num_edge > 0 && !keep_dev) {
+        set_error("ultra_relation_graph_bits_keep: NULL keep vector");
+        return ULTRA_ERR_INVALID;
+    }
+    return relation_graph_bits(edge_index_dev, edge_type_dev, keep_dev, num_edge, num_node, num_relation, hbits_dev, tbits_dev, adj_dev,
+                               row_counts_dev, stream);
 }
 
 int32_t ultra_relation_graph_emit(const void *adj_dev, const int64_t *row_offsets_dev, int64_t num_relation, int64_t total_edges,
@@ -206,6 +246,27 @@ int32_t ultra_relation_graph_dense_adjacency(const void *adj_dev, int64_t num_re
                        reinterpret_cast<hipStream_t>(stream), (const uint32_t *)adj_dev, (int)num_relation, words, (uint4 *)a_ex_out_dev);
     if (hipGetLastError() != hipSuccess) {
         set_error("dense_order_adjacency_kernel: launch failed");
+        return ULTRA_ERR_HIP;
+    }
+    return ULTRA_OK;
+}
+
+int32_t ultra_relation_graph_edge_keep(const void *adj_dev, int64_t num_relation, const int64_t *rel_edge_index_dev,
+                                       const int64_t *rel_edge_type_dev, int64_t num_rel_edge, float *keep_out_dev, void *stream) {
+    ULTRA_DEVICE_SCOPE(stream, adj_dev);
+    if (!adj_dev || num_relation <= 0 || num_relation > (1 << 20) || num_rel_edge < 0 ||
+        (num_rel_edge > 0 && (!rel_edge_index_dev || !rel_edge_type_dev || !keep_out_dev))) {
+        set_error("ultra_relation_graph_edge_keep: bad argument");
+        return ULTRA_ERR_INVALID;
+    }
+    if (num_rel_edge == 0) return ULTRA_OK;
+    const int words = (int)((num_relation + 31) / 32);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(relation_edge_keep_kernel, dim3((unsigned)((num_rel_edge + 255) / 256)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), (const uint32_t *)adj_dev, (int)num_relation, words, rel_edge_index_dev,
+                       rel_edge_type_dev, (long long)num_rel_edge, keep_out_dev);
+    if (hipGetLastError() != hipSuccess) {
+        set_error("relation_edge_keep_kernel: launch failed");
         return ULTRA_ERR_HIP;
     }
     return ULTRA_OK;

@@ -226,7 +226,7 @@ class RelNBFNet(BaseNBFNet):
                 nn.Linear(feature_dim, input_dim)
             )
 
-    def bellmanford(self, data, h_index, separate_grad=False):
+    def bellmanford(self, data, h_index, separate_grad=False, edge_keep=None):
         batch_size = len(h_index)
         ones = getattr(self, "_ones_query", None)
         if ones is None or ones.shape[0] != batch_size or ones.device != h_index.device or torch.is_grad_enabled():
@@ -241,8 +241,10 @@ class RelNBFNet(BaseNBFNet):
                 and (not torch.is_grad_enabled() or all(l.point_boundary_trains() for l in self.layers))):
             boundary = boundary.dense()
         # layer 0 reads the one-hot boundary itself: tell the layer which row of each sample is non-zero
+        # edge_keep: a 0/1 vector over the relation graph's edges (UltraQuery's training: the relation graph of a dropped graph)
         hiddens, edge_weights = self._propagate_layers(data, boundary, query, boundary, separate_grad=False,
-                                                       onehot_rows=h_index)
+                                                       onehot_rows=h_index, edge_weight=edge_keep,
+                                                       edge_keep=edge_keep is not None)
 
         node_query = query.unsqueeze(1).expand(-1, data.num_nodes, -1)
         if self.concat_hidden:
@@ -255,8 +257,8 @@ class RelNBFNet(BaseNBFNet):
             "edge_weights": edge_weights,
         }
 
-    def forward(self, rel_graph, query):
-        return self.bellmanford(rel_graph, h_index=query)["node_feature"]
+    def forward(self, rel_graph, query, edge_keep=None):
+        return self.bellmanford(rel_graph, h_index=query, edge_keep=edge_keep)["node_feature"]
 
 
 class EntityNBFNet(BaseNBFNet):
@@ -544,10 +546,20 @@ class QueryNBFNet(EntityNBFNet):
             "edge_weights": edge_weights,
         }
 
-    def forward(self, data, node_features, relation_representations, query):
+    def forward(self, data, node_features, relation_representations, query, edge_keep=None):
         for layer in self.layers:
             layer.relation = relation_representations
         self.query = relation_representations      # input of the batched relation projections
+        if edge_keep is not None:
+            # UltraQuery's training projection: traversal dropout as a 0/1 keep vector over the static edge list (read through
+            # the full graph's cached plan), and the readout of every node as one autograd node where it applies
+            hiddens, _ = self._propagate_layers(data, node_features, query, node_features, edge_weight=edge_keep,
+                                                edge_keep=True, relations=self._project_relations_batched())
+            if torch.is_grad_enabled() and dense.readout_train_supported(self, hiddens[-1], query):
+                return dense.readout_train(self, hiddens[-1], query)
+            node_query = query.unsqueeze(1).expand(-1, data.num_nodes, -1)
+            feature = torch.cat((hiddens if self.concat_hidden else hiddens[-1:]) + [node_query], dim=-1)
+            return self.mlp(feature).squeeze(-1)
         hiddens, _ = self._propagate_layers(data, node_features, query, node_features,
                                             relations=self._project_relations_batched())
         if dense.readout_supported(self, hiddens[-1]):

@@ -73,8 +73,8 @@ def _mask(ids, n):
 
 
 def load_betae(root, split="test", query_types=None):
-    """(graph, QueryDataset) of one split of a local BetaE directory.  query_types: type names to keep (default: the 14
-    of ID2TYPE).  The graph carries its relation graph; id2type is sorted as in the reference."""
+    """(graph, QueryDataset) of one split of a local BetaE directory ("train", "valid" or "test"; the train split reads
+    train-answers.pkl as easy answers and has no hard ones).  query_types: type names to keep (default: the 14 of ID2TYPE).  The graph carries its relation graph; id2type is sorted as in the reference."""
     num_node, num_rel = _read_sizes(root)
     h, r, t = [], [], []
     with open(os.path.join(root, "train.txt")) as fin:
@@ -89,10 +89,16 @@ def load_betae(root, split="test", query_types=None):
     type2id = {name: i for i, name in enumerate(id2type)}
     with open(os.path.join(root, "%s-queries.pkl" % split), "rb") as fin:
         struct2queries = pickle.load(fin)
-    with open(os.path.join(root, "%s-easy-answers.pkl" % split), "rb") as fin:
-        easy = pickle.load(fin)
-    with open(os.path.join(root, "%s-hard-answers.pkl" % split), "rb") as fin:
-        hard = pickle.load(fin)
+    if split == "train":
+        # the training split has one answer file, its answers are all easy (datasets_query.py:133-135)
+        with open(os.path.join(root, "train-answers.pkl"), "rb") as fin:
+            easy = pickle.load(fin)
+        hard = {}
+    else:
+        with open(os.path.join(root, "%s-easy-answers.pkl" % split), "rb") as fin:
+            easy = pickle.load(fin)
+        with open(os.path.join(root, "%s-hard-answers.pkl" % split), "rb") as fin:
+            hard = pickle.load(fin)
     queries, types, easy_answers, hard_answers = [], [], [], []
     for struct, qs in struct2queries.items():
         name = STRUCT2TYPE.get(struct)

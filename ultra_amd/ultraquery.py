@@ -7,9 +7,10 @@ union and negation combine them under a fuzzy logic, and every relation projecti
 is one `Ultra(RelNBFNet, QueryNBFNet)` forward on the HIP engine.  The stack machine stays in torch, as in the reference:
 it is control flow over whole fuzzy sets.  `SymbolicTraversal` (the exact, neural-free projection the reference runs next
 to the neural one) is one call of ultra_symbolic_traversal (csrc/query_kernels.hip) over a CSR keyed by (tail, relation)
-that is built once per graph and cached.  Inference only: traversal dropout (training) is not implemented.  DESIGN.md
-section 10.
+that is built once per graph and cached.  In train() mode every projection first drops edges (traversal dropout,
+query_train.traversal_dropout: keep vectors over the static graphs, read through their cached plans).  DESIGN.md section 10.
 """
+import copy
 import ctypes
 from collections import OrderedDict, namedtuple
 
@@ -178,11 +179,10 @@ def _logic(name):
 
 
 class UltraQuery(nn.Module):
-    """Query executor for multi-hop logical queries (ultraquery.py:12-243), inference only.
+    """Query executor for multi-hop logical queries (ultraquery.py:12-243).
 
     model: an `Ultra` whose entity model is a `QueryNBFNet`; logic: ``product``, ``godel`` or ``lukasiewicz``;
-    dropout_ratio / more_dropout: traversal dropout ratios of training (kept for the reference's signature; training is not
-    implemented); threshold: the projection's score threshold.  The submodules are named as the reference's, so the
+    dropout_ratio / more_dropout: traversal dropout ratios of training (train() mode, on the GPU); threshold: the projection's score threshold.  The submodules are named as the reference's, so the
     state_dict of ultraquery.pth (`model.model.relation_model...`) loads with strict=True.
     """
 
@@ -198,9 +198,15 @@ class UltraQuery(nn.Module):
 
     def execute(self, graph, query, symbolic_traversal):
         if self.training:
-            raise NotImplementedError(
-                "UltraQuery runs in eval() mode only: training needs traversal dropout (ultraquery.py:33-84), which is "
-                "not implemented here")
+            # the reference's training execution (ultraquery.py:96-98, 199-224): traversal dropout needs the symbolic sets,
+            # and runs on the GPU only (query_train: keep vectors over the static graphs' cached plans)
+            edge_index = getattr(graph, "edge_index", None)
+            if edge_index is None or not edge_index.is_cuda:
+                raise NotImplementedError(
+                    "UltraQuery trains on the GPU only: traversal dropout (ultraquery.py:33-84) is a HIP kernel; pass the "
+                    "graph on a CUDA device")
+            if symbolic_traversal is not True:
+                raise ValueError("symbolic_traversal is needed at train time for dropout")
         self.symbolic_traversal = symbolic_traversal
         query = query if isinstance(query, Query) else Query(query)
         batch_size = len(query)
@@ -265,6 +271,19 @@ class UltraQuery(nn.Module):
         r_index = r_index.as_subclass(torch.Tensor)
         h_prob = self.stack.pop(mask).detach()
         sym_h_prob = self.symbolic_stack.pop(mask) if self.symbolic_traversal else None
+        if self.training:
+            # traversal dropout (ultraquery.py:34-83, 202-206) as keep vectors: over the entity graph's edges from the symbolic
+            # sets, and over the relation graph's edges for the relation graph of the dropped graph
+            from . import query_train, rspmm
+            keep = query_train.traversal_dropout(graph.edge_index, graph.edge_type, graph.num_nodes, graph.num_relations,
+                                                 sym_h_prob, r_index, self.dropout_ratio, self.more_dropout,
+                                                 getattr(graph, "inverse_rel_plus_one", False))
+            rel_keep = query_train.relation_graph_keep(graph, keep)
+            # the dropped graph is the same graph object with its keep vectors attached (the reference's filtered copy,
+            # ultraquery.py:79-83): every plan and CSR of the static graphs stays cached
+            graph = copy.copy(graph)
+            graph.traversal_keep = rspmm.tag_edge_weight(keep)
+            graph.relation_keep = rspmm.tag_edge_weight(rel_keep)
         t_prob = self.model(graph, h_prob, r_index)
         sym = self.symbolic_model(graph, sym_h_prob, r_index) if self.symbolic_traversal else None
         self._push(mask, t_prob, sym)
@@ -308,9 +327,16 @@ class RelationProjection(nn.Module):
         self.threshold = threshold
 
     def forward(self, graph, h_prob, r_index):
+        # (training) graph.traversal_keep / graph.relation_keep: 0/1 vectors over the edges of the entity graph and of its
+        # relation graph -- the projection then runs on the graph without the zero edges (traversal dropout)
+        edge_keep = getattr(graph, "traversal_keep", None)
+        relation_keep = getattr(graph, "relation_keep", None)
         bs = r_index.shape[0]
         # relation representations conditioned on the query relations, (bs, num_rel, dim)  (ultraquery.py:258)
-        rel_reprs = self.model.relation_model(graph.relation_graph, query=r_index)
+        if relation_keep is not None:
+            rel_reprs = self.model.relation_model(graph.relation_graph, query=r_index, edge_keep=relation_keep)
+        else:
+            rel_reprs = self.model.relation_model(graph.relation_graph, query=r_index)
         query = rel_reprs[torch.arange(bs, device=r_index.device), r_index]            # (bs, dim)
         # initial node features: the fuzzy set scaled query vector (ultraquery.py:262); scores at or below the threshold
         # are cut off first (ultraquery.py:266-270: alleviates multi-source propagation)
@@ -318,7 +344,10 @@ class RelationProjection(nn.Module):
         if self.threshold > 0.0:
             prob = torch.where(h_prob <= self.threshold, torch.zeros_like(h_prob), h_prob)
         input = prob.unsqueeze(-1) * query.unsqueeze(1)                                # einsum("bn, bd -> bnd")
-        output = self.model.entity_model(graph, input, rel_reprs, query)               # (bs, num_nodes) scores
+        if edge_keep is not None:
+            output = self.model.entity_model(graph, input, rel_reprs, query, edge_keep=edge_keep)
+        else:
+            output = self.model.entity_model(graph, input, rel_reprs, query)           # (bs, num_nodes) scores
         return torch.sigmoid(output)
 
 
@@ -363,10 +392,32 @@ def traversal_csr(edge_index, edge_type, num_node):
 
 def clear_csr_cache():
     _CSR_CACHE.clear()
+    _ORDER_CACHE.clear()
 
 
-def symbolic_traversal(edge_index, edge_type, num_node, h_prob, r_index):
-    """t[b, v] = max(0, max{h[b, u] : edge u -> v of type r_index[b]}) on the GPU (ultra_symbolic_traversal)."""
+_ORDER_CACHE = OrderedDict()
+
+
+def traversal_order(edge_index, edge_type, num_node):
+    """The edge id of every slot of traversal_csr (the same stable sort), cached alike: training maps its keep vectors
+    into slot order with it."""
+    key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), tuple(edge_index.stride()),
+           edge_type.data_ptr(), edge_type._version, str(edge_index.device), int(num_node))
+    hit = _ORDER_CACHE.get(key)
+    if hit is not None:
+        _ORDER_CACHE.move_to_end(key)
+        return hit[0]
+    num_rel = int(edge_type.max()) + 1 if edge_type.numel() else 1
+    order = torch.sort(edge_index[1] * num_rel + edge_type, stable=True).indices
+    _ORDER_CACHE[key] = (order, edge_index, edge_type)
+    while len(_ORDER_CACHE) > _CSR_CACHE_SIZE:
+        _ORDER_CACHE.popitem(last=False)
+    return order
+
+
+def symbolic_traversal(edge_index, edge_type, num_node, h_prob, r_index, edge_keep=None):
+    """t[b, v] = max(0, max{h[b, u] : edge u -> v of type r_index[b]}) on the GPU (ultra_symbolic_traversal); with
+    edge_keep (num_edge, 0/1) over the edges whose keep is not 0 only (ultra_symbolic_traversal_keep)."""
     if h_prob.dtype not in (torch.float32, torch.float64):
         raise TypeError("the symbolic traversal takes fp32 or fp64 fuzzy sets, got %s" % h_prob.dtype)
     if h_prob.dim() != 2 or h_prob.shape[1] != num_node or r_index.shape != (h_prob.shape[0],):
@@ -379,6 +430,13 @@ def symbolic_traversal(edge_index, edge_type, num_node, h_prob, r_index):
     r = r_index.to(torch.int64).contiguous()
     t = torch.empty_like(h)
     stream = ctypes.c_void_p(torch.cuda.current_stream(h.device).cuda_stream)
+    if edge_keep is not None:
+        # the keep vector in the CSR's slot order
+        keep_slot = edge_keep.to(torch.float32)[traversal_order(edge_index, edge_type, num_node)].contiguous()
+        check(lib.ultra_symbolic_traversal_keep(csr.row_ptr.data_ptr(), csr.src.data_ptr(), csr.type.data_ptr(),
+                                                keep_slot.data_ptr(), csr.num_node, r.data_ptr(), h.shape[0],
+                                                0 if h.dtype == torch.float32 else 1, h.data_ptr(), t.data_ptr(), stream))
+        return t
     check(lib.ultra_symbolic_traversal(csr.row_ptr.data_ptr(), csr.src.data_ptr(), csr.type.data_ptr(), csr.num_node,
                                        r.data_ptr(), h.shape[0], 0 if h.dtype == torch.float32 else 1, h.data_ptr(),
                                        t.data_ptr(), stream))
@@ -402,4 +460,5 @@ class SymbolicTraversal(nn.Module):
     """Symbolic traversal (ultraquery.py:280-298): the exact projection of a fuzzy set along one relation per sample."""
 
     def forward(self, graph, h_prob, r_index):
-        return symbolic_traversal(graph.edge_index, graph.edge_type, graph.num_nodes, h_prob, r_index)
+        return symbolic_traversal(graph.edge_index, graph.edge_type, graph.num_nodes, h_prob, r_index,
+                                  edge_keep=getattr(graph, "traversal_keep", None))
