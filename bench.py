@@ -11,9 +11,14 @@ shard over ranks (each rank scores its own 8 queries, graph + weights replicated
 with one RCCL all-gather of the per-rank score rows.  Weak scaling: per-GPU work is fixed.  Rank 0 prints ONE JSON line.
 The forward is a captured hipGraph; by default THREE captures take the steps alternately on as many streams (--in-flight 3,
 ultra_amd/graph.py PipelinedForward): steps are independent batches, and the launches of one that leave the chip idle run
-beside the entity layers of the next.  ms_per_step = elapsed / steps; `modes.one_batch_in_flight` has the one-stream figure.
+beside the entity layers of the next.  ms_per_step = elapsed / steps.
 
-Extra blocks of the JSON line (rank 0, N = 1):
+A plain run does what the headline needs and nothing else: it sets up (build check, graph, model, captures, the slots' stream
+trial), runs the pre-warm and W warm-up steps, times the K steps once, writes --dump-outputs if asked and prints the line.
+Everything else the benchmark measures or checks runs only with --full: the timed loop repeated (`repeats`, five runs by default),
+the roofline / cpu_baseline / parity / modes / secondary blocks below (`modes.one_batch_in_flight` has the one-stream figure).
+
+Extra blocks of the JSON line with --full (rank 0, N = 1):
   roofline     -- the dominant kernel (one entity layer: reference-order rspmm + the layer update in its tail,
                   ultra_rspmm_forward_update) at the benchmark point AND at the
                   HBM-bound point (CoDEx-L shape, batch 8: x + out = 319 MB > the 256 MB Infinity Cache): kernel time
@@ -638,7 +643,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--shape", default="fb15k237")
     ap.add_argument("--bs", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline, parity and modes blocks")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-graph", action="store_true", help="launch the forward eagerly instead of replaying its hipGraph")
     ap.add_argument("--in-flight", type=int, default=3,
@@ -646,17 +651,23 @@ def main():
                          "stream.  Three: measured with the slots' streams picked by trial (graph.pick_slot_streams), plain process "
                          "0.568 / 0.558 - 0.573 ms first run / repeats against 0.583 - 0.593 / 0.584 - 0.589 with two; a launcher's rank "
                          "0.565 - 0.588 / 0.555 - 0.572 against 0.600 - 0.650 / 0.585 - 0.643 (profiles/r5_experiments.txt)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes of the roofline block")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the fine-tuning steps of the `secondary` block")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, run everything else the benchmark measures or checks: the repeats of the timed loop, "
+                         "the roofline block (HIP-event kernel times, rocprofv3 child passes), the CPU baseline with parity and the "
+                         "other modes, the secondary configurations.  Off: a plain run sets up, warms up, times the K steps once, "
+                         "writes --dump-outputs and prints the line")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the rocprofv3 counter passes of the roofline block")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline block")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the fine-tuning steps of the `secondary` block")
     ap.add_argument("--data-root", default=None,
                     help="directory with train.txt / valid.txt / test.txt (kg-datasets/FB15k-237 layout): score the real test "
                          "triples instead of the synthetic graph of --shape (data: \"real\")")
     ap.add_argument("--pre-warm", type=int, default=64,
                     help="untimed steps in front of the first timed run's W warm-up steps (the chip's clocks settle after tens of ms)")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="the timed loop of --steps steps runs this many times in the process: ms_per_step / value are the FIRST "
-                         "run's (the contract's exactly-K-steps figure), `repeats` carries every run, their median and spread")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the timed loop of --steps steps runs this many times in the process (default 5 with --full, else 1): "
+                         "ms_per_step / value are the FIRST run's (the contract's exactly-K-steps figure), `repeats` carries every "
+                         "run, their median and spread")
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo"),
                     help="nccl = RCCL (the measured configuration).  gloo: the N-rank code path where ranks must share a GPU "
                          "(tests on a one-GPU box: RCCL refuses two ranks on one device); ranks then map to GPUs modulo the "
@@ -673,6 +684,8 @@ def main():
     ap.add_argument("--pmc-target", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--trace-target", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     if args.pmc_target or args.trace_target:
         import __graft_entry__ as entry
@@ -852,15 +865,15 @@ def main():
             return elapsed_
 
     roofline = None
-    if rank == 0 and world == 1 and not launched and not args.no_roofline:
+    if args.full and rank == 0 and world == 1 and not launched and not args.no_roofline:
         # the dominant kernel's own measurement (HIP events around its launches, rocprofv3 child passes) runs BEFORE the timed
         # region: it is independent of it, and the GPU then enters the timed steps from sustained work rather than from idle
         roofline = measure_roofline(dev, use_pmc=not args.no_pmc, in_flight=1 if args.no_graph else args.in_flight)
     forward = make_forward()
     dumped = {} if args.dump_outputs and rank == 0 else None
     elapsed = timed_run(forward, world > 1 or launched, keep=dumped)
-    # the same K steps again, `--repeats` runs in all: box-to-box and run-to-run spread is of the size of a small kernel gain,
-    # so the line carries the median and the extremes beside the first run's figure
+    # the same K steps again, `--repeats` runs in all (five with --full): box-to-box and run-to-run spread is of the size of a
+    # small kernel gain, so the line carries the median and the extremes beside the first run's figure
     runs = [elapsed] + [timed_run(forward, world > 1 or launched) for _ in range(max(args.repeats, 1) - 1)]
     el = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     per_rank = None
@@ -932,11 +945,11 @@ def main():
         out["dump_outputs"] = {"dir": args.dump_outputs, "step": args.warmup + args.steps - 1,
                                "arrays": dump_outputs(args.dump_outputs, dumped)}
 
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         # (counter passes only at N = 1: they re-run the kernels in a child process on this rank's GPU)
         out["roofline"] = roofline if roofline is not None else measure_roofline(dev, use_pmc=False,
                                                                                in_flight=1 if args.no_graph else args.in_flight)
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
 
         # ---- CPU baseline + parity on the identical batch ----
         if not args.no_cpu_baseline:
@@ -1116,7 +1129,7 @@ def main():
                             "step): an engine feature for jobs that score many batches over one graph, not a benchmark figure"}
             finally:
                 model.drop_relation_cache()
-    if rank == 0 and world == 1 and not launched and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not launched and not args.no_secondary:
         # ---- BASELINE.json config 5 (fine-tuning): fwd + bwd + AdamW per step, beside the headline ----
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import secondary_bench

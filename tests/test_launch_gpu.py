@@ -34,7 +34,7 @@ def _env():
 def test_bench_under_torchrun_world_size_one():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
-           "--no-cpu-baseline", "--no-roofline", "--no-secondary"]
+           "--full", "--no-cpu-baseline", "--no-roofline", "--no-secondary"]
     r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -57,7 +57,7 @@ def test_bench_scores_real_triples_from_files():
     """bench.py --data-root on the committed kg-datasets-layout fixture (tests/golden/kg_fixture): `data: real`, and the
     parity block against the oracle flow on the same batch is green."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--data-root", os.path.join(ROOT, "tests", "golden", "kg_fixture"),
-           "--steps", "5", "--warmup", "2", "--repeats", "2", "--no-roofline", "--no-secondary", "--cpu-seconds", "1"]
+           "--steps", "5", "--warmup", "2", "--repeats", "2", "--full", "--no-roofline", "--no-secondary", "--cpu-seconds", "1"]
     r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -98,6 +98,21 @@ def test_bench_dump_outputs_are_the_last_timed_steps_scores(tmp_path):
     assert got.shape == (bs, data.num_nodes)
     torch.testing.assert_close(got, scores(W + K - 1), rtol=0, atol=1e-6)
     assert (got - scores(W + K - 2)).abs().max().item() > 1e-3         # not the step before
+
+
+def test_plain_bench_line_is_the_headline_alone():
+    """bench.py without --full: the timed loop runs once and the line carries none of the blocks --full adds."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2"]
+    r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-500:]
+    out = json.loads(lines[0])
+    for key in ("roofline", "cpu_baseline", "parity", "modes", "secondary"):
+        assert key not in out, key
+    assert out["steps"] == 5 and out["warmup"] == 2 and out["config"]["launch"].startswith("hipGraph")
+    assert out["repeats"]["runs"] == 1 and out["repeats"]["ms_per_step"][0] == pytest.approx(out["ms_per_step"], rel=1e-3)
+    assert out["value"] == pytest.approx(8 * 14541 * 5 / (out["ms_per_step"] * 5e-3), rel=1e-6)
 
 
 def test_bench_refuses_more_gpus_than_visible():

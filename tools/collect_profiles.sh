@@ -14,7 +14,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 if [ "$part" = "A" ]; then
     timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$OUT/${R}_smoke.txt" 2>&1
-    ULTRA_BENCH_PMC_KEEP="$PWD/$OUT/${R}_pmc" timeout 900 python bench.py > "$OUT/${R}_bench.json" 2> "$OUT/bench.err"
+    ULTRA_BENCH_PMC_KEEP="$PWD/$OUT/${R}_pmc" timeout 900 python bench.py --full > "$OUT/${R}_bench.json" 2> "$OUT/bench.err"
     # (bench.py's own --kernel-trace child pass: the forward as ONE captured graph on ONE stream -- the durations DESIGN.md section 4 quotes)
     # (bench.py's own --kernel-trace child passes: inflight1 = the forward as ONE captured graph on ONE stream -- the durations DESIGN.md
     # section 4 quotes; inflight<k> = k captures on k streams as the timed region runs them)
@@ -23,7 +23,7 @@ if [ "$part" = "A" ]; then
         python "$OLDPWD/bench.py" --no-cpu-baseline --no-roofline --no-secondary > /dev/null 2>&1)
     find /tmp/prof_stats -name "*kernel_stats.csv" -exec cp {} "$OUT/${R}_bench_kernel_stats.csv" \;
     timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 \
-        bench.py --gpus 1 --steps 20 --warmup 3 --no-cpu-baseline > "$OUT/${R}_bench_torchrun1.json" 2>> "$OUT/bench.err"
+        bench.py --gpus 1 --steps 20 --warmup 3 --full --no-cpu-baseline > "$OUT/${R}_bench_torchrun1.json" 2>> "$OUT/bench.err"
 elif [ "$part" = "C" ]; then
     # SQ / TCC counter passes over tools/pmc_target.py (separate passes, no other trace domain)
     i=0
