@@ -29,6 +29,8 @@ extern "C" {
  *     out = [x +] relu( LayerNorm_eps( W . cat[x, agg] + b ) )
  * x, agg, out: (rows, 64) contiguous; weight (64, 128) row-major = linear.weight; bias (64) may be NULL;
  * ln_weight / ln_bias (64) required with ULTRA_CONV_LAYER_NORM.  out may not alias x or agg.
+ * `flags`: ULTRA_CONV_LAYER_NORM | ULTRA_CONV_RELU | ULTRA_CONV_RESIDUAL; any other bit is ULTRA_ERR_INVALID (the
+ * measurement switch 256 of tools/conv_probe.py is accepted only by a library built with -DULTRA_CONV_DEBUG=1).
  */
 int32_t ultra_conv_update(const void *x, const void *agg, const void *weight, const void *bias, const void *ln_weight,
                           const void *ln_bias, void *out, int64_t rows, int32_t input_dim, int32_t output_dim, float eps,
@@ -39,7 +41,10 @@ int32_t ultra_conv_update(const void *x, const void *agg, const void *weight, co
  * reference: cat, addmm, native_layer_norm, relu and add nodes).  Nothing but x and agg has to be kept from the forward:
  * the pre-activation is recomputed on the matrix cores.
  *     grad_x, grad_agg (rows, 64); grad_weight (64, 128); grad_bias / grad_ln_weight / grad_ln_bias (64) may be NULL.
- * `flags` as in the forward.  workspace: ultra_conv_update_backward_workspace(rows) bytes of device memory (the
+ * `flags`: ULTRA_CONV_LAYER_NORM | ULTRA_CONV_RELU | ULTRA_CONV_RESIDUAL; any other bit is ULTRA_ERR_INVALID and nothing
+ * is launched or written.  The timing switches 256 / 512 / 1024 (skip one matrix product) and 2048 (clock ticks into the
+ * workspace) give wrong gradients and exist only in a library built with -DULTRA_CONV_BWD_DEBUG=1 (tools/conv_bwd_probe.py).
+ * workspace: ultra_conv_update_backward_workspace(rows) bytes of device memory (the
  * pre-activation gradient and the per-workgroup partial sums; combined in a fixed order -- no atomics, gradients are
  * reproducible run to run).  Gradients OVERWRITE their destinations.
  */

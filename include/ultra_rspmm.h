@@ -234,6 +234,7 @@ int32_t ultra_rspmm_forward_update(ultra_plan *plan, int32_t sum, int32_t mul, c
  * Rows that are neither src_rows[b] nor a target of one of its out-edges all equal relu(LayerNorm(bias)); they are
  * filled, the others are computed from the transposed plan.  relation: (n_outer, num_relation, 64); weight (64, 128)
  * row-major = linear.weight; output (n_outer, num_node, 64).  Needs the (row, col) plan of a square graph.
+ * flags: ULTRA_CONV_* and ULTRA_LAYER0_* of ultra_nbfnet.h; any other bit is ULTRA_ERR_INVALID.
  */
 int32_t ultra_nbf_layer0(ultra_plan *plan, const void *edge_weight_dev, const ultra_mat *relation, const int64_t *src_rows_dev,
                          const void *src_values_dev, const void *weight, const void *bias, const void *ln_weight,

@@ -1,6 +1,7 @@
 """Model-level parity on the GPU: Ultra.forward through the HIP engine vs (a) golden scores recorded
 from the reference and (b) the CPU oracle model on a larger seeded graph.  Tolerance: fp32 scores
 within 1e-4 (BASELINE north_star), rankings / metrics identical."""
+import copy
 import os
 
 import pytest
@@ -134,6 +135,135 @@ def test_training_step_gradients_match_cpu_autograd(dev):
             "%s: |gpu - fp64| = %g, |cpu fp32 - fp64| = %g (scale %g)" % (name, err_gpu, err_cpu, scale)
 
 
+
+def reference_easy_edge_keep(edge_index, edge_type, h_index, t_index, r_index, num_relations, remove_one_hop=False):
+    """base_nbfnet.py:54-77 as a plain loop: an edge is dropped when it is some (h, t, r) of the batch -- negatives included --
+    or its inverse (t, h, r + R/2); with remove_one_hop when it joins such a pair under any type."""
+    half = num_relations // 2
+    easy = set()
+    for h, t, r in zip(h_index.flatten().tolist(), t_index.flatten().tolist(), r_index.flatten().tolist()):
+        easy.add((h, t) if remove_one_hop else (h, t, r))
+        easy.add((t, h) if remove_one_hop else (t, h, r + half))
+    keep = []
+    for a, b, r in zip(edge_index[0].tolist(), edge_index[1].tolist(), edge_type.tolist()):
+        keep.append(((a, b) if remove_one_hop else (a, b, r)) not in easy)
+    return torch.tensor(keep, dtype=torch.bool)
+
+
+def test_easy_edge_loop_matches_reference_golden():
+    """The loop above keeps exactly the edges the reference's remove_easy_edges kept (tests/golden/easy_edges.pt)."""
+    from tests.test_tasks import easy_edges_golden
+    data, cases = easy_edges_golden()
+    for case in cases:
+        h, t, r = case["batch"].unbind(-1)
+        keep = reference_easy_edge_keep(data.edge_index, data.edge_type, h, t, r, data.num_relations, case["remove_one_hop"])
+        assert torch.equal(keep, case["keep"])
+
+
+class OracleRSPMM(torch.autograd.Function):
+    """rspmm_oracle.rspmm_forward / rspmm_backward as an autograd node: the reference's min / max tie rule (every tying edge
+    gets the full gradient), which neither an index_add restatement nor scatter_reduce (it splits ties) has."""
+
+    @staticmethod
+    def forward(ctx, edge_index, edge_type, edge_weight, relation, input, sum, mul):
+        from oracle import rspmm_oracle
+        ei, et, ew, _ = rspmm_oracle.sort_edges(edge_index, edge_type, edge_weight)
+        out = rspmm_oracle.rspmm_forward(ei, et, ew, relation, input, sum=sum, mul=mul)
+        ctx.save_for_backward(ei, et, ew, relation, input, out)
+        ctx.sum, ctx.mul = sum, mul
+        return out
+
+    @staticmethod
+    def backward(ctx, output_grad):
+        from oracle import rspmm_oracle
+        ei, et, ew, relation, input, out = ctx.saved_tensors
+        _, rel_grad, x_grad = rspmm_oracle.rspmm_backward(ei, et, ew, relation, input, out, output_grad.contiguous(),
+                                                          sum=ctx.sum, mul=ctx.mul)
+        return None, None, None, rel_grad, x_grad, None, None
+
+
+def oracle_rspmm(edge_index, edge_type, edge_weight, relation, input, sum="add", mul="mul"):
+    return OracleRSPMM.apply(edge_index, edge_type, edge_weight, relation, input, sum, mul)
+
+
+TRAIN_ROUTES = [("ultra_3g", "sum", "rows"), ("ultra_3g", "sum", "whole_graph"), ("ultra_3g", "sum", "old_routes"),
+                ("ultra_50g", "max", "default"), ("ultra_3g", "mean", "default")]
+
+
+@pytest.mark.parametrize("ckpt,aggr,route", TRAIN_ROUTES)
+def test_train_mode_step_gradients_match_cpu_oracle(dev, monkeypatch, ckpt, aggr, route):
+    """The training step as train() runs it: model.train() (the batch's own edges are dropped by the keep-mask kernels), the
+    self-adversarial loss at temperature 0.5 (train.ranking_loss, script/run.py:66-77), .backward().  Against torch autograd
+    over the CPU oracle model on the graph the reference's remove_easy_edges leaves, its rspmm an autograd node over the C
+    oracle (the reference's tie rule), in fp32 and fp64: the GPU may not be further from fp64 than a few times the CPU fp32
+    path.  sum / mean: max-abs per parameter; max: Frobenius norm per parameter, near-ties may fall either way between two
+    fp32 paths."""
+    from oracle import ultra_oracle_model as om
+    from tests.test_train_gpu import reference_loss
+    from ultra_amd import dense, layers, rspmm, train
+    _, state, _, cfg = load_golden(ckpt, "sum" if aggr == "mean" else aggr)
+    if aggr == "mean":
+        cfg = {k: dict(v) for k, v in cfg.items()}
+        cfg["entity_model_cfg"]["aggregate_func"] = "mean"
+    if route in ("rows", "whole_graph"):
+        monkeypatch.setattr(layers, "LAST_LAYER_ON_ROWS", route == "rows")
+    if route == "old_routes":      # (monkeypatch restores every switch afterwards)
+        for mod, name in ((models, "EASY_EDGE_KEEP_KERNEL"), (dense, "READOUT_TRAIN_NODE"), (models, "RELATION_PROJECTION_NODE"),
+                          (dense, "ROWS_BACKWARD_GATHER"), (rspmm, "DENSE_RELATION_GRAD"), (train, "FUSED_LOSS")):
+            assert hasattr(mod, name)
+            monkeypatch.setattr(mod, name, False)
+    data = synthetic.make_kg(num_node=300, num_triple=2400, num_relation_base=5, num_test=16, seed=4)
+    # the batch: graph edges, so that the training forward has easy edges to drop
+    pick = torch.tensor([0, 7, 900, 1900])
+    batch = torch.stack([data.edge_index[0, pick], data.edge_index[1, pick], data.edge_type[pick]], dim=-1)
+    torch.manual_seed(0)
+    neg = tasks.negative_sampling(data, batch, 8, strict=True)
+    num_negative = neg.shape[1] - 1
+    h, t, r = neg.unbind(-1)
+    keep = reference_easy_edge_keep(data.edge_index, data.edge_type, h, t, r, data.num_relations)
+    assert 0 < int((~keep).sum()) < 100
+    filtered = copy.copy(data)
+    filtered.edge_index, filtered.edge_type = data.edge_index[:, keep], data.edge_type[keep]
+
+    def cpu_step(dtype):
+        sd = {k: v.clone().to(dtype).requires_grad_() for k, v in state.items()}
+        with torch.enable_grad():
+            rel = om.rel_nbfnet(sd, data.relation_graph, neg[:, 0, 2], cfg["rel_model_cfg"], oracle_rspmm)
+            pred = om.entity_nbfnet(sd, filtered, rel, neg, cfg["entity_model_cfg"], oracle_rspmm)
+            loss = reference_loss(pred, 0.5, num_negative)
+            loss.backward()
+        return loss.item(), pred.detach(), {k: v.grad.double() for k, v in sd.items()}
+
+    loss32, pred32, g32 = cpu_step(torch.float32)
+    loss64, _, g64 = cpu_step(torch.float64)
+
+    model = models.Ultra(**cfg)
+    model.load_state_dict(state)
+    model = model.to(dev).train()
+    gdata = data.to(dev)
+    pred = model(gdata, neg.to(dev))
+    loss = train.ranking_loss(pred, 0.5, num_negative)
+    loss.backward()
+    # the masked route really ran: the scores are the filtered graph's, not the full graph's
+    with torch.no_grad():
+        model.eval()
+        full = model(gdata, neg.to(dev)).cpu()
+        model.train()
+    assert (pred.detach().cpu() - pred32).abs().max().item() <= TOL
+    assert (full - pred32).abs().max().item() > 10 * TOL, "dropping the easy edges did not change the scores"
+    assert abs(loss.item() - loss32) <= 1e-5, (loss.item(), loss32)
+    for name, p in model.named_parameters():
+        assert p.grad is not None, name
+        got, want, cpu = p.grad.cpu().double(), g64[name], g32[name]
+        if aggr == "max":
+            scale = max(want.norm().item(), 1e-6)
+            err_gpu, err_cpu = (got - want).norm().item(), (cpu - want).norm().item()
+        else:
+            scale = max(want.abs().max().item(), 1e-6)
+            err_gpu, err_cpu = (got - want).abs().max().item(), (cpu - want).abs().max().item()
+        assert err_gpu <= 4 * err_cpu + 1e-4 * scale + 1e-7, \
+            "%s: |gpu - fp64| = %g, |cpu fp32 - fp64| = %g (scale %g)" % (name, err_gpu, err_cpu, scale)
+
 def test_training_mode_removes_easy_edges(dev):
     _, state, _, cfg = load_golden("ultra_3g", "sum")
     data = synthetic.make_kg(num_node=200, num_triple=1500, num_relation_base=4, num_test=16, seed=6)
@@ -148,6 +278,15 @@ def test_training_mode_removes_easy_edges(dev):
         out_eval = model(data.to(dev), neg.to(dev))
     assert out_train.shape == out_eval.shape == (4, 5)
     assert not torch.allclose(out_train.detach(), out_eval)      # the direct edges were dropped in training mode
+    # ... exactly the edges the reference drops: the training scores are the eval scores of the filtered graph
+    h, t, r = neg.unbind(-1)
+    keep = reference_easy_edge_keep(data.edge_index, data.edge_type, h, t, r, data.num_relations)
+    assert int((~keep).sum()) > 0
+    filtered = copy.copy(data)
+    filtered.edge_index, filtered.edge_type = data.edge_index[:, keep], data.edge_type[keep]
+    with torch.no_grad():
+        out_filtered = model(filtered.to(dev), neg.to(dev))
+    assert (out_train.detach() - out_filtered).abs().max().item() <= 1e-5
 
 
 def test_graph_capture_replays_the_same_scores(dev):

@@ -26,7 +26,7 @@ def plain_update(x, agg, w, b, g, beta, eps, ln, relu, residual):
     return out + x if residual else out
 
 
-@pytest.mark.parametrize("rows", [1, 5, 32, 1000, 14541 * 8])
+@pytest.mark.parametrize("rows", [1, 5, 32, 1000, 14541 * 8, 123182 * 8])
 @pytest.mark.parametrize("ln,relu,residual", [(True, True, True), (True, True, False), (False, True, True), (True, False, False),
                                                (False, False, False)])
 def test_conv_update_backward_matches_autograd(dev, rows, ln, relu, residual):
@@ -68,6 +68,72 @@ def test_conv_update_backward_matches_autograd(dev, rows, ln, relu, residual):
         err_torch = (r32 - r64).abs().max().item()
         assert err <= 4 * err_torch + 2e-5 * scale, "%s: |fused - fp64| = %g, |torch fp32 - fp64| = %g (scale %g)" % (
             name, err, err_torch, scale)
+
+
+def test_update_entry_points_refuse_undefined_flag_bits(dev):
+    """The timing-only bits of the update backward (256 / 512 / 1024 skip a matrix product, 2048 writes clock ticks into the
+    workspace) and any other bit outside LN | RELU | RESIDUAL are refused by the default build before anything is launched:
+    ULTRA_ERR_INVALID, the gradients keep what they held.  Flags 0-7 still run.  The forward ultra_conv_update and
+    ultra_nbf_layer0 refuse bits outside their own sets the same way."""
+    import ctypes
+    from ultra_amd import _lib
+    from ultra_amd._lib import lib
+    rows = 1000
+    gen = torch.Generator().manual_seed(17)
+    x, agg, gout = (torch.randn(rows, 64, generator=gen).to(dev) for _ in range(3))
+    w = (torch.randn(64, 128, generator=gen) / 11).to(dev)
+    b, lw, lb = (torch.randn(64, generator=gen).to(dev) for _ in range(3))
+    nbytes = lib.ultra_conv_update_backward_workspace(rows)
+    work = torch.zeros(nbytes // 4, dtype=torch.float32, device=dev)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+    def backward(flags):
+        grads = [torch.full_like(t, 7.0) for t in (x, agg, w, b, b, b)]
+        rc = lib.ultra_conv_update_backward(x.data_ptr(), agg.data_ptr(), gout.data_ptr(), w.data_ptr(), b.data_ptr(),
+                                            lw.data_ptr(), lb.data_ptr(), *[t.data_ptr() for t in grads], work.data_ptr(),
+                                            nbytes, rows, 64, 64, 1e-5, flags, stream)
+        torch.cuda.synchronize(dev)
+        return rc, grads
+
+    for flags in (8, 16, 256, 512, 1024, 2048, 7 | 256, 7 | 2048, 1 << 30):
+        rc, grads = backward(flags)
+        assert rc == _lib.ULTRA_ERR_INVALID, flags
+        assert "flag" in lib.ultra_last_error().decode()
+        assert all(bool((t == 7.0).all()) for t in grads), "flags %d wrote a gradient" % flags
+        assert not bool(work.any()), "flags %d wrote the workspace" % flags
+    for flags in range(8):
+        ln, relu, residual = bool(flags & 1), bool(flags & 2), bool(flags & 4)
+        rc, grads = backward(flags)
+        assert rc == _lib.ULTRA_OK, flags
+        leaves = [t.detach().cpu().double().requires_grad_() for t in (x, agg, w, b, lw, lb)]
+        plain_update(*leaves, 1e-5, ln, relu, residual).backward(gout.cpu().double())
+        for name, got, leaf in zip(("x", "agg", "weight", "bias", "ln_weight", "ln_bias"), grads, leaves):
+            if name.startswith("ln_") and not ln:
+                continue
+            want = leaf.grad
+            err = (got.cpu().double() - want).abs().max().item()
+            assert err <= 1e-4 * max(want.abs().max().item(), 1e-6), (flags, name, err)
+
+    out = torch.full_like(x, 7.0)
+    for flags in (8, 256, 7 | 256, 1 << 20):
+        rc = lib.ultra_conv_update(x.data_ptr(), agg.data_ptr(), w.data_ptr(), b.data_ptr(), lw.data_ptr(), lb.data_ptr(),
+                                   out.data_ptr(), rows, 64, 64, 1e-5, flags, stream)
+        torch.cuda.synchronize(dev)
+        assert rc == _lib.ULTRA_ERR_INVALID, flags
+        assert bool((out == 7.0).all())
+    data = synthetic.make_kg(num_node=200, num_triple=1500, num_relation_base=4, seed=6).to(dev)
+    plan = rspmm.get_plan(data.edge_index, data.edge_type, data.num_nodes, data.num_relations, exact_order=False)
+    lin, norm = torch.nn.Linear(128, 64).to(dev), torch.nn.LayerNorm(64).to(dev)
+    fill = plan.layer0_fill(2, lin, norm)
+    assert torch.isfinite(fill).all()
+    _, mout = rspmm.as_mat(fill)
+    before = fill.clone()
+    for flags in (64, 128, 3 | 256):
+        rc = lib.ultra_nbf_layer0(plan._h, None, None, None, None, lin.weight.data_ptr(), lin.bias.data_ptr(),
+                                  norm.weight.data_ptr(), norm.bias.data_ptr(), 1e-5, flags | 16, ctypes.byref(mout), stream)
+        torch.cuda.synchronize(dev)
+        assert rc == _lib.ULTRA_ERR_INVALID, flags
+        assert torch.equal(fill, before)
 
 
 def test_conv_update_backward_is_deterministic(dev):

@@ -1,5 +1,12 @@
 """ultra_conv_update_backward (rows kernel + weights kernel + reduce) per call, HIP events over a hipGraph of 20 calls, for the row
-counts of the fine-tuning step.  ULTRA_CONV_BWD_SHAPE=blocks_cap,wpb_rows,wpb_weights selects the launch shape (0 = the library's)."""
+counts of the fine-tuning step.  ULTRA_CONV_BWD_SHAPE=blocks_cap,wpb_rows,wpb_weights selects the launch shape (0 = the library's).
+
+PROBE_FLAGS (the timing switches 256 / 512 / 1024 / 2048 of conv_update_bwd.hip) need a library built with them:
+
+    python tools/build_variant.py convdbg -DULTRA_CONV_BWD_DEBUG=1
+    ULTRA_AMD_LIB=ultra_amd/lib/variants/libultra_amd_convdbg.so PROBE_FLAGS=256 python tools/conv_bwd_probe.py
+
+the default build refuses them (ULTRA_ERR_INVALID)."""
 import ctypes
 import os
 import sys

@@ -1,4 +1,5 @@
-"""conv_update timing next to its matrix and byte floors."""
+"""conv_update timing next to its matrix and byte floors.  The "no matrix chain" lines (flag 256) need a library built with
+-DULTRA_CONV_DEBUG=1 (python tools/build_variant.py convdbg -DULTRA_CONV_DEBUG=1, then ULTRA_AMD_LIB=the printed path)."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

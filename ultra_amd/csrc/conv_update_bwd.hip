@@ -38,6 +38,12 @@ enum { CB_LN = 1, CB_RELU = 2, CB_RESIDUAL = 4,
        CB_DBG_NO_W_MFMA = 256, CB_DBG_NO_DX_MFMA = 512, CB_DBG_NO_Z_MFMA = 1024,
        // workgroup 0 leaves its shader-clock ticks (s_memtime) and its 100-MHz ticks (s_memrealtime) in the first 16 bytes of the workspace
        CB_DBG_CLOCK = 2048 };
+// The CB_DBG_* switches exist only in a build with -DULTRA_CONV_BWD_DEBUG=1 (tools/build_variant.py); elsewhere the kernels
+// do not test them and ultra_conv_update_backward refuses every bit outside CB_LN | CB_RELU | CB_RESIDUAL.
+#ifndef ULTRA_CONV_BWD_DEBUG
+#define ULTRA_CONV_BWD_DEBUG 0
+#endif
+constexpr int CB_DBG_BITS = ULTRA_CONV_BWD_DEBUG ? (CB_DBG_NO_W_MFMA | CB_DBG_NO_DX_MFMA | CB_DBG_NO_Z_MFMA | CB_DBG_CLOCK) : 0;
 constexpr int CB_WR_STRIDE = 136;                 // row stride (floats) of the row-major weight copy: 4 rows apart = 32 banks apart
 constexpr int CB_PART = 64 * 128 + 3 * 64;        // floats per workgroup partial: dW, db, d gamma, d beta
 
@@ -370,7 +376,8 @@ __global__ void __launch_bounds__(512) conv_update_bwd_fused_kernel(const ConvBw
     __shared__ __attribute__((aligned(16))) float lds_dz[4 * 2 * CBF_TILE];      // [pair][buffer][tile]; the weight waves' fold afterwards
     __shared__ int lds_flag[4 * 2];
     const int tid = threadIdx.x;
-    const unsigned long long clk0 = __builtin_readcyclecounter(), real0 = __builtin_amdgcn_s_memrealtime();
+    const unsigned long long clk0 = CB_DBG_BITS ? __builtin_readcyclecounter() : 0ull;
+    const unsigned long long real0 = CB_DBG_BITS ? __builtin_amdgcn_s_memrealtime() : 0ull;
     for (int idx4 = tid; idx4 < 2 * 16 * 64; idx4 += blockDim.x) {
         const int l = idx4 & 63, c = (idx4 >> 6) & 15, m = idx4 >> 10;
         reinterpret_cast<float4 *>(lds_wf)[idx4] =
@@ -436,7 +443,7 @@ __global__ void __launch_bounds__(512) conv_update_bwd_fused_kernel(const ConvBw
             f32x16 acc0, acc1;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc0[r] = 0.f, acc1[r] = 0.f;
-            if (p.flags & CB_DBG_NO_Z_MFMA) {      // (timing-only build switch: wrong results)
+            if (p.flags & CB_DBG_BITS & CB_DBG_NO_Z_MFMA) {      // (timing-only build switch: wrong results)
 #pragma unroll
                 for (int c = 0; c < 8; ++c) acc0[c] = bx[c].x + ba[c].y, acc1[c] = bx[c].z + ba[c].w;
             } else
@@ -553,7 +560,7 @@ __global__ void __launch_bounds__(512) conv_update_bwd_fused_kernel(const ConvBw
                     o1[4 * g + 0] = res ? g4[4 + g].x : 0.f, o1[4 * g + 1] = res ? g4[4 + g].y : 0.f;
                     o1[4 * g + 2] = res ? g4[4 + g].z : 0.f, o1[4 * g + 3] = res ? g4[4 + g].w : 0.f;
                 }
-                if (!(p.flags & CB_DBG_NO_DX_MFMA))      // (timing-only build switch: wrong results)
+                if (!(p.flags & CB_DBG_BITS & CB_DBG_NO_DX_MFMA))      // (timing-only build switch: wrong results)
 #pragma unroll
                 for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -644,7 +651,7 @@ __global__ void __launch_bounds__(512) conv_update_bwd_fused_kernel(const ConvBw
                     const float a0 = dzt[rt * 64 + (n ^ (32 * hh))], a1 = dzt[rt * 64 + ((32 + n) ^ (32 * hh))];
                     dbias[0] += a0;
                     dbias[1] += a1;
-                    if (p.flags & CB_DBG_NO_W_MFMA) {      // (timing-only build switch: wrong results)
+                    if (p.flags & CB_DBG_BITS & CB_DBG_NO_W_MFMA) {      // (timing-only build switch: wrong results)
                         acc[0][0][0] += a0 * cur.b[u][0] + a1 * cur.b[u][1] + cur.b[u][2] + cur.b[u][3];
                         continue;
                     }
@@ -691,7 +698,7 @@ __global__ void __launch_bounds__(512) conv_update_bwd_fused_kernel(const ConvBw
         for (int w = 0; w < 4; ++w) s += lds_wr[(w * 2 + which) * 64 + f];
         dst[64 * 128 + 64 + tid] = s;
     }
-    if ((p.flags & CB_DBG_CLOCK) && blockIdx.x == 0 && tid == 0) {
+    if ((p.flags & CB_DBG_BITS & CB_DBG_CLOCK) && blockIdx.x == 0 && tid == 0) {
         unsigned long long *out = reinterpret_cast<unsigned long long *>(p.dz);
         out[0] = __builtin_readcyclecounter() - clk0;
         out[1] = __builtin_amdgcn_s_memrealtime() - real0;
@@ -789,6 +796,11 @@ int32_t ultra_conv_update_backward(const void *x, const void *agg, const void *g
     if (!x || !agg || !grad_out || !weight || !grad_x || !grad_agg || !grad_weight || !workspace || rows <= 0 ||
         ((flags & CB_LN) && (!ln_weight || !ln_bias))) {
         set_error("ultra_conv_update_backward: NULL operand (or rows <= 0)");
+        return ULTRA_ERR_INVALID;
+    }
+    if (flags & ~(CB_LN | CB_RELU | CB_RESIDUAL | CB_DBG_BITS)) {
+        set_error("ultra_conv_update_backward: unknown flag bits " + std::to_string(flags & ~(CB_LN | CB_RELU | CB_RESIDUAL | CB_DBG_BITS)) +
+                  " (the CB_DBG_* measurement switches exist only in a -DULTRA_CONV_BWD_DEBUG=1 build)");
         return ULTRA_ERR_INVALID;
     }
     if (workspace_bytes < ultra_conv_update_backward_workspace(rows)) {

@@ -26,6 +26,13 @@
 
 namespace ultra {
 
+// CONV_DBG_NO_MATRIX (wrong results, for timing) reaches ultra_conv_update only in a -DULTRA_CONV_DEBUG=1 build
+// (tools/build_variant.py); elsewhere the entry point refuses every bit outside CONV_LN | CONV_RELU | CONV_RESIDUAL.
+#ifndef ULTRA_CONV_DEBUG
+#define ULTRA_CONV_DEBUG 0
+#endif
+constexpr int CONV_DBG_BITS = ULTRA_CONV_DEBUG ? CONV_DBG_NO_MATRIX : 0;
+
 struct ConvParams {
     const float *x;
     const float *agg;
@@ -126,7 +133,7 @@ __global__ void __launch_bounds__(512, 2) conv_update_kernel(const ConvParams p)
             swap32(bs[i].z, bs[i].w);   // .z: k pair s = 4 i + 1, .w: s = 4 i + 3
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (!(p.flags & CONV_DBG_NO_MATRIX))
+        if (!(p.flags & CONV_DBG_BITS & CONV_DBG_NO_MATRIX))
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const float4 b = bs[i];
@@ -523,6 +530,11 @@ int32_t ultra_conv_update(const void *x, const void *agg, const void *weight, co
     }
     if (!x || !agg || !weight || !out || rows < 0 || ((flags & CONV_LN) && (!ln_weight || !ln_bias))) {
         set_error("ultra_conv_update: NULL operand");
+        return ULTRA_ERR_INVALID;
+    }
+    if (flags & ~(CONV_LN | CONV_RELU | CONV_RESIDUAL | CONV_DBG_BITS)) {
+        set_error("ultra_conv_update: unknown flag bits " + std::to_string(flags & ~(CONV_LN | CONV_RELU | CONV_RESIDUAL | CONV_DBG_BITS)) +
+                  " (CONV_DBG_NO_MATRIX exists only in a -DULTRA_CONV_DEBUG=1 build)");
         return ULTRA_ERR_INVALID;
     }
     if (rows == 0) return ULTRA_OK;

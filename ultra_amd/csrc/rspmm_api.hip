@@ -879,6 +879,8 @@ static int layer0_impl(ultra_plan *p, const void *w, const ultra_mat *rel, const
     if (!p) return invalid("plan is NULL");
     (void)hipGetLastError();
     const bool only_fill = (flags & L0_ONLY_FILL) != 0;
+    if (flags & ~(L0_LN | L0_RELU | L0_RESIDUAL | L0_MAX | L0_ONLY_FILL | L0_SKIP_FILL))
+        return invalid("ultra_nbf_layer0: unknown flag bits " + std::to_string(flags & ~(L0_LN | L0_RELU | L0_RESIDUAL | L0_MAX | L0_ONLY_FILL | L0_SKIP_FILL)));
     if (only_fill && (flags & L0_SKIP_FILL)) return invalid("ultra_nbf_layer0: ULTRA_LAYER0_ONLY_FILL excludes ULTRA_LAYER0_SKIP_FILL");
     if (!out || !out->ptr || (!only_fill && (!src_rows || !weight))) return invalid("ultra_nbf_layer0: NULL operand");
     if ((flags & L0_LN) && (!ln_w || !ln_b)) return invalid("ultra_nbf_layer0: LayerNorm needs its weight and bias");
