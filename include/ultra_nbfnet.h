@@ -129,6 +129,19 @@ int32_t ultra_edge_keep_mask(const int64_t *head, const int64_t *tail, const int
 int32_t ultra_easy_edge_keep(const int64_t *head, const int64_t *tail, const int64_t *type, int64_t num_edge, const int64_t *h,
                              const int64_t *t, const int64_t *r, int64_t n_triple, int64_t stride, int64_t num_node,
                              int64_t num_rel, int64_t inverse_offset, void *keep, void *stream);
+/*
+ * ultra_easy_edge_keep for batches of ANY size (pre-training: 64 x 513 triples): the same operands and the same keep vector,
+ * the 2 n_triple keys hashed into an open-addressing table in global memory instead of LDS.  `workspace` holds the table:
+ * at least ultra_easy_edge_keep_table_workspace(n_triple) bytes of device memory (a power of two of >= 2 slots per key, 8 B
+ * each; -1 for a negative n_triple), 16-byte aligned.  Enqueues three kernels on `stream` (clear, insert, probe); no memset, no
+ * allocation, no host synchronisation, so the call records into a hipGraph.  Keys below zero are skipped, as in
+ * ultra_easy_edge_keep.
+ */
+int64_t ultra_easy_edge_keep_table_workspace(int64_t n_triple);
+int32_t ultra_easy_edge_keep_table(const int64_t *head, const int64_t *tail, const int64_t *type, int64_t num_edge,
+                                   const int64_t *h, const int64_t *t, const int64_t *r, int64_t n_triple, int64_t stride,
+                                   int64_t num_node, int64_t num_rel, int64_t inverse_offset, void *workspace,
+                                   int64_t workspace_bytes, void *keep, void *stream);
 
 /*
  * Boundary condition of EntityNBFNet (/root/reference/ultra/models.py:131-141) with the query gather fused:

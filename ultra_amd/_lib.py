@@ -112,6 +112,9 @@ def _load():
     lib.ultra_conv_update_backward.argtypes = [vp] * 14 + [i64, i64, i32, i32, ctypes.c_float, i32, vp]
     lib.ultra_edge_keep_mask.argtypes = [vp, vp, vp, i64, vp, i64, i64, i64, vp, vp]
     lib.ultra_easy_edge_keep.argtypes = [vp, vp, vp, i64, vp, vp, vp, i64, i64, i64, i64, i64, vp, vp]
+    lib.ultra_easy_edge_keep_table_workspace.argtypes = [i64]
+    lib.ultra_easy_edge_keep_table_workspace.restype = i64
+    lib.ultra_easy_edge_keep_table.argtypes = [vp, vp, vp, i64, vp, vp, vp, i64, i64, i64, i64, i64, vp, i64, vp, vp]
     lib.ultra_readout.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, i32, i32, vp]
     lib.ultra_stream_copy.argtypes = [vp, vp, i64, vp]
     lib.ultra_filtered_rank.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp, vp]

@@ -196,7 +196,128 @@ __global__ void __launch_bounds__(EASY_THREADS) easy_edge_keep_kernel(const long
     }
 }
 
+// The same vector for batches of any size (pre-training: 64 x 513 triples, 65,664 keys): the keys go into an open-addressing
+// table in GLOBAL memory -- a power of two of at least twice as many slots as keys, so a probe meets an empty slot within a
+// few steps -- that the caller owns (ultra_easy_edge_keep_table_workspace).  Three launches on one stream, none of which allocates
+// or synchronises with the host: one that empties the table (a kernel, not hipMemsetAsync: memset nodes captured into a hipGraph
+// replay wrongly once eager memsets interleave with the replays, rspmm_api.hip), one that inserts the keys (64-bit atomicCAS), one
+// that probes it once per edge.  The table is a set: which thread wins a slot changes where a key sits, never whether it is there.
+// Every probe sequence stops after one lap of the table, so no table content can keep a wave spinning.
+__device__ __forceinline__ unsigned long long table_slot(const unsigned long long key, const int log2_slots) {
+    return (key * 0x9E3779B97F4A7C15ull) >> (64 - log2_slots);
+}
+__global__ void __launch_bounds__(256) easy_table_clear_kernel(ulonglong2 *table, long long n16) {
+    const ulonglong2 empty = make_ulonglong2(~0ull, ~0ull);
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n16; i += (long long)gridDim.x * 256) table[i] = empty;
+}
+__global__ void __launch_bounds__(256) easy_table_insert_kernel(const long long *qh, const long long *qt, const long long *qr,
+                                                                long long n_triple, long long stride, long long num_node,
+                                                                long long num_rel, long long inverse_offset,
+                                                                unsigned long long *table, int log2_slots) {
+    constexpr unsigned long long EMPTY = ~0ull;
+    const unsigned long long mask = (1ull << log2_slots) - 1;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < 2 * n_triple; i += (long long)gridDim.x * 256) {
+        const bool inverse = i >= n_triple;
+        const long long j = inverse ? i - n_triple : i;
+        long long a = qh[j * stride], b = qt[j * stride];
+        if (inverse) {
+            const long long s = a;
+            a = b;
+            b = s;
+        }
+        long long key = a * num_node + b;
+        if (qr) key = key * num_rel + qr[j * stride] + (inverse ? inverse_offset : 0);
+        if (key < 0) continue;               // (no edge of a valid graph has a negative key)
+        unsigned long long slot = table_slot((unsigned long long)key, log2_slots);
+        for (unsigned long long lap = 0; lap <= mask; ++lap) {      // (a cleared table is at most half full: a few steps)
+            const unsigned long long old = atomicCAS(&table[slot], EMPTY, (unsigned long long)key);
+            if (old == EMPTY || old == (unsigned long long)key) break;
+            slot = (slot + 1) & mask;
+        }
+    }
+}
+__global__ void __launch_bounds__(256) easy_table_probe_kernel(const long long *head, const long long *tail, const long long *type,
+                                                               long long num_edge, long long num_node, long long num_rel,
+                                                               const unsigned long long *table, int log2_slots, float *keep) {
+    constexpr unsigned long long EMPTY = ~0ull;
+    const unsigned long long mask = (1ull << log2_slots) - 1;
+    for (long long e = blockIdx.x * 256ll + threadIdx.x; e < num_edge; e += (long long)gridDim.x * 256) {
+        long long key = head[e] * num_node + tail[e];
+        if (type) key = key * num_rel + type[e];
+        unsigned long long slot = table_slot((unsigned long long)key, log2_slots);
+        float k = 1.f;
+        for (unsigned long long lap = 0; lap <= mask; ++lap) {
+            const unsigned long long seen = table[slot];
+            if (seen == EMPTY) break;
+            if (seen == (unsigned long long)key) {
+                k = 0.f;
+                break;
+            }
+            slot = (slot + 1) & mask;
+        }
+        keep[e] = k;
+    }
+}
+
+// log2 of the table's slots for n_triple triples: >= 2 slots per key (2 n_triple keys), at least 1,024 slots
+static int easy_table_log2_slots(const long long n_triple) {
+    int lg = 10;
+    while ((1ll << lg) < 4 * n_triple) ++lg;
+    return lg;
+}
+
 }  // namespace ultra
+
+extern "C" int64_t ultra_easy_edge_keep_table_workspace(int64_t n_triple) {
+    if (n_triple < 0 || n_triple > (1ll << 40)) return -1;
+    return (int64_t)8 << ultra::easy_table_log2_slots(n_triple);
+}
+
+extern "C" int32_t ultra_easy_edge_keep_table(const int64_t *head, const int64_t *tail, const int64_t *type, int64_t num_edge,
+                                              const int64_t *h, const int64_t *t, const int64_t *r, int64_t n_triple,
+                                              int64_t stride, int64_t num_node, int64_t num_rel, int64_t inverse_offset,
+                                              void *workspace, int64_t workspace_bytes, void *keep, void *stream) {
+    ULTRA_DEVICE_SCOPE(stream, keep);
+    if (!head || !tail || !keep || !workspace || num_edge < 0 || n_triple < 0 || n_triple > (1ll << 40) ||
+        (n_triple > 0 && (!h || !t)) || stride <= 0 || num_node <= 0 || (type && (num_rel <= 0 || !r))) {
+        ultra::set_error("ultra_easy_edge_keep_table: NULL operand or empty key space");
+        return ULTRA_ERR_INVALID;
+    }
+    const int log2_slots = ultra::easy_table_log2_slots(n_triple);
+    const long long table_bytes = 8ll << log2_slots;
+    if (workspace_bytes < table_bytes || (reinterpret_cast<uintptr_t>(workspace) & 15)) {
+        ultra::set_error("ultra_easy_edge_keep_table: workspace smaller than ultra_easy_edge_keep_table_workspace(n_triple) or "
+                         "not 16-byte aligned");
+        return ULTRA_ERR_INVALID;
+    }
+    if (num_edge == 0) return ULTRA_OK;
+    (void)hipGetLastError();   // drop any stale error left by other users of the runtime
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    {
+        const long long n16 = table_bytes / 16;           // every slot EMPTY (~0)
+        const unsigned blocks = (unsigned)((n16 + 255) / 256 < 1024 ? (n16 + 255) / 256 : 1024);
+        hipLaunchKernelGGL(ultra::easy_table_clear_kernel, dim3(blocks), dim3(256), 0, s, (ulonglong2 *)workspace, n16);
+    }
+    if (n_triple > 0) {
+        const long long want = (2 * n_triple + 255) / 256;
+        const unsigned blocks = (unsigned)(want < 2048 ? want : 2048);
+        hipLaunchKernelGGL(ultra::easy_table_insert_kernel, dim3(blocks), dim3(256), 0, s, (const long long *)h,
+                           (const long long *)t, type ? (const long long *)r : (const long long *)nullptr, (long long)n_triple,
+                           (long long)stride, (long long)num_node, (long long)num_rel, (long long)inverse_offset,
+                           (unsigned long long *)workspace, log2_slots);
+    }
+    const long long want = (num_edge + 255) / 256;
+    const unsigned blocks = (unsigned)(want < 4096 ? want : 4096);
+    hipLaunchKernelGGL(ultra::easy_table_probe_kernel, dim3(blocks), dim3(256), 0, s, (const long long *)head,
+                       (const long long *)tail, (const long long *)type, (long long)num_edge, (long long)num_node,
+                       (long long)num_rel, (const unsigned long long *)workspace, log2_slots, (float *)keep);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        ultra::set_error(std::string("easy_table kernels launch: ") + hipGetErrorString(e));
+        return ULTRA_ERR_HIP;
+    }
+    return ULTRA_OK;
+}
 
 extern "C" int32_t ultra_easy_edge_keep(const int64_t *head, const int64_t *tail, const int64_t *type, int64_t num_edge,
                                         const int64_t *h, const int64_t *t, const int64_t *r, int64_t n_triple, int64_t stride,

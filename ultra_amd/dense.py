@@ -287,6 +287,38 @@ def easy_edge_keep(edge_index, edge_type, h_index, t_index, r_index, num_node, n
     return keep if dtype == torch.float32 else keep.to(dtype)
 
 
+def easy_edge_keep_table(edge_index, edge_type, h_index, t_index, r_index, num_node, num_relation, dtype=torch.float32):
+    """easy_edge_keep for batches of any size (ultra_easy_edge_keep_table: the keys in a hash table in global memory, three
+    launches -- clear, insert, probe --, no host synchronisation -- it records into a captured step).  The table is the caller's: allocated here
+    from torch's caching allocator, so under a capture it comes from the graph's pool.  h / t / r: equally shaped int64 GPU
+    tensors (columns of a contiguous (..., 3) tensor or contiguous themselves, copied otherwise); None where the key space
+    does not fit (the caller falls back to tasks.edge_match)."""
+    n = h_index.numel()
+    if not (edge_index.is_cuda and edge_index.dtype == torch.int64 and h_index.dtype == torch.int64 and h_index.is_cuda
+            and h_index.shape == t_index.shape == r_index.shape
+            and int(num_node) ** 2 * max(int(num_relation), 1) < 2 ** 62):
+        return None
+    want = tuple(3 * s for s in torch.empty(h_index.shape, device="meta").stride())
+    if h_index.is_contiguous() and t_index.is_contiguous() and r_index.is_contiguous():
+        stride = 1
+    elif h_index.stride() == t_index.stride() == r_index.stride() == want:
+        stride = 3
+    else:
+        h_index, t_index, r_index = h_index.contiguous(), t_index.contiguous(), r_index.contiguous()
+        stride = 1
+    edge_index = edge_index.contiguous()
+    if edge_type is not None:
+        edge_type = edge_type.contiguous()
+    table = torch.empty(int(lib.ultra_easy_edge_keep_table_workspace(n)), dtype=torch.uint8, device=edge_index.device)
+    keep = torch.empty(edge_index.shape[1], dtype=torch.float32, device=edge_index.device)
+    check(lib.ultra_easy_edge_keep_table(edge_index[0].data_ptr(), edge_index[1].data_ptr(), _ptr(edge_type),
+                                         edge_index.shape[1], h_index.data_ptr(), t_index.data_ptr(),
+                                         r_index.data_ptr() if edge_type is not None else None, n, stride, int(num_node),
+                                         int(num_relation), int(num_relation) // 2, table.data_ptr(), table.numel(),
+                                         keep.data_ptr(), _stream(keep)))
+    return keep if dtype == torch.float32 else keep.to(dtype)
+
+
 def readout_supported(model, hidden):
     mlp = model.mlp
     return (hidden.is_cuda and hidden.dtype == torch.float32 and hidden.shape[-1] == 64 and not model.concat_hidden

@@ -29,6 +29,9 @@ RELATION_PROJECTION_NODE = True
 # the training step's 0/1 edge vector straight from the batch's triples (dense.easy_edge_keep; A/B switch for tests: off = the
 # list of easy edges, its sorted keys and dense.edge_keep_mask)
 EASY_EDGE_KEEP_KERNEL = True
+# ... and for the batches neither of the LDS routes takes (> 8,192 keys): dense.easy_edge_keep_table (A/B switch for tests: off =
+# tasks.edge_match, a host synchronisation)
+EASY_EDGE_TABLE_KERNEL = True
 
 
 class NotOnFusedPath(RuntimeError):
@@ -98,6 +101,13 @@ class BaseNBFNet(nn.Module):
                                         data.num_nodes, data.num_relations, dtype)
             # (one vector for every layer's forward and backward walks of this step: permuted into each plan's order once)
             return rspmm.tag_edge_weight(keep)
+        if EASY_EDGE_TABLE_KERNEL and data.edge_index.is_cuda:
+            # batches above both LDS routes' 8,192 keys (pre-training's 64 x 513): the keys in a global hash table, no host
+            # synchronisation (edge_match reads its match count back, which no captured step can do)
+            keep = dense.easy_edge_keep_table(data.edge_index, None if self.remove_one_hop else data.edge_type, h_index,
+                                              t_index, r_index, data.num_nodes, data.num_relations, dtype)
+            if keep is not None:
+                return rspmm.tag_edge_weight(keep)
         return self.easy_edge_mask(data, h_index, t_index, r_index).to(dtype)
 
     def remove_easy_edges(self, data, h_index, t_index, r_index=None):

@@ -15,6 +15,7 @@ SHAPES = {
     "fb15k237": dict(num_node=14541, num_triple=272115, num_relation_base=237, num_test=20466),
     "wn18rr": dict(num_node=40943, num_triple=86835, num_relation_base=11, num_test=3134),
     "codex_l": dict(num_node=77951, num_triple=551193, num_relation_base=69, num_test=30622),
+    "codex_m": dict(num_node=17050, num_triple=185584, num_relation_base=51, num_test=10311),
     "yago310": dict(num_node=123182, num_triple=1079040, num_relation_base=37, num_test=5000),
 }
 
@@ -43,6 +44,32 @@ def make_kg(num_node, num_triple, num_relation_base, num_test=None, seed=1234, r
     if relation_graph:
         tasks.build_relation_graph(data)
     return data
+
+
+def make_split(num_node, num_triple, num_relation_base, num_valid=None, num_test=None, seed=1234, relation_graph=True):
+    """A transductive dataset in the reference's three-split layout (datasets.py:186-205), without data on disk: (train, valid,
+    test) graphs that share one fact graph -- the training triples and their inverses -- and whose targets are the training,
+    validation and test triples.  Seeded by its own generator (the global one is left alone)."""
+    g = torch.Generator().manual_seed(seed)
+    if num_valid is None:
+        num_valid = max(8, min(num_triple // 10, 4096))
+    if num_test is None:
+        num_test = num_valid
+    h, t, r = _draw(g, num_node, num_relation_base, num_triple + num_valid + num_test)
+    edge_index = torch.stack([torch.cat([h[:num_triple], t[:num_triple]]), torch.cat([t[:num_triple], h[:num_triple]])])
+    edge_type = torch.cat([r[:num_triple], r[:num_triple] + num_relation_base])
+    rel_graph = None
+    splits = []
+    for lo, hi in ((0, num_triple), (num_triple, num_triple + num_valid), (num_triple + num_valid, len(h))):
+        data = Data(edge_index=edge_index, edge_type=edge_type, num_nodes=num_node, num_relations=2 * num_relation_base,
+                    target_edge_index=torch.stack([h[lo:hi], t[lo:hi]]), target_edge_type=r[lo:hi],
+                    target_triples=torch.stack([h[lo:hi], t[lo:hi], r[lo:hi]], dim=-1))
+        if relation_graph:
+            if rel_graph is None:
+                rel_graph = tasks.build_relation_graph(data).relation_graph
+            data.relation_graph = rel_graph
+        splits.append(data)
+    return tuple(splits)
 
 
 def to_device(data, device):

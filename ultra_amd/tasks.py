@@ -210,12 +210,25 @@ def prefetch_negatives(batches, data, num_negative, strict=True):
     (script/run.py:32-34 keeps train_triplets on the device) -- are ordered in front of the sampler that reads the batch,
     instead of behind the previous step's backward on the training stream (where the sampler would read the batch before it
     is written: ADVICE r5).  What the iterable READS must be complete when the loop starts (the triple list is static).
-    A graph on the CPU: the plain loop, unchanged."""
+    A graph on the CPU: the plain loop, unchanged.
+
+    Several graphs (multi-graph pre-training, script/pretrain.py:81-84): `data` a list of graphs, and every item of `batches` a
+    (graph id, positives) pair -- the graph changes from step to step; each batch's negatives are drawn against its own graph,
+    and (graph id, batch) pairs come out."""
     it = iter(batches)
-    dev = data.edge_index.device
+    multi = isinstance(data, (list, tuple))
+    dev = (data[0] if multi else data).edge_index.device
+
+    def draw(item, to=None):
+        gid, batch = item if multi else (None, item)
+        if to is not None:
+            batch = batch.to(to, non_blocking=True)
+        out = negative_sampling(data[gid] if multi else data, batch, num_negative, strict=strict)
+        return (gid, out) if multi else out
+
     if dev.type != "cuda":
-        for batch in it:
-            yield negative_sampling(data, batch, num_negative, strict=strict)
+        for item in it:
+            yield draw(item)
         return
     with torch.cuda.device(dev):
         side = overlapping_stream(dev)
@@ -224,8 +237,7 @@ def prefetch_negatives(batches, data, num_negative, strict=True):
 
     def sample():
         with torch.cuda.stream(side):
-            batch = next(it)            # (StopIteration passes through)
-            return negative_sampling(data, batch.to(dev, non_blocking=True), num_negative, strict=strict)
+            return draw(next(it), to=dev)       # (StopIteration passes through)
 
     try:
         ahead = sample()
@@ -244,7 +256,7 @@ def prefetch_negatives(batches, data, num_negative, strict=True):
     while ahead is not None:
         main = torch.cuda.current_stream(dev)
         main.wait_stream(side)
-        ahead.record_stream(main)        # (allocated on the side stream, read by the step on the training stream)
+        (ahead[1] if multi else ahead).record_stream(main)     # (allocated on the side stream, read by the step on the training stream)
         current, ahead = ahead, None
         yield current                    # the caller enqueues its step ...
         behind_step = None
