@@ -9,7 +9,7 @@
  * Semantics (rspmm.cpp:50-75, operator.cuh:13-80):
  *   out[row, d] = NARY_{e : edge_index[0][e] == row}  w[e] * BINARY(rel[edge_type[e], d], in[edge_index[1][e], d])
  *   NARY in {add, min, max} with identity 0 / +MAX / -MAX (empty rows keep the identity),
- *   BINARY in {mul (DistMult), add (TransE)};  dtype float32 or float64.
+ *   BINARY in {mul (DistMult), add (TransE), rotate (RotatE, see ultra_mul)};  dtype float32 or float64.
  *
  * Plain pointers and sizes only -- no torch types.  All `*_dev` pointers are device (HBM) addresses
  * on the current HIP device, `*_host` pointers are host addresses.  Every function returns 0 on
@@ -44,7 +44,31 @@ typedef enum {
 } ultra_status;
 
 typedef enum { ULTRA_SUM_ADD = 0, ULTRA_SUM_MIN = 1, ULTRA_SUM_MAX = 2 } ultra_sum;   /* operator.cuh:43-80 */
-typedef enum { ULTRA_MUL_MUL = 0, ULTRA_MUL_ADD = 1 } ultra_mul;                     /* operator.cuh:13-41 */
+typedef enum { ULTRA_MUL_MUL = 0, ULTRA_MUL_ADD = 1, ULTRA_MUL_ROTATE = 2 } ultra_mul;   /* operator.cuh:13-41; rotate: below */
+/*
+ * ULTRA_MUL_ROTATE -- the RotatE message of the reference LAYER (ultra/layers.py:142-147; its rspmm extension has no such
+ * kernel).  A row of row_len = 2 h elements is ONE complex vector, real half [0, h) | imaginary half [h, 2 h), and the
+ * message is the complex product of the source row with the relation row:
+ *     ROT(r, x)[d]     = x[d] * r[d]     - x[d + h] * r[d + h]        d in [0, h)
+ *     ROT(r, x)[d + h] = x[d] * r[d + h] + x[d + h] * r[d]
+ *     out[row] = NARY_{e : row_e == row}  w_e * ROT(rel[type_e], in[col_e])
+ * Both products and their sum / difference round separately (no fma), as torch does on the CPU.  The halves are those of one
+ * row of one outer slice of an ultra_mat: in the 2-D reference layout (N, D) the WHOLE row is one complex vector, so batched
+ * callers pass the batch-major 3-D operands (n_outer = batch, row_len = dim).  Odd row_len: ULTRA_ERR_INVALID.
+ * Served by ultra_rspmm_forward / _forward_masked / _forward_point / _forward_timed and ultra_rspmm_backward / _backward_add,
+ * for add, min and max, fp32 and fp64, with the identities, empty-row rule, boundary fusion and keep-mask rule of the other
+ * operators; every other entry that takes a `mul` answers ULTRA_ERR_INVALID, and the twelve reference-shaped entries below
+ * have no rotate twin.  Plans: the sparse format, re-associating or ULTRA_PLAN_EXACT_ORDER (walked by one 16-lane group per row
+ * in sorted edge order, chain rows included; ULTRA_PLAN_TYPE_RUNS / ULTRA_PLAN_DENSE: ULTRA_ERR_UNSUPPORTED).  A point boundary
+ * is served under add; under min / max it answers ULTRA_ERR_UNSUPPORTED (pass the boundary as a tensor).
+ * Rows of exactly 64 elements with 16-byte aligned operands take the fast path (one 16-byte gather per lane and edge, the other
+ * half by a lane exchange); every other even row length loads the partner half a second time.
+ * Backward, with g = w_e * output_grad[row_e] (min / max: per ELEMENT, where the weighted message ties with the output):
+ *     input_grad[col_e] += ROT(conj(rel[type_e]), g)     relation_grad[type_e] += ROT(conj(in[col_e]), g)
+ *     weight_grad[e] = sum_d output_grad[row_e, d] * [tie] * ROT(rel[type_e], in[col_e])[d]
+ * EVERY rotate backward route is a gather in a fixed order without atomics (add: re-runs of the forward walk on the transposed
+ * and relation-major plans; min / max: a gather kernel that serves any even row length and alignment): the same bits run to run.
+ */
 typedef enum { ULTRA_F32 = 0, ULTRA_F64 = 1 } ultra_dtype;                           /* AT_DISPATCH_FLOATING_TYPES, rspmm.cpp:148 */
 
 /*
@@ -347,6 +371,9 @@ int32_t ultra_rspmm_onehot_backward(const int64_t *out_ptr_dev, const int64_t *o
  * NULL to skip), relation and input, given the forward output and its gradient.  min/max give the
  * full gradient to every tying edge (operator.cuh:62-64,75-77).
  * relation_grad / input_grad are overwritten (the reference returns fresh zeros_like + accumulation).
+ * Run to run: under add both gradients are atomics-free re-runs of the forward walk (reproducible); under min / max the
+ * gather route (whole 16-byte chunks; ULTRA_MUL_ROTATE: always) is reproducible, the scatter with float atomics that serves
+ * unaligned or odd-length mul / add rows is not.
  * input_grad may be NULL under sum == add: the input gradient is then left to the caller -- it is an rspmm forward over
  * the transposed graph (rspmm.cpp:110-112), which a graph with a dense-format twin runs on the matrix cores instead.
  */

@@ -22,7 +22,7 @@ ULTRA_ERR_HIP = 3
 ULTRA_ERR_UNSUPPORTED = 4
 
 SUM_CODES = {"add": 0, "min": 1, "max": 2}
-MUL_CODES = {"mul": 0, "add": 1}
+MUL_CODES = {"mul": 0, "add": 1, "rotate": 2}      # rotate: ULTRA_MUL_ROTATE (the plan API only)
 F32, F64 = 0, 1
 
 ARR_ROW_PTR, ARR_COL, ARR_TYPE, ARR_PERM, ARR_ITEM, ARR_SPLIT_ROW, ARR_SPLIT_PTR = range(7)

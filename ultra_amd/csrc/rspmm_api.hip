@@ -322,11 +322,15 @@ static int forward_impl(ultra_plan *p, int sum, int mul, int dtype, const void *
     if (!p) return invalid("plan is NULL");
     (void)hipGetLastError();   // drop any stale error left by other users of the HIP runtime
     if (int derr = take_device_error()) return derr;   // (an earlier launch ended on a bounded wait: say so now)
-    if (sum < 0 || sum > 2 || mul < 0 || mul > 3) return invalid("unknown sum/mul code");
+    // (mul: an internal BIN_* code -- the public entries have mapped ULTRA_MUL_ROTATE to BIN_ROT)
+    const bool rot = mul >= BIN_ROT && mul <= BIN_ROT_CX;
+    if (sum < 0 || sum > 2 || mul < 0 || (mul > 3 && !rot)) return invalid("unknown sum/mul code");
+    if (rot && mul != BIN_ROT && sum != ULTRA_SUM_ADD) return invalid("unknown sum/mul code");
     if (dtype != ULTRA_F32 && dtype != ULTRA_F64) return invalid("dtype must be ULTRA_F32 or ULTRA_F64");
     if (!out || !out->ptr) return invalid("output is NULL");
     const int64_t n_outer = out->n_outer, row_len = out->row_len;
     if (n_outer <= 0 || row_len <= 0) return invalid("output: empty n_outer / row_len");
+    if (rot && (row_len & 1)) return invalid("rotate: row_len must be even (a row is real half | imaginary half)");
     int rc;
     if ((rc = check_mat(out, "output", p->num_out, n_outer, row_len))) return rc;
     if (mul != BIN_RHS && (rc = check_mat(rel, "relation", p->num_rel, n_outer, row_len))) return rc;
@@ -346,6 +350,10 @@ static int forward_impl(ultra_plan *p, int sum, int mul, int dtype, const void *
         set_error("a point boundary under min / max is served by reference-order plans in the sparse format only");
         return ULTRA_ERR_UNSUPPORTED;
     }
+    if (rot && (p->flags & ULTRA_PLAN_DENSE)) {
+        set_error("rotate messages are served by the plans in the sparse format");
+        return ULTRA_ERR_UNSUPPORTED;
+    }
     if (p->flags & ULTRA_PLAN_DENSE) {
         if (g_ev_before) HIP_TRY(hipEventRecord(g_ev_before, stream));
         if ((rc = launch_dense_forward(p, sum, mul, dtype, w, rel, x, bnd, bnd_rows, out, stream))) return rc;
@@ -361,8 +369,13 @@ static int forward_impl(ultra_plan *p, int sum, int mul, int dtype, const void *
     if (mul != BIN_RHS) vec4 = vec4 && mat_vec_ok(rel, step);
     if (mul != BIN_LHS) vec4 = vec4 && mat_vec_ok(x, step);
     if (bnd) vec4 = vec4 && mat_vec_ok(bnd, step);
+    // rotate: a lane's 16-byte chunk and its partner's (row_len / 2 elements away) lie in ONE half each
+    if (rot) vec4 = vec4 && (row_len % 8 == 0);
     const int VEC = vec4 ? 4 : 1;
     const int SPAN = 16 * VEC;
+    // ... and a row of exactly one span has its halves in lanes 0-7 | 8-15 of a group: the partner comes by a lane exchange.
+    // Every other row length loads it (the BIN_ROTG* kernels, operands through L2).
+    const bool rot_far = rot && !(VEC == 4 && row_len == SPAN);
 
     FwdParams fp;
     std::memset(&fp, 0, sizeof(fp));
@@ -407,9 +420,12 @@ static int forward_impl(ultra_plan *p, int sum, int mul, int dtype, const void *
     }
     if (mul != BIN_LHS) fp.x_row_bytes = (uint32_t)(x->stride_row * (int64_t)esz);
     if (mul != BIN_RHS) fp.rel_row_bytes = (uint32_t)(rel->stride_row * (int64_t)esz);
+    fp.rot_half_bytes = (uint32_t)((row_len / 2) * (int64_t)esz);
 
     // ---- reference-order plans: the order kernels (no scratch, no fix-up launch) ----
-    if ((p->flags & ULTRA_PLAN_EXACT_ORDER) && VEC == 4 && g_tuning.reserved[0] == 0 && p->num_in < (1 << 24) &&
+    // (rotate: reference-order plans are walked by the general kernel below -- one 16-lane group per row, chain rows included,
+    // in sorted edge order; the order kernels and their generated walks serve mul / add)
+    if ((p->flags & ULTRA_PLAN_EXACT_ORDER) && !rot && VEC == 4 && g_tuning.reserved[0] == 0 && p->num_in < (1 << 24) &&
         p->num_rel < (1 << 24) && (mul == BIN_LHS || x->stride_row * (int64_t)esz < (1 << 24)) &&
         (mul == BIN_RHS || rel->stride_row * (int64_t)esz < (1 << 24))) {
         // (+ one row: the stream walk's row markers carry relation index num_rel)
@@ -594,7 +610,7 @@ static int forward_impl(ultra_plan *p, int sum, int mul, int dtype, const void *
     const size_t rel_bytes = (mul != BIN_RHS) ? (size_t)p->num_rel * SPAN * esz : 0;
     const size_t x_bytes = (mul != BIN_LHS) ? (size_t)p->num_in * SPAN * esz : 0;
     int mode = MODE_GLOBAL;
-    if (VEC == 4) {
+    if (VEC == 4 && !rot_far) {
         if (g_tuning.x_lds != 0 && g_tuning.rel_lds != 0 && rel_bytes + x_bytes <= budget && x_bytes > 0)
             mode = MODE_ALL_LDS;
         else if (g_tuning.rel_lds != 0 && rel_bytes <= budget && rel_bytes > 0)
@@ -609,7 +625,20 @@ static int forward_impl(ultra_plan *p, int sum, int mul, int dtype, const void *
 
     hipError_t e = hipErrorInvalidValue;
     if (g_ev_before) HIP_TRY(hipEventRecord(g_ev_before, stream));
-    if (dtype == ULTRA_F32) {
+    if (rot) {
+        const int rmul = rot_far ? mul + (BIN_ROTG - BIN_ROT) : mul;
+        if (dtype == ULTRA_F32) {
+            if (VEC == 1) e = launch_rot_variant<float, 1, 0>(sum, rmul, fp, grid, threads, lds, stream);
+            else if (mode == 0) e = launch_rot_variant<float, 4, 0>(sum, rmul, fp, grid, threads, lds, stream);
+            else if (mode == 1) e = launch_rot_variant<float, 4, 1>(sum, rmul, fp, grid, threads, lds, stream);
+            else e = launch_rot_variant<float, 4, 2>(sum, rmul, fp, grid, threads, lds, stream);
+        } else {
+            if (VEC == 1) e = launch_rot_variant<double, 1, 0>(sum, rmul, fp, grid, threads, lds, stream);
+            else if (mode == 0) e = launch_rot_variant<double, 4, 0>(sum, rmul, fp, grid, threads, lds, stream);
+            else if (mode == 1) e = launch_rot_variant<double, 4, 1>(sum, rmul, fp, grid, threads, lds, stream);
+            else e = launch_rot_variant<double, 4, 2>(sum, rmul, fp, grid, threads, lds, stream);
+        }
+    } else if (dtype == ULTRA_F32) {
         if (VEC == 1) e = launch_fwd_variant<float, 1, 0>(sum, mul, fp, grid, threads, lds, stream);
         else if (mode == 0) e = launch_fwd_variant<float, 4, 0>(sum, mul, fp, grid, threads, lds, stream);
         else if (mode == 1) e = launch_fwd_variant<float, 4, 1>(sum, mul, fp, grid, threads, lds, stream);
@@ -691,11 +720,13 @@ static int backward_impl(ultra_plan *p, int sum, int mul, int dtype, const void 
     if (xbase && (sum != ULTRA_SUM_ADD || !xgrad)) return invalid("input_grad_base is served under sum == add, with an input_grad");
     (void)hipGetLastError();
     if (p->flags & ULTRA_PLAN_DENSE) return invalid("a ULTRA_PLAN_DENSE plan has no backward; use the (row, col) plan");
-    if (sum < 0 || sum > 2 || mul < 0 || mul > 1) return invalid("unknown sum/mul code");
+    if (sum < 0 || sum > 2 || mul < 0 || mul > ULTRA_MUL_ROTATE) return invalid("unknown sum/mul code");
+    const bool rot = mul == ULTRA_MUL_ROTATE;
     if (dtype != ULTRA_F32 && dtype != ULTRA_F64) return invalid("dtype must be ULTRA_F32 or ULTRA_F64");
     if (!og || !og->ptr) return invalid("output_grad is NULL");
     const int64_t n_outer = og->n_outer, row_len = og->row_len;
     if (n_outer <= 0 || row_len <= 0) return invalid("output_grad: empty n_outer / row_len");   // (as the forward: rspmm.cpp's checkSize)
+    if (rot && (row_len & 1)) return invalid("rotate: row_len must be even (a row is real half | imaginary half)");
     int rc;
     if ((rc = check_mat(rel, "relation", p->num_rel, n_outer, row_len))) return rc;
     if ((rc = check_mat(x, "input", p->num_in, n_outer, row_len))) return rc;
@@ -740,16 +771,75 @@ static int backward_impl(ultra_plan *p, int sum, int mul, int dtype, const void 
     if (sum == ULTRA_SUM_ADD) {
         if ((rc = ensure_backward_plans(p))) return rc;
         // input_grad[col] = sum_e w * d(rel (x) in)/d in * out_grad[row]   (rspmm.cpp:110-112)
-        if (xgrad && (rc = forward_impl(p->tplan, ULTRA_SUM_ADD, mul == ULTRA_MUL_MUL ? BIN_MUL : BIN_RHS, dtype, w, rel, og,
-                                        xbase, xgrad, stream)))
+        // rotate: ROT(conj(rel), out_grad) -- the same walk with the relation operand conjugated
+        if (xgrad && (rc = forward_impl(p->tplan, ULTRA_SUM_ADD, rot ? BIN_ROT_CREL : mul == ULTRA_MUL_MUL ? BIN_MUL : BIN_RHS, dtype,
+                                        w, rel, og, xbase, xgrad, stream)))
             return rc;
         // relation_grad[type] = sum_e w * d(rel (x) in)/d rel * out_grad[row]   (rspmm.cpp:106-108)
-        if ((rc = forward_impl(p->rplan, ULTRA_SUM_ADD, mul == ULTRA_MUL_MUL ? BIN_MUL : BIN_LHS, dtype, w, og, x,
+        // rotate: ROT(conj(input), out_grad), out_grad in the relation operand's place
+        if ((rc = forward_impl(p->rplan, ULTRA_SUM_ADD, rot ? BIN_ROT_CX : mul == ULTRA_MUL_MUL ? BIN_MUL : BIN_LHS, dtype, w, og, x,
                                nullptr, rgrad, stream)))
             return rc;
         if (wgrad && p->num_edge > 0) {
-            if ((rc = launch_edge_kernel(dtype, vec4 ? 4 : 1, sum, mul, /*want_ri=*/false, ep, stream))) return rc;
+            if (rot) {
+                if ((rc = launch_rot_edge_kernel(dtype, sum, /*want_ri=*/false, ep, stream))) return rc;
+            } else if ((rc = launch_edge_kernel(dtype, vec4 ? 4 : 1, sum, mul, /*want_ri=*/false, ep, stream))) {
+                return rc;
+            }
         }
+        return ULTRA_OK;
+    }
+    // rotate under min / max: the gather below on its own kernel -- 16 complex elements a span, scalar loads, so EVERY even row
+    // length and alignment takes it (no atomics on any route: the same bits run to run)
+    if (rot && p->num_edge > 0) {
+        if ((rc = ensure_backward_plans(p))) return rc;
+        const bool fix4 = (row_len % 4 == 0) && mat_vec_ok(rgrad, step) && mat_vec_ok(xgrad, step);
+        for (int which = 0; which < 2; ++which) {
+            ultra_plan *q = which == 0 ? p->tplan : p->rplan;
+            const ultra_mat *dst = which == 0 ? xgrad : rgrad;
+            if ((rc = upload_plan(q))) return rc;
+            if (q->n_slot > 0 &&
+                (rc = ensure_scratch(&q->d.partial, &q->d.partial_bytes, (size_t)q->n_slot * n_outer * row_len * esz, q)))
+                return rc;
+            GatherBwdParams gp;
+            std::memset(&gp, 0, sizeof(gp));
+            gp.items = q->d.items;
+            gp.n_item = (int32_t)q->items.size();
+            gp.col = q->d.col, gp.type = q->d.type, gp.perm = q->d.perm;
+            gp.w = w;
+            gp.rel = ep.rel, gp.x = ep.x, gp.out = ep.out, gp.og = ep.og;
+            gp.grad = dst->ptr, gp.grad_so = dst->stride_outer, gp.grad_sr = dst->stride_row;
+            gp.partial = q->d.partial;
+            gp.n_outer = (int32_t)n_outer, gp.row_len = (int32_t)row_len;
+            gp.spans_per_outer = (int32_t)((row_len / 2 + 15) / 16);
+            gp.n_span = gp.spans_per_outer * gp.n_outer;
+            const int grid = 2048;
+            gp.smod = std::min<int32_t>(gp.n_span, grid);
+            gp.nparts = grid / gp.smod;
+            const hipError_t e = dtype == ULTRA_F32 ? launch_rot_gather_bwd_t<float>(sum, which == 1, gp, grid, stream)
+                                                    : launch_rot_gather_bwd_t<double>(sum, which == 1, gp, grid, stream);
+            if (e != hipSuccess) return hip_fail(e, "rspmm_rot_minmax_bwd_gather_kernel launch");
+            if (!q->split_row.empty()) {
+                FixupParams xp;
+                std::memset(&xp, 0, sizeof(xp));
+                xp.split_row = q->d.split_row, xp.split_ptr = q->d.split_ptr;
+                xp.n_split = (int32_t)q->split_row.size();
+                xp.partial = q->d.partial;
+                xp.out = dst->ptr, xp.out_stride_outer = dst->stride_outer, xp.out_stride_row = dst->stride_row;
+                xp.n_outer = gp.n_outer, xp.row_len = gp.row_len;
+                const long long total = (long long)xp.n_split * n_outer * (row_len / (fix4 ? 4 : 1));
+                const int blocks = (int)std::min<long long>((total + 15) / 16, 16384);
+                if (dtype == ULTRA_F32) {
+                    if (fix4) hipLaunchKernelGGL((rspmm_fixup_kernel<float, 4, 0>), dim3(blocks), dim3(256), 0, stream, xp);
+                    else hipLaunchKernelGGL((rspmm_fixup_kernel<float, 1, 0>), dim3(blocks), dim3(256), 0, stream, xp);
+                } else {
+                    if (fix4) hipLaunchKernelGGL((rspmm_fixup_kernel<double, 4, 0>), dim3(blocks), dim3(256), 0, stream, xp);
+                    else hipLaunchKernelGGL((rspmm_fixup_kernel<double, 1, 0>), dim3(blocks), dim3(256), 0, stream, xp);
+                }
+                HIP_TRY(hipGetLastError());
+            }
+        }
+        if (wgrad && (rc = launch_rot_edge_kernel(dtype, sum, /*want_ri=*/false, ep, stream))) return rc;
         return ULTRA_OK;
     }
     // min / max: gradient flows to every edge whose message equals the output (operator.cuh:62-64,75-77).  With whole
@@ -806,7 +896,7 @@ static int backward_impl(ultra_plan *p, int sum, int mul, int dtype, const void 
     }
     if ((rc = launch_fill_zero(dtype, rgrad, p->num_rel, stream))) return rc;
     if ((rc = launch_fill_zero(dtype, xgrad, p->num_in, stream))) return rc;
-    if (p->num_edge > 0) {
+    if (p->num_edge > 0 && !rot) {
         if ((rc = launch_edge_kernel(dtype, vec4 ? 4 : 1, sum, mul, /*want_ri=*/true, ep, stream))) return rc;
     }
     (void)esz;
@@ -1034,7 +1124,8 @@ int32_t ultra_rspmm_forward(ultra_plan *plan, int32_t sum, int32_t mul, int32_t 
                             const ultra_mat *output, void *stream) {
     ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);
     WeightEpochScope weight_epoch_scope;
-    if (mul < 0 || mul > 1) return invalid("unknown mul code");
+    if (mul < 0 || mul > ULTRA_MUL_ROTATE) return invalid("unknown mul code");
+    if (mul == ULTRA_MUL_ROTATE) mul = BIN_ROT;
     return forward_impl(plan, sum, mul, dtype, edge_weight_dev, relation, input, boundary, output,
                         reinterpret_cast<hipStream_t>(stream));
 }
@@ -1044,7 +1135,8 @@ int32_t ultra_rspmm_forward_masked(ultra_plan *plan, int32_t sum, int32_t mul, i
                                    const ultra_mat *output, void *stream) {
     ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);
     WeightEpochScope weight_epoch_scope;
-    if (mul < 0 || mul > 1) return invalid("unknown mul code");
+    if (mul < 0 || mul > ULTRA_MUL_ROTATE) return invalid("unknown mul code");
+    if (mul == ULTRA_MUL_ROTATE) mul = BIN_ROT;
     if (!edge_keep_dev) return invalid("ultra_rspmm_forward_masked: edge_keep is NULL");
     g_keep_mode = 1;
     const int rc = forward_impl(plan, sum, mul, dtype, edge_keep_dev, relation, input, boundary, output,
@@ -1058,7 +1150,8 @@ int32_t ultra_rspmm_forward_point(ultra_plan *plan, int32_t sum, int32_t mul, in
                                   const ultra_mat *point_values, const ultra_mat *output, void *stream) {
     ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);
     WeightEpochScope weight_epoch_scope;
-    if (mul < 0 || mul > 1) return invalid("unknown mul code");
+    if (mul < 0 || mul > ULTRA_MUL_ROTATE) return invalid("unknown mul code");
+    if (mul == ULTRA_MUL_ROTATE) mul = BIN_ROT;
     if (!point_rows_dev || !point_values) return invalid("ultra_rspmm_forward_point: NULL point boundary");
     return forward_impl(plan, sum, mul, dtype, edge_weight_dev, relation, input, point_values, output,
                         reinterpret_cast<hipStream_t>(stream), point_rows_dev);
@@ -1461,7 +1554,8 @@ int32_t ultra_rspmm_forward_timed(ultra_plan *plan, int32_t sum, int32_t mul, in
                                   const ultra_mat *boundary, const int64_t *point_rows_dev, const ultra_mat *output,
                                   void *stream, int32_t warmup, int32_t iters, float *ms_per_call, float *ms_main_kernel) {
     ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);
-    if (mul < 0 || mul > 1) return invalid("unknown mul code");
+    if (mul < 0 || mul > ULTRA_MUL_ROTATE) return invalid("unknown mul code");
+    if (mul == ULTRA_MUL_ROTATE) mul = BIN_ROT;
     const auto once = [&]() {
         return forward_impl(plan, sum, mul, dtype, edge_weight_dev, relation, input, boundary, output,
                             reinterpret_cast<hipStream_t>(stream), point_rows_dev);

@@ -343,4 +343,169 @@ inline int launch_edge_kernel(int dtype, int vec, int sum, int mul, bool want_ri
     return ULTRA_OK;
 }
 
+// ---- RotatE (ULTRA_MUL_ROTATE): a row is one complex vector, real half | imaginary half ----
+// Edge kernel: lane l of the 16-lane group that owns a sorted edge takes the complex elements c = l, l + 16, ... < row_len / 2
+// (both halves of each), so any even row length and any alignment is served.  weight_grad[e] = sum_d og[row, d] * [tie] *
+// ROT(rel, x)[d], one store per edge in ORIGINAL edge order; WANT_RI (min / max fallback, float atomics like the kernel above):
+// g = w * og * [tie] per ELEMENT, input_grad[col] += ROT(conj(rel), g), relation_grad[type] += ROT(conj(x), g) -- an element of
+// either half that ties sends gradient to both halves of x and rel.
+template <typename T, int SUM, bool WANT_RI>
+__global__ void __launch_bounds__(256) rspmm_rot_edge_bwd_kernel(const EdgeParams p) {
+    const int l16 = threadIdx.x & 15;
+    const long long g0 = (blockIdx.x * (long long)blockDim.x + threadIdx.x) >> 4;
+    const long long ng = ((long long)gridDim.x * blockDim.x) >> 4;
+    const int h = p.row_len >> 1;
+    for (long long k = g0; k < p.num_edge; k += ng) {
+        const int row = p.erow[k], col = p.col[k], type = p.type[k];
+        const int eid = p.perm[k];
+        const T w = p.w ? reinterpret_cast<const T *>(p.w)[eid] : T(1);
+        T wg = T(0);
+        for (int outer = 0; outer < p.n_outer; ++outer) {
+            const T *r = reinterpret_cast<const T *>(p.rel.ptr) + outer * p.rel.stride_outer + (long long)type * p.rel.stride_row;
+            const T *xi = reinterpret_cast<const T *>(p.x.ptr) + outer * p.x.stride_outer + (long long)col * p.x.stride_row;
+            const T *g = reinterpret_cast<const T *>(p.og.ptr) + outer * p.og.stride_outer + (long long)row * p.og.stride_row;
+            const T *o = reinterpret_cast<const T *>(p.out.ptr) + outer * p.out.stride_outer + (long long)row * p.out.stride_row;
+            for (int c = l16; c < h; c += 16) {
+                const T r_re = r[c], r_im = r[c + h], x_re = xi[c], x_im = xi[c + h];
+                const T m_re = x_re * r_re - x_im * r_im, m_im = x_re * r_im + x_im * r_re;
+                T t_re = g[c], t_im = g[c + h];
+                if (SUM != ULTRA_SUM_ADD) {
+                    t_re = t_re * (o[c] == w * m_re ? T(1) : T(0));
+                    t_im = t_im * (o[c + h] == w * m_im ? T(1) : T(0));
+                }
+                wg += t_re * m_re;
+                wg += t_im * m_im;
+                if (WANT_RI) {
+                    const T a = t_re * w, b = t_im * w;
+                    if (a != T(0) || b != T(0)) {
+                        T *rg = reinterpret_cast<T *>(p.rgrad) + outer * p.rgrad_so + (long long)type * p.rgrad_sr + c;
+                        T *xg = reinterpret_cast<T *>(p.xgrad) + outer * p.xgrad_so + (long long)col * p.xgrad_sr + c;
+                        unsafeAtomicAdd(rg, a * x_re + b * x_im);
+                        unsafeAtomicAdd(rg + h, b * x_re - a * x_im);
+                        unsafeAtomicAdd(xg, a * r_re + b * r_im);
+                        unsafeAtomicAdd(xg + h, b * r_re - a * r_im);
+                    }
+                }
+            }
+        }
+        if (p.wgrad) {
+            wg += __shfl_xor(wg, 8);
+            wg += __shfl_xor(wg, 4);
+            wg += __shfl_xor(wg, 2);
+            wg += __shfl_xor(wg, 1);
+            if (l16 == 0) reinterpret_cast<T *>(p.wgrad)[eid] = wg;
+        }
+    }
+}
+
+template <typename T>
+inline hipError_t launch_rot_edge_t(int sum, bool want_ri, const EdgeParams &p, hipStream_t s) {
+    const int blocks = (int)std::min<long long>((p.num_edge * 16 + 255) / 256, 16384);
+#define ULTRA_ROT_EDGE(S)                                                                                    \
+    if (sum == S) {                                                                                          \
+        if (want_ri)                                                                                         \
+            hipLaunchKernelGGL((rspmm_rot_edge_bwd_kernel<T, S, true>), dim3(blocks), dim3(256), 0, s, p);   \
+        else                                                                                                 \
+            hipLaunchKernelGGL((rspmm_rot_edge_bwd_kernel<T, S, false>), dim3(blocks), dim3(256), 0, s, p);  \
+        return hipGetLastError();                                                                            \
+    }
+    ULTRA_ROT_EDGE(0) ULTRA_ROT_EDGE(1) ULTRA_ROT_EDGE(2)
+#undef ULTRA_ROT_EDGE
+    return hipErrorInvalidValue;
+}
+
+inline int launch_rot_edge_kernel(int dtype, int sum, bool want_ri, const EdgeParams &p, hipStream_t s) {
+    const hipError_t e = dtype == ULTRA_F32 ? launch_rot_edge_t<float>(sum, want_ri, p, s) : launch_rot_edge_t<double>(sum, want_ri, p, s);
+    if (e != hipSuccess) {
+        set_error(std::string("rspmm_rot_edge_bwd_kernel launch: ") + hipGetErrorString(e));
+        return ULTRA_ERR_HIP;
+    }
+    return ULTRA_OK;
+}
+
+// min / max backward of RotatE as a GATHER over the destination-major plans, like rspmm_minmax_bwd_gather_kernel (no atomics,
+// a fixed order: the same bits run to run).  A "span" is 16 complex elements: lane l holds element c = 16 inner + l of BOTH halves,
+// scalar loads, so every even row length and every alignment takes this route.  Per edge, with a / b the weighted output
+// gradient of the real / imaginary element where that element's message ties with the output:
+//   input_grad[col]     re += a r_re + b r_im     im += b r_re - a r_im        (ROT(conj(rel), g))
+//   relation_grad[type] re += a x_re + b x_im     im += b x_re - a x_im        (ROT(conj(x), g))
+template <typename T, int SUM, bool REL_GRAD>
+__global__ void __launch_bounds__(256) rspmm_rot_minmax_bwd_gather_kernel(const GatherBwdParams p) {
+    const int l16 = threadIdx.x & 15;
+    const int part = blockIdx.x / p.smod;
+    if (part >= p.nparts) return;
+    const int groups_per_block = blockDim.x >> 4;
+    const int h = p.row_len >> 1;
+    const T *wt = reinterpret_cast<const T *>(p.w);
+    for (int span = blockIdx.x % p.smod; span < p.n_span; span += p.smod) {
+        const int outer = span / p.spans_per_outer, inner = span - outer * p.spans_per_outer;
+        const int c = inner * 16 + l16;
+        if (c >= h) continue;
+        const T *relp = reinterpret_cast<const T *>(p.rel.ptr) + outer * p.rel.stride_outer + c;
+        const T *xp = reinterpret_cast<const T *>(p.x.ptr) + outer * p.x.stride_outer + c;
+        const T *outp = reinterpret_cast<const T *>(p.out.ptr) + outer * p.out.stride_outer + c;
+        const T *ogp = reinterpret_cast<const T *>(p.og.ptr) + outer * p.og.stride_outer + c;
+        for (int q = part * groups_per_block + (threadIdx.x >> 4); q < p.n_item; q += p.nparts * groups_per_block) {
+            const Item it = p.items[q];
+            const T *selfp = REL_GRAD ? relp + (long long)it.row * p.rel.stride_row : xp + (long long)it.row * p.x.stride_row;
+            const T s_re = selfp[0], s_im = selfp[h];
+            T acc_re = T(0), acc_im = T(0);
+            const int end = it.begin + it.len;
+            for (int k = it.begin; k < end; k += 4) {
+                int a[4], b[4];
+                T wv[4], q_re[4], q_im[4], o_re[4], o_im[4], g_re[4], g_im[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int kk = k + u < end ? k + u : end - 1;
+                    a[u] = p.col[kk], b[u] = p.type[kk];
+                    wv[u] = wt ? wt[p.perm[kk]] : T(1);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int i = REL_GRAD ? b[u] : a[u];     // the aggregation row of the edge
+                    const T *other = REL_GRAD ? xp + (long long)a[u] * p.x.stride_row : relp + (long long)b[u] * p.rel.stride_row;
+                    const T *op = outp + (long long)i * p.out.stride_row, *gp = ogp + (long long)i * p.og.stride_row;
+                    q_re[u] = other[0], q_im[u] = other[h];
+                    o_re[u] = op[0], o_im[u] = op[h];
+                    g_re[u] = gp[0], g_im[u] = gp[h];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (k + u < end) {
+                        const T r_re = REL_GRAD ? s_re : q_re[u], r_im = REL_GRAD ? s_im : q_im[u];
+                        const T x_re = REL_GRAD ? q_re[u] : s_re, x_im = REL_GRAD ? q_im[u] : s_im;
+                        const T m_re = x_re * r_re - x_im * r_im, m_im = x_re * r_im + x_im * r_re;
+                        const T ta = g_re[u] * (o_re[u] == wv[u] * m_re ? T(1) : T(0));     // operator.cuh:62-64, 75-77, per element
+                        const T tb = g_im[u] * (o_im[u] == wv[u] * m_im ? T(1) : T(0));
+                        const T ga = ta * wv[u], gb = tb * wv[u];
+                        // the factor that is NOT the destination, conjugated
+                        const T f_re = REL_GRAD ? x_re : r_re, f_im = REL_GRAD ? x_im : r_im;
+                        acc_re += ga * f_re + gb * f_im;
+                        acc_im += gb * f_re - ga * f_im;
+                    }
+                }
+            }
+            T *dst = it.slot >= 0 ? reinterpret_cast<T *>(p.partial) + ((long long)it.slot * p.n_outer + outer) * p.row_len + c
+                                  : reinterpret_cast<T *>(p.grad) + outer * p.grad_so + (long long)it.row * p.grad_sr + c;
+            dst[0] = acc_re;
+            dst[h] = acc_im;
+        }
+    }
+}
+
+template <typename T>
+inline hipError_t launch_rot_gather_bwd_t(int sum, bool rel_grad, const GatherBwdParams &p, int grid, hipStream_t s) {
+#define ULTRA_ROT_GB(S)                                                                                              \
+    if (sum == S) {                                                                                                  \
+        if (rel_grad)                                                                                                \
+            hipLaunchKernelGGL((rspmm_rot_minmax_bwd_gather_kernel<T, S, true>), dim3(grid), dim3(256), 0, s, p);    \
+        else                                                                                                         \
+            hipLaunchKernelGGL((rspmm_rot_minmax_bwd_gather_kernel<T, S, false>), dim3(grid), dim3(256), 0, s, p);   \
+        return hipGetLastError();                                                                                    \
+    }
+    ULTRA_ROT_GB(1) ULTRA_ROT_GB(2)
+#undef ULTRA_ROT_GB
+    return hipErrorInvalidValue;
+}
+
 }  // namespace ultra

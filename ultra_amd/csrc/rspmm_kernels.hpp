@@ -43,6 +43,17 @@ enum { MODE_GLOBAL = 0, MODE_REL_LDS = 1, MODE_ALL_LDS = 2 };
 // BIN_MUL_TYPED: add_mul over a ULTRA_PLAN_TYPE_RUNS plan -- every item holds one relation, so the walk sums
 // the sources and the relation vector is applied once per item (its own kernel, no extra code in BIN_MUL).
 enum { BIN_MUL = 0, BIN_ADD = 1, BIN_LHS = 2, BIN_RHS = 3, BIN_MUL_TYPED = 4 };
+// BIN_ROT*: RotatE (ULTRA_MUL_ROTATE, layers.py:142-147) -- a row is one complex vector, real half | imaginary half, and the
+// message is the complex product ROT(rel, x).  _CREL / _CX conjugate the relation / the source operand: the two gradients
+// of the add aggregate, as re-runs of the forward walk (rspmm_api.hip backward_impl).  A lane needs its PARTNER's
+// operands (element d +- row_len / 2):
+//   BIN_ROT .. BIN_ROT_CX    the row is exactly one span (64 elements): the partner is lane ^ 8 of the same 16-lane group,
+//                            one DPP row rotate per register -- still one 16-byte gather per lane and edge;
+//   BIN_ROTG .. BIN_ROTG_CX  every other even row length: a second load at the partner's offset (MODE_GLOBAL only).
+enum { BIN_ROT = 5, BIN_ROT_CREL = 6, BIN_ROT_CX = 7, BIN_ROTG = 8, BIN_ROTG_CREL = 9, BIN_ROTG_CX = 10 };
+constexpr bool bin_is_rot(int mul) { return mul >= BIN_ROT && mul <= BIN_ROTG_CX; }
+constexpr bool bin_is_rot_far(int mul) { return mul >= BIN_ROTG && mul <= BIN_ROTG_CX; }
+constexpr int bin_rot_kind(int mul) { return mul >= BIN_ROTG ? mul - BIN_ROTG : mul - BIN_ROT; }   // 0 plain, 1 conj(rel), 2 conj(x)
 
 #ifndef ULTRA_UNROLL
 #define ULTRA_UNROLL 4
@@ -76,6 +87,7 @@ struct FwdParams {
     int32_t keep_mode;           // the weight stream is a 0/1 keep mask: a dropped edge is absent (matters for min / max)
     int32_t smod, nparts;
     uint32_t x_row_bytes, rel_row_bytes;   // row strides in bytes (each operand slice is < 4 GiB)
+    uint32_t rot_half_bytes;               // BIN_ROTG*: row_len / 2 elements in bytes, the distance to the partner half
 };
 
 struct FixupParams {
@@ -204,6 +216,64 @@ __device__ __forceinline__ V binary_vec(V rel, V x) {
     else return x;
 }
 
+// ---- RotatE ----
+// The value lane (l ^ 8) of the same 16-lane row holds: one v_mov_b32 with DPP row_ror:8 per 32-bit register, no LDS.
+__device__ __forceinline__ float xchg8(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false));
+}
+__device__ __forceinline__ double xchg8(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x128, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x128, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+// The same exchange for the lanes of one half only (BANKS: 0xc = lanes 8-15, 0x3 = lanes 0-7 of every 16-lane row; a DPP
+// bank is four lanes), the other half keeping its own value: "the real (0xc) / imaginary (0x3) part of this lane's complex
+// element" in one instruction, where a full exchange would need a select behind it.
+template <int BANKS>
+__device__ __forceinline__ float xchg8_half(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x128, 0xf, BANKS, false));
+}
+template <int BANKS>
+__device__ __forceinline__ double xchg8_half(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(__double2loint(v), __double2loint(v), 0x128, 0xf, BANKS, false);
+    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(v), __double2hiint(v), 0x128, 0xf, BANKS, false);
+    return __hiloint2double(hi, lo);
+}
+template <typename T, int VEC, int BANKS>
+__device__ __forceinline__ typename VecOf<T, VEC>::type xchg8_vec(const typename VecOf<T, VEC>::type &v) {
+    typename VecOf<T, VEC>::type r;
+    if constexpr (VEC == 1) {
+        r = BANKS == 0xf ? xchg8(v) : xchg8_half<BANKS>(v);
+    } else {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) r[e] = BANKS == 0xf ? xchg8(v[e]) : xchg8_half<BANKS>(v[e]);
+    }
+    return r;
+}
+
+// One half of the complex product for a lane that holds (r, x) and its partner's (rp, xp); `hi`: this lane sits in the
+// imaginary half.  Two products and one sum / difference, each rounded on its own (layers.py:142-147 on the CPU):
+//   KIND 0  ROT(r, x)        re = x_re r_re - x_im r_im      im = x_re r_im + x_im r_re
+//   KIND 1  ROT(conj(r), x)  re = x_re r_re + x_im r_im      im = x_im r_re - x_re r_im
+//   KIND 2  ROT(conj(x), r)  re = r_re x_re + r_im x_im      im = r_im x_re - r_re x_im
+// x_re / x_im: the real / imaginary part of the source element this lane's element belongs to (in either half).
+// The sign of the difference rides on one factor as a per-lane +-1 (exact: (-a) b = -(a b), p + (-q) = p - q), so that the lanes
+// of both halves run the same two products and one sum without a select.
+template <typename V, int KIND>
+__device__ __forceinline__ V rotate_parts(const V r, const V rp, const V x_re, const V x_im, const bool hi) {
+    using S = decltype(r * r);
+    if constexpr (KIND == 1) {
+        const S s = S(hi ? -1.0 : 1.0);
+        return x_re * (r * s) + x_im * rp;     // re: p1 + p2      im: p2 - p1
+    } else {
+        const S s = S((KIND == 0) == hi ? 1.0 : -1.0);
+        return x_re * r + x_im * (rp * s);     // ROT: re p1 - p2, im p1 + p2      conj(x): re p1 + p2, im p1 - p2
+    }
+}
+template <typename V, int KIND>
+__device__ __forceinline__ V rotate_vec(const V r, const V x, const V rp, const V xp, const bool hi) {
+    return rotate_parts<V, KIND>(r, rp, hi ? xp : x, hi ? x : xp, hi);
+}
 
 // Copies the span-wide column slice [inner * SPAN, +SPAN) of `rows` rows into LDS (row-major, SPAN
 // elements per row).  Four 16-byte loads are in flight per thread before the first LDS write.
@@ -239,11 +309,17 @@ template <typename T, int VEC, int SUM, int MUL, int MODE, bool PACKED, bool UNI
 __device__ __forceinline__ Pack<T, VEC> walk_edges(const FwdParams &p, const int begin, const int cnt, const int stride,
                                                    const int nsteps, const int nfull, const int lane, const int l16,
                                                    const char *xbase, const char *relbase, const uint32_t lane_bytes,
-                                                   const T *lds_x, const T *lds_rel) {
+                                                   const T *lds_x, const T *lds_rel, const uint32_t pair_bytes = 0,
+                                                   const bool hi = false) {
     constexpr int SPAN = 16 * VEC;
     constexpr bool TYPED = (MUL == BIN_MUL_TYPED);
+    // RotatE: `hi` = this lane holds elements of the imaginary half; ROTFAR: the partner half is loaded from pair_bytes
+    constexpr bool ROT = bin_is_rot(MUL), ROTFAR = bin_is_rot_far(MUL);
+    static_assert(!ROTFAR || MODE == MODE_GLOBAL, "the partner half of a long row is not in the staged span");
+    static_assert(!ROT || ROTFAR || VEC == 4, "the lane exchange serves rows of one 64-element span");
     // edges per group and chunk: LDS-resident gathers have short latency and cheap registers -> deeper chunks
-    constexpr int UNR = (MODE == MODE_ALL_LDS && sizeof(T) == 4) ? ULTRA_UNROLL_LDS : ULTRA_UNROLL;
+    // (a long RotatE row gathers twice per edge: half the depth keeps its two chunks in registers)
+    constexpr int UNR = bin_is_rot_far(MUL) ? 2 : (MODE == MODE_ALL_LDS && sizeof(T) == 4) ? ULTRA_UNROLL_LDS : ULTRA_UNROLL;
     using P = Pack<T, VEC>;
     using V = typename VecOf<T, VEC>::type;
     V acc = V(nary_zero<T, SUM>());
@@ -273,6 +349,7 @@ __device__ __forceinline__ Pack<T, VEC> walk_edges(const FwdParams &p, const int
         uint32_t t[UNR];
         T w[UNR];
         P xv[UNR];
+        P xp[ROTFAR ? UNR : 1];
     };
     auto fetch = [&](Fetched &f, const uint32_t rec_c, const uint32_t rec_t, const T rec_w, const int j) {
         uint32_t c[UNR];
@@ -297,11 +374,13 @@ __device__ __forceinline__ Pack<T, VEC> walk_edges(const FwdParams &p, const int
                 else
                     f.xv[q] = *reinterpret_cast<const P *>(xbase + (c[q] * p.x_row_bytes + lane_bytes));
             }
+            if constexpr (ROTFAR) f.xp[q] = *reinterpret_cast<const P *>(xbase + (c[q] * p.x_row_bytes + pair_bytes));
         }
     };
     auto compute = [&](auto pred_tag, const Fetched &f, const int kbase) {
         constexpr bool PRED = decltype(pred_tag)::value;
         P rv[UNR];
+        P rp[ROTFAR ? UNR : 1];
 #pragma unroll
         for (int q = 0; q < UNR; ++q) {
             if (MUL != BIN_RHS && !TYPED) {
@@ -310,13 +389,21 @@ __device__ __forceinline__ Pack<T, VEC> walk_edges(const FwdParams &p, const int
                 else
                     rv[q] = *reinterpret_cast<const P *>(relbase + (f.t[q] * p.rel_row_bytes + lane_bytes));
             }
+            if constexpr (ROTFAR) rp[q] = *reinterpret_cast<const P *>(relbase + (f.t[q] * p.rel_row_bytes + pair_bytes));
         }
 #pragma unroll
         for (int q = 0; q < UNR; ++q) {
             const V rr = (MUL != BIN_RHS && !TYPED) ? to_vec<T, VEC>(rv[q]) : V(T(0));
             const V xx = (MUL != BIN_LHS) ? to_vec<T, VEC>(f.xv[q]) : V(T(0));
             // TYPED items hold edges of ONE relation: sum the sources, multiply by rel[type] once at the end
-            V y = TYPED ? xx : binary_vec<V, MUL>(rr, xx);
+            V y;
+            if constexpr (ROTFAR)
+                y = rotate_vec<V, bin_rot_kind(MUL)>(rr, xx, to_vec<T, VEC>(rp[q]), to_vec<T, VEC>(f.xp[q]), hi);
+            else if constexpr (ROT)
+                y = rotate_parts<V, bin_rot_kind(MUL)>(rr, xchg8_vec<T, VEC, 0xf>(rr), xchg8_vec<T, VEC, 0xc>(xx),
+                                                       xchg8_vec<T, VEC, 0x3>(xx), hi);
+            else
+                y = TYPED ? xx : binary_vec<V, MUL>(rr, xx);
             if (!UNITW) y = weigh<T, SUM>(y, f.w[q], p.keep_mode);
             const V cand = nary_vec<V, SUM>(acc, y);
             if (PRED)
@@ -419,6 +506,9 @@ __global__ void __launch_bounds__(1024) rspmm_fwd_kernel(const FwdParams p) {
             reinterpret_cast<const char *>(reinterpret_cast<const T *>(p.rel.ptr) + outer * p.rel.stride_outer);
         const uint32_t lane_bytes = (uint32_t)d0c * (uint32_t)sizeof(T);
         const long long bnd_row = p.bnd_rows ? p.bnd_rows[outer] : -1;   // (stride_row of a point boundary is 0)
+        // RotatE: which half this lane holds, and (long rows) where its partner's elements lie
+        const bool rot_hi = bin_is_rot_far(MUL) ? lane_bytes >= p.rot_half_bytes : l16 >= 8;
+        const uint32_t pair_bytes = rot_hi ? lane_bytes - p.rot_half_bytes : lane_bytes + p.rot_half_bytes;
 
         if (MODE >= MODE_REL_LDS) {
             __syncthreads();  // readers of the previous span are done with the LDS image
@@ -470,7 +560,7 @@ __global__ void __launch_bounds__(1024) rspmm_fwd_kernel(const FwdParams p) {
             P acc;
 #define ULTRA_WALK(PK, UW)                                                                                       \
     acc = walk_edges<T, VEC, SUM, MUL, MODE, PK, UW>(p, begin, cnt, stride, nsteps, nfull, lane, l16, xbase, relbase, \
-                                                     lane_bytes, lds_x, lds_rel)
+                                                     lane_bytes, lds_x, lds_rel, pair_bytes, rot_hi)
             constexpr bool typed = (MUL == BIN_MUL_TYPED);
             if (p.packed_on) {
                 if (p.unit_w) ULTRA_WALK(true, true); else ULTRA_WALK(true, false);
@@ -632,6 +722,42 @@ hipError_t launch_fwd_variant(int sum, int mul, const FwdParams &p, int grid, in
             case 100: return launch_one<T, VEC, 0, BIN_MUL_TYPED, MODE>(p, grid, threads, lds, s);                 \
         }                                                                                                         \
         return hipErrorInvalidValue;                                                                              \
+    }
+
+
+// ---- RotatE variants (explicitly instantiated in rspmm_variant_rot_*.hip) ----
+// mul: BIN_ROT* (NEAR: the lane exchange) or BIN_ROTG* (FAR: the partner half loaded); the conjugating kinds under add only.
+template <typename T, int VEC, int MODE>
+hipError_t launch_rot_variant(int sum, int mul, const FwdParams &p, int grid, int threads, size_t lds, hipStream_t s);
+
+template <typename T, int VEC, int MODE, int BASE>
+inline hipError_t launch_rot_kinds(int sum, int mul, const FwdParams &p, int grid, int threads, size_t lds, hipStream_t s) {
+    switch (sum * 4 + (mul - BASE)) {
+        case 0: return launch_one<T, VEC, 0, BASE, MODE>(p, grid, threads, lds, s);
+        case 1: return launch_one<T, VEC, 0, BASE + 1, MODE>(p, grid, threads, lds, s);
+        case 2: return launch_one<T, VEC, 0, BASE + 2, MODE>(p, grid, threads, lds, s);
+        case 4: return launch_one<T, VEC, 1, BASE, MODE>(p, grid, threads, lds, s);
+        case 8: return launch_one<T, VEC, 2, BASE, MODE>(p, grid, threads, lds, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+template <typename T, int VEC, int MODE, bool NEAR, bool FAR>
+inline hipError_t launch_rot_dispatch(int sum, int mul, const FwdParams &p, int grid, int threads, size_t lds, hipStream_t s) {
+    if constexpr (NEAR) {
+        if (!bin_is_rot_far(mul)) return launch_rot_kinds<T, VEC, MODE, BIN_ROT>(sum, mul, p, grid, threads, lds, s);
+    }
+    if constexpr (FAR) {
+        if (bin_is_rot_far(mul)) return launch_rot_kinds<T, VEC, MODE, BIN_ROTG>(sum, mul, p, grid, threads, lds, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+#define ULTRA_DEFINE_ROT_VARIANT(T_, VEC_, MODE_, NEAR_, FAR_)                                                        \
+    template <>                                                                                                       \
+    hipError_t launch_rot_variant<T_, VEC_, MODE_>(int sum, int mul, const FwdParams &p, int grid, int threads,      \
+                                                   size_t lds, hipStream_t s) {                                       \
+        return launch_rot_dispatch<T_, VEC_, MODE_, NEAR_, FAR_>(sum, mul, p, grid, threads, lds, s);                 \
     }
 
 }  // namespace ultra

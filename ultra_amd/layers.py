@@ -4,8 +4,10 @@ Same constructor, forward signature, parameter names and numerics as the referen
 PyG: the fused path (layers.py:183-231) calls the HIP rspmm engine directly on the module-level
 batch-major layout (batch, N, dim), so the three `transpose(0, 1).flatten(1)` copies of the
 reference (layers.py:190-192) and the per-call edge sort disappear, and under no_grad the boundary
-epilogue (layers.py:199-207) is fused into the kernel.  The unfused message/aggregate path
-(layers.py:135-181; `rotate`, or differentiable edge weights) is kept as plain torch index ops.
+epilogue (layers.py:199-207) is fused into the kernel.  `rotate` messages, which the reference runs unfused, go through the
+same engine (mul="rotate") in the unfused path's direction for the sum / mean / max / min aggregates.  The unfused
+message/aggregate path (layers.py:135-181; differentiable edge weights, `rotate` with pna or on the CPU) is kept as
+plain torch index ops.
 """
 import os
 
@@ -37,6 +39,9 @@ FUSED_DENSE_LAYER = True
 # the rspmm kernel, on the rows each workgroup has just summed.  Same bits as the two launches, 1 - 2.7 % faster on the
 # benchmark step.  ULTRA_FUSED_SPARSE_LAYER=0 (or the attribute, for A/B tests) selects the two launches.
 FUSED_SPARSE_LAYER = os.environ.get("ULTRA_FUSED_SPARSE_LAYER", "1") != "0"
+# `rotate` messages through the rspmm engine (mul="rotate") instead of index_select / cat / scatter over (batch, |E|, d)
+# tensors: memory O(|V| d) instead of O(|E| d), a fixed summation order.  False = the unfused route (A/B switch for tests)
+FUSED_ROTATE = True
 
 
 class PointBoundary(object):
@@ -206,9 +211,10 @@ class GeneralizedRelationalConv(nn.Module):
 
     def propagate(self, edge_index, size=None, residual=False, onehot_rows=None, edge_keep=False, **kwargs):
         edge_weight = kwargs["edge_weight"]
-        if edge_keep and self.message_func == "rotate":
+        rotate_fused = self.rotate_fused(kwargs["input"], kwargs["relation"], edge_weight)
+        if edge_keep and self.message_func == "rotate" and not rotate_fused:
             # the unfused scatter path needs the edges really gone: the caller removes them
-            raise RuntimeError("edge_keep masks serve the fused TransE / DistMult path")
+            raise RuntimeError("edge_keep masks serve the fused TransE / DistMult / RotatE paths")
         if isinstance(kwargs["boundary"], PointBoundary) and (
                 (edge_weight is not None and edge_weight.requires_grad) or self.message_func == "rotate"
                 or self.aggregate_func not in ("sum", "max") or not kwargs["input"].is_cuda
@@ -217,8 +223,10 @@ class GeneralizedRelationalConv(nn.Module):
                     and (kwargs["input"].requires_grad or kwargs["relation"].requires_grad
                          or kwargs["boundary"].requires_grad))):
             kwargs["boundary"] = kwargs["boundary"].dense()     # paths that need the boundary as a tensor
+        if rotate_fused:
+            return self._propagate_rotate(edge_index, size, residual=residual, edge_keep=edge_keep, **kwargs)
         if (edge_weight is not None and edge_weight.requires_grad) or self.message_func == "rotate":
-            # layers.py:91-94: the fused kernel covers TransE / DistMult with constant edge weights only
+            # layers.py:91-94: the reference's fused kernel covers TransE / DistMult with constant edge weights only
             out = self._propagate_unfused(edge_index, size, **kwargs)
             return out + kwargs["input"] if residual else out
         num_node = size[0] if size is not None else kwargs["input"].shape[1]
@@ -350,6 +358,50 @@ class GeneralizedRelationalConv(nn.Module):
             rows, None if point is not None else boundary, point.rows if point is not None else None,
             point.values if point is not None else None, self.linear.weight, self.linear.bias,
             ln.weight if ln is not None else None, ln.bias if ln is not None else None)
+
+    # ---- RotatE through the engine, in the unfused path's direction ----
+    def rotate_fused(self, input, relation, edge_weight=None):
+        """Does this layer's `rotate` message run on the rspmm engine?  sum / mean / max / min, GPU tensors, constant edge
+        weights, an even feature dim (pna needs the squared MESSAGE, and (r x)^2 = r^2 x^2 does not hold for a complex
+        product: it stays unfused, like differentiable edge weights and CPU tensors)."""
+        return (FUSED_ROTATE and self.message_func == "rotate" and self.aggregate_func in ("sum", "mean", "max", "min")
+                and input.is_cuda and input.dim() == 3 and input.shape[-1] % 2 == 0
+                and input.dtype in (torch.float32, torch.float64) and relation.dtype == input.dtype
+                and (edge_weight is None or not edge_weight.requires_grad))
+
+    def _propagate_rotate(self, edge_index, size, input, relation, boundary, edge_type, edge_weight, residual=False,
+                          edge_keep=False):
+        """The reference runs `rotate` unfused: messages gathered at edge_index[0], aggregated into edge_index[1] together with
+        one boundary self-loop per node (layers.py:135-181).  The same on the engine: the plan of the FLIPPED edge list, the
+        boundary fused as the walk's last operand -- on a reference-order plan the sum is the CPU scatter_add_'s on an edge list
+        sorted by (target, source, id), bit for bit.  No (batch, |E|, d) tensor is formed."""
+        num_target = size[1] if size is not None else input.shape[1]
+        if edge_weight is not None and edge_weight.dtype != input.dtype:
+            edge_weight = edge_weight.to(input.dtype)
+        if boundary.dtype != input.dtype:
+            boundary = boundary.to(input.dtype)
+        needs_grad = torch.is_grad_enabled() and (input.requires_grad or relation.requires_grad or boundary.requires_grad)
+        flipped = _flipped_edges(edge_index)
+        # (as message_and_aggregate: reference order under no_grad, the re-associating plan for a training step)
+        plan = rspmm.get_plan(flipped, edge_type, num_target, relation.shape[1],
+                              exact_order=False if (needs_grad or self._order_free(edge_index, num_target)) else None)
+        sum = {"sum": "add", "mean": "add"}.get(self.aggregate_func, self.aggregate_func)
+        if not needs_grad:
+            update = plan.forward(relation, input, edge_weight=edge_weight, boundary=boundary, sum=sum, mul="rotate", keep=edge_keep)
+        elif sum == "add":
+            update = rspmm.plan_rspmm(plan, relation, input, edge_weight, sum=sum, mul="rotate", boundary=boundary, keep=edge_keep)
+        else:
+            update = rspmm.plan_rspmm(plan, relation, input, edge_weight, sum=sum, mul="rotate", keep=edge_keep)
+            update = torch.max(update, boundary) if sum == "max" else torch.min(update, boundary)
+        if self.aggregate_func == "mean":
+            # scatter(..., "mean") over the in-edges + the self loop; under a keep mask the kept edges only
+            if edge_keep and edge_weight is not None:
+                degree = torch.zeros(num_target, dtype=input.dtype, device=input.device).index_add_(
+                    0, edge_index[1], edge_weight.detach())
+            else:
+                degree = torch.bincount(edge_index[1], minlength=num_target).to(input.dtype)
+            update = update / (degree + 1).view(1, -1, 1)
+        return self.update(update, input, residual=residual)
 
     # ---- unfused path: gather edge_index[0], scatter to edge_index[1] -- PyG's direction (layers.py:135-181) ----
     def _propagate_unfused(self, edge_index, size, input, relation, boundary, edge_type, edge_weight):

@@ -111,7 +111,7 @@ class BaseNBFNet(nn.Module):
         return self.easy_edge_mask(data, h_index, t_index, r_index).to(dtype)
 
     def remove_easy_edges(self, data, h_index, t_index, r_index=None):
-        """The reference's route: a filtered copy of the graph (only the unfused `rotate` path still needs it)."""
+        """The reference's route: a filtered copy of the graph (only `rotate` off the engine still needs it: layers.rotate_fused)."""
         keep = self.easy_edge_mask(data, h_index, t_index, r_index)
         data = copy.copy(data)
         data.edge_index = data.edge_index[:, keep]
@@ -459,14 +459,18 @@ class EntityNBFNet(BaseNBFNet):
 
         edge_weight = None
         if self.training:
-            if self.aggregate_func in ("sum", "min", "max", "mean", "pna") and self.message_func in ("distmult", "transe"):
+            rotate_keep = (self.message_func == "rotate" and self.aggregate_func in ("sum", "min", "max", "mean")
+                           and all(layer.rotate_fused(relation_representations, relation_representations) for layer in self.layers))
+            if rotate_keep or (self.aggregate_func in ("sum", "min", "max", "mean", "pna")
+                               and self.message_func in ("distmult", "transe")):
                 # Edge dropout without touching the graph: a 0/1 keep vector over the static edge list (one kernel), read
                 # by the rspmm kernels as "edge absent" -- so the cached plan of the static graph serves every batch
                 # (the reference filters the edge list, base_nbfnet.py:54-77, and re-sorts it inside every rspmm call);
                 # mean / pna take their degree from the same vector (layers.message_and_aggregate).
                 edge_weight = self.easy_edge_keep(data, h_index, t_index, r_index, relation_representations.dtype)
             else:
-                # rotate runs the unfused scatter path: the reference's filtered copy of the graph
+                # rotate off the engine (pna, CPU tensors, layers.FUSED_ROTATE = False) runs the unfused scatter path: the
+                # reference's filtered copy of the graph
                 data = self.remove_easy_edges(data, h_index, t_index, r_index)
 
         shape = h_index.shape

@@ -1,4 +1,4 @@
-"""Drop-in operator boundary: generalized_rspmm and the six RSPMM*Function classes.
+"""Drop-in operator boundary: generalized_rspmm and the RSPMM*Function classes.
 
 Mirrors /root/reference/ultra/rspmm/rspmm.py (names, argument meaning, error behaviour):
   * generalized_rspmm(edge_index, edge_type, edge_weight, relation, input, sum="add", mul="mul")
@@ -7,6 +7,12 @@ Mirrors /root/reference/ultra/rspmm/rspmm.py (names, argument meaning, error beh
     (AssertionError "Expect sorted `edge_index`"), differentiable w.r.t. edge_weight, relation, input;
   * `rspmm` -- a namespace exporting the reference extension's function names
     rspmm_<sum>_<mul>_{forward,backward}_cuda (rspmm.cpp:270-282), bound to the stateless C entry points.
+
+Beyond the reference: mul="rotate" (ULTRA_MUL_ROTATE, include/ultra_rspmm.h) -- the RotatE message of the reference LAYER
+(layers.py:142-147) as an rspmm operator: a row is one complex vector, real half | imaginary half.  `Plan.forward` /
+`Plan.backward` / `plan_rspmm` / `generalized_rspmm` take it and RSPMM{Add,Min,Max}RotateFunction exist; the `rspmm`
+namespace of reference exports does not grow.  In the 2-D (N, D) layout the whole row is ONE complex vector: batched
+callers pass batch-major (batch, N, d) operands.
 
 What changes underneath: the per-call argsort / ind2ptr / host syncs of the reference are replaced by a
 cached `Plan` (built once per graph) and the HIP kernels of libultra_amd.so.  CPU tensors raise: this
@@ -460,9 +466,11 @@ class Plan(object):
         return out
 
     def backward(self, relation, input, output, output_grad, edge_weight=None, need_weight_grad=False, sum="add",
-                 mul="mul", weight_epoch=None, input_grad_base=None):
+                 mul="mul", weight_epoch=None, input_grad_base=None, keep=False):
         """input_grad_base (sum == "add"): a tensor of the input's shape that the returned input gradient starts from (the
-        input's gradient from another consumer); it is overwritten with the total and returned."""
+        input's gradient from another consumer); it is overwritten with the total and returned.
+        keep=True: `edge_weight` was the forward's 0/1 keep mask -- a dropped edge is absent from the graph, so its weight
+        gradient (asked for with need_weight_grad) is zero; relation / input gradients need no flag (ultra_rspmm_forward_masked)."""
         _require_gpu(relation, input, output, output_grad, edge_weight)
         dt = _dtype_code(relation, input, output, output_grad)
         relation, mrel = as_mat(relation)
@@ -519,6 +527,8 @@ class Plan(object):
             check(lib.ultra_rspmm_backward(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], dt, w, ctypes.byref(mrel),
                                            ctypes.byref(mx), ctypes.byref(mo), ctypes.byref(mog), wg, ctypes.byref(mrg),
                                            ctypes.byref(mxg) if mxg is not None else None, _stream(input)))
+        if keep and wgrad is not None and edge_weight is not None:
+            wgrad = wgrad * (edge_weight != 0).to(wgrad.dtype)
         return wgrad, rgrad, xgrad
 
     def forward_timed(self, relation, input, edge_weight=None, boundary=None, sum="add", mul="mul", warmup=3, iters=20,
@@ -651,6 +661,7 @@ class _PlanRSPMM(autograd.Function):
         output = plan.forward(relation, input, edge_weight=edge_weight, boundary=boundary, sum=sum, mul=mul, keep=keep,
                               point=point)
         ctx.plan, ctx.sum, ctx.mul = plan, sum, mul
+        ctx.keep = bool(keep)
         ctx.point_rows = point_rows
         ctx.weight_epoch = _weight_epoch(edge_weight)       # (the tag rides on the Python object: read it while it is at hand)
         ctx.save_for_backward(edge_weight, relation, input, output)   # rspmm.py:25
@@ -663,7 +674,7 @@ class _PlanRSPMM(autograd.Function):
         output_grad = output_grad.contiguous()
         weight_grad, relation_grad, input_grad = ctx.plan.backward(
             relation, input, output, output_grad, edge_weight=edge_weight, need_weight_grad=need_w,
-            sum=ctx.sum, mul=ctx.mul,
+            sum=ctx.sum, mul=ctx.mul, keep=ctx.keep,
             weight_epoch=ctx.weight_epoch if (edge_weight is not None and edge_weight.is_contiguous()) else 0)
         boundary_grad = output_grad if ctx.needs_input_grad[6] else None
         values_grad = None
@@ -841,6 +852,10 @@ RSPMMMaxMulFunction = _make_function("max", "mul")   # rspmm.py:64
 RSPMMAddAddFunction = _make_function("add", "add")   # rspmm.py:90
 RSPMMMinAddFunction = _make_function("min", "add")   # rspmm.py:116
 RSPMMMaxAddFunction = _make_function("max", "add")   # rspmm.py:142
+# RotatE messages (no reference twin): (N, D) operands, the whole row one complex vector -- real half | imaginary half
+RSPMMAddRotateFunction = _make_function("add", "rotate")
+RSPMMMinRotateFunction = _make_function("min", "rotate")
+RSPMMMaxRotateFunction = _make_function("max", "rotate")
 
 
 def generalized_rspmm(edge_index, edge_type, edge_weight, relation, input, sum="add", mul="mul"):
@@ -869,7 +884,7 @@ class _ReferenceExports(object):
 
     def __getattr__(self, name):
         parts = name.split("_")
-        if len(parts) == 5 and parts[0] == "rspmm" and parts[1] in _lib.SUM_CODES and parts[2] in _lib.MUL_CODES \
+        if len(parts) == 5 and parts[0] == "rspmm" and parts[1] in _lib.SUM_CODES and parts[2] in ("mul", "add") \
                 and parts[3] in ("forward", "backward") and parts[4] in ("cuda", "cpu"):
             if parts[4] == "cpu":
                 def no_cpu(*args, **kwargs):
