@@ -84,6 +84,18 @@ struct Schedule {
     int64_t srec_pad = 2 * ORDER_PAD;                   // readable zeros (int32 words) behind the last stream's records
 };
 
+// A per-call edge-weight vector in the plan's edge order, and the vector it was made from (ultra_rspmm_weight_epoch): its
+// tag, address, dtype, stream, and the stream capture the copy is valid in (0: made eagerly).
+struct WeightCopy {
+    void *buf = nullptr;
+    size_t bytes = 0;
+    int64_t epoch = 0;
+    const void *src = nullptr;
+    int32_t dtype = -1;
+    void *stream = nullptr;
+    unsigned long long cap_id = 0;
+};
+
 struct DevicePlan {
     int32_t *row_ptr = nullptr, *col = nullptr, *type = nullptr, *perm = nullptr, *erow = nullptr;
     int32_t *rec = nullptr;      // (col, type) pairs per sorted edge: the record stream of the reference-order kernel
@@ -94,10 +106,8 @@ struct DevicePlan {
     uint8_t *a16 = nullptr;         // ULTRA_PLAN_DENSE, 16-row tiles (fused layer kernel)
     uint8_t *a_ex = nullptr;        // ULTRA_PLAN_DENSE, reference-order layer kernel (dense_order_layer.hip)
     uint8_t *self_loop = nullptr;   // per node: bit 0 = has an edge onto itself, bit 1 = has an in-edge from another node (layer-0 path)
-    void *w_sorted = nullptr;
-    size_t w_sorted_bytes = 0;
-    void *w_sorted_cap = nullptr;     // the permuted weights of launches recorded into a hipGraph (replays never touch w_sorted)
-    size_t w_sorted_cap_bytes = 0;
+    // per-call edge weights in edge order: [0] of eager launches, [1] of launches recorded into a hipGraph (replays never touch [0])
+    WeightCopy w_copy[2];
     void *partial = nullptr;
     size_t partial_bytes = 0;
     // backward of the rspmm on listed rows as gathers (rows_bwd_kernels.hpp): the edge list grouped by source / by type, cut into
@@ -122,17 +132,6 @@ struct ultra_plan {
     int32_t seg_len = 256, g_max = 64, flags = 0;
     int32_t type_bits = 0;
     bool packed_ok = false;
-    // the weight vector whose permutation d.w_sorted holds (ultra_rspmm_weight_epoch): its tag, address, dtype, stream
-    int64_t w_epoch = 0;
-    const void *w_src = nullptr;
-    int32_t w_dtype = -1;
-    void *w_stream = nullptr;
-    // ... and the same for d.w_sorted_cap, valid inside the stream capture w_cap_id only
-    int64_t w_cap_epoch = 0;
-    const void *w_cap_src = nullptr;
-    int32_t w_cap_dtype = -1;
-    void *w_cap_stream = nullptr;
-    unsigned long long w_cap_id = 0;
     int32_t max_row_len = -1;     // longest row (edges); computed on first use (the layer-0 launch sizes its grid with it)
     // rows-backward index (d.rb_*): segments / owners with several segments / partial rows, by source and by type
     bool rb_built = false;

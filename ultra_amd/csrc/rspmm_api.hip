@@ -59,13 +59,14 @@ int launch_dense_layer(ultra_plan *p, const ultra_mat *rel, const ultra_mat *x, 
                        const ultra_mat *out, hipStream_t stream);   // dense_layer.hip
 
 static ultra_tuning g_tuning = {0, 0, -1, -1, 0, {0, 0, 0}};
+// ultra_tuning.reserved[], by the names ultra_amd/rspmm.py gives them
+static int general_walk() { return g_tuning.reserved[0]; }   // reference-order plans on the general walk kernel
+static int unit_walk() { return g_tuning.reserved[1]; }      // the order kernels walk units of four rows, not group streams
+static int update_form() { return g_tuning.reserved[2]; }    // where forward_update applies the layer update (choose_update_form)
 
-// measurement hook: when set, forward_impl records these events right before / after the main kernel launch
-static thread_local hipEvent_t g_ev_before = nullptr, g_ev_after = nullptr;
-// measurement hook: per-workgroup clock trace of the order kernel (ultra_order_trace)
+// measurement hook: per-workgroup clock trace of the order kernel.  State, not an argument: set by an ABI call of its own
+// (ultra_order_trace) and read by every order launch of the thread until it is cleared.
 static thread_local long long *g_order_trace = nullptr;
-// set by ultra_rspmm_forward_masked around its launch: the weight stream is a 0/1 keep mask (weigh(), rspmm_kernels.hpp)
-static thread_local int g_keep_mode = 0;
 // ultra_rspmm_weight_epoch: the caller's tag of the edge-weight vector it is about to pass (0 = none).  A plan that has
 // ALREADY brought the vector with this tag, at this address, into its own edge order keeps that copy: the fine-tuning step hands
 // one 0/1 keep vector to 5 forward and 10 backward walks, each of which would otherwise re-run the same permutation (24 us at
@@ -248,8 +249,8 @@ static void free_device(ultra_plan *p) {
     if (p->d.a16) (void)hipFree(p->d.a16);
     if (p->d.a_ex) (void)hipFree(p->d.a_ex);
     if (p->d.self_loop) (void)hipFree(p->d.self_loop);
-    if (p->d.w_sorted) (void)hipFree(p->d.w_sorted);
-    if (p->d.w_sorted_cap) (void)hipFree(p->d.w_sorted_cap);
+    for (WeightCopy &c : p->d.w_copy)
+        if (c.buf) (void)hipFree(c.buf);
     if (p->d.partial) (void)hipFree(p->d.partial);
     for (void *q : {p->d.rb_rec_c, p->d.rb_seg_c, p->d.rb_multi_c, p->d.rb_rec_t, p->d.rb_seg_t, p->d.rb_multi_t, p->d.rb_work})
         if (q) (void)hipFree(q);
@@ -296,6 +297,9 @@ static int device_info(DevInfo *out) {
     return ULTRA_OK;
 }
 
+// workgroups of a walk launch: the tuning's, else one per CU
+static int launch_grid(const DevInfo &di) { return std::max(1, g_tuning.grid > 0 ? g_tuning.grid : di.cu); }
+
 static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 static int check_mat(const ultra_mat *m, const char *name, int64_t min_rows, int64_t n_outer, int64_t row_len) {
@@ -311,14 +315,314 @@ static bool mat_vec_ok(const ultra_mat *m, int64_t step) {
     return aligned16(m->ptr) && (m->stride_row % step == 0) && (m->stride_outer % step == 0);
 }
 
-// Generic forward on a plan (internal: accepts the BIN_LHS / BIN_RHS variants used by backward).
-// bnd_rows != NULL: `bnd` is a POINT boundary -- one row per outer slice (n_row == 1), added to output row
-// bnd_rows[outer] only (the NBFNet boundary condition is zero everywhere else, models.py:135-141); sum aggregate only.
-// upd != NULL: the layer update of every output row is applied by the same launch (ultra_rspmm_forward_update); served by
-// the stream walk only -- ULTRA_ERR_UNSUPPORTED otherwise, with nothing launched.
+// What one forward call carries besides its operands.
+struct FwdCall {
+    // bnd_rows != NULL: `bnd` is a POINT boundary -- one row per outer slice (n_row == 1), added to output row
+    // bnd_rows[outer] only (the NBFNet boundary condition is zero everywhere else, models.py:135-141); sum aggregate only.
+    const int64_t *bnd_rows = nullptr;
+    // upd != NULL: the layer update of every output row is applied by the same launch (ultra_rspmm_forward_update); served by
+    // the stream walk only -- ULTRA_ERR_UNSUPPORTED otherwise, with nothing launched.
+    const OrderParams::Update *upd = nullptr;
+    int keep_mode = 0;      // ultra_rspmm_forward_masked: the weight stream is a 0/1 keep mask (weigh(), rspmm_kernels.hpp)
+    hipEvent_t ev_before = nullptr, ev_after = nullptr;   // measurement hook: recorded right before / after the main kernel launch
+};
+
+// Sums the partial rows of the plan's split rows into `dst` in slot order (after the walk that wrote them to q->d.partial).
+static int launch_fixup(const ultra_plan *q, const ultra_mat *dst, int sum, int dtype, int vec, hipStream_t stream,
+                        const MatArg *bnd = nullptr, const long long *bnd_rows = nullptr) {
+    if (q->split_row.empty()) return ULTRA_OK;
+    FixupParams xp;
+    std::memset(&xp, 0, sizeof(xp));
+    xp.split_row = q->d.split_row, xp.split_ptr = q->d.split_ptr;
+    xp.n_split = (int32_t)q->split_row.size();
+    xp.partial = q->d.partial;
+    if (bnd) xp.bnd = *bnd;
+    xp.bnd_rows = bnd_rows;
+    xp.has_bnd = bnd ? 1 : 0;
+    xp.out = dst->ptr, xp.out_stride_outer = dst->stride_outer, xp.out_stride_row = dst->stride_row;
+    xp.n_outer = (int32_t)dst->n_outer, xp.row_len = (int32_t)dst->row_len;
+    const long long total = (long long)xp.n_split * dst->n_outer * (dst->row_len / vec);
+    const int blocks = (int)std::min<long long>((total + 15) / 16, 16384);      // 16 output vectors per workgroup
+#define ULTRA_FIX(T_, V_)                                                                                          \
+    switch (sum) {                                                                                                \
+        case 0: hipLaunchKernelGGL((rspmm_fixup_kernel<T_, V_, 0>), dim3(blocks), dim3(256), 0, stream, xp); break; \
+        case 1: hipLaunchKernelGGL((rspmm_fixup_kernel<T_, V_, 1>), dim3(blocks), dim3(256), 0, stream, xp); break; \
+        default: hipLaunchKernelGGL((rspmm_fixup_kernel<T_, V_, 2>), dim3(blocks), dim3(256), 0, stream, xp); break; \
+    }
+    if (dtype == ULTRA_F32) {
+        if (vec == 4) { ULTRA_FIX(float, 4) } else { ULTRA_FIX(float, 1) }
+    } else {
+        if (vec == 4) { ULTRA_FIX(double, 4) } else { ULTRA_FIX(double, 1) }
+    }
+#undef ULTRA_FIX
+    HIP_TRY(hipGetLastError());
+    return ULTRA_OK;
+}
+
+// Per-call edge weights -> sorted order: *dst is the plan's copy of `w` in its own edge order, permuted by a launch on
+// `stream` unless the plan already holds this very vector (ultra_rspmm_weight_epoch).
+static int sorted_weights(ultra_plan *p, const void *w, int dtype, hipStream_t stream, const void **dst) {
+    // A launch that is being recorded into a hipGraph keeps its permuted copy in a buffer of its own (d.w_copy[1]): replays
+    // then never overwrite the copy an eager caller may still hold a tag for, and inside ONE capture a tagged vector is
+    // permuted once (a hit taken from outside the capture -- the warm-up runs -- would leave the replays without the
+    // permutation: the capture id is part of the key).
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    unsigned long long cap_id = 0;
+    if (hipStreamGetCaptureInfo(stream, &capturing, &cap_id) != hipSuccess) {
+        (void)hipGetLastError();
+        capturing = hipStreamCaptureStatusNone;
+    }
+    const bool in_cap = capturing != hipStreamCaptureStatusNone;
+    if (!in_cap) cap_id = 0;
+    const size_t w_bytes = (size_t)p->num_edge * (dtype == ULTRA_F32 ? 4 : 8);
+    WeightCopy &c = p->d.w_copy[in_cap ? 1 : 0];
+    int rc;
+    if (!in_cap) {      // (both buffers exist before any capture begins: no allocation while a stream records)
+        for (WeightCopy &b : p->d.w_copy)
+            if ((rc = ensure_scratch(&b.buf, &b.bytes, w_bytes, p))) return rc;
+    } else if (c.bytes < w_bytes) {
+        return invalid("a weighted rspmm call is being captured on a plan that has not served one eagerly (run the step once "
+                       "before capturing it: the plan's scratch buffers are allocated there)");
+    }
+    const bool hit = g_w_epoch != 0 && c.cap_id == cap_id && c.epoch == g_w_epoch && c.src == w && c.dtype == dtype && c.stream == stream;
+    if (!hit) {
+        const int blocks = (int)std::min<int64_t>((p->num_edge + 255) / 256, 4096);
+        if (dtype == ULTRA_F32)
+            hipLaunchKernelGGL(permute_weight_kernel<float>, dim3(blocks), dim3(256), 0, stream, (const float *)w,
+                               p->d.perm, (float *)c.buf, p->num_edge);
+        else
+            hipLaunchKernelGGL(permute_weight_kernel<double>, dim3(blocks), dim3(256), 0, stream, (const double *)w,
+                               p->d.perm, (double *)c.buf, p->num_edge);
+        HIP_TRY(hipGetLastError());
+        c.epoch = g_w_epoch, c.src = w, c.dtype = dtype, c.stream = stream, c.cap_id = cap_id;   // (epoch 0: untagged, never hit)
+    }
+    *dst = c.buf;
+    return ULTRA_OK;
+}
+
+// The dtype x VEC x MODE ladder of the walk kernels' launchers: calls launch(T(), VEC, MODE) with the element type as a
+// value and the two numbers as std::integral_constant.
+template <typename Launch>
+static hipError_t launch_walk_variant(int dtype, int vec, int mode, const Launch &launch) {
+    const auto of_type = [&](auto t) {
+        using std::integral_constant;
+        if (vec == 1) return launch(t, integral_constant<int, 1>(), integral_constant<int, 0>());
+        if (mode == 0) return launch(t, integral_constant<int, 4>(), integral_constant<int, 0>());
+        if (mode == 1) return launch(t, integral_constant<int, 4>(), integral_constant<int, 1>());
+        return launch(t, integral_constant<int, 4>(), integral_constant<int, 2>());
+    };
+    return dtype == ULTRA_F32 ? of_type(float()) : of_type(double());
+}
+
+// forward_update on the order kernel: which form applies the layer update -- 1, the tail after the walk, or 3, beside it --
+// with the LDS size and the stream / chain lists that form reads.  UNSUPPORTED where the call or the form asked for does not fit.
+static int choose_update_form(ultra_plan *p, const OrderParams::Update *upd, const Schedule *sched, const DevInfo &di,
+                              size_t rel_bytes, size_t ring_bytes, OrderParams *op, size_t *lds) {
+    int rc;
+    if (!op->use_streams || op->row_len != 64) {
+        set_error("ultra_rspmm_forward_update: this call is not served by the stream walk (fp32, 64-element rows, unit "
+                  "weights, relation slice in LDS, point boundary or none)");
+        return ULTRA_ERR_UNSUPPORTED;
+    }
+    op->upd = *upd;
+    op->upd.prow = sched->d_prow;
+    op->upd.prow_ptr = sched->d_prow_ptr;
+    op->upd.mode = 1;
+    *lds = std::max(*lds, (size_t)UPDATE_LDS_FLOATS * sizeof(float));   // (the weight image takes the dead relation slice's place)
+    Schedule *sched12 = nullptr;
+    // (the form beside the walk reads the twelve-walker schedules, whose records are pre-multiplied by the 256-byte pitch
+    // of whole-span rows: plan.hpp ULTRA_STREAM_PRESHIFT)
+    const bool pitch_ok = !ULTRA_STREAM_PRESHIFT || op->x_row_bytes == 256u;
+    // Form 3: beside the walk with the rows passing through LDS -- the walkers park every finished aggregate row AND its x
+    // row (a marker step gathers at its own row's offset) in a 64-row ring; the update waves keep the weight matrix in
+    // registers, so the room is there even beside a 474-relation slice, and they take no memory round trip (DESIGN.md
+    // 3.8c).  Measured on MI355X, layer in a hipGraph, against the tail form: FB15k237 bs 8 85.7 us vs 94.4, bs 16 166 vs
+    // 192, bs 4 68.5 vs 69.6, max aggregate 110.6 vs 113.7, CoDEx-L bs 8 324 vs 375 -- but WN18RR bs 8 141 vs 128: with 5
+    // steps a row the update is most of the work, and here only four of the sixteen waves do it.  So: on request
+    // (ultra_tuning.reserved[2] == 3) always, by default (0) from 10 steps a row up; 1 asks for the tail form.
+    const bool walk_heavy = (double)(p->num_edge + p->num_out) >= 10.0 * (double)p->num_out;
+    const bool want3 = update_form() == 3 || (update_form() == 0 && walk_heavy);
+    if (want3 && pitch_ok && ORDER_WAVES == 16 && upd->out_stride_row * (int64_t)sizeof(float) == (int64_t)op->x_row_bytes) {
+        if ((rc = get_schedule(p, op->nparts, &sched12, ORDER_WALKERS))) return rc;
+        const size_t overlay = std::max(ring_bytes, (size_t)UPD2_OVERLAY_BYTES);
+        const size_t need = rel_bytes + overlay + UPD2_CTL_BYTES;
+        if (need <= di.lds_optin && sched12->max_chain_rows <= UPD2_MAX_CHAIN_ROWS) {
+            op->upd.mode = 3;
+            op->max_stream_steps = sched12->max_stream_steps;
+            op->upd.ctl_off = (uint32_t)(rel_bytes + overlay);
+            op->srec = sched12->d_srec;
+            op->sdesc = reinterpret_cast<const int2 *>(sched12->d_sdesc);
+            op->chunk_ptr = sched12->d_chunk_ptr;      // (its own chain list: shorter chain rows are stream rows there)
+            op->chunks = reinterpret_cast<const int4 *>(sched12->d_chunks);
+            *lds = need;
+        }
+    }
+    if (update_form() == 2) {
+        set_error("ultra_rspmm_forward_update: update form 2 (rows by reference) was removed in ABI 6; ask for 0 (the library's "
+                  "choice), 1 (tail) or 3 (beside the walk, rows through LDS)");
+        return ULTRA_ERR_UNSUPPORTED;
+    }
+    if (update_form() >= 2 && op->upd.mode != update_form()) {
+        set_error("ultra_rspmm_forward_update: the update beside the walk does not fit this call (LDS / rows per workgroup)");
+        return ULTRA_ERR_UNSUPPORTED;
+    }
+    return ULTRA_OK;
+}
+
+// The operands of a forward call as both kernel routes read them (forward_impl has checked them).
+static FwdParams fwd_params(const ultra_plan *p, int mul, const void *w, const ultra_mat *rel, const ultra_mat *x,
+                            const ultra_mat *bnd, const ultra_mat *out, int SPAN, int64_t esz, const FwdCall &call) {
+    const int64_t *bnd_rows = call.bnd_rows;
+    FwdParams fp;
+    std::memset(&fp, 0, sizeof(fp));
+    fp.col = p->d.col;
+    fp.type = p->d.type;
+    fp.packed = p->d.packed;
+    fp.items = p->d.items;
+    fp.n_w = (int32_t)p->n_w;
+    fp.n_item = (int32_t)p->items.size();
+    fp.n_unit = (int32_t)p->n_unit;
+    if (mul != BIN_RHS) fp.rel = MatArg{rel->ptr, rel->stride_outer, rel->stride_row};
+    if (mul != BIN_LHS) fp.x = MatArg{x->ptr, x->stride_outer, x->stride_row};
+    if (bnd) fp.bnd = MatArg{bnd->ptr, bnd->stride_outer, bnd_rows ? 0 : bnd->stride_row};
+    fp.bnd_rows = bnd ? reinterpret_cast<const long long *>(bnd_rows) : nullptr;
+    fp.out = out->ptr;
+    fp.out_stride_outer = out->stride_outer;
+    fp.out_stride_row = out->stride_row;
+    fp.n_outer = (int32_t)out->n_outer;
+    fp.row_len = (int32_t)out->row_len;
+    fp.spans_per_outer = (int32_t)((out->row_len + SPAN - 1) / SPAN);
+    fp.n_span = fp.spans_per_outer * fp.n_outer;
+    fp.num_rel = (int32_t)p->num_rel;
+    fp.num_in = (int32_t)p->num_in;
+    fp.type_bits = p->type_bits;
+    fp.unit_w = w ? 0 : 1;
+    fp.packed_on = p->packed_ok ? 1 : 0;
+    fp.has_bnd = bnd ? 1 : 0;
+    fp.keep_mode = (w && call.keep_mode) ? 1 : 0;
+    if (mul != BIN_LHS) fp.x_row_bytes = (uint32_t)(x->stride_row * esz);
+    if (mul != BIN_RHS) fp.rel_row_bytes = (uint32_t)(rel->stride_row * esz);
+    fp.rot_half_bytes = (uint32_t)((out->row_len / 2) * esz);
+    return fp;
+}
+
+// Reference-order plans: the order kernels (no scratch, no fix-up launch).  `fp` describes the operands (forward_impl).
+static int forward_order(ultra_plan *p, int sum, int mul, int dtype, const void *w, const ultra_mat *x, const ultra_mat *bnd,
+                         const ultra_mat *out, hipStream_t stream, const FwdCall &call, const FwdParams &fp, const DevInfo &di,
+                         size_t ring_bytes, bool point_fill) {
+    const size_t esz = dtype == ULTRA_F32 ? 4 : 8;
+    const int64_t row_len = out->row_len;
+    const int64_t *bnd_rows = call.bnd_rows;
+    int rc;
+    // (+ one row: the stream walk's row markers carry relation index num_rel)
+    const size_t rel_bytes = (mul != BIN_RHS) ? (size_t)(p->num_rel + 1) * 64 * esz : 0;
+    const bool rel_lds = g_tuning.rel_lds != 0 && rel_bytes > 0 && rel_bytes + ring_bytes <= di.lds_optin;
+    const int grid = launch_grid(di);
+    OrderParams op;
+    std::memset(&op, 0, sizeof(op));
+    op.smod = std::min<int32_t>(fp.n_span, grid);
+    op.nparts = grid / op.smod;
+    Schedule *sched = nullptr;
+    if ((rc = get_schedule(p, op.nparts, &sched))) return rc;
+    op.rec = p->d.rec;
+    op.perm = p->d.perm;
+    op.w = w;
+    op.items = reinterpret_cast<const int4 *>(p->d.items);
+    op.unit_ptr = sched->d_unit_ptr;
+    op.units = sched->d_units;
+    op.chunk_ptr = sched->d_chunk_ptr;
+    op.chunks = reinterpret_cast<const int4 *>(sched->d_chunks);
+    op.n_chain = (int32_t)p->n_chain;
+    op.n_item = (int32_t)p->items.size();
+    op.rel = fp.rel, op.x = fp.x, op.bnd = fp.bnd;
+    op.bnd_rows = fp.bnd_rows;
+    op.bnd_fill_on = point_fill ? 1 : 0;
+    op.bnd_fill = 0.f;
+    op.out = fp.out;
+    op.out_stride_outer = fp.out_stride_outer, op.out_stride_row = fp.out_stride_row;
+    op.n_outer = fp.n_outer, op.row_len = fp.row_len, op.spans_per_outer = fp.spans_per_outer, op.n_span = fp.n_span;
+    op.num_rel = fp.num_rel;
+    op.has_bnd = fp.has_bnd;
+    op.has_chain = p->n_chain > 0 ? 1 : 0;
+    op.keep_mode = fp.keep_mode;
+    op.x_row_bytes = fp.x_row_bytes, op.rel_row_bytes = fp.rel_row_bytes;
+    op.trace = g_order_trace;
+    op.err = device_error_word();
+    // The group streams (assembly walk) serve the inference configuration: fp32, unit weights, relation slice in
+    // LDS, mul / add messages, whole 64-element spans, no boundary or a point boundary, source and output rows of
+    // one stride (a marker's gather offset is its store offset), every output row also a source row.
+    op.srec = sched->d_srec;
+    op.sdesc = reinterpret_cast<const int2 *>(sched->d_sdesc);
+    op.use_streams = (unit_walk() == 0 && dtype == ULTRA_F32 && rel_lds && !w && (mul == BIN_MUL || mul == BIN_ADD) &&
+                      row_len % 64 == 0 && (!bnd || bnd_rows) && out->stride_row == x->stride_row &&
+                      p->num_out <= p->num_in && (uint64_t)p->num_out * (uint64_t)out->stride_row * esz < (1ull << 32))
+                         ? 1
+                         : 0;
+    size_t lds = (rel_lds ? rel_bytes : 0) + ring_bytes;
+    if (call.upd && (rc = choose_update_form(p, call.upd, sched, di, rel_bytes, ring_bytes, &op, &lds))) return rc;
+    if (call.ev_before) HIP_TRY(hipEventRecord(call.ev_before, stream));
+#define ULTRA_ORDER_LAUNCH(T_)                                                                          \
+    (rel_lds ? (w ? launch_order_variant<T_, true, true>(sum, mul, op, grid, lds, stream)                \
+                  : launch_order_variant<T_, true, false>(sum, mul, op, grid, lds, stream))              \
+             : (w ? launch_order_variant<T_, false, true>(sum, mul, op, grid, lds, stream)               \
+                  : launch_order_variant<T_, false, false>(sum, mul, op, grid, lds, stream)))
+    const hipError_t e = dtype == ULTRA_F32 ? ULTRA_ORDER_LAUNCH(float) : ULTRA_ORDER_LAUNCH(double);
+#undef ULTRA_ORDER_LAUNCH
+    if (e != hipSuccess) return hip_fail(e, "rspmm_order_kernel launch");
+    if (call.ev_after) HIP_TRY(hipEventRecord(call.ev_after, stream));
+    return ULTRA_OK;
+}
+
+// The general walk (rotate messages included) and the fix-up launch of its split rows.  `fp` describes the operands
+// (forward_impl); the route adds what is its own: sorted weights, the partial rows, the launch geometry.
+static int forward_walk(ultra_plan *p, int sum, int mul, int dtype, const void *w, const ultra_mat *bnd, const ultra_mat *out,
+                        hipStream_t stream, const FwdCall &call, FwdParams &fp, const DevInfo &di, int VEC, bool rot_far) {
+    const size_t esz = dtype == ULTRA_F32 ? 4 : 8;
+    const bool rot = bin_is_rot(mul);
+    int rc;
+    if (w && p->num_edge > 0 && (rc = sorted_weights(p, w, dtype, stream, &fp.w_sorted))) return rc;
+    if (p->n_slot > 0) {
+        if ((rc = ensure_scratch(&p->d.partial, &p->d.partial_bytes, (size_t)p->n_slot * fp.n_outer * fp.row_len * esz, p)))
+            return rc;
+        fp.partial = p->d.partial;
+    }
+
+    // variant selection
+    const int SPAN = 16 * VEC;
+    const size_t rel_bytes = (mul != BIN_RHS) ? (size_t)p->num_rel * SPAN * esz : 0;
+    const size_t x_bytes = (mul != BIN_LHS) ? (size_t)p->num_in * SPAN * esz : 0;
+    int mode = MODE_GLOBAL;
+    if (VEC == 4 && !rot_far) {
+        if (g_tuning.x_lds != 0 && g_tuning.rel_lds != 0 && rel_bytes + x_bytes <= di.lds_optin && x_bytes > 0)
+            mode = MODE_ALL_LDS;
+        else if (g_tuning.rel_lds != 0 && rel_bytes <= di.lds_optin && rel_bytes > 0)
+            mode = MODE_REL_LDS;
+    }
+    const size_t lds = mode == MODE_ALL_LDS ? rel_bytes + x_bytes : (mode == MODE_REL_LDS ? rel_bytes : 0);
+    const int threads = g_tuning.threads > 0 ? g_tuning.threads : 1024;
+    const int grid = launch_grid(di);
+    fp.smod = std::min<int32_t>(fp.n_span, grid);
+    fp.nparts = grid / fp.smod;
+
+    if (call.ev_before) HIP_TRY(hipEventRecord(call.ev_before, stream));
+    const int rmul = rot_far ? mul + (BIN_ROTG - BIN_ROT) : mul;
+    const hipError_t e = launch_walk_variant(dtype, VEC, mode, [&](auto t, auto vec, auto lds_mode) {
+        using T = decltype(t);
+        constexpr int V = decltype(vec)::value, M = decltype(lds_mode)::value;
+        return rot ? launch_rot_variant<T, V, M>(sum, rmul, fp, grid, threads, lds, stream)
+                   : launch_fwd_variant<T, V, M>(sum, mul, fp, grid, threads, lds, stream);
+    });
+    if (e != hipSuccess) return hip_fail(e, "rspmm_fwd_kernel launch");
+    if (call.ev_after) HIP_TRY(hipEventRecord(call.ev_after, stream));
+    return launch_fixup(p, out, sum, dtype, VEC, stream, bnd ? &fp.bnd : nullptr, fp.bnd_rows);
+}
+
+// Generic forward on a plan (internal: accepts the BIN_LHS / BIN_RHS variants used by backward): validates, describes the
+// operands, and hands the call to the one route that serves it -- the dense format, the reference-order kernels or the walk.
 static int forward_impl(ultra_plan *p, int sum, int mul, int dtype, const void *w, const ultra_mat *rel,
                         const ultra_mat *x, const ultra_mat *bnd, const ultra_mat *out, hipStream_t stream,
-                        const int64_t *bnd_rows = nullptr, const OrderParams::Update *upd = nullptr) {
+                        const FwdCall &call = FwdCall()) {
+    const int64_t *bnd_rows = call.bnd_rows;
     if (!p) return invalid("plan is NULL");
     (void)hipGetLastError();   // drop any stale error left by other users of the HIP runtime
     if (int derr = take_device_error()) return derr;   // (an earlier launch ended on a bounded wait: say so now)
@@ -342,7 +646,7 @@ static int forward_impl(ultra_plan *p, int sum, int mul, int dtype, const void *
     if (bnd && (rc = check_mat(bnd, "boundary", bnd_rows ? 1 : p->num_out, n_outer, row_len))) return rc;
     if (p->num_out == 0) return ULTRA_OK;
     if ((rc = upload_plan(p))) return rc;
-    if (upd && ((p->flags & ULTRA_PLAN_DENSE) || !(p->flags & ULTRA_PLAN_EXACT_ORDER))) {
+    if (call.upd && ((p->flags & ULTRA_PLAN_DENSE) || !(p->flags & ULTRA_PLAN_EXACT_ORDER))) {
         set_error("ultra_rspmm_forward_update: served by reference-order plans in the sparse format only");
         return ULTRA_ERR_UNSUPPORTED;
     }
@@ -355,9 +659,9 @@ static int forward_impl(ultra_plan *p, int sum, int mul, int dtype, const void *
         return ULTRA_ERR_UNSUPPORTED;
     }
     if (p->flags & ULTRA_PLAN_DENSE) {
-        if (g_ev_before) HIP_TRY(hipEventRecord(g_ev_before, stream));
+        if (call.ev_before) HIP_TRY(hipEventRecord(call.ev_before, stream));
         if ((rc = launch_dense_forward(p, sum, mul, dtype, w, rel, x, bnd, bnd_rows, out, stream))) return rc;
-        if (g_ev_after) HIP_TRY(hipEventRecord(g_ev_after, stream));
+        if (call.ev_after) HIP_TRY(hipEventRecord(call.ev_after, stream));
         return ULTRA_OK;
     }
     DevInfo di;
@@ -377,33 +681,6 @@ static int forward_impl(ultra_plan *p, int sum, int mul, int dtype, const void *
     // Every other row length loads it (the BIN_ROTG* kernels, operands through L2).
     const bool rot_far = rot && !(VEC == 4 && row_len == SPAN);
 
-    FwdParams fp;
-    std::memset(&fp, 0, sizeof(fp));
-    fp.col = p->d.col;
-    fp.type = p->d.type;
-    fp.packed = p->d.packed;
-    fp.items = p->d.items;
-    fp.n_w = (int32_t)p->n_w;
-    fp.n_item = (int32_t)p->items.size();
-    fp.n_unit = (int32_t)p->n_unit;
-    if (mul != BIN_RHS) fp.rel = MatArg{rel->ptr, rel->stride_outer, rel->stride_row};
-    if (mul != BIN_LHS) fp.x = MatArg{x->ptr, x->stride_outer, x->stride_row};
-    if (bnd) fp.bnd = MatArg{bnd->ptr, bnd->stride_outer, bnd_rows ? 0 : bnd->stride_row};
-    fp.bnd_rows = bnd ? reinterpret_cast<const long long *>(bnd_rows) : nullptr;
-    fp.out = out->ptr;
-    fp.out_stride_outer = out->stride_outer;
-    fp.out_stride_row = out->stride_row;
-    fp.n_outer = (int32_t)n_outer;
-    fp.row_len = (int32_t)row_len;
-    fp.spans_per_outer = (int32_t)((row_len + SPAN - 1) / SPAN);
-    fp.n_span = fp.spans_per_outer * fp.n_outer;
-    fp.num_rel = (int32_t)p->num_rel;
-    fp.num_in = (int32_t)p->num_in;
-    fp.type_bits = p->type_bits;
-    fp.unit_w = w ? 0 : 1;
-    fp.packed_on = p->packed_ok ? 1 : 0;
-    fp.has_bnd = bnd ? 1 : 0;
-    fp.keep_mode = (w && g_keep_mode) ? 1 : 0;
     if ((p->flags & ULTRA_PLAN_TYPE_RUNS) && !(p->flags & ULTRA_PLAN_EXACT_ORDER)) {
         if (!(sum == ULTRA_SUM_ADD && mul == BIN_MUL)) {
             set_error("a ULTRA_PLAN_TYPE_RUNS plan serves add_mul only (distributivity)");
@@ -418,130 +695,17 @@ static int forward_impl(ultra_plan *p, int sum, int mul, int dtype, const void *
         set_error("rspmm: an operand slice (rows * stride_row) exceeds 4 GiB; use the batch-major layout");
         return ULTRA_ERR_UNSUPPORTED;
     }
-    if (mul != BIN_LHS) fp.x_row_bytes = (uint32_t)(x->stride_row * (int64_t)esz);
-    if (mul != BIN_RHS) fp.rel_row_bytes = (uint32_t)(rel->stride_row * (int64_t)esz);
-    fp.rot_half_bytes = (uint32_t)((row_len / 2) * (int64_t)esz);
+    FwdParams fp = fwd_params(p, mul, w, rel, x, bnd, out, SPAN, (int64_t)esz, call);
 
-    // ---- reference-order plans: the order kernels (no scratch, no fix-up launch) ----
-    // (rotate: reference-order plans are walked by the general kernel below -- one 16-lane group per row, chain rows included,
+    // (rotate: reference-order plans are walked by the general kernel -- one 16-lane group per row, chain rows included,
     // in sorted edge order; the order kernels and their generated walks serve mul / add)
-    if ((p->flags & ULTRA_PLAN_EXACT_ORDER) && !rot && VEC == 4 && g_tuning.reserved[0] == 0 && p->num_in < (1 << 24) &&
+    // ring: [2 halves][15 quads][64 lanes][4 messages]
+    const size_t ring_bytes = p->n_chain > 0 ? (size_t)2 * CHAIN_SLOTS * 64 * esz : 0;
+    if ((p->flags & ULTRA_PLAN_EXACT_ORDER) && !rot && VEC == 4 && general_walk() == 0 && p->num_in < (1 << 24) &&
         p->num_rel < (1 << 24) && (mul == BIN_LHS || x->stride_row * (int64_t)esz < (1 << 24)) &&
-        (mul == BIN_RHS || rel->stride_row * (int64_t)esz < (1 << 24))) {
-        // (+ one row: the stream walk's row markers carry relation index num_rel)
-        const size_t rel_bytes = (mul != BIN_RHS) ? (size_t)(p->num_rel + 1) * 64 * esz : 0;
-        // ring: [2 halves][15 quads][64 lanes][4 messages]
-        const size_t ring_bytes = p->n_chain > 0 ? (size_t)2 * CHAIN_SLOTS * 64 * esz : 0;
-        if (ring_bytes <= di.lds_optin) {
-            const bool rel_lds = g_tuning.rel_lds != 0 && rel_bytes > 0 && rel_bytes + ring_bytes <= di.lds_optin;
-            int grid = g_tuning.grid > 0 ? g_tuning.grid : di.cu;
-            if (grid < 1) grid = 1;
-            OrderParams op;
-            std::memset(&op, 0, sizeof(op));
-            op.smod = std::min<int32_t>(fp.n_span, grid);
-            op.nparts = grid / op.smod;
-            Schedule *sched = nullptr;
-            if ((rc = get_schedule(p, op.nparts, &sched))) return rc;
-            op.rec = p->d.rec;
-            op.perm = p->d.perm;
-            op.w = w;
-            op.items = reinterpret_cast<const int4 *>(p->d.items);
-            op.unit_ptr = sched->d_unit_ptr;
-            op.units = sched->d_units;
-            op.chunk_ptr = sched->d_chunk_ptr;
-            op.chunks = reinterpret_cast<const int4 *>(sched->d_chunks);
-            op.n_chain = (int32_t)p->n_chain;
-            op.n_item = (int32_t)p->items.size();
-            op.rel = fp.rel, op.x = fp.x, op.bnd = fp.bnd;
-            op.bnd_rows = fp.bnd_rows;
-            op.bnd_fill_on = point_fill ? 1 : 0;
-            op.bnd_fill = 0.f;
-            op.out = fp.out;
-            op.out_stride_outer = fp.out_stride_outer, op.out_stride_row = fp.out_stride_row;
-            op.n_outer = fp.n_outer, op.row_len = fp.row_len, op.spans_per_outer = fp.spans_per_outer, op.n_span = fp.n_span;
-            op.num_rel = fp.num_rel;
-            op.has_bnd = fp.has_bnd;
-            op.has_chain = p->n_chain > 0 ? 1 : 0;
-            op.keep_mode = fp.keep_mode;
-            op.x_row_bytes = fp.x_row_bytes, op.rel_row_bytes = fp.rel_row_bytes;
-            op.trace = g_order_trace;
-            op.err = device_error_word();
-            // The group streams (assembly walk) serve the inference configuration: fp32, unit weights, relation slice in
-            // LDS, mul / add messages, whole 64-element spans, no boundary or a point boundary, source and output rows of
-            // one stride (a marker's gather offset is its store offset), every output row also a source row.
-            op.srec = sched->d_srec;
-            op.sdesc = reinterpret_cast<const int2 *>(sched->d_sdesc);
-            op.use_streams = (g_tuning.reserved[1] == 0 && dtype == ULTRA_F32 && rel_lds && !w && (mul == BIN_MUL || mul == BIN_ADD) &&
-                              row_len % 64 == 0 && (!bnd || bnd_rows) && out->stride_row == x->stride_row &&
-                              p->num_out <= p->num_in && (uint64_t)p->num_out * (uint64_t)out->stride_row * esz < (1ull << 32))
-                                 ? 1
-                                 : 0;
-            size_t lds = (rel_lds ? rel_bytes : 0) + ring_bytes;
-            if (upd) {
-                if (!op.use_streams || row_len != 64) {
-                    set_error("ultra_rspmm_forward_update: this call is not served by the stream walk (fp32, 64-element rows, unit "
-                              "weights, relation slice in LDS, point boundary or none)");
-                    return ULTRA_ERR_UNSUPPORTED;
-                }
-                op.upd = *upd;
-                op.upd.prow = sched->d_prow;
-                op.upd.prow_ptr = sched->d_prow_ptr;
-                op.upd.mode = 1;
-                lds = std::max(lds, (size_t)UPDATE_LDS_FLOATS * sizeof(float));   // (the weight image takes the dead relation slice's place)
-                Schedule *sched12 = nullptr;
-                // (the form beside the walk reads the twelve-walker schedules, whose records are pre-multiplied by the 256-byte pitch
-                // of whole-span rows: plan.hpp ULTRA_STREAM_PRESHIFT)
-                const bool pitch_ok = !ULTRA_STREAM_PRESHIFT || op.x_row_bytes == 256u;
-                // Form 3: beside the walk with the rows passing through LDS -- the walkers park every finished aggregate row AND its x
-                // row (a marker step gathers at its own row's offset) in a 64-row ring; the update waves keep the weight matrix in
-                // registers, so the room is there even beside a 474-relation slice, and they take no memory round trip (DESIGN.md
-                // 3.8c).  Measured on MI355X, layer in a hipGraph, against the tail form: FB15k237 bs 8 85.7 us vs 94.4, bs 16 166 vs
-                // 192, bs 4 68.5 vs 69.6, max aggregate 110.6 vs 113.7, CoDEx-L bs 8 324 vs 375 -- but WN18RR bs 8 141 vs 128: with 5
-                // steps a row the update is most of the work, and here only four of the sixteen waves do it.  So: on request
-                // (ultra_tuning.reserved[2] == 3) always, by default (0) from 10 steps a row up; 1 asks for the tail form.
-                const bool walk_heavy = (double)(p->num_edge + p->num_out) >= 10.0 * (double)p->num_out;
-                const bool want3 = g_tuning.reserved[2] == 3 || (g_tuning.reserved[2] == 0 && walk_heavy);
-                if (want3 && pitch_ok && ORDER_WAVES == 16 && upd->out_stride_row * (int64_t)sizeof(float) == (int64_t)op.x_row_bytes) {
-                    if ((rc = get_schedule(p, op.nparts, &sched12, ORDER_WALKERS))) return rc;
-                    const size_t overlay = std::max(ring_bytes, (size_t)UPD2_OVERLAY_BYTES);
-                    const size_t need = rel_bytes + overlay + UPD2_CTL_BYTES;
-                    if (need <= di.lds_optin && sched12->max_chain_rows <= UPD2_MAX_CHAIN_ROWS) {
-                        op.upd.mode = 3;
-                        op.max_stream_steps = sched12->max_stream_steps;
-                        op.upd.ctl_off = (uint32_t)(rel_bytes + overlay);
-                        op.srec = sched12->d_srec;
-                        op.sdesc = reinterpret_cast<const int2 *>(sched12->d_sdesc);
-                        op.chunk_ptr = sched12->d_chunk_ptr;      // (its own chain list: shorter chain rows are stream rows there)
-                        op.chunks = reinterpret_cast<const int4 *>(sched12->d_chunks);
-                        lds = need;
-                    }
-                }
-                if (g_tuning.reserved[2] == 2) {
-                    set_error("ultra_rspmm_forward_update: update form 2 (rows by reference) was removed in ABI 6; ask for 0 (the library's "
-                              "choice), 1 (tail) or 3 (beside the walk, rows through LDS)");
-                    return ULTRA_ERR_UNSUPPORTED;
-                }
-                if (g_tuning.reserved[2] >= 2 && op.upd.mode != g_tuning.reserved[2]) {
-                    set_error("ultra_rspmm_forward_update: the update beside the walk does not fit this call (LDS / rows per workgroup)");
-                    return ULTRA_ERR_UNSUPPORTED;
-                }
-            }
-            hipError_t e = hipErrorInvalidValue;
-            if (g_ev_before) HIP_TRY(hipEventRecord(g_ev_before, stream));
-#define ULTRA_ORDER_LAUNCH(T_)                                                                          \
-    (rel_lds ? (w ? launch_order_variant<T_, true, true>(sum, mul, op, grid, lds, stream)                \
-                  : launch_order_variant<T_, true, false>(sum, mul, op, grid, lds, stream))              \
-             : (w ? launch_order_variant<T_, false, true>(sum, mul, op, grid, lds, stream)               \
-                  : launch_order_variant<T_, false, false>(sum, mul, op, grid, lds, stream)))
-            e = dtype == ULTRA_F32 ? ULTRA_ORDER_LAUNCH(float) : ULTRA_ORDER_LAUNCH(double);
-#undef ULTRA_ORDER_LAUNCH
-            if (e != hipSuccess) return hip_fail(e, "rspmm_order_kernel launch");
-            if (g_ev_after) HIP_TRY(hipEventRecord(g_ev_after, stream));
-            return ULTRA_OK;
-        }
-    }
-
-    if (upd) {
+        (mul == BIN_RHS || rel->stride_row * (int64_t)esz < (1 << 24)) && ring_bytes <= di.lds_optin)
+        return forward_order(p, sum, mul, dtype, w, x, bnd, out, stream, call, fp, di, ring_bytes, point_fill);
+    if (call.upd) {
         set_error("ultra_rspmm_forward_update: this call is not served by the reference-order kernels");
         return ULTRA_ERR_UNSUPPORTED;
     }
@@ -554,136 +718,7 @@ static int forward_impl(ultra_plan *p, int sum, int mul, int dtype, const void *
                   "alignment or tuning); pass the boundary as a tensor");
         return ULTRA_ERR_UNSUPPORTED;
     }
-    // per-call edge weights -> sorted order
-    if (w && p->num_edge > 0) {
-        // A launch that is being recorded into a hipGraph keeps its permuted copy in a buffer of its own (d.w_sorted_cap): replays
-        // then never overwrite the copy an eager caller may still hold a tag for, and inside ONE capture a tagged vector is
-        // permuted once (a hit taken from outside the capture -- the warm-up runs -- would leave the replays without the
-        // permutation: the capture id is part of the key).
-        hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-        unsigned long long cap_id = 0;
-        if (hipStreamGetCaptureInfo(stream, &capturing, &cap_id) != hipSuccess) {
-            (void)hipGetLastError();
-            capturing = hipStreamCaptureStatusNone;
-        }
-        const bool in_cap = capturing != hipStreamCaptureStatusNone;
-        const bool tagged = g_w_epoch != 0;
-        const size_t w_bytes = (size_t)p->num_edge * esz;
-        if (!in_cap) {      // (both buffers exist before any capture begins: no allocation while a stream records)
-            if ((rc = ensure_scratch(&p->d.w_sorted, &p->d.w_sorted_bytes, w_bytes, p))) return rc;
-            if ((rc = ensure_scratch(&p->d.w_sorted_cap, &p->d.w_sorted_cap_bytes, w_bytes, p))) return rc;
-        } else if (p->d.w_sorted_cap_bytes < w_bytes) {
-            return invalid("a weighted rspmm call is being captured on a plan that has not served one eagerly (run the step once "
-                           "before capturing it: the plan's scratch buffers are allocated there)");
-        }
-        void *dst = in_cap ? p->d.w_sorted_cap : p->d.w_sorted;
-        const bool hit = tagged && (in_cap ? (p->w_cap_id == cap_id && p->w_cap_epoch == g_w_epoch && p->w_cap_src == w &&
-                                              p->w_cap_dtype == dtype && p->w_cap_stream == stream)
-                                           : (p->w_epoch == g_w_epoch && p->w_src == w && p->w_dtype == dtype && p->w_stream == stream));
-        if (!hit) {
-            const int blocks = (int)std::min<int64_t>((p->num_edge + 255) / 256, 4096);
-            if (dtype == ULTRA_F32)
-                hipLaunchKernelGGL(permute_weight_kernel<float>, dim3(blocks), dim3(256), 0, stream, (const float *)w,
-                                   p->d.perm, (float *)dst, p->num_edge);
-            else
-                hipLaunchKernelGGL(permute_weight_kernel<double>, dim3(blocks), dim3(256), 0, stream, (const double *)w,
-                                   p->d.perm, (double *)dst, p->num_edge);
-            HIP_TRY(hipGetLastError());
-            if (in_cap) {
-                p->w_cap_epoch = tagged ? g_w_epoch : 0;
-                p->w_cap_src = w, p->w_cap_dtype = dtype, p->w_cap_stream = stream, p->w_cap_id = cap_id;
-            } else {
-                p->w_epoch = tagged ? g_w_epoch : 0;
-                p->w_src = w, p->w_dtype = dtype, p->w_stream = stream;
-            }
-        }
-        fp.w_sorted = dst;
-    }
-    if (p->n_slot > 0) {
-        if ((rc = ensure_scratch(&p->d.partial, &p->d.partial_bytes, (size_t)p->n_slot * n_outer * row_len * esz, p)))
-            return rc;
-        fp.partial = p->d.partial;
-    }
-
-    // variant selection
-    const size_t budget = di.lds_optin;
-    const size_t rel_bytes = (mul != BIN_RHS) ? (size_t)p->num_rel * SPAN * esz : 0;
-    const size_t x_bytes = (mul != BIN_LHS) ? (size_t)p->num_in * SPAN * esz : 0;
-    int mode = MODE_GLOBAL;
-    if (VEC == 4 && !rot_far) {
-        if (g_tuning.x_lds != 0 && g_tuning.rel_lds != 0 && rel_bytes + x_bytes <= budget && x_bytes > 0)
-            mode = MODE_ALL_LDS;
-        else if (g_tuning.rel_lds != 0 && rel_bytes <= budget && rel_bytes > 0)
-            mode = MODE_REL_LDS;
-    }
-    const size_t lds = mode == MODE_ALL_LDS ? rel_bytes + x_bytes : (mode == MODE_REL_LDS ? rel_bytes : 0);
-    const int threads = g_tuning.threads > 0 ? g_tuning.threads : 1024;
-    int grid = g_tuning.grid > 0 ? g_tuning.grid : di.cu;
-    if (grid < 1) grid = 1;
-    fp.smod = std::min<int32_t>(fp.n_span, grid);
-    fp.nparts = grid / fp.smod;
-
-    hipError_t e = hipErrorInvalidValue;
-    if (g_ev_before) HIP_TRY(hipEventRecord(g_ev_before, stream));
-    if (rot) {
-        const int rmul = rot_far ? mul + (BIN_ROTG - BIN_ROT) : mul;
-        if (dtype == ULTRA_F32) {
-            if (VEC == 1) e = launch_rot_variant<float, 1, 0>(sum, rmul, fp, grid, threads, lds, stream);
-            else if (mode == 0) e = launch_rot_variant<float, 4, 0>(sum, rmul, fp, grid, threads, lds, stream);
-            else if (mode == 1) e = launch_rot_variant<float, 4, 1>(sum, rmul, fp, grid, threads, lds, stream);
-            else e = launch_rot_variant<float, 4, 2>(sum, rmul, fp, grid, threads, lds, stream);
-        } else {
-            if (VEC == 1) e = launch_rot_variant<double, 1, 0>(sum, rmul, fp, grid, threads, lds, stream);
-            else if (mode == 0) e = launch_rot_variant<double, 4, 0>(sum, rmul, fp, grid, threads, lds, stream);
-            else if (mode == 1) e = launch_rot_variant<double, 4, 1>(sum, rmul, fp, grid, threads, lds, stream);
-            else e = launch_rot_variant<double, 4, 2>(sum, rmul, fp, grid, threads, lds, stream);
-        }
-    } else if (dtype == ULTRA_F32) {
-        if (VEC == 1) e = launch_fwd_variant<float, 1, 0>(sum, mul, fp, grid, threads, lds, stream);
-        else if (mode == 0) e = launch_fwd_variant<float, 4, 0>(sum, mul, fp, grid, threads, lds, stream);
-        else if (mode == 1) e = launch_fwd_variant<float, 4, 1>(sum, mul, fp, grid, threads, lds, stream);
-        else e = launch_fwd_variant<float, 4, 2>(sum, mul, fp, grid, threads, lds, stream);
-    } else {
-        if (VEC == 1) e = launch_fwd_variant<double, 1, 0>(sum, mul, fp, grid, threads, lds, stream);
-        else if (mode == 0) e = launch_fwd_variant<double, 4, 0>(sum, mul, fp, grid, threads, lds, stream);
-        else if (mode == 1) e = launch_fwd_variant<double, 4, 1>(sum, mul, fp, grid, threads, lds, stream);
-        else e = launch_fwd_variant<double, 4, 2>(sum, mul, fp, grid, threads, lds, stream);
-    }
-    if (e != hipSuccess) return hip_fail(e, "rspmm_fwd_kernel launch");
-    if (g_ev_after) HIP_TRY(hipEventRecord(g_ev_after, stream));
-
-    if (!p->split_row.empty()) {
-        FixupParams xp;
-        std::memset(&xp, 0, sizeof(xp));
-        xp.split_row = p->d.split_row;
-        xp.split_ptr = p->d.split_ptr;
-        xp.n_split = (int32_t)p->split_row.size();
-        xp.partial = p->d.partial;
-        if (bnd) xp.bnd = fp.bnd;
-        xp.bnd_rows = fp.bnd_rows;
-        xp.out = out->ptr;
-        xp.out_stride_outer = out->stride_outer;
-        xp.out_stride_row = out->stride_row;
-        xp.n_outer = fp.n_outer;
-        xp.row_len = fp.row_len;
-        xp.has_bnd = fp.has_bnd;
-        const long long total = (long long)xp.n_split * n_outer * (row_len / VEC);
-        const int blocks = (int)std::min<long long>((total + 15) / 16, 16384);      // 16 output vectors per workgroup
-#define ULTRA_FIX(T_, V_)                                                                                          \
-    switch (sum) {                                                                                                \
-        case 0: hipLaunchKernelGGL((rspmm_fixup_kernel<T_, V_, 0>), dim3(blocks), dim3(256), 0, stream, xp); break; \
-        case 1: hipLaunchKernelGGL((rspmm_fixup_kernel<T_, V_, 1>), dim3(blocks), dim3(256), 0, stream, xp); break; \
-        default: hipLaunchKernelGGL((rspmm_fixup_kernel<T_, V_, 2>), dim3(blocks), dim3(256), 0, stream, xp); break; \
-    }
-        if (dtype == ULTRA_F32) {
-            if (VEC == 4) { ULTRA_FIX(float, 4) } else { ULTRA_FIX(float, 1) }
-        } else {
-            if (VEC == 4) { ULTRA_FIX(double, 4) } else { ULTRA_FIX(double, 1) }
-        }
-#undef ULTRA_FIX
-        HIP_TRY(hipGetLastError());
-    }
-    return ULTRA_OK;
+    return forward_walk(p, sum, mul, dtype, w, bnd, out, stream, call, fp, di, VEC, rot_far);
 }
 
 static int ensure_backward_plans(ultra_plan *p) {
@@ -707,6 +742,45 @@ static int ensure_backward_plans(ultra_plan *p) {
         p->rplan = build_plan(p->h_type.data(), p->h_col.data(), p->h_row.data(), p->num_edge, p->num_rel, p->num_in,
                               p->num_out, &o, false);
         p->rplan->pinned = p->pinned;
+    }
+    return ULTRA_OK;
+}
+
+// Backward of min / max as gathers: the destinations walk the transposed (which = 0: input_grad) and the relation-major
+// (1: relation_grad) plan -- no atomics, the same bits run to run.  `launch(rel_grad, gp, grid)` starts the gather kernel
+// `what`, whose spans make spans_per_outer a row; the fix-up of the split rows takes fix_vec-wide chunks.
+template <typename Launch>
+static int backward_gather(ultra_plan *p, int dtype, const void *w, const EdgeParams &ep, const ultra_mat *xgrad,
+                           const ultra_mat *rgrad, int32_t spans_per_outer, int fix_vec, const char *what, hipStream_t stream,
+                           const Launch &launch) {
+    const size_t esz = dtype == ULTRA_F32 ? 4 : 8;
+    int rc;
+    if ((rc = ensure_backward_plans(p))) return rc;
+    for (int which = 0; which < 2; ++which) {
+        ultra_plan *q = which == 0 ? p->tplan : p->rplan;
+        const ultra_mat *dst = which == 0 ? xgrad : rgrad;
+        if ((rc = upload_plan(q))) return rc;
+        if (q->n_slot > 0 &&
+            (rc = ensure_scratch(&q->d.partial, &q->d.partial_bytes, (size_t)q->n_slot * ep.n_outer * ep.row_len * esz, q)))
+            return rc;
+        GatherBwdParams gp;
+        std::memset(&gp, 0, sizeof(gp));
+        gp.items = q->d.items;
+        gp.n_item = (int32_t)q->items.size();
+        gp.col = q->d.col, gp.type = q->d.type, gp.perm = q->d.perm;
+        gp.w = w;
+        gp.rel = ep.rel, gp.x = ep.x, gp.out = ep.out, gp.og = ep.og;
+        gp.grad = dst->ptr, gp.grad_so = dst->stride_outer, gp.grad_sr = dst->stride_row;
+        gp.partial = q->d.partial;
+        gp.n_outer = ep.n_outer, gp.row_len = ep.row_len;
+        gp.spans_per_outer = spans_per_outer;
+        gp.n_span = gp.spans_per_outer * gp.n_outer;
+        const int grid = 2048;
+        gp.smod = std::min<int32_t>(gp.n_span, grid);
+        gp.nparts = grid / gp.smod;
+        const hipError_t e = launch(which == 1, gp, grid);
+        if (e != hipSuccess) return hip_fail(e, what);
+        if ((rc = launch_fixup(q, dst, 0, dtype, fix_vec, stream))) return rc;
     }
     return ULTRA_OK;
 }
@@ -740,7 +814,6 @@ static int backward_impl(ultra_plan *p, int sum, int mul, int dtype, const void 
     if (xbase && (rc = check_mat(xbase, "input_grad_base", p->num_in, n_outer, row_len))) return rc;
     if ((rc = upload_plan(p))) return rc;
 
-    const size_t esz = dtype == ULTRA_F32 ? 4 : 8;
     const int64_t step = dtype == ULTRA_F32 ? 4 : 2;
     const bool vec4 = (row_len % 4 == 0) && mat_vec_ok(rel, step) && mat_vec_ok(x, step) && mat_vec_ok(outm, step) &&
                       mat_vec_ok(og, step) && mat_vec_ok(rgrad, step) && (!xgrad || mat_vec_ok(xgrad, step));
@@ -768,7 +841,7 @@ static int backward_impl(ultra_plan *p, int sum, int mul, int dtype, const void 
     ep.n_outer = (int32_t)n_outer;
     ep.row_len = (int32_t)row_len;
 
-    if (sum == ULTRA_SUM_ADD) {
+    if (sum == ULTRA_SUM_ADD) {      // both gradients are rspmm forwards over the transposed / relation-major plans
         if ((rc = ensure_backward_plans(p))) return rc;
         // input_grad[col] = sum_e w * d(rel (x) in)/d in * out_grad[row]   (rspmm.cpp:110-112)
         // rotate: ROT(conj(rel), out_grad) -- the same walk with the relation operand conjugated
@@ -780,126 +853,39 @@ static int backward_impl(ultra_plan *p, int sum, int mul, int dtype, const void 
         if ((rc = forward_impl(p->rplan, ULTRA_SUM_ADD, rot ? BIN_ROT_CX : mul == ULTRA_MUL_MUL ? BIN_MUL : BIN_LHS, dtype, w, og, x,
                                nullptr, rgrad, stream)))
             return rc;
-        if (wgrad && p->num_edge > 0) {
-            if (rot) {
-                if ((rc = launch_rot_edge_kernel(dtype, sum, /*want_ri=*/false, ep, stream))) return rc;
-            } else if ((rc = launch_edge_kernel(dtype, vec4 ? 4 : 1, sum, mul, /*want_ri=*/false, ep, stream))) {
-                return rc;
-            }
-        }
-        return ULTRA_OK;
+        if (!wgrad || p->num_edge <= 0) return ULTRA_OK;
+        if (rot) return launch_rot_edge_kernel(dtype, sum, /*want_ri=*/false, ep, stream);
+        return launch_edge_kernel(dtype, vec4 ? 4 : 1, sum, mul, /*want_ri=*/false, ep, stream);
     }
-    // rotate under min / max: the gather below on its own kernel -- 16 complex elements a span, scalar loads, so EVERY even row
+    // rotate under min / max: the gather on its own kernel -- 16 complex elements a span, scalar loads, so EVERY even row
     // length and alignment takes it (no atomics on any route: the same bits run to run)
     if (rot && p->num_edge > 0) {
-        if ((rc = ensure_backward_plans(p))) return rc;
         const bool fix4 = (row_len % 4 == 0) && mat_vec_ok(rgrad, step) && mat_vec_ok(xgrad, step);
-        for (int which = 0; which < 2; ++which) {
-            ultra_plan *q = which == 0 ? p->tplan : p->rplan;
-            const ultra_mat *dst = which == 0 ? xgrad : rgrad;
-            if ((rc = upload_plan(q))) return rc;
-            if (q->n_slot > 0 &&
-                (rc = ensure_scratch(&q->d.partial, &q->d.partial_bytes, (size_t)q->n_slot * n_outer * row_len * esz, q)))
-                return rc;
-            GatherBwdParams gp;
-            std::memset(&gp, 0, sizeof(gp));
-            gp.items = q->d.items;
-            gp.n_item = (int32_t)q->items.size();
-            gp.col = q->d.col, gp.type = q->d.type, gp.perm = q->d.perm;
-            gp.w = w;
-            gp.rel = ep.rel, gp.x = ep.x, gp.out = ep.out, gp.og = ep.og;
-            gp.grad = dst->ptr, gp.grad_so = dst->stride_outer, gp.grad_sr = dst->stride_row;
-            gp.partial = q->d.partial;
-            gp.n_outer = (int32_t)n_outer, gp.row_len = (int32_t)row_len;
-            gp.spans_per_outer = (int32_t)((row_len / 2 + 15) / 16);
-            gp.n_span = gp.spans_per_outer * gp.n_outer;
-            const int grid = 2048;
-            gp.smod = std::min<int32_t>(gp.n_span, grid);
-            gp.nparts = grid / gp.smod;
-            const hipError_t e = dtype == ULTRA_F32 ? launch_rot_gather_bwd_t<float>(sum, which == 1, gp, grid, stream)
-                                                    : launch_rot_gather_bwd_t<double>(sum, which == 1, gp, grid, stream);
-            if (e != hipSuccess) return hip_fail(e, "rspmm_rot_minmax_bwd_gather_kernel launch");
-            if (!q->split_row.empty()) {
-                FixupParams xp;
-                std::memset(&xp, 0, sizeof(xp));
-                xp.split_row = q->d.split_row, xp.split_ptr = q->d.split_ptr;
-                xp.n_split = (int32_t)q->split_row.size();
-                xp.partial = q->d.partial;
-                xp.out = dst->ptr, xp.out_stride_outer = dst->stride_outer, xp.out_stride_row = dst->stride_row;
-                xp.n_outer = gp.n_outer, xp.row_len = gp.row_len;
-                const long long total = (long long)xp.n_split * n_outer * (row_len / (fix4 ? 4 : 1));
-                const int blocks = (int)std::min<long long>((total + 15) / 16, 16384);
-                if (dtype == ULTRA_F32) {
-                    if (fix4) hipLaunchKernelGGL((rspmm_fixup_kernel<float, 4, 0>), dim3(blocks), dim3(256), 0, stream, xp);
-                    else hipLaunchKernelGGL((rspmm_fixup_kernel<float, 1, 0>), dim3(blocks), dim3(256), 0, stream, xp);
-                } else {
-                    if (fix4) hipLaunchKernelGGL((rspmm_fixup_kernel<double, 4, 0>), dim3(blocks), dim3(256), 0, stream, xp);
-                    else hipLaunchKernelGGL((rspmm_fixup_kernel<double, 1, 0>), dim3(blocks), dim3(256), 0, stream, xp);
-                }
-                HIP_TRY(hipGetLastError());
-            }
-        }
-        if (wgrad && (rc = launch_rot_edge_kernel(dtype, sum, /*want_ri=*/false, ep, stream))) return rc;
-        return ULTRA_OK;
+        const auto launch = [&](bool rel_grad, const GatherBwdParams &gp, int grid) {
+            return dtype == ULTRA_F32 ? launch_rot_gather_bwd_t<float>(sum, rel_grad, gp, grid, stream)
+                                      : launch_rot_gather_bwd_t<double>(sum, rel_grad, gp, grid, stream);
+        };
+        if ((rc = backward_gather(p, dtype, w, ep, xgrad, rgrad, (int32_t)((row_len / 2 + 15) / 16), fix4 ? 4 : 1,
+                                  "rspmm_rot_minmax_bwd_gather_kernel launch", stream, launch)))
+            return rc;
+        return wgrad ? launch_rot_edge_kernel(dtype, sum, /*want_ri=*/false, ep, stream) : ULTRA_OK;
     }
     // min / max: gradient flows to every edge whose message equals the output (operator.cuh:62-64,75-77).  With whole
     // 16-byte chunks the destinations GATHER over the transposed / relation-major plans (no atomics, deterministic); the
     // reference's scatter with atomics (restated in rspmm_edge_bwd_kernel) remains for unaligned / odd-length rows.
     if (vec4 && row_len % 4 == 0 && p->num_edge > 0) {
-        if ((rc = ensure_backward_plans(p))) return rc;
-        for (int which = 0; which < 2; ++which) {
-            ultra_plan *q = which == 0 ? p->tplan : p->rplan;
-            const ultra_mat *dst = which == 0 ? xgrad : rgrad;
-            if ((rc = upload_plan(q))) return rc;
-            if (q->n_slot > 0 &&
-                (rc = ensure_scratch(&q->d.partial, &q->d.partial_bytes, (size_t)q->n_slot * n_outer * row_len * esz, q)))
-                return rc;
-            GatherBwdParams gp;
-            std::memset(&gp, 0, sizeof(gp));
-            gp.items = q->d.items;
-            gp.n_item = (int32_t)q->items.size();
-            gp.col = q->d.col, gp.type = q->d.type, gp.perm = q->d.perm;
-            gp.w = w;
-            gp.rel = ep.rel, gp.x = ep.x, gp.out = ep.out, gp.og = ep.og;
-            gp.grad = dst->ptr, gp.grad_so = dst->stride_outer, gp.grad_sr = dst->stride_row;
-            gp.partial = q->d.partial;
-            gp.n_outer = (int32_t)n_outer, gp.row_len = (int32_t)row_len;
-            gp.spans_per_outer = (int32_t)((row_len + 63) / 64);
-            gp.n_span = gp.spans_per_outer * gp.n_outer;
-            const int grid = 2048;
-            gp.smod = std::min<int32_t>(gp.n_span, grid);
-            gp.nparts = grid / gp.smod;
-            const hipError_t e = dtype == ULTRA_F32 ? launch_gather_bwd_t<float>(sum, mul, which == 1, gp, grid, stream)
-                                                    : launch_gather_bwd_t<double>(sum, mul, which == 1, gp, grid, stream);
-            if (e != hipSuccess) return hip_fail(e, "rspmm_minmax_bwd_gather_kernel launch");
-            if (!q->split_row.empty()) {
-                FixupParams xp;
-                std::memset(&xp, 0, sizeof(xp));
-                xp.split_row = q->d.split_row, xp.split_ptr = q->d.split_ptr;
-                xp.n_split = (int32_t)q->split_row.size();
-                xp.partial = q->d.partial;
-                xp.out = dst->ptr, xp.out_stride_outer = dst->stride_outer, xp.out_stride_row = dst->stride_row;
-                xp.n_outer = gp.n_outer, xp.row_len = gp.row_len;
-                const long long total = (long long)xp.n_split * n_outer * (row_len / 4);
-                const int blocks = (int)std::min<long long>((total + 15) / 16, 16384);
-                if (dtype == ULTRA_F32)
-                    hipLaunchKernelGGL((rspmm_fixup_kernel<float, 4, 0>), dim3(blocks), dim3(256), 0, stream, xp);
-                else
-                    hipLaunchKernelGGL((rspmm_fixup_kernel<double, 4, 0>), dim3(blocks), dim3(256), 0, stream, xp);
-                HIP_TRY(hipGetLastError());
-            }
-        }
-        if (wgrad) {
-            if ((rc = launch_edge_kernel(dtype, 4, sum, mul, /*want_ri=*/false, ep, stream))) return rc;
-        }
-        return ULTRA_OK;
+        const auto launch = [&](bool rel_grad, const GatherBwdParams &gp, int grid) {
+            return dtype == ULTRA_F32 ? launch_gather_bwd_t<float>(sum, mul, rel_grad, gp, grid, stream)
+                                      : launch_gather_bwd_t<double>(sum, mul, rel_grad, gp, grid, stream);
+        };
+        if ((rc = backward_gather(p, dtype, w, ep, xgrad, rgrad, (int32_t)((row_len + 63) / 64), 4,
+                                  "rspmm_minmax_bwd_gather_kernel launch", stream, launch)))
+            return rc;
+        return wgrad ? launch_edge_kernel(dtype, 4, sum, mul, /*want_ri=*/false, ep, stream) : ULTRA_OK;
     }
     if ((rc = launch_fill_zero(dtype, rgrad, p->num_rel, stream))) return rc;
     if ((rc = launch_fill_zero(dtype, xgrad, p->num_in, stream))) return rc;
-    if (p->num_edge > 0 && !rot) {
-        if ((rc = launch_edge_kernel(dtype, vec4 ? 4 : 1, sum, mul, /*want_ri=*/true, ep, stream))) return rc;
-    }
-    (void)esz;
+    if (p->num_edge > 0 && !rot) return launch_edge_kernel(dtype, vec4 ? 4 : 1, sum, mul, /*want_ri=*/true, ep, stream);
     return ULTRA_OK;
 }
 
@@ -1039,6 +1025,40 @@ static int layer0_impl(ultra_plan *p, const void *w, const ultra_mat *rel, const
     return ULTRA_OK;
 }
 
+// The public forward entries' `mul` (ULTRA_MUL_*) as forward_impl's internal BIN_* code.
+static int internal_mul(int32_t *mul) {
+    if (*mul < 0 || *mul > ULTRA_MUL_ROTATE) return invalid("unknown mul code");
+    if (*mul == ULTRA_MUL_ROTATE) *mul = BIN_ROT;
+    return ULTRA_OK;
+}
+
+// ultra_rspmm_forward_update behind its device scope; `call` brings the point rows (and the events of the timed entry)
+static int forward_update(ultra_plan *plan, int sum, int mul, const ultra_mat *relation, const ultra_mat *input,
+                          const ultra_mat *point_values, const ultra_mat *aggregate, const void *weight, const void *bias,
+                          const void *ln_weight, const void *ln_bias, float eps, int flags, const ultra_mat *output,
+                          hipStream_t stream, FwdCall call) {
+    if (mul < 0 || mul > 1) return invalid("unknown mul code");
+    if ((call.bnd_rows == nullptr) != (point_values == nullptr)) return invalid("ultra_rspmm_forward_update: half a point boundary");
+    if (!weight || !output || !output->ptr || !aggregate || !aggregate->ptr || ((flags & CONV_LN) && (!ln_weight || !ln_bias)))
+        return invalid("ultra_rspmm_forward_update: NULL operand");
+    if (flags & ~(CONV_LN | CONV_RELU | CONV_RESIDUAL | CONV_DBG_NO_MATRIX | CONV_DBG_NO_UPDATE | CONV_DBG_LOSE_ARRIVAL))
+        return invalid("ultra_rspmm_forward_update: unknown flag");
+    if (!plan) return invalid("plan is NULL");
+    if (output->row_len != 64 || output->n_outer != aggregate->n_outer || output->n_row != aggregate->n_row ||
+        output->stride_row < 64 || (output->stride_row % 4) != 0 || (output->stride_outer % 4) != 0 ||
+        (reinterpret_cast<uintptr_t>(output->ptr) & 15) || output->ptr == aggregate->ptr || (input && output->ptr == input->ptr))
+        return invalid("ultra_rspmm_forward_update: output must be a 16-byte aligned (n_outer, num_node, 64) tensor of its own");
+    OrderParams::Update u;
+    std::memset(&u, 0, sizeof(u));
+    u.weight = (const float *)weight, u.bias = (const float *)bias;
+    u.ln_w = (const float *)ln_weight, u.ln_b = (const float *)ln_bias;
+    u.out = (float *)output->ptr;
+    u.out_stride_outer = output->stride_outer, u.out_stride_row = output->stride_row;
+    u.eps = eps, u.flags = flags;
+    call.upd = &u;
+    return forward_impl(plan, sum, mul, ULTRA_F32, nullptr, relation, input, point_values, aggregate, stream, call);
+}
+
 static ultra_mat dense2d(const void *ptr, int64_t rows, int64_t dim) {
     ultra_mat m;
     m.ptr = const_cast<void *>(ptr);
@@ -1124,8 +1144,7 @@ int32_t ultra_rspmm_forward(ultra_plan *plan, int32_t sum, int32_t mul, int32_t 
                             const ultra_mat *output, void *stream) {
     ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);
     WeightEpochScope weight_epoch_scope;
-    if (mul < 0 || mul > ULTRA_MUL_ROTATE) return invalid("unknown mul code");
-    if (mul == ULTRA_MUL_ROTATE) mul = BIN_ROT;
+    if (int rc = internal_mul(&mul)) return rc;
     return forward_impl(plan, sum, mul, dtype, edge_weight_dev, relation, input, boundary, output,
                         reinterpret_cast<hipStream_t>(stream));
 }
@@ -1135,14 +1154,12 @@ int32_t ultra_rspmm_forward_masked(ultra_plan *plan, int32_t sum, int32_t mul, i
                                    const ultra_mat *output, void *stream) {
     ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);
     WeightEpochScope weight_epoch_scope;
-    if (mul < 0 || mul > ULTRA_MUL_ROTATE) return invalid("unknown mul code");
-    if (mul == ULTRA_MUL_ROTATE) mul = BIN_ROT;
+    if (int rc = internal_mul(&mul)) return rc;
     if (!edge_keep_dev) return invalid("ultra_rspmm_forward_masked: edge_keep is NULL");
-    g_keep_mode = 1;
-    const int rc = forward_impl(plan, sum, mul, dtype, edge_keep_dev, relation, input, boundary, output,
-                                reinterpret_cast<hipStream_t>(stream));
-    g_keep_mode = 0;
-    return rc;
+    FwdCall call;
+    call.keep_mode = 1;
+    return forward_impl(plan, sum, mul, dtype, edge_keep_dev, relation, input, boundary, output,
+                        reinterpret_cast<hipStream_t>(stream), call);
 }
 
 int32_t ultra_rspmm_forward_point(ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const void *edge_weight_dev,
@@ -1150,11 +1167,10 @@ int32_t ultra_rspmm_forward_point(ultra_plan *plan, int32_t sum, int32_t mul, in
                                   const ultra_mat *point_values, const ultra_mat *output, void *stream) {
     ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);
     WeightEpochScope weight_epoch_scope;
-    if (mul < 0 || mul > ULTRA_MUL_ROTATE) return invalid("unknown mul code");
-    if (mul == ULTRA_MUL_ROTATE) mul = BIN_ROT;
+    if (int rc = internal_mul(&mul)) return rc;
     if (!point_rows_dev || !point_values) return invalid("ultra_rspmm_forward_point: NULL point boundary");
     return forward_impl(plan, sum, mul, dtype, edge_weight_dev, relation, input, point_values, output,
-                        reinterpret_cast<hipStream_t>(stream), point_rows_dev);
+                        reinterpret_cast<hipStream_t>(stream), FwdCall{point_rows_dev});
 }
 
 int32_t ultra_rspmm_forward_update(ultra_plan *plan, int32_t sum, int32_t mul, const ultra_mat *relation, const ultra_mat *input,
@@ -1162,26 +1178,8 @@ int32_t ultra_rspmm_forward_update(ultra_plan *plan, int32_t sum, int32_t mul, c
                                    const void *weight, const void *bias, const void *ln_weight, const void *ln_bias, float eps,
                                    int32_t flags, const ultra_mat *output, void *stream) {
     ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);
-    if (mul < 0 || mul > 1) return invalid("unknown mul code");
-    if ((point_rows_dev == nullptr) != (point_values == nullptr)) return invalid("ultra_rspmm_forward_update: half a point boundary");
-    if (!weight || !output || !output->ptr || !aggregate || !aggregate->ptr || ((flags & CONV_LN) && (!ln_weight || !ln_bias)))
-        return invalid("ultra_rspmm_forward_update: NULL operand");
-    if (flags & ~(CONV_LN | CONV_RELU | CONV_RESIDUAL | CONV_DBG_NO_MATRIX | CONV_DBG_NO_UPDATE | CONV_DBG_LOSE_ARRIVAL))
-        return invalid("ultra_rspmm_forward_update: unknown flag");
-    if (!plan) return invalid("plan is NULL");
-    if (output->row_len != 64 || output->n_outer != aggregate->n_outer || output->n_row != aggregate->n_row ||
-        output->stride_row < 64 || (output->stride_row % 4) != 0 || (output->stride_outer % 4) != 0 ||
-        (reinterpret_cast<uintptr_t>(output->ptr) & 15) || output->ptr == aggregate->ptr || (input && output->ptr == input->ptr))
-        return invalid("ultra_rspmm_forward_update: output must be a 16-byte aligned (n_outer, num_node, 64) tensor of its own");
-    OrderParams::Update u;
-    std::memset(&u, 0, sizeof(u));
-    u.weight = (const float *)weight, u.bias = (const float *)bias;
-    u.ln_w = (const float *)ln_weight, u.ln_b = (const float *)ln_bias;
-    u.out = (float *)output->ptr;
-    u.out_stride_outer = output->stride_outer, u.out_stride_row = output->stride_row;
-    u.eps = eps, u.flags = flags;
-    return forward_impl(plan, sum, mul, ULTRA_F32, nullptr, relation, input, point_values, aggregate,
-                        reinterpret_cast<hipStream_t>(stream), point_rows_dev, &u);
+    return forward_update(plan, sum, mul, relation, input, point_values, aggregate, weight, bias, ln_weight, ln_bias, eps, flags,
+                          output, reinterpret_cast<hipStream_t>(stream), FwdCall{point_rows_dev});
 }
 
 int32_t ultra_rspmm_forward_onehot(ultra_plan *plan, int32_t dtype, const void *edge_weight_dev,
@@ -1502,13 +1500,14 @@ int32_t ultra_rspmm_rows_backward(ultra_plan *plan, int32_t mul, const void *edg
 }
 
 // Times `once` (a launch sequence on stream s) with HIP events: the mean of `iters` back-to-back calls, and -- the figure
-// comparable with rocprofv3's per-kernel average -- the main kernel alone, events recorded right around its launch.
-static int time_launches(const std::function<int()> &once, hipStream_t s, int32_t warmup, int32_t iters, float *ms_per_call, float *ms_main_kernel,
+// comparable with rocprofv3's per-kernel average -- the main kernel alone: `once` hands the pair of events it is given to
+// forward_impl, which records them right around that launch.
+static int time_launches(const std::function<int(hipEvent_t, hipEvent_t)> &once, hipStream_t s, int32_t warmup, int32_t iters, float *ms_per_call, float *ms_main_kernel,
                          const char *who) {
     if (!ms_per_call || iters <= 0) return invalid(std::string(who) + ": bad iters / ms_per_call");
     int rc;
     for (int i = 0; i < warmup; ++i)
-        if ((rc = once()))
+        if ((rc = once(nullptr, nullptr)))
             return rc;
     struct Events {   // (destroyed on every path out)
         hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1523,7 +1522,7 @@ static int time_launches(const std::function<int()> &once, hipStream_t s, int32_
     // (1) the whole launch sequence (weight permute + main kernel + fix-up), back to back
     HIP_TRY(hipEventRecord(e0, s));
     for (int i = 0; i < iters; ++i)
-        if ((rc = once()))
+        if ((rc = once(nullptr, nullptr)))
             return rc;
     HIP_TRY(hipEventRecord(e1, s));
     HIP_TRY(hipEventSynchronize(e1));
@@ -1534,11 +1533,7 @@ static int time_launches(const std::function<int()> &once, hipStream_t s, int32_
     if (ms_main_kernel) {
         double acc = 0.0;
         for (int i = 0; i < iters; ++i) {
-            g_ev_before = e0;
-            g_ev_after = e1;
-            rc = once();
-            g_ev_before = g_ev_after = nullptr;
-            if (rc) return rc;
+            if ((rc = once(e0, e1))) return rc;
             HIP_TRY(hipEventSynchronize(e1));
             HIP_TRY(hipStreamSynchronize(s));
             HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
@@ -1554,11 +1549,12 @@ int32_t ultra_rspmm_forward_timed(ultra_plan *plan, int32_t sum, int32_t mul, in
                                   const ultra_mat *boundary, const int64_t *point_rows_dev, const ultra_mat *output,
                                   void *stream, int32_t warmup, int32_t iters, float *ms_per_call, float *ms_main_kernel) {
     ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);
-    if (mul < 0 || mul > ULTRA_MUL_ROTATE) return invalid("unknown mul code");
-    if (mul == ULTRA_MUL_ROTATE) mul = BIN_ROT;
-    const auto once = [&]() {
+    if (int rc = internal_mul(&mul)) return rc;
+    FwdCall call{point_rows_dev};
+    const auto once = [&](hipEvent_t before, hipEvent_t after) {
+        call.ev_before = before, call.ev_after = after;
         return forward_impl(plan, sum, mul, dtype, edge_weight_dev, relation, input, boundary, output,
-                            reinterpret_cast<hipStream_t>(stream), point_rows_dev);
+                            reinterpret_cast<hipStream_t>(stream), call);
     };
     return time_launches(once, reinterpret_cast<hipStream_t>(stream), warmup, iters, ms_per_call, ms_main_kernel,
                          "ultra_rspmm_forward_timed");
@@ -1570,9 +1566,11 @@ int32_t ultra_rspmm_forward_update_timed(ultra_plan *plan, int32_t sum, int32_t 
                                          int32_t flags, const ultra_mat *output, void *stream, int32_t warmup, int32_t iters,
                                          float *ms_per_call, float *ms_main_kernel) {
     ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);   // (the events are created and recorded on the operands' device)
-    const auto once = [&]() {
-        return ultra_rspmm_forward_update(plan, sum, mul, relation, input, point_rows_dev, point_values, aggregate, weight, bias, ln_weight,
-                                          ln_bias, eps, flags, output, stream);
+    FwdCall call{point_rows_dev};
+    const auto once = [&](hipEvent_t before, hipEvent_t after) {
+        call.ev_before = before, call.ev_after = after;
+        return forward_update(plan, sum, mul, relation, input, point_values, aggregate, weight, bias, ln_weight, ln_bias, eps, flags,
+                              output, reinterpret_cast<hipStream_t>(stream), call);
     };
     return time_launches(once, reinterpret_cast<hipStream_t>(stream), warmup, iters, ms_per_call, ms_main_kernel,
                          "ultra_rspmm_forward_update_timed");
