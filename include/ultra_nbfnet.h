@@ -351,6 +351,28 @@ int32_t ultra_traversal_dropout(const int64_t *edge_index, const int64_t *edge_t
 int32_t ultra_query_loss(const void *pred, const uint8_t *target, int64_t rows, int64_t n, float temperature, void *work,
                          void *loss, void *grad, void *stream);
 
+/* ---- serving link-prediction queries ----
+ * ultra_filtered_topk: the k best candidates of every row of score (batch, n_cand) fp32 contiguous, leaving out the row's
+ * known ids: known_index[known_ptr[b] : known_ptr[b + 1]], ascending and distinct within a row (the layout of
+ * ultra_filtered_rank; no positive has to be listed); known_ptr == NULL: no filter.  The order is the stable descending sort:
+ * score descending, equal scores by ascending id, every NaN above every number (NaNs tie with each other), -0.0 == +0.0.  A
+ * filtered candidate is removed, not rescored: a genuine -inf is a candidate like any other, ranked last.
+ *   ids_out (batch, k) int64; scores_out (batch, k) fp32, the stored bits of the selected scores (-0.0 stays -0.0, a NaN keeps
+ *   its payload); count_out[b] = min(k, n_cand - |known(b)|); slots at or beyond the count hold id -1 and score -inf.
+ * A row longer than ULTRA_TOPK_CHUNK is split over workgroups, each leaving at most k survivors in `workspace`
+ * (ultra_filtered_topk_workspace(batch, n_cand, k) bytes of device memory, 8-byte aligned; -1 for arguments out of range); a
+ * second launch merges any number of partial lists per row.  Exact and reproducible: the same bits on every run.  No
+ * allocation, no memset, no host synchronisation: the call records into a hipGraph.
+ * k outside [1, ULTRA_TOPK_MAX] or n_cand >= 2^31: ULTRA_ERR_UNSUPPORTED, decided before any pointer is looked at.  NULL score
+ * or outputs, n_cand <= 0 or a workspace that is too small: ULTRA_ERR_INVALID, nothing is launched.  batch == 0: ULTRA_OK.
+ */
+#define ULTRA_TOPK_MAX 256      /* largest k */
+#define ULTRA_TOPK_CHUNK 4096   /* candidates one workgroup selects from; a row longer than this is split */
+int64_t ultra_filtered_topk_workspace(int64_t batch, int64_t n_cand, int32_t k);
+int32_t ultra_filtered_topk(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
+                            int64_t n_cand, int32_t k, int64_t *ids_out, void *scores_out, int64_t *count_out, void *workspace,
+                            int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,59 @@
+"""Answer one link-prediction query on a dataset of triple files: the k entities the model predicts, with their scores.
+
+    python tools/predict.py --data-root DIR [--ckpt FILE] --head NAME --relation NAME [--inverse] [-k 10] [--unfiltered]
+
+DIR holds train.txt / valid.txt / test.txt (`head relation tail` per line) and optionally entities.dict / relations.dict
+(ultra_amd.data.load_triples_dir).  The query is (NAME, relation, ?); with --inverse it is (?, relation, NAME) and heads are
+predicted.  Answers the dataset already states (in any split) are left out unless --unfiltered.  --ckpt: an ULTRA
+checkpoint (a state dict, or a dict with the state under "model"); without it the weights are randomly initialised, and the
+tool says so.
+"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--data-root", required=True)
+    ap.add_argument("--ckpt")
+    ap.add_argument("--head", required=True, help="the known entity of the query (the tail with --inverse)")
+    ap.add_argument("--relation", required=True)
+    ap.add_argument("--inverse", action="store_true", help="predict heads of (?, relation, NAME)")
+    ap.add_argument("-k", type=int, default=10)
+    ap.add_argument("--unfiltered", action="store_true")
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        sys.exit("tools/predict.py needs a GPU: the engine has no CPU path")
+    from ultra_amd import data as udata
+    from ultra_amd import models, predict, synthetic
+    ent, rel = udata.read_vocab(args.data_root)
+    for name, vocab, what in ((args.head, ent, "entity"), (args.relation, rel, "relation")):
+        if name not in vocab:
+            sys.exit("unknown %s %r" % (what, name))
+    dev = torch.device("cuda:0")
+    data = udata.load_triples_dir(args.data_root).to(dev)
+    model = models.Ultra(**synthetic.default_model_cfg())
+    if args.ckpt:
+        state = torch.load(args.ckpt, map_location="cpu")
+        model.load_state_dict(state["model"] if "model" in state else state)
+    else:
+        print("no --ckpt: randomly initialised weights, the answers mean nothing")
+    model = model.to(dev).eval()
+    predictor = predict.Predictor(model, data, k=args.k, batch_size=1, filtered=not args.unfiltered)
+    anchor = torch.tensor([ent.index(args.head)], device=dev)
+    relation = torch.tensor([rel.index(args.relation)], device=dev)
+    ids, scores, count = (predictor.heads if args.inverse else predictor.tails)(anchor, relation)
+    query = "(?, %s, %s)" % (args.relation, args.head) if args.inverse else "(%s, %s, ?)" % (args.head, args.relation)
+    print("%s: top %d%s" % (query, int(count[0]), "" if args.unfiltered else ", known answers left out"))
+    for i in range(int(count[0])):
+        print("%3d  %-40s %.6g" % (i + 1, ent[int(ids[0, i])], float(scores[0, i])))
+
+
+if __name__ == "__main__":
+    main()

@@ -34,6 +34,8 @@ DENSE_MAX_IN_ROW = 1024
 BEAM_MAX = 64                # ULTRA_BEAM_MAX
 BEAM_HUB_DEGREE = 256        # ULTRA_BEAM_HUB_DEGREE
 RANKING_LDS_ANSWERS = 2048   # ULTRA_RANKING_LDS_ANSWERS
+TOPK_MAX = 256               # ULTRA_TOPK_MAX
+TOPK_CHUNK = 4096            # ULTRA_TOPK_CHUNK
 ARR_DENSE = 7
 ARR_DENSE_ORDER = 8
 
@@ -118,6 +120,9 @@ def _load():
     lib.ultra_readout.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, i32, i32, vp]
     lib.ultra_stream_copy.argtypes = [vp, vp, i64, vp]
     lib.ultra_filtered_rank.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp, vp]
+    lib.ultra_filtered_topk_workspace.argtypes = [i64, i64, i32]
+    lib.ultra_filtered_topk_workspace.restype = i64
+    lib.ultra_filtered_topk.argtypes = [vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp]
     lib.ultra_beam_search_layer.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, i64, i32, vp, vp, vp]
     lib.ultra_symbolic_traversal.argtypes = [vp, vp, vp, i64, vp, i64, i32, vp, vp, vp]
     lib.ultra_answer_ranking.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp]

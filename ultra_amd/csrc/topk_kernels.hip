@@ -1,0 +1,337 @@
+// Filtered top-k answers of a batch of link-prediction queries (include/ultra_nbfnet.h: ultra_filtered_topk).
+//
+//   candidates of row b = ids not in known(b), ordered by score descending, equal scores by ascending id, every NaN above
+//   every number (NaNs tie), -0.0 == +0.0: the stable descending torch.sort.  Exact and reproducible.
+//
+// One 64-bit key per candidate carries the whole order: an order-preserving map of the canonicalised score in the high word,
+// ~id in the low word.  Keys of a row are distinct, a larger key is an earlier answer, and 0 is free for "absent" -- a
+// filtered candidate is REMOVED (key 0), never rescored, so a genuine -inf stays a candidate.
+//
+// Two launches, the kernel boundary the only synchronisation between them:
+//   1. topk_chunk_kernel: one workgroup per (row, chunk of ULTRA_TOPK_CHUNK candidates) loads the chunk's keys, knocks out
+//      (through LDS) the slice of known(b) that falls into the chunk (binary search for its start in the sorted list), selects the k
+//      largest keys (select_topk: a floor from the threads' maxima, a radix select where that leaves too many), sorts them and
+//      writes at most k keys to the workspace (0-padded);
+//   2. topk_merge_kernel: one workgroup per row streams the row's partial lists through the same selection, any number of them,
+//      and writes ids, the STORED bits of the scores (gathered from the score matrix: -0.0 and NaN payloads survive) and the count.
+// A row of one chunk is finished by the first launch alone.  LDS atomics only count (histograms, the compaction cursor); the
+// survivors are sorted afterwards and their keys are distinct, so no output depends on the order atomics land in.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+
+#include "../../include/ultra_nbfnet.h"
+#include "../../include/ultra_rspmm.h"
+#include "plan.hpp"
+#include "device_scope.hpp"
+
+namespace ultra {
+
+constexpr int TOPK_THREADS = 256;
+constexpr int TOPK_CHUNK = ULTRA_TOPK_CHUNK;
+constexpr int TOPK_MAX = ULTRA_TOPK_MAX;
+constexpr int TOPK_CHUNK_BITS = 12;
+static_assert(TOPK_CHUNK == 1 << TOPK_CHUNK_BITS, "the in-chunk key packs the local index into TOPK_CHUNK_BITS bits");
+static_assert(TOPK_THREADS == 256 && TOPK_MAX <= TOPK_THREADS, "one thread per histogram bin and per survivor");
+
+typedef unsigned long long u64;
+
+constexpr int TOPK_SLOTS = TOPK_CHUNK / TOPK_THREADS;      // fresh keys a thread holds; one more slot takes a survivor (merge)
+constexpr int TOPK_HELD = TOPK_SLOTS + 1;
+
+struct TopkScratch {
+    unsigned hist[256];
+    u64 surv[TOPK_MAX];
+    u64 top[TOPK_THREADS];      // every thread's largest key
+    u64 prefix, low;
+    unsigned remaining, done, count, cursor;
+};
+
+// fp32 bits -> 32 bits whose unsigned order is the answer order of the scores: NaN (any sign, any payload) on top, then
+// +inf ... +0 == -0 ... -inf.  Never 0 (-inf maps to 0x007fffff).
+__device__ __forceinline__ unsigned ordered_score(unsigned u) {
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
+    if ((u & 0x7fffffffu) == 0u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// surv[0 .. m) -> sorted[0 .. min(m, k)), descending: rank by counting, the keys are distinct.  m <= TOPK_THREADS.
+__device__ __forceinline__ void rank_sort(const u64 *surv, int m, int k, u64 *sorted) {
+    const int tid = threadIdx.x;
+    if (tid < m) {
+        const u64 key = surv[tid];
+        int r = 0;
+        for (int j = 0; j < m; ++j) r += surv[j] > key ? 1 : 0;
+        if (r < k) sorted[r] = key;
+    }
+}
+
+// The keys of a workgroup, TOPK_HELD in the registers of every thread: 0 = absent, the others distinct and below 2^(8 bytes).
+// Leaves the m = min(k, #present) largest in sorted[0 .. m) (LDS), descending, and returns m (the same in every thread).  Ends
+// with a barrier.
+//
+// Most keys never reach the selection proper: every thread publishes its largest key; the k-th largest of those 256 maxima is
+// a floor under the k-th largest key (k keys, the maxima above it, are at least as large), so only keys at or above the floor
+// stay.  For scores in no particular order that is little more than k keys, which are ranked by counting.  When more than
+// TOPK_MAX stay (the winners crowd into few threads, or k is close to the number of threads) a radix select, a byte per pass
+// from the top, finds the k-th largest among them first.
+__device__ int select_topk(u64 (&held)[TOPK_HELD], int k, int bytes, TopkScratch &s, u64 *sorted) {
+    const int tid = threadIdx.x;
+    u64 best = 0;
+#pragma unroll
+    for (int j = 0; j < TOPK_HELD; ++j) best = held[j] > best ? held[j] : best;
+    s.top[tid] = best;
+    if (tid == 0) s.low = 1, s.cursor = 0, s.count = 0;      // (fewer than k threads hold a key: everything present stays)
+    __syncthreads();
+    {
+        int r = 0;
+        for (int j = 0; j < TOPK_THREADS; ++j) r += s.top[j] > best ? 1 : 0;
+        if (best != 0 && r == k - 1) s.low = best;
+    }
+    __syncthreads();
+    const u64 low = s.low;
+    int stay = 0;
+#pragma unroll
+    for (int j = 0; j < TOPK_HELD; ++j) {
+        held[j] = held[j] >= low ? held[j] : 0;     // (an absent key, 0, is below any floor)
+        stay += held[j] != 0 ? 1 : 0;
+    }
+    unsigned at = stay ? atomicAdd(&s.cursor, (unsigned)stay) : 0u;       // (the order is settled by the sort below)
+    __syncthreads();
+    const int n = (int)s.cursor;
+    if (n <= TOPK_MAX) {
+#pragma unroll
+        for (int j = 0; j < TOPK_HELD; ++j)
+            if (held[j] != 0) s.surv[at++] = held[j];
+        __syncthreads();
+        rank_sort(s.surv, n, k, sorted);
+        __syncthreads();
+        return n < k ? n : k;
+    }
+    // more than TOPK_MAX >= k keys are left: radix select of the k-th largest
+    u64 prefix = 0;
+    unsigned remaining = (unsigned)k;
+    int p = bytes - 1;
+    for (;; --p) {
+        s.hist[tid] = 0;
+        __syncthreads();
+        const int above_shift = 8 * (p + 1);
+#pragma unroll
+        for (int j = 0; j < TOPK_HELD; ++j) {
+            const u64 key = held[j];
+            const bool match = above_shift >= 64 ? true : (key >> above_shift) == prefix;
+            if (key != 0 && match) atomicAdd(&s.hist[(unsigned)(key >> (8 * p)) & 255u], 1u);
+        }
+        __syncthreads();
+        if (tid < 64) {     // (the whole first wave) lane l owns bins 4 l .. 4 l + 3; suffix sums from the top bin down
+            const unsigned c = s.hist[4 * tid] + s.hist[4 * tid + 1] + s.hist[4 * tid + 2] + s.hist[4 * tid + 3];
+            unsigned incl = c;
+            for (int off = 1; off < 64; off <<= 1) {
+                const unsigned v = __shfl_down(incl, off);
+                if (tid + off < 64) incl += v;
+            }
+            const unsigned above = incl - c;
+            if (incl >= remaining && above < remaining) {      // exactly one lane
+                unsigned acc = above, h = 0;
+                int d = 3;
+                for (; d > 0; --d) {
+                    h = s.hist[4 * tid + d];
+                    if (acc + h >= remaining) break;
+                    acc += h;
+                }
+                if (d == 0) h = s.hist[4 * tid];
+                s.prefix = (prefix << 8) | (u64)(4 * tid + d);
+                s.remaining = remaining - acc;
+                s.done = (acc + h == remaining) ? 1u : 0u;      // the bins from here up hold exactly what is wanted
+            }
+        }
+        __syncthreads();
+        prefix = s.prefix;
+        remaining = s.remaining;
+        if (s.done || p == 0) break;
+    }
+    const u64 threshold = prefix << (8 * p);
+#pragma unroll
+    for (int j = 0; j < TOPK_HELD; ++j) {
+        if (held[j] != 0 && held[j] >= threshold) {
+            const unsigned slot = atomicAdd(&s.count, 1u);
+            if (slot < (unsigned)TOPK_MAX) s.surv[slot] = held[j];
+        }
+    }
+    __syncthreads();
+    const int m = (int)s.count < k ? (int)s.count : k;
+    rank_sort(s.surv, m, k, sorted);
+    __syncthreads();
+    return m;
+}
+
+__device__ void write_answers(const float *row, long long n_cand, long long n_known, int k, int m, const u64 *sorted,
+                              int64_t *ids_out, unsigned *scores_out, int64_t *count_out) {
+    const int tid = threadIdx.x;
+    if (tid < k) {
+        if (tid < m) {
+            const unsigned id = ~(unsigned)sorted[tid];
+            ids_out[tid] = (int64_t)id;
+            scores_out[tid] = __float_as_uint(row[id]);
+        } else {
+            ids_out[tid] = -1;
+            scores_out[tid] = 0xff800000u;
+        }
+    }
+    if (tid == 0) {
+        const long long left = n_cand - n_known;
+        *count_out = left < 0 ? 0 : (left < k ? left : k);
+    }
+}
+
+__global__ void __launch_bounds__(TOPK_THREADS) topk_chunk_kernel(const float *__restrict__ score, const int64_t *__restrict__ known_ptr,
+                                                                  const int64_t *__restrict__ known_index, long long n_cand,
+                                                                  long long n_chunk, int k, u64 *__restrict__ partial,
+                                                                  int64_t *ids_out, unsigned *scores_out, int64_t *count_out) {
+    __shared__ unsigned ord[TOPK_CHUNK];
+    __shared__ u64 sorted[TOPK_MAX];
+    __shared__ TopkScratch s;
+    const int tid = threadIdx.x;
+    const long long b = blockIdx.x / n_chunk, c = blockIdx.x % n_chunk;
+    const float *row = score + b * n_cand;
+    const long long lo = c * TOPK_CHUNK;
+    const int n = (int)(n_cand - lo < TOPK_CHUNK ? n_cand - lo : TOPK_CHUNK);
+    // all of a thread's scores in flight at once, the search for the chunk's slice of known(b) beside them
+    unsigned bits[TOPK_SLOTS];
+#pragma unroll
+    for (int j = 0; j < TOPK_SLOTS; ++j) {
+        const int i = tid + j * TOPK_THREADS;
+        bits[j] = i < n ? ordered_score(__float_as_uint(row[lo + i])) : 0u;
+    }
+    long long n_known = 0, a = 0, k1 = 0;
+    bool any_known = false;      // (the same in every thread)
+    if (known_ptr) {
+        const long long k0 = known_ptr[b];
+        k1 = known_ptr[b + 1];
+        n_known = k1 - k0;
+        long long z = k1;       // first entry >= lo
+        a = k0;
+        while (a < z) {
+            const long long mid = a + ((z - a) >> 1);
+            if (known_index[mid] < lo) a = mid + 1; else z = mid;
+        }
+        any_known = a < k1 && known_index[a] < lo + n;
+    }
+    if (any_known) {        // the knock-out goes by id: through LDS
+#pragma unroll
+        for (int j = 0; j < TOPK_SLOTS; ++j) {
+            const int i = tid + j * TOPK_THREADS;
+            if (i < n) ord[i] = bits[j];
+        }
+        __syncthreads();
+        for (long long j = a + tid; j < k1; j += TOPK_THREADS) {
+            const long long id = known_index[j];
+            if (id >= lo + n) break;        // ascending: the rest of this thread's entries lie beyond the chunk too
+            if (id >= lo) ord[id - lo] = 0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < TOPK_SLOTS; ++j) {
+            const int i = tid + j * TOPK_THREADS;
+            bits[j] = i < n ? ord[i] : 0u;
+        }
+    }
+    // inside a chunk the local index orders the ids: 32 + TOPK_CHUNK_BITS bits of key, two radix passes fewer
+    u64 held[TOPK_HELD];
+#pragma unroll
+    for (int j = 0; j < TOPK_SLOTS; ++j)
+        held[j] = bits[j] ? ((u64)bits[j] << TOPK_CHUNK_BITS) | (u64)(TOPK_CHUNK - 1 - (tid + j * TOPK_THREADS)) : 0;
+    held[TOPK_SLOTS] = 0;
+    const int m = select_topk(held, k, (32 + TOPK_CHUNK_BITS + 7) / 8, s, sorted);
+    if (tid < m) {
+        const u64 key = sorted[tid];
+        const unsigned id = (unsigned)(lo + (TOPK_CHUNK - 1 - (int)(key & (TOPK_CHUNK - 1))));
+        sorted[tid] = ((key >> TOPK_CHUNK_BITS) << 32) | (u64)(~id);       // (each thread rewrites its own slot)
+    }
+    __syncthreads();
+    if (n_chunk == 1) {
+        write_answers(row, n_cand, n_known, k, m, sorted, ids_out + b * k, scores_out + b * k, count_out + b);
+    } else if (tid < k) {
+        partial[((long long)blockIdx.x) * k + tid] = tid < m ? sorted[tid] : 0;
+    }
+}
+
+__global__ void __launch_bounds__(TOPK_THREADS) topk_merge_kernel(const float *__restrict__ score, const int64_t *__restrict__ known_ptr,
+                                                                  long long n_cand, long long n_chunk, int k,
+                                                                  const u64 *__restrict__ partial, int64_t *ids_out,
+                                                                  unsigned *scores_out, int64_t *count_out) {
+    __shared__ u64 sorted[TOPK_MAX];
+    __shared__ TopkScratch s;
+    const int tid = threadIdx.x;
+    const long long b = blockIdx.x;
+    const long long total = n_chunk * k;
+    const u64 *src = partial + b * total;
+    int m = 0;
+    for (long long pos = 0; pos < total; pos += TOPK_CHUNK) {
+        u64 held[TOPK_HELD];
+#pragma unroll
+        for (int j = 0; j < TOPK_SLOTS; ++j) {      // the next stretch of partial lists (all loads in flight at once) ...
+            const long long i = pos + tid + j * TOPK_THREADS;
+            held[j] = i < total ? src[i] : 0;
+        }
+        held[TOPK_SLOTS] = tid < m ? sorted[tid] : 0;      // ... and the survivors so far
+        __syncthreads();       // (sorted[] is rewritten by the selection)
+        m = select_topk(held, k, 8, s, sorted);
+    }
+    const long long n_known = known_ptr ? known_ptr[b + 1] - known_ptr[b] : 0;
+    write_answers(score + b * n_cand, n_cand, n_known, k, m, sorted, ids_out + b * k, scores_out + b * k, count_out + b);
+}
+
+}  // namespace ultra
+
+extern "C" int64_t ultra_filtered_topk_workspace(int64_t batch, int64_t n_cand, int32_t k) {
+    if (batch < 0 || n_cand < 0 || k < 1 || k > ULTRA_TOPK_MAX) return -1;
+    const int64_t n_chunk = (n_cand + ULTRA_TOPK_CHUNK - 1) / ULTRA_TOPK_CHUNK;
+    return batch * n_chunk * (int64_t)k * (int64_t)sizeof(uint64_t);
+}
+
+extern "C" int32_t ultra_filtered_topk(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
+                                       int64_t n_cand, int32_t k, int64_t *ids_out, void *scores_out, int64_t *count_out,
+                                       void *workspace, int64_t workspace_bytes, void *stream) {
+    if (k < 1 || k > ULTRA_TOPK_MAX || n_cand >= (int64_t)1 << 31) {      // (before any pointer is looked at)
+        ultra::set_error("ultra_filtered_topk: k must lie in [1, " + std::to_string(ULTRA_TOPK_MAX) + "] and n_cand below 2^31");
+        return ULTRA_ERR_UNSUPPORTED;
+    }
+    if (!score || !ids_out || !scores_out || !count_out || batch < 0 || n_cand <= 0) {
+        ultra::set_error("ultra_filtered_topk: NULL operand or empty candidate set");
+        return ULTRA_ERR_INVALID;
+    }
+    const int64_t n_chunk = (n_cand + ULTRA_TOPK_CHUNK - 1) / ULTRA_TOPK_CHUNK;
+    const int64_t need = ultra_filtered_topk_workspace(batch, n_cand, k);
+    if (workspace_bytes < need || (need > 0 && !workspace) || ((uintptr_t)workspace & 7u) != 0) {
+        ultra::set_error("ultra_filtered_topk: workspace of " + std::to_string(workspace_bytes) + " bytes, needs " +
+                         std::to_string(need) + " (8-byte aligned)");
+        return ULTRA_ERR_INVALID;
+    }
+    if (batch * n_chunk >= (int64_t)1 << 31) {
+        ultra::set_error("ultra_filtered_topk: batch * chunks per row must stay below 2^31");
+        return ULTRA_ERR_UNSUPPORTED;
+    }
+    if (batch == 0) return ULTRA_OK;
+    ULTRA_DEVICE_SCOPE(stream, score);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    (void)hipGetLastError();   // drop any stale error left by other users of the runtime
+    hipLaunchKernelGGL(ultra::topk_chunk_kernel, dim3((unsigned)(batch * n_chunk)), dim3(ultra::TOPK_THREADS), 0, s,
+                       (const float *)score, known_ptr, known_index, (long long)n_cand, (long long)n_chunk, (int)k,
+                       (ultra::u64 *)workspace, ids_out, (unsigned *)scores_out, count_out);
+    if (hipGetLastError() != hipSuccess) {
+        ultra::set_error("topk_chunk_kernel launch failed");
+        return ULTRA_ERR_HIP;
+    }
+    if (n_chunk > 1) {
+        hipLaunchKernelGGL(ultra::topk_merge_kernel, dim3((unsigned)batch), dim3(ultra::TOPK_THREADS), 0, s, (const float *)score,
+                           known_ptr, (long long)n_cand, (long long)n_chunk, (int)k, (const ultra::u64 *)workspace, ids_out,
+                           (unsigned *)scores_out, count_out);
+        if (hipGetLastError() != hipSuccess) {
+            ultra::set_error("topk_merge_kernel launch failed");
+            return ULTRA_ERR_HIP;
+        }
+    }
+    return ULTRA_OK;
+}

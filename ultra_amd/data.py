@@ -47,18 +47,10 @@ class Data(object):
         return "Data(%s)" % ", ".join(parts)
 
 
-def load_triples_dir(root, relation_graph=True, split="test"):
-    """A transductive dataset from raw triple files -- `root` holds train.txt / valid.txt / test.txt with one
-    tab- (or space-) separated `head relation tail` triple per line, optionally entities.dict / relations.dict (`id name`
-    per line), the layout of kg-datasets/FB15k-237 (PyG RelLinkPredDataset raw files, ultra/datasets.py:186-205).  Returns
-    the TEST split in the reference's format: fact graph = training triples + their inverses (edge_type r + R),
-    num_relations = 2 R, targets = test triples; `target_triples` as (h, t, r) rows like ultra_amd.synthetic.make_kg.
-    `filtered_data` holds the transductive filtering graph of script/run.py:286-288 -- the target triples of ALL three
-    splits, no inverses -- which ultra_amd.eval.evaluate uses for the filtered ranking when the caller passes none.
-    split="train" / "valid": the same fact graph with that split's triples as the targets (the training and validation graphs of
-    a pre-training run, script/pretrain.py:226)."""
-    if split not in ("train", "valid", "test"):
-        raise ValueError("split must be 'train', 'valid' or 'test', got %r" % (split,))
+def _read_triple_files(root):
+    """(entity vocabulary, relation vocabulary, (train, valid, test) as (h, t, r) id rows) of a directory of triple files: ids
+    from entities.dict / relations.dict (`id name` per line) when present, else in first-seen order over train.txt, valid.txt,
+    test.txt."""
     import os
 
     def read_dict(name):
@@ -100,7 +92,36 @@ def load_triples_dir(root, relation_graph=True, split="test"):
                 rows.append((ent[h], ent[t], rel[r]))
         return torch.tensor(rows, dtype=torch.long).view(-1, 3)
 
-    train, valid, test = read_split("train.txt"), read_split("valid.txt"), read_split("test.txt")
+    splits = (read_split("train.txt"), read_split("valid.txt"), read_split("test.txt"))
+    return ent, rel, splits
+
+
+def read_vocab(root):
+    """(entity_names, relation_names) of the dataset in `root`, indexed by the ids load_triples_dir(root) assigns (the R base
+    relations: the graph's relation r + R is the inverse of r).  An id that no name maps to holds None."""
+    ent, rel, _ = _read_triple_files(root)
+
+    def names(vocab):
+        out = [None] * max([len(vocab)] + [i + 1 for i in vocab.values()])
+        for name, i in vocab.items():
+            out[i] = name
+        return out
+    return names(ent), names(rel)
+
+
+def load_triples_dir(root, relation_graph=True, split="test"):
+    """A transductive dataset from raw triple files -- `root` holds train.txt / valid.txt / test.txt with one
+    tab- (or space-) separated `head relation tail` triple per line, optionally entities.dict / relations.dict (`id name`
+    per line), the layout of kg-datasets/FB15k-237 (PyG RelLinkPredDataset raw files, ultra/datasets.py:186-205).  Returns
+    the TEST split in the reference's format: fact graph = training triples + their inverses (edge_type r + R),
+    num_relations = 2 R, targets = test triples; `target_triples` as (h, t, r) rows like ultra_amd.synthetic.make_kg.
+    `filtered_data` holds the transductive filtering graph of script/run.py:286-288 -- the target triples of ALL three
+    splits, no inverses -- which ultra_amd.eval.evaluate uses for the filtered ranking when the caller passes none.
+    split="train" / "valid": the same fact graph with that split's triples as the targets (the training and validation graphs of
+    a pre-training run, script/pretrain.py:226)."""
+    if split not in ("train", "valid", "test"):
+        raise ValueError("split must be 'train', 'valid' or 'test', got %r" % (split,))
+    ent, rel, (train, valid, test) = _read_triple_files(root)
     R = len(rel)
     edge_index = torch.stack([torch.cat([train[:, 0], train[:, 1]]), torch.cat([train[:, 1], train[:, 0]])])
     edge_type = torch.cat([train[:, 2], train[:, 2] + R])

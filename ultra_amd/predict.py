@@ -1,0 +1,297 @@
+"""Serving link-prediction queries: the filtered top-k answers of (h, r, ?) and (?, r, t).
+
+The evaluation protocol (eval.evaluate, tasks.filtered_ranking) returns the rank of a positive the caller already knows;
+this module answers the question a user of a pre-trained model asks: which entities does the model predict for this head
+and relation, leaving out the ones the graph already states?
+
+  filtered_topk_reference   the semantics in plain torch, on any device -- the definition the kernel is tested against
+  filtered_topk             csrc/topk_kernels.hip (ultra_filtered_topk): no (batch, N) mask, no clone of the scores
+  known_answers             the ragged lists of ids to leave out, from the filter graph (no positive is added)
+  Predictor                 .tails(h, r) / .heads(t, r): candidate construction, the forward and the selection as one
+                            hipGraph replay per batch
+
+Order: score descending, equal scores by ascending id, every NaN above every number (NaNs tie), -0.0 == +0.0
+-- the stable descending torch.sort.  A filtered candidate is removed, not rescored: a genuine -inf score is a candidate
+like any other, ranked last.  Slots beyond count = min(k, N - |known|) hold id -1 and score -inf.
+"""
+import ctypes
+
+import torch
+
+from . import _lib, models, rspmm, tasks
+
+
+def filtered_topk_reference(pred, k, ptr=None, index=None):
+    """(ids (batch, k) int64, scores (batch, k) pred's dtype, count (batch) int64) -- per row, the candidates are the ids not
+    in index[ptr[b] : ptr[b + 1]], in the order of the stable descending sort of their scores."""
+    k = int(k)
+    batch, n = pred.shape
+    ids = torch.full((batch, k), -1, dtype=torch.long, device=pred.device)
+    scores = torch.full((batch, k), float("-inf"), dtype=pred.dtype, device=pred.device)
+    count = torch.zeros(batch, dtype=torch.long, device=pred.device)
+    for b in range(batch):
+        keep = torch.ones(n, dtype=torch.bool, device=pred.device)
+        if ptr is not None:
+            keep[index[int(ptr[b]):int(ptr[b + 1])]] = False
+        cand = keep.nonzero().flatten()
+        order = torch.sort(pred[b, cand], descending=True, stable=True).indices[:k]
+        m = order.numel()
+        ids[b, :m] = cand[order]
+        scores[b, :m] = pred[b, cand[order]]
+        count[b] = m
+    return ids, scores, count
+
+
+def _stream(device):
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _check_k(k):
+    if not isinstance(k, int) or not 1 <= k <= _lib.TOPK_MAX:
+        raise ValueError("k must be an int in [1, %d], got %r" % (_lib.TOPK_MAX, k))
+
+
+def filtered_topk(pred, k, ptr=None, index=None):
+    """filtered_topk_reference through the HIP kernel: pred (batch, N) fp32 on the GPU; ptr (batch + 1) / index int64, ids
+    ascending and distinct within a row; ptr None: no filter."""
+    _check_k(k)
+    if not pred.is_cuda:
+        raise RuntimeError("ultra_amd.predict.filtered_topk: expected a GPU tensor; the MI355X engine has no CPU path")
+    if pred.dim() != 2 or pred.dtype != torch.float32:
+        raise TypeError("filtered_topk takes (batch, N) fp32 scores, got %s %s" % (tuple(pred.shape), pred.dtype))
+    pred = pred.contiguous()
+    batch, n = pred.shape
+    dev = pred.device
+    ids = torch.empty(batch, k, dtype=torch.long, device=dev)
+    scores = torch.empty(batch, k, dtype=torch.float32, device=dev)
+    count = torch.empty(batch, dtype=torch.long, device=dev)
+    if batch == 0:
+        return ids, scores, count
+    if ptr is not None:
+        if ptr.shape != (batch + 1,) or ptr.dtype != torch.long or index.dtype != torch.long or ptr.device != dev or index.device != dev:
+            raise ValueError("filtered_topk takes int64 `ptr` of shape (batch + 1,) and int64 `index` on the scores' device")
+        ptr, index = ptr.contiguous(), index.contiguous()      # (referenced until the launch is enqueued)
+    ws = torch.empty(max(1, _lib.lib.ultra_filtered_topk_workspace(batch, n, k) // 8), dtype=torch.long, device=dev)
+    _lib.check(_lib.lib.ultra_filtered_topk(pred.data_ptr(), None if ptr is None else ptr.data_ptr(),
+                                            None if ptr is None else index.data_ptr(), batch, n, k, ids.data_ptr(),
+                                            scores.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(dev)))
+    return ids, scores, count
+
+
+def known_answers(data, anchor, relation, mode="tail"):
+    """(ptr (n + 1), index): per query the distinct tails of (anchor, relation, .) in `data` (mode="tail") or the distinct
+    heads of (., relation, anchor) (mode="head"), ascending.  tasks.known_answers without the positive: for a true triple of
+    `data` the two agree."""
+    if mode not in ("tail", "head"):
+        raise ValueError("mode must be 'tail' or 'head', got %r" % (mode,))
+    keyed, answer_row = (0, 1) if mode == "tail" else (1, 0)
+    idx = tasks._key_index(mode, (data.edge_index, data.edge_type),
+                           lambda: tasks.EdgeKeyIndex(torch.stack([data.edge_index[keyed], data.edge_type])))
+    edge_id, count = tasks.edge_match(None, torch.stack([anchor, relation]), index=idx)
+    truth = data.edge_index[answer_row, edge_id]
+    sample = torch.arange(len(count), device=anchor.device).repeat_interleave(count)
+    n = data.num_nodes
+    key = torch.unique(sample * n + truth)                     # sorted: grouped by query, ids ascending
+    ptr = torch.searchsorted(key, torch.arange(len(anchor) + 1, device=anchor.device) * n)
+    return ptr, key % n
+
+
+def _candidates(data, anchor, relation, mode):
+    """The t_batch (mode="tail") or h_batch (mode="head") form of tasks.all_negative for queries without a positive: every
+    entity as the tail of (anchor, relation) or as the head of (relation, anchor).  The model turns the head form into a
+    tail query with the inverse relation, exactly as in evaluation."""
+    n = data.num_nodes
+    every = torch.arange(n, device=anchor.device).unsqueeze(0).expand(len(anchor), -1)
+    fixed = anchor.unsqueeze(-1).expand(-1, n)
+    r = relation.unsqueeze(-1).expand(-1, n)
+    return torch.stack([fixed, every, r] if mode == "tail" else [every, fixed, r], dim=-1)
+
+
+class _GraphedPredictStep(object):
+    """One batch of one direction as ONE hipGraph replay (modelled on graph.GraphedEvalStep): candidate construction, the
+    forward and ultra_filtered_topk.  Per batch the host copies the (bs) anchors and relations and the (bs + 1) offsets into
+    the known lists of the whole call, which live in a buffer of the step (`load_index`, once per call)."""
+
+    def __init__(self, model, data, batch_size, k, mode, index_capacity, warmup=2):
+        dev = data.edge_index.device
+        self.model, self.bs, self.k, self.mode = model, batch_size, k, mode
+        self.anchor = torch.zeros(batch_size, dtype=torch.long, device=dev)
+        self.relation = torch.zeros(batch_size, dtype=torch.long, device=dev)
+        self.filtered = index_capacity is not None
+        self.capacity = max(1, int(index_capacity)) if self.filtered else 0
+        self.ptr = torch.zeros(batch_size + 1, dtype=torch.long, device=dev)
+        self.index = torch.zeros(max(1, self.capacity), dtype=torch.long, device=dev)
+        self.ids = torch.empty(batch_size, k, dtype=torch.long, device=dev)
+        self.scores = torch.empty(batch_size, k, dtype=torch.float32, device=dev)
+        self.count = torch.empty(batch_size, dtype=torch.long, device=dev)
+        n = int(data.num_nodes)
+        ws_bytes = _lib.lib.ultra_filtered_topk_workspace(batch_size, n, k)
+        self.ws = torch.empty(max(1, ws_bytes // 8), dtype=torch.long, device=dev)
+        self._pinned = []
+
+        def step():
+            pred = model(data, _candidates(data, self.anchor, self.relation, mode)).float().contiguous()
+            _lib.check(_lib.lib.ultra_filtered_topk(pred.data_ptr(), self.ptr.data_ptr() if self.filtered else None,
+                                                    self.index.data_ptr() if self.filtered else None, batch_size, n, k,
+                                                    self.ids.data_ptr(), self.scores.data_ptr(), self.count.data_ptr(),
+                                                    self.ws.data_ptr(), self.ws.numel() * 8, _stream(dev)))
+
+        with torch.cuda.device(dev):
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.no_grad(), torch.cuda.stream(side), rspmm.record_plans() as used:
+                for _ in range(warmup):
+                    step()
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            self._pinned = used.plans
+            for plan in self._pinned:
+                plan.pin(+1)
+            try:
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+                    step()
+            except BaseException:
+                # (a failed capture must not leave its plans pinned for the life of the process: graph.GraphedEvalStep)
+                self.release()
+                raise
+        self.params = _param_state(model)
+
+    def load_index(self, index):
+        self.index[:index.numel()].copy_(index, non_blocking=True)
+
+    def __call__(self, anchor, relation, ptr):
+        """(ids, scores, count) of this batch -- views of the step's buffers: copy before the next call."""
+        self.anchor.copy_(anchor, non_blocking=True)
+        self.relation.copy_(relation, non_blocking=True)
+        if self.filtered:
+            self.ptr.copy_(ptr, non_blocking=True)
+        self.graph.replay()
+        return self.ids, self.scores, self.count
+
+    def release(self):
+        for plan in self._pinned:
+            plan.pin(-1)
+        self._pinned = []
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def _param_state(model):
+    return tuple((p.data_ptr(), p._version) for p in model.parameters())
+
+
+class Predictor(object):
+    """Top-k answers of link-prediction queries on one graph.
+
+        predictor = Predictor(model, data, k=10)
+        ids, scores, count = predictor.tails(h, r)       # (n, k), (n, k), (n): the best tails of every (h[i], r[i], ?)
+        ids, scores, count = predictor.heads(t, r)       # ... the best heads of every (?, r[i], t[i])
+
+    Known answers are left out (filtered=True): the tails of (h, r, .) / heads of (., r, t) in the filter graph --
+    `filtered_data`, else data.filtered_data when present, else `data` (the rule of eval.evaluate).  On the GPU with use_graph
+    every batch of batch_size queries is one hipGraph replay; one capture per direction is made on first use and kept (and
+    made again when the model's parameters change or a call's known lists outgrow the capture's buffer).  A last batch
+    shorter than batch_size is padded with copies of its last query and the padded rows are dropped.  A model outside the
+    fused inference path (models.NotOnFusedPath) runs batch by batch without a capture.  One step in flight, one stream."""
+
+    def __init__(self, model, data, k=10, batch_size=8, filtered_data=None, filtered=True, use_graph=True):
+        _check_k(k)
+        if filtered_data is None:
+            filtered_data = getattr(data, "filtered_data", None)
+        self.model, self.data, self.k, self.batch_size = model, data, k, int(batch_size)
+        self.filter_graph = data if filtered_data is None else filtered_data
+        self.filtered, self.use_graph = bool(filtered), bool(use_graph)
+        self._steps = {}
+        self._eager_only = False
+
+    def tails(self, h, r):
+        return self._run(h, r, "tail")
+
+    def heads(self, t, r):
+        return self._run(t, r, "head")
+
+    def close(self):
+        """Drop the captured steps (their plans are unpinned)."""
+        for step in self._steps.values():
+            step.release()
+        self._steps = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _step(self, mode, need):
+        """The captured step of this direction, (re)built when there is none, the weights changed or the known lists of the
+        call do not fit its buffer."""
+        step = self._steps.get(mode)
+        if step is not None and step.params == _param_state(self.model) and (need is None or need <= step.capacity):
+            return step
+        if step is not None:
+            step.release()
+            del self._steps[mode]
+        capacity = None if need is None else max(2 * need, 1 << 16)
+        step = _GraphedPredictStep(self.model, self.data, self.batch_size, self.k, mode, capacity)
+        self._steps[mode] = step
+        return step
+
+    @torch.no_grad()
+    def _run(self, anchor, relation, mode):
+        data, bs, k = self.data, self.batch_size, self.k
+        dev = data.edge_index.device
+        anchor = torch.as_tensor(anchor, dtype=torch.long, device=dev).flatten()
+        relation = torch.as_tensor(relation, dtype=torch.long, device=dev).flatten()
+        if anchor.shape != relation.shape:
+            raise ValueError("one relation per query: got %d entities and %d relations" % (len(anchor), len(relation)))
+        n = len(anchor)
+        ids = torch.empty(n, k, dtype=torch.long, device=dev)
+        scores = torch.empty(n, k, dtype=torch.float32, device=dev)
+        count = torch.empty(n, dtype=torch.long, device=dev)
+        if n == 0:
+            return ids, scores, count
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            ptr = index = None
+            if self.filtered:       # the known lists of the whole call, once
+                ptr, index = known_answers(self.filter_graph, anchor, relation, mode)
+            start = 0
+            if self.use_graph and dev.type == "cuda" and not self._eager_only:
+                try:
+                    step = self._step(mode, index.numel() if self.filtered else None)
+                    pad = (-n) % bs
+                    if pad:
+                        anchor_p = torch.cat([anchor, anchor[-1:].expand(pad)])
+                        relation_p = torch.cat([relation, relation[-1:].expand(pad)])
+                        ptr_p = None if ptr is None else torch.cat([ptr, ptr[-1:].expand(pad)])     # (padded rows: no list)
+                    else:
+                        anchor_p, relation_p, ptr_p = anchor, relation, ptr
+                    if self.filtered:
+                        step.load_index(index)
+                    for lo in range(0, n, bs):
+                        rows = min(bs, n - lo)
+                        b_ids, b_scores, b_count = step(anchor_p[lo:lo + bs], relation_p[lo:lo + bs],
+                                                        None if ptr_p is None else ptr_p[lo:lo + bs + 1])
+                        ids[lo:lo + rows].copy_(b_ids[:rows], non_blocking=True)
+                        scores[lo:lo + rows].copy_(b_scores[:rows], non_blocking=True)
+                        count[lo:lo + rows].copy_(b_count[:rows], non_blocking=True)
+                    start = n
+                except models.NotOnFusedPath:       # model outside the fused inference path: everything runs eagerly below
+                    torch.cuda.synchronize()
+                    self._eager_only = True
+            for lo in range(start, n, bs):
+                pred = self.model(data, _candidates(data, anchor[lo:lo + bs], relation[lo:lo + bs], mode)).float()
+                b_ptr = None if ptr is None else ptr[lo:lo + len(pred) + 1]
+                # the fused kernel on the GPU; the restatement with the same interface elsewhere (as eval._local_rows does)
+                select = filtered_topk if pred.is_cuda else filtered_topk_reference
+                b_ids, b_scores, b_count = select(pred, k, b_ptr, index)
+                ids[lo:lo + len(pred)], scores[lo:lo + len(pred)], count[lo:lo + len(pred)] = b_ids, b_scores, b_count
+        finally:
+            self.model.train(was_training)
+        return ids, scores, count
