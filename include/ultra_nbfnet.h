@@ -373,6 +373,40 @@ int32_t ultra_filtered_topk(const void *score, const int64_t *known_ptr, const i
                             int64_t n_cand, int32_t k, int64_t *ids_out, void *scores_out, int64_t *count_out, void *workspace,
                             int64_t workspace_bytes, void *stream);
 
+/* ---- compiled execution of complex logical queries ----
+ * ultra_query_segment: what a batch of UltraQuery stack machines does between two projection calls, as one launch.  The
+ * program arrays are device memory, int32: entry_depth, push_row, pop_row (batch each), op_ptr (batch + 1), ops
+ * (op_ptr[batch] words).  stack (batch, 2, num_node) fp32 contiguous: slot d of sample b at ((b * 2 + d) * num_node).
+ * Sample b, whose stack holds entry_depth[b] values on entry:
+ *   1. push_row[b] >= 0: push row push_row[b] of push_src (push_rows, num_node);
+ *   2. ops[op_ptr[b] : op_ptr[b + 1]] in order -- a word e >= 0 pushes the one-hot set of entity e (1.0 at e, 0.0 elsewhere),
+ *      -1 replaces the two top values x (below) and y (top) by x AND y, -2 by x OR y, -3 replaces the top x by 1 - x;
+ *   3. pop_row[b] >= 0: pop the top into row pop_row[b] of pop_dst (pop_rows, num_node).
+ * A sample without work is not touched; only live slots are read and only changed slots that are still live are written.  An
+ * op that would overflow or underflow the two slots, and a row outside push_rows / pop_rows, is skipped (the host compiler
+ * refuses such programs).  logic 0 product: x * y, (x + y) - x * y; 1 godel: min, max, a NaN in either operand gives NaN;
+ * 2 lukasiewicz: max(x + y - 1, 0), min(x + y, 1), NaN propagating -- each operation rounded as torch rounds it, no
+ * contraction.  sym_stack / sym_push_src / sym_pop_dst: a second stack that runs the same program (the symbolic sets), or all
+ * NULL.  push_src NULL (push_rows 0): nothing is pushed from it; pop_dst alike.
+ * No LDS, no atomics, no allocation, no memset, no host synchronisation: the call records into a hipGraph.
+ * stack_depth != 2, dtype != 0 (fp32) or num_node >= 2^31: ULTRA_ERR_UNSUPPORTED, decided before any pointer is looked at.
+ * NULL program arrays or stack, batch outside [0, 65535], num_node <= 0, logic outside [0, 2], a buffer that disagrees with
+ * its row count, symbolic buffers that do not mirror the neural ones: ULTRA_ERR_INVALID, nothing is launched.  batch == 0:
+ * ULTRA_OK.
+ *
+ * ultra_nonzero_lists: per row of x (batch, n) fp32 contiguous the ids v with x[b, v] != 0 (a NaN counts, -0.0 does not: the
+ * rule of ultra_traversal_dropout), ascending, at index_out[ptr_out[b] : ptr_out[b + 1]]; ptr_out (batch + 1) int64,
+ * ptr_out[0] = 0 -- the layout ultra_filtered_topk and ultra_filtered_rank take.  counts: (batch) int64 of scratch.  Two
+ * launches (counts per row; scan and fill), no atomics, no host synchronisation: the same integers on every run.
+ * capacity (the ids index_out holds) < batch * n: ULTRA_ERR_INVALID, decided on the host.
+ */
+int32_t ultra_query_segment(const int32_t *entry_depth, const int32_t *push_row, const int32_t *pop_row, const int32_t *op_ptr,
+                            const int32_t *ops, int64_t batch, int64_t num_node, int32_t stack_depth, int32_t dtype,
+                            int32_t logic, void *stack, const void *push_src, int64_t push_rows, void *pop_dst,
+                            int64_t pop_rows, void *sym_stack, const void *sym_push_src, void *sym_pop_dst, void *stream);
+int32_t ultra_nonzero_lists(const void *x, int64_t batch, int64_t n, int64_t *counts, int64_t *ptr_out, int64_t *index_out,
+                            int64_t capacity, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

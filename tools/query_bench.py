@@ -1,12 +1,14 @@
 """Timing of complex logical query answering (UltraQuery) at FB15k237's shape on one GPU.
 
-    python tools/query_bench.py [--per-type 16] [--reps 3]
+    python tools/query_bench.py [--per-type 16] [--reps 3] [--compiled]
 
 Prints one JSON line:
   types            per BetaE type: queries/s of UltraQuery.forward + batch_evaluate on a batch of `per-type` queries of that
                    type (host clock around a device synchronise, after one warm-up batch), and that time split into
                    projections (RelationProjection calls, by device events), ranking (batch_evaluate) and executor (the
-                   rest: the torch stack machine and fuzzy logic)
+                   rest: the torch stack machine and fuzzy logic); with --compiled also compiled_ms,
+                   compiled_projection_ms and compiled_executor_ms: the same batches through query_exec.forward (the host
+                   compiler, one upload and one ultra_query_segment launch per segment in place of the stack machine)
   traversal        ultra_symbolic_traversal vs its torch restatement (the reference's form: (B, E) relation mask, gather,
                    max-scatter), 64 queries, fp32, by device events; bytes = CSR + one read of h per edge of the query's
                    relation + the output -- the kernel is a gather whose time should be judged against latency, not HBM bytes
@@ -29,7 +31,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from ultra_amd import models, query_data, query_eval, synthetic, ultraquery  # noqa: E402
+from ultra_amd import models, query_data, query_eval, query_exec, synthetic, ultraquery  # noqa: E402
 
 HBM_BPS = 8e12
 
@@ -50,6 +52,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--per-type", type=int, default=16)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--compiled", action="store_true", help="also time the compiled executor (query_exec.forward)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     with open(os.path.join(ROOT, "tests", "golden", "ultraquery.pt.xz"), "rb") as f:
@@ -82,28 +85,37 @@ def main():
         for k in range(2):
             items = [ds[i] for i in idx[k * args.per_type:(k + 1) * args.per_type]]
             batches.append({key: torch.stack([torch.as_tensor(it[key]) for it in items]).to(dev) for key in items[0]})
-        rows = []
-        with torch.no_grad():
-            for rep in range(1 + args.reps):
-                batch = batches[rep % 2]
-                proj_ms.clear()
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                pred = model(graph, batch["query"], symbolic_traversal=False)
-                r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                r0.record()
-                query_eval.batch_evaluate(pred, (batch["type"], batch["easy_answer"], batch["hard_answer"]))
-                r1.record()
-                torch.cuda.synchronize()
-                total = (time.perf_counter() - t0) * 1e3
-                if rep:
-                    proj = sum(a.elapsed_time(b) for a, b in proj_ms)
-                    rank = r0.elapsed_time(r1)
-                    rows.append((total, proj, rank, len(proj_ms)))
-        total, proj, rank = (statistics.median(r[i] for r in rows) for i in range(3))
+
+        def measure(forward):
+            rows = []
+            with torch.no_grad():
+                for rep in range(1 + args.reps):
+                    batch = batches[rep % 2]
+                    proj_ms.clear()
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    pred = forward(batch["query"])
+                    r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    r0.record()
+                    query_eval.batch_evaluate(pred, (batch["type"], batch["easy_answer"], batch["hard_answer"]))
+                    r1.record()
+                    torch.cuda.synchronize()
+                    total = (time.perf_counter() - t0) * 1e3
+                    if rep:
+                        proj = sum(a.elapsed_time(b) for a, b in proj_ms)
+                        rank = r0.elapsed_time(r1)
+                        rows.append((total, proj, rank, len(proj_ms)))
+            return tuple(statistics.median(r[i] for r in rows) for i in range(3)) + (rows[0][3],)
+
+        total, proj, rank, calls = measure(lambda q: model(graph, q, symbolic_traversal=False))
         types[name] = dict(queries_per_s=round(args.per_type / total * 1e3, 1), ms=round(total, 2),
                            projection_ms=round(proj, 2), ranking_ms=round(rank, 3),
-                           executor_ms=round(total - proj - rank, 2), projection_calls=rows[0][3])
+                           executor_ms=round(total - proj - rank, 2), projection_calls=calls)
+        if args.compiled:
+            total, proj, rank, calls = measure(lambda q: query_exec.forward(model, graph, q, symbolic_traversal=False))
+            assert calls == types[name]["projection_calls"]
+            types[name].update(compiled_ms=round(total, 2), compiled_projection_ms=round(proj, 2),
+                               compiled_executor_ms=round(total - proj - rank, 2))
 
     # kernel 2a against the restatement
     n = graph.num_nodes

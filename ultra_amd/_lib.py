@@ -123,7 +123,9 @@ def _load():
     lib.ultra_filtered_topk_workspace.argtypes = [i64, i64, i32]
     lib.ultra_filtered_topk_workspace.restype = i64
     lib.ultra_filtered_topk.argtypes = [vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp]
-    lib.ultra_beam_search_layer.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, i64, i32, vp, vp, vp]
+    lib.ultra_query_segment.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, vp, vp, i64, vp, i64, vp, vp, vp, vp]
+    lib.ultra_nonzero_lists.argtypes = [vp, i64, i64, vp, vp, vp, i64, vp]
+    lib.ultra_beam_search_layer.argtypes =[vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, i64, i32, vp, vp, vp]
     lib.ultra_symbolic_traversal.argtypes = [vp, vp, vp, i64, vp, i64, i32, vp, vp, vp]
     lib.ultra_answer_ranking.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp]
     lib.ultra_strict_negatives.argtypes = [vp, i64, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp]

@@ -190,11 +190,17 @@ def evaluate(pred, target, metrics, id2type):
     return metric
 
 
-def predict_and_target(model, graph, batch, batch_evaluate_fn=batch_evaluate):
+def predict_and_target(model, graph, batch, batch_evaluate_fn=batch_evaluate, compiled=False):
     """run_query.py:32-52 at inference: the logits of a batch, its ranks and the predicted answer-set sizes
-    num_pred = sum(sigmoid(pred) * (sigmoid(pred) > 0.5)), over the restricted logits when the graph restricts nodes."""
+    num_pred = sum(sigmoid(pred) * (sigmoid(pred) > 0.5)), over the restricted logits when the graph restricts nodes.
+    compiled: the logits come from the compiled executor (query_exec.forward: the same bits, without the interpreter's host
+    synchronisations) instead of model.forward."""
     query, type, easy_answer, hard_answer = batch["query"], batch["type"], batch["easy_answer"], batch["hard_answer"]
-    pred = model(graph, query, symbolic_traversal=False)
+    if compiled:
+        from . import query_exec
+        pred = query_exec.forward(model, graph, query, symbolic_traversal=False)
+    else:
+        pred = model(graph, query, symbolic_traversal=False)
     restrict_nodes = getattr(graph, "restrict_nodes", None)
     ranking, answer_ranking = batch_evaluate_fn(pred, (type, easy_answer, hard_answer), restrict_nodes)
     keep = _keep_mask(restrict_nodes, pred.shape[-1], pred.device)
@@ -222,11 +228,11 @@ def gather_results(pred, target):
 @torch.no_grad()
 def test_queries(model, graph, queries, batch_size, id2type, metrics=("mrr", "hits@1", "hits@3", "hits@10", "mape",
                                                                       "spearmanr", "auroc"),
-                 device=None, batch_evaluate_fn=batch_evaluate):
+                 device=None, batch_evaluate_fn=batch_evaluate, compiled=False):
     """run_query.py:159-189: score `queries` (a dataset of dicts query / type / easy_answer / hard_answer, e.g.
     query_data.QueryDataset) in batches of `batch_size`, this rank's DistributedSampler shard (shuffled with its default
     seed, as the reference's; where the query count does not divide by the world size it pads with repeated queries, which
-    then count twice); gather every rank's results and return the metrics on every rank."""
+    then count twice); gather every rank's results and return the metrics on every rank.  compiled: see predict_and_target."""
     from torch.utils import data as torch_data
     world, rank = udist.world_size(), udist.rank()
     sampler = torch_data.DistributedSampler(queries, world, rank)
@@ -239,7 +245,7 @@ def test_queries(model, graph, queries, batch_size, id2type, metrics=("mrr", "hi
     for batch in loader:
         if device is not None:
             batch = {k: v.to(device) for k, v in batch.items()}
-        p, t = predict_and_target(model, graph, batch, batch_evaluate_fn)
+        p, t = predict_and_target(model, graph, batch, batch_evaluate_fn, compiled=compiled)
         preds.append(p)
         targets.append(t)
     pred = tuple(torch.cat(x) for x in zip(*preds))
