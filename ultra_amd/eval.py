@@ -163,7 +163,7 @@ def _local_rows(model, test_data, filt, mine, batch_size, use_graph, in_flight, 
                 steps = [GraphedEvalStep(model, test_data, batch_size, t_index, h_index)]
                 # ... if the plans the captured step really uses are all of that kind (a max-aggregate model sends its relation
                 # graph to a re-associating plan), and while another capture fits: each holds its own activation memory
-                while want_more and len(steps) < in_flight and all(p.exact for p in steps[0]._pinned):
+                while want_more and len(steps) < in_flight and steps[0].exact_order:
                     try:
                         steps.append(GraphedEvalStep(model, test_data, batch_size, t_index, h_index))
                     except (torch.cuda.OutOfMemoryError, RuntimeError) as err:

@@ -1,4 +1,4 @@
-"""hipGraph capture of the inference forward.
+"""hipGraph capture of the engine's steps.
 
 The forward of one batch is ~30 short launches (layer-0 kernels, 5 rspmm + updates on the entity graph, 5 fused
 relation-graph layers, prologue, projections, readout); on a static graph with a fixed batch shape
@@ -7,82 +7,143 @@ hipStreamBeginCapture / hipGraphLaunch) and replayed: one host call per forward 
 torch's current stream, which is the capturing stream during capture; plans, schedules and the
 LDS opt-in are created by the eager warm-up runs, so nothing allocates inside the captured region.
 
-What the captured graph points at stays alive and in place for as long as the GraphedForward does:
+Four steps are replayed this way -- the bare forward (GraphedForward), a batch of the filtered-ranking protocol
+(GraphedEvalStep), a batch of top-k answers (predict._GraphedPredictStep) and the training step (train.GraphedTrainStep) -- and
+all four inherit ONE lifecycle, `Capture`: warm-up on a side stream, pinning, capture, release.  What a captured graph points
+at stays alive and in place for as long as its Capture does:
   * the aggregation plans its warm-up runs asked for (rspmm.record_plans) are held and pinned (ultra_plan_pin) -- the
     plan cache is an LRU and would otherwise free device arrays the graph still reads once enough other graphs have
-    been seen; plans the capture never used stay free to grow their scratch buffers;
-  * the model's parameters are watched: the forward caches stacked copies of some weights (relation projections), so a
-    parameter update (optimizer step, load_state_dict) makes the next call re-capture instead of replaying stale values.
+    been seen; plans the capture never used stay free to grow their scratch buffers.  A warm-up or capture that fails
+    (out of memory, models.NotOnFusedPath, a kernel error) unpins them at once and leaves no graph behind: __del__ of a
+    half-built object is not something to rely on;
+  * the model's parameters are watched (param_state): the forward caches stacked copies of some weights (relation
+    projections), so a parameter update (optimizer step, load_state_dict) makes the next call re-capture instead of
+    replaying stale values.
 """
+import contextlib
+
 import torch
 
-from . import dense, rspmm
+from . import rspmm
 
 
-class GraphedForward(object):
+def param_state(model):
+    """What a capture that reads the model's parameters remembers of them: it is stale once this changes."""
+    return tuple((p.data_ptr(), p._version) for p in model.parameters())
+
+
+class Capture(object):
+    """warm_up(step, runs), then capture(step) once or twice; release() lets go of the plans and the graphs.
+
+    plans: the plans the warm-up asked for, each pinned once; graphs: the captured graphs, in order; stream: the warm-up's
+    side stream.  no_grad: warm-up and capture run under torch.no_grad() (the inference steps; the training step not)."""
+
+    def __init__(self, device, no_grad=True):
+        self.device, self.no_grad = device, no_grad
+        self.plans, self.graphs, self.stream = [], [], None
+
+    @property
+    def graph(self):
+        return self.graphs[0]
+
+    _pinned = property(lambda self: self.plans)       # (the list's former, private name: still readable)
+
+    @property
+    def exact_order(self):
+        """Every plan this capture uses is a reference-order plan (what it really uses, not the default kind)."""
+        return all(plan.exact for plan in self.plans)
+
+    def release(self):
+        while self.plans:
+            self.plans.pop().pin(-1)
+        self.graphs = []
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+    def _grad_mode(self):
+        return torch.no_grad() if self.no_grad else contextlib.nullcontext()
+
+    @contextlib.contextmanager
+    def recording(self):
+        """The plans get_plan() hands out inside the block are pinned when it ends, exactly those and each once (what the
+        Capture held before is released first); an exception inside leaves nothing pinned."""
+        self.release()
+        try:
+            with rspmm.record_plans() as used:
+                yield
+            for plan in used.plans:
+                plan.pin(+1)
+                self.plans.append(plan)
+        except BaseException:
+            self.release()
+            raise
+
+    def warm_up(self, step, runs):
+        """`runs` eager step() on a fresh side stream that waits for the current one; joined and synchronised afterwards."""
+        with torch.cuda.device(self.device), self.recording():
+            self.stream = torch.cuda.Stream()
+            self.stream.wait_stream(torch.cuda.current_stream())
+            with self._grad_mode(), torch.cuda.stream(self.stream):
+                for _ in range(runs):
+                    step()
+            torch.cuda.current_stream().wait_stream(self.stream)
+            torch.cuda.synchronize()
+
+    def capture(self, step, stream=None, pool=None, upload=False):
+        """step() recorded into a new graph (appended to `graphs`); returns what step() returned.  stream: the capture stream
+        (None: torch's own); pool: the memory pool of an earlier graph to share; upload: replay once and synchronise -- the first
+        launch of an instantiated graph also uploads it (kernel arguments, node descriptors), and that is then part of building
+        the graph, not of the caller's first batch (a real step for a graph that updates state: not for those)."""
+        try:
+            with torch.cuda.device(self.device):
+                graph = torch.cuda.CUDAGraph()
+                # thread-local capture mode: helper threads of the process (RCCL's watchdog polls events) must not be able to
+                # invalidate the capture; everything captured here is enqueued by this thread
+                with self._grad_mode(), torch.cuda.graph(graph, pool=pool, stream=stream, capture_error_mode="thread_local"):
+                    out = step()
+                if upload:
+                    graph.replay()
+                    torch.cuda.synchronize()
+        except BaseException:
+            self.release()
+            raise
+        self.graphs.append(graph)
+        return out
+
+
+class GraphedForward(Capture):
     """score = GraphedForward(model, data, example_batch)(batch) for batches of example_batch's shape."""
 
     def __init__(self, model, data, example_batch, warmup=3, launch_grid=0):
         """launch_grid > 0: the aggregation kernels of this capture are launched with that many workgroups instead of one per
         CU (rspmm.tuning_scope(grid=...) around warm-up and capture) -- see PipelinedForward."""
         assert example_batch.is_cuda, "graph capture needs GPU tensors"
+        Capture.__init__(self, example_batch.device)
         self.model = model
         self.data = data
         self.warmup = warmup
         self.launch_grid = int(launch_grid)
         self.static_batch = example_batch.clone()
-        self._pinned = []
-        self._capture()
+        self._recapture()
 
-    def _param_state(self):
-        return tuple((p.data_ptr(), p._version) for p in self.model.parameters())
-
-    def _release(self):
-        for plan in self._pinned:
-            plan.pin(-1)
-        self._pinned = []
-
-    def _capture(self):
-        if self.launch_grid > 0:
-            with rspmm.tuning_scope(grid=self.launch_grid):
-                self._capture_now()
-        else:
-            self._capture_now()
-
-    def _capture_now(self):
+    def _recapture(self):
         model, data = self.model, self.data
-        self._release()
+        self._watched = None                  # (a capture that fails is made again by the next call)
         model.eval()
-        with torch.cuda.device(self.static_batch.device):
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.no_grad(), torch.cuda.stream(side), rspmm.record_plans() as used:
-                for _ in range(self.warmup):
-                    model(data, self.static_batch)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            self._pinned = used.plans                 # exactly the plans the warm-up runs asked for
-            for plan in self._pinned:
-                plan.pin(+1)
+
+        def forward():
+            return model(data, self.static_batch)
+        with rspmm.tuning_scope(**({"grid": self.launch_grid} if self.launch_grid > 0 else {})):
+            self.warm_up(forward, self.warmup)
             # (a table of cached relation representations the capture reads from stays alive with the capture)
             self._rel_table_ref = getattr(model, "_rel_table", None)
-            self.graph = torch.cuda.CUDAGraph()
-            # thread-local capture mode: helper threads of the process (RCCL's watchdog polls events) must not be able to
-            # invalidate the capture; everything captured here is enqueued by this thread
-            with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                self.static_out = model(data, self.static_batch)
-            # the first launch of an instantiated graph also uploads it (kernel arguments, node descriptors): done here, as
-            # part of building the graph, not by the caller's first batch
-            self.graph.replay()
-            torch.cuda.synchronize()
+            self.static_out = self.capture(forward, upload=True)
         self.valid = getattr(model.entity_model, "_pending_valid", None) if hasattr(model, "entity_model") else None
-        self._params = self._param_state()
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
+        self._watched = param_state(model)
 
     def _load_input(self, batch):
         """batch -> the graph's input buffer.  A plain 16-byte streaming kernel: the runtime's device-to-device memcpy
@@ -101,8 +162,8 @@ class GraphedForward(object):
         if batch.shape != self.static_batch.shape:
             raise ValueError("GraphedForward was captured for batch shape %s, got %s"
                              % (tuple(self.static_batch.shape), tuple(batch.shape)))
-        if self._param_state() != self._params:       # weights changed since the capture: the cached stacks are stale
-            self._capture()
+        if param_state(self.model) != self._watched:      # weights changed since the capture: the cached stacks are stale
+            self._recapture()
         self._load_input(batch)
         self.graph.replay()
         if check and self.valid is not None:
@@ -218,7 +279,7 @@ class PipelinedForward(object):
         self.slots = []
         for _ in range(int(depth)):
             self.slots.append(make())
-            if not all(p.exact for p in getattr(self.slots[-1], "_pinned", [])):     # (what the capture really uses, not the default kind)
+            if not getattr(self.slots[-1], "exact_order", True):     # (what the capture really uses, not the default kind)
                 raise RuntimeError("PipelinedForward: this model's forward uses a re-associating plan (scratch buffers that "
                                    "concurrent forwards would share); run its batches one at a time")
         dev = example_batch.device
@@ -321,7 +382,7 @@ class PipelinedForward(object):
         return out
 
 
-class GraphedEvalStep(object):
+class GraphedEvalStep(Capture):
     """One batch of the filtered-ranking protocol (script/run.py:131-160) as ONE hipGraph replay: candidate construction
     (tasks.all_negative), the tail and the head forward, and the two fused rank kernels.  Per batch the host copies three
     small tensors into the graph's inputs -- the (bs, 3) triples and the two (bs + 1) offset vectors into the known-answer
@@ -333,6 +394,7 @@ class GraphedEvalStep(object):
         from . import tasks
         from ._lib import check, lib
         dev = data.edge_index.device
+        Capture.__init__(self, dev)
         self.model, self.data, self.bs = model, data, batch_size
         self.t_index, self.h_index = known_tail.contiguous(), known_head.contiguous()
         self.batch = torch.zeros(batch_size, 3, dtype=torch.long, device=dev)
@@ -340,7 +402,6 @@ class GraphedEvalStep(object):
         self.h_ptr = torch.zeros(batch_size + 1, dtype=torch.long, device=dev)
         self.rows = torch.zeros(2 * batch_size, 3, dtype=torch.long, device=dev)
         self.rows[:batch_size, 2] = 1
-        self._pinned = []
         n = data.num_nodes
 
         def step():
@@ -357,28 +418,9 @@ class GraphedEvalStep(object):
                 self.rows[lo:lo + batch_size, 0] = rank
                 self.rows[lo:lo + batch_size, 1] = neg
 
-        with torch.cuda.device(dev):
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.no_grad(), torch.cuda.stream(side), rspmm.record_plans() as used:
-                for _ in range(warmup):
-                    step()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            self._pinned = used.plans
-            for plan in self._pinned:
-                plan.pin(+1)
-            try:
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                    step()
-            except BaseException:
-                # a capture that fails (out of memory for the second step of evaluate(), a kernel error) must not leave its plans
-                # pinned for the life of the process: __del__ of a half-built object is not something to rely on
-                for plan in self._pinned:
-                    plan.pin(-1)
-                self._pinned = []
-                raise
+        # (a capture that fails -- out of memory for the second step of evaluate(), a kernel error -- leaves no plan pinned)
+        self.warm_up(step, warmup)
+        self.capture(step)
 
     def __call__(self, batch, t_ptr, h_ptr):
         """rows (2 bs, 3) of this batch -- a view of the static buffer: copy before the next call."""
@@ -387,10 +429,3 @@ class GraphedEvalStep(object):
         self.h_ptr.copy_(h_ptr, non_blocking=True)
         self.graph.replay()
         return self.rows
-
-    def __del__(self):
-        try:
-            for plan in self._pinned:
-                plan.pin(-1)
-        except Exception:
-            pass

@@ -7,7 +7,9 @@ names, constructor arguments, forward signatures and state-dict keys, so
 EntityNBFNet.visualize / beam_search_distance / topk_average_length (base_nbfnet.py:156-263) explain one prediction with
 its top paths: ultra_amd.explain (HIP beam search); Ultra.visualize is the same from the full model.
 """
+import contextlib
 import copy
+import threading
 from collections.abc import Sequence
 
 import torch
@@ -22,8 +24,22 @@ PROLOGUE_FAST_PATH = True
 # (measured on MI355X, tools/step_probe.py: the fork / join of the side stream inside the captured graph costs more than the
 # 11 us of fill it hides -- 0.717 vs 0.687 ms per step one batch at a time, 0.631 vs 0.621 two in flight -- so: off)
 PREFILL_LAYER0 = False
-# set by train.GraphedTrainStep around its capture: the generic (training) path of EntityNBFNet.forward may be recorded
-CAPTURE_GENERIC_PATH = False
+_capture_flags = threading.local()
+
+
+@contextlib.contextmanager
+def capture_generic_path():
+    """with capture_generic_path(): ... -- inside, a hipGraph capture made by THIS thread may record the generic (training) path of
+    EntityNBFNet.forward (train.GraphedTrainStep around its capture); off again afterwards, whatever happens."""
+    _capture_flags.generic = True
+    try:
+        yield
+    finally:
+        _capture_flags.generic = False
+
+
+def generic_path_capturable():
+    return getattr(_capture_flags, "generic", False)
 # the six relation_projection MLPs of a training step as one autograd node (A/B switch for tests: two batched torch products are the other side)
 RELATION_PROJECTION_NODE = True
 # the training step's 0/1 edge vector straight from the batch's triples (dense.easy_edge_keep; A/B switch for tests: off = the
@@ -484,11 +500,11 @@ class EntityNBFNet(BaseNBFNet):
                 self._check_valid(valid)
                 return score
             # (shape not covered by the fused readout: fall through to the generic path below)
-        if batch.is_cuda and torch.cuda.is_current_stream_capturing() and not CAPTURE_GENERIC_PATH:
+        if batch.is_cuda and torch.cuda.is_current_stream_capturing() and not generic_path_capturable():
             # the generic path goes through torch reductions / memsets whose captured nodes were seen to go stale
             # when replays interleave with eager work (ROCm 7.2); of the inference paths only the fused one is
-            # graph-captured.  train.GraphedTrainStep captures the training step (this path, under autograd) and sets the
-            # switch for the length of its capture.
+            # graph-captured.  train.GraphedTrainStep captures the training step (this path, under autograd) inside
+            # capture_generic_path().
             raise NotOnFusedPath("hipGraph capture is supported for the fused inference path only "
                                  "(64-d hidden, no concat_hidden, eval mode, no_grad)")
         # One reduction tells, per row, whether heads / tails / relations are constant along the candidates:

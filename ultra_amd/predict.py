@@ -18,7 +18,8 @@ import ctypes
 
 import torch
 
-from . import _lib, models, rspmm, tasks
+from . import _lib, models, tasks
+from .graph import Capture, param_state
 
 
 def filtered_topk_reference(pred, k, ptr=None, index=None):
@@ -107,13 +108,14 @@ def _candidates(data, anchor, relation, mode):
     return torch.stack([fixed, every, r] if mode == "tail" else [every, fixed, r], dim=-1)
 
 
-class _GraphedPredictStep(object):
-    """One batch of one direction as ONE hipGraph replay (modelled on graph.GraphedEvalStep): candidate construction, the
+class _GraphedPredictStep(Capture):
+    """One batch of one direction as ONE hipGraph replay (a graph.Capture, like graph.GraphedEvalStep): candidate construction, the
     forward and ultra_filtered_topk.  Per batch the host copies the (bs) anchors and relations and the (bs + 1) offsets into
     the known lists of the whole call, which live in a buffer of the step (`load_index`, once per call)."""
 
     def __init__(self, model, data, batch_size, k, mode, index_capacity, warmup=2):
         dev = data.edge_index.device
+        Capture.__init__(self, dev)
         self.model, self.bs, self.k, self.mode = model, batch_size, k, mode
         self.anchor = torch.zeros(batch_size, dtype=torch.long, device=dev)
         self.relation = torch.zeros(batch_size, dtype=torch.long, device=dev)
@@ -127,7 +129,6 @@ class _GraphedPredictStep(object):
         n = int(data.num_nodes)
         ws_bytes = _lib.lib.ultra_filtered_topk_workspace(batch_size, n, k)
         self.ws = torch.empty(max(1, ws_bytes // 8), dtype=torch.long, device=dev)
-        self._pinned = []
 
         def step():
             pred = model(data, _candidates(data, self.anchor, self.relation, mode)).float().contiguous()
@@ -136,26 +137,9 @@ class _GraphedPredictStep(object):
                                                     self.ids.data_ptr(), self.scores.data_ptr(), self.count.data_ptr(),
                                                     self.ws.data_ptr(), self.ws.numel() * 8, _stream(dev)))
 
-        with torch.cuda.device(dev):
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.no_grad(), torch.cuda.stream(side), rspmm.record_plans() as used:
-                for _ in range(warmup):
-                    step()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            self._pinned = used.plans
-            for plan in self._pinned:
-                plan.pin(+1)
-            try:
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                    step()
-            except BaseException:
-                # (a failed capture must not leave its plans pinned for the life of the process: graph.GraphedEvalStep)
-                self.release()
-                raise
-        self.params = _param_state(model)
+        self.warm_up(step, warmup)
+        self.capture(step)
+        self.params = param_state(model)
 
     def load_index(self, index):
         self.index[:index.numel()].copy_(index, non_blocking=True)
@@ -168,21 +152,6 @@ class _GraphedPredictStep(object):
             self.ptr.copy_(ptr, non_blocking=True)
         self.graph.replay()
         return self.ids, self.scores, self.count
-
-    def release(self):
-        for plan in self._pinned:
-            plan.pin(-1)
-        self._pinned = []
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
-
-def _param_state(model):
-    return tuple((p.data_ptr(), p._version) for p in model.parameters())
 
 
 class Predictor(object):
@@ -231,7 +200,7 @@ class Predictor(object):
         """The captured step of this direction, (re)built when there is none, the weights changed or the known lists of the
         call do not fit its buffer."""
         step = self._steps.get(mode)
-        if step is not None and step.params == _param_state(self.model) and (need is None or need <= step.capacity):
+        if step is not None and step.params == param_state(self.model) and (need is None or need <= step.capacity):
             return step
         if step is not None:
             step.release()

@@ -116,7 +116,7 @@ class PretrainTrainer(object):
 
     capture=True: a train.GraphedTrainStep per training graph for full batches of `batch_size` rows, all over the same model and
     optimizer (which must be capturable: train.make_adamw(model, capturable=True)).  Every capture starts with .grad unset (the
-    step's own warm-up does that), and each step's gradient tensors are held here: the graphs write them, and no later capture
+    step's own warm-up does that), and each step holds its own gradient tensors: the graphs write them, and no later capture
     may take their memory.  Each capture has a memory pool of its own.  Build the trainer before any eager training step on the
     model: such a step leaves the model holding its autograd graph (EntityNBFNet.query), whose gradient accumulators belong to
     the stream of that step, and a capture must not reach them.  Batches of another row count (the short last batch of an
@@ -135,10 +135,9 @@ class PretrainTrainer(object):
         self._replayed = set()
         if capture:
             for gid, graph in enumerate(self.graphs):
-                step = train.GraphedTrainStep(model, graph, optimizer, example_batch(graph, self.batch_size, self.num_negative),
-                                              adversarial_temperature, self.num_negative, warmup, process_group)
-                step._held_grads = [p.grad for p in step._params()]
-                self.steps[gid] = step
+                example = example_batch(graph, self.batch_size, self.num_negative)
+                self.steps[gid] = train.GraphedTrainStep(model, graph, optimizer, example, adversarial_temperature,
+                                                         self.num_negative, warmup, process_group)
             optimizer.zero_grad(set_to_none=True)
 
     @torch.no_grad()
@@ -163,12 +162,7 @@ class PretrainTrainer(object):
         loss = train.ranking_loss(pred, self.temperature, self.num_negative)
         loss.backward()
         if self.world > 1:
-            params = [p for group in opt.param_groups for p in group["params"] if p.grad is not None]
-            flat = torch.cat([p.grad.reshape(-1) for p in params])
-            torch.distributed.all_reduce(flat, group=self.group)
-            flat.div_(self.world)
-            torch._foreach_copy_([p.grad for p in params],
-                                 [piece.view_as(p.grad) for piece, p in zip(flat.split([p.numel() for p in params]), params)])
+            train.all_reduce_grads([p for group in opt.param_groups for p in group["params"]], self.world, self.group)
         opt.step()
         opt.zero_grad(set_to_none=True)
         return loss.detach()

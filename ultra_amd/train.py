@@ -17,6 +17,7 @@ import torch
 from torch.nn import functional as F
 
 from . import models, rspmm
+from .graph import Capture
 
 
 def ranking_loss(pred, adversarial_temperature=1.0, num_negative=None):
@@ -89,22 +90,46 @@ def train_step(model, data, batch, optimizer, adversarial_temperature=1.0, num_n
     return loss.detach()
 
 
-class GraphedTrainStep(object):
+def flatten_grads(params, out=None):
+    """The gradients of `params` as one flat bucket (into `out`, a bucket made by an earlier call, when given)."""
+    grads = [p.grad.reshape(-1) for p in params if p.grad is not None]
+    return torch.cat(grads) if out is None else torch.cat(grads, out=out)
+
+
+def unflatten_grads(flat, params):
+    grads = [p.grad for p in params if p.grad is not None]
+    torch._foreach_copy_(grads, [piece.view_as(g) for piece, g in zip(flat.split([g.numel() for g in grads]), grads)])
+
+
+def all_reduce_grads(params, world, group=None, flat=None):
+    """The gradients averaged over the ranks as DDP leaves them, by ONE all-reduce of one flat bucket: flatten, all-reduce,
+    divide by the world size, copy back.  Returns the bucket.  (GraphedTrainStep records the flattening into its first graph and
+    the rest behind the all-reduce into its second.)"""
+    flat = flatten_grads(params, flat)
+    torch.distributed.all_reduce(flat, group=group)
+    flat.div_(world)
+    unflatten_grads(flat, params)
+    return flat
+
+
+class GraphedTrainStep(Capture):
     """loss = GraphedTrainStep(model, data, optimizer, example_batch)(batch) for batches of example_batch's shape.
 
     `optimizer` must keep its state on the device (torch.optim.AdamW(..., fused=True, capturable=True): make_adamw(model,
     capturable=True)).  The warm-up runs that precede the capture are real steps on `example_batch`; parameters and optimiser
-    state are put back to what they were afterwards, IN PLACE (the graph holds their addresses).
+    state are put back to what they were afterwards, IN PLACE (the graph holds their addresses) -- also when the capture fails.
 
     process_group (or an initialised default group of more than one rank): the gradients are averaged over the ranks between
     the backward and the optimiser step -- one all-reduce of one flat bucket.
 
-    What the graph points at stays alive with this object: the plans its warm-up asked for (pinned), the out-edge lists of the
-    first layer's backward, the static input / loss tensors."""
+    What the graph points at stays alive with this object: the plans its warm-up asked for (pinned, graph.Capture), the out-edge
+    lists of the first layer's backward, the static input / loss tensors, and the gradient tensors the graph writes (several
+    steps may share a model: no later capture may take their memory)."""
 
     def __init__(self, model, data, optimizer, example_batch, adversarial_temperature=1.0, num_negative=None, warmup=3,
                  process_group=None):
         assert example_batch.is_cuda, "graph capture needs GPU tensors"
+        Capture.__init__(self, example_batch.device, no_grad=False)
         self.model, self.data, self.optimizer = model, data, optimizer
         self.temperature, self.num_negative = adversarial_temperature, num_negative
         self.static_batch = example_batch.clone()
@@ -116,10 +141,8 @@ class GraphedTrainStep(object):
             if not group.get("capturable", False):
                 raise ValueError("GraphedTrainStep: the optimizer must be built with capturable=True (train.make_adamw(model, "
                                  "capturable=True)): its step counters are read inside the captured graph")
-        self._pinned = []
-        self._capture(warmup)
+        self._build(warmup)
 
-    # ---- the pieces of a step ----
     def _forward_backward(self):
         pred = self.model(self.data, self.static_batch)
         loss = ranking_loss(pred, self.temperature, self.num_negative)
@@ -129,87 +152,65 @@ class GraphedTrainStep(object):
     def _params(self):
         return [p for group in self.optimizer.param_groups for p in group["params"]]
 
-    def _flatten_grads(self):
-        grads = [p.grad.reshape(-1) for p in self._params() if p.grad is not None]
-        if self._flat is None:
-            self._flat = torch.cat(grads)
-        else:
-            torch.cat(grads, out=self._flat)
-
-    def _unflatten_grads(self):
-        grads = [p.grad for p in self._params() if p.grad is not None]
-        pieces = self._flat.split([g.numel() for g in grads])
-        torch._foreach_copy_(grads, [piece.view_as(g) for piece, g in zip(pieces, grads)])
-
-    def _capture(self, warmup):
+    def _build(self, warmup):
         model, opt = self.model, self.optimizer
-        dev = self.static_batch.device
         model.train()
         params = self._params()
         saved_params = [p.detach().clone() for p in params]
         saved_state = {id(p): {k: (v.clone() if torch.is_tensor(v) else v) for k, v in opt.state.get(p, {}).items()}
                        for p in params}
         self._flat = None
-        with torch.cuda.device(dev):
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side), rspmm.record_plans() as used:
-                for _ in range(max(int(warmup), 1)):
-                    opt.zero_grad(set_to_none=True)
-                    self._forward_backward()
-                    if self.world > 1:
-                        self._flatten_grads()
-                        torch.distributed.all_reduce(self._flat, group=self.group)
-                        self._flat.div_(self.world)
-                        self._unflatten_grads()
-                    opt.step()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            self._pinned = used.plans
-            for plan in self._pinned:
-                plan.pin(+1)
-            # (the first layer's backward reads the graph's out-edge lists: an LRU cache owns them, so hold what it holds now)
-            self._held = list(rspmm._OUT_CSR_CACHE.values())
+
+        def warm():
+            opt.zero_grad(set_to_none=True)
+            self._forward_backward()
+            if self.world > 1:
+                self._flat = all_reduce_grads(params, self.world, self.group, self._flat)
+            opt.step()
+
+        def first():
+            loss = self._forward_backward()
+            if self.world > 1:
+                flatten_grads(params, self._flat)
+            else:
+                opt.step()
+            return loss
+
+        def second():
+            self._flat.div_(self.world)
+            unflatten_grads(self._flat, params)
+            opt.step()
+
+        with torch.cuda.device(self.device):
             try:
+                self.warm_up(warm, max(int(warmup), 1))
+                # (the first layer's backward reads the graph's out-edge lists: an LRU cache owns them, so hold what it holds now)
+                self._held = list(rspmm._OUT_CSR_CACHE.values())
                 # the captured backward allocates the gradients from the graph's pool; the capture runs on the warm-up's stream
                 # (autograd's AccumulateGrad nodes remember the stream they were made on)
                 opt.zero_grad(set_to_none=True)
-                models.CAPTURE_GENERIC_PATH = True
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
-                    self.static_loss = self._forward_backward()
+                with models.capture_generic_path():
+                    self.static_loss = self.capture(first, stream=self.stream)
+                    self.step_graph = None
                     if self.world > 1:
-                        self._flatten_grads()
-                    else:
-                        opt.step()
-                self.step_graph = None
-                if self.world > 1:
-                    self.step_graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self.step_graph, pool=self.graph.pool(), stream=side, capture_error_mode="thread_local"):
-                        self._flat.div_(self.world)
-                        self._unflatten_grads()
-                        opt.step()
-            except BaseException:
-                for plan in self._pinned:
-                    plan.pin(-1)
-                self._pinned = []
-                raise
+                        self.capture(second, stream=self.stream, pool=self.graph.pool())
+                        self.step_graph = self.graphs[1]
+                self._grads = [p.grad for p in params]
+                self.valid = getattr(model.entity_model, "_pending_valid", None) if hasattr(model, "entity_model") else None
             finally:
-                models.CAPTURE_GENERIC_PATH = False
-            self.valid = getattr(model.entity_model, "_pending_valid", None) if hasattr(model, "entity_model") else None
-            # parameters and optimiser state back to where they were before the warm-up steps, in place
-            with torch.no_grad():
-                for p, was in zip(params, saved_params):
-                    p.copy_(was)
-                for p in params:
-                    state, was = opt.state.get(p, {}), saved_state[id(p)]
-                    for k, v in state.items():
-                        if torch.is_tensor(v):
-                            if k in was:
-                                v.copy_(was[k])
-                            else:
-                                v.zero_()      # (no state before the warm-up: moments and step counter start at zero)
-            torch.cuda.synchronize()
+                # parameters and optimiser state back to where they were before the warm-up steps, in place
+                with torch.no_grad():
+                    for p, was in zip(params, saved_params):
+                        p.copy_(was)
+                    for p in params:
+                        state, was = opt.state.get(p, {}), saved_state[id(p)]
+                        for k, v in state.items():
+                            if torch.is_tensor(v):
+                                if k in was:
+                                    v.copy_(was[k])
+                                else:
+                                    v.zero_()      # (no state before the warm-up: moments and step counter start at zero)
+                torch.cuda.synchronize()
 
     def __call__(self, batch):
         """One training step on `batch`; returns the loss (a 0-d tensor of the graph: read it before the next call)."""
@@ -227,10 +228,3 @@ class GraphedTrainStep(object):
         """The assertion of models.py:196-197 for the LAST batch (a host synchronisation: call it when the loss is logged)."""
         if self.valid is not None:
             assert bool(self.valid.all()), "every row of `batch` must share its head (or tail) and its relation (models.py:196-197)"
-
-    def __del__(self):
-        try:
-            for plan in self._pinned:
-                plan.pin(-1)
-        except Exception:
-            pass
