@@ -298,6 +298,22 @@ int32_t ultra_beam_search_layer(const int64_t *row_ptr, const int32_t *csr_src, 
                                 const void *edge_grad, const void *dist_in, int64_t tail, int32_t num_beam, void *dist_out,
                                 int64_t *back_edge_out, void *stream);
 
+/*
+ * ultra_beam_search_layer for num_sample independent searches over one graph: edge_grad (num_sample, num_edge), dist_in /
+ * dist_out (num_sample, num_node, num_beam) fp32, back_edge_out (num_sample, num_node, num_beam, 4) int64, all contiguous,
+ * and tails (num_sample) int64 ON THE DEVICE -- nothing is read on the host, so a chain of layers costs no
+ * synchronisation.  Sample s is exactly ultra_beam_search_layer on slice s with tails[s], bit for bit: the sample is a grid
+ * dimension of the same two kernels, so a layer is two launches whatever num_sample is.  A tail is only compared with
+ * source ids (never an index): an entry outside [0, num_node) excludes no source; callers validate it where they hold it
+ * on the host.  num_sample == 0: ULTRA_OK, nothing launched.  num_beam outside [1, ULTRA_BEAM_MAX]: ULTRA_ERR_UNSUPPORTED;
+ * num_sample outside [0, 65535], a NULL operand or an empty graph: ULTRA_ERR_INVALID.
+ */
+int32_t ultra_beam_search_layer_batch(const int64_t *row_ptr, const int32_t *csr_src, const int32_t *csr_type,
+                                      const int32_t *csr_eid, const int64_t *hub_rows, int64_t num_hub, int64_t num_node,
+                                      int64_t num_edge, int64_t num_sample, const void *edge_grad, const void *dist_in,
+                                      const int64_t *tails, int32_t num_beam, void *dist_out, int64_t *back_edge_out,
+                                      void *stream);
+
 /* ---- complex logical queries (UltraQuery) ----
  * ultra_symbolic_traversal: SymbolicTraversal.forward (ultraquery.py:280-298),
  *   t[b, v] = max(0, max{ h[b, u] : edge u -> v of type r_index[b] })   (0 where no such edge)

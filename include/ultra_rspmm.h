@@ -395,6 +395,21 @@ int32_t ultra_rspmm_backward_add(ultra_plan *plan, int32_t sum, int32_t mul, int
                                  const ultra_mat *input_grad_base, const ultra_mat *input_grad, void *stream);
 
 /*
+ * The edge-weight gradient of the sum aggregate PER OUTER SLICE (ultra_rspmm_backward sums it over them):
+ *   weight_grad[o, e] = sum_d output_grad[o, row_e, d] * BINARY(relation[o, type_e, d], input[o, col_e, d])
+ * written to weight_grad_dev, (n_outer, num_edge) fp32 with outer stride weight_grad_stride >= num_edge, in ORIGINAL edge
+ * order.  What a batch of independent samples needs when each wants its own d score / d edge weight (path explanations of
+ * several triples at once).  The outer slice is a grid dimension; within a slice the walk and the reduction are those of
+ * ultra_rspmm_backward's weight gradient, so at n_outer == 1 the two agree bit for bit.  No atomics, one writer per
+ * element, every element written (the caller need not zero it): the same bits run to run.  relation may have outer
+ * stride 0 (one table for every slice).  n_outer in [1, 65535].
+ * sum other than ULTRA_SUM_ADD, ULTRA_MUL_ROTATE and dtypes other than ULTRA_F32: ULTRA_ERR_UNSUPPORTED, nothing launched.
+ */
+int32_t ultra_rspmm_edge_grad_samples(ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const ultra_mat *relation,
+                                      const ultra_mat *input, const ultra_mat *output_grad, void *weight_grad_dev,
+                                      int64_t weight_grad_stride, void *stream);
+
+/*
  * Reference-shaped stateless entry points (one per export of rspmm.h:63-105).  Operands are the
  * reference's: SORTED edge_index (2, E) int64, edge_type (E) int64, edge_weight (E), relation (R, D),
  * input (N, D), all contiguous device arrays; output (N, D) is written.  Unsorted edge_index ->

@@ -1,6 +1,7 @@
 """Timing of the path explanations (Ultra.visualize) at FB15k237's shape on one GPU.
 
     python tools/explain_bench.py [--triples 20] [--warmup 3] [--reps 20] [--num-beam 10]
+    python tools/explain_bench.py --batch 1,4,10,16 [--reps 20] [--num-beam 10]
 
 Reports, as one JSON line:
   visualize_ms     per-triple Ultra.visualize wall time (host clock around a device synchronise, after warm-up): relation
@@ -11,6 +12,13 @@ Reports, as one JSON line:
   beam_bytes       bytes a layer must move at least: CSR (row pointers, source / type / edge id per slot), the edge gradients,
                    the gathered beams (num_edge x K fp32) and the outputs (N x K x (4 + 32) bytes); beam_gbps = those bytes of
                    six layers over beam_hip_ms; roof = beam_gbps / 8 TB/s
+--batch S[,S...]: one JSON line per S instead -- S triples explained by one Ultra.visualize_batch call against the loop of S
+Ultra.visualize calls, in one process with the two routes alternating, by device events (recorded around the whole route,
+host work and read-backs included), the median of --reps:
+  batch_ms_per_triple / loop_ms_per_triple            the whole explanation, per triple
+  beam_batch_ms_per_triple / beam_loop_ms_per_triple  the six beam-search layers alone (explain.beam_search_distance_batch against
+                                                      S calls of explain.beam_search_distance on the same gradients)
+  same_paths                                          the two routes returned the same paths and weights
 Kernel times: run the same under `rocprofv3 --kernel-trace --stats -- python tools/explain_bench.py --triples 4` on its own.
 The graph is synthetic (ultra_amd.synthetic: FB15k237's node, edge and relation counts), the weights are ultra_3g's.
 """
@@ -32,8 +40,54 @@ from ultra_amd import explain, models, synthetic  # noqa: E402
 HBM_BPS = 8e12
 
 
+def _timed(fn, ev):
+    ev[0].record()
+    out = fn()
+    ev[1].record()
+    torch.cuda.synchronize()
+    return ev[0].elapsed_time(ev[1]), out
+
+
+def batch_mode(model, data, kg, sizes, args):
+    dev = data.edge_index.device
+    k = args.num_beam
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    for size in sizes:
+        triples = kg.target_triples[:size].to(dev)
+        host = triples.cpu()
+        loop = lambda: [model.visualize(data, triples[i:i + 1]) for i in range(size)]       # noqa: E731
+        batched = lambda: model.visualize_batch(data, triples, chunk=max(size, 1))           # noqa: E731
+        with torch.no_grad():
+            rel = model.relation_model(data.relation_graph, query=triples[:, 2])
+        model.entity_model.query = rel
+        grads, _ = model.entity_model.edge_grads_batch(data, triples)
+        single_grads = [[g[i] for g in grads] for i in range(size)]
+        beam_loop = lambda: [explain.beam_search_distance(data, single_grads[i], int(host[i, 0]), int(host[i, 1]), k)   # noqa: E731
+                             for i in range(size)]
+        beam_batched = lambda: explain.beam_search_distance_batch(data, grads, host[:, 0], host[:, 1], k)               # noqa: E731
+        t = dict(loop=[], batch=[], beam_loop=[], beam_batch=[])
+        for rep in range(args.reps + 2):
+            for name, fn in (("loop", loop), ("batch", batched), ("beam_loop", beam_loop), ("beam_batch", beam_batched)):
+                ms, out = _timed(fn, ev)
+                if rep >= 2:
+                    t[name].append(ms)
+                if name == "loop":
+                    want = out
+                elif name == "batch":
+                    same = [(list(p), list(w)) for p, w in out] == [(list(p), list(w)) for p, w in want]
+        med = {name: statistics.median(v) for name, v in t.items()}
+        print(json.dumps(dict(tool="explain_bench", mode="batch", batch=size, num_node=data.num_nodes, num_edge=data.num_edges,
+                              num_beam=k, reps=args.reps,
+                              batch_ms_per_triple=round(med["batch"] / size, 3), loop_ms_per_triple=round(med["loop"] / size, 3),
+                              speedup=round(med["loop"] / med["batch"], 2),
+                              beam_batch_ms_per_triple=round(med["beam_batch"] / size, 4),
+                              beam_loop_ms_per_triple=round(med["beam_loop"] / size, 4),
+                              beam_speedup=round(med["beam_loop"] / med["beam_batch"], 2), same_paths=same)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", help="comma-separated batch sizes: time visualize_batch against the per-triple loop")
     ap.add_argument("--triples", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=20)
@@ -46,6 +100,8 @@ def main():
     model.load_state_dict(torch.load(os.path.join(ROOT, "tests", "golden", "ultra_3g_model.pt")))
     model = model.to(dev).eval()
     model.entity_model.num_beam = args.num_beam
+    if args.batch:
+        return batch_mode(model, data, kg, [int(x) for x in args.batch.split(",")], args)
     triples = kg.target_triples[: args.warmup + args.triples].to(dev)
 
     # per-triple visualize

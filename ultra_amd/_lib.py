@@ -100,6 +100,7 @@ def _load():
     lib.ultra_nbf_layer0.argtypes = [vp, vp, matp, vp, vp, vp, vp, vp, vp, ctypes.c_float, i32, matp, vp]
     lib.ultra_rspmm_backward.argtypes = [vp, i32, i32, i32, vp, matp, matp, matp, matp, vp, matp, matp, vp]
     lib.ultra_rspmm_backward_add.argtypes = [vp, i32, i32, i32, vp, matp, matp, matp, matp, vp, matp, matp, matp, vp]
+    lib.ultra_rspmm_edge_grad_samples.argtypes = [vp, i32, i32, i32, matp, matp, matp, vp, i64, vp]
     lib.ultra_rspmm_dense_relation_grad.argtypes = [vp, matp, matp, matp, vp]
     lib.ultra_rspmm_rows_forward.argtypes = [vp, i32, vp, matp, matp, vp, i64, matp, vp, vp, vp, vp]
     lib.ultra_rspmm_rows_backward.argtypes = [vp, i32, vp, matp, matp, vp, i64, vp, matp, matp, vp]
@@ -126,6 +127,7 @@ def _load():
     lib.ultra_query_segment.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, vp, vp, i64, vp, i64, vp, vp, vp, vp]
     lib.ultra_nonzero_lists.argtypes = [vp, i64, i64, vp, vp, vp, i64, vp]
     lib.ultra_beam_search_layer.argtypes =[vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, i64, i32, vp, vp, vp]
+    lib.ultra_beam_search_layer_batch.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, i32, vp, vp, vp]
     lib.ultra_symbolic_traversal.argtypes = [vp, vp, vp, i64, vp, i64, i32, vp, vp, vp]
     lib.ultra_answer_ranking.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp]
     lib.ultra_strict_negatives.argtypes = [vp, i64, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp]

@@ -14,6 +14,11 @@
 // kept entries land in distinct LDS slots) -- no atomics, one writer per destination, deterministic.  Rows of in-degree
 // above ULTRA_BEAM_HUB_DEGREE go to a second kernel: one workgroup of 16 waves per row, each wave scanning a contiguous
 // slice, then wave 0 merging the 16 partial lists in slice order (ties to the earlier slice = the earlier candidate).
+//
+// ultra_beam_search_layer_batch: S independent searches over the same CSR.  The sample is blockIdx.y of both kernels --
+// each workgroup offsets the gradients, distances and outputs to its sample's slice and reads its sample's tail from a
+// device array -- so a layer stays two launches, the per-row work (and with it every bit of the result) is the single
+// entry's, and S searches fill S times as many workgroups: the hub kernel's 97 workgroups at FB15k237 become 97 S.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -125,10 +130,24 @@ struct BeamArgs {
     float *dist_out;
     int64_t *back_out;
     const int64_t *hub_rows;
+    const int64_t *tails;      // per sample, on the device (ultra_beam_search_layer_batch); NULL: `tail` for the one sample
     int64_t num_node;
+    int64_t num_edge;
     int64_t tail;
     int32_t K;
 };
+
+// The arguments of sample s (blockIdx.y): its slice of the gradients, distances and outputs, and its own tail.  The tail is
+// only ever compared with source ids, never used as an index.
+__device__ __forceinline__ BeamArgs beam_sample(BeamArgs a, int64_t s) {
+    if (a.tails) a.tail = a.tails[s];
+    const int64_t nk = a.num_node * a.K;
+    a.grad += s * a.num_edge;
+    a.dist_in += s * nk;
+    a.dist_out += s * nk;
+    a.back_out += s * nk * 4;
+    return a;
+}
 
 // Scan slots [pb, pe) of row v into `st`.  The carry (the candidate directly before slot pb's first one) is computed from
 // the row's slots before pb.
@@ -226,8 +245,9 @@ __device__ __forceinline__ void beam_write(const BeamArgs &a, int64_t v, const B
     be[3] = pr;
 }
 
-__global__ void __launch_bounds__(64 * BEAM_ROW_WAVES) beam_row_kernel(BeamArgs a) {
+__global__ void __launch_bounds__(64 * BEAM_ROW_WAVES) beam_row_kernel(BeamArgs all) {
     __shared__ BeamLds lds[BEAM_ROW_WAVES];
+    const BeamArgs a = beam_sample(all, blockIdx.y);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t v = (int64_t)blockIdx.x * BEAM_ROW_WAVES + wave;
     if (v >= a.num_node) return;
@@ -241,7 +261,8 @@ __global__ void __launch_bounds__(64 * BEAM_ROW_WAVES) beam_row_kernel(BeamArgs 
     beam_write(a, v, st, lane);
 }
 
-__global__ void __launch_bounds__(64 * BEAM_HUB_WAVES) beam_hub_kernel(BeamArgs a) {
+__global__ void __launch_bounds__(64 * BEAM_HUB_WAVES) beam_hub_kernel(BeamArgs all) {
+    const BeamArgs a = beam_sample(all, blockIdx.y);
     __shared__ BeamLds scratch[BEAM_HUB_WAVES];
     __shared__ BeamLds part[BEAM_HUB_WAVES];
     __shared__ int part_cnt[BEAM_HUB_WAVES];
@@ -275,6 +296,45 @@ __global__ void __launch_bounds__(64 * BEAM_HUB_WAVES) beam_hub_kernel(BeamArgs 
 
 }  // namespace ultra
 
+namespace ultra {
+
+// Both entry points: `num_sample` slices (the grid's y dimension) of one layer -- two launches whatever num_sample is.
+static int32_t beam_launch(const char *who, const int64_t *row_ptr, const int32_t *csr_src, const int32_t *csr_type,
+                           const int32_t *csr_eid, const int64_t *hub_rows, int64_t num_hub, int64_t num_node, int64_t num_edge,
+                           int64_t num_sample, const void *edge_grad, const void *dist_in, const int64_t *tails, int64_t tail,
+                           int32_t num_beam, void *dist_out, int64_t *back_edge_out, void *stream) {
+    ULTRA_DEVICE_SCOPE(stream, dist_out);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    BeamArgs a;
+    a.row_ptr = row_ptr;
+    a.src = csr_src;
+    a.type = csr_type;
+    a.eid = csr_eid;
+    a.grad = (const float *)edge_grad;
+    a.dist_in = (const float *)dist_in;
+    a.dist_out = (float *)dist_out;
+    a.back_out = back_edge_out;
+    a.hub_rows = hub_rows;
+    a.tails = tails;
+    a.num_node = num_node;
+    a.num_edge = num_edge;
+    a.tail = tail;
+    a.K = num_beam;
+    (void)hipGetLastError();   // drop any stale error left by other users of the runtime
+    const unsigned grid = (unsigned)((num_node + BEAM_ROW_WAVES - 1) / BEAM_ROW_WAVES);
+    hipLaunchKernelGGL(beam_row_kernel, dim3(grid, (unsigned)num_sample), dim3(64 * BEAM_ROW_WAVES), 0, s, a);
+    if (num_hub > 0)
+        hipLaunchKernelGGL(beam_hub_kernel, dim3((unsigned)num_hub, (unsigned)num_sample), dim3(64 * BEAM_HUB_WAVES), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_error(std::string(who) + " launch: " + hipGetErrorString(e));
+        return ULTRA_ERR_HIP;
+    }
+    return ULTRA_OK;
+}
+
+}  // namespace ultra
+
 extern "C" int32_t ultra_beam_search_layer(const int64_t *row_ptr, const int32_t *csr_src, const int32_t *csr_type,
                                            const int32_t *csr_eid, const int64_t *hub_rows, int64_t num_hub,
                                            int64_t num_node, int64_t num_edge, const void *edge_grad, const void *dist_in,
@@ -290,30 +350,35 @@ extern "C" int32_t ultra_beam_search_layer(const int64_t *row_ptr, const int32_t
         ultra::set_error("ultra_beam_search_layer: NULL operand, empty graph or tail out of range");
         return ULTRA_ERR_INVALID;
     }
-    ULTRA_DEVICE_SCOPE(stream, dist_out);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    ultra::BeamArgs a;
-    a.row_ptr = row_ptr;
-    a.src = csr_src;
-    a.type = csr_type;
-    a.eid = csr_eid;
-    a.grad = (const float *)edge_grad;
-    a.dist_in = (const float *)dist_in;
-    a.dist_out = (float *)dist_out;
-    a.back_out = back_edge_out;
-    a.hub_rows = hub_rows;
-    a.num_node = num_node;
-    a.tail = tail;
-    a.K = num_beam;
-    (void)hipGetLastError();   // drop any stale error left by other users of the runtime
-    const unsigned grid = (unsigned)((num_node + ultra::BEAM_ROW_WAVES - 1) / ultra::BEAM_ROW_WAVES);
-    hipLaunchKernelGGL(ultra::beam_row_kernel, dim3(grid), dim3(64 * ultra::BEAM_ROW_WAVES), 0, s, a);
-    if (num_hub > 0)
-        hipLaunchKernelGGL(ultra::beam_hub_kernel, dim3((unsigned)num_hub), dim3(64 * ultra::BEAM_HUB_WAVES), 0, s, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        ultra::set_error(std::string("beam search launch: ") + hipGetErrorString(e));
-        return ULTRA_ERR_HIP;
+    return ultra::beam_launch("beam search", row_ptr, csr_src, csr_type, csr_eid, hub_rows, num_hub, num_node, num_edge, 1, edge_grad,
+                              dist_in, nullptr, tail, num_beam, dist_out, back_edge_out, stream);
+}
+
+extern "C" int32_t ultra_beam_search_layer_batch(const int64_t *row_ptr, const int32_t *csr_src, const int32_t *csr_type,
+                                                 const int32_t *csr_eid, const int64_t *hub_rows, int64_t num_hub,
+                                                 int64_t num_node, int64_t num_edge, int64_t num_sample, const void *edge_grad,
+                                                 const void *dist_in, const int64_t *tails, int32_t num_beam, void *dist_out,
+                                                 int64_t *back_edge_out, void *stream) {
+    if (num_beam < 1 || num_beam > ULTRA_BEAM_MAX) {
+        ultra::set_error("ultra_beam_search_layer_batch: num_beam must be in [1, 64]");
+        return ULTRA_ERR_UNSUPPORTED;
     }
-    return ULTRA_OK;
+    if (num_sample < 0 || num_sample > 65535) {
+        ultra::set_error("ultra_beam_search_layer_batch: num_sample must be in [0, 65535]");
+        return ULTRA_ERR_INVALID;
+    }
+    if (num_sample == 0) return ULTRA_OK;
+    if (!tails) {
+        ultra::set_error("ultra_beam_search_layer_batch: tails is NULL");
+        return ULTRA_ERR_INVALID;
+    }
+    if (!row_ptr || !dist_out || !back_edge_out || !dist_in || num_node <= 0 || num_edge < 0 || num_hub < 0
+        || num_node >= INT32_MAX || num_edge >= INT32_MAX || (num_hub > 0 && !hub_rows)
+        || (num_edge > 0 && (!csr_src || !csr_type || !csr_eid || !edge_grad))) {
+        ultra::set_error("ultra_beam_search_layer_batch: NULL operand (row_ptr, csr, edge_grad, dist_in, dist_out, back_edge_out) "
+                         "or empty graph");
+        return ULTRA_ERR_INVALID;
+    }
+    return ultra::beam_launch("batched beam search", row_ptr, csr_src, csr_type, csr_eid, hub_rows, num_hub, num_node, num_edge,
+                              num_sample, edge_grad, dist_in, tails, 0, num_beam, dist_out, back_edge_out, stream);
 }

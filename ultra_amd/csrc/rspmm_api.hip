@@ -1248,6 +1248,47 @@ int32_t ultra_rspmm_backward_add(ultra_plan *plan, int32_t sum, int32_t mul, int
                          relation_grad, input_grad, reinterpret_cast<hipStream_t>(stream), input_grad_base);
 }
 
+int32_t ultra_rspmm_edge_grad_samples(ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const ultra_mat *relation,
+                                      const ultra_mat *input, const ultra_mat *output_grad, void *weight_grad_dev,
+                                      int64_t weight_grad_stride, void *stream) {
+    ULTRA_DEVICE_SCOPE(stream, weight_grad_dev);
+    if (!plan) return invalid("ultra_rspmm_edge_grad_samples: plan is NULL");
+    if (sum != ULTRA_SUM_ADD || (mul != ULTRA_MUL_MUL && mul != ULTRA_MUL_ADD) || dtype != ULTRA_F32) {
+        set_error("ultra_rspmm_edge_grad_samples: served for the sum aggregate, mul / add messages and fp32 only (sum, mul, dtype)");
+        return ULTRA_ERR_UNSUPPORTED;
+    }
+    (void)hipGetLastError();
+    if (plan->flags & ULTRA_PLAN_DENSE) return invalid("ultra_rspmm_edge_grad_samples: a ULTRA_PLAN_DENSE plan has no edge list; use the (row, col) plan");
+    if (!output_grad || !output_grad->ptr) return invalid("ultra_rspmm_edge_grad_samples: output_grad is NULL");
+    const int64_t n_outer = output_grad->n_outer, row_len = output_grad->row_len;
+    if (n_outer <= 0 || n_outer > 65535 || row_len <= 0 || row_len >= INT32_MAX)
+        return invalid("ultra_rspmm_edge_grad_samples: output_grad: n_outer must be in [1, 65535] and row_len positive");
+    int rc;
+    if ((rc = check_mat(relation, "relation", plan->num_rel, n_outer, row_len))) return rc;
+    if ((rc = check_mat(input, "input", plan->num_in, n_outer, row_len))) return rc;
+    if ((rc = check_mat(output_grad, "output_grad", plan->num_out, n_outer, row_len))) return rc;
+    if (plan->num_edge > 0 && !weight_grad_dev) return invalid("ultra_rspmm_edge_grad_samples: weight_grad is NULL");
+    if (weight_grad_stride < plan->num_edge) return invalid("ultra_rspmm_edge_grad_samples: weight_grad_stride < num_edge");
+    if (plan->num_edge <= 0) return ULTRA_OK;
+    if ((rc = upload_plan(plan))) return rc;
+    const bool vec4 = (row_len % 4 == 0) && mat_vec_ok(relation, 4) && mat_vec_ok(input, 4) && mat_vec_ok(output_grad, 4);
+    EdgeSamplesParams ep;
+    std::memset(&ep, 0, sizeof(ep));
+    ep.erow = plan->d.erow;
+    ep.col = plan->d.col;
+    ep.type = plan->d.type;
+    ep.perm = plan->d.perm;
+    ep.num_edge = plan->num_edge;
+    ep.rel = MatArg{relation->ptr, relation->stride_outer, relation->stride_row};
+    ep.x = MatArg{input->ptr, input->stride_outer, input->stride_row};
+    ep.og = MatArg{output_grad->ptr, output_grad->stride_outer, output_grad->stride_row};
+    ep.wgrad = weight_grad_dev;
+    ep.wgrad_so = weight_grad_stride;
+    ep.row_len = (int32_t)row_len;
+    return launch_edge_grad_samples(vec4 ? 4 : 1, mul == ULTRA_MUL_MUL ? BIN_MUL : BIN_ADD, (int)n_outer, ep,
+                                    reinterpret_cast<hipStream_t>(stream));
+}
+
 int32_t ultra_rspmm_dense_relation_grad(ultra_plan *plan, const ultra_mat *input, const ultra_mat *output_grad,
                                         const ultra_mat *relation_grad, void *stream) {
     ULTRA_DEVICE_SCOPE(stream, output_grad ? output_grad->ptr : nullptr);

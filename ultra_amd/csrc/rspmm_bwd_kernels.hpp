@@ -343,6 +343,75 @@ inline int launch_edge_kernel(int dtype, int vec, int sum, int mul, bool want_ri
     return ULTRA_OK;
 }
 
+// ---- per-sample weight gradient (ultra_rspmm_edge_grad_samples): sum aggregate, one (n_outer, num_edge) result ----
+// rspmm_edge_bwd_kernel's walk with the outer slice in the grid (blockIdx.y, like rspmm_onehot_kernel) instead of a serial
+// loop whose terms it sums: per lane ascending spans and elements, the xor-8/4/2/1 shuffles, then one store per (outer,
+// edge) in ORIGINAL edge order -- no atomics, one writer per element, every element written.  At n_outer == 1 the
+// arithmetic is that kernel's term for term, hence its weight_grad bit for bit.
+struct EdgeSamplesParams {
+    const int32_t *erow;
+    const int32_t *col;
+    const int32_t *type;
+    const int32_t *perm;
+    int64_t num_edge;
+    MatArg rel, x, og;
+    void *wgrad;            // (n_outer, num_edge), original edge order
+    long long wgrad_so;
+    int32_t row_len;
+};
+
+template <typename T, int VEC, int MUL>
+__global__ void __launch_bounds__(256) rspmm_edge_grad_samples_kernel(const EdgeSamplesParams p) {
+    constexpr int SPAN = 16 * VEC;
+    using P = Pack<T, VEC>;
+    const int outer = blockIdx.y;
+    const int l16 = threadIdx.x & 15;
+    const long long g0 = (blockIdx.x * (long long)blockDim.x + threadIdx.x) >> 4;
+    const long long ng = ((long long)gridDim.x * blockDim.x) >> 4;
+    const int spans = (p.row_len + SPAN - 1) / SPAN;
+    const T *relb = reinterpret_cast<const T *>(p.rel.ptr) + outer * p.rel.stride_outer;
+    const T *xb0 = reinterpret_cast<const T *>(p.x.ptr) + outer * p.x.stride_outer;
+    const T *ogb = reinterpret_cast<const T *>(p.og.ptr) + outer * p.og.stride_outer;
+    T *wgb = reinterpret_cast<T *>(p.wgrad) + outer * p.wgrad_so;
+    for (long long k = g0; k < p.num_edge; k += ng) {
+        const int row = p.erow[k], col = p.col[k], type = p.type[k];
+        const int eid = p.perm[k];
+        T wg = T(0);
+        for (int inner = 0; inner < spans; ++inner) {
+            const int d0 = inner * SPAN + l16 * VEC;
+            if (d0 >= p.row_len) continue;
+            const P r = *reinterpret_cast<const P *>(relb + (long long)type * p.rel.stride_row + d0);
+            const P xi = *reinterpret_cast<const P *>(xb0 + (long long)col * p.x.stride_row + d0);
+            const P g = *reinterpret_cast<const P *>(ogb + (long long)row * p.og.stride_row + d0);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const T xb = binary<T, MUL>(r.v[e], xi.v[e]);
+                wg += g.v[e] * xb;
+            }
+        }
+        wg += __shfl_xor(wg, 8);
+        wg += __shfl_xor(wg, 4);
+        wg += __shfl_xor(wg, 2);
+        wg += __shfl_xor(wg, 1);
+        if (l16 == 0) wgb[eid] = wg;
+    }
+}
+
+inline int launch_edge_grad_samples(int vec, int mul, int n_outer, const EdgeSamplesParams &p, hipStream_t s) {
+    const int blocks = (int)std::min<long long>((p.num_edge * 16 + 255) / 256, 16384);
+    const dim3 grid(blocks, n_outer), block(256);
+    if (vec == 4 && mul == BIN_MUL) hipLaunchKernelGGL((rspmm_edge_grad_samples_kernel<float, 4, BIN_MUL>), grid, block, 0, s, p);
+    else if (vec == 4) hipLaunchKernelGGL((rspmm_edge_grad_samples_kernel<float, 4, BIN_ADD>), grid, block, 0, s, p);
+    else if (mul == BIN_MUL) hipLaunchKernelGGL((rspmm_edge_grad_samples_kernel<float, 1, BIN_MUL>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((rspmm_edge_grad_samples_kernel<float, 1, BIN_ADD>), grid, block, 0, s, p);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_error(std::string("rspmm_edge_grad_samples_kernel launch: ") + hipGetErrorString(e));
+        return ULTRA_ERR_HIP;
+    }
+    return ULTRA_OK;
+}
+
 // ---- RotatE (ULTRA_MUL_ROTATE): a row is one complex vector, real half | imaginary half ----
 // Edge kernel: lane l of the 16-lane group that owns a sorted edge takes the complex elements c = l, l + 16, ... < row_len / 2
 // (both halves of each), so any even row length and any alignment is served.  weight_grad[e] = sum_d og[row, d] * [tie] *

@@ -4,7 +4,8 @@ visualize takes the gradient of one triple's score with respect to every layer's
 highest-weight paths from head to tail through those gradients and returns the top paths with their average edge weight.
 Here every layer of the beam search is one call of ultra_beam_search_layer (csrc/beam_search.hip) over a
 destination-major CSR of the graph that is built once per graph and cached, and the backtracking of topk_average_length
-runs as device gathers with one copy to the host at the end.
+runs as device gathers with one copy to the host at the end.  The *_batch functions do the same for S triples at once:
+the sample is a grid dimension of the beam kernels (ultra_beam_search_layer_batch), so S searches cost the launches of one.
 
 Semantics: the reference's with stable sorts and exact top-k keys.  The reference itself is
 order-dependent -- its ties follow whatever its unstable sorts produce, and its scatter_topk merges values closer than
@@ -132,6 +133,142 @@ def topk_average_length(distances, back_edges, t_index, k=10):
     if paths:
         average_lengths, paths = zip(*sorted(zip(average_lengths, paths), reverse=True)[:k])
     return paths, average_lengths
+
+
+# ---- a batch of S independent searches over one graph: the sample is a grid dimension of the same two kernels ----
+def _index_vector(index, name, num_sample=None):
+    """(S,) int64 of `index` (a tensor of S entries, a sequence or one int) plus its smallest and largest entry as Python
+    ints: read from the host copy where there is one, else with one device read."""
+    if not torch.is_tensor(index):
+        index = torch.as_tensor(index, dtype=torch.int64)
+    index = index.reshape(-1).to(torch.int64)
+    if num_sample is not None and index.numel() != num_sample:
+        raise ValueError("%s: expected %d entries, got %d" % (name, num_sample, index.numel()))
+    if index.numel() == 0:
+        return index, 0, -1
+    lo, hi = torch.aminmax(index)
+    return index, int(lo), int(hi)
+
+
+def _check_index_range(index, name, num_node, num_sample=None):
+    index, lo, hi = _index_vector(index, name, num_sample)
+    if lo < 0 or hi >= num_node:
+        raise ValueError("%s holds node ids outside [0, %d)" % (name, num_node))
+    return index
+
+
+def beam_search_layer_batch(csr, edge_grad, dist_in, tails, num_beam, tails_checked=False):
+    """One layer of S searches (ultra_beam_search_layer_batch): edge_grad (S, num_edge), dist_in (S, num_node, num_beam),
+    tails (S) -> (S, num_node, num_beam) fp32 distances and (S, num_node, num_beam, 4) int64 back edges; sample s is
+    beam_search_layer on slice s with tails[s], bit for bit.  Two launches whatever S is; `tails` is used on the device.
+    tails_checked: the caller has already checked the tails against [0, num_node) (beam_search_distance_batch does it once
+    for all layers: on device tensors the check is a read-back)."""
+    if not isinstance(num_beam, int) or not 1 <= num_beam <= _lib.BEAM_MAX:
+        raise ValueError("num_beam must be an int in [1, %d], got %r" % (_lib.BEAM_MAX, num_beam))
+    if edge_grad.dtype != torch.float32 or dist_in.dtype != torch.float32:
+        raise TypeError("the beam search takes fp32 edge gradients and distances, got %s / %s" % (edge_grad.dtype, dist_in.dtype))
+    if edge_grad.dim() != 2 or edge_grad.shape[1] != csr.num_edge:
+        raise ValueError("Expected edge gradients of shape (S, %d), got %s" % (csr.num_edge, tuple(edge_grad.shape)))
+    num_sample = edge_grad.shape[0]
+    if tuple(dist_in.shape) != (num_sample, csr.num_node, num_beam):
+        raise ValueError("Expected distances of shape (%d, %d, %d), got %s"
+                         % (num_sample, csr.num_node, num_beam, tuple(dist_in.shape)))
+    if num_sample > 65535:
+        raise ValueError("at most 65535 samples a call, got %d" % num_sample)
+    if not (edge_grad.is_cuda and dist_in.is_cuda and edge_grad.device == csr.row_ptr.device == dist_in.device):
+        raise RuntimeError("edge gradients, distances and graph must be on one CUDA device")
+    if not tails_checked:
+        tails = _check_index_range(tails, "tails", csr.num_node, num_sample)
+    elif tuple(tails.shape) != (num_sample,) or tails.dtype != torch.int64:
+        raise ValueError("Expected `tails` of shape (%d,) int64, got %s %s" % (num_sample, tuple(tails.shape), tails.dtype))
+    tails = tails.to(dist_in.device).contiguous()
+    edge_grad, dist_in = edge_grad.contiguous(), dist_in.contiguous()
+    dist = torch.empty((num_sample, csr.num_node, num_beam), dtype=torch.float32, device=dist_in.device)
+    back = torch.empty((num_sample, csr.num_node, num_beam, 4), dtype=torch.int64, device=dist_in.device)
+    if num_sample == 0:
+        return dist, back
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dist_in.device).cuda_stream)
+    check(lib.ultra_beam_search_layer_batch(csr.row_ptr.data_ptr(), csr.src.data_ptr(), csr.type.data_ptr(), csr.eid.data_ptr(),
+                                            csr.hub_rows.data_ptr() if csr.num_hub else None, csr.num_hub, csr.num_node,
+                                            csr.num_edge, num_sample, edge_grad.data_ptr(), dist_in.data_ptr(),
+                                            tails.data_ptr(), num_beam, dist.data_ptr(), back.data_ptr(), stream))
+    return dist, back
+
+
+def beam_search_distance_batch(data, edge_grads, h_index, t_index, num_beam=10):
+    """beam_search_distance for S triples at once: edge_grads is a list of (S, num_edge) tensors, one per layer, h_index and
+    t_index hold S node ids.  Returns per layer (S, num_node, num_beam) distances and (S, num_node, num_beam, 4) back
+    edges; slice s is beam_search_distance of triple s, the all -inf rule applied per sample on the device."""
+    csr = beam_csr(data.edge_index, data.edge_type, data.num_nodes)
+    dev = data.edge_index.device
+    num_sample = edge_grads[0].shape[0] if len(edge_grads) else _index_vector(h_index, "h_index")[0].numel()
+    h = _check_index_range(h_index, "h_index", csr.num_node, num_sample).to(dev)
+    t = _check_index_range(t_index, "t_index", csr.num_node, num_sample).to(dev)
+    if not isinstance(num_beam, int) or not 1 <= num_beam <= _lib.BEAM_MAX:
+        raise ValueError("num_beam must be an int in [1, %d], got %r" % (_lib.BEAM_MAX, num_beam))
+    dist = torch.full((num_sample, csr.num_node, num_beam), float("-inf"), device=dev)
+    dist[torch.arange(num_sample, device=dev), h, 0] = 0
+    distances, back_edges = [], []
+    with torch.no_grad():
+        for edge_grad in edge_grads:
+            dist, back = beam_search_layer_batch(csr, edge_grad, dist, t, num_beam, tails_checked=True)
+            # (beam_search_distance's all -inf rule, per sample and without leaving the device)
+            back.mul_(torch.isfinite(dist).flatten(1).any(dim=1).view(-1, 1, 1, 1))
+            distances.append(dist)
+            back_edges.append(back)
+    return distances, back_edges
+
+
+def topk_average_length_batch(distances, back_edges, t_index, k=10):
+    """topk_average_length for S samples: distances[i] (S, num_node, K), back_edges[i] (S, num_node, K, 4), t_index S node
+    ids.  The backtracking is device gathers over all samples at once and ONE copy to the host per call; returns a list of
+    (paths, average_lengths), entry s equal to topk_average_length on sample s's slices."""
+    if not distances:
+        return [([], []) for _ in range(_index_vector(t_index, "t_index")[0].numel())]
+    num_sample, num_node = distances[0].shape[0], distances[0].shape[1]
+    dev = distances[0].device
+    t = _check_index_range(t_index, "t_index", num_node, num_sample).to(dev)
+    if num_sample == 0:
+        return []
+    sample = torch.arange(num_sample, device=dev)
+    flat_d, flat_s, shapes = [], [], []
+    for i in range(len(distances)):
+        distance, order = distances[i][sample, t].sort(dim=1, descending=True, stable=True)       # (S, K)
+        distance, order = distance[:, :k], order[:, :k]
+        n = order.shape[1]
+        rows = sample.unsqueeze(1).expand(-1, n)
+        steps = [back_edges[i][rows, t.unsqueeze(1).expand(-1, n), order]]      # (S, n, 4) edges into t
+        for j in range(i - 1, -1, -1):
+            prev = steps[-1]
+            steps.append(back_edges[j][rows, prev[..., 0], prev[..., 3]])
+        steps = torch.stack(steps, dim=1)                                      # (S, i + 1, n, 4), last edge first
+        shapes.append((i + 1, n))
+        flat_d.append(distance.to(torch.float64).reshape(num_sample, -1))
+        flat_s.append(steps.reshape(num_sample, -1))
+    # one copy: the distances ride as fp64 bit patterns beside the int64 steps (fp32 -> fp64 is exact)
+    host = torch.cat([torch.cat(flat_d, dim=1).view(torch.int64), torch.cat(flat_s, dim=1)], dim=1).cpu()
+    n_dist = sum(n for _, n in shapes)
+    host_d = host[:, :n_dist].contiguous().view(torch.float64)
+    host_s = host[:, n_dist:]
+    results = []
+    for s in range(num_sample):
+        paths, average_lengths = [], []
+        d_off = s_off = 0
+        for i, (depth, n) in enumerate(shapes):
+            dist = host_d[s, d_off:d_off + n].tolist()
+            steps = host_s[s, s_off:s_off + depth * n * 4].view(depth, n, 4)
+            d_off += n
+            s_off += depth * n * 4
+            for m, d in enumerate(dist):
+                if d == float("-inf"):
+                    break
+                path = [tuple(int(x) for x in steps[j, m, :3]) for j in range(i, -1, -1)]
+                paths.append(path)
+                average_lengths.append(d / len(path))
+        if paths:
+            average_lengths, paths = zip(*sorted(zip(average_lengths, paths), reverse=True)[:k])
+        results.append((paths, average_lengths))
+    return results
 
 
 def _scalar_index(index, name):

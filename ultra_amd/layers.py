@@ -262,6 +262,27 @@ class GeneralizedRelationalConv(nn.Module):
         update = rspmm.plan_rspmm(plan, relation[0], input[0], edge_weight, sum="add", mul="mul", boundary=boundary[0])
         return self.update(update.unsqueeze(0), input, residual=residual)
 
+    def edge_grad_layer_batch(self, input, query, boundary, edge_index, edge_type, num_node, residual=False, relation=None):
+        """edge_grad_layer for S independent samples at once -- (S, N, d) operands, the same flipped-graph plan, CONSTANT unit
+        edge weights: a batched backward would sum the weight gradient over the samples, which explains none of them.  The
+        aggregate `update` is kept instead; with its gradient u the per-sample weight gradient of this layer is
+        plan.edge_grad_samples(relation, input, u) (ultra_rspmm_edge_grad_samples).  Returns (hidden, (plan, relation, input,
+        update)); None where edge_grad_layer would return None for a sample (the caller then explains triple by triple)."""
+        if not (self.aggregate_func == "sum" and self.message_func == "distmult" and input.is_cuda
+                and input.dtype == torch.float32 and input.dim() == 3):
+            return None
+        if relation is None:
+            relation = self._relation_for(query, len(query))
+        if relation.dtype != torch.float32 or relation.dim() != 3 or relation.shape[0] != input.shape[0]:
+            return None
+        if isinstance(boundary, PointBoundary):
+            boundary = boundary.dense()
+        plan = rspmm.get_plan(_flipped_edges(edge_index), edge_type, num_node, relation.shape[1], exact_order=False)
+        update = rspmm.plan_rspmm(plan, relation, input, None, sum="add", mul="mul", boundary=boundary)
+        if not update.requires_grad:      # (frozen parameters: nothing upstream asks for a gradient, this tensor still does)
+            update.requires_grad_()
+        return self.update(update, input, residual=residual), (plan, relation, input, update)
+
     def point_boundary_trains(self):
         """The differentiable rspmm takes the boundary condition in closed form for the sum aggregate (rspmm._PlanRSPMM,
         rspmm._OnehotRSPMM): no (batch, N, d) boundary gradient is formed, layer 0 walks the sources' edges only."""

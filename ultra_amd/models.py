@@ -152,13 +152,16 @@ class BaseNBFNet(nn.Module):
 
     def _propagate_layers(self, data, layer_input, query, boundary, separate_grad=False, relations=None,
                           edge_weight=None, onehot_rows=None, edge_keep=False, prefilled=None, last_rows=None,
-                          edge_grad_route=False):
+                          edge_grad_route=False, edge_grad_batch=None):
         """The Bellman-Ford loop shared by every model (models.py:72-80, 150-163, 233-246).
         `relations`: optional per-layer relation features computed up front (EntityNBFNet batches the six
         relation_projection MLPs, which all read the same relation representations).
         `boundary` may be a layers.PointBoundary (then `layer_input` is ignored: layer 0 reads the boundary condition).
         `edge_grad_route` (with separate_grad; visualize only): the layers that can take their edge-weight gradient from the
-        plan-based differentiable rspmm do (layers.edge_grad_layer), the others keep the unfused route."""
+        plan-based differentiable rspmm do (layers.edge_grad_layer), the others keep the unfused route.
+        `edge_grad_batch` (with separate_grad; edge_grads_batch only): a list that receives every layer's (plan, relation, input,
+        update) from layers.edge_grad_layer_batch -- constant weights, S samples; _BatchRouteUnsupported where a layer has no
+        such route."""
         size = (data.num_nodes, data.num_nodes)
         self._last_hidden_on_rows = False
         # edge_weight None = all ones (only materialised when its gradient is asked for); a 0/1 vector = edge dropout
@@ -188,6 +191,17 @@ class BaseNBFNet(nn.Module):
                     boundary = layer_input
         for i, layer in enumerate(self.layers):
             if i < first:
+                continue
+            if edge_grad_batch is not None:
+                residual = self.short_cut and layer.output_dim == layer_input.shape[-1]
+                out = layer.edge_grad_layer_batch(layer_input, query, boundary, data.edge_index, data.edge_type, data.num_nodes,
+                                                  residual=residual, relation=None if relations is None else relations[i])
+                if out is None:
+                    raise _BatchRouteUnsupported()
+                hiddens.append(out[0])
+                edge_weights.append(None)
+                edge_grad_batch.append(out[1])
+                layer_input = out[0]
                 continue
             if separate_grad and edge_grad_route:
                 # models.py:150-152: every layer's weights are a clone of the previous layer's, so d score / d weight of layer
@@ -227,6 +241,10 @@ class BaseNBFNet(nn.Module):
             edge_weights.append(edge_weight)
             layer_input = hidden
         return hiddens, edge_weights
+
+
+class _BatchRouteUnsupported(Exception):
+    """A layer or the engine does not serve the batched explanation route: edge_grads_batch falls back to one triple a call."""
 
 
 class RelNBFNet(BaseNBFNet):
@@ -337,7 +355,7 @@ class EntityNBFNet(BaseNBFNet):
         return out, side
 
     def _bellmanford_hidden(self, data, h_index, r_index, separate_grad=False, edge_weight=None, edge_keep=False, prefilled=None,
-                            last_rows=None, edge_grad_route=False):
+                            last_rows=None, edge_grad_route=False, edge_grad_batch=None):
         batch_size = len(r_index)
         # query = representation of each sample's query relation, scattered to its head node
         fused = (dense.boundary_supported(h_index, self.query) and self.query.dim() == 3
@@ -364,7 +382,8 @@ class EntityNBFNet(BaseNBFNet):
         hiddens, edge_weights = self._propagate_layers(data, boundary, query, boundary, separate_grad,
                                                        relations=self._project_relations_batched(),
                                                        edge_weight=edge_weight, onehot_rows=h_index, edge_keep=edge_keep,
-                                                       prefilled=prefilled, last_rows=last_rows, edge_grad_route=edge_grad_route)
+                                                       prefilled=prefilled, last_rows=last_rows, edge_grad_route=edge_grad_route,
+                                                       edge_grad_batch=edge_grad_batch)
         return hiddens, edge_weights, query
 
     def _project_relations_batched(self):
@@ -454,6 +473,102 @@ class EntityNBFNet(BaseNBFNet):
         edge_grads, _ = self.edge_grads(data, batch)
         distances, back_edges = self.beam_search_distance(data, edge_grads, h_index, t_index, self.num_beam)
         return self.topk_average_length(distances, back_edges, t_index, self.path_topk)
+
+    # ---- explanations of S triples at once (they may differ in h, r and t) ----
+    def _installed_slice(self, lo, hi):
+        """Install rows lo:hi of the installed (S, R, d) relation representations as the model's (what a forward() on those
+        triples alone would have installed); returns what to hand to _restore_installed."""
+        saved = (getattr(self, "query", None), [getattr(l, "relation", None) for l in self.layers])
+        full = saved[0]
+        self.query = full[lo:hi]
+        for layer, rel in zip(self.layers, saved[1]):
+            if torch.is_tensor(rel) and rel.dim() == 3 and rel.shape[0] == full.shape[0]:
+                layer.relation = rel[lo:hi]
+        return saved
+
+    def _restore_installed(self, saved):
+        self.query = saved[0]
+        for layer, rel in zip(self.layers, saved[1]):
+            layer.relation = rel
+
+    def _edge_grads_per_triple(self, data, batch):
+        """edge_grads_batch through edge_grads, one triple at a time (the route of every layer kind)."""
+        grads, scores = [], []
+        for s in range(batch.shape[0]):
+            saved = self._installed_slice(s, s + 1)
+            try:
+                g, score = self.edge_grads(data, batch[s:s + 1])
+            finally:
+                self._restore_installed(saved)
+            grads.append(g)
+            scores.append(score)
+        return [torch.stack([g[i] for g in grads]) for i in range(len(self.layers))], torch.cat(scores)
+
+    def edge_grads_batch(self, data, batch):
+        """edge_grads for S triples, batch (S, 3), with the (S, R, d) relation representations of their query relations
+        installed (self.query, row s for triple s): ONE forward and one backward for all of them.  The samples are independent,
+        so row s of the gradient of scores.sum() with respect to a layer's aggregate is triple s's; each layer's direct
+        edge-weight gradient then comes per sample from ultra_rspmm_edge_grad_samples, and the reference's clone chain
+        (models.py:150-152: layer i's weights are a clone of layer i - 1's) makes layer i's gradient the sum of the direct ones
+        of layers i .. L-1.  Returns ([(S, num_edge)] * L, scores (S)).  Models whose layers are not sum / DistMult / fp32 on
+        the GPU are explained triple by triple through edge_grads: the same values either way."""
+        if batch.dim() != 2 or batch.shape[1] != 3:
+            raise ValueError("Expected a batch of triples of shape (S, 3), got %s" % (tuple(batch.shape),))
+        query = getattr(self, "query", None)
+        if not torch.is_tensor(query) or query.dim() != 3 or query.shape[0] != batch.shape[0]:
+            raise ValueError("edge_grads_batch: install the (S, num_relation, d) relation representations of the batch's query "
+                             "relations first (self.query), S = %d" % batch.shape[0])
+        num_sample = batch.shape[0]
+        dev = data.edge_index.device
+        if num_sample == 0:
+            return ([torch.zeros((0, data.num_edges), device=dev) for _ in self.layers], torch.zeros(0, device=dev))
+        if not (batch.is_cuda and query.is_cuda and query.dtype == torch.float32):
+            return self._edge_grads_per_triple(data, batch)
+        h_index, t_index, r_index = batch.unbind(-1)
+        last_hidden_on_rows = getattr(self, "_last_hidden_on_rows", False)
+        try:
+            with torch.enable_grad():
+                records = []
+                hiddens, _, query = self._bellmanford_hidden(data, h_index, r_index, separate_grad=True, edge_grad_batch=records)
+                sample = torch.arange(num_sample, device=batch.device)
+                picked = [h[sample, t_index] for h in (hiddens if self.concat_hidden else hiddens[-1:])]     # (S, d) each
+                scores = self.mlp(torch.cat(picked + [query], dim=-1)).squeeze(-1)
+                update_grads = autograd.grad(scores.sum(), [rec[3] for rec in records])
+            edge_grads = [None] * len(records)
+            with torch.no_grad():
+                for i in range(len(records) - 1, -1, -1):
+                    plan, relation, layer_input, _ = records[i]
+                    direct = plan.edge_grad_samples(relation.detach(), layer_input.detach(), update_grads[i].contiguous())
+                    if direct is None:
+                        raise _BatchRouteUnsupported()
+                    edge_grads[i] = direct if i == len(records) - 1 else direct + edge_grads[i + 1]
+        except _BatchRouteUnsupported:
+            return self._edge_grads_per_triple(data, batch)
+        finally:
+            self._last_hidden_on_rows = last_hidden_on_rows
+        return edge_grads, scores.detach()
+
+    def visualize_batch(self, data, batch, chunk=16):
+        """visualize for S triples, batch (S, 3), with their (S, R, d) relation representations installed: a list of (paths,
+        weights), entry s what visualize returns for triple s.  `chunk` triples share one forward, one backward and the
+        launches of one beam search (explain.beam_search_distance_batch); it bounds the memory of the 2 L (chunk, ...) tables."""
+        if batch.dim() != 2 or batch.shape[1] != 3:
+            raise ValueError("Expected a batch of triples of shape (S, 3), got %s" % (tuple(batch.shape),))
+        if not isinstance(chunk, int) or chunk < 1:
+            raise ValueError("chunk must be a positive int, got %r" % (chunk,))
+        host = batch.cpu()      # (one read for the whole batch: the heads and tails are checked against the graph on the host)
+        results = []
+        for lo in range(0, batch.shape[0], chunk):
+            hi = min(lo + chunk, batch.shape[0])
+            saved = self._installed_slice(lo, hi)
+            try:
+                edge_grads, _ = self.edge_grads_batch(data, batch[lo:hi])
+            finally:
+                self._restore_installed(saved)
+            distances, back_edges = explain.beam_search_distance_batch(data, edge_grads, host[lo:hi, 0], host[lo:hi, 1],
+                                                                       self.num_beam)
+            results.extend(explain.topk_average_length_batch(distances, back_edges, host[lo:hi, 1], self.path_topk))
+        return results
 
     def prologue_supported(self, batch):
         """The inference fast path of forward(): one prologue kernel instead of the index arithmetic of models.py:190-197."""
@@ -675,6 +790,38 @@ class Ultra(nn.Module):
             ent.query = saved[0]
             for layer, r in zip(ent.layers, saved[1]):
                 layer.relation = r
+
+    def visualize_batch(self, data, batch, chunk=16):
+        """visualize for S triples at once, batch (S, 3) -- they may differ in h, r and t: a list of (paths, weights), entry s
+        what visualize(data, batch[s:s + 1]) returns.  Every chunk of `chunk` triples takes its query relations'
+        representations from the relation model (or the relation cache, as visualize does), one entity-model forward and
+        backward and the launches of one beam search (EntityNBFNet.visualize_batch).  The model is left as it was, like
+        visualize."""
+        if batch.dim() != 2 or batch.shape[1] != 3:
+            raise ValueError("Expected a batch of triples of shape (S, 3), got %s" % (tuple(batch.shape),))
+        if not isinstance(chunk, int) or chunk < 1:
+            raise ValueError("chunk must be a positive int, got %r" % (chunk,))
+        ent = self.entity_model
+        if not hasattr(ent, "visualize_batch"):
+            raise TypeError("%s cannot explain a batch; EntityNBFNet can" % type(ent).__name__)
+        saved = (getattr(ent, "query", None), [getattr(l, "relation", None) for l in ent.layers])
+        results = []
+        try:
+            for lo in range(0, batch.shape[0], chunk):
+                part = batch[lo:lo + chunk]
+                with torch.no_grad():
+                    rel = self._cached_relations(data, part[:, 2])
+                    if rel is None:
+                        rel = self.relation_model(data.relation_graph, query=part[:, 2])
+                ent.query = rel
+                for layer in ent.layers:
+                    layer.relation = rel
+                results.extend(ent.visualize_batch(data, part, chunk=chunk))
+        finally:
+            ent.query = saved[0]
+            for layer, r in zip(ent.layers, saved[1]):
+                layer.relation = r
+        return results
 
     def forward(self, data, batch):
         # batch: (bs, 1 + num_negs, 3); the relation is shared by every triple of a row

@@ -160,6 +160,7 @@ class Predictor(object):
         predictor = Predictor(model, data, k=10)
         ids, scores, count = predictor.tails(h, r)       # (n, k), (n, k), (n): the best tails of every (h[i], r[i], ?)
         ids, scores, count = predictor.heads(t, r)       # ... the best heads of every (?, r[i], t[i])
+        ids, scores, count, why = predictor.explain_tails(h, r)    # ... and the top paths behind every answer (explain_heads alike)
 
     Known answers are left out (filtered=True): the tails of (h, r, .) / heads of (., r, t) in the filter graph --
     `filtered_data`, else data.filtered_data when present, else `data` (the rule of eval.evaluate).  On the GPU with use_graph
@@ -183,6 +184,40 @@ class Predictor(object):
 
     def heads(self, t, r):
         return self._run(t, r, "head")
+
+    def explain_tails(self, h, r, chunk=16):
+        """tails(h, r) plus why: (ids, scores, count, explanations).  explanations[i][j], j < count[i], is the (paths, weights)
+        of model.visualize_batch for the triple (h[i], ids[i, j], r[i]) -- answer j of query i -- so every path runs from
+        h[i] to the answer.  The answers come from the same captured step as tails; the explanations run `chunk` triples a
+        forward / backward / beam search."""
+        return self._explain(h, r, "tail", chunk)
+
+    def explain_heads(self, t, r, chunk=16):
+        """heads(t, r) plus why.  The model scores (?, r, t) as the TAIL query (t, r + num_direct_rel, ?) -- the inverse
+        relation, as in evaluation -- so the triple explained for answer a is (t[i], a, r[i] + num_direct_rel), the one whose
+        score was served: every path runs from t[i] to the answer over the graph's edges, inverse ones included."""
+        return self._explain(t, r, "head", chunk)
+
+    def _explain(self, anchor, relation, mode, chunk):
+        if not hasattr(self.model, "visualize_batch"):
+            raise TypeError("%s cannot explain its answers: models.Ultra and models.EntityNBFNet (visualize_batch) can"
+                            % type(self.model).__name__)
+        ids, scores, count = self._run(anchor, relation, mode)
+        dev = ids.device
+        anchor = torch.as_tensor(anchor, dtype=torch.long, device=dev).flatten()
+        relation = torch.as_tensor(relation, dtype=torch.long, device=dev).flatten()
+        if mode == "head":
+            relation = relation + self.data.num_relations // 2
+        counts = count.tolist()
+        rows = torch.tensor([i for i, c in enumerate(counts) for _ in range(c)], dtype=torch.long, device=dev)
+        cols = torch.tensor([j for c in counts for j in range(c)], dtype=torch.long, device=dev)
+        triples = torch.stack([anchor[rows], ids[rows, cols], relation[rows]], dim=-1)
+        flat = self.model.visualize_batch(self.data, triples, chunk=chunk) if len(rows) else []
+        explanations, at = [], 0
+        for c in counts:
+            explanations.append(flat[at:at + c])
+            at += c
+        return ids, scores, count, explanations
 
     def close(self):
         """Drop the captured steps (their plans are unpinned)."""

@@ -531,6 +531,44 @@ class Plan(object):
             wgrad = wgrad * (edge_weight != 0).to(wgrad.dtype)
         return wgrad, rgrad, xgrad
 
+    def edge_grad_samples(self, relation, input, output_grad, sum="add", mul="mul"):
+        """The edge-weight gradient of every outer slice on its own (ultra_rspmm_edge_grad_samples) -- backward() sums it over
+        them: (n_outer, num_edge) fp32 in original edge order for (n_outer, rows, d) operands (2-D: one slice); relation may be
+        2-D or an expanded view, one table for every slice.  Deterministic, and at one slice backward()'s weight gradient bit
+        for bit.  None where the engine does not serve the call (min / max, rotate, other dtypes): the caller falls back."""
+        _require_gpu(relation, input, output_grad)
+        if (sum != "add" or mul not in ("mul", "add") or input.dtype != torch.float32 or relation.dtype != torch.float32
+                or output_grad.dtype != torch.float32):
+            return None
+        if input.dim() not in (2, 3) or output_grad.dim() != input.dim():
+            raise ValueError("Expected `input` and `output_grad` of the same 2 or 3 dimensions, got %d and %d"
+                             % (input.dim(), output_grad.dim()))
+        if input.dim() == 2:
+            input, output_grad = input.unsqueeze(0), output_grad.unsqueeze(0)
+        n_outer, d = input.shape[0], input.shape[2]
+        if relation.dim() == 2:
+            relation = relation.unsqueeze(0).expand(n_outer, -1, -1)
+        if (relation.dim() != 3 or relation.shape[0] != n_outer or relation.shape[2] != d or relation.shape[1] < self.num_relation
+                or input.shape[1] < self.num_in or tuple(output_grad.shape) != (n_outer, output_grad.shape[1], d)
+                or output_grad.shape[1] < self.num_node):
+            raise ValueError("edge_grad_samples: expected relation (n_outer, >= %d, d), input (n_outer, >= %d, d) and output_grad "
+                             "(n_outer, >= %d, d), got %s, %s and %s" % (self.num_relation, self.num_in, self.num_node,
+                                                                        tuple(relation.shape), tuple(input.shape),
+                                                                        tuple(output_grad.shape)))
+        wgrad = torch.empty((n_outer, self.num_edge), dtype=torch.float32, device=input.device)
+        if n_outer == 0 or d == 0 or self.num_edge == 0:
+            return wgrad.zero_()
+        relation, mrel = as_mat(relation)
+        input, mx = as_mat(input)
+        output_grad, mog = as_mat(output_grad)
+        rc = lib.ultra_rspmm_edge_grad_samples(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], _lib.F32, ctypes.byref(mrel),
+                                               ctypes.byref(mx), ctypes.byref(mog), wgrad.data_ptr(), self.num_edge,
+                                               _stream(input))
+        if rc == _lib.ULTRA_ERR_UNSUPPORTED:
+            return None
+        check(rc)
+        return wgrad
+
     def forward_timed(self, relation, input, edge_weight=None, boundary=None, sum="add", mul="mul", warmup=3, iters=20,
                       point=None):
         """Mean HIP-event time (ms) of the forward launch sequence on the current stream; `point` as in forward()."""
