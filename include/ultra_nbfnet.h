@@ -130,6 +130,21 @@ int32_t ultra_easy_edge_keep(const int64_t *head, const int64_t *tail, const int
                              const int64_t *t, const int64_t *r, int64_t n_triple, int64_t stride, int64_t num_node,
                              int64_t num_rel, int64_t inverse_offset, void *keep, void *stream);
 /*
+ * One keep ROW per sample (leave-one-out verification of stated facts): keep[s, e] = 0 where edge e is triple s -- (h_s, t_s,
+ * r_s) -- or its inverse (t_s, h_s, r_s + inverse_offset), else 1: the easy edges of base_nbfnet.py:57-59 for the single triple
+ * s, where ultra_easy_edge_keep marks their union over the batch.  Same operands and keys as ultra_easy_edge_keep (type == NULL
+ * / r == NULL: `remove_one_hop`, keys of (head, tail) alone, both directions).  keep: (n_sample, keep_stride) fp32, keep_stride
+ * >= num_edge; every element [s, 0:num_edge) is written and the padding of a row is left alone.  All duplicates of an edge
+ * go; a triple that is not in the graph gives a row of ones.  One launch: the 2 n_sample keys are staged in LDS and every thread
+ * compares its edge, loaded once, with all of them -- no atomics, no memset, no allocation, no host synchronisation, so the call
+ * records into a hipGraph (the rows feed ultra_rspmm_forward_masked_samples).  n_sample > 1024: ULTRA_ERR_UNSUPPORTED;
+ * keep_stride < num_edge or a negative size: ULTRA_ERR_INVALID -- both decided before any pointer is looked at.  n_sample == 0 or
+ * num_edge == 0: ULTRA_OK, nothing launched.
+ */
+int32_t ultra_leave_one_out_keep(const int64_t *head, const int64_t *tail, const int64_t *type, int64_t num_edge, const int64_t *h,
+                                 const int64_t *t, const int64_t *r, int64_t n_sample, int64_t stride, int64_t num_node,
+                                 int64_t num_rel, int64_t inverse_offset, void *keep, int64_t keep_stride, void *stream);
+/*
  * ultra_easy_edge_keep for batches of ANY size (pre-training: 64 x 513 triples): the same operands and the same keep vector,
  * the 2 n_triple keys hashed into an open-addressing table in global memory instead of LDS.  `workspace` holds the table:
  * at least ultra_easy_edge_keep_table_workspace(n_triple) bytes of device memory (a power of two of >= 2 slots per key, 8 B

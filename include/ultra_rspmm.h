@@ -206,6 +206,23 @@ int32_t ultra_rspmm_forward_masked(ultra_plan *plan, int32_t sum, int32_t mul, i
                                    const ultra_mat *output, void *stream);
 
 /*
+ * ultra_rspmm_forward_masked with one keep mask PER OUTER SLICE: edge_keep_dev is (n_outer, num_edge), dtype-typed, original
+ * edge order, slices keep_stride >= num_edge elements apart.  Outer slice s runs on the static graph without the edges e with
+ * keep[s, e] == 0 -- it equals ultra_rspmm_forward on a plan of the edge list filtered by row s, with slice s of the operands
+ * ("absent" as above: a zero weight under add, no part in the reduction under min / max).  Every sample of a batch sees its
+ * own sub-graph of one cached plan: leave-one-out verification of stated facts (ultra_leave_one_out_keep builds the rows).
+ * Served by ULTRA_PLAN_EXACT_ORDER plans in the sparse format through the weighted reference-order kernels, which read
+ * keep[perm[.]] from a base taken per span -- no sorted copy, no scratch, nothing that could not be recorded into a hipGraph.
+ * fp32 / fp64, add / min / max, mul / add messages, a dense boundary or none.  General-walk and dense-format plans, rotate
+ * messages and calls the reference-order kernels do not take (rows that are no multiple of 16 bytes, misaligned operands):
+ * ULTRA_ERR_UNSUPPORTED with nothing launched -- the caller then issues one ultra_rspmm_forward_masked per slice, which computes
+ * the same values.  keep_stride < num_edge, a NULL mask or output: ULTRA_ERR_INVALID.  n_outer == 0: ULTRA_OK.
+ */
+int32_t ultra_rspmm_forward_masked_samples(ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const void *edge_keep_dev,
+                                           int64_t keep_stride, const ultra_mat *relation, const ultra_mat *input,
+                                           const ultra_mat *boundary, const ultra_mat *output, void *stream);
+
+/*
  * Forward with a POINT boundary: the NBFNet boundary condition (/root/reference/ultra/models.py:59-66, 135-141) is zero
  * except for one row per outer slice, so `update + boundary` (/root/reference/ultra/layers.py:199-200) only touches that
  * row.  point_values: (n_outer, 1, row_len) -- n_row == 1 -- is added to output row point_rows[outer]; nothing of size

@@ -1,6 +1,7 @@
 """Answer one link-prediction query on a dataset of triple files: the k entities the model predicts, with their scores.
 
     python tools/predict.py --data-root DIR [--ckpt FILE] --head NAME --relation NAME [--inverse] [-k 10] [--unfiltered] [--explain]
+    python tools/predict.py --data-root DIR [--ckpt FILE] --verify (--head NAME --relation NAME --tail NAME | --triples FILE) [--inverse]
 
 DIR holds train.txt / valid.txt / test.txt (`head relation tail` per line) and optionally entities.dict / relations.dict
 (ultra_amd.data.load_triples_dir).  The query is (NAME, relation, ?); with --inverse it is (?, relation, NAME) and heads are
@@ -8,6 +9,11 @@ predicted.  Answers the dataset already states (in any split) are left out unles
 checkpoint (a state dict, or a dict with the state under "model"); without it the weights are randomly initialised, and the
 tool says so.  --explain: under every answer, the paths the model's score rests on (Predictor.explain_tails /
 explain_heads) with their weights; a relation walked against its direction is printed as NAME^-1.
+
+--verify judges facts the dataset may already state: every (head, relation, tail) -- one from the command line, or the
+`head relation tail` lines of FILE -- is scored on the graph WITHOUT itself and its inverse edge (Predictor.verify_tails; with
+--inverse the head is the answer judged, Predictor.verify_heads) and printed with its score, its filtered rank and the number
+of candidates it was ranked among.
 """
 import argparse
 import os
@@ -31,21 +37,36 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--data-root", required=True)
     ap.add_argument("--ckpt")
-    ap.add_argument("--head", required=True, help="the known entity of the query (the tail with --inverse)")
-    ap.add_argument("--relation", required=True)
+    ap.add_argument("--head", help="the known entity of the query (the tail with --inverse)")
+    ap.add_argument("--relation")
+    ap.add_argument("--verify", action="store_true", help="judge stated facts on the graph without themselves")
+    ap.add_argument("--tail", help="--verify: the tail of the fact")
+    ap.add_argument("--triples", help="--verify: a file of `head relation tail` lines")
     ap.add_argument("--inverse", action="store_true", help="predict heads of (?, relation, NAME)")
     ap.add_argument("-k", type=int, default=10)
     ap.add_argument("--unfiltered", action="store_true")
     ap.add_argument("--explain", action="store_true", help="print the top paths behind every answer")
     args = ap.parse_args(argv)
+    if args.verify:
+        if not (args.triples or (args.head and args.relation and args.tail)):
+            ap.error("--verify takes --head, --relation and --tail, or --triples FILE")
+    elif not (args.head and args.relation):
+        ap.error("--head and --relation are required")
     if not torch.cuda.is_available():
         sys.exit("tools/predict.py needs a GPU: the engine has no CPU path")
     from ultra_amd import data as udata
     from ultra_amd import models, predict, synthetic
     ent, rel = udata.read_vocab(args.data_root)
-    for name, vocab, what in ((args.head, ent, "entity"), (args.relation, rel, "relation")):
-        if name not in vocab:
-            sys.exit("unknown %s %r" % (what, name))
+    facts = None
+    if args.verify:
+        facts = [tuple(line.split()) for line in open(args.triples) if line.strip()] if args.triples \
+            else [(args.head, args.relation, args.tail)]
+        if any(len(f) != 3 for f in facts):
+            sys.exit("--triples: every line is `head relation tail`")
+    for h_name, r_name, t_name in facts if facts is not None else [(args.head, args.relation, args.head)]:
+        for name, vocab, what in ((h_name, ent, "entity"), (r_name, rel, "relation"), (t_name, ent, "entity")):
+            if name not in vocab:
+                sys.exit("unknown %s %r" % (what, name))
     dev = torch.device("cuda:0")
     data = udata.load_triples_dir(args.data_root).to(dev)
     model = models.Ultra(**synthetic.default_model_cfg())
@@ -55,6 +76,15 @@ def main(argv=None):
     else:
         print("no --ckpt: randomly initialised weights, the answers mean nothing")
     model = model.to(dev).eval()
+    if facts is not None:
+        predictor = predict.Predictor(model, data, batch_size=min(8, len(facts)))
+        h, r, t = (torch.tensor([vocab.index(f[i]) for f in facts], device=dev) for i, vocab in ((0, ent), (1, rel), (2, ent)))
+        score, rank, num_negative = (predictor.verify_heads if args.inverse else predictor.verify_tails)(h, r, t)
+        print("%s judged on the graph without the fact itself: score, filtered rank / candidates"
+              % ("heads" if args.inverse else "tails"))
+        for f, s, k, n in zip(facts, score.tolist(), rank.tolist(), num_negative.tolist()):
+            print("%-28s %-24s %-28s %12.6g  %6d / %d" % (f[0], f[1], f[2], s, k, n + 1))
+        return
     predictor = predict.Predictor(model, data, k=args.k, batch_size=1, filtered=not args.unfiltered)
     anchor = torch.tensor([ent.index(args.head)], device=dev)
     relation = torch.tensor([rel.index(args.relation)], device=dev)

@@ -91,6 +91,7 @@ def _load():
     lib.ultra_plan_export.argtypes = [vp, i32, vp, i64, ctypes.POINTER(i64)]
     lib.ultra_rspmm_forward.argtypes = [vp, i32, i32, i32, vp, matp, matp, matp, matp, vp]
     lib.ultra_rspmm_forward_masked.argtypes = [vp, i32, i32, i32, vp, matp, matp, matp, matp, vp]
+    lib.ultra_rspmm_forward_masked_samples.argtypes = [vp, i32, i32, i32, vp, i64, matp, matp, matp, matp, vp]
     lib.ultra_rspmm_forward_onehot.argtypes = [vp, i32, vp, matp, matp, vp, matp, matp, vp]
     lib.ultra_rspmm_forward_point.argtypes = [vp, i32, i32, i32, vp, matp, matp, vp, matp, matp, vp]
     lib.ultra_rspmm_forward_update.argtypes = [vp, i32, i32, matp, matp, vp, matp, matp, vp, vp, vp, vp, ctypes.c_float, i32, matp, vp]
@@ -115,6 +116,7 @@ def _load():
     lib.ultra_conv_update_backward.argtypes = [vp] * 14 + [i64, i64, i32, i32, ctypes.c_float, i32, vp]
     lib.ultra_edge_keep_mask.argtypes = [vp, vp, vp, i64, vp, i64, i64, i64, vp, vp]
     lib.ultra_easy_edge_keep.argtypes = [vp, vp, vp, i64, vp, vp, vp, i64, i64, i64, i64, i64, vp, vp]
+    lib.ultra_leave_one_out_keep.argtypes = [vp, vp, vp, i64, vp, vp, vp, i64, i64, i64, i64, i64, vp, i64, vp]
     lib.ultra_easy_edge_keep_table_workspace.argtypes = [i64]
     lib.ultra_easy_edge_keep_table_workspace.restype = i64
     lib.ultra_easy_edge_keep_table.argtypes = [vp, vp, vp, i64, vp, vp, vp, i64, i64, i64, i64, i64, vp, i64, vp, vp]

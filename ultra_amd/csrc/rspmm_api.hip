@@ -324,6 +324,11 @@ struct FwdCall {
     // the stream walk only -- ULTRA_ERR_UNSUPPORTED otherwise, with nothing launched.
     const OrderParams::Update *upd = nullptr;
     int keep_mode = 0;      // ultra_rspmm_forward_masked: the weight stream is a 0/1 keep mask (weigh(), rspmm_kernels.hpp)
+    // ultra_rspmm_forward_masked_samples: one keep mask per outer slice, w_stride_outer elements apart.  Served by the weighted
+    // reference-order kernels only (they read w[perm[.]] from a per-span base: no sorted copy to make per slice) --
+    // ULTRA_ERR_UNSUPPORTED on every other route, with nothing launched.
+    bool w_samples = false;
+    int64_t w_stride_outer = 0;
     hipEvent_t ev_before = nullptr, ev_after = nullptr;   // measurement hook: recorded right before / after the main kernel launch
 };
 
@@ -545,6 +550,7 @@ static int forward_order(ultra_plan *p, int sum, int mul, int dtype, const void 
     op.has_bnd = fp.has_bnd;
     op.has_chain = p->n_chain > 0 ? 1 : 0;
     op.keep_mode = fp.keep_mode;
+    op.w_stride_outer = (w && call.w_samples) ? (int32_t)call.w_stride_outer : 0;
     op.x_row_bytes = fp.x_row_bytes, op.rel_row_bytes = fp.rel_row_bytes;
     op.trace = g_order_trace;
     op.err = device_error_word();
@@ -654,6 +660,10 @@ static int forward_impl(ultra_plan *p, int sum, int mul, int dtype, const void *
         set_error("a point boundary under min / max is served by reference-order plans in the sparse format only");
         return ULTRA_ERR_UNSUPPORTED;
     }
+    if (call.w_samples && (rot || (p->flags & ULTRA_PLAN_DENSE) || !(p->flags & ULTRA_PLAN_EXACT_ORDER))) {
+        set_error("ultra_rspmm_forward_masked_samples: served by reference-order plans in the sparse format, mul / add messages");
+        return ULTRA_ERR_UNSUPPORTED;
+    }
     if (rot && (p->flags & ULTRA_PLAN_DENSE)) {
         set_error("rotate messages are served by the plans in the sparse format");
         return ULTRA_ERR_UNSUPPORTED;
@@ -707,6 +717,11 @@ static int forward_impl(ultra_plan *p, int sum, int mul, int dtype, const void *
         return forward_order(p, sum, mul, dtype, w, x, bnd, out, stream, call, fp, di, ring_bytes, point_fill);
     if (call.upd) {
         set_error("ultra_rspmm_forward_update: this call is not served by the reference-order kernels");
+        return ULTRA_ERR_UNSUPPORTED;
+    }
+    if (call.w_samples) {
+        set_error("ultra_rspmm_forward_masked_samples: this call is not served by the reference-order kernels (row length, "
+                  "alignment or tuning)");
         return ULTRA_ERR_UNSUPPORTED;
     }
     // The general walk below applies a point boundary at row bnd_rows[outer] only: it has no fill for the OTHER rows, which under
@@ -1158,6 +1173,29 @@ int32_t ultra_rspmm_forward_masked(ultra_plan *plan, int32_t sum, int32_t mul, i
     if (!edge_keep_dev) return invalid("ultra_rspmm_forward_masked: edge_keep is NULL");
     FwdCall call;
     call.keep_mode = 1;
+    return forward_impl(plan, sum, mul, dtype, edge_keep_dev, relation, input, boundary, output,
+                        reinterpret_cast<hipStream_t>(stream), call);
+}
+
+int32_t ultra_rspmm_forward_masked_samples(ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const void *edge_keep_dev,
+                                           int64_t keep_stride, const ultra_mat *relation, const ultra_mat *input,
+                                           const ultra_mat *boundary, const ultra_mat *output, void *stream) {
+    if (!plan) return invalid("plan is NULL");
+    if (keep_stride < plan->num_edge) return invalid("ultra_rspmm_forward_masked_samples: keep_stride < num_edge");
+    if (!edge_keep_dev) return invalid("ultra_rspmm_forward_masked_samples: edge_keep is NULL");
+    if (!output || !output->ptr) return invalid("output is NULL");
+    if (output->n_outer == 0) return ULTRA_OK;
+    if (keep_stride > INT32_MAX) {
+        set_error("ultra_rspmm_forward_masked_samples: keep_stride beyond 2^31 - 1 elements");
+        return ULTRA_ERR_UNSUPPORTED;
+    }
+    ULTRA_DEVICE_SCOPE(stream, output->ptr);
+    WeightEpochScope weight_epoch_scope;
+    if (int rc = internal_mul(&mul)) return rc;
+    FwdCall call;
+    call.keep_mode = 1;
+    call.w_samples = true;
+    call.w_stride_outer = keep_stride;
     return forward_impl(plan, sum, mul, dtype, edge_keep_dev, relation, input, boundary, output,
                         reinterpret_cast<hipStream_t>(stream), call);
 }

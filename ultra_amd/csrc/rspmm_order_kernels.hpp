@@ -65,7 +65,7 @@ static_assert(CHAIN_SLOTS == 4 * (ORDER_THREADS / 64 - 1), "one ring slot per pr
 struct OrderParams {
     const int32_t *rec;       // (col, type) per sorted edge
     const int32_t *perm;      // sorted position -> original edge id
-    const void *w;            // edge weights in ORIGINAL edge order, or NULL (all ones)
+    const void *w;            // edge weights in ORIGINAL edge order, or NULL (all ones); outer slice s reads w + s * w_stride_outer
     const int4 *items;        // {row, begin, len, -}; chain rows first, group items from n_chain on
     const int32_t *unit_ptr, *units, *chunk_ptr;
     const int4 *chunks;       // {row, begin, count, flags}
@@ -94,6 +94,9 @@ struct OrderParams {
     // (ultra_device_error, checked at the next entry), not a hung GPU.  Codes: ORDER_SPIN_*.
     uint32_t *err;
     int32_t max_stream_steps; // longest group stream of the schedule in steps (allowance of the update waves' wait for rows)
+    // WEIGHTED instances: elements between the weight vectors of consecutive outer slices -- 0: one vector shared by the batch
+    // (every call but ultra_rspmm_forward_masked_samples, whose keep mask is (n_outer, num_edge)).  (Sits in what was padding.)
+    int32_t w_stride_outer;
     // UPDATE instances: the layer update (update_tile.hpp) of the rows this workgroup aggregated, applied after its walk
     struct Update {
         const float *weight, *bias, *ln_w, *ln_b;   // Linear(128 -> 64) [+ LayerNorm(64)]
@@ -148,12 +151,11 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 template <typename T, int SUM, int MUL, bool REL_LDS, bool WEIGHTED>
 __device__ __forceinline__ Pack<T, 4> walk_row_in_order(const OrderParams &p, const int begin, const int cnt, const int nsteps,
                                                         const int nfull, const int l16, const char *xbase, const char *relbase,
-                                                        const uint32_t lane_bytes, const T *lds_rel_lane) {
+                                                        const uint32_t lane_bytes, const T *lds_rel_lane, const T *wt) {
     constexpr int SPAN = 64;
     using P = Pack<T, 4>;
     using V = typename VecOf<T, 4>::type;
     V acc = V(nary_zero<T, SUM>());
-    const T *wt = reinterpret_cast<const T *>(p.w);
     const int l8 = l16 & 7;
     // record / permutation streams: uniform base + 32-bit per-lane offset (no 64-bit address pair to keep alive)
     const char *rec_base = reinterpret_cast<const char *>(p.rec);
@@ -432,7 +434,6 @@ __global__ void __launch_bounds__(ORDER_THREADS) ULTRA_ORDER_VGPR_CAP rspmm_orde
     constexpr int nwave = ORDER_THREADS / 64;
     const int part = blockIdx.x / p.smod;
     if (part >= p.nparts) return;
-    const T *wt = reinterpret_cast<const T *>(p.w);
     // UPDATE == 3: the control block of the hand-off (update_tile.hpp UPD2_CTL_*)
     volatile uint32_t *ctl = reinterpret_cast<volatile uint32_t *>(smem + (UPDATE == 3 ? p.upd.ctl_off : 0));
     const T fill = (SUM != 0 && p.bnd_fill_on) ? (T)p.bnd_fill : nary_zero<T, SUM>();   // (what a non-boundary row meets under min / max)
@@ -446,6 +447,9 @@ __global__ void __launch_bounds__(ORDER_THREADS) ULTRA_ORDER_VGPR_CAP rspmm_orde
     for (int span = blockIdx.x % p.smod; span < p.n_span; span += p.smod) {
         const int outer = span / p.spans_per_outer;
         const int inner = span - outer * p.spans_per_outer;
+        // weights of this span's outer slice (the unweighted instances never look: keep the arithmetic out of them)
+        const T *wt = nullptr;
+        if constexpr (WEIGHTED) wt = reinterpret_cast<const T *>(p.w) + (long long)outer * p.w_stride_outer;
         const char *xbase = reinterpret_cast<const char *>(reinterpret_cast<const T *>(p.x.ptr) + outer * p.x.stride_outer);
         const char *relbase =
             reinterpret_cast<const char *>(reinterpret_cast<const T *>(p.rel.ptr) + outer * p.rel.stride_outer);
@@ -1153,7 +1157,7 @@ __global__ void __launch_bounds__(ORDER_THREADS) ULTRA_ORDER_VGPR_CAP rspmm_orde
             const int nfull = rfl(min(n01, n23));
 
             P acc = walk_row_in_order<T, SUM, MUL, REL_LDS, WEIGHTED>(p, begin, cnt, nsteps, nfull, l16, xbase, relbase, lane_bytes,
-                                                                      lds_rel_lane);
+                                                                      lds_rel_lane, wt);
             if (row >= 0 && dvalid) {
                 if (p.has_bnd && (bnd_row < 0 || bnd_row == row)) {
                     const P b = *reinterpret_cast<const P *>(reinterpret_cast<const T *>(p.bnd.ptr) + outer * p.bnd.stride_outer +

@@ -196,6 +196,42 @@ __global__ void __launch_bounds__(EASY_THREADS) easy_edge_keep_kernel(const long
     }
 }
 
+// One keep ROW per sample instead of the union over the batch: keep[s, e] = 0 where edge e is triple s or its inverse (the easy
+// edges of base_nbfnet.py:57-59 for the single triple s), else 1 -- sample s of a verified batch must not see its own fact and
+// must still see every other sample's.  One pass: the 2 n_sample keys sit in LDS ([s] direct, [LOO_MAX + s] inverse), a thread
+// loads its edge ONCE, compares it with every sample's two keys (all lanes read the same LDS word: a broadcast) and writes one
+// value per sample, consecutive lanes to consecutive edges of the row.  Every element [s, 0:num_edge) is written -- no memset
+// node, no atomics; the padding [num_edge, keep_stride) of a row is not touched.  A negative key (a padded triple) matches no edge.
+constexpr int LOO_MAX = 1024;
+constexpr int LOO_THREADS = 256;
+__global__ void __launch_bounds__(LOO_THREADS) leave_one_out_keep_kernel(const long long *head, const long long *tail,
+                                                                        const long long *type, long long num_edge,
+                                                                        const long long *qh, const long long *qt, const long long *qr,
+                                                                        int n_sample, long long stride, long long num_node,
+                                                                        long long num_rel, long long inverse_offset, float *keep,
+                                                                        long long keep_stride) {
+    __shared__ long long lds_key[2 * LOO_MAX];
+    for (int s = threadIdx.x; s < n_sample; s += LOO_THREADS) {
+        const long long a = qh[s * stride], b = qt[s * stride];
+        long long direct = a * num_node + b, inverse = b * num_node + a;
+        if (type) {
+            const long long r = qr[s * stride];
+            direct = direct * num_rel + r;
+            inverse = inverse * num_rel + r + inverse_offset;
+        }
+        lds_key[s] = direct;
+        lds_key[LOO_MAX + s] = inverse;
+    }
+    __syncthreads();
+    for (long long e = blockIdx.x * (long long)LOO_THREADS + threadIdx.x; e < num_edge; e += (long long)gridDim.x * LOO_THREADS) {
+        long long key = head[e] * num_node + tail[e];
+        if (type) key = key * num_rel + type[e];
+        float *dst = keep + e;
+        for (int s = 0; s < n_sample; ++s, dst += keep_stride)
+            *dst = (key == lds_key[s] || key == lds_key[LOO_MAX + s]) ? 0.f : 1.f;
+    }
+}
+
 // The same vector for batches of any size (pre-training: 64 x 513 triples, 65,664 keys): the keys go into an open-addressing
 // table in GLOBAL memory -- a power of two of at least twice as many slots as keys, so a probe meets an empty slot within a
 // few steps -- that the caller owns (ultra_easy_edge_keep_table_workspace).  Three launches on one stream, none of which allocates
@@ -342,6 +378,40 @@ extern "C" int32_t ultra_easy_edge_keep(const int64_t *head, const int64_t *tail
                        (long long)num_node, (long long)num_rel, (long long)inverse_offset, (float *)keep);
     if (hipGetLastError() != hipSuccess) {
         ultra::set_error("easy_edge_keep_kernel launch failed");
+        return ULTRA_ERR_HIP;
+    }
+    return ULTRA_OK;
+}
+
+extern "C" int32_t ultra_leave_one_out_keep(const int64_t *head, const int64_t *tail, const int64_t *type, int64_t num_edge,
+                                            const int64_t *h, const int64_t *t, const int64_t *r, int64_t n_sample, int64_t stride,
+                                            int64_t num_node, int64_t num_rel, int64_t inverse_offset, void *keep,
+                                            int64_t keep_stride, void *stream) {
+    // (sizes first: decided before any pointer is looked at)
+    if (n_sample > ultra::LOO_MAX) {
+        ultra::set_error("ultra_leave_one_out_keep: more than 1024 samples");
+        return ULTRA_ERR_UNSUPPORTED;
+    }
+    if (num_edge < 0 || n_sample < 0 || keep_stride < num_edge || stride <= 0 || num_node <= 0) {
+        ultra::set_error("ultra_leave_one_out_keep: negative size, keep_stride < num_edge or empty key space");
+        return ULTRA_ERR_INVALID;
+    }
+    if (!head || !tail || !keep || (n_sample > 0 && (!h || !t)) || (type && (num_rel <= 0 || !r))) {
+        ultra::set_error("ultra_leave_one_out_keep: NULL operand");
+        return ULTRA_ERR_INVALID;
+    }
+    if (num_edge == 0 || n_sample == 0) return ULTRA_OK;
+    ULTRA_DEVICE_SCOPE(stream, keep);
+    (void)hipGetLastError();   // drop any stale error left by other users of the runtime
+    const long long want = (num_edge + ultra::LOO_THREADS - 1) / ultra::LOO_THREADS;
+    const unsigned blocks = (unsigned)(want < 2048 ? want : 2048);
+    hipLaunchKernelGGL(ultra::leave_one_out_keep_kernel, dim3(blocks), dim3(ultra::LOO_THREADS), 0,
+                       reinterpret_cast<hipStream_t>(stream), (const long long *)head, (const long long *)tail,
+                       (const long long *)type, (long long)num_edge, (const long long *)h, (const long long *)t, (const long long *)r,
+                       (int)n_sample, (long long)stride, (long long)num_node, (long long)num_rel, (long long)inverse_offset,
+                       (float *)keep, (long long)keep_stride);
+    if (hipGetLastError() != hipSuccess) {
+        ultra::set_error("leave_one_out_keep_kernel launch failed");
         return ULTRA_ERR_HIP;
     }
     return ULTRA_OK;

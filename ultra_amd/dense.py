@@ -287,6 +287,42 @@ def easy_edge_keep(edge_index, edge_type, h_index, t_index, r_index, num_node, n
     return keep if dtype == torch.float32 else keep.to(dtype)
 
 
+LEAVE_ONE_OUT_MAX_SAMPLES = 1024      # ultra_leave_one_out_keep
+
+
+def leave_one_out_keep(edge_index, edge_type, h_index, t_index, r_index, num_node, num_relation, out=None):
+    """One keep ROW per triple: out[s, e] = 0 where edge e is (h_s, t_s, r_s) or its inverse (t_s, h_s, r_s + num_relation // 2),
+    else 1 (edge_type None: `remove_one_hop`, every edge between the two nodes) -- ultra_leave_one_out_keep, one launch, no
+    host synchronisation.  h / t / r: (n) int64 GPU vectors, contiguous or the columns of one contiguous (n, 3) tensor.  `out`:
+    an (n, >= num_edge) fp32 buffer whose rows are written up to num_edge (a captured step owns it); returns the (n, num_edge)
+    view.  None where the kernel does not take the call (the caller restates it in torch)."""
+    n = h_index.numel()
+    num_edge = edge_index.shape[1]
+    if not (edge_index.is_cuda and edge_index.dtype == torch.int64 and h_index.dtype == torch.int64 and h_index.is_cuda
+            and h_index.dim() == 1 and 0 < n <= LEAVE_ONE_OUT_MAX_SAMPLES and h_index.shape == t_index.shape == r_index.shape
+            and int(num_node) ** 2 * max(int(num_relation), 1) < 2 ** 62):
+        return None
+    if h_index.is_contiguous() and t_index.is_contiguous() and r_index.is_contiguous():
+        stride = 1
+    elif h_index.stride() == t_index.stride() == r_index.stride() == (3,):
+        stride = 3
+    else:
+        return None
+    edge_index = edge_index.contiguous()
+    if edge_type is not None:
+        edge_type = edge_type.contiguous()
+    if out is None:
+        out = torch.empty(n, num_edge, dtype=torch.float32, device=edge_index.device)
+    if not (out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] >= n and out.shape[1] >= num_edge
+            and (out.stride(1) == 1 or out.shape[1] <= 1) and out.device == edge_index.device):
+        raise ValueError("leave_one_out_keep: `out` must be an (n, >= num_edge) fp32 buffer on the graph's device")
+    check(lib.ultra_leave_one_out_keep(edge_index[0].data_ptr(), edge_index[1].data_ptr(), _ptr(edge_type), num_edge,
+                                       h_index.data_ptr(), t_index.data_ptr(), r_index.data_ptr() if edge_type is not None else None,
+                                       n, stride, int(num_node), int(num_relation), int(num_relation) // 2, out.data_ptr(),
+                                       out.stride(0), _stream(out)))
+    return out[:n, :num_edge]
+
+
 def easy_edge_keep_table(edge_index, edge_type, h_index, t_index, r_index, num_node, num_relation, dtype=torch.float32):
     """easy_edge_keep for batches of any size (ultra_easy_edge_keep_table: the keys in a hash table in global memory, three
     launches -- clear, insert, probe --, no host synchronisation -- it records into a captured step).  The table is the caller's: allocated here

@@ -211,6 +211,8 @@ class GeneralizedRelationalConv(nn.Module):
 
     def propagate(self, edge_index, size=None, residual=False, onehot_rows=None, edge_keep=False, **kwargs):
         edge_weight = kwargs["edge_weight"]
+        if edge_weight is not None and edge_weight.dim() == 2:
+            return self._propagate_samples(edge_index, size, residual=residual, edge_keep=edge_keep, **kwargs)
         rotate_fused = self.rotate_fused(kwargs["input"], kwargs["relation"], edge_weight)
         if edge_keep and self.message_func == "rotate" and not rotate_fused:
             # the unfused scatter path needs the edges really gone: the caller removes them
@@ -243,6 +245,40 @@ class GeneralizedRelationalConv(nn.Module):
                                          kwargs["edge_type"], edge_weight, edge_index[1], num_node,
                                          onehot_rows=onehot_rows, edge_keep=edge_keep)
         return self.update(out, kwargs["input"], residual=residual)
+
+    def _propagate_samples(self, edge_index, size, input, relation, boundary, edge_type, edge_weight, residual=False,
+                           edge_keep=False):
+        """The layer with one 0/1 keep mask PER SAMPLE: `edge_weight` (batch, num_edge), sample s runs on the graph without the
+        edges whose keep[s] is 0 (rspmm.Plan.forward with a 2-D mask).  Inference only: aggregate, then update -- two launches,
+        as every weighted inference call; the boundary condition goes in as a tensor."""
+        if not edge_keep:
+            raise RuntimeError("a 2-D `edge_weight` is a per-sample keep mask (edge_keep=True); per-sample weights are not served")
+        if torch.is_grad_enabled():
+            raise RuntimeError("per-sample keep masks serve inference (torch.no_grad()) only")
+        rotate = self.message_func == "rotate"
+        if self.aggregate_func == "pna" or (rotate and not self.rotate_fused(input, relation)) \
+                or (not rotate and self.aggregate_func not in ("sum", "mean", "max")):
+            raise RuntimeError("per-sample keep masks serve the fused sum / mean / max (RotatE: also min) paths")
+        if isinstance(boundary, PointBoundary):
+            boundary = boundary.dense()
+        edge_weight = edge_weight.to(input.dtype)
+        boundary = boundary.to(input.dtype)
+        if rotate:      # (the unfused path's direction on the flipped graph: _propagate_rotate)
+            num_node = size[1] if size is not None else input.shape[1]
+            edges, mul = _flipped_edges(edge_index), "rotate"
+        else:
+            num_node = size[0] if size is not None else input.shape[1]
+            edges, mul = edge_index, self.message2mul[self.message_func]
+        plan = rspmm.get_plan(edges, edge_type, num_node, relation.shape[1],
+                              exact_order=False if self._order_free(edge_index, num_node) else None)
+        sum = {"sum": "add", "mean": "add"}.get(self.aggregate_func, self.aggregate_func)
+        update = plan.forward(relation, input, edge_weight=edge_weight, boundary=boundary, sum=sum, mul=mul, keep=True)
+        if self.aggregate_func == "mean":
+            # the degree of each sample's own graph (+ 1: the boundary's self loop), counted at edge_index[1] like the shared mask
+            degree = torch.zeros(len(edge_weight), num_node, dtype=input.dtype, device=input.device).index_add_(
+                1, edge_index[1], edge_weight)
+            update = update / (degree + 1).unsqueeze(-1)
+        return self.update(update, input, residual=residual)
 
     def edge_grad_layer(self, input, query, boundary, edge_index, edge_type, num_node, edge_weight, residual=False,
                         relation=None):

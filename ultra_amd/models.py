@@ -126,6 +126,38 @@ class BaseNBFNet(nn.Module):
                 return rspmm.tag_edge_weight(keep)
         return self.easy_edge_mask(data, h_index, t_index, r_index).to(dtype)
 
+    # ---- leave-one-out verification: one keep row per stated fact ----
+    def leave_one_out_mask(self, data, h_index, t_index, r_index):
+        """The torch restatement of leave_one_out_keep (any device): row s is easy_edge_mask of the single triple s as 0/1 fp32."""
+        rows = [self.easy_edge_mask(data, h_index[s:s + 1], t_index[s:s + 1], r_index[s:s + 1]) for s in range(len(h_index))]
+        if not rows:
+            return torch.ones(0, data.edge_index.shape[1], dtype=torch.float32, device=data.edge_index.device)
+        return torch.stack(rows).to(torch.float32)
+
+    def leave_one_out_keep(self, data, triples, out=None, validate=True):
+        """(n, num_edge) fp32: row s is the 0/1 keep mask of `data`'s edge list WITHOUT the stated fact s = triples[s] = (h, t, r)
+        and its inverse (t, h, r + num_relations // 2) -- _easy_edges of that single triple; with `remove_one_hop` without
+        every edge between h and t.  All duplicates of an edge go; a triple that is not in the graph gives a row of ones.  r
+        must be a direct relation (ValueError otherwise; validate=False skips that host read -- a captured step's caller has
+        checked its ids already).  GPU: ultra_leave_one_out_keep, one launch into `out` if given; elsewhere the torch
+        restatement via tasks.edge_match."""
+        if triples.dim() != 2 or triples.shape[1] != 3:
+            raise ValueError("Expected triples of shape (n, 3) = (h, t, r), got %s" % (tuple(triples.shape),))
+        h_index, t_index, r_index = triples.unbind(-1)
+        if validate and triples.numel() and bool(((r_index < 0) | (r_index >= data.num_relations // 2)).any()):
+            raise ValueError("leave-one-out verification takes direct relations (r < num_relations // 2 = %d); a fact stated "
+                             "through an inverse relation is its direct twin" % (data.num_relations // 2))
+        if data.edge_index.is_cuda:
+            keep = dense.leave_one_out_keep(data.edge_index, None if self.remove_one_hop else data.edge_type, h_index, t_index,
+                                            r_index, data.num_nodes, data.num_relations, out=out)
+            if keep is not None:
+                return keep
+        keep = self.leave_one_out_mask(data, h_index, t_index, r_index)
+        if out is not None:
+            out[:keep.shape[0], :keep.shape[1]].copy_(keep)
+            return out[:keep.shape[0], :keep.shape[1]]
+        return keep
+
     def remove_easy_edges(self, data, h_index, t_index, r_index=None):
         """The reference's route: a filtered copy of the graph (only `rotate` off the engine still needs it: layers.rotate_fused)."""
         keep = self.easy_edge_mask(data, h_index, t_index, r_index)
@@ -170,7 +202,9 @@ class BaseNBFNet(nn.Module):
         if isinstance(boundary, layers.PointBoundary):
             layer = self.layers[0]
             rel0 = None if relations is None else relations[0]
-            if not separate_grad and layer.layer0_point_supported(boundary, rel0, edge_weight):
+            # (a per-sample keep mask -- 2-D -- has no layer-0 kernel: the layer takes the boundary as a tensor)
+            per_sample = edge_weight is not None and edge_weight.dim() == 2
+            if not separate_grad and not per_sample and layer.layer0_point_supported(boundary, rel0, edge_weight):
                 # layer 0 on its one-hot input: constant fill + the rows reached from the source (ultra_nbf_layer0);
                 # the boundary condition never becomes a (batch, N, d) tensor on this path
                 residual = self.short_cut and layer.output_dim == layer.input_dim
@@ -575,7 +609,21 @@ class EntityNBFNet(BaseNBFNet):
         return (PROLOGUE_FAST_PATH and not self.training and not torch.is_grad_enabled() and batch.is_cuda
                 and batch.dtype == torch.long and batch.dim() == 3 and not self.concat_hidden)
 
-    def forward(self, data, relation_representations, batch, prefill=None, prologue=None):
+    def _check_edge_keep(self, data, batch, edge_keep):
+        """edge_keep of forward(): one 0/1 keep row over data's edge list per sample; inference only."""
+        if self.training or torch.is_grad_enabled():
+            raise ValueError("edge_keep (per-sample keep masks) serves eval mode under torch.no_grad() only: a training step "
+                             "builds its own batch-wide vector")
+        if not torch.is_tensor(edge_keep) or edge_keep.dim() != 2 \
+                or tuple(edge_keep.shape) != (batch.shape[0], data.edge_index.shape[1]):
+            raise ValueError("edge_keep must be a (batch, num_edge) = (%d, %d) tensor" % (batch.shape[0], data.edge_index.shape[1]))
+
+    def forward(self, data, relation_representations, batch, prefill=None, prologue=None, edge_keep=None):
+        """edge_keep (batch, num_edge), 0/1, original edge order: sample s runs on the graph without the edges whose
+        edge_keep[s] is 0 -- row s of the result is this forward on data filtered by edge_keep[s] with batch[s:s+1] (eval mode
+        under no_grad only).  The relation graph is the caller's: not rebuilt."""
+        if edge_keep is not None:
+            self._check_edge_keep(data, batch, edge_keep)
         h_index, t_index, r_index = batch.unbind(-1)
         prefilled = None
         if prefill is not None:       # (prefill_layer0: the side stream joins here, whatever path the forward takes)
@@ -603,13 +651,21 @@ class EntityNBFNet(BaseNBFNet):
                 # rotate off the engine (pna, CPU tensors, layers.FUSED_ROTATE = False) runs the unfused scatter path: the
                 # reference's filtered copy of the graph
                 data = self.remove_easy_edges(data, h_index, t_index, r_index)
+        elif edge_keep is not None:
+            # per-sample masks: every layer walks the cached plan of the full graph with its sample's row (layers._propagate_samples)
+            edge_weight = edge_keep if edge_keep.dtype == relation_representations.dtype \
+                else edge_keep.to(relation_representations.dtype)
+            prefilled = None
 
         shape = h_index.shape
-        if edge_weight is None and self.prologue_supported(batch):
+        if (edge_weight is None or edge_keep is not None) and self.prologue_supported(batch):
             # inference fast path: one prologue kernel (row uniformity, head->tail conversion, validity flag) and
             # a readout that picks its candidate column straight from the raw batch
             batch_c, h0, r0, side, valid = prologue if prologue is not None else dense.batch_prologue(batch, data.num_relations // 2)
-            hiddens, _, query = self._bellmanford_hidden(data, h0, r0, prefilled=prefilled)
+            # (with edge_keep: the masked branch -- prologue, masked layers, readout, every step an engine launch, so a capture
+            # records it like the unmasked one)
+            hiddens, _, query = self._bellmanford_hidden(data, h0, r0, prefilled=prefilled, edge_weight=edge_weight,
+                                                         edge_keep=edge_weight is not None)
             if dense.readout_supported(self, hiddens[-1]):
                 score = dense.readout_batch(self, hiddens[-1], query, batch_c, side).view(shape)
                 self._check_valid(valid)
@@ -823,8 +879,15 @@ class Ultra(nn.Module):
                 layer.relation = r
         return results
 
-    def forward(self, data, batch):
+    def forward(self, data, batch, edge_keep=None):
         # batch: (bs, 1 + num_negs, 3); the relation is shared by every triple of a row
+        # edge_keep (bs, num_edge): per-sample 0/1 keep masks over data's edge list (EntityNBFNet.forward); the relation graph is
+        # not rebuilt -- the reference's filtered copy keeps data.relation_graph too
+        entity_kwargs = {}
+        if edge_keep is not None:
+            if self.training or torch.is_grad_enabled():
+                raise ValueError("edge_keep (per-sample keep masks) serves eval mode under torch.no_grad() only")
+            entity_kwargs["edge_keep"] = edge_keep
         prologue = None
         if getattr(self.entity_model, "prologue_supported", lambda b: False)(batch):
             # the batch prologue first: it also hands out every row's relation as a contiguous vector -- the relation model's
@@ -840,5 +903,5 @@ class Ultra(nn.Module):
         if relation_representations is None:
             relation_representations = self.relation_model(data.relation_graph, query=query_rels)
         if prefill is not None or prologue is not None:
-            return self.entity_model(data, relation_representations, batch, prefill=prefill, prologue=prologue)
-        return self.entity_model(data, relation_representations, batch)
+            return self.entity_model(data, relation_representations, batch, prefill=prefill, prologue=prologue, **entity_kwargs)
+        return self.entity_model(data, relation_representations, batch, **entity_kwargs)

@@ -9,6 +9,9 @@ and relation, leaving out the ones the graph already states?
   known_answers             the ragged lists of ids to leave out, from the filter graph (no positive is added)
   Predictor                 .tails(h, r) / .heads(t, r): candidate construction, the forward and the selection as one
                             hipGraph replay per batch
+  verify_reference          leave-one-out verification of stated facts in plain torch: per triple a filtered copy of the graph
+  Predictor.verify_tails    ... the same for a batch of facts as one hipGraph replay: per-sample keep masks over the cached plan
+    / .verify_heads         of the full graph
 
 Order: score descending, equal scores by ascending id, every NaN above every number (NaNs tie), -0.0 == +0.0
 -- the stable descending torch.sort.  A filtered candidate is removed, not rescored: a genuine -inf score is a candidate
@@ -18,7 +21,7 @@ import ctypes
 
 import torch
 
-from . import _lib, models, tasks
+from . import _lib, dense, models, tasks
 from .graph import Capture, param_state
 
 
@@ -154,6 +157,104 @@ class _GraphedPredictStep(Capture):
         return self.ids, self.scores, self.count
 
 
+def _entity_model(model):
+    return getattr(model, "entity_model", model)
+
+
+def _check_facts(data, h, r, t):
+    """(h, r, t) of verify_*: int64 vectors of one length on the graph's device, r a direct relation (ValueError otherwise)."""
+    dev = data.edge_index.device
+    h, r, t = (torch.as_tensor(v, dtype=torch.long, device=dev).flatten() for v in (h, r, t))
+    if not (h.shape == r.shape == t.shape):
+        raise ValueError("one head, relation and tail per fact: got %d heads, %d relations and %d tails" % (len(h), len(r), len(t)))
+    direct = int(data.num_relations) // 2
+    if len(r) and bool(((r < 0) | (r >= direct)).any()):
+        raise ValueError("verify takes direct relations (r < num_relations // 2 = %d): a fact stated through an inverse relation "
+                         "is its direct twin" % direct)
+    return h, r, t
+
+
+@torch.no_grad()
+def verify_reference(model, data, filter_graph, h, r, t, mode="tail"):
+    """Leave-one-out verification in the reference's own terms, on any device: fact i = (h[i], r[i], t[i]) is scored on a
+    filtered COPY of the graph without itself and its inverse (BaseNBFNet.remove_easy_edges of that single triple, relation
+    graph kept) -- mode="tail": t[i] among all tails of (h[i], r[i], ?); mode="head": h[i] among all heads of (?, r[i], t[i]),
+    scored through the inverse relation as in evaluation -- and ranked under the filtered protocol of tasks.py:94-141 against
+    `filter_graph`'s known answers (the positive among them; ties count against it).  Returns (score (n) fp32, rank (n)
+    int64, num_negative (n) int64).  One plan, one forward per triple: the definition Predictor.verify_* is tested against."""
+    if mode not in ("tail", "head"):
+        raise ValueError("mode must be 'tail' or 'head', got %r" % (mode,))
+    h, r, t = _check_facts(data, h, r, t)
+    dev = h.device
+    score = torch.empty(len(h), dtype=torch.float32, device=dev)
+    rank = torch.empty(len(h), dtype=torch.long, device=dev)
+    num_negative = torch.empty(len(h), dtype=torch.long, device=dev)
+    ent = _entity_model(model)
+    was_training = model.training
+    model.eval()
+    try:
+        for i in range(len(h)):
+            batch = torch.stack([h[i:i + 1], t[i:i + 1], r[i:i + 1]], dim=-1)
+            without = ent.remove_easy_edges(data, h[i:i + 1], t[i:i + 1], r[i:i + 1])
+            cand = tasks.all_negative(data, batch)[0 if mode == "tail" else 1]
+            pred = model(without, cand).float()
+            mask = tasks.strict_negative_mask(filter_graph, batch)[0 if mode == "tail" else 1]
+            pos = batch[:, 1] if mode == "tail" else batch[:, 0]
+            score[i] = pred[0, pos[0]]
+            rank[i] = tasks.compute_ranking(pred, pos, mask)[0]
+            num_negative[i] = mask.sum(dim=-1)[0]
+    finally:
+        model.train(was_training)
+    return score, rank, num_negative
+
+
+class _GraphedVerifyStep(Capture):
+    """One batch of stated facts of one direction as ONE hipGraph replay (a graph.Capture, like _GraphedPredictStep): the
+    leave-one-out keep rows from the (bs, 3) triples (ultra_leave_one_out_keep into the step's (bs, num_edge) fp32 buffer), the
+    candidates, the masked forward on the full graph's cached plans, ultra_filtered_rank and the gather of the positives' scores.
+    Per batch the host copies the triples and the (bs + 1) offsets into the known lists of the whole call (`load_index`)."""
+
+    def __init__(self, model, data, batch_size, mode, index_capacity, warmup=2):
+        dev = data.edge_index.device
+        Capture.__init__(self, dev)
+        self.model, self.bs, self.mode = model, batch_size, mode
+        self.capacity = max(1, int(index_capacity))
+        self.triples = torch.zeros(batch_size, 3, dtype=torch.long, device=dev)       # (h, t, r)
+        self.ptr = torch.zeros(batch_size + 1, dtype=torch.long, device=dev)
+        self.index = torch.zeros(self.capacity, dtype=torch.long, device=dev)
+        self.keep = torch.empty(batch_size, data.edge_index.shape[1], dtype=torch.float32, device=dev)
+        self.score = torch.empty(batch_size, dtype=torch.float32, device=dev)
+        self.rank = torch.empty(batch_size, dtype=torch.long, device=dev)
+        self.num_negative = torch.empty(batch_size, dtype=torch.long, device=dev)
+        n = int(data.num_nodes)
+        ent = _entity_model(model)
+
+        def step():
+            keep = ent.leave_one_out_keep(data, self.triples, out=self.keep, validate=False)
+            h, t, r = self.triples.unbind(-1)
+            anchor, pos = (h, t) if mode == "tail" else (t, h)
+            pred = model(data, _candidates(data, anchor, r, mode), edge_keep=keep).float().contiguous()
+            pos = pos.contiguous()
+            _lib.check(_lib.lib.ultra_filtered_rank(pred.data_ptr(), pos.data_ptr(), self.ptr.data_ptr(), self.index.data_ptr(),
+                                                    batch_size, n, self.rank.data_ptr(), self.num_negative.data_ptr(),
+                                                    _stream(dev)))
+            self.score.copy_(pred.gather(1, pos.unsqueeze(-1)).squeeze(-1))
+
+        self.warm_up(step, warmup)
+        self.capture(step)
+        self.params = param_state(model)
+
+    def load_index(self, index):
+        self.index[:index.numel()].copy_(index, non_blocking=True)
+
+    def __call__(self, triples, ptr):
+        """(score, rank, num_negative) of this batch -- views of the step's buffers: copy before the next call."""
+        self.triples.copy_(triples, non_blocking=True)
+        self.ptr.copy_(ptr, non_blocking=True)
+        self.graph.replay()
+        return self.score, self.rank, self.num_negative
+
+
 class Predictor(object):
     """Top-k answers of link-prediction queries on one graph.
 
@@ -161,6 +262,7 @@ class Predictor(object):
         ids, scores, count = predictor.tails(h, r)       # (n, k), (n, k), (n): the best tails of every (h[i], r[i], ?)
         ids, scores, count = predictor.heads(t, r)       # ... the best heads of every (?, r[i], t[i])
         ids, scores, count, why = predictor.explain_tails(h, r)    # ... and the top paths behind every answer (explain_heads alike)
+        score, rank, num_negative = predictor.verify_tails(h, r, t)     # each fact scored on the graph without itself
 
     Known answers are left out (filtered=True): the tails of (h, r, .) / heads of (., r, t) in the filter graph --
     `filtered_data`, else data.filtered_data when present, else `data` (the rule of eval.evaluate).  On the GPU with use_graph
@@ -219,6 +321,23 @@ class Predictor(object):
             at += c
         return ids, scores, count, explanations
 
+    def verify_tails(self, h, r, t):
+        """How plausible is each STATED fact (h[i], r[i], t[i]) given the rest of the graph?  Scoring a triple that is an edge of
+        the graph says nothing -- its own edge is a one-hop path from h to t -- so fact i is scored on the graph WITHOUT itself
+        and its inverse (with the model's `remove_one_hop`: without any edge between the two nodes), while it still sees every
+        other fact of the batch: a leave-one-out view per sample, as per-sample keep masks over the cached plan of the full
+        graph (the relation graph is not rebuilt, as in the reference's training-time removal).  Returns (score (n) fp32: the
+        logit of t[i] as the tail of (h[i], r[i], ?); rank (n) int64: 1 + the candidates outside the filter graph's known tails
+        of (h[i], r[i]) that score at least as high; num_negative (n) int64: how many such candidates there are).  r must be
+        direct relations (ValueError).  On the GPU with use_graph each batch is one hipGraph replay; predict.verify_reference
+        is the plain-torch restatement."""
+        return self._verify(h, r, t, "tail")
+
+    def verify_heads(self, h, r, t):
+        """verify_tails for h[i] as the head of (?, r[i], t[i]): scored as the tail query (t[i], r[i] + num_direct_rel, ?), exactly
+        as evaluation does; the removed edges are the same two."""
+        return self._verify(h, r, t, "head")
+
     def close(self):
         """Drop the captured steps (their plans are unpinned)."""
         for step in self._steps.values():
@@ -244,6 +363,73 @@ class Predictor(object):
         step = _GraphedPredictStep(self.model, self.data, self.batch_size, self.k, mode, capacity)
         self._steps[mode] = step
         return step
+
+    def _verify_step(self, mode, need):
+        key = "verify_" + mode
+        step = self._steps.get(key)
+        if step is not None and step.params == param_state(self.model) and need <= step.capacity:
+            return step
+        if step is not None:
+            step.release()
+            del self._steps[key]
+        step = _GraphedVerifyStep(self.model, self.data, self.batch_size, mode, max(2 * need, 1 << 16))
+        self._steps[key] = step
+        return step
+
+    @torch.no_grad()
+    def _verify(self, h, r, t, mode):
+        data, bs = self.data, self.batch_size
+        h, r, t = _check_facts(data, h, r, t)
+        dev = h.device
+        n = len(h)
+        score = torch.empty(n, dtype=torch.float32, device=dev)
+        rank = torch.empty(n, dtype=torch.long, device=dev)
+        num_negative = torch.empty(n, dtype=torch.long, device=dev)
+        if n == 0:
+            return score, rank, num_negative
+        ent = _entity_model(self.model)
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            triples = torch.stack([h, t, r], dim=-1)
+            ptr, index = tasks.known_answers(self.filter_graph, triples, mode)      # the known lists of the whole call, once
+            ptr, index = ptr.contiguous(), index.contiguous()
+            start = 0
+            if self.use_graph and dev.type == "cuda" and not self._eager_only and bs <= dense.LEAVE_ONE_OUT_MAX_SAMPLES:
+                try:
+                    step = self._verify_step(mode, index.numel())
+                    pad = (-n) % bs
+                    if pad:     # (padded rows: copies of the last fact with no known list; dropped below)
+                        triples_p = torch.cat([triples, triples[-1:].expand(pad, -1)])
+                        ptr_p = torch.cat([ptr, ptr[-1:].expand(pad)])
+                    else:
+                        triples_p, ptr_p = triples, ptr
+                    step.load_index(index)
+                    for lo in range(0, n, bs):
+                        rows = min(bs, n - lo)
+                        b_score, b_rank, b_neg = step(triples_p[lo:lo + bs], ptr_p[lo:lo + bs + 1])
+                        score[lo:lo + rows].copy_(b_score[:rows], non_blocking=True)
+                        rank[lo:lo + rows].copy_(b_rank[:rows], non_blocking=True)
+                        num_negative[lo:lo + rows].copy_(b_neg[:rows], non_blocking=True)
+                    start = n
+                except models.NotOnFusedPath:       # model outside the fused inference path: everything runs eagerly below
+                    torch.cuda.synchronize()
+                    self._eager_only = True
+            for lo in range(start, n, bs):
+                part = triples[lo:lo + bs].contiguous()
+                keep = ent.leave_one_out_keep(data, part, validate=False)
+                anchor, pos = (part[:, 0], part[:, 1]) if mode == "tail" else (part[:, 1], part[:, 0])
+                pred = self.model(data, _candidates(data, anchor, part[:, 2], mode), edge_keep=keep).float().contiguous()
+                pos, b_ptr = pos.contiguous(), ptr[lo:lo + len(part) + 1].contiguous()
+                b_rank, b_neg = torch.empty_like(pos), torch.empty_like(pos)
+                _lib.check(_lib.lib.ultra_filtered_rank(pred.data_ptr(), pos.data_ptr(), b_ptr.data_ptr(), index.data_ptr(),
+                                                        len(part), pred.shape[1], b_rank.data_ptr(), b_neg.data_ptr(),
+                                                        _stream(dev)))
+                score[lo:lo + len(part)] = pred.gather(1, pos.unsqueeze(-1)).squeeze(-1)
+                rank[lo:lo + len(part)], num_negative[lo:lo + len(part)] = b_rank, b_neg
+        finally:
+            self.model.train(was_training)
+        return score, rank, num_negative
 
     @torch.no_grad()
     def _run(self, anchor, relation, mode):

@@ -254,6 +254,8 @@ class Plan(object):
         reference-order plans; returns None where it is not (the caller then passes the boundary as a tensor).
         keep=True: `edge_weight` is a 0/1 keep mask -- an edge with 0 is absent from the graph for this call
         (ultra_rspmm_forward_masked; differs from a zero weight under min / max only)."""
+        if edge_weight is not None and edge_weight.dim() == 2:
+            return self._forward_samples(relation, input, edge_weight, boundary, sum, mul, out, point, keep)
         if point is not None:
             if boundary is not None:
                 raise RuntimeError("a point boundary excludes `boundary`")
@@ -309,6 +311,54 @@ class Plan(object):
         _announce_weight(edge_weight, weight_epoch)
         check(entry(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], dt, w, ctypes.byref(mrel),
                     ctypes.byref(mx), mb, ctypes.byref(mout), _stream(input)))
+        return out
+
+    def masked_samples_entry(self, relation, input, edge_keep, boundary, sum, mul, out):
+        """ultra_rspmm_forward_masked_samples on batch-major 3-D operands; returns the entry's status code (ULTRA_ERR_UNSUPPORTED:
+        nothing was launched -- general-walk plans, rotate messages, rows the reference-order kernels do not take)."""
+        _require_gpu(relation, input, edge_keep, boundary, out)
+        dt = _dtype_code(*([relation, input, edge_keep] + ([boundary] if boundary is not None else [])))
+        relation, mrel = as_mat(relation)
+        input, mx = as_mat(input)
+        out_c, mout = as_mat(out)
+        if out_c is not out:
+            raise RuntimeError("`out` must have unit stride along its last dimension")
+        mb = None
+        if boundary is not None:
+            boundary, mbv = as_mat(boundary)
+            mb = ctypes.byref(mbv)
+        return lib.ultra_rspmm_forward_masked_samples(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], dt, edge_keep.data_ptr(),
+                                                      edge_keep.stride(0), ctypes.byref(mrel), ctypes.byref(mx), mb,
+                                                      ctypes.byref(mout), _stream(input))
+
+    def _forward_samples(self, relation, input, edge_keep, boundary, sum, mul, out, point, keep):
+        """forward() with one keep mask per outer slice: `edge_keep` (n_outer, num_edge), 0/1, original edge order -- slice s
+        runs on the graph without the edges whose keep[s] is 0 (ultra_rspmm_forward_masked_samples).  Where the entry answers
+        ULTRA_ERR_UNSUPPORTED, one masked call per slice on views of the operands computes the same values."""
+        if not keep:
+            raise RuntimeError("a 2-D `edge_weight` is a per-sample keep mask: pass keep=True (per-sample weights are not served)")
+        if point is not None:
+            raise RuntimeError("per-sample keep masks take a dense boundary (or none), not a point boundary")
+        if relation.dim() != 3 or input.dim() != 3:
+            raise RuntimeError("per-sample keep masks need batch-major 3-D operands")
+        n_outer = input.shape[0]
+        if tuple(edge_keep.shape) != (n_outer, self.num_edge):
+            raise RuntimeError("Expected a per-sample `edge_weight` of shape (n_outer, num_edge) = (%d, %d), got %s"
+                               % (n_outer, self.num_edge, tuple(edge_keep.shape)))
+        if (edge_keep.stride(1) != 1 and self.num_edge > 1) or edge_keep.stride(0) < self.num_edge:      # (expanded rows too)
+            edge_keep = edge_keep.contiguous()
+        if out is None:
+            out = torch.empty((n_outer, self.num_node, input.shape[2]), dtype=input.dtype, device=input.device)
+        if n_outer == 0:
+            return out
+        rc = self.masked_samples_entry(relation, input, edge_keep, boundary, sum, mul, out)
+        if rc != _lib.ULTRA_ERR_UNSUPPORTED:
+            check(rc)
+            return out
+        for s in range(n_outer):
+            self.forward(relation[s:s + 1], input[s:s + 1], edge_weight=edge_keep[s],
+                         boundary=None if boundary is None else boundary[s:s + 1], sum=sum, mul=mul, out=out[s:s + 1],
+                         keep=True, weight_epoch=0)
         return out
 
     def forward_update(self, relation, input, weight, bias, ln_weight, ln_bias, eps, flags, mul="mul", point=None, timed=None,
