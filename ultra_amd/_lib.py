@@ -38,6 +38,9 @@ TOPK_MAX = 256               # ULTRA_TOPK_MAX
 TOPK_CHUNK = 4096            # ULTRA_TOPK_CHUNK
 ARR_DENSE = 7
 ARR_DENSE_ORDER = 8
+# the layer update's flag bits: ULTRA_CONV_* and, for ultra_nbf_layer0 alone, ULTRA_LAYER0_* (include/ultra_nbfnet.h)
+CONV_LAYER_NORM, CONV_RELU, CONV_RESIDUAL = 1, 2, 4
+LAYER0_MAX, LAYER0_ONLY_FILL, LAYER0_SKIP_FILL = 8, 16, 32
 
 
 class UltraMat(ctypes.Structure):
@@ -191,3 +194,22 @@ def check(rc):
     if rc == ULTRA_ERR_UNSORTED:
         raise AssertionError(msg)           # rspmm.py:18
     raise UltraError(msg)                    # c10::Error -> RuntimeError in the reference
+
+
+def stream_of(x):
+    """The current HIP stream of a tensor's device, or of a device (the C entry points make that device current for the launch)."""
+    return ctypes.c_void_p(torch.cuda.current_stream(x.device if isinstance(x, torch.Tensor) else x).cuda_stream)
+
+
+def ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def update_args(linear, layer_norm, relu, residual=False, extra_flags=0):
+    """(weight, bias, ln_weight, ln_bias, eps, flags) of the layer update `[x +] relu(layer_norm(linear(cat[x, agg])))` as
+    the entry points take it: None for an absent tensor, the default eps where there is no LayerNorm."""
+    ln = layer_norm
+    flags = (CONV_LAYER_NORM if ln is not None else 0) | (CONV_RELU if relu else 0) | (CONV_RESIDUAL if residual else 0) \
+        | extra_flags
+    return (linear.weight, linear.bias, ln.weight if ln is not None else None, ln.bias if ln is not None else None,
+            float(ln.eps) if ln is not None else 1e-5, flags)

@@ -8,16 +8,10 @@ from torch.autograd.function import once_differentiable
 from torch.nn import functional as F
 
 from . import _lib as _lib_codes
-from ._lib import check, lib
+from ._lib import CONV_LAYER_NORM, CONV_RELU, CONV_RESIDUAL, check, lib, ptr, stream_of  # noqa: F401 (CONV_*: aliases)
 
-CONV_LAYER_NORM, CONV_RELU, CONV_RESIDUAL = 1, 2, 4
 # the last layer's backward on the listed rows as gathers (A/B switch for tests: the scatter with float atomics is the other side)
 ROWS_BACKWARD_GATHER = True
-
-
-def _stream(t):
-    """The current HIP stream of the operand's device (the C entry points make that device current for the launch)."""
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def conv_update_supported(layer, input, update):
@@ -30,10 +24,6 @@ def conv_update_supported(layer, input, update):
             and (layer.layer_norm is None or (layer.layer_norm.elementwise_affine and layer.layer_norm.bias is not None)))
 
 
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
 def pick_rows(table, rows):
     """table[b, rows[b], :] for every b -- table[arange(batch), rows] as ONE gather launch (no arange; under autograd its backward
     is a zero fill + scatter_add of distinct rows, where advanced indexing's index_put_ sorts its indices first)."""
@@ -42,9 +32,26 @@ def pick_rows(table, rows):
 
 def _conv_update_forward(x, agg, weight, bias, ln_w, ln_b, eps, flags):
     out = torch.empty_like(x)
-    check(lib.ultra_conv_update(x.data_ptr(), agg.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(ln_w), _ptr(ln_b),
-                                out.data_ptr(), x.numel() // 64, 64, 64, eps, flags, _stream(x)))
+    check(lib.ultra_conv_update(x.data_ptr(), agg.data_ptr(), weight.data_ptr(), ptr(bias), ptr(ln_w), ptr(ln_b),
+                                out.data_ptr(), x.numel() // 64, 64, 64, eps, flags, stream_of(x)))
     return out
+
+
+def _conv_update_backward(x, agg, grad_out, weight, bias, ln_w, ln_b, eps, flags):
+    """The update's six gradients (x, agg, weight, bias, ln_w, ln_b; None for an absent parameter) from contiguous x, agg and
+    weight (ultra_conv_update_backward)."""
+    grad_out = grad_out.contiguous()
+    rows = x.numel() // 64
+    gx, gagg, gw = torch.empty_like(x), torch.empty_like(agg), torch.empty_like(weight)
+    gb = torch.empty_like(bias) if bias is not None else None
+    gln_w = torch.empty_like(ln_w) if ln_w is not None else None
+    gln_b = torch.empty_like(ln_b) if ln_b is not None else None
+    nbytes = lib.ultra_conv_update_backward_workspace(rows)
+    work = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    check(lib.ultra_conv_update_backward(x.data_ptr(), agg.data_ptr(), grad_out.data_ptr(), weight.data_ptr(), ptr(bias),
+                                         ptr(ln_w), ptr(ln_b), gx.data_ptr(), gagg.data_ptr(), gw.data_ptr(), ptr(gb),
+                                         ptr(gln_w), ptr(gln_b), work.data_ptr(), nbytes, rows, 64, 64, eps, flags, stream_of(x)))
+    return gx, gagg, gw, gb, gln_w, gln_b
 
 
 class ConvUpdateFunction(torch.autograd.Function):
@@ -63,19 +70,7 @@ class ConvUpdateFunction(torch.autograd.Function):
     @once_differentiable      # (the backward kernels are not themselves differentiable)
     def backward(ctx, grad_out):
         x, agg, weight, bias, ln_w, ln_b = ctx.saved_tensors
-        grad_out = grad_out.contiguous()
-        rows = x.numel() // 64
-        gx, gagg, gw = torch.empty_like(x), torch.empty_like(agg), torch.empty_like(weight)
-        gb = torch.empty_like(bias) if bias is not None else None
-        gln_w = torch.empty_like(ln_w) if ln_w is not None else None
-        gln_b = torch.empty_like(ln_b) if ln_b is not None else None
-        nbytes = lib.ultra_conv_update_backward_workspace(rows)
-        work = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
-        check(lib.ultra_conv_update_backward(x.data_ptr(), agg.data_ptr(), grad_out.data_ptr(), weight.data_ptr(), _ptr(bias),
-                                             _ptr(ln_w), _ptr(ln_b), gx.data_ptr(), gagg.data_ptr(), gw.data_ptr(), _ptr(gb),
-                                             _ptr(gln_w), _ptr(gln_b), work.data_ptr(), nbytes, rows, 64, 64, ctx.eps,
-                                             ctx.flags, _stream(x)))
-        return gx, gagg, gw, gb, gln_w, gln_b, None, None
+        return _conv_update_backward(x, agg, grad_out, weight, bias, ln_w, ln_b, ctx.eps, ctx.flags) + (None, None)
 
 
 class TrainLayerFunction(torch.autograd.Function):
@@ -104,18 +99,7 @@ class TrainLayerFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_out):
         edge_weight, relation, x, agg, weight, bias, ln_w, ln_b = ctx.saved_tensors
-        grad_out = grad_out.contiguous()
-        rows = x.numel() // 64
-        gx, gagg, gw = torch.empty_like(x), torch.empty_like(agg), torch.empty_like(weight)
-        gb = torch.empty_like(bias) if bias is not None else None
-        gln_w = torch.empty_like(ln_w) if ln_w is not None else None
-        gln_b = torch.empty_like(ln_b) if ln_b is not None else None
-        nbytes = lib.ultra_conv_update_backward_workspace(rows)
-        work = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
-        check(lib.ultra_conv_update_backward(x.data_ptr(), agg.data_ptr(), grad_out.data_ptr(), weight.data_ptr(), _ptr(bias),
-                                             _ptr(ln_w), _ptr(ln_b), gx.data_ptr(), gagg.data_ptr(), gw.data_ptr(), _ptr(gb),
-                                             _ptr(gln_w), _ptr(gln_b), work.data_ptr(), nbytes, rows, 64, 64, ctx.eps,
-                                             ctx.flags, _stream(x)))
+        gx, gagg, gw, gb, gln_w, gln_b = _conv_update_backward(x, agg, grad_out, weight, bias, ln_w, ln_b, ctx.eps, ctx.flags)
         need = ctx.needs_input_grad
         relation_grad, x_grad = None, gx
         if need[6] or need[7]:
@@ -150,17 +134,14 @@ class TrainRowsLayerFunction(torch.autograd.Function):
         bs, n_list = rows.shape
         relation_c, mrel = rspmm.as_mat(relation)
         _, mx = rspmm.as_mat(x)
-        mb = None
-        if boundary is not None:
-            boundary, mbv = rspmm.as_mat(boundary)
-            mb = ctypes.byref(mbv)
+        boundary, mb = rspmm._opt_mat(boundary)
         if point_values is not None:
             point_values = point_values.contiguous()
         agg = torch.empty(bs, n_list, 64, dtype=torch.float32, device=x.device)
-        w = edge_weight.contiguous() if edge_weight is not None else None
-        check(lib.ultra_rspmm_rows_forward(plan._h, rspmm._lib.MUL_CODES[mul], _ptr(w), ctypes.byref(mrel), ctypes.byref(mx),
-                                           rows.data_ptr(), n_list, mb, _ptr(point_rows), _ptr(point_values), agg.data_ptr(),
-                                           _stream(x)))
+        w, w_ptr, _ = rspmm._weight_operand(edge_weight, plan.num_edge)
+        check(lib.ultra_rspmm_rows_forward(plan._h, rspmm._lib.MUL_CODES[mul], w_ptr, ctypes.byref(mrel), ctypes.byref(mx),
+                                           rows.data_ptr(), n_list, mb, ptr(point_rows), ptr(point_values), agg.data_ptr(),
+                                           stream_of(x)))
         x_rows = x.gather(1, rows.unsqueeze(-1).expand(-1, -1, 64))
         ctx.plan, ctx.mul, ctx.eps, ctx.flags = plan, mul, eps, flags
         ctx.save_for_backward(w, relation_c, x, rows, x_rows, agg, point_rows, weight, bias, ln_w, ln_b)
@@ -171,18 +152,8 @@ class TrainRowsLayerFunction(torch.autograd.Function):
     def backward(ctx, grad_out):
         from . import rspmm
         w, relation, x, rows, x_rows, agg, point_rows, weight, bias, ln_w, ln_b = ctx.saved_tensors
-        grad_out = grad_out.contiguous()
-        n = x_rows.numel() // 64
-        gx_rows, gagg, gw = torch.empty_like(x_rows), torch.empty_like(agg), torch.empty_like(weight)
-        gb = torch.empty_like(bias) if bias is not None else None
-        gln_w = torch.empty_like(ln_w) if ln_w is not None else None
-        gln_b = torch.empty_like(ln_b) if ln_b is not None else None
-        nbytes = lib.ultra_conv_update_backward_workspace(n)
-        work = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
-        check(lib.ultra_conv_update_backward(x_rows.data_ptr(), agg.data_ptr(), grad_out.data_ptr(), weight.data_ptr(), _ptr(bias),
-                                             _ptr(ln_w), _ptr(ln_b), gx_rows.data_ptr(), gagg.data_ptr(), gw.data_ptr(), _ptr(gb),
-                                             _ptr(gln_w), _ptr(gln_b), work.data_ptr(), nbytes, n, 64, 64, ctx.eps,
-                                             ctx.flags, _stream(x)))
+        gx_rows, gagg, gw, gb, gln_w, gln_b = _conv_update_backward(x_rows, agg, grad_out, weight, bias, ln_w, ln_b, ctx.eps,
+                                                                    ctx.flags)
         need = ctx.needs_input_grad
         relation_grad = x_grad = values_grad = None
         want_values = point_rows is not None and need[10]
@@ -198,10 +169,10 @@ class TrainRowsLayerFunction(torch.autograd.Function):
                 _, mxg = rspmm.as_mat(x_grad)
                 if want_values:
                     values_grad = torch.empty(rows.shape[0], 64, dtype=torch.float32, device=x.device)
-                rc = lib.ultra_rspmm_rows_backward_gather(ctx.plan._h, rspmm._lib.MUL_CODES[ctx.mul], _ptr(w), ctypes.byref(mrel),
+                rc = lib.ultra_rspmm_rows_backward_gather(ctx.plan._h, rspmm._lib.MUL_CODES[ctx.mul], ptr(w), ctypes.byref(mrel),
                                                           ctypes.byref(mx), rows.data_ptr(), rows.shape[1], gagg.data_ptr(),
-                                                          gx_rows.data_ptr(), _ptr(point_rows) if want_values else None,
-                                                          _ptr(values_grad), ctypes.byref(mrg), ctypes.byref(mxg), _stream(x))
+                                                          gx_rows.data_ptr(), ptr(point_rows) if want_values else None,
+                                                          ptr(values_grad), ctypes.byref(mrg), ctypes.byref(mxg), stream_of(x))
                 if rc != _lib_codes.ULTRA_ERR_UNSUPPORTED:
                     check(rc)
             if rc == _lib_codes.ULTRA_ERR_UNSUPPORTED:
@@ -212,9 +183,9 @@ class TrainRowsLayerFunction(torch.autograd.Function):
                 relation_grad = torch.zeros(relation.shape, dtype=torch.float32, device=x.device)
                 _, mrg = rspmm.as_mat(relation_grad)
                 _, mxg = rspmm.as_mat(x_grad)
-                check(lib.ultra_rspmm_rows_backward(ctx.plan._h, rspmm._lib.MUL_CODES[ctx.mul], _ptr(w), ctypes.byref(mrel),
+                check(lib.ultra_rspmm_rows_backward(ctx.plan._h, rspmm._lib.MUL_CODES[ctx.mul], ptr(w), ctypes.byref(mrel),
                                                     ctypes.byref(mx), rows.data_ptr(), rows.shape[1], gagg.data_ptr(),
-                                                    ctypes.byref(mrg), ctypes.byref(mxg), _stream(x)))
+                                                    ctypes.byref(mrg), ctypes.byref(mxg), stream_of(x)))
         if want_values and values_grad is None:
             hit = (rows == point_rows.unsqueeze(1)).to(gagg.dtype).unsqueeze(-1)
             values_grad = (gagg * hit).sum(dim=1)
@@ -224,16 +195,10 @@ class TrainRowsLayerFunction(torch.autograd.Function):
 
 def conv_update(layer, input, update, residual):
     """out = [input +] relu(layer_norm(linear(cat[input, update]))) for (..., 64) fp32 GPU tensors."""
-    flags = (CONV_LAYER_NORM if layer.layer_norm is not None else 0) | (CONV_RELU if layer.activation is not None else 0) \
-        | (CONV_RESIDUAL if residual else 0)
-    ln = layer.layer_norm
-    eps = float(ln.eps) if ln is not None else 1e-5
-    args = (input, update, layer.linear.weight, layer.linear.bias, ln.weight if ln is not None else None,
-            ln.bias if ln is not None else None)
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in args):
-        return ConvUpdateFunction.apply(*args, eps, flags)
-    return _conv_update_forward(input.contiguous(), update.contiguous(), layer.linear.weight, layer.linear.bias, args[4],
-                                args[5], eps, flags)
+    args = (input, update) + layer.update_args(residual)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in args[:6]):
+        return ConvUpdateFunction.apply(*args)
+    return _conv_update_forward(input.contiguous(), update.contiguous(), *args[2:])
 
 
 EDGE_KEEP_MAX_EASY = 8192
@@ -254,8 +219,8 @@ def edge_keep_mask(edge_index, edge_type, easy_edge, num_node, num_relation, dty
         key = key * int(num_relation) + easy_edge[2]
     key = key.sort()[0].contiguous()
     keep = torch.empty(edge_index.shape[1], dtype=torch.float32, device=edge_index.device)
-    check(lib.ultra_edge_keep_mask(head.data_ptr(), tail.data_ptr(), _ptr(edge_type), edge_index.shape[1], key.data_ptr(),
-                                   key.numel(), int(num_node), int(num_relation), keep.data_ptr(), _stream(keep)))
+    check(lib.ultra_edge_keep_mask(head.data_ptr(), tail.data_ptr(), ptr(edge_type), edge_index.shape[1], key.data_ptr(),
+                                   key.numel(), int(num_node), int(num_relation), keep.data_ptr(), stream_of(keep)))
     return keep if dtype == torch.float32 else keep.to(dtype)
 
 
@@ -280,10 +245,10 @@ def easy_edge_keep(edge_index, edge_type, h_index, t_index, r_index, num_node, n
     if edge_type is not None:
         edge_type = edge_type.contiguous()
     keep = torch.empty(edge_index.shape[1], dtype=torch.float32, device=edge_index.device)
-    check(lib.ultra_easy_edge_keep(edge_index[0].data_ptr(), edge_index[1].data_ptr(), _ptr(edge_type), edge_index.shape[1],
+    check(lib.ultra_easy_edge_keep(edge_index[0].data_ptr(), edge_index[1].data_ptr(), ptr(edge_type), edge_index.shape[1],
                                    h_index.data_ptr(), t_index.data_ptr(), r_index.data_ptr() if edge_type is not None else None,
                                    n, stride, int(num_node), int(num_relation), int(num_relation) // 2, keep.data_ptr(),
-                                   _stream(keep)))
+                                   stream_of(keep)))
     return keep if dtype == torch.float32 else keep.to(dtype)
 
 
@@ -316,10 +281,10 @@ def leave_one_out_keep(edge_index, edge_type, h_index, t_index, r_index, num_nod
     if not (out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] >= n and out.shape[1] >= num_edge
             and (out.stride(1) == 1 or out.shape[1] <= 1) and out.device == edge_index.device):
         raise ValueError("leave_one_out_keep: `out` must be an (n, >= num_edge) fp32 buffer on the graph's device")
-    check(lib.ultra_leave_one_out_keep(edge_index[0].data_ptr(), edge_index[1].data_ptr(), _ptr(edge_type), num_edge,
+    check(lib.ultra_leave_one_out_keep(edge_index[0].data_ptr(), edge_index[1].data_ptr(), ptr(edge_type), num_edge,
                                        h_index.data_ptr(), t_index.data_ptr(), r_index.data_ptr() if edge_type is not None else None,
                                        n, stride, int(num_node), int(num_relation), int(num_relation) // 2, out.data_ptr(),
-                                       out.stride(0), _stream(out)))
+                                       out.stride(0), stream_of(out)))
     return out[:n, :num_edge]
 
 
@@ -347,11 +312,11 @@ def easy_edge_keep_table(edge_index, edge_type, h_index, t_index, r_index, num_n
         edge_type = edge_type.contiguous()
     table = torch.empty(int(lib.ultra_easy_edge_keep_table_workspace(n)), dtype=torch.uint8, device=edge_index.device)
     keep = torch.empty(edge_index.shape[1], dtype=torch.float32, device=edge_index.device)
-    check(lib.ultra_easy_edge_keep_table(edge_index[0].data_ptr(), edge_index[1].data_ptr(), _ptr(edge_type),
+    check(lib.ultra_easy_edge_keep_table(edge_index[0].data_ptr(), edge_index[1].data_ptr(), ptr(edge_type),
                                          edge_index.shape[1], h_index.data_ptr(), t_index.data_ptr(),
                                          r_index.data_ptr() if edge_type is not None else None, n, stride, int(num_node),
                                          int(num_relation), int(num_relation) // 2, table.data_ptr(), table.numel(),
-                                         keep.data_ptr(), _stream(keep)))
+                                         keep.data_ptr(), stream_of(keep)))
     return keep if dtype == torch.float32 else keep.to(dtype)
 
 
@@ -394,7 +359,7 @@ class ReadoutTrainFunction(torch.autograd.Function):
         h = torch.empty(bs * n, 128, dtype=torch.float32, device=hidden_rows.device)
         score = torch.empty(bs, n, dtype=torch.float32, device=hidden_rows.device)
         check(lib.ultra_readout_train_forward(hidden_rows.data_ptr(), query.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
-                                              b2.data_ptr(), h.data_ptr(), score.data_ptr(), bs, n, _stream(score)))
+                                              b2.data_ptr(), h.data_ptr(), score.data_ptr(), bs, n, stream_of(score)))
         ctx.save_for_backward(hidden_rows, query, w1, w2, h)
         return score
 
@@ -413,7 +378,7 @@ class ReadoutTrainFunction(torch.autograd.Function):
         check(lib.ultra_readout_train_backward(grad_score.data_ptr(), h.data_ptr(), hidden_rows.data_ptr(), query.data_ptr(),
                                                w1.data_ptr(), w2.data_ptr(), g_hid.data_ptr(), g_query.data_ptr(), g_w1.data_ptr(),
                                                g_b1.data_ptr(), g_w2.data_ptr(), g_b2.data_ptr(), work.data_ptr(), nbytes, bs, n,
-                                               _stream(g_hid)))
+                                               stream_of(g_hid)))
         return g_hid, g_query, g_w1, g_b1, g_w2, g_b2
 
 
@@ -450,7 +415,7 @@ def readout(model, hidden, query, t_index, order=None):
     score = torch.empty(batch, n_cand, dtype=hidden.dtype, device=hidden.device)
     check(lib.ultra_readout(hidden.data_ptr(), t_index.data_ptr(), mlp[0].weight.data_ptr(), query.data_ptr(),
                             mlp[0].bias.data_ptr(), mlp[2].weight.data_ptr(), mlp[2].bias.data_ptr(), order.data_ptr(),
-                            order.numel(), score.data_ptr(), batch, num_node, n_cand, 64, 128, _stream(hidden)))
+                            order.numel(), score.data_ptr(), batch, num_node, n_cand, 64, 128, stream_of(hidden)))
     return score
 
 
@@ -472,7 +437,7 @@ def batch_prologue(batch, num_direct_rel, candidates=False):
     side = torch.empty(bs, dtype=torch.int32, device=batch.device)
     valid = torch.empty(bs, dtype=torch.int32, device=batch.device)
     check(lib.ultra_batch_prologue_rows(batch.data_ptr(), bs, n_cand, int(num_direct_rel), h0.data_ptr(), r0.data_ptr(),
-                                        side.data_ptr(), valid.data_ptr(), rel_first.data_ptr(), _ptr(cand), _stream(batch)))
+                                        side.data_ptr(), valid.data_ptr(), rel_first.data_ptr(), ptr(cand), stream_of(batch)))
     out = Prologue((batch, h0, r0, side, valid))
     out.rel_first = rel_first
     out.cand = cand
@@ -491,7 +456,7 @@ def readout_batch(model, hidden, query, batch, side, order=None):
     check(lib.ultra_readout_batch(hidden.data_ptr(), batch.data_ptr(), side.data_ptr(), mlp[0].weight.data_ptr(),
                                   query.data_ptr(), mlp[0].bias.data_ptr(), mlp[2].weight.data_ptr(), mlp[2].bias.data_ptr(),
                                   order.data_ptr(), order.numel(), score.data_ptr(), bs, num_node, n_cand, 64, 128,
-                                  _stream(hidden)))
+                                  stream_of(hidden)))
     return score
 
 
@@ -506,8 +471,7 @@ def onehot_boundary(index, values, num_node, dim):
     out = torch.empty(batch, num_node, dim, dtype=torch.float32, device=index.device)
     index = index.to(torch.int64).contiguous()
     values = values.contiguous() if values is not None else None     # (kept referenced until the launch is enqueued)
-    check(lib.ultra_onehot_rows(out.data_ptr(), index.data_ptr(), values.data_ptr() if values is not None else None, batch,
-                                num_node, dim, _stream(out)))
+    check(lib.ultra_onehot_rows(out.data_ptr(), index.data_ptr(), ptr(values), batch, num_node, dim, stream_of(out)))
     return out
 
 
@@ -530,9 +494,9 @@ def query_boundary(h_index, relation_representations, r_index, num_node, readout
     # is enqueued: a temporary freed inside the argument list hands its memory to the next temporary
     rows = h_index.to(torch.int64).contiguous()
     pick = r_index.to(torch.int64).contiguous()
-    check(lib.ultra_query_boundary(boundary.data_ptr() if materialize else None, query.data_ptr(), rows.data_ptr(),
+    check(lib.ultra_query_boundary(ptr(boundary), query.data_ptr(), rows.data_ptr(),
                                    table.data_ptr(), pick.data_ptr(), bs, num_node, num_rel,
-                                   dim, w1, b1, qbias.data_ptr() if qbias is not None else None, _stream(table)))
+                                   dim, w1, b1, ptr(qbias), stream_of(table)))
     return boundary, query, qbias
 
 
@@ -555,7 +519,7 @@ class RelationProjectionFunction(torch.autograd.Function):
         w0, b0, w2, b2 = ([p.contiguous() for p in params[k::4]] for k in range(4))
         out = torch.empty((n_layer,) + tuple(xc.shape), dtype=torch.float32, device=xc.device)
         check(lib.ultra_relation_projection_layers(xc.data_ptr(), _ptr_array(w0), _ptr_array(b0), _ptr_array(w2), _ptr_array(b2),
-                                                   out.data_ptr(), rows, n_layer, 64, _stream(xc)))
+                                                   out.data_ptr(), rows, n_layer, 64, stream_of(xc)))
         ctx.save_for_backward(xc, *params)
         return tuple(out.unbind(0))
 
@@ -577,7 +541,7 @@ class RelationProjectionFunction(torch.autograd.Function):
         work = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
         check(lib.ultra_relation_projection_backward(xc.data_ptr(), _ptr_array(w0), _ptr_array(b0), _ptr_array(w2), _ptr_array(gout),
                                                      gx.data_ptr(), gw0.data_ptr(), gb0.data_ptr(), gw2.data_ptr(), gb2.data_ptr(),
-                                                     work.data_ptr(), nbytes, rows, n_layer, 64, _stream(xc)))
+                                                     work.data_ptr(), nbytes, rows, n_layer, 64, stream_of(xc)))
         grads = []
         for l in range(n_layer):
             grads += [gw0[l], gb0[l], gw2[l], gb2[l]]
@@ -597,5 +561,5 @@ def relation_projection(x, w0, b0, w2, b2):
     n_layer = w0.shape[0]
     out = torch.empty((n_layer,) + tuple(x.shape), dtype=torch.float32, device=x.device)
     check(lib.ultra_relation_projection(x.data_ptr(), w0.data_ptr(), b0.data_ptr(), w2.data_ptr(), b2.data_ptr(),
-                                        out.data_ptr(), rows, n_layer, 64, _stream(x)))
+                                        out.data_ptr(), rows, n_layer, 64, stream_of(x)))
     return out

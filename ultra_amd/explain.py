@@ -11,13 +11,12 @@ Semantics: the reference's with stable sorts and exact top-k key
 order-dependent -- its ties follow whatever its unstable sorts produce, and its scatter_topk merges values closer than
 about 4 (max - min) N 2^-23 -- so it is not a bit-exact target.
 """
-import ctypes
 from collections import OrderedDict, namedtuple
 
 import torch
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import check, lib, stream_of
 
 BeamCSR = namedtuple("BeamCSR", "row_ptr src type eid hub_rows num_hub num_node num_edge")
 
@@ -80,7 +79,7 @@ def beam_search_layer(csr, edge_grad, dist_in, tail, num_beam):
     edge_grad, dist_in = edge_grad.contiguous(), dist_in.contiguous()
     dist = torch.empty((csr.num_node, num_beam), dtype=torch.float32, device=dist_in.device)
     back = torch.empty((csr.num_node, num_beam, 4), dtype=torch.int64, device=dist_in.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dist_in.device).cuda_stream)
+    stream = stream_of(dist_in)
     check(lib.ultra_beam_search_layer(csr.row_ptr.data_ptr(), csr.src.data_ptr(), csr.type.data_ptr(), csr.eid.data_ptr(),
                                       csr.hub_rows.data_ptr() if csr.num_hub else None, csr.num_hub, csr.num_node,
                                       csr.num_edge, edge_grad.data_ptr(), dist_in.data_ptr(), tail, num_beam,
@@ -187,7 +186,7 @@ def beam_search_layer_batch(csr, edge_grad, dist_in, tails, num_beam, tails_chec
     back = torch.empty((num_sample, csr.num_node, num_beam, 4), dtype=torch.int64, device=dist_in.device)
     if num_sample == 0:
         return dist, back
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dist_in.device).cuda_stream)
+    stream = stream_of(dist_in)
     check(lib.ultra_beam_search_layer_batch(csr.row_ptr.data_ptr(), csr.src.data_ptr(), csr.type.data_ptr(), csr.eid.data_ptr(),
                                             csr.hub_rows.data_ptr() if csr.num_hub else None, csr.num_hub, csr.num_node,
                                             csr.num_edge, num_sample, edge_grad.data_ptr(), dist_in.data_ptr(),

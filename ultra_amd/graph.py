@@ -151,10 +151,8 @@ class GraphedForward(Capture):
         nbytes = batch.numel() * batch.element_size()
         if batch.is_cuda and batch.is_contiguous() and batch.dtype == self.static_batch.dtype and nbytes % 16 == 0 \
                 and batch.data_ptr() % 16 == 0 and self.static_batch.data_ptr() % 16 == 0:
-            import ctypes
-            from ._lib import check, lib
-            check(lib.ultra_stream_copy(self.static_batch.data_ptr(), batch.data_ptr(), nbytes,
-                                        ctypes.c_void_p(torch.cuda.current_stream(batch.device).cuda_stream)))
+            from ._lib import check, lib, stream_of
+            check(lib.ultra_stream_copy(self.static_batch.data_ptr(), batch.data_ptr(), nbytes, stream_of(batch)))
         else:
             self.static_batch.copy_(batch, non_blocking=True)
 
@@ -390,9 +388,8 @@ class GraphedEvalStep(Capture):
     come back in a static buffer.  No (bs, N, 3) candidate copy, no score clone, no per-batch sort / unique."""
 
     def __init__(self, model, data, batch_size, known_tail, known_head, warmup=2):
-        import ctypes
         from . import tasks
-        from ._lib import check, lib
+        from ._lib import check, lib, stream_of
         dev = data.edge_index.device
         Capture.__init__(self, dev)
         self.model, self.data, self.bs = model, data, batch_size
@@ -406,7 +403,7 @@ class GraphedEvalStep(Capture):
 
         def step():
             t_batch, h_batch = tasks.all_negative(data, self.batch)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = stream_of(dev)
             for cand, pos_col, ptr, index, lo in ((t_batch, 1, self.t_ptr, self.t_index, 0),
                                                    (h_batch, 0, self.h_ptr, self.h_index, batch_size)):
                 pred = model(data, cand).float().contiguous()

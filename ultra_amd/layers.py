@@ -15,7 +15,7 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
-from . import dense, rspmm
+from . import _lib, dense, rspmm
 
 
 # Layer 0 of every NBFNet reads the boundary condition itself: zero everywhere except the head row of each sample.
@@ -172,6 +172,10 @@ class GeneralizedRelationalConv(nn.Module):
         return self.propagate(input=input, relation=relation, boundary=boundary, edge_index=edge_index,
                               edge_type=edge_type, size=size, edge_weight=edge_weight, residual=residual,
                               onehot_rows=onehot_rows, edge_keep=edge_keep)
+
+    def update_args(self, residual=False):
+        """This layer's update as the engine's entry points take it: (weight, bias, ln_weight, ln_bias, eps, flags)."""
+        return _lib.update_args(self.linear, self.layer_norm, self.activation is not None, residual)
 
     def _relation_for(self, query, batch_size):
         if self.dependent:
@@ -356,11 +360,7 @@ class GeneralizedRelationalConv(nn.Module):
                 and not self._order_free(edge_index, num_node)):
             return None
         plan = rspmm.get_plan(edge_index, kwargs["edge_type"], num_node, relation.shape[1])
-        ln = self.layer_norm
-        flags = (dense.CONV_LAYER_NORM if ln is not None else 0) | (dense.CONV_RELU if self.activation is not None else 0) \
-            | (dense.CONV_RESIDUAL if residual else 0)
-        return plan.forward_update(relation, input, self.linear.weight, self.linear.bias, ln.weight if ln is not None else None,
-                                   ln.bias if ln is not None else None, float(ln.eps) if ln is not None else 1e-5, flags,
+        return plan.forward_update(relation, input, *self.update_args(residual),
                                    mul=self.message2mul[self.message_func], point=(boundary.rows, boundary.values),
                                    sum="add" if self.aggregate_func == "sum" else "max")
 
@@ -379,14 +379,12 @@ class GeneralizedRelationalConv(nn.Module):
                 and dense.conv_update_supported(self, input, input)):
             return None
         plan = rspmm.get_plan(edge_index, kwargs["edge_type"], num_node, relation.shape[1], exact_order=False)
-        ln = self.layer_norm
-        flags = (dense.CONV_LAYER_NORM if ln is not None else 0) | (dense.CONV_RELU if self.activation is not None else 0) \
-            | (dense.CONV_RESIDUAL if residual else 0)
+        weight, bias, ln_weight, ln_bias, eps, flags = self.update_args(residual)
         return dense.TrainLayerFunction.apply(
-            plan, self.message2mul[self.message_func], bool(edge_keep), float(ln.eps) if ln is not None else 1e-5, flags,
+            plan, self.message2mul[self.message_func], bool(edge_keep), eps, flags,
             edge_weight, relation, input, None if point is not None else boundary,
             point.rows if point is not None else None, point.values if point is not None else None,
-            self.linear.weight, self.linear.bias, ln.weight if ln is not None else None, ln.bias if ln is not None else None)
+            weight, bias, ln_weight, ln_bias)
 
     def training_rows_layer(self, input, query, boundary, edge_index, edge_type, num_node, rows, edge_weight=None, residual=False,
                             relation=None):
@@ -407,14 +405,11 @@ class GeneralizedRelationalConv(nn.Module):
                 and dense.conv_update_supported(self, input, input)):
             return None
         plan = rspmm.get_plan(edge_index, edge_type, num_node, relation.shape[1], exact_order=False)
-        ln = self.layer_norm
-        flags = (dense.CONV_LAYER_NORM if ln is not None else 0) | (dense.CONV_RELU if self.activation is not None else 0) \
-            | (dense.CONV_RESIDUAL if residual else 0)
+        weight, bias, ln_weight, ln_bias, eps, flags = self.update_args(residual)
         return dense.TrainRowsLayerFunction.apply(
-            plan, self.message2mul[self.message_func], float(ln.eps) if ln is not None else 1e-5, flags, edge_weight, relation, input,
+            plan, self.message2mul[self.message_func], eps, flags, edge_weight, relation, input,
             rows, None if point is not None else boundary, point.rows if point is not None else None,
-            point.values if point is not None else None, self.linear.weight, self.linear.bias,
-            ln.weight if ln is not None else None, ln.bias if ln is not None else None)
+            point.values if point is not None else None, weight, bias, ln_weight, ln_bias)
 
     # ---- RotatE through the engine, in the unfused path's direction ----
     def rotate_fused(self, input, relation, edge_weight=None):

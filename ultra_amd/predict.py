@@ -17,7 +17,6 @@ Order: score descending, equal scores by ascending id, every Na
 -- the stable descending torch.sort.  A filtered candidate is removed, not rescored: a genuine -inf score is a candidate
 like any other, ranked last.  Slots beyond count = min(k, N - |known|) hold id -1 and score -inf.
 """
-import ctypes
 
 import torch
 
@@ -44,10 +43,6 @@ def filtered_topk_reference(pred, k, ptr=None, index=None):
         scores[b, :m] = pred[b, cand[order]]
         count[b] = m
     return ids, scores, count
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _check_k(k):
@@ -78,7 +73,7 @@ def filtered_topk(pred, k, ptr=None, index=None):
     ws = torch.empty(max(1, _lib.lib.ultra_filtered_topk_workspace(batch, n, k) // 8), dtype=torch.long, device=dev)
     _lib.check(_lib.lib.ultra_filtered_topk(pred.data_ptr(), None if ptr is None else ptr.data_ptr(),
                                             None if ptr is None else index.data_ptr(), batch, n, k, ids.data_ptr(),
-                                            scores.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(dev)))
+                                            scores.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel() * 8, _lib.stream_of(dev)))
     return ids, scores, count
 
 
@@ -138,7 +133,7 @@ class _GraphedPredictStep(Capture):
             _lib.check(_lib.lib.ultra_filtered_topk(pred.data_ptr(), self.ptr.data_ptr() if self.filtered else None,
                                                     self.index.data_ptr() if self.filtered else None, batch_size, n, k,
                                                     self.ids.data_ptr(), self.scores.data_ptr(), self.count.data_ptr(),
-                                                    self.ws.data_ptr(), self.ws.numel() * 8, _stream(dev)))
+                                                    self.ws.data_ptr(), self.ws.numel() * 8, _lib.stream_of(dev)))
 
         self.warm_up(step, warmup)
         self.capture(step)
@@ -237,7 +232,7 @@ class _GraphedVerifyStep(Capture):
             pos = pos.contiguous()
             _lib.check(_lib.lib.ultra_filtered_rank(pred.data_ptr(), pos.data_ptr(), self.ptr.data_ptr(), self.index.data_ptr(),
                                                     batch_size, n, self.rank.data_ptr(), self.num_negative.data_ptr(),
-                                                    _stream(dev)))
+                                                    _lib.stream_of(dev)))
             self.score.copy_(pred.gather(1, pos.unsqueeze(-1)).squeeze(-1))
 
         self.warm_up(step, warmup)
@@ -424,7 +419,7 @@ class Predictor(object):
                 b_rank, b_neg = torch.empty_like(pos), torch.empty_like(pos)
                 _lib.check(_lib.lib.ultra_filtered_rank(pred.data_ptr(), pos.data_ptr(), b_ptr.data_ptr(), index.data_ptr(),
                                                         len(part), pred.shape[1], b_rank.data_ptr(), b_neg.data_ptr(),
-                                                        _stream(dev)))
+                                                        _lib.stream_of(dev)))
                 score[lo:lo + len(part)] = pred.gather(1, pos.unsqueeze(-1)).squeeze(-1)
                 rank[lo:lo + len(part)], num_negative[lo:lo + len(part)] = b_rank, b_neg
         finally:

@@ -6,13 +6,12 @@ batch_evaluate_reference, the torch restatement.  The order is the stable descen
 or p_u == p_v and u < v.  The reference sorts with an unstable argsort, so on tied scores its ranks
 follow whatever that sort returns.
 """
-import ctypes
 
 import torch
 
 from . import _lib
 from . import distributed as udist
-from ._lib import check, lib
+from ._lib import check, lib, ptr, stream_of
 
 
 def _answer_lists(easy_answer, hard_answer):
@@ -70,8 +69,8 @@ def batch_evaluate(pred, target, limit_nodes=None):
     ranking = torch.empty(total_hard, dtype=torch.int64, device=dev)
     pred_c = pred.contiguous()
     ent = ent.contiguous()
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    check(lib.ultra_answer_ranking(pred_c.data_ptr(), keep_u8.data_ptr() if keep_u8 is not None else None, ent.data_ptr(),
+    stream = stream_of(dev)
+    check(lib.ultra_answer_ranking(pred_c.data_ptr(), ptr(keep_u8), ent.data_ptr(),
                                    ans_ptr.data_ptr(), hard_ptr.data_ptr(), num_easy.data_ptr(), ws_off.data_ptr(),
                                    ws.data_ptr(), batch, num_entity, answer_ranking.data_ptr(), ranking.data_ptr(), stream))
     return ranking, answer_ranking

@@ -22,7 +22,6 @@ and the final symbolic sets.  It does NOT keep the interpreter's `var` / `symbol
 them) and it does not populate `model.stack` / `model.symbolic_stack`.  Training stays with the interpreter: its traversal
 dropout draws per projection.
 """
-import ctypes
 from collections import namedtuple
 
 import torch
@@ -232,17 +231,10 @@ def run_reference(program, logic, projection, symbolic=None, device=None):
     return results[0], (results[1] if symbolic is not None else None)
 
 
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def segment(words, offset, batch, num_nodes, logic, stack, push_src, pop_dst, sym_stack=None, sym_push_src=None,
             sym_pop_dst=None):
     """One launch of ultra_query_segment.  `words`: the int32 device tensor of Program.packed(), `offset` the segment's
     start in it; stack (batch, 2, N) fp32; push_src (rows, N) or None; pop_dst (rows, N) or None; the symbolic three alike."""
-    def ptr(t):
-        return None if t is None else t.data_ptr()
-
     def rows(t):
         return 0 if t is None else t.shape[0]
     for t in (stack, push_src, pop_dst, sym_stack, sym_push_src, sym_pop_dst):
@@ -254,8 +246,9 @@ def segment(words, offset, batch, num_nodes, logic, stack, push_src, pop_dst, sy
     total_ops_at = base + 4 * (3 * batch)
     _lib.check(_lib.lib.ultra_query_segment(
         base, base + 4 * batch, base + 8 * batch, total_ops_at, total_ops_at + 4 * (batch + 1), batch, num_nodes,
-        stack.shape[1] if stack.dim() == 3 else -1, dtype, LOGIC_CODES[logic], ptr(stack), ptr(push_src), rows(push_src),
-        ptr(pop_dst), rows(pop_dst), ptr(sym_stack), ptr(sym_push_src), ptr(sym_pop_dst), _stream(stack.device)))
+        stack.shape[1] if stack.dim() == 3 else -1, dtype, LOGIC_CODES[logic], _lib.ptr(stack), _lib.ptr(push_src),
+        rows(push_src), _lib.ptr(pop_dst), rows(pop_dst), _lib.ptr(sym_stack), _lib.ptr(sym_push_src), _lib.ptr(sym_pop_dst),
+        _lib.stream_of(stack)))
 
 
 def nonzero_lists(x):
@@ -271,7 +264,7 @@ def nonzero_lists(x):
     index = torch.empty(max(1, batch * n), dtype=torch.int64, device=x.device)
     counts = torch.empty(max(1, batch), dtype=torch.int64, device=x.device)
     _lib.check(_lib.lib.ultra_nonzero_lists(x.data_ptr(), batch, n, counts.data_ptr(), ptr.data_ptr(), index.data_ptr(),
-                                            batch * n, _stream(x.device)))
+                                            batch * n, _lib.stream_of(x)))
     return ptr, index
 
 

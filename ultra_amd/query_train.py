@@ -7,7 +7,6 @@ relation graph of the dropped graph becomes a 0/1 vector over the static relatio
 The query loss and its gradient are one launch (ultra_query_loss).  The loop follows run_query.py at world size 1.
 DESIGN.md section 10.4.
 """
-import ctypes
 import logging
 import math
 import os
@@ -16,17 +15,13 @@ from itertools import islice
 
 import torch
 
-from ._lib import check, lib
+from ._lib import check, lib, ptr, stream_of
 from .data import Data
 
 logger = logging.getLogger(__name__)
 
 _DEG_CACHE = OrderedDict()
 _DEG_CACHE_SIZE = 8
-
-
-def _stream(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def degrees(edge_index, num_node):
@@ -84,8 +79,8 @@ def traversal_dropout(edge_index, edge_type, num_node, num_relation, sym, r_inde
     check(lib.ultra_traversal_dropout(ei.data_ptr(), et.data_ptr(), num_edge, num_node, num_relation, int(bool(inverse_rel_plus_one)),
                                       deg_out.data_ptr(), deg_in.data_ptr(), r.data_ptr(), batch,
                                       0 if sym.dtype == torch.float32 else 1, sym.data_ptr(), q.data_ptr(), u1.data_ptr(),
-                                      u2.data_ptr() if u2 is not None else None, more, masks.data_ptr(), keep.data_ptr(),
-                                      k.data_ptr() if k is not None else None, _stream(keep)))
+                                      ptr(u2), more, masks.data_ptr(), keep.data_ptr(),
+                                      ptr(k), stream_of(keep)))
     return (keep, k) if return_k else keep
 
 
@@ -127,7 +122,7 @@ def relation_graph_bits_keep(graph, keep):
     adj = torch.zeros(4, r, w, dtype=torch.int32, device=dev)
     counts = torch.empty(4 * r, dtype=torch.int64, device=dev)
     check(lib.ultra_relation_graph_bits_keep(ei.data_ptr(), et.data_ptr(), keep.data_ptr(), ei.shape[1], n, r, hbits.data_ptr(),
-                                             tbits.data_ptr(), adj.data_ptr(), counts.data_ptr(), _stream(ei)))
+                                             tbits.data_ptr(), adj.data_ptr(), counts.data_ptr(), stream_of(ei)))
     return adj, counts
 
 
@@ -139,7 +134,7 @@ def relation_graph_keep(graph, keep):
     rei, ret = rg.edge_index.to(torch.int64).contiguous(), rg.edge_type.to(torch.int64).contiguous()
     out = torch.empty(rei.shape[1], dtype=torch.float32, device=rei.device)
     check(lib.ultra_relation_graph_edge_keep(adj.data_ptr(), int(graph.num_relations), rei.data_ptr(), ret.data_ptr(), rei.shape[1],
-                                             out.data_ptr(), _stream(out)))
+                                             out.data_ptr(), stream_of(out)))
     return out
 
 
@@ -154,7 +149,7 @@ def build_dropped_relation_graph(graph, keep):
     edge_index = torch.empty(2, total, dtype=torch.int64, device=dev)
     edge_type = torch.empty(total, dtype=torch.int64, device=dev)
     check(lib.ultra_relation_graph_emit(adj.data_ptr(), offsets.data_ptr(), r, total, edge_index.data_ptr(), edge_type.data_ptr(),
-                                        _stream(adj)))
+                                        stream_of(adj)))
     return Data(edge_index=edge_index, edge_type=edge_type, num_nodes=r, num_relations=4)
 
 
@@ -169,7 +164,7 @@ class _QueryLoss(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=p.device)
         grad = torch.empty_like(p)
         check(lib.ultra_query_loss(p.data_ptr(), t.data_ptr(), rows, n, float(temperature), work.data_ptr(), loss.data_ptr(),
-                                   grad.data_ptr(), _stream(p)))
+                                   grad.data_ptr(), stream_of(p)))
         ctx.save_for_backward(grad)
         return loss
 

@@ -20,13 +20,13 @@ engine has no CPU path (the reference's `rspmm_*_cpu` names exist only to say so
 """
 import ctypes
 import sys
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import torch
 from torch import autograd
 
 from . import _lib
-from ._lib import UltraMat, check, lib
+from ._lib import UltraMat, check, lib, ptr, stream_of
 
 module = sys.modules[__name__]
 
@@ -58,15 +58,6 @@ def _announce_weight(edge_weight, epoch=None):
         lib.ultra_rspmm_weight_epoch(int(_weight_epoch(edge_weight) if epoch is None else epoch))
 
 
-def _stream(t):
-    """The current HIP stream of the operand's device (the C entry points make that device current for the launch)."""
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
 def _require_gpu(*tensors):
     for t in tensors:
         if t is not None and t.device.type != "cuda":
@@ -96,6 +87,55 @@ def as_mat(t):
             t = t.contiguous()
         return t, UltraMat(t.data_ptr(), t.shape[0], t.stride(0), t.shape[1], t.stride(1), t.shape[2])
     raise RuntimeError("Expected a 2-dimensional (or batch-major 3-dimensional) tensor, got %d dims" % t.dim())
+
+
+def _opt_mat(t):
+    """An optional matrix operand: (the tensor as_mat describes -- hold it until the launch is enqueued --, byref of its
+    UltraMat), or (None, None)."""
+    if t is None:
+        return None, None
+    t, m = as_mat(t)
+    return t, ctypes.byref(m)
+
+
+def _point_operand(point, input):
+    """The point boundary (rows, values) of a 2-D or batch-major 3-D `input` as the entry points take it: (int64 rows, values
+    as one row per outer slice, the rows' pointer, byref of the values' UltraMat).  The caller holds the two tensors (and
+    checks their device)."""
+    rows, vals = point
+    n_outer = 1 if input.dim() == 2 else input.shape[0]
+    rows = rows.to(torch.int64).contiguous()
+    if rows.numel() != n_outer:
+        raise RuntimeError("Expected one boundary row per outer slice (%d), got %d" % (n_outer, rows.numel()))
+    vals, mv = as_mat(vals.reshape(n_outer, 1, vals.shape[-1]) if input.dim() == 3 else vals.reshape(1, vals.shape[-1]))
+    return rows, vals, rows.data_ptr(), ctypes.byref(mv)
+
+
+def _weight_operand(edge_weight, num_edge, weight_epoch=None):
+    """The edge-weight operand: (the contiguous vector, its pointer, its epoch -- the caller's, else the tag of a vector
+    that is passed on as it is, else 0), or (None, None, weight_epoch)."""
+    if edge_weight is None:
+        return None, None, weight_epoch
+    if edge_weight.dim() != 1 or edge_weight.shape[0] != num_edge:
+        raise RuntimeError("Expected `edge_weight` of shape (num_edge,)")
+    if weight_epoch is None:
+        weight_epoch = _weight_epoch(edge_weight) if edge_weight.is_contiguous() else 0
+    edge_weight = edge_weight.contiguous()
+    return edge_weight, edge_weight.data_ptr(), weight_epoch
+
+
+def _out_like(input, num_node):
+    """A fresh output of `num_node` rows, shaped like the input otherwise."""
+    shape = list(input.shape)
+    shape[-2] = num_node
+    return torch.empty(shape, dtype=input.dtype, device=input.device)
+
+
+# A forward launch's operands as the entry points take them: the dtype code, the edge-weight pointer (or None) and its epoch,
+# byrefs of relation and input, the boundary's byref (the point's values where a point is given, else the dense boundary or
+# None), the point's rows pointer (or None), the output and its byref, and `held`: the tensors behind the pointers, which
+# live as long as this tuple -- keep it until the launch is enqueued.
+_ForwardOperands = namedtuple("_ForwardOperands", "dtype weight epoch relation input boundary rows out out_ref held")
 
 
 class Plan(object):
@@ -202,47 +242,32 @@ class Plan(object):
         check(lib.ultra_plan_schedule_info(self._h, int(nparts), ctypes.byref(info)))
         return {name: getattr(info, name) for name, _ in _lib.ScheduleInfo._fields_ if name != "reserved"}
 
+    def _export(self, fn, *key):
+        """One array of the plan as an int32 host tensor: ask `fn` for the count, allocate, call again."""
+        n = ctypes.c_int64()
+        check(fn(self._h, *key, None, 0, ctypes.byref(n)))
+        out = torch.empty(n.value, dtype=torch.int32)
+        check(fn(self._h, *key, out.data_ptr(), n.value, ctypes.byref(n)))
+        return out
+
     def schedule(self, nparts):
         """(chunk_ptr, unit_ptr, units, chunks[n, 4]) of the static schedule for `nparts` workgroups per span."""
-        out = []
-        for which in range(4):
-            n = ctypes.c_int64()
-            check(lib.ultra_plan_schedule_export(self._h, int(nparts), which, None, 0, ctypes.byref(n)))
-            t = torch.empty(n.value, dtype=torch.int32)
-            check(lib.ultra_plan_schedule_export(self._h, int(nparts), which, t.data_ptr(), n.value, ctypes.byref(n)))
-            out.append(t.view(-1, 4) if which == 3 else t)
-        return tuple(out)
+        out = [self._export(lib.ultra_plan_schedule_export, int(nparts), which) for which in range(4)]
+        return tuple(out[:3]) + (out[3].view(-1, 4),)
 
     def streams(self, nparts, walkers=16):
         """(sdesc[nparts * 64, 2] = {first record, steps}, srec[n, 2] = (col, type) records, markers (row, num_relation)).
         walkers=12: the schedule of the launches whose last four waves apply the layer update beside the walk."""
-        out = []
         nparts = int(nparts) | ((1 << 24) if walkers == 12 else 0)
-        for which in (4, 5):
-            n = ctypes.c_int64()
-            check(lib.ultra_plan_schedule_export(self._h, nparts, which, None, 0, ctypes.byref(n)))
-            t = torch.empty(n.value, dtype=torch.int32)
-            check(lib.ultra_plan_schedule_export(self._h, nparts, which, t.data_ptr(), n.value, ctypes.byref(n)))
-            out.append(t.view(-1, 2))
-        return tuple(out)
+        return tuple(self._export(lib.ultra_plan_schedule_export, nparts, which).view(-1, 2) for which in (4, 5))
 
     def part_rows(self, nparts):
         """(prow, prow_ptr): the rows each workgroup aggregates -- ascending, -1 padded to whole 32-row tiles -- and their
         bounds per workgroup (schedule arrays 6 and 7: the work list of the update tail)."""
-        out = []
-        for which in (6, 7):
-            n = ctypes.c_int64()
-            check(lib.ultra_plan_schedule_export(self._h, int(nparts), which, None, 0, ctypes.byref(n)))
-            t = torch.empty(n.value, dtype=torch.int32)
-            check(lib.ultra_plan_schedule_export(self._h, int(nparts), which, t.data_ptr(), n.value, ctypes.byref(n)))
-            out.append(t)
-        return tuple(out)
+        return tuple(self._export(lib.ultra_plan_schedule_export, int(nparts), which) for which in (6, 7))
 
     def export(self, which):
-        n = ctypes.c_int64()
-        check(lib.ultra_plan_export(self._h, which, None, 0, ctypes.byref(n)))
-        out = torch.empty(n.value, dtype=torch.int32)
-        check(lib.ultra_plan_export(self._h, which, out.data_ptr(), n.value, ctypes.byref(n)))
+        out = self._export(lib.ultra_plan_export, which)
         return out.view(torch.uint8) if which in (_lib.ARR_DENSE, _lib.ARR_DENSE_ORDER) else out
 
     # ---- kernels ----
@@ -267,6 +292,22 @@ class Plan(object):
         if twin is not None:
             return twin.forward(relation, input, edge_weight=edge_weight, boundary=boundary, sum=sum, mul=mul, out=out,
                                 point=point, keep=keep, weight_epoch=weight_epoch)
+        op = self._forward_operands(relation, input, edge_weight, boundary, out, point, weight_epoch)
+        _announce_weight(edge_weight, op.epoch)
+        if point is not None:
+            rc = lib.ultra_rspmm_forward_point(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], op.dtype, op.weight, op.relation,
+                                               op.input, op.rows, op.boundary, op.out_ref, stream_of(input))
+            if rc == _lib.ULTRA_ERR_UNSUPPORTED and sum != "add":
+                return None      # (min / max: the caller passes the boundary as a tensor)
+            check(rc)
+            return op.out
+        entry = lib.ultra_rspmm_forward_masked if (keep and op.weight is not None and sum != "add") else lib.ultra_rspmm_forward
+        check(entry(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], op.dtype, op.weight, op.relation, op.input, op.boundary,
+                    op.out_ref, stream_of(input)))
+        return op.out
+
+    def _forward_operands(self, relation, input, edge_weight, boundary, out, point, weight_epoch=None):
+        """The operands of a forward launch, checked and described to the C ABI (_ForwardOperands)."""
         _require_gpu(relation, input, edge_weight, boundary)
         dt = _dtype_code(*([relation, input] + ([edge_weight] if edge_weight is not None else [])
                            + ([boundary] if boundary is not None else [])))
@@ -275,43 +316,17 @@ class Plan(object):
         if relation.dim() != input.dim():
             raise RuntimeError("relation and input must both be 2-D or both batch-major 3-D")
         if out is None:
-            shape = list(input.shape)
-            shape[-2] = self.num_node
-            out = torch.empty(shape, dtype=input.dtype, device=input.device)
+            out = _out_like(input, self.num_node)
         out, mout = as_mat(out)
-        mb = None
-        if boundary is not None:
-            boundary, mbv = as_mat(boundary)
-            mb = ctypes.byref(mbv)
-        w = None
-        if edge_weight is not None:
-            if edge_weight.dim() != 1 or edge_weight.shape[0] != self.num_edge:
-                raise RuntimeError("Expected `edge_weight` of shape (num_edge,)")
-            if weight_epoch is None:
-                weight_epoch = _weight_epoch(edge_weight) if edge_weight.is_contiguous() else 0
-            edge_weight = edge_weight.contiguous()
-            w = edge_weight.data_ptr()
+        if point is None:
+            boundary, mb = _opt_mat(boundary)
+        edge_weight, w, weight_epoch = _weight_operand(edge_weight, self.num_edge, weight_epoch)
+        rows = rows_ptr = None
         if point is not None:
-            rows, vals = point
-            n_outer = 1 if input.dim() == 2 else input.shape[0]
-            rows = rows.to(torch.int64).contiguous()
-            vals = vals.reshape(n_outer, 1, vals.shape[-1]) if input.dim() == 3 else vals.reshape(1, vals.shape[-1])
-            if rows.numel() != n_outer:
-                raise RuntimeError("Expected one boundary row per outer slice (%d), got %d" % (n_outer, rows.numel()))
-            _require_gpu(rows, vals)
-            vals, mv = as_mat(vals)
-            _announce_weight(edge_weight, weight_epoch)
-            rc = lib.ultra_rspmm_forward_point(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], dt, w, ctypes.byref(mrel),
-                                               ctypes.byref(mx), rows.data_ptr(), ctypes.byref(mv), ctypes.byref(mout), _stream(input))
-            if rc == _lib.ULTRA_ERR_UNSUPPORTED and sum != "add":
-                return None      # (min / max: the caller passes the boundary as a tensor)
-            check(rc)
-            return out
-        entry = lib.ultra_rspmm_forward_masked if (keep and w is not None and sum != "add") else lib.ultra_rspmm_forward
-        _announce_weight(edge_weight, weight_epoch)
-        check(entry(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], dt, w, ctypes.byref(mrel),
-                    ctypes.byref(mx), mb, ctypes.byref(mout), _stream(input)))
-        return out
+            rows, boundary, rows_ptr, mb = _point_operand(point, input)
+            _require_gpu(rows, boundary)
+        return _ForwardOperands(dt, w, weight_epoch, ctypes.byref(mrel), ctypes.byref(mx), mb, rows_ptr, out, ctypes.byref(mout),
+                                (relation, input, edge_weight, boundary, rows))
 
     def masked_samples_entry(self, relation, input, edge_keep, boundary, sum, mul, out):
         """ultra_rspmm_forward_masked_samples on batch-major 3-D operands; returns the entry's status code (ULTRA_ERR_UNSUPPORTED:
@@ -323,13 +338,10 @@ class Plan(object):
         out_c, mout = as_mat(out)
         if out_c is not out:
             raise RuntimeError("`out` must have unit stride along its last dimension")
-        mb = None
-        if boundary is not None:
-            boundary, mbv = as_mat(boundary)
-            mb = ctypes.byref(mbv)
+        boundary, mb = _opt_mat(boundary)
         return lib.ultra_rspmm_forward_masked_samples(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], dt, edge_keep.data_ptr(),
                                                       edge_keep.stride(0), ctypes.byref(mrel), ctypes.byref(mx), mb,
-                                                      ctypes.byref(mout), _stream(input))
+                                                      ctypes.byref(mout), stream_of(input))
 
     def _forward_samples(self, relation, input, edge_keep, boundary, sum, mul, out, point, keep):
         """forward() with one keep mask per outer slice: `edge_keep` (n_outer, num_edge), 0/1, original edge order -- slice s
@@ -380,18 +392,12 @@ class Plan(object):
         out, mout = as_mat(out)
         rows_ptr, mv = None, None
         if point is not None:
-            rows, vals = point
-            rows = rows.to(torch.int64).contiguous()
-            if rows.numel() != input.shape[0]:
-                raise RuntimeError("Expected one boundary row per outer slice (%d), got %d" % (input.shape[0], rows.numel()))
-            vals = vals.reshape(input.shape[0], 1, vals.shape[-1])
+            rows, vals, rows_ptr, mv = _point_operand(point, input)
             _require_gpu(rows, vals)
-            vals, mvv = as_mat(vals)
-            rows_ptr, mv = rows.data_ptr(), ctypes.byref(mvv)
         weight = weight.contiguous()
         args = (self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], ctypes.byref(mrel), ctypes.byref(mx), rows_ptr, mv, ctypes.byref(magg),
-                weight.data_ptr(),
-                _ptr(bias), _ptr(ln_weight), _ptr(ln_bias), float(eps), int(flags), ctypes.byref(mout), _stream(input))
+                weight.data_ptr(), ptr(bias), ptr(ln_weight), ptr(ln_bias), float(eps), int(flags), ctypes.byref(mout),
+                stream_of(input))
         if timed is not None:
             ms, ms_kernel = ctypes.c_float(), ctypes.c_float()
             rc = lib.ultra_rspmm_forward_update_timed(*(args + (int(timed[0]), int(timed[1]), ctypes.byref(ms), ctypes.byref(ms_kernel))))
@@ -414,24 +420,15 @@ class Plan(object):
                            + ([boundary] if boundary is not None else [])))
         relation, mrel = as_mat(relation)
         input, mx = as_mat(input)
-        shape = list(input.shape)
-        shape[-2] = self.num_node
-        out = torch.empty(shape, dtype=input.dtype, device=input.device)
-        out, mout = as_mat(out)
+        out, mout = as_mat(_out_like(input, self.num_node))
         n_outer = 1 if input.dim() == 2 else input.shape[0]
         src_rows = src_rows.to(torch.int64).contiguous()
         if src_rows.numel() != n_outer:
             raise RuntimeError("Expected one source row per outer slice (%d), got %d" % (n_outer, src_rows.numel()))
-        mb = None
-        if boundary is not None:
-            boundary, mbv = as_mat(boundary)
-            mb = ctypes.byref(mbv)
-        w = None
-        if edge_weight is not None:
-            edge_weight = edge_weight.contiguous()
-            w = edge_weight.data_ptr()
+        boundary, mb = _opt_mat(boundary)
+        edge_weight, w, _ = _weight_operand(edge_weight, self.num_edge)
         check(lib.ultra_rspmm_forward_onehot(self._h, dt, w, ctypes.byref(mrel), ctypes.byref(mx), src_rows.data_ptr(), mb,
-                                             ctypes.byref(mout), _stream(input)))
+                                             ctypes.byref(mout), stream_of(input)))
         return out
 
     def fused_layer(self, relation, input, linear, layer_norm=None, relu=True, residual=False, boundary=None, point=None):
@@ -450,23 +447,16 @@ class Plan(object):
         input, mx = as_mat(input)
         out = torch.empty_like(input)
         _, mout = as_mat(out)
-        mb, rows_ptr = None, None
+        rows = vals = rows_ptr = None
         if point is not None:
-            rows, vals = point
-            rows = rows.to(torch.int64).contiguous()
-            vals, mbv = as_mat(vals.reshape(input.shape[0], 1, 64))
-            mb, rows_ptr = ctypes.byref(mbv), rows.data_ptr()
-        elif boundary is not None:
-            boundary, mbv = as_mat(boundary)
-            mb = ctypes.byref(mbv)
-        flags = (1 if layer_norm is not None else 0) | (2 if relu else 0) | (4 if residual else 0) \
-            | (_lib.LAYER_REFERENCE_ORDER if self.exact else 0)
-        check(lib.ultra_nbf_dense_layer(d._h, ctypes.byref(mrel), ctypes.byref(mx), mb, rows_ptr, linear.weight.data_ptr(),
-                                        linear.bias.data_ptr() if linear.bias is not None else None,
-                                        layer_norm.weight.data_ptr() if layer_norm is not None else None,
-                                        layer_norm.bias.data_ptr() if layer_norm is not None else None,
-                                        float(layer_norm.eps) if layer_norm is not None else 1e-5, flags, ctypes.byref(mout),
-                                        _stream(input)))
+            rows, vals, rows_ptr, mb = _point_operand(point, input)
+        else:
+            boundary, mb = _opt_mat(boundary)
+        _require_gpu(relation, input, boundary, rows, vals)
+        weight, bias, ln_weight, ln_bias, eps, flags = _lib.update_args(
+            linear, layer_norm, relu, residual, _lib.LAYER_REFERENCE_ORDER if self.exact else 0)
+        check(lib.ultra_nbf_dense_layer(d._h, ctypes.byref(mrel), ctypes.byref(mx), mb, rows_ptr, weight.data_ptr(), ptr(bias),
+                                        ptr(ln_weight), ptr(ln_bias), eps, flags, ctypes.byref(mout), stream_of(input)))
         return out
 
     def layer0_fill(self, batch_size, linear, layer_norm=None, relu=True, device=None):
@@ -476,13 +466,10 @@ class Plan(object):
         device = device if device is not None else linear.weight.device
         out = torch.empty(batch_size, self.num_node, 64, dtype=torch.float32, device=device)
         _, mout = as_mat(out)
-        flags = (1 if layer_norm is not None else 0) | (2 if relu else 0) | 16
-        check(lib.ultra_nbf_layer0(self._h, None, None, None, None, linear.weight.data_ptr(),
-                                   linear.bias.data_ptr() if linear.bias is not None else None,
-                                   layer_norm.weight.data_ptr() if layer_norm is not None else None,
-                                   layer_norm.bias.data_ptr() if layer_norm is not None else None,
-                                   float(layer_norm.eps) if layer_norm is not None else 1e-5, flags, ctypes.byref(mout),
-                                   _stream(out)))
+        weight, bias, ln_weight, ln_bias, eps, flags = _lib.update_args(linear, layer_norm, relu,
+                                                                        extra_flags=_lib.LAYER0_ONLY_FILL)
+        check(lib.ultra_nbf_layer0(self._h, None, None, None, None, weight.data_ptr(), ptr(bias), ptr(ln_weight), ptr(ln_bias),
+                                   eps, flags, ctypes.byref(mout), stream_of(out)))
         return out
 
     def layer0(self, relation, src_rows, src_values, linear, layer_norm=None, relu=True, residual=False, edge_weight=None,
@@ -504,15 +491,12 @@ class Plan(object):
             src_values = src_values.contiguous()
         if edge_weight is not None:
             edge_weight = edge_weight.to(torch.float32).contiguous()
-        flags = (1 if layer_norm is not None else 0) | (2 if relu else 0) | (4 if residual else 0) | (8 if aggregate == "max" else 0) \
-            | (32 if prefilled else 0)
-        check(lib.ultra_nbf_layer0(self._h, edge_weight.data_ptr() if edge_weight is not None else None, ctypes.byref(mrel),
-                                   src_rows.data_ptr(), src_values.data_ptr() if src_values is not None else None,
-                                   linear.weight.data_ptr(), linear.bias.data_ptr() if linear.bias is not None else None,
-                                   layer_norm.weight.data_ptr() if layer_norm is not None else None,
-                                   layer_norm.bias.data_ptr() if layer_norm is not None else None,
-                                   float(layer_norm.eps) if layer_norm is not None else 1e-5, flags, ctypes.byref(mout),
-                                   _stream(relation)))
+        weight, bias, ln_weight, ln_bias, eps, flags = _lib.update_args(
+            linear, layer_norm, relu, residual,
+            (_lib.LAYER0_MAX if aggregate == "max" else 0) | (_lib.LAYER0_SKIP_FILL if prefilled else 0))
+        check(lib.ultra_nbf_layer0(self._h, ptr(edge_weight), ctypes.byref(mrel), src_rows.data_ptr(), ptr(src_values),
+                                   weight.data_ptr(), ptr(bias), ptr(ln_weight), ptr(ln_bias), eps, flags, ctypes.byref(mout),
+                                   stream_of(relation)))
         return out
 
     def backward(self, relation, input, output, output_grad, edge_weight=None, need_weight_grad=False, sum="add",
@@ -542,7 +526,7 @@ class Plan(object):
             # with output_grad (ultra_rspmm_dense_relation_grad) -- 15 us where the walk over the relation-major plan took 71 + 12
             if xgrad is not None and not need_weight_grad and DENSE_RELATION_GRAD:
                 rc = lib.ultra_rspmm_dense_relation_grad(self.dense._h, ctypes.byref(mx), ctypes.byref(mog), ctypes.byref(mrg),
-                                                         _stream(input))
+                                                         stream_of(input))
                 if rc == _lib.ULTRA_OK:
                     return None, rgrad, xgrad
                 if rc != _lib.ULTRA_ERR_UNSUPPORTED:
@@ -557,12 +541,7 @@ class Plan(object):
             else:
                 xgrad = torch.empty(input.shape, dtype=input.dtype, device=input.device)
             _, mxg = as_mat(xgrad)
-        w = None
-        if edge_weight is not None:
-            if weight_epoch is None:
-                weight_epoch = _weight_epoch(edge_weight) if edge_weight.is_contiguous() else 0
-            edge_weight = edge_weight.contiguous()
-            w = edge_weight.data_ptr()
+        edge_weight, w, weight_epoch = _weight_operand(edge_weight, self.num_edge, weight_epoch)
         wgrad = None
         wg = None
         if need_weight_grad:
@@ -572,11 +551,11 @@ class Plan(object):
         if base is not None:      # (in place: every row's base is read by the thread that writes its total)
             check(lib.ultra_rspmm_backward_add(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], dt, w, ctypes.byref(mrel),
                                                ctypes.byref(mx), ctypes.byref(mo), ctypes.byref(mog), wg, ctypes.byref(mrg),
-                                               ctypes.byref(mxg), ctypes.byref(mxg), _stream(input)))
+                                               ctypes.byref(mxg), ctypes.byref(mxg), stream_of(input)))
         else:
             check(lib.ultra_rspmm_backward(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], dt, w, ctypes.byref(mrel),
                                            ctypes.byref(mx), ctypes.byref(mo), ctypes.byref(mog), wg, ctypes.byref(mrg),
-                                           ctypes.byref(mxg) if mxg is not None else None, _stream(input)))
+                                           ctypes.byref(mxg) if mxg is not None else None, stream_of(input)))
         if keep and wgrad is not None and edge_weight is not None:
             wgrad = wgrad * (edge_weight != 0).to(wgrad.dtype)
         return wgrad, rgrad, xgrad
@@ -613,7 +592,7 @@ class Plan(object):
         output_grad, mog = as_mat(output_grad)
         rc = lib.ultra_rspmm_edge_grad_samples(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], _lib.F32, ctypes.byref(mrel),
                                                ctypes.byref(mx), ctypes.byref(mog), wgrad.data_ptr(), self.num_edge,
-                                               _stream(input))
+                                               stream_of(input))
         if rc == _lib.ULTRA_ERR_UNSUPPORTED:
             return None
         check(rc)
@@ -628,31 +607,13 @@ class Plan(object):
                                      mul=mul, warmup=warmup, iters=iters, point=point)
             self.last_main_kernel_ms = twin.last_main_kernel_ms
             return res
-        dt = _dtype_code(relation, input)
-        relation, mrel = as_mat(relation)
-        input, mx = as_mat(input)
-        shape = list(input.shape)
-        shape[-2] = self.num_node
-        out = torch.empty(shape, dtype=input.dtype, device=input.device)
-        out, mout = as_mat(out)
-        mb, rows_ptr = None, None
-        if point is not None:
-            rows, vals = point
-            rows = rows.to(torch.int64).contiguous()
-            n_outer = 1 if input.dim() == 2 else input.shape[0]
-            vals, mbv = as_mat(vals.reshape(n_outer, 1, vals.shape[-1]) if input.dim() == 3 else vals.reshape(1, vals.shape[-1]))
-            mb, rows_ptr = ctypes.byref(mbv), rows.data_ptr()
-        elif boundary is not None:
-            boundary, mbv = as_mat(boundary)
-            mb = ctypes.byref(mbv)
-        edge_weight = edge_weight.contiguous() if edge_weight is not None else None
-        w = edge_weight.data_ptr() if edge_weight is not None else None
+        op = self._forward_operands(relation, input, edge_weight, boundary, None, point)
         ms, ms_kernel = ctypes.c_float(), ctypes.c_float()
-        check(lib.ultra_rspmm_forward_timed(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], dt, w, ctypes.byref(mrel),
-                                            ctypes.byref(mx), mb, rows_ptr, ctypes.byref(mout), _stream(input), warmup, iters,
+        check(lib.ultra_rspmm_forward_timed(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], op.dtype, op.weight, op.relation,
+                                            op.input, op.boundary, op.rows, op.out_ref, stream_of(input), warmup, iters,
                                             ctypes.byref(ms), ctypes.byref(ms_kernel)))
         self.last_main_kernel_ms = ms_kernel.value
-        return ms.value, out
+        return ms.value, op.out
 
 
 # ---- plan cache: the graph is static across the 12 rspmm calls of a forward and across batches ----
@@ -848,10 +809,8 @@ def _onehot_backward_kernel(ptr, order, edge_index, edge_type, edge_weight, rela
     rel_grad = torch.empty(bs, relation.shape[1], dim, dtype=torch.float32, device=og.device) if need_rel else None
     val_grad = torch.empty(bs, dim, dtype=torch.float32, device=og.device) if need_val else None
     rc = lib.ultra_rspmm_onehot_backward(ptr.data_ptr(), order.data_ptr(), target.data_ptr(), edge_type.data_ptr(),
-                                         weight.data_ptr() if weight is not None else None, ctypes.byref(mrel),
-                                         values.data_ptr(), rows.data_ptr(), ctypes.byref(mog),
-                                         rel_grad.data_ptr() if need_rel else None, val_grad.data_ptr() if need_val else None,
-                                         _stream(og))
+                                         _lib.ptr(weight), ctypes.byref(mrel), values.data_ptr(), rows.data_ptr(),
+                                         ctypes.byref(mog), _lib.ptr(rel_grad), _lib.ptr(val_grad), stream_of(og))
     if rc == _lib.ULTRA_ERR_UNSUPPORTED:
         return None
     check(rc)
@@ -992,7 +951,7 @@ class _ReferenceExports(object):
             rel, x = relation.contiguous(), input.contiguous()
             out = torch.empty_like(x)
             check(fn(ei.data_ptr(), et.data_ptr(), ew.data_ptr(), rel.data_ptr(), x.data_ptr(), out.data_ptr(),
-                     ei.shape[1], x.shape[0], rel.shape[0], x.shape[1], dt, _stream(input)))
+                     ei.shape[1], x.shape[0], rel.shape[0], x.shape[1], dt, stream_of(input)))
             return out
         return forward
 
@@ -1009,7 +968,7 @@ class _ReferenceExports(object):
             wg, rg, xg = torch.zeros_like(ew), torch.zeros_like(rel), torch.zeros_like(x)
             check(fn(ei.data_ptr(), et.data_ptr(), ew.data_ptr(), rel.data_ptr(), x.data_ptr(), o.data_ptr(),
                      og.data_ptr(), wg.data_ptr(), rg.data_ptr(), xg.data_ptr(), ei.shape[1], x.shape[0],
-                     rel.shape[0], x.shape[1], dt, _stream(input)))
+                     rel.shape[0], x.shape[1], dt, stream_of(input)))
             return wg, rg, xg
         return backward
 

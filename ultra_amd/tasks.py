@@ -108,8 +108,7 @@ def _strict_negatives_gpu(data, anchor, relation, positive, num_negative, known,
     candidate[floor(rand * count)] (tasks.py:57-61) for the same torch.rand draws, no mask, no host synchronisation.
     rand: the (rows, num_negative) uniform draws to use instead of torch.rand on the device (tests feed the CPU generator's, to
     replay batches recorded from the reference)."""
-    import ctypes
-    from ._lib import check, lib
+    from ._lib import check, lib, stream_of
     keys = _answer_keys(data, known)
     rows = len(anchor)
     if rand is None:
@@ -119,7 +118,7 @@ def _strict_negatives_gpu(data, anchor, relation, positive, num_negative, known,
     anchor, relation, positive = anchor.contiguous(), relation.contiguous(), positive.contiguous()
     check(lib.ultra_strict_negatives(keys.data_ptr(), keys.numel(), anchor.data_ptr(), relation.data_ptr(), positive.data_ptr(),
                                      rand.data_ptr(), rows, num_negative, int(data.num_nodes), int(data.num_relations),
-                                     out.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(anchor.device).cuda_stream)))
+                                     out.data_ptr(), stream_of(anchor)))
     return out
 
 
@@ -334,8 +333,7 @@ def known_answers(data, batch, mode="tail"):
 def filtered_ranking(data, batch, pred, mode="tail"):
     """(ranking, num_negative) of the positives under the filtered protocol == compute_ranking(pred, pos,
     strict_negative_mask(...)) and mask.sum(-1), through the fused HIP kernel (no (batch, N) mask)."""
-    import ctypes
-    from ._lib import check, lib
+    from ._lib import check, lib, stream_of
     if not pred.is_cuda:
         raise RuntimeError("ultra_amd.tasks.filtered_ranking: expected a GPU tensor; the MI355X engine has no CPU path")
     pos = (batch[:, 1] if mode == "tail" else batch[:, 0]).contiguous()
@@ -345,8 +343,7 @@ def filtered_ranking(data, batch, pred, mode="tail"):
     rank = torch.empty(len(batch), dtype=torch.long, device=pred.device)
     num_neg = torch.empty_like(rank)
     check(lib.ultra_filtered_rank(pred.data_ptr(), pos.data_ptr(), ptr.data_ptr(), index.data_ptr(),
-                                  pred.shape[0], pred.shape[1], rank.data_ptr(), num_neg.data_ptr(),
-                                  ctypes.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)))
+                                  pred.shape[0], pred.shape[1], rank.data_ptr(), num_neg.data_ptr(), stream_of(pred)))
     return rank, num_neg
 
 
@@ -362,8 +359,7 @@ def filtered_ranking_masks(data, batch, pred, mode="tail"):
 def relation_graph_bits(graph):
     """(adj, row_counts): the four adjacency bit matrices [hh | tt | ht | th] of graph's relation graph, shape
     (4, num_relations, W) int32 words, and the edges per (type, row) -- built by the HIP kernels of csrc/relgraph.hip."""
-    import ctypes
-    from ._lib import check, lib
+    from ._lib import check, lib, stream_of
     ei, et = graph.edge_index.to(torch.int64).contiguous(), graph.edge_type.to(torch.int64).contiguous()
     n, r = int(graph.num_nodes), int(graph.num_relations)
     w = (r + 31) // 32
@@ -373,8 +369,7 @@ def relation_graph_bits(graph):
     adj = torch.zeros(4, r, w, dtype=torch.int32, device=dev)
     counts = torch.empty(4 * r, dtype=torch.int64, device=dev)
     check(lib.ultra_relation_graph_bits(ei.data_ptr(), et.data_ptr(), ei.shape[1], n, r, hbits.data_ptr(), tbits.data_ptr(),
-                                        adj.data_ptr(), counts.data_ptr(),
-                                        ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                        adj.data_ptr(), counts.data_ptr(), stream_of(dev)))
     return adj, counts
 
 
@@ -382,8 +377,7 @@ def build_relation_graph_gpu(graph):
     """build_relation_graph for a graph resident on the GPU: bit-matrix kernels instead of the reference's four sparse
     products (tasks.py:186-189); relation_graph.edge_index / edge_type equal the reference's element for element.  The
     bit matrices stay attached (relation_graph.adjacency_bits) for consumers that want plan format without the edge list."""
-    import ctypes
-    from ._lib import check, lib
+    from ._lib import check, lib, stream_of
     adj, counts = relation_graph_bits(graph)
     r = int(graph.num_relations)
     offsets = torch.cumsum(counts, 0) - counts
@@ -392,20 +386,18 @@ def build_relation_graph_gpu(graph):
     edge_index = torch.empty(2, total, dtype=torch.int64, device=dev)
     edge_type = torch.empty(total, dtype=torch.int64, device=dev)
     check(lib.ultra_relation_graph_emit(adj.data_ptr(), offsets.data_ptr(), r, total, edge_index.data_ptr(), edge_type.data_ptr(),
-                                        ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                        stream_of(dev)))
     graph.relation_graph = Data(edge_index=edge_index, edge_type=edge_type, num_nodes=r, num_relations=4, adjacency_bits=adj)
     return graph
 
 
 def relation_graph_dense_adjacency(adj):
     """The byte adjacency of the reference-order layer kernel (plan.hpp `a_ex`) from the bit matrices, on the device."""
-    import ctypes
-    from ._lib import check, lib
+    from ._lib import check, lib, stream_of
     r = adj.shape[1]
     nt = (r + 15) // 16
     out = torch.empty(nt * nt * 1024, dtype=torch.uint8, device=adj.device)
-    check(lib.ultra_relation_graph_dense_adjacency(adj.contiguous().data_ptr(), r, out.data_ptr(),
-                                                   ctypes.c_void_p(torch.cuda.current_stream(adj.device).cuda_stream)))
+    check(lib.ultra_relation_graph_dense_adjacency(adj.contiguous().data_ptr(), r, out.data_ptr(), stream_of(adj)))
     return out
 
 

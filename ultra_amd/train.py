@@ -48,14 +48,12 @@ class _RankingLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, temperature, uniform_weight):
-        import ctypes
-        from ._lib import check, lib
+        from ._lib import check, lib, stream_of
         pred = pred.contiguous()
         loss = torch.empty((), dtype=torch.float32, device=pred.device)
         grad = torch.empty_like(pred)
         check(lib.ultra_ranking_loss(pred.data_ptr(), pred.shape[0], pred.shape[1], float(temperature), float(uniform_weight),
-                                     loss.data_ptr(), grad.data_ptr(),
-                                     ctypes.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)))
+                                     loss.data_ptr(), grad.data_ptr(), stream_of(pred)))
         ctx.save_for_backward(grad)
         return loss
 

@@ -11,13 +11,12 @@ that is built once per graph and cached.  In train() mode every projection first
 query_train.traversal_dropout: keep vectors over the static graphs, read through their cached plans).  DESIGN.md section 10.
 """
 import copy
-import ctypes
 from collections import OrderedDict, namedtuple
 
 import torch
 from torch import nn
 
-from ._lib import check, lib
+from ._lib import check, lib, stream_of
 
 
 class Query(torch.Tensor):
@@ -429,7 +428,7 @@ def symbolic_traversal(edge_index, edge_type, num_node, h_prob, r_index, edge_ke
     h = h_prob.contiguous()
     r = r_index.to(torch.int64).contiguous()
     t = torch.empty_like(h)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(h.device).cuda_stream)
+    stream = stream_of(h)
     if edge_keep is not None:
         # the keep vector in the CSR's slot order
         keep_slot = edge_keep.to(torch.float32)[traversal_order(edge_index, edge_type, num_node)].contiguous()
