@@ -9,6 +9,19 @@ from ultra_amd import _lib
 FLT_MAX = {np.float32: np.finfo(np.float32).max, np.float64: np.finfo(np.float64).max}
 
 
+# the graphs of tests/test_rspmm_gpu.py (random_graph's arguments)
+RSPMM_CASES = [
+    dict(num_node=50, num_edge=400, num_relation=5, seed=0),
+    dict(num_node=64, num_edge=300, num_relation=3, seed=1, hub=(7, 700)),
+    dict(num_node=40, num_edge=100, num_relation=4, seed=2, empty_rows=10),
+    dict(num_node=30, num_edge=200, num_relation=1, seed=3, duplicates=50),
+    dict(num_node=5, num_edge=0, num_relation=2, seed=4),
+    dict(num_node=1, num_edge=17, num_relation=2, seed=5),
+    dict(num_node=700, num_edge=9000, num_relation=600, seed=6, hub=(3, 1500)),   # relation slice > x slice
+    dict(num_node=100, num_edge=20000, num_relation=4, seed=7),                  # dense, 4 relations: type-run twin plan
+]
+
+
 def random_graph(num_node, num_edge, num_relation, seed=0, hub=None, empty_rows=0, duplicates=0):
     """Unsorted random multigraph.  hub=(node, count) adds a high-degree row; the last `empty_rows`
     node ids never appear as aggregation targets; `duplicates` repeats some (row, col, type) triples."""
@@ -126,10 +139,12 @@ def emulate_plan_forward(plan, relation, input, edge_weight=None, boundary=None,
     return torch.from_numpy(out)
 
 
-def assert_sum_close(got, want, edge_index, edge_type, edge_weight, relation, input, mul="mul", boundary=None, k=None):
+def assert_sum_close(got, want, edge_index, edge_type, edge_weight, relation, input, mul="mul", boundary=None, k=None,
+                     dtype=None):
     """Two fp sums of the same n terms in different association orders differ by a random walk of
     roundings, each <= eps * |partial sum| <= eps * sum|terms|: bound = (2 + sqrt(n)) * eps * sum|terms|
-    per element, a data-dependent tolerance instead of a blanket one."""
+    per element, a data-dependent tolerance instead of a blanket one.  dtype: the format `got` was summed in where
+    `want` (and the operands the mass is taken from) are a higher-precision reference; eps is that format's."""
     if k is None:
         deg = torch.bincount(edge_index[0].cpu(), minlength=1).max().item() if edge_index.shape[1] else 0
         k = 2.0 + float(deg) ** 0.5
@@ -138,11 +153,26 @@ def assert_sum_close(got, want, edge_index, edge_type, edge_weight, relation, in
                                           sum="add", mul=mul)
     if boundary is not None:
         mass = mass + boundary.abs()
-    eps = torch.finfo(want.dtype).eps
+    eps = torch.finfo(want.dtype if dtype is None else dtype).eps
     bound = k * eps * mass + 10 * torch.finfo(want.dtype).tiny
-    diff = (got - want).abs()
+    diff = (got.to(want.dtype) - want).abs()
     bad = diff > bound
     assert not bad.any(), "max excess %g at %s" % ((diff - bound).max().item(), bad.nonzero()[0].tolist())
+
+
+C_ROUND = 2.0       # a sum of n terms with two roundings each: |error| <= (n + 1) eps sum|term|
+
+
+def assert_within(got, want, mass, count, eps, what, c=C_ROUND):
+    """The worst-case bound of a sum of `count` terms of absolute sum `mass` (fp64 `want`), eps the unit roundoff of the
+    format `got` was summed in: c * (count + 1) * eps * mass per element."""
+    bound = c * (count + 1) * eps * mass + 10 * torch.finfo(torch.float64).tiny
+    err = (got.to(torch.float64) - want).abs()
+    bad = err > bound
+    if bad.any():
+        i = tuple(bad.nonzero()[0].tolist())
+        raise AssertionError("%s: %d elements off, first %s: got %r want %r (bound %g, %d tying terms)"
+                             % (what, int(bad.sum()), i, got[i].item(), want[i].item(), bound[i].item(), count[i].item()))
 
 
 REFERENCE_TU = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_tu.pt.xz")

@@ -6,7 +6,11 @@ The restatement computes each message in the kernel's dtype, one rounding per op
 mask against the forward output (itself checked against the C oracle first) and sums the gradient terms in fp64, with
 sum |term| and the number of terms per element: an fp32 result may differ from the exact sum by the rounding of its own
 n terms, c * n * 2^-24 * sum |term|, which one missing or doubled edge term exceeds.  The graphs and features are built
-so that ties are common, as they are after a ReLU."""
+so that ties are common, as they are after a ReLU.
+
+The case builders take a `width`: the first 64 columns are the tensors they have always drawn (pinned by fingerprint in
+test_backward_bounds_cpu.py), the columns past 64 come from a second generator, so the kernels' span loops (ceil(d / 64)
+spans a slice) are walked at partial, two and three spans with the same cases."""
 import resource
 import time
 
@@ -14,11 +18,10 @@ import pytest
 import torch
 
 from oracle import rspmm_oracle
+from tests.helpers import C_ROUND, assert_within       # noqa: F401  (the bound of this file, shared with tests/add_backward.py)
 from ultra_amd import rspmm, synthetic
 
 pytestmark = pytest.mark.gpu
-
-C_ROUND = 2.0       # a sum of n terms with two roundings each: |error| <= (n + 1) eps sum|term|
 
 
 @pytest.fixture(scope="module")
@@ -83,16 +86,6 @@ def oracle_forward(row, col, typ, w, rel, x, sum, mul):
     return out.view(n, bs, d).transpose(0, 1)
 
 
-def assert_within(got, want, mass, count, eps, what, c=C_ROUND):
-    bound = c * (count + 1) * eps * mass + 10 * torch.finfo(torch.float64).tiny
-    err = (got.to(torch.float64) - want).abs()
-    bad = err > bound
-    if bad.any():
-        i = tuple(bad.nonzero()[0].tolist())
-        raise AssertionError("%s: %d elements off, first %s: got %r want %r (bound %g, %d tying terms)"
-                             % (what, int(bad.sum()), i, got[i].item(), want[i].item(), bound[i].item(), count[i].item()))
-
-
 # ---- graphs and features: each case targets one edge of the tie rule ----
 
 def _edges(g, num_node, num_edge, num_rel, rows=None):
@@ -106,54 +99,71 @@ def _relu_like(g, shape, zero_share=0.4):
     return v
 
 
-def case_relu_zeros(g):
+def _columns(g, rows, width, draw):
+    """(rows, max(width, 64)) features: the first 64 columns are draw(g, (rows, 64)), whatever the width -- the tensors and
+    the generator state every width-64 case has always had -- and the columns past 64 come from a generator of their own."""
+    v = draw(g, (rows, 64))
+    if width > 64:
+        v = torch.cat([v, draw(torch.Generator().manual_seed(1000 * width + rows), (rows, width - 64))], dim=1)
+    return v
+
+
+def _randn(g, shape):
+    return torch.randn(shape, generator=g, dtype=torch.float64)
+
+
+def _rand01(g, shape):
+    return torch.rand(shape, generator=g, dtype=torch.float64) + 0.1
+
+
+def case_relu_zeros(g, width=64):
     """~40 % exact zeros and whole zero rows of x: rows whose maximum is an exact 0 reached by many edges (every zero-row
     neighbour's message is +-0); the min aggregate sees the same from below."""
     n, r = 300, 6
     row, col, typ = _edges(g, n, 4000, r)
-    x = _relu_like(g, (n, 64)).abs()
+    x = _columns(g, n, width, _relu_like).abs()
     x[torch.randperm(n, generator=g)[:60]] = 0.0
-    rel = torch.randn(r, 64, generator=g, dtype=torch.float64)
+    rel = _columns(g, r, width, _randn)
     return dict(n=n, r=r, edges=(row, col, typ), x=x, rel=rel)
 
 
-def case_all_negative(g):
+def case_all_negative(g, width=64):
     """Rows whose messages are all negative (mul: positive x, negative relations; add: both negative): the maximum is the
     least negative message, not a 0 that an absent edge would bring in."""
     n, r = 200, 4
     row, col, typ = _edges(g, n, 2500, r)
-    x = torch.rand(n, 64, generator=g, dtype=torch.float64) + 0.1
-    rel = -(torch.rand(r, 64, generator=g, dtype=torch.float64) + 0.1)
+    x = _columns(g, n, width, _rand01)
+    rel = -_columns(g, r, width, _rand01)
     return dict(n=n, r=r, edges=(row, col, typ), x=x, rel=rel, x_add=-x)
 
 
-def case_signed_zeros(g):
+def case_signed_zeros(g, width=64):
     """+0.0 and -0.0 messages in one row (x rows of +0.0 and of -0.0 times positive relations) next to negative messages (the
     other x rows are negative): under max the two zeros compare equal, so both edges tie, whichever of them the forward kept."""
     n, r = 160, 4
     row, col, typ = _edges(g, n, 2000, r)
-    x = -(torch.rand(n, 64, generator=g, dtype=torch.float64) + 0.1)
+    x = -_columns(g, n, width, _rand01)
     x[0::6] = 0.0
     x[3::6] = -0.0
-    rel = torch.rand(r, 64, generator=g, dtype=torch.float64) + 0.1
+    rel = _columns(g, r, width, _rand01)
     return dict(n=n, r=r, edges=(row, col, typ), x=x, rel=rel)
 
 
-def case_copies(g):
+def case_copies(g, width=64):
     """Distinct edges with identical messages: copied x rows (cols 2k and 2k+1 hold the same features) and copied relation
     rows (types 0 / 1 and 2 / 3), plus exact duplicate (row, col, type) edges."""
     n, r = 200, 4
     row, col, typ = _edges(g, n, 2500, r)
     dup = torch.randint(0, row.numel(), (400,), generator=g)
     row, col, typ = torch.cat([row, row[dup]]), torch.cat([col, col[dup]]), torch.cat([typ, typ[dup]])
-    x = _relu_like(g, (n, 64), 0.1)
+    x = _columns(g, n, width, lambda gen, shape: _relu_like(gen, shape, 0.1))
     x[1::2] = x[0::2]
-    rel = torch.randn(r, 64, generator=g, dtype=torch.float64)
+    rel = _columns(g, r, width, _randn)
     rel[1], rel[3] = rel[0], rel[2]
     return dict(n=n, r=r, edges=(row, col, typ), x=x, rel=rel)
 
 
-def case_empty(g):
+def case_empty(g, width=64):
     """Empty rows (no in-edges), nodes that are no edge's source and unused relation types: their gradients must be written
     as 0, not left as whatever the allocator held."""
     n, r = 150, 7
@@ -161,12 +171,12 @@ def case_empty(g):
     row = row % 100            # rows 100.. receive nothing
     col = col % 120 + 30       # nodes 0..29 send nothing
     typ = typ % 5              # types 5, 6 unused
-    x = _relu_like(g, (n, 64))
-    rel = torch.randn(r, 64, generator=g, dtype=torch.float64)
+    x = _columns(g, n, width, _relu_like)
+    rel = _columns(g, r, width, _randn)
     return dict(n=n, r=r, edges=(row, col, typ), x=x, rel=rel)
 
 
-def case_hub(g):
+def case_hub(g, width=64):
     """A hub row (4000 in-edges) and a hub source node (3000 out-edges) far past the segment length: with
     Plan(seg_len=16, g_max=4) both the transposed plan (input gradient) and the relation-major plan (few types over many
     edges) cut rows into items with partial slots, and rspmm_fixup_kernel folds them."""
@@ -177,9 +187,21 @@ def case_hub(g):
     row = torch.cat([row, hub_row, torch.randint(0, n, (3000,), generator=g)])
     col = torch.cat([col, torch.randint(0, n, (4000,), generator=g), hub_col])
     typ = torch.cat([typ, torch.randint(0, r, (7000,), generator=g)])
-    x = _relu_like(g, (n, 64))
-    rel = torch.randn(r, 64, generator=g, dtype=torch.float64)
+    x = _columns(g, n, width, _relu_like)
+    rel = _columns(g, r, width, _randn)
     return dict(n=n, r=r, edges=(row, col, typ), x=x, rel=rel, split=True)
+
+
+def case_tiny(g, width=64):
+    """A dozen nodes: small enough that a batch of over a thousand samples keeps the restatement's (batch, E, d) fp64
+    temporaries in the tens of MB.  Node 11 receives nothing, node 0 sends nothing."""
+    n, r = 12, 3
+    row, col, typ = _edges(g, n, 60, r)
+    row = row % 11
+    col = col % 11 + 1
+    x = _columns(g, n, width, _relu_like)
+    rel = _columns(g, r, width, _randn)
+    return dict(n=n, r=r, edges=(row, col, typ), x=x, rel=rel)
 
 
 CASES = {"relu_zeros": case_relu_zeros, "all_negative": case_all_negative, "signed_zeros": case_signed_zeros,
@@ -193,6 +215,7 @@ def operands(spec, layout, mul, dtype, g, bs=3, d=64):
     differentiates (shared: the (R, d) table whose gradient is the batch sum of the expanded view's)."""
     x = spec["x_add"] if (mul == "add" and "x_add" in spec) else spec["x"]
     rel = spec["rel"]
+    assert x.shape[1] >= d and rel.shape[1] >= d, "build the case with width >= d"
     x, rel = x[:, :d], rel[:, :d]
     if layout == "2d":
         xs, rels = x.unsqueeze(0), rel.unsqueeze(0)
@@ -215,11 +238,11 @@ def to_dev(t, dev, unaligned=False):
     return big[..., 1:]          # rows 4 bytes off 16-byte alignment: the atomic edge kernel
 
 
-def run_case(dev, spec, sum, mul, dtype, layout, weights, plan_kw=None, d=64, unaligned=False, seed=0):
+def run_case(dev, spec, sum, mul, dtype, layout, weights, plan_kw=None, d=64, unaligned=False, seed=0, bs=3):
     g = torch.Generator().manual_seed(seed)
     row, col, typ = spec["edges"]
     n, r = spec["n"], spec["r"]
-    rels, xs = operands(spec, layout, mul, dtype, g, d=d)
+    rels, xs = operands(spec, layout, mul, dtype, g, bs=bs, d=d)
     bs = xs.shape[0]
     E = row.numel()
     w = None
@@ -296,20 +319,76 @@ def test_minmax_backward_matches_tie_restatement(dev, case, sum, mul, dtype):
                 raise AssertionError("%s / %s: %s" % (layout, weights, e))
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("mul", ["mul", "add"])
+@pytest.mark.parametrize("sum", ["max", "min"])
+@pytest.mark.parametrize("case", ["relu_zeros", "copies", "empty"])
+@pytest.mark.parametrize("d", [4, 72, 128, 200])
+def test_minmax_backward_at_wide_and_partial_rows(dev, d, case, sum, mul, dtype):
+    """Row lengths other than 64 on the gather route (d % 4 == 0): one active lane of a span (4), a partial second span
+    (72), two whole spans (128), three whole spans and 8 elements (200).  rspmm_minmax_bwd_gather_kernel and
+    rspmm_fixup_kernel walk ceil(d / 64) spans a slice and rspmm_edge_bwd_kernel sums the weight gradient over them; the
+    `empty` case's untouched rows must come out 0 in every span.  run_case keeps the bit equality of Plan.backward with
+    the autograd call."""
+    spec = CASES[case](torch.Generator().manual_seed(sorted(CASES).index(case)), width=d)
+    for layout in LAYOUTS:
+        for weights in WEIGHTS:
+            try:
+                run_case(dev, spec, sum, mul, dtype, layout, weights, d=d, seed=len(layout) * 7 + len(weights))
+            except AssertionError as e:
+                raise AssertionError("%s / %s: %s" % (layout, weights, e))
+
+
+@pytest.mark.parametrize("layout", ["batch", "shared"])
+def test_more_spans_than_the_gather_grid(dev, layout):
+    """1100 samples of d = 72: 2200 spans for the 2048 workgroups of backward_gather, so smod == 2048, nparts == 1 and the
+    kernels' `span += smod` stride takes a second turn (every other test has at most a dozen spans)."""
+    bs, d = 1100, 72
+    assert bs * -(-d // 64) > 2048
+    spec = case_tiny(torch.Generator().manual_seed(17), width=d)
+    for weights in WEIGHTS:
+        try:
+            run_case(dev, spec, "max", "mul", torch.float32, layout, weights, d=d, bs=bs, seed=23)
+        except AssertionError as e:
+            raise AssertionError("%s: %s" % (weights, e))
+
+
+def _assert_derived_plans_split_rows(spec, kw):
+    """The plans the backward derives (ensure_backward_plans: same seg_len / g_max, re-associating) have partial slots."""
+    row, col, typ = spec["edges"]
+    derived = (rspmm.Plan(torch.stack([col, row]), typ, spec["n"], spec["r"], type_runs=False, dense=False, **kw),
+               rspmm.Plan(torch.stack([typ, col]), row, spec["r"], spec["n"], num_in=spec["n"], type_runs=False, dense=False, **kw))
+    for p in derived:
+        info = p.info()
+        assert info["n_partial_slot"] > 0 and info["n_split_row"] > 0, info
+
+
+@pytest.mark.parametrize("mul", ["mul", "add"])
+@pytest.mark.parametrize("sum", ["max", "min"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["f32", "f64"])
+def test_split_rows_run_the_fixup_at_a_wide_row(dev, sum, dtype, mul):
+    """test_split_rows_run_the_fixup at d = 136: rspmm_fixup_kernel folds the partial slots of three spans a slice, the
+    last of them 8 elements long."""
+    d = 136
+    spec = case_hub(torch.Generator().manual_seed(99), width=d)
+    kw = dict(seg_len=16, g_max=4)
+    _assert_derived_plans_split_rows(spec, kw)
+    for layout in LAYOUTS:
+        for weights in WEIGHTS:
+            try:
+                run_case(dev, spec, sum, mul, dtype, layout, weights, plan_kw=kw, d=d, seed=5)
+            except AssertionError as e:
+                raise AssertionError("%s / %s: %s" % (layout, weights, e))
+
+
 @pytest.mark.parametrize("sum", ["max", "min"])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["f32", "f64"])
 def test_split_rows_run_the_fixup(dev, sum, dtype):
     """Plan(seg_len=16, g_max=4): the hub rows of the transposed and relation-major plans are cut into items whose partial
     sums rspmm_fixup_kernel adds; every layout and weighting against the restatement."""
     spec = case_hub(torch.Generator().manual_seed(99))
-    row, col, typ = spec["edges"]
     kw = dict(seg_len=16, g_max=4)
-    # the plans the backward derives (ensure_backward_plans: same seg_len / g_max, re-associating)
-    derived = (rspmm.Plan(torch.stack([col, row]), typ, spec["n"], spec["r"], type_runs=False, dense=False, **kw),
-               rspmm.Plan(torch.stack([typ, col]), row, spec["r"], spec["n"], num_in=spec["n"], type_runs=False, dense=False, **kw))
-    for p in derived:
-        info = p.info()
-        assert info["n_partial_slot"] > 0 and info["n_split_row"] > 0, info
+    _assert_derived_plans_split_rows(spec, kw)
     for mul in ("mul", "add"):
         for layout in LAYOUTS:
             for weights in WEIGHTS:
@@ -319,21 +398,21 @@ def test_split_rows_run_the_fixup(dev, sum, dtype):
                     raise AssertionError("%s / %s / %s: %s" % (mul, layout, weights, e))
 
 
-@pytest.mark.parametrize("shape", ["d62", "unaligned"])
+@pytest.mark.parametrize("shape", ["d62", "d130", "unaligned"])
 @pytest.mark.parametrize("sum", ["max", "min"])
 def test_atomic_fallback_within_tolerance(dev, shape, sum):
     """A row length that is not a multiple of 4, or rows off 16-byte alignment, take the reference's atomic scatter
     (rspmm_edge_bwd_kernel): not bit-deterministic, so compared within the rounding bound only."""
+    d = {"d62": 62, "d130": 130, "unaligned": 64}[shape]        # 130: nine 16-element spans of the scalar kernel, the last of 2
     for name in ("relu_zeros", "signed_zeros", "copies", "empty"):
-        spec = CASES[name](torch.Generator().manual_seed(31))
+        spec = CASES[name](torch.Generator().manual_seed(31), width=d)
         for mul in ("mul", "add"):
             for dtype in (torch.float32, torch.float64):
                 for layout, weights in (("2d", "none"), ("2d", "random"), ("batch", "keep"), ("shared", "random")):
-                    if shape == "d62" and layout != "2d":
+                    if shape != "unaligned" and layout != "2d":
                         continue
                     try:
-                        run_case(dev, spec, sum, mul, dtype, layout, weights, d=62 if shape == "d62" else 64,
-                                 unaligned=shape == "unaligned", seed=3)
+                        run_case(dev, spec, sum, mul, dtype, layout, weights, d=d, unaligned=shape == "unaligned", seed=3)
                     except AssertionError as e:
                         raise AssertionError("%s / %s / %s / %s / %s: %s" % (name, mul, dtype, layout, weights, e))
 

@@ -198,8 +198,6 @@ def test_train_mode_step_gradients_match_cpu_oracle(dev, monkeypatch, ckpt, aggr
     oracle (the reference's tie rule), in fp32 and fp64: the GPU may not be further from fp64 than a few times the CPU fp32
     path.  sum / mean: max-abs per parameter; max: Frobenius norm per parameter, near-ties may fall either way between two
     fp32 paths."""
-    from oracle import ultra_oracle_model as om
-    from tests.test_train_gpu import reference_loss
     from ultra_amd import dense, layers, rspmm, train
     _, state, _, cfg = load_golden(ckpt, "sum" if aggr == "mean" else aggr)
     if aggr == "mean":
@@ -212,30 +210,81 @@ def test_train_mode_step_gradients_match_cpu_oracle(dev, monkeypatch, ckpt, aggr
                           (dense, "ROWS_BACKWARD_GATHER"), (rspmm, "DENSE_RELATION_GRAD"), (train, "FUSED_LOSS")):
             assert hasattr(mod, name)
             monkeypatch.setattr(mod, name, False)
+    _train_step_against_the_cpu_oracle(dev, state, cfg, aggr)
+
+
+FUSED_TRAINING_NODES = ("ConvUpdateFunction", "TrainLayerFunction", "TrainRowsLayerFunction", "ReadoutTrainFunction",
+                        "RelationProjectionFunction")
+
+
+def _autograd_node_names(root):
+    """The class names of every autograd node reachable from `root` (a grad_fn)."""
+    names, seen, stack = set(), set(), [root]
+    while stack:
+        fn = stack.pop()
+        if fn is None or fn in seen:
+            continue
+        seen.add(fn)
+        names.add(type(fn).__name__)
+        stack.extend(nxt for nxt, _ in fn.next_functions)
+    return names
+
+
+def train_step_inputs():
+    """(data, the graph the reference's remove_easy_edges leaves, batch with its negatives) of the train-mode step tests."""
     data = synthetic.make_kg(num_node=300, num_triple=2400, num_relation_base=5, num_test=16, seed=4)
     # the batch: graph edges, so that the training forward has easy edges to drop
     pick = torch.tensor([0, 7, 900, 1900])
     batch = torch.stack([data.edge_index[0, pick], data.edge_index[1, pick], data.edge_type[pick]], dim=-1)
     torch.manual_seed(0)
     neg = tasks.negative_sampling(data, batch, 8, strict=True)
-    num_negative = neg.shape[1] - 1
     h, t, r = neg.unbind(-1)
     keep = reference_easy_edge_keep(data.edge_index, data.edge_type, h, t, r, data.num_relations)
     assert 0 < int((~keep).sum()) < 100
     filtered = copy.copy(data)
     filtered.edge_index, filtered.edge_type = data.edge_index[:, keep], data.edge_type[keep]
+    return data, filtered, neg
 
-    def cpu_step(dtype):
-        sd = {k: v.clone().to(dtype).requires_grad_() for k, v in state.items()}
-        with torch.enable_grad():
-            rel = om.rel_nbfnet(sd, data.relation_graph, neg[:, 0, 2], cfg["rel_model_cfg"], oracle_rspmm)
-            pred = om.entity_nbfnet(sd, filtered, rel, neg, cfg["entity_model_cfg"], oracle_rspmm)
-            loss = reference_loss(pred, 0.5, num_negative)
-            loss.backward()
-        return loss.item(), pred.detach(), {k: v.grad.double() for k, v in sd.items()}
 
-    loss32, pred32, g32 = cpu_step(torch.float32)
-    loss64, _, g64 = cpu_step(torch.float64)
+def cpu_train_step(state, cfg, data, filtered, neg, dtype):
+    """The step on the CPU oracle model in `dtype`: (loss, scores, fp64 copies of the parameter gradients)."""
+    from oracle import ultra_oracle_model as om
+    from tests.test_train_gpu import reference_loss
+    sd = {k: v.clone().to(dtype).requires_grad_() for k, v in state.items()}
+    with torch.enable_grad():
+        rel = om.rel_nbfnet(sd, data.relation_graph, neg[:, 0, 2], cfg["rel_model_cfg"], oracle_rspmm)
+        pred = om.entity_nbfnet(sd, filtered, rel, neg, cfg["entity_model_cfg"], oracle_rspmm)
+        loss = reference_loss(pred, 0.5, neg.shape[1] - 1)
+        loss.backward()
+    return loss.item(), pred.detach(), {k: v.grad.double() for k, v in sd.items()}
+
+
+# (hidden size, layers, aggregate, message, layer_norm, short_cut) of the training steps at widths other than 64
+OTHER_HIDDEN_SIZES = [(32, 3, "sum", "distmult", True, True), (128, 2, "max", "distmult", True, False),
+                      (48, 2, "sum", "transe", False, False)]
+
+
+def random_model(dim, layers_n, aggr, message, layer_norm, short_cut):
+    """(state dict, cfg) of an Ultra with random weights under a fixed seed, as
+    test_shapes_outside_the_fused_kernels_match_the_oracle builds its models."""
+    torch.manual_seed(dim + layers_n)
+    def one(cls):
+        return {"class": cls, "input_dim": dim, "hidden_dims": [dim] * layers_n, "message_func": message,
+                "aggregate_func": aggr, "short_cut": short_cut, "layer_norm": layer_norm}
+    cfg = {"rel_model_cfg": one("RelNBFNet"), "entity_model_cfg": one("EntityNBFNet")}
+    model = models.Ultra(rel_model_cfg=dict(cfg["rel_model_cfg"]), entity_model_cfg=dict(cfg["entity_model_cfg"]))
+    return {k: v.detach().clone() for k, v in model.state_dict().items()}, cfg
+
+
+def _train_step_against_the_cpu_oracle(dev, state, cfg, aggr, generic_routes_only=False):
+    """One training step of Ultra(**cfg) with the weights `state` against the CPU oracle model in fp32 and fp64 (see
+    test_train_mode_step_gradients_match_cpu_oracle).  generic_routes_only: no fused 64-wide training node may be in the
+    graph, and the score and loss checks are relative to the scores' size -- see where score_scale is set."""
+    from ultra_amd import dense, train
+    data, filtered, neg = train_step_inputs()
+    num_negative = neg.shape[1] - 1
+    loss32, pred32, g32 = cpu_train_step(state, cfg, data, filtered, neg, torch.float32)
+    loss64, _, g64 = cpu_train_step(state, cfg, data, filtered, neg, torch.float64)
 
     model = models.Ultra(**cfg)
     model.load_state_dict(state)
@@ -243,15 +292,27 @@ def test_train_mode_step_gradients_match_cpu_oracle(dev, monkeypatch, ckpt, aggr
     gdata = data.to(dev)
     pred = model(gdata, neg.to(dev))
     loss = train.ranking_loss(pred, 0.5, num_negative)
+    if generic_routes_only:
+        assert all(hasattr(dense, name) for name in FUSED_TRAINING_NODES)
+        nodes = _autograd_node_names(loss.grad_fn)
+        assert any(n.startswith("_PlanRSPMM") for n in nodes), sorted(nodes)        # (the walk does see custom nodes)
+        fused = sorted(n for n in nodes if any(n.startswith(f) for f in FUSED_TRAINING_NODES))
+        assert not fused, "a fused 64-wide training node in a model of another width: %s" % fused
     loss.backward()
     # the masked route really ran: the scores are the filtered graph's, not the full graph's
     with torch.no_grad():
         model.eval()
         full = model(gdata, neg.to(dev)).cpu()
         model.train()
-    assert (pred.detach().cpu() - pred32).abs().max().item() <= TOL
-    assert (full - pred32).abs().max().item() > 10 * TOL, "dropping the easy edges did not change the scores"
-    assert abs(loss.item() - loss32) <= 1e-5, (loss.item(), loss32)
+    # The checkpoints' scores are O(1) and are held to the absolute TOL and 1e-5.  The random-weight models are held to the
+    # same figures times max(1, max |score|): that is 1.0 at hidden 32 and 128 (max |score| 0.64 and 0.083), so nothing
+    # changes there, and 54 at hidden 48 / TransE / no LayerNorm (max |score| 53.95), where the CPU oracle's own fp32
+    # scores are 4.2e-4 and its fp32 loss 2.1e-5 from its fp64 ones -- no fp32 path meets the absolute figures there.
+    # tests/test_backward_bounds_cpu.py pins these scales and that the CPU fp32 path meets the scaled figures.
+    score_scale = max(1.0, pred32.abs().max().item()) if generic_routes_only else 1.0
+    assert (pred.detach().cpu() - pred32).abs().max().item() <= TOL * score_scale
+    assert (full - pred32).abs().max().item() > 10 * TOL * score_scale, "dropping the easy edges did not change the scores"
+    assert abs(loss.item() - loss32) <= 1e-5 * score_scale, (loss.item(), loss32)      # (the loss is 1-Lipschitz in the scores)
     for name, p in model.named_parameters():
         assert p.grad is not None, name
         got, want, cpu = p.grad.cpu().double(), g64[name], g32[name]
@@ -263,6 +324,17 @@ def test_train_mode_step_gradients_match_cpu_oracle(dev, monkeypatch, ckpt, aggr
             err_gpu, err_cpu = (got - want).abs().max().item(), (cpu - want).abs().max().item()
         assert err_gpu <= 4 * err_cpu + 1e-4 * scale + 1e-7, \
             "%s: |gpu - fp64| = %g, |cpu fp32 - fp64| = %g (scale %g)" % (name, err_gpu, err_cpu, scale)
+
+
+@pytest.mark.parametrize("dim,layers_n,aggr,message,layer_norm,short_cut", OTHER_HIDDEN_SIZES)
+def test_train_mode_step_at_other_hidden_sizes_matches_cpu_oracle(dev, dim, layers_n, aggr, message, layer_norm, short_cut):
+    """test_train_mode_step_gradients_match_cpu_oracle for models built as test_shapes_outside_the_fused_kernels_match_the_oracle
+    builds them (random weights under a fixed seed): at hidden sizes other than 64 the training step falls through the
+    fused conv-update, whole-layer, listed-rows, readout and relation-projection nodes to the generic rspmm backward --
+    the same data, batch, negatives, easy-edge filtering and acceptance rule for the gradients."""
+    state, cfg = random_model(dim, layers_n, aggr, message, layer_norm, short_cut)
+    _train_step_against_the_cpu_oracle(dev, state, cfg, aggr, generic_routes_only=True)
+
 
 def test_training_mode_removes_easy_edges(dev):
     _, state, _, cfg = load_golden("ultra_3g", "sum")

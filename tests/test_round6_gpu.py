@@ -67,7 +67,7 @@ def test_dense_relation_gradient_against_the_oracle(dev, n, num_type, bs):
 
 
 # ---- rspmm on a list of output rows: forward, scatter backward (round 5) and gather backward (round 6) vs the oracle ----
-def _rows_case(seed, n=500, e=7000, bs=3, num_rel=7, n_list=40, masked=True):
+def _rows_case(seed, n=500, e=7000, bs=3, num_rel=7, n_list=40, masked=True, d=64):
     gen = torch.Generator().manual_seed(seed)
     ei = torch.randint(1, n, (2, e), generator=gen)
     ei[0, :1800] = 4                                      # a hub row on the aggregation side
@@ -83,11 +83,11 @@ def _rows_case(seed, n=500, e=7000, bs=3, num_rel=7, n_list=40, masked=True):
     if bs > 1:
         rows[1, 5] = 17                                   # a listed row that carries the boundary value
     keep = (torch.rand(e, generator=gen) > 0.25).float() if masked else torch.ones(e)
-    rel = torch.randn(bs, num_rel, 64, generator=gen)
-    x = torch.randn(bs, n, 64, generator=gen)
-    values = torch.randn(bs, 64, generator=gen)
-    gagg = torch.randn(bs, n_list, 64, generator=gen)
-    gupd = torch.randn(bs, n_list, 64, generator=gen)
+    rel = torch.randn(bs, num_rel, d, generator=gen)
+    x = torch.randn(bs, n, d, generator=gen)
+    values = torch.randn(bs, d, generator=gen)
+    gagg = torch.randn(bs, n_list, d, generator=gen)
+    gupd = torch.randn(bs, n_list, d, generator=gen)
     return ei, et, rows, point_rows, keep, rel, x, values, gagg, gupd
 
 
@@ -96,7 +96,7 @@ def _call_rows_forward(plan, mul, keep, rel, x, rows, point_rows, values):
     from ultra_amd._lib import MUL_CODES, check, lib
     _, mrel = rspmm.as_mat(rel)
     _, mx = rspmm.as_mat(x)
-    agg = torch.empty(rows.shape[0], rows.shape[1], 64, device=x.device)
+    agg = torch.empty(rows.shape[0], rows.shape[1], x.shape[-1], device=x.device)
     check(lib.ultra_rspmm_rows_forward(plan._h, MUL_CODES[mul], keep.data_ptr() if keep is not None else None, ctypes.byref(mrel),
                                        ctypes.byref(mx), rows.data_ptr(), rows.shape[1], None,
                                        point_rows.data_ptr() if point_rows is not None else None,
@@ -105,11 +105,8 @@ def _call_rows_forward(plan, mul, keep, rel, x, rows, point_rows, values):
     return agg
 
 
-@pytest.mark.parametrize("mul", ["mul", "add"])
-@pytest.mark.parametrize("masked", [True, False])
-def test_rows_forward_against_the_oracle(dev, mul, masked):
-    """ultra_rspmm_rows_forward == rspmm_forward_cpu(...)[rows] (+ the point boundary's value on the query's row)."""
-    ei, et, rows, point_rows, keep, rel, x, values, _, _ = _rows_case(51, masked=masked)
+def _rows_forward_against_the_oracle(dev, mul, masked, row_len):
+    ei, et, rows, point_rows, keep, rel, x, values, _, _ = _rows_case(51, masked=masked, d=row_len)
     sei, set_, sw, _ = rspmm_oracle.sort_edges(ei, et, keep)
     plan = rspmm.Plan(ei, et, x.shape[1], rel.shape[1], exact_order=False)
     got = _call_rows_forward(plan, mul, keep.to(dev), rel.to(dev), x.to(dev), rows.to(dev), point_rows.to(dev), values.to(dev)).cpu()
@@ -121,23 +118,34 @@ def test_rows_forward_against_the_oracle(dev, mul, masked):
 
 
 @pytest.mark.parametrize("mul", ["mul", "add"])
-@pytest.mark.parametrize("route", ["gather", "scatter"])
-def test_rows_backward_against_the_oracle(dev, mul, route):
-    """Both backward entries of the listed-rows rspmm vs rspmm_backward_cpu with an output_grad that is zero off the listed rows
-    (repeated entries add up): relation_grad and input_grad; the gather entry also adds the update's share on the listed rows,
-    returns the point boundary's gradient, and is reproducible bit for bit."""
+@pytest.mark.parametrize("masked", [True, False])
+def test_rows_forward_against_the_oracle(dev, mul, masked):
+    """ultra_rspmm_rows_forward == rspmm_forward_cpu(...)[rows] (+ the point boundary's value on the query's row)."""
+    _rows_forward_against_the_oracle(dev, mul, masked, 64)
+
+
+@pytest.mark.parametrize("row_len", [128, 192])
+@pytest.mark.parametrize("mul", ["mul", "add"])
+@pytest.mark.parametrize("masked", [True, False])
+def test_rows_forward_at_two_and_three_spans(dev, mul, masked, row_len):
+    """The same at the other row lengths the entry accepts (whole 64-element spans): one workgroup per (sample, span, listed
+    row), each at its span's offset of the row."""
+    _rows_forward_against_the_oracle(dev, mul, masked, row_len)
+
+
+def _rows_backward_against_the_oracle(dev, mul, route, row_len):
     import ctypes
     from ultra_amd._lib import MUL_CODES, check, lib
-    ei, et, rows, point_rows, keep, rel, x, values, gagg, gupd = _rows_case(52)
+    ei, et, rows, point_rows, keep, rel, x, values, gagg, gupd = _rows_case(52, d=row_len)
     bs, n = x.shape[:2]
     sei, set_, sw, _ = rspmm_oracle.sort_edges(ei, et, keep)
     want_rg, want_xg, want_vg = [], [], []
     for b in range(bs):
-        og = torch.zeros(n, 64).index_add_(0, rows[b], gagg[b])
+        og = torch.zeros(n, row_len).index_add_(0, rows[b], gagg[b])
         out = rspmm_oracle.rspmm_forward(sei, set_, sw, rel[b], x[b], sum="add", mul=mul)
         _, rg, xg = rspmm_oracle.rspmm_backward(sei, set_, sw, rel[b], x[b], out, og, sum="add", mul=mul)
         if route == "gather":
-            xg = xg + torch.zeros(n, 64).index_add_(0, rows[b], gupd[b])
+            xg = xg + torch.zeros(n, row_len).index_add_(0, rows[b], gupd[b])
         want_rg.append(rg), want_xg.append(xg), want_vg.append(og[point_rows[b]])
     want_rg, want_xg, want_vg = torch.stack(want_rg), torch.stack(want_xg), torch.stack(want_vg)
 
@@ -151,7 +159,7 @@ def test_rows_backward_against_the_oracle(dev, mul, route):
     def run():
         if route == "gather":
             rg, xg = torch.full_like(rel_d, float("nan")), torch.full_like(x_d, float("nan"))      # written in full
-            vg = torch.full((bs, 64), float("nan"), device=dev)
+            vg = torch.full((bs, row_len), float("nan"), device=dev)
         else:
             rg, xg, vg = torch.zeros_like(rel_d), torch.zeros_like(x_d), None
         _, mrg = rspmm.as_mat(rg)
@@ -173,6 +181,43 @@ def test_rows_backward_against_the_oracle(dev, mul, route):
         assert (vg.cpu() - want_vg).abs().max().item() <= 1e-5 * max(1.0, want_vg.abs().max().item())
         rg2, xg2, vg2 = run()
         assert torch.equal(rg, rg2) and torch.equal(xg, xg2) and torch.equal(vg, vg2)
+
+
+@pytest.mark.parametrize("mul", ["mul", "add"])
+@pytest.mark.parametrize("route", ["gather", "scatter"])
+def test_rows_backward_against_the_oracle(dev, mul, route):
+    """Both backward entries of the listed-rows rspmm vs rspmm_backward_cpu with an output_grad that is zero off the listed rows
+    (repeated entries add up): relation_grad and input_grad; the gather entry also adds the update's share on the listed rows,
+    returns the point boundary's gradient, and is reproducible bit for bit."""
+    _rows_backward_against_the_oracle(dev, mul, route, 64)
+
+
+@pytest.mark.parametrize("row_len", [128, 192])
+@pytest.mark.parametrize("mul", ["mul", "add"])
+def test_rows_backward_scatter_at_two_and_three_spans(dev, mul, row_len):
+    """ultra_rspmm_rows_backward at the other row lengths it accepts: every span of relation_grad and input_grad."""
+    _rows_backward_against_the_oracle(dev, mul, "scatter", row_len)
+
+
+def test_rows_backward_gather_declines_a_two_span_row_and_launches_nothing(dev):
+    """ultra_rspmm_rows_backward_gather serves 64-element rows: at 128 it returns ULTRA_ERR_UNSUPPORTED (the caller takes the
+    scatter entry) and has written nothing -- the gradient buffers still hold the NaN they were filled with."""
+    import ctypes
+    from ultra_amd._lib import ULTRA_ERR_UNSUPPORTED, lib
+    ei, et, rows, point_rows, keep, rel, x, values, gagg, gupd = _rows_case(54, d=128)
+    plan = rspmm.Plan(ei, et, x.shape[1], rel.shape[1], exact_order=False)
+    d = lambda t: t.to(dev).contiguous()
+    keep_d, rel_d, x_d, rows_d, pr_d, gagg_d, gupd_d = d(keep), d(rel), d(x), d(rows), d(point_rows), d(gagg), d(gupd)
+    rg, xg = torch.full_like(rel_d, float("nan")), torch.full_like(x_d, float("nan"))
+    vg = torch.full((x.shape[0], 128), float("nan"), device=dev)
+    mats = [rspmm.as_mat(t)[1] for t in (rel_d, x_d, rg, xg)]
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    rc = lib.ultra_rspmm_rows_backward_gather(plan._h, 0, keep_d.data_ptr(), ctypes.byref(mats[0]), ctypes.byref(mats[1]),
+                                              rows_d.data_ptr(), rows.shape[1], gagg_d.data_ptr(), gupd_d.data_ptr(), pr_d.data_ptr(),
+                                              vg.data_ptr(), ctypes.byref(mats[2]), ctypes.byref(mats[3]), stream)
+    assert rc == ULTRA_ERR_UNSUPPORTED
+    torch.cuda.synchronize()
+    assert rg.isnan().all() and xg.isnan().all() and vg.isnan().all()
 
 
 def test_rows_backward_gather_serves_more_than_eight_samples_and_declines_long_lists(dev):

@@ -5,22 +5,13 @@ import pytest
 import torch
 
 from oracle import rspmm_oracle
-from tests import helpers
+from tests import add_backward, helpers
 
 pytestmark = pytest.mark.gpu
 
 SUMS = ["add", "min", "max"]
 MULS = ["mul", "add"]
-CASES = [
-    dict(num_node=50, num_edge=400, num_relation=5, seed=0),
-    dict(num_node=64, num_edge=300, num_relation=3, seed=1, hub=(7, 700)),
-    dict(num_node=40, num_edge=100, num_relation=4, seed=2, empty_rows=10),
-    dict(num_node=30, num_edge=200, num_relation=1, seed=3, duplicates=50),
-    dict(num_node=5, num_edge=0, num_relation=2, seed=4),
-    dict(num_node=1, num_edge=17, num_relation=2, seed=5),
-    dict(num_node=700, num_edge=9000, num_relation=600, seed=6, hub=(3, 1500)),   # relation slice > x slice
-    dict(num_node=100, num_edge=20000, num_relation=4, seed=7),                  # dense, 4 relations: type-run twin plan
-]
+CASES = helpers.RSPMM_CASES
 
 
 @pytest.fixture(scope="module")
@@ -167,6 +158,75 @@ def test_backward_matches_oracle(dev, case, sum, mul, dtype):
     torch.testing.assert_close(dx.grad.cpu(), xg, **tol)
     torch.testing.assert_close(drel.grad.cpu(), rg, **tol)
     torch.testing.assert_close(dw.grad.cpu(), wg, **tol)
+
+
+ADD_BACKWARD_SHAPES, ADD_BACKWARD_CASES = add_backward.SHAPES, add_backward.CASES
+
+
+def _run_add_backward(dev, ops, dtype, unaligned=False):
+    """One differentiable call through plan_rspmm on the cached plan, then Plan.backward with and without input_grad_base,
+    each against the fp64 oracle (add_backward.check).  unaligned: input and output_grad rows 4 (8) bytes off 16-byte
+    alignment.  The direct Plan.backward calls hand them to the engine as they are, so vec4 is false in both walks and in
+    the edge kernel; autograd makes its output_grad contiguous first, so there only the relation-major walk and the edge
+    kernel (which read the input) are non-vector.  Plan.backward always hands the engine a contiguous input_grad_base."""
+    from tests.test_minmax_backward_gpu import to_dev
+    from ultra_amd import rspmm
+    layout, weights = ops["layout"], ops["weights"]
+    two_d, keep = layout == "2d", weights == "keep"
+    plan = rspmm.get_plan(ops["ei"].to(dev), ops["et"].to(dev), ops["N"], ops["R"])
+    pick = lambda t: t[0] if two_d else t
+    x_leaf = to_dev(pick(ops["x"]), dev, unaligned).detach().requires_grad_()
+    rel_leaf = (ops["rel"][0] if layout != "batch" else ops["rel"]).to(dev).requires_grad_()
+    rel_in = rel_leaf.unsqueeze(0).expand(ops["bs"], -1, -1) if layout == "shared" else rel_leaf
+    if layout == "shared":
+        assert rel_in.stride(0) == 0
+    w_dev = None if ops["w"] is None else ops["w"].to(dev)
+    if weights == "random":
+        w_dev.requires_grad_()
+    og = to_dev(pick(ops["og"]), dev, unaligned)
+    out = rspmm.plan_rspmm(plan, rel_in, x_leaf, edge_weight=w_dev, sum="add", mul=ops["mul"], keep=keep)
+    out.backward(og)
+    add_backward.check(ops, dtype, w_dev.grad.cpu() if weights == "random" else None, rel_leaf.grad.cpu(), x_leaf.grad.cpu())
+    # Plan.backward itself, every gradient asked for, then once more onto input_grad_base
+    w_plain = None if w_dev is None else w_dev.detach()
+    args = (rel_in.detach(), x_leaf.detach(), out.detach(), og)
+    kw = dict(edge_weight=w_plain, need_weight_grad=True, sum="add", mul=ops["mul"], keep=keep)
+    wgrad, rgrad, xgrad = plan.backward(*args, **kw)
+    _, rgrad_b, total = plan.backward(*args, input_grad_base=pick(ops["base"]).to(dev), **kw)
+    leaf = lambda t: t.sum(0) if layout == "shared" else t
+    add_backward.check(ops, dtype, wgrad.cpu(), leaf(rgrad).cpu(), xgrad.cpu(), got_total=total.cpu())
+    assert torch.equal(rgrad_b, rgrad)
+
+
+@pytest.mark.parametrize("case", ADD_BACKWARD_CASES)
+@pytest.mark.parametrize("mul", MULS)
+@pytest.mark.parametrize("dtype,dim", ADD_BACKWARD_SHAPES)
+def test_add_backward_matches_fp64_oracle(dev, case, mul, dtype, dim):
+    """The backward under sum == "add" -- two forward walks over the derived transposed and relation-major plans, the
+    output gradient in the relation operand's place, rspmm_edge_bwd_kernel for the weights -- at row lengths other than
+    64, batch-major and shared-relation (outer stride 0) operands, every weighting, with the input_grad_base epilogue of
+    ultra_rspmm_backward_add, against the C oracle in fp64 under a bound taken from each element's own terms."""
+    for layout in add_backward.LAYOUTS:
+        for weights in add_backward.WEIGHTS:
+            ops = add_backward.make_operands(case, dim, dtype, layout, weights, mul)
+            try:
+                _run_add_backward(dev, ops, dtype)
+            except AssertionError as e:
+                raise AssertionError("%s / %s: %s" % (layout, weights, e))
+
+
+@pytest.mark.parametrize("case", ADD_BACKWARD_CASES)
+@pytest.mark.parametrize("mul", MULS)
+@pytest.mark.parametrize("dtype,dim", [(torch.float32, 128), (torch.float64, 72)])
+def test_add_backward_on_rows_off_16_byte_alignment(dev, case, mul, dtype, dim):
+    """Whole 16-byte chunks in length, but every row one element off alignment: vec4 == false in the walks and in the
+    edge kernel."""
+    for layout, weights in (("2d", "random"), ("batch", "none"), ("shared", "keep")):
+        ops = add_backward.make_operands(case, dim, dtype, layout, weights, mul, seed=1)
+        try:
+            _run_add_backward(dev, ops, dtype, unaligned=True)
+        except AssertionError as e:
+            raise AssertionError("%s / %s: %s" % (layout, weights, e))
 
 
 def test_function_classes_and_reference_exports(dev):

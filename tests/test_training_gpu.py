@@ -337,24 +337,20 @@ def _index_add_rspmm(ei, et, rel, x, keep, n):
     return torch.zeros(x.shape[0], n, x.shape[2], dtype=x.dtype, device=x.device).index_add(1, ei[0], msg)
 
 
-@pytest.mark.parametrize("masked", [False, True])
-def test_first_layer_rspmm_on_the_boundary_condition_matches_autograd(dev, masked):
-    """rspmm.onehot_rspmm: layer 0's add_mul on its one-hot input (values[b] at row rows[b]) + that boundary -- output,
-    relation gradient and values gradient against fp64 autograd of the dense formulation; one source is a hub, one has no
-    out-edge, a keep mask drops a fifth of the edges."""
+def _first_layer_rspmm_matches_autograd(dev, masked, d):
     gen = torch.Generator().manual_seed(21)
     n, e, bs, num_rel = 500, 6000, 4, 11
     ei = torch.randint(1, n, (2, e), generator=gen)          # (node 0 has no edge at all)
     ei[1, :1500] = 7                                         # hub source
     et = torch.randint(0, num_rel, (e,), generator=gen)
     rows = torch.tensor([7, 0, 123, 7])
-    values = torch.randn(bs, 64, generator=gen)
-    rel = torch.randn(bs, num_rel, 64, generator=gen)
-    og = torch.randn(bs, n, 64, generator=gen)
+    values = torch.randn(bs, d, generator=gen)
+    rel = torch.randn(bs, num_rel, d, generator=gen)
+    og = torch.randn(bs, n, d, generator=gen)
     keep = (torch.rand(e, generator=gen) > 0.2).float() if masked else None
 
     v64, r64 = (t.double().to(dev).requires_grad_() for t in (values, rel))
-    x0 = torch.zeros(bs, n, 64, dtype=torch.float64, device=dev).index_put((torch.arange(bs, device=dev), rows.to(dev)), v64)
+    x0 = torch.zeros(bs, n, d, dtype=torch.float64, device=dev).index_put((torch.arange(bs, device=dev), rows.to(dev)), v64)
     want = _index_add_rspmm(ei.to(dev), et.to(dev), r64, x0, keep.double().to(dev) if masked else None, n) + x0
     want.backward(og.double().to(dev))
 
@@ -367,27 +363,49 @@ def test_first_layer_rspmm_on_the_boundary_condition_matches_autograd(dev, maske
     out.backward(og.to(dev))
     torch.testing.assert_close(dr.grad.double(), r64.grad, rtol=1e-4, atol=1e-3)
     torch.testing.assert_close(dv.grad.double(), v64.grad, rtol=1e-4, atol=1e-3)
+    # which route gave them: the kernel serves whole 64-element spans and declines the rest (the torch route ran above)
+    ptr, order, _ = rspmm.out_edge_csr(dei, det, n)
+    direct = rspmm._onehot_backward_kernel(ptr, order, dei, det, keep.to(dev) if masked else None, dr.detach(), boundary.rows,
+                                           dv.detach(), og.to(dev), True, True)
+    if d % 64:
+        assert direct is None
+    else:
+        assert torch.equal(direct[0], dr.grad) and torch.equal(direct[1], dv.grad)
 
 
-def test_closed_form_boundary_gradient_of_the_differentiable_rspmm(dev):
-    """plan_rspmm(point=(rows, values)): same output and gradients as the boundary passed as a tensor built from
-    `values`; the values' gradient is bs rows of the output gradient."""
+@pytest.mark.parametrize("masked", [False, True])
+def test_first_layer_rspmm_on_the_boundary_condition_matches_autograd(dev, masked):
+    """rspmm.onehot_rspmm: layer 0's add_mul on its one-hot input (values[b] at row rows[b]) + that boundary -- output,
+    relation gradient and values gradient against fp64 autograd of the dense formulation; one source is a hub, one has no
+    out-edge, a keep mask drops a fifth of the edges."""
+    _first_layer_rspmm_matches_autograd(dev, masked, 64)
+
+
+@pytest.mark.parametrize("d", [128, 192, 96])
+@pytest.mark.parametrize("masked", [False, True])
+def test_first_layer_rspmm_on_the_boundary_condition_at_other_widths(dev, masked, d):
+    """The same at two and three spans a row (one workgroup of onehot_bwd_kernel per (sample, span)), and at 96, which the
+    kernel wrapper declines: the torch route then gives the gradients, under the same tolerances."""
+    _first_layer_rspmm_matches_autograd(dev, masked, d)
+
+
+def _closed_form_boundary_gradient(dev, d):
     gen = torch.Generator().manual_seed(22)
     n, e, bs, num_rel = 400, 5000, 3, 9
     ei = torch.randint(0, n, (2, e), generator=gen).to(dev)
     et = torch.randint(0, num_rel, (e,), generator=gen).to(dev)
     rows = torch.tensor([5, 5, 399], device=dev)
-    og = torch.randn(bs, n, 64, generator=gen).to(dev)
+    og = torch.randn(bs, n, d, generator=gen).to(dev)
     plan = rspmm.get_plan(ei, et, n, num_rel, exact_order=False)
     grads = []
     for closed in (False, True):
         g2 = torch.Generator().manual_seed(23)
-        values, rel, x = (t.to(dev).requires_grad_() for t in (torch.randn(bs, 64, generator=g2), torch.randn(bs, num_rel, 64, generator=g2),
-                                                               torch.randn(bs, n, 64, generator=g2)))
+        values, rel, x = (t.to(dev).requires_grad_() for t in (torch.randn(bs, d, generator=g2), torch.randn(bs, num_rel, d, generator=g2),
+                                                               torch.randn(bs, n, d, generator=g2)))
         if closed:
             out = rspmm.plan_rspmm(plan, rel, x, point=(rows, values))
         else:
-            dense_b = torch.zeros(bs, n, 64, device=dev).index_put((torch.arange(bs, device=dev), rows), values)
+            dense_b = torch.zeros(bs, n, d, device=dev).index_put((torch.arange(bs, device=dev), rows), values)
             out = rspmm.plan_rspmm(plan, rel, x, boundary=dense_b)
         out.backward(og)
         grads.append((out.detach(), values.grad, rel.grad, x.grad))
@@ -395,11 +413,20 @@ def test_closed_form_boundary_gradient_of_the_differentiable_rspmm(dev):
         assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("num_rel,n_edge", [(4, 40000), (37, 6000), (474, 6000), (600, 3000)])
-def test_first_layer_backward_kernel_against_its_torch_restatement(dev, num_rel, n_edge):
-    """csrc/onehot_bwd.hip (type-sorted runs per 16-lane group, boundary partials folded in order) against the padded-table
-    torch formulation: hubs whose edges of one type span many groups, sources without edges, a relation table that fills
-    the LDS (474) or exceeds it (600: declined, the torch route runs); the same bits run to run."""
+def test_closed_form_boundary_gradient_of_the_differentiable_rspmm(dev):
+    """plan_rspmm(point=(rows, values)): same output and gradients as the boundary passed as a tensor built from
+    `values`; the values' gradient is bs rows of the output gradient."""
+    _closed_form_boundary_gradient(dev, 64)
+
+
+@pytest.mark.parametrize("d", [128, 30])
+def test_closed_form_boundary_gradient_at_other_widths(dev, d):
+    """The same bit equality at two spans a row and at a row that is not whole 16-byte chunks: under sum == "add" the
+    backward is two forward walks over the derived plans on either route -- no atomics, so d = 30 is bit-equal too."""
+    _closed_form_boundary_gradient(dev, d)
+
+
+def _first_layer_backward_kernel_against_torch(dev, num_rel, n_edge, d):
     gen = torch.Generator().manual_seed(num_rel)
     n, bs = 600, 5
     ei = torch.randint(1, n, (2, n_edge), generator=gen)
@@ -408,15 +435,21 @@ def test_first_layer_backward_kernel_against_its_torch_restatement(dev, num_rel,
     et[: n_edge // 4] = num_rel - 1                          # ... a quarter of them with one type (a run across many chunks)
     ei, et = ei.to(dev), et.to(dev)
     rows = torch.tensor([3, 0, 17, 3, 599], device=dev)
-    values = torch.randn(bs, 64, generator=gen).to(dev)
-    rel = torch.randn(bs, num_rel, 64, generator=gen).to(dev)
-    og = torch.randn(bs, n, 64, generator=gen).to(dev)
+    values = torch.randn(bs, d, generator=gen).to(dev)
+    rel = torch.randn(bs, num_rel, d, generator=gen).to(dev)
+    og = torch.randn(bs, n, d, generator=gen).to(dev)
     keep = (torch.rand(n_edge, generator=gen) > 0.3).float().to(dev)
     ptr, order, max_deg = rspmm.out_edge_csr(ei, et, n)
     for weight in (None, keep):
         want = rspmm._onehot_backward_torch(ptr, order, max_deg, ei, et, weight, rel.double(), rows, values.double(), og.double(),
                                             True, True)
         got = rspmm._onehot_backward_kernel(ptr, order, ei, et, weight, rel, rows, values, og, True, True)
+        if d % 64:           # not whole 64-element spans: declined, and the torch route in fp32 gives the right answer
+            assert got is None
+            torch32 = rspmm._onehot_backward_torch(ptr, order, max_deg, ei, et, weight, rel, rows, values, og, True, True)
+            torch.testing.assert_close(torch32[0].double(), want[0], rtol=1e-4, atol=2e-3)
+            torch.testing.assert_close(torch32[1].double(), want[1], rtol=1e-4, atol=2e-3)
+            continue
         if num_rel * 256 + 64 * 2 * 68 * 4 > 160 * 1024:
             assert got is None
             continue
@@ -426,6 +459,22 @@ def test_first_layer_backward_kernel_against_its_torch_restatement(dev, num_rel,
         assert torch.equal(got[0], again[0]) and torch.equal(got[1], again[1])
         only_rel = rspmm._onehot_backward_kernel(ptr, order, ei, et, weight, rel, rows, values, og, True, False)
         assert only_rel[1] is None and torch.equal(only_rel[0], got[0])
+
+
+@pytest.mark.parametrize("num_rel,n_edge", [(4, 40000), (37, 6000), (474, 6000), (600, 3000)])
+def test_first_layer_backward_kernel_against_its_torch_restatement(dev, num_rel, n_edge):
+    """csrc/onehot_bwd.hip (type-sorted runs per 16-lane group, boundary partials folded in order) against the padded-table
+    torch formulation: hubs whose edges of one type span many groups, sources without edges, a relation table that fills
+    the LDS (474) or exceeds it (600: declined, the torch route runs); the same bits run to run."""
+    _first_layer_backward_kernel_against_torch(dev, num_rel, n_edge, 64)
+
+
+@pytest.mark.parametrize("d", [128, 192, 96])
+@pytest.mark.parametrize("num_rel,n_edge", [(4, 40000), (37, 6000), (474, 6000)])
+def test_first_layer_backward_kernel_at_other_widths(dev, num_rel, n_edge, d):
+    """Two and three spans a row -- one workgroup per (sample, span), the LDS image is one span's whatever the width -- with
+    the same tolerances and run-to-run bit equality; 96 is declined (None) and the torch route answers."""
+    _first_layer_backward_kernel_against_torch(dev, num_rel, n_edge, d)
 
 
 def test_tagged_edge_weights_are_permuted_once_and_never_stale(dev):
