@@ -438,6 +438,31 @@ int32_t ultra_query_segment(const int32_t *entry_depth, const int32_t *push_row,
 int32_t ultra_nonzero_lists(const void *x, int64_t batch, int64_t n, int64_t *counts, int64_t *ptr_out, int64_t *index_out,
                             int64_t capacity, void *stream);
 
+/* ---- serving answer sets ----
+ * ultra_filtered_above: per row of score (batch, n_cand) fp32 contiguous every candidate above `threshold`, ranked.  id v is a
+ * MEMBER of row b iff score[b, v] > threshold as an fp32 comparison: strict, a NaN is never a member, +inf is a member of any
+ * threshold, and with threshold -inf everything but -inf and NaN is.  size_out[b] (batch) int64: the members among all n_cand
+ * ids, counted BEFORE the filter.  The list of row b: the members not in known(b) (known_ptr / known_index: the layout of
+ * ultra_filtered_topk; known_ptr == NULL: no filter), in the stable descending order -- score descending, equal scores by
+ * ascending id, -0.0 == +0.0 -- at ids_out[ptr_out[b] : ptr_out[b + 1]] (int64) and scores_out (fp32, the STORED bits of the
+ * listed scores: -0.0 stays -0.0; a filtered member is removed, never rescored); ptr_out (batch + 1) int64, ptr_out[0] = 0.
+ * ids_out / scores_out hold `capacity` entries each; entries at or beyond ptr_out[batch] are unspecified.
+ * Launches: counts per chunk of ULTRA_TOPK_CHUNK candidates; one scan; the survivors' keys sorted per chunk; ceil(log2(chunks))
+ * merge levels.  The kernel boundary is the only synchronisation between workgroups, there are no global atomics (LDS atomics
+ * only hand out slots before a sort), no allocation, no memset of the workspace (its initial contents do not matter) and no
+ * host synchronisation; the number of launches depends on (batch, n_cand) alone, so the call records into a hipGraph.  Exact
+ * and reproducible: the same bits on every run.
+ * workspace: ultra_filtered_above_workspace(batch, n_cand) bytes of device memory, 8-byte aligned (offsets, counts and two key
+ * buffers of batch * n_cand * 8 bytes each); -1 for batch outside [0, 65535] or n_cand outside [0, 2^31).
+ * n_cand >= 2^31, a NaN or +inf threshold: ULTRA_ERR_UNSUPPORTED, decided before any pointer is looked at.  NULL score or
+ * outputs, n_cand <= 0, batch outside [0, 65535], capacity < batch * n_cand (the rule of ultra_nonzero_lists: no overflow path
+ * exists) or a workspace that is too small: ULTRA_ERR_INVALID, nothing is launched.  batch == 0: ULTRA_OK.
+ */
+int64_t ultra_filtered_above_workspace(int64_t batch, int64_t n_cand);
+int32_t ultra_filtered_above(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
+                             int64_t n_cand, float threshold, int64_t *ptr_out, int64_t *ids_out, void *scores_out,
+                             int64_t capacity, int64_t *size_out, void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,14 +1,16 @@
 """Answer one complex logical query on a dataset of triple files: the k entities the model predicts, with their scores.
 
     python tools/query_predict.py --data-root DIR [--ckpt FILE] --query "(('e1', ('r1',)), ('e2', ('r2', -2)))" [-k 10]
-                                  [--logic product] [--unfiltered]
+                                  [--logic product] [--unfiltered] [--above P]
 
 DIR holds train.txt / valid.txt / test.txt (`head relation tail` per line) and optionally entities.dict / relations.dict
 (ultra_amd.data.load_triples_dir).  The query is a BetaE nested tuple (ultra_amd.ultraquery.Query.from_nested): a pair
 (anchor, (relation, ...)) projects the anchor -- an entity, or a nested query -- along the chain, where -2 negates; any other
 tuple intersects its branches, or unites them when it ends with (-1,).  Entities and relations are names of the
 vocabularies or integer ids.  Answers the graph already entails (the symbolic traversal of the query) are left out unless
---unfiltered.  --ckpt: an UltraQuery checkpoint (a state dict, or a dict with the state under "model"); without it the
+--unfiltered.  --above P prints the answer SET instead of the k best: every entity the model predicts with probability above P
+(0 < P < 1: a logit above log(P / (1 - P)), QueryPredictor.answer_sets), ranked, and the predicted size of the set, which
+counts the entailed answers too.  --ckpt: an UltraQuery checkpoint (a state dict, or a dict with the state under "model"); without it the
 weights are randomly initialised, and the tool says so.
 """
 import argparse
@@ -45,7 +47,10 @@ def main(argv=None):
     ap.add_argument("-k", type=int, default=10)
     ap.add_argument("--logic", default="product", choices=["product", "godel", "lukasiewicz"])
     ap.add_argument("--unfiltered", action="store_true")
+    ap.add_argument("--above", type=float, metavar="P", help="print the whole answer set: every entity with probability above P")
     args = ap.parse_args(argv)
+    if args.above is not None and not 0.0 < args.above < 1.0:
+        sys.exit("--above takes a probability strictly between 0 and 1, got %r" % args.above)
     if not torch.cuda.is_available():
         sys.exit("tools/query_predict.py needs a GPU: the engine has no CPU path")
     from ultra_amd import data as udata
@@ -64,8 +69,15 @@ def main(argv=None):
         print("no --ckpt: randomly initialised weights, the answers mean nothing")
     model = model.to(dev).eval()
     qp = query_predict.QueryPredictor(model, data, k=args.k, batch_size=1, filtered=not args.unfiltered)
-    ids, scores, count = qp.answers([nested])
     print(ultraquery.Query.from_nested(nested).to_readable())
+    if args.above is not None:
+        ptr, ids, scores, size = qp.answer_sets([nested], probability=args.above)
+        print("%d answers with probability above %g%s; predicted size of the set %d"
+              % (int(ptr[1]), args.above, "" if args.unfiltered else ", entailed answers left out", int(size[0])))
+        for i, (v, s) in enumerate(zip(ids.tolist(), scores.tolist())):
+            print("%3d  %-40s %.6g" % (i + 1, ent[v], s))
+        return
+    ids, scores, count = qp.answers([nested])
     print("top %d%s" % (int(count[0]), "" if args.unfiltered else ", entailed answers left out"))
     for i in range(int(count[0])):
         print("%3d  %-40s %.6g" % (i + 1, ent[int(ids[0, i])], float(scores[0, i])))

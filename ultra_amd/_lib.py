@@ -36,6 +36,7 @@ BEAM_HUB_DEGREE = 256        # ULTRA_BEAM_HUB_DEGREE
 RANKING_LDS_ANSWERS = 2048   # ULTRA_RANKING_LDS_ANSWERS
 TOPK_MAX = 256               # ULTRA_TOPK_MAX
 TOPK_CHUNK = 4096            # ULTRA_TOPK_CHUNK
+ABOVE_MAX_BATCH = 65535      # the most rows ultra_filtered_above takes
 ARR_DENSE = 7
 ARR_DENSE_ORDER = 8
 # the layer update's flag bits: ULTRA_CONV_* and, for ultra_nbf_layer0 alone, ULTRA_LAYER0_* (include/ultra_nbfnet.h)
@@ -129,6 +130,9 @@ def _load():
     lib.ultra_filtered_topk_workspace.argtypes = [i64, i64, i32]
     lib.ultra_filtered_topk_workspace.restype = i64
     lib.ultra_filtered_topk.argtypes = [vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp]
+    lib.ultra_filtered_above_workspace.argtypes = [i64, i64]
+    lib.ultra_filtered_above_workspace.restype = i64
+    lib.ultra_filtered_above.argtypes = [vp, vp, vp, i64, i64, ctypes.c_float, vp, vp, vp, i64, vp, vp, i64, vp]
     lib.ultra_query_segment.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, vp, vp, i64, vp, i64, vp, vp, vp, vp]
     lib.ultra_nonzero_lists.argtypes = [vp, i64, i64, vp, vp, vp, i64, vp]
     lib.ultra_beam_search_layer.argtypes =[vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, i64, i32, vp, vp, vp]

@@ -25,6 +25,7 @@
 #include "../../include/ultra_rspmm.h"
 #include "plan.hpp"
 #include "device_scope.hpp"
+#include "score_key.hpp"
 
 namespace ultra {
 
@@ -47,14 +48,6 @@ struct TopkScratch {
     u64 prefix, low;
     unsigned remaining, done, count, cursor;
 };
-
-// fp32 bits -> 32 bits whose unsigned order is the answer order of the scores: NaN (any sign, any payload) on top, then
-// +inf ... +0 == -0 ... -inf.  Never 0 (-inf maps to 0x007fffff).
-__device__ __forceinline__ unsigned ordered_score(unsigned u) {
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
-    if ((u & 0x7fffffffu) == 0u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // surv[0 .. m) -> sorted[0 .. min(m, k)), descending: rank by counting, the keys are distinct.  m <= TOPK_THREADS.
 __device__ __forceinline__ void rank_sort(const u64 *surv, int m, int k, u64 *sorted) {

@@ -6,9 +6,12 @@ and relation, leaving out the ones the graph already states?
 
   filtered_topk_reference   the semantics in plain torch, on any device -- the definition the kernel is tested against
   filtered_topk             csrc/topk_kernels.hip (ultra_filtered_topk): no (batch, N) mask, no clone of the scores
+  filtered_above_reference  the answer SET of a row -- every candidate above a threshold, ranked -- in plain torch
+  filtered_above            csrc/above_kernels.hip (ultra_filtered_above): the length of the lists is decided on the device
+  logit_threshold           the logit threshold of a probability
   known_answers             the ragged lists of ids to leave out, from the filter graph (no positive is added)
   Predictor                 .tails(h, r) / .heads(t, r): candidate construction, the forward and the selection as one
-                            hipGraph replay per batch
+                            hipGraph replay per batch; .tails_above(h, r, min_score) / .heads_above(t, r, min_score): the sets
   verify_reference          leave-one-out verification of stated facts in plain torch: per triple a filtered copy of the graph
   Predictor.verify_tails    ... the same for a batch of facts as one hipGraph replay: per-sample keep masks over the cached plan
     / .verify_heads         of the full graph
@@ -17,6 +20,8 @@ Order: score descending, equal scores by ascending id, every Na
 -- the stable descending torch.sort.  A filtered candidate is removed, not rescored: a genuine -inf score is a candidate
 like any other, ranked last.  Slots beyond count = min(k, N - |known|) hold id -1 and score -inf.
 """
+
+import math
 
 import torch
 
@@ -75,6 +80,95 @@ def filtered_topk(pred, k, ptr=None, index=None):
                                             None if ptr is None else index.data_ptr(), batch, n, k, ids.data_ptr(),
                                             scores.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel() * 8, _lib.stream_of(dev)))
     return ids, scores, count
+
+
+def _fp32_threshold(threshold):
+    """`threshold` rounded to fp32 (a Python float); ValueError unless it is finite or -inf."""
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)):
+        raise TypeError("the threshold is a Python float, got %r" % (threshold,))
+    value = float(torch.tensor(float(threshold), dtype=torch.float64).to(torch.float32))
+    if math.isnan(value) or value == float("inf"):
+        raise ValueError("the threshold must be finite or -inf (after rounding to fp32), got %r" % (threshold,))
+    return value
+
+
+def logit_threshold(probability):
+    """The logit at which sigmoid crosses `probability`: log(p / (1 - p)) in fp64, rounded to fp32; 0 < p < 1 (ValueError
+    otherwise); p = 0.5 gives exactly 0.0.  The threshold `filtered_above` takes for "predicted with probability above p"."""
+    p = float(probability)
+    if not 0.0 < p < 1.0:
+        raise ValueError("probability must lie strictly between 0 and 1, got %r" % (probability,))
+    return float(torch.tensor(math.log(p / (1.0 - p)), dtype=torch.float64).to(torch.float32))
+
+
+def filtered_above_reference(pred, threshold, ptr=None, index=None):
+    """The answer SET of every row, ranked: (out_ptr (batch + 1) int64, ids (total) int64, scores (total) pred's dtype, size
+    (batch) int64), on any device -- the definition ultra_filtered_above is tested against.
+
+    v is a member of row b iff pred[b, v] > threshold as an fp32 comparison: strict, a NaN is never a member, +inf is a member
+    of any threshold, and with threshold -inf everything but -inf and NaN is.  threshold: a Python float, rounded to fp32,
+    finite or -inf (ValueError otherwise).  size[b] counts the members among all ids, BEFORE the filter: the integer predicted
+    cardinality, comparable with num_easy + num_hard.  ids[out_ptr[b] : out_ptr[b + 1]]: the members not in
+    index[ptr[b] : ptr[b + 1]] (the lists of filtered_topk; ptr None: no filter) in the stable descending order -- score
+    descending, equal scores by ascending id, -0.0 == +0.0; scores: their stored bits (a filtered member is removed, never
+    rescored).
+
+    Two differences from the reference's rule (script/run_query.py:42-44, `prob > 0.5`).  The rule here is on the LOGIT, logit
+    > logit_threshold(p): for p = 0.5 the reference's fp32 sigmoid(x) > 0.5 is false for positive logits so small that the
+    sigmoid rounds to 0.5 (roughly below 1e-7); such logits are members here.  And `size` is an integer count, not the
+    reference's soft num_pred; query_eval keeps the reference's metrics as they are."""
+    thr = _fp32_threshold(threshold)
+    batch, n = pred.shape
+    dev = pred.device
+    member = pred.float() > torch.tensor(thr, dtype=torch.float32, device=dev)
+    size = member.sum(dim=-1)
+    out_ptr = torch.zeros(batch + 1, dtype=torch.long, device=dev)
+    ids, scores = [], []
+    for b in range(batch):
+        keep = member[b].clone()
+        if ptr is not None:
+            keep[index[int(ptr[b]):int(ptr[b + 1])]] = False
+        cand = keep.nonzero().flatten()
+        order = torch.sort(pred[b, cand], descending=True, stable=True).indices
+        ids.append(cand[order])
+        scores.append(pred[b, cand[order]])
+        out_ptr[b + 1] = out_ptr[b] + cand.numel()
+    ids = torch.cat(ids) if ids else torch.zeros(0, dtype=torch.long, device=dev)
+    scores = torch.cat(scores) if scores else torch.zeros(0, dtype=pred.dtype, device=dev)
+    return out_ptr, ids, scores, size
+
+
+def filtered_above(pred, threshold, ptr=None, index=None):
+    """filtered_above_reference through the HIP kernels (csrc/above_kernels.hip): pred (batch, N) fp32 on the GPU; ptr
+    (batch + 1) / index int64, ids ascending and distinct within a row; ptr None: no filter.  `ids` and `scores` come back as
+    the full-capacity (batch * N) buffers: entries at or beyond out_ptr[batch] are unspecified.  No host wait is made -- the
+    caller reads out_ptr[-1] when it wants to slice."""
+    thr = _fp32_threshold(threshold)
+    if not pred.is_cuda:
+        raise RuntimeError("ultra_amd.predict.filtered_above: expected a GPU tensor; the MI355X engine has no CPU path")
+    if pred.dim() != 2 or pred.dtype != torch.float32:
+        raise TypeError("filtered_above takes (batch, N) fp32 scores, got %s %s" % (tuple(pred.shape), pred.dtype))
+    pred = pred.contiguous()
+    batch, n = pred.shape
+    dev = pred.device
+    out_ptr = torch.zeros(batch + 1, dtype=torch.long, device=dev)
+    ids = torch.empty(batch * n, dtype=torch.long, device=dev)
+    scores = torch.empty(batch * n, dtype=torch.float32, device=dev)
+    size = torch.empty(batch, dtype=torch.long, device=dev)
+    if batch == 0:
+        return out_ptr, ids, scores, size
+    if n == 0 or batch > _lib.ABOVE_MAX_BATCH:
+        raise ValueError("filtered_above takes 1 to %d rows of at least one candidate, got %s" % (_lib.ABOVE_MAX_BATCH, tuple(pred.shape)))
+    if ptr is not None:
+        if ptr.shape != (batch + 1,) or ptr.dtype != torch.long or index.dtype != torch.long or ptr.device != dev or index.device != dev:
+            raise ValueError("filtered_above takes int64 `ptr` of shape (batch + 1,) and int64 `index` on the scores' device")
+        ptr, index = ptr.contiguous(), index.contiguous()      # (referenced until the launch is enqueued)
+    ws = torch.empty(max(1, _lib.lib.ultra_filtered_above_workspace(batch, n) // 8), dtype=torch.long, device=dev)
+    _lib.check(_lib.lib.ultra_filtered_above(pred.data_ptr(), None if ptr is None else ptr.data_ptr(),
+                                             None if ptr is None else index.data_ptr(), batch, n, thr, out_ptr.data_ptr(),
+                                             ids.data_ptr(), scores.data_ptr(), ids.numel(), size.data_ptr(), ws.data_ptr(),
+                                             ws.numel() * 8, _lib.stream_of(dev)))
+    return out_ptr, ids, scores, size
 
 
 def known_answers(data, anchor, relation, mode="tail"):
@@ -282,6 +376,19 @@ class Predictor(object):
     def heads(self, t, r):
         return self._run(t, r, "head")
 
+    def tails_above(self, h, r, min_score):
+        """Every tail of (h[i], r[i], ?) whose logit exceeds `min_score` (a Python float: the threshold of
+        filtered_above_reference), ranked: (ptr (n + 1) int64, ids, scores, size (n) int64) for the whole call, in query order
+        -- the set of query i is ids[ptr[i] : ptr[i + 1]], best first; known answers are left out as in `tails`, while size[i]
+        counts every entity above the threshold, known ones included.  The forward runs eagerly, batch by batch, and
+        ultra_filtered_above selects on the device; the host reads one number per batch (the batch's total) to slice the
+        batch's lists out of their full-capacity buffers.  Off the GPU the plain-torch restatement selects, as in `tails`."""
+        return self._run_above(h, r, min_score, "tail")
+
+    def heads_above(self, t, r, min_score):
+        """tails_above for the heads of (?, r[i], t[i])."""
+        return self._run_above(t, r, min_score, "head")
+
     def explain_tails(self, h, r, chunk=16):
         """tails(h, r) plus why: (ids, scores, count, explanations).  explanations[i][j], j < count[i], is the (paths, weights)
         of model.visualize_batch for the triple (h[i], ids[i, j], r[i]) -- answer j of query i -- so every path runs from
@@ -425,6 +532,46 @@ class Predictor(object):
         finally:
             self.model.train(was_training)
         return score, rank, num_negative
+
+    @torch.no_grad()
+    def _run_above(self, anchor, relation, min_score, mode):
+        threshold = _fp32_threshold(min_score)
+        data, bs = self.data, self.batch_size
+        dev = data.edge_index.device
+        anchor = torch.as_tensor(anchor, dtype=torch.long, device=dev).flatten()
+        relation = torch.as_tensor(relation, dtype=torch.long, device=dev).flatten()
+        if anchor.shape != relation.shape:
+            raise ValueError("one relation per query: got %d entities and %d relations" % (len(anchor), len(relation)))
+        n = len(anchor)
+        out_ptr, ids, scores, size = [torch.zeros(1, dtype=torch.long, device=dev)], [], [], []
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            ptr = index = None
+            if self.filtered and n:     # the known lists of the whole call, once
+                ptr, index = known_answers(self.filter_graph, anchor, relation, mode)
+            at = 0
+            for lo in range(0, n, bs):
+                pred = self.model(data, _candidates(data, anchor[lo:lo + bs], relation[lo:lo + bs], mode)).float()
+                b_ptr = None if ptr is None else ptr[lo:lo + len(pred) + 1]
+                if pred.is_cuda:
+                    b_out, b_ids, b_scores, b_size = filtered_above(pred, threshold, b_ptr, index)
+                    total = int(b_out[-1])      # (the one host read of the batch)
+                    b_ids, b_scores = b_ids[:total].clone(), b_scores[:total].clone()
+                else:
+                    b_out, b_ids, b_scores, b_size = filtered_above_reference(pred, threshold, b_ptr, index)
+                    total = b_ids.numel()
+                out_ptr.append(b_out[1:] + at)
+                ids.append(b_ids)
+                scores.append(b_scores)
+                size.append(b_size)
+                at += total
+        finally:
+            self.model.train(was_training)
+        if not ids:
+            return (out_ptr[0], torch.zeros(0, dtype=torch.long, device=dev), torch.zeros(0, dtype=torch.float32, device=dev),
+                    torch.zeros(0, dtype=torch.long, device=dev))
+        return torch.cat(out_ptr), torch.cat(ids), torch.cat(scores), torch.cat(size)
 
     @torch.no_grad()
     def _run(self, anchor, relation, mode):
