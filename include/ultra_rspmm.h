@@ -237,6 +237,38 @@ int32_t ultra_rspmm_forward_point(ultra_plan *plan, int32_t sum, int32_t mul, in
                                   const ultra_mat *point_values, const ultra_mat *output, void *stream);
 
 /*
+ * Added facts as a DELTA on a cached plan (serving a graph that changes; csrc/delta_kernels.hip).  The plan of the base graph
+ * stays as it is; the added edges live in a few device arrays, prepared once when facts are added:
+ *   col_dev / type_dev  int32 [capacity_edges]     the delta's edges in the plan's direction (row = edge_index[0], col =
+ *                                                  edge_index[1]), sorted by (row, col, insertion id)
+ *   row_dev             int32 [capacity_rows]      the distinct rows they point into, ascending
+ *   ptr_dev             int32 [capacity_rows + 1]  edges [ptr[k], ptr[k + 1]) of the sorted arrays belong to row_dev[k]
+ *   count_dev           int32 [1]                  the live number of touched rows, read ON THE DEVICE
+ * ultra_rspmm_delta_rows is called on the output of ultra_rspmm_forward / _forward_point (same plan, sum, mul, relation, input
+ * and boundary -- a dense boundary, or with point_rows_dev the point's values, or NULL).  It recomputes the touched rows
+ * only, each as the two-way merge on col of its base edges and its delta edges, base edges first at equal col -- the sorted
+ * (row, col, edge id) order of a plan of the edge list [base ; delta], whose delta edges carry the highest ids -- summed
+ * sequentially with the boundary last, and OVERWRITES output[outer, row].  On ULTRA_PLAN_EXACT_ORDER plans the output then
+ * equals ultra_rspmm_forward on a fresh reference-order plan of the concatenated list bit for bit; no other row is written.
+ * The grid is sized by capacity_rows * n_outer and the groups beyond *count_dev end at once: a launch recorded into a hipGraph
+ * serves every later content of the same arrays.  No atomics, no allocation, no memset, no host synchronisation.  A row longer
+ * than seg_len is walked by one 16-lane group as one dependent chain.
+ * Served: fp32 / fp64, add / min / max, mul / add messages, unit edge weights, reference-order plans in the sparse format, rows
+ * that are whole 16-byte chunks at 16-byte aligned addresses and strides.  General-walk and dense-format plans, rotate messages
+ * and misaligned rows: ULTRA_ERR_UNSUPPORTED with nothing launched (weighted or masked calls have no argument here: the caller
+ * does not combine them with a delta).  Invalid arguments: ULTRA_ERR_INVALID.  capacity_rows == 0 or n_outer == 0: ULTRA_OK.
+ * The caller keeps every index of the delta inside the plan's num_out_row / num_in_row / num_relation; an index outside is never
+ * dereferenced (its edge is left out, a touched row outside is not written).
+ */
+typedef struct {
+    const int32_t *row_dev, *ptr_dev, *col_dev, *type_dev, *count_dev;
+    int64_t capacity_rows, capacity_edges;
+} ultra_delta;
+int32_t ultra_rspmm_delta_rows(ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const ultra_mat *relation,
+                               const ultra_mat *input, const ultra_mat *boundary, const int64_t *point_rows_dev,
+                               const ultra_mat *output, const ultra_delta *delta, void *stream);
+
+/*
  * Aggregate + layer update in ONE launch (fp32 inference path of GeneralizedRelationalConv.forward,
  * /root/reference/ultra/layers.py:84-131, 190-240, with the residual of /root/reference/ultra/models.py:158-160):
  *

@@ -49,6 +49,13 @@ class UltraMat(ctypes.Structure):
                 ("n_row", ctypes.c_int64), ("stride_row", ctypes.c_int64), ("row_len", ctypes.c_int64)]
 
 
+class UltraDelta(ctypes.Structure):
+    """ultra_delta: the device arrays of a graph delta (include/ultra_rspmm.h, ultra_rspmm_delta_rows)."""
+    _fields_ = [("row_dev", ctypes.c_void_p), ("ptr_dev", ctypes.c_void_p), ("col_dev", ctypes.c_void_p),
+                ("type_dev", ctypes.c_void_p), ("count_dev", ctypes.c_void_p), ("capacity_rows", ctypes.c_int64),
+                ("capacity_edges", ctypes.c_int64)]
+
+
 class PlanOpts(ctypes.Structure):
     _fields_ = [("seg_len", ctypes.c_int32), ("g_max", ctypes.c_int32), ("flags", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)]
@@ -96,6 +103,7 @@ def _load():
     lib.ultra_rspmm_forward.argtypes = [vp, i32, i32, i32, vp, matp, matp, matp, matp, vp]
     lib.ultra_rspmm_forward_masked.argtypes = [vp, i32, i32, i32, vp, matp, matp, matp, matp, vp]
     lib.ultra_rspmm_forward_masked_samples.argtypes = [vp, i32, i32, i32, vp, i64, matp, matp, matp, matp, vp]
+    lib.ultra_rspmm_delta_rows.argtypes = [vp, i32, i32, i32, matp, matp, matp, vp, matp, ctypes.POINTER(UltraDelta), vp]
     lib.ultra_rspmm_forward_onehot.argtypes = [vp, i32, vp, matp, matp, vp, matp, matp, vp]
     lib.ultra_rspmm_forward_point.argtypes = [vp, i32, i32, i32, vp, matp, matp, vp, matp, matp, vp]
     lib.ultra_rspmm_forward_update.argtypes = [vp, i32, i32, matp, matp, vp, matp, matp, vp, vp, vp, vp, ctypes.c_float, i32, matp, vp]

@@ -1,0 +1,225 @@
+// Added facts as a DELTA on the cached plan of a served graph (ultra_rspmm_delta_rows, include/ultra_rspmm.h).
+//
+// The plan of the base graph stays as it is.  After a layer's aggregate (ultra_rspmm_forward / _forward_point on the base
+// plan) ONE launch recomputes the output rows that an added edge points into -- the only rows whose value differs on the
+// graph with the added facts -- and overwrites them.  Per (touched row, outer slice) one 16-lane group walks the row's base
+// edges (the plan's device CSR: row_ptr / col / type, sorted by (row, col, edge id)) and the row's delta edges (sorted by
+// (row, col, insertion id)) as a two-way merge on col, base edges first at equal col: the sorted (row, col, edge id) order of a
+// plan of the concatenated edge list, where the delta edges carry the highest ids.  Messages and the sequential reduction
+// are those of the reference-order kernels for unit edge weights (rspmm_kernels.hpp: binary / nary), the epilogue is the
+// boundary epilogue of rspmm_order_kernels.hpp: with -ffp-contract=off the rows equal those of a fresh reference-order plan of
+// the materialised graph bit for bit.
+//
+// The grid is sized by the delta's CAPACITY; the live number of touched rows is read from device memory and the groups
+// beyond it end at once, so a launch recorded into a hipGraph serves every later content of the same buffers.  No atomics,
+// no allocation, no memset, no host synchronisation.
+//
+// A hub row (longer than the plan's seg_len, a chain row of the base walk) is walked here by ONE group as one dependent
+// chain: loads are issued DELTA_BATCH edges ahead, the additions stay in order.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+
+#include "device_scope.hpp"
+#include "rspmm_kernels.hpp"
+
+namespace ultra {
+
+constexpr int DELTA_BATCH = 8;        // source / relation rows requested ahead of the ordered additions
+constexpr int DELTA_THREADS = 256;    // sixteen 16-lane groups a workgroup
+
+struct DeltaParams {
+    const int32_t *row_ptr, *col, *type;                 // the base plan's CSR (sorted edge order)
+    const int32_t *d_row, *d_ptr, *d_col, *d_type;       // the delta: touched rows, their edge ranges, the sorted delta edges
+    const int32_t *d_count;                              // live number of touched rows (device memory)
+    int32_t cap_rows, cap_edges;
+    MatArg rel, x, bnd;
+    const long long *bnd_rows;                           // != NULL: `bnd` is a point boundary (one row per outer slice)
+    int32_t has_bnd;
+    void *out;
+    long long out_stride_outer, out_stride_row;
+    int32_t n_outer, row_len, num_out, num_in, num_rel;
+    long long num_edge;
+};
+
+template <typename T, int SUM, int MUL>
+__global__ void __launch_bounds__(DELTA_THREADS) rspmm_delta_rows_kernel(const DeltaParams p) {
+    constexpr int VEC = 16 / (int)sizeof(T);      // elements per 16-byte chunk
+    using P = Pack<T, VEC>;
+    const int l16 = threadIdx.x & 15;
+    const long long group = (long long)blockIdx.x * (DELTA_THREADS / 16) + (threadIdx.x >> 4);
+    const int k = (int)(group / p.n_outer), outer = (int)(group - (long long)k * p.n_outer);
+    const int live = min(max(*p.d_count, 0), p.cap_rows);
+    if (k >= live) return;
+    const int row = p.d_row[k];
+    if (row < 0 || row >= p.num_out) return;      // (a delta prepared for another graph: nothing is written)
+    int i = p.row_ptr[row];
+    const int ie = p.row_ptr[row + 1];
+    int j = min(max(p.d_ptr[k], 0), p.cap_edges);
+    const int je = min(max(p.d_ptr[k + 1], j), p.cap_edges);
+    if (i < 0 || ie < i || ie > p.num_edge) return;
+
+    const T *rel = reinterpret_cast<const T *>(p.rel.ptr) + outer * p.rel.stride_outer;
+    const T *x = reinterpret_cast<const T *>(p.x.ptr) + outer * p.x.stride_outer;
+    T *dst = reinterpret_cast<T *>(p.out) + outer * p.out_stride_outer + (long long)row * p.out_stride_row;
+    const long long bnd_row = p.bnd_rows ? p.bnd_rows[outer] : -1;
+
+    for (int d0 = VEC * l16; d0 < p.row_len; d0 += 16 * VEC) {
+        int bi = i, dj = j;
+        int bcol = bi < ie ? p.col[bi] : 0, dcol = dj < je ? p.d_col[dj] : 0;
+        P acc;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc.v[e] = nary_zero<T, SUM>();
+        while (bi < ie || dj < je) {
+            // the next DELTA_BATCH edges of the merged order: (col, type) each
+            int c[DELTA_BATCH], t[DELTA_BATCH];
+            bool take[DELTA_BATCH];
+#pragma unroll
+            for (int u = 0; u < DELTA_BATCH; ++u) {
+                c[u] = 0, t[u] = 0, take[u] = false;
+                if (bi < ie && (dj >= je || bcol <= dcol)) {        // (equal col: the base edge has the lower edge id)
+                    c[u] = bcol, t[u] = p.type[bi], take[u] = true;
+                    ++bi;
+                    if (bi < ie) bcol = p.col[bi];
+                } else if (dj < je) {
+                    c[u] = dcol, t[u] = p.d_type[dj], take[u] = true;
+                    ++dj;
+                    if (dj < je) dcol = p.d_col[dj];
+                }
+                // (an index outside the operands is never dereferenced: such an edge reads row 0 and is left out of the reduction)
+                if (c[u] < 0 || c[u] >= p.num_in || t[u] < 0 || t[u] >= p.num_rel) c[u] = 0, t[u] = 0, take[u] = false;
+            }
+            P xv[DELTA_BATCH], rv[DELTA_BATCH];
+#pragma unroll
+            for (int u = 0; u < DELTA_BATCH; ++u) {
+                xv[u] = *reinterpret_cast<const P *>(x + (long long)c[u] * p.x.stride_row + d0);
+                rv[u] = *reinterpret_cast<const P *>(rel + (long long)t[u] * p.rel.stride_row + d0);
+            }
+#pragma unroll
+            for (int u = 0; u < DELTA_BATCH; ++u) {
+                if (take[u]) {
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) acc.v[e] = nary<T, SUM>(acc.v[e], binary<T, MUL>(rv[u].v[e], xv[u].v[e]));
+                }
+            }
+        }
+        // the boundary epilogue of the reference-order kernels
+        if (p.has_bnd && (bnd_row < 0 || bnd_row == row)) {
+            const P b = *reinterpret_cast<const P *>(reinterpret_cast<const T *>(p.bnd.ptr) + outer * p.bnd.stride_outer +
+                                                     (bnd_row < 0 ? (long long)row * p.bnd.stride_row : 0) + d0);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc.v[e] = nary<T, SUM>(acc.v[e], b.v[e]);
+        } else if (SUM != ULTRA_SUM_ADD && p.has_bnd) {     // (min / max: a point boundary stands for zeros elsewhere)
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc.v[e] = nary<T, SUM>(acc.v[e], T(0));
+        }
+        *reinterpret_cast<P *>(dst + d0) = acc;
+    }
+}
+
+template <typename T>
+static hipError_t launch_delta(int sum, int mul, const DeltaParams &p, unsigned grid, hipStream_t s) {
+#define ULTRA_DELTA_CASE(S_, M_)                                                                                    \
+    case S_ * 2 + M_:                                                                                               \
+        hipLaunchKernelGGL((rspmm_delta_rows_kernel<T, S_, M_>), dim3(grid), dim3(DELTA_THREADS), 0, s, p);          \
+        break;
+    switch (sum * 2 + mul) {
+        ULTRA_DELTA_CASE(0, 0) ULTRA_DELTA_CASE(0, 1) ULTRA_DELTA_CASE(1, 0) ULTRA_DELTA_CASE(1, 1) ULTRA_DELTA_CASE(2, 0)
+        ULTRA_DELTA_CASE(2, 1)
+        default: return hipErrorInvalidValue;
+    }
+#undef ULTRA_DELTA_CASE
+    return hipGetLastError();
+}
+
+static int delta_invalid(const std::string &msg) {
+    set_error("ultra_rspmm_delta_rows: " + msg);
+    return ULTRA_ERR_INVALID;
+}
+static int delta_unsupported(const std::string &msg) {
+    set_error("ultra_rspmm_delta_rows: " + msg);
+    return ULTRA_ERR_UNSUPPORTED;
+}
+
+static int delta_check_mat(const ultra_mat *m, const char *name, int64_t min_rows, int64_t n_outer, int64_t row_len) {
+    if (!m || !m->ptr) return delta_invalid(std::string(name) + " is NULL");
+    if (m->n_outer != n_outer) return delta_invalid(std::string(name) + ": n_outer mismatch");
+    if (m->row_len != row_len) return delta_invalid(std::string(name) + ": row_len mismatch");
+    if (m->n_row < min_rows) return delta_invalid(std::string(name) + ": too few rows");
+    if (m->stride_row < row_len && m->n_row > 1) return delta_invalid(std::string(name) + ": stride_row < row_len");
+    return ULTRA_OK;
+}
+
+static bool delta_vec_ok(const ultra_mat *m, int64_t step) {
+    return (reinterpret_cast<uintptr_t>(m->ptr) & 15u) == 0 && m->stride_row % step == 0 && m->stride_outer % step == 0;
+}
+
+}  // namespace ultra
+
+using namespace ultra;
+
+extern "C" int32_t ultra_rspmm_delta_rows(ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const ultra_mat *relation,
+                                          const ultra_mat *input, const ultra_mat *boundary, const int64_t *point_rows_dev,
+                                          const ultra_mat *output, const ultra_delta *delta, void *stream) {
+    ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);
+    if (!plan) return delta_invalid("plan is NULL");
+    if (sum < 0 || sum > 2) return delta_invalid("unknown sum code");
+    if (mul != ULTRA_MUL_MUL && mul != ULTRA_MUL_ADD && mul != ULTRA_MUL_ROTATE) return delta_invalid("unknown mul code");
+    if (dtype != ULTRA_F32 && dtype != ULTRA_F64) return delta_invalid("dtype must be ULTRA_F32 or ULTRA_F64");
+    if (!delta) return delta_invalid("delta is NULL");
+    if (delta->capacity_rows < 0 || delta->capacity_edges < 0 || delta->capacity_rows >= (1ll << 30) ||
+        delta->capacity_edges >= (1ll << 30))
+        return delta_invalid("delta: capacities must lie in [0, 2^30)");
+    if (!output || !output->ptr) return delta_invalid("output is NULL");
+    const int64_t n_outer = output->n_outer, row_len = output->row_len;
+    if (n_outer < 0 || row_len <= 0) return delta_invalid("output: negative n_outer or empty row_len");
+    if (n_outer == 0 || delta->capacity_rows == 0) return ULTRA_OK;
+    if (!delta->row_dev || !delta->ptr_dev || !delta->col_dev || !delta->type_dev || !delta->count_dev)
+        return delta_invalid("delta: a NULL array");
+    int rc;
+    if ((rc = delta_check_mat(output, "output", plan->num_out, n_outer, row_len))) return rc;
+    if ((rc = delta_check_mat(relation, "relation", plan->num_rel, n_outer, row_len))) return rc;
+    if ((rc = delta_check_mat(input, "input", plan->num_in, n_outer, row_len))) return rc;
+    if (point_rows_dev && !boundary) return delta_invalid("a point boundary needs its value rows");
+    if (boundary && (rc = delta_check_mat(boundary, "boundary", point_rows_dev ? 1 : plan->num_out, n_outer, row_len))) return rc;
+    if (mul == ULTRA_MUL_ROTATE) return delta_unsupported("rotate messages are not served");
+    if ((plan->flags & ULTRA_PLAN_DENSE) || !(plan->flags & ULTRA_PLAN_EXACT_ORDER))
+        return delta_unsupported("served by ULTRA_PLAN_EXACT_ORDER plans in the sparse format only");
+    const int64_t step = dtype == ULTRA_F32 ? 4 : 2;      // elements per 16 bytes
+    if (row_len % step != 0 || !delta_vec_ok(output, step) || !delta_vec_ok(relation, step) || !delta_vec_ok(input, step) ||
+        (boundary && !delta_vec_ok(boundary, step)))
+        return delta_unsupported("rows must be whole 16-byte chunks at 16-byte aligned addresses and strides");
+    if (plan->num_out == 0 || plan->num_in == 0 || plan->num_rel == 0) return ULTRA_OK;
+    const int64_t groups = delta->capacity_rows * n_outer;
+    const int64_t grid = (groups + DELTA_THREADS / 16 - 1) / (DELTA_THREADS / 16);
+    if (grid >= (1ll << 31)) return delta_invalid("capacity_rows * n_outer exceeds the launch grid");
+    if ((rc = ultra_plan_upload(plan))) return rc;
+
+    DeltaParams p;
+    p.row_ptr = plan->d.row_ptr, p.col = plan->d.col, p.type = plan->d.type;
+    p.d_row = delta->row_dev, p.d_ptr = delta->ptr_dev, p.d_col = delta->col_dev, p.d_type = delta->type_dev;
+    p.d_count = delta->count_dev;
+    p.cap_rows = (int32_t)delta->capacity_rows, p.cap_edges = (int32_t)delta->capacity_edges;
+    p.rel = MatArg{relation->ptr, relation->stride_outer, relation->stride_row};
+    p.x = MatArg{input->ptr, input->stride_outer, input->stride_row};
+    p.bnd = boundary ? MatArg{boundary->ptr, boundary->stride_outer, point_rows_dev ? 0 : boundary->stride_row}
+                     : MatArg{nullptr, 0, 0};
+    p.bnd_rows = boundary ? reinterpret_cast<const long long *>(point_rows_dev) : nullptr;
+    p.has_bnd = boundary ? 1 : 0;
+    p.out = output->ptr;
+    p.out_stride_outer = output->stride_outer, p.out_stride_row = output->stride_row;
+    p.n_outer = (int32_t)n_outer, p.row_len = (int32_t)row_len;
+    p.num_out = (int32_t)plan->num_out, p.num_in = (int32_t)plan->num_in, p.num_rel = (int32_t)plan->num_rel;
+    p.num_edge = plan->num_edge;
+    if (n_outer >= (1ll << 31) || row_len >= (1ll << 31)) return delta_invalid("n_outer / row_len exceed 2^31");
+    (void)hipGetLastError();   // drop any stale error left by other users of the HIP runtime
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const hipError_t e = dtype == ULTRA_F32 ? launch_delta<float>(sum, mul, p, (unsigned)grid, s)
+                                            : launch_delta<double>(sum, mul, p, (unsigned)grid, s);
+    if (e != hipSuccess) {
+        set_error(std::string("rspmm_delta_rows_kernel launch: ") + hipGetErrorString(e));
+        return ULTRA_ERR_HIP;
+    }
+    return ULTRA_OK;
+}

@@ -104,6 +104,20 @@ def _flipped_edges(edge_index):
     return hit[0]
 
 
+_IN_DEGREE = {}
+
+
+def _in_degree(edge_index, num_node):
+    """bincount(edge_index[1]) as int64, one tensor per graph (bincount reads its size back: not for a captured step)."""
+    key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), str(edge_index.device), int(num_node))
+    hit = _IN_DEGREE.get(key)
+    if hit is None:
+        if len(_IN_DEGREE) >= 8:
+            _IN_DEGREE.clear()
+        hit = _IN_DEGREE[key] = (torch.bincount(edge_index[1], minlength=num_node), edge_index)
+    return hit[0]
+
+
 class GeneralizedRelationalConv(nn.Module):
 
     eps = 1e-6
@@ -154,21 +168,34 @@ class GeneralizedRelationalConv(nn.Module):
                     nn.Linear(input_dim, input_dim)
                 )
 
-    def forward(self, input, query, boundary, edge_index, edge_type, size, edge_weight=None):
+    def forward(self, input, query, boundary, edge_index, edge_type, size, edge_weight=None, delta=None):
+        """delta (rspmm.GraphDelta, inference only): the layer on the graph with the delta's added facts, computed on the cached
+        plan of (edge_index, edge_type) -- _propagate_delta; where the engine does not serve that, on the materialised edge list."""
+        if delta is not None and len(delta):
+            out = self._forward_impl(input, query, boundary, edge_index, edge_type, size, edge_weight, residual=False, delta=delta)
+            if out is not None:
+                return out
+            extra_index, extra_type = delta.edges()
+            edge_index, edge_type = torch.cat([edge_index, extra_index], dim=1), torch.cat([edge_type, extra_type])
         return self._forward_impl(input, query, boundary, edge_index, edge_type, size, edge_weight, residual=False)
 
     def _forward_impl(self, input, query, boundary, edge_index, edge_type, size, edge_weight=None, residual=False,
-                      relation=None, onehot_rows=None, edge_keep=False):
+                      relation=None, onehot_rows=None, edge_keep=False, delta=None):
         """forward() plus the option to fuse the caller's residual `hidden + layer_input` (models.py:158-160),
         to take this layer's relation features precomputed by the caller, to be told that `input` is zero
-        outside row onehot_rows[b] of every sample (the layer-0 boundary condition, models.py:139-141), and that
-        `edge_weight` is a 0/1 keep mask (edge_keep=True: edges with 0 are absent, base_nbfnet.py:54-77)."""
+        outside row onehot_rows[b] of every sample (the layer-0 boundary condition, models.py:139-141), that
+        `edge_weight` is a 0/1 keep mask (edge_keep=True: edges with 0 are absent, base_nbfnet.py:54-77), and to run on
+        the graph with the added facts of `delta` (rspmm.GraphDelta; _propagate_delta)."""
         batch_size = len(query)
 
         if relation is None:
             relation = self._relation_for(query, batch_size)
         # edge_weight=None means "all ones" (what every caller on the fused path passes, models.py:143):
         # the kernel then skips the weight stream instead of multiplying by 1.
+        if delta is not None:
+            if edge_weight is not None or edge_keep:
+                raise RuntimeError("a graph delta (added facts) is not combined with edge weights or keep masks")
+            return self._propagate_delta(edge_index, size, input, relation, boundary, edge_type, delta, residual=residual)
         return self.propagate(input=input, relation=relation, boundary=boundary, edge_index=edge_index,
                               edge_type=edge_type, size=size, edge_weight=edge_weight, residual=residual,
                               onehot_rows=onehot_rows, edge_keep=edge_keep)
@@ -282,6 +309,50 @@ class GeneralizedRelationalConv(nn.Module):
             degree = torch.zeros(len(edge_weight), num_node, dtype=input.dtype, device=input.device).index_add_(
                 1, edge_index[1], edge_weight)
             update = update / (degree + 1).unsqueeze(-1)
+        return self.update(update, input, residual=residual)
+
+    def delta_supported(self):
+        """Does _propagate_delta serve this layer's configuration?  (sum / mean / max / min with TransE or DistMult)"""
+        return self.aggregate_func in ("sum", "mean", "max", "min") and self.message_func in self.message2mul
+
+    def _propagate_delta(self, edge_index, size, input, relation, boundary, edge_type, delta, residual=False):
+        """The layer on the graph WITH the added facts of `delta` (rspmm.GraphDelta), on the cached plan of the base graph: the
+        aggregate by plan.forward (the two-launch form: the one-launch layer would update rows before they are fixed), then
+        plan.delta_rows, which recomputes the rows an added edge points into in the reference's order, then the update.  Equals
+        the layer on delta.materialize(...) bit for bit.  Inference only; sum / mean / max / min, TransE / DistMult; a dense or a
+        point boundary (layer 0 included: its closed form does not know the delta).  Returns None where the engine does not
+        serve the call (a re-associating or dense-format plan, misaligned rows): the caller materialises."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("a graph delta (added facts) serves inference (torch.no_grad()) only")
+        if not self.delta_supported():
+            raise RuntimeError("a graph delta (added facts) serves the sum / mean / max / min aggregates with TransE / DistMult "
+                               "messages, not `%s` / `%s`" % (self.aggregate_func, self.message_func))
+        num_node = size[0] if size is not None else input.shape[1]
+        if not input.is_cuda or self._order_free(edge_index, num_node):
+            return None
+        plan = rspmm.get_plan(edge_index, edge_type, num_node, relation.shape[1])
+        sum = {"sum": "add", "mean": "add"}.get(self.aggregate_func, self.aggregate_func)
+        mul = self.message2mul[self.message_func]
+        update = None
+        if isinstance(boundary, PointBoundary):
+            point = (boundary.rows, boundary.values)
+            update = plan.forward(relation, input, sum=sum, mul=mul, point=point)
+            if update is not None:
+                update = plan.delta_rows(relation, input, update, delta, sum=sum, mul=mul, point=point)
+            else:       # (a plan that does not serve the point form under min / max: the boundary as a tensor)
+                boundary = boundary.dense()
+        if update is None:
+            if isinstance(boundary, PointBoundary):
+                return None
+            boundary = boundary.to(input.dtype)
+            update = plan.forward(relation, input, boundary=boundary, sum=sum, mul=mul)
+            update = plan.delta_rows(relation, input, update, delta, boundary=boundary, sum=sum, mul=mul)
+            if update is None:
+                return None
+        if self.aggregate_func == "mean":
+            # bincount(edge_index[1]) of the materialised list (+ 1: the boundary's self loop), as message_and_aggregate counts it
+            degree = _in_degree(edge_index, num_node) + delta.degree
+            update = update / (degree.to(input.dtype) + 1).view(1, -1, 1)
         return self.update(update, input, residual=residual)
 
     def edge_grad_layer(self, input, query, boundary, edge_index, edge_type, num_node, edge_weight, residual=False,

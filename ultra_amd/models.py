@@ -184,8 +184,10 @@ class BaseNBFNet(nn.Module):
 
     def _propagate_layers(self, data, layer_input, query, boundary, separate_grad=False, relations=None,
                           edge_weight=None, onehot_rows=None, edge_keep=False, prefilled=None, last_rows=None,
-                          edge_grad_route=False, edge_grad_batch=None):
+                          edge_grad_route=False, edge_grad_batch=None, delta=None):
         """The Bellman-Ford loop shared by every model (models.py:72-80, 150-163, 233-246).
+        `delta` (rspmm.GraphDelta, inference only): every layer runs on the graph with the delta's added facts, on the cached
+        plan of `data` (layers._propagate_delta); _DeltaRouteUnsupported where a layer or the engine does not serve that.
         `relations`: optional per-layer relation features computed up front (EntityNBFNet batches the six
         relation_projection MLPs, which all read the same relation representations).
         `boundary` may be a layers.PointBoundary (then `layer_input` is ignored: layer 0 reads the boundary condition).
@@ -204,7 +206,8 @@ class BaseNBFNet(nn.Module):
             rel0 = None if relations is None else relations[0]
             # (a per-sample keep mask -- 2-D -- has no layer-0 kernel: the layer takes the boundary as a tensor)
             per_sample = edge_weight is not None and edge_weight.dim() == 2
-            if not separate_grad and not per_sample and layer.layer0_point_supported(boundary, rel0, edge_weight):
+            # (... nor does a graph delta: the closed form walks the base graph's out-edges only)
+            if not separate_grad and not per_sample and delta is None and layer.layer0_point_supported(boundary, rel0, edge_weight):
                 # layer 0 on its one-hot input: constant fill + the rows reached from the source (ultra_nbf_layer0);
                 # the boundary condition never becomes a (batch, N, d) tensor on this path
                 residual = self.short_cut and layer.output_dim == layer.input_dim
@@ -266,6 +269,18 @@ class BaseNBFNet(nn.Module):
                     edge_weights.append(edge_weight)
                     self._last_hidden_on_rows = True
                     break
+            if delta is not None:
+                if separate_grad or torch.is_grad_enabled() or not layer.delta_supported():
+                    raise _DeltaRouteUnsupported()
+                hidden = layer._forward_impl(layer_input, query, boundary, data.edge_index, data.edge_type, size,
+                                             residual=residual, relation=None if relations is None else relations[i],
+                                             delta=delta)
+                if hidden is None:
+                    raise _DeltaRouteUnsupported()
+                hiddens.append(hidden)
+                edge_weights.append(None)
+                layer_input = hidden
+                continue
             hidden = layer._forward_impl(layer_input, query, boundary, data.edge_index, data.edge_type, size,
                                          edge_weight, residual=residual,
                                          relation=None if relations is None else relations[i],
@@ -275,6 +290,20 @@ class BaseNBFNet(nn.Module):
             edge_weights.append(edge_weight)
             layer_input = hidden
         return hiddens, edge_weights
+
+
+class _DeltaRouteUnsupported(Exception):
+    """The engine route of a graph delta (added facts on the cached plan) does not apply -- CPU tensors, a model outside the 64-d
+    fused inference path, a layer kind or a plan the delta kernel does not serve: the forward runs on the materialised graph."""
+
+
+def _materialized_forward(run, data, delta, on_gpu):
+    """`run(graph)` on delta.materialize(data) -- today's route: a host plan of the concatenated edge list (the plan cache keeps
+    it until the next add).  Not under a hipGraph capture, like the generic path."""
+    if on_gpu and torch.cuda.is_current_stream_capturing():
+        raise NotOnFusedPath("a graph delta outside the engine route runs on the materialised graph (a host plan): not "
+                             "capturable")
+    return run(delta.materialize(data))
 
 
 class _BatchRouteUnsupported(Exception):
@@ -306,11 +335,14 @@ class RelNBFNet(BaseNBFNet):
 
     def bellmanford(self, data, h_index, separate_grad=False, edge_keep=None):
         batch_size = len(h_index)
-        ones = getattr(self, "_ones_query", None)
-        if ones is None or ones.shape[0] != batch_size or ones.device != h_index.device or torch.is_grad_enabled():
+        # (one tensor per batch size and device, never dropped: a captured step points at the one its warm-up made, and a
+        # forward of another batch size in between -- a ragged last batch run eagerly -- must not free it under the graph)
+        cached = self.__dict__.setdefault("_ones_queries", {})
+        ones = None if torch.is_grad_enabled() else cached.get((batch_size, h_index.device))
+        if ones is None:
             ones = torch.ones(batch_size, self.dims[0], device=h_index.device, dtype=torch.float)
             if not torch.is_grad_enabled():
-                self._ones_query = ones        # constant: not refilled on every forward
+                cached[(batch_size, h_index.device)] = ones        # constant: not refilled on every forward
         query = ones
         index = h_index.unsqueeze(-1).expand_as(query)
         # boundary: ones at the query relation's node, zeros elsewhere (models.py:59-66) -- in closed form
@@ -389,7 +421,7 @@ class EntityNBFNet(BaseNBFNet):
         return out, side
 
     def _bellmanford_hidden(self, data, h_index, r_index, separate_grad=False, edge_weight=None, edge_keep=False, prefilled=None,
-                            last_rows=None, edge_grad_route=False, edge_grad_batch=None):
+                            last_rows=None, edge_grad_route=False, edge_grad_batch=None, delta=None):
         batch_size = len(r_index)
         # query = representation of each sample's query relation, scattered to its head node
         fused = (dense.boundary_supported(h_index, self.query) and self.query.dim() == 3
@@ -417,7 +449,7 @@ class EntityNBFNet(BaseNBFNet):
                                                        relations=self._project_relations_batched(),
                                                        edge_weight=edge_weight, onehot_rows=h_index, edge_keep=edge_keep,
                                                        prefilled=prefilled, last_rows=last_rows, edge_grad_route=edge_grad_route,
-                                                       edge_grad_batch=edge_grad_batch)
+                                                       edge_grad_batch=edge_grad_batch, delta=delta)
         return hiddens, edge_weights, query
 
     def _project_relations_batched(self):
@@ -618,10 +650,26 @@ class EntityNBFNet(BaseNBFNet):
                 or tuple(edge_keep.shape) != (batch.shape[0], data.edge_index.shape[1]):
             raise ValueError("edge_keep must be a (batch, num_edge) = (%d, %d) tensor" % (batch.shape[0], data.edge_index.shape[1]))
 
-    def forward(self, data, relation_representations, batch, prefill=None, prologue=None, edge_keep=None):
+    def forward(self, data, relation_representations, batch, prefill=None, prologue=None, edge_keep=None, delta=None):
         """edge_keep (batch, num_edge), 0/1, original edge order: sample s runs on the graph without the edges whose
         edge_keep[s] is 0 -- row s of the result is this forward on data filtered by edge_keep[s] with batch[s:s+1] (eval mode
-        under no_grad only).  The relation graph is the caller's: not rebuilt."""
+        under no_grad only).  The relation graph is the caller's: not rebuilt.
+        delta (rspmm.GraphDelta; eval mode under no_grad, not with edge_keep): the forward on the graph with the delta's added
+        facts -- it equals this forward on delta.materialize(data).  On the fused inference path a branch shaped like the masked
+        one runs on data's cached plans (prologue, delta layers, readout: every step an engine launch, so a capture records
+        it); elsewhere the materialised graph is used (relation_representations are the caller's in both cases)."""
+        if delta is not None and len(delta) == 0:
+            delta = None
+        if delta is not None:
+            if edge_keep is not None or self.training or torch.is_grad_enabled():
+                raise ValueError("a graph delta (added facts) serves eval mode under torch.no_grad() only, without edge_keep")
+            try:
+                if not self.prologue_supported(batch):
+                    raise _DeltaRouteUnsupported()
+                return self._forward_delta(data, relation_representations, batch, prologue, delta)
+            except _DeltaRouteUnsupported:
+                return _materialized_forward(lambda graph: self.forward(graph, relation_representations, batch), data, delta,
+                                             batch.is_cuda)
         if edge_keep is not None:
             self._check_edge_keep(data, batch, edge_keep)
         h_index, t_index, r_index = batch.unbind(-1)
@@ -724,6 +772,20 @@ class EntityNBFNet(BaseNBFNet):
         self._check_valid(valid)
         return score.view(shape)
 
+    def _forward_delta(self, data, relation_representations, batch, prologue, delta):
+        """The delta branch of forward(): dense.batch_prologue, the layers with the delta's rows fixed after every aggregate,
+        dense.readout_batch."""
+        self.query = relation_representations
+        for layer in self.layers:
+            layer.relation = relation_representations
+        batch_c, h0, r0, side, valid = prologue if prologue is not None else dense.batch_prologue(batch, data.num_relations // 2)
+        hiddens, _, query = self._bellmanford_hidden(data, h0, r0, delta=delta)
+        if not dense.readout_supported(self, hiddens[-1]):
+            raise _DeltaRouteUnsupported()
+        score = dense.readout_batch(self, hiddens[-1], query, batch_c, side).view(batch.shape[:-1])
+        self._check_valid(valid)
+        return score
+
     def _check_valid(self, valid):
         if valid.is_cuda and torch.cuda.is_current_stream_capturing():
             self._pending_valid = valid      # checked by the graph wrapper after replay (graph.py)
@@ -747,10 +809,27 @@ class QueryNBFNet(EntityNBFNet):
             "edge_weights": edge_weights,
         }
 
-    def forward(self, data, node_features, relation_representations, query, edge_keep=None):
+    def forward(self, data, node_features, relation_representations, query, edge_keep=None, delta=None):
+        """delta (rspmm.GraphDelta; under no_grad, not with edge_keep): the scores on the graph with the delta's added facts --
+        the layers on data's cached plan where the engine serves them, else on delta.materialize(data)."""
         for layer in self.layers:
             layer.relation = relation_representations
         self.query = relation_representations      # input of the batched relation projections
+        if delta is not None and len(delta):
+            if edge_keep is not None or torch.is_grad_enabled():
+                raise ValueError("a graph delta (added facts) serves inference under torch.no_grad() only, without edge_keep")
+            try:
+                hiddens, _ = self._propagate_layers(data, node_features, query, node_features, delta=delta,
+                                                    relations=self._project_relations_batched())
+            except _DeltaRouteUnsupported:
+                return _materialized_forward(lambda graph: self.forward(graph, node_features, relation_representations, query),
+                                             data, delta, query.is_cuda)
+            if dense.readout_supported(self, hiddens[-1]):
+                every = torch.arange(data.num_nodes, device=query.device).unsqueeze(0).expand(len(query), -1)
+                return dense.readout(self, hiddens[-1], query, every)
+            node_query = query.unsqueeze(1).expand(-1, data.num_nodes, -1)
+            feature = torch.cat((hiddens if self.concat_hidden else hiddens[-1:]) + [node_query], dim=-1)
+            return self.mlp(feature).squeeze(-1)
         if edge_keep is not None:
             # UltraQuery's training projection: traversal dropout as a 0/1 keep vector over the static edge list (read through
             # the full graph's cached plan), and the readout of every node as one autograd node where it applies
@@ -879,11 +958,21 @@ class Ultra(nn.Module):
                 layer.relation = r
         return results
 
-    def forward(self, data, batch, edge_keep=None):
+    def forward(self, data, batch, edge_keep=None, delta=None):
         # batch: (bs, 1 + num_negs, 3); the relation is shared by every triple of a row
         # edge_keep (bs, num_edge): per-sample 0/1 keep masks over data's edge list (EntityNBFNet.forward); the relation graph is
         # not rebuilt -- the reference's filtered copy keeps data.relation_graph too
+        # delta (rspmm.GraphDelta, a non-empty one; eval mode under no_grad): the scores on the graph WITH the delta's added facts
+        # -- this forward on delta.materialize(data), bit for bit on reference-order plans.  The relation model runs on
+        # delta.relation_graph, the entity model on data's cached plan with the touched rows fixed after every aggregate; where
+        # that route does not apply (EntityNBFNet.forward), on the materialised graph.  An empty delta (or None): nothing changes.
         entity_kwargs = {}
+        if delta is not None and len(delta):
+            if edge_keep is not None:
+                raise ValueError("a graph delta (added facts) is not combined with edge_keep")
+            if delta.relation_graph is not None and delta.relation_graph is not data.relation_graph:
+                data = delta.live_view(data)
+            entity_kwargs["delta"] = delta
         if edge_keep is not None:
             if self.training or torch.is_grad_enabled():
                 raise ValueError("edge_keep (per-sample keep masks) serves eval mode under torch.no_grad() only")
@@ -897,7 +986,8 @@ class Ultra(nn.Module):
         else:
             query_rels = batch[:, 0, 2]
         prefill = None
-        if PREFILL_LAYER0 and batch.is_cuda and batch.dim() == 3 and hasattr(self.entity_model, "prefill_layer0"):
+        if PREFILL_LAYER0 and batch.is_cuda and batch.dim() == 3 and hasattr(self.entity_model, "prefill_layer0") \
+                and "delta" not in entity_kwargs:      # (the delta's layer 0 is a full layer: nothing to prefill)
             prefill = self.entity_model.prefill_layer0(data, batch.shape[0])
         relation_representations = self._cached_relations(data, query_rels)
         if relation_representations is None:

@@ -21,11 +21,13 @@ Order: score descending, equal scores by ascending id, every Na
 like any other, ranked last.  Slots beyond count = min(k, N - |known|) hold id -1 and score -inf.
 """
 
+import copy
+import inspect
 import math
 
 import torch
 
-from . import _lib, dense, models, tasks
+from . import _lib, dense, models, rspmm, tasks
 from .graph import Capture, param_state
 
 
@@ -205,10 +207,15 @@ class _GraphedPredictStep(Capture):
     forward and ultra_filtered_topk.  Per batch the host copies the (bs) anchors and relations and the (bs + 1) offsets into
     the known lists of the whole call, which live in a buffer of the step (`load_index`, once per call)."""
 
-    def __init__(self, model, data, batch_size, k, mode, index_capacity, warmup=2):
+    def __init__(self, model, data, batch_size, k, mode, index_capacity, warmup=2, delta=None):
+        """delta (rspmm.GraphDelta or None): handed to the model from the first capture.  While it is empty the model takes its
+        normal path; once it holds facts the capture records the delta's launches, which read its device buffers at replay --
+        `route` is what the Predictor compares to know whether this capture still serves the delta."""
         dev = data.edge_index.device
         Capture.__init__(self, dev)
         self.model, self.bs, self.k, self.mode = model, batch_size, k, mode
+        self.delta, self.route = delta, _delta_route(delta)
+        model_kwargs = {} if delta is None else {"delta": delta}
         self.anchor = torch.zeros(batch_size, dtype=torch.long, device=dev)
         self.relation = torch.zeros(batch_size, dtype=torch.long, device=dev)
         self.filtered = index_capacity is not None
@@ -223,7 +230,7 @@ class _GraphedPredictStep(Capture):
         self.ws = torch.empty(max(1, ws_bytes // 8), dtype=torch.long, device=dev)
 
         def step():
-            pred = model(data, _candidates(data, self.anchor, self.relation, mode)).float().contiguous()
+            pred = model(data, _candidates(data, self.anchor, self.relation, mode), **model_kwargs).float().contiguous()
             _lib.check(_lib.lib.ultra_filtered_topk(pred.data_ptr(), self.ptr.data_ptr() if self.filtered else None,
                                                     self.index.data_ptr() if self.filtered else None, batch_size, n, k,
                                                     self.ids.data_ptr(), self.scores.data_ptr(), self.count.data_ptr(),
@@ -244,6 +251,25 @@ class _GraphedPredictStep(Capture):
             self.ptr.copy_(ptr, non_blocking=True)
         self.graph.replay()
         return self.ids, self.scores, self.count
+
+
+def _delta_route(delta):
+    """What a captured step remembers of the delta it was recorded with: whether it held facts (the model's route) and which
+    relation-graph object the relation model walked."""
+    if delta is None:
+        return None
+    return (len(delta) > 0, id(delta.relation_graph))
+
+
+def _with_facts(graph, h, r, t):
+    """A copy of `graph` with the edges of the facts appended the way GraphDelta.materialize appends them: the direct edges
+    (h, t, r), then the inverse ones (t, h, r + num_relations / 2)."""
+    out = copy.copy(graph)
+    dev = graph.edge_index.device
+    h, r, t = h.to(dev), r.to(dev), t.to(dev)
+    out.edge_index = torch.cat([graph.edge_index, torch.stack([torch.cat([h, t]), torch.cat([t, h])])], dim=1)
+    out.edge_type = torch.cat([graph.edge_type, torch.cat([r, r + int(graph.num_relations) // 2])])
+    return out
 
 
 def _entity_model(model):
@@ -358,9 +384,17 @@ class Predictor(object):
     every batch of batch_size queries is one hipGraph replay; one capture per direction is made on first use and kept (and
     made again when the model's parameters change or a call's known lists outgrow the capture's buffer).  A last batch
     shorter than batch_size is padded with copies of its last query and the padded rows are dropped.  A model outside the
-    fused inference path (models.NotOnFusedPath) runs batch by batch without a capture.  One step in flight, one stream."""
+    fused inference path (models.NotOnFusedPath) runs batch by batch without a capture.  One step in flight, one stream.
 
-    def __init__(self, model, data, k=10, batch_size=8, filtered_data=None, filtered=True, use_graph=True):
+    A LIVE graph: add_facts(h, r, t) states new facts between existing entities.  They are held in a delta of
+    up to `delta_capacity` facts beside the cached plan of `data` (rspmm.GraphDelta) and join the filter graph, so a tail that
+    was just stated is a known answer from then on; tails / heads / tails_above / heads_above answer on the graph with the
+    facts, exactly as a fresh Predictor on the materialised graph (GraphDelta.materialize) would.  The captured step is made
+    again when the first facts arrive and when the relation graph changes; otherwise a further add_facts costs no capture and
+    no plan.  compact() folds the delta into `data` (a host plan, new captures); add_facts does so itself when the capacity
+    would be exceeded, and explain_* / verify_* do so first when the delta holds facts."""
+
+    def __init__(self, model, data, k=10, batch_size=8, filtered_data=None, filtered=True, use_graph=True, delta_capacity=256):
         _check_k(k)
         if filtered_data is None:
             filtered_data = getattr(data, "filtered_data", None)
@@ -369,6 +403,58 @@ class Predictor(object):
         self.filtered, self.use_graph = bool(filtered), bool(use_graph)
         self._steps = {}
         self._eager_only = False
+        if not isinstance(delta_capacity, int) or delta_capacity < 1:
+            raise ValueError("delta_capacity must be a positive int (facts), got %r" % (delta_capacity,))
+        self.delta_capacity = delta_capacity
+        self._filter_is_data = self.filter_graph is data
+        self._filter_base = self.filter_graph
+        # (a model whose forward takes no `delta` is served by compacting at every add_facts)
+        try:
+            self._takes_delta = "delta" in inspect.signature(getattr(model, "forward", model)).parameters
+        except (TypeError, ValueError):
+            self._takes_delta = False
+        self.delta = rspmm.GraphDelta(data, delta_capacity) if self._takes_delta else None
+
+    # ---- the live graph ----
+    def add_facts(self, h, r, t):
+        """State the facts (h[i], r[i], t[i]) -- ints or vectors; r direct relations, h and t existing entities (ValueError
+        otherwise: the sets of entities and relations are fixed).  Each adds the edges (h, t, r) and (t, h, r + num_relations / 2)
+        to the served graph and to the filter graph; a repeated fact is one more parallel edge.  Returns the number of facts the
+        delta holds afterwards (0 after a compaction: more facts than delta_capacity, or a model without a delta route)."""
+        probe = self.delta if self.delta is not None else rspmm.GraphDelta(self.data, 1)
+        h, r, t = probe.check(h, r, t)
+        if len(h) == 0:
+            return 0 if self.delta is None else len(self.delta)
+        if self.delta is None or len(self.delta) + len(h) > self.delta_capacity:
+            self.compact(extra=(h, r, t))
+            return 0
+        self.delta.add(h, r, t)
+        fh, fr, ft = self.delta.facts[:len(self.delta)].unbind(1)
+        self.filter_graph = self.delta.materialize(self.data) if self._filter_is_data else _with_facts(self._filter_base, fh, fr, ft)
+        return len(self.delta)
+
+    def compact(self, extra=None):
+        """Fold the delta's facts (and `extra` = (h, r, t), checked by the caller) into `data`: the materialised graph becomes the
+        served graph -- its relation graph rebuilt, a host plan on the next query, new captures -- and the delta is emptied."""
+        facts = [] if self.delta is None else [self.delta.facts[:len(self.delta)]]
+        if extra is not None:
+            facts.append(torch.stack(list(extra), dim=1))
+        facts = torch.cat(facts) if facts else torch.zeros(0, 3, dtype=torch.long)
+        if len(facts) == 0:
+            return
+        fh, fr, ft = facts.unbind(1)
+        data = _with_facts(self.data, fh, fr, ft)
+        if getattr(self.data, "relation_graph", None) is not None:
+            tasks.build_relation_graph(data)
+        self._filter_base = data if self._filter_is_data else _with_facts(self._filter_base, fh, fr, ft)
+        self.filter_graph = self._filter_base
+        self.close()
+        self.data = data
+        if self._takes_delta:
+            self.delta = rspmm.GraphDelta(data, self.delta_capacity)
+
+    def _model_kwargs(self):
+        return {} if self.delta is None else {"delta": self.delta}
 
     def tails(self, h, r):
         return self._run(h, r, "tail")
@@ -406,6 +492,8 @@ class Predictor(object):
         if not hasattr(self.model, "visualize_batch"):
             raise TypeError("%s cannot explain its answers: models.Ultra and models.EntityNBFNet (visualize_batch) can"
                             % type(self.model).__name__)
+        if self.delta is not None and len(self.delta):
+            self.compact()      # (explanations walk the graph's own edge list: the added facts become part of it first)
         ids, scores, count = self._run(anchor, relation, mode)
         dev = ids.device
         anchor = torch.as_tensor(anchor, dtype=torch.long, device=dev).flatten()
@@ -456,13 +544,14 @@ class Predictor(object):
         """The captured step of this direction, (re)built when there is none, the weights changed or the known lists of the
         call do not fit its buffer."""
         step = self._steps.get(mode)
-        if step is not None and step.params == param_state(self.model) and (need is None or need <= step.capacity):
+        if step is not None and step.params == param_state(self.model) and (need is None or need <= step.capacity) \
+                and step.delta is self.delta and step.route == _delta_route(self.delta):
             return step
         if step is not None:
             step.release()
             del self._steps[mode]
         capacity = None if need is None else max(2 * need, 1 << 16)
-        step = _GraphedPredictStep(self.model, self.data, self.batch_size, self.k, mode, capacity)
+        step = _GraphedPredictStep(self.model, self.data, self.batch_size, self.k, mode, capacity, delta=self.delta)
         self._steps[mode] = step
         return step
 
@@ -480,6 +569,8 @@ class Predictor(object):
 
     @torch.no_grad()
     def _verify(self, h, r, t, mode):
+        if self.delta is not None and len(self.delta):
+            self.compact()      # (the keep masks run over the graph's own edge list: the added facts become part of it first)
         data, bs = self.data, self.batch_size
         h, r, t = _check_facts(data, h, r, t)
         dev = h.device
@@ -552,7 +643,8 @@ class Predictor(object):
                 ptr, index = known_answers(self.filter_graph, anchor, relation, mode)
             at = 0
             for lo in range(0, n, bs):
-                pred = self.model(data, _candidates(data, anchor[lo:lo + bs], relation[lo:lo + bs], mode)).float()
+                pred = self.model(data, _candidates(data, anchor[lo:lo + bs], relation[lo:lo + bs], mode),
+                                  **self._model_kwargs()).float()
                 b_ptr = None if ptr is None else ptr[lo:lo + len(pred) + 1]
                 if pred.is_cuda:
                     b_out, b_ids, b_scores, b_size = filtered_above(pred, threshold, b_ptr, index)
@@ -618,7 +710,8 @@ class Predictor(object):
                     torch.cuda.synchronize()
                     self._eager_only = True
             for lo in range(start, n, bs):
-                pred = self.model(data, _candidates(data, anchor[lo:lo + bs], relation[lo:lo + bs], mode)).float()
+                pred = self.model(data, _candidates(data, anchor[lo:lo + bs], relation[lo:lo + bs], mode),
+                                  **self._model_kwargs()).float()
                 b_ptr = None if ptr is None else ptr[lo:lo + len(pred) + 1]
                 # the fused kernel on the GPU; the restatement with the same interface elsewhere (as eval._local_rows does)
                 select = filtered_topk if pred.is_cuda else filtered_topk_reference

@@ -18,6 +18,7 @@ What changes underneath: the per-call argsort / ind2ptr / host syncs of the refe
 cached `Plan` (built once per graph) and the HIP kernels of libultra_amd.so.  CPU tensors raise: this
 engine has no CPU path (the reference's `rspmm_*_cpu` names exist only to say so).
 """
+import copy
 import ctypes
 import sys
 from collections import OrderedDict, namedtuple
@@ -25,7 +26,8 @@ from collections import OrderedDict, namedtuple
 import torch
 from torch import autograd
 
-from . import _lib
+from . import _lib, tasks
+from .data import Data
 from ._lib import UltraMat, check, lib, ptr, stream_of
 
 module = sys.modules[__name__]
@@ -373,6 +375,32 @@ class Plan(object):
                          keep=True, weight_epoch=0)
         return out
 
+    def delta_rows(self, relation, input, out, delta, boundary=None, sum="add", mul="mul", point=None):
+        """`out` = forward(relation, input, boundary / point, sum, mul) on THIS plan; afterwards `out` is that forward on a fresh
+        reference-order plan of the graph with `delta`'s added edges (GraphDelta), bit for bit: the rows an added edge points
+        into are recomputed in place, nothing else is written (ultra_rspmm_delta_rows).  One launch sized by the delta's
+        capacity, so a hipGraph that recorded it serves the delta's later contents.  Returns `out`, or None where the engine
+        does not serve the call (general-walk and dense-format plans, rotate messages, misaligned rows) -- nothing was
+        launched then."""
+        if not self.exact:
+            return None
+        if (delta.num_nodes, delta.num_relations) != (self.num_node, self.num_relation) or self.num_in != self.num_node:
+            raise RuntimeError("the delta was made for a graph of %d nodes and %d relations, the plan has %d and %d"
+                               % (delta.num_nodes, delta.num_relations, self.num_node, self.num_relation))
+        if point is not None and boundary is not None:
+            raise RuntimeError("a point boundary excludes `boundary`")
+        _require_gpu(out, delta.count)
+        op = self._forward_operands(relation, input, None, boundary, out, point)
+        if op.out is not out:
+            raise RuntimeError("`out` must have unit stride along its last dimension")
+        operand = delta.operand()
+        rc = lib.ultra_rspmm_delta_rows(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], op.dtype, op.relation, op.input,
+                                        op.boundary, op.rows, op.out_ref, ctypes.byref(operand), stream_of(input))
+        if rc == _lib.ULTRA_ERR_UNSUPPORTED:
+            return None
+        check(rc)
+        return out
+
     def forward_update(self, relation, input, weight, bias, ln_weight, ln_bias, eps, flags, mul="mul", point=None, timed=None,
                        sum="add"):
         """Aggregate (`sum`, `mul`, optional point boundary) AND the layer update
@@ -614,6 +642,150 @@ class Plan(object):
                                             ctypes.byref(ms), ctypes.byref(ms_kernel)))
         self.last_main_kernel_ms = ms_kernel.value
         return ms.value, op.out
+
+
+class GraphDelta(object):
+    """Facts added to a served graph, held beside the cached plan of the base graph instead of rebuilding it.
+
+    A fact (h, r, t) -- r a direct relation, h and t existing entities -- contributes the two edges the loader would create,
+    (h, t, r) and (t, h, r + num_relations / 2).  The MATERIALISED graph of the base graph plus m facts is the edge list
+    [base edges ; m direct edges in insertion order ; m inverse edges in insertion order] (`materialize`); a repeated fact, or
+    one the base graph already states, is one more parallel edge.  Every result on (base graph, delta) is defined as the same
+    call on the materialised graph.
+
+    `capacity` counts facts (twice as many edges).  Prepared at add() time with torch on the edge list's device, into buffers
+    that keep their address (a captured launch reads whatever they hold at replay):
+      col / type  int32 (2 capacity)      the delta's edges in the plan's direction (row = edge_index[0], col = edge_index[1]),
+                                          sorted by (row, col, id) with id = the edge's position in the materialised list
+      rows        int32 (2 capacity)      the distinct rows they point into, ascending;  ptr int32 (2 capacity + 1): their ranges
+      count       int32 (1)               the number of touched rows -- the SAME tensor object across add() calls
+      degree      int64 (num_nodes)       the delta's edges counted at edge_index[1] (what `mean` adds to the base bincount)
+    relation_graph: tasks.build_relation_graph of the materialised list, rebuilt at add(); the previous object is kept when the
+    new adjacency equals the old one (the common case), so its plan and the captures that pin it stay valid."""
+
+    def __init__(self, data, capacity=1024):
+        if not isinstance(capacity, int) or capacity < 1:
+            raise ValueError("capacity must be a positive int (facts), got %r" % (capacity,))
+        self.base = data
+        self.num_nodes, self.num_relations = int(data.num_nodes), int(data.num_relations)
+        self.capacity = capacity
+        dev = data.edge_index.device
+        self.device = dev
+        self.facts = torch.zeros(capacity, 3, dtype=torch.long, device=dev)        # (h, r, t) in insertion order
+        self.num_facts = 0
+        self.version = 0
+        self.col = torch.zeros(2 * capacity, dtype=torch.int32, device=dev)
+        self.type = torch.zeros(2 * capacity, dtype=torch.int32, device=dev)
+        self.rows = torch.zeros(2 * capacity, dtype=torch.int32, device=dev)
+        self.ptr = torch.zeros(2 * capacity + 1, dtype=torch.int32, device=dev)
+        self.count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.degree = torch.zeros(self.num_nodes, dtype=torch.long, device=dev)
+        self.relation_graph = getattr(data, "relation_graph", None)
+        self._materialized = None
+
+    def __len__(self):
+        return self.num_facts
+
+    def edges(self):
+        """(edge_index (2, 2 m), edge_type (2 m)): the appended edges in materialised order -- the m direct ones, then the m
+        inverse ones."""
+        h, r, t = self.facts[:self.num_facts].unbind(1)
+        return torch.stack([torch.cat([h, t]), torch.cat([t, h])]), torch.cat([r, r + self.num_relations // 2])
+
+    def check(self, h, r, t):
+        """(h, r, t) as int64 vectors of one length on the delta's device; ValueError for ids outside the graph or a relation
+        that is not direct (num_nodes and num_relations are fixed: no new entities or relations)."""
+        h, r, t = (torch.as_tensor(v, dtype=torch.long, device=self.device).flatten() for v in (h, r, t))
+        if not (h.shape == r.shape == t.shape):
+            raise ValueError("one head, relation and tail per fact: got %d heads, %d relations and %d tails" % (len(h), len(r), len(t)))
+        if len(h):
+            if bool(((h < 0) | (h >= self.num_nodes) | (t < 0) | (t >= self.num_nodes)).any()):
+                raise ValueError("a fact's head and tail must be existing entities (ids in [0, %d))" % self.num_nodes)
+            if bool(((r < 0) | (r >= self.num_relations // 2)).any()):
+                raise ValueError("a fact is stated through a direct relation (r < num_relations // 2 = %d); its inverse edge "
+                                 "is added with it" % (self.num_relations // 2))
+        return h, r, t
+
+    def add(self, h, r, t):
+        """Append the facts (h[i], r[i], t[i]) (ints or vectors); returns the number of facts held.  ValueError for ids out of
+        range, inverse relations, or more facts than the capacity holds (the caller compacts first: Predictor.add_facts)."""
+        h, r, t = self.check(h, r, t)
+        n = len(h)
+        if self.num_facts + n > self.capacity:
+            raise ValueError("the delta holds %d of %d facts: %d more do not fit" % (self.num_facts, self.capacity, n))
+        if n == 0:
+            return self.num_facts
+        self.facts[self.num_facts:self.num_facts + n] = torch.stack([h, r, t], dim=1)
+        self.num_facts += n
+        self.version += 1
+        self._materialized = None
+        self._prepare()
+        self._rebuild_relation_graph()
+        return self.num_facts
+
+    def _prepare(self):
+        """Sort, unique rows and ptr of the delta's edges, into the fixed buffers."""
+        edge_index, edge_type = self.edges()
+        num_edge = edge_index.shape[1]
+        row, col = edge_index
+        ids = torch.arange(num_edge, device=self.device)
+        order = torch.argsort((row * self.num_nodes + col) * num_edge + ids)
+        row, col, edge_type = row[order], col[order], edge_type[order]
+        touched, counts = torch.unique_consecutive(row, return_counts=True)
+        self.col[:num_edge] = col.to(torch.int32)
+        self.type[:num_edge] = edge_type.to(torch.int32)
+        self.rows[:len(touched)] = touched.to(torch.int32)
+        self.ptr[1:len(touched) + 1] = counts.cumsum(0).to(torch.int32)
+        self.degree.copy_(torch.bincount(edge_index[1], minlength=self.num_nodes))
+        self.count.fill_(len(touched))
+
+    def _rebuild_relation_graph(self):
+        if self.relation_graph is None:
+            return
+        edge_index, edge_type = self.edges()
+        full = Data(edge_index=torch.cat([self.base.edge_index, edge_index], dim=1),
+                    edge_type=torch.cat([self.base.edge_type, edge_type]), num_nodes=self.num_nodes,
+                    num_relations=self.num_relations)
+        new, old = tasks.build_relation_graph(full).relation_graph, self.relation_graph
+        old_bits, new_bits = getattr(old, "adjacency_bits", None), getattr(new, "adjacency_bits", None)
+        if old_bits is not None and new_bits is not None and old_bits.device == new_bits.device:
+            same = old_bits.shape == new_bits.shape and torch.equal(old_bits, new_bits)
+        else:
+            same = (old.edge_index.shape == new.edge_index.shape and torch.equal(old.edge_index, new.edge_index)
+                    and torch.equal(old.edge_type, new.edge_type))
+        if not same:
+            self.relation_graph = new
+
+    def materialize(self, data=None):
+        """`data` (default: the base graph) with the delta's edges appended in materialised order, and the delta's relation
+        graph: a copy that shares every other field.  Kept until the next add(), so the plan cache sees one graph."""
+        data = self.base if data is None else data
+        hit = self._materialized
+        if hit is not None and hit[0] is data:
+            return hit[1]
+        edge_index, edge_type = self.edges()
+        out = copy.copy(data)
+        out.edge_index = torch.cat([data.edge_index, edge_index.to(data.edge_index.device)], dim=1)
+        out.edge_type = torch.cat([data.edge_type, edge_type.to(data.edge_type.device)])
+        if self.relation_graph is not None and data is self.base:
+            out.relation_graph = self.relation_graph
+        self._materialized = (data, out)
+        return out
+
+    def live_view(self, data):
+        """`data` with the delta's relation graph in place of its own and nothing else changed (the edge list stays the base
+        graph's, so the cached plan is found): what the models walk with this delta beside it.  One object per relation graph."""
+        hit = getattr(self, "_live", None)
+        if hit is None or hit[0] is not data or hit[1].relation_graph is not self.relation_graph:
+            view = copy.copy(data)
+            view.relation_graph = self.relation_graph
+            hit = self._live = (data, view)
+        return hit[1]
+
+    def operand(self):
+        """The delta as the engine takes it (ultra_delta); valid while this object lives."""
+        return _lib.UltraDelta(self.rows.data_ptr(), self.ptr.data_ptr(), self.col.data_ptr(), self.type.data_ptr(),
+                               self.count.data_ptr(), self.rows.numel(), self.col.numel())
 
 
 # ---- plan cache: the graph is static across the 12 rspmm calls of a forward and across batches ----
