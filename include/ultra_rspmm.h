@@ -269,6 +269,31 @@ int32_t ultra_rspmm_delta_rows(ultra_plan *plan, int32_t sum, int32_t mul, int32
                                const ultra_mat *output, const ultra_delta *delta, void *stream);
 
 /*
+ * RETRACTED facts as TOMBSTONES on the same cached plan, with or without added ones (csrc/delta_kernels.hip).  A
+ * removed edge changes exactly the output row it points into, so retraction is the operation above with dead base edges skipped:
+ *   delta->row_dev      the UNION of the rows an added edge points into and the rows a removed edge points into, ascending
+ *                       (a row touched by removals only has an empty delta->ptr_dev range)
+ *   removed->ptr_dev    int32 [delta->capacity_rows + 1]  keys [ptr[k], ptr[k + 1]) belong to touched row k
+ *   removed->col_dev / type_dev  int32 [capacity_keys]    the DISTINCT dead (col, type) keys of each touched row, sorted by
+ *                       (col, type): every base edge of that row with that col and type is absent (all duplicates go)
+ * ultra_rspmm_edit_rows recomputes the touched rows as the same merge, where a base edge whose (col, type) is among its row's keys
+ * takes no part; tombstones never apply to the delta's own edges.  On ULTRA_PLAN_EXACT_ORDER plans the output equals
+ * ultra_rspmm_forward on a fresh reference-order plan of [base edges without the dead ones, in base order ; delta edges] bit for
+ * bit.  A touched row left with NO edge holds what that walk writes for an edge-less row: the reduction's start value (0; the
+ * largest / lowest FINITE number under min / max) met by the boundary epilogue -- the boundary row under a dense or an on-row
+ * point boundary, 0 under an off-row point boundary with min / max.  Grid, capture, served cases, error codes and the handling of
+ * out-of-range indices are those of ultra_rspmm_delta_rows (a key is only compared, never used as an index); the kernel reads
+ * nothing per edge of the graph.  removed == NULL computes exactly ultra_rspmm_delta_rows.
+ */
+typedef struct {
+    const int32_t *ptr_dev, *col_dev, *type_dev;
+    int64_t capacity_keys;
+} ultra_tombstones;
+int32_t ultra_rspmm_edit_rows(ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const ultra_mat *relation,
+                              const ultra_mat *input, const ultra_mat *boundary, const int64_t *point_rows_dev,
+                              const ultra_mat *output, const ultra_delta *delta, const ultra_tombstones *removed, void *stream);
+
+/*
  * Aggregate + layer update in ONE launch (fp32 inference path of GeneralizedRelationalConv.forward,
  * /root/reference/ultra/layers.py:84-131, 190-240, with the residual of /root/reference/ultra/models.py:158-160):
  *

@@ -1,7 +1,7 @@
 """Answer one link-prediction query on a dataset of triple files: the k entities the model predicts, with their scores.
 
     python tools/predict.py --data-root DIR [--ckpt FILE] --head NAME --relation NAME [--inverse] [-k 10] [--unfiltered] [--explain]
-                            [--add-fact H R T]...
+                            [--add-fact H R T]... [--remove-fact H R T]...
     python tools/predict.py --data-root DIR [--ckpt FILE] --verify (--head NAME --relation NAME --tail NAME | --triples FILE) [--inverse]
 
 DIR holds train.txt / valid.txt / test.txt (`head relation tail` per line) and optionally entities.dict / relations.dict
@@ -12,7 +12,9 @@ tool says so.  --explain: under every answer, the paths the model's score rests 
 explain_heads) with their weights; a relation walked against its direction is printed as NAME^-1.
 
 --add-fact H R T (repeatable) states a fact between known entities before the query is answered (Predictor.add_facts): the
-graph served is the dataset's plus these facts, and their tails and heads count as known answers.
+graph served is the dataset's plus these facts, and their tails and heads count as known answers.  --remove-fact H R T
+(repeatable) retracts a fact before the query is answered (Predictor.remove_facts): every edge that states it leaves the graph
+served and the known answers, so its tail can be predicted again.  Both kinds are applied in command-line order.
 
 --verify judges facts the dataset may already state: every (head, relation, tail) -- one from the command line, or the
 `head relation tail` lines of FILE -- is scored on the graph WITHOUT itself and its inverse edge (Predictor.verify_tails; with
@@ -50,8 +52,16 @@ def main(argv=None):
     ap.add_argument("-k", type=int, default=10)
     ap.add_argument("--unfiltered", action="store_true")
     ap.add_argument("--explain", action="store_true", help="print the top paths behind every answer")
-    ap.add_argument("--add-fact", nargs=3, action="append", default=[], metavar=("H", "R", "T"),
+    class Edit(argparse.Action):       # (one list for both kinds: they are applied in command-line order)
+        def __call__(self, parser, namespace, values, option_string=None):
+            namespace.edits = getattr(namespace, "edits", None) or []
+            namespace.edits.append((option_string == "--add-fact", tuple(values)))
+
+    ap.add_argument("--add-fact", nargs=3, action=Edit, metavar=("H", "R", "T"),
                     help="state the fact (H, R, T) before the query; repeatable")
+    ap.add_argument("--remove-fact", nargs=3, action=Edit, metavar=("H", "R", "T"),
+                    help="retract the fact (H, R, T) before the query; repeatable, applied in order with --add-fact")
+    ap.set_defaults(edits=[])
     args = ap.parse_args(argv)
     if args.verify:
         if not (args.triples or (args.head and args.relation and args.tail)):
@@ -70,7 +80,7 @@ def main(argv=None):
         if any(len(f) != 3 for f in facts):
             sys.exit("--triples: every line is `head relation tail`")
     for h_name, r_name, t_name in (facts if facts is not None else [(args.head, args.relation, args.head)]) \
-            + [tuple(f) for f in args.add_fact]:
+            + [f for _, f in args.edits]:
         for name, vocab, what in ((h_name, ent, "entity"), (r_name, rel, "relation"), (t_name, ent, "entity")):
             if name not in vocab:
                 sys.exit("unknown %s %r" % (what, name))
@@ -93,9 +103,20 @@ def main(argv=None):
             print("%-28s %-24s %-28s %12.6g  %6d / %d" % (f[0], f[1], f[2], s, k, n + 1))
         return
     predictor = predict.Predictor(model, data, k=args.k, batch_size=1, filtered=not args.unfiltered)
-    if args.add_fact:
-        held = predictor.add_facts(*([vocab.index(f[i]) for f in args.add_fact] for i, vocab in ((0, ent), (1, rel), (2, ent))))
-        print("%d fact(s) stated on top of the dataset%s" % (len(args.add_fact), "" if held else " (folded into the graph)"))
+    at = 0
+    while at < len(args.edits):        # (runs of one kind go in one call)
+        end = at
+        while end < len(args.edits) and args.edits[end][0] == args.edits[at][0]:
+            end += 1
+        run = [f for _, f in args.edits[at:end]]
+        ids = [[vocab.index(f[i]) for f in run] for i, vocab in ((0, ent), (1, rel), (2, ent))]
+        if args.edits[at][0]:
+            held = predictor.add_facts(*ids)
+            print("%d fact(s) stated on top of the dataset%s" % (len(run), "" if held else " (folded into the graph)"))
+        else:
+            took = predictor.remove_facts(*ids).tolist()
+            print("%d fact(s) retracted from the dataset: %s edge(s) removed" % (len(run), " + ".join(str(n) for n in took)))
+        at = end
     anchor = torch.tensor([ent.index(args.head)], device=dev)
     relation = torch.tensor([rel.index(args.relation)], device=dev)
     why = None

@@ -56,6 +56,12 @@ class UltraDelta(ctypes.Structure):
                 ("capacity_edges", ctypes.c_int64)]
 
 
+class UltraTombstones(ctypes.Structure):
+    """ultra_tombstones: the dead (col, type) keys of a graph delta's touched rows (ultra_rspmm_edit_rows)."""
+    _fields_ = [("ptr_dev", ctypes.c_void_p), ("col_dev", ctypes.c_void_p), ("type_dev", ctypes.c_void_p),
+                ("capacity_keys", ctypes.c_int64)]
+
+
 class PlanOpts(ctypes.Structure):
     _fields_ = [("seg_len", ctypes.c_int32), ("g_max", ctypes.c_int32), ("flags", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)]
@@ -104,6 +110,8 @@ def _load():
     lib.ultra_rspmm_forward_masked.argtypes = [vp, i32, i32, i32, vp, matp, matp, matp, matp, vp]
     lib.ultra_rspmm_forward_masked_samples.argtypes = [vp, i32, i32, i32, vp, i64, matp, matp, matp, matp, vp]
     lib.ultra_rspmm_delta_rows.argtypes = [vp, i32, i32, i32, matp, matp, matp, vp, matp, ctypes.POINTER(UltraDelta), vp]
+    lib.ultra_rspmm_edit_rows.argtypes = [vp, i32, i32, i32, matp, matp, matp, vp, matp, ctypes.POINTER(UltraDelta),
+                                          ctypes.POINTER(UltraTombstones), vp]
     lib.ultra_rspmm_forward_onehot.argtypes = [vp, i32, vp, matp, matp, vp, matp, matp, vp]
     lib.ultra_rspmm_forward_point.argtypes = [vp, i32, i32, i32, vp, matp, matp, vp, matp, matp, vp]
     lib.ultra_rspmm_forward_update.argtypes = [vp, i32, i32, matp, matp, vp, matp, matp, vp, vp, vp, vp, ctypes.c_float, i32, matp, vp]

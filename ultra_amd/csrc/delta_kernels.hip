@@ -16,6 +16,16 @@
 //
 // A hub row (longer than the plan's seg_len, a chain row of the base walk) is walked here by ONE group as one dependent
 // chain: loads are issued DELTA_BATCH edges ahead, the additions stay in order.
+//
+// RETRACTED facts are TOMBSTONES on the same plan (ultra_rspmm_edit_rows).  A removed edge changes the one row it
+// points into, so the touched rows are the union of both kinds and rspmm_edit_rows_kernel is the merge above with one more
+// cursor: per touched row the distinct dead (col, type) keys, sorted; a base edge whose (col, type) is among them takes no part
+// (base edges of one col come in edge-id order, not type order: the keys of that col are scanned).  The base row's (col, type)
+// pairs are read sixteen at a time, one per lane of the group, and handed round by lane shuffles.  A subsequence of a sorted
+// row is still sorted, so the bit-equality argument is the same one.  A row left with NO edge holds what the reference-order walk
+// writes for an edge-less row: the reduction's start value (0; the largest / lowest finite number under min / max, NaryOp::zero
+// of the reference, never an infinity) met by the boundary epilogue -- the boundary row under a dense or an on-row point
+// boundary, 0 under an off-row point boundary with min / max, nothing without a boundary.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -118,6 +128,130 @@ __global__ void __launch_bounds__(DELTA_THREADS) rspmm_delta_rows_kernel(const D
     }
 }
 
+struct EditParams : DeltaParams {
+    const int32_t *t_ptr, *t_col, *t_type;               // the tombstones: per touched row its dead (col, type) keys, sorted
+    int32_t cap_keys;
+};
+
+// rspmm_delta_rows_kernel with the dead base edges left out.  (bi, bcol, btype) is always the next LIVE base edge of the row.
+template <typename T, int SUM, int MUL>
+__global__ void __launch_bounds__(DELTA_THREADS) rspmm_edit_rows_kernel(const EditParams p) {
+    constexpr int VEC = 16 / (int)sizeof(T);      // elements per 16-byte chunk
+    using P = Pack<T, VEC>;
+    const int l16 = threadIdx.x & 15;
+    const long long group = (long long)blockIdx.x * (DELTA_THREADS / 16) + (threadIdx.x >> 4);
+    const int k = (int)(group / p.n_outer), outer = (int)(group - (long long)k * p.n_outer);
+    const int live = min(max(*p.d_count, 0), p.cap_rows);
+    if (k >= live) return;
+    const int row = p.d_row[k];
+    if (row < 0 || row >= p.num_out) return;      // (a delta prepared for another graph: nothing is written)
+    const int i = p.row_ptr[row];
+    const int ie = p.row_ptr[row + 1];
+    const int j = min(max(p.d_ptr[k], 0), p.cap_edges);
+    const int je = min(max(p.d_ptr[k + 1], j), p.cap_edges);
+    const int q = min(max(p.t_ptr[k], 0), p.cap_keys);
+    const int qe = min(max(p.t_ptr[k + 1], q), p.cap_keys);
+    if (i < 0 || ie < i || ie > p.num_edge) return;
+
+    const T *rel = reinterpret_cast<const T *>(p.rel.ptr) + outer * p.rel.stride_outer;
+    const T *x = reinterpret_cast<const T *>(p.x.ptr) + outer * p.x.stride_outer;
+    T *dst = reinterpret_cast<T *>(p.out) + outer * p.out_stride_outer + (long long)row * p.out_stride_row;
+    const long long bnd_row = p.bnd_rows ? p.bnd_rows[outer] : -1;
+
+    // (every lane of the group takes every trip, the lanes beyond a short row on chunk 0 without storing: the base indices
+    // below pass between the group's lanes)
+    for (int dbase = 0; dbase < p.row_len; dbase += 16 * VEC) {
+        const bool dvalid = dbase + VEC * l16 < p.row_len;
+        const int d0 = dvalid ? dbase + VEC * l16 : 0;
+        int bi = i - 1, dj = j, kq = q;
+        int bcol = 0, btype = 0, dcol = dj < je ? p.d_col[dj] : 0;
+        // the base row's (col, type) pairs, sixteen at a time: lane l holds pair cbase + l, one coalesced load for sixteen
+        // steps of the walk instead of a dependent load per step
+        int cbase = i - 16, ccol = 0, ctype = 0;
+        int kcol = kq < qe ? p.t_col[kq] : INT32_MAX;    // the key under the cursor
+        // step to the next base edge that carries no tombstone (the key cursor only moves forward: cols ascend along the row)
+        const auto next_base = [&]() {
+            for (++bi; bi < ie; ++bi) {
+                if (bi >= cbase + 16) {
+                    cbase = bi;
+                    const int mine = min(bi + l16, ie - 1);
+                    ccol = p.col[mine], ctype = p.type[mine];
+                }
+                bcol = __shfl(ccol, bi - cbase, 16), btype = __shfl(ctype, bi - cbase, 16);
+                while (kcol < bcol) {
+                    ++kq;
+                    kcol = kq < qe ? p.t_col[kq] : INT32_MAX;
+                }
+                if (kcol != bcol) return;                        // (no key at this col: the edge lives)
+                bool dead = false;
+                for (int s = kq; s < qe && p.t_col[s] == bcol; ++s) dead |= p.t_type[s] == btype;
+                if (!dead) return;
+            }
+        };
+        next_base();
+        P acc;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc.v[e] = nary_zero<T, SUM>();
+        while (bi < ie || dj < je) {
+            int c[DELTA_BATCH], t[DELTA_BATCH];
+            bool take[DELTA_BATCH];
+#pragma unroll
+            for (int u = 0; u < DELTA_BATCH; ++u) {
+                c[u] = 0, t[u] = 0, take[u] = false;
+                if (bi < ie && (dj >= je || bcol <= dcol)) {        // (equal col: the base edge has the lower edge id)
+                    c[u] = bcol, t[u] = btype, take[u] = true;
+                    next_base();
+                } else if (dj < je) {
+                    c[u] = dcol, t[u] = p.d_type[dj], take[u] = true;
+                    ++dj;
+                    if (dj < je) dcol = p.d_col[dj];
+                }
+                // (an index outside the operands is never dereferenced: such an edge reads row 0 and is left out of the reduction)
+                if (c[u] < 0 || c[u] >= p.num_in || t[u] < 0 || t[u] >= p.num_rel) c[u] = 0, t[u] = 0, take[u] = false;
+            }
+            P xv[DELTA_BATCH], rv[DELTA_BATCH];
+#pragma unroll
+            for (int u = 0; u < DELTA_BATCH; ++u) {
+                xv[u] = *reinterpret_cast<const P *>(x + (long long)c[u] * p.x.stride_row + d0);
+                rv[u] = *reinterpret_cast<const P *>(rel + (long long)t[u] * p.rel.stride_row + d0);
+            }
+#pragma unroll
+            for (int u = 0; u < DELTA_BATCH; ++u) {
+                if (take[u]) {
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) acc.v[e] = nary<T, SUM>(acc.v[e], binary<T, MUL>(rv[u].v[e], xv[u].v[e]));
+                }
+            }
+        }
+        // the boundary epilogue of the reference-order kernels; a row with no surviving edge meets it with the start value
+        if (p.has_bnd && (bnd_row < 0 || bnd_row == row)) {
+            const P b = *reinterpret_cast<const P *>(reinterpret_cast<const T *>(p.bnd.ptr) + outer * p.bnd.stride_outer +
+                                                     (bnd_row < 0 ? (long long)row * p.bnd.stride_row : 0) + d0);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc.v[e] = nary<T, SUM>(acc.v[e], b.v[e]);
+        } else if (SUM != ULTRA_SUM_ADD && p.has_bnd) {     // (min / max: a point boundary stands for zeros elsewhere)
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc.v[e] = nary<T, SUM>(acc.v[e], T(0));
+        }
+        if (dvalid) *reinterpret_cast<P *>(dst + d0) = acc;
+    }
+}
+
+template <typename T>
+static hipError_t launch_edit(int sum, int mul, const EditParams &p, unsigned grid, hipStream_t s) {
+#define ULTRA_EDIT_CASE(S_, M_)                                                                                     \
+    case S_ * 2 + M_:                                                                                               \
+        hipLaunchKernelGGL((rspmm_edit_rows_kernel<T, S_, M_>), dim3(grid), dim3(DELTA_THREADS), 0, s, p);           \
+        break;
+    switch (sum * 2 + mul) {
+        ULTRA_EDIT_CASE(0, 0) ULTRA_EDIT_CASE(0, 1) ULTRA_EDIT_CASE(1, 0) ULTRA_EDIT_CASE(1, 1) ULTRA_EDIT_CASE(2, 0)
+        ULTRA_EDIT_CASE(2, 1)
+        default: return hipErrorInvalidValue;
+    }
+#undef ULTRA_EDIT_CASE
+    return hipGetLastError();
+}
+
 template <typename T>
 static hipError_t launch_delta(int sum, int mul, const DeltaParams &p, unsigned grid, hipStream_t s) {
 #define ULTRA_DELTA_CASE(S_, M_)                                                                                    \
@@ -133,21 +267,22 @@ static hipError_t launch_delta(int sum, int mul, const DeltaParams &p, unsigned 
     return hipGetLastError();
 }
 
-static int delta_invalid(const std::string &msg) {
-    set_error("ultra_rspmm_delta_rows: " + msg);
+static int delta_invalid(const char *who, const std::string &msg) {
+    set_error(std::string(who) + ": " + msg);
     return ULTRA_ERR_INVALID;
 }
-static int delta_unsupported(const std::string &msg) {
-    set_error("ultra_rspmm_delta_rows: " + msg);
+static int delta_unsupported(const char *who, const std::string &msg) {
+    set_error(std::string(who) + ": " + msg);
     return ULTRA_ERR_UNSUPPORTED;
 }
 
-static int delta_check_mat(const ultra_mat *m, const char *name, int64_t min_rows, int64_t n_outer, int64_t row_len) {
-    if (!m || !m->ptr) return delta_invalid(std::string(name) + " is NULL");
-    if (m->n_outer != n_outer) return delta_invalid(std::string(name) + ": n_outer mismatch");
-    if (m->row_len != row_len) return delta_invalid(std::string(name) + ": row_len mismatch");
-    if (m->n_row < min_rows) return delta_invalid(std::string(name) + ": too few rows");
-    if (m->stride_row < row_len && m->n_row > 1) return delta_invalid(std::string(name) + ": stride_row < row_len");
+static int delta_check_mat(const char *who, const ultra_mat *m, const char *name, int64_t min_rows, int64_t n_outer,
+                           int64_t row_len) {
+    if (!m || !m->ptr) return delta_invalid(who, std::string(name) + " is NULL");
+    if (m->n_outer != n_outer) return delta_invalid(who, std::string(name) + ": n_outer mismatch");
+    if (m->row_len != row_len) return delta_invalid(who, std::string(name) + ": row_len mismatch");
+    if (m->n_row < min_rows) return delta_invalid(who, std::string(name) + ": too few rows");
+    if (m->stride_row < row_len && m->n_row > 1) return delta_invalid(who, std::string(name) + ": stride_row < row_len");
     return ULTRA_OK;
 }
 
@@ -155,48 +290,50 @@ static bool delta_vec_ok(const ultra_mat *m, int64_t step) {
     return (reinterpret_cast<uintptr_t>(m->ptr) & 15u) == 0 && m->stride_row % step == 0 && m->stride_outer % step == 0;
 }
 
-}  // namespace ultra
-
-using namespace ultra;
-
-extern "C" int32_t ultra_rspmm_delta_rows(ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const ultra_mat *relation,
-                                          const ultra_mat *input, const ultra_mat *boundary, const int64_t *point_rows_dev,
-                                          const ultra_mat *output, const ultra_delta *delta, void *stream) {
-    ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);
-    if (!plan) return delta_invalid("plan is NULL");
-    if (sum < 0 || sum > 2) return delta_invalid("unknown sum code");
-    if (mul != ULTRA_MUL_MUL && mul != ULTRA_MUL_ADD && mul != ULTRA_MUL_ROTATE) return delta_invalid("unknown mul code");
-    if (dtype != ULTRA_F32 && dtype != ULTRA_F64) return delta_invalid("dtype must be ULTRA_F32 or ULTRA_F64");
-    if (!delta) return delta_invalid("delta is NULL");
+// Both entries: the checks, then rspmm_delta_rows_kernel (removed == NULL) or rspmm_edit_rows_kernel.
+static int delta_rows_impl(const char *who, ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const ultra_mat *relation,
+                           const ultra_mat *input, const ultra_mat *boundary, const int64_t *point_rows_dev,
+                           const ultra_mat *output, const ultra_delta *delta, const ultra_tombstones *removed, void *stream) {
+    if (!plan) return delta_invalid(who, "plan is NULL");
+    if (sum < 0 || sum > 2) return delta_invalid(who, "unknown sum code");
+    if (mul != ULTRA_MUL_MUL && mul != ULTRA_MUL_ADD && mul != ULTRA_MUL_ROTATE) return delta_invalid(who, "unknown mul code");
+    if (dtype != ULTRA_F32 && dtype != ULTRA_F64) return delta_invalid(who, "dtype must be ULTRA_F32 or ULTRA_F64");
+    if (!delta) return delta_invalid(who, "delta is NULL");
     if (delta->capacity_rows < 0 || delta->capacity_edges < 0 || delta->capacity_rows >= (1ll << 30) ||
         delta->capacity_edges >= (1ll << 30))
-        return delta_invalid("delta: capacities must lie in [0, 2^30)");
-    if (!output || !output->ptr) return delta_invalid("output is NULL");
+        return delta_invalid(who, "delta: capacities must lie in [0, 2^30)");
+    if (removed && (removed->capacity_keys < 0 || removed->capacity_keys >= (1ll << 30)))
+        return delta_invalid(who, "removed: capacity_keys must lie in [0, 2^30)");
+    if (!output || !output->ptr) return delta_invalid(who, "output is NULL");
     const int64_t n_outer = output->n_outer, row_len = output->row_len;
-    if (n_outer < 0 || row_len <= 0) return delta_invalid("output: negative n_outer or empty row_len");
+    if (n_outer < 0 || row_len <= 0) return delta_invalid(who, "output: negative n_outer or empty row_len");
     if (n_outer == 0 || delta->capacity_rows == 0) return ULTRA_OK;
     if (!delta->row_dev || !delta->ptr_dev || !delta->col_dev || !delta->type_dev || !delta->count_dev)
-        return delta_invalid("delta: a NULL array");
+        return delta_invalid(who, "delta: a NULL array");
+    // (ptr_dev is read for every touched row; the key arrays only below a non-zero capacity)
+    if (removed && (!removed->ptr_dev || (removed->capacity_keys > 0 && (!removed->col_dev || !removed->type_dev))))
+        return delta_invalid(who, "removed: a NULL array");
     int rc;
-    if ((rc = delta_check_mat(output, "output", plan->num_out, n_outer, row_len))) return rc;
-    if ((rc = delta_check_mat(relation, "relation", plan->num_rel, n_outer, row_len))) return rc;
-    if ((rc = delta_check_mat(input, "input", plan->num_in, n_outer, row_len))) return rc;
-    if (point_rows_dev && !boundary) return delta_invalid("a point boundary needs its value rows");
-    if (boundary && (rc = delta_check_mat(boundary, "boundary", point_rows_dev ? 1 : plan->num_out, n_outer, row_len))) return rc;
-    if (mul == ULTRA_MUL_ROTATE) return delta_unsupported("rotate messages are not served");
+    if ((rc = delta_check_mat(who, output, "output", plan->num_out, n_outer, row_len))) return rc;
+    if ((rc = delta_check_mat(who, relation, "relation", plan->num_rel, n_outer, row_len))) return rc;
+    if ((rc = delta_check_mat(who, input, "input", plan->num_in, n_outer, row_len))) return rc;
+    if (point_rows_dev && !boundary) return delta_invalid(who, "a point boundary needs its value rows");
+    if (boundary && (rc = delta_check_mat(who, boundary, "boundary", point_rows_dev ? 1 : plan->num_out, n_outer, row_len)))
+        return rc;
+    if (mul == ULTRA_MUL_ROTATE) return delta_unsupported(who, "rotate messages are not served");
     if ((plan->flags & ULTRA_PLAN_DENSE) || !(plan->flags & ULTRA_PLAN_EXACT_ORDER))
-        return delta_unsupported("served by ULTRA_PLAN_EXACT_ORDER plans in the sparse format only");
+        return delta_unsupported(who, "served by ULTRA_PLAN_EXACT_ORDER plans in the sparse format only");
     const int64_t step = dtype == ULTRA_F32 ? 4 : 2;      // elements per 16 bytes
     if (row_len % step != 0 || !delta_vec_ok(output, step) || !delta_vec_ok(relation, step) || !delta_vec_ok(input, step) ||
         (boundary && !delta_vec_ok(boundary, step)))
-        return delta_unsupported("rows must be whole 16-byte chunks at 16-byte aligned addresses and strides");
+        return delta_unsupported(who, "rows must be whole 16-byte chunks at 16-byte aligned addresses and strides");
     if (plan->num_out == 0 || plan->num_in == 0 || plan->num_rel == 0) return ULTRA_OK;
     const int64_t groups = delta->capacity_rows * n_outer;
     const int64_t grid = (groups + DELTA_THREADS / 16 - 1) / (DELTA_THREADS / 16);
-    if (grid >= (1ll << 31)) return delta_invalid("capacity_rows * n_outer exceeds the launch grid");
+    if (grid >= (1ll << 31)) return delta_invalid(who, "capacity_rows * n_outer exceeds the launch grid");
     if ((rc = ultra_plan_upload(plan))) return rc;
 
-    DeltaParams p;
+    EditParams p;
     p.row_ptr = plan->d.row_ptr, p.col = plan->d.col, p.type = plan->d.type;
     p.d_row = delta->row_dev, p.d_ptr = delta->ptr_dev, p.d_col = delta->col_dev, p.d_type = delta->type_dev;
     p.d_count = delta->count_dev;
@@ -212,14 +349,39 @@ extern "C" int32_t ultra_rspmm_delta_rows(ultra_plan *plan, int32_t sum, int32_t
     p.n_outer = (int32_t)n_outer, p.row_len = (int32_t)row_len;
     p.num_out = (int32_t)plan->num_out, p.num_in = (int32_t)plan->num_in, p.num_rel = (int32_t)plan->num_rel;
     p.num_edge = plan->num_edge;
-    if (n_outer >= (1ll << 31) || row_len >= (1ll << 31)) return delta_invalid("n_outer / row_len exceed 2^31");
+    p.t_ptr = removed ? removed->ptr_dev : nullptr, p.t_col = removed ? removed->col_dev : nullptr;
+    p.t_type = removed ? removed->type_dev : nullptr, p.cap_keys = removed ? (int32_t)removed->capacity_keys : 0;
+    if (n_outer >= (1ll << 31) || row_len >= (1ll << 31)) return delta_invalid(who, "n_outer / row_len exceed 2^31");
     (void)hipGetLastError();   // drop any stale error left by other users of the HIP runtime
     const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const hipError_t e = dtype == ULTRA_F32 ? launch_delta<float>(sum, mul, p, (unsigned)grid, s)
-                                            : launch_delta<double>(sum, mul, p, (unsigned)grid, s);
+    const DeltaParams &dp = p;
+    const bool f32 = dtype == ULTRA_F32;
+    const hipError_t e = removed ? (f32 ? launch_edit<float>(sum, mul, p, (unsigned)grid, s) : launch_edit<double>(sum, mul, p, (unsigned)grid, s))
+                                 : (f32 ? launch_delta<float>(sum, mul, dp, (unsigned)grid, s) : launch_delta<double>(sum, mul, dp, (unsigned)grid, s));
     if (e != hipSuccess) {
-        set_error(std::string("rspmm_delta_rows_kernel launch: ") + hipGetErrorString(e));
+        set_error(std::string(removed ? "rspmm_edit_rows_kernel" : "rspmm_delta_rows_kernel") + " launch: " + hipGetErrorString(e));
         return ULTRA_ERR_HIP;
     }
     return ULTRA_OK;
+}
+
+}  // namespace ultra
+
+using namespace ultra;
+
+extern "C" int32_t ultra_rspmm_delta_rows(ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const ultra_mat *relation,
+                                          const ultra_mat *input, const ultra_mat *boundary, const int64_t *point_rows_dev,
+                                          const ultra_mat *output, const ultra_delta *delta, void *stream) {
+    ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);
+    return delta_rows_impl("ultra_rspmm_delta_rows", plan, sum, mul, dtype, relation, input, boundary, point_rows_dev, output, delta,
+                           nullptr, stream);
+}
+
+extern "C" int32_t ultra_rspmm_edit_rows(ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const ultra_mat *relation,
+                                         const ultra_mat *input, const ultra_mat *boundary, const int64_t *point_rows_dev,
+                                         const ultra_mat *output, const ultra_delta *delta, const ultra_tombstones *removed,
+                                         void *stream) {
+    ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);
+    return delta_rows_impl(removed ? "ultra_rspmm_edit_rows" : "ultra_rspmm_delta_rows", plan, sum, mul, dtype, relation, input,
+                           boundary, point_rows_dev, output, delta, removed, stream);
 }

@@ -169,13 +169,15 @@ class GeneralizedRelationalConv(nn.Module):
                 )
 
     def forward(self, input, query, boundary, edge_index, edge_type, size, edge_weight=None, delta=None):
-        """delta (rspmm.GraphDelta, inference only): the layer on the graph with the delta's added facts, computed on the cached
-        plan of (edge_index, edge_type) -- _propagate_delta; where the engine does not serve that, on the materialised edge list."""
-        if delta is not None and len(delta):
+        """delta (rspmm.GraphDelta, inference only): the layer on the graph with the delta's added and without its retracted
+        facts, computed on the cached plan of (edge_index, edge_type) -- _propagate_delta; where the engine does not serve that,
+        on the materialised edge list."""
+        if delta is not None and delta.edited:
             out = self._forward_impl(input, query, boundary, edge_index, edge_type, size, edge_weight, residual=False, delta=delta)
             if out is not None:
                 return out
             extra_index, extra_type = delta.edges()
+            edge_index, edge_type = delta.surviving(edge_index, edge_type)
             edge_index, edge_type = torch.cat([edge_index, extra_index], dim=1), torch.cat([edge_type, extra_type])
         return self._forward_impl(input, query, boundary, edge_index, edge_type, size, edge_weight, residual=False)
 
@@ -316,9 +318,10 @@ class GeneralizedRelationalConv(nn.Module):
         return self.aggregate_func in ("sum", "mean", "max", "min") and self.message_func in self.message2mul
 
     def _propagate_delta(self, edge_index, size, input, relation, boundary, edge_type, delta, residual=False):
-        """The layer on the graph WITH the added facts of `delta` (rspmm.GraphDelta), on the cached plan of the base graph: the
-        aggregate by plan.forward (the two-launch form: the one-launch layer would update rows before they are fixed), then
-        plan.delta_rows, which recomputes the rows an added edge points into in the reference's order, then the update.  Equals
+        """The layer on the graph WITH the added and WITHOUT the retracted facts of `delta` (rspmm.GraphDelta), on the cached plan
+        of the base graph: the aggregate by plan.forward (the two-launch form: the one-launch layer would update rows before they
+        are fixed), then plan.delta_rows -- plan.edit_rows once the delta holds tombstones -- which recomputes the rows an added
+        or a removed edge points into in the reference's order, then the update.  Equals
         the layer on delta.materialize(...) bit for bit.  Inference only; sum / mean / max / min, TransE / DistMult; a dense or a
         point boundary (layer 0 included: its closed form does not know the delta).  Returns None where the engine does not
         serve the call (a re-associating or dense-format plan, misaligned rows): the caller materialises."""
@@ -333,12 +336,13 @@ class GeneralizedRelationalConv(nn.Module):
         plan = rspmm.get_plan(edge_index, edge_type, num_node, relation.shape[1])
         sum = {"sum": "add", "mean": "add"}.get(self.aggregate_func, self.aggregate_func)
         mul = self.message2mul[self.message_func]
+        fix_rows = plan.edit_rows if delta.num_removed else plan.delta_rows
         update = None
         if isinstance(boundary, PointBoundary):
             point = (boundary.rows, boundary.values)
             update = plan.forward(relation, input, sum=sum, mul=mul, point=point)
             if update is not None:
-                update = plan.delta_rows(relation, input, update, delta, sum=sum, mul=mul, point=point)
+                update = fix_rows(relation, input, update, delta, sum=sum, mul=mul, point=point)
             else:       # (a plan that does not serve the point form under min / max: the boundary as a tensor)
                 boundary = boundary.dense()
         if update is None:
@@ -346,11 +350,12 @@ class GeneralizedRelationalConv(nn.Module):
                 return None
             boundary = boundary.to(input.dtype)
             update = plan.forward(relation, input, boundary=boundary, sum=sum, mul=mul)
-            update = plan.delta_rows(relation, input, update, delta, boundary=boundary, sum=sum, mul=mul)
+            update = fix_rows(relation, input, update, delta, boundary=boundary, sum=sum, mul=mul)
             if update is None:
                 return None
         if self.aggregate_func == "mean":
             # bincount(edge_index[1]) of the materialised list (+ 1: the boundary's self loop), as message_and_aggregate counts it
+            # (delta.degree is signed: added minus retracted edges)
             degree = _in_degree(edge_index, num_node) + delta.degree
             update = update / (degree.to(input.dtype) + 1).view(1, -1, 1)
         return self.update(update, input, residual=residual)

@@ -658,7 +658,7 @@ class EntityNBFNet(BaseNBFNet):
         facts -- it equals this forward on delta.materialize(data).  On the fused inference path a branch shaped like the masked
         one runs on data's cached plans (prologue, delta layers, readout: every step an engine launch, so a capture records
         it); elsewhere the materialised graph is used (relation_representations are the caller's in both cases)."""
-        if delta is not None and len(delta) == 0:
+        if delta is not None and not delta.edited:
             delta = None
         if delta is not None:
             if edge_keep is not None or self.training or torch.is_grad_enabled():
@@ -815,7 +815,7 @@ class QueryNBFNet(EntityNBFNet):
         for layer in self.layers:
             layer.relation = relation_representations
         self.query = relation_representations      # input of the batched relation projections
-        if delta is not None and len(delta):
+        if delta is not None and delta.edited:
             if edge_keep is not None or torch.is_grad_enabled():
                 raise ValueError("a graph delta (added facts) serves inference under torch.no_grad() only, without edge_keep")
             try:
@@ -967,7 +967,7 @@ class Ultra(nn.Module):
         # delta.relation_graph, the entity model on data's cached plan with the touched rows fixed after every aggregate; where
         # that route does not apply (EntityNBFNet.forward), on the materialised graph.  An empty delta (or None): nothing changes.
         entity_kwargs = {}
-        if delta is not None and len(delta):
+        if delta is not None and delta.edited:
             if edge_keep is not None:
                 raise ValueError("a graph delta (added facts) is not combined with edge_keep")
             if delta.relation_graph is not None and delta.relation_graph is not data.relation_graph:

@@ -209,7 +209,8 @@ class _GraphedPredictStep(Capture):
 
     def __init__(self, model, data, batch_size, k, mode, index_capacity, warmup=2, delta=None):
         """delta (rspmm.GraphDelta or None): handed to the model from the first capture.  While it is empty the model takes its
-        normal path; once it holds facts the capture records the delta's launches, which read its device buffers at replay --
+        normal path; once it holds facts or tombstones the capture records the delta's launches, which read its device buffers
+        at replay --
         `route` is what the Predictor compares to know whether this capture still serves the delta."""
         dev = data.edge_index.device
         Capture.__init__(self, dev)
@@ -254,11 +255,12 @@ class _GraphedPredictStep(Capture):
 
 
 def _delta_route(delta):
-    """What a captured step remembers of the delta it was recorded with: whether it held facts (the model's route) and which
-    relation-graph object the relation model walked."""
+    """What a captured step remembers of the delta it was recorded with: whether it held edits (the model's route), whether it
+    held tombstones (the layers then launch ultra_rspmm_edit_rows, not _delta_rows) and which relation-graph object the relation
+    model walked."""
     if delta is None:
         return None
-    return (len(delta) > 0, id(delta.relation_graph))
+    return (delta.edited, delta.num_removed > 0, id(delta.relation_graph))
 
 
 def _with_facts(graph, h, r, t):
@@ -269,6 +271,19 @@ def _with_facts(graph, h, r, t):
     h, r, t = h.to(dev), r.to(dev), t.to(dev)
     out.edge_index = torch.cat([graph.edge_index, torch.stack([torch.cat([h, t]), torch.cat([t, h])])], dim=1)
     out.edge_type = torch.cat([graph.edge_type, torch.cat([r, r + int(graph.num_relations) // 2])])
+    return out
+
+
+def _without_facts(graph, h, r, t):
+    """A copy of `graph` without every edge equal to (h[i], t[i], r[i]) or to (t[i], h[i], r[i] + num_relations / 2)."""
+    out = copy.copy(graph)
+    dev = graph.edge_index.device
+    h, r, t = h.to(dev), r.to(dev), t.to(dev)
+    n, rels = int(graph.num_nodes), int(graph.num_relations)
+    gone = torch.cat([(h * n + t) * rels + r, (t * n + h) * rels + r + rels // 2]).unique()
+    codes = (graph.edge_index[0] * n + graph.edge_index[1]) * rels + graph.edge_type
+    keep = gone[torch.searchsorted(gone, codes).clamp_(max=len(gone) - 1)] != codes
+    out.edge_index, out.edge_type = graph.edge_index[:, keep], graph.edge_type[keep]
     return out
 
 
@@ -391,8 +406,12 @@ class Predictor(object):
     was just stated is a known answer from then on; tails / heads / tails_above / heads_above answer on the graph with the
     facts, exactly as a fresh Predictor on the materialised graph (GraphDelta.materialize) would.  The captured step is made
     again when the first facts arrive and when the relation graph changes; otherwise a further add_facts costs no capture and
-    no plan.  compact() folds the delta into `data` (a host plan, new captures); add_facts does so itself when the capacity
-    would be exceeded, and explain_* / verify_* do so first when the delta holds facts."""
+    no plan.  remove_facts(h, r, t) retracts facts: every edge equal to (h, t, r) or its inverse leaves the served
+    graph -- base edges as tombstones beside the same cached plan, added facts out of the delta -- and the filter graph, so a
+    retracted tail can be returned as an answer again.  The captured step is made again when the first tombstone arrives; from
+    then on further remove_facts / add_facts cost no capture and no plan unless the relation graph changes.  compact() folds
+    the delta, tombstones included, into `data` (a host plan, new captures); add_facts / remove_facts do so themselves when
+    the capacity would be exceeded, and explain_* / verify_* do so first when the delta holds edits."""
 
     def __init__(self, model, data, k=10, batch_size=8, filtered_data=None, filtered=True, use_graph=True, delta_capacity=256):
         _check_k(k)
@@ -425,25 +444,67 @@ class Predictor(object):
         h, r, t = probe.check(h, r, t)
         if len(h) == 0:
             return 0 if self.delta is None else len(self.delta)
-        if self.delta is None or len(self.delta) + len(h) > self.delta_capacity:
+        if self.delta is None or 2 * (len(self.delta) + len(h)) + self.delta.num_removed > 2 * self.delta_capacity:
             self.compact(extra=(h, r, t))
             return 0
         self.delta.add(h, r, t)
-        fh, fr, ft = self.delta.facts[:len(self.delta)].unbind(1)
-        self.filter_graph = self.delta.materialize(self.data) if self._filter_is_data else _with_facts(self._filter_base, fh, fr, ft)
+        self._refresh_filter_graph()
         return len(self.delta)
 
-    def compact(self, extra=None):
-        """Fold the delta's facts (and `extra` = (h, r, t), checked by the caller) into `data`: the materialised graph becomes the
-        served graph -- its relation graph rebuilt, a host plan on the next query, new captures -- and the delta is emptied."""
-        facts = [] if self.delta is None else [self.delta.facts[:len(self.delta)]]
+    def remove_facts(self, h, r, t):
+        """Retract the facts (h[i], r[i], t[i]) -- the argument rules of add_facts -- one after the other: every edge equal to
+        (h, t, r) or (t, h, r + num_relations / 2) leaves the served graph and the filter graph (a fact stated nowhere is a
+        no-op).  Returns an int64 vector: the number of direct edges each fact took out of the served graph
+        (GraphDelta.remove).  Compacts first where the delta cannot hold the tombstones."""
+        probe = self.delta if self.delta is not None else rspmm.GraphDelta(self.data, 1)
+        h, r, t = probe.check(h, r, t)
+        if len(h) == 0:
+            return torch.zeros(0, dtype=torch.long, device=h.device)
+        # (every retraction holds at most two keys: a call that may not fit compacts first, and one larger than the whole capacity is
+        # applied to a delta of its own and folded at once)
+        fits = lambda: self.delta is not None and \
+            2 * (len(self.delta) + len(h)) + self.delta.num_removed <= 2 * self.delta_capacity
+        fold = None
+        if not fits():
+            self.compact()
+        if fits():
+            removed = self.delta.remove(h, r, t)
+        else:
+            fold = rspmm.GraphDelta(self.data, len(h))
+            removed = fold.remove(h, r, t)
+        if not self._filter_is_data:
+            self._filter_base = _without_facts(self._filter_base, h, r, t)
+        if fold is not None:
+            self.compact(delta=fold)
+        self._refresh_filter_graph()
+        return removed
+
+    def _refresh_filter_graph(self):
+        if self.delta is None:
+            self.filter_graph = self._filter_base
+        elif self._filter_is_data:
+            self.filter_graph = self.delta.materialize(self.data)
+        else:
+            fh, fr, ft = self.delta.facts[:len(self.delta)].unbind(1)
+            self.filter_graph = _with_facts(self._filter_base, fh, fr, ft)
+
+    def compact(self, extra=None, delta=None):
+        """Fold the delta's edits (and `extra` = (h, r, t), checked by the caller) into `data`: the materialised graph -- without
+        the tombstoned edges, with the added ones -- becomes the served graph -- its relation graph rebuilt, a host plan on the
+        next query, new captures -- and the delta is emptied.  `delta`: fold that one instead of the Predictor's own."""
+        delta = self.delta if delta is None else delta
+        facts = [] if delta is None else [delta.facts[:len(delta)]]
         if extra is not None:
             facts.append(torch.stack(list(extra), dim=1))
         facts = torch.cat(facts) if facts else torch.zeros(0, 3, dtype=torch.long)
-        if len(facts) == 0:
+        if len(facts) == 0 and not (delta is not None and delta.num_removed):
             return
         fh, fr, ft = facts.unbind(1)
-        data = _with_facts(self.data, fh, fr, ft)
+        base = self.data
+        if delta is not None and delta.num_removed:
+            base = copy.copy(self.data)
+            base.edge_index, base.edge_type = delta.surviving(self.data.edge_index, self.data.edge_type)
+        data = _with_facts(base, fh, fr, ft)
         if getattr(self.data, "relation_graph", None) is not None:
             tasks.build_relation_graph(data)
         self._filter_base = data if self._filter_is_data else _with_facts(self._filter_base, fh, fr, ft)
@@ -492,8 +553,8 @@ class Predictor(object):
         if not hasattr(self.model, "visualize_batch"):
             raise TypeError("%s cannot explain its answers: models.Ultra and models.EntityNBFNet (visualize_batch) can"
                             % type(self.model).__name__)
-        if self.delta is not None and len(self.delta):
-            self.compact()      # (explanations walk the graph's own edge list: the added facts become part of it first)
+        if self.delta is not None and self.delta.edited:
+            self.compact()      # (explanations walk the graph's own edge list: the edits become part of it first)
         ids, scores, count = self._run(anchor, relation, mode)
         dev = ids.device
         anchor = torch.as_tensor(anchor, dtype=torch.long, device=dev).flatten()
@@ -569,8 +630,8 @@ class Predictor(object):
 
     @torch.no_grad()
     def _verify(self, h, r, t, mode):
-        if self.delta is not None and len(self.delta):
-            self.compact()      # (the keep masks run over the graph's own edge list: the added facts become part of it first)
+        if self.delta is not None and self.delta.edited:
+            self.compact()      # (the keep masks run over the graph's own edge list: the edits become part of it first)
         data, bs = self.data, self.batch_size
         h, r, t = _check_facts(data, h, r, t)
         dev = h.device

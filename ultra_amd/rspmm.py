@@ -401,6 +401,32 @@ class Plan(object):
         check(rc)
         return out
 
+    def edit_rows(self, relation, input, out, delta, boundary=None, sum="add", mul="mul", point=None):
+        """delta_rows for a delta that also holds RETRACTED facts (GraphDelta.remove): afterwards `out` is the forward on a fresh
+        reference-order plan of delta.materialize(...) -- the base edges without the tombstoned ones, then the added edges --
+        bit for bit.  The rows an added or a removed edge points into are recomputed in place, dead base edges skipped
+        (ultra_rspmm_edit_rows); nothing is read per edge of the graph, nothing else is written, and a captured launch follows
+        the delta's buffers.  Returns `out`, or None exactly where delta_rows does."""
+        if not self.exact:
+            return None
+        if (delta.num_nodes, delta.num_relations) != (self.num_node, self.num_relation) or self.num_in != self.num_node:
+            raise RuntimeError("the delta was made for a graph of %d nodes and %d relations, the plan has %d and %d"
+                               % (delta.num_nodes, delta.num_relations, self.num_node, self.num_relation))
+        if point is not None and boundary is not None:
+            raise RuntimeError("a point boundary excludes `boundary`")
+        _require_gpu(out, delta.count)
+        op = self._forward_operands(relation, input, None, boundary, out, point)
+        if op.out is not out:
+            raise RuntimeError("`out` must have unit stride along its last dimension")
+        operand, removed = delta.operand(), delta.removed_operand()
+        rc = lib.ultra_rspmm_edit_rows(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], op.dtype, op.relation, op.input,
+                                       op.boundary, op.rows, op.out_ref, ctypes.byref(operand), ctypes.byref(removed),
+                                       stream_of(input))
+        if rc == _lib.ULTRA_ERR_UNSUPPORTED:
+            return None
+        check(rc)
+        return out
+
     def forward_update(self, relation, input, weight, bias, ln_weight, ln_bias, eps, flags, mul="mul", point=None, timed=None,
                        sum="add"):
         """Aggregate (`sum`, `mul`, optional point boundary) AND the layer update
@@ -645,23 +671,32 @@ class Plan(object):
 
 
 class GraphDelta(object):
-    """Facts added to a served graph, held beside the cached plan of the base graph instead of rebuilding it.
+    """Facts added to and retracted from a served graph, held beside the cached plan of the base graph instead of rebuilding it
+    (DESIGN.md 17, 18).
 
     A fact (h, r, t) -- r a direct relation, h and t existing entities -- contributes the two edges the loader would create,
-    (h, t, r) and (t, h, r + num_relations / 2).  The MATERIALISED graph of the base graph plus m facts is the edge list
-    [base edges ; m direct edges in insertion order ; m inverse edges in insertion order] (`materialize`); a repeated fact, or
-    one the base graph already states, is one more parallel edge.  Every result on (base graph, delta) is defined as the same
-    call on the materialised graph.
+    (h, t, r) and (t, h, r + num_relations / 2).  add() appends them; a repeated fact, or one the base graph already states, is
+    one more parallel edge.  remove() takes EVERY edge equal to either of the two out of the graph: matching base edges become
+    tombstones (one (row, col, type) key stands for all duplicates), matching added facts are deleted from `facts` (later facts
+    move up).  Tombstones apply to base edges only, so a fact removed and then added again is one new edge at the end of the
+    list.  The MATERIALISED graph is the edge list
+    [base edges that carry no tombstone, in base order ; m direct edges in insertion order ; m inverse edges in insertion order]
+    (`materialize`), and every result on (base graph, delta) is defined as the same call on the materialised graph.
 
-    `capacity` counts facts (twice as many edges).  Prepared at add() time with torch on the edge list's device, into buffers
-    that keep their address (a captured launch reads whatever they hold at replay):
+    `capacity` counts edits: num_facts + num_removed / 2 <= capacity (a retracted fact holds up to two keys, an added one two
+    edges).  Prepared at add() / remove() time with torch on the edge list's device, into buffers that keep their address (a
+    captured launch reads whatever they hold at replay):
       col / type  int32 (2 capacity)      the delta's edges in the plan's direction (row = edge_index[0], col = edge_index[1]),
                                           sorted by (row, col, id) with id = the edge's position in the materialised list
-      rows        int32 (2 capacity)      the distinct rows they point into, ascending;  ptr int32 (2 capacity + 1): their ranges
-      count       int32 (1)               the number of touched rows -- the SAME tensor object across add() calls
-      degree      int64 (num_nodes)       the delta's edges counted at edge_index[1] (what `mean` adds to the base bincount)
-    relation_graph: tasks.build_relation_graph of the materialised list, rebuilt at add(); the previous object is kept when the
-    new adjacency equals the old one (the common case), so its plan and the captures that pin it stay valid."""
+      rows        int32 (2 capacity)      the distinct rows an added OR a removed edge points into, ascending
+      ptr         int32 (2 capacity + 1)  the added edges' ranges per touched row (empty for a row touched by removals only)
+      dead_ptr    int32 (2 capacity + 1)  the tombstone keys' ranges per touched row
+      dead_col / dead_type  int32 (2 capacity)   the distinct dead (col, type) keys, sorted by (row, col, type)
+      count       int32 (1)               the number of touched rows -- the SAME tensor object across add() / remove() calls
+      degree      int64 (num_nodes)       SIGNED: added minus removed edges counted at edge_index[1] (what `mean` adds to the base
+                                          bincount)
+    relation_graph: tasks.build_relation_graph of the materialised list, rebuilt at add() / remove(); the previous object is kept
+    when the new adjacency equals the old one (the common case), so its plan and the captures that pin it stay valid."""
 
     def __init__(self, data, capacity=1024):
         if not isinstance(capacity, int) or capacity < 1:
@@ -680,11 +715,27 @@ class GraphDelta(object):
         self.ptr = torch.zeros(2 * capacity + 1, dtype=torch.int32, device=dev)
         self.count = torch.zeros(1, dtype=torch.int32, device=dev)
         self.degree = torch.zeros(self.num_nodes, dtype=torch.long, device=dev)
+        # tombstones: the keys as codes (row * num_nodes + col) * num_relations + type, ascending = sorted by (row, col, type)
+        self.dead_keys = []
+        self.dead_col = torch.zeros(2 * capacity, dtype=torch.int32, device=dev)
+        self.dead_type = torch.zeros(2 * capacity, dtype=torch.int32, device=dev)
+        self.dead_ptr = torch.zeros(2 * capacity + 1, dtype=torch.int32, device=dev)
+        self._base_codes = None
         self.relation_graph = getattr(data, "relation_graph", None)
         self._materialized = None
 
     def __len__(self):
         return self.num_facts
+
+    @property
+    def num_removed(self):
+        """The number of tombstone keys held (two per retracted fact the base graph states in both directions)."""
+        return len(self.dead_keys)
+
+    @property
+    def edited(self):
+        """Does the delta change the graph at all (added facts or tombstones)?"""
+        return self.num_facts > 0 or len(self.dead_keys) > 0
 
     def edges(self):
         """(edge_index (2, 2 m), edge_type (2 m)): the appended edges in materialised order -- the m direct ones, then the m
@@ -708,43 +759,117 @@ class GraphDelta(object):
 
     def add(self, h, r, t):
         """Append the facts (h[i], r[i], t[i]) (ints or vectors); returns the number of facts held.  ValueError for ids out of
-        range, inverse relations, or more facts than the capacity holds (the caller compacts first: Predictor.add_facts)."""
+        range, inverse relations, or more edits than the capacity holds (the caller compacts first: Predictor.add_facts)."""
         h, r, t = self.check(h, r, t)
         n = len(h)
-        if self.num_facts + n > self.capacity:
-            raise ValueError("the delta holds %d of %d facts: %d more do not fit" % (self.num_facts, self.capacity, n))
+        if 2 * (self.num_facts + n) + len(self.dead_keys) > 2 * self.capacity:
+            raise ValueError("the delta holds %d facts and %d tombstone keys of %d edits: %d more facts do not fit"
+                             % (self.num_facts, len(self.dead_keys), self.capacity, n))
         if n == 0:
             return self.num_facts
         self.facts[self.num_facts:self.num_facts + n] = torch.stack([h, r, t], dim=1)
         self.num_facts += n
+        self._changed()
+        return self.num_facts
+
+    def _edge_codes(self, row, col, edge_type):
+        return (row * self.num_nodes + col) * self.num_relations + edge_type
+
+    def remove(self, h, r, t):
+        """Retract the facts (h[i], r[i], t[i]) (ints or vectors, the argument rules of add), one after the other: every base
+        edge equal to (h, t, r) or to (t, h, r + num_relations / 2) becomes a tombstone, every added fact equal to (h, r, t) is
+        deleted.  Returns an int64 vector: entry i is the number of DIRECT edges fact i took out (0 for a fact stated nowhere,
+        which uses no capacity and changes no version).  ValueError where the tombstones would exceed the capacity -- nothing
+        is changed then (the caller compacts first: Predictor.remove_facts)."""
+        h, r, t = self.check(h, r, t)
+        n = len(h)
+        removed = [0] * n
+        if n == 0:
+            return torch.zeros(0, dtype=torch.long, device=self.device)
+        if self._base_codes is None:      # the base edges' codes, sorted once: a retraction is two binary searches
+            row, col = self.base.edge_index.to(self.device)
+            self._base_codes = torch.sort(self._edge_codes(row, col, self.base.edge_type.to(self.device))).values
+        queries = torch.stack([self._edge_codes(h, t, r), self._edge_codes(t, h, r + self.num_relations // 2)])
+        stated = torch.searchsorted(self._base_codes, queries, right=True) - torch.searchsorted(self._base_codes, queries)
+        (direct, inverse), (n_direct, n_inverse) = queries.tolist(), stated.tolist()
+        wanted = torch.stack([h, r, t], dim=1).tolist()
+        facts = self.facts[:self.num_facts].tolist()
+        keys = set(self.dead_keys)
+        for i in range(n):
+            kept = [f for f in facts if f != wanted[i]]
+            removed[i] = len(facts) - len(kept)
+            facts = kept
+            if n_direct[i] and direct[i] not in keys:
+                keys.add(direct[i])
+                removed[i] += n_direct[i]
+            if n_inverse[i] and inverse[i] not in keys:
+                keys.add(inverse[i])
+        if len(facts) != self.num_facts or len(keys) != len(self.dead_keys):
+            if 2 * len(facts) + len(keys) > 2 * self.capacity:
+                raise ValueError("the delta holds %d facts and %d tombstone keys of %d edits: these retractions do not fit"
+                                 % (self.num_facts, len(self.dead_keys), self.capacity))
+            if len(facts) != self.num_facts:
+                self.num_facts = len(facts)
+                if facts:
+                    self.facts[:len(facts)] = torch.tensor(facts, dtype=torch.long, device=self.device)
+            self.dead_keys = sorted(keys)
+            self._changed()
+        return torch.tensor(removed, dtype=torch.long, device=self.device)
+
+    def _changed(self):
         self.version += 1
         self._materialized = None
         self._prepare()
         self._rebuild_relation_graph()
-        return self.num_facts
 
     def _prepare(self):
-        """Sort, unique rows and ptr of the delta's edges, into the fixed buffers."""
+        """Sort the delta's edges, decode the tombstone keys, and lay out the union of their rows with both ptr arrays, into the
+        fixed buffers."""
         edge_index, edge_type = self.edges()
         num_edge = edge_index.shape[1]
         row, col = edge_index
         ids = torch.arange(num_edge, device=self.device)
-        order = torch.argsort((row * self.num_nodes + col) * num_edge + ids)
+        order = torch.argsort((row * self.num_nodes + col) * max(num_edge, 1) + ids)
         row, col, edge_type = row[order], col[order], edge_type[order]
-        touched, counts = torch.unique_consecutive(row, return_counts=True)
+        keys = torch.tensor(self.dead_keys, dtype=torch.long, device=self.device)
+        key_type = keys % self.num_relations
+        key_col = (keys // self.num_relations) % self.num_nodes
+        key_row = keys // (self.num_relations * self.num_nodes)
+        touched = torch.unique(torch.cat([row, key_row]))      # (ascending)
+        num_touched = len(touched)
         self.col[:num_edge] = col.to(torch.int32)
         self.type[:num_edge] = edge_type.to(torch.int32)
-        self.rows[:len(touched)] = touched.to(torch.int32)
-        self.ptr[1:len(touched) + 1] = counts.cumsum(0).to(torch.int32)
+        self.dead_col[:len(keys)] = key_col.to(torch.int32)
+        self.dead_type[:len(keys)] = key_type.to(torch.int32)
+        self.rows[:num_touched] = touched.to(torch.int32)
+        for ptr, of in ((self.ptr, row), (self.dead_ptr, key_row)):
+            counts = torch.bincount(torch.searchsorted(touched, of), minlength=num_touched)
+            ptr[1:num_touched + 1] = counts.cumsum(0).to(torch.int32)
         self.degree.copy_(torch.bincount(edge_index[1], minlength=self.num_nodes))
-        self.count.fill_(len(touched))
+        if len(keys):
+            lo, hi = torch.searchsorted(self._base_codes, keys), torch.searchsorted(self._base_codes, keys, right=True)
+            self.degree -= torch.bincount(key_col, weights=(hi - lo).double(), minlength=self.num_nodes).long()
+        self.count.fill_(num_touched)
+
+    def surviving(self, edge_index, edge_type):
+        """(edge_index, edge_type) without the edges a tombstone key matches, in their order (the arguments themselves where no
+        key is held)."""
+        if not self.dead_keys:
+            return edge_index, edge_type
+        dev = edge_index.device
+        keys = torch.tensor(self.dead_keys, dtype=torch.long, device=dev)
+        codes = self._edge_codes(edge_index[0], edge_index[1], edge_type.to(dev))
+        at = torch.searchsorted(keys, codes).clamp_(max=len(keys) - 1)
+        keep = keys[at] != codes
+        return edge_index[:, keep], edge_type[keep]
 
     def _rebuild_relation_graph(self):
         if self.relation_graph is None:
             return
         edge_index, edge_type = self.edges()
-        full = Data(edge_index=torch.cat([self.base.edge_index, edge_index], dim=1),
-                    edge_type=torch.cat([self.base.edge_type, edge_type]), num_nodes=self.num_nodes,
+        base_index, base_type = self.surviving(self.base.edge_index, self.base.edge_type)
+        full = Data(edge_index=torch.cat([base_index, edge_index], dim=1),
+                    edge_type=torch.cat([base_type, edge_type]), num_nodes=self.num_nodes,
                     num_relations=self.num_relations)
         new, old = tasks.build_relation_graph(full).relation_graph, self.relation_graph
         old_bits, new_bits = getattr(old, "adjacency_bits", None), getattr(new, "adjacency_bits", None)
@@ -757,16 +882,18 @@ class GraphDelta(object):
             self.relation_graph = new
 
     def materialize(self, data=None):
-        """`data` (default: the base graph) with the delta's edges appended in materialised order, and the delta's relation
-        graph: a copy that shares every other field.  Kept until the next add(), so the plan cache sees one graph."""
+        """`data` (default: the base graph) without the edges a tombstone matches and with the delta's edges appended in
+        materialised order, and the delta's relation graph: a copy that shares every other field.  Kept until the next add() /
+        remove(), so the plan cache sees one graph."""
         data = self.base if data is None else data
         hit = self._materialized
         if hit is not None and hit[0] is data:
             return hit[1]
         edge_index, edge_type = self.edges()
+        base_index, base_type = self.surviving(data.edge_index, data.edge_type)
         out = copy.copy(data)
-        out.edge_index = torch.cat([data.edge_index, edge_index.to(data.edge_index.device)], dim=1)
-        out.edge_type = torch.cat([data.edge_type, edge_type.to(data.edge_type.device)])
+        out.edge_index = torch.cat([base_index, edge_index.to(data.edge_index.device)], dim=1)
+        out.edge_type = torch.cat([base_type, edge_type.to(data.edge_type.device)])
         if self.relation_graph is not None and data is self.base:
             out.relation_graph = self.relation_graph
         self._materialized = (data, out)
@@ -786,6 +913,11 @@ class GraphDelta(object):
         """The delta as the engine takes it (ultra_delta); valid while this object lives."""
         return _lib.UltraDelta(self.rows.data_ptr(), self.ptr.data_ptr(), self.col.data_ptr(), self.type.data_ptr(),
                                self.count.data_ptr(), self.rows.numel(), self.col.numel())
+
+    def removed_operand(self):
+        """The tombstones as the engine takes them (ultra_tombstones); valid while this object lives."""
+        return _lib.UltraTombstones(self.dead_ptr.data_ptr(), self.dead_col.data_ptr(), self.dead_type.data_ptr(),
+                                    self.dead_col.numel())
 
 
 # ---- plan cache: the graph is static across the 12 rspmm calls of a forward and across batches ----
