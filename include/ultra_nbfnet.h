@@ -216,6 +216,12 @@ int32_t ultra_relation_projection_backward(const void *x, const void *const *w0,
 int32_t ultra_filtered_rank(const void *score, const int64_t *pos_index, const int64_t *known_ptr,
                             const int64_t *known_index, int64_t batch, int64_t n_cand, int64_t *rank_out,
                             int64_t *num_negative_out, void *stream);
+/* ... over the LIVE ids of rows of n_cand slots: the live-count rules of ultra_filtered_topk_live.  Only
+ * ids below *n_live are counted, num_negative_out[q] = *n_live - |known(q)|; pos_index and the known ids are live.  NULL
+ * n_live: ULTRA_ERR_INVALID. */
+int32_t ultra_filtered_rank_live(const void *score, const int64_t *pos_index, const int64_t *known_ptr,
+                                 const int64_t *known_index, int64_t batch, int64_t n_cand, int64_t *rank_out,
+                                 int64_t *num_negative_out, const int64_t *n_live, void *stream);
 
 /*
  * Strict negative sampling (/root/reference/ultra/tasks.py:42-76, strict = True) for n_query positives, n_draw negatives each,
@@ -403,6 +409,18 @@ int64_t ultra_filtered_topk_workspace(int64_t batch, int64_t n_cand, int32_t k);
 int32_t ultra_filtered_topk(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
                             int64_t n_cand, int32_t k, int64_t *ids_out, void *scores_out, int64_t *count_out, void *workspace,
                             int64_t workspace_bytes, void *stream);
+/* ---- a growing graph: selection over the live ids of reserved rows ----
+ * The _live twins of ultra_filtered_topk / ultra_filtered_above / ultra_filtered_rank take the arguments of their parents plus
+ * n_live, a DEVICE pointer to one int64 with 1 <= *n_live <= n_cand.  n_cand is the number of SLOTS: the row stride of score,
+ * the launch shape and the workspace size depend on (batch, n_cand) alone, and *n_live is read by the kernels, so a call recorded
+ * into a hipGraph serves every later value.  An id >= *n_live is absent: its slot is never read (it may hold anything, a NaN or
+ * +inf included) and it is never counted -- count_out[b] = min(k, *n_live - |known(b)|), size_out and num_negative_out count
+ * live ids.  The known ids (and the positives of the rank) must be live.  The value is clamped on the device to [0, n_cand]
+ * and never used to index past a row.  The same kernels serve the parents (n_live == NULL inside: every slot is live), whose
+ * results keep their bits.  Errors: those of the parent, under the twin's name; a NULL n_live is ULTRA_ERR_INVALID. */
+int32_t ultra_filtered_topk_live(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
+                                 int64_t n_cand, int32_t k, int64_t *ids_out, void *scores_out, int64_t *count_out,
+                                 void *workspace, int64_t workspace_bytes, const int64_t *n_live, void *stream);
 
 /* ---- compiled execution of complex logical queries ----
  * ultra_query_segment: what a batch of UltraQuery stack machines does between two projection calls, as one launch.  The
@@ -462,6 +480,11 @@ int64_t ultra_filtered_above_workspace(int64_t batch, int64_t n_cand);
 int32_t ultra_filtered_above(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
                              int64_t n_cand, float threshold, int64_t *ptr_out, int64_t *ids_out, void *scores_out,
                              int64_t capacity, int64_t *size_out, void *workspace, int64_t workspace_bytes, void *stream);
+/* ... over the live ids (the rules stated at ultra_filtered_topk_live): the workspace is that of ultra_filtered_above. */
+int32_t ultra_filtered_above_live(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
+                                  int64_t n_cand, float threshold, int64_t *ptr_out, int64_t *ids_out, void *scores_out,
+                                  int64_t capacity, int64_t *size_out, void *workspace, int64_t workspace_bytes,
+                                  const int64_t *n_live, void *stream);
 
 #ifdef __cplusplus
 }

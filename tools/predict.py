@@ -1,7 +1,7 @@
 """Answer one link-prediction query on a dataset of triple files: the k entities the model predicts, with their scores.
 
     python tools/predict.py --data-root DIR [--ckpt FILE] --head NAME --relation NAME [--inverse] [-k 10] [--unfiltered] [--explain]
-                            [--add-fact H R T]... [--remove-fact H R T]...
+                            [--add-fact H R T]... [--remove-fact H R T]... [--entity-capacity M] [--add-entity NAME]...
     python tools/predict.py --data-root DIR [--ckpt FILE] --verify (--head NAME --relation NAME --tail NAME | --triples FILE) [--inverse]
 
 DIR holds train.txt / valid.txt / test.txt (`head relation tail` per line) and optionally entities.dict / relations.dict
@@ -15,6 +15,11 @@ explain_heads) with their weights; a relation walked against its direction is pr
 graph served is the dataset's plus these facts, and their tails and heads count as known answers.  --remove-fact H R T
 (repeatable) retracts a fact before the query is answered (Predictor.remove_facts): every edge that states it leaves the graph
 served and the known answers, so its tail can be predicted again.  Both kinds are applied in command-line order.
+
+--add-entity NAME (repeatable) introduces an entity the dataset does not know (Predictor.add_entities): it takes one of the rows
+reserved by --entity-capacity M (default: as many as there are --add-entity options), costs no plan and no capture, and from then
+on NAME can be used by the --add-fact / --remove-fact options that FOLLOW it on the command line and by --head; answers print it
+by its name.  It is applied in command-line order with the fact options.
 
 --verify judges facts the dataset may already state: every (head, relation, tail) -- one from the command line, or the
 `head relation tail` lines of FILE -- is scored on the graph WITHOUT itself and its inverse edge (Predictor.verify_tails; with
@@ -52,15 +57,22 @@ def main(argv=None):
     ap.add_argument("-k", type=int, default=10)
     ap.add_argument("--unfiltered", action="store_true")
     ap.add_argument("--explain", action="store_true", help="print the top paths behind every answer")
-    class Edit(argparse.Action):       # (one list for both kinds: they are applied in command-line order)
+    class Edit(argparse.Action):       # (one list for all kinds: they are applied in command-line order)
         def __call__(self, parser, namespace, values, option_string=None):
             namespace.edits = getattr(namespace, "edits", None) or []
-            namespace.edits.append((option_string == "--add-fact", tuple(values)))
+            if option_string == "--add-entity":
+                namespace.edits.append((None, values))
+            else:
+                namespace.edits.append((option_string == "--add-fact", tuple(values)))
 
     ap.add_argument("--add-fact", nargs=3, action=Edit, metavar=("H", "R", "T"),
                     help="state the fact (H, R, T) before the query; repeatable")
     ap.add_argument("--remove-fact", nargs=3, action=Edit, metavar=("H", "R", "T"),
                     help="retract the fact (H, R, T) before the query; repeatable, applied in order with --add-fact")
+    ap.add_argument("--add-entity", action=Edit, metavar="NAME",
+                    help="introduce a new entity before the query; repeatable, applied in order with the fact options")
+    ap.add_argument("--entity-capacity", type=int, default=None, metavar="M",
+                    help="rows reserved for new entities (default: the number of --add-entity options)")
     ap.set_defaults(edits=[])
     args = ap.parse_args(argv)
     if args.verify:
@@ -79,9 +91,24 @@ def main(argv=None):
             else [(args.head, args.relation, args.tail)]
         if any(len(f) != 3 for f in facts):
             sys.exit("--triples: every line is `head relation tail`")
-    for h_name, r_name, t_name in (facts if facts is not None else [(args.head, args.relation, args.head)]) \
-            + [f for _, f in args.edits]:
-        for name, vocab, what in ((h_name, ent, "entity"), (r_name, rel, "relation"), (t_name, ent, "entity")):
+    new_names = [name for kind, name in args.edits if kind is None]
+    if facts is not None and new_names:
+        sys.exit("--add-entity serves queries, not --verify")
+    if args.entity_capacity is not None and args.entity_capacity < 0:
+        sys.exit("--entity-capacity must not be negative")
+    known = set(ent)        # (grows along the command line: a name can be used after its --add-entity)
+    checks = []
+    for kind, value in args.edits:
+        if kind is None:
+            if value in known:
+                sys.exit("--add-entity %r: the entity exists" % value)
+            known.add(value)
+        else:
+            checks.append((value, set(known)))
+    for triple in (facts if facts is not None else [(args.head, args.relation, args.head)]):
+        checks.append((triple, known))
+    for (h_name, r_name, t_name), names in checks:
+        for name, vocab, what in ((h_name, names, "entity"), (r_name, rel, "relation"), (t_name, names, "entity")):
             if name not in vocab:
                 sys.exit("unknown %s %r" % (what, name))
     dev = torch.device("cuda:0")
@@ -102,9 +129,20 @@ def main(argv=None):
         for f, s, k, n in zip(facts, score.tolist(), rank.tolist(), num_negative.tolist()):
             print("%-28s %-24s %-28s %12.6g  %6d / %d" % (f[0], f[1], f[2], s, k, n + 1))
         return
-    predictor = predict.Predictor(model, data, k=args.k, batch_size=1, filtered=not args.unfiltered)
+    reserve = len(new_names) if args.entity_capacity is None else args.entity_capacity
+    predictor = predict.Predictor(model, data, k=args.k, batch_size=1, filtered=not args.unfiltered, entity_capacity=reserve)
+    ent = list(ent)
     at = 0
     while at < len(args.edits):        # (runs of one kind go in one call)
+        if args.edits[at][0] is None:
+            if not reserve:
+                sys.exit("--add-entity needs --entity-capacity above 0")
+            (new_id,) = predictor.add_entities(1).tolist()
+            assert new_id == len(ent)
+            ent.append(args.edits[at][1])
+            print("entity %r added as id %d (%d of %d rows in use)" % (ent[-1], new_id, predictor.num_entities, predictor.num_slots))
+            at += 1
+            continue
         end = at
         while end < len(args.edits) and args.edits[end][0] == args.edits[at][0]:
             end += 1

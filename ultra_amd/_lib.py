@@ -146,6 +146,10 @@ def _load():
     lib.ultra_filtered_topk_workspace.argtypes = [i64, i64, i32]
     lib.ultra_filtered_topk_workspace.restype = i64
     lib.ultra_filtered_topk.argtypes = [vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp]
+    # the live-count twins: the parent's arguments plus a device pointer to the int64 live count before the stream
+    lib.ultra_filtered_rank_live.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp, vp, vp]
+    lib.ultra_filtered_topk_live.argtypes = [vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp, vp]
+    lib.ultra_filtered_above_live.argtypes = [vp, vp, vp, i64, i64, ctypes.c_float, vp, vp, vp, i64, vp, vp, i64, vp, vp]
     lib.ultra_filtered_above_workspace.argtypes = [i64, i64]
     lib.ultra_filtered_above_workspace.restype = i64
     lib.ultra_filtered_above.argtypes = [vp, vp, vp, i64, i64, ctypes.c_float, vp, vp, vp, i64, vp, vp, i64, vp]

@@ -22,6 +22,12 @@
 //      STORED bits of the scores (gathered from the score matrix: -0.0 stays -0.0) instead of keys.
 // The key buffers are indexed by output position, so a pair's merged run lies exactly where its two runs lay.  LDS atomics
 // only hand out compaction slots before the sort; the keys are distinct, so no output depends on the order they land in.
+//
+// A LIVE COUNT (ultra_filtered_above_live): the row stride, the grid, the workspace layout and the number of
+// launches stay those of n_cand SLOTS; only the ids below *n_live -- read on the device, clamped to [0, n_cand] -- are looked at.
+// A dead id is never loaded (a NaN or +inf in its slot is no member and reaches no key), a chunk wholly beyond the live count
+// writes its two zero counts and an empty run, so the scan and every merge level see what they see for an empty chunk.
+// n_live == NULL (ultra_filtered_above) means n_cand: the same kernels, the same bits.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -47,6 +53,17 @@ static_assert(ABOVE_CHUNK % ABOVE_TILE == 0 && ABOVE_TILE % ABOVE_THREADS == 0, 
 static_assert((ABOVE_CHUNK & (ABOVE_CHUNK - 1)) == 0, "the bitonic sort runs over powers of two up to a chunk");
 
 typedef unsigned long long u64;
+
+// The candidates of chunk [lo, lo + ABOVE_CHUNK) of a row of n_cand slots of which the ids below *n_live (clamped to
+// [0, n_cand]; NULL: all) are live: 0 for a chunk beyond the live count.
+__device__ __forceinline__ int live_in_chunk(const int64_t *__restrict__ n_live, long long n_cand, long long lo) {
+    long long live = n_cand;
+    if (n_live) {
+        const long long v = *n_live;
+        live = v < 0 ? 0 : (v < n_cand ? v : n_cand);
+    }
+    return (int)(live - lo < ABOVE_CHUNK ? (live > lo ? live - lo : 0) : ABOVE_CHUNK);
+}
 
 // The chunk [lo, lo + n) of `row`: bits[j] = ordered_score of candidate tid + j * ABOVE_THREADS when it is a member that
 // known(b) does not list, else 0.  Returns this thread's number of members (before the filter).  ord: ABOVE_CHUNK words of LDS,
@@ -99,13 +116,14 @@ __device__ __forceinline__ int wave_sum(int v) {
 
 __global__ void __launch_bounds__(ABOVE_THREADS) above_count_kernel(const float *__restrict__ score, const int64_t *__restrict__ known_ptr,
                                                                     const int64_t *__restrict__ known_index, long long n_cand,
-                                                                    long long n_chunk, float threshold, int *__restrict__ counts) {
+                                                                    long long n_chunk, float threshold, int *__restrict__ counts,
+                                                                    const int64_t *__restrict__ n_live) {
     __shared__ unsigned ord[ABOVE_CHUNK];
     __shared__ int part[2][ABOVE_THREADS / 64];
     const int tid = threadIdx.x;
     const long long b = blockIdx.x / n_chunk, c = blockIdx.x % n_chunk;
     const long long lo = c * ABOVE_CHUNK;
-    const int n = (int)(n_cand - lo < ABOVE_CHUNK ? n_cand - lo : ABOVE_CHUNK);
+    const int n = live_in_chunk(n_live, n_cand, lo);
     unsigned bits[ABOVE_SLOTS];
     int members = chunk_survivors(score + b * n_cand, lo, n, threshold, known_ptr, known_index, b, ord, bits);
     int kept = 0;
@@ -178,7 +196,8 @@ __global__ void __launch_bounds__(ABOVE_THREADS) above_fill_kernel(const float *
                                                                    const int64_t *__restrict__ known_index, long long n_cand,
                                                                    long long n_chunk, float threshold, const long long *__restrict__ offs,
                                                                    u64 *__restrict__ keys_out, int64_t *__restrict__ ids_out,
-                                                                   unsigned *__restrict__ scores_out) {
+                                                                   unsigned *__restrict__ scores_out,
+                                                                   const int64_t *__restrict__ n_live) {
     __shared__ unsigned ord[ABOVE_CHUNK];
     __shared__ u64 keys[ABOVE_CHUNK];
     __shared__ unsigned cursor;
@@ -186,7 +205,7 @@ __global__ void __launch_bounds__(ABOVE_THREADS) above_fill_kernel(const float *
     const long long b = blockIdx.x / n_chunk, c = blockIdx.x % n_chunk;
     const float *row = score + b * n_cand;
     const long long lo = c * ABOVE_CHUNK;
-    const int n = (int)(n_cand - lo < ABOVE_CHUNK ? n_cand - lo : ABOVE_CHUNK);
+    const int n = live_in_chunk(n_live, n_cand, lo);
     if (tid == 0) cursor = 0;
     unsigned bits[ABOVE_SLOTS];
     chunk_survivors(row, lo, n, threshold, known_ptr, known_index, b, ord, bits);
@@ -307,33 +326,35 @@ extern "C" int64_t ultra_filtered_above_workspace(int64_t batch, int64_t n_cand)
     return (slots + 1) * 8 + 2 * batch * n_cand * 8 + slots * 8;
 }
 
-extern "C" int32_t ultra_filtered_above(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
-                                        int64_t n_cand, float threshold, int64_t *ptr_out, int64_t *ids_out, void *scores_out,
-                                        int64_t capacity, int64_t *size_out, void *workspace, int64_t workspace_bytes,
-                                        void *stream) {
+// Both entries: `who` names the caller in the messages; n_live == NULL: every slot is a candidate.
+static int32_t filtered_above_impl(const char *who_, const void *score, const int64_t *known_ptr, const int64_t *known_index,
+                                   int64_t batch, int64_t n_cand, float threshold, int64_t *ptr_out, int64_t *ids_out,
+                                   void *scores_out, int64_t capacity, int64_t *size_out, void *workspace, int64_t workspace_bytes,
+                                   const int64_t *n_live, void *stream) {
+    const std::string who(who_);
     if (n_cand >= (int64_t)1 << 31 || std::isnan(threshold) || (std::isinf(threshold) && threshold > 0)) {      // (before any pointer is looked at)
-        ultra::set_error("ultra_filtered_above: n_cand must stay below 2^31 and the threshold be finite or -inf");
+        ultra::set_error(who + ": n_cand must stay below 2^31 and the threshold be finite or -inf");
         return ULTRA_ERR_UNSUPPORTED;
     }
     if (!score || !ptr_out || !ids_out || !scores_out || !size_out || n_cand <= 0 || batch < 0 || batch > ultra::ABOVE_MAX_BATCH) {
-        ultra::set_error("ultra_filtered_above: NULL operand, empty candidate set or batch outside [0, 65535]");
+        ultra::set_error(who + ": NULL operand, empty candidate set or batch outside [0, 65535]");
         return ULTRA_ERR_INVALID;
     }
     if (capacity < batch * n_cand) {
-        ultra::set_error("ultra_filtered_above: capacity " + std::to_string(capacity) + " is below batch * n_cand = " +
+        ultra::set_error(who + ": capacity " + std::to_string(capacity) + " is below batch * n_cand = " +
                          std::to_string(batch * n_cand));
         return ULTRA_ERR_INVALID;
     }
     const int64_t need = ultra_filtered_above_workspace(batch, n_cand);
     if (workspace_bytes < need || !workspace || ((uintptr_t)workspace & 7u) != 0) {
-        ultra::set_error("ultra_filtered_above: workspace of " + std::to_string(workspace_bytes) + " bytes, needs " +
+        ultra::set_error(who + ": workspace of " + std::to_string(workspace_bytes) + " bytes, needs " +
                          std::to_string(need) + " (8-byte aligned)");
         return ULTRA_ERR_INVALID;
     }
     const int64_t n_chunk = ultra::above_chunks(n_cand);
     const int64_t slots = batch * n_chunk;
     if (slots * ultra::ABOVE_TILES_PER_CHUNK >= (int64_t)1 << 31) {
-        ultra::set_error("ultra_filtered_above: batch * chunks per row must stay below 2^30");
+        ultra::set_error(who + ": batch * chunks per row must stay below 2^30");
         return ULTRA_ERR_UNSUPPORTED;
     }
     if (batch == 0) return ULTRA_OK;
@@ -345,7 +366,7 @@ extern "C" int32_t ultra_filtered_above(const void *score, const int64_t *known_
     (void)hipGetLastError();   // drop any stale error left by other users of the runtime
     const dim3 threads(ultra::ABOVE_THREADS);
     hipLaunchKernelGGL(ultra::above_count_kernel, dim3((unsigned)slots), threads, 0, s, (const float *)score, known_ptr, known_index,
-                       (long long)n_cand, (long long)n_chunk, threshold, counts);
+                       (long long)n_cand, (long long)n_chunk, threshold, counts, n_live);
     if (hipGetLastError() != hipSuccess) {
         ultra::set_error("above_count_kernel launch failed");
         return ULTRA_ERR_HIP;
@@ -358,7 +379,7 @@ extern "C" int32_t ultra_filtered_above(const void *score, const int64_t *known_
     }
     hipLaunchKernelGGL(ultra::above_fill_kernel, dim3((unsigned)slots), threads, 0, s, (const float *)score, known_ptr, known_index,
                        (long long)n_cand, (long long)n_chunk, threshold, (const long long *)offs, keys0, ids_out,
-                       (unsigned *)scores_out);
+                       (unsigned *)scores_out, n_live);
     if (hipGetLastError() != hipSuccess) {
         ultra::set_error("above_fill_kernel launch failed");
         return ULTRA_ERR_HIP;
@@ -378,4 +399,25 @@ extern "C" int32_t ultra_filtered_above(const void *score, const int64_t *known_
         dst = swap;
     }
     return ULTRA_OK;
+}
+
+extern "C" int32_t ultra_filtered_above(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
+                                        int64_t n_cand, float threshold, int64_t *ptr_out, int64_t *ids_out, void *scores_out,
+                                        int64_t capacity, int64_t *size_out, void *workspace, int64_t workspace_bytes,
+                                        void *stream) {
+    return filtered_above_impl("ultra_filtered_above", score, known_ptr, known_index, batch, n_cand, threshold, ptr_out, ids_out,
+                               scores_out, capacity, size_out, workspace, workspace_bytes, nullptr, stream);
+}
+
+extern "C" int32_t ultra_filtered_above_live(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
+                                             int64_t n_cand, float threshold, int64_t *ptr_out, int64_t *ids_out, void *scores_out,
+                                             int64_t capacity, int64_t *size_out, void *workspace, int64_t workspace_bytes,
+                                             const int64_t *n_live, void *stream) {
+    // (the parent's UNSUPPORTED cases come first)
+    if (!n_live && n_cand < (int64_t)1 << 31 && !std::isnan(threshold) && !(std::isinf(threshold) && threshold > 0)) {
+        ultra::set_error("ultra_filtered_above_live: n_live is NULL");
+        return ULTRA_ERR_INVALID;
+    }
+    return filtered_above_impl("ultra_filtered_above_live", score, known_ptr, known_index, batch, n_cand, threshold, ptr_out, ids_out,
+                               scores_out, capacity, size_out, workspace, workspace_bytes, n_live, stream);
 }

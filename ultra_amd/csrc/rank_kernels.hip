@@ -6,6 +6,10 @@
 // computed as  1 + #{t : pos <= score[t]}  -  #{t in known(q) : pos <= score[t]}  where known(q) is the
 // de-duplicated list of true answers INCLUDING the positive itself (a ragged int64 list per query).
 // Integer counting: bit-exact against the reference for any score tensor (ties count against the positive).
+//
+// A LIVE COUNT (ultra_filtered_rank_live): the row stride stays n_cand slots, only t < *n_live -- read on the
+// device, clamped to [0, n_cand] -- is counted, and num_negative counts live ids; a dead slot is never loaded.  The positives
+// and the known ids are live by construction.  n_live == NULL (ultra_filtered_rank) means n_cand.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -22,12 +26,18 @@ constexpr int RANK_CHUNK = 4096;
 __global__ void __launch_bounds__(256) filtered_rank_kernel(const float *__restrict__ score, const int64_t *__restrict__ pos,
                                                             const int64_t *__restrict__ known_ptr,
                                                             const int64_t *__restrict__ known_index, long long n_cand,
-                                                            unsigned long long *rank, long long *num_negative) {
+                                                            unsigned long long *rank, long long *num_negative,
+                                                            const int64_t *__restrict__ n_live) {
     const int q = blockIdx.y;
+    long long live = n_cand;
+    if (n_live) {
+        const long long v = *n_live;
+        live = v < 0 ? 0 : (v < n_cand ? v : n_cand);
+    }
     const float *row = score + (long long)q * n_cand;
     const float pos_score = row[pos[q]];
     const long long lo = (long long)blockIdx.x * RANK_CHUNK;
-    const long long hi = lo + RANK_CHUNK < n_cand ? lo + RANK_CHUNK : n_cand;
+    const long long hi = lo + RANK_CHUNK < live ? lo + RANK_CHUNK : live;
     long long count = 0;
     for (long long t = lo + threadIdx.x; t < hi; t += blockDim.x) count += (pos_score <= row[t]) ? 1 : 0;
     if (blockIdx.x == 0) {
@@ -36,12 +46,19 @@ __global__ void __launch_bounds__(256) filtered_rank_kernel(const float *__restr
         for (long long k = k0 + threadIdx.x; k < k1; k += blockDim.x) count -= (pos_score <= row[known_index[k]]) ? 1 : 0;
         if (threadIdx.x == 0) {
             count += 1;
-            num_negative[q] = n_cand - (k1 - k0);
+            num_negative[q] = live - (k1 - k0);
         }
     }
     // wave reduce, then one atomic per wave (integer: order independent)
     for (int off = 32; off > 0; off >>= 1) count += __shfl_down(count, off);
     if ((threadIdx.x & 63) == 0) atomicAdd(rank + q, (unsigned long long)count);
+}
+
+// rank[q] = 0 ahead of filtered_rank_kernel's atomics, for the live-count entry: a kernel, not hipMemsetAsync -- that entry exists
+// to be replayed from a hipGraph between eager work, and memset nodes captured into a hipGraph replay wrongly once eager memsets
+// interleave with the replays (rspmm_api.hip).  ultra_filtered_rank keeps its memset: the same nodes as ever.
+__global__ void __launch_bounds__(256) rank_zero_kernel(unsigned long long *rank, long long batch) {
+    for (long long q = blockIdx.x * 256ll + threadIdx.x; q < batch; q += (long long)gridDim.x * 256) rank[q] = 0;
 }
 
 // Batch prologue of EntityNBFNet.forward (models.py:190-197 + base_nbfnet.py:79-86) in one pass over the
@@ -155,28 +172,54 @@ extern "C" int32_t ultra_batch_prologue(const int64_t *batch, int64_t batch_size
     return ultra_batch_prologue_rows(batch, batch_size, n_cand, num_direct_rel, h0, r0, side, valid, rel_first, nullptr, stream);
 }
 
-extern "C" int32_t ultra_filtered_rank(const void *score, const int64_t *pos_index, const int64_t *known_ptr,
-                                       const int64_t *known_index, int64_t batch, int64_t n_cand, int64_t *rank_out,
-                                       int64_t *num_negative_out, void *stream) {
+static int32_t filtered_rank_impl(const char *who, const void *score, const int64_t *pos_index, const int64_t *known_ptr,
+                                  const int64_t *known_index, int64_t batch, int64_t n_cand, int64_t *rank_out,
+                                  int64_t *num_negative_out, const int64_t *n_live, void *stream) {
     ULTRA_DEVICE_SCOPE(stream, score);
     if (!score || !pos_index || !known_ptr || !rank_out || !num_negative_out || batch < 0 || n_cand <= 0) {
-        ultra::set_error("ultra_filtered_rank: NULL operand or empty candidate set");
+        ultra::set_error(std::string(who) + ": NULL operand or empty candidate set");
         return ULTRA_ERR_INVALID;
     }
     if (batch == 0) return ULTRA_OK;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (hipMemsetAsync(rank_out, 0, sizeof(int64_t) * (size_t)batch, s) != hipSuccess) {
-        ultra::set_error("ultra_filtered_rank: hipMemsetAsync failed");
+    (void)hipGetLastError();   // drop any stale error left by other users of the runtime
+    if (n_live) {
+        const unsigned blocks = (unsigned)(batch < 256 * 1024 ? (batch + 255) / 256 : 1024);
+        hipLaunchKernelGGL(ultra::rank_zero_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<unsigned long long *>(rank_out),
+                           (long long)batch);
+        if (hipGetLastError() != hipSuccess) {
+            ultra::set_error(std::string(who) + ": rank_zero_kernel launch failed");
+            return ULTRA_ERR_HIP;
+        }
+    } else if (hipMemsetAsync(rank_out, 0, sizeof(int64_t) * (size_t)batch, s) != hipSuccess) {
+        ultra::set_error(std::string(who) + ": hipMemsetAsync failed");
         return ULTRA_ERR_HIP;
     }
     const dim3 grid((unsigned)((n_cand + ultra::RANK_CHUNK - 1) / ultra::RANK_CHUNK), (unsigned)batch);
-    (void)hipGetLastError();   // drop any stale error left by other users of the runtime
     hipLaunchKernelGGL(ultra::filtered_rank_kernel, grid, dim3(256), 0, s, (const float *)score, pos_index, known_ptr,
                        known_index, (long long)n_cand, reinterpret_cast<unsigned long long *>(rank_out),
-                       reinterpret_cast<long long *>(num_negative_out));
+                       reinterpret_cast<long long *>(num_negative_out), n_live);
     if (hipGetLastError() != hipSuccess) {
         ultra::set_error("filtered_rank_kernel launch failed");
         return ULTRA_ERR_HIP;
     }
     return ULTRA_OK;
+}
+
+extern "C" int32_t ultra_filtered_rank(const void *score, const int64_t *pos_index, const int64_t *known_ptr,
+                                       const int64_t *known_index, int64_t batch, int64_t n_cand, int64_t *rank_out,
+                                       int64_t *num_negative_out, void *stream) {
+    return filtered_rank_impl("ultra_filtered_rank", score, pos_index, known_ptr, known_index, batch, n_cand, rank_out,
+                              num_negative_out, nullptr, stream);
+}
+
+extern "C" int32_t ultra_filtered_rank_live(const void *score, const int64_t *pos_index, const int64_t *known_ptr,
+                                            const int64_t *known_index, int64_t batch, int64_t n_cand, int64_t *rank_out,
+                                            int64_t *num_negative_out, const int64_t *n_live, void *stream) {
+    if (!n_live) {
+        ultra::set_error("ultra_filtered_rank_live: n_live is NULL");
+        return ULTRA_ERR_INVALID;
+    }
+    return filtered_rank_impl("ultra_filtered_rank_live", score, pos_index, known_ptr, known_index, batch, n_cand, rank_out,
+                              num_negative_out, n_live, stream);
 }

@@ -16,6 +16,12 @@
 //      and writes ids, the STORED bits of the scores (gathered from the score matrix: -0.0 and NaN payloads survive) and the count.
 // A row of one chunk is finished by the first launch alone.  LDS atomics only count (histograms, the compaction cursor); the
 // survivors are sorted afterwards and their keys are distinct, so no output depends on the order atomics land in.
+//
+// A LIVE COUNT (ultra_filtered_topk_live): the row stride stays n_cand, the number of SLOTS, while only the ids
+// below *n_live -- read on the device, clamped to [0, n_cand] -- are candidates.  A dead id is never loaded, so whatever its
+// slot holds (a NaN, +inf) cannot reach a key; a chunk workgroup wholly beyond the live count still writes its empty partial
+// list, so the merge reads no stale workspace.  The grid and the workspace depend on (batch, n_cand) alone.  n_live == NULL
+// (ultra_filtered_topk) means n_cand: the same kernels, the same bits.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -159,6 +165,7 @@ __device__ int select_topk(u64 (&held)[TOPK_HELD], int k, int bytes, TopkScratch
     return m;
 }
 
+// (n_cand: the row's LIVE candidates, of which the known ids are a part)
 __device__ void write_answers(const float *row, long long n_cand, long long n_known, int k, int m, const u64 *sorted,
                               int64_t *ids_out, unsigned *scores_out, int64_t *count_out) {
     const int tid = threadIdx.x;
@@ -178,10 +185,18 @@ __device__ void write_answers(const float *row, long long n_cand, long long n_kn
     }
 }
 
+// The number of live candidates of a row of n_cand slots: *n_live clamped to [0, n_cand]; NULL: every slot.
+__device__ __forceinline__ long long live_count(const int64_t *__restrict__ n_live, long long n_cand) {
+    if (!n_live) return n_cand;
+    const long long v = *n_live;
+    return v < 0 ? 0 : (v < n_cand ? v : n_cand);
+}
+
 __global__ void __launch_bounds__(TOPK_THREADS) topk_chunk_kernel(const float *__restrict__ score, const int64_t *__restrict__ known_ptr,
                                                                   const int64_t *__restrict__ known_index, long long n_cand,
                                                                   long long n_chunk, int k, u64 *__restrict__ partial,
-                                                                  int64_t *ids_out, unsigned *scores_out, int64_t *count_out) {
+                                                                  int64_t *ids_out, unsigned *scores_out, int64_t *count_out,
+                                                                  const int64_t *__restrict__ n_live) {
     __shared__ unsigned ord[TOPK_CHUNK];
     __shared__ u64 sorted[TOPK_MAX];
     __shared__ TopkScratch s;
@@ -189,7 +204,9 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_chunk_kernel(const float *_
     const long long b = blockIdx.x / n_chunk, c = blockIdx.x % n_chunk;
     const float *row = score + b * n_cand;
     const long long lo = c * TOPK_CHUNK;
-    const int n = (int)(n_cand - lo < TOPK_CHUNK ? n_cand - lo : TOPK_CHUNK);
+    const long long live = live_count(n_live, n_cand);
+    // (a chunk beyond the live count holds no candidate: n == 0, nothing is loaded, an empty list is written)
+    const int n = (int)(live - lo < TOPK_CHUNK ? (live > lo ? live - lo : 0) : TOPK_CHUNK);
     // all of a thread's scores in flight at once, the search for the chunk's slice of known(b) beside them
     unsigned bits[TOPK_SLOTS];
 #pragma unroll
@@ -244,7 +261,7 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_chunk_kernel(const float *_
     }
     __syncthreads();
     if (n_chunk == 1) {
-        write_answers(row, n_cand, n_known, k, m, sorted, ids_out + b * k, scores_out + b * k, count_out + b);
+        write_answers(row, live, n_known, k, m, sorted, ids_out + b * k, scores_out + b * k, count_out + b);
     } else if (tid < k) {
         partial[((long long)blockIdx.x) * k + tid] = tid < m ? sorted[tid] : 0;
     }
@@ -253,7 +270,8 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_chunk_kernel(const float *_
 __global__ void __launch_bounds__(TOPK_THREADS) topk_merge_kernel(const float *__restrict__ score, const int64_t *__restrict__ known_ptr,
                                                                   long long n_cand, long long n_chunk, int k,
                                                                   const u64 *__restrict__ partial, int64_t *ids_out,
-                                                                  unsigned *scores_out, int64_t *count_out) {
+                                                                  unsigned *scores_out, int64_t *count_out,
+                                                                  const int64_t *__restrict__ n_live) {
     __shared__ u64 sorted[TOPK_MAX];
     __shared__ TopkScratch s;
     const int tid = threadIdx.x;
@@ -273,7 +291,8 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_merge_kernel(const float *_
         m = select_topk(held, k, 8, s, sorted);
     }
     const long long n_known = known_ptr ? known_ptr[b + 1] - known_ptr[b] : 0;
-    write_answers(score + b * n_cand, n_cand, n_known, k, m, sorted, ids_out + b * k, scores_out + b * k, count_out + b);
+    write_answers(score + b * n_cand, live_count(n_live, n_cand), n_known, k, m, sorted, ids_out + b * k, scores_out + b * k,
+                  count_out + b);
 }
 
 }  // namespace ultra
@@ -284,26 +303,28 @@ extern "C" int64_t ultra_filtered_topk_workspace(int64_t batch, int64_t n_cand, 
     return batch * n_chunk * (int64_t)k * (int64_t)sizeof(uint64_t);
 }
 
-extern "C" int32_t ultra_filtered_topk(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
-                                       int64_t n_cand, int32_t k, int64_t *ids_out, void *scores_out, int64_t *count_out,
-                                       void *workspace, int64_t workspace_bytes, void *stream) {
+// Both entries: `who` names the caller in the messages; n_live == NULL: every slot is a candidate.
+static int32_t filtered_topk_impl(const char *who_, const void *score, const int64_t *known_ptr, const int64_t *known_index,
+                                  int64_t batch, int64_t n_cand, int32_t k, int64_t *ids_out, void *scores_out, int64_t *count_out,
+                                  void *workspace, int64_t workspace_bytes, const int64_t *n_live, void *stream) {
+    const std::string who(who_);
     if (k < 1 || k > ULTRA_TOPK_MAX || n_cand >= (int64_t)1 << 31) {      // (before any pointer is looked at)
-        ultra::set_error("ultra_filtered_topk: k must lie in [1, " + std::to_string(ULTRA_TOPK_MAX) + "] and n_cand below 2^31");
+        ultra::set_error(who + ": k must lie in [1, " + std::to_string(ULTRA_TOPK_MAX) + "] and n_cand below 2^31");
         return ULTRA_ERR_UNSUPPORTED;
     }
     if (!score || !ids_out || !scores_out || !count_out || batch < 0 || n_cand <= 0) {
-        ultra::set_error("ultra_filtered_topk: NULL operand or empty candidate set");
+        ultra::set_error(who + ": NULL operand or empty candidate set");
         return ULTRA_ERR_INVALID;
     }
     const int64_t n_chunk = (n_cand + ULTRA_TOPK_CHUNK - 1) / ULTRA_TOPK_CHUNK;
     const int64_t need = ultra_filtered_topk_workspace(batch, n_cand, k);
     if (workspace_bytes < need || (need > 0 && !workspace) || ((uintptr_t)workspace & 7u) != 0) {
-        ultra::set_error("ultra_filtered_topk: workspace of " + std::to_string(workspace_bytes) + " bytes, needs " +
+        ultra::set_error(who + ": workspace of " + std::to_string(workspace_bytes) + " bytes, needs " +
                          std::to_string(need) + " (8-byte aligned)");
         return ULTRA_ERR_INVALID;
     }
     if (batch * n_chunk >= (int64_t)1 << 31) {
-        ultra::set_error("ultra_filtered_topk: batch * chunks per row must stay below 2^31");
+        ultra::set_error(who + ": batch * chunks per row must stay below 2^31");
         return ULTRA_ERR_UNSUPPORTED;
     }
     if (batch == 0) return ULTRA_OK;
@@ -312,7 +333,7 @@ extern "C" int32_t ultra_filtered_topk(const void *score, const int64_t *known_p
     (void)hipGetLastError();   // drop any stale error left by other users of the runtime
     hipLaunchKernelGGL(ultra::topk_chunk_kernel, dim3((unsigned)(batch * n_chunk)), dim3(ultra::TOPK_THREADS), 0, s,
                        (const float *)score, known_ptr, known_index, (long long)n_cand, (long long)n_chunk, (int)k,
-                       (ultra::u64 *)workspace, ids_out, (unsigned *)scores_out, count_out);
+                       (ultra::u64 *)workspace, ids_out, (unsigned *)scores_out, count_out, n_live);
     if (hipGetLastError() != hipSuccess) {
         ultra::set_error("topk_chunk_kernel launch failed");
         return ULTRA_ERR_HIP;
@@ -320,11 +341,29 @@ extern "C" int32_t ultra_filtered_topk(const void *score, const int64_t *known_p
     if (n_chunk > 1) {
         hipLaunchKernelGGL(ultra::topk_merge_kernel, dim3((unsigned)batch), dim3(ultra::TOPK_THREADS), 0, s, (const float *)score,
                            known_ptr, (long long)n_cand, (long long)n_chunk, (int)k, (const ultra::u64 *)workspace, ids_out,
-                           (unsigned *)scores_out, count_out);
+                           (unsigned *)scores_out, count_out, n_live);
         if (hipGetLastError() != hipSuccess) {
             ultra::set_error("topk_merge_kernel launch failed");
             return ULTRA_ERR_HIP;
         }
     }
     return ULTRA_OK;
+}
+
+extern "C" int32_t ultra_filtered_topk(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
+                                       int64_t n_cand, int32_t k, int64_t *ids_out, void *scores_out, int64_t *count_out,
+                                       void *workspace, int64_t workspace_bytes, void *stream) {
+    return filtered_topk_impl("ultra_filtered_topk", score, known_ptr, known_index, batch, n_cand, k, ids_out, scores_out, count_out,
+                              workspace, workspace_bytes, nullptr, stream);
+}
+
+extern "C" int32_t ultra_filtered_topk_live(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
+                                            int64_t n_cand, int32_t k, int64_t *ids_out, void *scores_out, int64_t *count_out,
+                                            void *workspace, int64_t workspace_bytes, const int64_t *n_live, void *stream) {
+    if (!n_live && k >= 1 && k <= ULTRA_TOPK_MAX && n_cand < (int64_t)1 << 31) {      // (the parent's UNSUPPORTED cases come first)
+        ultra::set_error("ultra_filtered_topk_live: n_live is NULL");
+        return ULTRA_ERR_INVALID;
+    }
+    return filtered_topk_impl("ultra_filtered_topk_live", score, known_ptr, known_index, batch, n_cand, k, ids_out, scores_out,
+                              count_out, workspace, workspace_bytes, n_live, stream);
 }

@@ -19,6 +19,10 @@ and relation, leaving out the ones the graph already states?
 Order: score descending, equal scores by ascending id, every NaN above every number (NaNs tie), -0.0 == +0.0
 -- the stable descending torch.sort.  A filtered candidate is removed, not rescored: a genuine -inf score is a candidate
 like any other, ranked last.  Slots beyond count = min(k, N - |known|) hold id -1 and score -inf.
+
+A GROWING graph: Predictor(entity_capacity=M) reserves M rows for entities that arrive later
+(Predictor.add_entities); the selection then runs over the LIVE ids of rows of N + M slots -- `num_live` of filtered_topk /
+filtered_above and their restatements, the ultra_filtered_*_live entries.
 """
 
 import copy
@@ -31,9 +35,30 @@ from . import _lib, dense, models, rspmm, tasks
 from .graph import Capture, param_state
 
 
-def filtered_topk_reference(pred, k, ptr=None, index=None):
+def _live_int(num_live, n):
+    """`num_live` (an int, or a one-element integer tensor) as an int in [1, n] (ValueError otherwise)."""
+    live = int(num_live)
+    if not 1 <= live <= n:
+        raise ValueError("num_live must lie in [1, %d] (the slots of a row), got %d" % (n, live))
+    return live
+
+
+def _live_operand(num_live, n, dev):
+    """`num_live` as the device int64 the _live entries read: a one-element int64 tensor on `dev` is passed as it is (its value is
+    not looked at on the host -- the kernels clamp it), an int is checked against [1, n] and uploaded."""
+    if torch.is_tensor(num_live):
+        if num_live.numel() != 1 or num_live.dtype != torch.long or num_live.device != dev:
+            raise ValueError("a tensor `num_live` is one int64 on the scores' device")
+        return num_live
+    return torch.tensor(_live_int(num_live, n), dtype=torch.long, device=dev)
+
+
+def filtered_topk_reference(pred, k, ptr=None, index=None, num_live=None):
     """(ids (batch, k) int64, scores (batch, k) pred's dtype, count (batch) int64) -- per row, the candidates are the ids not
-    in index[ptr[b] : ptr[b + 1]], in the order of the stable descending sort of their scores."""
+    in index[ptr[b] : ptr[b + 1]], in the order of the stable descending sort of their scores.  num_live: only the ids below it
+    exist -- this function on pred[:, :num_live]."""
+    if num_live is not None:
+        return filtered_topk_reference(pred[:, :_live_int(num_live, pred.shape[1])], k, ptr, index)
     k = int(k)
     batch, n = pred.shape
     ids = torch.full((batch, k), -1, dtype=torch.long, device=pred.device)
@@ -57,9 +82,10 @@ def _check_k(k):
         raise ValueError("k must be an int in [1, %d], got %r" % (_lib.TOPK_MAX, k))
 
 
-def filtered_topk(pred, k, ptr=None, index=None):
+def filtered_topk(pred, k, ptr=None, index=None, num_live=None):
     """filtered_topk_reference through the HIP kernel: pred (batch, N) fp32 on the GPU; ptr (batch + 1) / index int64, ids
-    ascending and distinct within a row; ptr None: no filter."""
+    ascending and distinct within a row; ptr None: no filter.  num_live (an int in [1, N], or one int64 on the device, read by
+    the kernels): ultra_filtered_topk_live on the full rows -- no slice, no copy; None: ultra_filtered_topk."""
     _check_k(k)
     if not pred.is_cuda:
         raise RuntimeError("ultra_amd.predict.filtered_topk: expected a GPU tensor; the MI355X engine has no CPU path")
@@ -78,9 +104,13 @@ def filtered_topk(pred, k, ptr=None, index=None):
             raise ValueError("filtered_topk takes int64 `ptr` of shape (batch + 1,) and int64 `index` on the scores' device")
         ptr, index = ptr.contiguous(), index.contiguous()      # (referenced until the launch is enqueued)
     ws = torch.empty(max(1, _lib.lib.ultra_filtered_topk_workspace(batch, n, k) // 8), dtype=torch.long, device=dev)
-    _lib.check(_lib.lib.ultra_filtered_topk(pred.data_ptr(), None if ptr is None else ptr.data_ptr(),
-                                            None if ptr is None else index.data_ptr(), batch, n, k, ids.data_ptr(),
-                                            scores.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel() * 8, _lib.stream_of(dev)))
+    args = (pred.data_ptr(), None if ptr is None else ptr.data_ptr(), None if ptr is None else index.data_ptr(), batch, n, k,
+            ids.data_ptr(), scores.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel() * 8)
+    if num_live is None:
+        _lib.check(_lib.lib.ultra_filtered_topk(*args, _lib.stream_of(dev)))
+    else:
+        live = _live_operand(num_live, n, dev)     # (referenced until the launch is enqueued)
+        _lib.check(_lib.lib.ultra_filtered_topk_live(*args, live.data_ptr(), _lib.stream_of(dev)))
     return ids, scores, count
 
 
@@ -103,7 +133,7 @@ def logit_threshold(probability):
     return float(torch.tensor(math.log(p / (1.0 - p)), dtype=torch.float64).to(torch.float32))
 
 
-def filtered_above_reference(pred, threshold, ptr=None, index=None):
+def filtered_above_reference(pred, threshold, ptr=None, index=None, num_live=None):
     """The answer SET of every row, ranked: (out_ptr (batch + 1) int64, ids (total) int64, scores (total) pred's dtype, size
     (batch) int64), on any device -- the definition ultra_filtered_above is tested against.
 
@@ -118,7 +148,11 @@ def filtered_above_reference(pred, threshold, ptr=None, index=None):
     Two differences from the reference's rule (script/run_query.py:42-44, `prob > 0.5`).  The rule here is on the LOGIT, logit
     > logit_threshold(p): for p = 0.5 the reference's fp32 sigmoid(x) > 0.5 is false for positive logits so small that the
     sigmoid rounds to 0.5 (roughly below 1e-7); such logits are members here.  And `size` is an integer count, not the
-    reference's soft num_pred; query_eval keeps the reference's metrics as they are."""
+    reference's soft num_pred; query_eval keeps the reference's metrics as they are.
+
+    num_live: only the ids below it exist -- this function on pred[:, :num_live]."""
+    if num_live is not None:
+        return filtered_above_reference(pred[:, :_live_int(num_live, pred.shape[1])], threshold, ptr, index)
     thr = _fp32_threshold(threshold)
     batch, n = pred.shape
     dev = pred.device
@@ -140,11 +174,12 @@ def filtered_above_reference(pred, threshold, ptr=None, index=None):
     return out_ptr, ids, scores, size
 
 
-def filtered_above(pred, threshold, ptr=None, index=None):
+def filtered_above(pred, threshold, ptr=None, index=None, num_live=None):
     """filtered_above_reference through the HIP kernels (csrc/above_kernels.hip): pred (batch, N) fp32 on the GPU; ptr
     (batch + 1) / index int64, ids ascending and distinct within a row; ptr None: no filter.  `ids` and `scores` come back as
     the full-capacity (batch * N) buffers: entries at or beyond out_ptr[batch] are unspecified.  No host wait is made -- the
-    caller reads out_ptr[-1] when it wants to slice."""
+    caller reads out_ptr[-1] when it wants to slice.  num_live (an int in [1, N], or one int64 on the device, read by the
+    kernels): ultra_filtered_above_live on the full rows; None: ultra_filtered_above."""
     thr = _fp32_threshold(threshold)
     if not pred.is_cuda:
         raise RuntimeError("ultra_amd.predict.filtered_above: expected a GPU tensor; the MI355X engine has no CPU path")
@@ -166,10 +201,13 @@ def filtered_above(pred, threshold, ptr=None, index=None):
             raise ValueError("filtered_above takes int64 `ptr` of shape (batch + 1,) and int64 `index` on the scores' device")
         ptr, index = ptr.contiguous(), index.contiguous()      # (referenced until the launch is enqueued)
     ws = torch.empty(max(1, _lib.lib.ultra_filtered_above_workspace(batch, n) // 8), dtype=torch.long, device=dev)
-    _lib.check(_lib.lib.ultra_filtered_above(pred.data_ptr(), None if ptr is None else ptr.data_ptr(),
-                                             None if ptr is None else index.data_ptr(), batch, n, thr, out_ptr.data_ptr(),
-                                             ids.data_ptr(), scores.data_ptr(), ids.numel(), size.data_ptr(), ws.data_ptr(),
-                                             ws.numel() * 8, _lib.stream_of(dev)))
+    args = (pred.data_ptr(), None if ptr is None else ptr.data_ptr(), None if ptr is None else index.data_ptr(), batch, n, thr,
+            out_ptr.data_ptr(), ids.data_ptr(), scores.data_ptr(), ids.numel(), size.data_ptr(), ws.data_ptr(), ws.numel() * 8)
+    if num_live is None:
+        _lib.check(_lib.lib.ultra_filtered_above(*args, _lib.stream_of(dev)))
+    else:
+        live = _live_operand(num_live, n, dev)     # (referenced until the launch is enqueued)
+        _lib.check(_lib.lib.ultra_filtered_above_live(*args, live.data_ptr(), _lib.stream_of(dev)))
     return out_ptr, ids, scores, size
 
 
@@ -194,7 +232,8 @@ def known_answers(data, anchor, relation, mode="tail"):
 def _candidates(data, anchor, relation, mode):
     """The t_batch (mode="tail") or h_batch (mode="head") form of tasks.all_negative for queries without a positive: every
     entity as the tail of (anchor, relation) or as the head of (relation, anchor).  The model turns the head form into a
-    tail query with the inverse relation, exactly as in evaluation."""
+    tail query with the inverse relation, exactly as in evaluation.  On a graph with reserved rows (Predictor(entity_capacity))
+    data.num_nodes counts slots: the batch runs over all of them, and the selection afterwards knows how many are live."""
     n = data.num_nodes
     every = torch.arange(n, device=anchor.device).unsqueeze(0).expand(len(anchor), -1)
     fixed = anchor.unsqueeze(-1).expand(-1, n)
@@ -207,8 +246,10 @@ class _GraphedPredictStep(Capture):
     forward and ultra_filtered_topk.  Per batch the host copies the (bs) anchors and relations and the (bs + 1) offsets into
     the known lists of the whole call, which live in a buffer of the step (`load_index`, once per call)."""
 
-    def __init__(self, model, data, batch_size, k, mode, index_capacity, warmup=2, delta=None):
-        """delta (rspmm.GraphDelta or None): handed to the model from the first capture.  While it is empty the model takes its
+    def __init__(self, model, data, batch_size, k, mode, index_capacity, warmup=2, delta=None, n_live=None):
+        """n_live (one int64 on the device, or None): the live count of a graph with reserved rows -- the selection is then
+        ultra_filtered_topk_live, which reads it at replay; None: ultra_filtered_topk, exactly as before.
+        delta (rspmm.GraphDelta or None): handed to the model from the first capture.  While it is empty the model takes its
         normal path; once it holds facts or tombstones the capture records the delta's launches, which read its device buffers
         at replay --
         `route` is what the Predictor compares to know whether this capture still serves the delta."""
@@ -230,12 +271,17 @@ class _GraphedPredictStep(Capture):
         ws_bytes = _lib.lib.ultra_filtered_topk_workspace(batch_size, n, k)
         self.ws = torch.empty(max(1, ws_bytes // 8), dtype=torch.long, device=dev)
 
+        self.n_live = n_live
+
         def step():
             pred = model(data, _candidates(data, self.anchor, self.relation, mode), **model_kwargs).float().contiguous()
-            _lib.check(_lib.lib.ultra_filtered_topk(pred.data_ptr(), self.ptr.data_ptr() if self.filtered else None,
-                                                    self.index.data_ptr() if self.filtered else None, batch_size, n, k,
-                                                    self.ids.data_ptr(), self.scores.data_ptr(), self.count.data_ptr(),
-                                                    self.ws.data_ptr(), self.ws.numel() * 8, _lib.stream_of(dev)))
+            args = (pred.data_ptr(), self.ptr.data_ptr() if self.filtered else None,
+                    self.index.data_ptr() if self.filtered else None, batch_size, n, k, self.ids.data_ptr(),
+                    self.scores.data_ptr(), self.count.data_ptr(), self.ws.data_ptr(), self.ws.numel() * 8)
+            if n_live is None:
+                _lib.check(_lib.lib.ultra_filtered_topk(*args, _lib.stream_of(dev)))
+            else:
+                _lib.check(_lib.lib.ultra_filtered_topk_live(*args, n_live.data_ptr(), _lib.stream_of(dev)))
 
         self.warm_up(step, warmup)
         self.capture(step)
@@ -287,12 +333,31 @@ def _without_facts(graph, h, r, t):
     return out
 
 
+def _with_slots(graph, slots, relation_graph=False):
+    """A shallow copy of `graph` with num_nodes = slots >= graph.num_nodes: the same edge list, the rows beyond the old count
+    reserved (no edge names them).  relation_graph: build the copy's own where `graph` carries one -- it equals graph's, a
+    node without edges plays no role."""
+    out = copy.copy(graph)
+    out.num_nodes = int(slots)
+    if relation_graph and getattr(graph, "relation_graph", None) is not None:
+        tasks.build_relation_graph(out)
+    return out
+
+
 def _entity_model(model):
     return getattr(model, "entity_model", model)
 
 
-def _check_facts(data, h, r, t):
-    """(h, r, t) of verify_*: int64 vectors of one length on the graph's device, r a direct relation (ValueError otherwise)."""
+def _check_live(ids, num_live, what):
+    """ValueError unless every id is an entity in use: ids in [0, num_live) (a graph with reserved rows; one host read)."""
+    if len(ids) and bool(((ids < 0) | (ids >= num_live)).any()):
+        raise ValueError("%s must be existing entities (ids in [0, %d)): a reserved row is no entity until add_entities hands "
+                         "it out" % (what, num_live))
+
+
+def _check_facts(data, h, r, t, num_live=None):
+    """(h, r, t) of verify_*: int64 vectors of one length on the graph's device, r a direct relation (ValueError otherwise);
+    num_live (a graph with reserved rows): h and t below it."""
     dev = data.edge_index.device
     h, r, t = (torch.as_tensor(v, dtype=torch.long, device=dev).flatten() for v in (h, r, t))
     if not (h.shape == r.shape == t.shape):
@@ -301,6 +366,8 @@ def _check_facts(data, h, r, t):
     if len(r) and bool(((r < 0) | (r >= direct)).any()):
         raise ValueError("verify takes direct relations (r < num_relations // 2 = %d): a fact stated through an inverse relation "
                          "is its direct twin" % direct)
+    if num_live is not None:
+        _check_live(torch.cat([h, t]), num_live, "a fact's head and tail")
     return h, r, t
 
 
@@ -344,10 +411,11 @@ class _GraphedVerifyStep(Capture):
     candidates, the masked forward on the full graph's cached plans, ultra_filtered_rank and the gather of the positives' scores.
     Per batch the host copies the triples and the (bs + 1) offsets into the known lists of the whole call (`load_index`)."""
 
-    def __init__(self, model, data, batch_size, mode, index_capacity, warmup=2):
+    def __init__(self, model, data, batch_size, mode, index_capacity, warmup=2, n_live=None):
+        """n_live: as in _GraphedPredictStep -- ultra_filtered_rank_live over the live ids, or (None) ultra_filtered_rank."""
         dev = data.edge_index.device
         Capture.__init__(self, dev)
-        self.model, self.bs, self.mode = model, batch_size, mode
+        self.model, self.bs, self.mode, self.n_live = model, batch_size, mode, n_live
         self.capacity = max(1, int(index_capacity))
         self.triples = torch.zeros(batch_size, 3, dtype=torch.long, device=dev)       # (h, t, r)
         self.ptr = torch.zeros(batch_size + 1, dtype=torch.long, device=dev)
@@ -365,9 +433,12 @@ class _GraphedVerifyStep(Capture):
             anchor, pos = (h, t) if mode == "tail" else (t, h)
             pred = model(data, _candidates(data, anchor, r, mode), edge_keep=keep).float().contiguous()
             pos = pos.contiguous()
-            _lib.check(_lib.lib.ultra_filtered_rank(pred.data_ptr(), pos.data_ptr(), self.ptr.data_ptr(), self.index.data_ptr(),
-                                                    batch_size, n, self.rank.data_ptr(), self.num_negative.data_ptr(),
-                                                    _lib.stream_of(dev)))
+            args = (pred.data_ptr(), pos.data_ptr(), self.ptr.data_ptr(), self.index.data_ptr(), batch_size, n,
+                    self.rank.data_ptr(), self.num_negative.data_ptr())
+            if n_live is None:
+                _lib.check(_lib.lib.ultra_filtered_rank(*args, _lib.stream_of(dev)))
+            else:
+                _lib.check(_lib.lib.ultra_filtered_rank_live(*args, n_live.data_ptr(), _lib.stream_of(dev)))
             self.score.copy_(pred.gather(1, pos.unsqueeze(-1)).squeeze(-1))
 
         self.warm_up(step, warmup)
@@ -411,12 +482,34 @@ class Predictor(object):
     retracted tail can be returned as an answer again.  The captured step is made again when the first tombstone arrives; from
     then on further remove_facts / add_facts cost no capture and no plan unless the relation graph changes.  compact() folds
     the delta, tombstones included, into `data` (a host plan, new captures); add_facts / remove_facts do so themselves when
-    the capacity would be exceeded, and explain_* / verify_* do so first when the delta holds edits."""
+    the capacity would be exceeded, and explain_* / verify_* do so first when the delta holds edits.
 
-    def __init__(self, model, data, k=10, batch_size=8, filtered_data=None, filtered=True, use_graph=True, delta_capacity=256):
+    A GROWING graph: entity_capacity=M > 0 reserves M rows for entities that arrive later.  The graph served is
+    then a shallow copy of `data` with num_nodes = N + M SLOTS (the same edge list; its own relation graph, equal to the
+    unpadded one), `num_entities` of them live; add_entities(count) hands out the next ids and does nothing else -- no plan, no
+    capture: the live count also lives in one device int64 (`live_count`, the same tensor for the predictor's life) that the
+    selection kernels read at replay.  The new ids are heads, tails and anchors like any other from then on; an id in
+    [num_entities, slots) is a ValueError everywhere and never an answer.  Every result is that of a fresh
+    Predictor(entity_capacity=0) on delta.materialize(data, num_nodes=num_entities).  A call that would exceed the reserve
+    compacts and reserves M rows anew (one rebuild).  entity_capacity=0 (the default): `data` itself is served, by exactly the
+    entry points of before, and add_entities raises."""
+
+    def __init__(self, model, data, k=10, batch_size=8, filtered_data=None, filtered=True, use_graph=True, delta_capacity=256,
+                 entity_capacity=0):
         _check_k(k)
         if filtered_data is None:
             filtered_data = getattr(data, "filtered_data", None)
+        if isinstance(entity_capacity, bool) or not isinstance(entity_capacity, int) or entity_capacity < 0:
+            raise ValueError("entity_capacity must be a non-negative int (reserved rows), got %r" % (entity_capacity,))
+        self.entity_capacity = entity_capacity
+        self.num_entities = int(data.num_nodes)
+        self.live_count = None
+        if entity_capacity:
+            slots = self.num_entities + entity_capacity
+            data = _with_slots(data, slots, relation_graph=True)
+            if filtered_data is not None:
+                filtered_data = _with_slots(filtered_data, slots)
+            self.live_count = torch.full((1,), self.num_entities, dtype=torch.long, device=data.edge_index.device)
         self.model, self.data, self.k, self.batch_size = model, data, k, int(batch_size)
         self.filter_graph = data if filtered_data is None else filtered_data
         self.filtered, self.use_graph = bool(filtered), bool(use_graph)
@@ -432,7 +525,47 @@ class Predictor(object):
             self._takes_delta = "delta" in inspect.signature(getattr(model, "forward", model)).parameters
         except (TypeError, ValueError):
             self._takes_delta = False
-        self.delta = rspmm.GraphDelta(data, delta_capacity) if self._takes_delta else None
+        self.delta = self._new_delta(data) if self._takes_delta else None
+
+    def _new_delta(self, data, capacity=None):
+        return rspmm.GraphDelta(data, self.delta_capacity if capacity is None else capacity, num_live=self.num_entities)
+
+    @property
+    def num_slots(self):
+        """The rows of the served graph: num_entities live ones and the rest of the reserve."""
+        return int(self.data.num_nodes)
+
+    # ---- the growing graph ----
+    def add_entities(self, count=1):
+        """`count` new entities: returns their ids [num_entities, num_entities + count) (int64, on the graph's device) and raises
+        the live count -- the host int and the device scalar the captured selection reads.  Nothing else happens: no plan, no
+        capture, no relation graph (an entity without facts plays no role); it is a candidate of every query from now on, scored
+        as an isolated node, and add_facts / remove_facts / tails / heads / ... take its id.  Beyond the reserve the graph is
+        compacted and num_entities + count + entity_capacity slots are laid out: one rebuild.  ValueError on a predictor
+        without a reserve (entity_capacity=0)."""
+        if not self.entity_capacity:
+            raise ValueError("this Predictor reserves no rows: create it with entity_capacity > 0 to add entities")
+        if isinstance(count, bool) or not isinstance(count, int) or count < 1:
+            raise ValueError("count must be a positive int, got %r" % (count,))
+        first = self.num_entities
+        if first + count > self.num_slots:
+            self.compact(slots=first + count + self.entity_capacity)
+        self.num_entities = first + count
+        self.live_count.fill_(self.num_entities)
+        if self.delta is not None:
+            self.delta.num_live = self.num_entities
+        return torch.arange(first, first + count, dtype=torch.long, device=self.data.edge_index.device)
+
+    def materialized(self):
+        """The graph a fresh Predictor would be given for the same answers: the served edge list with the delta's edits
+        (GraphDelta.materialize) and num_nodes = num_entities -- no reserved row -- with the filter graph held now as its
+        `filtered_data` where that is a graph of its own.  A new copy at every call."""
+        probe = self.delta if self.delta is not None else self._new_delta(self.data, 1)
+        out = copy.copy(probe.materialize(self.data, num_nodes=self.num_entities))
+        if not self._filter_is_data:        # (a separate filter graph: the one held now, the stated facts included)
+            out.filtered_data = copy.copy(self.filter_graph)
+            out.filtered_data.num_nodes = self.num_entities
+        return out
 
     # ---- the live graph ----
     def add_facts(self, h, r, t):
@@ -440,7 +573,7 @@ class Predictor(object):
         otherwise: the sets of entities and relations are fixed).  Each adds the edges (h, t, r) and (t, h, r + num_relations / 2)
         to the served graph and to the filter graph; a repeated fact is one more parallel edge.  Returns the number of facts the
         delta holds afterwards (0 after a compaction: more facts than delta_capacity, or a model without a delta route)."""
-        probe = self.delta if self.delta is not None else rspmm.GraphDelta(self.data, 1)
+        probe = self.delta if self.delta is not None else self._new_delta(self.data, 1)
         h, r, t = probe.check(h, r, t)
         if len(h) == 0:
             return 0 if self.delta is None else len(self.delta)
@@ -456,7 +589,7 @@ class Predictor(object):
         (h, t, r) or (t, h, r + num_relations / 2) leaves the served graph and the filter graph (a fact stated nowhere is a
         no-op).  Returns an int64 vector: the number of direct edges each fact took out of the served graph
         (GraphDelta.remove).  Compacts first where the delta cannot hold the tombstones."""
-        probe = self.delta if self.delta is not None else rspmm.GraphDelta(self.data, 1)
+        probe = self.delta if self.delta is not None else self._new_delta(self.data, 1)
         h, r, t = probe.check(h, r, t)
         if len(h) == 0:
             return torch.zeros(0, dtype=torch.long, device=h.device)
@@ -470,7 +603,7 @@ class Predictor(object):
         if fits():
             removed = self.delta.remove(h, r, t)
         else:
-            fold = rspmm.GraphDelta(self.data, len(h))
+            fold = self._new_delta(self.data, len(h))
             removed = fold.remove(h, r, t)
         if not self._filter_is_data:
             self._filter_base = _without_facts(self._filter_base, h, r, t)
@@ -488,16 +621,20 @@ class Predictor(object):
             fh, fr, ft = self.delta.facts[:len(self.delta)].unbind(1)
             self.filter_graph = _with_facts(self._filter_base, fh, fr, ft)
 
-    def compact(self, extra=None, delta=None):
+    def compact(self, extra=None, delta=None, slots=None):
         """Fold the delta's edits (and `extra` = (h, r, t), checked by the caller) into `data`: the materialised graph -- without
         the tombstoned edges, with the added ones -- becomes the served graph -- its relation graph rebuilt, a host plan on the
-        next query, new captures -- and the delta is emptied.  `delta`: fold that one instead of the Predictor's own."""
+        next query, new captures -- and the delta is emptied.  `delta`: fold that one instead of the Predictor's own.  The
+        slot count and the live count of a graph with reserved rows stay; `slots` (add_entities beyond the reserve): the new
+        slot count, laid out in the same rebuild."""
         delta = self.delta if delta is None else delta
         facts = [] if delta is None else [delta.facts[:len(delta)]]
         if extra is not None:
             facts.append(torch.stack(list(extra), dim=1))
         facts = torch.cat(facts) if facts else torch.zeros(0, 3, dtype=torch.long)
-        if len(facts) == 0 and not (delta is not None and delta.num_removed):
+        if slots is not None and int(slots) == self.num_slots:
+            slots = None
+        if len(facts) == 0 and not (delta is not None and delta.num_removed) and slots is None:
             return
         fh, fr, ft = facts.unbind(1)
         base = self.data
@@ -505,17 +642,31 @@ class Predictor(object):
             base = copy.copy(self.data)
             base.edge_index, base.edge_type = delta.surviving(self.data.edge_index, self.data.edge_type)
         data = _with_facts(base, fh, fr, ft)
+        if slots is not None:
+            data.num_nodes = int(slots)
         if getattr(self.data, "relation_graph", None) is not None:
             tasks.build_relation_graph(data)
-        self._filter_base = data if self._filter_is_data else _with_facts(self._filter_base, fh, fr, ft)
+        if self._filter_is_data:
+            self._filter_base = data
+        else:
+            self._filter_base = _with_facts(self._filter_base, fh, fr, ft)
+            if slots is not None:
+                self._filter_base.num_nodes = int(slots)
         self.filter_graph = self._filter_base
         self.close()
         self.data = data
         if self._takes_delta:
-            self.delta = rspmm.GraphDelta(data, self.delta_capacity)
+            self.delta = self._new_delta(data)
 
     def _model_kwargs(self):
         return {} if self.delta is None else {"delta": self.delta}
+
+    def _select_kwargs(self, pred):
+        """What the eager selection takes beside today's arguments: nothing without a reserve; with one, the live count -- the
+        device scalar for the kernels, the host int for the plain-torch restatements."""
+        if not self.entity_capacity:
+            return {}
+        return {"num_live": self.live_count if pred.is_cuda else self.num_entities}
 
     def tails(self, h, r):
         return self._run(h, r, "tail")
@@ -612,7 +763,8 @@ class Predictor(object):
             step.release()
             del self._steps[mode]
         capacity = None if need is None else max(2 * need, 1 << 16)
-        step = _GraphedPredictStep(self.model, self.data, self.batch_size, self.k, mode, capacity, delta=self.delta)
+        step = _GraphedPredictStep(self.model, self.data, self.batch_size, self.k, mode, capacity, delta=self.delta,
+                                   n_live=self.live_count)
         self._steps[mode] = step
         return step
 
@@ -624,16 +776,16 @@ class Predictor(object):
         if step is not None:
             step.release()
             del self._steps[key]
-        step = _GraphedVerifyStep(self.model, self.data, self.batch_size, mode, max(2 * need, 1 << 16))
+        step = _GraphedVerifyStep(self.model, self.data, self.batch_size, mode, max(2 * need, 1 << 16), n_live=self.live_count)
         self._steps[key] = step
         return step
 
     @torch.no_grad()
     def _verify(self, h, r, t, mode):
+        h, r, t = _check_facts(self.data, h, r, t, num_live=self.num_entities if self.entity_capacity else None)
         if self.delta is not None and self.delta.edited:
             self.compact()      # (the keep masks run over the graph's own edge list: the edits become part of it first)
         data, bs = self.data, self.batch_size
-        h, r, t = _check_facts(data, h, r, t)
         dev = h.device
         n = len(h)
         score = torch.empty(n, dtype=torch.float32, device=dev)
@@ -676,9 +828,12 @@ class Predictor(object):
                 pred = self.model(data, _candidates(data, anchor, part[:, 2], mode), edge_keep=keep).float().contiguous()
                 pos, b_ptr = pos.contiguous(), ptr[lo:lo + len(part) + 1].contiguous()
                 b_rank, b_neg = torch.empty_like(pos), torch.empty_like(pos)
-                _lib.check(_lib.lib.ultra_filtered_rank(pred.data_ptr(), pos.data_ptr(), b_ptr.data_ptr(), index.data_ptr(),
-                                                        len(part), pred.shape[1], b_rank.data_ptr(), b_neg.data_ptr(),
-                                                        _lib.stream_of(dev)))
+                args = (pred.data_ptr(), pos.data_ptr(), b_ptr.data_ptr(), index.data_ptr(), len(part), pred.shape[1],
+                        b_rank.data_ptr(), b_neg.data_ptr())
+                if self.live_count is None:
+                    _lib.check(_lib.lib.ultra_filtered_rank(*args, _lib.stream_of(dev)))
+                else:
+                    _lib.check(_lib.lib.ultra_filtered_rank_live(*args, self.live_count.data_ptr(), _lib.stream_of(dev)))
                 score[lo:lo + len(part)] = pred.gather(1, pos.unsqueeze(-1)).squeeze(-1)
                 rank[lo:lo + len(part)], num_negative[lo:lo + len(part)] = b_rank, b_neg
         finally:
@@ -694,6 +849,8 @@ class Predictor(object):
         relation = torch.as_tensor(relation, dtype=torch.long, device=dev).flatten()
         if anchor.shape != relation.shape:
             raise ValueError("one relation per query: got %d entities and %d relations" % (len(anchor), len(relation)))
+        if self.entity_capacity:
+            _check_live(anchor, self.num_entities, "the anchors of a query")
         n = len(anchor)
         out_ptr, ids, scores, size = [torch.zeros(1, dtype=torch.long, device=dev)], [], [], []
         was_training = self.model.training
@@ -708,11 +865,12 @@ class Predictor(object):
                                   **self._model_kwargs()).float()
                 b_ptr = None if ptr is None else ptr[lo:lo + len(pred) + 1]
                 if pred.is_cuda:
-                    b_out, b_ids, b_scores, b_size = filtered_above(pred, threshold, b_ptr, index)
+                    b_out, b_ids, b_scores, b_size = filtered_above(pred, threshold, b_ptr, index, **self._select_kwargs(pred))
                     total = int(b_out[-1])      # (the one host read of the batch)
                     b_ids, b_scores = b_ids[:total].clone(), b_scores[:total].clone()
                 else:
-                    b_out, b_ids, b_scores, b_size = filtered_above_reference(pred, threshold, b_ptr, index)
+                    b_out, b_ids, b_scores, b_size = filtered_above_reference(pred, threshold, b_ptr, index,
+                                                                              **self._select_kwargs(pred))
                     total = b_ids.numel()
                 out_ptr.append(b_out[1:] + at)
                 ids.append(b_ids)
@@ -734,6 +892,8 @@ class Predictor(object):
         relation = torch.as_tensor(relation, dtype=torch.long, device=dev).flatten()
         if anchor.shape != relation.shape:
             raise ValueError("one relation per query: got %d entities and %d relations" % (len(anchor), len(relation)))
+        if self.entity_capacity:
+            _check_live(anchor, self.num_entities, "the anchors of a query")
         n = len(anchor)
         ids = torch.empty(n, k, dtype=torch.long, device=dev)
         scores = torch.empty(n, k, dtype=torch.float32, device=dev)
@@ -776,7 +936,7 @@ class Predictor(object):
                 b_ptr = None if ptr is None else ptr[lo:lo + len(pred) + 1]
                 # the fused kernel on the GPU; the restatement with the same interface elsewhere (as eval._local_rows does)
                 select = filtered_topk if pred.is_cuda else filtered_topk_reference
-                b_ids, b_scores, b_count = select(pred, k, b_ptr, index)
+                b_ids, b_scores, b_count = select(pred, k, b_ptr, index, **self._select_kwargs(pred))
                 ids[lo:lo + len(pred)], scores[lo:lo + len(pred)], count[lo:lo + len(pred)] = b_ids, b_scores, b_count
         finally:
             self.model.train(was_training)

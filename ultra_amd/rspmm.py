@@ -696,13 +696,21 @@ class GraphDelta(object):
       degree      int64 (num_nodes)       SIGNED: added minus removed edges counted at edge_index[1] (what `mean` adds to the base
                                           bincount)
     relation_graph: tasks.build_relation_graph of the materialised list, rebuilt at add() / remove(); the previous object is kept
-    when the new adjacency equals the old one (the common case), so its plan and the captures that pin it stay valid."""
+    when the new adjacency equals the old one (the common case), so its plan and the captures that pin it stay valid.
 
-    def __init__(self, data, capacity=1024):
+    A GROWING graph: `data` may hold reserved rows -- num_nodes counts SLOTS, of which the ids below `num_live`
+    are entities in use.  num_nodes stays what the plan check of Plan.delta_rows / edit_rows compares and what sizes `degree`
+    and the key codes; `check` takes the live bound, which the owner raises as entities arrive (Predictor.add_entities), and
+    materialize(num_nodes=num_live) is the graph a fresh predictor would be given."""
+
+    def __init__(self, data, capacity=1024, num_live=None):
         if not isinstance(capacity, int) or capacity < 1:
             raise ValueError("capacity must be a positive int (facts), got %r" % (capacity,))
         self.base = data
         self.num_nodes, self.num_relations = int(data.num_nodes), int(data.num_relations)
+        self.num_live = self.num_nodes if num_live is None else int(num_live)
+        if not 0 <= self.num_live <= self.num_nodes:
+            raise ValueError("num_live must lie in [0, num_nodes = %d], got %r" % (self.num_nodes, num_live))
         self.capacity = capacity
         dev = data.edge_index.device
         self.device = dev
@@ -745,13 +753,14 @@ class GraphDelta(object):
 
     def check(self, h, r, t):
         """(h, r, t) as int64 vectors of one length on the delta's device; ValueError for ids outside the graph or a relation
-        that is not direct (num_nodes and num_relations are fixed: no new entities or relations)."""
+        that is not direct (the entities are the ids below num_live -- num_nodes unless rows are reserved -- and num_relations
+        is fixed)."""
         h, r, t = (torch.as_tensor(v, dtype=torch.long, device=self.device).flatten() for v in (h, r, t))
         if not (h.shape == r.shape == t.shape):
             raise ValueError("one head, relation and tail per fact: got %d heads, %d relations and %d tails" % (len(h), len(r), len(t)))
         if len(h):
-            if bool(((h < 0) | (h >= self.num_nodes) | (t < 0) | (t >= self.num_nodes)).any()):
-                raise ValueError("a fact's head and tail must be existing entities (ids in [0, %d))" % self.num_nodes)
+            if bool(((h < 0) | (h >= self.num_live) | (t < 0) | (t >= self.num_live)).any()):
+                raise ValueError("a fact's head and tail must be existing entities (ids in [0, %d))" % self.num_live)
             if bool(((r < 0) | (r >= self.num_relations // 2)).any()):
                 raise ValueError("a fact is stated through a direct relation (r < num_relations // 2 = %d); its inverse edge "
                                  "is added with it" % (self.num_relations // 2))
@@ -881,11 +890,18 @@ class GraphDelta(object):
         if not same:
             self.relation_graph = new
 
-    def materialize(self, data=None):
+    def materialize(self, data=None, num_nodes=None):
         """`data` (default: the base graph) without the edges a tombstone matches and with the delta's edges appended in
         materialised order, and the delta's relation graph: a copy that shares every other field.  Kept until the next add() /
-        remove(), so the plan cache sees one graph."""
+        remove(), so the plan cache sees one graph.  num_nodes (a graph with reserved rows: the live count): the copy's
+        num_nodes, every edge below it -- the same edge list without the reserved rows, a new copy at every call."""
         data = self.base if data is None else data
+        if num_nodes is not None and int(num_nodes) != int(data.num_nodes):
+            out = copy.copy(self.materialize(data))
+            out.num_nodes = int(num_nodes)
+            if out.edge_index.numel() and int(out.edge_index.max()) >= out.num_nodes:
+                raise ValueError("an edge names id %d, outside num_nodes = %d" % (int(out.edge_index.max()), out.num_nodes))
+            return out
         hit = self._materialized
         if hit is not None and hit[0] is data:
             return hit[1]
