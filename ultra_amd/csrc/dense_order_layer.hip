@@ -61,6 +61,9 @@ struct DenseOrderParams {
     float eps;
 };
 
+constexpr int DOL_GROUP = 4;       // columns per burst of the four-tile chain (see there); 2, 8 and 16 measured within 1 - 4 us of it
+constexpr int DOL_FENCE = 0x94;    // what may cross the fences of that chain (sched_barrier mask): scalar, vector-memory and LDS
+                                   // instructions -- they issue beside the matrix pipe -- but no vector arithmetic
 constexpr int DOL_ROW_STRIDE = 68;   // floats per LDS tile row (see dense_layer.hip)
 
 __device__ __forceinline__ float byte_of(uint32_t w, int q) { return (float)((w >> (8 * q)) & 0xffu); }
@@ -72,12 +75,19 @@ __device__ __forceinline__ float byte_of(uint32_t w, int q) { return (float)((w 
 #else
 #define ULTRA_DOL_ATTR
 #endif
-// TILES: 16-row tiles of one workgroup (1 or 2).  Two tiles share every B operand of the chain -- the messages rel * x[column] are
+// TILES: 16-row tiles of one workgroup (1, 2 or 4).  Two tiles share every B operand of the chain -- the messages rel * x[column] are
 // the same for all rows; only the adjacency bytes and the accumulator differ -- so a wave runs two independent chains over one
 // stream of operands: half the workgroups (120 instead of 240 at 474 nodes x 8 samples), half the x traffic, and the second
 // chain's matrix instruction hides the byte -> float conversions and the product that one chain per SIMD leaves in the open.
 // Chosen where the launch does not own the chip (two batches in flight: the relation-graph layers of one batch run on the 64 CUs
 // the other batch's entity layers leave -- 240 workgroups need two rounds there, 120 one); same bits either way.
+// FOUR tiles: the footprint of the packed form below (one workgroup per four row tiles of a sample) as one wave per SIMD with four
+// independent chains.  Measured with in-kernel cycle stamps at 2.38 GHz: a matrix instruction costs 54 - 57 cycles, not 32,
+// wherever a vector instruction of the same SIMD sits between it and the next one -- one tile 67 - 81 cycles a column, two 121,
+// four 230, the packed form (four waves a SIMD) 258: vector arithmetic does not run under a wave's f32 matrix instructions, and
+// every switch between the two costs a drain.  The four-tile chain therefore (a) does the vector work of four columns in one
+// burst and issues their sixteen matrix instructions back to back, and (b) fetches a stage's x slice with one 16-byte load per
+// lane through a wave-private LDS tile instead of sixteen 4-byte loads (WIDE below).  Alone 58.2 -> 45.7 - 49.2 us a layer (two boxes).
 // LEAN: the same body in at most 128 registers a lane, so that FOUR of its workgroups share a CU (four waves per SIMD, their
 // chains interleaved on the matrix pipe: 4 x 32 cycles per column where one wave alone takes 67).  With batches in flight the
 // relation-graph layers of one batch run on the 64 CUs the other batches' entity layers leave: 240 workgroups at three a CU
@@ -110,10 +120,15 @@ __device__ __forceinline__ void dense_order_layer_impl(const DenseOrderParams &p
     const bool quartet_live = rt_raw * TILES < p.n_rt16;
     const int rt = quartet_live ? rt_raw : (p.n_rt16 - 1) / TILES;
     const float *xo = p.x + (long long)outer * p.x_so;
+    constexpr bool WIDE = TILES >= 4 && !ULTRA_DOL_ASM;      // the B operands come through a wave-private LDS tile (see fetch)
+    __shared__ __attribute__((aligned(16))) float xs_lds_all[WIDE ? 4 * 256 : 4];
     const int row0 = rt * 16 * TILES;
     const int c0 = 16 * wave;
-    // (a second tile past the graph: reads the last tile's adjacency, its rows are never stored)
-    const bool tile1 = TILES > 1 && TILES * rt + 1 < p.n_rt16;
+    // (a tile past the graph -- the last workgroup of a sample holds 1 .. TILES live ones -- is pointed at the last tile's adjacency,
+    // chains zeros, clamps its row indices in phases 2 / 3 and stores nothing)
+    bool tile_live[TILES];
+#pragma unroll
+    for (int t = 0; t < TILES; ++t) tile_live[t] = quartet_live && TILES * rt + t < p.n_rt16;
 
     // ---- phase 1 operands: all requested before anything waits ----
     // One wave per SIMD: whatever the wave does between two matrix instructions of the chain stalls the chain.  The fetch
@@ -138,12 +153,24 @@ __device__ __forceinline__ void dense_order_layer_impl(const DenseOrderParams &p
     struct Stage {
         uint4 a[TILES];
         float x[16];
+        float4 xw;      // (WIDE: the stage's slice of x as loaded; x[] is filled from it through LDS one stage ahead of its chain)
     };
+    // WIDE: a stage's 16 x 16 slice of x (16 source rows, this wave's 16 features) is ONE 16-byte load per lane -- lane l takes
+    // row l / 4, features 4 (l % 4) .. + 3 -- instead of sixteen 4-byte loads; it reaches the B-operand layout (lane (kk, n) holds
+    // x[row q][c0 + n], q = 0 .. 15) through a 1 KB LDS tile of the wave's own: written and read by the same wave, in order, so
+    // no barrier.  A vector-memory instruction costs the chain ~20 cycles of issue, an LDS read between matrix instructions ~3.
+    float *xs_lds = xs_lds_all + (WIDE ? wave * 256 : 0);
+    const uint32_t wide_lane_bytes = (uint32_t)(c0 + 4 * (lane & 3)) * 4u;
     const auto fetch = [&](const int jc, Stage &st) {
         const bool last = jc >= p.n_jc - 1;                                   // uniform
         const int jcc = last ? p.n_jc - 1 : jc;
 #pragma unroll
         for (int t = 0; t < TILES; ++t) st.a[t] = ap[t][(size_t)jcc * 64 + lane];
+        if (WIDE) {
+            const uint32_t row = (uint32_t)min(16 * jcc + (lane >> 2), p.n_in - 1);      // (rows past the graph: their adjacency is 0)
+            st.xw = *reinterpret_cast<const float4 *>(xbase + row * x_row_bytes + wide_lane_bytes);
+            return;
+        }
         if (LEAN) {
             const char *sbase = xbase + (uint32_t)jcc * 16u * x_row_bytes;
             const uint32_t cap = last ? off_max : 0xffffffffu;
@@ -161,6 +188,12 @@ __device__ __forceinline__ void dense_order_layer_impl(const DenseOrderParams &p
     fetch(0, st0);
     fetch(1, st1);
     fetch(2, st2);
+    const auto transpose = [&](Stage &st) {
+        if (!WIDE) return;
+        *reinterpret_cast<float4 *>(xs_lds + 4 * lane) = st.xw;       // tile[row l / 4][4 (l % 4) ..] = byte offset 16 l
+#pragma unroll
+        for (int q = 0; q < 16; ++q) st.x[q] = xs_lds[16 * q + i16];
+    };
 #endif
     const float relv = kk < p.n_rel ? p.rel[(long long)outer * p.rel_so + (long long)kk * p.rel_sr + c0 + i16] : 0.f;
 
@@ -216,11 +249,35 @@ __device__ __forceinline__ void dense_order_layer_impl(const DenseOrderParams &p
     const auto chain = [&](const Stage &cur, const int jc) {
         // (stages past the graph chain zeros: fma(0, b, acc) = acc exactly -- rounds have no conditional exit, which
         // would be a join where the compiler stops counting outstanding loads and drains the queue)
-        const uint32_t m = jc < p.n_jc ? 0xffffffffu : 0u;
         uint32_t aw[TILES][4];
 #pragma unroll
         for (int t = 0; t < TILES; ++t) {
+            const uint32_t m = (jc < p.n_jc && (TILES == 1 || tile_live[t])) ? 0xffffffffu : 0u;
             aw[t][0] = cur.a[t].x & m, aw[t][1] = cur.a[t].y & m, aw[t][2] = cur.a[t].z & m, aw[t][3] = cur.a[t].w & m;
+        }
+        if (TILES >= 4) {
+            // Vector instructions do not run under this wave's f32 matrix instructions: a conversion between two of them waits for
+            // the first to drain (40 cycles, not 32) and the second waits for the conversion -- 57 cycles per matrix instruction
+            // measured with the two interleaved, as the compiler schedules them.  So the vector work of DOL_GROUP columns (their
+            // products and TILES conversions each) is done in one burst and their TILES * DOL_GROUP matrix instructions issue back
+            // to back; the fences keep the scheduler from interleaving them again.  Same operations on the data: same bits.
+#pragma unroll
+            for (int q0 = 0; q0 < 16; q0 += DOL_GROUP) {
+                float b[DOL_GROUP], af[DOL_GROUP][TILES];
+#pragma unroll
+                for (int g = 0; g < DOL_GROUP; ++g) {
+                    b[g] = relv * cur.x[q0 + g];
+#pragma unroll
+                    for (int t = 0; t < TILES; ++t) af[g][t] = byte_of(aw[t][(q0 + g) >> 2], (q0 + g) & 3);
+                }
+                __builtin_amdgcn_sched_barrier(DOL_FENCE);
+#pragma unroll
+                for (int g = 0; g < DOL_GROUP; ++g)
+#pragma unroll
+                    for (int t = 0; t < TILES; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[g][t], b[g], acc[t], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(DOL_FENCE);
+            }
+            return;
         }
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
@@ -230,11 +287,15 @@ __device__ __forceinline__ void dense_order_layer_impl(const DenseOrderParams &p
                 acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(byte_of(aw[t][q >> 2], q & 3), b, acc[t], 0, 0, 0);
         }
     };
+    transpose(st0);
     for (int jc = 0; jc < p.n_jc; jc += 3) {
+        transpose(st1);
         chain(st0, jc);
         fetch(jc + 3, st0);
+        transpose(st2);
         chain(st1, jc + 1);
         fetch(jc + 4, st1);
+        transpose(st0);
         chain(st2, jc + 2);
         fetch(jc + 5, st2);
     }
@@ -284,14 +345,19 @@ __device__ __forceinline__ void dense_order_layer_impl(const DenseOrderParams &p
 #pragma unroll
             for (int r = 0; r < 4; ++r) agg_lds[(16 * t + i16) * DOL_ROW_STRIDE + f0 + r] = y[t][r];
         __syncthreads();
-        if (tid < 128 * TILES) {
-            const int row = tid >> 3, i = tid & 7;
-            float xv[8];
+        // (8 threads a row: the quartet's 256 threads cover 32 rows a pass -- four tiles take two)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) xv[j] = agg_lds[row * DOL_ROW_STRIDE + 8 * j + i];
-            const Moments w = welford8(xv);
-            ln_mom[row][i][0] = w.m1;
-            ln_mom[row][i][1] = w.m2;
+        for (int base = 0; base < 128 * TILES; base += 256) {
+            const int slot = base + tid;
+            if (slot < 128 * TILES) {
+                const int row = slot >> 3, i = slot & 7;
+                float xv[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) xv[j] = agg_lds[row * DOL_ROW_STRIDE + 8 * j + i];
+                const Moments w = welford8(xv);
+                ln_mom[row][i][0] = w.m1;
+                ln_mom[row][i][1] = w.m2;
+            }
         }
         __syncthreads();
         if (tid < 16 * TILES) {
@@ -322,7 +388,7 @@ __device__ __forceinline__ void dense_order_layer_impl(const DenseOrderParams &p
             for (int r = 0; r < 4; ++r) y[t][r] += x_lds[(16 * t + i16) * DOL_ROW_STRIDE + f0 + r];
         }
         const int row = row0 + 16 * t + i16;
-        if (row < p.n_out && (t == 0 || tile1) && quartet_live)
+        if (row < p.n_out && tile_live[t])
             *reinterpret_cast<float4 *>(p.out + (long long)outer * p.out_so + (long long)row * p.out_sr + f0) =
                 make_float4(y[t][0], y[t][1], y[t][2], y[t][3]);
     }
@@ -333,6 +399,15 @@ __global__ void __launch_bounds__(256) ULTRA_DOL_ATTR dense_order_layer_kernel(c
     dense_order_layer_impl<TILES, false>(p);
 }
 
+// Four tiles: one wave per SIMD by design, so the wave may take more than 256 registers (nothing of phases 2 / 3 is spilled around
+// the chain)
+#if !ULTRA_DOL_ASM
+template <>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) dense_order_layer_kernel<4>(const DenseOrderParams p) {
+    dense_order_layer_impl<4, false>(p);
+}
+#endif
+
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) dense_order_layer_lean_kernel(const DenseOrderParams p) {
     dense_order_layer_impl<1, true>(p);
 }
@@ -340,6 +415,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
 __global__ void __launch_bounds__(1024) dense_order_layer_packed_kernel(const DenseOrderParams p) {
     dense_order_layer_impl<1, true, 4>(p);
 }
+
+// Whether the four-tile form is the default where the launch shares the chip (see launch_dense_order_layer).
+constexpr bool DOL_SHARED_DEFAULT_TILES4 = true;
 
 static bool dol_ok16(const ultra_mat *m) {
     return (reinterpret_cast<uintptr_t>(m->ptr) & 15u) == 0 && m->stride_row % 4 == 0 && m->stride_outer % 4 == 0;
@@ -386,20 +464,42 @@ int launch_dense_order_layer(ultra_plan *p, const ultra_mat *rel, const ultra_ma
     dp.has_bnd = bnd ? 1 : 0;
     dp.flags = flags;
     dp.eps = eps;
-    const char *tiles_str = std::getenv("ULTRA_DOL_TILES");      // (read per launch: the test toggles it)
+    // Which form runs (all give the same bits: tests/test_order_gpu.py, tests/test_dense_tiles4_gpu.py):
+    //   form 0   dense_order_layer_kernel<1>: one tile per 256-thread workgroup, 162 registers, the operands of phases 2 / 3 requested
+    //            before the chain.  The shortest launch where it owns the chip (one batch in flight, training): 240 workgroups at
+    //            474 nodes x 8 samples, one chain per SIMD at 67 cycles a column.
+    //   two      dense_order_layer_kernel<2> (ULTRA_DOL_TILES=2): two chains per wave over one operand stream.  Opt-in.
+    //   lean     ULTRA_DOL_LEAN=1: form 0 in 128 registers, four workgroups a CU.
+    //   packed   ULTRA_DOL_LEAN=2: one 1024-thread workgroup of four lean quartets, four row tiles of one sample.  Its four waves
+    //            per SIMD each issue the same x loads and the same products rel * x[column]; their vector work queues on the issue
+    //            port behind each other's matrix instructions: ~250 cycles a column per SIMD as timed with batches in flight.
+    //   four     dense_order_layer_kernel<4> (ULTRA_DOL_TILES=4): the packed form's footprint -- one workgroup per four row tiles of
+    //            a sample, one CU's matrix pipes -- as ONE wave per SIMD that feeds four independent chains back to back and issues
+    //            the shared loads and products once per column instead of four times.  Needs n_rt16 >= 4; a smaller graph falls
+    //            back to one tile per workgroup.  hipcc for gfx950: 175 + 16 accumulator registers, no scratch, 59,904 B of LDS
+    //            (39,424 of tiles and LayerNorm scratch, 4,096 of the waves' x tiles, 16,384 where the compiler keeps the
+    //            operands of phases 2 / 3 over the chain).  45.7 - 49.2 us a layer alone (two boxes) against the packed form's 58.2 on
+    //            both, 48 - 50 against 59 - 61 as timed with three batches in flight (profiles/dol_tiles4_*.txt).
+    // With batches in flight the step is bound by CU-time (the relation-graph layers of one batch run on the CUs the other batches'
+    // entity layers leave), so what counts there is workgroups x duration, not the latency of one launch: the default where the
+    // launch shares the chip is DOL_SHARED_DEFAULT_TILES4 ? four : packed (four: the step 0.540 ms against 0.561 - 0.565, same file set).  ULTRA_DOL_TILES / ULTRA_DOL_LEAN (read per launch: the
+    // tests toggle them) override it; measurement builds with the assembly chain stay one-tile.
+    const char *tiles_str = std::getenv("ULTRA_DOL_TILES");
     const int tiles_env = tiles_str ? std::atoi(tiles_str) : 0;
-    // Measured (round 5, tools/dense_order_probe.py and tools/step_probe.py on one box): the two-tile form runs 32.2 us per layer
-    // against 23.7 stand-alone -- its two chains share one matrix pipe, 64 cycles a column -- and the step with two batches in
-    // flight 0.603 ms against 0.581: the relation-graph layers on the 64 free CUs are not what bounds that step.  So one tile
-    // per workgroup stays the choice everywhere; ULTRA_DOL_TILES=2 selects the other form (same bits: tests/test_order_gpu.py).
-    // ULTRA_DOL_LEAN=0 / 1 overrides the choice of the four-workgroups-a-CU form (default: where the launch shares the chip).
     const char *lean_str = std::getenv("ULTRA_DOL_LEAN");
-    // 0: the 160-register form; 1: four 256-thread workgroups a CU; 2 (default where the launch shares the chip): ONE 1024-thread
-    // workgroup of four quartets -- the packing by construction
-    const int lean = (ULTRA_DOL_ASM || tiles_env == 2) ? 0 : (lean_str ? std::atoi(lean_str) : (shared_chip ? 2 : 0));
-    const int tiles = (ULTRA_DOL_ASM || dp.n_rt16 < 2) ? 1 : (tiles_env == 2 ? 2 : 1);
+    int tiles = 1;
+    if (!ULTRA_DOL_ASM) {
+        if (tiles_env == 4 && dp.n_rt16 >= 4) tiles = 4;
+        else if (tiles_env == 2 && dp.n_rt16 >= 2) tiles = 2;
+        else if (DOL_SHARED_DEFAULT_TILES4 && !tiles_str && !lean_str && shared_chip && dp.n_rt16 >= 4) tiles = 4;
+    }
+    const int lean = (ULTRA_DOL_ASM || tiles > 1 || tiles_env == 2) ? 0 : (lean_str ? std::atoi(lean_str) : (shared_chip ? 2 : 0));
     const long long blocks = (long long)((dp.n_rt16 + tiles - 1) / tiles) * out->n_outer;
-    if (tiles == 2) {
+    if (tiles == 4) {
+#if !ULTRA_DOL_ASM
+        hipLaunchKernelGGL(dense_order_layer_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, stream, dp);
+#endif
+    } else if (tiles == 2) {
 #if !ULTRA_DOL_ASM
         hipLaunchKernelGGL(dense_order_layer_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, stream, dp);
 #endif
