@@ -360,6 +360,39 @@ int32_t ultra_answer_ranking(const void *pred, const uint8_t *keep, const int64_
                              const int64_t *hard_ptr, const int64_t *num_easy, const int64_t *ws_off, void *ws, int64_t batch,
                              int64_t num_node, int64_t *answer_ranking, int64_t *ranking, void *stream);
 
+/* ---- the symbolic traversal of a CHANGING graph (csrc/traversal_edit_kernels.hip) ----
+ * Added and retracted facts (rspmm.GraphDelta) in the TRAVERSAL's direction: the traversal writes t[b, v] for v = edge_index[1],
+ * so the edits are keyed by the tail they point into.  Prepared at add() / remove() time into arrays of fixed address:
+ *   row_dev       int32 [capacity_rows]      the distinct tails an added OR a removed edge points into, ascending
+ *   count_dev     int32 [1]                  the live number of touched tails, read ON THE DEVICE
+ *   add_ptr_dev   int32 [capacity_rows + 1]  added edges [ptr[k], ptr[k + 1]) point into row_dev[k]
+ *   add_src_dev / add_type_dev   int32 [capacity_edges]  their (source, relation), sorted by (relation, source) within a tail
+ *   dead_ptr_dev  int32 [capacity_rows + 1]  dead keys [ptr[k], ptr[k + 1]) belong to row_dev[k]; NULL: no tombstones at all
+ *   dead_src_dev / dead_type_dev int32 [capacity_keys]   the DISTINCT dead (source, relation) keys, sorted by (relation, source)
+ *                                            within a tail: EVERY base edge source -> tail of that relation is absent
+ * ultra_symbolic_traversal_edit_rows is called on the output of ultra_symbolic_traversal (same CSR of the BASE graph, r_index,
+ * h).  It OVERWRITES t[b, v] for the touched tails v, and nothing else, with
+ *   max(0, max{h[b, u] : live base edge u -> v of type r_index[b]}, max{h[b, u] : added edge u -> v of type r_index[b]})
+ * -- ultra_symbolic_traversal on the materialised graph, the same bits (a max has no order).  Tombstones never apply to the added
+ * edges.  One wave per (touched tail, sample): the relation's base segment by the base kernel's two binary searches, scanned 64
+ * slots a trip and combined by lane shuffles; the relation's dead keys are one sorted range, found by binary search, in which
+ * every lane binary-searches its edge's source.  The grid is sized by (capacity_rows, batch) and a wave at or beyond *count_dev
+ * ends at once: a launch recorded into a hipGraph serves every later content of the arrays.  No atomics, no allocation, no memset,
+ * no host synchronisation.  fp32 (dtype 0) / fp64 (1).  A key is only compared, never used as an index; a touched tail outside
+ * [0, num_node) is not written; a source outside [0, num_node) is left out, never dereferenced; ptr values are clamped to their
+ * capacity.  A NULL operand, a dtype other than 0 / 1, negative capacities, batch outside [0, 65535] or num_node outside
+ * (0, 2^31): ULTRA_ERR_INVALID, decided before any GPU call.  capacity_rows == 0 or batch == 0: ULTRA_OK, nothing launched.
+ */
+typedef struct {
+    const int32_t *row_dev, *count_dev;
+    const int32_t *add_ptr_dev, *add_src_dev, *add_type_dev;
+    const int32_t *dead_ptr_dev, *dead_src_dev, *dead_type_dev;
+    int64_t capacity_rows, capacity_edges, capacity_keys;
+} ultra_traversal_edits;
+int32_t ultra_symbolic_traversal_edit_rows(const int64_t *row_ptr, const int32_t *csr_src, const int32_t *csr_type,
+                                           int64_t num_node, const ultra_traversal_edits *edits, const int64_t *r_index,
+                                           int64_t batch, int32_t dtype, const void *h, void *t, void *stream);
+
 /* ---- training UltraQuery ----
  * ultra_symbolic_traversal_keep: ultra_symbolic_traversal on the graph without its dropped edges; keep_slot (num_edge) fp32 in
  *   the CSR's slot order, 0 = absent.

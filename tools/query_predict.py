@@ -1,7 +1,7 @@
 """Answer one complex logical query on a dataset of triple files: the k entities the model predicts, with their scores.
 
     python tools/query_predict.py --data-root DIR [--ckpt FILE] --query "(('e1', ('r1',)), ('e2', ('r2', -2)))" [-k 10]
-                                  [--logic product] [--unfiltered] [--above P]
+                                  [--logic product] [--unfiltered] [--above P] [--add-fact H R T]... [--remove-fact H R T]...
 
 DIR holds train.txt / valid.txt / test.txt (`head relation tail` per line) and optionally entities.dict / relations.dict
 (ultra_amd.data.load_triples_dir).  The query is a BetaE nested tuple (ultra_amd.ultraquery.Query.from_nested): a pair
@@ -12,6 +12,12 @@ vocabularies or integer ids.  Answers the graph already entails (the symbolic tr
 (0 < P < 1: a logit above log(P / (1 - P)), QueryPredictor.answer_sets), ranked, and the predicted size of the set, which
 counts the entailed answers too.  --ckpt: an UltraQuery checkpoint (a state dict, or a dict with the state under "model"); without it the
 weights are randomly initialised, and the tool says so.
+
+--add-fact H R T (repeatable) states a fact between known entities before the query is answered (QueryPredictor.add_facts): the
+query's projections traverse it and the answers it entails are left out.  --remove-fact H R T (repeatable) retracts one
+(QueryPredictor.remove_facts): every edge that states it leaves the graph, so it is no longer traversed and its tail can be
+predicted again.  Both kinds are applied in command-line order; H, R and T are names of the vocabularies or integer ids, R a
+relation of the dataset (not an inverse).
 """
 import argparse
 import ast
@@ -39,6 +45,19 @@ def resolve(nested, ent, rel):
     return tuple(branch if branch == (-1,) else resolve(branch, ent, rel) for branch in nested)
 
 
+def lookup_fact(fact, ent, rel):
+    """(h, r, t) ids of an --add-fact / --remove-fact option: names of the vocabularies, or integer ids."""
+    out = []
+    for name, vocab, what in zip(fact, (ent, rel, ent), ("entity", "relation", "entity")):
+        if name in vocab:
+            out.append(vocab.index(name))
+        elif name.lstrip("-").isdigit():
+            out.append(int(name))
+        else:
+            sys.exit("unknown %s %r" % (what, name))
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--data-root", required=True)
@@ -48,6 +67,16 @@ def main(argv=None):
     ap.add_argument("--logic", default="product", choices=["product", "godel", "lukasiewicz"])
     ap.add_argument("--unfiltered", action="store_true")
     ap.add_argument("--above", type=float, metavar="P", help="print the whole answer set: every entity with probability above P")
+    class Edit(argparse.Action):       # (one list for both kinds: they are applied in command-line order)
+        def __call__(self, parser, namespace, values, option_string=None):
+            namespace.edits = getattr(namespace, "edits", None) or []
+            namespace.edits.append((option_string == "--add-fact", tuple(values)))
+
+    ap.add_argument("--add-fact", nargs=3, action=Edit, metavar=("H", "R", "T"),
+                    help="state the fact (H, R, T) before the query; repeatable")
+    ap.add_argument("--remove-fact", nargs=3, action=Edit, metavar=("H", "R", "T"),
+                    help="retract the fact (H, R, T) before the query; repeatable, applied in order with --add-fact")
+    ap.set_defaults(edits=[])
     args = ap.parse_args(argv)
     if args.above is not None and not 0.0 < args.above < 1.0:
         sys.exit("--above takes a probability strictly between 0 and 1, got %r" % args.above)
@@ -57,6 +86,7 @@ def main(argv=None):
     from ultra_amd import models, query_predict, synthetic, ultraquery
     ent, rel = udata.read_vocab(args.data_root)
     nested = resolve(ast.literal_eval(args.query), ent, rel)
+    edits = [(add, lookup_fact(fact, ent, rel)) for add, fact in args.edits]
     dev = torch.device("cuda:0")
     data = udata.load_triples_dir(args.data_root).to(dev)
     cfg = synthetic.default_model_cfg()
@@ -69,6 +99,22 @@ def main(argv=None):
         print("no --ckpt: randomly initialised weights, the answers mean nothing")
     model = model.to(dev).eval()
     qp = query_predict.QueryPredictor(model, data, k=args.k, batch_size=1, filtered=not args.unfiltered)
+    at = 0
+    while at < len(edits):        # (runs of one kind go in one call)
+        end = at
+        while end < len(edits) and edits[end][0] == edits[at][0]:
+            end += 1
+        ids = [list(column) for column in zip(*(fact for _, fact in edits[at:end]))]
+        try:
+            if edits[at][0]:
+                held = qp.add_facts(*ids)
+                print("%d fact(s) stated on top of the dataset%s" % (end - at, "" if held else " (folded into the graph)"))
+            else:
+                took = qp.remove_facts(*ids).tolist()
+                print("%d fact(s) retracted from the dataset: %s edge(s) removed" % (end - at, " + ".join(str(n) for n in took)))
+        except ValueError as exc:
+            sys.exit(str(exc))
+        at = end
     print(ultraquery.Query.from_nested(nested).to_readable())
     if args.above is not None:
         ptr, ids, scores, size = qp.answer_sets([nested], probability=args.above)

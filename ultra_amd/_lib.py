@@ -62,6 +62,15 @@ class UltraTombstones(ctypes.Structure):
                 ("capacity_keys", ctypes.c_int64)]
 
 
+class UltraTraversalEdits(ctypes.Structure):
+    """ultra_traversal_edits: a graph delta in the symbolic traversal's direction (include/ultra_nbfnet.h,
+    ultra_symbolic_traversal_edit_rows)."""
+    _fields_ = [("row_dev", ctypes.c_void_p), ("count_dev", ctypes.c_void_p), ("add_ptr_dev", ctypes.c_void_p),
+                ("add_src_dev", ctypes.c_void_p), ("add_type_dev", ctypes.c_void_p), ("dead_ptr_dev", ctypes.c_void_p),
+                ("dead_src_dev", ctypes.c_void_p), ("dead_type_dev", ctypes.c_void_p), ("capacity_rows", ctypes.c_int64),
+                ("capacity_edges", ctypes.c_int64), ("capacity_keys", ctypes.c_int64)]
+
+
 class PlanOpts(ctypes.Structure):
     _fields_ = [("seg_len", ctypes.c_int32), ("g_max", ctypes.c_int32), ("flags", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)]
@@ -158,6 +167,8 @@ def _load():
     lib.ultra_beam_search_layer.argtypes =[vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, i64, i32, vp, vp, vp]
     lib.ultra_beam_search_layer_batch.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, i32, vp, vp, vp]
     lib.ultra_symbolic_traversal.argtypes = [vp, vp, vp, i64, vp, i64, i32, vp, vp, vp]
+    lib.ultra_symbolic_traversal_edit_rows.argtypes = [vp, vp, vp, i64, ctypes.POINTER(UltraTraversalEdits), vp, i64, i32, vp,
+                                                       vp, vp]
     lib.ultra_answer_ranking.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp]
     lib.ultra_strict_negatives.argtypes = [vp, i64, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp]
     lib.ultra_ranking_loss.argtypes = [vp, i64, i64, ctypes.c_float, ctypes.c_float, vp, vp, vp]

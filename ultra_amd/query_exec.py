@@ -22,6 +22,7 @@ and the final symbolic sets.  It does NOT keep the interpreter's `var` / `symbol
 them) and it does not populate `model.stack` / `model.symbolic_stack`.  Training stays with the interpreter: its traversal
 dropout draws per projection.
 """
+import inspect
 from collections import namedtuple
 
 import torch
@@ -301,8 +302,9 @@ class Executor(object):
         return buf[:8 * n_rel].view(torch.int64), buf[8 * n_rel:size].view(torch.int32), rel_off, seg_off
 
     @torch.no_grad()
-    def run(self, model, graph, program, symbolic_traversal=True):
-        """(prob, final symbolic set or None) of `program` through `model` (an UltraQuery in eval mode) on a CUDA graph."""
+    def run(self, model, graph, program, symbolic_traversal=True, delta=None):
+        """(prob, final symbolic set or None) of `program` through `model` (an UltraQuery in eval mode) on a CUDA graph.
+        delta (rspmm.GraphDelta of `graph`): the same on delta.materialize(graph) -- see `projections`."""
         if model.training:
             raise ValueError("the compiled executor serves eval mode only: training keeps UltraQuery.execute, whose "
                              "traversal dropout draws per projection")
@@ -320,6 +322,7 @@ class Executor(object):
             return results[0], (results[1] if symbolic else None)
         stacks, inputs = self._get(dev, batch, n, symbolic)
         rel, words, rel_off, seg_off = self._upload(dev, program)
+        project, project_symbolic = projections(model, graph, delta)
         outs = [None, None]
         last = len(program.segments) - 1
         for s in range(last + 1):
@@ -330,9 +333,9 @@ class Executor(object):
                 break
             rows = len(program.projections[s].samples)
             r_index = rel[rel_off[s]:rel_off[s] + rows]
-            outs[0] = self._output(model.model(graph, inputs[0][:rows], r_index), inputs[0], rows, n)
+            outs[0] = self._output(project(inputs[0][:rows], r_index), inputs[0], rows, n)
             if symbolic:
-                outs[1] = self._output(model.symbolic_model(graph, inputs[1][:rows], r_index), inputs[1], rows, n)
+                outs[1] = self._output(project_symbolic(inputs[1][:rows], r_index), inputs[1], rows, n)
         return results[0], (results[1] if symbolic else None)
 
     @staticmethod
@@ -355,23 +358,50 @@ def _on_gpu(model, graph):
     return edge_index is not None and edge_index.is_cuda and (param is None or param.is_cuda)
 
 
-def execute(model, graph, query_or_program, symbolic_traversal=True, executor=None):
+def _takes_delta(module):
+    try:
+        return "delta" in inspect.signature(getattr(module, "forward", module)).parameters
+    except (TypeError, ValueError):
+        return False
+
+
+def projections(model, graph, delta=None):
+    """The two projection calls (h_prob, r_index) -> set of a run: model.model and model.symbolic_model on `graph`.  Without a
+    delta, or with one that holds no edit, exactly `projection(graph, h_prob, r_index)`.  With an edited delta
+    `projection(graph, h_prob, r_index, delta=delta)` -- the cached plan and CSR of `graph` with the touched rows fixed; a
+    projection whose forward keeps the reference's three arguments offers `forward_delta(graph, h_prob, r_index, delta)`
+    instead (RelationProjection) --, and `projection(delta.materialize(graph), h_prob, r_index)` on a CPU graph or where a
+    projection offers neither."""
+    def call(projection):
+        if delta is None or not delta.edited:
+            return lambda h, r: projection(graph, h, r)
+        if graph.edge_index.is_cuda and _takes_delta(projection):
+            return lambda h, r: projection(graph, h, r, delta=delta)
+        if graph.edge_index.is_cuda and hasattr(projection, "forward_delta"):
+            return lambda h, r: projection.forward_delta(graph, h, r, delta)
+        return lambda h, r: projection(delta.materialize(graph), h, r)
+    return call(model.model), call(model.symbolic_model)
+
+
+def execute(model, graph, query_or_program, symbolic_traversal=True, executor=None, delta=None):
     """(logits (batch, num_nodes), final symbolic sets or None): `UltraQuery.forward` and the top of its symbolic stack,
-    through the compiled program.  A CPU graph or model runs `run_reference` on the model's own projections."""
+    through the compiled program.  A CPU graph or model runs `run_reference` on the model's own projections.  delta
+    (rspmm.GraphDelta of `graph`): the same on delta.materialize(graph) (`projections`)."""
     program = _as_program(query_or_program, graph)
     if model.training:
         raise ValueError("the compiled executor serves eval mode only: training keeps UltraQuery.execute, whose traversal "
                          "dropout draws per projection")
     if _on_gpu(model, graph):
-        prob, sym = (executor or _EXECUTOR).run(model, graph, program, symbolic_traversal)
+        prob, sym = (executor or _EXECUTOR).run(model, graph, program, symbolic_traversal, delta=delta)
     else:
+        project, project_symbolic = projections(model, graph, delta)
         with torch.no_grad():
-            prob, sym = run_reference(program, model.logic, lambda h, r: model.model(graph, h, r),
-                                      (lambda h, r: model.symbolic_model(graph, h, r)) if symbolic_traversal else None,
+            prob, sym = run_reference(program, model.logic, project, project_symbolic if symbolic_traversal else None,
                                       device=graph.edge_index.device)
     return logit(prob), sym
 
 
-def forward(model, graph, query_or_program, symbolic_traversal=True):
-    """`UltraQuery.forward(graph, query, symbolic_traversal)` through the compiled program: the same logits, bit for bit."""
-    return execute(model, graph, query_or_program, symbolic_traversal)[0]
+def forward(model, graph, query_or_program, symbolic_traversal=True, delta=None):
+    """`UltraQuery.forward(graph, query, symbolic_traversal)` through the compiled program: the same logits, bit for bit.
+    delta: as in `execute`."""
+    return execute(model, graph, query_or_program, symbolic_traversal, delta=delta)[0]

@@ -10,18 +10,26 @@ their programs (`Program.signature()`), in input order within a group, and every
 selected by ultra_filtered_topk on the logits.  With filtered=True the entities whose final symbolic set is non-zero -- the
 answers the graph already entails, from the symbolic traversal of the same run -- are left out: ultra_nonzero_lists turns the
 sets into the kernel's lists on the device.  Order, count and padding are those of predict.filtered_topk.
+
+A CHANGING graph: `add_facts` / `remove_facts` hold the edits in an rspmm.GraphDelta beside the served graph --
+no new relation-graph plan, host plan or traversal CSR -- and every answer equals a fresh QueryPredictor's on `materialized()`.
 """
+import copy
+
 import torch
 
-from . import predict, query_exec
+from . import predict, query_exec, rspmm, tasks
 from .ultraquery import Query, _logic
 
 
 class QueryPredictor(object):
-    """model: an `UltraQuery`; graph: the graph to answer on; logic: overrides model.logic for the calls of this predictor."""
+    """model: an `UltraQuery`; graph: the graph to answer on; logic: overrides model.logic for the calls of this predictor;
+    delta_capacity: the edits (added facts + retracted facts) held beside the served graph before they are folded into it."""
 
-    def __init__(self, model, graph, k=10, batch_size=16, filtered=True, logic=None):
+    def __init__(self, model, graph, k=10, batch_size=16, filtered=True, logic=None, delta_capacity=256):
         predict._check_k(k)
+        if isinstance(delta_capacity, bool) or not isinstance(delta_capacity, int) or delta_capacity < 1:
+            raise ValueError("delta_capacity must be a positive int (facts), got %r" % (delta_capacity,))
         if int(batch_size) < 1:
             raise ValueError("batch_size must be positive, got %r" % (batch_size,))
         if logic is not None:
@@ -29,6 +37,86 @@ class QueryPredictor(object):
         self.model, self.graph, self.k, self.batch_size = model, graph, k, int(batch_size)
         self.filtered, self.logic = bool(filtered), logic
         self._executor = query_exec.Executor()
+        self.delta_capacity = delta_capacity
+        self.delta = None       # made at the first edit: a predictor that was never edited runs exactly what it ran before
+
+    # ---- the live graph (the rules of Predictor.add_facts / remove_facts; there is no separate filter graph: the entailed
+    # answers come from the symbolic traversal of the same run) ----
+    def _new_delta(self, capacity=None):
+        return rspmm.GraphDelta(self.graph, self.delta_capacity if capacity is None else capacity)
+
+    def _fits(self, n):
+        held = 0 if self.delta is None else 2 * len(self.delta) + self.delta.num_removed
+        return held + 2 * n <= 2 * self.delta_capacity
+
+    def add_facts(self, h, r, t):
+        """State the facts (h[i], r[i], t[i]) -- ints or vectors; r direct relations, h and t existing entities (ValueError
+        otherwise).  Each adds the edges (h, t, r) and (t, h, r + num_relations / 2) to the served graph: the projections
+        traverse them and the symbolic side entails through them from the next call on.  Returns the number of facts the
+        delta holds afterwards (0 after a compaction: more edits than delta_capacity)."""
+        probe = self.delta if self.delta is not None else self._new_delta(1)
+        h, r, t = probe.check(h, r, t)
+        if len(h) == 0:
+            return 0 if self.delta is None else len(self.delta)
+        if not self._fits(len(h)):
+            self.compact(extra=(h, r, t))
+            return 0
+        if self.delta is None:
+            self.delta = self._new_delta()
+        self.delta.add(h, r, t)
+        return len(self.delta)
+
+    def remove_facts(self, h, r, t):
+        """Retract the facts (h[i], r[i], t[i]) -- the argument rules of add_facts -- one after the other: every edge equal to
+        (h, t, r) or (t, h, r + num_relations / 2) leaves the served graph (a fact stated nowhere is a no-op).  Returns an
+        int64 vector: the number of direct edges each fact took out (GraphDelta.remove).  A call that may not fit compacts
+        first; one larger than the whole capacity is applied to a delta of its own and folded at once."""
+        probe = self.delta if self.delta is not None else self._new_delta(1)
+        h, r, t = probe.check(h, r, t)
+        if len(h) == 0:
+            return torch.zeros(0, dtype=torch.long, device=h.device)
+        if not self._fits(len(h)):
+            self.compact()
+        if self._fits(len(h)):
+            if self.delta is None:
+                self.delta = self._new_delta()
+            return self.delta.remove(h, r, t)
+        fold = self._new_delta(len(h))
+        removed = fold.remove(h, r, t)
+        self.compact(delta=fold)
+        return removed
+
+    def compact(self, extra=None, delta=None):
+        """Fold the delta's edits (and `extra` = (h, r, t), checked by the caller) into the served graph: the materialised graph
+        -- its relation graph rebuilt; a host plan and a traversal CSR on the next query -- becomes `graph`, and the delta is
+        emptied.  `delta`: fold that one instead of the predictor's own."""
+        delta = self.delta if delta is None else delta
+        facts = [] if delta is None else [delta.facts[:len(delta)]]
+        if extra is not None:
+            facts.append(torch.stack(list(extra), dim=1))
+        facts = torch.cat(facts) if facts else torch.zeros(0, 3, dtype=torch.long)
+        if len(facts) == 0 and not (delta is not None and delta.num_removed):
+            return
+        fh, fr, ft = facts.unbind(1)
+        base = self.graph
+        if delta is not None and delta.num_removed:
+            base = copy.copy(self.graph)
+            base.edge_index, base.edge_type = delta.surviving(self.graph.edge_index, self.graph.edge_type)
+        graph = predict._with_facts(base, fh, fr, ft)
+        if getattr(self.graph, "relation_graph", None) is not None:
+            tasks.build_relation_graph(graph)
+        self.graph = graph
+        self.delta = None
+
+    def materialized(self):
+        """The graph a fresh QueryPredictor would be given for the same answers: the served edge list with the delta's edits and
+        the delta's relation graph (GraphDelta.materialize); the served graph itself where no edit is held."""
+        if self.delta is None or not self.delta.edited:
+            return self.graph
+        return self.delta.materialize(self.graph)
+
+    def _delta_kwargs(self):
+        return {"delta": self.delta} if self.delta is not None and self.delta.edited else {}
 
     def _rows(self, queries):
         """One postfix row (a list ending with stop) per query."""
@@ -75,7 +163,7 @@ class QueryPredictor(object):
         try:
             for index, program in plan:
                 logits, sym = query_exec.execute(self.model, self.graph, program, symbolic_traversal=self.filtered,
-                                                 executor=self._executor)
+                                                 executor=self._executor, **self._delta_kwargs())
                 ptr = known = None
                 if logits.is_cuda:
                     if self.filtered:
@@ -117,7 +205,7 @@ class QueryPredictor(object):
         try:
             for index, program in plan:
                 logits, sym = query_exec.execute(self.model, self.graph, program, symbolic_traversal=self.filtered,
-                                                 executor=self._executor)
+                                                 executor=self._executor, **self._delta_kwargs())
                 ptr = known = None
                 if logits.is_cuda:
                     if self.filtered:

@@ -670,6 +670,9 @@ class Plan(object):
         return ms.value, op.out
 
 
+TraversalLayout = namedtuple("TraversalLayout", "rows count add_ptr add_src add_type dead_ptr dead_src dead_type")
+
+
 class GraphDelta(object):
     """Facts added to and retracted from a served graph, held beside the cached plan of the base graph instead of rebuilding it
     (DESIGN.md 17, 18).
@@ -697,6 +700,8 @@ class GraphDelta(object):
                                           bincount)
     relation_graph: tasks.build_relation_graph of the materialised list, rebuilt at add() / remove(); the previous object is kept
     when the new adjacency equals the old one (the common case), so its plan and the captures that pin it stay valid.
+    `traversal`: a second layout of the same edits keyed by the tail, for the symbolic traversal -- None until
+    traversal_operand() is first called (a Predictor never asks), then refreshed with the arrays above (_prepare_traversal).
 
     A GROWING graph: `data` may hold reserved rows -- num_nodes counts SLOTS, of which the ids below `num_live`
     are entities in use.  num_nodes stays what the plan check of Plan.delta_rows / edit_rows compares and what sizes `degree`
@@ -731,6 +736,7 @@ class GraphDelta(object):
         self._base_codes = None
         self.relation_graph = getattr(data, "relation_graph", None)
         self._materialized = None
+        self.traversal = None       # the layout in the symbolic traversal's direction: laid out when first asked for
 
     def __len__(self):
         return self.num_facts
@@ -829,7 +835,62 @@ class GraphDelta(object):
         self.version += 1
         self._materialized = None
         self._prepare()
+        if self.traversal is not None:
+            self._prepare_traversal()
         self._rebuild_relation_graph()
+
+    def _prepare_traversal(self):
+        """The edits keyed by the TAIL they point into, into buffers allocated at the first call and refreshed in
+        place by every later add() / remove().  The symbolic traversal writes t[b, v] for v = edge_index[1], the other end of
+        the plan's row.  Laid out from the facts and the tombstone codes themselves, not from the plan-direction arrays with
+        the relations mapped to their inverses: a base graph may state a fact in one direction only, and then the tombstones
+        are not symmetric.
+          rows       int32 (2 capacity)      the distinct tails an added or a removed edge points into, ascending
+          count      int32 (1)               their number -- the SAME tensor object for the delta's life
+          add_ptr    int32 (2 capacity + 1)  the added edges' ranges per touched tail
+          add_src / add_type    int32 (2 capacity)   the added edges (source, relation), sorted by (tail, relation, source)
+          dead_ptr   int32 (2 capacity + 1)  the dead keys' ranges per touched tail
+          dead_src / dead_type  int32 (2 capacity)   the distinct dead keys (source, relation), sorted alike: every base edge
+                                             source -> tail of that relation is absent; never an added edge"""
+        dev, cap = self.device, 2 * self.capacity
+        if self.traversal is None:
+            buf = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
+            self.traversal = TraversalLayout(rows=buf(cap), count=buf(1), add_ptr=buf(cap + 1), add_src=buf(cap),
+                                             add_type=buf(cap), dead_ptr=buf(cap + 1), dead_src=buf(cap), dead_type=buf(cap))
+        lay = self.traversal
+        edge_index, edge_type = self.edges()
+        src, dst = edge_index
+        order = torch.argsort((dst * self.num_relations + edge_type) * self.num_nodes + src)
+        src, dst, edge_type = src[order], dst[order], edge_type[order]
+        keys = torch.tensor(self.dead_keys, dtype=torch.long, device=dev)
+        key_type = keys % self.num_relations
+        key_dst = (keys // self.num_relations) % self.num_nodes
+        key_src = keys // (self.num_relations * self.num_nodes)
+        order = torch.argsort((key_dst * self.num_relations + key_type) * self.num_nodes + key_src)
+        key_src, key_dst, key_type = key_src[order], key_dst[order], key_type[order]
+        touched = torch.unique(torch.cat([dst, key_dst]))      # (ascending)
+        num_touched = len(touched)
+        lay.add_src[:len(src)] = src.to(torch.int32)
+        lay.add_type[:len(src)] = edge_type.to(torch.int32)
+        lay.dead_src[:len(keys)] = key_src.to(torch.int32)
+        lay.dead_type[:len(keys)] = key_type.to(torch.int32)
+        lay.rows[:num_touched] = touched.to(torch.int32)
+        for ptr, of in ((lay.add_ptr, dst), (lay.dead_ptr, key_dst)):
+            counts = torch.bincount(torch.searchsorted(touched, of), minlength=num_touched)
+            ptr[1:num_touched + 1] = counts.cumsum(0).to(torch.int32)
+        lay.count.fill_(num_touched)
+
+    def traversal_operand(self):
+        """The edits in the traversal's direction as the engine takes them (ultra_traversal_edits); valid while this object
+        lives.  The first call lays the buffers out; from then on add() / remove() keep them current.  The dead arrays are always
+        handed over (empty ranges where no tombstone is held): a captured launch then serves tombstones that arrive later."""
+        if self.traversal is None:
+            self._prepare_traversal()
+        lay = self.traversal
+        return _lib.UltraTraversalEdits(lay.rows.data_ptr(), lay.count.data_ptr(), lay.add_ptr.data_ptr(),
+                                        lay.add_src.data_ptr(), lay.add_type.data_ptr(), lay.dead_ptr.data_ptr(),
+                                        lay.dead_src.data_ptr(), lay.dead_type.data_ptr(), lay.rows.numel(),
+                                        lay.add_src.numel(), lay.dead_src.numel())
 
     def _prepare(self):
         """Sort the delta's edges, decode the tombstone keys, and lay out the union of their rows with both ptr arrays, into the

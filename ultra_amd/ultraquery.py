@@ -11,6 +11,7 @@ that is built once per graph and cached.  In train() mode every projection first
 query_train.traversal_dropout: keep vectors over the static graphs, read through their cached plans).  DESIGN.md section 10.
 """
 import copy
+import ctypes
 from collections import OrderedDict, namedtuple
 
 import torch
@@ -326,10 +327,28 @@ class RelationProjection(nn.Module):
         self.threshold = threshold
 
     def forward(self, graph, h_prob, r_index):
+        # (the reference's interface, ultraquery.py:245-277, pinned by tests/test_models_cpu.py: a graph delta comes in through
+        # forward_delta)
+        return self._project(graph, h_prob, r_index, None)
+
+    def forward_delta(self, graph, h_prob, r_index, delta=None):
+        """forward on a CHANGING graph (serving): the projection on delta.materialize(graph) -- the relation model
+        on the delta's relation graph (delta.live_view), the entity model on graph's cached plan with the touched rows fixed
+        (QueryNBFNet.forward(delta=), which falls back to the materialised graph by itself).  delta None or without edits:
+        forward.  ValueError in training mode or with traversal_keep / relation_keep on the graph."""
+        return self._project(graph, h_prob, r_index, delta)
+
+    def _project(self, graph, h_prob, r_index, delta):
         # (training) graph.traversal_keep / graph.relation_keep: 0/1 vectors over the edges of the entity graph and of its
         # relation graph -- the projection then runs on the graph without the zero edges (traversal dropout)
         edge_keep = getattr(graph, "traversal_keep", None)
         relation_keep = getattr(graph, "relation_keep", None)
+        if delta is not None and not delta.edited:
+            delta = None
+        if delta is not None:
+            if self.training or edge_keep is not None or relation_keep is not None:
+                raise ValueError("a graph delta serves eval mode only, without traversal_keep / relation_keep on the graph")
+            graph = delta.live_view(graph)
         bs = r_index.shape[0]
         # relation representations conditioned on the query relations, (bs, num_rel, dim)  (ultraquery.py:258)
         if relation_keep is not None:
@@ -343,7 +362,9 @@ class RelationProjection(nn.Module):
         if self.threshold > 0.0:
             prob = torch.where(h_prob <= self.threshold, torch.zeros_like(h_prob), h_prob)
         input = prob.unsqueeze(-1) * query.unsqueeze(1)                                # einsum("bn, bd -> bnd")
-        if edge_keep is not None:
+        if delta is not None:
+            output = self.model.entity_model(graph, input, rel_reprs, query, delta=delta)
+        elif edge_keep is not None:
             output = self.model.entity_model(graph, input, rel_reprs, query, edge_keep=edge_keep)
         else:
             output = self.model.entity_model(graph, input, rel_reprs, query)           # (bs, num_nodes) scores
@@ -414,9 +435,20 @@ def traversal_order(edge_index, edge_type, num_node):
     return order
 
 
-def symbolic_traversal(edge_index, edge_type, num_node, h_prob, r_index, edge_keep=None):
+def symbolic_traversal(edge_index, edge_type, num_node, h_prob, r_index, edge_keep=None, delta=None):
     """t[b, v] = max(0, max{h[b, u] : edge u -> v of type r_index[b]}) on the GPU (ultra_symbolic_traversal); with
-    edge_keep (num_edge, 0/1) over the edges whose keep is not 0 only (ultra_symbolic_traversal_keep)."""
+    edge_keep (num_edge, 0/1) over the edges whose keep is not 0 only (ultra_symbolic_traversal_keep).  delta (an edited
+    rspmm.GraphDelta whose base graph the edge list is; not with edge_keep): the traversal of delta.materialize(...) -- the base
+    launch on the cached CSR of the base graph, then one launch that recomputes the tails an added or a removed edge points
+    into (ultra_symbolic_traversal_edit_rows).  The same bits: a max has no order."""
+    if delta is not None and not delta.edited:
+        delta = None
+    if delta is not None:
+        if edge_keep is not None:
+            raise ValueError("a graph delta is not combined with edge_keep")
+        if delta.num_nodes != int(num_node) or delta.device != edge_index.device:
+            raise ValueError("the delta was made for a graph of %d nodes on %s, the traversal runs over %d nodes on %s"
+                             % (delta.num_nodes, delta.device, num_node, edge_index.device))
     if h_prob.dtype not in (torch.float32, torch.float64):
         raise TypeError("the symbolic traversal takes fp32 or fp64 fuzzy sets, got %s" % h_prob.dtype)
     if h_prob.dim() != 2 or h_prob.shape[1] != num_node or r_index.shape != (h_prob.shape[0],):
@@ -439,6 +471,11 @@ def symbolic_traversal(edge_index, edge_type, num_node, h_prob, r_index, edge_ke
     check(lib.ultra_symbolic_traversal(csr.row_ptr.data_ptr(), csr.src.data_ptr(), csr.type.data_ptr(), csr.num_node,
                                        r.data_ptr(), h.shape[0], 0 if h.dtype == torch.float32 else 1, h.data_ptr(),
                                        t.data_ptr(), stream))
+    if delta is not None:
+        edits = delta.traversal_operand()
+        check(lib.ultra_symbolic_traversal_edit_rows(csr.row_ptr.data_ptr(), csr.src.data_ptr(), csr.type.data_ptr(),
+                                                     csr.num_node, ctypes.byref(edits), r.data_ptr(), h.shape[0],
+                                                     0 if h.dtype == torch.float32 else 1, h.data_ptr(), t.data_ptr(), stream))
     return t
 
 
@@ -458,6 +495,7 @@ def symbolic_traversal_reference(edge_index, edge_type, num_node, h_prob, r_inde
 class SymbolicTraversal(nn.Module):
     """Symbolic traversal (ultraquery.py:280-298): the exact projection of a fuzzy set along one relation per sample."""
 
-    def forward(self, graph, h_prob, r_index):
+    def forward(self, graph, h_prob, r_index, delta=None):
+        """delta (rspmm.GraphDelta of `graph`, serving): the traversal of delta.materialize(graph) on graph's cached CSR."""
         return symbolic_traversal(graph.edge_index, graph.edge_type, graph.num_nodes, h_prob, r_index,
-                                  edge_keep=getattr(graph, "traversal_keep", None))
+                                  edge_keep=getattr(graph, "traversal_keep", None), delta=delta)
