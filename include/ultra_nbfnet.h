@@ -481,6 +481,17 @@ int32_t ultra_filtered_topk_live(const void *score, const int64_t *known_ptr, co
  * ptr_out[0] = 0 -- the layout ultra_filtered_topk and ultra_filtered_rank take.  counts: (batch) int64 of scratch.  Two
  * launches (counts per row; scan and fill), no atomics, no host synchronisation: the same integers on every run.
  * capacity (the ids index_out holds) < batch * n: ULTRA_ERR_INVALID, decided on the host.
+ *
+ * ultra_nonzero_lists_live: the lists over the LIVE ids of rows of n SLOTS -- the final symbolic sets of a
+ * graph served with reserved rows, whose dead slots hold 1.0 after a negation.  The arguments of ultra_nonzero_lists plus n_live,
+ * a DEVICE pointer to one int64 (the scalar the ultra_filtered_*_live entries read).  n stays the row stride of x; the launch
+ * shape, counts, ptr_out and the capacity rule (capacity >= batch * n) depend on (batch, n) alone and *n_live is read by the
+ * kernels, once per workgroup, so a call recorded into a hipGraph serves every later value.  An id >= *n_live is absent: its
+ * slot is never loaded (it may hold anything, a NaN included) and it is never counted or listed.  The value is clamped on the
+ * device to [0, n] and never used as an index.  The same two kernels serve ultra_nonzero_lists (n_live == NULL inside: every
+ * slot is live), whose results keep their bits.  No memset node is recorded: for batch == 0 a one-thread kernel writes
+ * ptr_out[0] = 0.  Errors: those of ultra_nonzero_lists, under this name; a NULL n_live is ULTRA_ERR_INVALID, decided before
+ * any GPU call.
  */
 int32_t ultra_query_segment(const int32_t *entry_depth, const int32_t *push_row, const int32_t *pop_row, const int32_t *op_ptr,
                             const int32_t *ops, int64_t batch, int64_t num_node, int32_t stack_depth, int32_t dtype,
@@ -488,6 +499,8 @@ int32_t ultra_query_segment(const int32_t *entry_depth, const int32_t *push_row,
                             int64_t pop_rows, void *sym_stack, const void *sym_push_src, void *sym_pop_dst, void *stream);
 int32_t ultra_nonzero_lists(const void *x, int64_t batch, int64_t n, int64_t *counts, int64_t *ptr_out, int64_t *index_out,
                             int64_t capacity, void *stream);
+int32_t ultra_nonzero_lists_live(const void *x, int64_t batch, int64_t n, int64_t *counts, int64_t *ptr_out,
+                                 int64_t *index_out, int64_t capacity, const int64_t *n_live, void *stream);
 
 /* ---- serving answer sets ----
  * ultra_filtered_above: per row of score (batch, n_cand) fp32 contiguous every candidate above `threshold`, ranked.  id v is a

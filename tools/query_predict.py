@@ -2,6 +2,7 @@
 
     python tools/query_predict.py --data-root DIR [--ckpt FILE] --query "(('e1', ('r1',)), ('e2', ('r2', -2)))" [-k 10]
                                   [--logic product] [--unfiltered] [--above P] [--add-fact H R T]... [--remove-fact H R T]...
+                                  [--entity-capacity M] [--add-entity NAME]...
 
 DIR holds train.txt / valid.txt / test.txt (`head relation tail` per line) and optionally entities.dict / relations.dict
 (ultra_amd.data.load_triples_dir).  The query is a BetaE nested tuple (ultra_amd.ultraquery.Query.from_nested): a pair
@@ -18,6 +19,11 @@ query's projections traverse it and the answers it entails are left out.  --remo
 (QueryPredictor.remove_facts): every edge that states it leaves the graph, so it is no longer traversed and its tail can be
 predicted again.  Both kinds are applied in command-line order; H, R and T are names of the vocabularies or integer ids, R a
 relation of the dataset (not an inverse).
+
+--add-entity NAME (repeatable) introduces an entity the dataset does not know (QueryPredictor.add_entities): it takes one of the
+rows reserved by --entity-capacity M (default: as many as there are --add-entity options), costs no plan, no relation graph and
+no traversal index, and from then on NAME is an entity like any other -- in the --add-fact / --remove-fact options that FOLLOW it
+on the command line, as an anchor of the query and in the printed answers.
 """
 import argparse
 import ast
@@ -67,17 +73,26 @@ def main(argv=None):
     ap.add_argument("--logic", default="product", choices=["product", "godel", "lukasiewicz"])
     ap.add_argument("--unfiltered", action="store_true")
     ap.add_argument("--above", type=float, metavar="P", help="print the whole answer set: every entity with probability above P")
-    class Edit(argparse.Action):       # (one list for both kinds: they are applied in command-line order)
+    class Edit(argparse.Action):       # (one list for all kinds: they are applied in command-line order)
         def __call__(self, parser, namespace, values, option_string=None):
             namespace.edits = getattr(namespace, "edits", None) or []
-            namespace.edits.append((option_string == "--add-fact", tuple(values)))
+            if option_string == "--add-entity":
+                namespace.edits.append((None, values))
+            else:
+                namespace.edits.append((option_string == "--add-fact", tuple(values)))
 
     ap.add_argument("--add-fact", nargs=3, action=Edit, metavar=("H", "R", "T"),
                     help="state the fact (H, R, T) before the query; repeatable")
     ap.add_argument("--remove-fact", nargs=3, action=Edit, metavar=("H", "R", "T"),
                     help="retract the fact (H, R, T) before the query; repeatable, applied in order with --add-fact")
+    ap.add_argument("--add-entity", action=Edit, metavar="NAME",
+                    help="introduce a new entity before the query; repeatable, applied in order with the fact options")
+    ap.add_argument("--entity-capacity", type=int, default=None, metavar="M",
+                    help="rows reserved for new entities (default: the number of --add-entity options)")
     ap.set_defaults(edits=[])
     args = ap.parse_args(argv)
+    if args.entity_capacity is not None and args.entity_capacity < 0:
+        sys.exit("--entity-capacity must not be negative")
     if args.above is not None and not 0.0 < args.above < 1.0:
         sys.exit("--above takes a probability strictly between 0 and 1, got %r" % args.above)
     if not torch.cuda.is_available():
@@ -85,8 +100,21 @@ def main(argv=None):
     from ultra_amd import data as udata
     from ultra_amd import models, query_predict, synthetic, ultraquery
     ent, rel = udata.read_vocab(args.data_root)
+    ent = list(ent)        # (grows along the command line: a name resolves in the options after its --add-entity; the ids are
+    num_known = len(ent)   # handed out in that order)
+    edits = []
+    for kind, value in args.edits:
+        if kind is None:
+            if value in ent:
+                sys.exit("--add-entity %r: the entity exists" % value)
+            ent.append(value)
+            edits.append((None, value))
+        else:
+            edits.append((kind, lookup_fact(value, ent, rel)))
+    reserve = len(ent) - num_known if args.entity_capacity is None else args.entity_capacity
+    if len(ent) > num_known and not reserve:
+        sys.exit("--add-entity needs --entity-capacity above 0")
     nested = resolve(ast.literal_eval(args.query), ent, rel)
-    edits = [(add, lookup_fact(fact, ent, rel)) for add, fact in args.edits]
     dev = torch.device("cuda:0")
     data = udata.load_triples_dir(args.data_root).to(dev)
     cfg = synthetic.default_model_cfg()
@@ -98,9 +126,15 @@ def main(argv=None):
     else:
         print("no --ckpt: randomly initialised weights, the answers mean nothing")
     model = model.to(dev).eval()
-    qp = query_predict.QueryPredictor(model, data, k=args.k, batch_size=1, filtered=not args.unfiltered)
+    qp = query_predict.QueryPredictor(model, data, k=args.k, batch_size=1, filtered=not args.unfiltered, entity_capacity=reserve)
     at = 0
     while at < len(edits):        # (runs of one kind go in one call)
+        if edits[at][0] is None:
+            (new_id,) = qp.add_entities(1).tolist()
+            assert ent[new_id] == edits[at][1]
+            print("entity %r added as id %d (%d of %d rows in use)" % (edits[at][1], new_id, qp.num_entities, qp.num_slots))
+            at += 1
+            continue
         end = at
         while end < len(edits) and edits[end][0] == edits[at][0]:
             end += 1

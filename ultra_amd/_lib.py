@@ -164,6 +164,8 @@ def _load():
     lib.ultra_filtered_above.argtypes = [vp, vp, vp, i64, i64, ctypes.c_float, vp, vp, vp, i64, vp, vp, i64, vp]
     lib.ultra_query_segment.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, vp, vp, i64, vp, i64, vp, vp, vp, vp]
     lib.ultra_nonzero_lists.argtypes = [vp, i64, i64, vp, vp, vp, i64, vp]
+    # ... over the live ids of rows of n slots: the device pointer to the int64 live count before the stream
+    lib.ultra_nonzero_lists_live.argtypes = [vp, i64, i64, vp, vp, vp, i64, vp, vp]
     lib.ultra_beam_search_layer.argtypes =[vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, i64, i32, vp, vp, vp]
     lib.ultra_beam_search_layer_batch.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, i32, vp, vp, vp]
     lib.ultra_symbolic_traversal.argtypes = [vp, vp, vp, i64, vp, i64, i32, vp, vp, vp]

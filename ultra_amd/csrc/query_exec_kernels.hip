@@ -1,5 +1,5 @@
-// Compiled execution of complex logical queries (include/ultra_nbfnet.h: ultra_query_segment, ultra_nonzero_lists;
-// DESIGN.md §14).
+// Compiled execution of complex logical queries (include/ultra_nbfnet.h: ultra_query_segment, ultra_nonzero_lists,
+// ultra_nonzero_lists_live).
 //
 // ultra_query_segment: what a batch of UltraQuery stack machines does between two projection calls, as ONE launch.  The host
 // has compiled the batch's postfix queries into a program (ultra_amd/query_exec.py): per sample the depth of its stack on
@@ -16,6 +16,24 @@
 // ultra_nonzero_lists: the non-zero ids of every row of a matrix as ragged ascending lists -- the known-answer layout of
 // ultra_filtered_topk, built from the final symbolic sets without a host round trip.  Two launches: counts per row; then per
 // row a sum of the counts before it and an ordered compaction (block scan per tile of the row).  No atomics.
+//
+// ultra_nonzero_lists_live: the same two kernels over the LIVE prefix of rows of n slots -- a graph served with
+// reserved rows, whose dead slots hold 1.0 after a negation and must not be listed as entailed answers.
+//   Work split     one workgroup of 256 threads per row in both kernels, as in the parent: the grid, `counts` and `ptr_out`
+//                  depend on (batch, n) alone, so a recorded launch serves every later live count.
+//   Live count     one uniform 8-byte load of *n_live per workgroup (a scalar load: the pointer is a kernel argument), clamped
+//                  to [0, n]; it replaces n as the bound of the count loop, of the tile loop and of the per-id test.  The row
+//                  stride stays n.  The clamped value bounds loops only and is never an index; an id at or beyond it is never
+//                  loaded, so whatever a dead slot holds (1.0, NaN) reaches neither a count nor a list.
+//   Memory         every live element is read twice (count, fill), 4-byte loads coalesced across the workgroup (count) or 16
+//                  consecutive bytes per thread (fill); each listed id is one 8-byte store.  At serving sizes (16 x 14,541
+//                  fp32 = 0.9 MB) both launches are latency-bound, not bandwidth-bound.
+//   LDS / sync     four wave totals (32 B) and four wave counts (16 B); two barriers per tile.  No atomics, no memset node:
+//                  for batch == 0 a one-thread kernel writes ptr_out[0] (a captured memset replays wrongly between eager
+//                  work).
+//   Registers      count 11 VGPRs / 20 SGPRs, fill 32 VGPRs / 48 SGPRs (four hit flags, two 64-bit cursors), no scratch, 8 waves a
+//                  SIMD allowed: occupancy is bounded by the grid (one workgroup a row), not by registers.
+// The parent passes n_live == NULL -- every slot is live -- and keeps its results bit for bit.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -180,20 +198,31 @@ __device__ __forceinline__ long long block_sum(long long v, long long *wave_tota
     return total;
 }
 
-__global__ void __launch_bounds__(NZ_THREADS) nonzero_count_kernel(const float *__restrict__ x, long long n, int64_t *__restrict__ counts) {
+// The live ids of a row of n slots: *n_live clamped to [0, n]; NULL: every slot (the rule of csrc/topk_kernels.hip).
+__device__ __forceinline__ long long nonzero_live(const int64_t *__restrict__ n_live, long long n) {
+    if (!n_live) return n;
+    const long long v = *n_live;
+    return v < 0 ? 0 : (v < n ? v : n);
+}
+
+__global__ void __launch_bounds__(NZ_THREADS) nonzero_count_kernel(const float *__restrict__ x, long long n, int64_t *__restrict__ counts,
+                                                                   const int64_t *__restrict__ n_live) {
     __shared__ long long wave_total[NZ_THREADS / 64];
     const float *row = x + (long long)blockIdx.x * n;
+    const long long live = nonzero_live(n_live, n);
     long long c = 0;
-    for (long long i = threadIdx.x; i < n; i += NZ_THREADS) c += is_nonzero(row[i]) ? 1 : 0;
+    for (long long i = threadIdx.x; i < live; i += NZ_THREADS) c += is_nonzero(row[i]) ? 1 : 0;
     c = block_sum(c, wave_total);
     if (threadIdx.x == 0) counts[blockIdx.x] = c;
 }
 
 __global__ void __launch_bounds__(NZ_THREADS) nonzero_fill_kernel(const float *__restrict__ x, long long n, const int64_t *__restrict__ counts,
-                                                                  int64_t *__restrict__ ptr_out, int64_t *__restrict__ index_out) {
+                                                                  int64_t *__restrict__ ptr_out, int64_t *__restrict__ index_out,
+                                                                  const int64_t *__restrict__ n_live) {
     __shared__ long long wave_total[NZ_THREADS / 64];
     __shared__ int wave_count[NZ_THREADS / 64];
     const long long b = blockIdx.x;
+    const long long live = nonzero_live(n_live, n);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     long long before = 0;
     for (long long r = tid; r < b; r += NZ_THREADS) before += counts[r];
@@ -203,14 +232,14 @@ __global__ void __launch_bounds__(NZ_THREADS) nonzero_fill_kernel(const float *_
         ptr_out[b + 1] = at + counts[b];
     }
     const float *row = x + b * n;
-    for (long long lo = 0; lo < n; lo += NZ_TILE) {
+    for (long long lo = 0; lo < live; lo += NZ_TILE) {
         // thread t owns NZ_PER_THREAD consecutive ids: the order of the ids is the order of (thread, slot)
         const long long first = lo + (long long)tid * NZ_PER_THREAD;
         bool hit[NZ_PER_THREAD];
         int mine = 0;
 #pragma unroll
         for (int j = 0; j < NZ_PER_THREAD; ++j) {
-            hit[j] = first + j < n && is_nonzero(row[first + j]);
+            hit[j] = first + j < live && is_nonzero(row[first + j]);
             mine += hit[j] ? 1 : 0;
         }
         int incl = mine;
@@ -233,6 +262,9 @@ __global__ void __launch_bounds__(NZ_THREADS) nonzero_fill_kernel(const float *_
         __syncthreads();        // (wave_count is rewritten by the next tile)
     }
 }
+
+// ptr_out of an empty batch, without a memset node
+__global__ void nonzero_empty_kernel(int64_t *__restrict__ ptr_out) { ptr_out[0] = 0; }
 
 }  // namespace ultra
 
@@ -289,18 +321,24 @@ extern "C" int32_t ultra_query_segment(const int32_t *entry_depth, const int32_t
     return ULTRA_OK;
 }
 
-extern "C" int32_t ultra_nonzero_lists(const void *x, int64_t batch, int64_t n, int64_t *counts, int64_t *ptr_out,
-                                       int64_t *index_out, int64_t capacity, void *stream) {
+// Both entries: `who` names the caller in the messages; n_live == NULL: every slot is live (the parent).
+static int32_t nonzero_lists_impl(const char *who, bool twin, const void *x, int64_t batch, int64_t n, int64_t *counts,
+                                  int64_t *ptr_out, int64_t *index_out, int64_t capacity, const int64_t *n_live, void *stream) {
+    const std::string name(who);
     if (n >= (int64_t)1 << 31 || batch >= (int64_t)1 << 31) {
-        ultra::set_error("ultra_nonzero_lists: batch and n must stay below 2^31");
+        ultra::set_error(name + ": batch and n must stay below 2^31");
         return ULTRA_ERR_UNSUPPORTED;
     }
+    if (twin && !n_live) {
+        ultra::set_error(name + ": n_live is NULL");
+        return ULTRA_ERR_INVALID;
+    }
     if (!ptr_out || batch < 0 || n < 0 || (batch > 0 && (!counts || (n > 0 && (!x || !index_out))))) {
-        ultra::set_error("ultra_nonzero_lists: NULL operand or negative size");
+        ultra::set_error(name + ": NULL operand or negative size");
         return ULTRA_ERR_INVALID;
     }
     if (capacity < batch * n) {
-        ultra::set_error("ultra_nonzero_lists: index_out holds " + std::to_string(capacity) + " ids, a full matrix has " +
+        ultra::set_error(name + ": index_out holds " + std::to_string(capacity) + " ids, a full matrix has " +
                          std::to_string(batch * n));
         return ULTRA_ERR_INVALID;
     }
@@ -308,23 +346,39 @@ extern "C" int32_t ultra_nonzero_lists(const void *x, int64_t batch, int64_t n, 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     (void)hipGetLastError();
     if (batch == 0) {       // ptr_out = [0]
-        if (hipMemsetAsync(ptr_out, 0, sizeof(int64_t), s) != hipSuccess) {
-            ultra::set_error("ultra_nonzero_lists: could not clear ptr_out");
+        if (twin) {
+            hipLaunchKernelGGL(ultra::nonzero_empty_kernel, dim3(1), dim3(1), 0, s, ptr_out);
+            if (hipGetLastError() != hipSuccess) {
+                ultra::set_error("nonzero_empty_kernel launch failed");
+                return ULTRA_ERR_HIP;
+            }
+        } else if (hipMemsetAsync(ptr_out, 0, sizeof(int64_t), s) != hipSuccess) {
+            ultra::set_error(name + ": could not clear ptr_out");
             return ULTRA_ERR_HIP;
         }
         return ULTRA_OK;
     }
     hipLaunchKernelGGL(ultra::nonzero_count_kernel, dim3((unsigned)batch), dim3(ultra::NZ_THREADS), 0, s, (const float *)x,
-                       (long long)n, counts);
+                       (long long)n, counts, n_live);
     if (hipGetLastError() != hipSuccess) {
         ultra::set_error("nonzero_count_kernel launch failed");
         return ULTRA_ERR_HIP;
     }
     hipLaunchKernelGGL(ultra::nonzero_fill_kernel, dim3((unsigned)batch), dim3(ultra::NZ_THREADS), 0, s, (const float *)x,
-                       (long long)n, (const int64_t *)counts, ptr_out, index_out);
+                       (long long)n, (const int64_t *)counts, ptr_out, index_out, n_live);
     if (hipGetLastError() != hipSuccess) {
         ultra::set_error("nonzero_fill_kernel launch failed");
         return ULTRA_ERR_HIP;
     }
     return ULTRA_OK;
+}
+
+extern "C" int32_t ultra_nonzero_lists(const void *x, int64_t batch, int64_t n, int64_t *counts, int64_t *ptr_out,
+                                       int64_t *index_out, int64_t capacity, void *stream) {
+    return nonzero_lists_impl("ultra_nonzero_lists", false, x, batch, n, counts, ptr_out, index_out, capacity, nullptr, stream);
+}
+
+extern "C" int32_t ultra_nonzero_lists_live(const void *x, int64_t batch, int64_t n, int64_t *counts, int64_t *ptr_out,
+                                            int64_t *index_out, int64_t capacity, const int64_t *n_live, void *stream) {
+    return nonzero_lists_impl("ultra_nonzero_lists_live", true, x, batch, n, counts, ptr_out, index_out, capacity, n_live, stream);
 }

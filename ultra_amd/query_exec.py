@@ -14,7 +14,8 @@ the queries are known on the host before anything runs, so the interpreter's who
                    ultra_query_segment (csrc/query_exec_kernels.hip) per segment, the unchanged `model.model` /
                    `model.symbolic_model` per projection, and no call that waits for the device
   nonzero_lists    the non-zero ids of every row of a (batch, n) matrix as ragged ascending lists (ultra_nonzero_lists): the
-                   layout ultra_filtered_topk takes for the entities to leave out
+                   layout ultra_filtered_topk takes for the entities to leave out; num_live: over the live ids of a graph
+                   with reserved rows (ultra_nonzero_lists_live)
 
 The compiled route computes exactly what the interpreter computes: the same fuzzy-set arithmetic operation for operation,
 the same projection calls with the same inputs in the same order.  It keeps what a caller of `forward` gets -- the logits
@@ -107,17 +108,21 @@ def _kind(word, row):
     return flags
 
 
-def compile(query, num_nodes, num_relations, stack_size=UltraQuery.stack_size):
+def compile(query, num_nodes, num_relations, stack_size=UltraQuery.stack_size, num_live=None):
     """The `Program` of a (batch, L) int64 batch of postfix queries (a `Query` or a tensor; a CUDA tensor is copied to the
     host once).  Raises ValueError for everything `UltraQuery.forward` would refuse, or fault on, while it runs: stack
     overflow and underflow, more than one value left, nothing left, a row without `stop`, an entity id outside
-    [0, num_nodes), a relation id outside [0, num_relations)."""
+    [0, num_nodes), a relation id outside [0, num_relations).  num_live (a graph with reserved rows, DESIGN.md section 21:
+    num_nodes counts slots): the anchors are the ids below it; None: below num_nodes."""
     q = torch.as_tensor(query)
     if q.dim() != 2 or q.dtype != torch.int64:
         raise ValueError("compile takes a (batch, L) int64 batch of postfix queries, got %s %s" % (tuple(q.shape), q.dtype))
     rows = q.detach().as_subclass(torch.Tensor).cpu().tolist()
     batch, length = len(rows), q.shape[1]
     num_nodes, num_relations, stack_size = int(num_nodes), int(num_relations), int(stack_size)
+    num_live = num_nodes if num_live is None else int(num_live)
+    if not 0 <= num_live <= num_nodes:
+        raise ValueError("num_live must lie in [0, num_nodes = %d], got %d" % (num_nodes, num_live))
     payload = ~Query.operation
     ip, depth = [0] * batch, [0] * batch
     segments, projections = [], []
@@ -135,8 +140,8 @@ def compile(query, num_nodes, num_relations, stack_size=UltraQuery.stack_size):
             if kind[b] == 0:
                 if depth[b] >= stack_size:
                     raise ValueError(_OVERFLOW % stack_size)
-                if not 0 <= word[b] < num_nodes:
-                    raise ValueError("query %d: entity id %d outside [0, %d)" % (b, word[b], num_nodes))
+                if not 0 <= word[b] < num_live:
+                    raise ValueError("query %d: entity id %d outside [0, %d)" % (b, word[b], num_live))
                 ops[b].append((PUSH_ENTITY, word[b]))
                 depth[b] += 1
             elif kind[b] == Query.negation:
@@ -252,9 +257,12 @@ def segment(words, offset, batch, num_nodes, logic, stack, push_src, pop_dst, sy
         _lib.stream_of(stack)))
 
 
-def nonzero_lists(x):
+def nonzero_lists(x, num_live=None):
     """(ptr (batch + 1) int64, index int64): per row of x (batch, n) fp32 on the GPU the ids v with x[b, v] != 0, ascending
-    (NaN counts, -0.0 does not).  `index` has room for batch * n ids; the first ptr[-1] are filled.  No host wait."""
+    (NaN counts, -0.0 does not).  `index` has room for batch * n ids; the first ptr[-1] are filled.  No host wait.
+    num_live (rows of n SLOTS of which the first num_live are entities in use): ultra_nonzero_lists_live on the full rows -- no
+    slice, no copy; a dead slot is never read.  One int64 on x's device is handed to the kernels as it is (they clamp it to
+    [0, n]); an int is checked against [0, n] on the host and uploaded.  None: ultra_nonzero_lists."""
     if not x.is_cuda:
         raise RuntimeError("ultra_amd.query_exec.nonzero_lists: expected a GPU tensor; the MI355X engine has no CPU path")
     if x.dim() != 2 or x.dtype != torch.float32:
@@ -264,8 +272,20 @@ def nonzero_lists(x):
     ptr = torch.empty(batch + 1, dtype=torch.int64, device=x.device)
     index = torch.empty(max(1, batch * n), dtype=torch.int64, device=x.device)
     counts = torch.empty(max(1, batch), dtype=torch.int64, device=x.device)
-    _lib.check(_lib.lib.ultra_nonzero_lists(x.data_ptr(), batch, n, counts.data_ptr(), ptr.data_ptr(), index.data_ptr(),
-                                            batch * n, _lib.stream_of(x)))
+    if num_live is None:
+        _lib.check(_lib.lib.ultra_nonzero_lists(x.data_ptr(), batch, n, counts.data_ptr(), ptr.data_ptr(), index.data_ptr(),
+                                                batch * n, _lib.stream_of(x)))
+        return ptr, index
+    if torch.is_tensor(num_live):
+        if num_live.numel() != 1 or num_live.dtype != torch.long or num_live.device != x.device:
+            raise ValueError("a tensor `num_live` is one int64 on the matrix's device")
+        live = num_live      # (referenced until the launch is enqueued)
+    else:
+        if isinstance(num_live, bool) or not 0 <= int(num_live) <= n:
+            raise ValueError("num_live must lie in [0, %d] (the slots of a row), got %r" % (n, num_live))
+        live = torch.tensor(int(num_live), dtype=torch.long, device=x.device)
+    _lib.check(_lib.lib.ultra_nonzero_lists_live(x.data_ptr(), batch, n, counts.data_ptr(), ptr.data_ptr(), index.data_ptr(),
+                                                 batch * n, live.data_ptr(), _lib.stream_of(x)))
     return ptr, index
 
 
