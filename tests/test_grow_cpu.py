@@ -20,6 +20,7 @@ import torch
 
 from ultra_amd import _lib, models, predict, rspmm, synthetic, tasks
 from ultra_amd import data as udata
+from ultra_amd.live import with_slots
 from ultra_amd.data import Data
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
@@ -77,7 +78,7 @@ def test_padding_leaves_the_scores_of_the_entities_alone(served):
     model, data = served
     n = int(data.num_nodes)
     h, _, r = data.target_triples[:4].unbind(-1)
-    padded = predict._with_slots(data, n + 8, relation_graph=True)
+    padded = with_slots(data, n + 8, relation_graph=True)
     assert padded is not data and padded.num_nodes == n + 8 and padded.edge_index is data.edge_index
     with torch.no_grad():
         want = model(data, predict._candidates(data, h, r, "tail"))
@@ -88,7 +89,7 @@ def test_padding_leaves_the_scores_of_the_entities_alone(served):
 
 def test_the_relation_graph_of_a_padded_graph_is_that_of_the_graph(served):
     _, data = served
-    padded = predict._with_slots(data, int(data.num_nodes) + 8, relation_graph=True)
+    padded = with_slots(data, int(data.num_nodes) + 8, relation_graph=True)
     assert padded.relation_graph is not data.relation_graph
     assert torch.equal(padded.relation_graph.edge_index, data.relation_graph.edge_index)
     assert torch.equal(padded.relation_graph.edge_type, data.relation_graph.edge_type)

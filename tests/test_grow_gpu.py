@@ -8,6 +8,7 @@ import torch
 
 from ultra_amd import _lib, models, predict, rspmm, synthetic, tasks
 from ultra_amd import data as udata
+from ultra_amd.live import with_slots
 from ultra_amd.data import Data
 
 pytestmark = pytest.mark.gpu
@@ -307,7 +308,7 @@ def grow(live):
 def test_padding_leaves_the_engine_scores_bit_equal(dev, model, fixture_graph):
     """The premise, on the engine: reserved rows change no score of an entity by a bit, and the relation graph not at all."""
     data = fixture_graph
-    padded = predict._with_slots(data, 308, relation_graph=True)
+    padded = with_slots(data, 308, relation_graph=True)
     assert torch.equal(padded.relation_graph.adjacency_bits, data.relation_graph.adjacency_bits)
     assert torch.equal(padded.relation_graph.edge_index, data.relation_graph.edge_index)
     h, t, r = data.target_triples[:4].unbind(-1)

@@ -31,6 +31,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from ultra_amd import _lib, models, predict, rspmm, synthetic, tasks  # noqa: E402
+from ultra_amd.live import with_slots  # noqa: E402
 from ultra_amd.data import Data  # noqa: E402
 
 
@@ -180,7 +181,7 @@ def shape_case(name, k, bs, reps, warmup, fact_reps, dev):
     for key, reserve in (("0", 0), ("0_again", 0), ("256", 256), ("4096", 4096)):
         served, n_live = data, None
         if reserve:
-            served = predict._with_slots(data, n + reserve, relation_graph=True)
+            served = with_slots(data, n + reserve, relation_graph=True)
             n_live = torch.tensor([n], dtype=torch.long, device=dev)
         keep.append((served, n_live))
         steps[key] = predict._GraphedPredictStep(model, served, bs, k, "tail", 1 << 16, n_live=n_live)

@@ -1,0 +1,251 @@
+"""The edit state of one served graph, in one place ("The live graph's state in one place").
+
+predict.Predictor and query_predict.QueryPredictor each hold one LiveGraph and forward add_facts / remove_facts / add_entities /
+compact / materialized to it.  The rules that define a served graph live here and nowhere else: what counts as an edit, when the
+delta is folded into the graph, which ids are live, and what `materialized()` means.
+
+  LiveGraph        the served graph (reserved rows included), its rspmm.GraphDelta, the live count and -- where the owner reads known
+                   answers from a graph -- the filter graph
+  with_facts       a copy of a graph with facts appended the way GraphDelta.materialize appends them
+  without_facts    ... without every edge of the facts
+  with_slots       ... with reserved rows
+  check_live       ValueError for an id in the reserve
+  forwarded        a read-only property of an owner that reads a field of its LiveGraph
+"""
+import copy
+import operator
+
+import torch
+
+from . import rspmm, tasks
+
+
+def with_facts(graph, h, r, t):
+    """A copy of `graph` with the edges of the facts appended the way GraphDelta.materialize appends them: the direct edges
+    (h, t, r), then the inverse ones (t, h, r + num_relations / 2)."""
+    out = copy.copy(graph)
+    dev = graph.edge_index.device
+    h, r, t = h.to(dev), r.to(dev), t.to(dev)
+    out.edge_index = torch.cat([graph.edge_index, torch.stack([torch.cat([h, t]), torch.cat([t, h])])], dim=1)
+    out.edge_type = torch.cat([graph.edge_type, torch.cat([r, r + int(graph.num_relations) // 2])])
+    return out
+
+
+def without_facts(graph, h, r, t):
+    """A copy of `graph` without every edge equal to (h[i], t[i], r[i]) or to (t[i], h[i], r[i] + num_relations / 2)."""
+    out = copy.copy(graph)
+    dev = graph.edge_index.device
+    h, r, t = h.to(dev), r.to(dev), t.to(dev)
+    n, rels = int(graph.num_nodes), int(graph.num_relations)
+    gone = torch.cat([(h * n + t) * rels + r, (t * n + h) * rels + r + rels // 2]).unique()
+    codes = (graph.edge_index[0] * n + graph.edge_index[1]) * rels + graph.edge_type
+    keep = gone[torch.searchsorted(gone, codes).clamp_(max=len(gone) - 1)] != codes
+    out.edge_index, out.edge_type = graph.edge_index[:, keep], graph.edge_type[keep]
+    return out
+
+
+def with_slots(graph, slots, relation_graph=False):
+    """A shallow copy of `graph` with num_nodes = slots >= graph.num_nodes: the same edge list, the rows beyond the old count
+    reserved (no edge names them).  relation_graph: build the copy's own where `graph` carries one -- it equals graph's, a
+    node without edges plays no role."""
+    out = copy.copy(graph)
+    out.num_nodes = int(slots)
+    if relation_graph and getattr(graph, "relation_graph", None) is not None:
+        tasks.build_relation_graph(out)
+    return out
+
+
+def check_live(ids, num_live, what):
+    """ValueError unless every id is an entity in use: ids in [0, num_live) (a graph with reserved rows; one host read)."""
+    if len(ids) and bool(((ids < 0) | (ids >= num_live)).any()):
+        raise ValueError("%s must be existing entities (ids in [0, %d)): a reserved row is no entity until add_entities hands "
+                         "it out" % (what, num_live))
+
+
+def forwarded(name):
+    """For an owner that holds its LiveGraph as `_live`: a read-only property that reads `name` of it, so that the owner's
+    attributes of before stay readable under their names."""
+    return property(operator.attrgetter("_live." + name))
+
+
+class LiveGraph(object):
+    """data: the graph to serve; delta_capacity: the facts (added + retracted) held in an rspmm.GraphDelta beside it before they
+    are folded into it; entity_capacity=M > 0: M rows reserved for entities that arrive later -- `graph` is then a shallow copy
+    of `data` with num_nodes = N + M slots and its own relation graph, `num_entities` of them live, and `live_count` one device
+    int64 that holds the same number for the owner's life (None without a reserve).
+
+    delta_policy: when the delta exists.  "eager": from construction, and a new empty one after every compaction (a captured
+    step is handed the delta before the first edit).  "lazy": None until the first edit and None again after a compaction (an
+    owner that was never edited runs exactly what it ran before).  "never": no delta -- every add_facts compacts, every
+    remove_facts is folded at once (a model without a delta route).
+
+    keep_filter: also hold the graph known answers are read from, `filter_graph` -- `filter_data` with the same edits, or (None)
+    the served graph with them.  Without it `filter_graph` is None.
+
+    owner: the class name in add_entities' error text.  on_rebuild(): called in every compaction that changes the served
+    graph, before `graph` is replaced."""
+
+    def __init__(self, data, delta_capacity=256, entity_capacity=0, filter_data=None, keep_filter=False, delta_policy="lazy",
+                 owner="LiveGraph", on_rebuild=None):
+        if isinstance(entity_capacity, bool) or not isinstance(entity_capacity, int) or entity_capacity < 0:
+            raise ValueError("entity_capacity must be a non-negative int (reserved rows), got %r" % (entity_capacity,))
+        if isinstance(delta_capacity, bool) or not isinstance(delta_capacity, int) or delta_capacity < 1:
+            raise ValueError("delta_capacity must be a positive int (facts), got %r" % (delta_capacity,))
+        if delta_policy not in ("eager", "lazy", "never"):
+            raise ValueError("delta_policy must be 'eager', 'lazy' or 'never', got %r" % (delta_policy,))
+        self.entity_capacity, self.delta_capacity = entity_capacity, delta_capacity
+        self.num_entities = int(data.num_nodes)
+        self.live_count = None
+        if entity_capacity:
+            slots = self.num_entities + entity_capacity
+            data = with_slots(data, slots, relation_graph=True)
+            if filter_data is not None:
+                filter_data = with_slots(filter_data, slots)
+            self.live_count = torch.full((1,), self.num_entities, dtype=torch.long, device=data.edge_index.device)
+        self.graph = data
+        self._policy, self._owner, self._on_rebuild = delta_policy, owner, on_rebuild
+        self.filter_graph = self._filter_base = None
+        self._filter_is_graph = False
+        if keep_filter:
+            self.filter_graph = self._filter_base = data if filter_data is None else filter_data
+            self._filter_is_graph = self.filter_graph is data
+        self.delta = self._new_delta() if delta_policy == "eager" else None
+
+    @property
+    def num_slots(self):
+        """The rows of the served graph: num_entities live ones and the rest of the reserve."""
+        return int(self.graph.num_nodes)
+
+    def _new_delta(self, capacity=None):
+        return rspmm.GraphDelta(self.graph, self.delta_capacity if capacity is None else capacity, num_live=self.num_entities)
+
+    def _probe(self):
+        """A delta to check arguments with or to materialise through: the one held, or an empty one."""
+        return self.delta if self.delta is not None else self._new_delta(1)
+
+    def _own_delta(self):
+        if self.delta is None:      # ("lazy": made at the first edit that fits)
+            self.delta = self._new_delta()
+        return self.delta
+
+    def _fits(self, n):
+        """Can the delta take n more facts or retractions?  A fact holds two edges, a retraction at most two tombstone keys."""
+        if self._policy == "never":
+            return False
+        held = 0 if self.delta is None else 2 * len(self.delta) + self.delta.num_removed
+        return held + 2 * n <= 2 * self.delta_capacity
+
+    def num_live_for(self, on_gpu):
+        """What the lists and the selection take beside their arguments: nothing without a reserve; with one, the live count --
+        the device scalar for the kernels, the host int for the plain-torch restatements."""
+        if not self.entity_capacity:
+            return {}
+        return {"num_live": self.live_count if on_gpu else self.num_entities}
+
+    # ---- the growing graph ----
+    def add_entities(self, count=1, compact=None):
+        """`count` new entities: their ids [num_entities, num_entities + count), and the live count raised -- the host int, the
+        device scalar and the delta's bound.  Beyond the reserve num_entities + count + entity_capacity slots are laid out by
+        `compact(slots=...)`: this object's, or the owner's own `compact` where it hands that in (it forwards here)."""
+        if not self.entity_capacity:
+            raise ValueError("this %s reserves no rows: create it with entity_capacity > 0 to add entities" % self._owner)
+        if isinstance(count, bool) or not isinstance(count, int) or count < 1:
+            raise ValueError("count must be a positive int, got %r" % (count,))
+        first = self.num_entities
+        if first + count > self.num_slots:
+            (compact or self.compact)(slots=first + count + self.entity_capacity)
+        self.num_entities = first + count
+        self.live_count.fill_(self.num_entities)
+        if self.delta is not None:
+            self.delta.num_live = self.num_entities
+        return torch.arange(first, first + count, dtype=torch.long, device=self.graph.edge_index.device)
+
+    def materialized(self):
+        """The served edge list with the delta's edits (GraphDelta.materialize) and num_nodes = num_entities -- no reserved row --
+        with the filter graph held now as its `filtered_data` where that is a graph of its own.  A new copy at every call."""
+        out = copy.copy(self._probe().materialize(self.graph, num_nodes=self.num_entities))
+        if self.filter_graph is not None and not self._filter_is_graph:     # (the one held now, the stated facts included)
+            out.filtered_data = copy.copy(self.filter_graph)
+            out.filtered_data.num_nodes = self.num_entities
+        return out
+
+    # ---- the changing graph ----
+    def add_facts(self, h, r, t):
+        h, r, t = self._probe().check(h, r, t)
+        if len(h) == 0:
+            return 0 if self.delta is None else len(self.delta)
+        if not self._fits(len(h)):
+            self.compact(extra=(h, r, t))
+            return 0
+        self._own_delta().add(h, r, t)
+        self._refresh_filter_graph()
+        return len(self.delta)
+
+    def remove_facts(self, h, r, t):
+        h, r, t = self._probe().check(h, r, t)
+        if len(h) == 0:
+            return torch.zeros(0, dtype=torch.long, device=h.device)
+        # (a call that may not fit compacts first, and one larger than the whole capacity is applied to a delta of its own and
+        # folded at once)
+        if not self._fits(len(h)):
+            self.compact()
+        fold = None
+        if self._fits(len(h)):
+            removed = self._own_delta().remove(h, r, t)
+        else:
+            fold = self._new_delta(len(h))
+            removed = fold.remove(h, r, t)
+        if self.filter_graph is not None and not self._filter_is_graph:
+            self._filter_base = without_facts(self._filter_base, h, r, t)
+        if fold is not None:
+            self.compact(delta=fold)
+        self._refresh_filter_graph()
+        return removed
+
+    def _refresh_filter_graph(self):
+        if self.filter_graph is None:
+            return
+        if self.delta is None:
+            self.filter_graph = self._filter_base
+        elif self._filter_is_graph:
+            self.filter_graph = self.delta.materialize(self.graph)
+        else:
+            fh, fr, ft = self.delta.facts[:len(self.delta)].unbind(1)
+            self.filter_graph = with_facts(self._filter_base, fh, fr, ft)
+
+    def compact(self, extra=None, delta=None, slots=None):
+        """Fold the delta's edits (and `extra` = (h, r, t), checked by the caller) into the served graph: the materialised graph
+        -- without the tombstoned edges, with the added ones, its relation graph rebuilt -- becomes `graph`, and the delta is
+        emptied.  `delta`: fold that one instead of the one held.  The slot count and the live count of a graph with reserved
+        rows stay; `slots` (add_entities beyond the reserve): the new slot count, laid out in the same rebuild."""
+        delta = self.delta if delta is None else delta
+        facts = [] if delta is None else [delta.facts[:len(delta)]]
+        if extra is not None:
+            facts.append(torch.stack(list(extra), dim=1))
+        facts = torch.cat(facts) if facts else torch.zeros(0, 3, dtype=torch.long)
+        if slots is not None and int(slots) == self.num_slots:
+            slots = None
+        if len(facts) == 0 and not (delta is not None and delta.num_removed) and slots is None:
+            return
+        fh, fr, ft = facts.unbind(1)
+        base = self.graph
+        if delta is not None and delta.num_removed:
+            base = copy.copy(self.graph)
+            base.edge_index, base.edge_type = delta.surviving(self.graph.edge_index, self.graph.edge_type)
+        graph = with_facts(base, fh, fr, ft)
+        if slots is not None:
+            graph.num_nodes = int(slots)
+        if getattr(self.graph, "relation_graph", None) is not None:
+            tasks.build_relation_graph(graph)
+        if self.filter_graph is not None:
+            if self._filter_is_graph:
+                self._filter_base = graph
+            else:
+                self._filter_base = with_facts(self._filter_base, fh, fr, ft)
+                if slots is not None:
+                    self._filter_base.num_nodes = int(slots)
+            self.filter_graph = self._filter_base
+        if self._on_rebuild is not None:
+            self._on_rebuild()
+        self.graph = graph
+        self.delta = self._new_delta() if self._policy == "eager" else None

@@ -25,14 +25,15 @@ A GROWING graph: Predictor(entity_capacity=M) reserves M rows f
 filtered_above and their restatements, the ultra_filtered_*_live entries.
 """
 
-import copy
+import functools
 import inspect
 import math
 
 import torch
 
-from . import _lib, dense, models, rspmm, tasks
+from . import _lib, dense, models, tasks
 from .graph import Capture, param_state
+from .live import LiveGraph, check_live, forwarded
 
 
 def _live_int(num_live, n):
@@ -51,6 +52,15 @@ def _live_operand(num_live, n, dev):
             raise ValueError("a tensor `num_live` is one int64 on the scores' device")
         return num_live
     return torch.tensor(_live_int(num_live, n), dtype=torch.long, device=dev)
+
+
+def _select(entry, args, n_live, dev):
+    """One launch of a selection entry on `dev`'s stream: `entry` without a live count, its `_live` twin with the device scalar
+    `n_live` appended to the same arguments.  The entry is looked up when it is called."""
+    if n_live is None:
+        _lib.check(getattr(_lib.lib, entry)(*args, _lib.stream_of(dev)))
+    else:
+        _lib.check(getattr(_lib.lib, entry + "_live")(*args, n_live.data_ptr(), _lib.stream_of(dev)))
 
 
 def filtered_topk_reference(pred, k, ptr=None, index=None, num_live=None):
@@ -77,7 +87,7 @@ def filtered_topk_reference(pred, k, ptr=None, index=None, num_live=None):
     return ids, scores, count
 
 
-def _check_k(k):
+def check_k(k):
     if not isinstance(k, int) or not 1 <= k <= _lib.TOPK_MAX:
         raise ValueError("k must be an int in [1, %d], got %r" % (_lib.TOPK_MAX, k))
 
@@ -86,7 +96,7 @@ def filtered_topk(pred, k, ptr=None, index=None, num_live=None):
     """filtered_topk_reference through the HIP kernel: pred (batch, N) fp32 on the GPU; ptr (batch + 1) / index int64, ids
     ascending and distinct within a row; ptr None: no filter.  num_live (an int in [1, N], or one int64 on the device, read by
     the kernels): ultra_filtered_topk_live on the full rows -- no slice, no copy; None: ultra_filtered_topk."""
-    _check_k(k)
+    check_k(k)
     if not pred.is_cuda:
         raise RuntimeError("ultra_amd.predict.filtered_topk: expected a GPU tensor; the MI355X engine has no CPU path")
     if pred.dim() != 2 or pred.dtype != torch.float32:
@@ -106,11 +116,8 @@ def filtered_topk(pred, k, ptr=None, index=None, num_live=None):
     ws = torch.empty(max(1, _lib.lib.ultra_filtered_topk_workspace(batch, n, k) // 8), dtype=torch.long, device=dev)
     args = (pred.data_ptr(), None if ptr is None else ptr.data_ptr(), None if ptr is None else index.data_ptr(), batch, n, k,
             ids.data_ptr(), scores.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel() * 8)
-    if num_live is None:
-        _lib.check(_lib.lib.ultra_filtered_topk(*args, _lib.stream_of(dev)))
-    else:
-        live = _live_operand(num_live, n, dev)     # (referenced until the launch is enqueued)
-        _lib.check(_lib.lib.ultra_filtered_topk_live(*args, live.data_ptr(), _lib.stream_of(dev)))
+    live = None if num_live is None else _live_operand(num_live, n, dev)     # (referenced until the launch is enqueued)
+    _select("ultra_filtered_topk", args, live, dev)
     return ids, scores, count
 
 
@@ -203,11 +210,8 @@ def filtered_above(pred, threshold, ptr=None, index=None, num_live=None):
     ws = torch.empty(max(1, _lib.lib.ultra_filtered_above_workspace(batch, n) // 8), dtype=torch.long, device=dev)
     args = (pred.data_ptr(), None if ptr is None else ptr.data_ptr(), None if ptr is None else index.data_ptr(), batch, n, thr,
             out_ptr.data_ptr(), ids.data_ptr(), scores.data_ptr(), ids.numel(), size.data_ptr(), ws.data_ptr(), ws.numel() * 8)
-    if num_live is None:
-        _lib.check(_lib.lib.ultra_filtered_above(*args, _lib.stream_of(dev)))
-    else:
-        live = _live_operand(num_live, n, dev)     # (referenced until the launch is enqueued)
-        _lib.check(_lib.lib.ultra_filtered_above_live(*args, live.data_ptr(), _lib.stream_of(dev)))
+    live = None if num_live is None else _live_operand(num_live, n, dev)     # (referenced until the launch is enqueued)
+    _select("ultra_filtered_above", args, live, dev)
     return out_ptr, ids, scores, size
 
 
@@ -241,7 +245,14 @@ def _candidates(data, anchor, relation, mode):
     return torch.stack([fixed, every, r] if mode == "tail" else [every, fixed, r], dim=-1)
 
 
-class _GraphedPredictStep(Capture):
+class _IndexedStep(Capture):
+    """A captured step that reads the known lists of a whole call from a buffer of its own, `index` (loaded once per call)."""
+
+    def load_index(self, index):
+        self.index[:index.numel()].copy_(index, non_blocking=True)
+
+
+class _GraphedPredictStep(_IndexedStep):
     """One batch of one direction as ONE hipGraph replay (a graph.Capture, like graph.GraphedEvalStep): candidate construction, the
     forward and ultra_filtered_topk.  Per batch the host copies the (bs) anchors and relations and the (bs + 1) offsets into
     the known lists of the whole call, which live in a buffer of the step (`load_index`, once per call)."""
@@ -278,17 +289,11 @@ class _GraphedPredictStep(Capture):
             args = (pred.data_ptr(), self.ptr.data_ptr() if self.filtered else None,
                     self.index.data_ptr() if self.filtered else None, batch_size, n, k, self.ids.data_ptr(),
                     self.scores.data_ptr(), self.count.data_ptr(), self.ws.data_ptr(), self.ws.numel() * 8)
-            if n_live is None:
-                _lib.check(_lib.lib.ultra_filtered_topk(*args, _lib.stream_of(dev)))
-            else:
-                _lib.check(_lib.lib.ultra_filtered_topk_live(*args, n_live.data_ptr(), _lib.stream_of(dev)))
+            _select("ultra_filtered_topk", args, n_live, dev)
 
         self.warm_up(step, warmup)
         self.capture(step)
         self.params = param_state(model)
-
-    def load_index(self, index):
-        self.index[:index.numel()].copy_(index, non_blocking=True)
 
     def __call__(self, anchor, relation, ptr):
         """(ids, scores, count) of this batch -- views of the step's buffers: copy before the next call."""
@@ -300,6 +305,13 @@ class _GraphedPredictStep(Capture):
         return self.ids, self.scores, self.count
 
 
+def _release(steps):
+    """Release every captured step of the dict `steps` and empty it."""
+    for step in steps.values():
+        step.release()
+    steps.clear()
+
+
 def _delta_route(delta):
     """What a captured step remembers of the delta it was recorded with: whether it held edits (the model's route), whether it
     held tombstones (the layers then launch ultra_rspmm_edit_rows, not _delta_rows) and which relation-graph object the relation
@@ -309,50 +321,8 @@ def _delta_route(delta):
     return (delta.edited, delta.num_removed > 0, id(delta.relation_graph))
 
 
-def _with_facts(graph, h, r, t):
-    """A copy of `graph` with the edges of the facts appended the way GraphDelta.materialize appends them: the direct edges
-    (h, t, r), then the inverse ones (t, h, r + num_relations / 2)."""
-    out = copy.copy(graph)
-    dev = graph.edge_index.device
-    h, r, t = h.to(dev), r.to(dev), t.to(dev)
-    out.edge_index = torch.cat([graph.edge_index, torch.stack([torch.cat([h, t]), torch.cat([t, h])])], dim=1)
-    out.edge_type = torch.cat([graph.edge_type, torch.cat([r, r + int(graph.num_relations) // 2])])
-    return out
-
-
-def _without_facts(graph, h, r, t):
-    """A copy of `graph` without every edge equal to (h[i], t[i], r[i]) or to (t[i], h[i], r[i] + num_relations / 2)."""
-    out = copy.copy(graph)
-    dev = graph.edge_index.device
-    h, r, t = h.to(dev), r.to(dev), t.to(dev)
-    n, rels = int(graph.num_nodes), int(graph.num_relations)
-    gone = torch.cat([(h * n + t) * rels + r, (t * n + h) * rels + r + rels // 2]).unique()
-    codes = (graph.edge_index[0] * n + graph.edge_index[1]) * rels + graph.edge_type
-    keep = gone[torch.searchsorted(gone, codes).clamp_(max=len(gone) - 1)] != codes
-    out.edge_index, out.edge_type = graph.edge_index[:, keep], graph.edge_type[keep]
-    return out
-
-
-def _with_slots(graph, slots, relation_graph=False):
-    """A shallow copy of `graph` with num_nodes = slots >= graph.num_nodes: the same edge list, the rows beyond the old count
-    reserved (no edge names them).  relation_graph: build the copy's own where `graph` carries one -- it equals graph's, a
-    node without edges plays no role."""
-    out = copy.copy(graph)
-    out.num_nodes = int(slots)
-    if relation_graph and getattr(graph, "relation_graph", None) is not None:
-        tasks.build_relation_graph(out)
-    return out
-
-
 def _entity_model(model):
     return getattr(model, "entity_model", model)
-
-
-def _check_live(ids, num_live, what):
-    """ValueError unless every id is an entity in use: ids in [0, num_live) (a graph with reserved rows; one host read)."""
-    if len(ids) and bool(((ids < 0) | (ids >= num_live)).any()):
-        raise ValueError("%s must be existing entities (ids in [0, %d)): a reserved row is no entity until add_entities hands "
-                         "it out" % (what, num_live))
 
 
 def _check_facts(data, h, r, t, num_live=None):
@@ -367,7 +337,7 @@ def _check_facts(data, h, r, t, num_live=None):
         raise ValueError("verify takes direct relations (r < num_relations // 2 = %d): a fact stated through an inverse relation "
                          "is its direct twin" % direct)
     if num_live is not None:
-        _check_live(torch.cat([h, t]), num_live, "a fact's head and tail")
+        check_live(torch.cat([h, t]), num_live, "a fact's head and tail")
     return h, r, t
 
 
@@ -405,7 +375,7 @@ def verify_reference(model, data, filter_graph, h, r, t, mode="tail"):
     return score, rank, num_negative
 
 
-class _GraphedVerifyStep(Capture):
+class _GraphedVerifyStep(_IndexedStep):
     """One batch of stated facts of one direction as ONE hipGraph replay (a graph.Capture, like _GraphedPredictStep): the
     leave-one-out keep rows from the (bs, 3) triples (ultra_leave_one_out_keep into the step's (bs, num_edge) fp32 buffer), the
     candidates, the masked forward on the full graph's cached plans, ultra_filtered_rank and the gather of the positives' scores.
@@ -435,18 +405,12 @@ class _GraphedVerifyStep(Capture):
             pos = pos.contiguous()
             args = (pred.data_ptr(), pos.data_ptr(), self.ptr.data_ptr(), self.index.data_ptr(), batch_size, n,
                     self.rank.data_ptr(), self.num_negative.data_ptr())
-            if n_live is None:
-                _lib.check(_lib.lib.ultra_filtered_rank(*args, _lib.stream_of(dev)))
-            else:
-                _lib.check(_lib.lib.ultra_filtered_rank_live(*args, n_live.data_ptr(), _lib.stream_of(dev)))
+            _select("ultra_filtered_rank", args, n_live, dev)
             self.score.copy_(pred.gather(1, pos.unsqueeze(-1)).squeeze(-1))
 
         self.warm_up(step, warmup)
         self.capture(step)
         self.params = param_state(model)
-
-    def load_index(self, index):
-        self.index[:index.numel()].copy_(index, non_blocking=True)
 
     def __call__(self, triples, ptr):
         """(score, rank, num_negative) of this batch -- views of the step's buffers: copy before the next call."""
@@ -496,44 +460,32 @@ class Predictor(object):
 
     def __init__(self, model, data, k=10, batch_size=8, filtered_data=None, filtered=True, use_graph=True, delta_capacity=256,
                  entity_capacity=0):
-        _check_k(k)
+        check_k(k)
         if filtered_data is None:
             filtered_data = getattr(data, "filtered_data", None)
-        if isinstance(entity_capacity, bool) or not isinstance(entity_capacity, int) or entity_capacity < 0:
-            raise ValueError("entity_capacity must be a non-negative int (reserved rows), got %r" % (entity_capacity,))
-        self.entity_capacity = entity_capacity
-        self.num_entities = int(data.num_nodes)
-        self.live_count = None
-        if entity_capacity:
-            slots = self.num_entities + entity_capacity
-            data = _with_slots(data, slots, relation_graph=True)
-            if filtered_data is not None:
-                filtered_data = _with_slots(filtered_data, slots)
-            self.live_count = torch.full((1,), self.num_entities, dtype=torch.long, device=data.edge_index.device)
-        self.model, self.data, self.k, self.batch_size = model, data, k, int(batch_size)
-        self.filter_graph = data if filtered_data is None else filtered_data
-        self.filtered, self.use_graph = bool(filtered), bool(use_graph)
-        self._steps = {}
-        self._eager_only = False
-        if not isinstance(delta_capacity, int) or delta_capacity < 1:
-            raise ValueError("delta_capacity must be a positive int (facts), got %r" % (delta_capacity,))
-        self.delta_capacity = delta_capacity
-        self._filter_is_data = self.filter_graph is data
-        self._filter_base = self.filter_graph
         # (a model whose forward takes no `delta` is served by compacting at every add_facts)
         try:
-            self._takes_delta = "delta" in inspect.signature(getattr(model, "forward", model)).parameters
+            takes_delta = "delta" in inspect.signature(getattr(model, "forward", model)).parameters
         except (TypeError, ValueError):
-            self._takes_delta = False
-        self.delta = self._new_delta(data) if self._takes_delta else None
+            takes_delta = False
+        self._steps = {}
+        self._eager_only = False
+        # (a rebuild drops the captures.  The hook holds the dict, not the predictor: no cycle, so __del__ runs with the last reference)
+        self._live = LiveGraph(data, delta_capacity, entity_capacity, filter_data=filtered_data, keep_filter=True,
+                               delta_policy="eager" if takes_delta else "never", owner="Predictor",
+                               on_rebuild=functools.partial(_release, self._steps))
+        self.model, self.k, self.batch_size = model, k, int(batch_size)
+        self.filtered, self.use_graph = bool(filtered), bool(use_graph)
 
-    def _new_delta(self, data, capacity=None):
-        return rspmm.GraphDelta(data, self.delta_capacity if capacity is None else capacity, num_live=self.num_entities)
-
-    @property
-    def num_slots(self):
-        """The rows of the served graph: num_entities live ones and the rest of the reserve."""
-        return int(self.data.num_nodes)
+    # ---- the state of the served graph: held by the LiveGraph ("The live graph's state in one place") ----
+    data = forwarded("graph")
+    filter_graph = forwarded("filter_graph")
+    delta = forwarded("delta")
+    entity_capacity = forwarded("entity_capacity")
+    delta_capacity = forwarded("delta_capacity")
+    num_entities = forwarded("num_entities")
+    num_slots = forwarded("num_slots")
+    live_count = forwarded("live_count")
 
     # ---- the growing graph ----
     def add_entities(self, count=1):
@@ -543,29 +495,13 @@ class Predictor(object):
         as an isolated node, and add_facts / remove_facts / tails / heads / ... take its id.  Beyond the reserve the graph is
         compacted and num_entities + count + entity_capacity slots are laid out: one rebuild.  ValueError on a predictor
         without a reserve (entity_capacity=0)."""
-        if not self.entity_capacity:
-            raise ValueError("this Predictor reserves no rows: create it with entity_capacity > 0 to add entities")
-        if isinstance(count, bool) or not isinstance(count, int) or count < 1:
-            raise ValueError("count must be a positive int, got %r" % (count,))
-        first = self.num_entities
-        if first + count > self.num_slots:
-            self.compact(slots=first + count + self.entity_capacity)
-        self.num_entities = first + count
-        self.live_count.fill_(self.num_entities)
-        if self.delta is not None:
-            self.delta.num_live = self.num_entities
-        return torch.arange(first, first + count, dtype=torch.long, device=self.data.edge_index.device)
+        return self._live.add_entities(count, compact=self.compact)
 
     def materialized(self):
         """The graph a fresh Predictor would be given for the same answers: the served edge list with the delta's edits
         (GraphDelta.materialize) and num_nodes = num_entities -- no reserved row -- with the filter graph held now as its
         `filtered_data` where that is a graph of its own.  A new copy at every call."""
-        probe = self.delta if self.delta is not None else self._new_delta(self.data, 1)
-        out = copy.copy(probe.materialize(self.data, num_nodes=self.num_entities))
-        if not self._filter_is_data:        # (a separate filter graph: the one held now, the stated facts included)
-            out.filtered_data = copy.copy(self.filter_graph)
-            out.filtered_data.num_nodes = self.num_entities
-        return out
+        return self._live.materialized()
 
     # ---- the live graph ----
     def add_facts(self, h, r, t):
@@ -573,53 +509,14 @@ class Predictor(object):
         otherwise: the sets of entities and relations are fixed).  Each adds the edges (h, t, r) and (t, h, r + num_relations / 2)
         to the served graph and to the filter graph; a repeated fact is one more parallel edge.  Returns the number of facts the
         delta holds afterwards (0 after a compaction: more facts than delta_capacity, or a model without a delta route)."""
-        probe = self.delta if self.delta is not None else self._new_delta(self.data, 1)
-        h, r, t = probe.check(h, r, t)
-        if len(h) == 0:
-            return 0 if self.delta is None else len(self.delta)
-        if self.delta is None or 2 * (len(self.delta) + len(h)) + self.delta.num_removed > 2 * self.delta_capacity:
-            self.compact(extra=(h, r, t))
-            return 0
-        self.delta.add(h, r, t)
-        self._refresh_filter_graph()
-        return len(self.delta)
+        return self._live.add_facts(h, r, t)
 
     def remove_facts(self, h, r, t):
         """Retract the facts (h[i], r[i], t[i]) -- the argument rules of add_facts -- one after the other: every edge equal to
         (h, t, r) or (t, h, r + num_relations / 2) leaves the served graph and the filter graph (a fact stated nowhere is a
         no-op).  Returns an int64 vector: the number of direct edges each fact took out of the served graph
         (GraphDelta.remove).  Compacts first where the delta cannot hold the tombstones."""
-        probe = self.delta if self.delta is not None else self._new_delta(self.data, 1)
-        h, r, t = probe.check(h, r, t)
-        if len(h) == 0:
-            return torch.zeros(0, dtype=torch.long, device=h.device)
-        # (every retraction holds at most two keys: a call that may not fit compacts first, and one larger than the whole capacity is
-        # applied to a delta of its own and folded at once)
-        fits = lambda: self.delta is not None and \
-            2 * (len(self.delta) + len(h)) + self.delta.num_removed <= 2 * self.delta_capacity
-        fold = None
-        if not fits():
-            self.compact()
-        if fits():
-            removed = self.delta.remove(h, r, t)
-        else:
-            fold = self._new_delta(self.data, len(h))
-            removed = fold.remove(h, r, t)
-        if not self._filter_is_data:
-            self._filter_base = _without_facts(self._filter_base, h, r, t)
-        if fold is not None:
-            self.compact(delta=fold)
-        self._refresh_filter_graph()
-        return removed
-
-    def _refresh_filter_graph(self):
-        if self.delta is None:
-            self.filter_graph = self._filter_base
-        elif self._filter_is_data:
-            self.filter_graph = self.delta.materialize(self.data)
-        else:
-            fh, fr, ft = self.delta.facts[:len(self.delta)].unbind(1)
-            self.filter_graph = _with_facts(self._filter_base, fh, fr, ft)
+        return self._live.remove_facts(h, r, t)
 
     def compact(self, extra=None, delta=None, slots=None):
         """Fold the delta's edits (and `extra` = (h, r, t), checked by the caller) into `data`: the materialised graph -- without
@@ -627,46 +524,11 @@ class Predictor(object):
         next query, new captures -- and the delta is emptied.  `delta`: fold that one instead of the Predictor's own.  The
         slot count and the live count of a graph with reserved rows stay; `slots` (add_entities beyond the reserve): the new
         slot count, laid out in the same rebuild."""
-        delta = self.delta if delta is None else delta
-        facts = [] if delta is None else [delta.facts[:len(delta)]]
-        if extra is not None:
-            facts.append(torch.stack(list(extra), dim=1))
-        facts = torch.cat(facts) if facts else torch.zeros(0, 3, dtype=torch.long)
-        if slots is not None and int(slots) == self.num_slots:
-            slots = None
-        if len(facts) == 0 and not (delta is not None and delta.num_removed) and slots is None:
-            return
-        fh, fr, ft = facts.unbind(1)
-        base = self.data
-        if delta is not None and delta.num_removed:
-            base = copy.copy(self.data)
-            base.edge_index, base.edge_type = delta.surviving(self.data.edge_index, self.data.edge_type)
-        data = _with_facts(base, fh, fr, ft)
-        if slots is not None:
-            data.num_nodes = int(slots)
-        if getattr(self.data, "relation_graph", None) is not None:
-            tasks.build_relation_graph(data)
-        if self._filter_is_data:
-            self._filter_base = data
-        else:
-            self._filter_base = _with_facts(self._filter_base, fh, fr, ft)
-            if slots is not None:
-                self._filter_base.num_nodes = int(slots)
-        self.filter_graph = self._filter_base
-        self.close()
-        self.data = data
-        if self._takes_delta:
-            self.delta = self._new_delta(data)
+        self._live.compact(extra, delta, slots)
 
     def _model_kwargs(self):
-        return {} if self.delta is None else {"delta": self.delta}
-
-    def _select_kwargs(self, pred):
-        """What the eager selection takes beside today's arguments: nothing without a reserve; with one, the live count -- the
-        device scalar for the kernels, the host int for the plain-torch restatements."""
-        if not self.entity_capacity:
-            return {}
-        return {"num_live": self.live_count if pred.is_cuda else self.num_entities}
+        delta = self.delta      # (handed over whenever it exists, empty or not: the capture relies on it)
+        return {} if delta is None else {"delta": delta}
 
     def tails(self, h, r):
         return self._run(h, r, "tail")
@@ -742,9 +604,7 @@ class Predictor(object):
 
     def close(self):
         """Drop the captured steps (their plans are unpinned)."""
-        for step in self._steps.values():
-            step.release()
-        self._steps = {}
+        _release(self._steps)
 
     def __del__(self):
         try:
@@ -785,7 +645,7 @@ class Predictor(object):
         h, r, t = _check_facts(self.data, h, r, t, num_live=self.num_entities if self.entity_capacity else None)
         if self.delta is not None and self.delta.edited:
             self.compact()      # (the keep masks run over the graph's own edge list: the edits become part of it first)
-        data, bs = self.data, self.batch_size
+        data, bs, live_count = self.data, self.batch_size, self.live_count
         dev = h.device
         n = len(h)
         score = torch.empty(n, dtype=torch.float32, device=dev)
@@ -830,10 +690,7 @@ class Predictor(object):
                 b_rank, b_neg = torch.empty_like(pos), torch.empty_like(pos)
                 args = (pred.data_ptr(), pos.data_ptr(), b_ptr.data_ptr(), index.data_ptr(), len(part), pred.shape[1],
                         b_rank.data_ptr(), b_neg.data_ptr())
-                if self.live_count is None:
-                    _lib.check(_lib.lib.ultra_filtered_rank(*args, _lib.stream_of(dev)))
-                else:
-                    _lib.check(_lib.lib.ultra_filtered_rank_live(*args, self.live_count.data_ptr(), _lib.stream_of(dev)))
+                _select("ultra_filtered_rank", args, live_count, dev)
                 score[lo:lo + len(part)] = pred.gather(1, pos.unsqueeze(-1)).squeeze(-1)
                 rank[lo:lo + len(part)], num_negative[lo:lo + len(part)] = b_rank, b_neg
         finally:
@@ -843,14 +700,14 @@ class Predictor(object):
     @torch.no_grad()
     def _run_above(self, anchor, relation, min_score, mode):
         threshold = _fp32_threshold(min_score)
-        data, bs = self.data, self.batch_size
+        data, bs, live, model_kwargs = self.data, self.batch_size, self._live, self._model_kwargs()
         dev = data.edge_index.device
         anchor = torch.as_tensor(anchor, dtype=torch.long, device=dev).flatten()
         relation = torch.as_tensor(relation, dtype=torch.long, device=dev).flatten()
         if anchor.shape != relation.shape:
             raise ValueError("one relation per query: got %d entities and %d relations" % (len(anchor), len(relation)))
         if self.entity_capacity:
-            _check_live(anchor, self.num_entities, "the anchors of a query")
+            check_live(anchor, self.num_entities, "the anchors of a query")
         n = len(anchor)
         out_ptr, ids, scores, size = [torch.zeros(1, dtype=torch.long, device=dev)], [], [], []
         was_training = self.model.training
@@ -862,15 +719,15 @@ class Predictor(object):
             at = 0
             for lo in range(0, n, bs):
                 pred = self.model(data, _candidates(data, anchor[lo:lo + bs], relation[lo:lo + bs], mode),
-                                  **self._model_kwargs()).float()
+                                  **model_kwargs).float()
                 b_ptr = None if ptr is None else ptr[lo:lo + len(pred) + 1]
                 if pred.is_cuda:
-                    b_out, b_ids, b_scores, b_size = filtered_above(pred, threshold, b_ptr, index, **self._select_kwargs(pred))
+                    b_out, b_ids, b_scores, b_size = filtered_above(pred, threshold, b_ptr, index, **live.num_live_for(pred.is_cuda))
                     total = int(b_out[-1])      # (the one host read of the batch)
                     b_ids, b_scores = b_ids[:total].clone(), b_scores[:total].clone()
                 else:
                     b_out, b_ids, b_scores, b_size = filtered_above_reference(pred, threshold, b_ptr, index,
-                                                                              **self._select_kwargs(pred))
+                                                                              **live.num_live_for(pred.is_cuda))
                     total = b_ids.numel()
                 out_ptr.append(b_out[1:] + at)
                 ids.append(b_ids)
@@ -886,14 +743,14 @@ class Predictor(object):
 
     @torch.no_grad()
     def _run(self, anchor, relation, mode):
-        data, bs, k = self.data, self.batch_size, self.k
+        data, bs, k, live, model_kwargs = self.data, self.batch_size, self.k, self._live, self._model_kwargs()
         dev = data.edge_index.device
         anchor = torch.as_tensor(anchor, dtype=torch.long, device=dev).flatten()
         relation = torch.as_tensor(relation, dtype=torch.long, device=dev).flatten()
         if anchor.shape != relation.shape:
             raise ValueError("one relation per query: got %d entities and %d relations" % (len(anchor), len(relation)))
         if self.entity_capacity:
-            _check_live(anchor, self.num_entities, "the anchors of a query")
+            check_live(anchor, self.num_entities, "the anchors of a query")
         n = len(anchor)
         ids = torch.empty(n, k, dtype=torch.long, device=dev)
         scores = torch.empty(n, k, dtype=torch.float32, device=dev)
@@ -932,11 +789,11 @@ class Predictor(object):
                     self._eager_only = True
             for lo in range(start, n, bs):
                 pred = self.model(data, _candidates(data, anchor[lo:lo + bs], relation[lo:lo + bs], mode),
-                                  **self._model_kwargs()).float()
+                                  **model_kwargs).float()
                 b_ptr = None if ptr is None else ptr[lo:lo + len(pred) + 1]
                 # the fused kernel on the GPU; the restatement with the same interface elsewhere (as eval._local_rows does)
                 select = filtered_topk if pred.is_cuda else filtered_topk_reference
-                b_ids, b_scores, b_count = select(pred, k, b_ptr, index, **self._select_kwargs(pred))
+                b_ids, b_scores, b_count = select(pred, k, b_ptr, index, **live.num_live_for(pred.is_cuda))
                 ids[lo:lo + len(pred)], scores[lo:lo + len(pred)], count[lo:lo + len(pred)] = b_ids, b_scores, b_count
         finally:
             self.model.train(was_training)

@@ -19,11 +19,12 @@ A GROWING graph: QueryPredictor(entity_capacity=M) reserves M r
 (ultra_nonzero_lists_live: after a negation every reserved slot holds 1.0) and the selection runs over them
 (ultra_filtered_topk_live / ultra_filtered_above_live).
 """
-import copy
+import contextlib
 
 import torch
 
-from . import predict, query_exec, rspmm, tasks
+from . import predict, query_exec
+from .live import LiveGraph, forwarded
 from .ultraquery import Query, _logic
 
 
@@ -40,41 +41,28 @@ class QueryPredictor(object):
     served, by exactly the entry points of before, and add_entities raises."""
 
     def __init__(self, model, graph, k=10, batch_size=16, filtered=True, logic=None, delta_capacity=256, entity_capacity=0):
-        predict._check_k(k)
-        if isinstance(entity_capacity, bool) or not isinstance(entity_capacity, int) or entity_capacity < 0:
-            raise ValueError("entity_capacity must be a non-negative int (reserved rows), got %r" % (entity_capacity,))
-        if isinstance(delta_capacity, bool) or not isinstance(delta_capacity, int) or delta_capacity < 1:
-            raise ValueError("delta_capacity must be a positive int (facts), got %r" % (delta_capacity,))
+        predict.check_k(k)
         if int(batch_size) < 1:
             raise ValueError("batch_size must be positive, got %r" % (batch_size,))
         if logic is not None:
             _logic(logic)
-        self.entity_capacity = entity_capacity
-        self.num_entities = int(graph.num_nodes)
-        self.live_count = None
-        if entity_capacity:
-            graph = predict._with_slots(graph, self.num_entities + entity_capacity, relation_graph=True)
-            self.live_count = torch.full((1,), self.num_entities, dtype=torch.long, device=graph.edge_index.device)
-        self.model, self.graph, self.k, self.batch_size = model, graph, k, int(batch_size)
+        # (the delta is made at the first edit: a predictor that was never edited runs exactly what it ran before.  There is no
+        # filter graph: the entailed answers come from the symbolic traversal of the same run)
+        self._live = LiveGraph(graph, delta_capacity, entity_capacity, delta_policy="lazy", owner="QueryPredictor")
+        self.model, self.k, self.batch_size = model, k, int(batch_size)
         self.filtered, self.logic = bool(filtered), logic
         self._executor = query_exec.Executor()
-        self.delta_capacity = delta_capacity
-        self.delta = None       # made at the first edit: a predictor that was never edited runs exactly what it ran before
 
-    # ---- the live graph (the rules of Predictor.add_facts / remove_facts; there is no separate filter graph: the entailed
-    # answers come from the symbolic traversal of the same run) ----
-    def _new_delta(self, capacity=None):
-        capacity = self.delta_capacity if capacity is None else capacity
-        if not self.entity_capacity:
-            return rspmm.GraphDelta(self.graph, capacity)
-        return rspmm.GraphDelta(self.graph, capacity, num_live=self.num_entities)
+    # ---- the state of the served graph: held by the LiveGraph (DESIGN.md, "The live graph's state in one place") ----
+    graph = forwarded("graph")
+    delta = forwarded("delta")
+    entity_capacity = forwarded("entity_capacity")
+    delta_capacity = forwarded("delta_capacity")
+    num_entities = forwarded("num_entities")
+    num_slots = forwarded("num_slots")
+    live_count = forwarded("live_count")
 
     # ---- the growing graph (the rules of Predictor.add_entities) ----
-    @property
-    def num_slots(self):
-        """The rows of the served graph: num_entities live ones and the rest of the reserve."""
-        return int(self.graph.num_nodes)
-
     def add_entities(self, count=1):
         """`count` new entities: returns their ids [num_entities, num_entities + count) (int64, on the graph's device) and raises
         the live count -- the host int, the device scalar the kernels read and the delta's bound.  Nothing else happens: no plan,
@@ -82,107 +70,42 @@ class QueryPredictor(object):
         on, scored as an isolated node, and add_facts / remove_facts / the anchors of a query take its id.  Beyond the reserve
         the graph is compacted and num_entities + count + entity_capacity slots are laid out: one rebuild.  ValueError on a
         predictor without a reserve (entity_capacity=0)."""
-        if not self.entity_capacity:
-            raise ValueError("this QueryPredictor reserves no rows: create it with entity_capacity > 0 to add entities")
-        if isinstance(count, bool) or not isinstance(count, int) or count < 1:
-            raise ValueError("count must be a positive int, got %r" % (count,))
-        first = self.num_entities
-        if first + count > self.num_slots:
-            self.compact(slots=first + count + self.entity_capacity)
-        self.num_entities = first + count
-        self.live_count.fill_(self.num_entities)
-        if self.delta is not None:
-            self.delta.num_live = self.num_entities
-        return torch.arange(first, first + count, dtype=torch.long, device=self.graph.edge_index.device)
+        return self._live.add_entities(count, compact=self.compact)
 
-    def _fits(self, n):
-        held = 0 if self.delta is None else 2 * len(self.delta) + self.delta.num_removed
-        return held + 2 * n <= 2 * self.delta_capacity
-
+    # ---- the live graph (the rules of Predictor.add_facts / remove_facts) ----
     def add_facts(self, h, r, t):
         """State the facts (h[i], r[i], t[i]) -- ints or vectors; r direct relations, h and t existing entities (ValueError
         otherwise).  Each adds the edges (h, t, r) and (t, h, r + num_relations / 2) to the served graph: the projections
         traverse them and the symbolic side entails through them from the next call on.  Returns the number of facts the
         delta holds afterwards (0 after a compaction: more edits than delta_capacity)."""
-        probe = self.delta if self.delta is not None else self._new_delta(1)
-        h, r, t = probe.check(h, r, t)
-        if len(h) == 0:
-            return 0 if self.delta is None else len(self.delta)
-        if not self._fits(len(h)):
-            self.compact(extra=(h, r, t))
-            return 0
-        if self.delta is None:
-            self.delta = self._new_delta()
-        self.delta.add(h, r, t)
-        return len(self.delta)
+        return self._live.add_facts(h, r, t)
 
     def remove_facts(self, h, r, t):
         """Retract the facts (h[i], r[i], t[i]) -- the argument rules of add_facts -- one after the other: every edge equal to
         (h, t, r) or (t, h, r + num_relations / 2) leaves the served graph (a fact stated nowhere is a no-op).  Returns an
         int64 vector: the number of direct edges each fact took out (GraphDelta.remove).  A call that may not fit compacts
         first; one larger than the whole capacity is applied to a delta of its own and folded at once."""
-        probe = self.delta if self.delta is not None else self._new_delta(1)
-        h, r, t = probe.check(h, r, t)
-        if len(h) == 0:
-            return torch.zeros(0, dtype=torch.long, device=h.device)
-        if not self._fits(len(h)):
-            self.compact()
-        if self._fits(len(h)):
-            if self.delta is None:
-                self.delta = self._new_delta()
-            return self.delta.remove(h, r, t)
-        fold = self._new_delta(len(h))
-        removed = fold.remove(h, r, t)
-        self.compact(delta=fold)
-        return removed
+        return self._live.remove_facts(h, r, t)
 
     def compact(self, extra=None, delta=None, slots=None):
         """Fold the delta's edits (and `extra` = (h, r, t), checked by the caller) into the served graph: the materialised graph
         -- its relation graph rebuilt; a host plan and a traversal CSR on the next query -- becomes `graph`, and the delta is
         emptied.  `delta`: fold that one instead of the predictor's own.  The slot count and the live count of a graph with
         reserved rows stay; `slots` (add_entities beyond the reserve): the new slot count, laid out in the same rebuild."""
-        delta = self.delta if delta is None else delta
-        facts = [] if delta is None else [delta.facts[:len(delta)]]
-        if extra is not None:
-            facts.append(torch.stack(list(extra), dim=1))
-        facts = torch.cat(facts) if facts else torch.zeros(0, 3, dtype=torch.long)
-        if slots is not None and int(slots) == self.num_slots:
-            slots = None
-        if len(facts) == 0 and not (delta is not None and delta.num_removed) and slots is None:
-            return
-        fh, fr, ft = facts.unbind(1)
-        base = self.graph
-        if delta is not None and delta.num_removed:
-            base = copy.copy(self.graph)
-            base.edge_index, base.edge_type = delta.surviving(self.graph.edge_index, self.graph.edge_type)
-        graph = predict._with_facts(base, fh, fr, ft)
-        if slots is not None:
-            graph.num_nodes = int(slots)
-        if getattr(self.graph, "relation_graph", None) is not None:
-            tasks.build_relation_graph(graph)
-        self.graph = graph
-        self.delta = None
+        self._live.compact(extra, delta, slots)
 
     def materialized(self):
         """The graph a fresh QueryPredictor would be given for the same answers: the served edge list with the delta's edits and
         the delta's relation graph (GraphDelta.materialize); the served graph itself where no edit is held.  With a reserve:
         num_nodes = num_entities -- no reserved row -- and a new copy at every call."""
         if self.entity_capacity:
-            probe = self.delta if self.delta is not None else self._new_delta(1)
-            return copy.copy(probe.materialize(self.graph, num_nodes=self.num_entities))
-        if self.delta is None or not self.delta.edited:
-            return self.graph
-        return self.delta.materialize(self.graph)
+            return self._live.materialized()
+        delta = self.delta
+        return self.graph if delta is None or not delta.edited else delta.materialize(self.graph)
 
     def _delta_kwargs(self):
-        return {"delta": self.delta} if self.delta is not None and self.delta.edited else {}
-
-    def _live_kwargs(self, on_gpu):
-        """What the lists and the selection take beside today's arguments: nothing without a reserve; with one, the live count --
-        the device scalar for the kernels, the host int for the plain-torch restatements."""
-        if not self.entity_capacity:
-            return {}
-        return {"num_live": self.live_count if on_gpu else self.num_entities}
+        delta = self.delta      # (handed over only while it holds edits)
+        return {"delta": delta} if delta is not None and delta.edited else {}
 
     def _known_reference(self, sym, rows):
         """(ptr, index) of the final symbolic sets in plain torch (the CPU route): the non-zero LIVE ids of every row."""
@@ -225,6 +148,34 @@ class QueryPredictor(object):
         """The index lists of the batches `answers` runs, in the order it runs them."""
         return [index for index, _ in self._programs(queries)]
 
+    @contextlib.contextmanager
+    def _batches(self, plan):
+        """The batches of `plan` (_programs) as answers and answer_sets run them: inside the block the model is in eval mode
+        under this predictor's logic (both restored on the way out), and the value is an iterator of (index, logits, ptr, known,
+        live) -- the batch's query indices, its logits from the compiled executor, the lists of its entailed answers (None, None
+        unless filtered) and the live-count kwargs of the selection."""
+        graph, live_graph, delta_kwargs = self.graph, self._live, self._delta_kwargs()
+
+        def run():
+            for index, program in plan:
+                logits, sym = query_exec.execute(self.model, graph, program, symbolic_traversal=self.filtered,
+                                                 executor=self._executor, **delta_kwargs)
+                live = live_graph.num_live_for(logits.is_cuda)
+                ptr = known = None
+                if self.filtered:
+                    ptr, known = query_exec.nonzero_lists(sym, **live) if logits.is_cuda else self._known_reference(sym, len(index))
+                yield index, logits, ptr, known, live
+
+        was_training, logic = self.model.training, self.model.logic
+        self.model.eval()
+        if self.logic is not None:
+            self.model.logic = self.logic
+        try:
+            yield run()
+        finally:
+            self.model.train(was_training)
+            self.model.logic = logic
+
     @torch.no_grad()
     def answers(self, queries):
         dev = self.graph.edge_index.device
@@ -233,29 +184,12 @@ class QueryPredictor(object):
         ids = torch.empty(n, k, dtype=torch.long, device=dev)
         scores = torch.empty(n, k, dtype=torch.float32, device=dev)
         count = torch.empty(n, dtype=torch.long, device=dev)
-        was_training, logic = self.model.training, self.model.logic
-        self.model.eval()
-        if self.logic is not None:
-            self.model.logic = self.logic
-        try:
-            for index, program in plan:
-                logits, sym = query_exec.execute(self.model, self.graph, program, symbolic_traversal=self.filtered,
-                                                 executor=self._executor, **self._delta_kwargs())
-                ptr = known = None
-                live = self._live_kwargs(logits.is_cuda)
-                if logits.is_cuda:
-                    if self.filtered:
-                        ptr, known = query_exec.nonzero_lists(sym, **live)
-                    got = predict.filtered_topk(logits, k, ptr, known, **live)
-                else:
-                    if self.filtered:
-                        ptr, known = self._known_reference(sym, len(index))
-                    got = predict.filtered_topk_reference(logits, k, ptr, known, **live)
+        with self._batches(plan) as batches:
+            for index, logits, ptr, known, live in batches:
+                select = predict.filtered_topk if logits.is_cuda else predict.filtered_topk_reference
+                got = select(logits, k, ptr, known, **live)
                 where = torch.tensor(index, dtype=torch.long).to(dev, non_blocking=True)
                 ids[where], scores[where], count[where] = got
-        finally:
-            self.model.train(was_training)
-            self.model.logic = logic
         return ids, scores, count
 
     @torch.no_grad()
@@ -275,32 +209,17 @@ class QueryPredictor(object):
         length = torch.zeros(n, dtype=torch.long, device=dev)
         size = torch.zeros(n, dtype=torch.long, device=dev)
         done = []
-        was_training, logic = self.model.training, self.model.logic
-        self.model.eval()
-        if self.logic is not None:
-            self.model.logic = self.logic
-        try:
-            for index, program in plan:
-                logits, sym = query_exec.execute(self.model, self.graph, program, symbolic_traversal=self.filtered,
-                                                 executor=self._executor, **self._delta_kwargs())
-                ptr = known = None
-                live = self._live_kwargs(logits.is_cuda)
+        with self._batches(plan) as batches:
+            for index, logits, ptr, known, live in batches:
                 if logits.is_cuda:
-                    if self.filtered:
-                        ptr, known = query_exec.nonzero_lists(sym, **live)
                     b_ptr, b_ids, b_scores, b_size = predict.filtered_above(logits, threshold, ptr, known, **live)
                     total = int(b_ptr[-1])      # (the one host read of the batch)
                     b_ids, b_scores = b_ids[:total].clone(), b_scores[:total].clone()
                 else:
-                    if self.filtered:
-                        ptr, known = self._known_reference(sym, len(index))
                     b_ptr, b_ids, b_scores, b_size = predict.filtered_above_reference(logits, threshold, ptr, known, **live)
                 where = torch.tensor(index, dtype=torch.long).to(dev, non_blocking=True)
                 length[where], size[where] = b_ptr[1:] - b_ptr[:-1], b_size
                 done.append((where, b_ptr, b_ids, b_scores))
-        finally:
-            self.model.train(was_training)
-            self.model.logic = logic
         # the lists of every batch, moved to where the input order puts them
         out_ptr = torch.zeros(n + 1, dtype=torch.long, device=dev)
         out_ptr[1:] = length.cumsum(0)
