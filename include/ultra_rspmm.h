@@ -256,7 +256,8 @@ int32_t ultra_rspmm_forward_point(ultra_plan *plan, int32_t sum, int32_t mul, in
  * Served: fp32 / fp64, add / min / max, mul / add messages, unit edge weights, reference-order plans in the sparse format, rows
  * that are whole 16-byte chunks at 16-byte aligned addresses and strides.  General-walk and dense-format plans, rotate messages
  * and misaligned rows: ULTRA_ERR_UNSUPPORTED with nothing launched (weighted or masked calls have no argument here: the caller
- * does not combine them with a delta).  Invalid arguments: ULTRA_ERR_INVALID.  capacity_rows == 0 or n_outer == 0: ULTRA_OK.
+ * does not combine them with a delta, but for the per-sample keep rows of leave-one-out verification, whose touched rows
+ * ultra_rspmm_edit_rows_samples below recomputes).  Invalid arguments: ULTRA_ERR_INVALID.  capacity_rows == 0 or n_outer == 0: ULTRA_OK.
  * The caller keeps every index of the delta inside the plan's num_out_row / num_in_row / num_relation; an index outside is never
  * dereferenced (its edge is left out, a touched row outside is not written).
  */
@@ -292,6 +293,34 @@ typedef struct {
 int32_t ultra_rspmm_edit_rows(ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const ultra_mat *relation,
                               const ultra_mat *input, const ultra_mat *boundary, const int64_t *point_rows_dev,
                               const ultra_mat *output, const ultra_delta *delta, const ultra_tombstones *removed, void *stream);
+
+/*
+ * ultra_rspmm_edit_rows with dead keys PER OUTER SLICE (csrc/delta_kernels.hip): leave-one-out verification of
+ * stated facts on a graph that holds edits, without folding the edits into the plan first.
+ *   keys->row_dev / col_dev / type_dev  int32 [n_outer * per_sample]: slice s owns [s * per_sample, (s + 1) * per_sample)
+ *   keys->per_sample                    1 .. 8
+ * Touched row k of outer slice s is recomputed as ultra_rspmm_edit_rows recomputes it, where an edge (row, col, type) -- a base
+ * edge OR one of the delta's own -- takes no part in slice s if one of that slice's keys has key.row == row, key.col == col and
+ * (key.type < 0 || key.type == type).  A negative type matches every type (the `remove_one_hop` form); all duplicates go; a key
+ * that matches nothing changes nothing.  Tombstones keep their meaning (base edges only); removed == NULL: none.  A row left
+ * with no surviving edge in some slice holds the edge-less-row value of ultra_rspmm_edit_rows in that slice, and only there.
+ * On ULTRA_PLAN_EXACT_ORDER plans slice s of the touched rows equals ultra_rspmm_forward on a fresh reference-order plan of
+ * [base edges without the tombstoned ones and without slice s's dead ones ; delta edges without slice s's dead ones], bit for
+ * bit (a subsequence of a sorted row is still sorted).  The rows no edit points into are not written: the caller computes them
+ * with ultra_rspmm_forward_masked_samples, whose keep rows leave the same base edges out.
+ * A group first filters its slice's keys down to those that name its row, into registers; a group with none walks at the cost
+ * of ultra_rspmm_edit_rows.  A key is only compared, never used as an index.  Grid, capture, served cases and
+ * ULTRA_ERR_UNSUPPORTED are those of ultra_rspmm_edit_rows.  keys == NULL or per_sample outside 1 .. 8: ULTRA_ERR_INVALID
+ * before any pointer is read.
+ */
+typedef struct {
+    const int32_t *row_dev, *col_dev, *type_dev;
+    int64_t per_sample;
+} ultra_sample_keys;
+int32_t ultra_rspmm_edit_rows_samples(ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const ultra_mat *relation,
+                                      const ultra_mat *input, const ultra_mat *boundary, const int64_t *point_rows_dev,
+                                      const ultra_mat *output, const ultra_delta *delta, const ultra_tombstones *removed,
+                                      const ultra_sample_keys *keys, void *stream);
 
 /*
  * Aggregate + layer update in ONE launch (fp32 inference path of GeneralizedRelationalConv.forward,

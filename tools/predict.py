@@ -24,7 +24,9 @@ by its name.  It is applied in command-line order with the fact options.
 --verify judges facts the dataset may already state: every (head, relation, tail) -- one from the command line, or the
 `head relation tail` lines of FILE -- is scored on the graph WITHOUT itself and its inverse edge (Predictor.verify_tails; with
 --inverse the head is the answer judged, Predictor.verify_heads) and printed with its score, its filtered rank and the number
-of candidates it was ranked among.
+of candidates it was ranked among.  With --add-fact / --remove-fact / --add-entity the facts are judged on the EDITED graph -- a
+fact that was just stated is judged without itself -- and without --add-entity the edits stay a delta beside the cached plan
+(with reserved rows they are folded into the graph first).
 """
 import argparse
 import os
@@ -92,8 +94,6 @@ def main(argv=None):
         if any(len(f) != 3 for f in facts):
             sys.exit("--triples: every line is `head relation tail`")
     new_names = [name for kind, name in args.edits if kind is None]
-    if facts is not None and new_names:
-        sys.exit("--add-entity serves queries, not --verify")
     if args.entity_capacity is not None and args.entity_capacity < 0:
         sys.exit("--entity-capacity must not be negative")
     known = set(ent)        # (grows along the command line: a name can be used after its --add-entity)
@@ -120,17 +120,11 @@ def main(argv=None):
     else:
         print("no --ckpt: randomly initialised weights, the answers mean nothing")
     model = model.to(dev).eval()
-    if facts is not None:
-        predictor = predict.Predictor(model, data, batch_size=min(8, len(facts)))
-        h, r, t = (torch.tensor([vocab.index(f[i]) for f in facts], device=dev) for i, vocab in ((0, ent), (1, rel), (2, ent)))
-        score, rank, num_negative = (predictor.verify_heads if args.inverse else predictor.verify_tails)(h, r, t)
-        print("%s judged on the graph without the fact itself: score, filtered rank / candidates"
-              % ("heads" if args.inverse else "tails"))
-        for f, s, k, n in zip(facts, score.tolist(), rank.tolist(), num_negative.tolist()):
-            print("%-28s %-24s %-28s %12.6g  %6d / %d" % (f[0], f[1], f[2], s, k, n + 1))
-        return
     reserve = len(new_names) if args.entity_capacity is None else args.entity_capacity
-    predictor = predict.Predictor(model, data, k=args.k, batch_size=1, filtered=not args.unfiltered, entity_capacity=reserve)
+    if facts is not None:
+        predictor = predict.Predictor(model, data, batch_size=min(8, len(facts)), entity_capacity=reserve)
+    else:
+        predictor = predict.Predictor(model, data, k=args.k, batch_size=1, filtered=not args.unfiltered, entity_capacity=reserve)
     ent = list(ent)
     at = 0
     while at < len(args.edits):        # (runs of one kind go in one call)
@@ -155,6 +149,15 @@ def main(argv=None):
             took = predictor.remove_facts(*ids).tolist()
             print("%d fact(s) retracted from the dataset: %s edge(s) removed" % (len(run), " + ".join(str(n) for n in took)))
         at = end
+    if facts is not None:
+        # (the edits above stay a delta beside the cached plan: every fact is judged on the edited graph without itself)
+        h, r, t = (torch.tensor([vocab.index(f[i]) for f in facts], device=dev) for i, vocab in ((0, ent), (1, rel), (2, ent)))
+        score, rank, num_negative = (predictor.verify_heads if args.inverse else predictor.verify_tails)(h, r, t)
+        print("%s judged on the graph without the fact itself: score, filtered rank / candidates"
+              % ("heads" if args.inverse else "tails"))
+        for f, s, k, n in zip(facts, score.tolist(), rank.tolist(), num_negative.tolist()):
+            print("%-28s %-24s %-28s %12.6g  %6d / %d" % (f[0], f[1], f[2], s, k, n + 1))
+        return
     anchor = torch.tensor([ent.index(args.head)], device=dev)
     relation = torch.tensor([rel.index(args.relation)], device=dev)
     why = None

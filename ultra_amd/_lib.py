@@ -62,6 +62,13 @@ class UltraTombstones(ctypes.Structure):
                 ("capacity_keys", ctypes.c_int64)]
 
 
+class UltraSampleKeys(ctypes.Structure):
+    """ultra_sample_keys: per outer slice the (row, col, type) keys of the edges that slice must not see
+    (ultra_rspmm_edit_rows_samples)."""
+    _fields_ = [("row_dev", ctypes.c_void_p), ("col_dev", ctypes.c_void_p), ("type_dev", ctypes.c_void_p),
+                ("per_sample", ctypes.c_int64)]
+
+
 class UltraTraversalEdits(ctypes.Structure):
     """ultra_traversal_edits: a graph delta in the symbolic traversal's direction (include/ultra_nbfnet.h,
     ultra_symbolic_traversal_edit_rows)."""
@@ -121,6 +128,8 @@ def _load():
     lib.ultra_rspmm_delta_rows.argtypes = [vp, i32, i32, i32, matp, matp, matp, vp, matp, ctypes.POINTER(UltraDelta), vp]
     lib.ultra_rspmm_edit_rows.argtypes = [vp, i32, i32, i32, matp, matp, matp, vp, matp, ctypes.POINTER(UltraDelta),
                                           ctypes.POINTER(UltraTombstones), vp]
+    lib.ultra_rspmm_edit_rows_samples.argtypes = [vp, i32, i32, i32, matp, matp, matp, vp, matp, ctypes.POINTER(UltraDelta),
+                                                  ctypes.POINTER(UltraTombstones), ctypes.POINTER(UltraSampleKeys), vp]
     lib.ultra_rspmm_forward_onehot.argtypes = [vp, i32, vp, matp, matp, vp, matp, matp, vp]
     lib.ultra_rspmm_forward_point.argtypes = [vp, i32, i32, i32, vp, matp, matp, vp, matp, matp, vp]
     lib.ultra_rspmm_forward_update.argtypes = [vp, i32, i32, matp, matp, vp, matp, matp, vp, vp, vp, vp, ctypes.c_float, i32, matp, vp]

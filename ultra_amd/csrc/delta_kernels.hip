@@ -26,6 +26,12 @@
 // writes for an edge-less row: the reduction's start value (0; the largest / lowest finite number under min / max, NaryOp::zero
 // of the reference, never an infinity) met by the boundary epilogue -- the boundary row under a dense or an on-row point
 // boundary, 0 under an off-row point boundary with min / max, nothing without a boundary.
+//
+// PER-SLICE dead keys on top of both (ultra_rspmm_edit_rows_samples): leave-one-out verification on a graph that
+// holds edits.  Outer slice s must not see a few (row, col, type) edges -- its stated fact and the inverse -- whether they are
+// base edges or delta edges.  rspmm_edit_rows_samples_kernel is the merge above where both cursors also skip an edge that one of
+// the slice's keys names (type < 0: any type).  A group keeps the keys of its own row in registers (at most eight); the rows no
+// edit points into are the business of the per-sample keep masks of the base walk.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -237,6 +243,159 @@ __global__ void __launch_bounds__(DELTA_THREADS) rspmm_edit_rows_kernel(const Ed
     }
 }
 
+struct SampleParams : EditParams {
+    const int32_t *k_row, *k_col, *k_type;               // per outer slice `per_sample` dead (row, col, type) keys; type < 0: any
+    int32_t per_sample;
+};
+
+constexpr int SAMPLE_KEYS_MAX = 8;
+
+// rspmm_edit_rows_kernel with per-outer-slice dead keys that apply to base AND delta edges (leave-one-out verification on a live
+// graph).  The slice's keys that name this row are filtered into registers once per group; a group with none takes
+// one always-false branch per edge.  (bi, bcol, btype) is the next live base edge, (dj, dcol, dtype) the next live delta edge.
+template <typename T, int SUM, int MUL>
+__global__ void __launch_bounds__(DELTA_THREADS) rspmm_edit_rows_samples_kernel(const SampleParams p) {
+    constexpr int VEC = 16 / (int)sizeof(T);      // elements per 16-byte chunk
+    using P = Pack<T, VEC>;
+    const int l16 = threadIdx.x & 15;
+    const long long group = (long long)blockIdx.x * (DELTA_THREADS / 16) + (threadIdx.x >> 4);
+    const int k = (int)(group / p.n_outer), outer = (int)(group - (long long)k * p.n_outer);
+    const int live = min(max(*p.d_count, 0), p.cap_rows);
+    if (k >= live) return;
+    const int row = p.d_row[k];
+    if (row < 0 || row >= p.num_out) return;      // (a delta prepared for another graph: nothing is written)
+    const int i = p.row_ptr[row];
+    const int ie = p.row_ptr[row + 1];
+    const int j = min(max(p.d_ptr[k], 0), p.cap_edges);
+    const int je = min(max(p.d_ptr[k + 1], j), p.cap_edges);
+    const int q = p.t_ptr ? min(max(p.t_ptr[k], 0), p.cap_keys) : 0;      // (no tombstones: an empty key range)
+    const int qe = p.t_ptr ? min(max(p.t_ptr[k + 1], q), p.cap_keys) : 0;
+    if (i < 0 || ie < i || ie > p.num_edge) return;
+
+    // this slice's keys that name this row (compared only, never used as an index)
+    int sc[SAMPLE_KEYS_MAX], st[SAMPLE_KEYS_MAX];
+    unsigned smask = 0;
+    const long long sbase = (long long)outer * p.per_sample;
+#pragma unroll
+    for (int u = 0; u < SAMPLE_KEYS_MAX; ++u) {
+        sc[u] = 0, st[u] = 0;
+        if (u < p.per_sample && p.k_row[sbase + u] == row) {
+            sc[u] = p.k_col[sbase + u], st[u] = p.k_type[sbase + u];
+            smask |= 1u << u;
+        }
+    }
+    const auto sample_dead = [&](int col, int type) {
+        bool dead = false;
+#pragma unroll
+        for (int u = 0; u < SAMPLE_KEYS_MAX; ++u)
+            dead |= ((smask >> u) & 1u) && sc[u] == col && (st[u] < 0 || st[u] == type);
+        return dead;
+    };
+
+    const T *rel = reinterpret_cast<const T *>(p.rel.ptr) + outer * p.rel.stride_outer;
+    const T *x = reinterpret_cast<const T *>(p.x.ptr) + outer * p.x.stride_outer;
+    T *dst = reinterpret_cast<T *>(p.out) + outer * p.out_stride_outer + (long long)row * p.out_stride_row;
+    const long long bnd_row = p.bnd_rows ? p.bnd_rows[outer] : -1;
+
+    // (every lane of the group takes every trip, as in rspmm_edit_rows_kernel: the base indices pass between the group's lanes)
+    for (int dbase = 0; dbase < p.row_len; dbase += 16 * VEC) {
+        const bool dvalid = dbase + VEC * l16 < p.row_len;
+        const int d0 = dvalid ? dbase + VEC * l16 : 0;
+        int bi = i - 1, dj = j - 1, kq = q;
+        int bcol = 0, btype = 0, dcol = 0, dtype = 0;
+        int cbase = i - 16, ccol = 0, ctype = 0;
+        int kcol = kq < qe ? p.t_col[kq] : INT32_MAX;    // the tombstone key under the cursor
+        // step to the next base edge that carries neither a tombstone nor one of the slice's keys
+        const auto next_base = [&]() {
+            for (++bi; bi < ie; ++bi) {
+                if (bi >= cbase + 16) {
+                    cbase = bi;
+                    const int mine = min(bi + l16, ie - 1);
+                    ccol = p.col[mine], ctype = p.type[mine];
+                }
+                bcol = __shfl(ccol, bi - cbase, 16), btype = __shfl(ctype, bi - cbase, 16);
+                while (kcol < bcol) {
+                    ++kq;
+                    kcol = kq < qe ? p.t_col[kq] : INT32_MAX;
+                }
+                bool dead = false;
+                if (kcol == bcol)
+                    for (int s = kq; s < qe && p.t_col[s] == bcol; ++s) dead |= p.t_type[s] == btype;
+                if (smask && !dead) dead = sample_dead(bcol, btype);
+                if (!dead) return;
+            }
+        };
+        // step to the next delta edge that carries none of the slice's keys (tombstones never apply to delta edges)
+        const auto next_delta = [&]() {
+            for (++dj; dj < je; ++dj) {
+                dcol = p.d_col[dj], dtype = p.d_type[dj];
+                if (!smask || !sample_dead(dcol, dtype)) return;
+            }
+        };
+        next_base();
+        next_delta();
+        P acc;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc.v[e] = nary_zero<T, SUM>();
+        while (bi < ie || dj < je) {
+            int c[DELTA_BATCH], t[DELTA_BATCH];
+            bool take[DELTA_BATCH];
+#pragma unroll
+            for (int u = 0; u < DELTA_BATCH; ++u) {
+                c[u] = 0, t[u] = 0, take[u] = false;
+                if (bi < ie && (dj >= je || bcol <= dcol)) {        // (equal col: the base edge has the lower edge id)
+                    c[u] = bcol, t[u] = btype, take[u] = true;
+                    next_base();
+                } else if (dj < je) {
+                    c[u] = dcol, t[u] = dtype, take[u] = true;
+                    next_delta();
+                }
+                // (an index outside the operands is never dereferenced: such an edge reads row 0 and is left out of the reduction)
+                if (c[u] < 0 || c[u] >= p.num_in || t[u] < 0 || t[u] >= p.num_rel) c[u] = 0, t[u] = 0, take[u] = false;
+            }
+            P xv[DELTA_BATCH], rv[DELTA_BATCH];
+#pragma unroll
+            for (int u = 0; u < DELTA_BATCH; ++u) {
+                xv[u] = *reinterpret_cast<const P *>(x + (long long)c[u] * p.x.stride_row + d0);
+                rv[u] = *reinterpret_cast<const P *>(rel + (long long)t[u] * p.rel.stride_row + d0);
+            }
+#pragma unroll
+            for (int u = 0; u < DELTA_BATCH; ++u) {
+                if (take[u]) {
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) acc.v[e] = nary<T, SUM>(acc.v[e], binary<T, MUL>(rv[u].v[e], xv[u].v[e]));
+                }
+            }
+        }
+        // the boundary epilogue of the reference-order kernels; a row with no surviving edge meets it with the start value
+        if (p.has_bnd && (bnd_row < 0 || bnd_row == row)) {
+            const P b = *reinterpret_cast<const P *>(reinterpret_cast<const T *>(p.bnd.ptr) + outer * p.bnd.stride_outer +
+                                                     (bnd_row < 0 ? (long long)row * p.bnd.stride_row : 0) + d0);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc.v[e] = nary<T, SUM>(acc.v[e], b.v[e]);
+        } else if (SUM != ULTRA_SUM_ADD && p.has_bnd) {     // (min / max: a point boundary stands for zeros elsewhere)
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc.v[e] = nary<T, SUM>(acc.v[e], T(0));
+        }
+        if (dvalid) *reinterpret_cast<P *>(dst + d0) = acc;
+    }
+}
+
+template <typename T>
+static hipError_t launch_samples(int sum, int mul, const SampleParams &p, unsigned grid, hipStream_t s) {
+#define ULTRA_SAMPLES_CASE(S_, M_)                                                                                  \
+    case S_ * 2 + M_:                                                                                               \
+        hipLaunchKernelGGL((rspmm_edit_rows_samples_kernel<T, S_, M_>), dim3(grid), dim3(DELTA_THREADS), 0, s, p);   \
+        break;
+    switch (sum * 2 + mul) {
+        ULTRA_SAMPLES_CASE(0, 0) ULTRA_SAMPLES_CASE(0, 1) ULTRA_SAMPLES_CASE(1, 0) ULTRA_SAMPLES_CASE(1, 1)
+        ULTRA_SAMPLES_CASE(2, 0) ULTRA_SAMPLES_CASE(2, 1)
+        default: return hipErrorInvalidValue;
+    }
+#undef ULTRA_SAMPLES_CASE
+    return hipGetLastError();
+}
+
 template <typename T>
 static hipError_t launch_edit(int sum, int mul, const EditParams &p, unsigned grid, hipStream_t s) {
 #define ULTRA_EDIT_CASE(S_, M_)                                                                                     \
@@ -290,10 +449,12 @@ static bool delta_vec_ok(const ultra_mat *m, int64_t step) {
     return (reinterpret_cast<uintptr_t>(m->ptr) & 15u) == 0 && m->stride_row % step == 0 && m->stride_outer % step == 0;
 }
 
-// Both entries: the checks, then rspmm_delta_rows_kernel (removed == NULL) or rspmm_edit_rows_kernel.
+// Every entry: the checks, then rspmm_delta_rows_kernel (removed == NULL), rspmm_edit_rows_kernel, or -- with per-slice keys --
+// rspmm_edit_rows_samples_kernel (which takes removed == NULL as "no tombstones").
 static int delta_rows_impl(const char *who, ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const ultra_mat *relation,
                            const ultra_mat *input, const ultra_mat *boundary, const int64_t *point_rows_dev,
-                           const ultra_mat *output, const ultra_delta *delta, const ultra_tombstones *removed, void *stream) {
+                           const ultra_mat *output, const ultra_delta *delta, const ultra_tombstones *removed, void *stream,
+                           const ultra_sample_keys *keys = nullptr) {
     if (!plan) return delta_invalid(who, "plan is NULL");
     if (sum < 0 || sum > 2) return delta_invalid(who, "unknown sum code");
     if (mul != ULTRA_MUL_MUL && mul != ULTRA_MUL_ADD && mul != ULTRA_MUL_ROTATE) return delta_invalid(who, "unknown mul code");
@@ -313,6 +474,7 @@ static int delta_rows_impl(const char *who, ultra_plan *plan, int32_t sum, int32
     // (ptr_dev is read for every touched row; the key arrays only below a non-zero capacity)
     if (removed && (!removed->ptr_dev || (removed->capacity_keys > 0 && (!removed->col_dev || !removed->type_dev))))
         return delta_invalid(who, "removed: a NULL array");
+    if (keys && (!keys->row_dev || !keys->col_dev || !keys->type_dev)) return delta_invalid(who, "keys: a NULL array");
     int rc;
     if ((rc = delta_check_mat(who, output, "output", plan->num_out, n_outer, row_len))) return rc;
     if ((rc = delta_check_mat(who, relation, "relation", plan->num_rel, n_outer, row_len))) return rc;
@@ -333,7 +495,7 @@ static int delta_rows_impl(const char *who, ultra_plan *plan, int32_t sum, int32
     if (grid >= (1ll << 31)) return delta_invalid(who, "capacity_rows * n_outer exceeds the launch grid");
     if ((rc = ultra_plan_upload(plan))) return rc;
 
-    EditParams p;
+    SampleParams p;
     p.row_ptr = plan->d.row_ptr, p.col = plan->d.col, p.type = plan->d.type;
     p.d_row = delta->row_dev, p.d_ptr = delta->ptr_dev, p.d_col = delta->col_dev, p.d_type = delta->type_dev;
     p.d_count = delta->count_dev;
@@ -351,15 +513,20 @@ static int delta_rows_impl(const char *who, ultra_plan *plan, int32_t sum, int32
     p.num_edge = plan->num_edge;
     p.t_ptr = removed ? removed->ptr_dev : nullptr, p.t_col = removed ? removed->col_dev : nullptr;
     p.t_type = removed ? removed->type_dev : nullptr, p.cap_keys = removed ? (int32_t)removed->capacity_keys : 0;
+    p.k_row = keys ? keys->row_dev : nullptr, p.k_col = keys ? keys->col_dev : nullptr;
+    p.k_type = keys ? keys->type_dev : nullptr, p.per_sample = keys ? (int32_t)keys->per_sample : 0;
     if (n_outer >= (1ll << 31) || row_len >= (1ll << 31)) return delta_invalid(who, "n_outer / row_len exceed 2^31");
     (void)hipGetLastError();   // drop any stale error left by other users of the HIP runtime
     const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const DeltaParams &dp = p;
+    const EditParams &ep = p;
     const bool f32 = dtype == ULTRA_F32;
-    const hipError_t e = removed ? (f32 ? launch_edit<float>(sum, mul, p, (unsigned)grid, s) : launch_edit<double>(sum, mul, p, (unsigned)grid, s))
-                                 : (f32 ? launch_delta<float>(sum, mul, dp, (unsigned)grid, s) : launch_delta<double>(sum, mul, dp, (unsigned)grid, s));
+    const hipError_t e = keys    ? (f32 ? launch_samples<float>(sum, mul, p, (unsigned)grid, s) : launch_samples<double>(sum, mul, p, (unsigned)grid, s))
+                         : removed ? (f32 ? launch_edit<float>(sum, mul, ep, (unsigned)grid, s) : launch_edit<double>(sum, mul, ep, (unsigned)grid, s))
+                                   : (f32 ? launch_delta<float>(sum, mul, dp, (unsigned)grid, s) : launch_delta<double>(sum, mul, dp, (unsigned)grid, s));
     if (e != hipSuccess) {
-        set_error(std::string(removed ? "rspmm_edit_rows_kernel" : "rspmm_delta_rows_kernel") + " launch: " + hipGetErrorString(e));
+        set_error(std::string(keys ? "rspmm_edit_rows_samples_kernel" : removed ? "rspmm_edit_rows_kernel" : "rspmm_delta_rows_kernel") +
+                  " launch: " + hipGetErrorString(e));
         return ULTRA_ERR_HIP;
     }
     return ULTRA_OK;
@@ -384,4 +551,15 @@ extern "C" int32_t ultra_rspmm_edit_rows(ultra_plan *plan, int32_t sum, int32_t 
     ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);
     return delta_rows_impl(removed ? "ultra_rspmm_edit_rows" : "ultra_rspmm_delta_rows", plan, sum, mul, dtype, relation, input,
                            boundary, point_rows_dev, output, delta, removed, stream);
+}
+
+extern "C" int32_t ultra_rspmm_edit_rows_samples(ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const ultra_mat *relation,
+                                                 const ultra_mat *input, const ultra_mat *boundary, const int64_t *point_rows_dev,
+                                                 const ultra_mat *output, const ultra_delta *delta, const ultra_tombstones *removed,
+                                                 const ultra_sample_keys *keys, void *stream) {
+    const char *who = "ultra_rspmm_edit_rows_samples";
+    if (!keys) return delta_invalid(who, "keys is NULL");
+    if (keys->per_sample < 1 || keys->per_sample > SAMPLE_KEYS_MAX) return delta_invalid(who, "keys: per_sample must lie in [1, 8]");
+    ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);
+    return delta_rows_impl(who, plan, sum, mul, dtype, relation, input, boundary, point_rows_dev, output, delta, removed, stream, keys);
 }

@@ -182,12 +182,13 @@ class GeneralizedRelationalConv(nn.Module):
         return self._forward_impl(input, query, boundary, edge_index, edge_type, size, edge_weight, residual=False)
 
     def _forward_impl(self, input, query, boundary, edge_index, edge_type, size, edge_weight=None, residual=False,
-                      relation=None, onehot_rows=None, edge_keep=False, delta=None):
+                      relation=None, onehot_rows=None, edge_keep=False, delta=None, sample_keys=None):
         """forward() plus the option to fuse the caller's residual `hidden + layer_input` (models.py:158-160),
         to take this layer's relation features precomputed by the caller, to be told that `input` is zero
         outside row onehot_rows[b] of every sample (the layer-0 boundary condition, models.py:139-141), that
         `edge_weight` is a 0/1 keep mask (edge_keep=True: edges with 0 are absent, base_nbfnet.py:54-77), and to run on
-        the graph with the added facts of `delta` (rspmm.GraphDelta; _propagate_delta)."""
+        the graph with the added facts of `delta` (rspmm.GraphDelta; _propagate_delta) -- with `sample_keys` and 2-D keep rows:
+        without each sample's own dead edges (_propagate_delta_samples)."""
         batch_size = len(query)
 
         if relation is None:
@@ -195,8 +196,15 @@ class GeneralizedRelationalConv(nn.Module):
         # edge_weight=None means "all ones" (what every caller on the fused path passes, models.py:143):
         # the kernel then skips the weight stream instead of multiplying by 1.
         if delta is not None:
+            if sample_keys is not None:
+                # leave-one-out on a live graph: per-sample keep rows over the base edges AND the same edges as keys
+                if edge_weight is None or edge_weight.dim() != 2 or not edge_keep:
+                    raise RuntimeError("`sample_keys` go with the per-sample keep rows of the base edge list (edge_keep=True)")
+                return self._propagate_delta_samples(edge_index, size, input, relation, boundary, edge_type, delta, edge_weight,
+                                                     sample_keys, residual=residual)
             if edge_weight is not None or edge_keep:
-                raise RuntimeError("a graph delta (added facts) is not combined with edge weights or keep masks")
+                raise RuntimeError("a graph delta (added facts) is combined with per-sample keep rows only through `sample_keys` "
+                                   "(leave-one-out verification), not with edge weights or other keep masks")
             return self._propagate_delta(edge_index, size, input, relation, boundary, edge_type, delta, residual=residual)
         return self.propagate(input=input, relation=relation, boundary=boundary, edge_index=edge_index,
                               edge_type=edge_type, size=size, edge_weight=edge_weight, residual=residual,
@@ -358,6 +366,45 @@ class GeneralizedRelationalConv(nn.Module):
             # (delta.degree is signed: added minus retracted edges)
             degree = _in_degree(edge_index, num_node) + delta.degree
             update = update / (degree.to(input.dtype) + 1).view(1, -1, 1)
+        return self.update(update, input, residual=residual)
+
+    def delta_samples_supported(self):
+        """Does _propagate_delta_samples serve this layer's configuration?  (sum / max with TransE or DistMult: what
+        _propagate_samples and _propagate_delta both serve, minus `mean`, whose per-sample degree of the materialised list is
+        not built)"""
+        return self.aggregate_func in ("sum", "max") and self.message_func in self.message2mul
+
+    def _propagate_delta_samples(self, edge_index, size, input, relation, boundary, edge_type, delta, edge_weight, sample_keys,
+                                 residual=False):
+        """The layer on the graph with `delta`'s edits where sample s does not see a few edges of its own (leave-one-out
+        verification on a live graph): `edge_weight` (batch, num_edge) are the 0/1 keep rows over the BASE edge list
+        (BaseNBFNet.leave_one_out_keep), `sample_keys` = (row, col, type) name the same edges for the rows an edit points into,
+        base and delta edges alike (GraphDelta.sample_keys).  The aggregate by plan.forward with the keep rows -- right for
+        every row no edit points into -- then plan.edit_rows_samples on the same buffer with the same dense boundary, which
+        recomputes the touched rows of every sample without that sample's dead edges, then the update.  Equals the layer on
+        delta.materialize(...) filtered per sample, bit for bit.  Inference only; sum / max, TransE / DistMult.  Returns None
+        where the engine does not serve the call: the caller runs sample by sample on the materialised graph."""
+        if torch.is_grad_enabled():
+            raise RuntimeError("a graph delta with per-sample keep masks serves inference (torch.no_grad()) only")
+        if not self.delta_samples_supported():
+            raise RuntimeError("a graph delta with per-sample keep masks serves the sum / max aggregates with TransE / DistMult "
+                               "messages, not `%s` / `%s`" % (self.aggregate_func, self.message_func))
+        num_node = size[0] if size is not None else input.shape[1]
+        if not input.is_cuda or self._order_free(edge_index, num_node):
+            return None
+        if isinstance(boundary, PointBoundary):
+            boundary = boundary.dense()
+        edge_weight = edge_weight.to(input.dtype)
+        boundary = boundary.to(input.dtype)
+        plan = rspmm.get_plan(edge_index, edge_type, num_node, relation.shape[1])
+        if not plan.exact:
+            return None
+        sum = {"sum": "add"}.get(self.aggregate_func, self.aggregate_func)
+        mul = self.message2mul[self.message_func]
+        update = plan.forward(relation, input, edge_weight=edge_weight, boundary=boundary, sum=sum, mul=mul, keep=True)
+        update = plan.edit_rows_samples(relation, input, update, delta, sample_keys, boundary=boundary, sum=sum, mul=mul)
+        if update is None:
+            return None
         return self.update(update, input, residual=residual)
 
     def edge_grad_layer(self, input, query, boundary, edge_index, edge_type, num_node, edge_weight, residual=False,

@@ -184,10 +184,12 @@ class BaseNBFNet(nn.Module):
 
     def _propagate_layers(self, data, layer_input, query, boundary, separate_grad=False, relations=None,
                           edge_weight=None, onehot_rows=None, edge_keep=False, prefilled=None, last_rows=None,
-                          edge_grad_route=False, edge_grad_batch=None, delta=None):
+                          edge_grad_route=False, edge_grad_batch=None, delta=None, sample_keys=None):
         """The Bellman-Ford loop shared by every model (models.py:72-80, 150-163, 233-246).
         `delta` (rspmm.GraphDelta, inference only): every layer runs on the graph with the delta's added facts, on the cached
         plan of `data` (layers._propagate_delta); _DeltaRouteUnsupported where a layer or the engine does not serve that.
+        `sample_keys` (with `delta` and a 2-D keep mask `edge_weight` over data's edge list): every sample also without its own
+        dead edges, base or added (layers._propagate_delta_samples; GraphDelta.sample_keys).
         `relations`: optional per-layer relation features computed up front (EntityNBFNet batches the six
         relation_projection MLPs, which all read the same relation representations).
         `boundary` may be a layers.PointBoundary (then `layer_input` is ignored: layer 0 reads the boundary condition).
@@ -270,11 +272,13 @@ class BaseNBFNet(nn.Module):
                     self._last_hidden_on_rows = True
                     break
             if delta is not None:
-                if separate_grad or torch.is_grad_enabled() or not layer.delta_supported():
+                served = layer.delta_supported() if sample_keys is None else layer.delta_samples_supported()
+                if separate_grad or torch.is_grad_enabled() or not served:
                     raise _DeltaRouteUnsupported()
+                masked = {} if sample_keys is None else {"edge_weight": edge_weight, "edge_keep": True, "sample_keys": sample_keys}
                 hidden = layer._forward_impl(layer_input, query, boundary, data.edge_index, data.edge_type, size,
                                              residual=residual, relation=None if relations is None else relations[i],
-                                             delta=delta)
+                                             delta=delta, **masked)
                 if hidden is None:
                     raise _DeltaRouteUnsupported()
                 hiddens.append(hidden)
@@ -304,6 +308,10 @@ def _materialized_forward(run, data, delta, on_gpu):
         raise NotOnFusedPath("a graph delta outside the engine route runs on the materialised graph (a host plan): not "
                              "capturable")
     return run(delta.materialize(data))
+
+
+def _capturing(tensor):
+    return tensor.is_cuda and torch.cuda.is_current_stream_capturing()
 
 
 class _BatchRouteUnsupported(Exception):
@@ -421,7 +429,7 @@ class EntityNBFNet(BaseNBFNet):
         return out, side
 
     def _bellmanford_hidden(self, data, h_index, r_index, separate_grad=False, edge_weight=None, edge_keep=False, prefilled=None,
-                            last_rows=None, edge_grad_route=False, edge_grad_batch=None, delta=None):
+                            last_rows=None, edge_grad_route=False, edge_grad_batch=None, delta=None, sample_keys=None):
         batch_size = len(r_index)
         # query = representation of each sample's query relation, scattered to its head node
         fused = (dense.boundary_supported(h_index, self.query) and self.query.dim() == 3
@@ -449,7 +457,7 @@ class EntityNBFNet(BaseNBFNet):
                                                        relations=self._project_relations_batched(),
                                                        edge_weight=edge_weight, onehot_rows=h_index, edge_keep=edge_keep,
                                                        prefilled=prefilled, last_rows=last_rows, edge_grad_route=edge_grad_route,
-                                                       edge_grad_batch=edge_grad_batch, delta=delta)
+                                                       edge_grad_batch=edge_grad_batch, delta=delta, sample_keys=sample_keys)
         return hiddens, edge_weights, query
 
     def _project_relations_batched(self):
@@ -650,16 +658,37 @@ class EntityNBFNet(BaseNBFNet):
                 or tuple(edge_keep.shape) != (batch.shape[0], data.edge_index.shape[1]):
             raise ValueError("edge_keep must be a (batch, num_edge) = (%d, %d) tensor" % (batch.shape[0], data.edge_index.shape[1]))
 
-    def forward(self, data, relation_representations, batch, prefill=None, prologue=None, edge_keep=None, delta=None):
+    def forward(self, data, relation_representations, batch, prefill=None, prologue=None, edge_keep=None, delta=None,
+                leave_out=None, leave_out_buffers=None, leave_out_fallback=None):
         """edge_keep (batch, num_edge), 0/1, original edge order: sample s runs on the graph without the edges whose
         edge_keep[s] is 0 -- row s of the result is this forward on data filtered by edge_keep[s] with batch[s:s+1] (eval mode
         under no_grad only).  The relation graph is the caller's: not rebuilt.
         delta (rspmm.GraphDelta; eval mode under no_grad, not with edge_keep): the forward on the graph with the delta's added
         facts -- it equals this forward on delta.materialize(data).  On the fused inference path a branch shaped like the masked
         one runs on data's cached plans (prologue, delta layers, readout: every step an engine launch, so a capture records
-        it); elsewhere the materialised graph is used (relation_representations are the caller's in both cases)."""
+        it); elsewhere the materialised graph is used (relation_representations are the caller's in both cases).
+        leave_out (batch, 3) int64 = the stated facts (h, t, r), r direct (eval mode under no_grad, not with edge_keep): sample s
+        is scored without fact s and its inverse -- with `remove_one_hop` without any edge between the two nodes.  Without a
+        delta (or with an unedited one) that is edge_keep=leave_one_out_keep(data, leave_out).  With an edited delta sample s
+        runs on delta.materialize(data) without those edges, whether they are base edges or the delta's own
+        (_forward_leave_out); the delta is not folded into the graph.  leave_out_buffers = (keep (batch, num_edge) fp32,
+        (row, col, type) int32 (batch, 2) each): a captured step's own buffers for the keep rows and the keys.
+        leave_out_fallback: the caller's definition loop for the case the engine route does not apply (Ultra.forward's)."""
         if delta is not None and not delta.edited:
             delta = None
+        if leave_out is not None:
+            if edge_keep is not None:
+                raise ValueError("leave_out builds its own keep rows: not together with edge_keep")
+            if self.training or torch.is_grad_enabled():
+                raise ValueError("leave_out (leave-one-out verification) serves eval mode under torch.no_grad() only")
+            if not torch.is_tensor(leave_out) or leave_out.dim() != 2 or tuple(leave_out.shape) != (batch.shape[0], 3):
+                raise ValueError("leave_out must be a (batch, 3) = (%d, 3) tensor of stated facts (h, t, r)" % batch.shape[0])
+            keep_out, keys_out = leave_out_buffers if leave_out_buffers is not None else (None, None)
+            if delta is None:       # (no edits: exactly the keep rows' route)
+                edge_keep = self.leave_one_out_keep(data, leave_out, out=keep_out, validate=not _capturing(leave_out))
+            else:
+                return self._forward_leave_out(data, relation_representations, batch, prologue, delta, leave_out, keep_out,
+                                               keys_out, leave_out_fallback)
         if delta is not None:
             if edge_keep is not None or self.training or torch.is_grad_enabled():
                 raise ValueError("a graph delta (added facts) serves eval mode under torch.no_grad() only, without edge_keep")
@@ -785,6 +814,46 @@ class EntityNBFNet(BaseNBFNet):
         score = dense.readout_batch(self, hiddens[-1], query, batch_c, side).view(batch.shape[:-1])
         self._check_valid(valid)
         return score
+
+    def _forward_leave_out(self, data, relation_representations, batch, prologue, delta, leave_out, keep_out, keys_out,
+                           fallback):
+        """leave_out= with an edited delta.  The engine route: dense.batch_prologue, the keep rows over data's (the base) edge
+        list and the same edges as per-sample keys, every layer as layers._propagate_delta_samples, dense.readout_batch -- every
+        step an engine launch or a small torch copy, so a capture records it.  Where that does not apply (CPU tensors, a model
+        off the fused path, a layer kind or a plan the kernel does not serve) the DEFINITION runs: sample by sample this forward
+        on remove_easy_edges(delta.materialize(data), fact s)."""
+        try:
+            if not self.prologue_supported(batch) or not all(l.delta_samples_supported() for l in self.layers):
+                raise _DeltaRouteUnsupported()
+            self.query = relation_representations
+            for layer in self.layers:
+                layer.relation = relation_representations
+            keep = self.leave_one_out_keep(data, leave_out, out=keep_out, validate=not _capturing(leave_out))
+            keys = delta.sample_keys(leave_out, any_type=self.remove_one_hop, out=keys_out)
+            if keep.dtype != relation_representations.dtype:
+                keep = keep.to(relation_representations.dtype)
+            batch_c, h0, r0, side, valid = prologue if prologue is not None else dense.batch_prologue(batch, data.num_relations // 2)
+            hiddens, _, query = self._bellmanford_hidden(data, h0, r0, delta=delta, edge_weight=keep, edge_keep=True,
+                                                         sample_keys=keys)
+            if not dense.readout_supported(self, hiddens[-1]):
+                raise _DeltaRouteUnsupported()
+            score = dense.readout_batch(self, hiddens[-1], query, batch_c, side).view(batch.shape[:-1])
+            self._check_valid(valid)
+            return score
+        except _DeltaRouteUnsupported:
+            pass
+        if _capturing(batch):
+            raise NotOnFusedPath("leave_out with a graph delta outside the engine route runs sample by sample on the materialised "
+                                 "graph (host plans): not capturable")
+        if fallback is not None:
+            return fallback()
+        full = delta.materialize(data)
+        h_index, t_index, r_index = leave_out.unbind(-1)
+        rows = []
+        for s in range(batch.shape[0]):
+            without = self.remove_easy_edges(full, h_index[s:s + 1], t_index[s:s + 1], r_index[s:s + 1])
+            rows.append(self.forward(without, relation_representations[s:s + 1], batch[s:s + 1]))
+        return torch.cat(rows)
 
     def _check_valid(self, valid):
         if valid.is_cuda and torch.cuda.is_current_stream_capturing():
@@ -958,7 +1027,7 @@ class Ultra(nn.Module):
                 layer.relation = r
         return results
 
-    def forward(self, data, batch, edge_keep=None, delta=None):
+    def forward(self, data, batch, edge_keep=None, delta=None, leave_out=None, leave_out_buffers=None):
         # batch: (bs, 1 + num_negs, 3); the relation is shared by every triple of a row
         # edge_keep (bs, num_edge): per-sample 0/1 keep masks over data's edge list (EntityNBFNet.forward); the relation graph is
         # not rebuilt -- the reference's filtered copy keeps data.relation_graph too
@@ -966,10 +1035,40 @@ class Ultra(nn.Module):
         # -- this forward on delta.materialize(data), bit for bit on reference-order plans.  The relation model runs on
         # delta.relation_graph, the entity model on data's cached plan with the touched rows fixed after every aggregate; where
         # that route does not apply (EntityNBFNet.forward), on the materialised graph.  An empty delta (or None): nothing changes.
+        # leave_out (bs, 3) = stated facts (h, t, r), r direct (eval mode under no_grad, not with edge_keep): sample s is scored
+        # without fact s and its inverse (remove_one_hop: without any edge between the two nodes).  Without edits this is
+        # edge_keep=leave_one_out_keep(data, leave_out); with an edited delta sample s runs on delta.materialize(data) without
+        # those edges -- base edges or the delta's own -- on data's cached plan (EntityNBFNet._forward_leave_out), the relation
+        # model on delta.relation_graph, unmasked.  The definition, and the route where the engine does not serve the call: per
+        # sample this forward on remove_easy_edges(delta.materialize(data), fact s).
         entity_kwargs = {}
+        if leave_out is not None:
+            if edge_keep is not None:
+                raise ValueError("leave_out builds its own keep rows: not together with edge_keep")
+            if self.training or torch.is_grad_enabled():
+                raise ValueError("leave_out (leave-one-out verification) serves eval mode under torch.no_grad() only")
+            if not hasattr(self.entity_model, "_forward_leave_out"):
+                raise TypeError("%s has no leave-one-out route; EntityNBFNet has" % type(self.entity_model).__name__)
+            entity_kwargs["leave_out"] = leave_out
+            if leave_out_buffers is not None:
+                entity_kwargs["leave_out_buffers"] = leave_out_buffers
+            if delta is not None and delta.edited:
+                served = data
+
+                def definition():
+                    full = delta.materialize(served)
+                    rows = []
+                    for s in range(batch.shape[0]):
+                        h_index, t_index, r_index = leave_out[s:s + 1].unbind(-1)
+                        rows.append(self.forward(self.entity_model.remove_easy_edges(full, h_index, t_index, r_index),
+                                                 batch[s:s + 1]))
+                    return torch.cat(rows)
+
+                entity_kwargs["leave_out_fallback"] = definition
         if delta is not None and delta.edited:
             if edge_keep is not None:
-                raise ValueError("a graph delta (added facts) is not combined with edge_keep")
+                raise ValueError("a graph delta (added facts) is not combined with edge_keep: a caller-made mask runs over an "
+                                 "edge list of which the caller cannot see the delta's part (leave-one-out: leave_out=)")
             if delta.relation_graph is not None and delta.relation_graph is not data.relation_graph:
                 data = delta.live_view(data)
             entity_kwargs["delta"] = delta

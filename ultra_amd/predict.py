@@ -63,6 +63,19 @@ def _select(entry, args, n_live, dev):
         _lib.check(getattr(_lib.lib, entry + "_live")(*args, n_live.data_ptr(), _lib.stream_of(dev)))
 
 
+def filtered_rank_reference(pred, pos, ptr, index, num_live=None):
+    """(rank (batch) int64, num_negative (batch) int64) of pred[b, pos[b]] among the candidates of row b -- the ids not in
+    index[ptr[b] : ptr[b + 1]] (the known answers, the positive among them), ties counting against the positive: what
+    ultra_filtered_rank computes, in plain torch on any device (tasks.compute_ranking over the mask the lists stand for).
+    num_live: only the ids below it exist."""
+    if num_live is not None:
+        pred = pred[:, :_live_int(num_live, pred.shape[1])]
+    mask = torch.ones(pred.shape, dtype=torch.bool, device=pred.device)
+    for b in range(pred.shape[0]):
+        mask[b, index[int(ptr[b]):int(ptr[b + 1])]] = False
+    return tasks.compute_ranking(pred, pos, mask), mask.sum(dim=-1)
+
+
 def filtered_topk_reference(pred, k, ptr=None, index=None, num_live=None):
     """(ids (batch, k) int64, scores (batch, k) pred's dtype, count (batch) int64) -- per row, the candidates are the ids not
     in index[ptr[b] : ptr[b + 1]], in the order of the stable descending sort of their scores.  num_live: only the ids below it
@@ -325,6 +338,19 @@ def _entity_model(model):
     return getattr(model, "entity_model", model)
 
 
+def delta_samples_supported(model):
+    """Does `model` verify stated facts on a graph that holds edits WITHOUT folding them in first -- forward(leave_out=,
+    delta=) with every entity layer on layers._propagate_delta_samples (sum / max, TransE / DistMult)?"""
+    try:
+        params = inspect.signature(getattr(model, "forward", model)).parameters
+    except (TypeError, ValueError):
+        return False
+    ent = _entity_model(model)
+    layers = getattr(ent, "layers", None)
+    return ("leave_out" in params and "delta" in params and hasattr(ent, "_forward_leave_out") and layers is not None
+            and all(getattr(layer, "delta_samples_supported", lambda: False)() for layer in layers))
+
+
 def _check_facts(data, h, r, t, num_live=None):
     """(h, r, t) of verify_*: int64 vectors of one length on the graph's device, r a direct relation (ValueError otherwise);
     num_live (a graph with reserved rows): h and t below it."""
@@ -381,11 +407,19 @@ class _GraphedVerifyStep(_IndexedStep):
     candidates, the masked forward on the full graph's cached plans, ultra_filtered_rank and the gather of the positives' scores.
     Per batch the host copies the triples and the (bs + 1) offsets into the known lists of the whole call (`load_index`)."""
 
-    def __init__(self, model, data, batch_size, mode, index_capacity, warmup=2, n_live=None):
-        """n_live: as in _GraphedPredictStep -- ultra_filtered_rank_live over the live ids, or (None) ultra_filtered_rank."""
+    def __init__(self, model, data, batch_size, mode, index_capacity, warmup=2, n_live=None, delta=None):
+        """n_live: as in _GraphedPredictStep -- ultra_filtered_rank_live over the live ids, or (None) ultra_filtered_rank.
+        delta (rspmm.GraphDelta or None; a model with the leave_out route): while it holds no edit the step records the masked
+        forward above; once it holds facts or tombstones it records model(..., leave_out=triples, delta=delta) -- the keep rows
+        over the base edge list, the same edges as per-sample keys (GraphDelta.sample_keys into the step's own key buffers) and
+        the delta's fix-up launches, which read its device buffers at replay.  `route` is what the Predictor compares."""
         dev = data.edge_index.device
         Capture.__init__(self, dev)
         self.model, self.bs, self.mode, self.n_live = model, batch_size, mode, n_live
+        self.delta, self.route = delta, _delta_route(delta)
+        live = delta is not None and delta.edited
+        # (row, col, type) of every sample's two dead edges: allocated once, at fixed addresses
+        self.keys = tuple(torch.zeros(batch_size, 2, dtype=torch.int32, device=dev) for _ in range(3)) if live else None
         self.capacity = max(1, int(index_capacity))
         self.triples = torch.zeros(batch_size, 3, dtype=torch.long, device=dev)       # (h, t, r)
         self.ptr = torch.zeros(batch_size + 1, dtype=torch.long, device=dev)
@@ -396,16 +430,25 @@ class _GraphedVerifyStep(_IndexedStep):
         self.num_negative = torch.empty(batch_size, dtype=torch.long, device=dev)
         n = int(data.num_nodes)
         ent = _entity_model(model)
+        # The live route is replayed between eager edits (add_facts / remove_facts run torch ops of their own), and a memset node
+        # captured into a hipGraph replays wrongly once eager memsets interleave with the replays (csrc/rank_kernels.hip): its
+        # rank goes through the live-count entry, which zeroes with a kernel -- over all n ids where no rows are reserved.
+        self.n_all = torch.full((1,), n, dtype=torch.long, device=dev) if live and n_live is None else None
+        rank_count = n_live if n_live is not None else self.n_all
 
         def step():
-            keep = ent.leave_one_out_keep(data, self.triples, out=self.keep, validate=False)
             h, t, r = self.triples.unbind(-1)
             anchor, pos = (h, t) if mode == "tail" else (t, h)
-            pred = model(data, _candidates(data, anchor, r, mode), edge_keep=keep).float().contiguous()
+            if live:
+                pred = model(data, _candidates(data, anchor, r, mode), leave_out=self.triples,
+                             leave_out_buffers=(self.keep, self.keys), delta=delta).float().contiguous()
+            else:
+                keep = ent.leave_one_out_keep(data, self.triples, out=self.keep, validate=False)
+                pred = model(data, _candidates(data, anchor, r, mode), edge_keep=keep).float().contiguous()
             pos = pos.contiguous()
             args = (pred.data_ptr(), pos.data_ptr(), self.ptr.data_ptr(), self.index.data_ptr(), batch_size, n,
                     self.rank.data_ptr(), self.num_negative.data_ptr())
-            _select("ultra_filtered_rank", args, n_live, dev)
+            _select("ultra_filtered_rank", args, rank_count, dev)
             self.score.copy_(pred.gather(1, pos.unsqueeze(-1)).squeeze(-1))
 
         self.warm_up(step, warmup)
@@ -446,7 +489,14 @@ class Predictor(object):
     retracted tail can be returned as an answer again.  The captured step is made again when the first tombstone arrives; from
     then on further remove_facts / add_facts cost no capture and no plan unless the relation graph changes.  compact() folds
     the delta, tombstones included, into `data` (a host plan, new captures); add_facts / remove_facts do so themselves when
-    the capacity would be exceeded, and explain_* / verify_* do so first when the delta holds edits.
+    the capacity would be exceeded, and explain_* does so first when the delta holds edits.  verify_* does NOT:
+    fact i is scored on the materialised graph without itself, whether its edges are base edges or were just stated, on the
+    same cached plan -- per-sample keep rows over the base edge list plus the same edges as per-sample keys for the rows an
+    edit points into (ultra_rspmm_edit_rows_samples).  Its captured step follows the rule of the answer steps: made again
+    when the first edits and the first tombstone arrive and when the relation-graph object changes, otherwise add_facts ->
+    verify_* costs no plan and no capture.  A model whose layers do not serve that route (mean / min / pna aggregates, RotatE
+    messages: delta_samples_supported) is verified after a compaction, as before; so is every model on a predictor with a
+    reserve (entity_capacity > 0), whose "compact first" rule of DESIGN.md 19 stays.
 
     A GROWING graph: entity_capacity=M > 0 reserves M rows for entities that arrive later.  The graph served is
     then a shallow copy of `data` with num_nodes = N + M SLOTS (the same edge list; its own relation graph, equal to the
@@ -590,7 +640,8 @@ class Predictor(object):
         the graph says nothing -- its own edge is a one-hop path from h to t -- so fact i is scored on the graph WITHOUT itself
         and its inverse (with the model's `remove_one_hop`: without any edge between the two nodes), while it still sees every
         other fact of the batch: a leave-one-out view per sample, as per-sample keep masks over the cached plan of the full
-        graph (the relation graph is not rebuilt, as in the reference's training-time removal).  Returns (score (n) fp32: the
+        graph (the relation graph is not rebuilt, as in the reference's training-time removal).  On a live graph "the graph" is
+        the materialised one -- added facts in, retracted ones out -- and the delta stays a delta.  Returns (score (n) fp32: the
         logit of t[i] as the tail of (h[i], r[i], ?); rank (n) int64: 1 + the candidates outside the filter graph's known tails
         of (h[i], r[i]) that score at least as high; num_negative (n) int64: how many such candidates there are).  r must be
         direct relations (ValueError).  On the GPU with use_graph each batch is one hipGraph replay; predict.verify_reference
@@ -631,21 +682,26 @@ class Predictor(object):
     def _verify_step(self, mode, need):
         key = "verify_" + mode
         step = self._steps.get(key)
-        if step is not None and step.params == param_state(self.model) and need <= step.capacity:
+        if step is not None and step.params == param_state(self.model) and need <= step.capacity \
+                and step.delta is self.delta and step.route == _delta_route(self.delta):
             return step
         if step is not None:
             step.release()
             del self._steps[key]
-        step = _GraphedVerifyStep(self.model, self.data, self.batch_size, mode, max(2 * need, 1 << 16), n_live=self.live_count)
+        step = _GraphedVerifyStep(self.model, self.data, self.batch_size, mode, max(2 * need, 1 << 16), n_live=self.live_count,
+                                  delta=self.delta)
         self._steps[key] = step
         return step
 
     @torch.no_grad()
     def _verify(self, h, r, t, mode):
         h, r, t = _check_facts(self.data, h, r, t, num_live=self.num_entities if self.entity_capacity else None)
-        if self.delta is not None and self.delta.edited:
-            self.compact()      # (the keep masks run over the graph's own edge list: the edits become part of it first)
-        data, bs, live_count = self.data, self.batch_size, self.live_count
+        if self.delta is not None and self.delta.edited and (self.entity_capacity or not delta_samples_supported(self.model)):
+            # a model without the combined route: the keep masks run over the graph's own edge list.  A graph with reserved rows
+            # keeps DESIGN.md 19's rule -- compact first, the slot count and the live count stay -- which its tests pin
+            self.compact()
+        data, bs, live_count, delta = self.data, self.batch_size, self.live_count, self.delta
+        live = delta is not None and delta.edited      # (the edits stay beside the plan: leave_out= with the delta)
         dev = h.device
         n = len(h)
         score = torch.empty(n, dtype=torch.float32, device=dev)
@@ -683,14 +739,21 @@ class Predictor(object):
                     self._eager_only = True
             for lo in range(start, n, bs):
                 part = triples[lo:lo + bs].contiguous()
-                keep = ent.leave_one_out_keep(data, part, validate=False)
                 anchor, pos = (part[:, 0], part[:, 1]) if mode == "tail" else (part[:, 1], part[:, 0])
-                pred = self.model(data, _candidates(data, anchor, part[:, 2], mode), edge_keep=keep).float().contiguous()
+                if live:
+                    pred = self.model(data, _candidates(data, anchor, part[:, 2], mode), leave_out=part,
+                                      delta=delta).float().contiguous()
+                else:
+                    keep = ent.leave_one_out_keep(data, part, validate=False)
+                    pred = self.model(data, _candidates(data, anchor, part[:, 2], mode), edge_keep=keep).float().contiguous()
                 pos, b_ptr = pos.contiguous(), ptr[lo:lo + len(part) + 1].contiguous()
-                b_rank, b_neg = torch.empty_like(pos), torch.empty_like(pos)
-                args = (pred.data_ptr(), pos.data_ptr(), b_ptr.data_ptr(), index.data_ptr(), len(part), pred.shape[1],
-                        b_rank.data_ptr(), b_neg.data_ptr())
-                _select("ultra_filtered_rank", args, live_count, dev)
+                if pred.is_cuda:
+                    b_rank, b_neg = torch.empty_like(pos), torch.empty_like(pos)
+                    args = (pred.data_ptr(), pos.data_ptr(), b_ptr.data_ptr(), index.data_ptr(), len(part), pred.shape[1],
+                            b_rank.data_ptr(), b_neg.data_ptr())
+                    _select("ultra_filtered_rank", args, live_count, dev)
+                else:       # off the GPU: the plain-torch restatement, as in `tails`
+                    b_rank, b_neg = filtered_rank_reference(pred, pos, b_ptr, index, **self._live.num_live_for(False))
                 score[lo:lo + len(part)] = pred.gather(1, pos.unsqueeze(-1)).squeeze(-1)
                 rank[lo:lo + len(part)], num_negative[lo:lo + len(part)] = b_rank, b_neg
         finally:

@@ -427,6 +427,42 @@ class Plan(object):
         check(rc)
         return out
 
+    def edit_rows_samples(self, relation, input, out, delta, keys, boundary=None, sum="add", mul="mul", point=None):
+        """edit_rows with dead edges PER OUTER SLICE: `keys` = (row, col, type), int32 (n_outer, per_sample) each, per_sample in
+        1 .. 8 (GraphDelta.sample_keys).  The rows an edit of `delta` points into are recomputed in place; in slice s an edge
+        (row, col, type) -- of the base graph or of the delta -- takes no part if one of keys[.][s] names it (type < 0: every
+        type).  Afterwards those rows of out[s] are the forward on a fresh reference-order plan of delta.materialize(...) without
+        slice s's dead edges, bit for bit (ultra_rspmm_edit_rows_samples); the other rows are not written -- they are right
+        where `out` came from forward(edge_weight=keep (n_outer, num_edge), keep=True) with keep rows that leave the same base
+        edges out.  Returns `out`, or None exactly where edit_rows does."""
+        if not self.exact:
+            return None
+        if (delta.num_nodes, delta.num_relations) != (self.num_node, self.num_relation) or self.num_in != self.num_node:
+            raise RuntimeError("the delta was made for a graph of %d nodes and %d relations, the plan has %d and %d"
+                               % (delta.num_nodes, delta.num_relations, self.num_node, self.num_relation))
+        if point is not None and boundary is not None:
+            raise RuntimeError("a point boundary excludes `boundary`")
+        key_row, key_col, key_type = keys
+        _require_gpu(out, delta.count, key_row, key_col, key_type)
+        op = self._forward_operands(relation, input, None, boundary, out, point)
+        if op.out is not out:
+            raise RuntimeError("`out` must have unit stride along its last dimension")
+        n_outer = out.shape[0] if out.dim() == 3 else 1
+        for t in (key_row, key_col, key_type):
+            if t.dtype != torch.int32 or t.dim() != 2 or t.shape != key_row.shape or not t.is_contiguous():
+                raise RuntimeError("`keys` are three contiguous int32 tensors of one shape (n_outer, per_sample)")
+        if key_row.shape[0] != n_outer or not 1 <= key_row.shape[1] <= 8:
+            raise RuntimeError("Expected keys of shape (n_outer = %d, 1 .. 8), got %s" % (n_outer, tuple(key_row.shape)))
+        operand, removed = delta.operand(), delta.removed_operand()
+        sample_keys = _lib.UltraSampleKeys(key_row.data_ptr(), key_col.data_ptr(), key_type.data_ptr(), key_row.shape[1])
+        rc = lib.ultra_rspmm_edit_rows_samples(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], op.dtype, op.relation, op.input,
+                                               op.boundary, op.rows, op.out_ref, ctypes.byref(operand), ctypes.byref(removed),
+                                               ctypes.byref(sample_keys), stream_of(input))
+        if rc == _lib.ULTRA_ERR_UNSUPPORTED:
+            return None
+        check(rc)
+        return out
+
     def forward_update(self, relation, input, weight, bias, ln_weight, ln_bias, eps, flags, mul="mul", point=None, timed=None,
                        sum="add"):
         """Aggregate (`sum`, `mul`, optional point boundary) AND the layer update
@@ -990,6 +1026,33 @@ class GraphDelta(object):
         """The delta as the engine takes it (ultra_delta); valid while this object lives."""
         return _lib.UltraDelta(self.rows.data_ptr(), self.ptr.data_ptr(), self.col.data_ptr(), self.type.data_ptr(),
                                self.count.data_ptr(), self.rows.numel(), self.col.numel())
+
+    def sample_keys(self, triples, any_type=False, out=None):
+        """The edges each stated fact triples[s] = (h, t, r) -- (n, 3) int64 on the delta's device, r direct -- must not see, as
+        Plan.edit_rows_samples takes them: (row, col, type), int32 (n, 2) each, in the plan's direction (row = edge_index[0],
+        col = edge_index[1], as `_prepare` lays the delta out).  Key 0 is the fact (h, t, r), key 1 its inverse
+        (t, h, r + num_relations // 2); any_type=True (the model's `remove_one_hop`): both types are -1, every edge between
+        the two nodes goes.  The same edges BaseNBFNet.easy_edge_mask of that single triple drops on materialize().  A few
+        copies that a capture records; `out` = (row, col, type): written in place and returned."""
+        if triples.dim() != 2 or triples.shape[1] != 3:
+            raise ValueError("Expected triples of shape (n, 3) = (h, t, r), got %s" % (tuple(triples.shape),))
+        n = triples.shape[0]
+        if out is None:
+            out = tuple(torch.empty(n, 2, dtype=torch.int32, device=triples.device) for _ in range(3))
+        row, col, edge_type = out
+        for t in out:
+            if t.dtype != torch.int32 or tuple(t.shape) != (n, 2):
+                raise ValueError("`out` is three int32 tensors of shape (n, 2) = (%d, 2)" % n)
+        ends = triples[:, :2]
+        row.copy_(ends)                      # (h, t)
+        col[:, 0].copy_(ends[:, 1])          # (t, h)
+        col[:, 1].copy_(ends[:, 0])
+        if any_type:
+            edge_type.fill_(-1)
+        else:
+            edge_type[:, 0].copy_(triples[:, 2])
+            edge_type[:, 1].copy_(triples[:, 2] + self.num_relations // 2)
+        return out
 
     def removed_operand(self):
         """The tombstones as the engine takes them (ultra_tombstones); valid while this object lives."""
