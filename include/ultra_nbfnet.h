@@ -297,6 +297,22 @@ int32_t ultra_relation_graph_bits_keep(const int64_t *edge_index_dev, const int6
                                        void *adj_dev, int64_t *row_counts_dev, void *stream);
 int32_t ultra_relation_graph_edge_keep(const void *adj_dev, int64_t num_relation, const int64_t *rel_edge_index_dev,
                                        const int64_t *rel_edge_type_dev, int64_t num_rel_edge, float *keep_out_dev, void *stream);
+/*
+ * ultra_relation_graph_add_edges:  the bit sets of ultra_relation_graph_bits kept current while edges are ADDED.  hbits / tbits /
+ *   adj hold the state of some edge list (as ultra_relation_graph_bits left it); afterwards they hold the state of that list with
+ *   the given edges appended, word for word what ultra_relation_graph_bits computes for the concatenated list, and row_counts is
+ *   refreshed for ultra_relation_graph_emit.  Cost: the given edges and the bit sets of their endpoints, not the graph.
+ *   Launches, in stream order: a check of every index; the heads' and tails' relation bits; one wave per listed endpoint that
+ *   applies the whole pair marking of that entity (a repeated endpoint repeats idempotent ORs); the row counts.
+ *   changed (one int32 on the device, written whole by the call): bit 0 (value 1) -- a bit was added to adj; bit 1 (value 2) -- an
+ *   index lies outside [0, num_node) / [0, num_relation): no index is dereferenced and hbits / tbits / adj stay as they were.
+ *   The index values live on the device and the call neither waits for it nor allocates, so an index out of range is reported
+ *   through `changed`; arguments the host can see (NULL pointers, negative sizes, num_node or num_relation <= 0, more than 2^20
+ *   relations) answer ULTRA_ERR_INVALID with nothing launched.
+ */
+int32_t ultra_relation_graph_add_edges(const int64_t *edge_index_dev, const int64_t *edge_type_dev, int64_t num_edge, int64_t num_node,
+                                       int64_t num_relation, void *hbits_dev, void *tbits_dev, void *adj_dev, int64_t *row_counts_dev,
+                                       int32_t *changed_dev, void *stream);
 
 /*
  * One layer of the path beam search behind BaseNBFNet.visualize (/root/reference/ultra/base_nbfnet.py:173-232), with the

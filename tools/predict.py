@@ -2,6 +2,7 @@
 
     python tools/predict.py --data-root DIR [--ckpt FILE] --head NAME --relation NAME [--inverse] [-k 10] [--unfiltered] [--explain]
                             [--add-fact H R T]... [--remove-fact H R T]... [--entity-capacity M] [--add-entity NAME]...
+                            [--relation-capacity K] [--add-relation NAME]...
     python tools/predict.py --data-root DIR [--ckpt FILE] --verify (--head NAME --relation NAME --tail NAME | --triples FILE) [--inverse]
 
 DIR holds train.txt / valid.txt / test.txt (`head relation tail` per line) and optionally entities.dict / relations.dict
@@ -20,6 +21,11 @@ served and the known answers, so its tail can be predicted again.  Both kinds ar
 reserved by --entity-capacity M (default: as many as there are --add-entity options), costs no plan and no capture, and from then
 on NAME can be used by the --add-fact / --remove-fact options that FOLLOW it on the command line and by --head; answers print it
 by its name.  It is applied in command-line order with the fact options.
+
+--add-relation NAME (repeatable) introduces a relation type the dataset does not know (Predictor.add_relations): it takes one of
+the slots reserved by --relation-capacity K (default: as many as there are --add-relation options) and costs no plan, no relation
+graph and no capture.  The --add-relation options are applied in command-line order BEFORE every --add-fact / --remove-fact, so
+NAME can be used by all of them and by --relation.
 
 --verify judges facts the dataset may already state: every (head, relation, tail) -- one from the command line, or the
 `head relation tail` lines of FILE -- is scored on the graph WITHOUT itself and its inverse edge (Predictor.verify_tails; with
@@ -75,6 +81,10 @@ def main(argv=None):
                     help="introduce a new entity before the query; repeatable, applied in order with the fact options")
     ap.add_argument("--entity-capacity", type=int, default=None, metavar="M",
                     help="rows reserved for new entities (default: the number of --add-entity options)")
+    ap.add_argument("--add-relation", action="append", default=[], metavar="NAME",
+                    help="introduce a new relation type before the facts and the query; repeatable")
+    ap.add_argument("--relation-capacity", type=int, default=None, metavar="K",
+                    help="slots reserved for new relation types (default: the number of --add-relation options)")
     ap.set_defaults(edits=[])
     args = ap.parse_args(argv)
     if args.verify:
@@ -96,6 +106,14 @@ def main(argv=None):
     new_names = [name for kind, name in args.edits if kind is None]
     if args.entity_capacity is not None and args.entity_capacity < 0:
         sys.exit("--entity-capacity must not be negative")
+    if args.relation_capacity is not None and args.relation_capacity < 0:
+        sys.exit("--relation-capacity must not be negative")
+    rel = list(rel)
+    num_old_relations = len(rel)
+    for name in args.add_relation:      # (applied before the facts: usable by every one of them and by --relation)
+        if name in rel:
+            sys.exit("--add-relation %r: the relation exists" % name)
+        rel.append(name)
     known = set(ent)        # (grows along the command line: a name can be used after its --add-entity)
     checks = []
     for kind, value in args.edits:
@@ -121,10 +139,20 @@ def main(argv=None):
         print("no --ckpt: randomly initialised weights, the answers mean nothing")
     model = model.to(dev).eval()
     reserve = len(new_names) if args.entity_capacity is None else args.entity_capacity
+    rel_reserve = len(args.add_relation) if args.relation_capacity is None else args.relation_capacity
     if facts is not None:
-        predictor = predict.Predictor(model, data, batch_size=min(8, len(facts)), entity_capacity=reserve)
+        predictor = predict.Predictor(model, data, batch_size=min(8, len(facts)), entity_capacity=reserve,
+                                      relation_capacity=rel_reserve)
     else:
-        predictor = predict.Predictor(model, data, k=args.k, batch_size=1, filtered=not args.unfiltered, entity_capacity=reserve)
+        predictor = predict.Predictor(model, data, k=args.k, batch_size=1, filtered=not args.unfiltered, entity_capacity=reserve,
+                                      relation_capacity=rel_reserve)
+    for name in args.add_relation:
+        if not rel_reserve:
+            sys.exit("--add-relation needs --relation-capacity above 0")
+        (new_id,) = predictor.add_relations(1).tolist()
+        assert rel[new_id] == name and new_id >= num_old_relations
+        print("relation %r added as id %d (%d of %d slots in use)"
+              % (name, new_id, predictor.num_direct_relations, predictor.num_relation_slots))
     ent = list(ent)
     at = 0
     while at < len(args.edits):        # (runs of one kind go in one call)

@@ -42,6 +42,8 @@ ARR_DENSE_ORDER = 8
 # the layer update's flag bits: ULTRA_CONV_* and, for ultra_nbf_layer0 alone, ULTRA_LAYER0_* (include/ultra_nbfnet.h)
 CONV_LAYER_NORM, CONV_RELU, CONV_RESIDUAL = 1, 2, 4
 LAYER0_MAX, LAYER0_ONLY_FILL, LAYER0_SKIP_FILL = 8, 16, 32
+# the bits of ultra_relation_graph_add_edges' `changed` word
+RELGRAPH_CHANGED, RELGRAPH_OUT_OF_RANGE = 1, 2
 
 
 class UltraMat(ctypes.Structure):
@@ -206,6 +208,7 @@ def _load():
     lib.ultra_relation_graph_dense_adjacency.argtypes = [vp, i64, vp, vp]
     lib.ultra_relation_graph_bits_keep.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]
     lib.ultra_relation_graph_edge_keep.argtypes = [vp, i64, vp, vp, i64, vp, vp]
+    lib.ultra_relation_graph_add_edges.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp]
     lib.ultra_symbolic_traversal_keep.argtypes = [vp, vp, vp, vp, i64, vp, i64, i32, vp, vp, vp]
     lib.ultra_traversal_dropout_mask_words.argtypes = [i64]
     lib.ultra_traversal_dropout_mask_words.restype = i64

@@ -13,6 +13,8 @@
 //      reference's relation_graph.edge_index / edge_type element for element;
 //   4. dense_order_adjacency_kernel : the same bit matrices as the byte adjacency of the reference-order layer kernel
 //      (dense_order_layer.hip, plan.hpp `a_ex`): plan format straight from the device, no edge list in between.
+//   5. add_edges_*_kernel : the bit sets of 1. and 2. kept RESIDENT and brought up to date for appended edges -- the relation graph
+//      is monotone under additions -- at the cost of those edges and their endpoints' bit sets (ultra_relation_graph_add_edges).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -39,39 +41,105 @@ __global__ void __launch_bounds__(256) incidence_bits_kernel(const int64_t *__re
     }
 }
 
-// one wave per entity; lane w owns word w (+ 64, ...) of the relation bit sets
+// row word |= bits, skipped where the row already holds them.  TRACK: did this lane add a bit -- read off the atomic's old value,
+// so a bit another wave set first is not counted
+template <bool TRACK>
+__device__ __forceinline__ bool or_into(uint32_t *word, uint32_t bits) {
+    if (!(bits & ~*word)) return false;
+    if (!TRACK) {
+        atomicOr(word, bits);
+        return false;
+    }
+    return (bits & ~atomicOr(word, bits)) != 0;
+}
+
+// the whole pair marking of entity n by one wave; lane w owns word w (+ 64, ...) of the relation bit sets.  TRACK: returns whether
+// this lane added a bit to adj
+template <bool TRACK>
+__device__ __forceinline__ bool mark_entity_pairs(const uint32_t *__restrict__ hbits, const uint32_t *__restrict__ tbits, long long n,
+                                                  int lane, int words, size_t mat, uint32_t *__restrict__ adj) {
+    bool added = false;
+    for (int w0 = 0; w0 < words; w0 += 64) {           // the words this lane ORs into the rows
+        const int w = w0 + lane;
+        const uint32_t hv = w < words ? hbits[n * words + w] : 0u, tv = w < words ? tbits[n * words + w] : 0u;
+        for (int s = 0; s < words; ++s) {              // the relations (rows) of this entity, word by word (wave-uniform)
+            uint32_t hs = hbits[n * words + s], ts = tbits[n * words + s];
+            while (hs) {
+                const int r1 = 32 * s + __builtin_ctz(hs);
+                hs &= hs - 1;
+                if (w < words) {
+                    uint32_t *a = adj + 0 * mat + (size_t)r1 * words + w, *b = adj + 2 * mat + (size_t)r1 * words + w;
+                    added |= or_into<TRACK>(a, hv);     // hh
+                    added |= or_into<TRACK>(b, tv);     // ht
+                }
+            }
+            while (ts) {
+                const int r1 = 32 * s + __builtin_ctz(ts);
+                ts &= ts - 1;
+                if (w < words) {
+                    uint32_t *a = adj + 1 * mat + (size_t)r1 * words + w, *b = adj + 3 * mat + (size_t)r1 * words + w;
+                    added |= or_into<TRACK>(a, tv);     // tt
+                    added |= or_into<TRACK>(b, hv);     // th
+                }
+            }
+        }
+    }
+    return added;
+}
+
+// one wave per entity
 __global__ void __launch_bounds__(256) pair_mark_kernel(const uint32_t *__restrict__ hbits, const uint32_t *__restrict__ tbits,
                                                         long long num_node, int num_rel, int words, uint32_t *__restrict__ adj) {
     const int lane = threadIdx.x & 63;
     const long long wave = (blockIdx.x * (long long)blockDim.x + threadIdx.x) >> 6, nwave = ((long long)gridDim.x * blockDim.x) >> 6;
     const size_t mat = (size_t)num_rel * words;    // words per type matrix; adj = [hh | tt | ht | th]
-    for (long long n = wave; n < num_node; n += nwave) {
-        for (int w0 = 0; w0 < words; w0 += 64) {           // the words this lane ORs into the rows
-            const int w = w0 + lane;
-            const uint32_t hv = w < words ? hbits[n * words + w] : 0u, tv = w < words ? tbits[n * words + w] : 0u;
-            for (int s = 0; s < words; ++s) {              // the relations (rows) of this entity, word by word (wave-uniform)
-                uint32_t hs = hbits[n * words + s], ts = tbits[n * words + s];
-                while (hs) {
-                    const int r1 = 32 * s + __builtin_ctz(hs);
-                    hs &= hs - 1;
-                    if (w < words) {
-                        uint32_t *a = adj + 0 * mat + (size_t)r1 * words + w, *b = adj + 2 * mat + (size_t)r1 * words + w;
-                        if (hv & ~*a) atomicOr(a, hv);     // hh
-                        if (tv & ~*b) atomicOr(b, tv);     // ht
-                    }
-                }
-                while (ts) {
-                    const int r1 = 32 * s + __builtin_ctz(ts);
-                    ts &= ts - 1;
-                    if (w < words) {
-                        uint32_t *a = adj + 1 * mat + (size_t)r1 * words + w, *b = adj + 3 * mat + (size_t)r1 * words + w;
-                        if (tv & ~*a) atomicOr(a, tv);     // tt
-                        if (hv & ~*b) atomicOr(b, hv);     // th
-                    }
-                }
-            }
-        }
+    for (long long n = wave; n < num_node; n += nwave) mark_entity_pairs<false>(hbits, tbits, n, lane, words, mat, adj);
+}
+
+// ---- edges added to resident bit sets (ultra_relation_graph_add_edges) ----
+// status word: bit 0 = a bit was added to adj, bit 1 = an index lies outside the graph (then nothing is marked)
+constexpr int32_t ADD_CHANGED = 1, ADD_OUT_OF_RANGE = 2;
+
+// one block: every index is looked at before anything is marked, and the status word is written whole (no zeroing by the caller)
+__global__ void __launch_bounds__(1024) add_edges_check_kernel(const int64_t *__restrict__ edge_index, const int64_t *__restrict__ edge_type,
+                                                               long long num_edge, long long num_node, long long num_rel,
+                                                               int32_t *__restrict__ status) {
+    int bad = 0;
+    for (long long e = threadIdx.x; e < num_edge; e += blockDim.x) {
+        const long long h = edge_index[e], t = edge_index[num_edge + e], r = edge_type[e];
+        bad |= h < 0 || h >= num_node || t < 0 || t >= num_node || r < 0 || r >= num_rel;
     }
+    bad = __syncthreads_or(bad);
+    if (threadIdx.x == 0) *status = bad ? ADD_OUT_OF_RANGE : 0;
+}
+
+// incidence_bits_kernel for the added edges, behind the check
+__global__ void __launch_bounds__(256) add_edges_incidence_kernel(const int64_t *__restrict__ edge_index, const int64_t *__restrict__ edge_type,
+                                                                  long long num_edge, int words, uint32_t *__restrict__ hbits,
+                                                                  uint32_t *__restrict__ tbits, const int32_t *__restrict__ status) {
+    if (*status & ADD_OUT_OF_RANGE) return;
+    for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < num_edge; e += (long long)gridDim.x * blockDim.x) {
+        const long long h = edge_index[e], t = edge_index[num_edge + e], r = edge_type[e];
+        const uint32_t bit = 1u << (r & 31);
+        uint32_t *hw = hbits + h * words + (r >> 5), *tw = tbits + t * words + (r >> 5);
+        if (!(*hw & bit)) atomicOr(hw, bit);
+        if (!(*tw & bit)) atomicOr(tw, bit);
+    }
+}
+
+// one wave per listed endpoint (the 2 num_edge entries of edge_index): the pair marking of pair_mark_kernel for that entity.  A
+// repeated endpoint repeats idempotent ORs.  `status` is read for bit 1 only, which no wave of this launch writes.
+__global__ void __launch_bounds__(256) add_edges_pair_kernel(const int64_t *__restrict__ edge_index, long long num_endpoint,
+                                                             const uint32_t *__restrict__ hbits, const uint32_t *__restrict__ tbits,
+                                                             int num_rel, int words, uint32_t *__restrict__ adj, int32_t *status) {
+    if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ADD_OUT_OF_RANGE) return;
+    const int lane = threadIdx.x & 63;
+    const long long wave = (blockIdx.x * (long long)blockDim.x + threadIdx.x) >> 6, nwave = ((long long)gridDim.x * blockDim.x) >> 6;
+    const size_t mat = (size_t)num_rel * words;
+    bool added = false;
+    for (long long i = wave; i < num_endpoint; i += nwave)
+        added |= mark_entity_pairs<true>(hbits, tbits, edge_index[i], lane, words, mat, adj);
+    if (added) atomicOr(status, ADD_CHANGED);
 }
 
 __global__ void __launch_bounds__(256) row_count_kernel(const uint32_t *__restrict__ adj, int rows_total, int words,
@@ -209,6 +277,38 @@ int32_t ultra_relation_graph_bits_keep(const int64_t *edge_index_dev, const int6
     }
     return relation_graph_bits(edge_index_dev, edge_type_dev, keep_dev, num_edge, num_node, num_relation, hbits_dev, tbits_dev, adj_dev,
                                row_counts_dev, stream);
+}
+
+int32_t ultra_relation_graph_add_edges(const int64_t *edge_index_dev, const int64_t *edge_type_dev, int64_t num_edge, int64_t num_node,
+                                       int64_t num_relation, void *hbits_dev, void *tbits_dev, void *adj_dev, int64_t *row_counts_dev,
+                                       int32_t *changed_dev, void *stream) {
+    ULTRA_DEVICE_SCOPE(stream, adj_dev);
+    if (num_edge < 0 || num_node <= 0 || num_relation <= 0 || num_relation > (1 << 20) || (num_edge > 0 && (!edge_index_dev || !edge_type_dev)) ||
+        !hbits_dev || !tbits_dev || !adj_dev || !row_counts_dev || !changed_dev) {
+        set_error("ultra_relation_graph_add_edges: bad argument");
+        return ULTRA_ERR_INVALID;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int words = (int)((num_relation + 31) / 32);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(add_edges_check_kernel, dim3(1), dim3(1024), 0, s, edge_index_dev, edge_type_dev, (long long)num_edge,
+                       (long long)num_node, (long long)num_relation, changed_dev);
+    if (num_edge > 0) {
+        hipLaunchKernelGGL(add_edges_incidence_kernel, dim3((unsigned)std::min<int64_t>((num_edge + 255) / 256, 4096)), dim3(256), 0, s,
+                           edge_index_dev, edge_type_dev, (long long)num_edge, words, (uint32_t *)hbits_dev, (uint32_t *)tbits_dev,
+                           (const int32_t *)changed_dev);
+        hipLaunchKernelGGL(add_edges_pair_kernel, dim3((unsigned)std::min<int64_t>((2 * num_edge + 3) / 4, 8192)), dim3(256), 0, s,
+                           edge_index_dev, (long long)(2 * num_edge), (const uint32_t *)hbits_dev, (const uint32_t *)tbits_dev,
+                           (int)num_relation, words, (uint32_t *)adj_dev, changed_dev);
+    }
+    const int rows_total = (int)(4 * num_relation);
+    hipLaunchKernelGGL(row_count_kernel, dim3((rows_total + 255) / 256), dim3(256), 0, s, (const uint32_t *)adj_dev, rows_total, words,
+                       row_counts_dev);
+    if (hipGetLastError() != hipSuccess) {
+        set_error("ultra_relation_graph_add_edges: launch failed");
+        return ULTRA_ERR_HIP;
+    }
+    return ULTRA_OK;
 }
 
 int32_t ultra_relation_graph_emit(const void *adj_dev, const int64_t *row_offsets_dev, int64_t num_relation, int64_t total_edges,

@@ -9,7 +9,9 @@ delta is folded into the graph, which ids are live, and what `materialized()` me
   with_facts       a copy of a graph with facts appended the way GraphDelta.materialize appends them
   without_facts    ... without every edge of the facts
   with_slots       ... with reserved rows
+  with_relation_slots / compact_relations   ... laid out over reserved relation slots, and back in the compact numbering
   check_live       ValueError for an id in the reserve
+  check_live_relations   ... for a relation id that is no direct relation in use
   forwarded        a read-only property of an owner that reads a field of its LiveGraph
 """
 import copy
@@ -55,6 +57,40 @@ def with_slots(graph, slots, relation_graph=False):
     return out
 
 
+def _renumbered(graph, old_direct, new_direct, relation_graph):
+    out = copy.copy(graph)
+    out.num_relations = 2 * int(new_direct)
+    if new_direct != old_direct:
+        out.edge_type = torch.where(graph.edge_type >= old_direct, graph.edge_type + (new_direct - old_direct), graph.edge_type)
+    if relation_graph and getattr(graph, "relation_graph", None) is not None:
+        tasks.build_relation_graph(out)
+    return out
+
+
+def with_relation_slots(graph, direct_slots, direct_live, relation_graph=True):
+    """A shallow copy of `graph` -- direct_live direct relations, inverse type r + direct_live -- laid out over direct_slots >=
+    direct_live direct relation SLOTS: num_relations = 2 direct_slots, every inverse type moved to r + direct_slots, the edge
+    order untouched.  relation_graph: build the copy's own where `graph` carries one -- over the 2 direct_slots
+    nodes, the slots without a relation isolated."""
+    if int(direct_slots) < int(direct_live):
+        raise ValueError("%d direct relations do not fit %d slots" % (direct_live, direct_slots))
+    return _renumbered(graph, int(direct_live), int(direct_slots), relation_graph)
+
+
+def compact_relations(graph, direct_slots, direct_live, relation_graph=True):
+    """The inverse of with_relation_slots: `graph`, laid out over direct_slots slots of which the ids below direct_live are in
+    use, in the compact numbering -- num_relations = 2 direct_live, inverse type r + direct_live."""
+    return _renumbered(graph, int(direct_slots), int(direct_live), relation_graph)
+
+
+def check_live_relations(ids, num_live, what):
+    """ValueError unless every id is a direct relation in use: ids in [0, num_live) (a graph with reserved relation slots; one
+    host read)."""
+    if len(ids) and bool(((ids < 0) | (ids >= num_live)).any()):
+        raise ValueError("%s must be direct relations in use (ids in [0, %d)): a reserved slot is no relation until "
+                         "add_relations hands it out" % (what, num_live))
+
+
 def check_live(ids, num_live, what):
     """ValueError unless every id is an entity in use: ids in [0, num_live) (a graph with reserved rows; one host read)."""
     if len(ids) and bool(((ids < 0) | (ids >= num_live)).any()):
@@ -72,7 +108,10 @@ class LiveGraph(object):
     """data: the graph to serve; delta_capacity: the facts (added + retracted) held in an rspmm.GraphDelta beside it before they
     are folded into it; entity_capacity=M > 0: M rows reserved for entities that arrive later -- `graph` is then a shallow copy
     of `data` with num_nodes = N + M slots and its own relation graph, `num_entities` of them live, and `live_count` one device
-    int64 that holds the same number for the owner's life (None without a reserve).
+    int64 that holds the same number for the owner's life (None without a reserve).  relation_capacity=K > 0: K
+    direct relation slots reserved for relations that arrive later -- `graph` is then laid out over R + K direct slots
+    (with_relation_slots; the filter graph alike), `num_direct_relations` of them in use.  relation_bits_budget: the delta's
+    (rspmm.GraphDelta).
 
     delta_policy: when the delta exists.  "eager": from construction, and a new empty one after every compaction (a captured
     step is handed the delta before the first edit).  "lazy": None until the first edit and None again after a compaction (an
@@ -86,22 +125,31 @@ class LiveGraph(object):
     graph, before `graph` is replaced."""
 
     def __init__(self, data, delta_capacity=256, entity_capacity=0, filter_data=None, keep_filter=False, delta_policy="lazy",
-                 owner="LiveGraph", on_rebuild=None):
+                 owner="LiveGraph", on_rebuild=None, relation_capacity=0, relation_bits_budget=256 << 20):
         if isinstance(entity_capacity, bool) or not isinstance(entity_capacity, int) or entity_capacity < 0:
             raise ValueError("entity_capacity must be a non-negative int (reserved rows), got %r" % (entity_capacity,))
+        if isinstance(relation_capacity, bool) or not isinstance(relation_capacity, int) or relation_capacity < 0:
+            raise ValueError("relation_capacity must be a non-negative int (reserved relation slots), got %r" % (relation_capacity,))
         if isinstance(delta_capacity, bool) or not isinstance(delta_capacity, int) or delta_capacity < 1:
             raise ValueError("delta_capacity must be a positive int (facts), got %r" % (delta_capacity,))
         if delta_policy not in ("eager", "lazy", "never"):
             raise ValueError("delta_policy must be 'eager', 'lazy' or 'never', got %r" % (delta_policy,))
         self.entity_capacity, self.delta_capacity = entity_capacity, delta_capacity
+        self.relation_capacity, self.relation_bits_budget = relation_capacity, relation_bits_budget
         self.num_entities = int(data.num_nodes)
+        self.num_direct_relations = int(data.num_relations) // 2
         self.live_count = None
         if entity_capacity:
             slots = self.num_entities + entity_capacity
-            data = with_slots(data, slots, relation_graph=True)
+            data = with_slots(data, slots, relation_graph=not relation_capacity)
             if filter_data is not None:
                 filter_data = with_slots(filter_data, slots)
             self.live_count = torch.full((1,), self.num_entities, dtype=torch.long, device=data.edge_index.device)
+        if relation_capacity:
+            direct = self.num_direct_relations
+            data = with_relation_slots(data, direct + relation_capacity, direct)
+            if filter_data is not None:
+                filter_data = with_relation_slots(filter_data, direct + relation_capacity, direct, relation_graph=False)
         self.graph = data
         self._policy, self._owner, self._on_rebuild = delta_policy, owner, on_rebuild
         self.filter_graph = self._filter_base = None
@@ -116,8 +164,14 @@ class LiveGraph(object):
         """The rows of the served graph: num_entities live ones and the rest of the reserve."""
         return int(self.graph.num_nodes)
 
+    @property
+    def num_relation_slots(self):
+        """The direct relation slots of the served graph: num_direct_relations in use and the rest of the reserve."""
+        return int(self.graph.num_relations) // 2
+
     def _new_delta(self, capacity=None):
-        return rspmm.GraphDelta(self.graph, self.delta_capacity if capacity is None else capacity, num_live=self.num_entities)
+        return rspmm.GraphDelta(self.graph, self.delta_capacity if capacity is None else capacity, num_live=self.num_entities,
+                                num_live_relations=self.num_direct_relations, relation_bits_budget=self.relation_bits_budget)
 
     def _probe(self):
         """A delta to check arguments with or to materialise through: the one held, or an empty one."""
@@ -160,13 +214,37 @@ class LiveGraph(object):
             self.delta.num_live = self.num_entities
         return torch.arange(first, first + count, dtype=torch.long, device=self.graph.edge_index.device)
 
+    def add_relations(self, count=1, compact=None):
+        """`count` new direct relations: their ids [num_direct_relations, num_direct_relations + count), and the live count
+        raised, here and in the delta.  No plan, no relation graph, no capture: a slot without facts is an isolated node the
+        relation graph already holds.  Beyond the reserve num_direct_relations + count + relation_capacity slots are laid out
+        by `compact(relation_slots=...)` -- this object's, or the owner's own where it hands that in."""
+        if not self.relation_capacity:
+            raise ValueError("this %s reserves no relation slots: create it with relation_capacity > 0 to add relations" % self._owner)
+        if isinstance(count, bool) or not isinstance(count, int) or count < 1:
+            raise ValueError("count must be a positive int, got %r" % (count,))
+        first = self.num_direct_relations
+        if first + count > self.num_relation_slots:
+            (compact or self.compact)(relation_slots=first + count + self.relation_capacity)
+        self.num_direct_relations = first + count
+        if self.delta is not None:
+            self.delta.num_live_relations = self.num_direct_relations
+        return torch.arange(first, first + count, dtype=torch.long, device=self.graph.edge_index.device)
+
     def materialized(self):
         """The served edge list with the delta's edits (GraphDelta.materialize) and num_nodes = num_entities -- no reserved row --
-        with the filter graph held now as its `filtered_data` where that is a graph of its own.  A new copy at every call."""
+        with the filter graph held now as its `filtered_data` where that is a graph of its own.  With reserved relation slots:
+        in the compact numbering -- num_relations = 2 num_direct_relations, inverse type r + num_direct_relations, the relation
+        graph built for it (the filter graph alike).  A new copy at every call."""
         out = copy.copy(self._probe().materialize(self.graph, num_nodes=self.num_entities))
+        slots, live = self.num_relation_slots, self.num_direct_relations
+        if self.relation_capacity:
+            out = compact_relations(out, slots, live)
         if self.filter_graph is not None and not self._filter_is_graph:     # (the one held now, the stated facts included)
             out.filtered_data = copy.copy(self.filter_graph)
             out.filtered_data.num_nodes = self.num_entities
+            if self.relation_capacity:
+                out.filtered_data = compact_relations(out.filtered_data, slots, live, relation_graph=False)
         return out
 
     # ---- the changing graph ----
@@ -213,11 +291,12 @@ class LiveGraph(object):
             fh, fr, ft = self.delta.facts[:len(self.delta)].unbind(1)
             self.filter_graph = with_facts(self._filter_base, fh, fr, ft)
 
-    def compact(self, extra=None, delta=None, slots=None):
+    def compact(self, extra=None, delta=None, slots=None, relation_slots=None):
         """Fold the delta's edits (and `extra` = (h, r, t), checked by the caller) into the served graph: the materialised graph
         -- without the tombstoned edges, with the added ones, its relation graph rebuilt -- becomes `graph`, and the delta is
         emptied.  `delta`: fold that one instead of the one held.  The slot count and the live count of a graph with reserved
-        rows stay; `slots` (add_entities beyond the reserve): the new slot count, laid out in the same rebuild."""
+        rows stay; `slots` (add_entities beyond the reserve): the new slot count, laid out in the same rebuild; `relation_slots`
+        (add_relations beyond the reserve): the new count of direct relation slots, the inverse types renumbered in it."""
         delta = self.delta if delta is None else delta
         facts = [] if delta is None else [delta.facts[:len(delta)]]
         if extra is not None:
@@ -225,7 +304,10 @@ class LiveGraph(object):
         facts = torch.cat(facts) if facts else torch.zeros(0, 3, dtype=torch.long)
         if slots is not None and int(slots) == self.num_slots:
             slots = None
-        if len(facts) == 0 and not (delta is not None and delta.num_removed) and slots is None:
+        old_rel = self.num_relation_slots
+        if relation_slots is not None and int(relation_slots) == old_rel:
+            relation_slots = None
+        if len(facts) == 0 and not (delta is not None and delta.num_removed) and slots is None and relation_slots is None:
             return
         fh, fr, ft = facts.unbind(1)
         base = self.graph
@@ -235,6 +317,8 @@ class LiveGraph(object):
         graph = with_facts(base, fh, fr, ft)
         if slots is not None:
             graph.num_nodes = int(slots)
+        if relation_slots is not None:      # (the in-use ids lie below both counts: only the inverse types move)
+            graph = _renumbered(graph, old_rel, int(relation_slots), relation_graph=False)
         if getattr(self.graph, "relation_graph", None) is not None:
             tasks.build_relation_graph(graph)
         if self.filter_graph is not None:
@@ -244,6 +328,8 @@ class LiveGraph(object):
                 self._filter_base = with_facts(self._filter_base, fh, fr, ft)
                 if slots is not None:
                     self._filter_base.num_nodes = int(slots)
+                if relation_slots is not None:
+                    self._filter_base = _renumbered(self._filter_base, old_rel, int(relation_slots), relation_graph=False)
             self.filter_graph = self._filter_base
         if self._on_rebuild is not None:
             self._on_rebuild()

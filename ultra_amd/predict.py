@@ -33,7 +33,7 @@ import torch
 
 from . import _lib, dense, models, tasks
 from .graph import Capture, param_state
-from .live import LiveGraph, check_live, forwarded
+from .live import LiveGraph, check_live, check_live_relations, forwarded
 
 
 def _live_int(num_live, n):
@@ -351,14 +351,15 @@ def delta_samples_supported(model):
             and all(getattr(layer, "delta_samples_supported", lambda: False)() for layer in layers))
 
 
-def _check_facts(data, h, r, t, num_live=None):
+def _check_facts(data, h, r, t, num_live=None, num_direct=None):
     """(h, r, t) of verify_*: int64 vectors of one length on the graph's device, r a direct relation (ValueError otherwise);
-    num_live (a graph with reserved rows): h and t below it."""
+    num_live (a graph with reserved rows): h and t below it; num_direct (a graph with reserved relation slots): the direct
+    relations in use, in place of num_relations // 2."""
     dev = data.edge_index.device
     h, r, t = (torch.as_tensor(v, dtype=torch.long, device=dev).flatten() for v in (h, r, t))
     if not (h.shape == r.shape == t.shape):
         raise ValueError("one head, relation and tail per fact: got %d heads, %d relations and %d tails" % (len(h), len(r), len(t)))
-    direct = int(data.num_relations) // 2
+    direct = int(data.num_relations) // 2 if num_direct is None else int(num_direct)
     if len(r) and bool(((r < 0) | (r >= direct)).any()):
         raise ValueError("verify takes direct relations (r < num_relations // 2 = %d): a fact stated through an inverse relation "
                          "is its direct twin" % direct)
@@ -506,10 +507,19 @@ class Predictor(object):
     [num_entities, slots) is a ValueError everywhere and never an answer.  Every result is that of a fresh
     Predictor(entity_capacity=0) on delta.materialize(data, num_nodes=num_entities).  A call that would exceed the reserve
     compacts and reserves M rows anew (one rebuild).  entity_capacity=0 (the default): `data` itself is served, by exactly the
-    entry points of before, and add_entities raises."""
+    entry points of before, and add_entities raises.
+
+    A growing VOCABULARY: relation_capacity=K > 0 reserves K direct relation slots for relation types that arrive
+    later.  The graph served is then a shallow copy of `data` laid out over R + K direct slots (num_relations = 2 (R + K), every
+    inverse type moved from r + R to r + R + K, its own relation graph in which the unused slots are isolated nodes),
+    `num_direct_relations` of them in use; add_relations(count) hands out the next direct ids and does nothing else.  A relation
+    argument is a direct relation below num_direct_relations everywhere (ValueError otherwise), and every relation id handed back
+    -- materialized(), the paths of explain_* -- is in the compact numbering, inverse type r + num_direct_relations.  Every result
+    is that of a fresh Predictor on materialized().  explain_* and verify_* compact first where the delta is edited (the slot
+    counts stay).  Both reserves may be used together.  relation_bits_budget: rspmm.GraphDelta's."""
 
     def __init__(self, model, data, k=10, batch_size=8, filtered_data=None, filtered=True, use_graph=True, delta_capacity=256,
-                 entity_capacity=0):
+                 entity_capacity=0, relation_capacity=0, relation_bits_budget=256 << 20):
         check_k(k)
         if filtered_data is None:
             filtered_data = getattr(data, "filtered_data", None)
@@ -523,7 +533,8 @@ class Predictor(object):
         # (a rebuild drops the captures.  The hook holds the dict, not the predictor: no cycle, so __del__ runs with the last reference)
         self._live = LiveGraph(data, delta_capacity, entity_capacity, filter_data=filtered_data, keep_filter=True,
                                delta_policy="eager" if takes_delta else "never", owner="Predictor",
-                               on_rebuild=functools.partial(_release, self._steps))
+                               on_rebuild=functools.partial(_release, self._steps), relation_capacity=relation_capacity,
+                               relation_bits_budget=relation_bits_budget)
         self.model, self.k, self.batch_size = model, k, int(batch_size)
         self.filtered, self.use_graph = bool(filtered), bool(use_graph)
 
@@ -536,6 +547,19 @@ class Predictor(object):
     num_entities = forwarded("num_entities")
     num_slots = forwarded("num_slots")
     live_count = forwarded("live_count")
+    relation_capacity = forwarded("relation_capacity")
+    num_direct_relations = forwarded("num_direct_relations")
+    num_relation_slots = forwarded("num_relation_slots")
+
+    # ---- the growing vocabulary ----
+    def add_relations(self, count=1):
+        """`count` new relation types: returns their direct ids [num_direct_relations, num_direct_relations + count) (int64, on
+        the graph's device) and raises the live count.  Nothing else happens -- no plan, no relation graph, no capture: a slot
+        without facts is an isolated node the relation graph already holds; add_facts / tails / heads / ... take the ids from
+        now on, and the first facts through one cost what any fact that changes the relation graph costs.  Beyond the reserve
+        the graph is compacted and num_direct_relations + count + relation_capacity slots are laid out: one rebuild.
+        ValueError on a predictor without a reserve (relation_capacity=0)."""
+        return self._live.add_relations(count, compact=self.compact)
 
     # ---- the growing graph ----
     def add_entities(self, count=1):
@@ -568,13 +592,14 @@ class Predictor(object):
         (GraphDelta.remove).  Compacts first where the delta cannot hold the tombstones."""
         return self._live.remove_facts(h, r, t)
 
-    def compact(self, extra=None, delta=None, slots=None):
+    def compact(self, extra=None, delta=None, slots=None, relation_slots=None):
         """Fold the delta's edits (and `extra` = (h, r, t), checked by the caller) into `data`: the materialised graph -- without
         the tombstoned edges, with the added ones -- becomes the served graph -- its relation graph rebuilt, a host plan on the
         next query, new captures -- and the delta is emptied.  `delta`: fold that one instead of the Predictor's own.  The
-        slot count and the live count of a graph with reserved rows stay; `slots` (add_entities beyond the reserve): the new
-        slot count, laid out in the same rebuild."""
-        self._live.compact(extra, delta, slots)
+        slot counts and the live counts of a graph with reserved rows or relation slots stay; `slots` (add_entities beyond the
+        reserve): the new slot count, laid out in the same rebuild; `relation_slots` (add_relations beyond its reserve): the
+        new count of direct relation slots."""
+        self._live.compact(extra, delta, slots, relation_slots)
 
     def _model_kwargs(self):
         delta = self.delta      # (handed over whenever it exists, empty or not: the capture relies on it)
@@ -629,6 +654,10 @@ class Predictor(object):
         cols = torch.tensor([j for c in counts for j in range(c)], dtype=torch.long, device=dev)
         triples = torch.stack([anchor[rows], ids[rows, cols], relation[rows]], dim=-1)
         flat = self.model.visualize_batch(self.data, triples, chunk=chunk) if len(rows) else []
+        slots, live = self.num_relation_slots, self.num_direct_relations
+        if slots != live:       # (the caller sees the compact numbering of materialized(): inverse type r + live)
+            flat = [(type(paths)([(h, t, r - (slots - live) if r >= slots else r) for h, t, r in path] for path in paths), weights)
+                    for paths, weights in flat]
         explanations, at = [], 0
         for c in counts:
             explanations.append(flat[at:at + c])
@@ -695,10 +724,12 @@ class Predictor(object):
 
     @torch.no_grad()
     def _verify(self, h, r, t, mode):
-        h, r, t = _check_facts(self.data, h, r, t, num_live=self.num_entities if self.entity_capacity else None)
-        if self.delta is not None and self.delta.edited and (self.entity_capacity or not delta_samples_supported(self.model)):
+        h, r, t = _check_facts(self.data, h, r, t, num_live=self.num_entities if self.entity_capacity else None,
+                               num_direct=self.num_direct_relations if self.relation_capacity else None)
+        if self.delta is not None and self.delta.edited and (self.entity_capacity or self.relation_capacity
+                                                             or not delta_samples_supported(self.model)):
             # a model without the combined route: the keep masks run over the graph's own edge list.  A graph with reserved rows
-            # keeps DESIGN.md 19's rule -- compact first, the slot count and the live count stay -- which its tests pin
+            # or relation slots keeps DESIGN.md 19's rule -- compact first, the slot counts and the live counts stay
             self.compact()
         data, bs, live_count, delta = self.data, self.batch_size, self.live_count, self.delta
         live = delta is not None and delta.edited      # (the edits stay beside the plan: leave_out= with the delta)
@@ -771,6 +802,8 @@ class Predictor(object):
             raise ValueError("one relation per query: got %d entities and %d relations" % (len(anchor), len(relation)))
         if self.entity_capacity:
             check_live(anchor, self.num_entities, "the anchors of a query")
+        if self.relation_capacity:
+            check_live_relations(relation, self.num_direct_relations, "the relations of a query")
         n = len(anchor)
         out_ptr, ids, scores, size = [torch.zeros(1, dtype=torch.long, device=dev)], [], [], []
         was_training = self.model.training
@@ -814,6 +847,8 @@ class Predictor(object):
             raise ValueError("one relation per query: got %d entities and %d relations" % (len(anchor), len(relation)))
         if self.entity_capacity:
             check_live(anchor, self.num_entities, "the anchors of a query")
+        if self.relation_capacity:
+            check_live_relations(relation, self.num_direct_relations, "the relations of a query")
         n = len(anchor)
         ids = torch.empty(n, k, dtype=torch.long, device=dev)
         scores = torch.empty(n, k, dtype=torch.float32, device=dev)

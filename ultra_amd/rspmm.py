@@ -742,9 +742,21 @@ class GraphDelta(object):
     A GROWING graph: `data` may hold reserved rows -- num_nodes counts SLOTS, of which the ids below `num_live`
     are entities in use.  num_nodes stays what the plan check of Plan.delta_rows / edit_rows compares and what sizes `degree`
     and the key codes; `check` takes the live bound, which the owner raises as entities arrive (Predictor.add_entities), and
-    materialize(num_nodes=num_live) is the graph a fresh predictor would be given."""
+    materialize(num_nodes=num_live) is the graph a fresh predictor would be given.
 
-    def __init__(self, data, capacity=1024, num_live=None):
+    A growing VOCABULARY (DESIGN.md 24): `data` may be laid out over reserved relation slots -- num_relations // 2 counts the
+    direct SLOTS (it stays the inverse offset of edges() and the served numbering), of which the ids below `num_live_relations`
+    are relations in use: the bound `check` takes, raised by the owner as relations arrive (Predictor.add_relations).
+
+    The relation graph kept current: on the GPU, add() does not rebuild the relation graph from all base edges.
+    The entities' relation bit sets and the four adjacency bit matrices stay resident (`_resident`, seeded at the first add()
+    by ultra_relation_graph_bits while the two (num_nodes, W) bit sets fit `relation_bits_budget` bytes), add() runs
+    ultra_relation_graph_add_edges over the new facts' edges alone and reads its `changed` word: unchanged -- the relation-graph
+    object is kept; changed -- a new one is emitted from a copy of the resident matrices.  remove() cannot clear bits: it
+    rebuilds from the edge list as before and drops the resident state, which the next add() seeds again.  `_full_rebuild`
+    (tools and tests only): True forces the rebuild from the edge list at every add()."""
+
+    def __init__(self, data, capacity=1024, num_live=None, num_live_relations=None, relation_bits_budget=256 << 20):
         if not isinstance(capacity, int) or capacity < 1:
             raise ValueError("capacity must be a positive int (facts), got %r" % (capacity,))
         self.base = data
@@ -752,6 +764,13 @@ class GraphDelta(object):
         self.num_live = self.num_nodes if num_live is None else int(num_live)
         if not 0 <= self.num_live <= self.num_nodes:
             raise ValueError("num_live must lie in [0, num_nodes = %d], got %r" % (self.num_nodes, num_live))
+        self.num_live_relations = self.num_relations // 2 if num_live_relations is None else int(num_live_relations)
+        if not 0 <= self.num_live_relations <= self.num_relations // 2:
+            raise ValueError("num_live_relations must lie in [0, num_relations // 2 = %d], got %r"
+                             % (self.num_relations // 2, num_live_relations))
+        self.relation_bits_budget = int(relation_bits_budget)
+        self._resident = None           # (hbits, tbits, adj, row_counts, changed) of the materialised list, on the GPU
+        self._full_rebuild = False
         self.capacity = capacity
         dev = data.edge_index.device
         self.device = dev
@@ -795,17 +814,17 @@ class GraphDelta(object):
 
     def check(self, h, r, t):
         """(h, r, t) as int64 vectors of one length on the delta's device; ValueError for ids outside the graph or a relation
-        that is not direct (the entities are the ids below num_live -- num_nodes unless rows are reserved -- and num_relations
-        is fixed)."""
+        that is not direct (the entities are the ids below num_live -- num_nodes unless rows are reserved -- and the direct
+        relations the ids below num_live_relations -- num_relations // 2 unless relation slots are reserved)."""
         h, r, t = (torch.as_tensor(v, dtype=torch.long, device=self.device).flatten() for v in (h, r, t))
         if not (h.shape == r.shape == t.shape):
             raise ValueError("one head, relation and tail per fact: got %d heads, %d relations and %d tails" % (len(h), len(r), len(t)))
         if len(h):
             if bool(((h < 0) | (h >= self.num_live) | (t < 0) | (t >= self.num_live)).any()):
                 raise ValueError("a fact's head and tail must be existing entities (ids in [0, %d))" % self.num_live)
-            if bool(((r < 0) | (r >= self.num_relations // 2)).any()):
+            if bool(((r < 0) | (r >= self.num_live_relations)).any()):
                 raise ValueError("a fact is stated through a direct relation (r < num_relations // 2 = %d); its inverse edge "
-                                 "is added with it" % (self.num_relations // 2))
+                                 "is added with it" % self.num_live_relations)
         return h, r, t
 
     def add(self, h, r, t):
@@ -820,7 +839,7 @@ class GraphDelta(object):
             return self.num_facts
         self.facts[self.num_facts:self.num_facts + n] = torch.stack([h, r, t], dim=1)
         self.num_facts += n
-        self._changed()
+        self._changed(added=n)
         return self.num_facts
 
     def _edge_codes(self, row, col, edge_type):
@@ -867,13 +886,14 @@ class GraphDelta(object):
             self._changed()
         return torch.tensor(removed, dtype=torch.long, device=self.device)
 
-    def _changed(self):
+    def _changed(self, added=0):
         self.version += 1
         self._materialized = None
         self._prepare()
         if self.traversal is not None:
             self._prepare_traversal()
-        self._rebuild_relation_graph()
+        if not (added and self._add_to_relation_graph(added)):
+            self._rebuild_relation_graph()
 
     def _prepare_traversal(self):
         """The edits keyed by the TAIL they point into, into buffers allocated at the first call and refreshed in
@@ -969,23 +989,60 @@ class GraphDelta(object):
         keep = keys[at] != codes
         return edge_index[:, keep], edge_type[keep]
 
+    def _add_to_relation_graph(self, added):
+        """The relation graph after the last `added` facts were appended, from their edges alone (the class docstring).  False
+        where this route does not apply -- off the GPU, bit sets beyond the budget, no relation graph, the private switch --
+        and the caller rebuilds from the edge list."""
+        words = (self.num_relations + 31) // 32
+        if (self.relation_graph is None or self._full_rebuild or self.device.type != "cuda"
+                or 2 * self.num_nodes * words * 4 > self.relation_bits_budget):
+            return False
+        edge_index, edge_type = self.edges()
+        m = self.num_facts
+        new = torch.cat([torch.arange(m - added, m, device=self.device), torch.arange(2 * m - added, 2 * m, device=self.device)])
+        if self._resident is None:      # seeded from the list as it was before these facts
+            old = torch.ones(2 * m, dtype=torch.bool, device=self.device)
+            old[new] = False
+            base_index, base_type = self.surviving(self.base.edge_index, self.base.edge_type)
+            before = Data(edge_index=torch.cat([base_index, edge_index[:, old]], dim=1),
+                          edge_type=torch.cat([base_type, edge_type[old]]), num_nodes=self.num_nodes,
+                          num_relations=self.num_relations)
+            adj, counts, hbits, tbits = tasks.relation_graph_bits(before, incidence=True)
+            self._resident = (hbits, tbits, adj, counts, torch.zeros(1, dtype=torch.int32, device=self.device))
+            # (a relation graph handed in that is not the edge list's own is replaced here, as the rebuild replaces it)
+            seeded = tasks.relation_graph_from_bits(adj.clone(), counts)
+            if not self._same_relation_graph(self.relation_graph, seeded):
+                self.relation_graph = seeded
+        hbits, tbits, adj, counts, changed = self._resident
+        tasks.relation_graph_add_edges(edge_index[:, new], edge_type[new], self.num_nodes, hbits, tbits, adj, counts, changed)
+        status = int(changed)       # (the one host read of the update)
+        if status & _lib.RELGRAPH_OUT_OF_RANGE:     # (check() has seen every id: the state and the facts disagree)
+            raise RuntimeError("GraphDelta: an added edge lies outside the graph the relation bit sets were laid out for")
+        if status & _lib.RELGRAPH_CHANGED:
+            # a copy: the object an older capture holds is not written to by later additions
+            self.relation_graph = tasks.relation_graph_from_bits(adj.clone(), counts)
+        return True
+
     def _rebuild_relation_graph(self):
         if self.relation_graph is None:
             return
+        self._resident = None       # (bits cannot be cleared: seeded again by the next add())
         edge_index, edge_type = self.edges()
         base_index, base_type = self.surviving(self.base.edge_index, self.base.edge_type)
         full = Data(edge_index=torch.cat([base_index, edge_index], dim=1),
                     edge_type=torch.cat([base_type, edge_type]), num_nodes=self.num_nodes,
                     num_relations=self.num_relations)
-        new, old = tasks.build_relation_graph(full).relation_graph, self.relation_graph
+        new = tasks.build_relation_graph(full).relation_graph
+        if not self._same_relation_graph(self.relation_graph, new):
+            self.relation_graph = new
+
+    @staticmethod
+    def _same_relation_graph(old, new):
         old_bits, new_bits = getattr(old, "adjacency_bits", None), getattr(new, "adjacency_bits", None)
         if old_bits is not None and new_bits is not None and old_bits.device == new_bits.device:
-            same = old_bits.shape == new_bits.shape and torch.equal(old_bits, new_bits)
-        else:
-            same = (old.edge_index.shape == new.edge_index.shape and torch.equal(old.edge_index, new.edge_index)
-                    and torch.equal(old.edge_type, new.edge_type))
-        if not same:
-            self.relation_graph = new
+            return old_bits.shape == new_bits.shape and torch.equal(old_bits, new_bits)
+        return (old.edge_index.shape == new.edge_index.shape and torch.equal(old.edge_index, new.edge_index)
+                and torch.equal(old.edge_type, new.edge_type))
 
     def materialize(self, data=None, num_nodes=None):
         """`data` (default: the base graph) without the edges a tombstone matches and with the delta's edges appended in

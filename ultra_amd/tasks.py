@@ -356,9 +356,11 @@ def filtered_ranking_masks(data, batch, pred, mode="tail"):
     return compute_ranking(pred, pos, mask), mask.sum(dim=-1)
 
 
-def relation_graph_bits(graph):
+def relation_graph_bits(graph, incidence=False):
     """(adj, row_counts): the four adjacency bit matrices [hh | tt | ht | th] of graph's relation graph, shape
-    (4, num_relations, W) int32 words, and the edges per (type, row) -- built by the HIP kernels of csrc/relgraph.hip."""
+    (4, num_relations, W) int32 words, and the edges per (type, row) -- built by the HIP kernels of csrc/relgraph.hip.
+    incidence: (adj, row_counts, hbits, tbits) -- with the entities' relation bit sets, (num_nodes * W) words each: the state
+    relation_graph_add_edges keeps current."""
     from ._lib import check, lib, stream_of
     ei, et = graph.edge_index.to(torch.int64).contiguous(), graph.edge_type.to(torch.int64).contiguous()
     n, r = int(graph.num_nodes), int(graph.num_relations)
@@ -370,16 +372,26 @@ def relation_graph_bits(graph):
     counts = torch.empty(4 * r, dtype=torch.int64, device=dev)
     check(lib.ultra_relation_graph_bits(ei.data_ptr(), et.data_ptr(), ei.shape[1], n, r, hbits.data_ptr(), tbits.data_ptr(),
                                         adj.data_ptr(), counts.data_ptr(), stream_of(dev)))
-    return adj, counts
+    return (adj, counts, hbits, tbits) if incidence else (adj, counts)
 
 
-def build_relation_graph_gpu(graph):
-    """build_relation_graph for a graph resident on the GPU: bit-matrix kernels instead of the reference's four sparse
-    products (tasks.py:186-189); relation_graph.edge_index / edge_type equal the reference's element for element.  The
-    bit matrices stay attached (relation_graph.adjacency_bits) for consumers that want plan format without the edge list."""
+def relation_graph_add_edges(edge_index, edge_type, num_nodes, hbits, tbits, adj, counts, changed):
+    """The resident state of relation_graph_bits(incidence=True) brought up to date for the appended edges (edge_index (2, m),
+    edge_type (m), int64 on the state's device), in place: ultra_relation_graph_add_edges.  `changed` (one int32 on the device)
+    receives _lib.RELGRAPH_CHANGED where adj gained a bit, _lib.RELGRAPH_OUT_OF_RANGE -- nothing marked -- where an index lies
+    outside the graph.  Launches only: the caller reads `changed` when it wants to know."""
     from ._lib import check, lib, stream_of
-    adj, counts = relation_graph_bits(graph)
-    r = int(graph.num_relations)
+    ei, et = edge_index.to(torch.int64).contiguous(), edge_type.to(torch.int64).contiguous()
+    check(lib.ultra_relation_graph_add_edges(ei.data_ptr(), et.data_ptr(), ei.shape[1], int(num_nodes), adj.shape[1],
+                                             hbits.data_ptr(), tbits.data_ptr(), adj.data_ptr(), counts.data_ptr(),
+                                             changed.data_ptr(), stream_of(adj.device)))
+
+
+def relation_graph_from_bits(adj, counts):
+    """The relation graph (edge list in the reference's order) the bit matrices stand for: ultra_relation_graph_emit.  `adj` is
+    attached as adjacency_bits, not copied."""
+    from ._lib import check, lib, stream_of
+    r = adj.shape[1]
     offsets = torch.cumsum(counts, 0) - counts
     total = int(counts.sum())
     dev = adj.device
@@ -387,7 +399,14 @@ def build_relation_graph_gpu(graph):
     edge_type = torch.empty(total, dtype=torch.int64, device=dev)
     check(lib.ultra_relation_graph_emit(adj.data_ptr(), offsets.data_ptr(), r, total, edge_index.data_ptr(), edge_type.data_ptr(),
                                         stream_of(dev)))
-    graph.relation_graph = Data(edge_index=edge_index, edge_type=edge_type, num_nodes=r, num_relations=4, adjacency_bits=adj)
+    return Data(edge_index=edge_index, edge_type=edge_type, num_nodes=r, num_relations=4, adjacency_bits=adj)
+
+
+def build_relation_graph_gpu(graph):
+    """build_relation_graph for a graph resident on the GPU: bit-matrix kernels instead of the reference's four sparse
+    products (tasks.py:186-189); relation_graph.edge_index / edge_type equal the reference's element for element.  The
+    bit matrices stay attached (relation_graph.adjacency_bits) for consumers that want plan format without the edge list."""
+    graph.relation_graph = relation_graph_from_bits(*relation_graph_bits(graph))
     return graph
 
 
