@@ -384,6 +384,33 @@ int32_t ultra_nbf_dense_layer(ultra_plan *plan, const ultra_mat *relation, const
                               const void *ln_bias, float eps, int32_t flags, const ultra_mat *output, void *stream);
 
 /*
+ * ultra_nbf_dense_layer with ULTRA_LAYER_REFERENCE_ORDER on a byte adjacency that is an OPERAND instead of a plan's: a_ex_dev,
+ * ceil(num_node / 16)^2 * 1024 bytes on the device in the layout [row tile 16][col chunk 16][lane = row % 16 + 16 type][col % 16]
+ * over num_node nodes and four relation types -- what ULTRA_ARR_DENSE_ORDER exports and ultra_relation_graph_dense_adjacency
+ * (ultra_nbfnet.h) writes.  The owner may rewrite the bytes in place between launches (a relation graph kept current, DESIGN.md
+ * 25); the launch reads whatever they hold when it runs.  Same kernels, same choice of form, same operand checks as
+ * ultra_nbf_dense_layer; relation is (n_outer, >= 4, 64).  ULTRA_ERR_INVALID for a NULL adjacency, num_node outside
+ * [1, ULTRA_DENSE_MAX_IN_ROW], or flags without ULTRA_LAYER_REFERENCE_ORDER.
+ */
+int32_t ultra_nbf_dense_layer_adjacency(const void *a_ex_dev, int64_t num_node, const ultra_mat *relation, const ultra_mat *input,
+                                        const ultra_mat *boundary, const int64_t *point_rows_dev, const void *weight,
+                                        const void *bias, const void *ln_weight, const void *ln_bias, float eps, int32_t flags,
+                                        const ultra_mat *output, void *stream);
+
+/*
+ * ultra_nbf_layer0 (sum aggregate, no edge weights) read off the same byte adjacency: for sample b with source q = src_rows[b],
+ * row i aggregates the at most four cells A[i][t][q], t ascending -- the order of one column's parallel edges in a
+ * reference-order plan -- then the boundary at row q and the update.  The output equals ultra_nbf_layer0's on a fresh
+ * ULTRA_PLAN_EXACT_ORDER plan of the edge list the bytes stand for, bit for bit on every row (the rows layer 0 does not reach
+ * hold relu(LayerNorm(bias))).  One launch, no atomics, no allocation, no host wait.  flags: ULTRA_CONV_LAYER_NORM / _RELU /
+ * _RESIDUAL.  fp32, hidden dim 64, weight (64, 128): ULTRA_ERR_UNSUPPORTED otherwise (ULTRA_LAYER0_MAX included);
+ * ULTRA_ERR_INVALID for a NULL adjacency or operand, num_node outside [1, ULTRA_DENSE_MAX_IN_ROW], unknown flag bits.
+ */
+int32_t ultra_nbf_dense_layer0_adjacency(const void *a_ex_dev, int64_t num_node, const ultra_mat *relation, const int64_t *src_rows_dev,
+                                         const void *src_values_dev, const void *weight, const void *bias, const void *ln_weight,
+                                         const void *ln_bias, float eps, int32_t flags, const ultra_mat *output, void *stream);
+
+/*
  * add_mul forward for a ROW-SPARSE input: input[o] is zero outside row src_rows_dev[o] (int64, one per outer
  * slice) -- the layer-0 input of every NBFNet, whose boundary condition puts the query vector at the head node
  * and zeros elsewhere (/root/reference/ultra/models.py:59-66, 135-141).  Zero rows contribute exact zeros to a

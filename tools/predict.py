@@ -2,7 +2,7 @@
 
     python tools/predict.py --data-root DIR [--ckpt FILE] --head NAME --relation NAME [--inverse] [-k 10] [--unfiltered] [--explain]
                             [--add-fact H R T]... [--remove-fact H R T]... [--entity-capacity M] [--add-entity NAME]...
-                            [--relation-capacity K] [--add-relation NAME]...
+                            [--relation-capacity K] [--add-relation NAME]... [--live-relation-graph]
     python tools/predict.py --data-root DIR [--ckpt FILE] --verify (--head NAME --relation NAME --tail NAME | --triples FILE) [--inverse]
 
 DIR holds train.txt / valid.txt / test.txt (`head relation tail` per line) and optionally entities.dict / relations.dict
@@ -26,6 +26,10 @@ by its name.  It is applied in command-line order with the fact options.
 the slots reserved by --relation-capacity K (default: as many as there are --add-relation options) and costs no plan, no relation
 graph and no capture.  The --add-relation options are applied in command-line order BEFORE every --add-fact / --remove-fact, so
 NAME can be used by all of them and by --relation.
+
+--live-relation-graph keeps the relation graph current in place (Predictor(live_relation_graph=True)): a fact that
+changes relation-graph cells -- every first fact through an --add-relation -- then costs no relation-graph plan and no new
+capture.  The answers are the same.  Needs a relation model of sum / DistMult layers (the default configuration's).
 
 --verify judges facts the dataset may already state: every (head, relation, tail) -- one from the command line, or the
 `head relation tail` lines of FILE -- is scored on the graph WITHOUT itself and its inverse edge (Predictor.verify_tails; with
@@ -85,6 +89,8 @@ def main(argv=None):
                     help="introduce a new relation type before the facts and the query; repeatable")
     ap.add_argument("--relation-capacity", type=int, default=None, metavar="K",
                     help="slots reserved for new relation types (default: the number of --add-relation options)")
+    ap.add_argument("--live-relation-graph", action="store_true",
+                    help="keep the relation graph current in place: no relation-graph plan, no new capture for an edit")
     ap.set_defaults(edits=[])
     args = ap.parse_args(argv)
     if args.verify:
@@ -142,10 +148,10 @@ def main(argv=None):
     rel_reserve = len(args.add_relation) if args.relation_capacity is None else args.relation_capacity
     if facts is not None:
         predictor = predict.Predictor(model, data, batch_size=min(8, len(facts)), entity_capacity=reserve,
-                                      relation_capacity=rel_reserve)
+                                      relation_capacity=rel_reserve, live_relation_graph=args.live_relation_graph)
     else:
         predictor = predict.Predictor(model, data, k=args.k, batch_size=1, filtered=not args.unfiltered, entity_capacity=reserve,
-                                      relation_capacity=rel_reserve)
+                                      relation_capacity=rel_reserve, live_relation_graph=args.live_relation_graph)
     for name in args.add_relation:
         if not rel_reserve:
             sys.exit("--add-relation needs --relation-capacity above 0")

@@ -139,6 +139,9 @@ def _load():
                                                      i32, i32, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     lib.ultra_nbf_dense_layer.argtypes = [vp, matp, matp, matp, vp, vp, vp, vp, vp, ctypes.c_float, i32, matp, vp]
     lib.ultra_nbf_layer0.argtypes = [vp, vp, matp, vp, vp, vp, vp, vp, vp, ctypes.c_float, i32, matp, vp]
+    # the two on a byte adjacency that is an operand: (a_ex, num_node) in place of the plan
+    lib.ultra_nbf_dense_layer_adjacency.argtypes = [vp, i64, matp, matp, matp, vp, vp, vp, vp, vp, ctypes.c_float, i32, matp, vp]
+    lib.ultra_nbf_dense_layer0_adjacency.argtypes = [vp, i64, matp, vp, vp, vp, vp, vp, vp, ctypes.c_float, i32, matp, vp]
     lib.ultra_rspmm_backward.argtypes = [vp, i32, i32, i32, vp, matp, matp, matp, matp, vp, matp, matp, vp]
     lib.ultra_rspmm_backward_add.argtypes = [vp, i32, i32, i32, vp, matp, matp, matp, matp, vp, matp, matp, matp, vp]
     lib.ultra_rspmm_edge_grad_samples.argtypes = [vp, i32, i32, i32, matp, matp, matp, vp, i64, vp]

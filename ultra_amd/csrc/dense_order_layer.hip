@@ -423,29 +423,25 @@ static bool dol_ok16(const ultra_mat *m) {
     return (reinterpret_cast<uintptr_t>(m->ptr) & 15u) == 0 && m->stride_row % 4 == 0 && m->stride_outer % 4 == 0;
 }
 
-// Called by ultra_nbf_dense_layer (rspmm_api.hip) with the plan uploaded, when the caller asks for the reference order.
-int launch_dense_order_layer(ultra_plan *p, const ultra_mat *rel, const ultra_mat *x, const ultra_mat *bnd, const int64_t *bnd_rows,
-                             const void *weight, const void *bias, const void *ln_w, const void *ln_b, float eps, int flags,
-                             const ultra_mat *out, hipStream_t stream, bool shared_chip) {
-    if (!(p->flags & ULTRA_PLAN_DENSE) || p->a_ex.empty() || !p->d.a_ex) {
-        set_error("ultra_nbf_dense_layer (reference order) needs a ULTRA_PLAN_DENSE plan of a graph with at most 4 relation types "
-                  "whose parallel edges are sorted by type and never repeated");
-        return ULTRA_ERR_UNSUPPORTED;
-    }
-    if (out->row_len != 64 || p->num_out != p->num_in) {
-        set_error("ultra_nbf_dense_layer: hidden dim 64 on a square graph only");
+// The launch itself, from (adjacency bytes on the device, node count n, relation types n_rel): what both entry points fill
+// DenseOrderParams from.  `name` is the entry point's, for the error texts.
+static int launch_dense_order(const void *a_ex_dev, int64_t n, int64_t n_rel, const char *name, const ultra_mat *rel, const ultra_mat *x,
+                              const ultra_mat *bnd, const int64_t *bnd_rows, const void *weight, const void *bias, const void *ln_w,
+                              const void *ln_b, float eps, int flags, const ultra_mat *out, hipStream_t stream, bool shared_chip) {
+    if (out->row_len != 64) {
+        set_error(std::string(name) + ": hidden dim 64 on a square graph only");
         return ULTRA_ERR_UNSUPPORTED;
     }
     if (!dol_ok16(rel) || !dol_ok16(x) || !dol_ok16(out) || (bnd && !dol_ok16(bnd)) || (reinterpret_cast<uintptr_t>(weight) & 15u)) {
-        set_error("ultra_nbf_dense_layer: operands must be 16-byte aligned with strides that are multiples of 4");
+        set_error(std::string(name) + ": operands must be 16-byte aligned with strides that are multiples of 4");
         return ULTRA_ERR_UNSUPPORTED;
     }
-    if ((uint64_t)p->num_in * (uint64_t)x->stride_row * 4u >= (1ull << 32)) {
-        set_error("ultra_nbf_dense_layer: an input slice (rows * stride_row) exceeds 4 GiB");
+    if ((uint64_t)n * (uint64_t)x->stride_row * 4u >= (1ull << 32)) {
+        set_error(std::string(name) + ": an input slice (rows * stride_row) exceeds 4 GiB");
         return ULTRA_ERR_UNSUPPORTED;
     }
     DenseOrderParams dp;
-    dp.a_ex = reinterpret_cast<const uint4 *>(p->d.a_ex);
+    dp.a_ex = reinterpret_cast<const uint4 *>(a_ex_dev);
     dp.rel = static_cast<const float *>(rel->ptr);
     dp.x = static_cast<const float *>(x->ptr);
     dp.bnd = bnd ? static_cast<const float *>(bnd->ptr) : nullptr;
@@ -459,8 +455,8 @@ int launch_dense_order_layer(ultra_plan *p, const ultra_mat *rel, const ultra_ma
     dp.x_so = x->stride_outer, dp.x_sr = x->stride_row;
     dp.bnd_so = bnd ? bnd->stride_outer : 0, dp.bnd_sr = (bnd && !bnd_rows) ? bnd->stride_row : 0;
     dp.out_so = out->stride_outer, dp.out_sr = out->stride_row;
-    dp.n_out = (int)p->num_out, dp.n_in = (int)p->num_in, dp.n_rel = (int)p->num_rel;
-    dp.n_jc = (int)((p->num_in + 15) / 16), dp.n_rt16 = (int)((p->num_out + 15) / 16);
+    dp.n_out = (int)n, dp.n_in = (int)n, dp.n_rel = (int)n_rel;
+    dp.n_jc = (int)((n + 15) / 16), dp.n_rt16 = (int)((n + 15) / 16);
     dp.has_bnd = bnd ? 1 : 0;
     dp.flags = flags;
     dp.eps = eps;
@@ -521,6 +517,33 @@ int launch_dense_order_layer(ultra_plan *p, const ultra_mat *rel, const ultra_ma
         return ULTRA_ERR_HIP;
     }
     return ULTRA_OK;
+}
+
+// Called by ultra_nbf_dense_layer (rspmm_api.hip) with the plan uploaded, when the caller asks for the reference order.
+int launch_dense_order_layer(ultra_plan *p, const ultra_mat *rel, const ultra_mat *x, const ultra_mat *bnd, const int64_t *bnd_rows,
+                             const void *weight, const void *bias, const void *ln_w, const void *ln_b, float eps, int flags,
+                             const ultra_mat *out, hipStream_t stream, bool shared_chip) {
+    if (!(p->flags & ULTRA_PLAN_DENSE) || p->a_ex.empty() || !p->d.a_ex) {
+        set_error("ultra_nbf_dense_layer (reference order) needs a ULTRA_PLAN_DENSE plan of a graph with at most 4 relation types "
+                  "whose parallel edges are sorted by type and never repeated");
+        return ULTRA_ERR_UNSUPPORTED;
+    }
+    if (p->num_out != p->num_in) {
+        set_error("ultra_nbf_dense_layer: hidden dim 64 on a square graph only");
+        return ULTRA_ERR_UNSUPPORTED;
+    }
+    return launch_dense_order(p->d.a_ex, p->num_out, p->num_rel, "ultra_nbf_dense_layer", rel, x, bnd, bnd_rows, weight, bias, ln_w,
+                              ln_b, eps, flags, out, stream, shared_chip);
+}
+
+// Called by ultra_nbf_dense_layer_adjacency: the same launch on a byte adjacency that is an operand -- `a_ex_dev` in the layout
+// of DenseOrderParams::a_ex over n nodes and four relation types, kept current by its owner (ultra_relation_graph_dense_adjacency).
+int launch_dense_order_layer_adjacency(const void *a_ex_dev, int64_t n, const ultra_mat *rel, const ultra_mat *x, const ultra_mat *bnd,
+                                       const int64_t *bnd_rows, const void *weight, const void *bias, const void *ln_w,
+                                       const void *ln_b, float eps, int flags, const ultra_mat *out, hipStream_t stream,
+                                       bool shared_chip) {
+    return launch_dense_order(a_ex_dev, n, 4, "ultra_nbf_dense_layer_adjacency", rel, x, bnd, bnd_rows, weight, bias, ln_w, ln_b, eps,
+                              flags, out, stream, shared_chip);
 }
 
 }  // namespace ultra

@@ -53,6 +53,13 @@ int launch_dense_forward(ultra_plan *p, int sum, int mul, int dtype, const void 
 int launch_dense_order_layer(ultra_plan *p, const ultra_mat *rel, const ultra_mat *x, const ultra_mat *bnd, const int64_t *bnd_rows,
                              const void *weight, const void *bias, const void *ln_w, const void *ln_b, float eps, int flags,
                              const ultra_mat *out, hipStream_t stream, bool shared_chip);   // dense_order_layer.hip
+int launch_dense_order_layer_adjacency(const void *a_ex_dev, int64_t n, const ultra_mat *rel, const ultra_mat *x, const ultra_mat *bnd,
+                                       const int64_t *bnd_rows, const void *weight, const void *bias, const void *ln_w,
+                                       const void *ln_b, float eps, int flags, const ultra_mat *out, hipStream_t stream,
+                                       bool shared_chip);   // dense_order_layer.hip
+int launch_dense_layer0_adjacency(const void *a_ex_dev, int64_t n, const ultra_mat *rel, const int64_t *src_rows, const void *src_vals,
+                                  const void *weight, const void *bias, const void *ln_w, const void *ln_b, float eps, int flags,
+                                  const ultra_mat *out, hipStream_t stream);   // dense_layer0_adjacency.hip
 
 int launch_dense_layer(ultra_plan *p, const ultra_mat *rel, const ultra_mat *x, const ultra_mat *bnd, const int64_t *bnd_rows,
                        const void *weight, const void *bias, const void *ln_w, const void *ln_b, float eps, int flags,
@@ -1263,6 +1270,67 @@ int32_t ultra_nbf_dense_layer(ultra_plan *plan, const ultra_mat *relation, const
     }
     return launch_dense_layer(plan, relation, input, boundary, point_rows_dev, weight, bias, ln_weight, ln_bias, eps, flags,
                               output, reinterpret_cast<hipStream_t>(stream));
+}
+
+// what the two byte-adjacency entries ask of (a_ex_dev, num_node)
+static int check_adjacency(const char *name, const void *a_ex_dev, int64_t num_node) {
+    if (!a_ex_dev) return invalid(std::string(name) + ": the adjacency is NULL");
+    if (num_node <= 0 || num_node > ULTRA_DENSE_MAX_IN_ROW)
+        return invalid(std::string(name) + ": num_node must lie in [1, " + std::to_string(ULTRA_DENSE_MAX_IN_ROW) + "], got " +
+                       std::to_string((long long)num_node));
+    return ULTRA_OK;
+}
+
+int32_t ultra_nbf_dense_layer_adjacency(const void *a_ex_dev, int64_t num_node, const ultra_mat *relation, const ultra_mat *input,
+                                        const ultra_mat *boundary, const int64_t *point_rows_dev, const void *weight,
+                                        const void *bias, const void *ln_weight, const void *ln_bias, float eps, int32_t flags,
+                                        const ultra_mat *output, void *stream) {
+    ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);
+    (void)hipGetLastError();
+    int rc;
+    if ((rc = check_adjacency("ultra_nbf_dense_layer_adjacency", a_ex_dev, num_node))) return rc;
+    if (!(flags & ULTRA_LAYER_REFERENCE_ORDER))
+        return invalid("ultra_nbf_dense_layer_adjacency: served in the reference's order only (ULTRA_LAYER_REFERENCE_ORDER)");
+    if (!output || !output->ptr || !weight) return invalid("ultra_nbf_dense_layer_adjacency: NULL operand");
+    if ((flags & 1) && (!ln_weight || !ln_bias)) return invalid("ultra_nbf_dense_layer_adjacency: LayerNorm needs its weight and bias");
+    if (point_rows_dev && !boundary) return invalid("ultra_nbf_dense_layer_adjacency: point rows without their values");
+    const int64_t n_outer = output->n_outer;
+    if ((rc = check_mat(output, "output", num_node, n_outer, output->row_len))) return rc;
+    if ((rc = check_mat(relation, "relation", 4, n_outer, output->row_len))) return rc;
+    if ((rc = check_mat(input, "input", num_node, n_outer, output->row_len))) return rc;
+    if (boundary && (rc = check_mat(boundary, "boundary", point_rows_dev ? 1 : num_node, n_outer, output->row_len))) return rc;
+    if (n_outer == 0) return ULTRA_OK;
+    DevInfo di;
+    if ((rc = device_info(&di))) return rc;
+    const bool shared_chip = g_tuning.grid > 0 && g_tuning.grid < di.cu;
+    return launch_dense_order_layer_adjacency(a_ex_dev, num_node, relation, input, boundary, point_rows_dev, weight, bias, ln_weight,
+                                              ln_bias, eps, flags & 7, output, reinterpret_cast<hipStream_t>(stream), shared_chip);
+}
+
+int32_t ultra_nbf_dense_layer0_adjacency(const void *a_ex_dev, int64_t num_node, const ultra_mat *relation, const int64_t *src_rows_dev,
+                                         const void *src_values_dev, const void *weight, const void *bias, const void *ln_weight,
+                                         const void *ln_bias, float eps, int32_t flags, const ultra_mat *output, void *stream) {
+    ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);
+    (void)hipGetLastError();
+    int rc;
+    if ((rc = check_adjacency("ultra_nbf_dense_layer0_adjacency", a_ex_dev, num_node))) return rc;
+    if (flags & ~(L0_LN | L0_RELU | L0_RESIDUAL | L0_MAX))
+        return invalid("ultra_nbf_dense_layer0_adjacency: unknown flag bits " + std::to_string(flags & ~(L0_LN | L0_RELU | L0_RESIDUAL | L0_MAX)));
+    if (!output || !output->ptr || !src_rows_dev || !weight) return invalid("ultra_nbf_dense_layer0_adjacency: NULL operand");
+    if ((flags & L0_LN) && (!ln_weight || !ln_bias)) return invalid("ultra_nbf_dense_layer0_adjacency: LayerNorm needs its weight and bias");
+    if (output->row_len != 64 || (flags & L0_MAX)) {
+        set_error("ultra_nbf_dense_layer0_adjacency: the sum aggregate at hidden dim 64 (weight (64, 128)) in fp32 only");
+        return ULTRA_ERR_UNSUPPORTED;
+    }
+    const int64_t n_outer = output->n_outer;
+    if ((rc = check_mat(output, "output", num_node, n_outer, 64))) return rc;
+    if ((rc = check_mat(relation, "relation", 4, n_outer, 64))) return rc;
+    if (n_outer > 65535) return invalid("ultra_nbf_dense_layer0_adjacency: at most 65535 samples a launch");
+    if (!mat_vec_ok(output, 4) || !mat_vec_ok(relation, 4) || !aligned16(weight) || (src_values_dev && !aligned16(src_values_dev)))
+        return invalid("ultra_nbf_dense_layer0_adjacency: operands must be 16-byte aligned with strides that are multiples of 4");
+    if (n_outer == 0) return ULTRA_OK;
+    return launch_dense_layer0_adjacency(a_ex_dev, num_node, relation, src_rows_dev, src_values_dev, weight, bias, ln_weight, ln_bias,
+                                         eps, flags, output, reinterpret_cast<hipStream_t>(stream));
 }
 
 int32_t ultra_rspmm_backward(ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const void *edge_weight_dev,

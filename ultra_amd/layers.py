@@ -230,6 +230,26 @@ class GeneralizedRelationalConv(nn.Module):
                 and (relation is None or (relation.dtype == torch.float32 and relation.shape[-1] == 64))
                 and (edge_weight is None or not edge_weight.requires_grad))
 
+    def adjacency_supported(self):
+        """Can this layer run on a relation graph's byte adjacency alone (ultra_nbf_dense_layer0_adjacency as layer
+        0, ultra_nbf_dense_layer_adjacency as any other)?  sum / DistMult, 64-d, fp32, its own relation embedding of at least
+        the graph's four types -- what the layer is, not what a call hands it."""
+        return (self.aggregate_func == "sum" and self.message_func == "distmult" and self.input_dim == 64
+                and self.output_dim == 64 and self.linear.in_features == 128 and self.linear.weight.dtype == torch.float32
+                and (self.activation is None or self.activation is F.relu) and not self.dependent
+                and not self.project_relations and self.relation.weight.shape[0] >= 4)
+
+    def forward_adjacency(self, adjacency, num_node, point, input=None, residual=False):
+        """This layer on the byte adjacency of a live relation graph, no plan involved.  `point`: the boundary condition (a
+        PointBoundary).  input=None: the boundary condition is the input too -- layer 0, evaluated in closed form."""
+        relation = self._relation_for(None, len(point.rows))
+        if input is None:
+            return rspmm.dense_layer0_adjacency(adjacency, num_node, relation, point.rows, point.values, self.linear,
+                                                self.layer_norm, relu=self.activation is not None, residual=residual)
+        return rspmm.dense_layer_adjacency(adjacency, num_node, relation, input, self.linear, self.layer_norm,
+                                           relu=self.activation is not None, residual=residual,
+                                           point=(point.rows, point.values))
+
     def layer0_fill(self, edge_index, edge_type, num_node, num_relation, batch_size):
         """The constant rows of forward_layer0_point (every row that layer 0 cannot reach: relu(LayerNorm(bias))) as a fresh
         (batch, N, 64) tensor on the CURRENT stream -- they depend on this layer's parameters only, so a model may launch

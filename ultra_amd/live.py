@@ -111,7 +111,8 @@ class LiveGraph(object):
     int64 that holds the same number for the owner's life (None without a reserve).  relation_capacity=K > 0: K
     direct relation slots reserved for relations that arrive later -- `graph` is then laid out over R + K direct slots
     (with_relation_slots; the filter graph alike), `num_direct_relations` of them in use.  relation_bits_budget: the delta's
-    (rspmm.GraphDelta).
+    (rspmm.GraphDelta).  live_relation_graph: the delta's too -- True: its relation graph is one object that is
+    kept current in place, so an edit that changes relation-graph cells costs no plan and no new capture.
 
     delta_policy: when the delta exists.  "eager": from construction, and a new empty one after every compaction (a captured
     step is handed the delta before the first edit).  "lazy": None until the first edit and None again after a compaction (an
@@ -125,7 +126,11 @@ class LiveGraph(object):
     graph, before `graph` is replaced."""
 
     def __init__(self, data, delta_capacity=256, entity_capacity=0, filter_data=None, keep_filter=False, delta_policy="lazy",
-                 owner="LiveGraph", on_rebuild=None, relation_capacity=0, relation_bits_budget=256 << 20):
+                 owner="LiveGraph", on_rebuild=None, relation_capacity=0, relation_bits_budget=256 << 20,
+                 live_relation_graph=False):
+        if not isinstance(live_relation_graph, bool):
+            raise ValueError("live_relation_graph must be True or False, got %r" % (live_relation_graph,))
+        self.live_relation_graph = live_relation_graph
         if isinstance(entity_capacity, bool) or not isinstance(entity_capacity, int) or entity_capacity < 0:
             raise ValueError("entity_capacity must be a non-negative int (reserved rows), got %r" % (entity_capacity,))
         if isinstance(relation_capacity, bool) or not isinstance(relation_capacity, int) or relation_capacity < 0:
@@ -171,7 +176,8 @@ class LiveGraph(object):
 
     def _new_delta(self, capacity=None):
         return rspmm.GraphDelta(self.graph, self.delta_capacity if capacity is None else capacity, num_live=self.num_entities,
-                                num_live_relations=self.num_direct_relations, relation_bits_budget=self.relation_bits_budget)
+                                num_live_relations=self.num_direct_relations, relation_bits_budget=self.relation_bits_budget,
+                                live_relation_graph=self.live_relation_graph)
 
     def _probe(self):
         """A delta to check arguments with or to materialise through: the one held, or an empty one."""

@@ -355,6 +355,18 @@ class RelNBFNet(BaseNBFNet):
         index = h_index.unsqueeze(-1).expand_as(query)
         # boundary: ones at the query relation's node, zeros elsewhere (models.py:59-66) -- in closed form
         boundary = layers.PointBoundary(h_index, query, data.num_nodes)
+        adjacency = getattr(data, "dense_adjacency", None)
+        if (adjacency is not None and edge_keep is None and not separate_grad and not self.training
+                and not torch.is_grad_enabled() and h_index.is_cuda and self.adjacency_blocker() is None):
+            # a relation graph kept current in place (tasks.LiveRelationGraph): every layer reads its byte
+            # adjacency -- layer 0 in closed form, the others as the reference-order dense layer -- and no plan is asked for, so
+            # a captured step sees the cells of a later change at its next replay
+            hiddens, hidden = [], None
+            for layer in self.layers:
+                hidden = layer.forward_adjacency(adjacency, data.num_nodes, boundary, input=hidden,
+                                                 residual=self.short_cut and layer.output_dim == layer.input_dim)
+                hiddens.append(hidden)
+            return self._readout(hiddens, query, data.num_nodes, [None] * len(hiddens))
         if not (layers.POINT_BOUNDARY_FAST_PATH and h_index.is_cuda
                 and (not torch.is_grad_enabled() or all(l.point_boundary_trains() for l in self.layers))):
             boundary = boundary.dense()
@@ -363,8 +375,19 @@ class RelNBFNet(BaseNBFNet):
         hiddens, edge_weights = self._propagate_layers(data, boundary, query, boundary, separate_grad=False,
                                                        onehot_rows=h_index, edge_weight=edge_keep,
                                                        edge_keep=edge_keep is not None)
+        return self._readout(hiddens, query, data.num_nodes, edge_weights)
 
-        node_query = query.unsqueeze(1).expand(-1, data.num_nodes, -1)
+    def adjacency_blocker(self):
+        """None where every layer can run on a live relation graph's byte adjacency (layers.adjacency_supported); else the
+        name of the first layer that cannot, with what it is."""
+        for i, layer in enumerate(self.layers):
+            if not layer.adjacency_supported():
+                return "layers.%d (%s aggregate, %s message, %d -> %d)" % (i, layer.aggregate_func, layer.message_func,
+                                                                           layer.input_dim, layer.output_dim)
+        return None
+
+    def _readout(self, hiddens, query, num_nodes, edge_weights):
+        node_query = query.unsqueeze(1).expand(-1, num_nodes, -1)
         if self.concat_hidden:
             output = torch.cat(hiddens + [node_query], dim=-1)
             output = self.mlp(output)
@@ -938,7 +961,8 @@ class Ultra(nn.Module):
         """Fill the table for `data.relation_graph` under the current parameters (inference only); forward() then gathers
         from it while the graph object and the parameters stay the same.  Returns the table."""
         rg = data.relation_graph
-        dev = rg.edge_index.device
+        # (a live relation graph emits its edge list on demand only: its bits name the device)
+        dev = rg.adjacency_bits.device if getattr(rg, "dense_adjacency", None) is not None else rg.edge_index.device
         num_rel = int(rg.num_nodes)
         was_training = self.training
         self.eval()
@@ -954,12 +978,16 @@ class Ultra(nn.Module):
                 table[lo:min(lo + chunk, num_rel)] = rep[: min(chunk, num_rel - lo)]
         self.train(was_training)
         self._rel_table = table
-        self._rel_table_key = (id(rg), self._relation_param_state())
+        self._rel_table_key = self._relation_table_key(rg)
         return self._rel_table
 
     def drop_relation_cache(self):
         self._rel_table = None
         self._rel_table_key = None
+
+    def _relation_table_key(self, rg):
+        # (the version: a live relation graph changes in place, under one id -- tasks.LiveRelationGraph)
+        return (id(rg), getattr(rg, "version", None), self._relation_param_state())
 
     def _relation_param_state(self):
         return tuple((p.data_ptr(), p._version) for p in self.relation_model.parameters())
@@ -968,7 +996,7 @@ class Ultra(nn.Module):
         table = getattr(self, "_rel_table", None)
         if table is None or self.training or torch.is_grad_enabled():
             return None
-        if self._rel_table_key != (id(data.relation_graph), self._relation_param_state()):
+        if self._rel_table_key != self._relation_table_key(data.relation_graph):
             self.drop_relation_cache()       # another graph, or the weights moved: the table is stale
             return None
         return table.index_select(0, query_rels)

@@ -351,6 +351,21 @@ def delta_samples_supported(model):
             and all(getattr(layer, "delta_samples_supported", lambda: False)() for layer in layers))
 
 
+def live_relation_graph_blocker(model):
+    """None where every layer of `model`'s relation model can run on a relation graph that is kept current in place (its
+    byte adjacency alone, DESIGN.md 25: sum aggregate, DistMult messages, 64-d, fp32); else the name of what cannot."""
+    rel = getattr(model, "relation_model", None)
+    if rel is None or not hasattr(rel, "adjacency_blocker"):
+        return "%s (no relation model with an adjacency route)" % type(model).__name__
+    blocker = rel.adjacency_blocker()
+    return None if blocker is None else "relation_model." + blocker
+
+
+def live_relation_graph_supported(model):
+    """Does every relation-model layer of `model` qualify for Predictor(live_relation_graph=True)?"""
+    return live_relation_graph_blocker(model) is None
+
+
 def _check_facts(data, h, r, t, num_live=None, num_direct=None):
     """(h, r, t) of verify_*: int64 vectors of one length on the graph's device, r a direct relation (ValueError otherwise);
     num_live (a graph with reserved rows): h and t below it; num_direct (a graph with reserved relation slots): the direct
@@ -516,11 +531,27 @@ class Predictor(object):
     argument is a direct relation below num_direct_relations everywhere (ValueError otherwise), and every relation id handed back
     -- materialized(), the paths of explain_* -- is in the compact numbering, inverse type r + num_direct_relations.  Every result
     is that of a fresh Predictor on materialized().  explain_* and verify_* compact first where the delta is edited (the slot
-    counts stay).  Both reserves may be used together.  relation_bits_budget: rspmm.GraphDelta's."""
+    counts stay).  Both reserves may be used together.  relation_bits_budget: rspmm.GraphDelta's.
+
+    A relation graph kept current IN PLACE: live_relation_graph=True (default False: everything above).  From the
+    first add_facts on, the delta's relation graph is ONE tasks.LiveRelationGraph whose cells are rewritten in place, and the
+    relation model reads its byte adjacency without a plan -- so a fact that changes relation-graph cells (every first fact
+    through a new relation does) costs no relation-graph plan and no new capture: the captured steps see the new cells at
+    their next replay.  remove_facts keeps the object too.  Results are those of the flag-off route, bit for bit.  Needs a
+    relation model of sum / DistMult 64-d layers (live_relation_graph_supported; ValueError otherwise) and applies on the GPU
+    to relation graphs of at most 1024 nodes; elsewhere the flag-off route runs.  A replay still in flight while add_facts
+    writes is the caller's to order, as for the delta's own buffers."""
 
     def __init__(self, model, data, k=10, batch_size=8, filtered_data=None, filtered=True, use_graph=True, delta_capacity=256,
-                 entity_capacity=0, relation_capacity=0, relation_bits_budget=256 << 20):
+                 entity_capacity=0, relation_capacity=0, relation_bits_budget=256 << 20, live_relation_graph=False):
         check_k(k)
+        if not isinstance(live_relation_graph, bool):
+            raise ValueError("live_relation_graph must be True or False, got %r" % (live_relation_graph,))
+        if live_relation_graph:
+            blocker = live_relation_graph_blocker(model)
+            if blocker is not None:
+                raise ValueError("live_relation_graph=True needs a relation model whose layers all run on the relation graph's "
+                                 "byte adjacency (sum aggregate, DistMult messages, 64-d, fp32): %s does not" % blocker)
         if filtered_data is None:
             filtered_data = getattr(data, "filtered_data", None)
         # (a model whose forward takes no `delta` is served by compacting at every add_facts)
@@ -534,7 +565,7 @@ class Predictor(object):
         self._live = LiveGraph(data, delta_capacity, entity_capacity, filter_data=filtered_data, keep_filter=True,
                                delta_policy="eager" if takes_delta else "never", owner="Predictor",
                                on_rebuild=functools.partial(_release, self._steps), relation_capacity=relation_capacity,
-                               relation_bits_budget=relation_bits_budget)
+                               relation_bits_budget=relation_bits_budget, live_relation_graph=live_relation_graph)
         self.model, self.k, self.batch_size = model, k, int(batch_size)
         self.filtered, self.use_graph = bool(filtered), bool(use_graph)
 
@@ -548,6 +579,7 @@ class Predictor(object):
     num_slots = forwarded("num_slots")
     live_count = forwarded("live_count")
     relation_capacity = forwarded("relation_capacity")
+    live_relation_graph = forwarded("live_relation_graph")
     num_direct_relations = forwarded("num_direct_relations")
     num_relation_slots = forwarded("num_relation_slots")
 
@@ -583,14 +615,33 @@ class Predictor(object):
         otherwise: the sets of entities and relations are fixed).  Each adds the edges (h, t, r) and (t, h, r + num_relations / 2)
         to the served graph and to the filter graph; a repeated fact is one more parallel edge.  Returns the number of facts the
         delta holds afterwards (0 after a compaction: more facts than delta_capacity, or a model without a delta route)."""
-        return self._live.add_facts(h, r, t)
+        before = self._relation_graph_state()
+        out = self._live.add_facts(h, r, t)
+        self._relation_graph_edited(before)
+        return out
 
     def remove_facts(self, h, r, t):
         """Retract the facts (h[i], r[i], t[i]) -- the argument rules of add_facts -- one after the other: every edge equal to
         (h, t, r) or (t, h, r + num_relations / 2) leaves the served graph and the filter graph (a fact stated nowhere is a
         no-op).  Returns an int64 vector: the number of direct edges each fact took out of the served graph
         (GraphDelta.remove).  Compacts first where the delta cannot hold the tombstones."""
-        return self._live.remove_facts(h, r, t)
+        before = self._relation_graph_state()
+        out = self._live.remove_facts(h, r, t)
+        self._relation_graph_edited(before)
+        return out
+
+    def _relation_graph_state(self):
+        rg = None if self.delta is None else self.delta.relation_graph
+        return (rg, getattr(rg, "version", None))
+
+    def _relation_graph_edited(self, before):
+        """A live relation graph that changed in place under a model that holds a relation table
+        (Ultra.cache_relation_representations): a captured step gathers from the table it was recorded with, which is stale
+        now -- the table is dropped and the steps are made again (they then run the relation model)."""
+        rg, version = self._relation_graph_state()
+        if rg is before[0] and version != before[1] and getattr(self.model, "_rel_table", None) is not None:
+            self.model.drop_relation_cache()
+            _release(self._steps)
 
     def compact(self, extra=None, delta=None, slots=None, relation_slots=None):
         """Fold the delta's edits (and `extra` = (h, r, t), checked by the caller) into `data`: the materialised graph -- without

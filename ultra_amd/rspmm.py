@@ -706,6 +706,64 @@ class Plan(object):
         return ms.value, op.out
 
 
+def _check_adjacency(adjacency, num_node):
+    tiles = (int(num_node) + 15) // 16
+    if adjacency.dtype != torch.uint8 or adjacency.dim() != 1 or adjacency.numel() != tiles * tiles * 1024 \
+            or not adjacency.is_contiguous():
+        raise RuntimeError("Expected the byte adjacency of %d nodes: a contiguous uint8 vector of ceil(n / 16)^2 * 1024 = %d "
+                           "bytes, got %s %s" % (num_node, tiles * tiles * 1024, adjacency.dtype, tuple(adjacency.shape)))
+
+
+def dense_layer_adjacency(adjacency, num_node, relation, input, linear, layer_norm=None, relu=True, residual=False,
+                          boundary=None, point=None):
+    """Plan.fused_layer in the reference's order on a byte adjacency that is an operand (ultra_nbf_dense_layer_adjacency):
+    `adjacency` is tasks.relation_graph_dense_adjacency's vector over `num_node` nodes, read as it stands when the launch
+    runs -- a live relation graph rewrites it in place.  No plan is involved.  An operand the engine does not
+    serve is an error here, not a None: the caller decided on this route by the layer's kind."""
+    _check_adjacency(adjacency, num_node)
+    if input.dtype != torch.float32 or relation.dtype != torch.float32 or input.dim() != 3 or input.shape[-1] != 64 \
+            or tuple(linear.weight.shape) != (64, 128):
+        raise RuntimeError("dense_layer_adjacency serves fp32 at hidden dim 64 (input (batch, num_node, 64), weight (64, 128))")
+    relation, mrel = as_mat(relation)
+    input, mx = as_mat(input)
+    out = torch.empty_like(input)
+    _, mout = as_mat(out)
+    rows = vals = rows_ptr = None
+    if point is not None:
+        rows, vals, rows_ptr, mb = _point_operand(point, input)
+    else:
+        boundary, mb = _opt_mat(boundary)
+    _require_gpu(adjacency, relation, input, boundary, rows, vals)
+    weight, bias, ln_weight, ln_bias, eps, flags = _lib.update_args(linear, layer_norm, relu, residual, _lib.LAYER_REFERENCE_ORDER)
+    check(lib.ultra_nbf_dense_layer_adjacency(adjacency.data_ptr(), int(num_node), ctypes.byref(mrel), ctypes.byref(mx), mb,
+                                              rows_ptr, weight.data_ptr(), ptr(bias), ptr(ln_weight), ptr(ln_bias), eps, flags,
+                                              ctypes.byref(mout), stream_of(input)))
+    return out
+
+
+def dense_layer0_adjacency(adjacency, num_node, relation, src_rows, src_values, linear, layer_norm=None, relu=True,
+                           residual=False):
+    """Plan.layer0 (sum aggregate, no edge weights) read off the byte adjacency (ultra_nbf_dense_layer0_adjacency): the
+    (batch, num_node, 64) hidden state of layer 0 on its one-hot boundary condition, bit for bit what Plan.layer0 returns on
+    a fresh reference-order plan of the edge list the bytes stand for."""
+    _check_adjacency(adjacency, num_node)
+    _require_gpu(adjacency, relation, src_rows, src_values)
+    if relation.dtype != torch.float32 or relation.dim() != 3 or tuple(linear.weight.shape) != (64, 128) \
+            or linear.weight.dtype != torch.float32 or (src_values is not None and src_values.dtype != torch.float32):
+        raise RuntimeError("dense_layer0_adjacency serves fp32 at hidden dim 64 (relation (batch, >= 4, 64), weight (64, 128))")
+    relation, mrel = as_mat(relation)
+    out = torch.empty(relation.shape[0], int(num_node), 64, dtype=torch.float32, device=relation.device)
+    _, mout = as_mat(out)
+    src_rows = src_rows.to(torch.int64).contiguous()
+    if src_values is not None:
+        src_values = src_values.contiguous()
+    weight, bias, ln_weight, ln_bias, eps, flags = _lib.update_args(linear, layer_norm, relu, residual)
+    check(lib.ultra_nbf_dense_layer0_adjacency(adjacency.data_ptr(), int(num_node), ctypes.byref(mrel), src_rows.data_ptr(),
+                                               ptr(src_values), weight.data_ptr(), ptr(bias), ptr(ln_weight), ptr(ln_bias), eps,
+                                               flags, ctypes.byref(mout), stream_of(relation)))
+    return out
+
+
 TraversalLayout = namedtuple("TraversalLayout", "rows count add_ptr add_src add_type dead_ptr dead_src dead_type")
 
 
@@ -754,11 +812,23 @@ class GraphDelta(object):
     ultra_relation_graph_add_edges over the new facts' edges alone and reads its `changed` word: unchanged -- the relation-graph
     object is kept; changed -- a new one is emitted from a copy of the resident matrices.  remove() cannot clear bits: it
     rebuilds from the edge list as before and drops the resident state, which the next add() seeds again.  `_full_rebuild`
-    (tools and tests only): True forces the rebuild from the edge list at every add()."""
+    (tools and tests only): True forces the rebuild from the edge list at every add().
 
-    def __init__(self, data, capacity=1024, num_live=None, num_live_relations=None, relation_bits_budget=256 << 20):
+    The relation graph kept current IN PLACE (`live_relation_graph=True`, default False = everything above):
+    where the resident route applies and the relation graph has at most DENSE_MAX_IN_ROW nodes, the first add() installs ONE
+    tasks.LiveRelationGraph over the resident matrices as `relation_graph`, and that object stays: a later add() that changes
+    cells rewrites its byte adjacency in place and raises its version; remove() zeroes the resident sets and marks them again
+    from the surviving + added edges into the same buffers (one pass on the device, no host plan).  materialize() hands out
+    the object's snapshot(), which no later change writes to.  Where the route does not apply, add() / remove() take the
+    route above and the object changes as it does there."""
+
+    def __init__(self, data, capacity=1024, num_live=None, num_live_relations=None, relation_bits_budget=256 << 20,
+                 live_relation_graph=False):
         if not isinstance(capacity, int) or capacity < 1:
             raise ValueError("capacity must be a positive int (facts), got %r" % (capacity,))
+        if not isinstance(live_relation_graph, bool):
+            raise ValueError("live_relation_graph must be True or False, got %r" % (live_relation_graph,))
+        self.live_relation_graph = live_relation_graph
         self.base = data
         self.num_nodes, self.num_relations = int(data.num_nodes), int(data.num_relations)
         self.num_live = self.num_nodes if num_live is None else int(num_live)
@@ -892,7 +962,7 @@ class GraphDelta(object):
         self._prepare()
         if self.traversal is not None:
             self._prepare_traversal()
-        if not (added and self._add_to_relation_graph(added)):
+        if not (added and self._add_to_relation_graph(added)) and not (not added and self._remark_live_relation_graph()):
             self._rebuild_relation_graph()
 
     def _prepare_traversal(self):
@@ -1000,6 +1070,7 @@ class GraphDelta(object):
         edge_index, edge_type = self.edges()
         m = self.num_facts
         new = torch.cat([torch.arange(m - added, m, device=self.device), torch.arange(2 * m - added, 2 * m, device=self.device)])
+        live = self.live_relation_graph and self.num_relations <= _lib.DENSE_MAX_IN_ROW
         if self._resident is None:      # seeded from the list as it was before these facts
             old = torch.ones(2 * m, dtype=torch.bool, device=self.device)
             old[new] = False
@@ -1009,18 +1080,43 @@ class GraphDelta(object):
                           num_relations=self.num_relations)
             adj, counts, hbits, tbits = tasks.relation_graph_bits(before, incidence=True)
             self._resident = (hbits, tbits, adj, counts, torch.zeros(1, dtype=torch.int32, device=self.device))
-            # (a relation graph handed in that is not the edge list's own is replaced here, as the rebuild replaces it)
-            seeded = tasks.relation_graph_from_bits(adj.clone(), counts)
-            if not self._same_relation_graph(self.relation_graph, seeded):
-                self.relation_graph = seeded
+            if live:
+                # the ONE object change of the live route: from here on the resident matrices are the relation graph
+                self.relation_graph = tasks.LiveRelationGraph(adj, counts)
+            else:
+                # (a relation graph handed in that is not the edge list's own is replaced here, as the rebuild replaces it)
+                seeded = tasks.relation_graph_from_bits(adj.clone(), counts)
+                if not self._same_relation_graph(self.relation_graph, seeded):
+                    self.relation_graph = seeded
+        live = live and isinstance(self.relation_graph, tasks.LiveRelationGraph)
         hbits, tbits, adj, counts, changed = self._resident
         tasks.relation_graph_add_edges(edge_index[:, new], edge_type[new], self.num_nodes, hbits, tbits, adj, counts, changed)
         status = int(changed)       # (the one host read of the update)
         if status & _lib.RELGRAPH_OUT_OF_RANGE:     # (check() has seen every id: the state and the facts disagree)
             raise RuntimeError("GraphDelta: an added edge lies outside the graph the relation bit sets were laid out for")
         if status & _lib.RELGRAPH_CHANGED:
-            # a copy: the object an older capture holds is not written to by later additions
-            self.relation_graph = tasks.relation_graph_from_bits(adj.clone(), counts)
+            if live:
+                # in place: the byte adjacency a captured step reads keeps its address and holds the new cells at the next replay
+                self.relation_graph.changed()
+            else:
+                # a copy: the object an older capture holds is not written to by later additions
+                self.relation_graph = tasks.relation_graph_from_bits(adj.clone(), counts)
+        return True
+
+    def _remark_live_relation_graph(self):
+        """The live relation graph after a retraction: bits cannot be cleared one by one, so the resident sets are zeroed and
+        marked again from the surviving + added edges, into the SAME buffers -- one pass over the edge list on the device, the
+        object and its byte adjacency's address kept.  False where no live relation graph is installed or the route is off."""
+        if (not isinstance(self.relation_graph, tasks.LiveRelationGraph) or self._resident is None or self._full_rebuild
+                or self.relation_graph.adjacency_bits is not self._resident[2]):
+            return False
+        hbits, tbits, adj, counts, _ = self._resident
+        edge_index, edge_type = self.edges()
+        base_index, base_type = self.surviving(self.base.edge_index, self.base.edge_type)
+        full = Data(edge_index=torch.cat([base_index, edge_index], dim=1), edge_type=torch.cat([base_type, edge_type]),
+                    num_nodes=self.num_nodes, num_relations=self.num_relations)
+        tasks.relation_graph_bits(full, incidence=True, out=(adj, counts, hbits, tbits))
+        self.relation_graph.changed()
         return True
 
     def _rebuild_relation_graph(self):
@@ -1033,7 +1129,8 @@ class GraphDelta(object):
                     edge_type=torch.cat([base_type, edge_type]), num_nodes=self.num_nodes,
                     num_relations=self.num_relations)
         new = tasks.build_relation_graph(full).relation_graph
-        if not self._same_relation_graph(self.relation_graph, new):
+        # (a live relation graph whose resident state was just dropped is never kept: nothing would keep it current)
+        if isinstance(self.relation_graph, tasks.LiveRelationGraph) or not self._same_relation_graph(self.relation_graph, new):
             self.relation_graph = new
 
     @staticmethod
@@ -1065,7 +1162,9 @@ class GraphDelta(object):
         out.edge_index = torch.cat([base_index, edge_index.to(data.edge_index.device)], dim=1)
         out.edge_type = torch.cat([base_type, edge_type.to(data.edge_type.device)])
         if self.relation_graph is not None and data is self.base:
-            out.relation_graph = self.relation_graph
+            # (a live relation graph is written in place: the caller gets the snapshot of this version, which never is)
+            live = isinstance(self.relation_graph, tasks.LiveRelationGraph)
+            out.relation_graph = self.relation_graph.snapshot() if live else self.relation_graph
         self._materialized = (data, out)
         return out
 

@@ -356,20 +356,29 @@ def filtered_ranking_masks(data, batch, pred, mode="tail"):
     return compute_ranking(pred, pos, mask), mask.sum(dim=-1)
 
 
-def relation_graph_bits(graph, incidence=False):
+def relation_graph_bits(graph, incidence=False, out=None):
     """(adj, row_counts): the four adjacency bit matrices [hh | tt | ht | th] of graph's relation graph, shape
     (4, num_relations, W) int32 words, and the edges per (type, row) -- built by the HIP kernels of csrc/relgraph.hip.
     incidence: (adj, row_counts, hbits, tbits) -- with the entities' relation bit sets, (num_nodes * W) words each: the state
-    relation_graph_add_edges keeps current."""
+    relation_graph_add_edges keeps current.  out: that tuple from an earlier call for a graph of the same shape -- zeroed and
+    marked again in place, the same tensors returned (a live relation graph after a retraction)."""
     from ._lib import check, lib, stream_of
     ei, et = graph.edge_index.to(torch.int64).contiguous(), graph.edge_type.to(torch.int64).contiguous()
     n, r = int(graph.num_nodes), int(graph.num_relations)
     w = (r + 31) // 32
     dev = ei.device
-    hbits = torch.zeros(n * w, dtype=torch.int32, device=dev)
-    tbits = torch.zeros(n * w, dtype=torch.int32, device=dev)
-    adj = torch.zeros(4, r, w, dtype=torch.int32, device=dev)
-    counts = torch.empty(4 * r, dtype=torch.int64, device=dev)
+    if out is not None:
+        adj, counts, hbits, tbits = out
+        if (tuple(adj.shape), hbits.numel(), tbits.numel(), counts.numel()) != ((4, r, w), n * w, n * w, 4 * r) \
+                or any(t.device != dev or not t.is_contiguous() for t in out):
+            raise ValueError("`out` is the (adj, row_counts, hbits, tbits) of an earlier incidence=True call for this shape")
+        for t in (adj, hbits, tbits):
+            t.zero_()
+    else:
+        hbits = torch.zeros(n * w, dtype=torch.int32, device=dev)
+        tbits = torch.zeros(n * w, dtype=torch.int32, device=dev)
+        adj = torch.zeros(4, r, w, dtype=torch.int32, device=dev)
+        counts = torch.empty(4 * r, dtype=torch.int64, device=dev)
     check(lib.ultra_relation_graph_bits(ei.data_ptr(), et.data_ptr(), ei.shape[1], n, r, hbits.data_ptr(), tbits.data_ptr(),
                                         adj.data_ptr(), counts.data_ptr(), stream_of(dev)))
     return (adj, counts, hbits, tbits) if incidence else (adj, counts)
@@ -410,14 +419,103 @@ def build_relation_graph_gpu(graph):
     return graph
 
 
-def relation_graph_dense_adjacency(adj):
-    """The byte adjacency of the reference-order layer kernel (plan.hpp `a_ex`) from the bit matrices, on the device."""
+def relation_graph_dense_adjacency(adj, out=None):
+    """The byte adjacency of the reference-order layer kernel (plan.hpp `a_ex`) from the bit matrices, on the device.  `out`: the
+    vector of an earlier call for the same shape, rewritten in place (every byte is written) and returned."""
     from ._lib import check, lib, stream_of
     r = adj.shape[1]
     nt = (r + 15) // 16
-    out = torch.empty(nt * nt * 1024, dtype=torch.uint8, device=adj.device)
+    if out is None:
+        out = torch.empty(nt * nt * 1024, dtype=torch.uint8, device=adj.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (nt * nt * 1024,) or not out.is_contiguous() or out.device != adj.device:
+        raise ValueError("`out` is the contiguous uint8 vector of %d bytes on %s an earlier call returned" % (nt * nt * 1024, adj.device))
     check(lib.ultra_relation_graph_dense_adjacency(adj.contiguous().data_ptr(), r, out.data_ptr(), stream_of(adj)))
     return out
+
+
+def _edges_of_bits(adj):
+    """(edge_index, edge_type) of the bit matrices in the reference's order -- the hh, tt, ht, th blocks, each sorted by
+    (row, col) -- in plain torch: what ultra_relation_graph_emit writes, for bits that live on the CPU."""
+    r, words = adj.shape[1], adj.shape[2]
+    shifts = torch.arange(32, dtype=torch.int32, device=adj.device)
+    cells = ((adj.to(torch.int32).unsqueeze(-1) >> shifts) & 1).reshape(4, r, words * 32)[:, :, :r]
+    edge_type, row, col = cells.nonzero().unbind(1)      # (lexicographic: type, row, col)
+    return torch.stack([row, col]), edge_type
+
+
+class LiveRelationGraph(object):
+    """A relation graph that is kept current IN PLACE: one object for the life of a graph delta, so that whatever
+    recorded its identity -- the plan cache's key, a captured step -- survives a change of its cells.
+
+    adjacency_bits   the RESIDENT (4, 2 R', W) bit matrices [hh | tt | ht | th] themselves, not a copy: their owner
+                     (rspmm.GraphDelta) ORs new cells into them and calls changed().
+    dense_adjacency  the same cells as the byte adjacency of the reference-order layer kernel (`a_ex` layout), one uint8 tensor
+                     that keeps its address: changed() rewrites it on the current stream.  None for bits on the CPU or more than
+                     DENSE_MAX_IN_ROW nodes (no kernel reads it there).
+    version          an int raised by every changed(): what a cache keyed by this object must also compare.
+    edge_index / edge_type   the edge list in the reference's order, emitted on demand (ultra_relation_graph_emit) and kept until
+                     the next changed(): for consumers off the live route.  The tensors of one version are never written again.
+    snapshot()       an ordinary relation graph (tasks.relation_graph_from_bits of a COPY of the bits), kept per version: what
+                     materialize() hands out, never written by a later change."""
+
+    num_relations = 4
+
+    def __init__(self, adj, counts):
+        if adj.dim() != 3 or adj.shape[0] != 4 or adj.dtype != torch.int32 or adj.shape[2] != (adj.shape[1] + 31) // 32:
+            raise ValueError("Expected the (4, num_relations, ceil(num_relations / 32)) int32 bit matrices, got %s %s"
+                             % (adj.dtype, tuple(adj.shape)))
+        if counts is not None and (counts.numel() != 4 * adj.shape[1] or counts.device != adj.device):
+            raise ValueError("Expected the %d edge counts per (type, row) on the bits' device" % (4 * adj.shape[1]))
+        self.adjacency_bits = adj
+        self._counts = counts
+        self.num_nodes = int(adj.shape[1])
+        self.version = 0
+        self._edges = None          # (version, edge_index, edge_type)
+        self._snapshot = None       # (version, Data)
+        from ._lib import DENSE_MAX_IN_ROW
+        self.dense_adjacency = None
+        if adj.is_cuda and self.num_nodes <= DENSE_MAX_IN_ROW:
+            self.dense_adjacency = relation_graph_dense_adjacency(adj)
+
+    def changed(self):
+        """The owner has written adjacency_bits (and the counts): refresh dense_adjacency in place, on the current stream, and
+        raise the version."""
+        if self.dense_adjacency is not None:
+            relation_graph_dense_adjacency(self.adjacency_bits, out=self.dense_adjacency)
+        self.version += 1
+
+    def _emit(self, adj):
+        if adj.is_cuda:
+            return relation_graph_from_bits(adj, self._counts)
+        edge_index, edge_type = _edges_of_bits(adj)
+        return Data(edge_index=edge_index, edge_type=edge_type, num_nodes=self.num_nodes, num_relations=4, adjacency_bits=adj)
+
+    def _current_edges(self):
+        if self._edges is None or self._edges[0] != self.version:
+            emitted = self._emit(self.adjacency_bits)
+            self._edges = (self.version, emitted.edge_index, emitted.edge_type)
+        return self._edges
+
+    @property
+    def edge_index(self):
+        return self._current_edges()[1]
+
+    @property
+    def edge_type(self):
+        return self._current_edges()[2]
+
+    @property
+    def num_edges(self):
+        return self.edge_index.shape[1]
+
+    @property
+    def device(self):
+        return self.adjacency_bits.device
+
+    def snapshot(self):
+        if self._snapshot is None or self._snapshot[0] != self.version:
+            self._snapshot = (self.version, self._emit(self.adjacency_bits.clone()))
+        return self._snapshot[1]
 
 
 def build_relation_graph(graph, node_chunk=1 << 16):
