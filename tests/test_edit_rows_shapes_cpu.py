@@ -92,6 +92,8 @@ ADD_0 = [(ROW_0, 20, 1), (ROW_0, 11, 5), (ROW_0, 20, 3)]
 ADD_1 = (ROW_1, 126, 0)
 ADD_17 = other_type(ROW_17, 16)                               # a delta edge behind the 17-row's last base edge
 ADD_100 = [(ROW_100, 0, 2), other_type(ROW_100, 80)]
+ADD_16 = (ROW_16, 124, 1)                                     # above the 16-row's last column: the base cursor ends where a reload would begin
+ADD_33 = [other_type(ROW_33, 15), other_type(ROW_33, 32)]     # equal columns on both sides of the second reload and at the last pair
 
 # added: edges (row, col, type) in the plan's direction, each stated through its fact; dead: (row, sorted base positions);
 # survivors: the number of edges the named rows keep in materialize()
@@ -105,6 +107,9 @@ CASES = {
     "r17_all_dead": Case([], {ROW_17: list(range(17))}, {ROW_17: 0}),
     "r17_delta_behind_16": Case([ADD_17], {}, {ROW_17: 18}),
     "r16_dead_15_the_last": Case([], {ROW_16: [15]}, {ROW_16: 15}),
+    "r16_add_above": Case([ADD_16], {}, {ROW_16: 17}),
+    "r33_add_equal_15_32": Case(ADD_33, {}, {ROW_33: 35}),
+    "r100_two_added": Case(ADD_100, {}, {ROW_100: 102}),
     "r33_dead_16": Case([], {ROW_33: [16]}, {ROW_33: 32}),
     "r33_dead_31_32": Case([], {ROW_33: [31, 32]}, {ROW_33: 31}),
     "r33_dead_15_to_32_over_a_chunk": Case([], {ROW_33: list(range(15, 33))}, {ROW_33: 15}),
@@ -190,6 +195,7 @@ def test_the_base_graph_is_what_the_cases_rely_on(data):
         cols = [col for col, _ in BASE_ROWS[row]]
         assert places["below"][1] < cols[0] and places["above"][1] > cols[-1] and places["equal"][1] in cols, row
     assert ADD_17[1] == BASE_ROWS[ROW_17][16][0] and ADD_17 not in BASE_SET
+    assert ADD_16[1] > BASE_ROWS[ROW_16][15][0] and [edge[1] for edge in ADD_33] == [BASE_ROWS[ROW_33][p][0] for p in (15, 32)]
     assert all(edge not in BASE_SET for case in CASES.values() for edge in case.added)
 
 

@@ -1,14 +1,15 @@
-// Added facts as a DELTA on the cached plan of a served graph (ultra_rspmm_delta_rows, include/ultra_rspmm.h).
+// Edits as a DELTA on the cached plan of a served graph: ONE walk of the edited rows with two optional cursors
+// (ultra_rspmm_delta_rows / _edit_rows / _edit_rows_samples, include/ultra_rspmm.h).
 //
 // The plan of the base graph stays as it is.  After a layer's aggregate (ultra_rspmm_forward / _forward_point on the base
-// plan) ONE launch recomputes the output rows that an added edge points into -- the only rows whose value differs on the
-// graph with the added facts -- and overwrites them.  Per (touched row, outer slice) one 16-lane group walks the row's base
-// edges (the plan's device CSR: row_ptr / col / type, sorted by (row, col, edge id)) and the row's delta edges (sorted by
-// (row, col, insertion id)) as a two-way merge on col, base edges first at equal col: the sorted (row, col, edge id) order of a
-// plan of the concatenated edge list, where the delta edges carry the highest ids.  Messages and the sequential reduction
-// are those of the reference-order kernels for unit edge weights (rspmm_kernels.hpp: binary / nary), the epilogue is the
-// boundary epilogue of rspmm_order_kernels.hpp: with -ffp-contract=off the rows equal those of a fresh reference-order plan of
-// the materialised graph bit for bit.
+// plan) ONE launch recomputes the output rows that an edit points into -- the only rows whose value differs on the edited
+// graph -- and overwrites them.  Per (touched row, outer slice) one 16-lane group walks the row's base edges (the plan's device
+// CSR: row_ptr / col / type, sorted by (row, col, edge id)) and the row's delta edges (sorted by (row, col, insertion id)) as a
+// two-way merge on col, base edges first at equal col: the sorted (row, col, edge id) order of a plan of the concatenated edge
+// list, where the delta edges carry the highest ids.  Messages and the sequential reduction are those of the reference-order
+// kernels for unit edge weights (rspmm_kernels.hpp: binary / nary), the epilogue is the boundary epilogue of
+// rspmm_order_kernels.hpp: with -ffp-contract=off the rows equal those of a fresh reference-order plan of the materialised
+// graph bit for bit.
 //
 // The grid is sized by the delta's CAPACITY; the live number of touched rows is read from device memory and the groups
 // beyond it end at once, so a launch recorded into a hipGraph serves every later content of the same buffers.  No atomics,
@@ -17,21 +18,24 @@
 // A hub row (longer than the plan's seg_len, a chain row of the base walk) is walked here by ONE group as one dependent
 // chain: loads are issued DELTA_BATCH edges ahead, the additions stay in order.
 //
-// RETRACTED facts are TOMBSTONES on the same plan (ultra_rspmm_edit_rows).  A removed edge changes the one row it
-// points into, so the touched rows are the union of both kinds and rspmm_edit_rows_kernel is the merge above with one more
-// cursor: per touched row the distinct dead (col, type) keys, sorted; a base edge whose (col, type) is among them takes no part
-// (base edges of one col come in edge-id order, not type order: the keys of that col are scanned).  The base row's (col, type)
-// pairs are read sixteen at a time, one per lane of the group, and handed round by lane shuffles.  A subsequence of a sorted
-// row is still sorted, so the bit-equality argument is the same one.  A row left with NO edge holds what the reference-order walk
-// writes for an edge-less row: the reduction's start value (0; the largest / lowest finite number under min / max, NaryOp::zero
-// of the reference, never an infinity) met by the boundary epilogue -- the boundary row under a dense or an on-row point
-// boundary, 0 under an off-row point boundary with min / max, nothing without a boundary.
+// The walk (edit_rows_walk) is written once; three kernels instantiate it:
+//   rspmm_delta_rows_kernel         <TOMBS = false, KEYS = false>   ADDED facts alone: every base edge and every
+//                                                                   delta edge of the row takes part.
+//   rspmm_edit_rows_kernel          <TOMBS = true,  KEYS = false>   plus RETRACTED facts, TOMBSTONES on the same plan.
+//   rspmm_edit_rows_samples_kernel  <TOMBS = true,  KEYS = true>    plus PER-SLICE dead keys.
 //
-// PER-SLICE dead keys on top of both (ultra_rspmm_edit_rows_samples): leave-one-out verification on a graph that
-// holds edits.  Outer slice s must not see a few (row, col, type) edges -- its stated fact and the inverse -- whether they are
-// base edges or delta edges.  rspmm_edit_rows_samples_kernel is the merge above where both cursors also skip an edge that one of
-// the slice's keys names (type < 0: any type).  A group keeps the keys of its own row in registers (at most eight); the rows no
-// edit points into are the business of the per-sample keep masks of the base walk.
+// TOMBS: a removed edge changes the one row it points into, so the touched rows are the union of both kinds and the base cursor
+// gets one more cursor beside it: per touched row the distinct dead (col, type) keys, sorted; a base edge whose (col, type) is
+// among them takes no part (base edges of one col come in edge-id order, not type order: the keys of that col are scanned).  A
+// subsequence of a sorted row is still sorted, so the bit-equality argument is the same one.  A row left with NO edge holds what
+// the reference-order walk writes for an edge-less row: the reduction's start value (0; the largest / lowest finite number under
+// min / max, NaryOp::zero of the reference, never an infinity) met by the boundary epilogue -- the boundary row under a dense
+// or an on-row point boundary, 0 under an off-row point boundary with min / max, nothing without a boundary.
+//
+// KEYS: leave-one-out verification on a graph that holds edits.  Outer slice s must not see a few (row, col, type) edges -- its
+// stated fact and the inverse -- whether they are base edges or delta edges, so both cursors also skip an edge that one of the
+// slice's keys names (type < 0: any type).  A group keeps the keys of its own row in registers (at most eight); the rows no edit
+// points into are the business of the per-sample keep masks of the base walk.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -44,6 +48,7 @@ namespace ultra {
 
 constexpr int DELTA_BATCH = 8;        // source / relation rows requested ahead of the ordered additions
 constexpr int DELTA_THREADS = 256;    // sixteen 16-lane groups a workgroup
+constexpr int SAMPLE_KEYS_MAX = 8;
 
 struct DeltaParams {
     const int32_t *row_ptr, *col, *type;                 // the base plan's CSR (sorted edge order)
@@ -59,202 +64,21 @@ struct DeltaParams {
     long long num_edge;
 };
 
-template <typename T, int SUM, int MUL>
-__global__ void __launch_bounds__(DELTA_THREADS) rspmm_delta_rows_kernel(const DeltaParams p) {
-    constexpr int VEC = 16 / (int)sizeof(T);      // elements per 16-byte chunk
-    using P = Pack<T, VEC>;
-    const int l16 = threadIdx.x & 15;
-    const long long group = (long long)blockIdx.x * (DELTA_THREADS / 16) + (threadIdx.x >> 4);
-    const int k = (int)(group / p.n_outer), outer = (int)(group - (long long)k * p.n_outer);
-    const int live = min(max(*p.d_count, 0), p.cap_rows);
-    if (k >= live) return;
-    const int row = p.d_row[k];
-    if (row < 0 || row >= p.num_out) return;      // (a delta prepared for another graph: nothing is written)
-    int i = p.row_ptr[row];
-    const int ie = p.row_ptr[row + 1];
-    int j = min(max(p.d_ptr[k], 0), p.cap_edges);
-    const int je = min(max(p.d_ptr[k + 1], j), p.cap_edges);
-    if (i < 0 || ie < i || ie > p.num_edge) return;
-
-    const T *rel = reinterpret_cast<const T *>(p.rel.ptr) + outer * p.rel.stride_outer;
-    const T *x = reinterpret_cast<const T *>(p.x.ptr) + outer * p.x.stride_outer;
-    T *dst = reinterpret_cast<T *>(p.out) + outer * p.out_stride_outer + (long long)row * p.out_stride_row;
-    const long long bnd_row = p.bnd_rows ? p.bnd_rows[outer] : -1;
-
-    for (int d0 = VEC * l16; d0 < p.row_len; d0 += 16 * VEC) {
-        int bi = i, dj = j;
-        int bcol = bi < ie ? p.col[bi] : 0, dcol = dj < je ? p.d_col[dj] : 0;
-        P acc;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) acc.v[e] = nary_zero<T, SUM>();
-        while (bi < ie || dj < je) {
-            // the next DELTA_BATCH edges of the merged order: (col, type) each
-            int c[DELTA_BATCH], t[DELTA_BATCH];
-            bool take[DELTA_BATCH];
-#pragma unroll
-            for (int u = 0; u < DELTA_BATCH; ++u) {
-                c[u] = 0, t[u] = 0, take[u] = false;
-                if (bi < ie && (dj >= je || bcol <= dcol)) {        // (equal col: the base edge has the lower edge id)
-                    c[u] = bcol, t[u] = p.type[bi], take[u] = true;
-                    ++bi;
-                    if (bi < ie) bcol = p.col[bi];
-                } else if (dj < je) {
-                    c[u] = dcol, t[u] = p.d_type[dj], take[u] = true;
-                    ++dj;
-                    if (dj < je) dcol = p.d_col[dj];
-                }
-                // (an index outside the operands is never dereferenced: such an edge reads row 0 and is left out of the reduction)
-                if (c[u] < 0 || c[u] >= p.num_in || t[u] < 0 || t[u] >= p.num_rel) c[u] = 0, t[u] = 0, take[u] = false;
-            }
-            P xv[DELTA_BATCH], rv[DELTA_BATCH];
-#pragma unroll
-            for (int u = 0; u < DELTA_BATCH; ++u) {
-                xv[u] = *reinterpret_cast<const P *>(x + (long long)c[u] * p.x.stride_row + d0);
-                rv[u] = *reinterpret_cast<const P *>(rel + (long long)t[u] * p.rel.stride_row + d0);
-            }
-#pragma unroll
-            for (int u = 0; u < DELTA_BATCH; ++u) {
-                if (take[u]) {
-#pragma unroll
-                    for (int e = 0; e < VEC; ++e) acc.v[e] = nary<T, SUM>(acc.v[e], binary<T, MUL>(rv[u].v[e], xv[u].v[e]));
-                }
-            }
-        }
-        // the boundary epilogue of the reference-order kernels
-        if (p.has_bnd && (bnd_row < 0 || bnd_row == row)) {
-            const P b = *reinterpret_cast<const P *>(reinterpret_cast<const T *>(p.bnd.ptr) + outer * p.bnd.stride_outer +
-                                                     (bnd_row < 0 ? (long long)row * p.bnd.stride_row : 0) + d0);
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) acc.v[e] = nary<T, SUM>(acc.v[e], b.v[e]);
-        } else if (SUM != ULTRA_SUM_ADD && p.has_bnd) {     // (min / max: a point boundary stands for zeros elsewhere)
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) acc.v[e] = nary<T, SUM>(acc.v[e], T(0));
-        }
-        *reinterpret_cast<P *>(dst + d0) = acc;
-    }
-}
-
 struct EditParams : DeltaParams {
     const int32_t *t_ptr, *t_col, *t_type;               // the tombstones: per touched row its dead (col, type) keys, sorted
     int32_t cap_keys;
 };
-
-// rspmm_delta_rows_kernel with the dead base edges left out.  (bi, bcol, btype) is always the next LIVE base edge of the row.
-template <typename T, int SUM, int MUL>
-__global__ void __launch_bounds__(DELTA_THREADS) rspmm_edit_rows_kernel(const EditParams p) {
-    constexpr int VEC = 16 / (int)sizeof(T);      // elements per 16-byte chunk
-    using P = Pack<T, VEC>;
-    const int l16 = threadIdx.x & 15;
-    const long long group = (long long)blockIdx.x * (DELTA_THREADS / 16) + (threadIdx.x >> 4);
-    const int k = (int)(group / p.n_outer), outer = (int)(group - (long long)k * p.n_outer);
-    const int live = min(max(*p.d_count, 0), p.cap_rows);
-    if (k >= live) return;
-    const int row = p.d_row[k];
-    if (row < 0 || row >= p.num_out) return;      // (a delta prepared for another graph: nothing is written)
-    const int i = p.row_ptr[row];
-    const int ie = p.row_ptr[row + 1];
-    const int j = min(max(p.d_ptr[k], 0), p.cap_edges);
-    const int je = min(max(p.d_ptr[k + 1], j), p.cap_edges);
-    const int q = min(max(p.t_ptr[k], 0), p.cap_keys);
-    const int qe = min(max(p.t_ptr[k + 1], q), p.cap_keys);
-    if (i < 0 || ie < i || ie > p.num_edge) return;
-
-    const T *rel = reinterpret_cast<const T *>(p.rel.ptr) + outer * p.rel.stride_outer;
-    const T *x = reinterpret_cast<const T *>(p.x.ptr) + outer * p.x.stride_outer;
-    T *dst = reinterpret_cast<T *>(p.out) + outer * p.out_stride_outer + (long long)row * p.out_stride_row;
-    const long long bnd_row = p.bnd_rows ? p.bnd_rows[outer] : -1;
-
-    // (every lane of the group takes every trip, the lanes beyond a short row on chunk 0 without storing: the base indices
-    // below pass between the group's lanes)
-    for (int dbase = 0; dbase < p.row_len; dbase += 16 * VEC) {
-        const bool dvalid = dbase + VEC * l16 < p.row_len;
-        const int d0 = dvalid ? dbase + VEC * l16 : 0;
-        int bi = i - 1, dj = j, kq = q;
-        int bcol = 0, btype = 0, dcol = dj < je ? p.d_col[dj] : 0;
-        // the base row's (col, type) pairs, sixteen at a time: lane l holds pair cbase + l, one coalesced load for sixteen
-        // steps of the walk instead of a dependent load per step
-        int cbase = i - 16, ccol = 0, ctype = 0;
-        int kcol = kq < qe ? p.t_col[kq] : INT32_MAX;    // the key under the cursor
-        // step to the next base edge that carries no tombstone (the key cursor only moves forward: cols ascend along the row)
-        const auto next_base = [&]() {
-            for (++bi; bi < ie; ++bi) {
-                if (bi >= cbase + 16) {
-                    cbase = bi;
-                    const int mine = min(bi + l16, ie - 1);
-                    ccol = p.col[mine], ctype = p.type[mine];
-                }
-                bcol = __shfl(ccol, bi - cbase, 16), btype = __shfl(ctype, bi - cbase, 16);
-                while (kcol < bcol) {
-                    ++kq;
-                    kcol = kq < qe ? p.t_col[kq] : INT32_MAX;
-                }
-                if (kcol != bcol) return;                        // (no key at this col: the edge lives)
-                bool dead = false;
-                for (int s = kq; s < qe && p.t_col[s] == bcol; ++s) dead |= p.t_type[s] == btype;
-                if (!dead) return;
-            }
-        };
-        next_base();
-        P acc;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) acc.v[e] = nary_zero<T, SUM>();
-        while (bi < ie || dj < je) {
-            int c[DELTA_BATCH], t[DELTA_BATCH];
-            bool take[DELTA_BATCH];
-#pragma unroll
-            for (int u = 0; u < DELTA_BATCH; ++u) {
-                c[u] = 0, t[u] = 0, take[u] = false;
-                if (bi < ie && (dj >= je || bcol <= dcol)) {        // (equal col: the base edge has the lower edge id)
-                    c[u] = bcol, t[u] = btype, take[u] = true;
-                    next_base();
-                } else if (dj < je) {
-                    c[u] = dcol, t[u] = p.d_type[dj], take[u] = true;
-                    ++dj;
-                    if (dj < je) dcol = p.d_col[dj];
-                }
-                // (an index outside the operands is never dereferenced: such an edge reads row 0 and is left out of the reduction)
-                if (c[u] < 0 || c[u] >= p.num_in || t[u] < 0 || t[u] >= p.num_rel) c[u] = 0, t[u] = 0, take[u] = false;
-            }
-            P xv[DELTA_BATCH], rv[DELTA_BATCH];
-#pragma unroll
-            for (int u = 0; u < DELTA_BATCH; ++u) {
-                xv[u] = *reinterpret_cast<const P *>(x + (long long)c[u] * p.x.stride_row + d0);
-                rv[u] = *reinterpret_cast<const P *>(rel + (long long)t[u] * p.rel.stride_row + d0);
-            }
-#pragma unroll
-            for (int u = 0; u < DELTA_BATCH; ++u) {
-                if (take[u]) {
-#pragma unroll
-                    for (int e = 0; e < VEC; ++e) acc.v[e] = nary<T, SUM>(acc.v[e], binary<T, MUL>(rv[u].v[e], xv[u].v[e]));
-                }
-            }
-        }
-        // the boundary epilogue of the reference-order kernels; a row with no surviving edge meets it with the start value
-        if (p.has_bnd && (bnd_row < 0 || bnd_row == row)) {
-            const P b = *reinterpret_cast<const P *>(reinterpret_cast<const T *>(p.bnd.ptr) + outer * p.bnd.stride_outer +
-                                                     (bnd_row < 0 ? (long long)row * p.bnd.stride_row : 0) + d0);
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) acc.v[e] = nary<T, SUM>(acc.v[e], b.v[e]);
-        } else if (SUM != ULTRA_SUM_ADD && p.has_bnd) {     // (min / max: a point boundary stands for zeros elsewhere)
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) acc.v[e] = nary<T, SUM>(acc.v[e], T(0));
-        }
-        if (dvalid) *reinterpret_cast<P *>(dst + d0) = acc;
-    }
-}
 
 struct SampleParams : EditParams {
     const int32_t *k_row, *k_col, *k_type;               // per outer slice `per_sample` dead (row, col, type) keys; type < 0: any
     int32_t per_sample;
 };
 
-constexpr int SAMPLE_KEYS_MAX = 8;
-
-// rspmm_edit_rows_kernel with per-outer-slice dead keys that apply to base AND delta edges (leave-one-out verification on a live
-// graph).  The slice's keys that name this row are filtered into registers once per group; a group with none takes
-// one always-false branch per edge.  (bi, bcol, btype) is the next live base edge, (dj, dcol, dtype) the next live delta edge.
-template <typename T, int SUM, int MUL>
-__global__ void __launch_bounds__(DELTA_THREADS) rspmm_edit_rows_samples_kernel(const SampleParams p) {
+// The walk of one (touched row, outer slice) by one 16-lane group.  (bi, bcol, btype) is always the next LIVE base edge of the
+// row, (dj, dcol, dtype) the next live delta edge.  TOMBS reads EditParams' tombstones, KEYS SampleParams' per-slice keys; with
+// KEYS a NULL t_ptr means "no tombstones".
+template <typename T, int SUM, int MUL, bool TOMBS, bool KEYS, typename Params>
+__device__ __forceinline__ void edit_rows_walk(const Params &p) {
     constexpr int VEC = 16 / (int)sizeof(T);      // elements per 16-byte chunk
     using P = Pack<T, VEC>;
     const int l16 = threadIdx.x & 15;
@@ -268,23 +92,29 @@ __global__ void __launch_bounds__(DELTA_THREADS) rspmm_edit_rows_samples_kernel(
     const int ie = p.row_ptr[row + 1];
     const int j = min(max(p.d_ptr[k], 0), p.cap_edges);
     const int je = min(max(p.d_ptr[k + 1], j), p.cap_edges);
-    const int q = p.t_ptr ? min(max(p.t_ptr[k], 0), p.cap_keys) : 0;      // (no tombstones: an empty key range)
-    const int qe = p.t_ptr ? min(max(p.t_ptr[k + 1], q), p.cap_keys) : 0;
+    int q = 0, qe = 0;                            // (no tombstones: an empty key range)
+    if constexpr (TOMBS) {                        // (two selects, not one branch: DESIGN.md 26 has the measurement)
+        q = (!KEYS || p.t_ptr) ? min(max(p.t_ptr[k], 0), p.cap_keys) : 0;
+        qe = (!KEYS || p.t_ptr) ? min(max(p.t_ptr[k + 1], q), p.cap_keys) : 0;
+    }
     if (i < 0 || ie < i || ie > p.num_edge) return;
 
-    // this slice's keys that name this row (compared only, never used as an index)
+    // KEYS: this slice's keys that name this row (compared only, never used as an index), filtered into registers once per
+    // group; a group with none takes one always-false branch per edge
     int sc[SAMPLE_KEYS_MAX], st[SAMPLE_KEYS_MAX];
     unsigned smask = 0;
-    const long long sbase = (long long)outer * p.per_sample;
+    if constexpr (KEYS) {
+        const long long sbase = (long long)outer * p.per_sample;
 #pragma unroll
-    for (int u = 0; u < SAMPLE_KEYS_MAX; ++u) {
-        sc[u] = 0, st[u] = 0;
-        if (u < p.per_sample && p.k_row[sbase + u] == row) {
-            sc[u] = p.k_col[sbase + u], st[u] = p.k_type[sbase + u];
-            smask |= 1u << u;
+        for (int u = 0; u < SAMPLE_KEYS_MAX; ++u) {
+            sc[u] = 0, st[u] = 0;
+            if (u < p.per_sample && p.k_row[sbase + u] == row) {
+                sc[u] = p.k_col[sbase + u], st[u] = p.k_type[sbase + u];
+                smask |= 1u << u;
+            }
         }
     }
-    const auto sample_dead = [&](int col, int type) {
+    [[maybe_unused]] const auto sample_dead = [&](int col, int type) {
         bool dead = false;
 #pragma unroll
         for (int u = 0; u < SAMPLE_KEYS_MAX; ++u)
@@ -297,15 +127,20 @@ __global__ void __launch_bounds__(DELTA_THREADS) rspmm_edit_rows_samples_kernel(
     T *dst = reinterpret_cast<T *>(p.out) + outer * p.out_stride_outer + (long long)row * p.out_stride_row;
     const long long bnd_row = p.bnd_rows ? p.bnd_rows[outer] : -1;
 
-    // (every lane of the group takes every trip, as in rspmm_edit_rows_kernel: the base indices pass between the group's lanes)
+    // (every lane of the group takes every trip, the lanes beyond a short row on chunk 0 without storing: the base indices
+    // below pass between the group's lanes)
     for (int dbase = 0; dbase < p.row_len; dbase += 16 * VEC) {
         const bool dvalid = dbase + VEC * l16 < p.row_len;
         const int d0 = dvalid ? dbase + VEC * l16 : 0;
         int bi = i - 1, dj = j - 1, kq = q;
         int bcol = 0, btype = 0, dcol = 0, dtype = 0;
+        // the base row's (col, type) pairs, sixteen at a time: lane l holds pair cbase + l, one coalesced load for sixteen
+        // steps of the walk instead of a dependent load per step
         int cbase = i - 16, ccol = 0, ctype = 0;
-        int kcol = kq < qe ? p.t_col[kq] : INT32_MAX;    // the tombstone key under the cursor
-        // step to the next base edge that carries neither a tombstone nor one of the slice's keys
+        [[maybe_unused]] int kcol = INT32_MAX;           // TOMBS: the tombstone key under the cursor
+        if constexpr (TOMBS) kcol = kq < qe ? p.t_col[kq] : INT32_MAX;
+        // step to the next base edge that carries neither a tombstone nor one of the slice's keys (the key cursor only moves
+        // forward: cols ascend along the row)
         const auto next_base = [&]() {
             for (++bi; bi < ie; ++bi) {
                 if (bi >= cbase + 16) {
@@ -314,14 +149,17 @@ __global__ void __launch_bounds__(DELTA_THREADS) rspmm_edit_rows_samples_kernel(
                     ccol = p.col[mine], ctype = p.type[mine];
                 }
                 bcol = __shfl(ccol, bi - cbase, 16), btype = __shfl(ctype, bi - cbase, 16);
-                while (kcol < bcol) {
-                    ++kq;
-                    kcol = kq < qe ? p.t_col[kq] : INT32_MAX;
-                }
                 bool dead = false;
-                if (kcol == bcol)
-                    for (int s = kq; s < qe && p.t_col[s] == bcol; ++s) dead |= p.t_type[s] == btype;
-                if (smask && !dead) dead = sample_dead(bcol, btype);
+                if constexpr (TOMBS) {
+                    while (kcol < bcol) {
+                        ++kq;
+                        kcol = kq < qe ? p.t_col[kq] : INT32_MAX;
+                    }
+                    if (kcol == bcol)
+                        for (int s = kq; s < qe && p.t_col[s] == bcol; ++s) dead |= p.t_type[s] == btype;
+                }
+                if constexpr (KEYS)
+                    if (smask && !dead) dead = sample_dead(bcol, btype);
                 if (!dead) return;
             }
         };
@@ -329,7 +167,11 @@ __global__ void __launch_bounds__(DELTA_THREADS) rspmm_edit_rows_samples_kernel(
         const auto next_delta = [&]() {
             for (++dj; dj < je; ++dj) {
                 dcol = p.d_col[dj], dtype = p.d_type[dj];
-                if (!smask || !sample_dead(dcol, dtype)) return;
+                if constexpr (KEYS) {
+                    if (!smask || !sample_dead(dcol, dtype)) return;
+                } else {
+                    return;
+                }
             }
         };
         next_base();
@@ -338,6 +180,7 @@ __global__ void __launch_bounds__(DELTA_THREADS) rspmm_edit_rows_samples_kernel(
 #pragma unroll
         for (int e = 0; e < VEC; ++e) acc.v[e] = nary_zero<T, SUM>();
         while (bi < ie || dj < je) {
+            // the next DELTA_BATCH edges of the merged order: (col, type) each
             int c[DELTA_BATCH], t[DELTA_BATCH];
             bool take[DELTA_BATCH];
 #pragma unroll
@@ -381,50 +224,37 @@ __global__ void __launch_bounds__(DELTA_THREADS) rspmm_edit_rows_samples_kernel(
     }
 }
 
-template <typename T>
-static hipError_t launch_samples(int sum, int mul, const SampleParams &p, unsigned grid, hipStream_t s) {
-#define ULTRA_SAMPLES_CASE(S_, M_)                                                                                  \
-    case S_ * 2 + M_:                                                                                               \
-        hipLaunchKernelGGL((rspmm_edit_rows_samples_kernel<T, S_, M_>), dim3(grid), dim3(DELTA_THREADS), 0, s, p);   \
-        break;
-    switch (sum * 2 + mul) {
-        ULTRA_SAMPLES_CASE(0, 0) ULTRA_SAMPLES_CASE(0, 1) ULTRA_SAMPLES_CASE(1, 0) ULTRA_SAMPLES_CASE(1, 1)
-        ULTRA_SAMPLES_CASE(2, 0) ULTRA_SAMPLES_CASE(2, 1)
-        default: return hipErrorInvalidValue;
-    }
-#undef ULTRA_SAMPLES_CASE
+// The three shells keep their names: profiles and tools/retract_bench.py tell an add-only step from a retraction by them.
+template <typename T, int SUM, int MUL>
+__global__ void __launch_bounds__(DELTA_THREADS) rspmm_delta_rows_kernel(const DeltaParams p) {
+    edit_rows_walk<T, SUM, MUL, false, false>(p);
+}
+template <typename T, int SUM, int MUL>
+__global__ void __launch_bounds__(DELTA_THREADS) rspmm_edit_rows_kernel(const EditParams p) {
+    edit_rows_walk<T, SUM, MUL, true, false>(p);
+}
+template <typename T, int SUM, int MUL>
+__global__ void __launch_bounds__(DELTA_THREADS) rspmm_edit_rows_samples_kernel(const SampleParams p) {
+    edit_rows_walk<T, SUM, MUL, true, true>(p);
+}
+
+// kernel K_'s instantiations by [dtype != ULTRA_F32][sum * 2 + mul]
+#define ULTRA_ROWS_KERNELS(K_)                                                                               \
+    {{K_<float, 0, 0>, K_<float, 0, 1>, K_<float, 1, 0>, K_<float, 1, 1>, K_<float, 2, 0>, K_<float, 2, 1>},   \
+     {K_<double, 0, 0>, K_<double, 0, 1>, K_<double, 1, 0>, K_<double, 1, 1>, K_<double, 2, 0>, K_<double, 2, 1>}}
+
+template <typename Params>
+static hipError_t launch_rows(void (*const (&kernels)[2][6])(Params), bool f32, int sum, int mul, const Params &p, unsigned grid,
+                              hipStream_t s) {
+    if (sum < 0 || sum > 2 || mul < 0 || mul > 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kernels[f32 ? 0 : 1][sum * 2 + mul], dim3(grid), dim3(DELTA_THREADS), 0, s, p);
     return hipGetLastError();
 }
 
-template <typename T>
-static hipError_t launch_edit(int sum, int mul, const EditParams &p, unsigned grid, hipStream_t s) {
-#define ULTRA_EDIT_CASE(S_, M_)                                                                                     \
-    case S_ * 2 + M_:                                                                                               \
-        hipLaunchKernelGGL((rspmm_edit_rows_kernel<T, S_, M_>), dim3(grid), dim3(DELTA_THREADS), 0, s, p);           \
-        break;
-    switch (sum * 2 + mul) {
-        ULTRA_EDIT_CASE(0, 0) ULTRA_EDIT_CASE(0, 1) ULTRA_EDIT_CASE(1, 0) ULTRA_EDIT_CASE(1, 1) ULTRA_EDIT_CASE(2, 0)
-        ULTRA_EDIT_CASE(2, 1)
-        default: return hipErrorInvalidValue;
-    }
-#undef ULTRA_EDIT_CASE
-    return hipGetLastError();
-}
-
-template <typename T>
-static hipError_t launch_delta(int sum, int mul, const DeltaParams &p, unsigned grid, hipStream_t s) {
-#define ULTRA_DELTA_CASE(S_, M_)                                                                                    \
-    case S_ * 2 + M_:                                                                                               \
-        hipLaunchKernelGGL((rspmm_delta_rows_kernel<T, S_, M_>), dim3(grid), dim3(DELTA_THREADS), 0, s, p);          \
-        break;
-    switch (sum * 2 + mul) {
-        ULTRA_DELTA_CASE(0, 0) ULTRA_DELTA_CASE(0, 1) ULTRA_DELTA_CASE(1, 0) ULTRA_DELTA_CASE(1, 1) ULTRA_DELTA_CASE(2, 0)
-        ULTRA_DELTA_CASE(2, 1)
-        default: return hipErrorInvalidValue;
-    }
-#undef ULTRA_DELTA_CASE
-    return hipGetLastError();
-}
+static void (*const DELTA_KERNELS[2][6])(DeltaParams) = ULTRA_ROWS_KERNELS(rspmm_delta_rows_kernel);
+static void (*const EDIT_KERNELS[2][6])(EditParams) = ULTRA_ROWS_KERNELS(rspmm_edit_rows_kernel);
+static void (*const SAMPLES_KERNELS[2][6])(SampleParams) = ULTRA_ROWS_KERNELS(rspmm_edit_rows_samples_kernel);
+#undef ULTRA_ROWS_KERNELS
 
 static int delta_invalid(const char *who, const std::string &msg) {
     set_error(std::string(who) + ": " + msg);
@@ -518,12 +348,10 @@ static int delta_rows_impl(const char *who, ultra_plan *plan, int32_t sum, int32
     if (n_outer >= (1ll << 31) || row_len >= (1ll << 31)) return delta_invalid(who, "n_outer / row_len exceed 2^31");
     (void)hipGetLastError();   // drop any stale error left by other users of the HIP runtime
     const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const DeltaParams &dp = p;
-    const EditParams &ep = p;
     const bool f32 = dtype == ULTRA_F32;
-    const hipError_t e = keys    ? (f32 ? launch_samples<float>(sum, mul, p, (unsigned)grid, s) : launch_samples<double>(sum, mul, p, (unsigned)grid, s))
-                         : removed ? (f32 ? launch_edit<float>(sum, mul, ep, (unsigned)grid, s) : launch_edit<double>(sum, mul, ep, (unsigned)grid, s))
-                                   : (f32 ? launch_delta<float>(sum, mul, dp, (unsigned)grid, s) : launch_delta<double>(sum, mul, dp, (unsigned)grid, s));
+    const hipError_t e = keys      ? launch_rows<SampleParams>(SAMPLES_KERNELS, f32, sum, mul, p, (unsigned)grid, s)
+                         : removed ? launch_rows<EditParams>(EDIT_KERNELS, f32, sum, mul, p, (unsigned)grid, s)
+                                   : launch_rows<DeltaParams>(DELTA_KERNELS, f32, sum, mul, p, (unsigned)grid, s);
     if (e != hipSuccess) {
         set_error(std::string(keys ? "rspmm_edit_rows_samples_kernel" : removed ? "rspmm_edit_rows_kernel" : "rspmm_delta_rows_kernel") +
                   " launch: " + hipGetErrorString(e));

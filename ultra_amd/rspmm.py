@@ -382,6 +382,13 @@ class Plan(object):
         capacity, so a hipGraph that recorded it serves the delta's later contents.  Returns `out`, or None where the engine
         does not serve the call (general-walk and dense-format plans, rotate messages, misaligned rows) -- nothing was
         launched then."""
+        return self._recompute_rows(lib.ultra_rspmm_delta_rows, relation, input, out, delta, boundary, sum, mul, point,
+                                    lambda: (delta.operand(),))
+
+    def _recompute_rows(self, entry, relation, input, out, delta, boundary, sum, mul, point, edits, on_gpu=()):
+        """The body of delta_rows, edit_rows and edit_rows_samples: the checks, the operands, one call of `entry`.  `edits()` --
+        called once the checks have passed -- returns the entry's operands between `output` and `stream`, the delta's first;
+        `on_gpu`: further tensors the entry reads."""
         if not self.exact:
             return None
         if (delta.num_nodes, delta.num_relations) != (self.num_node, self.num_relation) or self.num_in != self.num_node:
@@ -389,13 +396,13 @@ class Plan(object):
                                % (delta.num_nodes, delta.num_relations, self.num_node, self.num_relation))
         if point is not None and boundary is not None:
             raise RuntimeError("a point boundary excludes `boundary`")
-        _require_gpu(out, delta.count)
+        _require_gpu(out, delta.count, *on_gpu)
         op = self._forward_operands(relation, input, None, boundary, out, point)
         if op.out is not out:
             raise RuntimeError("`out` must have unit stride along its last dimension")
-        operand = delta.operand()
-        rc = lib.ultra_rspmm_delta_rows(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], op.dtype, op.relation, op.input,
-                                        op.boundary, op.rows, op.out_ref, ctypes.byref(operand), stream_of(input))
+        operands = edits()
+        rc = entry(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], op.dtype, op.relation, op.input, op.boundary, op.rows,
+                   op.out_ref, *[ctypes.byref(operand) for operand in operands], stream_of(input))
         if rc == _lib.ULTRA_ERR_UNSUPPORTED:
             return None
         check(rc)
@@ -407,25 +414,8 @@ class Plan(object):
         bit for bit.  The rows an added or a removed edge points into are recomputed in place, dead base edges skipped
         (ultra_rspmm_edit_rows); nothing is read per edge of the graph, nothing else is written, and a captured launch follows
         the delta's buffers.  Returns `out`, or None exactly where delta_rows does."""
-        if not self.exact:
-            return None
-        if (delta.num_nodes, delta.num_relations) != (self.num_node, self.num_relation) or self.num_in != self.num_node:
-            raise RuntimeError("the delta was made for a graph of %d nodes and %d relations, the plan has %d and %d"
-                               % (delta.num_nodes, delta.num_relations, self.num_node, self.num_relation))
-        if point is not None and boundary is not None:
-            raise RuntimeError("a point boundary excludes `boundary`")
-        _require_gpu(out, delta.count)
-        op = self._forward_operands(relation, input, None, boundary, out, point)
-        if op.out is not out:
-            raise RuntimeError("`out` must have unit stride along its last dimension")
-        operand, removed = delta.operand(), delta.removed_operand()
-        rc = lib.ultra_rspmm_edit_rows(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], op.dtype, op.relation, op.input,
-                                       op.boundary, op.rows, op.out_ref, ctypes.byref(operand), ctypes.byref(removed),
-                                       stream_of(input))
-        if rc == _lib.ULTRA_ERR_UNSUPPORTED:
-            return None
-        check(rc)
-        return out
+        return self._recompute_rows(lib.ultra_rspmm_edit_rows, relation, input, out, delta, boundary, sum, mul, point,
+                                    lambda: (delta.operand(), delta.removed_operand()))
 
     def edit_rows_samples(self, relation, input, out, delta, keys, boundary=None, sum="add", mul="mul", point=None):
         """edit_rows with dead edges PER OUTER SLICE: `keys` = (row, col, type), int32 (n_outer, per_sample) each, per_sample in
@@ -435,33 +425,19 @@ class Plan(object):
         slice s's dead edges, bit for bit (ultra_rspmm_edit_rows_samples); the other rows are not written -- they are right
         where `out` came from forward(edge_weight=keep (n_outer, num_edge), keep=True) with keep rows that leave the same base
         edges out.  Returns `out`, or None exactly where edit_rows does."""
-        if not self.exact:
-            return None
-        if (delta.num_nodes, delta.num_relations) != (self.num_node, self.num_relation) or self.num_in != self.num_node:
-            raise RuntimeError("the delta was made for a graph of %d nodes and %d relations, the plan has %d and %d"
-                               % (delta.num_nodes, delta.num_relations, self.num_node, self.num_relation))
-        if point is not None and boundary is not None:
-            raise RuntimeError("a point boundary excludes `boundary`")
-        key_row, key_col, key_type = keys
-        _require_gpu(out, delta.count, key_row, key_col, key_type)
-        op = self._forward_operands(relation, input, None, boundary, out, point)
-        if op.out is not out:
-            raise RuntimeError("`out` must have unit stride along its last dimension")
-        n_outer = out.shape[0] if out.dim() == 3 else 1
-        for t in (key_row, key_col, key_type):
-            if t.dtype != torch.int32 or t.dim() != 2 or t.shape != key_row.shape or not t.is_contiguous():
-                raise RuntimeError("`keys` are three contiguous int32 tensors of one shape (n_outer, per_sample)")
-        if key_row.shape[0] != n_outer or not 1 <= key_row.shape[1] <= 8:
-            raise RuntimeError("Expected keys of shape (n_outer = %d, 1 .. 8), got %s" % (n_outer, tuple(key_row.shape)))
-        operand, removed = delta.operand(), delta.removed_operand()
-        sample_keys = _lib.UltraSampleKeys(key_row.data_ptr(), key_col.data_ptr(), key_type.data_ptr(), key_row.shape[1])
-        rc = lib.ultra_rspmm_edit_rows_samples(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], op.dtype, op.relation, op.input,
-                                               op.boundary, op.rows, op.out_ref, ctypes.byref(operand), ctypes.byref(removed),
-                                               ctypes.byref(sample_keys), stream_of(input))
-        if rc == _lib.ULTRA_ERR_UNSUPPORTED:
-            return None
-        check(rc)
-        return out
+        def edits():
+            key_row, key_col, key_type = keys
+            n_outer = out.shape[0] if out.dim() == 3 else 1
+            for t in keys:
+                if t.dtype != torch.int32 or t.dim() != 2 or t.shape != key_row.shape or not t.is_contiguous():
+                    raise RuntimeError("`keys` are three contiguous int32 tensors of one shape (n_outer, per_sample)")
+            if key_row.shape[0] != n_outer or not 1 <= key_row.shape[1] <= 8:
+                raise RuntimeError("Expected keys of shape (n_outer = %d, 1 .. 8), got %s" % (n_outer, tuple(key_row.shape)))
+            sample_keys = _lib.UltraSampleKeys(key_row.data_ptr(), key_col.data_ptr(), key_type.data_ptr(), key_row.shape[1])
+            return delta.operand(), delta.removed_operand(), sample_keys
+
+        return self._recompute_rows(lib.ultra_rspmm_edit_rows_samples, relation, input, out, delta, boundary, sum, mul, point,
+                                    edits, on_gpu=keys)
 
     def forward_update(self, relation, input, weight, bias, ln_weight, ln_bias, eps, flags, mul="mul", point=None, timed=None,
                        sum="add"):
