@@ -11,6 +11,8 @@
 
 #include <stdint.h>
 
+#include "ultra_rspmm.h"    /* ultra_explain_edits (ultra_beam_search_edit_rows_batch) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -350,6 +352,24 @@ int32_t ultra_beam_search_layer_batch(const int64_t *row_ptr, const int32_t *csr
                                       int64_t num_edge, int64_t num_sample, const void *edge_grad, const void *dist_in,
                                       const int64_t *tails, int32_t num_beam, void *dist_out, int64_t *back_edge_out,
                                       void *stream);
+
+/*
+ * The beam search on (base graph, delta): called AFTER ultra_beam_search_layer_batch on the base CSR, on the same
+ * stream and with the same dist_in / dist_out / back_edge_out, it recomputes every touched destination row of every sample
+ * (edits->row_dev; ultra_explain_edits, ultra_rspmm.h) and overwrites it; no other row is written.  The candidate stream of
+ * row v is the materialised graph's: the base slots in ascending edge id WITHOUT those whose (src, type) is a dead key of the
+ * row (a binary search in the row's key range), then the row's added edges in ascending j; values dist_in[src, b] + grad with
+ * grad = edge_grad[s, base edge id] or added_grad[s, j] (added_grad: (num_sample, added_grad_stride) fp32).  A dead slot is
+ * skipped like a slot whose source is the sample's tail: it is never "the candidate directly before".  One workgroup of 16 waves
+ * per (touched row, sample), the slice-and-merge of the hub kernel with the added edges as the tail of the last slice -- the
+ * same scan, merge and write routines as the base launch.  The grid is capacity_rows x num_sample, the live row count is read
+ * on the device: no host read.  Arguments as ultra_beam_search_layer_batch; edits == NULL or a NULL array: ULTRA_ERR_INVALID.
+ */
+int32_t ultra_beam_search_edit_rows_batch(const int64_t *row_ptr, const int32_t *csr_src, const int32_t *csr_type,
+                                          const int32_t *csr_eid, int64_t num_node, int64_t num_edge, int64_t num_sample,
+                                          const void *edge_grad, const ultra_explain_edits *edits, const void *added_grad,
+                                          int64_t added_grad_stride, const void *dist_in, const int64_t *tails,
+                                          int32_t num_beam, void *dist_out, int64_t *back_edge_out, void *stream);
 
 /* ---- complex logical queries (UltraQuery) ----
  * ultra_symbolic_traversal: SymbolicTraversal.forward (ultraquery.py:280-298),

@@ -323,6 +323,50 @@ int32_t ultra_rspmm_edit_rows_samples(ultra_plan *plan, int32_t sum, int32_t mul
                                       const ultra_sample_keys *keys, void *stream);
 
 /*
+ * The edits of a graph delta keyed by DESTINATION, for path explanations on (base graph, delta) (csrc/explain_live_kernels.hip,
+ * csrc/beam_search.hip).  The explanation direction sends messages from edge_index[0] (src) into edge_index[1]
+ * (dst); j is an added edge's position among the 2 m appended edges in materialised order.
+ *   row_dev        int32 [capacity_rows]      the distinct destinations an added OR a tombstoned edge points into, ascending
+ *   count_dev      int32 [1]                  their live number, read ON THE DEVICE
+ *   add_ptr_dev    int32 [capacity_rows + 1]  added edges [ptr[k], ptr[k + 1]) point into row_dev[k]
+ *   add_src_dev / add_dst_dev / add_type_dev / add_j_dev   int32 [capacity_edges]   those edges, ascending j within a row
+ *   dead_ptr_dev   int32 [capacity_rows + 1]  dead keys [ptr[k], ptr[k + 1]) belong to row_dev[k]
+ *   dead_src_dev / dead_type_dev              int32 [capacity_keys]   the distinct dead (src, type) keys of a row, sorted by
+ *                                             (src, type): every BASE edge src -> row of that type is absent
+ *   src_row_dev    int32 [capacity_rows]      the distinct SOURCES of the added edges, ascending (the transpose)
+ *   src_count_dev  int32 [1]                  their live number
+ *   src_ptr_dev    int32 [capacity_rows + 1]  added edges [ptr[k], ptr[k + 1]) leave src_row_dev[k]
+ *   src_dst_dev / src_type_dev                int32 [capacity_edges]   those edges, ascending j within a row
+ * An index outside the operands is never dereferenced: its edge takes no part, a row outside is not written.
+ *
+ * ultra_rspmm_delta_edges_forward: output[s, row] += sum over the row's added edges, ascending j, of relation[s, type] *
+ * input[s, src], for every touched row and outer slice: one 16-lane group per (row, slice) sums the messages sequentially and
+ * adds the total to the row with one add -- one writer, no atomics, the same bits run to run.  Called after ultra_rspmm_forward on
+ * the base plan with the 0 / 1 keep vector of the tombstones as edge weights.
+ * ultra_rspmm_delta_edges_backward_input: the transpose, input_grad[s, src] += sum of relation[s, type] * output_grad[s, dst] over
+ * the by-source ranges.  Both: fp32, (n_outer, rows, row_len) operands, row_len a multiple of 4 at 16-byte aligned addresses and
+ * strides (else ULTRA_ERR_UNSUPPORTED, nothing launched); the grid is sized by capacity_rows * n_outer and the groups beyond the
+ * live count end at once.  num_node: rows of input / output; num_relation: rows of relation.
+ * ultra_rspmm_delta_edge_grad_samples: weight_grad[s, j] = sum_d output_grad[s, dst_j, d] * (relation[s, type_j, d] *
+ * input[s, src_j, d]) into (n_outer, weight_grad_stride >= capacity_edges) fp32: one wave per (slot, slice), lane l sums the
+ * elements l, l + 64, ... in ascending order, then the xor-32/16/8/4/2/1 shuffles; EVERY column below capacity_edges is written,
+ * those at or above the live number of added edges with 0 (any row_len >= 1).
+ */
+typedef struct {
+    const int32_t *row_dev, *count_dev, *add_ptr_dev, *add_src_dev, *add_dst_dev, *add_type_dev, *add_j_dev;
+    const int32_t *dead_ptr_dev, *dead_src_dev, *dead_type_dev;
+    const int32_t *src_row_dev, *src_count_dev, *src_ptr_dev, *src_dst_dev, *src_type_dev;
+    int64_t capacity_rows, capacity_edges, capacity_keys;
+} ultra_explain_edits;
+int32_t ultra_rspmm_delta_edges_forward(const ultra_explain_edits *edits, const ultra_mat *relation, const ultra_mat *input,
+                                        const ultra_mat *output, void *stream);
+int32_t ultra_rspmm_delta_edges_backward_input(const ultra_explain_edits *edits, const ultra_mat *relation,
+                                               const ultra_mat *output_grad, const ultra_mat *input_grad, void *stream);
+int32_t ultra_rspmm_delta_edge_grad_samples(const ultra_explain_edits *edits, const ultra_mat *relation, const ultra_mat *input,
+                                            const ultra_mat *output_grad, void *weight_grad_dev, int64_t weight_grad_stride,
+                                            void *stream);
+
+/*
  * Aggregate + layer update in ONE launch (fp32 inference path of GeneralizedRelationalConv.forward,
  * /root/reference/ultra/layers.py:84-131, 190-240, with the residual of /root/reference/ultra/models.py:158-160):
  *

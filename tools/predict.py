@@ -1,6 +1,6 @@
 """Answer one link-prediction query on a dataset of triple files: the k entities the model predicts, with their scores.
 
-    python tools/predict.py --data-root DIR [--ckpt FILE] --head NAME --relation NAME [--inverse] [-k 10] [--unfiltered] [--explain]
+    python tools/predict.py --data-root DIR [--ckpt FILE] --head NAME --relation NAME [--inverse] [-k 10] [--unfiltered] [--explain [--no-compact]]
                             [--add-fact H R T]... [--remove-fact H R T]... [--entity-capacity M] [--add-entity NAME]...
                             [--relation-capacity K] [--add-relation NAME]... [--live-relation-graph]
     python tools/predict.py --data-root DIR [--ckpt FILE] --verify (--head NAME --relation NAME --tail NAME | --triples FILE) [--inverse]
@@ -69,6 +69,8 @@ def main(argv=None):
     ap.add_argument("-k", type=int, default=10)
     ap.add_argument("--unfiltered", action="store_true")
     ap.add_argument("--explain", action="store_true", help="print the top paths behind every answer")
+    ap.add_argument("--no-compact", action="store_true",
+                    help="--explain on a graph that holds edits: explain on the delta, do not fold it into the graph first")
     class Edit(argparse.Action):       # (one list for all kinds: they are applied in command-line order)
         def __call__(self, parser, namespace, values, option_string=None):
             namespace.edits = getattr(namespace, "edits", None) or []
@@ -196,7 +198,8 @@ def main(argv=None):
     relation = torch.tensor([rel.index(args.relation)], device=dev)
     why = None
     if args.explain:
-        ids, scores, count, why = (predictor.explain_heads if args.inverse else predictor.explain_tails)(anchor, relation)
+        ids, scores, count, why = (predictor.explain_heads if args.inverse else predictor.explain_tails)(
+            anchor, relation, compact=not args.no_compact)
     else:
         ids, scores, count = (predictor.heads if args.inverse else predictor.tails)(anchor, relation)
     query = "(?, %s, %s)" % (args.relation, args.head) if args.inverse else "(%s, %s, ?)" % (args.head, args.relation)

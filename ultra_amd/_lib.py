@@ -71,6 +71,15 @@ class UltraSampleKeys(ctypes.Structure):
                 ("per_sample", ctypes.c_int64)]
 
 
+class UltraExplainEdits(ctypes.Structure):
+    """ultra_explain_edits: a graph delta keyed by destination, with the transpose of its added edges, for the explanation
+    route (include/ultra_rspmm.h, ultra_rspmm_delta_edges_forward; ultra_beam_search_edit_rows_batch)."""
+    _fields_ = [(name, ctypes.c_void_p) for name in (
+        "row_dev", "count_dev", "add_ptr_dev", "add_src_dev", "add_dst_dev", "add_type_dev", "add_j_dev", "dead_ptr_dev",
+        "dead_src_dev", "dead_type_dev", "src_row_dev", "src_count_dev", "src_ptr_dev", "src_dst_dev", "src_type_dev")] + [
+        ("capacity_rows", ctypes.c_int64), ("capacity_edges", ctypes.c_int64), ("capacity_keys", ctypes.c_int64)]
+
+
 class UltraTraversalEdits(ctypes.Structure):
     """ultra_traversal_edits: a graph delta in the symbolic traversal's direction (include/ultra_nbfnet.h,
     ultra_symbolic_traversal_edit_rows)."""
@@ -182,6 +191,11 @@ def _load():
     lib.ultra_nonzero_lists_live.argtypes = [vp, i64, i64, vp, vp, vp, i64, vp, vp]
     lib.ultra_beam_search_layer.argtypes =[vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, i64, i32, vp, vp, vp]
     lib.ultra_beam_search_layer_batch.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, i32, vp, vp, vp]
+    editsp = ctypes.POINTER(UltraExplainEdits)
+    lib.ultra_beam_search_edit_rows_batch.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, editsp, vp, i64, vp, vp, i32, vp, vp, vp]
+    lib.ultra_rspmm_delta_edges_forward.argtypes = [editsp, matp, matp, matp, vp]
+    lib.ultra_rspmm_delta_edges_backward_input.argtypes = [editsp, matp, matp, matp, vp]
+    lib.ultra_rspmm_delta_edge_grad_samples.argtypes = [editsp, matp, matp, matp, vp, i64, vp]
     lib.ultra_symbolic_traversal.argtypes = [vp, vp, vp, i64, vp, i64, i32, vp, vp, vp]
     lib.ultra_symbolic_traversal_edit_rows.argtypes = [vp, vp, vp, i64, ctypes.POINTER(UltraTraversalEdits), vp, i64, i32, vp,
                                                        vp, vp]

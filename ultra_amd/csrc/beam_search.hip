@@ -149,25 +149,40 @@ __device__ __forceinline__ BeamArgs beam_sample(BeamArgs a, int64_t s) {
     return a;
 }
 
+// Where a scan takes its candidates from.  src_at(q): the source of slot q, or the sample's tail for a slot that takes no part
+// (the scan skips a tail-sourced slot, and it never becomes "the candidate directly before"); rest(q, ty, g): the slot's type
+// and gradient.  BaseSlots: the CSR's own slots.
+struct BaseSlots {
+    const BeamArgs &a;
+    __device__ __forceinline__ int src_at(int64_t q) const { return a.src[q]; }
+    __device__ __forceinline__ void rest(int64_t q, int &ty, float &g) const {
+        ty = a.type[q];
+        g = a.grad[a.eid[q]];
+    }
+};
+
 // Scan slots [pb, pe) of row v into `st`.  The carry (the candidate directly before slot pb's first one) is computed from
 // the row's slots before pb.
-__device__ void beam_scan(const BeamArgs &a, int64_t v, int64_t row_begin, int64_t pb, int64_t pe, BeamState &st, int lane,
-                          BeamLds &lds) {
+template <typename Slots>
+__device__ void beam_scan(const BeamArgs &a, const Slots &slots, int64_t v, int64_t row_begin, int64_t pb, int64_t pe,
+                          BeamState &st, int lane, BeamLds &lds) {
     const int K = a.K;
     const int t = (int)a.tail;
     bool has_prev = false;
     int prev_src = 0, prev_ty = 0, prev_pr = 0;
     {
         int64_t q = pb - 1;
-        while (q >= row_begin && a.src[q] == t) --q;
+        while (q >= row_begin && slots.src_at(q) == t) --q;
         if (q >= row_begin) {
-            const int s = a.src[q];
-            const float gv = a.grad[a.eid[q]];
+            const int s = slots.src_at(q);
+            int ty;
+            float gv;
+            slots.rest(q, ty, gv);
             const float m = lane < K ? a.dist_in[(int64_t)s * K + lane] + gv : -INFINITY;
             const int pr = beam_prev_rank(m, K);
             has_prev = true;
             prev_src = s;
-            prev_ty = a.type[q];
+            prev_ty = ty;
             prev_pr = __shfl(pr, K - 1);
         }
     }
@@ -177,9 +192,8 @@ __device__ void beam_scan(const BeamArgs &a, int64_t v, int64_t row_begin, int64
         int my_src = t, my_ty = 0;
         float my_g = 0.f;
         if (lane < n) {
-            my_src = a.src[c0 + lane];
-            my_ty = a.type[c0 + lane];
-            my_g = a.grad[a.eid[c0 + lane]];
+            my_src = slots.src_at(c0 + lane);
+            slots.rest(c0 + lane, my_ty, my_g);
         }
         int s_next = __shfl(my_src, 0);
         float d_next = (lane < K && s_next != t) ? a.dist_in[(int64_t)s_next * K + lane] : -INFINITY;
@@ -257,7 +271,26 @@ __global__ void __launch_bounds__(64 * BEAM_ROW_WAVES) beam_row_kernel(BeamArgs 
     st.v = -INFINITY;
     st.src = st.ty = st.pr = 0;
     st.cnt = 0;
-    beam_scan(a, v, rb, rb, re, st, lane, lds[wave]);
+    beam_scan(a, BaseSlots{a}, v, rb, rb, re, st, lane, lds[wave]);
+    beam_write(a, v, st, lane);
+}
+
+// The end of a sliced row: every wave parks its partial list, wave 0 merges them in slice order (ties to the earlier slice =
+// the earlier candidate) and writes the row.
+__device__ __forceinline__ void beam_merge_slices(const BeamArgs &a, int64_t v, BeamState &st, int wave, int lane,
+                                                  BeamLds *scratch, BeamLds *part, int *part_cnt) {
+    part[wave].v[lane] = st.v;
+    part[wave].src[lane] = st.src;
+    part[wave].ty[lane] = st.ty;
+    part[wave].pr[lane] = st.pr;
+    if (lane == 0) part_cnt[wave] = st.cnt;
+    __syncthreads();
+    if (wave != 0) return;
+    for (int w = 1; w < BEAM_HUB_WAVES; ++w) {
+        const int n = part_cnt[w];
+        const bool valid = lane < n;
+        beam_merge(st, part[w].v[lane], valid, part[w].src[lane], part[w].ty[lane], part[w].pr[lane], a.K, lane, scratch[0]);
+    }
     beam_write(a, v, st, lane);
 }
 
@@ -276,22 +309,90 @@ __global__ void __launch_bounds__(64 * BEAM_HUB_WAVES) beam_hub_kernel(BeamArgs 
     st.v = -INFINITY;
     st.src = st.ty = st.pr = 0;
     st.cnt = 0;
-    beam_scan(a, v, rb, pb, pe, st, lane, scratch[wave]);
-    if (lane < 64) {
-        part[wave].v[lane] = st.v;
-        part[wave].src[lane] = st.src;
-        part[wave].ty[lane] = st.ty;
-        part[wave].pr[lane] = st.pr;
+    beam_scan(a, BaseSlots{a}, v, rb, pb, pe, st, lane, scratch[wave]);
+    beam_merge_slices(a, v, st, wave, lane, scratch, part, part_cnt);
+}
+
+// ---- the touched rows of a graph delta (ultra_beam_search_edit_rows_batch) ----
+// The slots of touched row v on the MATERIALISED graph: positions [rb, re) are the row's base slots, where a slot whose
+// (src, type) is among the row's dead keys answers with the tail (it takes no part); positions [re, re + added) are the row's
+// added edges in ascending j, the materialised list's order.  An added edge with an index outside the operands takes no part.
+struct BeamEdits {
+    const int32_t *rows, *count, *add_ptr, *add_src, *add_type, *add_j, *dead_ptr, *dead_src, *dead_type;
+    const float *add_grad;         // (num_sample, add_grad_stride)
+    int64_t add_grad_stride;
+    int32_t cap_rows, cap_edges, cap_keys;
+};
+
+struct EditSlots {
+    const BeamArgs &a;
+    const BeamEdits &e;
+    const float *add_grad;         // this sample's row of the added gradients
+    int64_t re;                    // the end of the base slots
+    int ab, kb, ke;                // the row's first added edge, its dead-key range
+    __device__ __forceinline__ bool dead(int s, int ty) const {
+        int lo = kb, hi = ke;      // the first key >= (s, ty)
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            const int ks = e.dead_src[mid], kt = e.dead_type[mid];
+            if (ks < s || (ks == s && kt < ty)) lo = mid + 1;
+            else hi = mid;
+        }
+        return lo < ke && e.dead_src[lo] == s && e.dead_type[lo] == ty;
     }
-    if (lane == 0) part_cnt[wave] = st.cnt;
-    __syncthreads();
-    if (wave != 0) return;
-    for (int w = 1; w < BEAM_HUB_WAVES; ++w) {
-        const int n = part_cnt[w];
-        const bool valid = lane < n;
-        beam_merge(st, part[w].v[lane], valid, part[w].src[lane], part[w].ty[lane], part[w].pr[lane], a.K, lane, scratch[0]);
+    __device__ __forceinline__ int src_at(int64_t q) const {
+        const int t = (int)a.tail;
+        if (q < re) {
+            const int s = a.src[q];
+            return (kb < ke && dead(s, a.type[q])) ? t : s;
+        }
+        const int64_t at = ab + (q - re);
+        const int s = e.add_src[at], j = e.add_j[at];
+        return (s < 0 || s >= a.num_node || j < 0 || j >= e.cap_edges) ? t : s;
     }
-    beam_write(a, v, st, lane);
+    __device__ __forceinline__ void rest(int64_t q, int &ty, float &g) const {
+        if (q < re) {
+            ty = a.type[q];
+            g = a.grad[a.eid[q]];
+            return;
+        }
+        const int64_t at = ab + (q - re);
+        const int j = e.add_j[at];
+        ty = e.add_type[at];
+        g = (j >= 0 && j < e.cap_edges) ? add_grad[j] : 0.f;
+    }
+};
+
+// One workgroup per (touched row, sample), the hub kernel's shape whatever the row's degree: sixteen contiguous slices of the
+// base slots, the added edges as the tail of the last one.  Overwrites what the base launch wrote for the row.
+__global__ void __launch_bounds__(64 * BEAM_HUB_WAVES) beam_edit_rows_kernel(BeamArgs all, BeamEdits e) {
+    __shared__ BeamLds scratch[BEAM_HUB_WAVES];
+    __shared__ BeamLds part[BEAM_HUB_WAVES];
+    __shared__ int part_cnt[BEAM_HUB_WAVES];
+    const int k = blockIdx.x;
+    const int live = min(max(*e.count, 0), e.cap_rows);
+    if (k >= live) return;                                 // (the whole workgroup)
+    const BeamArgs a = beam_sample(all, blockIdx.y);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t v = e.rows[k];
+    if (v < 0 || v >= a.num_node) return;                  // (a delta of another graph: nothing is written)
+    const int64_t rb = a.row_ptr[v], re = a.row_ptr[v + 1];
+    if (rb < 0 || re < rb || re > a.num_edge) return;
+    EditSlots slots{a, e, e.add_grad + (int64_t)blockIdx.y * e.add_grad_stride, re, 0, 0, 0};
+    slots.ab = min(max(e.add_ptr[k], 0), e.cap_edges);
+    const int ae = min(max(e.add_ptr[k + 1], slots.ab), e.cap_edges);
+    slots.kb = min(max(e.dead_ptr[k], 0), e.cap_keys);
+    slots.ke = min(max(e.dead_ptr[k + 1], slots.kb), e.cap_keys);
+    const int64_t per = (re - rb + BEAM_HUB_WAVES - 1) / BEAM_HUB_WAVES;
+    const int64_t pb = rb + per * wave < re ? rb + per * wave : re;
+    int64_t pe = pb + per < re ? pb + per : re;
+    if (wave == BEAM_HUB_WAVES - 1) pe = re + (ae - slots.ab);
+    BeamState st;
+    st.v = -INFINITY;
+    st.src = st.ty = st.pr = 0;
+    st.cnt = 0;
+    beam_scan(a, slots, v, rb, pb, pe, st, lane, scratch[wave]);
+    beam_merge_slices(a, v, st, wave, lane, scratch, part, part_cnt);
 }
 
 }  // namespace ultra
@@ -381,4 +482,69 @@ extern "C" int32_t ultra_beam_search_layer_batch(const int64_t *row_ptr, const i
     }
     return ultra::beam_launch("batched beam search", row_ptr, csr_src, csr_type, csr_eid, hub_rows, num_hub, num_node, num_edge,
                               num_sample, edge_grad, dist_in, tails, 0, num_beam, dist_out, back_edge_out, stream);
+}
+
+extern "C" int32_t ultra_beam_search_edit_rows_batch(const int64_t *row_ptr, const int32_t *csr_src, const int32_t *csr_type,
+                                                     const int32_t *csr_eid, int64_t num_node, int64_t num_edge,
+                                                     int64_t num_sample, const void *edge_grad, const ultra_explain_edits *edits,
+                                                     const void *added_grad, int64_t added_grad_stride, const void *dist_in,
+                                                     const int64_t *tails, int32_t num_beam, void *dist_out,
+                                                     int64_t *back_edge_out, void *stream) {
+    const char *who = "ultra_beam_search_edit_rows_batch";
+    if (num_beam < 1 || num_beam > ULTRA_BEAM_MAX) {
+        ultra::set_error(std::string(who) + ": num_beam must be in [1, 64]");
+        return ULTRA_ERR_UNSUPPORTED;
+    }
+    if (num_sample < 0 || num_sample > 65535) {
+        ultra::set_error(std::string(who) + ": num_sample must be in [0, 65535]");
+        return ULTRA_ERR_INVALID;
+    }
+    if (!edits || edits->capacity_rows < 0 || edits->capacity_edges < 0 || edits->capacity_keys < 0 ||
+        edits->capacity_rows >= (1ll << 30) || edits->capacity_edges >= (1ll << 30) || edits->capacity_keys >= (1ll << 30)) {
+        ultra::set_error(std::string(who) + ": edits is NULL or a capacity lies outside [0, 2^30)");
+        return ULTRA_ERR_INVALID;
+    }
+    if (num_sample == 0 || edits->capacity_rows == 0) return ULTRA_OK;
+    if (!tails || !row_ptr || !dist_out || !back_edge_out || !dist_in || num_node <= 0 || num_edge < 0 || num_node >= INT32_MAX ||
+        num_edge >= INT32_MAX || (num_edge > 0 && (!csr_src || !csr_type || !csr_eid || !edge_grad)) || !edits->row_dev ||
+        !edits->count_dev || !edits->add_ptr_dev || !edits->dead_ptr_dev ||
+        (edits->capacity_edges > 0 && (!edits->add_src_dev || !edits->add_type_dev || !edits->add_j_dev || !added_grad)) ||
+        (edits->capacity_keys > 0 && (!edits->dead_src_dev || !edits->dead_type_dev)) ||
+        added_grad_stride < edits->capacity_edges) {
+        ultra::set_error(std::string(who) + ": NULL operand, empty graph, or added_grad_stride < capacity_edges");
+        return ULTRA_ERR_INVALID;
+    }
+    ULTRA_DEVICE_SCOPE(stream, dist_out);
+    ultra::BeamArgs a;
+    a.row_ptr = row_ptr;
+    a.src = csr_src;
+    a.type = csr_type;
+    a.eid = csr_eid;
+    a.grad = (const float *)edge_grad;
+    a.dist_in = (const float *)dist_in;
+    a.dist_out = (float *)dist_out;
+    a.back_out = back_edge_out;
+    a.hub_rows = nullptr;
+    a.tails = tails;
+    a.num_node = num_node;
+    a.num_edge = num_edge;
+    a.tail = 0;
+    a.K = num_beam;
+    ultra::BeamEdits e;
+    e.rows = edits->row_dev, e.count = edits->count_dev, e.add_ptr = edits->add_ptr_dev, e.add_src = edits->add_src_dev;
+    e.add_type = edits->add_type_dev, e.add_j = edits->add_j_dev, e.dead_ptr = edits->dead_ptr_dev;
+    e.dead_src = edits->dead_src_dev, e.dead_type = edits->dead_type_dev;
+    e.add_grad = (const float *)added_grad;
+    e.add_grad_stride = added_grad_stride;
+    e.cap_rows = (int32_t)edits->capacity_rows, e.cap_edges = (int32_t)edits->capacity_edges;
+    e.cap_keys = (int32_t)edits->capacity_keys;
+    (void)hipGetLastError();   // drop any stale error left by other users of the runtime
+    hipLaunchKernelGGL(ultra::beam_edit_rows_kernel, dim3((unsigned)edits->capacity_rows, (unsigned)num_sample),
+                       dim3(64 * ultra::BEAM_HUB_WAVES), 0, reinterpret_cast<hipStream_t>(stream), a, e);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) {
+        ultra::set_error(std::string(who) + " launch: " + hipGetErrorString(err));
+        return ULTRA_ERR_HIP;
+    }
+    return ULTRA_OK;
 }

@@ -13,6 +13,8 @@ about 4 (max - min) N 2^-23 -- so it is not a bit-exact target.
 """
 from collections import OrderedDict, namedtuple
 
+import ctypes
+
 import torch
 
 from . import _lib
@@ -156,12 +158,17 @@ def _check_index_range(index, name, num_node, num_sample=None):
     return index
 
 
-def beam_search_layer_batch(csr, edge_grad, dist_in, tails, num_beam, tails_checked=False):
+def beam_search_layer_batch(csr, edge_grad, dist_in, tails, num_beam, tails_checked=False, delta=None, added_grad=None):
     """One layer of S searches (ultra_beam_search_layer_batch): edge_grad (S, num_edge), dist_in (S, num_node, num_beam),
     tails (S) -> (S, num_node, num_beam) fp32 distances and (S, num_node, num_beam, 4) int64 back edges; sample s is
     beam_search_layer on slice s with tails[s], bit for bit.  Two launches whatever S is; `tails` is used on the device.
     tails_checked: the caller has already checked the tails against [0, num_node) (beam_search_distance_batch does it once
-    for all layers: on device tensors the check is a read-back)."""
+    for all layers: on device tensors the check is a read-back).
+    delta (rspmm.GraphDelta of the CSR's graph) with added_grad (S, 2 capacity) fp32, column j the gradient of the edge at
+    position j of delta.edges(): the layer on delta.materialize(), bit for bit, from the base graph's CSR -- after the two
+    launches ultra_beam_search_edit_rows_batch recomputes the rows an added or a tombstoned edge points into (the base slots
+    minus the dead keys, then the added edges in ascending j); edge_grad stays over the BASE edge list, the columns of
+    tombstoned edges are never read.  One launch more, sized by the delta's capacity: nothing is read on the host."""
     if not isinstance(num_beam, int) or not 1 <= num_beam <= _lib.BEAM_MAX:
         raise ValueError("num_beam must be an int in [1, %d], got %r" % (_lib.BEAM_MAX, num_beam))
     if edge_grad.dtype != torch.float32 or dist_in.dtype != torch.float32:
@@ -180,6 +187,17 @@ def beam_search_layer_batch(csr, edge_grad, dist_in, tails, num_beam, tails_chec
         tails = _check_index_range(tails, "tails", csr.num_node, num_sample)
     elif tuple(tails.shape) != (num_sample,) or tails.dtype != torch.int64:
         raise ValueError("Expected `tails` of shape (%d,) int64, got %s %s" % (num_sample, tuple(tails.shape), tails.dtype))
+    if (delta is None) != (added_grad is None):
+        raise ValueError("`delta` and `added_grad` go together")
+    if delta is not None:
+        if delta.num_nodes != csr.num_node or delta.base.edge_index.shape[1] != csr.num_edge:
+            raise ValueError("the delta was made for a graph of %d nodes, the CSR has %d" % (delta.num_nodes, csr.num_node))
+        if added_grad.dtype != torch.float32 or tuple(added_grad.shape) != (num_sample, 2 * delta.capacity):
+            raise ValueError("Expected added gradients of shape (%d, %d) fp32, got %s %s"
+                             % (num_sample, 2 * delta.capacity, tuple(added_grad.shape), added_grad.dtype))
+        if added_grad.device != dist_in.device or delta.device != dist_in.device:
+            raise RuntimeError("added gradients, delta and distances must be on one CUDA device")
+        added_grad = added_grad.contiguous()
     tails = tails.to(dist_in.device).contiguous()
     edge_grad, dist_in = edge_grad.contiguous(), dist_in.contiguous()
     dist = torch.empty((num_sample, csr.num_node, num_beam), dtype=torch.float32, device=dist_in.device)
@@ -191,13 +209,22 @@ def beam_search_layer_batch(csr, edge_grad, dist_in, tails, num_beam, tails_chec
                                             csr.hub_rows.data_ptr() if csr.num_hub else None, csr.num_hub, csr.num_node,
                                             csr.num_edge, num_sample, edge_grad.data_ptr(), dist_in.data_ptr(),
                                             tails.data_ptr(), num_beam, dist.data_ptr(), back.data_ptr(), stream))
+    if delta is not None:
+        edits = delta.explain_operand()
+        check(lib.ultra_beam_search_edit_rows_batch(csr.row_ptr.data_ptr(), csr.src.data_ptr(), csr.type.data_ptr(),
+                                                    csr.eid.data_ptr(), csr.num_node, csr.num_edge, num_sample,
+                                                    edge_grad.data_ptr(), ctypes.byref(edits), added_grad.data_ptr(),
+                                                    added_grad.stride(0), dist_in.data_ptr(), tails.data_ptr(), num_beam,
+                                                    dist.data_ptr(), back.data_ptr(), stream))
     return dist, back
 
 
-def beam_search_distance_batch(data, edge_grads, h_index, t_index, num_beam=10):
+def beam_search_distance_batch(data, edge_grads, h_index, t_index, num_beam=10, delta=None, added_grads=None):
     """beam_search_distance for S triples at once: edge_grads is a list of (S, num_edge) tensors, one per layer, h_index and
     t_index hold S node ids.  Returns per layer (S, num_node, num_beam) distances and (S, num_node, num_beam, 4) back
-    edges; slice s is beam_search_distance of triple s, the all -inf rule applied per sample on the device."""
+    edges; slice s is beam_search_distance of triple s, the all -inf rule applied per sample on the device.
+    delta / added_grads (one (S, 2 capacity) tensor per layer): the search on delta.materialize(data) from data's own cached
+    CSR (beam_search_layer_batch) -- no sort when the delta changes."""
     csr = beam_csr(data.edge_index, data.edge_type, data.num_nodes)
     dev = data.edge_index.device
     num_sample = edge_grads[0].shape[0] if len(edge_grads) else _index_vector(h_index, "h_index")[0].numel()
@@ -209,8 +236,11 @@ def beam_search_distance_batch(data, edge_grads, h_index, t_index, num_beam=10):
     dist[torch.arange(num_sample, device=dev), h, 0] = 0
     distances, back_edges = [], []
     with torch.no_grad():
-        for edge_grad in edge_grads:
-            dist, back = beam_search_layer_batch(csr, edge_grad, dist, t, num_beam, tails_checked=True)
+        if (delta is None) != (added_grads is None) or (delta is not None and len(added_grads) != len(edge_grads)):
+            raise ValueError("`delta` goes with one `added_grads` tensor per layer")
+        for i, edge_grad in enumerate(edge_grads):
+            dist, back = beam_search_layer_batch(csr, edge_grad, dist, t, num_beam, tails_checked=True, delta=delta,
+                                                 added_grad=None if delta is None else added_grads[i])
             # (beam_search_distance's all -inf rule, per sample and without leaving the device)
             back.mul_(torch.isfinite(dist).flatten(1).any(dim=1).view(-1, 1, 1, 1))
             distances.append(dist)

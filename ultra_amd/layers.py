@@ -96,11 +96,14 @@ _FLIPPED = {}
 def _flipped_edges(edge_index):
     """edge_index with its two rows swapped, one tensor per graph (so the plan cache, keyed on the tensor, hits)."""
     key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), str(edge_index.device))
-    hit = _FLIPPED.get(key)
+    hit = _FLIPPED.pop(key, None)
     if hit is None:
-        if len(_FLIPPED) >= 8:
-            _FLIPPED.clear()
-        hit = _FLIPPED[key] = (edge_index.flip(0).contiguous(), edge_index)
+        # (the eight graphs used last stay: a served base graph keeps its tensor -- and with it its cached plan -- while
+        # explanations of other graphs come and go)
+        while len(_FLIPPED) >= 8:
+            del _FLIPPED[next(iter(_FLIPPED))]
+        hit = (edge_index.flip(0).contiguous(), edge_index)
+    _FLIPPED[key] = hit
     return hit[0]
 
 
@@ -445,12 +448,16 @@ class GeneralizedRelationalConv(nn.Module):
         update = rspmm.plan_rspmm(plan, relation[0], input[0], edge_weight, sum="add", mul="mul", boundary=boundary[0])
         return self.update(update.unsqueeze(0), input, residual=residual)
 
-    def edge_grad_layer_batch(self, input, query, boundary, edge_index, edge_type, num_node, residual=False, relation=None):
+    def edge_grad_layer_batch(self, input, query, boundary, edge_index, edge_type, num_node, residual=False, relation=None,
+                              delta=None):
         """edge_grad_layer for S independent samples at once -- (S, N, d) operands, the same flipped-graph plan, CONSTANT unit
         edge weights: a batched backward would sum the weight gradient over the samples, which explains none of them.  The
         aggregate `update` is kept instead; with its gradient u the per-sample weight gradient of this layer is
         plan.edge_grad_samples(relation, input, u) (ultra_rspmm_edge_grad_samples).  Returns (hidden, (plan, relation, input,
-        update)); None where edge_grad_layer would return None for a sample (the caller then explains triple by triple)."""
+        update)); None where edge_grad_layer would return None for a sample (the caller then explains triple by triple).
+        `delta` (an edited rspmm.GraphDelta of this graph): the aggregate on (graph, delta) -- without the tombstoned edges,
+        with the added ones -- on the same plan of the base graph (rspmm.plan_delta_rspmm); the relation is then a constant, and
+        the added edges' gradients are delta.delta_edge_grad_samples(relation, input, u)."""
         if not (self.aggregate_func == "sum" and self.message_func == "distmult" and input.is_cuda
                 and input.dtype == torch.float32 and input.dim() == 3):
             return None
@@ -461,10 +468,18 @@ class GeneralizedRelationalConv(nn.Module):
         if isinstance(boundary, PointBoundary):
             boundary = boundary.dense()
         plan = rspmm.get_plan(_flipped_edges(edge_index), edge_type, num_node, relation.shape[1], exact_order=False)
-        update = rspmm.plan_rspmm(plan, relation, input, None, sum="add", mul="mul", boundary=boundary)
+        if delta is not None and delta.edited:
+            relation = relation.detach()
+            update = rspmm.plan_delta_rspmm(plan, delta, relation, input, boundary)
+        else:
+            update = rspmm.plan_rspmm(plan, relation, input, None, sum="add", mul="mul", boundary=boundary)
         if not update.requires_grad:      # (frozen parameters: nothing upstream asks for a gradient, this tensor still does)
             update.requires_grad_()
         return self.update(update, input, residual=residual), (plan, relation, input, update)
+
+    def explain_live_supported(self):
+        """Does edge_grad_layer_batch(delta=) serve this layer's configuration?  (sum / DistMult: the batched explanation route)"""
+        return self.aggregate_func == "sum" and self.message_func == "distmult"
 
     def point_boundary_trains(self):
         """The differentiable rspmm takes the boundary condition in closed form for the sum aggregate (rspmm._PlanRSPMM,

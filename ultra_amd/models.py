@@ -197,7 +197,7 @@ class BaseNBFNet(nn.Module):
         plan-based differentiable rspmm do (layers.edge_grad_layer), the others keep the unfused route.
         `edge_grad_batch` (with separate_grad; edge_grads_batch only): a list that receives every layer's (plan, relation, input,
         update) from layers.edge_grad_layer_batch -- constant weights, S samples; _BatchRouteUnsupported where a layer has no
-        such route."""
+        such route; with `delta` the aggregates run on (data, delta) (layers.edge_grad_layer_batch)."""
         size = (data.num_nodes, data.num_nodes)
         self._last_hidden_on_rows = False
         # edge_weight None = all ones (only materialised when its gradient is asked for); a 0/1 vector = edge dropout
@@ -234,7 +234,8 @@ class BaseNBFNet(nn.Module):
             if edge_grad_batch is not None:
                 residual = self.short_cut and layer.output_dim == layer_input.shape[-1]
                 out = layer.edge_grad_layer_batch(layer_input, query, boundary, data.edge_index, data.edge_type, data.num_nodes,
-                                                  residual=residual, relation=None if relations is None else relations[i])
+                                                  residual=residual, relation=None if relations is None else relations[i],
+                                                  delta=delta)
                 if out is None:
                     raise _BatchRouteUnsupported()
                 hiddens.append(out[0])
@@ -601,16 +602,25 @@ class EntityNBFNet(BaseNBFNet):
             scores.append(score)
         return [torch.stack([g[i] for g in grads]) for i in range(len(self.layers))], torch.cat(scores)
 
-    def edge_grads_batch(self, data, batch):
+    def edge_grads_batch(self, data, batch, delta=None):
         """edge_grads for S triples, batch (S, 3), with the (S, R, d) relation representations of their query relations
         installed (self.query, row s for triple s): ONE forward and one backward for all of them.  The samples are independent,
         so row s of the gradient of scores.sum() with respect to a layer's aggregate is triple s's; each layer's direct
         edge-weight gradient then comes per sample from ultra_rspmm_edge_grad_samples, and the reference's clone chain
         (models.py:150-152: layer i's weights are a clone of layer i - 1's) makes layer i's gradient the sum of the direct ones
         of layers i .. L-1.  Returns ([(S, num_edge)] * L, scores (S)).  Models whose layers are not sum / DistMult / fp32 on
-        the GPU are explained triple by triple through edge_grads: the same values either way."""
+        the GPU are explained triple by triple through edge_grads: the same values either way.
+        `delta` (rspmm.GraphDelta of `data`): the gradients on (data, delta), defined as those of this call on
+        delta.materialize(data) -- equal to them up to fp32 re-association, not bit for bit: the route was never order-pinned
+        (the re-associating plan and autograd), and an edited row adds its new edges' total with one more add.  The plan and the
+        edge list stay the base graph's.  Returns (base_grads [(S, num_edge)] * L over data's edge list -- the columns of
+        tombstoned edges are not part of the result --, added_grads [(S, 2 capacity)] * L over delta.edges() with the columns
+        from 2 num_facts on zero, scores (S)); the clone chain applies to both halves.  No per-triple fallback: RuntimeError
+        where a layer or the engine does not serve the batched route (predict.explain_live_supported)."""
         if batch.dim() != 2 or batch.shape[1] != 3:
             raise ValueError("Expected a batch of triples of shape (S, 3), got %s" % (tuple(batch.shape),))
+        if delta is not None:
+            return self._edge_grads_batch_delta(data, batch, delta)
         query = getattr(self, "query", None)
         if not torch.is_tensor(query) or query.dim() != 3 or query.shape[0] != batch.shape[0]:
             raise ValueError("edge_grads_batch: install the (S, num_relation, d) relation representations of the batch's query "
@@ -645,25 +655,78 @@ class EntityNBFNet(BaseNBFNet):
             self._last_hidden_on_rows = last_hidden_on_rows
         return edge_grads, scores.detach()
 
-    def visualize_batch(self, data, batch, chunk=16):
+    def _edge_grads_batch_delta(self, data, batch, delta):
+        """edge_grads_batch on (data, delta): the batched route alone."""
+        query = getattr(self, "query", None)
+        num_sample = batch.shape[0]
+        if not torch.is_tensor(query) or query.dim() != 3 or query.shape[0] != num_sample:
+            raise ValueError("edge_grads_batch: install the (S, num_relation, d) relation representations of the batch's query "
+                             "relations first (self.query), S = %d" % num_sample)
+        dev = data.edge_index.device
+        if not (batch.is_cuda and query.is_cuda and query.dtype == torch.float32) or num_sample == 0:
+            raise RuntimeError("edge_grads_batch(delta=) serves a non-empty batch of fp32 representations on the GPU")
+        unserved = RuntimeError("edge_grads_batch(delta=): a layer or the engine does not serve the batched explanation route "
+                                "on a graph delta (sum / DistMult, fp32)")
+        h_index, t_index, r_index = batch.unbind(-1)
+        last_hidden_on_rows = getattr(self, "_last_hidden_on_rows", False)
+        try:
+            with torch.enable_grad():
+                records = []
+                hiddens, _, query = self._bellmanford_hidden(data, h_index, r_index, separate_grad=True, edge_grad_batch=records,
+                                                             delta=delta)
+                sample = torch.arange(num_sample, device=batch.device)
+                picked = [h[sample, t_index] for h in (hiddens if self.concat_hidden else hiddens[-1:])]     # (S, d) each
+                scores = self.mlp(torch.cat(picked + [query], dim=-1)).squeeze(-1)
+                update_grads = autograd.grad(scores.sum(), [rec[3] for rec in records])
+            base_grads, added_grads = [None] * len(records), [None] * len(records)
+            with torch.no_grad():
+                for i in range(len(records) - 1, -1, -1):
+                    plan, relation, layer_input, _ = records[i]
+                    grad = update_grads[i].contiguous()
+                    direct = plan.edge_grad_samples(relation.detach(), layer_input.detach(), grad)
+                    if direct is None:
+                        raise unserved
+                    if delta.edited:
+                        added = delta.delta_edge_grad_samples(relation.detach(), layer_input.detach(), grad)
+                    else:
+                        added = torch.zeros((num_sample, 2 * delta.capacity), device=dev)
+                    last = i == len(records) - 1
+                    base_grads[i] = direct if last else direct + base_grads[i + 1]
+                    added_grads[i] = added if last else added + added_grads[i + 1]
+        except _BatchRouteUnsupported:
+            raise unserved
+        finally:
+            self._last_hidden_on_rows = last_hidden_on_rows
+        return base_grads, added_grads, scores.detach()
+
+    def visualize_batch(self, data, batch, chunk=16, delta=None):
         """visualize for S triples, batch (S, 3), with their (S, R, d) relation representations installed: a list of (paths,
         weights), entry s what visualize returns for triple s.  `chunk` triples share one forward, one backward and the
-        launches of one beam search (explain.beam_search_distance_batch); it bounds the memory of the 2 L (chunk, ...) tables."""
+        launches of one beam search (explain.beam_search_distance_batch); it bounds the memory of the 2 L (chunk, ...) tables.
+        `delta` (an edited rspmm.GraphDelta of `data`): the explanations on (data, delta), defined as those of this call on
+        delta.materialize(data) (edge_grads_batch(delta=), beam_search_distance_batch(delta=)); an unedited or absent delta is
+        the call without it."""
         if batch.dim() != 2 or batch.shape[1] != 3:
             raise ValueError("Expected a batch of triples of shape (S, 3), got %s" % (tuple(batch.shape),))
         if not isinstance(chunk, int) or chunk < 1:
             raise ValueError("chunk must be a positive int, got %r" % (chunk,))
         host = batch.cpu()      # (one read for the whole batch: the heads and tails are checked against the graph on the host)
         results = []
+        live = delta is not None and delta.edited
+        live_args = (lambda added: {"delta": delta, "added_grads": added}) if live else (lambda added: {})
         for lo in range(0, batch.shape[0], chunk):
             hi = min(lo + chunk, batch.shape[0])
             saved = self._installed_slice(lo, hi)
+            added_grads = None
             try:
-                edge_grads, _ = self.edge_grads_batch(data, batch[lo:hi])
+                if live:
+                    edge_grads, added_grads, _ = self.edge_grads_batch(data, batch[lo:hi], delta=delta)
+                else:
+                    edge_grads, _ = self.edge_grads_batch(data, batch[lo:hi])
             finally:
                 self._restore_installed(saved)
             distances, back_edges = explain.beam_search_distance_batch(data, edge_grads, host[lo:hi, 0], host[lo:hi, 1],
-                                                                       self.num_beam)
+                                                                       self.num_beam, **live_args(added_grads))
             results.extend(explain.topk_average_length_batch(distances, back_edges, host[lo:hi, 1], self.path_topk))
         return results
 
@@ -1023,12 +1086,17 @@ class Ultra(nn.Module):
             for layer, r in zip(ent.layers, saved[1]):
                 layer.relation = r
 
-    def visualize_batch(self, data, batch, chunk=16):
+    def visualize_batch(self, data, batch, chunk=16, delta=None):
         """visualize for S triples at once, batch (S, 3) -- they may differ in h, r and t: a list of (paths, weights), entry s
         what visualize(data, batch[s:s + 1]) returns.  Every chunk of `chunk` triples takes its query relations'
         representations from the relation model (or the relation cache, as visualize does), one entity-model forward and
         backward and the launches of one beam search (EntityNBFNet.visualize_batch).  The model is left as it was, like
-        visualize."""
+        visualize.
+        `delta` (an edited rspmm.GraphDelta of `data`): the explanations on (data, delta), defined as those of this
+        call on delta.materialize(data).  The relation representations come from delta.live_view(data).relation_graph, as
+        forward(delta=) takes them; the entity model keeps data's plan and CSR.  Edge gradients equal the materialised route's
+        up to fp32 re-association (EntityNBFNet.edge_grads_batch); given the gradients the beam search is exact.  An unedited
+        or absent delta is exactly the call without it."""
         if batch.dim() != 2 or batch.shape[1] != 3:
             raise ValueError("Expected a batch of triples of shape (S, 3), got %s" % (tuple(batch.shape),))
         if not isinstance(chunk, int) or chunk < 1:
@@ -1038,17 +1106,19 @@ class Ultra(nn.Module):
             raise TypeError("%s cannot explain a batch; EntityNBFNet can" % type(ent).__name__)
         saved = (getattr(ent, "query", None), [getattr(l, "relation", None) for l in ent.layers])
         results = []
+        live = delta is not None and delta.edited
+        view = delta.live_view(data) if live else data
         try:
             for lo in range(0, batch.shape[0], chunk):
                 part = batch[lo:lo + chunk]
                 with torch.no_grad():
-                    rel = self._cached_relations(data, part[:, 2])
+                    rel = self._cached_relations(view, part[:, 2])
                     if rel is None:
-                        rel = self.relation_model(data.relation_graph, query=part[:, 2])
+                        rel = self.relation_model(view.relation_graph, query=part[:, 2])
                 ent.query = rel
                 for layer in ent.layers:
                     layer.relation = rel
-                results.extend(ent.visualize_batch(data, part, chunk=chunk))
+                results.extend(ent.visualize_batch(data, part, chunk=chunk, **({"delta": delta} if live else {})))
         finally:
             ent.query = saved[0]
             for layer, r in zip(ent.layers, saved[1]):

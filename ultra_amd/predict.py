@@ -351,6 +351,34 @@ def delta_samples_supported(model):
             and all(getattr(layer, "delta_samples_supported", lambda: False)() for layer in layers))
 
 
+def explain_live_blocker(model):
+    """None where `model` explains its answers on a graph that holds edits WITHOUT folding them in first
+    (visualize_batch(delta=): every entity layer on the batched explanation route, sum / DistMult, fp32); else
+    the name of what cannot."""
+    try:
+        params = inspect.signature(getattr(model, "visualize_batch", None)).parameters
+    except (TypeError, ValueError):
+        return "%s (no visualize_batch)" % type(model).__name__
+    if "delta" not in params:
+        return "%s.visualize_batch (takes no delta)" % type(model).__name__
+    ent = _entity_model(model)
+    layers = getattr(ent, "layers", None)
+    if layers is None or not hasattr(ent, "edge_grads_batch"):
+        return "%s (no batched explanation route)" % type(ent).__name__
+    for i, layer in enumerate(layers):
+        if not getattr(layer, "explain_live_supported", lambda: False)():
+            return "entity layer %d (%s aggregate, %s messages: the route serves sum / distmult)" % (
+                i, getattr(layer, "aggregate_func", "?"), getattr(layer, "message_func", "?"))
+        if any(p.dtype != torch.float32 for p in layer.parameters()):
+            return "entity layer %d (%s parameters: the route serves fp32)" % (i, next(layer.parameters()).dtype)
+    return None
+
+
+def explain_live_supported(model):
+    """Does `model` serve explain_tails / explain_heads(compact=False)?  (explain_live_blocker names what does not)"""
+    return explain_live_blocker(model) is None
+
+
 def live_relation_graph_blocker(model):
     """None where every layer of `model`'s relation model can run on a relation graph that is kept current in place (its
     byte adjacency alone, DESIGN.md 25: sum aggregate, DistMult messages, 64-d, fp32); else the name of what cannot."""
@@ -675,25 +703,44 @@ class Predictor(object):
         """tails_above for the heads of (?, r[i], t[i])."""
         return self._run_above(t, r, min_score, "head")
 
-    def explain_tails(self, h, r, chunk=16):
+    def explain_tails(self, h, r, chunk=16, compact=True):
         """tails(h, r) plus why: (ids, scores, count, explanations).  explanations[i][j], j < count[i], is the (paths, weights)
         of model.visualize_batch for the triple (h[i], ids[i, j], r[i]) -- answer j of query i -- so every path runs from
         h[i] to the answer.  The answers come from the same captured step as tails; the explanations run `chunk` triples a
-        forward / backward / beam search."""
-        return self._explain(h, r, "tail", chunk)
+        forward / backward / beam search.
+        compact=True: a delta that holds edits is folded into the graph first (compact()), and the explanations walk the
+        graph's own edge list.  compact=False: the delta stays a delta -- the answers come from the live step as
+        tails' do, the explanations are computed on (base graph, delta) and are DEFINED as those of the same call on
+        materialized(): no host plan, no relation-graph rebuild, no new capture.  The explanation path was never order-pinned
+        (the re-associating plan and autograd), so the edge gradients of this route equal those of the
+        materialised route up to fp32 re-association, not bit for bit; given the gradients the beam search is exact.  Paths
+        whose weights differ by less than that may come in another order.  ValueError on a model the route does not serve
+        (explain_live_supported: sum / DistMult / fp32 entity layers); an unedited delta is compact=True."""
+        return self._explain(h, r, "tail", chunk, compact)
 
-    def explain_heads(self, t, r, chunk=16):
+    def explain_heads(self, t, r, chunk=16, compact=True):
         """heads(t, r) plus why.  The model scores (?, r, t) as the TAIL query (t, r + num_direct_rel, ?) -- the inverse
         relation, as in evaluation -- so the triple explained for answer a is (t[i], a, r[i] + num_direct_rel), the one whose
-        score was served: every path runs from t[i] to the answer over the graph's edges, inverse ones included."""
-        return self._explain(t, r, "head", chunk)
+        score was served: every path runs from t[i] to the answer over the graph's edges, inverse ones included.  `compact` as
+        in explain_tails."""
+        return self._explain(t, r, "head", chunk, compact)
 
-    def _explain(self, anchor, relation, mode, chunk):
+    def _explain(self, anchor, relation, mode, chunk, compact=True):
         if not hasattr(self.model, "visualize_batch"):
             raise TypeError("%s cannot explain its answers: models.Ultra and models.EntityNBFNet (visualize_batch) can"
                             % type(self.model).__name__)
+        if not isinstance(compact, bool):
+            raise ValueError("compact must be True or False, got %r" % (compact,))
+        if not compact:
+            blocker = explain_live_blocker(self.model)
+            if blocker is not None:
+                raise ValueError("compact=False: explanations on a graph delta are not served by %s" % blocker)
+        live = {}
         if self.delta is not None and self.delta.edited:
-            self.compact()      # (explanations walk the graph's own edge list: the edits become part of it first)
+            if compact:
+                self.compact()      # (explanations walk the graph's own edge list: the edits become part of it first)
+            else:
+                live = {"delta": self.delta}
         ids, scores, count = self._run(anchor, relation, mode)
         dev = ids.device
         anchor = torch.as_tensor(anchor, dtype=torch.long, device=dev).flatten()
@@ -704,7 +751,7 @@ class Predictor(object):
         rows = torch.tensor([i for i, c in enumerate(counts) for _ in range(c)], dtype=torch.long, device=dev)
         cols = torch.tensor([j for c in counts for j in range(c)], dtype=torch.long, device=dev)
         triples = torch.stack([anchor[rows], ids[rows, cols], relation[rows]], dim=-1)
-        flat = self.model.visualize_batch(self.data, triples, chunk=chunk) if len(rows) else []
+        flat = self.model.visualize_batch(self.data, triples, chunk=chunk, **live) if len(rows) else []
         slots, live = self.num_relation_slots, self.num_direct_relations
         if slots != live:       # (the caller sees the compact numbering of materialized(): inverse type r + live)
             flat = [(type(paths)([(h, t, r - (slots - live) if r >= slots else r) for h, t, r in path] for path in paths), weights)

@@ -741,6 +741,8 @@ def dense_layer0_adjacency(adjacency, num_node, relation, src_rows, src_values, 
 
 
 TraversalLayout = namedtuple("TraversalLayout", "rows count add_ptr add_src add_type dead_ptr dead_src dead_type")
+ExplainLayout = namedtuple("ExplainLayout", "rows count add_ptr add_src add_dst add_type add_j dead_ptr dead_src dead_type "
+                                            "src_rows src_count src_ptr src_dst src_type src_j")
 
 
 class GraphDelta(object):
@@ -838,6 +840,8 @@ class GraphDelta(object):
         self.relation_graph = getattr(data, "relation_graph", None)
         self._materialized = None
         self.traversal = None       # the layout in the symbolic traversal's direction: laid out when first asked for
+        self.explain = None         # the layout keyed by destination, for explanations: laid out when first asked for
+        self._keep = None           # (version, keep vector)
 
     def __len__(self):
         return self.num_facts
@@ -938,6 +942,8 @@ class GraphDelta(object):
         self._prepare()
         if self.traversal is not None:
             self._prepare_traversal()
+        if self.explain is not None:
+            self._prepare_explain()
         if not (added and self._add_to_relation_graph(added)) and not (not added and self._remark_live_relation_graph()):
             self._rebuild_relation_graph()
 
@@ -993,6 +999,93 @@ class GraphDelta(object):
                                         lay.add_src.data_ptr(), lay.add_type.data_ptr(), lay.dead_ptr.data_ptr(),
                                         lay.dead_src.data_ptr(), lay.dead_type.data_ptr(), lay.rows.numel(),
                                         lay.add_src.numel(), lay.dead_src.numel())
+
+    def _prepare_explain(self):
+        """The edits keyed by the DESTINATION they point into, for the explanation route, whose messages go from
+        edge_index[0] into edge_index[1] -- the flipped plan, the opposite of col / type / rows / ptr.  Buffers allocated at the
+        first call and refreshed in place by every later add() / remove(); j is an added edge's position in edges().
+          rows       int32 (2 capacity)      the distinct destinations an added or a tombstoned edge points into, ascending
+          count      int32 (1)               their number -- the SAME tensor object for the delta's life
+          add_ptr    int32 (2 capacity + 1)  the added edges' ranges per touched row
+          add_src / add_dst / add_type / add_j   int32 (2 capacity)   the added edges, sorted by (destination, j)
+          dead_ptr   int32 (2 capacity + 1)  the dead keys' ranges per touched row
+          dead_src / dead_type  int32 (2 capacity)   the distinct dead (source, type) keys, sorted by (destination, source, type)
+          src_rows / src_count / src_ptr / src_dst / src_type / src_j   the transpose of the added edges: the distinct sources
+                                             ascending, their number, and per source its edges (destination, type, j) by j"""
+        dev, cap = self.device, 2 * self.capacity
+        if self.explain is None:
+            buf = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
+            self.explain = ExplainLayout(rows=buf(cap), count=buf(1), add_ptr=buf(cap + 1), add_src=buf(cap), add_dst=buf(cap),
+                                         add_type=buf(cap), add_j=buf(cap), dead_ptr=buf(cap + 1), dead_src=buf(cap),
+                                         dead_type=buf(cap), src_rows=buf(cap), src_count=buf(1), src_ptr=buf(cap + 1),
+                                         src_dst=buf(cap), src_type=buf(cap), src_j=buf(cap))
+        lay = self.explain
+        edge_index, edge_type = self.edges()
+        src, dst = edge_index
+        num_edge = len(src)
+        ids = torch.arange(num_edge, device=dev)
+        keys = torch.tensor(self.dead_keys, dtype=torch.long, device=dev)
+        key_type = keys % self.num_relations
+        key_dst = (keys // self.num_relations) % self.num_nodes
+        key_src = keys // (self.num_relations * self.num_nodes)
+        order = torch.argsort((key_dst * self.num_nodes + key_src) * self.num_relations + key_type)
+        key_src, key_dst, key_type = key_src[order], key_dst[order], key_type[order]
+        by_dst = torch.argsort(dst * max(num_edge, 1) + ids)
+        by_src = torch.argsort(src * max(num_edge, 1) + ids)
+        touched = torch.unique(torch.cat([dst, key_dst]))      # (ascending)
+        sources = torch.unique(src)
+        for buffer, values in ((lay.add_src, src[by_dst]), (lay.add_dst, dst[by_dst]), (lay.add_type, edge_type[by_dst]),
+                               (lay.add_j, by_dst), (lay.src_dst, dst[by_src]), (lay.src_type, edge_type[by_src]),
+                               (lay.src_j, by_src), (lay.dead_src, key_src), (lay.dead_type, key_type), (lay.rows, touched),
+                               (lay.src_rows, sources)):
+            buffer[:len(values)] = values.to(torch.int32)
+        for ptr, rows, of in ((lay.add_ptr, touched, dst), (lay.dead_ptr, touched, key_dst), (lay.src_ptr, sources, src)):
+            counts = torch.bincount(torch.searchsorted(rows, of), minlength=len(rows))
+            ptr[1:len(rows) + 1] = counts.cumsum(0).to(torch.int32)
+        lay.count.fill_(len(touched))
+        lay.src_count.fill_(len(sources))
+
+    def explain_operand(self):
+        """The edits keyed by destination as the engine takes them (ultra_explain_edits); valid while this object lives.  The
+        first call lays the buffers out; from then on add() / remove() keep them current."""
+        if self.explain is None:
+            self._prepare_explain()
+        lay = self.explain
+        return _lib.UltraExplainEdits(*([getattr(lay, name).data_ptr() for name in ExplainLayout._fields if name != "src_j"]
+                                        + [lay.rows.numel(), lay.add_src.numel(), lay.dead_src.numel()]))
+
+    def keep_vector(self):
+        """(num_edge,) fp32 over the BASE edge list: 0 where a tombstone key matches the edge, 1 elsewhere -- the rule of
+        surviving().  Built with torch on the delta's device, once per version."""
+        hit = self._keep
+        if hit is not None and hit[0] == self.version:
+            return hit[1]
+        edge_index, edge_type = self.base.edge_index.to(self.device), self.base.edge_type.to(self.device)
+        if not self.dead_keys:
+            keep = torch.ones(edge_index.shape[1], dtype=torch.float32, device=self.device)
+        else:
+            keys = torch.tensor(self.dead_keys, dtype=torch.long, device=self.device)
+            codes = self._edge_codes(edge_index[0], edge_index[1], edge_type)
+            at = torch.searchsorted(keys, codes).clamp_(max=len(keys) - 1)
+            keep = (keys[at] != codes).to(torch.float32)
+        self._keep = (self.version, keep)
+        return keep
+
+    def delta_edge_grad_samples(self, relation, input, output_grad):
+        """The per-sample edge-weight gradients of the ADDED edges (ultra_rspmm_delta_edge_grad_samples): (S, 2 capacity) fp32,
+        column j = sum_d output_grad[s, dst_j, d] * relation[s, type_j, d] * input[s, src_j, d] for the edge at position j of
+        edges(), the columns from 2 num_facts on zero.  (S, N, d) fp32 operands on the GPU."""
+        _require_gpu(relation, input, output_grad)
+        if not (relation.dtype == input.dtype == output_grad.dtype == torch.float32) or input.dim() != 3:
+            raise RuntimeError("delta_edge_grad_samples takes (S, N, d) fp32 operands")
+        operand = self.explain_operand()
+        relation, mrel = as_mat(relation)
+        input, mx = as_mat(input)
+        output_grad, mog = as_mat(output_grad)
+        wgrad = torch.empty((input.shape[0], 2 * self.capacity), dtype=torch.float32, device=input.device)
+        check(lib.ultra_rspmm_delta_edge_grad_samples(ctypes.byref(operand), ctypes.byref(mrel), ctypes.byref(mx),
+                                                      ctypes.byref(mog), wgrad.data_ptr(), wgrad.stride(0), stream_of(input)))
+        return wgrad
 
     def _prepare(self):
         """Sort the delta's edges, decode the tombstone keys, and lay out the union of their rows with both ptr arrays, into the
@@ -1308,6 +1401,57 @@ class _PlanRSPMM(autograd.Function):
             values_grad = (output_grad.gather(1, rows.view(-1, 1, 1).expand(-1, 1, output_grad.shape[-1])).squeeze(1) if output_grad.dim() == 3
                            else output_grad[rows[0]].unsqueeze(0))
         return None, None, None, weight_grad, relation_grad, input_grad, boundary_grad, None, None, values_grad   # rspmm.py:35
+
+
+class _PlanDeltaRSPMM(autograd.Function):
+    """The sum / DistMult aggregate of the explanation direction on (base graph, delta): `plan` is the flipped
+    re-associating plan of the BASE graph, `delta` a GraphDelta of it.  fp32, (S, N, d) operands; the relation is a constant.
+    Both engine calls of each pass write in place."""
+
+    @staticmethod
+    def forward(ctx, plan, delta, relation, input, boundary=None):
+        if relation.requires_grad:
+            raise RuntimeError("the differentiable aggregate on a graph delta takes the relation as a constant: detach it")
+        if input.dim() != 3 or relation.dim() != 3 or input.dtype != torch.float32 or relation.dtype != torch.float32:
+            raise RuntimeError("the differentiable aggregate on a graph delta serves (S, N, d) fp32 operands")
+        if (delta.num_nodes, delta.num_relations) != (plan.num_node, plan.num_relation) or plan.num_in != plan.num_node \
+                or delta.base.edge_index.shape[1] != plan.num_edge:
+            raise RuntimeError("the delta was made for a graph of %d nodes and %d relations, the plan has %d and %d"
+                               % (delta.num_nodes, delta.num_relations, plan.num_node, plan.num_relation))
+        # a tombstoned edge is absent, exactly: its message is multiplied by 0 (no tombstone held: unit weights, no vector)
+        keep = delta.keep_vector() if delta.num_removed else None
+        operand = delta.explain_operand()
+        output = plan.forward(relation, input, edge_weight=keep, boundary=boundary, sum="add", mul="mul", keep=keep is not None)
+        rel, mrel = as_mat(relation)
+        x, mx = as_mat(input)
+        out, mout = as_mat(output)
+        check(lib.ultra_rspmm_delta_edges_forward(ctypes.byref(operand), ctypes.byref(mrel), ctypes.byref(mx), ctypes.byref(mout),
+                                                  stream_of(input)))
+        ctx.plan, ctx.delta, ctx.version = plan, delta, delta.version
+        ctx.save_for_backward(keep, relation, input, output)
+        return output
+
+    @staticmethod
+    def backward(ctx, output_grad):
+        keep, relation, input, output = ctx.saved_tensors
+        if ctx.delta.version != ctx.version:
+            raise RuntimeError("the graph delta changed between the forward and the backward of an explanation")
+        output_grad = output_grad.contiguous()
+        _, _, input_grad = ctx.plan.backward(relation, input, output, output_grad, edge_weight=keep, sum="add", mul="mul",
+                                             keep=keep is not None)
+        operand = ctx.delta.explain_operand()
+        rel, mrel = as_mat(relation)
+        og, mog = as_mat(output_grad)
+        xg, mxg = as_mat(input_grad)
+        check(lib.ultra_rspmm_delta_edges_backward_input(ctypes.byref(operand), ctypes.byref(mrel), ctypes.byref(mog),
+                                                         ctypes.byref(mxg), stream_of(input)))
+        return None, None, None, input_grad, (output_grad if ctx.needs_input_grad[4] else None)
+
+
+def plan_delta_rspmm(plan, delta, relation, input, boundary=None):
+    """sum / DistMult aggregate on (the base graph of `plan`, `delta`), differentiable in `input` and `boundary`
+    (_PlanDeltaRSPMM)."""
+    return _PlanDeltaRSPMM.apply(plan, delta, relation, input, boundary)
 
 
 _OUT_CSR_CACHE = OrderedDict()
