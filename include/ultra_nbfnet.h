@@ -224,6 +224,13 @@ int32_t ultra_filtered_rank(const void *score, const int64_t *pos_index, const i
 int32_t ultra_filtered_rank_live(const void *score, const int64_t *pos_index, const int64_t *known_ptr,
                                  const int64_t *known_index, int64_t batch, int64_t n_cand, int64_t *rank_out,
                                  int64_t *num_negative_out, const int64_t *n_live, void *stream);
+/* ... over the ids that are ALIVE: the rules of ultra_filtered_topk_alive.  A retired t is skipped,
+ * num_negative_out[q] = live - retired - |known(q)|; pos_index and the known ids are alive.  n_live may be NULL (every slot is
+ * below the bound); NULL retired_bits or n_retired: ULTRA_ERR_INVALID.  rank_out is zeroed by a kernel, never a memset node. */
+int32_t ultra_filtered_rank_alive(const void *score, const int64_t *pos_index, const int64_t *known_ptr,
+                                  const int64_t *known_index, int64_t batch, int64_t n_cand, int64_t *rank_out,
+                                  int64_t *num_negative_out, const int64_t *n_live, const uint32_t *retired_bits,
+                                  const int64_t *n_retired, void *stream);
 
 /*
  * Strict negative sampling (/root/reference/ultra/tasks.py:42-76, strict = True) for n_query positives, n_draw negatives each,
@@ -490,6 +497,22 @@ int32_t ultra_filtered_topk(const void *score, const int64_t *known_ptr, const i
 int32_t ultra_filtered_topk_live(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
                                  int64_t n_cand, int32_t k, int64_t *ids_out, void *scores_out, int64_t *count_out,
                                  void *workspace, int64_t workspace_bytes, const int64_t *n_live, void *stream);
+/* ---- retired entities: selection over the ids that are ALIVE, not just below a bound ----
+ * The _alive entries take the arguments of their _live twins plus retired_bits, a DEVICE bitmap of ceil(n_cand / 32) uint32
+ * words (id v is bit v & 31 of word v >> 5), and n_retired, a DEVICE pointer to one int64: the number of set bits below the
+ * bound.  n_live may be NULL here: every slot is below the bound.  An id whose bit is set is ABSENT: never a key, a member or
+ * a competitor -- whatever its score slot holds (a NaN, +inf) reaches no output.  Bits at ids >= *n_live are ignored.
+ * *n_retired is clamped on the device to [0, live] and used only in the counts -- count_out[b] = min(k, live - retired -
+ * |known(b)|), num_negative_out[q] = live - retired - |known(q)|; size_out never counts a retired id -- never as an index.  The
+ * known ids and the positives of the rank must be alive.  The launch shapes, the workspace and the number of launches depend on
+ * (batch, n_cand) alone and both operands are read by the kernels, so a call recorded into a hipGraph serves every later
+ * retirement.  No global atomics beyond the rank's own, no memset, no allocation, no host wait.  The same kernels serve the
+ * _live twins and the parents (retired_bits == NULL inside), whose results keep their bits.  Errors: those of the parent, under
+ * the entry's name; NULL retired_bits or n_retired: ULTRA_ERR_INVALID, nothing is launched. */
+int32_t ultra_filtered_topk_alive(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
+                                  int64_t n_cand, int32_t k, int64_t *ids_out, void *scores_out, int64_t *count_out,
+                                  void *workspace, int64_t workspace_bytes, const int64_t *n_live, const uint32_t *retired_bits,
+                                  const int64_t *n_retired, void *stream);
 
 /* ---- compiled execution of complex logical queries ----
  * ultra_query_segment: what a batch of UltraQuery stack machines does between two projection calls, as one launch.  The
@@ -567,6 +590,11 @@ int32_t ultra_filtered_above_live(const void *score, const int64_t *known_ptr, c
                                   int64_t n_cand, float threshold, int64_t *ptr_out, int64_t *ids_out, void *scores_out,
                                   int64_t capacity, int64_t *size_out, void *workspace, int64_t workspace_bytes,
                                   const int64_t *n_live, void *stream);
+/* ... over the ids that are alive (the rules stated at ultra_filtered_topk_alive). */
+int32_t ultra_filtered_above_alive(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
+                                   int64_t n_cand, float threshold, int64_t *ptr_out, int64_t *ids_out, void *scores_out,
+                                   int64_t capacity, int64_t *size_out, void *workspace, int64_t workspace_bytes,
+                                   const int64_t *n_live, const uint32_t *retired_bits, const int64_t *n_retired, void *stream);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,7 @@
 
     python tools/predict.py --data-root DIR [--ckpt FILE] --head NAME --relation NAME [--inverse] [-k 10] [--unfiltered] [--explain [--no-compact]]
                             [--add-fact H R T]... [--remove-fact H R T]... [--entity-capacity M] [--add-entity NAME]...
-                            [--relation-capacity K] [--add-relation NAME]... [--live-relation-graph]
+                            [--relation-capacity K] [--add-relation NAME]... [--live-relation-graph] [--remove-entity NAME]...
     python tools/predict.py --data-root DIR [--ckpt FILE] --verify (--head NAME --relation NAME --tail NAME | --triples FILE) [--inverse]
 
 DIR holds train.txt / valid.txt / test.txt (`head relation tail` per line) and optionally entities.dict / relations.dict
@@ -21,6 +21,11 @@ served and the known answers, so its tail can be predicted again.  Both kinds ar
 reserved by --entity-capacity M (default: as many as there are --add-entity options), costs no plan and no capture, and from then
 on NAME can be used by the --add-fact / --remove-fact options that FOLLOW it on the command line and by --head; answers print it
 by its name.  It is applied in command-line order with the fact options.
+
+--remove-entity NAME (repeatable) takes an entity out of the graph served before the query is answered
+(Predictor.remove_entities): every fact that names it is retracted and the entity is retired -- never an answer,
+never counted among the candidates.  It is applied in command-line order with the other edit options, and NAME no longer
+resolves in the options that FOLLOW it on the command line, nor in --head / --tail / --triples.
 
 --add-relation NAME (repeatable) introduces a relation type the dataset does not know (Predictor.add_relations): it takes one of
 the slots reserved by --relation-capacity K (default: as many as there are --add-relation options) and costs no plan, no relation
@@ -76,6 +81,8 @@ def main(argv=None):
             namespace.edits = getattr(namespace, "edits", None) or []
             if option_string == "--add-entity":
                 namespace.edits.append((None, values))
+            elif option_string == "--remove-entity":
+                namespace.edits.append(("retire", values))
             else:
                 namespace.edits.append((option_string == "--add-fact", tuple(values)))
 
@@ -85,6 +92,8 @@ def main(argv=None):
                     help="retract the fact (H, R, T) before the query; repeatable, applied in order with --add-fact")
     ap.add_argument("--add-entity", action=Edit, metavar="NAME",
                     help="introduce a new entity before the query; repeatable, applied in order with the fact options")
+    ap.add_argument("--remove-entity", action=Edit, metavar="NAME",
+                    help="retire an entity and retract its facts before the query; repeatable, applied in order with the other edits")
     ap.add_argument("--entity-capacity", type=int, default=None, metavar="M",
                     help="rows reserved for new entities (default: the number of --add-entity options)")
     ap.add_argument("--add-relation", action="append", default=[], metavar="NAME",
@@ -129,6 +138,10 @@ def main(argv=None):
             if value in known:
                 sys.exit("--add-entity %r: the entity exists" % value)
             known.add(value)
+        elif kind == "retire":
+            if value not in known:
+                sys.exit("--remove-entity %r: unknown entity (or one retired earlier on the command line)" % value)
+            known.discard(value)
         else:
             checks.append((value, set(known)))
     for triple in (facts if facts is not None else [(args.head, args.relation, args.head)]):
@@ -171,6 +184,13 @@ def main(argv=None):
             assert new_id == len(ent)
             ent.append(args.edits[at][1])
             print("entity %r added as id %d (%d of %d rows in use)" % (ent[-1], new_id, predictor.num_entities, predictor.num_slots))
+            at += 1
+            continue
+        if args.edits[at][0] == "retire":
+            name = args.edits[at][1]
+            (took,) = predictor.remove_entities(ent.index(name)).tolist()
+            print("entity %r retired: %d fact(s) retracted (%d of %d entities retired)"
+                  % (name, took, predictor.num_retired, predictor.num_entities))
             at += 1
             continue
         end = at

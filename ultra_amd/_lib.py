@@ -182,6 +182,11 @@ def _load():
     lib.ultra_filtered_rank_live.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp, vp, vp]
     lib.ultra_filtered_topk_live.argtypes = [vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp, vp]
     lib.ultra_filtered_above_live.argtypes = [vp, vp, vp, i64, i64, ctypes.c_float, vp, vp, vp, i64, vp, vp, i64, vp, vp]
+    # the twins over the ids that are alive: the _live arguments plus the retired bitmap and the device pointer to
+    # the int64 retired count, before the stream
+    lib.ultra_filtered_rank_alive.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp]
+    lib.ultra_filtered_topk_alive.argtypes = [vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp]
+    lib.ultra_filtered_above_alive.argtypes = [vp, vp, vp, i64, i64, ctypes.c_float, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp]
     lib.ultra_filtered_above_workspace.argtypes = [i64, i64]
     lib.ultra_filtered_above_workspace.restype = i64
     lib.ultra_filtered_above.argtypes = [vp, vp, vp, i64, i64, ctypes.c_float, vp, vp, vp, i64, vp, vp, i64, vp]

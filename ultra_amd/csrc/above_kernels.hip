@@ -28,6 +28,11 @@
 // A dead id is never loaded (a NaN or +inf in its slot is no member and reaches no key), a chunk wholly beyond the live count
 // writes its two zero counts and an empty run, so the scan and every merge level see what they see for an empty chunk.
 // n_live == NULL (ultra_filtered_above) means n_cand: the same kernels, the same bits.
+//
+// RETIRED IDS (ultra_filtered_above_alive): a device bitmap names ids below the live count that are absent.  Both
+// passes over a chunk zero a retired candidate's key next to the predicate -- before the members are counted, so size_out never
+// counts it, and before the knock-out and the sort.  The retired count is not needed here.  retired_bits == NULL: the _live twin
+// and the parent, the same bits.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -66,18 +71,27 @@ __device__ __forceinline__ int live_in_chunk(const int64_t *__restrict__ n_live,
 }
 
 // The chunk [lo, lo + n) of `row`: bits[j] = ordered_score of candidate tid + j * ABOVE_THREADS when it is a member that
-// known(b) does not list, else 0.  Returns this thread's number of members (before the filter).  ord: ABOVE_CHUNK words of LDS,
-// touched only when the chunk's slice of known(b) is non-empty.  Every thread of the workgroup calls it.
+// known(b) does not list, else 0.  Returns this thread's number of members (before the filter).  A candidate whose bit is set
+// in retired_bits (NULL: none) is no member.  ord: ABOVE_CHUNK words of LDS, touched only when the chunk's slice of known(b) is
+// non-empty.  Every thread of the workgroup calls it.
 __device__ __forceinline__ int chunk_survivors(const float *__restrict__ row, long long lo, int n, float threshold,
                                                const int64_t *__restrict__ known_ptr, const int64_t *__restrict__ known_index,
-                                               long long b, unsigned *ord, unsigned (&bits)[ABOVE_SLOTS]) {
+                                               long long b, unsigned *ord, unsigned (&bits)[ABOVE_SLOTS],
+                                               const uint32_t *__restrict__ retired_bits) {
     const int tid = threadIdx.x;
+    unsigned mask[ABOVE_SLOTS];
+    retired_slots<ABOVE_SLOTS, ABOVE_THREADS>(retired_bits, lo, n, mask);      // (in flight with the scores)
+    float v[ABOVE_SLOTS];
+#pragma unroll
+    for (int j = 0; j < ABOVE_SLOTS; ++j) {
+        const int i = tid + j * ABOVE_THREADS;
+        v[j] = i < n ? row[lo + i] : 0.f;
+    }
     int members = 0;
 #pragma unroll
     for (int j = 0; j < ABOVE_SLOTS; ++j) {
         const int i = tid + j * ABOVE_THREADS;
-        const float v = i < n ? row[lo + i] : 0.f;
-        bits[j] = (i < n && v > threshold) ? ordered_score(__float_as_uint(v)) : 0u;
+        bits[j] = (i < n && v[j] > threshold && !slot_retired(mask[j])) ? ordered_score(__float_as_uint(v[j])) : 0u;
         members += bits[j] != 0u ? 1 : 0;
     }
     if (!known_ptr) return members;
@@ -117,7 +131,8 @@ __device__ __forceinline__ int wave_sum(int v) {
 __global__ void __launch_bounds__(ABOVE_THREADS) above_count_kernel(const float *__restrict__ score, const int64_t *__restrict__ known_ptr,
                                                                     const int64_t *__restrict__ known_index, long long n_cand,
                                                                     long long n_chunk, float threshold, int *__restrict__ counts,
-                                                                    const int64_t *__restrict__ n_live) {
+                                                                    const int64_t *__restrict__ n_live,
+                                                                    const uint32_t *__restrict__ retired_bits) {
     __shared__ unsigned ord[ABOVE_CHUNK];
     __shared__ int part[2][ABOVE_THREADS / 64];
     const int tid = threadIdx.x;
@@ -125,7 +140,7 @@ __global__ void __launch_bounds__(ABOVE_THREADS) above_count_kernel(const float 
     const long long lo = c * ABOVE_CHUNK;
     const int n = live_in_chunk(n_live, n_cand, lo);
     unsigned bits[ABOVE_SLOTS];
-    int members = chunk_survivors(score + b * n_cand, lo, n, threshold, known_ptr, known_index, b, ord, bits);
+    int members = chunk_survivors(score + b * n_cand, lo, n, threshold, known_ptr, known_index, b, ord, bits, retired_bits);
     int kept = 0;
 #pragma unroll
     for (int j = 0; j < ABOVE_SLOTS; ++j) kept += bits[j] != 0u ? 1 : 0;
@@ -197,7 +212,8 @@ __global__ void __launch_bounds__(ABOVE_THREADS) above_fill_kernel(const float *
                                                                    long long n_chunk, float threshold, const long long *__restrict__ offs,
                                                                    u64 *__restrict__ keys_out, int64_t *__restrict__ ids_out,
                                                                    unsigned *__restrict__ scores_out,
-                                                                   const int64_t *__restrict__ n_live) {
+                                                                   const int64_t *__restrict__ n_live,
+                                                                   const uint32_t *__restrict__ retired_bits) {
     __shared__ unsigned ord[ABOVE_CHUNK];
     __shared__ u64 keys[ABOVE_CHUNK];
     __shared__ unsigned cursor;
@@ -208,7 +224,7 @@ __global__ void __launch_bounds__(ABOVE_THREADS) above_fill_kernel(const float *
     const int n = live_in_chunk(n_live, n_cand, lo);
     if (tid == 0) cursor = 0;
     unsigned bits[ABOVE_SLOTS];
-    chunk_survivors(row, lo, n, threshold, known_ptr, known_index, b, ord, bits);
+    chunk_survivors(row, lo, n, threshold, known_ptr, known_index, b, ord, bits, retired_bits);
     int stay = 0;
 #pragma unroll
     for (int j = 0; j < ABOVE_SLOTS; ++j) stay += bits[j] != 0u ? 1 : 0;
@@ -326,11 +342,12 @@ extern "C" int64_t ultra_filtered_above_workspace(int64_t batch, int64_t n_cand)
     return (slots + 1) * 8 + 2 * batch * n_cand * 8 + slots * 8;
 }
 
-// Both entries: `who` names the caller in the messages; n_live == NULL: every slot is a candidate.
+// The three entries: `who` names the caller in the messages; n_live == NULL: every slot is a candidate; retired_bits == NULL: no
+// id is retired.
 static int32_t filtered_above_impl(const char *who_, const void *score, const int64_t *known_ptr, const int64_t *known_index,
                                    int64_t batch, int64_t n_cand, float threshold, int64_t *ptr_out, int64_t *ids_out,
                                    void *scores_out, int64_t capacity, int64_t *size_out, void *workspace, int64_t workspace_bytes,
-                                   const int64_t *n_live, void *stream) {
+                                   const int64_t *n_live, const uint32_t *retired_bits, void *stream) {
     const std::string who(who_);
     if (n_cand >= (int64_t)1 << 31 || std::isnan(threshold) || (std::isinf(threshold) && threshold > 0)) {      // (before any pointer is looked at)
         ultra::set_error(who + ": n_cand must stay below 2^31 and the threshold be finite or -inf");
@@ -366,7 +383,7 @@ static int32_t filtered_above_impl(const char *who_, const void *score, const in
     (void)hipGetLastError();   // drop any stale error left by other users of the runtime
     const dim3 threads(ultra::ABOVE_THREADS);
     hipLaunchKernelGGL(ultra::above_count_kernel, dim3((unsigned)slots), threads, 0, s, (const float *)score, known_ptr, known_index,
-                       (long long)n_cand, (long long)n_chunk, threshold, counts, n_live);
+                       (long long)n_cand, (long long)n_chunk, threshold, counts, n_live, retired_bits);
     if (hipGetLastError() != hipSuccess) {
         ultra::set_error("above_count_kernel launch failed");
         return ULTRA_ERR_HIP;
@@ -379,7 +396,7 @@ static int32_t filtered_above_impl(const char *who_, const void *score, const in
     }
     hipLaunchKernelGGL(ultra::above_fill_kernel, dim3((unsigned)slots), threads, 0, s, (const float *)score, known_ptr, known_index,
                        (long long)n_cand, (long long)n_chunk, threshold, (const long long *)offs, keys0, ids_out,
-                       (unsigned *)scores_out, n_live);
+                       (unsigned *)scores_out, n_live, retired_bits);
     if (hipGetLastError() != hipSuccess) {
         ultra::set_error("above_fill_kernel launch failed");
         return ULTRA_ERR_HIP;
@@ -406,7 +423,7 @@ extern "C" int32_t ultra_filtered_above(const void *score, const int64_t *known_
                                         int64_t capacity, int64_t *size_out, void *workspace, int64_t workspace_bytes,
                                         void *stream) {
     return filtered_above_impl("ultra_filtered_above", score, known_ptr, known_index, batch, n_cand, threshold, ptr_out, ids_out,
-                               scores_out, capacity, size_out, workspace, workspace_bytes, nullptr, stream);
+                               scores_out, capacity, size_out, workspace, workspace_bytes, nullptr, nullptr, stream);
 }
 
 extern "C" int32_t ultra_filtered_above_live(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
@@ -419,5 +436,21 @@ extern "C" int32_t ultra_filtered_above_live(const void *score, const int64_t *k
         return ULTRA_ERR_INVALID;
     }
     return filtered_above_impl("ultra_filtered_above_live", score, known_ptr, known_index, batch, n_cand, threshold, ptr_out, ids_out,
-                               scores_out, capacity, size_out, workspace, workspace_bytes, n_live, stream);
+                               scores_out, capacity, size_out, workspace, workspace_bytes, n_live, nullptr, stream);
+}
+
+// (n_retired is part of the contract of the three _alive entries; the answer sets have no count that needs it)
+extern "C" int32_t ultra_filtered_above_alive(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
+                                              int64_t n_cand, float threshold, int64_t *ptr_out, int64_t *ids_out, void *scores_out,
+                                              int64_t capacity, int64_t *size_out, void *workspace, int64_t workspace_bytes,
+                                              const int64_t *n_live, const uint32_t *retired_bits, const int64_t *n_retired,
+                                              void *stream) {
+    // (the parent's UNSUPPORTED cases come first)
+    if ((!retired_bits || !n_retired) && n_cand < (int64_t)1 << 31 && !std::isnan(threshold) &&
+        !(std::isinf(threshold) && threshold > 0)) {
+        ultra::set_error("ultra_filtered_above_alive: retired_bits or n_retired is NULL");
+        return ULTRA_ERR_INVALID;
+    }
+    return filtered_above_impl("ultra_filtered_above_alive", score, known_ptr, known_index, batch, n_cand, threshold, ptr_out,
+                               ids_out, scores_out, capacity, size_out, workspace, workspace_bytes, n_live, retired_bits, stream);
 }

@@ -10,6 +10,10 @@
 // A LIVE COUNT (ultra_filtered_rank_live): the row stride stays n_cand slots, only t < *n_live -- read on the
 // device, clamped to [0, n_cand] -- is counted, and num_negative counts live ids; a dead slot is never loaded.  The positives
 // and the known ids are live by construction.  n_live == NULL (ultra_filtered_rank) means n_cand.
+//
+// RETIRED IDS (ultra_filtered_rank_alive): a t whose bit is set in the device bitmap is skipped -- its score is
+// loaded beside the mask word and never compared -- and num_negative = live - retired - known, the retired count read on the device and clamped to [0, live].  The
+// positives and the known ids are alive by construction.  retired_bits == NULL: the entries above, the same integers.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -18,6 +22,7 @@
 #include "../../include/ultra_rspmm.h"
 #include "plan.hpp"
 #include "device_scope.hpp"
+#include "score_key.hpp"
 
 namespace ultra {
 
@@ -27,7 +32,9 @@ __global__ void __launch_bounds__(256) filtered_rank_kernel(const float *__restr
                                                             const int64_t *__restrict__ known_ptr,
                                                             const int64_t *__restrict__ known_index, long long n_cand,
                                                             unsigned long long *rank, long long *num_negative,
-                                                            const int64_t *__restrict__ n_live) {
+                                                            const int64_t *__restrict__ n_live,
+                                                            const uint32_t *__restrict__ retired_bits,
+                                                            const int64_t *__restrict__ n_retired) {
     const int q = blockIdx.y;
     long long live = n_cand;
     if (n_live) {
@@ -39,14 +46,22 @@ __global__ void __launch_bounds__(256) filtered_rank_kernel(const float *__restr
     const long long lo = (long long)blockIdx.x * RANK_CHUNK;
     const long long hi = lo + RANK_CHUNK < live ? lo + RANK_CHUNK : live;
     long long count = 0;
-    for (long long t = lo + threadIdx.x; t < hi; t += blockDim.x) count += (pos_score <= row[t]) ? 1 : 0;
+    if (retired_bits) {
+        for (long long t = lo + threadIdx.x; t < hi; t += blockDim.x) {     // (both loads unconditional: in flight together)
+            const bool dead = is_retired(retired_bits, t);
+            const float v = row[t];
+            count += (!dead && pos_score <= v) ? 1 : 0;
+        }
+    } else {
+        for (long long t = lo + threadIdx.x; t < hi; t += blockDim.x) count += (pos_score <= row[t]) ? 1 : 0;
+    }
     if (blockIdx.x == 0) {
         // the known answers (and the positive itself) do not count; the leading "+ 1" of the rank lives here too
         const long long k0 = known_ptr[q], k1 = known_ptr[q + 1];
         for (long long k = k0 + threadIdx.x; k < k1; k += blockDim.x) count -= (pos_score <= row[known_index[k]]) ? 1 : 0;
         if (threadIdx.x == 0) {
             count += 1;
-            num_negative[q] = live - (k1 - k0);
+            num_negative[q] = live - retired_count(n_retired, live) - (k1 - k0);
         }
     }
     // wave reduce, then one atomic per wave (integer: order independent)
@@ -174,7 +189,8 @@ extern "C" int32_t ultra_batch_prologue(const int64_t *batch, int64_t batch_size
 
 static int32_t filtered_rank_impl(const char *who, const void *score, const int64_t *pos_index, const int64_t *known_ptr,
                                   const int64_t *known_index, int64_t batch, int64_t n_cand, int64_t *rank_out,
-                                  int64_t *num_negative_out, const int64_t *n_live, void *stream) {
+                                  int64_t *num_negative_out, const int64_t *n_live, const uint32_t *retired_bits,
+                                  const int64_t *n_retired, void *stream) {
     ULTRA_DEVICE_SCOPE(stream, score);
     if (!score || !pos_index || !known_ptr || !rank_out || !num_negative_out || batch < 0 || n_cand <= 0) {
         ultra::set_error(std::string(who) + ": NULL operand or empty candidate set");
@@ -183,7 +199,7 @@ static int32_t filtered_rank_impl(const char *who, const void *score, const int6
     if (batch == 0) return ULTRA_OK;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     (void)hipGetLastError();   // drop any stale error left by other users of the runtime
-    if (n_live) {
+    if (n_live || retired_bits) {      // (the entries that are replayed from a hipGraph between eager work)
         const unsigned blocks = (unsigned)(batch < 256 * 1024 ? (batch + 255) / 256 : 1024);
         hipLaunchKernelGGL(ultra::rank_zero_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<unsigned long long *>(rank_out),
                            (long long)batch);
@@ -198,7 +214,7 @@ static int32_t filtered_rank_impl(const char *who, const void *score, const int6
     const dim3 grid((unsigned)((n_cand + ultra::RANK_CHUNK - 1) / ultra::RANK_CHUNK), (unsigned)batch);
     hipLaunchKernelGGL(ultra::filtered_rank_kernel, grid, dim3(256), 0, s, (const float *)score, pos_index, known_ptr,
                        known_index, (long long)n_cand, reinterpret_cast<unsigned long long *>(rank_out),
-                       reinterpret_cast<long long *>(num_negative_out), n_live);
+                       reinterpret_cast<long long *>(num_negative_out), n_live, retired_bits, n_retired);
     if (hipGetLastError() != hipSuccess) {
         ultra::set_error("filtered_rank_kernel launch failed");
         return ULTRA_ERR_HIP;
@@ -210,7 +226,7 @@ extern "C" int32_t ultra_filtered_rank(const void *score, const int64_t *pos_ind
                                        const int64_t *known_index, int64_t batch, int64_t n_cand, int64_t *rank_out,
                                        int64_t *num_negative_out, void *stream) {
     return filtered_rank_impl("ultra_filtered_rank", score, pos_index, known_ptr, known_index, batch, n_cand, rank_out,
-                              num_negative_out, nullptr, stream);
+                              num_negative_out, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int32_t ultra_filtered_rank_live(const void *score, const int64_t *pos_index, const int64_t *known_ptr,
@@ -221,5 +237,17 @@ extern "C" int32_t ultra_filtered_rank_live(const void *score, const int64_t *po
         return ULTRA_ERR_INVALID;
     }
     return filtered_rank_impl("ultra_filtered_rank_live", score, pos_index, known_ptr, known_index, batch, n_cand, rank_out,
-                              num_negative_out, n_live, stream);
+                              num_negative_out, n_live, nullptr, nullptr, stream);
+}
+
+extern "C" int32_t ultra_filtered_rank_alive(const void *score, const int64_t *pos_index, const int64_t *known_ptr,
+                                             const int64_t *known_index, int64_t batch, int64_t n_cand, int64_t *rank_out,
+                                             int64_t *num_negative_out, const int64_t *n_live, const uint32_t *retired_bits,
+                                             const int64_t *n_retired, void *stream) {
+    if (!retired_bits || !n_retired) {
+        ultra::set_error("ultra_filtered_rank_alive: retired_bits or n_retired is NULL");
+        return ULTRA_ERR_INVALID;
+    }
+    return filtered_rank_impl("ultra_filtered_rank_alive", score, pos_index, known_ptr, known_index, batch, n_cand, rank_out,
+                              num_negative_out, n_live, retired_bits, n_retired, stream);
 }

@@ -22,6 +22,12 @@
 // slot holds (a NaN, +inf) cannot reach a key; a chunk workgroup wholly beyond the live count still writes its empty partial
 // list, so the merge reads no stale workspace.  The grid and the workspace depend on (batch, n_cand) alone.  n_live == NULL
 // (ultra_filtered_topk) means n_cand: the same kernels, the same bits.
+//
+// RETIRED IDS (ultra_filtered_topk_alive): a device bitmap names ids below the live count that are absent.  A
+// chunk starts at a multiple of TOPK_CHUNK, so its candidates' mask words are whole words; they are loaded next to the scores
+// (ahead of them in program order, looked at after them: score_key.hpp) and the key of a retired candidate is zeroed before the
+// knock-out and the selection -- its score is loaded but reaches no key.  count_out is taken from live - retired - known, the retired count read on the device and clamped to [0, live].
+// retired_bits == NULL: the _live twin and the parent, the same bits.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -165,7 +171,7 @@ __device__ int select_topk(u64 (&held)[TOPK_HELD], int k, int bytes, TopkScratch
     return m;
 }
 
-// (n_cand: the row's LIVE candidates, of which the known ids are a part)
+// (n_cand: the row's LIVE candidates that are not retired, of which the known ids are a part)
 __device__ void write_answers(const float *row, long long n_cand, long long n_known, int k, int m, const u64 *sorted,
                               int64_t *ids_out, unsigned *scores_out, int64_t *count_out) {
     const int tid = threadIdx.x;
@@ -196,7 +202,9 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_chunk_kernel(const float *_
                                                                   const int64_t *__restrict__ known_index, long long n_cand,
                                                                   long long n_chunk, int k, u64 *__restrict__ partial,
                                                                   int64_t *ids_out, unsigned *scores_out, int64_t *count_out,
-                                                                  const int64_t *__restrict__ n_live) {
+                                                                  const int64_t *__restrict__ n_live,
+                                                                  const uint32_t *__restrict__ retired_bits,
+                                                                  const int64_t *__restrict__ n_retired) {
     __shared__ unsigned ord[TOPK_CHUNK];
     __shared__ u64 sorted[TOPK_MAX];
     __shared__ TopkScratch s;
@@ -207,13 +215,18 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_chunk_kernel(const float *_
     const long long live = live_count(n_live, n_cand);
     // (a chunk beyond the live count holds no candidate: n == 0, nothing is loaded, an empty list is written)
     const int n = (int)(live - lo < TOPK_CHUNK ? (live > lo ? live - lo : 0) : TOPK_CHUNK);
-    // all of a thread's scores in flight at once, the search for the chunk's slice of known(b) beside them
+    // all of a thread's scores in flight at once, its mask words ahead of them and the search for the chunk's slice of known(b)
+    // beside them; a retired candidate is absent before anything looks at its key
+    unsigned mask[TOPK_SLOTS];
+    retired_slots<TOPK_SLOTS, TOPK_THREADS>(retired_bits, lo, n, mask);
     unsigned bits[TOPK_SLOTS];
 #pragma unroll
     for (int j = 0; j < TOPK_SLOTS; ++j) {
         const int i = tid + j * TOPK_THREADS;
         bits[j] = i < n ? ordered_score(__float_as_uint(row[lo + i])) : 0u;
     }
+#pragma unroll
+    for (int j = 0; j < TOPK_SLOTS; ++j) bits[j] = slot_retired(mask[j]) ? 0u : bits[j];
     long long n_known = 0, a = 0, k1 = 0;
     bool any_known = false;      // (the same in every thread)
     if (known_ptr) {
@@ -261,7 +274,8 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_chunk_kernel(const float *_
     }
     __syncthreads();
     if (n_chunk == 1) {
-        write_answers(row, live, n_known, k, m, sorted, ids_out + b * k, scores_out + b * k, count_out + b);
+        write_answers(row, live - retired_count(n_retired, live), n_known, k, m, sorted, ids_out + b * k, scores_out + b * k,
+                      count_out + b);
     } else if (tid < k) {
         partial[((long long)blockIdx.x) * k + tid] = tid < m ? sorted[tid] : 0;
     }
@@ -271,7 +285,8 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_merge_kernel(const float *_
                                                                   long long n_cand, long long n_chunk, int k,
                                                                   const u64 *__restrict__ partial, int64_t *ids_out,
                                                                   unsigned *scores_out, int64_t *count_out,
-                                                                  const int64_t *__restrict__ n_live) {
+                                                                  const int64_t *__restrict__ n_live,
+                                                                  const int64_t *__restrict__ n_retired) {
     __shared__ u64 sorted[TOPK_MAX];
     __shared__ TopkScratch s;
     const int tid = threadIdx.x;
@@ -291,8 +306,9 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_merge_kernel(const float *_
         m = select_topk(held, k, 8, s, sorted);
     }
     const long long n_known = known_ptr ? known_ptr[b + 1] - known_ptr[b] : 0;
-    write_answers(score + b * n_cand, live_count(n_live, n_cand), n_known, k, m, sorted, ids_out + b * k, scores_out + b * k,
-                  count_out + b);
+    const long long live = live_count(n_live, n_cand);
+    write_answers(score + b * n_cand, live - retired_count(n_retired, live), n_known, k, m, sorted, ids_out + b * k,
+                  scores_out + b * k, count_out + b);
 }
 
 }  // namespace ultra
@@ -303,10 +319,12 @@ extern "C" int64_t ultra_filtered_topk_workspace(int64_t batch, int64_t n_cand, 
     return batch * n_chunk * (int64_t)k * (int64_t)sizeof(uint64_t);
 }
 
-// Both entries: `who` names the caller in the messages; n_live == NULL: every slot is a candidate.
+// The three entries: `who` names the caller in the messages; n_live == NULL: every slot is a candidate; retired_bits == NULL: no
+// id is retired.
 static int32_t filtered_topk_impl(const char *who_, const void *score, const int64_t *known_ptr, const int64_t *known_index,
                                   int64_t batch, int64_t n_cand, int32_t k, int64_t *ids_out, void *scores_out, int64_t *count_out,
-                                  void *workspace, int64_t workspace_bytes, const int64_t *n_live, void *stream) {
+                                  void *workspace, int64_t workspace_bytes, const int64_t *n_live, const uint32_t *retired_bits,
+                                  const int64_t *n_retired, void *stream) {
     const std::string who(who_);
     if (k < 1 || k > ULTRA_TOPK_MAX || n_cand >= (int64_t)1 << 31) {      // (before any pointer is looked at)
         ultra::set_error(who + ": k must lie in [1, " + std::to_string(ULTRA_TOPK_MAX) + "] and n_cand below 2^31");
@@ -333,7 +351,7 @@ static int32_t filtered_topk_impl(const char *who_, const void *score, const int
     (void)hipGetLastError();   // drop any stale error left by other users of the runtime
     hipLaunchKernelGGL(ultra::topk_chunk_kernel, dim3((unsigned)(batch * n_chunk)), dim3(ultra::TOPK_THREADS), 0, s,
                        (const float *)score, known_ptr, known_index, (long long)n_cand, (long long)n_chunk, (int)k,
-                       (ultra::u64 *)workspace, ids_out, (unsigned *)scores_out, count_out, n_live);
+                       (ultra::u64 *)workspace, ids_out, (unsigned *)scores_out, count_out, n_live, retired_bits, n_retired);
     if (hipGetLastError() != hipSuccess) {
         ultra::set_error("topk_chunk_kernel launch failed");
         return ULTRA_ERR_HIP;
@@ -341,7 +359,7 @@ static int32_t filtered_topk_impl(const char *who_, const void *score, const int
     if (n_chunk > 1) {
         hipLaunchKernelGGL(ultra::topk_merge_kernel, dim3((unsigned)batch), dim3(ultra::TOPK_THREADS), 0, s, (const float *)score,
                            known_ptr, (long long)n_cand, (long long)n_chunk, (int)k, (const ultra::u64 *)workspace, ids_out,
-                           (unsigned *)scores_out, count_out, n_live);
+                           (unsigned *)scores_out, count_out, n_live, n_retired);
         if (hipGetLastError() != hipSuccess) {
             ultra::set_error("topk_merge_kernel launch failed");
             return ULTRA_ERR_HIP;
@@ -354,7 +372,7 @@ extern "C" int32_t ultra_filtered_topk(const void *score, const int64_t *known_p
                                        int64_t n_cand, int32_t k, int64_t *ids_out, void *scores_out, int64_t *count_out,
                                        void *workspace, int64_t workspace_bytes, void *stream) {
     return filtered_topk_impl("ultra_filtered_topk", score, known_ptr, known_index, batch, n_cand, k, ids_out, scores_out, count_out,
-                              workspace, workspace_bytes, nullptr, stream);
+                              workspace, workspace_bytes, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int32_t ultra_filtered_topk_live(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
@@ -365,5 +383,18 @@ extern "C" int32_t ultra_filtered_topk_live(const void *score, const int64_t *kn
         return ULTRA_ERR_INVALID;
     }
     return filtered_topk_impl("ultra_filtered_topk_live", score, known_ptr, known_index, batch, n_cand, k, ids_out, scores_out,
-                              count_out, workspace, workspace_bytes, n_live, stream);
+                              count_out, workspace, workspace_bytes, n_live, nullptr, nullptr, stream);
+}
+
+extern "C" int32_t ultra_filtered_topk_alive(const void *score, const int64_t *known_ptr, const int64_t *known_index, int64_t batch,
+                                             int64_t n_cand, int32_t k, int64_t *ids_out, void *scores_out, int64_t *count_out,
+                                             void *workspace, int64_t workspace_bytes, const int64_t *n_live,
+                                             const uint32_t *retired_bits, const int64_t *n_retired, void *stream) {
+    // (the parent's UNSUPPORTED cases come first)
+    if ((!retired_bits || !n_retired) && k >= 1 && k <= ULTRA_TOPK_MAX && n_cand < (int64_t)1 << 31) {
+        ultra::set_error("ultra_filtered_topk_alive: retired_bits or n_retired is NULL");
+        return ULTRA_ERR_INVALID;
+    }
+    return filtered_topk_impl("ultra_filtered_topk_alive", score, known_ptr, known_index, batch, n_cand, k, ids_out, scores_out,
+                              count_out, workspace, workspace_bytes, n_live, retired_bits, n_retired, stream);
 }

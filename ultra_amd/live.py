@@ -11,6 +11,8 @@ delta is folded into the graph, which ids are live, and what `materialized()` me
   with_slots       ... with reserved rows
   with_relation_slots / compact_relations   ... laid out over reserved relation slots, and back in the compact numbering
   check_live       ValueError for an id in the reserve
+  check_not_retired   ... for an id that was retired (LiveGraph.remove_entities)
+  retired_words    the retired bitmap of a set of ids, as the ultra_filtered_*_alive entries read it
   check_live_relations   ... for a relation id that is no direct relation in use
   forwarded        a read-only property of an owner that reads a field of its LiveGraph
 """
@@ -98,6 +100,23 @@ def check_live(ids, num_live, what):
                          "it out" % (what, num_live))
 
 
+def check_not_retired(ids, retired, what):
+    """ValueError where an id is one of `retired` (a sorted int64 vector, or None: nothing is retired; one host read)."""
+    if retired is not None and len(retired) and len(ids) and bool(torch.isin(ids, retired.to(ids.device)).any()):
+        raise ValueError("%s must be existing entities: %s retired (remove_entities) and an id is never handed out again"
+                         % (what, "ids %s are" % retired.tolist() if len(retired) <= 8 else "%d ids are" % len(retired)))
+
+
+def retired_words(ids, num_slots, device=None):
+    """The bitmap of the distinct ids `ids` over num_slots slots: ceil(num_slots / 32) 32-bit words, id v bit v & 31 of word
+    v >> 5 -- the uint32 words the ultra_filtered_*_alive entries read, held as int32 (torch has no arithmetic on uint32; bit
+    31 is the sign bit, the bits are the same)."""
+    ids = torch.as_tensor(ids, dtype=torch.long, device=device).flatten()
+    words = torch.zeros((int(num_slots) + 31) // 32, dtype=torch.long, device=ids.device)
+    words.index_add_(0, ids >> 5, torch.ones_like(ids) << (ids & 31))      # (distinct ids: a sum of distinct bits is their OR)
+    return torch.where(words >= 1 << 31, words - (1 << 32), words).to(torch.int32)
+
+
 def forwarded(name):
     """For an owner that holds its LiveGraph as `_live`: a read-only property that reads `name` of it, so that the owner's
     attributes of before stay readable under their names."""
@@ -123,7 +142,15 @@ class LiveGraph(object):
     the served graph with them.  Without it `filter_graph` is None.
 
     owner: the class name in add_entities' error text.  on_rebuild(): called in every compaction that changes the served
-    graph, before `graph` is replaced."""
+    graph, before `graph` is replaced.
+
+    RETIRED entities (remove_entities): `retired_entities` (a sorted int64 vector on the graph's device) are ids
+    below num_entities whose facts are gone and that are never an answer, an anchor or an argument again; ids are not
+    renumbered and a slot is not handed out again.  From the first retirement on `retired_bits` (retired_words over num_slots:
+    one device bitmap, rewritten in place) and `retired_count` (one device int64) hold the same set for the selection kernels;
+    both keep their addresses, survive compact(), and only a rebuild that changes the slot count lays a longer bitmap out (the
+    captured steps are released there anyway).  `retired_operand`: the pair (retired_bits, retired_count), one object while the
+    bitmap is -- what a captured step takes and remembers.  All three are None before the first retirement."""
 
     def __init__(self, data, delta_capacity=256, entity_capacity=0, filter_data=None, keep_filter=False, delta_policy="lazy",
                  owner="LiveGraph", on_rebuild=None, relation_capacity=0, relation_bits_budget=256 << 20,
@@ -162,7 +189,14 @@ class LiveGraph(object):
         if keep_filter:
             self.filter_graph = self._filter_base = data if filter_data is None else filter_data
             self._filter_is_graph = self.filter_graph is data
+        self.retired_entities = torch.zeros(0, dtype=torch.long, device=data.edge_index.device)
+        self.retired_bits = self.retired_count = self.retired_operand = None
         self.delta = self._new_delta() if delta_policy == "eager" else None
+
+    @property
+    def num_retired(self):
+        """How many entities were retired (remove_entities)."""
+        return int(self.retired_entities.numel())
 
     @property
     def num_slots(self):
@@ -175,9 +209,11 @@ class LiveGraph(object):
         return int(self.graph.num_relations) // 2
 
     def _new_delta(self, capacity=None):
-        return rspmm.GraphDelta(self.graph, self.delta_capacity if capacity is None else capacity, num_live=self.num_entities,
-                                num_live_relations=self.num_direct_relations, relation_bits_budget=self.relation_bits_budget,
-                                live_relation_graph=self.live_relation_graph)
+        delta = rspmm.GraphDelta(self.graph, self.delta_capacity if capacity is None else capacity, num_live=self.num_entities,
+                                 num_live_relations=self.num_direct_relations, relation_bits_budget=self.relation_bits_budget,
+                                 live_relation_graph=self.live_relation_graph)
+        delta.retired = self.retired_entities if self.num_retired else None
+        return delta
 
     def _probe(self):
         """A delta to check arguments with or to materialise through: the one held, or an empty one."""
@@ -201,6 +237,84 @@ class LiveGraph(object):
         if not self.entity_capacity:
             return {}
         return {"num_live": self.live_count if on_gpu else self.num_entities}
+
+    def selection_for(self, on_gpu):
+        """num_live_for plus, once an entity was retired, `retired`: the device pair (retired_bits, retired_count) for the
+        kernels, the sorted id vector for the plain-torch restatements.  Before the first retirement: num_live_for."""
+        out = self.num_live_for(on_gpu)
+        if self.num_retired:
+            out["retired"] = self.retired_operand if on_gpu else self.retired_entities
+        return out
+
+    def check_entities(self, ids, what):
+        """ValueError unless every id is an entity in use: not in the reserve (where rows are reserved) and not retired."""
+        if self.entity_capacity:
+            check_live(ids, self.num_entities, what)
+        check_not_retired(ids, self.retired_entities, what)
+
+    # ---- retiring entities (DESIGN.md 28) ----
+    def remove_entities(self, ids):
+        """Retire the entities `ids` (an int or a vector of distinct live ids that are not retired yet; ValueError otherwise, and
+        nothing is changed): every fact of the materialised graph that names one of them as head or tail is retracted through
+        remove_facts -- base edges become tombstones, held delta facts leave the delta, the filter graph loses them in both
+        directions (a filter graph of its own also loses every other edge at the ids: no retired id is a known answer), a call
+        that does not fit compacts or folds as remove_facts does -- and the ids are retired: never an answer, never counted, a
+        ValueError as an anchor or as h / t of add_facts / remove_facts.  Ids stay what they are; num_entities stays the prefix
+        bound.  The incident facts are collected on the device, once per call, from BOTH columns of the edge list (a list that
+        is not closed under inverses loses every edge at the ids) as distinct direct triples.  Returns an int64 vector: per id
+        the number of distinct facts retracted that name it (a fact between two ids of the call counts for both)."""
+        dev = self.graph.edge_index.device
+        ids = torch.as_tensor(ids, dtype=torch.long, device=dev).flatten()
+        if len(ids) == 0:
+            return torch.zeros(0, dtype=torch.long, device=dev)
+        if bool(((ids < 0) | (ids >= self.num_entities)).any()):
+            raise ValueError("remove_entities takes existing entities (ids in [0, %d)): a negative id, an id beyond the slots or "
+                             "a reserved row is none" % self.num_entities)
+        if len(torch.unique(ids)) != len(ids):
+            raise ValueError("remove_entities takes distinct ids: one is repeated")
+        check_not_retired(ids, self.retired_entities, "the entities to retire")
+        graph = self._probe().materialize(self.graph)
+        (row, col), edge_type = graph.edge_index, graph.edge_type
+        at = (torch.isin(row, ids) | torch.isin(col, ids)).nonzero().flatten()
+        row, col, edge_type = row[at], col[at], edge_type[at]
+        direct = self.num_relation_slots
+        inverse = edge_type >= direct
+        triples = torch.stack([torch.where(inverse, col, row), torch.where(inverse, edge_type - direct, edge_type),
+                               torch.where(inverse, row, col)], dim=1)
+        triples = torch.unique(triples, dim=0) if len(triples) else triples
+        h, r, t = triples.unbind(1)
+        counts = ((h.unsqueeze(0) == ids.unsqueeze(1)) | (t.unsqueeze(0) == ids.unsqueeze(1))).sum(dim=1)
+        if len(h):
+            self.remove_facts(h, r, t)
+        if self.filter_graph is not None and not self._filter_is_graph:
+            base = self._filter_base
+            keep = ~(torch.isin(base.edge_index[0], ids.to(base.edge_index.device))
+                     | torch.isin(base.edge_index[1], ids.to(base.edge_index.device)))
+            if not bool(keep.all()):
+                self._filter_base = copy.copy(base)
+                self._filter_base.edge_index, self._filter_base.edge_type = base.edge_index[:, keep], base.edge_type[keep]
+                self._refresh_filter_graph()
+        self.retired_entities = torch.sort(torch.cat([self.retired_entities, ids])).values
+        self._lay_out_retired()
+        if self.delta is not None:
+            self.delta.retired = self.retired_entities
+        return counts
+
+    def _lay_out_retired(self):
+        """retired_bits / retired_count of retired_entities over the slots there are now: written into the tensors held, which
+        are allocated at the first retirement and replaced only where the slot count changed."""
+        if not self.num_retired:
+            return
+        words = retired_words(self.retired_entities, self.num_slots)
+        if self.retired_bits is None or self.retired_bits.numel() != words.numel():
+            self.retired_bits = words
+        else:
+            self.retired_bits.copy_(words)
+        if self.retired_count is None:
+            self.retired_count = torch.zeros(1, dtype=torch.long, device=words.device)
+        self.retired_count.fill_(self.num_retired)
+        if self.retired_operand is None or self.retired_operand[0] is not self.retired_bits:
+            self.retired_operand = (self.retired_bits, self.retired_count)
 
     # ---- the growing graph ----
     def add_entities(self, count=1, compact=None):
@@ -241,8 +355,10 @@ class LiveGraph(object):
         """The served edge list with the delta's edits (GraphDelta.materialize) and num_nodes = num_entities -- no reserved row --
         with the filter graph held now as its `filtered_data` where that is a graph of its own.  With reserved relation slots:
         in the compact numbering -- num_relations = 2 num_direct_relations, inverse type r + num_direct_relations, the relation
-        graph built for it (the filter graph alike).  A new copy at every call."""
+        graph built for it (the filter graph alike).  Retired ids keep their place: they are isolated nodes of the copy, named
+        by its `retired_entities` (a sorted int64 vector).  A new copy at every call."""
         out = copy.copy(self._probe().materialize(self.graph, num_nodes=self.num_entities))
+        out.retired_entities = self.retired_entities.clone()
         slots, live = self.num_relation_slots, self.num_direct_relations
         if self.relation_capacity:
             out = compact_relations(out, slots, live)
@@ -340,4 +456,5 @@ class LiveGraph(object):
         if self._on_rebuild is not None:
             self._on_rebuild()
         self.graph = graph
+        self._lay_out_retired()     # (the retired rows stay, as isolated slots; a new slot count: a longer bitmap, the bits kept)
         self.delta = self._new_delta() if self._policy == "eager" else None

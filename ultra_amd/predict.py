@@ -23,6 +23,10 @@ like any other, ranked last.  Slots beyond count = min(k, N - |known|) hold id -
 A GROWING graph: Predictor(entity_capacity=M) reserves M rows for entities that arrive later
 (Predictor.add_entities); the selection then runs over the LIVE ids of rows of N + M slots -- `num_live` of filtered_topk /
 filtered_above and their restatements, the ultra_filtered_*_live entries.
+
+RETIRED entities: Predictor.remove_entities(ids) retracts every fact of an entity and takes its id out of the
+candidate set for good -- `retired` of filtered_topk / filtered_above / filtered_rank_reference and their restatements, the
+ultra_filtered_*_alive entries.
 """
 
 import functools
@@ -33,7 +37,7 @@ import torch
 
 from . import _lib, dense, models, tasks
 from .graph import Capture, param_state
-from .live import LiveGraph, check_live, check_live_relations, forwarded
+from .live import LiveGraph, check_live, check_live_relations, check_not_retired, forwarded
 
 
 def _live_int(num_live, n):
@@ -54,20 +58,60 @@ def _live_operand(num_live, n, dev):
     return torch.tensor(_live_int(num_live, n), dtype=torch.long, device=dev)
 
 
-def _select(entry, args, n_live, dev):
+def _select(entry, args, n_live, dev, retired=None):
     """One launch of a selection entry on `dev`'s stream: `entry` without a live count, its `_live` twin with the device scalar
-    `n_live` appended to the same arguments.  The entry is looked up when it is called."""
-    if n_live is None:
+    `n_live` appended to the same arguments; with `retired` -- the device pair (bitmap, count) -- its `_alive` twin with the live
+    count (or NULL: every slot), the bitmap and the count appended.  The entry is looked up when it is called."""
+    if retired is not None:
+        _lib.check(getattr(_lib.lib, entry + "_alive")(*args, None if n_live is None else n_live.data_ptr(), retired[0].data_ptr(),
+                                                       retired[1].data_ptr(), _lib.stream_of(dev)))
+    elif n_live is None:
         _lib.check(getattr(_lib.lib, entry)(*args, _lib.stream_of(dev)))
     else:
         _lib.check(getattr(_lib.lib, entry + "_live")(*args, n_live.data_ptr(), _lib.stream_of(dev)))
 
 
-def filtered_rank_reference(pred, pos, ptr, index, num_live=None):
+def _retired_operand(retired, n, dev):
+    """`retired` of the kernels' wrappers: the pair (bits, count) on `dev` -- bits at least ceil(n / 32) 32-bit words (int32 or
+    uint32: live.retired_words), count one int64 -- as it is (neither is looked at on the host)."""
+    try:
+        bits, count = retired
+        ok = (torch.is_tensor(bits) and torch.is_tensor(count) and bits.dim() == 1 and bits.is_contiguous()
+              and bits.dtype in (torch.int32, torch.uint32) and bits.numel() >= (n + 31) // 32 and bits.device == dev
+              and count.numel() == 1 and count.dtype == torch.long and count.device == dev)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("`retired` is the pair (bits, count) on the scores' device: at least ceil(N / 32) = %d 32-bit words "
+                         "and one int64 (the sorted id vector is the _reference functions' form)" % ((n + 31) // 32))
+    return bits, count
+
+
+def _alive_columns(pred, retired, num_live, index=None):
+    """The _reference functions with `retired` (a sorted int64 id vector): (pred with the columns at or beyond num_live and the
+    retired columns deleted, the ids of the columns kept, `index` -- ids that are alive -- as positions among them)."""
+    n = pred.shape[1] if num_live is None else _live_int(num_live, pred.shape[1])
+    keep = torch.ones(n, dtype=torch.bool, device=pred.device)
+    retired = torch.as_tensor(retired, dtype=torch.long, device=pred.device).flatten()
+    keep[retired[retired < n]] = False
+    cols = keep.nonzero().flatten()
+    if index is not None:
+        at = torch.searchsorted(cols, index)
+        if len(index) and (bool((at >= len(cols)).any()) or not torch.equal(cols[at.clamp(max=max(len(cols) - 1, 0))], index)):
+            raise ValueError("a known id or a positive is retired or not live: they must be alive")
+        index = at
+    return pred[:, cols], cols, index
+
+
+def filtered_rank_reference(pred, pos, ptr, index, num_live=None, retired=None):
     """(rank (batch) int64, num_negative (batch) int64) of pred[b, pos[b]] among the candidates of row b -- the ids not in
     index[ptr[b] : ptr[b + 1]] (the known answers, the positive among them), ties counting against the positive: what
     ultra_filtered_rank computes, in plain torch on any device (tasks.compute_ranking over the mask the lists stand for).
-    num_live: only the ids below it exist."""
+    num_live: only the ids below it exist.  retired (a sorted int64 id vector): those ids do not exist either -- this function on
+    pred with their columns deleted, the positives and the known ids (all alive) renumbered."""
+    if retired is not None:
+        alive, cols, index = _alive_columns(pred, retired, num_live, index)
+        return filtered_rank_reference(alive, _alive_columns(pred, retired, num_live, pos)[2], ptr, index)
     if num_live is not None:
         pred = pred[:, :_live_int(num_live, pred.shape[1])]
     mask = torch.ones(pred.shape, dtype=torch.bool, device=pred.device)
@@ -76,10 +120,15 @@ def filtered_rank_reference(pred, pos, ptr, index, num_live=None):
     return tasks.compute_ranking(pred, pos, mask), mask.sum(dim=-1)
 
 
-def filtered_topk_reference(pred, k, ptr=None, index=None, num_live=None):
+def filtered_topk_reference(pred, k, ptr=None, index=None, num_live=None, retired=None):
     """(ids (batch, k) int64, scores (batch, k) pred's dtype, count (batch) int64) -- per row, the candidates are the ids not
     in index[ptr[b] : ptr[b + 1]], in the order of the stable descending sort of their scores.  num_live: only the ids below it
-    exist -- this function on pred[:, :num_live]."""
+    exist -- this function on pred[:, :num_live].  retired (a sorted int64 id vector): those ids do not exist either -- this
+    function on pred with their columns deleted (the known ids are alive), the ids mapped back."""
+    if retired is not None:
+        alive, cols, index = _alive_columns(pred, retired, num_live, index)
+        ids, scores, count = filtered_topk_reference(alive, k, ptr, index)
+        return torch.where(ids >= 0, cols[ids.clamp(min=0)] if len(cols) else ids, ids), scores, count
     if num_live is not None:
         return filtered_topk_reference(pred[:, :_live_int(num_live, pred.shape[1])], k, ptr, index)
     k = int(k)
@@ -105,10 +154,12 @@ def check_k(k):
         raise ValueError("k must be an int in [1, %d], got %r" % (_lib.TOPK_MAX, k))
 
 
-def filtered_topk(pred, k, ptr=None, index=None, num_live=None):
+def filtered_topk(pred, k, ptr=None, index=None, num_live=None, retired=None):
     """filtered_topk_reference through the HIP kernel: pred (batch, N) fp32 on the GPU; ptr (batch + 1) / index int64, ids
     ascending and distinct within a row; ptr None: no filter.  num_live (an int in [1, N], or one int64 on the device, read by
-    the kernels): ultra_filtered_topk_live on the full rows -- no slice, no copy; None: ultra_filtered_topk."""
+    the kernels): ultra_filtered_topk_live on the full rows -- no slice, no copy; None: ultra_filtered_topk.  retired (the device
+    pair (bits, count): live.retired_words over at least N slots and one int64, both read by the kernels):
+    ultra_filtered_topk_alive, with num_live or without."""
     check_k(k)
     if not pred.is_cuda:
         raise RuntimeError("ultra_amd.predict.filtered_topk: expected a GPU tensor; the MI355X engine has no CPU path")
@@ -130,7 +181,7 @@ def filtered_topk(pred, k, ptr=None, index=None, num_live=None):
     args = (pred.data_ptr(), None if ptr is None else ptr.data_ptr(), None if ptr is None else index.data_ptr(), batch, n, k,
             ids.data_ptr(), scores.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel() * 8)
     live = None if num_live is None else _live_operand(num_live, n, dev)     # (referenced until the launch is enqueued)
-    _select("ultra_filtered_topk", args, live, dev)
+    _select("ultra_filtered_topk", args, live, dev, None if retired is None else _retired_operand(retired, n, dev))
     return ids, scores, count
 
 
@@ -153,7 +204,7 @@ def logit_threshold(probability):
     return float(torch.tensor(math.log(p / (1.0 - p)), dtype=torch.float64).to(torch.float32))
 
 
-def filtered_above_reference(pred, threshold, ptr=None, index=None, num_live=None):
+def filtered_above_reference(pred, threshold, ptr=None, index=None, num_live=None, retired=None):
     """The answer SET of every row, ranked: (out_ptr (batch + 1) int64, ids (total) int64, scores (total) pred's dtype, size
     (batch) int64), on any device -- the definition ultra_filtered_above is tested against.
 
@@ -170,7 +221,12 @@ def filtered_above_reference(pred, threshold, ptr=None, index=None, num_live=Non
     sigmoid rounds to 0.5 (roughly below 1e-7); such logits are members here.  And `size` is an integer count, not the
     reference's soft num_pred; query_eval keeps the reference's metrics as they are.
 
-    num_live: only the ids below it exist -- this function on pred[:, :num_live]."""
+    num_live: only the ids below it exist -- this function on pred[:, :num_live].  retired (a sorted int64 id vector): those ids
+    do not exist either, in the lists and in `size` -- this function on pred with their columns deleted, the ids mapped back."""
+    if retired is not None:
+        alive, cols, index = _alive_columns(pred, retired, num_live, index)
+        out_ptr, ids, scores, size = filtered_above_reference(alive, threshold, ptr, index)
+        return out_ptr, cols[ids], scores, size
     if num_live is not None:
         return filtered_above_reference(pred[:, :_live_int(num_live, pred.shape[1])], threshold, ptr, index)
     thr = _fp32_threshold(threshold)
@@ -194,12 +250,13 @@ def filtered_above_reference(pred, threshold, ptr=None, index=None, num_live=Non
     return out_ptr, ids, scores, size
 
 
-def filtered_above(pred, threshold, ptr=None, index=None, num_live=None):
+def filtered_above(pred, threshold, ptr=None, index=None, num_live=None, retired=None):
     """filtered_above_reference through the HIP kernels (csrc/above_kernels.hip): pred (batch, N) fp32 on the GPU; ptr
     (batch + 1) / index int64, ids ascending and distinct within a row; ptr None: no filter.  `ids` and `scores` come back as
     the full-capacity (batch * N) buffers: entries at or beyond out_ptr[batch] are unspecified.  No host wait is made -- the
     caller reads out_ptr[-1] when it wants to slice.  num_live (an int in [1, N], or one int64 on the device, read by the
-    kernels): ultra_filtered_above_live on the full rows; None: ultra_filtered_above."""
+    kernels): ultra_filtered_above_live on the full rows; None: ultra_filtered_above.  retired (the device pair (bits, count) of
+    filtered_topk): ultra_filtered_above_alive."""
     thr = _fp32_threshold(threshold)
     if not pred.is_cuda:
         raise RuntimeError("ultra_amd.predict.filtered_above: expected a GPU tensor; the MI355X engine has no CPU path")
@@ -224,7 +281,7 @@ def filtered_above(pred, threshold, ptr=None, index=None, num_live=None):
     args = (pred.data_ptr(), None if ptr is None else ptr.data_ptr(), None if ptr is None else index.data_ptr(), batch, n, thr,
             out_ptr.data_ptr(), ids.data_ptr(), scores.data_ptr(), ids.numel(), size.data_ptr(), ws.data_ptr(), ws.numel() * 8)
     live = None if num_live is None else _live_operand(num_live, n, dev)     # (referenced until the launch is enqueued)
-    _select("ultra_filtered_above", args, live, dev)
+    _select("ultra_filtered_above", args, live, dev, None if retired is None else _retired_operand(retired, n, dev))
     return out_ptr, ids, scores, size
 
 
@@ -270,9 +327,11 @@ class _GraphedPredictStep(_IndexedStep):
     forward and ultra_filtered_topk.  Per batch the host copies the (bs) anchors and relations and the (bs + 1) offsets into
     the known lists of the whole call, which live in a buffer of the step (`load_index`, once per call)."""
 
-    def __init__(self, model, data, batch_size, k, mode, index_capacity, warmup=2, delta=None, n_live=None):
+    def __init__(self, model, data, batch_size, k, mode, index_capacity, warmup=2, delta=None, n_live=None, retired=None):
         """n_live (one int64 on the device, or None): the live count of a graph with reserved rows -- the selection is then
         ultra_filtered_topk_live, which reads it at replay; None: ultra_filtered_topk, exactly as before.
+        retired (the device pair (bitmap, count) of a graph that retired entities, or None): the selection is
+        ultra_filtered_topk_alive, which reads both at replay -- `retired` is what the Predictor compares.
         delta (rspmm.GraphDelta or None): handed to the model from the first capture.  While it is empty the model takes its
         normal path; once it holds facts or tombstones the capture records the delta's launches, which read its device buffers
         at replay --
@@ -295,14 +354,14 @@ class _GraphedPredictStep(_IndexedStep):
         ws_bytes = _lib.lib.ultra_filtered_topk_workspace(batch_size, n, k)
         self.ws = torch.empty(max(1, ws_bytes // 8), dtype=torch.long, device=dev)
 
-        self.n_live = n_live
+        self.n_live, self.retired = n_live, retired
 
         def step():
             pred = model(data, _candidates(data, self.anchor, self.relation, mode), **model_kwargs).float().contiguous()
             args = (pred.data_ptr(), self.ptr.data_ptr() if self.filtered else None,
                     self.index.data_ptr() if self.filtered else None, batch_size, n, k, self.ids.data_ptr(),
                     self.scores.data_ptr(), self.count.data_ptr(), self.ws.data_ptr(), self.ws.numel() * 8)
-            _select("ultra_filtered_topk", args, n_live, dev)
+            _select("ultra_filtered_topk", args, n_live, dev, retired)
 
         self.warm_up(step, warmup)
         self.capture(step)
@@ -394,10 +453,10 @@ def live_relation_graph_supported(model):
     return live_relation_graph_blocker(model) is None
 
 
-def _check_facts(data, h, r, t, num_live=None, num_direct=None):
+def _check_facts(data, h, r, t, num_live=None, num_direct=None, retired=None):
     """(h, r, t) of verify_*: int64 vectors of one length on the graph's device, r a direct relation (ValueError otherwise);
     num_live (a graph with reserved rows): h and t below it; num_direct (a graph with reserved relation slots): the direct
-    relations in use, in place of num_relations // 2."""
+    relations in use, in place of num_relations // 2; retired (a sorted id vector): h and t are none of them."""
     dev = data.edge_index.device
     h, r, t = (torch.as_tensor(v, dtype=torch.long, device=dev).flatten() for v in (h, r, t))
     if not (h.shape == r.shape == t.shape):
@@ -408,6 +467,7 @@ def _check_facts(data, h, r, t, num_live=None, num_direct=None):
                          "is its direct twin" % direct)
     if num_live is not None:
         check_live(torch.cat([h, t]), num_live, "a fact's head and tail")
+    check_not_retired(torch.cat([h, t]), retired, "a fact's head and tail")
     return h, r, t
 
 
@@ -451,15 +511,16 @@ class _GraphedVerifyStep(_IndexedStep):
     candidates, the masked forward on the full graph's cached plans, ultra_filtered_rank and the gather of the positives' scores.
     Per batch the host copies the triples and the (bs + 1) offsets into the known lists of the whole call (`load_index`)."""
 
-    def __init__(self, model, data, batch_size, mode, index_capacity, warmup=2, n_live=None, delta=None):
+    def __init__(self, model, data, batch_size, mode, index_capacity, warmup=2, n_live=None, delta=None, retired=None):
         """n_live: as in _GraphedPredictStep -- ultra_filtered_rank_live over the live ids, or (None) ultra_filtered_rank.
+        retired: as in _GraphedPredictStep -- ultra_filtered_rank_alive, which takes a NULL live count and zeroes with a kernel.
         delta (rspmm.GraphDelta or None; a model with the leave_out route): while it holds no edit the step records the masked
         forward above; once it holds facts or tombstones it records model(..., leave_out=triples, delta=delta) -- the keep rows
         over the base edge list, the same edges as per-sample keys (GraphDelta.sample_keys into the step's own key buffers) and
         the delta's fix-up launches, which read its device buffers at replay.  `route` is what the Predictor compares."""
         dev = data.edge_index.device
         Capture.__init__(self, dev)
-        self.model, self.bs, self.mode, self.n_live = model, batch_size, mode, n_live
+        self.model, self.bs, self.mode, self.n_live, self.retired = model, batch_size, mode, n_live, retired
         self.delta, self.route = delta, _delta_route(delta)
         live = delta is not None and delta.edited
         # (row, col, type) of every sample's two dead edges: allocated once, at fixed addresses
@@ -477,7 +538,7 @@ class _GraphedVerifyStep(_IndexedStep):
         # The live route is replayed between eager edits (add_facts / remove_facts run torch ops of their own), and a memset node
         # captured into a hipGraph replays wrongly once eager memsets interleave with the replays (csrc/rank_kernels.hip): its
         # rank goes through the live-count entry, which zeroes with a kernel -- over all n ids where no rows are reserved.
-        self.n_all = torch.full((1,), n, dtype=torch.long, device=dev) if live and n_live is None else None
+        self.n_all = torch.full((1,), n, dtype=torch.long, device=dev) if live and n_live is None and retired is None else None
         rank_count = n_live if n_live is not None else self.n_all
 
         def step():
@@ -492,7 +553,7 @@ class _GraphedVerifyStep(_IndexedStep):
             pos = pos.contiguous()
             args = (pred.data_ptr(), pos.data_ptr(), self.ptr.data_ptr(), self.index.data_ptr(), batch_size, n,
                     self.rank.data_ptr(), self.num_negative.data_ptr())
-            _select("ultra_filtered_rank", args, rank_count, dev)
+            _select("ultra_filtered_rank", args, rank_count, dev, retired)
             self.score.copy_(pred.gather(1, pos.unsqueeze(-1)).squeeze(-1))
 
         self.warm_up(step, warmup)
@@ -568,7 +629,16 @@ class Predictor(object):
     their next replay.  remove_facts keeps the object too.  Results are those of the flag-off route, bit for bit.  Needs a
     relation model of sum / DistMult 64-d layers (live_relation_graph_supported; ValueError otherwise) and applies on the GPU
     to relation graphs of at most 1024 nodes; elsewhere the flag-off route runs.  A replay still in flight while add_facts
-    writes is the caller's to order, as for the delta's own buffers."""
+    writes is the caller's to order, as for the delta's own buffers.
+
+    RETIRED entities: remove_entities(ids) takes entities out of the served graph -- every fact that names one is
+    retracted (remove_facts: tombstones, the delta, the filter graph) and the id is retired: never an answer, never counted in
+    count / size / num_negative, a ValueError as an anchor and as h / t of add_facts / remove_facts / verify_*.  Ids are not
+    renumbered and a retired slot is not handed out again; `num_retired` and `retired_entities` tell which.  The retired set
+    lives in one device bitmap and one device int64 that the ultra_filtered_*_alive entries read at replay: the first
+    retirement makes the captured steps again (as the first tombstone does), later ones cost no capture.  Every result is that
+    of a fresh Predictor on materialized() -- which keeps the id space, the retired ids isolated nodes -- with the retired ids
+    taken out of the candidate set.  A predictor that never retires calls exactly the entries it called before."""
 
     def __init__(self, model, data, k=10, batch_size=8, filtered_data=None, filtered=True, use_graph=True, delta_capacity=256,
                  entity_capacity=0, relation_capacity=0, relation_bits_budget=256 << 20, live_relation_graph=False):
@@ -610,6 +680,8 @@ class Predictor(object):
     live_relation_graph = forwarded("live_relation_graph")
     num_direct_relations = forwarded("num_direct_relations")
     num_relation_slots = forwarded("num_relation_slots")
+    num_retired = forwarded("num_retired")
+    retired_entities = forwarded("retired_entities")
 
     # ---- the growing vocabulary ----
     def add_relations(self, count=1):
@@ -655,6 +727,16 @@ class Predictor(object):
         (GraphDelta.remove).  Compacts first where the delta cannot hold the tombstones."""
         before = self._relation_graph_state()
         out = self._live.remove_facts(h, r, t)
+        self._relation_graph_edited(before)
+        return out
+
+    def remove_entities(self, ids):
+        """Retire the entities `ids` -- an int or a vector of distinct ids in use, none retired before (ValueError otherwise):
+        every fact that names one as head or tail is retracted (remove_facts) and the ids are never an answer, a candidate that
+        is counted, an anchor or an argument of an edit again (LiveGraph.remove_entities).  Returns an int64 vector: per id the
+        number of distinct facts retracted."""
+        before = self._relation_graph_state()
+        out = self._live.remove_entities(ids)
         self._relation_graph_edited(before)
         return out
 
@@ -790,19 +872,24 @@ class Predictor(object):
         except Exception:
             pass
 
+    def _retired(self):
+        """What the captured steps take and remember of the retired set: the device pair (bitmap, count) -- one object while the
+        bitmap is -- or None before the first retirement."""
+        return self._live.retired_operand
+
     def _step(self, mode, need):
         """The captured step of this direction, (re)built when there is none, the weights changed or the known lists of the
         call do not fit its buffer."""
         step = self._steps.get(mode)
         if step is not None and step.params == param_state(self.model) and (need is None or need <= step.capacity) \
-                and step.delta is self.delta and step.route == _delta_route(self.delta):
+                and step.delta is self.delta and step.route == _delta_route(self.delta) and step.retired is self._retired():
             return step
         if step is not None:
             step.release()
             del self._steps[mode]
         capacity = None if need is None else max(2 * need, 1 << 16)
         step = _GraphedPredictStep(self.model, self.data, self.batch_size, self.k, mode, capacity, delta=self.delta,
-                                   n_live=self.live_count)
+                                   n_live=self.live_count, retired=self._retired())
         self._steps[mode] = step
         return step
 
@@ -810,20 +897,21 @@ class Predictor(object):
         key = "verify_" + mode
         step = self._steps.get(key)
         if step is not None and step.params == param_state(self.model) and need <= step.capacity \
-                and step.delta is self.delta and step.route == _delta_route(self.delta):
+                and step.delta is self.delta and step.route == _delta_route(self.delta) and step.retired is self._retired():
             return step
         if step is not None:
             step.release()
             del self._steps[key]
         step = _GraphedVerifyStep(self.model, self.data, self.batch_size, mode, max(2 * need, 1 << 16), n_live=self.live_count,
-                                  delta=self.delta)
+                                  delta=self.delta, retired=self._retired())
         self._steps[key] = step
         return step
 
     @torch.no_grad()
     def _verify(self, h, r, t, mode):
         h, r, t = _check_facts(self.data, h, r, t, num_live=self.num_entities if self.entity_capacity else None,
-                               num_direct=self.num_direct_relations if self.relation_capacity else None)
+                               num_direct=self.num_direct_relations if self.relation_capacity else None,
+                               retired=self.retired_entities)
         if self.delta is not None and self.delta.edited and (self.entity_capacity or self.relation_capacity
                                                              or not delta_samples_supported(self.model)):
             # a model without the combined route: the keep masks run over the graph's own edge list.  A graph with reserved rows
@@ -880,9 +968,9 @@ class Predictor(object):
                     b_rank, b_neg = torch.empty_like(pos), torch.empty_like(pos)
                     args = (pred.data_ptr(), pos.data_ptr(), b_ptr.data_ptr(), index.data_ptr(), len(part), pred.shape[1],
                             b_rank.data_ptr(), b_neg.data_ptr())
-                    _select("ultra_filtered_rank", args, live_count, dev)
+                    _select("ultra_filtered_rank", args, live_count, dev, self._retired())
                 else:       # off the GPU: the plain-torch restatement, as in `tails`
-                    b_rank, b_neg = filtered_rank_reference(pred, pos, b_ptr, index, **self._live.num_live_for(False))
+                    b_rank, b_neg = filtered_rank_reference(pred, pos, b_ptr, index, **self._live.selection_for(False))
                 score[lo:lo + len(part)] = pred.gather(1, pos.unsqueeze(-1)).squeeze(-1)
                 rank[lo:lo + len(part)], num_negative[lo:lo + len(part)] = b_rank, b_neg
         finally:
@@ -898,8 +986,7 @@ class Predictor(object):
         relation = torch.as_tensor(relation, dtype=torch.long, device=dev).flatten()
         if anchor.shape != relation.shape:
             raise ValueError("one relation per query: got %d entities and %d relations" % (len(anchor), len(relation)))
-        if self.entity_capacity:
-            check_live(anchor, self.num_entities, "the anchors of a query")
+        self._live.check_entities(anchor, "the anchors of a query")
         if self.relation_capacity:
             check_live_relations(relation, self.num_direct_relations, "the relations of a query")
         n = len(anchor)
@@ -916,12 +1003,12 @@ class Predictor(object):
                                   **model_kwargs).float()
                 b_ptr = None if ptr is None else ptr[lo:lo + len(pred) + 1]
                 if pred.is_cuda:
-                    b_out, b_ids, b_scores, b_size = filtered_above(pred, threshold, b_ptr, index, **live.num_live_for(pred.is_cuda))
+                    b_out, b_ids, b_scores, b_size = filtered_above(pred, threshold, b_ptr, index, **live.selection_for(pred.is_cuda))
                     total = int(b_out[-1])      # (the one host read of the batch)
                     b_ids, b_scores = b_ids[:total].clone(), b_scores[:total].clone()
                 else:
                     b_out, b_ids, b_scores, b_size = filtered_above_reference(pred, threshold, b_ptr, index,
-                                                                              **live.num_live_for(pred.is_cuda))
+                                                                              **live.selection_for(pred.is_cuda))
                     total = b_ids.numel()
                 out_ptr.append(b_out[1:] + at)
                 ids.append(b_ids)
@@ -943,8 +1030,7 @@ class Predictor(object):
         relation = torch.as_tensor(relation, dtype=torch.long, device=dev).flatten()
         if anchor.shape != relation.shape:
             raise ValueError("one relation per query: got %d entities and %d relations" % (len(anchor), len(relation)))
-        if self.entity_capacity:
-            check_live(anchor, self.num_entities, "the anchors of a query")
+        self._live.check_entities(anchor, "the anchors of a query")
         if self.relation_capacity:
             check_live_relations(relation, self.num_direct_relations, "the relations of a query")
         n = len(anchor)
@@ -989,7 +1075,7 @@ class Predictor(object):
                 b_ptr = None if ptr is None else ptr[lo:lo + len(pred) + 1]
                 # the fused kernel on the GPU; the restatement with the same interface elsewhere (as eval._local_rows does)
                 select = filtered_topk if pred.is_cuda else filtered_topk_reference
-                b_ids, b_scores, b_count = select(pred, k, b_ptr, index, **live.num_live_for(pred.is_cuda))
+                b_ids, b_scores, b_count = select(pred, k, b_ptr, index, **live.selection_for(pred.is_cuda))
                 ids[lo:lo + len(pred)], scores[lo:lo + len(pred)], count[lo:lo + len(pred)] = b_ids, b_scores, b_count
         finally:
             self.model.train(was_training)

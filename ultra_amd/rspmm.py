@@ -842,6 +842,7 @@ class GraphDelta(object):
         self.traversal = None       # the layout in the symbolic traversal's direction: laid out when first asked for
         self.explain = None         # the layout keyed by destination, for explanations: laid out when first asked for
         self._keep = None           # (version, keep vector)
+        self.retired = None         # ids `check` refuses (a sorted int64 vector; set by the owner: LiveGraph.remove_entities)
 
     def __len__(self):
         return self.num_facts
@@ -872,6 +873,9 @@ class GraphDelta(object):
         if len(h):
             if bool(((h < 0) | (h >= self.num_live) | (t < 0) | (t >= self.num_live)).any()):
                 raise ValueError("a fact's head and tail must be existing entities (ids in [0, %d))" % self.num_live)
+            if self.retired is not None and len(self.retired) and bool(torch.isin(torch.cat([h, t]), self.retired).any()):
+                raise ValueError("a fact's head and tail must be existing entities: %d ids are retired (remove_entities) and "
+                                 "an id is never handed out again" % len(self.retired))
             if bool(((r < 0) | (r >= self.num_live_relations)).any()):
                 raise ValueError("a fact is stated through a direct relation (r < num_relations // 2 = %d); its inverse edge "
                                  "is added with it" % self.num_live_relations)
