@@ -551,6 +551,19 @@ int32_t ultra_filtered_topk_alive(const void *score, const int64_t *known_ptr, c
  * slot is live), whose results keep their bits.  No memset node is recorded: for batch == 0 a one-thread kernel writes
  * ptr_out[0] = 0.  Errors: those of ultra_nonzero_lists, under this name; a NULL n_live is ULTRA_ERR_INVALID, decided before
  * any GPU call.
+ *
+ * ultra_nonzero_lists_alive: the lists of ultra_nonzero_lists_live with every RETIRED id left out -- the
+ * final symbolic sets of a graph that retired entities, whose retired slots hold 1.0 after a negation in the middle of the id
+ * range.  The arguments of ultra_nonzero_lists_live plus retired_bits, a DEVICE bitmap of at least ceil(n / 32) 32-bit words:
+ * id v is bit v & 31 of word v >> 5 (the words the ultra_filtered_*_alive entries read).  n_live may be NULL here: every slot
+ * is below the bound (a graph without reserved rows).  No retired count is taken: the lists do no count arithmetic.  The value
+ * in a retired slot may be loaded but reaches neither a count nor a list, whatever it holds; a word none of whose ids is below
+ * the clamped live count is not loaded and a bit at an id >= *n_live is never looked at.  The bitmap is read by the kernels at
+ * run time and the launch shape depends on (batch, n) alone, so a call recorded into a hipGraph serves every later retirement.
+ * The same two kernels (retired_bits == NULL inside: the twin and the parent, whose results keep their bits); no atomics, no
+ * memset node (batch == 0: the one-thread kernel), no allocation, no host wait.  Errors: those of ultra_nonzero_lists, under this
+ * name; retired_bits == NULL is ULTRA_ERR_INVALID ("ultra_nonzero_lists_alive: retired_bits is NULL"), decided before anything
+ * is launched.
  */
 int32_t ultra_query_segment(const int32_t *entry_depth, const int32_t *push_row, const int32_t *pop_row, const int32_t *op_ptr,
                             const int32_t *ops, int64_t batch, int64_t num_node, int32_t stack_depth, int32_t dtype,
@@ -560,6 +573,9 @@ int32_t ultra_nonzero_lists(const void *x, int64_t batch, int64_t n, int64_t *co
                             int64_t capacity, void *stream);
 int32_t ultra_nonzero_lists_live(const void *x, int64_t batch, int64_t n, int64_t *counts, int64_t *ptr_out,
                                  int64_t *index_out, int64_t capacity, const int64_t *n_live, void *stream);
+int32_t ultra_nonzero_lists_alive(const void *x, int64_t batch, int64_t n, int64_t *counts, int64_t *ptr_out,
+                                  int64_t *index_out, int64_t capacity, const int64_t *n_live,
+                                  const uint32_t *retired_bits, void *stream);
 
 /* ---- serving answer sets ----
  * ultra_filtered_above: per row of score (batch, n_cand) fp32 contiguous every candidate above `threshold`, ranked.  id v is a

@@ -2,7 +2,7 @@
 
     python tools/query_predict.py --data-root DIR [--ckpt FILE] --query "(('e1', ('r1',)), ('e2', ('r2', -2)))" [-k 10]
                                   [--logic product] [--unfiltered] [--above P] [--add-fact H R T]... [--remove-fact H R T]...
-                                  [--entity-capacity M] [--add-entity NAME]...
+                                  [--entity-capacity M] [--add-entity NAME]... [--remove-entity NAME]...
 
 DIR holds train.txt / valid.txt / test.txt (`head relation tail` per line) and optionally entities.dict / relations.dict
 (ultra_amd.data.load_triples_dir).  The query is a BetaE nested tuple (ultra_amd.ultraquery.Query.from_nested): a pair
@@ -24,6 +24,12 @@ relation of the dataset (not an inverse).
 rows reserved by --entity-capacity M (default: as many as there are --add-entity options), costs no plan, no relation graph and
 no traversal index, and from then on NAME is an entity like any other -- in the --add-fact / --remove-fact options that FOLLOW it
 on the command line, as an anchor of the query and in the printed answers.
+
+--remove-entity NAME (repeatable) takes an entity out of the graph served before the query is answered
+(QueryPredictor.retire_entities): every fact that names it is retracted and the entity is retired -- never an
+answer, never an entailed answer, no anchor.  It is applied in command-line order with the other edit options; NAME (a name of
+the vocabulary, one added earlier on the command line, or an integer id) no longer resolves in the options that follow it, nor
+in the query.
 """
 import argparse
 import ast
@@ -36,26 +42,28 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 
-def resolve(nested, ent, rel):
-    """The nested tuple with every name replaced by its id (the shapes are those of Query.nested_to_postfix)."""
+def resolve(nested, ent, rel, gone=()):
+    """The nested tuple with every name replaced by its id (the shapes are those of Query.nested_to_postfix); `gone`: the names
+    that were retired on the command line, which resolve no longer."""
     def lookup(name, vocab, what):
         if isinstance(name, int):
             return name
-        if name not in vocab:
+        if name not in vocab or (vocab is ent and name in gone):
             sys.exit("unknown %s %r" % (what, name))
         return vocab.index(name)
     if len(nested) == 2 and not isinstance(nested[1][-1], tuple):
         anchor, chain = nested
-        anchor = resolve(anchor, ent, rel) if isinstance(anchor, tuple) else lookup(anchor, ent, "entity")
+        anchor = resolve(anchor, ent, rel, gone) if isinstance(anchor, tuple) else lookup(anchor, ent, "entity")
         return (anchor, tuple(lookup(step, rel, "relation") for step in chain))
-    return tuple(branch if branch == (-1,) else resolve(branch, ent, rel) for branch in nested)
+    return tuple(branch if branch == (-1,) else resolve(branch, ent, rel, gone) for branch in nested)
 
 
-def lookup_fact(fact, ent, rel):
-    """(h, r, t) ids of an --add-fact / --remove-fact option: names of the vocabularies, or integer ids."""
+def lookup_fact(fact, ent, rel, gone=()):
+    """(h, r, t) ids of an --add-fact / --remove-fact option: names of the vocabularies, or integer ids; `gone`: the entity
+    names retired earlier on the command line, which resolve no longer."""
     out = []
     for name, vocab, what in zip(fact, (ent, rel, ent), ("entity", "relation", "entity")):
-        if name in vocab:
+        if name in vocab and not (vocab is ent and name in gone):
             out.append(vocab.index(name))
         elif name.lstrip("-").isdigit():
             out.append(int(name))
@@ -78,6 +86,8 @@ def main(argv=None):
             namespace.edits = getattr(namespace, "edits", None) or []
             if option_string == "--add-entity":
                 namespace.edits.append((None, values))
+            elif option_string == "--remove-entity":
+                namespace.edits.append(("retire", values))
             else:
                 namespace.edits.append((option_string == "--add-fact", tuple(values)))
 
@@ -87,6 +97,8 @@ def main(argv=None):
                     help="retract the fact (H, R, T) before the query; repeatable, applied in order with --add-fact")
     ap.add_argument("--add-entity", action=Edit, metavar="NAME",
                     help="introduce a new entity before the query; repeatable, applied in order with the fact options")
+    ap.add_argument("--remove-entity", action=Edit, metavar="NAME",
+                    help="retire an entity and retract its facts before the query; repeatable, applied in order with the other edits")
     ap.add_argument("--entity-capacity", type=int, default=None, metavar="M",
                     help="rows reserved for new entities (default: the number of --add-entity options)")
     ap.set_defaults(edits=[])
@@ -102,6 +114,7 @@ def main(argv=None):
     ent, rel = udata.read_vocab(args.data_root)
     ent = list(ent)        # (grows along the command line: a name resolves in the options after its --add-entity; the ids are
     num_known = len(ent)   # handed out in that order)
+    gone = set()           # (the names retired so far: they resolve no longer; their ids stay theirs)
     edits = []
     for kind, value in args.edits:
         if kind is None:
@@ -109,12 +122,21 @@ def main(argv=None):
                 sys.exit("--add-entity %r: the entity exists" % value)
             ent.append(value)
             edits.append((None, value))
+        elif kind == "retire":
+            if value in ent and value not in gone:
+                retired_id = ent.index(value)
+            elif value not in ent and value.isdigit() and int(value) < len(ent) and ent[int(value)] not in gone:
+                retired_id = int(value)
+            else:
+                sys.exit("--remove-entity %r: unknown entity (or one retired earlier on the command line)" % value)
+            gone.add(ent[retired_id])
+            edits.append(("retire", retired_id))
         else:
-            edits.append((kind, lookup_fact(value, ent, rel)))
+            edits.append((kind, lookup_fact(value, ent, rel, gone)))
     reserve = len(ent) - num_known if args.entity_capacity is None else args.entity_capacity
     if len(ent) > num_known and not reserve:
         sys.exit("--add-entity needs --entity-capacity above 0")
-    nested = resolve(ast.literal_eval(args.query), ent, rel)
+    nested = resolve(ast.literal_eval(args.query), ent, rel, gone)
     dev = torch.device("cuda:0")
     data = udata.load_triples_dir(args.data_root).to(dev)
     cfg = synthetic.default_model_cfg()
@@ -133,6 +155,15 @@ def main(argv=None):
             (new_id,) = qp.add_entities(1).tolist()
             assert ent[new_id] == edits[at][1]
             print("entity %r added as id %d (%d of %d rows in use)" % (edits[at][1], new_id, qp.num_entities, qp.num_slots))
+            at += 1
+            continue
+        if edits[at][0] == "retire":
+            try:
+                (took,) = qp.retire_entities(edits[at][1]).tolist()
+            except ValueError as exc:
+                sys.exit(str(exc))
+            print("entity %r retired: %d fact(s) retracted (%d of %d entities retired)"
+                  % (ent[edits[at][1]], took, qp.num_retired, qp.num_entities))
             at += 1
             continue
         end = at

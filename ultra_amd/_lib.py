@@ -194,6 +194,8 @@ def _load():
     lib.ultra_nonzero_lists.argtypes = [vp, i64, i64, vp, vp, vp, i64, vp]
     # ... over the live ids of rows of n slots: the device pointer to the int64 live count before the stream
     lib.ultra_nonzero_lists_live.argtypes = [vp, i64, i64, vp, vp, vp, i64, vp, vp]
+    # ... without the retired ids: the live count (or None: every slot) and the retired bitmap before the stream
+    lib.ultra_nonzero_lists_alive.argtypes = [vp, i64, i64, vp, vp, vp, i64, vp, vp, vp]
     lib.ultra_beam_search_layer.argtypes =[vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, i64, i32, vp, vp, vp]
     lib.ultra_beam_search_layer_batch.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, i32, vp, vp, vp]
     editsp = ctypes.POINTER(UltraExplainEdits)

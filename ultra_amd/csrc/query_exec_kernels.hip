@@ -1,5 +1,5 @@
 // Compiled execution of complex logical queries (include/ultra_nbfnet.h: ultra_query_segment, ultra_nonzero_lists,
-// ultra_nonzero_lists_live).
+// ultra_nonzero_lists_live, ultra_nonzero_lists_alive).
 //
 // ultra_query_segment: what a batch of UltraQuery stack machines does between two projection calls, as ONE launch.  The host
 // has compiled the batch's postfix queries into a program (ultra_amd/query_exec.py): per sample the depth of its stack on
@@ -34,6 +34,28 @@
 //   Registers      count 11 VGPRs / 20 SGPRs, fill 32 VGPRs / 48 SGPRs (four hit flags, two 64-bit cursors), no scratch, 8 waves a
 //                  SIMD allowed: occupancy is bounded by the grid (one workgroup a row), not by registers.
 // The parent passes n_live == NULL -- every slot is live -- and keeps its results bit for bit.
+//
+// ultra_nonzero_lists_alive: the same two kernels with one more operand, the RETIRED bitmap of a graph that took
+// entities out (id v is bit v & 31 of word v >> 5: live.retired_words, the words the ultra_filtered_*_alive entries read).  An id
+// whose bit is set is left out of the count and of the list, whatever its slot holds (1.0 after a negation, NaN, +inf).
+//   Work split     unchanged: one workgroup of 256 threads per row; the grid, `counts` and `ptr_out` depend on (batch, n) alone
+//                  and the bitmap is read at run time, so a recorded launch serves every later retirement.
+//   Mask word      count: the thread that tests id i loads word i >> 5 -- 32 neighbouring lanes read the same 4 bytes, two
+//                  words a wave.  fill: a thread's four ids start at a multiple of 4 and lie in one word, so one word load per
+//                  thread per tile (a tile starts at a multiple of 1024 and covers 32 whole words; eight lanes share a word).
+//                  The word load is issued BESIDE the value loads -- ahead of them in program order, looked at after them,
+//                  unconditional inside a loop body that is chosen once per workgroup (retired_bits != NULL is the same in
+//                  every thread) -- not inside a branch of the loop: there the compiler waited for the word before it issued
+//                  the value load (§28 measured that at twice the cost).  Plain loads.  A word is loaded only by a thread
+//                  whose first id lies below the clamped live count, and the bit of an id at or beyond it is never looked at
+//                  (the per-id bound comes first).  retired_bits == NULL: the loop bodies of before, word 0 folded away --
+//                  the twin and the parent, the same bits.
+//   Retired slot   its value may be loaded but reaches neither a count nor a list: the bit is ANDed in after the comparison.
+//   LDS / sync     as above: 32 B + 16 B, two barriers per tile; no atomics, no memset node (batch == 0: the one-thread kernel).
+//   Registers      the compiler's resource report of the gfx950 build, both loop bodies in each kernel: count 13 VGPRs / 24
+//                  SGPRs, fill 40 VGPRs / 60 SGPRs (the report's totals, VCC and the reserved pairs included; they replace
+//                  the figures above, which were those of the kernels with one body), 0 bytes of scratch and no spill in
+//                  either, 8 waves a SIMD allowed.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -205,41 +227,52 @@ __device__ __forceinline__ long long nonzero_live(const int64_t *__restrict__ n_
     return v < 0 ? 0 : (v < n ? v : n);
 }
 
+// Is the bit of id v (v & 31) clear in the mask word that covers it?  (word 0: nothing is retired)
+__device__ __forceinline__ bool nonzero_alive(unsigned word, long long v) { return ((word >> (unsigned)(v & 31)) & 1u) == 0u; }
+
+// The non-zero ids of one row below `live` that this thread tests: i = tid, tid + 256, ...  MASKED: the mask word of id i ahead
+// of its value in program order and looked at after it -- both loads unconditional, so they are in flight together.  The branch
+// on retired_bits is taken once, outside the loop (inside it the word was waited for before the value load was issued).
+template <bool MASKED> __device__ __forceinline__ long long nonzero_count_row(const float *__restrict__ row, long long live,
+                                                                             const uint32_t *__restrict__ retired_bits) {
+    long long c = 0;
+    for (long long i = threadIdx.x; i < live; i += NZ_THREADS) {
+        unsigned word = 0u;
+        if (MASKED) word = retired_bits[i >> 5];        // (i < live <= n: a word of the bitmap)
+        const float v = row[i];
+        c += is_nonzero(v) && nonzero_alive(word, i) ? 1 : 0;
+    }
+    return c;
+}
+
 __global__ void __launch_bounds__(NZ_THREADS) nonzero_count_kernel(const float *__restrict__ x, long long n, int64_t *__restrict__ counts,
-                                                                   const int64_t *__restrict__ n_live) {
+                                                                   const int64_t *__restrict__ n_live,
+                                                                   const uint32_t *__restrict__ retired_bits) {
     __shared__ long long wave_total[NZ_THREADS / 64];
     const float *row = x + (long long)blockIdx.x * n;
     const long long live = nonzero_live(n_live, n);
-    long long c = 0;
-    for (long long i = threadIdx.x; i < live; i += NZ_THREADS) c += is_nonzero(row[i]) ? 1 : 0;
+    long long c = retired_bits ? nonzero_count_row<true>(row, live, retired_bits) : nonzero_count_row<false>(row, live, nullptr);
     c = block_sum(c, wave_total);
     if (threadIdx.x == 0) counts[blockIdx.x] = c;
 }
 
-__global__ void __launch_bounds__(NZ_THREADS) nonzero_fill_kernel(const float *__restrict__ x, long long n, const int64_t *__restrict__ counts,
-                                                                  int64_t *__restrict__ ptr_out, int64_t *__restrict__ index_out,
-                                                                  const int64_t *__restrict__ n_live) {
-    __shared__ long long wave_total[NZ_THREADS / 64];
-    __shared__ int wave_count[NZ_THREADS / 64];
-    const long long b = blockIdx.x;
-    const long long live = nonzero_live(n_live, n);
+// The ordered compaction of one row's live ids into index_out from `at` on, tile by tile.  MASKED: one mask word per thread per
+// tile -- its four ids start at a multiple of 4 and lie in one word -- issued ahead of the values and looked at after them; a
+// thread whose first id is not live loads none.
+template <bool MASKED> __device__ __forceinline__ void nonzero_fill_row(const float *__restrict__ row, long long live, long long at,
+                                                                        int64_t *__restrict__ index_out,
+                                                                        const uint32_t *__restrict__ retired_bits, int *wave_count) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    long long before = 0;
-    for (long long r = tid; r < b; r += NZ_THREADS) before += counts[r];
-    long long at = block_sum(before, wave_total);       // where this row's list starts
-    if (tid == 0) {
-        if (b == 0) ptr_out[0] = 0;
-        ptr_out[b + 1] = at + counts[b];
-    }
-    const float *row = x + b * n;
     for (long long lo = 0; lo < live; lo += NZ_TILE) {
         // thread t owns NZ_PER_THREAD consecutive ids: the order of the ids is the order of (thread, slot)
         const long long first = lo + (long long)tid * NZ_PER_THREAD;
+        unsigned word = 0u;
+        if (MASKED && first < live) word = retired_bits[first >> 5];
         bool hit[NZ_PER_THREAD];
         int mine = 0;
 #pragma unroll
         for (int j = 0; j < NZ_PER_THREAD; ++j) {
-            hit[j] = first + j < live && is_nonzero(row[first + j]);
+            hit[j] = first + j < live && is_nonzero(row[first + j]) && nonzero_alive(word, first + j);
             mine += hit[j] ? 1 : 0;
         }
         int incl = mine;
@@ -261,6 +294,29 @@ __global__ void __launch_bounds__(NZ_THREADS) nonzero_fill_kernel(const float *_
         at += tile_total;
         __syncthreads();        // (wave_count is rewritten by the next tile)
     }
+}
+
+__global__ void __launch_bounds__(NZ_THREADS) nonzero_fill_kernel(const float *__restrict__ x, long long n, const int64_t *__restrict__ counts,
+                                                                  int64_t *__restrict__ ptr_out, int64_t *__restrict__ index_out,
+                                                                  const int64_t *__restrict__ n_live,
+                                                                  const uint32_t *__restrict__ retired_bits) {
+    __shared__ long long wave_total[NZ_THREADS / 64];
+    __shared__ int wave_count[NZ_THREADS / 64];
+    const long long b = blockIdx.x;
+    const long long live = nonzero_live(n_live, n);
+    const int tid = threadIdx.x;
+    long long before = 0;
+    for (long long r = tid; r < b; r += NZ_THREADS) before += counts[r];
+    const long long at = block_sum(before, wave_total);       // where this row's list starts
+    if (tid == 0) {
+        if (b == 0) ptr_out[0] = 0;
+        ptr_out[b + 1] = at + counts[b];
+    }
+    const float *row = x + b * n;
+    if (retired_bits)       // (the same in every thread)
+        nonzero_fill_row<true>(row, live, at, index_out, retired_bits, wave_count);
+    else
+        nonzero_fill_row<false>(row, live, at, index_out, nullptr, wave_count);
 }
 
 // ptr_out of an empty batch, without a memset node
@@ -321,16 +377,23 @@ extern "C" int32_t ultra_query_segment(const int32_t *entry_depth, const int32_t
     return ULTRA_OK;
 }
 
-// Both entries: `who` names the caller in the messages; n_live == NULL: every slot is live (the parent).
-static int32_t nonzero_lists_impl(const char *who, bool twin, const void *x, int64_t batch, int64_t n, int64_t *counts,
-                                  int64_t *ptr_out, int64_t *index_out, int64_t capacity, const int64_t *n_live, void *stream) {
+// The three entries: `who` names the caller in the messages; n_live == NULL: every slot is live (the parent, and _alive on a
+// graph without a reserve); retired_bits == NULL: no id is retired (the parent and the _live twin).
+enum { NZ_PARENT = 0, NZ_LIVE = 1, NZ_ALIVE = 2 };
+static int32_t nonzero_lists_impl(const char *who, int entry, const void *x, int64_t batch, int64_t n, int64_t *counts,
+                                  int64_t *ptr_out, int64_t *index_out, int64_t capacity, const int64_t *n_live,
+                                  const uint32_t *retired_bits, void *stream) {
     const std::string name(who);
     if (n >= (int64_t)1 << 31 || batch >= (int64_t)1 << 31) {
         ultra::set_error(name + ": batch and n must stay below 2^31");
         return ULTRA_ERR_UNSUPPORTED;
     }
-    if (twin && !n_live) {
+    if (entry == NZ_LIVE && !n_live) {
         ultra::set_error(name + ": n_live is NULL");
+        return ULTRA_ERR_INVALID;
+    }
+    if (entry == NZ_ALIVE && !retired_bits) {
+        ultra::set_error(name + ": retired_bits is NULL");
         return ULTRA_ERR_INVALID;
     }
     if (!ptr_out || batch < 0 || n < 0 || (batch > 0 && (!counts || (n > 0 && (!x || !index_out))))) {
@@ -346,7 +409,7 @@ static int32_t nonzero_lists_impl(const char *who, bool twin, const void *x, int
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     (void)hipGetLastError();
     if (batch == 0) {       // ptr_out = [0]
-        if (twin) {
+        if (entry != NZ_PARENT) {
             hipLaunchKernelGGL(ultra::nonzero_empty_kernel, dim3(1), dim3(1), 0, s, ptr_out);
             if (hipGetLastError() != hipSuccess) {
                 ultra::set_error("nonzero_empty_kernel launch failed");
@@ -359,13 +422,13 @@ static int32_t nonzero_lists_impl(const char *who, bool twin, const void *x, int
         return ULTRA_OK;
     }
     hipLaunchKernelGGL(ultra::nonzero_count_kernel, dim3((unsigned)batch), dim3(ultra::NZ_THREADS), 0, s, (const float *)x,
-                       (long long)n, counts, n_live);
+                       (long long)n, counts, n_live, retired_bits);
     if (hipGetLastError() != hipSuccess) {
         ultra::set_error("nonzero_count_kernel launch failed");
         return ULTRA_ERR_HIP;
     }
     hipLaunchKernelGGL(ultra::nonzero_fill_kernel, dim3((unsigned)batch), dim3(ultra::NZ_THREADS), 0, s, (const float *)x,
-                       (long long)n, (const int64_t *)counts, ptr_out, index_out, n_live);
+                       (long long)n, (const int64_t *)counts, ptr_out, index_out, n_live, retired_bits);
     if (hipGetLastError() != hipSuccess) {
         ultra::set_error("nonzero_fill_kernel launch failed");
         return ULTRA_ERR_HIP;
@@ -375,10 +438,19 @@ static int32_t nonzero_lists_impl(const char *who, bool twin, const void *x, int
 
 extern "C" int32_t ultra_nonzero_lists(const void *x, int64_t batch, int64_t n, int64_t *counts, int64_t *ptr_out,
                                        int64_t *index_out, int64_t capacity, void *stream) {
-    return nonzero_lists_impl("ultra_nonzero_lists", false, x, batch, n, counts, ptr_out, index_out, capacity, nullptr, stream);
+    return nonzero_lists_impl("ultra_nonzero_lists", NZ_PARENT, x, batch, n, counts, ptr_out, index_out, capacity, nullptr, nullptr,
+                              stream);
 }
 
 extern "C" int32_t ultra_nonzero_lists_live(const void *x, int64_t batch, int64_t n, int64_t *counts, int64_t *ptr_out,
                                             int64_t *index_out, int64_t capacity, const int64_t *n_live, void *stream) {
-    return nonzero_lists_impl("ultra_nonzero_lists_live", true, x, batch, n, counts, ptr_out, index_out, capacity, n_live, stream);
+    return nonzero_lists_impl("ultra_nonzero_lists_live", NZ_LIVE, x, batch, n, counts, ptr_out, index_out, capacity, n_live,
+                              nullptr, stream);
+}
+
+extern "C" int32_t ultra_nonzero_lists_alive(const void *x, int64_t batch, int64_t n, int64_t *counts, int64_t *ptr_out,
+                                             int64_t *index_out, int64_t capacity, const int64_t *n_live,
+                                             const uint32_t *retired_bits, void *stream) {
+    return nonzero_lists_impl("ultra_nonzero_lists_alive", NZ_ALIVE, x, batch, n, counts, ptr_out, index_out, capacity, n_live,
+                              retired_bits, stream);
 }

@@ -740,6 +740,8 @@ class Predictor(object):
         self._relation_graph_edited(before)
         return out
 
+    retire_entities = remove_entities       # (the one spelling QueryPredictor has too: DESIGN.md §29, "The name")
+
     def _relation_graph_state(self):
         rg = None if self.delta is None else self.delta.relation_graph
         return (rg, getattr(rg, "version", None))

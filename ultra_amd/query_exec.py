@@ -15,7 +15,8 @@ the queries are known on the host before anything runs, so the interpreter's who
                    `model.symbolic_model` per projection, and no call that waits for the device
   nonzero_lists    the non-zero ids of every row of a (batch, n) matrix as ragged ascending lists (ultra_nonzero_lists): the
                    layout ultra_filtered_topk takes for the entities to leave out; num_live: over the live ids of a graph
-                   with reserved rows (ultra_nonzero_lists_live)
+                   with reserved rows (ultra_nonzero_lists_live); retired: without the ids of a device
+                   bitmap (ultra_nonzero_lists_alive)
 
 The compiled route computes exactly what the interpreter computes: the same fuzzy-set arithmetic operation for operation,
 the same projection calls with the same inputs in the same order.  It keeps what a caller of `forward` gets -- the logits
@@ -108,12 +109,13 @@ def _kind(word, row):
     return flags
 
 
-def compile(query, num_nodes, num_relations, stack_size=UltraQuery.stack_size, num_live=None):
+def compile(query, num_nodes, num_relations, stack_size=UltraQuery.stack_size, num_live=None, retired=None):
     """The `Program` of a (batch, L) int64 batch of postfix queries (a `Query` or a tensor; a CUDA tensor is copied to the
     host once).  Raises ValueError for everything `UltraQuery.forward` would refuse, or fault on, while it runs: stack
     overflow and underflow, more than one value left, nothing left, a row without `stop`, an entity id outside
     [0, num_nodes), a relation id outside [0, num_relations).  num_live (a graph with reserved rows, DESIGN.md section 21:
-    num_nodes counts slots): the anchors are the ids below it; None: below num_nodes."""
+    num_nodes counts slots): the anchors are the ids below it; None: below num_nodes.  retired (a collection of ids, DESIGN.md
+    section 29: the entities a served graph retired): an anchor among them is a ValueError too."""
     q = torch.as_tensor(query)
     if q.dim() != 2 or q.dtype != torch.int64:
         raise ValueError("compile takes a (batch, L) int64 batch of postfix queries, got %s %s" % (tuple(q.shape), q.dtype))
@@ -123,6 +125,11 @@ def compile(query, num_nodes, num_relations, stack_size=UltraQuery.stack_size, n
     num_live = num_nodes if num_live is None else int(num_live)
     if not 0 <= num_live <= num_nodes:
         raise ValueError("num_live must lie in [0, num_nodes = %d], got %d" % (num_nodes, num_live))
+    if retired is None:
+        retired = ()
+    elif torch.is_tensor(retired):
+        retired = retired.detach().as_subclass(torch.Tensor).flatten().cpu().tolist()
+    retired = frozenset(int(v) for v in retired)
     payload = ~Query.operation
     ip, depth = [0] * batch, [0] * batch
     segments, projections = [], []
@@ -142,6 +149,8 @@ def compile(query, num_nodes, num_relations, stack_size=UltraQuery.stack_size, n
                     raise ValueError(_OVERFLOW % stack_size)
                 if not 0 <= word[b] < num_live:
                     raise ValueError("query %d: entity id %d outside [0, %d)" % (b, word[b], num_live))
+                if word[b] in retired:
+                    raise ValueError("query %d: entity id %d was retired and is no anchor" % (b, word[b]))
                 ops[b].append((PUSH_ENTITY, word[b]))
                 depth[b] += 1
             elif kind[b] == Query.negation:
@@ -257,12 +266,30 @@ def segment(words, offset, batch, num_nodes, logic, stack, push_src, pop_dst, sy
         _lib.stream_of(stack)))
 
 
-def nonzero_lists(x, num_live=None):
+def _retired_bits(retired, n, dev):
+    """`retired` of nonzero_lists: the device bitmap -- int32 or uint32, at least ceil(n / 32) words (live.retired_words), on
+    `dev` -- or the pair (bits, count) as LiveGraph.retired_operand holds it, of which the bitmap is used."""
+    bits = retired
+    if isinstance(retired, (tuple, list)) and len(retired) == 2:
+        bits = retired[0]
+    if not (torch.is_tensor(bits) and bits.dim() == 1 and bits.is_contiguous() and bits.dtype in (torch.int32, torch.uint32)
+            and bits.numel() >= (n + 31) // 32 and bits.device == dev):
+        raise ValueError("`retired` is the bitmap on the matrix's device -- at least ceil(n / 32) = %d int32 or uint32 words -- "
+                         "or the pair (bits, count) that holds it" % ((n + 31) // 32))
+    return bits
+
+
+def nonzero_lists(x, num_live=None, retired=None):
     """(ptr (batch + 1) int64, index int64): per row of x (batch, n) fp32 on the GPU the ids v with x[b, v] != 0, ascending
     (NaN counts, -0.0 does not).  `index` has room for batch * n ids; the first ptr[-1] are filled.  No host wait.
     num_live (rows of n SLOTS of which the first num_live are entities in use): ultra_nonzero_lists_live on the full rows -- no
     slice, no copy; a dead slot is never read.  One int64 on x's device is handed to the kernels as it is (they clamp it to
-    [0, n]); an int is checked against [0, n] on the host and uploaded.  None: ultra_nonzero_lists."""
+    [0, n]); an int is checked against [0, n] on the host and uploaded.  None: ultra_nonzero_lists.
+    retired (the device bitmap of a graph that retired entities -- id v is bit v & 31 of word v >> 5, live.retired_words -- or
+    the pair (bits, count) of LiveGraph.retired_operand): ultra_nonzero_lists_alive, the lists without those ids, with num_live
+    or without it (every slot is below the bound).  The bitmap is read by the kernels, not on the host."""
+    # (the operand's own rules first, against x as it is: they hold wherever x lives)
+    bits = None if retired is None or x.dim() != 2 else _retired_bits(retired, x.shape[1], x.device)
     if not x.is_cuda:
         raise RuntimeError("ultra_amd.query_exec.nonzero_lists: expected a GPU tensor; the MI355X engine has no CPU path")
     if x.dim() != 2 or x.dtype != torch.float32:
@@ -272,11 +299,13 @@ def nonzero_lists(x, num_live=None):
     ptr = torch.empty(batch + 1, dtype=torch.int64, device=x.device)
     index = torch.empty(max(1, batch * n), dtype=torch.int64, device=x.device)
     counts = torch.empty(max(1, batch), dtype=torch.int64, device=x.device)
-    if num_live is None:
+    if num_live is None and bits is None:
         _lib.check(_lib.lib.ultra_nonzero_lists(x.data_ptr(), batch, n, counts.data_ptr(), ptr.data_ptr(), index.data_ptr(),
                                                 batch * n, _lib.stream_of(x)))
         return ptr, index
-    if torch.is_tensor(num_live):
+    if num_live is None:
+        live = None
+    elif torch.is_tensor(num_live):
         if num_live.numel() != 1 or num_live.dtype != torch.long or num_live.device != x.device:
             raise ValueError("a tensor `num_live` is one int64 on the matrix's device")
         live = num_live      # (referenced until the launch is enqueued)
@@ -284,6 +313,11 @@ def nonzero_lists(x, num_live=None):
         if isinstance(num_live, bool) or not 0 <= int(num_live) <= n:
             raise ValueError("num_live must lie in [0, %d] (the slots of a row), got %r" % (n, num_live))
         live = torch.tensor(int(num_live), dtype=torch.long, device=x.device)
+    if bits is not None:
+        _lib.check(_lib.lib.ultra_nonzero_lists_alive(x.data_ptr(), batch, n, counts.data_ptr(), ptr.data_ptr(), index.data_ptr(),
+                                                      batch * n, None if live is None else live.data_ptr(), bits.data_ptr(),
+                                                      _lib.stream_of(x)))
+        return ptr, index
     _lib.check(_lib.lib.ultra_nonzero_lists_live(x.data_ptr(), batch, n, counts.data_ptr(), ptr.data_ptr(), index.data_ptr(),
                                                  batch * n, live.data_ptr(), _lib.stream_of(x)))
     return ptr, index

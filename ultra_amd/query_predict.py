@@ -18,6 +18,12 @@ A GROWING graph: QueryPredictor(entity_capacity=M) reserves M r
 (`add_entities`), as predict.Predictor does (§19).  The final symbolic sets are then listed over the LIVE ids
 (ultra_nonzero_lists_live: after a negation every reserved slot holds 1.0) and the selection runs over them
 (ultra_filtered_topk_live / ultra_filtered_above_live).
+
+RETIRED entities: `retire_entities` takes entities out of the served graph as predict.Predictor.remove_entities
+does (§28) -- their facts retracted, their ids never a candidate, an entailed answer or an anchor again.  From the first
+retirement on the lists leave the ids of the device bitmap out (ultra_nonzero_lists_alive: after a negation a retired slot holds
+1.0 in the middle of the id range) and the selection runs over the alive ids (ultra_filtered_topk_alive /
+ultra_filtered_above_alive).
 """
 import contextlib
 
@@ -38,7 +44,14 @@ class QueryPredictor(object):
     (`live_count`, the same tensor for the predictor's life) that the list and selection kernels read.  The new ids are heads,
     tails and anchors from then on; an id in [num_entities, slots) is a ValueError everywhere and never an answer.  Every result
     is that of a fresh QueryPredictor(entity_capacity=0) on `materialized()`.  entity_capacity=0 (the default): `graph` itself is
-    served, by exactly the entry points of before, and add_entities raises."""
+    served, by exactly the entry points of before, and add_entities raises.
+
+    retire_entities(ids) (LiveGraph.remove_entities, §28): with or without a reserve.  Every result is then that
+    of a fresh QueryPredictor on `materialized()` -- which keeps the id space, the retired ids isolated nodes named by its
+    `retired_entities` -- with the retired ids taken out of the candidates and of the entailed lists.  A retired slot of an
+    intermediate fuzzy or symbolic set is left as the logic leaves it: nothing is zeroed on the way, so every score keeps the
+    bits of the fresh predictor's.  Until the first retirement every call reaches exactly the entries it reached before.  (The
+    method is not called remove_entities: see DESIGN.md §29, "The name".)"""
 
     def __init__(self, model, graph, k=10, batch_size=16, filtered=True, logic=None, delta_capacity=256, entity_capacity=0):
         predict.check_k(k)
@@ -61,6 +74,8 @@ class QueryPredictor(object):
     num_entities = forwarded("num_entities")
     num_slots = forwarded("num_slots")
     live_count = forwarded("live_count")
+    num_retired = forwarded("num_retired")
+    retired_entities = forwarded("retired_entities")
 
     # ---- the growing graph (the rules of Predictor.add_entities) ----
     def add_entities(self, count=1):
@@ -71,6 +86,15 @@ class QueryPredictor(object):
         the graph is compacted and num_entities + count + entity_capacity slots are laid out: one rebuild.  ValueError on a
         predictor without a reserve (entity_capacity=0)."""
         return self._live.add_entities(count, compact=self.compact)
+
+    # ---- retiring entities (the rules of Predictor.remove_entities) ----
+    def retire_entities(self, ids):
+        """Retire the entities `ids` -- an int or a vector of distinct ids in use, none retired before (ValueError otherwise, and
+        nothing is changed): every fact that names one as head or tail is retracted (remove_facts: tombstones, the delta) and
+        the ids are never an answer, an entailed answer, a candidate that is counted, an anchor or an argument of an edit again
+        (LiveGraph.remove_entities).  Ids are not renumbered and a slot is not handed out again; the set survives compact() and
+        a rebuild beyond the reserve.  Returns an int64 vector: per id the number of distinct facts retracted."""
+        return self._live.remove_entities(ids)
 
     # ---- the live graph (the rules of Predictor.add_facts / remove_facts) ----
     def add_facts(self, h, r, t):
@@ -97,8 +121,9 @@ class QueryPredictor(object):
     def materialized(self):
         """The graph a fresh QueryPredictor would be given for the same answers: the served edge list with the delta's edits and
         the delta's relation graph (GraphDelta.materialize); the served graph itself where no edit is held.  With a reserve:
-        num_nodes = num_entities -- no reserved row -- and a new copy at every call."""
-        if self.entity_capacity:
+        num_nodes = num_entities -- no reserved row -- and a new copy at every call.  Once an entity was retired, with a reserve
+        or without: LiveGraph.materialized() too -- the copy keeps the id space and names `retired_entities`."""
+        if self.entity_capacity or self.num_retired:
             return self._live.materialized()
         delta = self.delta
         return self.graph if delta is None or not delta.edited else delta.materialize(self.graph)
@@ -108,10 +133,15 @@ class QueryPredictor(object):
         return {"delta": delta} if delta is not None and delta.edited else {}
 
     def _known_reference(self, sym, rows):
-        """(ptr, index) of the final symbolic sets in plain torch (the CPU route): the non-zero LIVE ids of every row."""
+        """(ptr, index) of the final symbolic sets in plain torch (the CPU route): the non-zero LIVE ids of every row that are
+        not retired (after a negation a retired slot holds 1.0)."""
         if self.entity_capacity:
             sym = sym[:, :self.num_entities]
-        sample, known = (sym != 0).nonzero().t()
+        listed = sym != 0
+        if self.num_retired:
+            retired = self.retired_entities.to(sym.device)
+            listed[:, retired[retired < sym.shape[1]]] = False
+        sample, known = listed.nonzero().t()
         return torch.searchsorted(sample.contiguous(), torch.arange(rows + 1)), known
 
     def _rows(self, queries):
@@ -125,12 +155,15 @@ class QueryPredictor(object):
 
     def _programs(self, queries):
         """[(indices, Program)] of the batches of `answers`.  With a reserve the programs are compiled against the slot count
-        (the served graph's num_nodes) and an anchor in [num_entities, slots) is a ValueError."""
+        (the served graph's num_nodes) and an anchor in [num_entities, slots) is a ValueError; a retired anchor is one too."""
         rows = self._rows(queries)
         n, r = self.graph.num_nodes, self.graph.num_relations
         compile = query_exec.compile
-        if self.entity_capacity:
-            compile = lambda q, n, r: query_exec.compile(q, n, r, num_live=self.num_entities)
+        if self.entity_capacity or self.num_retired:
+            live = {"num_live": self.num_entities} if self.entity_capacity else {}
+            if self.num_retired:
+                live["retired"] = frozenset(self.retired_entities.tolist())
+            compile = lambda q, n, r: query_exec.compile(q, n, r, **live)
         groups = {}
         for i, row in enumerate(rows):
             single = compile(torch.tensor([row], dtype=torch.long), n, r)
@@ -153,14 +186,15 @@ class QueryPredictor(object):
         """The batches of `plan` (_programs) as answers and answer_sets run them: inside the block the model is in eval mode
         under this predictor's logic (both restored on the way out), and the value is an iterator of (index, logits, ptr, known,
         live) -- the batch's query indices, its logits from the compiled executor, the lists of its entailed answers (None, None
-        unless filtered) and the live-count kwargs of the selection."""
+        unless filtered) and the kwargs of the selection: the live count and, once an entity was retired, the retired set
+        (LiveGraph.selection_for) -- the lists take the same two."""
         graph, live_graph, delta_kwargs = self.graph, self._live, self._delta_kwargs()
 
         def run():
             for index, program in plan:
                 logits, sym = query_exec.execute(self.model, graph, program, symbolic_traversal=self.filtered,
                                                  executor=self._executor, **delta_kwargs)
-                live = live_graph.num_live_for(logits.is_cuda)
+                live = live_graph.selection_for(logits.is_cuda)
                 ptr = known = None
                 if self.filtered:
                     ptr, known = query_exec.nonzero_lists(sym, **live) if logits.is_cuda else self._known_reference(sym, len(index))
