@@ -15,6 +15,7 @@
 //     l = binary_cross_entropy_with_logits(pred, target);  w = 1 / num_pos on positives,
 //     softmax(pred_neg / T) over the negatives (T > 0, a constant) or 1 / num_neg (T == 0)
 //     loss = mean_b( sum_i l w / sum_i w );   grad = w (sigmoid(pred) - target) / (sum_i w * rows)
+//   (exp(x / T - max) with the argument's rounding errors carried along: exp_arg.hpp)
 //   One workgroup per row; every sum runs in a fixed order (per-thread strides, then an LDS tree).  The last workgroup to
 //   finish (a counter in the workspace, reset by that workgroup) averages the row losses in row order: reproducible.
 #include <hip/hip_runtime.h>
@@ -25,6 +26,7 @@
 #include "../../include/ultra_nbfnet.h"
 #include "plan.hpp"
 #include "device_scope.hpp"
+#include "exp_arg.hpp"
 
 namespace ultra {
 
@@ -129,10 +131,11 @@ __global__ void __launch_bounds__(QLOSS_THREADS) query_loss_kernel(const float *
     float *g = grad + (long long)b * n;
     const int tid = threadIdx.x;
 
+    const float inv_t = temperature > 0.f ? 1.f / temperature : 0.f;      // (pred / T as a product: exp_arg.hpp)
     float npos = 0.f, mx = -__builtin_inff();
     for (long long i = tid; i < n; i += QLOSS_THREADS) {
         if (y[i]) npos += 1.f;
-        else if (temperature > 0.f) mx = fmaxf(mx, p[i] / temperature);
+        else if (temperature > 0.f) mx = fmaxf(mx, p[i] * inv_t);
     }
     npos = block_sum(npos, red);
     const float nneg = (float)n - npos;
@@ -141,14 +144,14 @@ __global__ void __launch_bounds__(QLOSS_THREADS) query_loss_kernel(const float *
         mx = block_max(mx, red);
         float s = 0.f;
         for (long long i = tid; i < n; i += QLOSS_THREADS)
-            if (!y[i]) s += expf(p[i] / temperature - mx);
+            if (!y[i]) s += exp_scaled_minus(p[i], inv_t, mx);
         z = block_sum(s, red);
     }
     const float wpos = 1.f / npos, wneg = 1.f / nneg;
     float lw = 0.f, ws = 0.f;
     for (long long i = tid; i < n; i += QLOSS_THREADS) {
         const float x = p[i], t = y[i] ? 1.f : 0.f;
-        const float w = y[i] ? wpos : (temperature > 0.f ? expf(x / temperature - mx) / z : wneg);
+        const float w = y[i] ? wpos : (temperature > 0.f ? exp_scaled_minus(x, inv_t, mx) / z : wneg);
         // (1 - t) x - log_sigmoid(x),  log_sigmoid(x) = min(x, 0) - log1p(exp(-|x|))
         const float l = (1.f - t) * x - (fminf(x, 0.f) - log1pf(expf(-fabsf(x))));
         lw += l * w;
@@ -159,7 +162,7 @@ __global__ void __launch_bounds__(QLOSS_THREADS) query_loss_kernel(const float *
     const float scale = 1.f / (ws * (float)rows);
     for (long long i = tid; i < n; i += QLOSS_THREADS) {
         const float x = p[i], t = y[i] ? 1.f : 0.f;
-        const float w = y[i] ? wpos : (temperature > 0.f ? expf(x / temperature - mx) / z : wneg);
+        const float w = y[i] ? wpos : (temperature > 0.f ? exp_scaled_minus(x, inv_t, mx) / z : wneg);
         const float sig = 1.f / (1.f + expf(-x));
         g[i] = w * (sig - t) * scale;
     }
