@@ -91,12 +91,29 @@ def above_lists(out):
 
 
 def rank_call(pred, pos, ptr, index, n_live=None, retired=None):
-    rank, neg = torch.full_like(pos, -7), torch.full_like(pos, -7)
-    args = (pred.data_ptr(), pos.data_ptr(), ptr.data_ptr(), index.data_ptr(), pred.shape[0], pred.shape[1], rank.data_ptr(),
-            neg.data_ptr())
-    predict._select("ultra_filtered_rank", args, n_live, pred.device, retired)
+    rank, neg = predict.filtered_rank(pred, pos, ptr, index, num_live=n_live, retired=retired,
+                                      out=(torch.full_like(pos, -7), torch.full_like(pos, -7)))
     torch.cuda.synchronize()
     return rank, neg
+
+
+@pytest.mark.parametrize("n_cand", (70, 4101))
+def test_filtered_rank_equals_its_restatement(dev, scores, n_cand):
+    """predict.filtered_rank, the wrapper of the three rank entries: without operands, with a live count, with a retired set --
+    rank and num_negative bit for bit; `out=` is written and handed back; a CPU tensor is the RuntimeError of the other wrappers."""
+    pred = scores[:, :n_cand].contiguous()
+    for live, gone in ((None, None), (n_cand - 7, None), (None, [31, 32])):
+        pos, ptr, index = lists(n_cand if live is None else live, dev)[1]
+        kw = {} if live is None else {"num_live": live}
+        want = predict.filtered_rank_reference(pred, pos, ptr, index, **kw,
+                                               **({} if gone is None else {"retired": torch.tensor(gone, device=dev)}))
+        retired = None if gone is None else operands(gone, n_cand, dev)
+        assert same(predict.filtered_rank(pred, pos, ptr, index, retired=retired, **kw), want), (live, gone)
+        out = torch.full_like(pos, -7), torch.full_like(pos, -7)
+        got = predict.filtered_rank(pred, pos, ptr, index, retired=retired, out=out, **kw)
+        assert got[0] is out[0] and got[1] is out[1] and same(out, want), (live, gone)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        predict.filtered_rank(pred.cpu(), pos.cpu(), ptr.cpu(), index.cpu())
 
 
 @pytest.mark.parametrize("reserve", [0, 7], ids=["no_n_live", "n_live"])

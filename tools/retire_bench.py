@@ -194,7 +194,7 @@ def shape_case(name, k, bs, reps, warmup, fact_reps, dev):
         assert live.delta.num_removed > 0 and live.num_retired == count
         holders.append(live)
         known = predict.known_answers(live.filter_graph, h, r, "tail")
-        for key, retired in (("retired_%d" % count, live._retired()), ("tombstones_%d" % count, None)):
+        for key, retired in (("retired_%d" % count, live._live.retired_operand), ("tombstones_%d" % count, None)):
             steps[key] = predict._GraphedPredictStep(model, live.data, bs, k, "tail", 1 << 16, delta=live.delta, retired=retired)
             lists[key] = known
         out["retired_%d" % count] = dict(facts=facts, tombstone_keys=live.delta.num_removed, touched_rows=int(live.delta.count),

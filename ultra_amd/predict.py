@@ -6,6 +6,7 @@ and relation, leaving out the ones the graph already states?
 
   filtered_topk_reference   the semantics in plain torch, on any device -- the definition the kernel is tested against
   filtered_topk             csrc/topk_kernels.hip (ultra_filtered_topk): no (batch, N) mask, no clone of the scores
+  filtered_rank             csrc/rank_kernels.hip (ultra_filtered_rank): the rank of a positive among a row's candidates
   filtered_above_reference  the answer SET of a row -- every candidate above a threshold, ranked -- in plain torch
   filtered_above            csrc/above_kernels.hip (ultra_filtered_above): the length of the lists is decided on the device
   logit_threshold           the logit threshold of a probability
@@ -20,77 +21,29 @@ Order: score descending, equal scores by ascending id, every Na
 -- the stable descending torch.sort.  A filtered candidate is removed, not rescored: a genuine -inf score is a candidate
 like any other, ranked last.  Slots beyond count = min(k, N - |known|) hold id -1 and score -inf.
 
-A GROWING graph: Predictor(entity_capacity=M) reserves M rows for entities that arrive later
-(Predictor.add_entities); the selection then runs over the LIVE ids of rows of N + M slots -- `num_live` of filtered_topk /
-filtered_above and their restatements, the ultra_filtered_*_live entries.
-
-RETIRED entities: Predictor.remove_entities(ids) retracts every fact of an entity and takes its id out of the
-candidate set for good -- `retired` of filtered_topk / filtered_above / filtered_rank_reference and their restatements, the
-ultra_filtered_*_alive entries.
+A GROWING graph and RETIRED entities: Predictor(entity_capacity=M) reserves rows for entities
+that arrive later and Predictor.remove_entities(ids) takes ids out of the candidate set for good -- `num_live` and `retired` of
+every function here.  What the two operands are and which entry takes them: ultra_amd/selection.py.
 """
 
+import contextlib
 import functools
 import inspect
 import math
 
 import torch
 
-from . import _lib, dense, models, tasks
+from . import _lib, dense, models, selection, tasks
 from .graph import Capture, param_state
 from .live import LiveGraph, check_live, check_live_relations, check_not_retired, forwarded
 
-
-def _live_int(num_live, n):
-    """`num_live` (an int, or a one-element integer tensor) as an int in [1, n] (ValueError otherwise)."""
-    live = int(num_live)
-    if not 1 <= live <= n:
-        raise ValueError("num_live must lie in [1, %d] (the slots of a row), got %d" % (n, live))
-    return live
-
-
-def _live_operand(num_live, n, dev):
-    """`num_live` as the device int64 the _live entries read: a one-element int64 tensor on `dev` is passed as it is (its value is
-    not looked at on the host -- the kernels clamp it), an int is checked against [1, n] and uploaded."""
-    if torch.is_tensor(num_live):
-        if num_live.numel() != 1 or num_live.dtype != torch.long or num_live.device != dev:
-            raise ValueError("a tensor `num_live` is one int64 on the scores' device")
-        return num_live
-    return torch.tensor(_live_int(num_live, n), dtype=torch.long, device=dev)
-
-
-def _select(entry, args, n_live, dev, retired=None):
-    """One launch of a selection entry on `dev`'s stream: `entry` without a live count, its `_live` twin with the device scalar
-    `n_live` appended to the same arguments; with `retired` -- the device pair (bitmap, count) -- its `_alive` twin with the live
-    count (or NULL: every slot), the bitmap and the count appended.  The entry is looked up when it is called."""
-    if retired is not None:
-        _lib.check(getattr(_lib.lib, entry + "_alive")(*args, None if n_live is None else n_live.data_ptr(), retired[0].data_ptr(),
-                                                       retired[1].data_ptr(), _lib.stream_of(dev)))
-    elif n_live is None:
-        _lib.check(getattr(_lib.lib, entry)(*args, _lib.stream_of(dev)))
-    else:
-        _lib.check(getattr(_lib.lib, entry + "_live")(*args, n_live.data_ptr(), _lib.stream_of(dev)))
-
-
-def _retired_operand(retired, n, dev):
-    """`retired` of the kernels' wrappers: the pair (bits, count) on `dev` -- bits at least ceil(n / 32) 32-bit words (int32 or
-    uint32: live.retired_words), count one int64 -- as it is (neither is looked at on the host)."""
-    try:
-        bits, count = retired
-        ok = (torch.is_tensor(bits) and torch.is_tensor(count) and bits.dim() == 1 and bits.is_contiguous()
-              and bits.dtype in (torch.int32, torch.uint32) and bits.numel() >= (n + 31) // 32 and bits.device == dev
-              and count.numel() == 1 and count.dtype == torch.long and count.device == dev)
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError("`retired` is the pair (bits, count) on the scores' device: at least ceil(N / 32) = %d 32-bit words "
-                         "and one int64 (the sorted id vector is the _reference functions' form)" % ((n + 31) // 32))
-    return bits, count
+_select = selection.launch      # (the dispatcher, under the name and with the arguments it is called by here)
 
 
 def _alive_columns(pred, retired, num_live, index=None):
     """The _reference functions with `retired` (a sorted int64 id vector): (pred with the columns at or beyond num_live and the
     retired columns deleted, the ids of the columns kept, `index` -- ids that are alive -- as positions among them)."""
-    n = pred.shape[1] if num_live is None else _live_int(num_live, pred.shape[1])
+    n = pred.shape[1] if num_live is None else selection.live_int(num_live, pred.shape[1])
     keep = torch.ones(n, dtype=torch.bool, device=pred.device)
     retired = torch.as_tensor(retired, dtype=torch.long, device=pred.device).flatten()
     keep[retired[retired < n]] = False
@@ -113,7 +66,7 @@ def filtered_rank_reference(pred, pos, ptr, index, num_live=None, retired=None):
         alive, cols, index = _alive_columns(pred, retired, num_live, index)
         return filtered_rank_reference(alive, _alive_columns(pred, retired, num_live, pos)[2], ptr, index)
     if num_live is not None:
-        pred = pred[:, :_live_int(num_live, pred.shape[1])]
+        pred = pred[:, :selection.live_int(num_live, pred.shape[1])]
     mask = torch.ones(pred.shape, dtype=torch.bool, device=pred.device)
     for b in range(pred.shape[0]):
         mask[b, index[int(ptr[b]):int(ptr[b + 1])]] = False
@@ -130,7 +83,7 @@ def filtered_topk_reference(pred, k, ptr=None, index=None, num_live=None, retire
         ids, scores, count = filtered_topk_reference(alive, k, ptr, index)
         return torch.where(ids >= 0, cols[ids.clamp(min=0)] if len(cols) else ids, ids), scores, count
     if num_live is not None:
-        return filtered_topk_reference(pred[:, :_live_int(num_live, pred.shape[1])], k, ptr, index)
+        return filtered_topk_reference(pred[:, :selection.live_int(num_live, pred.shape[1])], k, ptr, index)
     k = int(k)
     batch, n = pred.shape
     ids = torch.full((batch, k), -1, dtype=torch.long, device=pred.device)
@@ -154,6 +107,22 @@ def check_k(k):
         raise ValueError("k must be an int in [1, %d], got %r" % (_lib.TOPK_MAX, k))
 
 
+def _gpu_scores(name, pred):
+    """`pred` of the wrapper `name` as contiguous (batch, N) fp32 scores on the GPU (RuntimeError off it, else TypeError)."""
+    if not pred.is_cuda:
+        raise RuntimeError("ultra_amd.predict.%s: expected a GPU tensor; the MI355X engine has no CPU path" % name)
+    if pred.dim() != 2 or pred.dtype != torch.float32:
+        raise TypeError("%s takes (batch, N) fp32 scores, got %s %s" % (name, tuple(pred.shape), pred.dtype))
+    return pred.contiguous()
+
+
+def _known_lists(name, ptr, index, batch, dev):
+    """The lists (ptr, index) of the wrapper `name`, contiguous: the caller holds them until the launch is enqueued."""
+    if ptr.shape != (batch + 1,) or ptr.dtype != torch.long or index.dtype != torch.long or ptr.device != dev or index.device != dev:
+        raise ValueError("%s takes int64 `ptr` of shape (batch + 1,) and int64 `index` on the scores' device" % name)
+    return ptr.contiguous(), index.contiguous()
+
+
 def filtered_topk(pred, k, ptr=None, index=None, num_live=None, retired=None):
     """filtered_topk_reference through the HIP kernel: pred (batch, N) fp32 on the GPU; ptr (batch + 1) / index int64, ids
     ascending and distinct within a row; ptr None: no filter.  num_live (an int in [1, N], or one int64 on the device, read by
@@ -161,11 +130,7 @@ def filtered_topk(pred, k, ptr=None, index=None, num_live=None, retired=None):
     pair (bits, count): live.retired_words over at least N slots and one int64, both read by the kernels):
     ultra_filtered_topk_alive, with num_live or without."""
     check_k(k)
-    if not pred.is_cuda:
-        raise RuntimeError("ultra_amd.predict.filtered_topk: expected a GPU tensor; the MI355X engine has no CPU path")
-    if pred.dim() != 2 or pred.dtype != torch.float32:
-        raise TypeError("filtered_topk takes (batch, N) fp32 scores, got %s %s" % (tuple(pred.shape), pred.dtype))
-    pred = pred.contiguous()
+    pred = _gpu_scores("filtered_topk", pred)
     batch, n = pred.shape
     dev = pred.device
     ids = torch.empty(batch, k, dtype=torch.long, device=dev)
@@ -174,15 +139,39 @@ def filtered_topk(pred, k, ptr=None, index=None, num_live=None, retired=None):
     if batch == 0:
         return ids, scores, count
     if ptr is not None:
-        if ptr.shape != (batch + 1,) or ptr.dtype != torch.long or index.dtype != torch.long or ptr.device != dev or index.device != dev:
-            raise ValueError("filtered_topk takes int64 `ptr` of shape (batch + 1,) and int64 `index` on the scores' device")
-        ptr, index = ptr.contiguous(), index.contiguous()      # (referenced until the launch is enqueued)
+        ptr, index = _known_lists("filtered_topk", ptr, index, batch, dev)
     ws = torch.empty(max(1, _lib.lib.ultra_filtered_topk_workspace(batch, n, k) // 8), dtype=torch.long, device=dev)
     args = (pred.data_ptr(), None if ptr is None else ptr.data_ptr(), None if ptr is None else index.data_ptr(), batch, n, k,
             ids.data_ptr(), scores.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel() * 8)
-    live = None if num_live is None else _live_operand(num_live, n, dev)     # (referenced until the launch is enqueued)
-    _select("ultra_filtered_topk", args, live, dev, None if retired is None else _retired_operand(retired, n, dev))
+    live = selection.live_operand(num_live, n, dev)     # (referenced until the launch is enqueued)
+    _select("ultra_filtered_topk", args, live, dev, selection.retired_operand(retired, n, dev))
     return ids, scores, count
+
+
+def filtered_rank(pred, pos, ptr, index, num_live=None, retired=None, out=None):
+    """filtered_rank_reference through the HIP kernel (csrc/rank_kernels.hip): pred (batch, N) fp32 on the GPU; pos (batch), ptr
+    (batch + 1) and index int64 on its device, the ids of a row ascending and distinct, the positive among them.  num_live,
+    retired: as in filtered_topk -- ultra_filtered_rank_live / ultra_filtered_rank_alive; neither: ultra_filtered_rank.
+    out: the pair (rank, num_negative) of (batch) int64 tensors to write into -- a captured step's own buffers -- and to
+    return; None: new ones."""
+    pred = _gpu_scores("filtered_rank", pred)
+    batch, n = pred.shape
+    dev = pred.device
+    ptr, index = _known_lists("filtered_rank", ptr, index, batch, dev)
+    if pos.shape != (batch,) or pos.dtype != torch.long or pos.device != dev:
+        raise ValueError("filtered_rank takes int64 `pos` of shape (batch,) on the scores' device")
+    if out is None:
+        out = torch.empty(batch, dtype=torch.long, device=dev), torch.empty(batch, dtype=torch.long, device=dev)
+    rank, num_negative = out
+    if any(t.shape != (batch,) or t.dtype != torch.long or t.device != dev or not t.is_contiguous() for t in out):
+        raise ValueError("`out` is the pair (rank, num_negative): contiguous int64 tensors of shape (batch,) on the scores' device")
+    if batch == 0:
+        return rank, num_negative
+    pos = pos.contiguous()      # (referenced until the launch is enqueued)
+    args = (pred.data_ptr(), pos.data_ptr(), ptr.data_ptr(), index.data_ptr(), batch, n, rank.data_ptr(), num_negative.data_ptr())
+    live = selection.live_operand(num_live, n, dev)     # (referenced until the launch is enqueued)
+    _select("ultra_filtered_rank", args, live, dev, selection.retired_operand(retired, n, dev))
+    return rank, num_negative
 
 
 def _fp32_threshold(threshold):
@@ -228,7 +217,7 @@ def filtered_above_reference(pred, threshold, ptr=None, index=None, num_live=Non
         out_ptr, ids, scores, size = filtered_above_reference(alive, threshold, ptr, index)
         return out_ptr, cols[ids], scores, size
     if num_live is not None:
-        return filtered_above_reference(pred[:, :_live_int(num_live, pred.shape[1])], threshold, ptr, index)
+        return filtered_above_reference(pred[:, :selection.live_int(num_live, pred.shape[1])], threshold, ptr, index)
     thr = _fp32_threshold(threshold)
     batch, n = pred.shape
     dev = pred.device
@@ -258,11 +247,7 @@ def filtered_above(pred, threshold, ptr=None, index=None, num_live=None, retired
     kernels): ultra_filtered_above_live on the full rows; None: ultra_filtered_above.  retired (the device pair (bits, count) of
     filtered_topk): ultra_filtered_above_alive."""
     thr = _fp32_threshold(threshold)
-    if not pred.is_cuda:
-        raise RuntimeError("ultra_amd.predict.filtered_above: expected a GPU tensor; the MI355X engine has no CPU path")
-    if pred.dim() != 2 or pred.dtype != torch.float32:
-        raise TypeError("filtered_above takes (batch, N) fp32 scores, got %s %s" % (tuple(pred.shape), pred.dtype))
-    pred = pred.contiguous()
+    pred = _gpu_scores("filtered_above", pred)
     batch, n = pred.shape
     dev = pred.device
     out_ptr = torch.zeros(batch + 1, dtype=torch.long, device=dev)
@@ -274,14 +259,12 @@ def filtered_above(pred, threshold, ptr=None, index=None, num_live=None, retired
     if n == 0 or batch > _lib.ABOVE_MAX_BATCH:
         raise ValueError("filtered_above takes 1 to %d rows of at least one candidate, got %s" % (_lib.ABOVE_MAX_BATCH, tuple(pred.shape)))
     if ptr is not None:
-        if ptr.shape != (batch + 1,) or ptr.dtype != torch.long or index.dtype != torch.long or ptr.device != dev or index.device != dev:
-            raise ValueError("filtered_above takes int64 `ptr` of shape (batch + 1,) and int64 `index` on the scores' device")
-        ptr, index = ptr.contiguous(), index.contiguous()      # (referenced until the launch is enqueued)
+        ptr, index = _known_lists("filtered_above", ptr, index, batch, dev)
     ws = torch.empty(max(1, _lib.lib.ultra_filtered_above_workspace(batch, n) // 8), dtype=torch.long, device=dev)
     args = (pred.data_ptr(), None if ptr is None else ptr.data_ptr(), None if ptr is None else index.data_ptr(), batch, n, thr,
             out_ptr.data_ptr(), ids.data_ptr(), scores.data_ptr(), ids.numel(), size.data_ptr(), ws.data_ptr(), ws.numel() * 8)
-    live = None if num_live is None else _live_operand(num_live, n, dev)     # (referenced until the launch is enqueued)
-    _select("ultra_filtered_above", args, live, dev, None if retired is None else _retired_operand(retired, n, dev))
+    live = selection.live_operand(num_live, n, dev)     # (referenced until the launch is enqueued)
+    _select("ultra_filtered_above", args, live, dev, selection.retired_operand(retired, n, dev))
     return out_ptr, ids, scores, size
 
 
@@ -316,7 +299,37 @@ def _candidates(data, anchor, relation, mode):
 
 
 class _IndexedStep(Capture):
-    """A captured step that reads the known lists of a whole call from a buffer of its own, `index` (loaded once per call)."""
+    """A captured step that reads the known lists of a whole call from a buffer of its own, `index` (loaded once per call), and
+    the offsets of a batch's lists from `ptr`.  It holds what the Predictor compares to know whether the capture still serves:
+    `params`, `capacity` (of `index`; 0 for index_capacity None -- no filter, nothing to load), `delta` and its `route`, and
+    `retired`; `n_live` is the device live count the selection reads at replay."""
+
+    def __init__(self, model, data, batch_size, index_capacity, delta, n_live, retired):
+        dev = data.edge_index.device
+        Capture.__init__(self, dev)
+        self.model, self.bs = model, batch_size
+        self.delta, self.route, self.n_live, self.retired = delta, _delta_route(delta), n_live, retired
+        self.filtered = index_capacity is not None
+        self.capacity = max(1, int(index_capacity)) if self.filtered else 0
+        self.ptr = torch.zeros(batch_size + 1, dtype=torch.long, device=dev)
+        self.index = torch.zeros(max(1, self.capacity), dtype=torch.long, device=dev)
+
+    def record_step(self, step, warmup, inputs, outputs):
+        """Warm up and capture `step`, which reads the buffers `inputs` (and `ptr`, `index`) and writes the buffers `outputs`."""
+        self.inputs, self.outputs = inputs, outputs
+        self.warm_up(step, warmup)
+        self.capture(step)
+        self.params = param_state(self.model)
+
+    def __call__(self, *rows_and_ptr):
+        """The `outputs` of this batch -- the step's own buffers: copy before the next call -- from one row tensor per input and
+        the batch's (bs + 1) offsets into the known lists (None where nothing is filtered)."""
+        for buffer, rows in zip(self.inputs, rows_and_ptr):
+            buffer.copy_(rows, non_blocking=True)
+        if self.filtered:
+            self.ptr.copy_(rows_and_ptr[-1], non_blocking=True)
+        self.graph.replay()
+        return self.outputs
 
     def load_index(self, index):
         self.index[:index.numel()].copy_(index, non_blocking=True)
@@ -336,25 +349,18 @@ class _GraphedPredictStep(_IndexedStep):
         normal path; once it holds facts or tombstones the capture records the delta's launches, which read its device buffers
         at replay --
         `route` is what the Predictor compares to know whether this capture still serves the delta."""
+        _IndexedStep.__init__(self, model, data, batch_size, index_capacity, delta, n_live, retired)
         dev = data.edge_index.device
-        Capture.__init__(self, dev)
-        self.model, self.bs, self.k, self.mode = model, batch_size, k, mode
-        self.delta, self.route = delta, _delta_route(delta)
+        self.k, self.mode = k, mode
         model_kwargs = {} if delta is None else {"delta": delta}
         self.anchor = torch.zeros(batch_size, dtype=torch.long, device=dev)
         self.relation = torch.zeros(batch_size, dtype=torch.long, device=dev)
-        self.filtered = index_capacity is not None
-        self.capacity = max(1, int(index_capacity)) if self.filtered else 0
-        self.ptr = torch.zeros(batch_size + 1, dtype=torch.long, device=dev)
-        self.index = torch.zeros(max(1, self.capacity), dtype=torch.long, device=dev)
         self.ids = torch.empty(batch_size, k, dtype=torch.long, device=dev)
         self.scores = torch.empty(batch_size, k, dtype=torch.float32, device=dev)
         self.count = torch.empty(batch_size, dtype=torch.long, device=dev)
         n = int(data.num_nodes)
         ws_bytes = _lib.lib.ultra_filtered_topk_workspace(batch_size, n, k)
         self.ws = torch.empty(max(1, ws_bytes // 8), dtype=torch.long, device=dev)
-
-        self.n_live, self.retired = n_live, retired
 
         def step():
             pred = model(data, _candidates(data, self.anchor, self.relation, mode), **model_kwargs).float().contiguous()
@@ -363,18 +369,7 @@ class _GraphedPredictStep(_IndexedStep):
                     self.scores.data_ptr(), self.count.data_ptr(), self.ws.data_ptr(), self.ws.numel() * 8)
             _select("ultra_filtered_topk", args, n_live, dev, retired)
 
-        self.warm_up(step, warmup)
-        self.capture(step)
-        self.params = param_state(model)
-
-    def __call__(self, anchor, relation, ptr):
-        """(ids, scores, count) of this batch -- views of the step's buffers: copy before the next call."""
-        self.anchor.copy_(anchor, non_blocking=True)
-        self.relation.copy_(relation, non_blocking=True)
-        if self.filtered:
-            self.ptr.copy_(ptr, non_blocking=True)
-        self.graph.replay()
-        return self.ids, self.scores, self.count
+        self.record_step(step, warmup, (self.anchor, self.relation), (self.ids, self.scores, self.count))
 
 
 def _release(steps):
@@ -395,6 +390,17 @@ def _delta_route(delta):
 
 def _entity_model(model):
     return getattr(model, "entity_model", model)
+
+
+@contextlib.contextmanager
+def eval_mode(model):
+    """Inside the block `model` is in eval mode; on the way out it is in the mode it was in."""
+    was_training = model.training
+    model.eval()
+    try:
+        yield
+    finally:
+        model.train(was_training)
 
 
 def delta_samples_supported(model):
@@ -487,9 +493,7 @@ def verify_reference(model, data, filter_graph, h, r, t, mode="tail"):
     rank = torch.empty(len(h), dtype=torch.long, device=dev)
     num_negative = torch.empty(len(h), dtype=torch.long, device=dev)
     ent = _entity_model(model)
-    was_training = model.training
-    model.eval()
-    try:
+    with eval_mode(model):
         for i in range(len(h)):
             batch = torch.stack([h[i:i + 1], t[i:i + 1], r[i:i + 1]], dim=-1)
             without = ent.remove_easy_edges(data, h[i:i + 1], t[i:i + 1], r[i:i + 1])
@@ -500,8 +504,6 @@ def verify_reference(model, data, filter_graph, h, r, t, mode="tail"):
             score[i] = pred[0, pos[0]]
             rank[i] = tasks.compute_ranking(pred, pos, mask)[0]
             num_negative[i] = mask.sum(dim=-1)[0]
-    finally:
-        model.train(was_training)
     return score, rank, num_negative
 
 
@@ -518,27 +520,22 @@ class _GraphedVerifyStep(_IndexedStep):
         forward above; once it holds facts or tombstones it records model(..., leave_out=triples, delta=delta) -- the keep rows
         over the base edge list, the same edges as per-sample keys (GraphDelta.sample_keys into the step's own key buffers) and
         the delta's fix-up launches, which read its device buffers at replay.  `route` is what the Predictor compares."""
+        _IndexedStep.__init__(self, model, data, batch_size, index_capacity, delta, n_live, retired)
         dev = data.edge_index.device
-        Capture.__init__(self, dev)
-        self.model, self.bs, self.mode, self.n_live, self.retired = model, batch_size, mode, n_live, retired
-        self.delta, self.route = delta, _delta_route(delta)
+        self.mode = mode
         live = delta is not None and delta.edited
         # (row, col, type) of every sample's two dead edges: allocated once, at fixed addresses
         self.keys = tuple(torch.zeros(batch_size, 2, dtype=torch.int32, device=dev) for _ in range(3)) if live else None
-        self.capacity = max(1, int(index_capacity))
         self.triples = torch.zeros(batch_size, 3, dtype=torch.long, device=dev)       # (h, t, r)
-        self.ptr = torch.zeros(batch_size + 1, dtype=torch.long, device=dev)
-        self.index = torch.zeros(self.capacity, dtype=torch.long, device=dev)
         self.keep = torch.empty(batch_size, data.edge_index.shape[1], dtype=torch.float32, device=dev)
         self.score = torch.empty(batch_size, dtype=torch.float32, device=dev)
         self.rank = torch.empty(batch_size, dtype=torch.long, device=dev)
         self.num_negative = torch.empty(batch_size, dtype=torch.long, device=dev)
-        n = int(data.num_nodes)
         ent = _entity_model(model)
         # The live route is replayed between eager edits (add_facts / remove_facts run torch ops of their own), and a memset node
         # captured into a hipGraph replays wrongly once eager memsets interleave with the replays (csrc/rank_kernels.hip): its
         # rank goes through the live-count entry, which zeroes with a kernel -- over all n ids where no rows are reserved.
-        self.n_all = torch.full((1,), n, dtype=torch.long, device=dev) if live and n_live is None and retired is None else None
+        self.n_all = torch.full((1,), int(data.num_nodes), dtype=torch.long, device=dev) if live and n_live is None and retired is None else None
         rank_count = n_live if n_live is not None else self.n_all
 
         def step():
@@ -551,21 +548,11 @@ class _GraphedVerifyStep(_IndexedStep):
                 keep = ent.leave_one_out_keep(data, self.triples, out=self.keep, validate=False)
                 pred = model(data, _candidates(data, anchor, r, mode), edge_keep=keep).float().contiguous()
             pos = pos.contiguous()
-            args = (pred.data_ptr(), pos.data_ptr(), self.ptr.data_ptr(), self.index.data_ptr(), batch_size, n,
-                    self.rank.data_ptr(), self.num_negative.data_ptr())
-            _select("ultra_filtered_rank", args, rank_count, dev, retired)
+            filtered_rank(pred, pos, self.ptr, self.index, num_live=rank_count, retired=retired, out=(self.rank, self.num_negative))
             self.score.copy_(pred.gather(1, pos.unsqueeze(-1)).squeeze(-1))
 
-        self.warm_up(step, warmup)
-        self.capture(step)
-        self.params = param_state(model)
+        self.record_step(step, warmup, (self.triples,), (self.score, self.rank, self.num_negative))
 
-    def __call__(self, triples, ptr):
-        """(score, rank, num_negative) of this batch -- views of the step's buffers: copy before the next call."""
-        self.triples.copy_(triples, non_blocking=True)
-        self.ptr.copy_(ptr, non_blocking=True)
-        self.graph.replay()
-        return self.score, self.rank, self.num_negative
 
 
 class Predictor(object):
@@ -769,10 +756,10 @@ class Predictor(object):
         return {} if delta is None else {"delta": delta}
 
     def tails(self, h, r):
-        return self._run(h, r, "tail")
+        return self._run(*self._query(h, r), "tail")
 
     def heads(self, t, r):
-        return self._run(t, r, "head")
+        return self._run(*self._query(t, r), "head")
 
     def tails_above(self, h, r, min_score):
         """Every tail of (h[i], r[i], ?) whose logit exceeds `min_score` (a Python float: the threshold of
@@ -825,10 +812,9 @@ class Predictor(object):
                 self.compact()      # (explanations walk the graph's own edge list: the edits become part of it first)
             else:
                 live = {"delta": self.delta}
+        anchor, relation = self._query(anchor, relation)
         ids, scores, count = self._run(anchor, relation, mode)
         dev = ids.device
-        anchor = torch.as_tensor(anchor, dtype=torch.long, device=dev).flatten()
-        relation = torch.as_tensor(relation, dtype=torch.long, device=dev).flatten()
         if mode == "head":
             relation = relation + self.data.num_relations // 2
         counts = count.tolist()
@@ -874,40 +860,61 @@ class Predictor(object):
         except Exception:
             pass
 
-    def _retired(self):
-        """What the captured steps take and remember of the retired set: the device pair (bitmap, count) -- one object while the
-        bitmap is -- or None before the first retirement."""
-        return self._live.retired_operand
+    def _query(self, anchor, relation):
+        """(anchor, relation) of a query as int64 vectors on the graph's device: one relation per anchor, the anchors entities in
+        use -- not in the reserve, not retired --, the relations direct relations in use (ValueError otherwise)."""
+        dev = self.data.edge_index.device
+        anchor = torch.as_tensor(anchor, dtype=torch.long, device=dev).flatten()
+        relation = torch.as_tensor(relation, dtype=torch.long, device=dev).flatten()
+        if anchor.shape != relation.shape:
+            raise ValueError("one relation per query: got %d entities and %d relations" % (len(anchor), len(relation)))
+        self._live.check_entities(anchor, "the anchors of a query")
+        if self.relation_capacity:
+            check_live_relations(relation, self.num_direct_relations, "the relations of a query")
+        return anchor, relation
 
-    def _step(self, mode, need):
-        """The captured step of this direction, (re)built when there is none, the weights changed or the known lists of the
-        call do not fit its buffer."""
-        step = self._steps.get(mode)
-        if step is not None and step.params == param_state(self.model) and (need is None or need <= step.capacity) \
-                and step.delta is self.delta and step.route == _delta_route(self.delta) and step.retired is self._retired():
-            return step
-        if step is not None:
-            step.release()
-            del self._steps[mode]
-        capacity = None if need is None else max(2 * need, 1 << 16)
-        step = _GraphedPredictStep(self.model, self.data, self.batch_size, self.k, mode, capacity, delta=self.delta,
-                                   n_live=self.live_count, retired=self._retired())
-        self._steps[mode] = step
-        return step
-
-    def _verify_step(self, mode, need):
-        key = "verify_" + mode
+    def _step(self, key, need, build):
+        """The captured step `key` of `_steps`, (re)built -- build(capacity) -- when there is none, the weights changed, the known
+        lists of the call (`need` ids; None: no filter) do not fit its buffer, the delta, its route or the retired pair changed."""
         step = self._steps.get(key)
-        if step is not None and step.params == param_state(self.model) and need <= step.capacity \
-                and step.delta is self.delta and step.route == _delta_route(self.delta) and step.retired is self._retired():
+        if step is not None and step.params == param_state(self.model) and (need is None or need <= step.capacity) \
+                and step.delta is self.delta and step.route == _delta_route(self.delta) and step.retired is self._live.retired_operand:
             return step
         if step is not None:
             step.release()
             del self._steps[key]
-        step = _GraphedVerifyStep(self.model, self.data, self.batch_size, mode, max(2 * need, 1 << 16), n_live=self.live_count,
-                                  delta=self.delta, retired=self._retired())
-        self._steps[key] = step
+        step = self._steps[key] = build(None if need is None else max(2 * need, 1 << 16))
         return step
+
+    def _batched(self, key, build, rows, ptr, index, outs, eager, capturable=True):
+        """The batch loop of tails / heads / verify_*, inside eval_mode: `rows` (the per-query tensors a step takes) in batches of
+        batch_size into `outs`.  On the GPU with use_graph each batch is one replay of the captured step `key` (_step): a last
+        batch that is short is padded with copies of its last row with no known list, `index` is loaded once, and the step's
+        buffers are copied out, the padded rows dropped.  A model outside the fused inference path (models.NotOnFusedPath),
+        and every other case: eager(lo) gives the outputs of the batch that starts at row lo."""
+        n, bs = len(rows[0]), self.batch_size
+        start = 0
+        if capturable and self.use_graph and outs[0].is_cuda and not self._eager_only:
+            try:
+                step = self._step(key, None if index is None else index.numel(), build)
+                pad = (-n) % bs
+                padded, ptr_p = rows, ptr
+                if pad:
+                    padded = [torch.cat([t, t[-1:].expand(pad, *t.shape[1:])]) for t in rows]
+                    ptr_p = None if ptr is None else torch.cat([ptr, ptr[-1:].expand(pad)])
+                if index is not None:
+                    step.load_index(index)
+                for lo in range(0, n, bs):
+                    got = step(*(t[lo:lo + bs] for t in padded), None if ptr_p is None else ptr_p[lo:lo + bs + 1])
+                    for out, b_out in zip(outs, got):
+                        out[lo:lo + bs].copy_(b_out[:min(bs, n - lo)], non_blocking=True)
+                start = n
+            except models.NotOnFusedPath:       # model outside the fused inference path: everything runs eagerly below
+                torch.cuda.synchronize()
+                self._eager_only = True
+        for lo in range(start, n, bs):
+            for out, b_out in zip(outs, eager(lo)):
+                out[lo:lo + len(b_out)] = b_out
 
     @torch.no_grad()
     def _verify(self, h, r, t, mode):
@@ -919,44 +926,21 @@ class Predictor(object):
             # a model without the combined route: the keep masks run over the graph's own edge list.  A graph with reserved rows
             # or relation slots keeps DESIGN.md 19's rule -- compact first, the slot counts and the live counts stay
             self.compact()
-        data, bs, live_count, delta = self.data, self.batch_size, self.live_count, self.delta
+        data, bs, delta = self.data, self.batch_size, self.delta
         live = delta is not None and delta.edited      # (the edits stay beside the plan: leave_out= with the delta)
         dev = h.device
         n = len(h)
-        score = torch.empty(n, dtype=torch.float32, device=dev)
-        rank = torch.empty(n, dtype=torch.long, device=dev)
-        num_negative = torch.empty(n, dtype=torch.long, device=dev)
+        outs = (torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.long, device=dev),
+                torch.empty(n, dtype=torch.long, device=dev))       # (score, rank, num_negative)
         if n == 0:
-            return score, rank, num_negative
+            return outs
         ent = _entity_model(self.model)
-        was_training = self.model.training
-        self.model.eval()
-        try:
+        with eval_mode(self.model):
             triples = torch.stack([h, t, r], dim=-1)
             ptr, index = tasks.known_answers(self.filter_graph, triples, mode)      # the known lists of the whole call, once
             ptr, index = ptr.contiguous(), index.contiguous()
-            start = 0
-            if self.use_graph and dev.type == "cuda" and not self._eager_only and bs <= dense.LEAVE_ONE_OUT_MAX_SAMPLES:
-                try:
-                    step = self._verify_step(mode, index.numel())
-                    pad = (-n) % bs
-                    if pad:     # (padded rows: copies of the last fact with no known list; dropped below)
-                        triples_p = torch.cat([triples, triples[-1:].expand(pad, -1)])
-                        ptr_p = torch.cat([ptr, ptr[-1:].expand(pad)])
-                    else:
-                        triples_p, ptr_p = triples, ptr
-                    step.load_index(index)
-                    for lo in range(0, n, bs):
-                        rows = min(bs, n - lo)
-                        b_score, b_rank, b_neg = step(triples_p[lo:lo + bs], ptr_p[lo:lo + bs + 1])
-                        score[lo:lo + rows].copy_(b_score[:rows], non_blocking=True)
-                        rank[lo:lo + rows].copy_(b_rank[:rows], non_blocking=True)
-                        num_negative[lo:lo + rows].copy_(b_neg[:rows], non_blocking=True)
-                    start = n
-                except models.NotOnFusedPath:       # model outside the fused inference path: everything runs eagerly below
-                    torch.cuda.synchronize()
-                    self._eager_only = True
-            for lo in range(start, n, bs):
+
+            def eager(lo):
                 part = triples[lo:lo + bs].contiguous()
                 anchor, pos = (part[:, 0], part[:, 1]) if mode == "tail" else (part[:, 1], part[:, 0])
                 if live:
@@ -965,37 +949,26 @@ class Predictor(object):
                 else:
                     keep = ent.leave_one_out_keep(data, part, validate=False)
                     pred = self.model(data, _candidates(data, anchor, part[:, 2], mode), edge_keep=keep).float().contiguous()
-                pos, b_ptr = pos.contiguous(), ptr[lo:lo + len(part) + 1].contiguous()
-                if pred.is_cuda:
-                    b_rank, b_neg = torch.empty_like(pos), torch.empty_like(pos)
-                    args = (pred.data_ptr(), pos.data_ptr(), b_ptr.data_ptr(), index.data_ptr(), len(part), pred.shape[1],
-                            b_rank.data_ptr(), b_neg.data_ptr())
-                    _select("ultra_filtered_rank", args, live_count, dev, self._retired())
-                else:       # off the GPU: the plain-torch restatement, as in `tails`
-                    b_rank, b_neg = filtered_rank_reference(pred, pos, b_ptr, index, **self._live.selection_for(False))
-                score[lo:lo + len(part)] = pred.gather(1, pos.unsqueeze(-1)).squeeze(-1)
-                rank[lo:lo + len(part)], num_negative[lo:lo + len(part)] = b_rank, b_neg
-        finally:
-            self.model.train(was_training)
-        return score, rank, num_negative
+                pos = pos.contiguous()
+                # the kernel on the GPU; the restatement with the same interface elsewhere, as in `tails`
+                rank_of = filtered_rank if pred.is_cuda else filtered_rank_reference
+                b_rank, b_neg = rank_of(pred, pos, ptr[lo:lo + len(part) + 1], index, **self._live.selection_for(pred.is_cuda))
+                return pred.gather(1, pos.unsqueeze(-1)).squeeze(-1), b_rank, b_neg
+
+            self._batched("verify_" + mode, lambda capacity: _GraphedVerifyStep(
+                self.model, data, bs, mode, capacity, n_live=self.live_count, delta=delta, retired=self._live.retired_operand),
+                (triples,), ptr, index, outs, eager, capturable=bs <= dense.LEAVE_ONE_OUT_MAX_SAMPLES)
+        return outs
 
     @torch.no_grad()
     def _run_above(self, anchor, relation, min_score, mode):
         threshold = _fp32_threshold(min_score)
         data, bs, live, model_kwargs = self.data, self.batch_size, self._live, self._model_kwargs()
         dev = data.edge_index.device
-        anchor = torch.as_tensor(anchor, dtype=torch.long, device=dev).flatten()
-        relation = torch.as_tensor(relation, dtype=torch.long, device=dev).flatten()
-        if anchor.shape != relation.shape:
-            raise ValueError("one relation per query: got %d entities and %d relations" % (len(anchor), len(relation)))
-        self._live.check_entities(anchor, "the anchors of a query")
-        if self.relation_capacity:
-            check_live_relations(relation, self.num_direct_relations, "the relations of a query")
+        anchor, relation = self._query(anchor, relation)
         n = len(anchor)
         out_ptr, ids, scores, size = [torch.zeros(1, dtype=torch.long, device=dev)], [], [], []
-        was_training = self.model.training
-        self.model.eval()
-        try:
+        with eval_mode(self.model):
             ptr = index = None
             if self.filtered and n:     # the known lists of the whole call, once
                 ptr, index = known_answers(self.filter_graph, anchor, relation, mode)
@@ -1017,8 +990,6 @@ class Predictor(object):
                 scores.append(b_scores)
                 size.append(b_size)
                 at += total
-        finally:
-            self.model.train(was_training)
         if not ids:
             return (out_ptr[0], torch.zeros(0, dtype=torch.long, device=dev), torch.zeros(0, dtype=torch.float32, device=dev),
                     torch.zeros(0, dtype=torch.long, device=dev))
@@ -1026,59 +997,26 @@ class Predictor(object):
 
     @torch.no_grad()
     def _run(self, anchor, relation, mode):
+        """tails / heads of the queries (anchor, relation) as _query gives them."""
         data, bs, k, live, model_kwargs = self.data, self.batch_size, self.k, self._live, self._model_kwargs()
         dev = data.edge_index.device
-        anchor = torch.as_tensor(anchor, dtype=torch.long, device=dev).flatten()
-        relation = torch.as_tensor(relation, dtype=torch.long, device=dev).flatten()
-        if anchor.shape != relation.shape:
-            raise ValueError("one relation per query: got %d entities and %d relations" % (len(anchor), len(relation)))
-        self._live.check_entities(anchor, "the anchors of a query")
-        if self.relation_capacity:
-            check_live_relations(relation, self.num_direct_relations, "the relations of a query")
         n = len(anchor)
-        ids = torch.empty(n, k, dtype=torch.long, device=dev)
-        scores = torch.empty(n, k, dtype=torch.float32, device=dev)
-        count = torch.empty(n, dtype=torch.long, device=dev)
+        outs = (torch.empty(n, k, dtype=torch.long, device=dev), torch.empty(n, k, dtype=torch.float32, device=dev),
+                torch.empty(n, dtype=torch.long, device=dev))       # (ids, scores, count)
         if n == 0:
-            return ids, scores, count
-        was_training = self.model.training
-        self.model.eval()
-        try:
+            return outs
+        with eval_mode(self.model):
             ptr = index = None
             if self.filtered:       # the known lists of the whole call, once
                 ptr, index = known_answers(self.filter_graph, anchor, relation, mode)
-            start = 0
-            if self.use_graph and dev.type == "cuda" and not self._eager_only:
-                try:
-                    step = self._step(mode, index.numel() if self.filtered else None)
-                    pad = (-n) % bs
-                    if pad:
-                        anchor_p = torch.cat([anchor, anchor[-1:].expand(pad)])
-                        relation_p = torch.cat([relation, relation[-1:].expand(pad)])
-                        ptr_p = None if ptr is None else torch.cat([ptr, ptr[-1:].expand(pad)])     # (padded rows: no list)
-                    else:
-                        anchor_p, relation_p, ptr_p = anchor, relation, ptr
-                    if self.filtered:
-                        step.load_index(index)
-                    for lo in range(0, n, bs):
-                        rows = min(bs, n - lo)
-                        b_ids, b_scores, b_count = step(anchor_p[lo:lo + bs], relation_p[lo:lo + bs],
-                                                        None if ptr_p is None else ptr_p[lo:lo + bs + 1])
-                        ids[lo:lo + rows].copy_(b_ids[:rows], non_blocking=True)
-                        scores[lo:lo + rows].copy_(b_scores[:rows], non_blocking=True)
-                        count[lo:lo + rows].copy_(b_count[:rows], non_blocking=True)
-                    start = n
-                except models.NotOnFusedPath:       # model outside the fused inference path: everything runs eagerly below
-                    torch.cuda.synchronize()
-                    self._eager_only = True
-            for lo in range(start, n, bs):
-                pred = self.model(data, _candidates(data, anchor[lo:lo + bs], relation[lo:lo + bs], mode),
-                                  **model_kwargs).float()
-                b_ptr = None if ptr is None else ptr[lo:lo + len(pred) + 1]
+
+            def eager(lo):
+                pred = self.model(data, _candidates(data, anchor[lo:lo + bs], relation[lo:lo + bs], mode), **model_kwargs).float()
                 # the fused kernel on the GPU; the restatement with the same interface elsewhere (as eval._local_rows does)
                 select = filtered_topk if pred.is_cuda else filtered_topk_reference
-                b_ids, b_scores, b_count = select(pred, k, b_ptr, index, **live.selection_for(pred.is_cuda))
-                ids[lo:lo + len(pred)], scores[lo:lo + len(pred)], count[lo:lo + len(pred)] = b_ids, b_scores, b_count
-        finally:
-            self.model.train(was_training)
-        return ids, scores, count
+                return select(pred, k, None if ptr is None else ptr[lo:lo + len(pred) + 1], index, **live.selection_for(pred.is_cuda))
+
+            self._batched(mode, lambda capacity: _GraphedPredictStep(
+                self.model, data, bs, k, mode, capacity, delta=self.delta, n_live=self.live_count, retired=self._live.retired_operand),
+                (anchor, relation), ptr, index, outs, eager)
+        return outs

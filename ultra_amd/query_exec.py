@@ -29,7 +29,7 @@ from collections import namedtuple
 
 import torch
 
-from . import _lib
+from . import _lib, selection
 from .ultraquery import Query, UltraQuery, _logic
 
 PUSH_ENTITY, AND, OR, NOT = 0, 1, 2, 3
@@ -266,19 +266,6 @@ def segment(words, offset, batch, num_nodes, logic, stack, push_src, pop_dst, sy
         _lib.stream_of(stack)))
 
 
-def _retired_bits(retired, n, dev):
-    """`retired` of nonzero_lists: the device bitmap -- int32 or uint32, at least ceil(n / 32) words (live.retired_words), on
-    `dev` -- or the pair (bits, count) as LiveGraph.retired_operand holds it, of which the bitmap is used."""
-    bits = retired
-    if isinstance(retired, (tuple, list)) and len(retired) == 2:
-        bits = retired[0]
-    if not (torch.is_tensor(bits) and bits.dim() == 1 and bits.is_contiguous() and bits.dtype in (torch.int32, torch.uint32)
-            and bits.numel() >= (n + 31) // 32 and bits.device == dev):
-        raise ValueError("`retired` is the bitmap on the matrix's device -- at least ceil(n / 32) = %d int32 or uint32 words -- "
-                         "or the pair (bits, count) that holds it" % ((n + 31) // 32))
-    return bits
-
-
 def nonzero_lists(x, num_live=None, retired=None):
     """(ptr (batch + 1) int64, index int64): per row of x (batch, n) fp32 on the GPU the ids v with x[b, v] != 0, ascending
     (NaN counts, -0.0 does not).  `index` has room for batch * n ids; the first ptr[-1] are filled.  No host wait.
@@ -289,7 +276,7 @@ def nonzero_lists(x, num_live=None, retired=None):
     the pair (bits, count) of LiveGraph.retired_operand): ultra_nonzero_lists_alive, the lists without those ids, with num_live
     or without it (every slot is below the bound).  The bitmap is read by the kernels, not on the host."""
     # (the operand's own rules first, against x as it is: they hold wherever x lives)
-    bits = None if retired is None or x.dim() != 2 else _retired_bits(retired, x.shape[1], x.device)
+    retired = None if x.dim() != 2 else selection.retired_operand(retired, x.shape[1], x.device, bare=True)
     if not x.is_cuda:
         raise RuntimeError("ultra_amd.query_exec.nonzero_lists: expected a GPU tensor; the MI355X engine has no CPU path")
     if x.dim() != 2 or x.dtype != torch.float32:
@@ -299,27 +286,10 @@ def nonzero_lists(x, num_live=None, retired=None):
     ptr = torch.empty(batch + 1, dtype=torch.int64, device=x.device)
     index = torch.empty(max(1, batch * n), dtype=torch.int64, device=x.device)
     counts = torch.empty(max(1, batch), dtype=torch.int64, device=x.device)
-    if num_live is None and bits is None:
-        _lib.check(_lib.lib.ultra_nonzero_lists(x.data_ptr(), batch, n, counts.data_ptr(), ptr.data_ptr(), index.data_ptr(),
-                                                batch * n, _lib.stream_of(x)))
-        return ptr, index
-    if num_live is None:
-        live = None
-    elif torch.is_tensor(num_live):
-        if num_live.numel() != 1 or num_live.dtype != torch.long or num_live.device != x.device:
-            raise ValueError("a tensor `num_live` is one int64 on the matrix's device")
-        live = num_live      # (referenced until the launch is enqueued)
-    else:
-        if isinstance(num_live, bool) or not 0 <= int(num_live) <= n:
-            raise ValueError("num_live must lie in [0, %d] (the slots of a row), got %r" % (n, num_live))
-        live = torch.tensor(int(num_live), dtype=torch.long, device=x.device)
-    if bits is not None:
-        _lib.check(_lib.lib.ultra_nonzero_lists_alive(x.data_ptr(), batch, n, counts.data_ptr(), ptr.data_ptr(), index.data_ptr(),
-                                                      batch * n, None if live is None else live.data_ptr(), bits.data_ptr(),
-                                                      _lib.stream_of(x)))
-        return ptr, index
-    _lib.check(_lib.lib.ultra_nonzero_lists_live(x.data_ptr(), batch, n, counts.data_ptr(), ptr.data_ptr(), index.data_ptr(),
-                                                 batch * n, live.data_ptr(), _lib.stream_of(x)))
+    # (an empty list is a list: the live count may be 0 here.  Referenced until the launch is enqueued)
+    live = selection.live_operand(num_live, n, x.device, lowest=0, exact=True, whose="matrix's")
+    selection.launch("ultra_nonzero_lists", (x.data_ptr(), batch, n, counts.data_ptr(), ptr.data_ptr(), index.data_ptr(), batch * n),
+                     live, x.device, retired)
     return ptr, index
 
 

@@ -200,15 +200,14 @@ class QueryPredictor(object):
                     ptr, known = query_exec.nonzero_lists(sym, **live) if logits.is_cuda else self._known_reference(sym, len(index))
                 yield index, logits, ptr, known, live
 
-        was_training, logic = self.model.training, self.model.logic
-        self.model.eval()
-        if self.logic is not None:
-            self.model.logic = self.logic
-        try:
-            yield run()
-        finally:
-            self.model.train(was_training)
-            self.model.logic = logic
+        logic = self.model.logic
+        with predict.eval_mode(self.model):
+            if self.logic is not None:
+                self.model.logic = self.logic
+            try:
+                yield run()
+            finally:
+                self.model.logic = logic
 
     @torch.no_grad()
     def answers(self, queries):
