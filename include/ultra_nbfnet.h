@@ -612,6 +612,57 @@ int32_t ultra_filtered_above_alive(const void *score, const int64_t *known_ptr, 
                                    int64_t capacity, int64_t *size_out, void *workspace, int64_t workspace_bytes,
                                    const int64_t *n_live, const uint32_t *retired_bits, const int64_t *n_retired, void *stream);
 
+/* ---- candidate sets: selection AMONG an allow list per row ----
+ * The _among entries take the arguments of their parents plus, behind the known lists,
+ *   among_span (batch, 2) int64, DEVICE: the candidates of row b are among_index[among_span[b][0] : among_span[b][1]];
+ *   among_index int64, DEVICE: ids ascending and distinct within a span (the contract of the known lists).  Spans may be shared
+ *     by rows, may overlap and may be empty (an inverted or negative span is empty);
+ * and, behind n_cand, among_capacity: a HOST int64 in [1, 2^31), at least the longest span the call may meet.  It alone, with
+ * batch, sizes the grids and the workspaces; the spans are read on the device and a span longer than among_capacity is cut to it
+ * there: nothing is read past among_index[begin + among_capacity).
+ * n_live, retired_bits and n_retired (the operands of the _live and _alive twins) are OPTIONAL operands of the same entry: NULL
+ * n_live means every slot is live, NULL retired_bits that nothing is retired; n_retired is taken for symmetry and not read.
+ *   An id v of row b's span is ELIGIBLE iff 0 <= v < live and its retired bit is clear, live = *n_live clamped to [0, n_cand],
+ *   or n_cand.  An id that is not eligible is ABSENT: its score slot is never loaded and it is never counted, whatever the slot
+ *   holds; a negative id or an id >= n_cand is never used as an index.  A list made earlier stays valid after a retirement and
+ *   may name ids that only become live later.
+ * ultra_filtered_topk_among: the eligible ids not in known(b), in the order of ultra_filtered_topk (score descending, equal
+ *   scores by ascending id, NaN on top, -0.0 == +0.0); scores_out the stored bits; padding -1 / -inf.  count_out[b] =
+ *   min(k, #{eligible, not known}), COUNTED by the kernels: every chunk of ULTRA_TOPK_CHUNK list positions writes its survivor
+ *   count beside its partial list and the merge adds them.  workspace: ultra_filtered_topk_among_workspace(batch,
+ *   among_capacity, k) bytes, 8-byte aligned; -1 out of range.  A row whose capacity fits one chunk is finished by the first
+ *   launch.
+ * ultra_filtered_above_among: members = the eligible ids with score > threshold (strict, fp32); size_out[b] counts them before
+ *   the known filter; the list is the members not known, ranked, at ids_out[ptr_out[b] : ptr_out[b + 1]].  capacity >=
+ *   batch * among_capacity or ULTRA_ERR_INVALID (no overflow path).  workspace: ultra_filtered_above_among_workspace(batch,
+ *   among_capacity) bytes -- the layout of ultra_filtered_above_workspace over rows of among_capacity positions.
+ * ultra_filtered_rank_among: rank_out[q] = 1 + #{t eligible, t not in known(q) : score[q, pos[q]] <= score[q, t]};
+ *   num_negative_out[q] = #{t eligible, not in known(q)}.  pos[q] is in known(q) by the parent's contract and need not be in
+ *   the span.  Both outputs are zeroed by a kernel and added to with integer atomics, one per wave: the rank's own counters.
+ * The launch shapes, the workspace sizes and the number of launches depend on (batch, among_capacity) alone; no allocation, no
+ * memset, no host wait, no other global atomics: a recorded call serves any later spans, list contents, live count and retired
+ * set within the capacity.  Exact and reproducible.
+ * Errors, in the parents' order: k outside [1, ULTRA_TOPK_MAX], n_cand >= 2^31, a NaN or +inf threshold: ULTRA_ERR_UNSUPPORTED,
+ * decided before any pointer is looked at.  NULL among_span or among_index, among_capacity outside [1, 2^31), NULL score or
+ * outputs, n_cand <= 0, a short or misaligned workspace, (above) batch outside [0, 65535] or a short capacity, (rank) NULL
+ * pos_index or known_ptr: ULTRA_ERR_INVALID, nothing is launched.  batch == 0: ULTRA_OK. */
+int64_t ultra_filtered_topk_among_workspace(int64_t batch, int64_t among_capacity, int32_t k);
+int32_t ultra_filtered_topk_among(const void *score, const int64_t *known_ptr, const int64_t *known_index,
+                                  const int64_t *among_span, const int64_t *among_index, int64_t batch, int64_t n_cand,
+                                  int64_t among_capacity, int32_t k, int64_t *ids_out, void *scores_out, int64_t *count_out,
+                                  void *workspace, int64_t workspace_bytes, const int64_t *n_live, const uint32_t *retired_bits,
+                                  const int64_t *n_retired, void *stream);
+int64_t ultra_filtered_above_among_workspace(int64_t batch, int64_t among_capacity);
+int32_t ultra_filtered_above_among(const void *score, const int64_t *known_ptr, const int64_t *known_index,
+                                   const int64_t *among_span, const int64_t *among_index, int64_t batch, int64_t n_cand,
+                                   int64_t among_capacity, float threshold, int64_t *ptr_out, int64_t *ids_out, void *scores_out,
+                                   int64_t capacity, int64_t *size_out, void *workspace, int64_t workspace_bytes,
+                                   const int64_t *n_live, const uint32_t *retired_bits, const int64_t *n_retired, void *stream);
+int32_t ultra_filtered_rank_among(const void *score, const int64_t *pos_index, const int64_t *known_ptr,
+                                  const int64_t *known_index, const int64_t *among_span, const int64_t *among_index, int64_t batch,
+                                  int64_t n_cand, int64_t among_capacity, int64_t *rank_out, int64_t *num_negative_out,
+                                  const int64_t *n_live, const uint32_t *retired_bits, const int64_t *n_retired, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

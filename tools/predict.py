@@ -3,6 +3,7 @@
     python tools/predict.py --data-root DIR [--ckpt FILE] --head NAME --relation NAME [--inverse] [-k 10] [--unfiltered] [--explain [--no-compact]]
                             [--add-fact H R T]... [--remove-fact H R T]... [--entity-capacity M] [--add-entity NAME]...
                             [--relation-capacity K] [--add-relation NAME]... [--live-relation-graph] [--remove-entity NAME]...
+                            [--among NAME [NAME ...]] [--among-file FILE]
     python tools/predict.py --data-root DIR [--ckpt FILE] --verify (--head NAME --relation NAME --tail NAME | --triples FILE) [--inverse]
 
 DIR holds train.txt / valid.txt / test.txt (`head relation tail` per line) and optionally entities.dict / relations.dict
@@ -35,6 +36,11 @@ NAME can be used by all of them and by --relation.
 --live-relation-graph keeps the relation graph current in place (Predictor(live_relation_graph=True)): a fact that
 changes relation-graph cells -- every first fact through an --add-relation -- then costs no relation-graph plan and no new
 capture.  The answers are the same.  Needs a relation model of sum / DistMult layers (the default configuration's).
+
+--among NAME [NAME ...] and --among-file FILE (entity names, one per line; both may be given, the set is their union) restrict
+the candidates to a set (Predictor.tails(among=)): only these entities are ranked -- a shortlist, or the entities
+of a type -- and with --verify the fact is ranked among them.  An unknown name is an error that names it; a name introduced by
+--add-entity may be listed, and an entity retired by --remove-entity is simply absent.
 
 --verify judges facts the dataset may already state: every (head, relation, tail) -- one from the command line, or the
 `head relation tail` lines of FILE -- is scored on the graph WITHOUT itself and its inverse edge (Predictor.verify_tails; with
@@ -102,6 +108,8 @@ def main(argv=None):
                     help="slots reserved for new relation types (default: the number of --add-relation options)")
     ap.add_argument("--live-relation-graph", action="store_true",
                     help="keep the relation graph current in place: no relation-graph plan, no new capture for an edit")
+    ap.add_argument("--among", nargs="+", metavar="NAME", help="rank only these entities (a shortlist, a type)")
+    ap.add_argument("--among-file", metavar="FILE", help="... the entity names of FILE, one per line")
     ap.set_defaults(edits=[])
     args = ap.parse_args(argv)
     if args.verify:
@@ -205,10 +213,18 @@ def main(argv=None):
             took = predictor.remove_facts(*ids).tolist()
             print("%d fact(s) retracted from the dataset: %s edge(s) removed" % (len(run), " + ".join(str(n) for n in took)))
         at = end
+    among = {}
+    if args.among or args.among_file:
+        from ultra_amd.candidates import named_ids
+        try:
+            among = {"among": named_ids(ent, args.among, args.among_file)}
+        except ValueError as exc:
+            sys.exit("--among: %s" % exc)
+        print("candidates: the %d listed entities" % len(set(among["among"])))
     if facts is not None:
         # (the edits above stay a delta beside the cached plan: every fact is judged on the edited graph without itself)
         h, r, t = (torch.tensor([vocab.index(f[i]) for f in facts], device=dev) for i, vocab in ((0, ent), (1, rel), (2, ent)))
-        score, rank, num_negative = (predictor.verify_heads if args.inverse else predictor.verify_tails)(h, r, t)
+        score, rank, num_negative = (predictor.verify_heads if args.inverse else predictor.verify_tails)(h, r, t, **among)
         print("%s judged on the graph without the fact itself: score, filtered rank / candidates"
               % ("heads" if args.inverse else "tails"))
         for f, s, k, n in zip(facts, score.tolist(), rank.tolist(), num_negative.tolist()):
@@ -219,9 +235,9 @@ def main(argv=None):
     why = None
     if args.explain:
         ids, scores, count, why = (predictor.explain_heads if args.inverse else predictor.explain_tails)(
-            anchor, relation, compact=not args.no_compact)
+            anchor, relation, compact=not args.no_compact, **among)
     else:
-        ids, scores, count = (predictor.heads if args.inverse else predictor.tails)(anchor, relation)
+        ids, scores, count = (predictor.heads if args.inverse else predictor.tails)(anchor, relation, **among)
     query = "(?, %s, %s)" % (args.relation, args.head) if args.inverse else "(%s, %s, ?)" % (args.head, args.relation)
     print("%s: top %d%s" % (query, int(count[0]), "" if args.unfiltered else ", known answers left out"))
     for i in range(int(count[0])):

@@ -3,6 +3,7 @@
     python tools/query_predict.py --data-root DIR [--ckpt FILE] --query "(('e1', ('r1',)), ('e2', ('r2', -2)))" [-k 10]
                                   [--logic product] [--unfiltered] [--above P] [--add-fact H R T]... [--remove-fact H R T]...
                                   [--entity-capacity M] [--add-entity NAME]... [--remove-entity NAME]...
+                                  [--among NAME [NAME ...]] [--among-file FILE]
 
 DIR holds train.txt / valid.txt / test.txt (`head relation tail` per line) and optionally entities.dict / relations.dict
 (ultra_amd.data.load_triples_dir).  The query is a BetaE nested tuple (ultra_amd.ultraquery.Query.from_nested): a pair
@@ -30,6 +31,10 @@ on the command line, as an anchor of the query and in the printed answers.
 answer, never an entailed answer, no anchor.  It is applied in command-line order with the other edit options; NAME (a name of
 the vocabulary, one added earlier on the command line, or an integer id) no longer resolves in the options that follow it, nor
 in the query.
+
+--among NAME [NAME ...] and --among-file FILE (entity names, one per line; both may be given, the set is their union) restrict
+the candidates to a set (QueryPredictor.answers(among=)): only these entities are ranked, or listed by --above.
+An unknown name is an error that names it; a name introduced by --add-entity may be listed, a retired entity is simply absent.
 """
 import argparse
 import ast
@@ -101,6 +106,8 @@ def main(argv=None):
                     help="retire an entity and retract its facts before the query; repeatable, applied in order with the other edits")
     ap.add_argument("--entity-capacity", type=int, default=None, metavar="M",
                     help="rows reserved for new entities (default: the number of --add-entity options)")
+    ap.add_argument("--among", nargs="+", metavar="NAME", help="rank only these entities (a shortlist, a type)")
+    ap.add_argument("--among-file", metavar="FILE", help="... the entity names of FILE, one per line")
     ap.set_defaults(edits=[])
     args = ap.parse_args(argv)
     if args.entity_capacity is not None and args.entity_capacity < 0:
@@ -137,6 +144,13 @@ def main(argv=None):
     if len(ent) > num_known and not reserve:
         sys.exit("--add-entity needs --entity-capacity above 0")
     nested = resolve(ast.literal_eval(args.query), ent, rel, gone)
+    among = {}
+    if args.among or args.among_file:
+        from ultra_amd.candidates import named_ids
+        try:
+            among = {"among": named_ids(ent, args.among, args.among_file)}
+        except ValueError as exc:
+            sys.exit("--among: %s" % exc)
     dev = torch.device("cuda:0")
     data = udata.load_triples_dir(args.data_root).to(dev)
     cfg = synthetic.default_model_cfg()
@@ -181,14 +195,16 @@ def main(argv=None):
             sys.exit(str(exc))
         at = end
     print(ultraquery.Query.from_nested(nested).to_readable())
+    if among:
+        print("candidates: the %d listed entities" % len(set(among["among"])))
     if args.above is not None:
-        ptr, ids, scores, size = qp.answer_sets([nested], probability=args.above)
+        ptr, ids, scores, size = qp.answer_sets([nested], probability=args.above, **among)
         print("%d answers with probability above %g%s; predicted size of the set %d"
               % (int(ptr[1]), args.above, "" if args.unfiltered else ", entailed answers left out", int(size[0])))
         for i, (v, s) in enumerate(zip(ids.tolist(), scores.tolist())):
             print("%3d  %-40s %.6g" % (i + 1, ent[v], s))
         return
-    ids, scores, count = qp.answers([nested])
+    ids, scores, count = qp.answers([nested], **among)
     print("top %d%s" % (int(count[0]), "" if args.unfiltered else ", entailed answers left out"))
     for i in range(int(count[0])):
         print("%3d  %-40s %.6g" % (i + 1, ent[int(ids[0, i])], float(scores[0, i])))

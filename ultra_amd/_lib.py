@@ -190,6 +190,17 @@ def _load():
     lib.ultra_filtered_above_workspace.argtypes = [i64, i64]
     lib.ultra_filtered_above_workspace.restype = i64
     lib.ultra_filtered_above.argtypes = [vp, vp, vp, i64, i64, ctypes.c_float, vp, vp, vp, i64, vp, vp, i64, vp]
+    # the selections among a candidate list per row: the parent's arguments with (among_span, among_index) behind
+    # the known lists and among_capacity behind n_cand; the live count, the retired bitmap and the retired count (None each:
+    # absent) before the stream
+    lib.ultra_filtered_topk_among_workspace.argtypes = [i64, i64, i32]
+    lib.ultra_filtered_topk_among_workspace.restype = i64
+    lib.ultra_filtered_topk_among.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp]
+    lib.ultra_filtered_above_among_workspace.argtypes = [i64, i64]
+    lib.ultra_filtered_above_among_workspace.restype = i64
+    lib.ultra_filtered_above_among.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, ctypes.c_float, vp, vp, vp, i64, vp, vp, i64,
+                                               vp, vp, vp, vp]
+    lib.ultra_filtered_rank_among.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp]
     lib.ultra_query_segment.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, vp, vp, i64, vp, i64, vp, vp, vp, vp]
     lib.ultra_nonzero_lists.argtypes = [vp, i64, i64, vp, vp, vp, i64, vp]
     # ... over the live ids of rows of n slots: the device pointer to the int64 live count before the stream

@@ -44,20 +44,9 @@
 #include "plan.hpp"
 #include "device_scope.hpp"
 #include "score_key.hpp"
+#include "topk_select.hpp"      // the ABOVE_ constants, wave_sum, sort_and_write_run, the scan and merge launches
 
 namespace ultra {
-
-constexpr int ABOVE_THREADS = 256;
-constexpr int ABOVE_CHUNK = ULTRA_TOPK_CHUNK;
-constexpr int ABOVE_SLOTS = ABOVE_CHUNK / ABOVE_THREADS;      // candidates a thread holds
-constexpr int ABOVE_TILE = 2048;                              // merged keys one workgroup of a merge level produces
-constexpr int ABOVE_ITEMS = ABOVE_TILE / ABOVE_THREADS;
-constexpr int ABOVE_TILES_PER_CHUNK = ABOVE_CHUNK / ABOVE_TILE;
-constexpr long long ABOVE_MAX_BATCH = 65535;
-static_assert(ABOVE_CHUNK % ABOVE_TILE == 0 && ABOVE_TILE % ABOVE_THREADS == 0, "tiles cut chunks evenly");
-static_assert((ABOVE_CHUNK & (ABOVE_CHUNK - 1)) == 0, "the bitonic sort runs over powers of two up to a chunk");
-
-typedef unsigned long long u64;
 
 // The candidates of chunk [lo, lo + ABOVE_CHUNK) of a row of n_cand slots of which the ids below *n_live (clamped to
 // [0, n_cand]; NULL: all) are live: 0 for a chunk beyond the live count.
@@ -121,11 +110,6 @@ __device__ __forceinline__ int chunk_survivors(const float *__restrict__ row, lo
         bits[j] = i < n ? ord[i] : 0u;
     }
     return members;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;       // (lane 0 holds the sum)
 }
 
 __global__ void __launch_bounds__(ABOVE_THREADS) above_count_kernel(const float *__restrict__ score, const int64_t *__restrict__ known_ptr,
@@ -236,35 +220,8 @@ __global__ void __launch_bounds__(ABOVE_THREADS) above_fill_kernel(const float *
         if (bits[j] != 0u) keys[at++] = ((u64)bits[j] << 32) | (u64)(~id);
     }
     __syncthreads();
-    const int m = (int)cursor;      // (the chunk's kept count: what above_count_kernel wrote)
-    if (m == 0) return;
-    int p = 1;
-    while (p < m) p <<= 1;
-    for (int i = m + tid; i < p; i += ABOVE_THREADS) keys[i] = 0;      // absent keys sort last
-    __syncthreads();
-    for (int k = 2; k <= p; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (p >> 1); t += ABOVE_THREADS) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const int l = i | j;
-                const bool descending = (i & k) == 0;
-                const u64 x = keys[i], y = keys[l];
-                if ((x < y) == descending) keys[i] = y, keys[l] = x;
-            }
-            __syncthreads();
-        }
-    }
-    const long long at_out = offs[blockIdx.x];
-    for (int t = tid; t < m; t += ABOVE_THREADS) {
-        const u64 key = keys[t];
-        if (n_chunk == 1) {
-            const unsigned id = ~(unsigned)key;
-            ids_out[at_out + t] = (int64_t)id;
-            scores_out[at_out + t] = __float_as_uint(row[id]);
-        } else {
-            keys_out[at_out + t] = key;
-        }
-    }
+    // (cursor: the chunk's kept count, what above_count_kernel wrote)
+    sort_and_write_run(keys, (int)cursor, row, offs[blockIdx.x], n_chunk == 1, keys_out, ids_out, scores_out);
 }
 
 // How many of the first d keys of the descending merge of x[0 .. nx) and y[0 .. ny) come from x.  The keys are distinct.
@@ -333,6 +290,28 @@ __global__ void __launch_bounds__(ABOVE_THREADS) above_merge_kernel(const float 
 
 static int64_t above_chunks(int64_t n_cand) { return (n_cand + ULTRA_TOPK_CHUNK - 1) / ULTRA_TOPK_CHUNK; }
 
+hipError_t launch_above_scan(const int *counts, long long batch, long long n_chunk, long long *offs, int64_t *ptr_out,
+                             int64_t *size_out, hipStream_t s) {
+    hipLaunchKernelGGL(above_scan_kernel, dim3(1), dim3(ABOVE_THREADS), 0, s, counts, batch, n_chunk, offs, ptr_out, size_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_above_merges(const float *score, long long n_cand, long long batch, long long n_chunk, const long long *offs,
+                               u64 *keys0, u64 *keys1, int64_t *ids_out, unsigned *scores_out, hipStream_t s) {
+    u64 *src = keys0, *dst = keys1;
+    for (long long width = 1; width < n_chunk; width <<= 1) {
+        const int last = 2 * width >= n_chunk ? 1 : 0;
+        hipLaunchKernelGGL(above_merge_kernel, dim3((unsigned)(batch * n_chunk * ABOVE_TILES_PER_CHUNK)), dim3(ABOVE_THREADS), 0, s,
+                           score, n_cand, n_chunk, width, offs, (const u64 *)src, dst, ids_out, scores_out, last);
+        const hipError_t err = hipGetLastError();
+        if (err != hipSuccess) return err;
+        u64 *swap = src;
+        src = dst;
+        dst = swap;
+    }
+    return hipSuccess;
+}
+
 }  // namespace ultra
 
 // Layout: offsets (batch * chunks + 1) int64 | key buffer 0, key buffer 1 (batch * n_cand) uint64 each | counts (batch * chunks, 2) int32.
@@ -388,9 +367,7 @@ static int32_t filtered_above_impl(const char *who_, const void *score, const in
         ultra::set_error("above_count_kernel launch failed");
         return ULTRA_ERR_HIP;
     }
-    hipLaunchKernelGGL(ultra::above_scan_kernel, dim3(1), threads, 0, s, (const int *)counts, (long long)batch, (long long)n_chunk, offs,
-                       ptr_out, size_out);
-    if (hipGetLastError() != hipSuccess) {
+    if (ultra::launch_above_scan(counts, batch, n_chunk, offs, ptr_out, size_out, s) != hipSuccess) {
         ultra::set_error("above_scan_kernel launch failed");
         return ULTRA_ERR_HIP;
     }
@@ -401,19 +378,10 @@ static int32_t filtered_above_impl(const char *who_, const void *score, const in
         ultra::set_error("above_fill_kernel launch failed");
         return ULTRA_ERR_HIP;
     }
-    ultra::u64 *src = keys0, *dst = keys1;
-    for (int64_t width = 1; width < n_chunk; width <<= 1) {
-        const int last = 2 * width >= n_chunk ? 1 : 0;
-        hipLaunchKernelGGL(ultra::above_merge_kernel, dim3((unsigned)(slots * ultra::ABOVE_TILES_PER_CHUNK)), threads, 0, s,
-                           (const float *)score, (long long)n_cand, (long long)n_chunk, (long long)width, (const long long *)offs,
-                           (const ultra::u64 *)src, dst, ids_out, (unsigned *)scores_out, last);
-        if (hipGetLastError() != hipSuccess) {
-            ultra::set_error("above_merge_kernel launch failed");
-            return ULTRA_ERR_HIP;
-        }
-        ultra::u64 *swap = src;
-        src = dst;
-        dst = swap;
+    if (ultra::launch_above_merges((const float *)score, n_cand, batch, n_chunk, offs, keys0, keys1, ids_out, (unsigned *)scores_out,
+                                   s) != hipSuccess) {
+        ultra::set_error("above_merge_kernel launch failed");
+        return ULTRA_ERR_HIP;
     }
     return ULTRA_OK;
 }

@@ -38,165 +38,9 @@
 #include "plan.hpp"
 #include "device_scope.hpp"
 #include "score_key.hpp"
+#include "topk_select.hpp"      // select_topk, write_answers, live_count, merge_partial_lists
 
 namespace ultra {
-
-constexpr int TOPK_THREADS = 256;
-constexpr int TOPK_CHUNK = ULTRA_TOPK_CHUNK;
-constexpr int TOPK_MAX = ULTRA_TOPK_MAX;
-constexpr int TOPK_CHUNK_BITS = 12;
-static_assert(TOPK_CHUNK == 1 << TOPK_CHUNK_BITS, "the in-chunk key packs the local index into TOPK_CHUNK_BITS bits");
-static_assert(TOPK_THREADS == 256 && TOPK_MAX <= TOPK_THREADS, "one thread per histogram bin and per survivor");
-
-typedef unsigned long long u64;
-
-constexpr int TOPK_SLOTS = TOPK_CHUNK / TOPK_THREADS;      // fresh keys a thread holds; one more slot takes a survivor (merge)
-constexpr int TOPK_HELD = TOPK_SLOTS + 1;
-
-struct TopkScratch {
-    unsigned hist[256];
-    u64 surv[TOPK_MAX];
-    u64 top[TOPK_THREADS];      // every thread's largest key
-    u64 prefix, low;
-    unsigned remaining, done, count, cursor;
-};
-
-// surv[0 .. m) -> sorted[0 .. min(m, k)), descending: rank by counting, the keys are distinct.  m <= TOPK_THREADS.
-__device__ __forceinline__ void rank_sort(const u64 *surv, int m, int k, u64 *sorted) {
-    const int tid = threadIdx.x;
-    if (tid < m) {
-        const u64 key = surv[tid];
-        int r = 0;
-        for (int j = 0; j < m; ++j) r += surv[j] > key ? 1 : 0;
-        if (r < k) sorted[r] = key;
-    }
-}
-
-// The keys of a workgroup, TOPK_HELD in the registers of every thread: 0 = absent, the others distinct and below 2^(8 bytes).
-// Leaves the m = min(k, #present) largest in sorted[0 .. m) (LDS), descending, and returns m (the same in every thread).  Ends
-// with a barrier.
-//
-// Most keys never reach the selection proper: every thread publishes its largest key; the k-th largest of those 256 maxima is
-// a floor under the k-th largest key (k keys, the maxima above it, are at least as large), so only keys at or above the floor
-// stay.  For scores in no particular order that is little more than k keys, which are ranked by counting.  When more than
-// TOPK_MAX stay (the winners crowd into few threads, or k is close to the number of threads) a radix select, a byte per pass
-// from the top, finds the k-th largest among them first.
-__device__ int select_topk(u64 (&held)[TOPK_HELD], int k, int bytes, TopkScratch &s, u64 *sorted) {
-    const int tid = threadIdx.x;
-    u64 best = 0;
-#pragma unroll
-    for (int j = 0; j < TOPK_HELD; ++j) best = held[j] > best ? held[j] : best;
-    s.top[tid] = best;
-    if (tid == 0) s.low = 1, s.cursor = 0, s.count = 0;      // (fewer than k threads hold a key: everything present stays)
-    __syncthreads();
-    {
-        int r = 0;
-        for (int j = 0; j < TOPK_THREADS; ++j) r += s.top[j] > best ? 1 : 0;
-        if (best != 0 && r == k - 1) s.low = best;
-    }
-    __syncthreads();
-    const u64 low = s.low;
-    int stay = 0;
-#pragma unroll
-    for (int j = 0; j < TOPK_HELD; ++j) {
-        held[j] = held[j] >= low ? held[j] : 0;     // (an absent key, 0, is below any floor)
-        stay += held[j] != 0 ? 1 : 0;
-    }
-    unsigned at = stay ? atomicAdd(&s.cursor, (unsigned)stay) : 0u;       // (the order is settled by the sort below)
-    __syncthreads();
-    const int n = (int)s.cursor;
-    if (n <= TOPK_MAX) {
-#pragma unroll
-        for (int j = 0; j < TOPK_HELD; ++j)
-            if (held[j] != 0) s.surv[at++] = held[j];
-        __syncthreads();
-        rank_sort(s.surv, n, k, sorted);
-        __syncthreads();
-        return n < k ? n : k;
-    }
-    // more than TOPK_MAX >= k keys are left: radix select of the k-th largest
-    u64 prefix = 0;
-    unsigned remaining = (unsigned)k;
-    int p = bytes - 1;
-    for (;; --p) {
-        s.hist[tid] = 0;
-        __syncthreads();
-        const int above_shift = 8 * (p + 1);
-#pragma unroll
-        for (int j = 0; j < TOPK_HELD; ++j) {
-            const u64 key = held[j];
-            const bool match = above_shift >= 64 ? true : (key >> above_shift) == prefix;
-            if (key != 0 && match) atomicAdd(&s.hist[(unsigned)(key >> (8 * p)) & 255u], 1u);
-        }
-        __syncthreads();
-        if (tid < 64) {     // (the whole first wave) lane l owns bins 4 l .. 4 l + 3; suffix sums from the top bin down
-            const unsigned c = s.hist[4 * tid] + s.hist[4 * tid + 1] + s.hist[4 * tid + 2] + s.hist[4 * tid + 3];
-            unsigned incl = c;
-            for (int off = 1; off < 64; off <<= 1) {
-                const unsigned v = __shfl_down(incl, off);
-                if (tid + off < 64) incl += v;
-            }
-            const unsigned above = incl - c;
-            if (incl >= remaining && above < remaining) {      // exactly one lane
-                unsigned acc = above, h = 0;
-                int d = 3;
-                for (; d > 0; --d) {
-                    h = s.hist[4 * tid + d];
-                    if (acc + h >= remaining) break;
-                    acc += h;
-                }
-                if (d == 0) h = s.hist[4 * tid];
-                s.prefix = (prefix << 8) | (u64)(4 * tid + d);
-                s.remaining = remaining - acc;
-                s.done = (acc + h == remaining) ? 1u : 0u;      // the bins from here up hold exactly what is wanted
-            }
-        }
-        __syncthreads();
-        prefix = s.prefix;
-        remaining = s.remaining;
-        if (s.done || p == 0) break;
-    }
-    const u64 threshold = prefix << (8 * p);
-#pragma unroll
-    for (int j = 0; j < TOPK_HELD; ++j) {
-        if (held[j] != 0 && held[j] >= threshold) {
-            const unsigned slot = atomicAdd(&s.count, 1u);
-            if (slot < (unsigned)TOPK_MAX) s.surv[slot] = held[j];
-        }
-    }
-    __syncthreads();
-    const int m = (int)s.count < k ? (int)s.count : k;
-    rank_sort(s.surv, m, k, sorted);
-    __syncthreads();
-    return m;
-}
-
-// (n_cand: the row's LIVE candidates that are not retired, of which the known ids are a part)
-__device__ void write_answers(const float *row, long long n_cand, long long n_known, int k, int m, const u64 *sorted,
-                              int64_t *ids_out, unsigned *scores_out, int64_t *count_out) {
-    const int tid = threadIdx.x;
-    if (tid < k) {
-        if (tid < m) {
-            const unsigned id = ~(unsigned)sorted[tid];
-            ids_out[tid] = (int64_t)id;
-            scores_out[tid] = __float_as_uint(row[id]);
-        } else {
-            ids_out[tid] = -1;
-            scores_out[tid] = 0xff800000u;
-        }
-    }
-    if (tid == 0) {
-        const long long left = n_cand - n_known;
-        *count_out = left < 0 ? 0 : (left < k ? left : k);
-    }
-}
-
-// The number of live candidates of a row of n_cand slots: *n_live clamped to [0, n_cand]; NULL: every slot.
-__device__ __forceinline__ long long live_count(const int64_t *__restrict__ n_live, long long n_cand) {
-    if (!n_live) return n_cand;
-    const long long v = *n_live;
-    return v < 0 ? 0 : (v < n_cand ? v : n_cand);
-}
 
 __global__ void __launch_bounds__(TOPK_THREADS) topk_chunk_kernel(const float *__restrict__ score, const int64_t *__restrict__ known_ptr,
                                                                   const int64_t *__restrict__ known_index, long long n_cand,
@@ -289,22 +133,8 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_merge_kernel(const float *_
                                                                   const int64_t *__restrict__ n_retired) {
     __shared__ u64 sorted[TOPK_MAX];
     __shared__ TopkScratch s;
-    const int tid = threadIdx.x;
     const long long b = blockIdx.x;
-    const long long total = n_chunk * k;
-    const u64 *src = partial + b * total;
-    int m = 0;
-    for (long long pos = 0; pos < total; pos += TOPK_CHUNK) {
-        u64 held[TOPK_HELD];
-#pragma unroll
-        for (int j = 0; j < TOPK_SLOTS; ++j) {      // the next stretch of partial lists (all loads in flight at once) ...
-            const long long i = pos + tid + j * TOPK_THREADS;
-            held[j] = i < total ? src[i] : 0;
-        }
-        held[TOPK_SLOTS] = tid < m ? sorted[tid] : 0;      // ... and the survivors so far
-        __syncthreads();       // (sorted[] is rewritten by the selection)
-        m = select_topk(held, k, 8, s, sorted);
-    }
+    const int m = merge_partial_lists(partial + b * n_chunk * k, n_chunk * k, k, s, sorted);
     const long long n_known = known_ptr ? known_ptr[b + 1] - known_ptr[b] : 0;
     const long long live = live_count(n_live, n_cand);
     write_answers(score + b * n_cand, live - retired_count(n_retired, live), n_known, k, m, sorted, ids_out + b * k,

@@ -34,6 +34,7 @@ import math
 import torch
 
 from . import _lib, dense, models, selection, tasks
+from .candidates import CandidateSets, span_rows
 from .graph import Capture, param_state
 from .live import LiveGraph, check_live, check_live_relations, check_not_retired, forwarded
 
@@ -56,12 +57,43 @@ def _alive_columns(pred, retired, num_live, index=None):
     return pred[:, cols], cols, index
 
 
-def filtered_rank_reference(pred, pos, ptr, index, num_live=None, retired=None):
+def _among_keep(among, b, n, num_live, retired, dev):
+    """The _reference functions with `among` (per row a vector or list of ids): the (n) bool row of the ELIGIBLE ids of row b's
+    set -- listed, in [0, num_live or n), not retired.  By sets: order and repeats in the list do not matter."""
+    live = n if num_live is None else selection.live_int(num_live, n)
+    ids = torch.as_tensor(among[b], dtype=torch.long, device=dev).flatten()
+    keep = torch.zeros(n, dtype=torch.bool, device=dev)
+    keep[ids[(ids >= 0) & (ids < live)]] = True
+    if retired is not None:
+        gone = torch.as_tensor(retired, dtype=torch.long, device=dev).flatten()
+        keep[gone[(gone >= 0) & (gone < n)]] = False
+    return keep
+
+
+def _among_rows(among, batch):
+    if len(among) != batch:
+        raise ValueError("`among` of a _reference function is one id vector per row: got %d for %d rows" % (len(among), batch))
+    return among
+
+
+def filtered_rank_reference(pred, pos, ptr, index, num_live=None, retired=None, among=None):
     """(rank (batch) int64, num_negative (batch) int64) of pred[b, pos[b]] among the candidates of row b -- the ids not in
     index[ptr[b] : ptr[b + 1]] (the known answers, the positive among them), ties counting against the positive: what
     ultra_filtered_rank computes, in plain torch on any device (tasks.compute_ranking over the mask the lists stand for).
     num_live: only the ids below it exist.  retired (a sorted int64 id vector): those ids do not exist either -- this function on
-    pred with their columns deleted, the positives and the known ids (all alive) renumbered."""
+    pred with their columns deleted, the positives and the known ids (all alive) renumbered.  among (one id vector per row):
+    the candidates of row b are the eligible ids of among[b] (listed, below num_live, not retired) that are not known --
+    rank = 1 + those that score at least pred[b, pos[b]], num_negative = how many there are; pos[b] need not be listed."""
+    if among is not None:
+        batch, n = pred.shape
+        rank = torch.empty(batch, dtype=torch.long, device=pred.device)
+        num_negative = torch.empty(batch, dtype=torch.long, device=pred.device)
+        for b in range(batch):
+            keep = _among_keep(_among_rows(among, batch), b, n, num_live, retired, pred.device)
+            keep[index[int(ptr[b]):int(ptr[b + 1])]] = False
+            rank[b] = 1 + int((keep & (pred[b, pos[b]] <= pred[b])).sum())
+            num_negative[b] = int(keep.sum())
+        return rank, num_negative
     if retired is not None:
         alive, cols, index = _alive_columns(pred, retired, num_live, index)
         return filtered_rank_reference(alive, _alive_columns(pred, retired, num_live, pos)[2], ptr, index)
@@ -73,16 +105,18 @@ def filtered_rank_reference(pred, pos, ptr, index, num_live=None, retired=None):
     return tasks.compute_ranking(pred, pos, mask), mask.sum(dim=-1)
 
 
-def filtered_topk_reference(pred, k, ptr=None, index=None, num_live=None, retired=None):
+def filtered_topk_reference(pred, k, ptr=None, index=None, num_live=None, retired=None, among=None):
     """(ids (batch, k) int64, scores (batch, k) pred's dtype, count (batch) int64) -- per row, the candidates are the ids not
     in index[ptr[b] : ptr[b + 1]], in the order of the stable descending sort of their scores.  num_live: only the ids below it
     exist -- this function on pred[:, :num_live].  retired (a sorted int64 id vector): those ids do not exist either -- this
-    function on pred with their columns deleted (the known ids are alive), the ids mapped back."""
-    if retired is not None:
+    function on pred with their columns deleted (the known ids are alive), the ids mapped back.  among (one id vector per row):
+    the candidates of row b are the eligible ids of among[b] (listed, below num_live, not retired) that are not known, and
+    count[b] = min(k, how many there are)."""
+    if among is None and retired is not None:
         alive, cols, index = _alive_columns(pred, retired, num_live, index)
         ids, scores, count = filtered_topk_reference(alive, k, ptr, index)
         return torch.where(ids >= 0, cols[ids.clamp(min=0)] if len(cols) else ids, ids), scores, count
-    if num_live is not None:
+    if among is None and num_live is not None:
         return filtered_topk_reference(pred[:, :selection.live_int(num_live, pred.shape[1])], k, ptr, index)
     k = int(k)
     batch, n = pred.shape
@@ -90,7 +124,10 @@ def filtered_topk_reference(pred, k, ptr=None, index=None, num_live=None, retire
     scores = torch.full((batch, k), float("-inf"), dtype=pred.dtype, device=pred.device)
     count = torch.zeros(batch, dtype=torch.long, device=pred.device)
     for b in range(batch):
-        keep = torch.ones(n, dtype=torch.bool, device=pred.device)
+        if among is None:
+            keep = torch.ones(n, dtype=torch.bool, device=pred.device)
+        else:
+            keep = _among_keep(_among_rows(among, batch), b, n, num_live, retired, pred.device)
         if ptr is not None:
             keep[index[int(ptr[b]):int(ptr[b + 1])]] = False
         cand = keep.nonzero().flatten()
@@ -123,12 +160,15 @@ def _known_lists(name, ptr, index, batch, dev):
     return ptr.contiguous(), index.contiguous()
 
 
-def filtered_topk(pred, k, ptr=None, index=None, num_live=None, retired=None):
+def filtered_topk(pred, k, ptr=None, index=None, num_live=None, retired=None, among=None, among_capacity=None):
     """filtered_topk_reference through the HIP kernel: pred (batch, N) fp32 on the GPU; ptr (batch + 1) / index int64, ids
     ascending and distinct within a row; ptr None: no filter.  num_live (an int in [1, N], or one int64 on the device, read by
     the kernels): ultra_filtered_topk_live on the full rows -- no slice, no copy; None: ultra_filtered_topk.  retired (the device
     pair (bits, count): live.retired_words over at least N slots and one int64, both read by the kernels):
-    ultra_filtered_topk_alive, with num_live or without."""
+    ultra_filtered_topk_alive, with num_live or without.  among (the device pair (span (batch, 2), index): row b's candidates
+    are index[span[b, 0] : span[b, 1]], ascending and distinct; selection.among_operand): ultra_filtered_topk_among, with
+    num_live and retired or without -- work and workspace O(among_capacity), which defaults to the longest span (one host
+    read; a captured caller passes it)."""
     check_k(k)
     pred = _gpu_scores("filtered_topk", pred)
     batch, n = pred.shape
@@ -140,20 +180,26 @@ def filtered_topk(pred, k, ptr=None, index=None, num_live=None, retired=None):
         return ids, scores, count
     if ptr is not None:
         ptr, index = _known_lists("filtered_topk", ptr, index, batch, dev)
-    ws = torch.empty(max(1, _lib.lib.ultra_filtered_topk_workspace(batch, n, k) // 8), dtype=torch.long, device=dev)
+    among = selection.among_operand(among, batch, n, dev, among_capacity)
+    if among is None:
+        ws_bytes = _lib.lib.ultra_filtered_topk_workspace(batch, n, k)
+    else:
+        ws_bytes = _lib.lib.ultra_filtered_topk_among_workspace(batch, among[2], k)
+    ws = torch.empty(max(1, ws_bytes // 8), dtype=torch.long, device=dev)
     args = (pred.data_ptr(), None if ptr is None else ptr.data_ptr(), None if ptr is None else index.data_ptr(), batch, n, k,
             ids.data_ptr(), scores.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel() * 8)
     live = selection.live_operand(num_live, n, dev)     # (referenced until the launch is enqueued)
-    _select("ultra_filtered_topk", args, live, dev, selection.retired_operand(retired, n, dev))
+    _select("ultra_filtered_topk", args, live, dev, selection.retired_operand(retired, n, dev), among=among)
     return ids, scores, count
 
 
-def filtered_rank(pred, pos, ptr, index, num_live=None, retired=None, out=None):
+def filtered_rank(pred, pos, ptr, index, num_live=None, retired=None, out=None, among=None, among_capacity=None):
     """filtered_rank_reference through the HIP kernel (csrc/rank_kernels.hip): pred (batch, N) fp32 on the GPU; pos (batch), ptr
     (batch + 1) and index int64 on its device, the ids of a row ascending and distinct, the positive among them.  num_live,
     retired: as in filtered_topk -- ultra_filtered_rank_live / ultra_filtered_rank_alive; neither: ultra_filtered_rank.
     out: the pair (rank, num_negative) of (batch) int64 tensors to write into -- a captured step's own buffers -- and to
-    return; None: new ones."""
+    return; None: new ones.  among, among_capacity: as in filtered_topk -- ultra_filtered_rank_among, the rank of the positive
+    among the eligible listed ids that are not known; pos[b] need not be listed."""
     pred = _gpu_scores("filtered_rank", pred)
     batch, n = pred.shape
     dev = pred.device
@@ -170,7 +216,8 @@ def filtered_rank(pred, pos, ptr, index, num_live=None, retired=None, out=None):
     pos = pos.contiguous()      # (referenced until the launch is enqueued)
     args = (pred.data_ptr(), pos.data_ptr(), ptr.data_ptr(), index.data_ptr(), batch, n, rank.data_ptr(), num_negative.data_ptr())
     live = selection.live_operand(num_live, n, dev)     # (referenced until the launch is enqueued)
-    _select("ultra_filtered_rank", args, live, dev, selection.retired_operand(retired, n, dev))
+    _select("ultra_filtered_rank", args, live, dev, selection.retired_operand(retired, n, dev),
+            among=selection.among_operand(among, batch, n, dev, among_capacity), among_at=4)
     return rank, num_negative
 
 
@@ -193,7 +240,7 @@ def logit_threshold(probability):
     return float(torch.tensor(math.log(p / (1.0 - p)), dtype=torch.float64).to(torch.float32))
 
 
-def filtered_above_reference(pred, threshold, ptr=None, index=None, num_live=None, retired=None):
+def filtered_above_reference(pred, threshold, ptr=None, index=None, num_live=None, retired=None, among=None):
     """The answer SET of every row, ranked: (out_ptr (batch + 1) int64, ids (total) int64, scores (total) pred's dtype, size
     (batch) int64), on any device -- the definition ultra_filtered_above is tested against.
 
@@ -211,17 +258,22 @@ def filtered_above_reference(pred, threshold, ptr=None, index=None, num_live=Non
     reference's soft num_pred; query_eval keeps the reference's metrics as they are.
 
     num_live: only the ids below it exist -- this function on pred[:, :num_live].  retired (a sorted int64 id vector): those ids
-    do not exist either, in the lists and in `size` -- this function on pred with their columns deleted, the ids mapped back."""
-    if retired is not None:
+    do not exist either, in the lists and in `size` -- this function on pred with their columns deleted, the ids mapped back.
+    among (one id vector per row): only the eligible ids of among[b] (listed, below num_live, not retired) can be members of
+    row b, in the lists and in `size`."""
+    if among is None and retired is not None:
         alive, cols, index = _alive_columns(pred, retired, num_live, index)
         out_ptr, ids, scores, size = filtered_above_reference(alive, threshold, ptr, index)
         return out_ptr, cols[ids], scores, size
-    if num_live is not None:
+    if among is None and num_live is not None:
         return filtered_above_reference(pred[:, :selection.live_int(num_live, pred.shape[1])], threshold, ptr, index)
     thr = _fp32_threshold(threshold)
     batch, n = pred.shape
     dev = pred.device
     member = pred.float() > torch.tensor(thr, dtype=torch.float32, device=dev)
+    if among is not None:
+        member &= torch.stack([_among_keep(_among_rows(among, batch), b, n, num_live, retired, dev) for b in range(batch)]) \
+            if batch else member
     size = member.sum(dim=-1)
     out_ptr = torch.zeros(batch + 1, dtype=torch.long, device=dev)
     ids, scores = [], []
@@ -239,20 +291,22 @@ def filtered_above_reference(pred, threshold, ptr=None, index=None, num_live=Non
     return out_ptr, ids, scores, size
 
 
-def filtered_above(pred, threshold, ptr=None, index=None, num_live=None, retired=None):
+def filtered_above(pred, threshold, ptr=None, index=None, num_live=None, retired=None, among=None, among_capacity=None):
     """filtered_above_reference through the HIP kernels (csrc/above_kernels.hip): pred (batch, N) fp32 on the GPU; ptr
     (batch + 1) / index int64, ids ascending and distinct within a row; ptr None: no filter.  `ids` and `scores` come back as
     the full-capacity (batch * N) buffers: entries at or beyond out_ptr[batch] are unspecified.  No host wait is made -- the
     caller reads out_ptr[-1] when it wants to slice.  num_live (an int in [1, N], or one int64 on the device, read by the
     kernels): ultra_filtered_above_live on the full rows; None: ultra_filtered_above.  retired (the device pair (bits, count) of
-    filtered_topk): ultra_filtered_above_alive."""
+    filtered_topk): ultra_filtered_above_alive.  among, among_capacity: as in filtered_topk -- ultra_filtered_above_among; the
+    buffers that come back then hold batch * among_capacity entries."""
     thr = _fp32_threshold(threshold)
     pred = _gpu_scores("filtered_above", pred)
     batch, n = pred.shape
     dev = pred.device
+    among = selection.among_operand(among, batch, n, dev, among_capacity) if batch else None
     out_ptr = torch.zeros(batch + 1, dtype=torch.long, device=dev)
-    ids = torch.empty(batch * n, dtype=torch.long, device=dev)
-    scores = torch.empty(batch * n, dtype=torch.float32, device=dev)
+    ids = torch.empty(batch * (n if among is None else among[2]), dtype=torch.long, device=dev)
+    scores = torch.empty(ids.numel(), dtype=torch.float32, device=dev)
     size = torch.empty(batch, dtype=torch.long, device=dev)
     if batch == 0:
         return out_ptr, ids, scores, size
@@ -260,11 +314,15 @@ def filtered_above(pred, threshold, ptr=None, index=None, num_live=None, retired
         raise ValueError("filtered_above takes 1 to %d rows of at least one candidate, got %s" % (_lib.ABOVE_MAX_BATCH, tuple(pred.shape)))
     if ptr is not None:
         ptr, index = _known_lists("filtered_above", ptr, index, batch, dev)
-    ws = torch.empty(max(1, _lib.lib.ultra_filtered_above_workspace(batch, n) // 8), dtype=torch.long, device=dev)
+    if among is None:
+        ws_bytes = _lib.lib.ultra_filtered_above_workspace(batch, n)
+    else:
+        ws_bytes = _lib.lib.ultra_filtered_above_among_workspace(batch, among[2])
+    ws = torch.empty(max(1, ws_bytes // 8), dtype=torch.long, device=dev)
     args = (pred.data_ptr(), None if ptr is None else ptr.data_ptr(), None if ptr is None else index.data_ptr(), batch, n, thr,
             out_ptr.data_ptr(), ids.data_ptr(), scores.data_ptr(), ids.numel(), size.data_ptr(), ws.data_ptr(), ws.numel() * 8)
     live = selection.live_operand(num_live, n, dev)     # (referenced until the launch is enqueued)
-    _select("ultra_filtered_above", args, live, dev, selection.retired_operand(retired, n, dev))
+    _select("ultra_filtered_above", args, live, dev, selection.retired_operand(retired, n, dev), among=among)
     return out_ptr, ids, scores, size
 
 
@@ -304,9 +362,18 @@ class _IndexedStep(Capture):
     `params`, `capacity` (of `index`; 0 for index_capacity None -- no filter, nothing to load), `delta` and its `route`, and
     `retired`; `n_live` is the device live count the selection reads at replay."""
 
-    def __init__(self, model, data, batch_size, index_capacity, delta, n_live, retired):
+    def __init__(self, model, data, batch_size, index_capacity, delta, n_live, retired, among=None):
+        """among (None, or (index capacity, list capacity): a step that selects among candidate lists): two
+        more buffers -- `among_span` (bs, 2), copied per batch like `ptr`, and `among_index`, loaded once per call like
+        `index` -- and the fixed `among_capacity` its selection is recorded with; `among_operand` is the triple it passes."""
         dev = data.edge_index.device
         Capture.__init__(self, dev)
+        self.among_operand = None
+        if among is not None:
+            self.among_capacity = max(1, int(among[1]))
+            self.among_span = torch.zeros(batch_size, 2, dtype=torch.long, device=dev)
+            self.among_index = torch.zeros(max(1, int(among[0])), dtype=torch.long, device=dev)
+            self.among_operand = (self.among_span, self.among_index, self.among_capacity)
         self.model, self.bs = model, batch_size
         self.delta, self.route, self.n_live, self.retired = delta, _delta_route(delta), n_live, retired
         self.filtered = index_capacity is not None
@@ -334,14 +401,24 @@ class _IndexedStep(Capture):
     def load_index(self, index):
         self.index[:index.numel()].copy_(index, non_blocking=True)
 
+    def load_among(self, index):
+        self.among_index[:index.numel()].copy_(index, non_blocking=True)
+
+    def among_fits(self, total, longest):
+        """Do a call's candidate lists -- `total` ids, the longest `longest` -- fit this step's buffer and capacity?"""
+        return self.among_operand is not None and total <= self.among_index.numel() and longest <= self.among_capacity
+
 
 class _GraphedPredictStep(_IndexedStep):
     """One batch of one direction as ONE hipGraph replay (a graph.Capture, like graph.GraphedEvalStep): candidate construction, the
     forward and ultra_filtered_topk.  Per batch the host copies the (bs) anchors and relations and the (bs + 1) offsets into
     the known lists of the whole call, which live in a buffer of the step (`load_index`, once per call)."""
 
-    def __init__(self, model, data, batch_size, k, mode, index_capacity, warmup=2, delta=None, n_live=None, retired=None):
-        """n_live (one int64 on the device, or None): the live count of a graph with reserved rows -- the selection is then
+    def __init__(self, model, data, batch_size, k, mode, index_capacity, warmup=2, delta=None, n_live=None, retired=None,
+                 among=None):
+        """among (None, or _IndexedStep's (index capacity, list capacity)): the selection is ultra_filtered_topk_among over the
+        step's own span and list buffers, n_live and retired its nullable operands; None: exactly the step of before.
+        n_live (one int64 on the device, or None): the live count of a graph with reserved rows -- the selection is then
         ultra_filtered_topk_live, which reads it at replay; None: ultra_filtered_topk, exactly as before.
         retired (the device pair (bitmap, count) of a graph that retired entities, or None): the selection is
         ultra_filtered_topk_alive, which reads both at replay -- `retired` is what the Predictor compares.
@@ -349,7 +426,7 @@ class _GraphedPredictStep(_IndexedStep):
         normal path; once it holds facts or tombstones the capture records the delta's launches, which read its device buffers
         at replay --
         `route` is what the Predictor compares to know whether this capture still serves the delta."""
-        _IndexedStep.__init__(self, model, data, batch_size, index_capacity, delta, n_live, retired)
+        _IndexedStep.__init__(self, model, data, batch_size, index_capacity, delta, n_live, retired, among)
         dev = data.edge_index.device
         self.k, self.mode = k, mode
         model_kwargs = {} if delta is None else {"delta": delta}
@@ -359,7 +436,10 @@ class _GraphedPredictStep(_IndexedStep):
         self.scores = torch.empty(batch_size, k, dtype=torch.float32, device=dev)
         self.count = torch.empty(batch_size, dtype=torch.long, device=dev)
         n = int(data.num_nodes)
-        ws_bytes = _lib.lib.ultra_filtered_topk_workspace(batch_size, n, k)
+        if among is None:
+            ws_bytes = _lib.lib.ultra_filtered_topk_workspace(batch_size, n, k)
+        else:
+            ws_bytes = _lib.lib.ultra_filtered_topk_among_workspace(batch_size, self.among_capacity, k)
         self.ws = torch.empty(max(1, ws_bytes // 8), dtype=torch.long, device=dev)
 
         def step():
@@ -367,7 +447,7 @@ class _GraphedPredictStep(_IndexedStep):
             args = (pred.data_ptr(), self.ptr.data_ptr() if self.filtered else None,
                     self.index.data_ptr() if self.filtered else None, batch_size, n, k, self.ids.data_ptr(),
                     self.scores.data_ptr(), self.count.data_ptr(), self.ws.data_ptr(), self.ws.numel() * 8)
-            _select("ultra_filtered_topk", args, n_live, dev, retired)
+            _select("ultra_filtered_topk", args, n_live, dev, retired, among=self.among_operand)
 
         self.record_step(step, warmup, (self.anchor, self.relation), (self.ids, self.scores, self.count))
 
@@ -513,14 +593,16 @@ class _GraphedVerifyStep(_IndexedStep):
     candidates, the masked forward on the full graph's cached plans, ultra_filtered_rank and the gather of the positives' scores.
     Per batch the host copies the triples and the (bs + 1) offsets into the known lists of the whole call (`load_index`)."""
 
-    def __init__(self, model, data, batch_size, mode, index_capacity, warmup=2, n_live=None, delta=None, retired=None):
-        """n_live: as in _GraphedPredictStep -- ultra_filtered_rank_live over the live ids, or (None) ultra_filtered_rank.
+    def __init__(self, model, data, batch_size, mode, index_capacity, warmup=2, n_live=None, delta=None, retired=None,
+                 among=None):
+        """among: as in _GraphedPredictStep -- ultra_filtered_rank_among, which zeroes with a kernel.
+        n_live: as in _GraphedPredictStep -- ultra_filtered_rank_live over the live ids, or (None) ultra_filtered_rank.
         retired: as in _GraphedPredictStep -- ultra_filtered_rank_alive, which takes a NULL live count and zeroes with a kernel.
         delta (rspmm.GraphDelta or None; a model with the leave_out route): while it holds no edit the step records the masked
         forward above; once it holds facts or tombstones it records model(..., leave_out=triples, delta=delta) -- the keep rows
         over the base edge list, the same edges as per-sample keys (GraphDelta.sample_keys into the step's own key buffers) and
         the delta's fix-up launches, which read its device buffers at replay.  `route` is what the Predictor compares."""
-        _IndexedStep.__init__(self, model, data, batch_size, index_capacity, delta, n_live, retired)
+        _IndexedStep.__init__(self, model, data, batch_size, index_capacity, delta, n_live, retired, among)
         dev = data.edge_index.device
         self.mode = mode
         live = delta is not None and delta.edited
@@ -535,7 +617,8 @@ class _GraphedVerifyStep(_IndexedStep):
         # The live route is replayed between eager edits (add_facts / remove_facts run torch ops of their own), and a memset node
         # captured into a hipGraph replays wrongly once eager memsets interleave with the replays (csrc/rank_kernels.hip): its
         # rank goes through the live-count entry, which zeroes with a kernel -- over all n ids where no rows are reserved.
-        self.n_all = torch.full((1,), int(data.num_nodes), dtype=torch.long, device=dev) if live and n_live is None and retired is None else None
+        self.n_all = (torch.full((1,), int(data.num_nodes), dtype=torch.long, device=dev)
+                      if live and n_live is None and retired is None and among is None else None)
         rank_count = n_live if n_live is not None else self.n_all
 
         def step():
@@ -548,7 +631,11 @@ class _GraphedVerifyStep(_IndexedStep):
                 keep = ent.leave_one_out_keep(data, self.triples, out=self.keep, validate=False)
                 pred = model(data, _candidates(data, anchor, r, mode), edge_keep=keep).float().contiguous()
             pos = pos.contiguous()
-            filtered_rank(pred, pos, self.ptr, self.index, num_live=rank_count, retired=retired, out=(self.rank, self.num_negative))
+            if among is None:
+                filtered_rank(pred, pos, self.ptr, self.index, num_live=rank_count, retired=retired, out=(self.rank, self.num_negative))
+            else:
+                filtered_rank(pred, pos, self.ptr, self.index, num_live=n_live, retired=retired, out=(self.rank, self.num_negative),
+                              among=(self.among_span, self.among_index), among_capacity=self.among_capacity)
             self.score.copy_(pred.gather(1, pos.unsqueeze(-1)).squeeze(-1))
 
         self.record_step(step, warmup, (self.triples,), (self.score, self.rank, self.num_negative))
@@ -653,6 +740,9 @@ class Predictor(object):
                                relation_bits_budget=relation_bits_budget, live_relation_graph=live_relation_graph)
         self.model, self.k, self.batch_size = model, k, int(batch_size)
         self.filtered, self.use_graph = bool(filtered), bool(use_graph)
+        # (ids are stable: the sets outlive compact() and a rebuild.  The registry reads the slot count off the LiveGraph, not
+        # off the predictor: no cycle, so __del__ runs with the last reference)
+        self._sets = CandidateSets(functools.partial(getattr, self._live, "num_slots"))
 
     # ---- the state of the served graph: held by the LiveGraph ("The live graph's state in one place") ----
     data = forwarded("graph")
@@ -669,6 +759,20 @@ class Predictor(object):
     num_relation_slots = forwarded("num_relation_slots")
     num_retired = forwarded("num_retired")
     retired_entities = forwarded("retired_entities")
+
+    # ---- candidate sets ----
+    def define_set(self, name, ids):
+        """Name a candidate set: `among=name` of tails / heads / ..._above / verify_* / explain_* then restricts a query's
+        candidates to `ids` -- any slots of the graph, sorted and de-duplicated here (ValueError outside [0, num_slots)); an id
+        in the reserve or a retired one is absent until it is live and alive.  Replaces a set of that name; returns its size."""
+        return self._sets.define_set(name, ids)
+
+    def drop_set(self, name):
+        self._sets.drop_set(name)
+
+    def sets(self):
+        """{name: size} of the candidate sets defined now."""
+        return self._sets.sets()
 
     # ---- the growing vocabulary ----
     def add_relations(self, count=1):
@@ -755,26 +859,32 @@ class Predictor(object):
         delta = self.delta      # (handed over whenever it exists, empty or not: the capture relies on it)
         return {} if delta is None else {"delta": delta}
 
-    def tails(self, h, r):
-        return self._run(*self._query(h, r), "tail")
+    def tails(self, h, r, among=None):
+        """among (None: every entity): the candidates of query i are the ids of a set -- a name (define_set), a 1-D
+        id vector or list (one set for every query) or a sequence of one name or vector per query (ValueError for a wrong
+        count, KeyError for an unknown name, ValueError for an id outside [0, num_slots)) -- that are live, alive and not
+        known: count[i] = min(k, how many there are).  The selection gathers the listed scores (ultra_filtered_topk_among): the
+        same order and bits as the full ranking restricted to the set.  Captured under a key of its own; a later call whose
+        sets fit the step's buffers records nothing."""
+        return self._run(*self._query(h, r), "tail", among)
 
-    def heads(self, t, r):
-        return self._run(*self._query(t, r), "head")
+    def heads(self, t, r, among=None):
+        return self._run(*self._query(t, r), "head", among)
 
-    def tails_above(self, h, r, min_score):
+    def tails_above(self, h, r, min_score, among=None):
         """Every tail of (h[i], r[i], ?) whose logit exceeds `min_score` (a Python float: the threshold of
         filtered_above_reference), ranked: (ptr (n + 1) int64, ids, scores, size (n) int64) for the whole call, in query order
         -- the set of query i is ids[ptr[i] : ptr[i + 1]], best first; known answers are left out as in `tails`, while size[i]
         counts every entity above the threshold, known ones included.  The forward runs eagerly, batch by batch, and
         ultra_filtered_above selects on the device; the host reads one number per batch (the batch's total) to slice the
         batch's lists out of their full-capacity buffers.  Off the GPU the plain-torch restatement selects, as in `tails`."""
-        return self._run_above(h, r, min_score, "tail")
+        return self._run_above(h, r, min_score, "tail", among)
 
-    def heads_above(self, t, r, min_score):
+    def heads_above(self, t, r, min_score, among=None):
         """tails_above for the heads of (?, r[i], t[i])."""
-        return self._run_above(t, r, min_score, "head")
+        return self._run_above(t, r, min_score, "head", among)
 
-    def explain_tails(self, h, r, chunk=16, compact=True):
+    def explain_tails(self, h, r, chunk=16, compact=True, among=None):
         """tails(h, r) plus why: (ids, scores, count, explanations).  explanations[i][j], j < count[i], is the (paths, weights)
         of model.visualize_batch for the triple (h[i], ids[i, j], r[i]) -- answer j of query i -- so every path runs from
         h[i] to the answer.  The answers come from the same captured step as tails; the explanations run `chunk` triples a
@@ -787,16 +897,16 @@ class Predictor(object):
         materialised route up to fp32 re-association, not bit for bit; given the gradients the beam search is exact.  Paths
         whose weights differ by less than that may come in another order.  ValueError on a model the route does not serve
         (explain_live_supported: sum / DistMult / fp32 entity layers); an unedited delta is compact=True."""
-        return self._explain(h, r, "tail", chunk, compact)
+        return self._explain(h, r, "tail", chunk, compact, among)
 
-    def explain_heads(self, t, r, chunk=16, compact=True):
+    def explain_heads(self, t, r, chunk=16, compact=True, among=None):
         """heads(t, r) plus why.  The model scores (?, r, t) as the TAIL query (t, r + num_direct_rel, ?) -- the inverse
         relation, as in evaluation -- so the triple explained for answer a is (t[i], a, r[i] + num_direct_rel), the one whose
         score was served: every path runs from t[i] to the answer over the graph's edges, inverse ones included.  `compact` as
         in explain_tails."""
-        return self._explain(t, r, "head", chunk, compact)
+        return self._explain(t, r, "head", chunk, compact, among)
 
-    def _explain(self, anchor, relation, mode, chunk, compact=True):
+    def _explain(self, anchor, relation, mode, chunk, compact=True, among=None):
         if not hasattr(self.model, "visualize_batch"):
             raise TypeError("%s cannot explain its answers: models.Ultra and models.EntityNBFNet (visualize_batch) can"
                             % type(self.model).__name__)
@@ -813,7 +923,7 @@ class Predictor(object):
             else:
                 live = {"delta": self.delta}
         anchor, relation = self._query(anchor, relation)
-        ids, scores, count = self._run(anchor, relation, mode)
+        ids, scores, count = self._run(anchor, relation, mode) if among is None else self._run(anchor, relation, mode, among)
         dev = ids.device
         if mode == "head":
             relation = relation + self.data.num_relations // 2
@@ -832,7 +942,7 @@ class Predictor(object):
             at += c
         return ids, scores, count, explanations
 
-    def verify_tails(self, h, r, t):
+    def verify_tails(self, h, r, t, among=None):
         """How plausible is each STATED fact (h[i], r[i], t[i]) given the rest of the graph?  Scoring a triple that is an edge of
         the graph says nothing -- its own edge is a one-hop path from h to t -- so fact i is scored on the graph WITHOUT itself
         and its inverse (with the model's `remove_one_hop`: without any edge between the two nodes), while it still sees every
@@ -842,13 +952,14 @@ class Predictor(object):
         logit of t[i] as the tail of (h[i], r[i], ?); rank (n) int64: 1 + the candidates outside the filter graph's known tails
         of (h[i], r[i]) that score at least as high; num_negative (n) int64: how many such candidates there are).  r must be
         direct relations (ValueError).  On the GPU with use_graph each batch is one hipGraph replay; predict.verify_reference
-        is the plain-torch restatement."""
-        return self._verify(h, r, t, "tail")
+        is the plain-torch restatement.  among (as in `tails`): the type-constrained filtered rank -- rank and num_negative
+        count only the candidates of fact i's set (ultra_filtered_rank_among); t[i] itself need not be in it."""
+        return self._verify(h, r, t, "tail", among)
 
-    def verify_heads(self, h, r, t):
+    def verify_heads(self, h, r, t, among=None):
         """verify_tails for h[i] as the head of (?, r[i], t[i]): scored as the tail query (t[i], r[i] + num_direct_rel, ?), exactly
         as evaluation does; the removed edges are the same two."""
-        return self._verify(h, r, t, "head")
+        return self._verify(h, r, t, "head", among)
 
     def close(self):
         """Drop the captured steps (their plans are unpinned)."""
@@ -873,30 +984,40 @@ class Predictor(object):
             check_live_relations(relation, self.num_direct_relations, "the relations of a query")
         return anchor, relation
 
-    def _step(self, key, need, build):
+    def _step(self, key, need, build, among_need=None):
         """The captured step `key` of `_steps`, (re)built -- build(capacity) -- when there is none, the weights changed, the known
-        lists of the call (`need` ids; None: no filter) do not fit its buffer, the delta, its route or the retired pair changed."""
+        lists of the call (`need` ids; None: no filter) do not fit its buffer, the delta, its route or the retired pair changed.
+        among_need ((ids in all, longest list) of a call with candidate sets; None: none): ... or the call's lists do not fit the
+        step's buffer or its longest list its capacity -- build(capacity, (index capacity, list capacity)) then, both doubled."""
         step = self._steps.get(key)
         if step is not None and step.params == param_state(self.model) and (need is None or need <= step.capacity) \
-                and step.delta is self.delta and step.route == _delta_route(self.delta) and step.retired is self._live.retired_operand:
+                and step.delta is self.delta and step.route == _delta_route(self.delta) and step.retired is self._live.retired_operand \
+                and (among_need is None or step.among_fits(*among_need)):
             return step
         if step is not None:
             step.release()
             del self._steps[key]
-        step = self._steps[key] = build(None if need is None else max(2 * need, 1 << 16))
+        capacity = None if need is None else max(2 * need, 1 << 16)
+        if among_need is None:
+            step = self._steps[key] = build(capacity)
+        else:       # (a list capacity up to a chunk costs one chunk: no less is reserved)
+            step = self._steps[key] = build(capacity, (max(2 * among_need[0], 1 << 16), max(2 * among_need[1], _lib.TOPK_CHUNK)))
         return step
 
-    def _batched(self, key, build, rows, ptr, index, outs, eager, capturable=True):
+    def _batched(self, key, build, rows, ptr, index, outs, eager, capturable=True, among=None):
         """The batch loop of tails / heads / verify_*, inside eval_mode: `rows` (the per-query tensors a step takes) in batches of
         batch_size into `outs`.  On the GPU with use_graph each batch is one replay of the captured step `key` (_step): a last
         batch that is short is padded with copies of its last row with no known list, `index` is loaded once, and the step's
         buffers are copied out, the padded rows dropped.  A model outside the fused inference path (models.NotOnFusedPath),
-        and every other case: eager(lo) gives the outputs of the batch that starts at row lo."""
+        and every other case: eager(lo) gives the outputs of the batch that starts at row lo.
+        among (None, or the call's (span, index, longest) of CandidateSets.assemble): the step -- under a key of its own --
+        takes the call's lists once (load_among) and a batch's spans per replay; a padded row gets an empty span."""
         n, bs = len(rows[0]), self.batch_size
         start = 0
         if capturable and self.use_graph and outs[0].is_cuda and not self._eager_only:
             try:
-                step = self._step(key, None if index is None else index.numel(), build)
+                step = self._step(key, None if index is None else index.numel(), build,
+                                  None if among is None else (among[1].numel(), among[2]))
                 pad = (-n) % bs
                 padded, ptr_p = rows, ptr
                 if pad:
@@ -904,7 +1025,12 @@ class Predictor(object):
                     ptr_p = None if ptr is None else torch.cat([ptr, ptr[-1:].expand(pad)])
                 if index is not None:
                     step.load_index(index)
+                if among is not None:
+                    step.load_among(among[1])
+                    span_p = torch.cat([among[0], among[0].new_zeros(pad, 2)]) if pad else among[0]
                 for lo in range(0, n, bs):
+                    if among is not None:
+                        step.among_span.copy_(span_p[lo:lo + bs], non_blocking=True)
                     got = step(*(t[lo:lo + bs] for t in padded), None if ptr_p is None else ptr_p[lo:lo + bs + 1])
                     for out, b_out in zip(outs, got):
                         out[lo:lo + bs].copy_(b_out[:min(bs, n - lo)], non_blocking=True)
@@ -917,7 +1043,7 @@ class Predictor(object):
                 out[lo:lo + len(b_out)] = b_out
 
     @torch.no_grad()
-    def _verify(self, h, r, t, mode):
+    def _verify(self, h, r, t, mode, among=None):
         h, r, t = _check_facts(self.data, h, r, t, num_live=self.num_entities if self.entity_capacity else None,
                                num_direct=self.num_direct_relations if self.relation_capacity else None,
                                retired=self.retired_entities)
@@ -935,6 +1061,8 @@ class Predictor(object):
         if n == 0:
             return outs
         ent = _entity_model(self.model)
+        if among is not None:
+            among = self._sets.assemble(among, n, dev)
         with eval_mode(self.model):
             triples = torch.stack([h, t, r], dim=-1)
             ptr, index = tasks.known_answers(self.filter_graph, triples, mode)      # the known lists of the whole call, once
@@ -952,21 +1080,38 @@ class Predictor(object):
                 pos = pos.contiguous()
                 # the kernel on the GPU; the restatement with the same interface elsewhere, as in `tails`
                 rank_of = filtered_rank if pred.is_cuda else filtered_rank_reference
-                b_rank, b_neg = rank_of(pred, pos, ptr[lo:lo + len(part) + 1], index, **self._live.selection_for(pred.is_cuda))
+                b_rank, b_neg = rank_of(pred, pos, ptr[lo:lo + len(part) + 1], index, **self._live.selection_for(pred.is_cuda),
+                                        **self._among_for(among, lo, len(part), pred.is_cuda))
                 return pred.gather(1, pos.unsqueeze(-1)).squeeze(-1), b_rank, b_neg
 
-            self._batched("verify_" + mode, lambda capacity: _GraphedVerifyStep(
-                self.model, data, bs, mode, capacity, n_live=self.live_count, delta=delta, retired=self._live.retired_operand),
-                (triples,), ptr, index, outs, eager, capturable=bs <= dense.LEAVE_ONE_OUT_MAX_SAMPLES)
+            self._batched("verify_" + mode if among is None else ("verify_" + mode, "among"),
+                          lambda capacity, among_sizes=None: _GraphedVerifyStep(
+                              self.model, data, bs, mode, capacity, n_live=self.live_count, delta=delta,
+                              retired=self._live.retired_operand, **({} if among_sizes is None else {"among": among_sizes})),
+                          (triples,), ptr, index, outs, eager, capturable=bs <= dense.LEAVE_ONE_OUT_MAX_SAMPLES, among=among)
         return outs
 
+    @staticmethod
+    def _among_for(among, lo, rows, on_gpu):
+        """The among= arguments of one eager batch -- rows [lo, lo + rows) of the call's assembled (span, index, longest) -- for
+        the kernels' wrappers (the device pair and the capacity) or for the _reference functions (a list of id vectors)."""
+        if among is None:
+            return {}
+        span, index, longest = among
+        part = span[lo:lo + rows].contiguous()
+        if on_gpu:
+            return {"among": (part, index), "among_capacity": max(1, longest)}
+        return {"among": span_rows(part, index)}
+
     @torch.no_grad()
-    def _run_above(self, anchor, relation, min_score, mode):
+    def _run_above(self, anchor, relation, min_score, mode, among=None):
         threshold = _fp32_threshold(min_score)
         data, bs, live, model_kwargs = self.data, self.batch_size, self._live, self._model_kwargs()
         dev = data.edge_index.device
         anchor, relation = self._query(anchor, relation)
         n = len(anchor)
+        if among is not None:
+            among = self._sets.assemble(among, n, dev)
         out_ptr, ids, scores, size = [torch.zeros(1, dtype=torch.long, device=dev)], [], [], []
         with eval_mode(self.model):
             ptr = index = None
@@ -978,12 +1123,14 @@ class Predictor(object):
                                   **model_kwargs).float()
                 b_ptr = None if ptr is None else ptr[lo:lo + len(pred) + 1]
                 if pred.is_cuda:
-                    b_out, b_ids, b_scores, b_size = filtered_above(pred, threshold, b_ptr, index, **live.selection_for(pred.is_cuda))
+                    b_out, b_ids, b_scores, b_size = filtered_above(pred, threshold, b_ptr, index, **live.selection_for(pred.is_cuda),
+                                                                    **self._among_for(among, lo, len(pred), True))
                     total = int(b_out[-1])      # (the one host read of the batch)
                     b_ids, b_scores = b_ids[:total].clone(), b_scores[:total].clone()
                 else:
                     b_out, b_ids, b_scores, b_size = filtered_above_reference(pred, threshold, b_ptr, index,
-                                                                              **live.selection_for(pred.is_cuda))
+                                                                              **live.selection_for(pred.is_cuda),
+                                                                              **self._among_for(among, lo, len(pred), False))
                     total = b_ids.numel()
                 out_ptr.append(b_out[1:] + at)
                 ids.append(b_ids)
@@ -996,13 +1143,15 @@ class Predictor(object):
         return torch.cat(out_ptr), torch.cat(ids), torch.cat(scores), torch.cat(size)
 
     @torch.no_grad()
-    def _run(self, anchor, relation, mode):
-        """tails / heads of the queries (anchor, relation) as _query gives them."""
+    def _run(self, anchor, relation, mode, among=None):
+        """tails / heads of the queries (anchor, relation) as _query gives them; among: as the caller gave it."""
         data, bs, k, live, model_kwargs = self.data, self.batch_size, self.k, self._live, self._model_kwargs()
         dev = data.edge_index.device
         n = len(anchor)
         outs = (torch.empty(n, k, dtype=torch.long, device=dev), torch.empty(n, k, dtype=torch.float32, device=dev),
                 torch.empty(n, dtype=torch.long, device=dev))       # (ids, scores, count)
+        if among is not None:
+            among = self._sets.assemble(among, n, dev)
         if n == 0:
             return outs
         with eval_mode(self.model):
@@ -1014,9 +1163,11 @@ class Predictor(object):
                 pred = self.model(data, _candidates(data, anchor[lo:lo + bs], relation[lo:lo + bs], mode), **model_kwargs).float()
                 # the fused kernel on the GPU; the restatement with the same interface elsewhere (as eval._local_rows does)
                 select = filtered_topk if pred.is_cuda else filtered_topk_reference
-                return select(pred, k, None if ptr is None else ptr[lo:lo + len(pred) + 1], index, **live.selection_for(pred.is_cuda))
+                return select(pred, k, None if ptr is None else ptr[lo:lo + len(pred) + 1], index, **live.selection_for(pred.is_cuda),
+                              **self._among_for(among, lo, len(pred), pred.is_cuda))
 
-            self._batched(mode, lambda capacity: _GraphedPredictStep(
-                self.model, data, bs, k, mode, capacity, delta=self.delta, n_live=self.live_count, retired=self._live.retired_operand),
-                (anchor, relation), ptr, index, outs, eager)
+            self._batched(mode if among is None else (mode, "among"), lambda capacity, among_sizes=None: _GraphedPredictStep(
+                self.model, data, bs, k, mode, capacity, delta=self.delta, n_live=self.live_count, retired=self._live.retired_operand,
+                **({} if among_sizes is None else {"among": among_sizes})),
+                (anchor, relation), ptr, index, outs, eager, among=among)
         return outs

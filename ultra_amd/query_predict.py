@@ -24,12 +24,19 @@ does (§28) -- their facts retracted, their ids never a candidate, an entailed a
 retirement on the lists leave the ids of the device bitmap out (ultra_nonzero_lists_alive: after a negation a retired slot holds
 1.0 in the middle of the id range) and the selection runs over the alive ids (ultra_filtered_topk_alive /
 ultra_filtered_above_alive).
+
+CANDIDATE sets: `answers(queries, among=)` / `answer_sets(queries, probability, among=)` restrict a query's
+candidates to a set -- a name (`define_set`), one id vector for every query, or one name or vector per query, which follows its
+query through the grouping into batches.  The entailed lists stay the deny list; the selection gathers the listed logits
+(ultra_filtered_topk_among / ultra_filtered_above_among) with the live count and the retired set as its optional operands.
 """
 import contextlib
+import functools
 
 import torch
 
 from . import predict, query_exec
+from .candidates import CandidateSets, span_rows
 from .live import LiveGraph, forwarded
 from .ultraquery import Query, _logic
 
@@ -65,6 +72,9 @@ class QueryPredictor(object):
         self.model, self.k, self.batch_size = model, k, int(batch_size)
         self.filtered, self.logic = bool(filtered), logic
         self._executor = query_exec.Executor()
+        # (ids are stable: the sets outlive compact() and a rebuild.  The registry reads the slot count off the LiveGraph, not
+        # off the predictor: no cycle, so __del__ runs with the last reference)
+        self._sets = CandidateSets(functools.partial(getattr, self._live, "num_slots"))
 
     # ---- the state of the served graph: held by the LiveGraph ("The live graph's state in one place") ----
     graph = forwarded("graph")
@@ -76,6 +86,19 @@ class QueryPredictor(object):
     live_count = forwarded("live_count")
     num_retired = forwarded("num_retired")
     retired_entities = forwarded("retired_entities")
+
+    # ---- candidate sets (the rules of Predictor.define_set) ----
+    def define_set(self, name, ids):
+        """Name a candidate set for `among=name`: any slots of the graph, sorted and de-duplicated (ValueError outside
+        [0, num_slots)); an id in the reserve or a retired one is absent until it is live and alive.  Returns its size."""
+        return self._sets.define_set(name, ids)
+
+    def drop_set(self, name):
+        self._sets.drop_set(name)
+
+    def sets(self):
+        """{name: size} of the candidate sets defined now."""
+        return self._sets.sets()
 
     # ---- the growing graph (the rules of Predictor.add_entities) ----
     def add_entities(self, count=1):
@@ -182,12 +205,14 @@ class QueryPredictor(object):
         return [index for index, _ in self._programs(queries)]
 
     @contextlib.contextmanager
-    def _batches(self, plan):
+    def _batches(self, plan, among=None):
         """The batches of `plan` (_programs) as answers and answer_sets run them: inside the block the model is in eval mode
         under this predictor's logic (both restored on the way out), and the value is an iterator of (index, logits, ptr, known,
         live) -- the batch's query indices, its logits from the compiled executor, the lists of its entailed answers (None, None
         unless filtered) and the kwargs of the selection: the live count and, once an entity was retired, the retired set
-        (LiveGraph.selection_for) -- the lists take the same two."""
+        (LiveGraph.selection_for) -- the lists take the same two.  among (the call's assembled (span, index, longest), or None):
+        the kwargs gain the batch's candidate lists -- the spans of its queries, through `index` -- in the form the selection
+        of that device takes."""
         graph, live_graph, delta_kwargs = self.graph, self._live, self._delta_kwargs()
 
         def run():
@@ -198,6 +223,13 @@ class QueryPredictor(object):
                 ptr = known = None
                 if self.filtered:
                     ptr, known = query_exec.nonzero_lists(sym, **live) if logits.is_cuda else self._known_reference(sym, len(index))
+                if among is not None:
+                    span, listed, longest = among
+                    part = span[torch.tensor(index, dtype=torch.long, device=span.device)].contiguous()
+                    if logits.is_cuda:
+                        live = dict(live, among=(part, listed), among_capacity=max(1, longest))
+                    else:
+                        live = dict(live, among=span_rows(part, listed))
                 yield index, logits, ptr, known, live
 
         logic = self.model.logic
@@ -210,14 +242,18 @@ class QueryPredictor(object):
                 self.model.logic = logic
 
     @torch.no_grad()
-    def answers(self, queries):
+    def answers(self, queries, among=None):
+        """among (None: every entity): a candidate set per query -- a name, one id vector for all, or one name or vector per
+        query, in input order (CandidateSets.resolve) -- count[i] = min(k, its ids that are live, alive and not entailed)."""
         dev = self.graph.edge_index.device
         plan = self._programs(queries)
         n, k = sum(len(index) for index, _ in plan), self.k
+        if among is not None:
+            among = self._sets.assemble(among, n, dev)
         ids = torch.empty(n, k, dtype=torch.long, device=dev)
         scores = torch.empty(n, k, dtype=torch.float32, device=dev)
         count = torch.empty(n, dtype=torch.long, device=dev)
-        with self._batches(plan) as batches:
+        with self._batches(plan, among) as batches:
             for index, logits, ptr, known, live in batches:
                 select = predict.filtered_topk if logits.is_cuda else predict.filtered_topk_reference
                 got = select(logits, k, ptr, known, **live)
@@ -226,7 +262,7 @@ class QueryPredictor(object):
         return ids, scores, count
 
     @torch.no_grad()
-    def answer_sets(self, queries, probability=0.5):
+    def answer_sets(self, queries, probability=0.5, among=None):
         """The answer SET of every query, ranked: (ptr (n + 1) int64, ids, scores, size (n) int64) in INPUT order -- the set of
         query i is ids[ptr[i] : ptr[i + 1]], best first.  An entity belongs to the set iff its logit exceeds
         predict.logit_threshold(probability) (predict.filtered_above_reference: the rule is on the logit, so a positive logit
@@ -234,15 +270,18 @@ class QueryPredictor(object):
         every entity above the threshold, entailed ones included -- not the reference's soft num_pred.  With filtered=True
         the entailed answers are left out of the lists exactly as in `answers`.  The batches are those of `answers`, through
         the same executor call; ultra_filtered_above selects on the device and the host reads one number per batch (the
-        batch's total) to slice the batch's lists."""
+        batch's total) to slice the batch's lists.  among: as in `answers` -- only the set's ids can be members, in the lists
+        and in size."""
         threshold = predict.logit_threshold(probability)
         dev = self.graph.edge_index.device
         plan = self._programs(queries)
         n = sum(len(index) for index, _ in plan)
+        if among is not None:
+            among = self._sets.assemble(among, n, dev)
         length = torch.zeros(n, dtype=torch.long, device=dev)
         size = torch.zeros(n, dtype=torch.long, device=dev)
         done = []
-        with self._batches(plan) as batches:
+        with self._batches(plan, among) as batches:
             for index, logits, ptr, known, live in batches:
                 if logits.is_cuda:
                     b_ptr, b_ids, b_scores, b_size = predict.filtered_above(logits, threshold, ptr, known, **live)

@@ -7,6 +7,8 @@ else: the wrappers in predict and query_exec, the captured steps and the eager l
 
 A GROWING graph: a predictor with entity_capacity=M serves rows of N + M slots; the selection then runs over
 the LIVE ids -- `num_live`.  The selections take a count in [1, n]; ultra_nonzero_lists, whose lists may be empty, one in [0, n].
+CANDIDATE lists: `among` -- per row an allow list, the dual of the known lists -- takes each selection to its
+`_among` entry, of which there is one: the live count and the retired pair are its nullable operands.
 RETIRED entities: their ids are taken out of the candidate set for good -- `retired`: for the kernels one
 device bitmap (live.retired_words: id v is bit v & 31 of word v >> 5) and one device int64, both read at replay; for the
 restatements the sorted id vector.  Neither operand is looked at on the host once it is a device tensor: the kernels clamp.
@@ -64,12 +66,46 @@ def retired_operand(retired, n, dev, bare=False):
                      "and one int64 (the sorted id vector is the _reference functions' form)" % words)
 
 
-def launch(entry, args, n_live, dev, retired=None):
+def among_operand(among, batch, n, dev, capacity=None):
+    """`among` of the kernels' wrappers -- the pair (span (batch, 2) int64, index int64), contiguous, on `dev`: row b's candidates
+    are index[span[b, 0] : span[b, 1]], ids ascending and distinct within a span -- checked once, as the triple
+    (span, index, capacity) that `launch` takes.  capacity (a host int, at least the longest span the call may meet; a captured
+    caller passes it): None reads the longest span from the device, one host read.  None stays None: no candidate lists.  n: the
+    slots of a row (the ids' range; they are not looked at on the host -- the kernels skip an id that is not eligible)."""
+    if among is None:
+        return None
+    try:
+        span, index = among
+        ok = (torch.is_tensor(span) and torch.is_tensor(index) and span.shape == (batch, 2) and index.dim() == 1
+              and span.dtype == torch.long and index.dtype == torch.long and span.device == dev and index.device == dev
+              and span.is_contiguous() and index.is_contiguous())
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("`among` is the pair (span, index) on the scores' device: contiguous int64 tensors, span of shape "
+                         "(batch, 2) = (%d, 2) and index 1-D (a list of per-row id vectors is the _reference functions' form)" % batch)
+    if capacity is None:
+        capacity = int((span[:, 1] - span[:, 0]).max()) if batch else 1
+    elif isinstance(capacity, bool) or not isinstance(capacity, int):
+        raise ValueError("among_capacity is an int, got %r" % (capacity,))
+    return span, index, max(1, min(int(capacity), (1 << 31) - 1))
+
+
+def launch(entry, args, n_live, dev, retired=None, among=None, among_at=3):
     """One launch of a selection entry on `dev`'s stream: `entry` without operands; its `_live` twin with the device scalar
     `n_live` appended to the same arguments; with `retired` = (bits, count) its `_alive` twin with the live count (or NULL: every
     slot), the bitmap and -- where the caller gives one: ultra_nonzero_lists_alive takes none -- the count appended.  The entry
-    is looked up when it is called (the call-count tests wrap the attributes of _lib.lib)."""
+    is looked up when it is called (the call-count tests wrap the attributes of _lib.lib).
+    among (among_operand's triple, or None: everything above, unchanged): the `_among` entry -- ONE entry per selection, the
+    live count, the bitmap and the retired count its nullable operands.  `args` are the parent's; among_at: the position of
+    `batch` in them, where the known lists end -- (span, index) go in front of it and the capacity behind n, which follows it."""
     stream = _lib.stream_of(dev)
+    if among is not None:
+        span, index, capacity = among
+        bits, count = (None, None) if retired is None else retired
+        args = args[:among_at] + (span.data_ptr(), index.data_ptr()) + args[among_at:among_at + 2] + (capacity,) + args[among_at + 2:]
+        _lib.check(getattr(_lib.lib, entry + "_among")(*args, _lib.ptr(n_live), _lib.ptr(bits), _lib.ptr(count), stream))
+        return
     if retired is not None:
         bits, count = retired
         operands = (bits.data_ptr(),) if count is None else (bits.data_ptr(), count.data_ptr())
