@@ -323,6 +323,29 @@ int32_t ultra_rspmm_edit_rows_samples(ultra_plan *plan, int32_t sum, int32_t mul
                                       const ultra_sample_keys *keys, void *stream);
 
 /*
+ * The three entries above with HUB ROWS handed to a workgroup each (csrc/delta_kernels.hip).  The same operands,
+ * the same checks, the same served cases and error codes, the same rows written with the same bits; removed == NULL: no
+ * tombstones (ultra_rspmm_delta_rows), keys == NULL: no per-slice keys (ultra_rspmm_edit_rows), keys with per_sample outside
+ * 1 .. 8: ULTRA_ERR_INVALID before any pointer is read.
+ *   hub_len   a touched row whose BASE length row_ptr[row + 1] - row_ptr[row] (read on the device) exceeds hub_len is a hub.
+ *             hub_len < 0 selects the plan's seg_len; 0 makes every touched row with a base edge a hub; a value above every
+ *             row's length reproduces the entries above.
+ * A touched row that is no hub is walked by one 16-lane group as above.  A hub is walked by one WORKGROUP per outer slice: three
+ * wavefronts produce the messages of its base edges in tiles of 96 consecutive base slots (deadness decided per slot, many
+ * gathers in flight) and one wavefront adds them in the stream's order into the one chain per element, merging the row's delta
+ * edges in by col (base first at equal col) and skipping dead edges -- the same sequence of roundings.  ONE launch of
+ * ceil(capacity_rows * n_outer / 16) + capacity_rows * n_outer workgroups: which rows are hubs is read at run time, a workgroup
+ * whose row is no live hub ends at once, so a recorded launch serves every later content of the same arrays, another row
+ * becoming the hub included.  Workgroup barriers only; no atomics, no allocation, no memset, no host synchronisation.
+ */
+int32_t ultra_rspmm_edit_rows_split(ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const ultra_mat *relation,
+                                    const ultra_mat *input, const ultra_mat *boundary, const int64_t *point_rows_dev,
+                                    const ultra_mat *output, const ultra_delta *delta, const ultra_tombstones *removed,
+                                    const ultra_sample_keys *keys, int64_t hub_len, void *stream);
+/* the number of consecutive base slots of a hub row that one tile of the hub walker holds (tests place edges at its edges) */
+int32_t ultra_rspmm_hub_tile(void);
+
+/*
  * The edits of a graph delta keyed by DESTINATION, for path explanations on (base graph, delta) (csrc/explain_live_kernels.hip,
  * csrc/beam_search.hip).  The explanation direction sends messages from edge_index[0] (src) into edge_index[1]
  * (dst); j is an added edge's position among the 2 m appended edges in materialised order.

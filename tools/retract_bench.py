@@ -1,6 +1,7 @@
 """Timing of RETRACTING facts from a served graph (ultra_amd.predict.Predictor.remove_facts) on one GPU:
 
     python tools/retract_bench.py [--reps 30] [--warmup 5] [--shapes fb15k237,yago310] [--out profiles/retract_bench.jsonl]
+                                  [--routes split,old] [--parts abcd]
 
 Synthetic graphs of FB15k237's and YAGO3-10's node, edge and relation counts, ultra_3g weights, batch 8, tail queries.  The
 retracted facts are triples the graph states, drawn at random.
@@ -23,6 +24,12 @@ retracted facts are triples the graph states, drawn at random.
   (c) edit_rows             ultra_rspmm_edit_rows alone (a captured call) with those deltas: touched rows, base edges walked,
                             longest row, bytes (per edge a source row, a relation row and 8 bytes of indices, per row one output
                             row, times the batch), their share of 8 TB/s
+  (d) length_sweep          one retracted fact whose row has about 32 .. 8,192 base edges, and the graph's longest row: the
+                            16-lane walk (ultra_rspmm_edit_rows) against the hub walker (ultra_rspmm_edit_rows_split with
+                            hub_len = 0: every touched row by a workgroup), captured calls run alternately
+--routes: (b) and (c) once per route -- `split`: rspmm.EDIT_ROWS_HUB_SPLIT on, a touched row longer than seg_len by a workgroup
+(the kernels' names end in _split_kernel); `old`: the switch off, the kernels of DESIGN.md 17 / 18, whose names the
+assertions of (b) check.  The keys of the `old` route carry no suffix, those of `split` end in `_split`.
 One JSON line per shape, appended to --out."""
 import argparse
 import json
@@ -73,7 +80,7 @@ def masked_forward(model, data, batch, keep):
     return dense.readout_batch(ent, hiddens[-1], query, pro[0], pro[3]).view(batch.shape[:2])
 
 
-def edit_rows_case(data, delta, bs, reps, warmup, dev):
+def edit_rows_case(data, delta, bs, reps, warmup, dev, routes=("old",), hub_len=None):
     plan = rspmm.get_plan(data.edge_index, data.edge_type, data.num_nodes, data.num_relations)
     g = torch.Generator().manual_seed(1)
     x = torch.randn(bs, data.num_nodes, 64, generator=g).to(dev)
@@ -81,18 +88,43 @@ def edit_rows_case(data, delta, bs, reps, warmup, dev):
     rows = torch.zeros(bs, dtype=torch.long, device=dev)
     vals = torch.randn(bs, 64, generator=g).to(dev)
     out = plan.forward(rel, x, point=(rows, vals))
-    call = graphed(lambda: plan.edit_rows(rel, x, out, delta, point=(rows, vals)))
-    (ms,), (ms_min,) = timed([call], reps, warmup)
+    entries = {"old": lambda: plan.edit_rows(rel, x, out, delta, point=(rows, vals)),
+               "split": lambda: plan.edit_rows_split(rel, x, out, delta, point=(rows, vals), hub_len=hub_len)}
+    med, low = timed([graphed(entries[route]) for route in routes], reps, warmup)
+    ms, ms_min = med[0], low[0]
     touched = delta.rows[:int(delta.count)].long()
     base_degree = torch.bincount(data.edge_index[0], minlength=data.num_nodes)[touched]
     edges = int(base_degree.sum()) + 2 * len(delta)        # (dead edges are walked too: their indices are read, their rows are not)
     nbytes = bs * (edges * (256 + 256) + len(touched) * 256) + edges * 8
-    return dict(retractions=delta.num_removed // 2, keys=delta.num_removed, touched_rows=len(touched), edges_walked=edges,
-                longest_row=int(base_degree.max()), ms=round(ms, 4), ms_min=round(ms_min, 4), bytes=nbytes,
+    line = dict(retractions=delta.num_removed // 2, keys=delta.num_removed, touched_rows=len(touched), edges_walked=edges,
+                longest_row=int(base_degree.max()), route=routes[0], ms=round(ms, 4), ms_min=round(ms_min, 4), bytes=nbytes,
                 gbps=round(nbytes / (ms * 1e-3) / 1e9, 1), roof=round(nbytes / (ms * 1e-3) / HBM_BPS, 4))
+    for route, m, lo in list(zip(routes, med, low))[1:]:
+        line.update({route + "_ms": round(m, 4), route + "_ms_min": round(lo, 4), route + "_roof": round(nbytes / (m * 1e-3) / HBM_BPS, 4)})
+    return line
 
 
-def shape_case(name, k, bs, reps, warmup, fact_reps, dev):
+def length_sweep(data, bs, reps, warmup, dev):
+    """(d): per target length the row of the nearest base degree loses one stated fact -- the one whose other end is the
+    shortest row, which is touched too."""
+    degree = torch.bincount(data.edge_index[0], minlength=data.num_nodes)
+    half = int(data.num_relations) // 2
+    lines = []
+    for target in [32, 64, 128, 256, 512, 1024, 2048, 4096, 8192, int(degree.max())]:
+        row = int((degree - target).abs().argmin())
+        at = (data.edge_index[0] == row).nonzero().flatten()
+        e = int(at[degree[data.edge_index[1, at]].argmin()])
+        col, kind = int(data.edge_index[1, e]), int(data.edge_type[e])
+        fact = (row, kind, col) if kind < half else (col, kind - half, row)
+        delta = rspmm.GraphDelta(data, 1024)
+        delta.remove(*fact)
+        line = edit_rows_case(data, delta, bs, reps, warmup, dev, routes=("old", "split"), hub_len=0)
+        line.update(target=target, row_len=int(degree[row]), other_row_len=int(degree[col]))
+        lines.append(line)
+    return lines
+
+
+def shape_case(name, k, bs, reps, warmup, fact_reps, dev, routes=("split", "old"), parts="abcd"):
     kg = synthetic.make_kg(**synthetic.SHAPES[name], seed=1234)
     data = synthetic.to_device(kg, dev)
     tasks.build_relation_graph(data)
@@ -107,7 +139,7 @@ def shape_case(name, k, bs, reps, warmup, fact_reps, dev):
 
     # (a) from retractions to the first answers without them: the three routes, in turn, in every repetition
     live_first, live_next, rebuild, masked = [], [], [], []
-    for rep in range(fact_reps):
+    for rep in range(fact_reps if "a" in parts else 0):
         facts = stated_facts(data, 32, 100 + rep, dev)
         fh, fr, ft = (f[:16] for f in facts)
         live = predict.Predictor(model, data, k=k, batch_size=bs)
@@ -138,47 +170,70 @@ def shape_case(name, k, bs, reps, warmup, fact_reps, dev):
             out["masked_route_error"] = repr(exc)
         rspmm.clear_plan_cache()
     med = statistics.median
-    out["retraction_to_answer"] = dict(retractions=16, reps=fact_reps, live_first_ms=round(med(live_first), 3),
-                                       live_next_ms=round(med(live_next), 3), rebuild_ms=round(med(rebuild), 3),
-                                       masked_ms=round(med(masked), 3) if masked else None,
-                                       rebuild_over_live_next=round(med(rebuild) / med(live_next), 1),
-                                       masked_over_live_next=round(med(masked) / med(live_next), 2) if masked else None)
+    if "a" in parts:
+        out["retraction_to_answer"] = dict(retractions=16, reps=fact_reps, live_first_ms=round(med(live_first), 3),
+                                           live_next_ms=round(med(live_next), 3), rebuild_ms=round(med(rebuild), 3),
+                                           masked_ms=round(med(masked), 3) if masked else None,
+                                           rebuild_over_live_next=round(med(rebuild) / med(live_next), 1),
+                                           masked_over_live_next=round(med(masked) / med(live_next), 2) if masked else None)
 
-    # (b) the steady-state step
+    # (b) the steady-state step, per route
     deltas = {}
     for count in (16, 1024):
         deltas[count] = rspmm.GraphDelta(data, 1024)
         deltas[count].remove(*stated_facts(data, count, 7, dev))
     added = rspmm.GraphDelta(data, 1024)
     added.add(*random_facts(data, 16, 7, dev))
-    steps = {"static": predict._GraphedPredictStep(model, data, bs, k, "tail", 1 << 16),
-             "added16": predict._GraphedPredictStep(model, data, bs, k, "tail", 1 << 16, delta=added)}
-    for count, delta in deltas.items():
-        steps[count] = predict._GraphedPredictStep(model, data, bs, k, "tail", 1 << 16, delta=delta)
-    for step in steps.values():
-        step.load_index(index)
-    order = ["static", "added16", 16, 1024]
-    med_ms, low = timed([lambda s=steps[key]: s(h, r, ptr) for key in order], reps, warmup)
-    out["step_ms"] = {str(key): round(m, 4) for key, m in zip(order, med_ms)}
-    out["step_ms_min"] = {str(key): round(m, 4) for key, m in zip(order, low)}
-    out["step_over_static"] = {str(key): round(m / med_ms[0], 4) for key, m in zip(order, med_ms)}
-    out["relation_graph_kept"] = {str(c): bool(d.relation_graph is data.relation_graph) for c, d in deltas.items()}
-    try:
-        kernels = {str(key): replay_kernels(steps[key], (h, r, ptr)) for key in order}
-    except Exception as exc:      # (no profiler on this build: the count is not taken, and the line says so)
-        kernels = {str(key): None for key in order}
-        out["kernel_count_error"] = repr(exc)
-    if kernels["added16"] is not None and kernels["16"] is not None:
-        # an add-only delta keeps its kernels: ultra_rspmm_delta_rows' launches and none of the retraction kernel's; the step with
-        # tombstones runs the same NUMBER of kernels, the retraction kernel in the other's place
-        assert not any("edit_rows" in name for name in kernels["added16"]), "an add-only delta launches the retraction kernel"
-        assert any("delta_rows" in name for name in kernels["added16"])
-        assert len(kernels["16"]) == len(kernels["added16"]), (len(kernels["16"]), len(kernels["added16"]))
-        assert any("edit_rows" in name for name in kernels["16"]) and not any("delta_rows" in name for name in kernels["16"])
-    out["kernels"] = {key: None if names is None else len(names) for key, names in kernels.items()}
+    quiet = rspmm.GraphDelta(data, 1024)                # 16 added facts between the rows of the fewest edges: no hub touched
+    degree = torch.bincount(data.edge_index[0], minlength=data.num_nodes)
+    short = degree.argsort()[:32]
+    quiet.add(short[:16].contiguous(), torch.zeros(16, dtype=torch.long, device=dev), short[16:].contiguous())
+    plan = rspmm.get_plan(data.edge_index, data.edge_type, data.num_nodes, data.num_relations)
+    out["seg_len"], out["has_hub_rows"] = plan.info()["seg_len"], bool(plan.has_hub_rows)
+    steps = {"static": predict._GraphedPredictStep(model, data, bs, k, "tail", 1 << 16)}
+    order = ["static"]
+    for route in (routes if "b" in parts else ()):
+        rspmm.EDIT_ROWS_HUB_SPLIT = route == "split"
+        suffix = "_split" if route == "split" else ""
+        for key, delta in (("added16_no_hub", quiet), ("added16", added), ("16", deltas[16]), ("1024", deltas[1024])):
+            steps[key + suffix] = predict._GraphedPredictStep(model, data, bs, k, "tail", 1 << 16, delta=delta)
+            steps[key + suffix].load_index(index)
+            steps[key + suffix](h, r, ptr)              # (captured under its route's switch)
+            order.append(key + suffix)
+    rspmm.EDIT_ROWS_HUB_SPLIT = True
+    steps["static"].load_index(index)
+    if "b" in parts:
+        med_ms, low = timed([lambda s=steps[key]: s(h, r, ptr) for key in order], reps, warmup)
+        out["step_ms"] = {key: round(m, 4) for key, m in zip(order, med_ms)}
+        out["step_ms_min"] = {key: round(m, 4) for key, m in zip(order, low)}
+        out["step_over_static"] = {key: round(m / med_ms[0], 4) for key, m in zip(order, med_ms)}
+        out["relation_graph_kept"] = {str(c): bool(d.relation_graph is data.relation_graph) for c, d in deltas.items()}
+        try:
+            kernels = {key: replay_kernels(steps[key], (h, r, ptr)) for key in order}
+        except Exception as exc:      # (no profiler on this build: the count is not taken, and the line says so)
+            kernels = {key: None for key in order}
+            out["kernel_count_error"] = repr(exc)
+        if kernels.get("added16") is not None and kernels.get("16") is not None:
+            # an add-only delta keeps its kernels: ultra_rspmm_delta_rows' launches and none of the retraction kernel's; the step
+            # with tombstones runs the same NUMBER of kernels, the retraction kernel in the other's place
+            assert not any("edit_rows" in name for name in kernels["added16"]), "an add-only delta launches the retraction kernel"
+            assert any("delta_rows" in name for name in kernels["added16"])
+            assert not any("split" in name for name in kernels["added16"] + kernels["16"]), "the switch is off: the old kernels"
+            assert len(kernels["16"]) == len(kernels["added16"]), (len(kernels["16"]), len(kernels["added16"]))
+            assert any("edit_rows" in name for name in kernels["16"]) and not any("delta_rows" in name for name in kernels["16"])
+        if kernels.get("added16_split") is not None and kernels.get("16_split") is not None and plan.has_hub_rows:
+            # the split route: one launch in the other's place, the roles inside it
+            assert any("delta_rows_split" in name for name in kernels["added16_split"])
+            assert any("edit_rows_split" in name for name in kernels["16_split"])
+            assert len(kernels["16_split"]) == len(kernels["added16_split"])
+        out["kernels"] = {key: None if names is None else len(names) for key, names in kernels.items()}
 
     # (c) the retraction kernel alone
-    out["edit_rows"] = [edit_rows_case(data, deltas[count], bs, reps, warmup, dev) for count in (16, 1024)]
+    if "c" in parts:
+        out["edit_rows"] = [edit_rows_case(data, deltas[count], bs, reps, warmup, dev, routes=tuple(reversed(routes)))
+                            for count in (16, 1024)]
+    if "d" in parts:
+        out["length_sweep"] = length_sweep(data, bs, reps, warmup, dev)
     for step in steps.values():
         step.release()
     return out
@@ -192,13 +247,16 @@ def main():
     ap.add_argument("-k", type=int, default=10)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--shapes", default="fb15k237,yago310")
+    ap.add_argument("--routes", default="split,old", help="comma list of split, old: the routes (b) and (c) measure")
+    ap.add_argument("--parts", default="abcd", help="the parts to run, letters of abcd")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "retract_bench.jsonl"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("tools/retract_bench.py needs a GPU")
     dev = torch.device("cuda:0")
     for name in args.shapes.split(","):
-        line = json.dumps(shape_case(name, args.k, args.batch, args.reps, args.warmup, args.fact_reps, dev))
+        line = json.dumps(shape_case(name, args.k, args.batch, args.reps, args.warmup, args.fact_reps, dev,
+                                     routes=tuple(args.routes.split(",")), parts=args.parts))
         print(line, flush=True)
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "a") as f:

@@ -141,6 +141,9 @@ def _load():
                                           ctypes.POINTER(UltraTombstones), vp]
     lib.ultra_rspmm_edit_rows_samples.argtypes = [vp, i32, i32, i32, matp, matp, matp, vp, matp, ctypes.POINTER(UltraDelta),
                                                   ctypes.POINTER(UltraTombstones), ctypes.POINTER(UltraSampleKeys), vp]
+    lib.ultra_rspmm_edit_rows_split.argtypes = [vp, i32, i32, i32, matp, matp, matp, vp, matp, ctypes.POINTER(UltraDelta),
+                                                ctypes.POINTER(UltraTombstones), ctypes.POINTER(UltraSampleKeys), i64, vp]
+    lib.ultra_rspmm_hub_tile.restype = i32
     lib.ultra_rspmm_forward_onehot.argtypes = [vp, i32, vp, matp, matp, vp, matp, matp, vp]
     lib.ultra_rspmm_forward_point.argtypes = [vp, i32, i32, i32, vp, matp, matp, vp, matp, matp, vp]
     lib.ultra_rspmm_forward_update.argtypes = [vp, i32, i32, matp, matp, vp, matp, matp, vp, vp, vp, vp, ctypes.c_float, i32, matp, vp]
@@ -264,6 +267,8 @@ def _load():
 lib = _load()
 if lib.ultra_abi_version() != 7:
     raise ImportError("ultra_amd: libultra_amd.so ABI version mismatch")
+# base slots per tile of the hub-row walker (ultra_rspmm_edit_rows_split; csrc/delta_kernels.hip HUB_TILE)
+HUB_TILE = int(lib.ultra_rspmm_hub_tile())
 
 
 class UltraError(RuntimeError):

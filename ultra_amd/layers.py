@@ -367,7 +367,10 @@ class GeneralizedRelationalConv(nn.Module):
         plan = rspmm.get_plan(edge_index, edge_type, num_node, relation.shape[1])
         sum = {"sum": "add", "mean": "add"}.get(self.aggregate_func, self.aggregate_func)
         mul = self.message2mul[self.message_func]
-        fix_rows = plan.edit_rows if delta.num_removed else plan.delta_rows
+        if rspmm.EDIT_ROWS_HUB_SPLIT and plan.has_hub_rows:      # (the same rows, the same bits: hub rows by a workgroup each)
+            fix_rows = plan.edit_rows_split
+        else:
+            fix_rows = plan.edit_rows if delta.num_removed else plan.delta_rows
         update = None
         if isinstance(boundary, PointBoundary):
             point = (boundary.rows, boundary.values)
@@ -425,7 +428,10 @@ class GeneralizedRelationalConv(nn.Module):
         sum = {"sum": "add"}.get(self.aggregate_func, self.aggregate_func)
         mul = self.message2mul[self.message_func]
         update = plan.forward(relation, input, edge_weight=edge_weight, boundary=boundary, sum=sum, mul=mul, keep=True)
-        update = plan.edit_rows_samples(relation, input, update, delta, sample_keys, boundary=boundary, sum=sum, mul=mul)
+        if rspmm.EDIT_ROWS_HUB_SPLIT and plan.has_hub_rows:
+            update = plan.edit_rows_split(relation, input, update, delta, keys=sample_keys, boundary=boundary, sum=sum, mul=mul)
+        else:
+            update = plan.edit_rows_samples(relation, input, update, delta, sample_keys, boundary=boundary, sum=sum, mul=mul)
         if update is None:
             return None
         return self.update(update, input, residual=residual)

@@ -38,6 +38,9 @@ _DTYPES = {torch.float32: _lib.F32, torch.float64: _lib.F64}
 _WEIGHT_EPOCH = [0]
 # the relation gradient of dense-twin graphs on the matrix cores (A/B switch for tests: the relation-major edge walk is the other side)
 DENSE_RELATION_GRAD = True
+# the touched rows of a graph delta through ultra_rspmm_edit_rows_split: a row longer than the plan's seg_len is recomputed by a
+# workgroup, not by one 16-lane chain (A/B switch for tests: delta_rows / edit_rows / edit_rows_samples are the other side)
+EDIT_ROWS_HUB_SPLIT = True
 
 
 def tag_edge_weight(edge_weight):
@@ -168,6 +171,7 @@ class Plan(object):
                                     self.num_in, self.num_relation, ctypes.byref(opts)))
         self._h = handle
         self.exact = bool(exact_order)
+        self._has_hub_rows = None
         # Dense graphs with few relation types (ULTRA's relation graph: 474 nodes, 4 types, ~470 edges per
         # (row, type) run) get a twin plan whose items hold one relation each; add_mul forwards use it.
         self.typed = None
@@ -238,6 +242,14 @@ class Plan(object):
         info = _lib.PlanInfo()
         check(lib.ultra_plan_get_info(self._h, ctypes.byref(info)))
         return {name: getattr(info, name) for name, _ in _lib.PlanInfo._fields_}
+
+    @property
+    def has_hub_rows(self):
+        """Does a row of this reference-order plan hold more than seg_len edges (a chain row of the base walk: n_chain_row)?
+        Only such a row is a hub to edit_rows_split at its default hub_len; a plan without one gains nothing from it."""
+        if self._has_hub_rows is None:
+            self._has_hub_rows = self.exact and self.info()["n_chain_row"] > 0
+        return self._has_hub_rows
 
     def schedule_info(self, nparts):
         info = _lib.ScheduleInfo()
@@ -385,10 +397,10 @@ class Plan(object):
         return self._recompute_rows(lib.ultra_rspmm_delta_rows, relation, input, out, delta, boundary, sum, mul, point,
                                     lambda: (delta.operand(),))
 
-    def _recompute_rows(self, entry, relation, input, out, delta, boundary, sum, mul, point, edits, on_gpu=()):
-        """The body of delta_rows, edit_rows and edit_rows_samples: the checks, the operands, one call of `entry`.  `edits()` --
-        called once the checks have passed -- returns the entry's operands between `output` and `stream`, the delta's first;
-        `on_gpu`: further tensors the entry reads."""
+    def _recompute_rows(self, entry, relation, input, out, delta, boundary, sum, mul, point, edits, on_gpu=(), tail=()):
+        """The body of delta_rows, edit_rows, edit_rows_samples and edit_rows_split: the checks, the operands, one call of `entry`.
+        `edits()` -- called once the checks have passed -- returns the entry's struct operands between `output` and `stream`, the
+        delta's first (None: a NULL pointer); `tail`: plain arguments that follow them; `on_gpu`: further tensors the entry reads."""
         if not self.exact:
             return None
         if (delta.num_nodes, delta.num_relations) != (self.num_node, self.num_relation) or self.num_in != self.num_node:
@@ -402,7 +414,8 @@ class Plan(object):
             raise RuntimeError("`out` must have unit stride along its last dimension")
         operands = edits()
         rc = entry(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], op.dtype, op.relation, op.input, op.boundary, op.rows,
-                   op.out_ref, *[ctypes.byref(operand) for operand in operands], stream_of(input))
+                   op.out_ref, *[None if operand is None else ctypes.byref(operand) for operand in operands], *tail,
+                   stream_of(input))
         if rc == _lib.ULTRA_ERR_UNSUPPORTED:
             return None
         check(rc)
@@ -426,18 +439,39 @@ class Plan(object):
         where `out` came from forward(edge_weight=keep (n_outer, num_edge), keep=True) with keep rows that leave the same base
         edges out.  Returns `out`, or None exactly where edit_rows does."""
         def edits():
-            key_row, key_col, key_type = keys
-            n_outer = out.shape[0] if out.dim() == 3 else 1
-            for t in keys:
-                if t.dtype != torch.int32 or t.dim() != 2 or t.shape != key_row.shape or not t.is_contiguous():
-                    raise RuntimeError("`keys` are three contiguous int32 tensors of one shape (n_outer, per_sample)")
-            if key_row.shape[0] != n_outer or not 1 <= key_row.shape[1] <= 8:
-                raise RuntimeError("Expected keys of shape (n_outer = %d, 1 .. 8), got %s" % (n_outer, tuple(key_row.shape)))
-            sample_keys = _lib.UltraSampleKeys(key_row.data_ptr(), key_col.data_ptr(), key_type.data_ptr(), key_row.shape[1])
-            return delta.operand(), delta.removed_operand(), sample_keys
+            return delta.operand(), delta.removed_operand(), self._sample_keys_operand(keys, out)
 
         return self._recompute_rows(lib.ultra_rspmm_edit_rows_samples, relation, input, out, delta, boundary, sum, mul, point,
                                     edits, on_gpu=keys)
+
+    def edit_rows_split(self, relation, input, out, delta, keys=None, boundary=None, sum="add", mul="mul", point=None,
+                        hub_len=None):
+        """edit_rows -- with `keys` edit_rows_samples -- where a touched row of more than `hub_len` BASE edges is recomputed by a
+        whole workgroup per outer slice, not by one 16-lane group (ultra_rspmm_edit_rows_split): the same rows
+        written with the same bits, in one launch sized by the delta's capacity; which rows are hubs is read on the device, so a
+        captured launch follows the delta's buffers.  hub_len None: the plan's seg_len; 0: every touched row with a base edge.
+        A delta without tombstones passes none (delta_rows).  Returns `out`, or None exactly where edit_rows does."""
+        def edits():
+            sample_keys = None
+            if keys is not None:
+                sample_keys = self._sample_keys_operand(keys, out)
+            removed = delta.removed_operand() if delta.num_removed or keys is not None else None
+            return delta.operand(), removed, sample_keys
+
+        return self._recompute_rows(lib.ultra_rspmm_edit_rows_split, relation, input, out, delta, boundary, sum, mul, point,
+                                    edits, on_gpu=keys or (), tail=(ctypes.c_int64(-1 if hub_len is None else int(hub_len)),))
+
+    @staticmethod
+    def _sample_keys_operand(keys, out):
+        """The per-slice keys of edit_rows_samples / edit_rows_split as the entries take them, checked against `out`."""
+        key_row, key_col, key_type = keys
+        n_outer = out.shape[0] if out.dim() == 3 else 1
+        for t in keys:
+            if t.dtype != torch.int32 or t.dim() != 2 or t.shape != key_row.shape or not t.is_contiguous():
+                raise RuntimeError("`keys` are three contiguous int32 tensors of one shape (n_outer, per_sample)")
+        if key_row.shape[0] != n_outer or not 1 <= key_row.shape[1] <= 8:
+            raise RuntimeError("Expected keys of shape (n_outer = %d, 1 .. 8), got %s" % (n_outer, tuple(key_row.shape)))
+        return _lib.UltraSampleKeys(key_row.data_ptr(), key_col.data_ptr(), key_type.data_ptr(), key_row.shape[1])
 
     def forward_update(self, relation, input, weight, bias, ln_weight, ln_bias, eps, flags, mul="mul", point=None, timed=None,
                        sum="add"):
