@@ -342,6 +342,25 @@ int32_t ultra_rspmm_edit_rows_split(ultra_plan *plan, int32_t sum, int32_t mul, 
                                     const ultra_mat *input, const ultra_mat *boundary, const int64_t *point_rows_dev,
                                     const ultra_mat *output, const ultra_delta *delta, const ultra_tombstones *removed,
                                     const ultra_sample_keys *keys, int64_t hub_len, void *stream);
+/*
+ * ultra_rspmm_edit_rows_split where every delta edge has an OWNER (csrc/delta_kernels.hip): facts assumed per
+ * query -- "what if (a, r, b) were true?" -- beside the facts every query sees, without stating anything.
+ *   owner_dev   int32 [delta->capacity_edges], parallel to delta->col_dev: -1 -- the edge is live in every outer slice; s in
+ *               [0, n_outer) -- live in slice s only; any other value -- live nowhere.  Only compared, never used as an index.
+ * The caller sorts the delta's edges by (row, col, insertion id), the shared edges carrying the lower ids: the live subsequence
+ * of slice s is then the sorted row of slice s's own graph [base edges without the dead ones ; shared edges ; slice s's edges],
+ * and on ULTRA_PLAN_EXACT_ORDER plans slice s of a recomputed row equals ultra_rspmm_forward on a fresh reference-order plan of
+ * that list bit for bit.  Tombstones keep their meaning (base edges only); removed == NULL: none.
+ * NOT WRITTEN (a contract): a (touched row, slice) with no tombstone key in the row and no delta edge live in that slice -- the
+ * base walk already wrote its bits.  A hub touched by one slice's edges is then walked by one workgroup, not n_outer; the hub role
+ * decides ahead of its first barrier, uniformly across the workgroup, from a scan of the row's delta range.
+ * Launch shape (one launch, both roles), hub_len, checks, served cases and error codes: ultra_rspmm_edit_rows_split's;
+ * owner_dev == NULL: ULTRA_ERR_INVALID.  No atomics, no allocation, no memset, no host synchronisation.
+ */
+int32_t ultra_rspmm_edit_rows_owned(ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const ultra_mat *relation,
+                                    const ultra_mat *input, const ultra_mat *boundary, const int64_t *point_rows_dev,
+                                    const ultra_mat *output, const ultra_delta *delta, const int32_t *owner_dev,
+                                    const ultra_tombstones *removed, int64_t hub_len, void *stream);
 /* the number of consecutive base slots of a hub row that one tile of the hub walker holds (tests place edges at its edges) */
 int32_t ultra_rspmm_hub_tile(void);
 

@@ -3,7 +3,7 @@
     python tools/predict.py --data-root DIR [--ckpt FILE] --head NAME --relation NAME [--inverse] [-k 10] [--unfiltered] [--explain [--no-compact]]
                             [--add-fact H R T]... [--remove-fact H R T]... [--entity-capacity M] [--add-entity NAME]...
                             [--relation-capacity K] [--add-relation NAME]... [--live-relation-graph] [--remove-entity NAME]...
-                            [--among NAME [NAME ...]] [--among-file FILE]
+                            [--among NAME [NAME ...]] [--among-file FILE] [--assume H R T]...
     python tools/predict.py --data-root DIR [--ckpt FILE] --verify (--head NAME --relation NAME --tail NAME | --triples FILE) [--inverse]
 
 DIR holds train.txt / valid.txt / test.txt (`head relation tail` per line) and optionally entities.dict / relations.dict
@@ -41,6 +41,10 @@ capture.  The answers are the same.  Needs a relation model of sum / DistMult la
 the candidates to a set (Predictor.tails(among=)): only these entities are ranked -- a shortlist, or the entities
 of a type -- and with --verify the fact is ranked among them.  An unknown name is an error that names it; a name introduced by
 --add-entity may be listed, and an entity retired by --remove-entity is simply absent.
+
+--assume H R T (repeatable) answers the query as if the fact were true WITHOUT stating it (Predictor.tails(assuming=), DESIGN.md
+32): the graph served, the delta and the known answers of later queries stay what they were; an assumed tail of the query's own
+(head, relation) is left out of its answers.  The names are those known after every edit option.  Not with --verify / --explain.
 
 --verify judges facts the dataset may already state: every (head, relation, tail) -- one from the command line, or the
 `head relation tail` lines of FILE -- is scored on the graph WITHOUT itself and its inverse edge (Predictor.verify_tails; with
@@ -108,6 +112,8 @@ def main(argv=None):
                     help="slots reserved for new relation types (default: the number of --add-relation options)")
     ap.add_argument("--live-relation-graph", action="store_true",
                     help="keep the relation graph current in place: no relation-graph plan, no new capture for an edit")
+    ap.add_argument("--assume", nargs=3, action="append", default=[], metavar=("H", "R", "T"),
+                    help="answer as if the fact (H, R, T) were true, without stating it; repeatable")
     ap.add_argument("--among", nargs="+", metavar="NAME", help="rank only these entities (a shortlist, a type)")
     ap.add_argument("--among-file", metavar="FILE", help="... the entity names of FILE, one per line")
     ap.set_defaults(edits=[])
@@ -154,6 +160,10 @@ def main(argv=None):
             checks.append((value, set(known)))
     for triple in (facts if facts is not None else [(args.head, args.relation, args.head)]):
         checks.append((triple, known))
+    if args.assume and (args.verify or args.explain):
+        sys.exit("--assume goes with the plain query: not with --verify or --explain")
+    for triple in args.assume:          # (judged against the names known after every edit)
+        checks.append((tuple(triple), known))
     for (h_name, r_name, t_name), names in checks:
         for name, vocab, what in ((h_name, names, "entity"), (r_name, rel, "relation"), (t_name, names, "entity")):
             if name not in vocab:
@@ -174,7 +184,8 @@ def main(argv=None):
                                       relation_capacity=rel_reserve, live_relation_graph=args.live_relation_graph)
     else:
         predictor = predict.Predictor(model, data, k=args.k, batch_size=1, filtered=not args.unfiltered, entity_capacity=reserve,
-                                      relation_capacity=rel_reserve, live_relation_graph=args.live_relation_graph)
+                                      relation_capacity=rel_reserve, live_relation_graph=args.live_relation_graph,
+                                      assume_capacity=max(8, len(args.assume)))
     for name in args.add_relation:
         if not rel_reserve:
             sys.exit("--add-relation needs --relation-capacity above 0")
@@ -237,6 +248,10 @@ def main(argv=None):
         ids, scores, count, why = (predictor.explain_heads if args.inverse else predictor.explain_tails)(
             anchor, relation, compact=not args.no_compact, **among)
     else:
+        if args.assume:
+            among["assuming"] = torch.tensor([[vocab.index(f[i]) for i, vocab in ((0, ent), (1, rel), (2, ent))]
+                                              for f in args.assume], device=dev)
+            print("assuming %d fact(s) for this query only: nothing is stated" % len(args.assume))
         ids, scores, count = (predictor.heads if args.inverse else predictor.tails)(anchor, relation, **among)
     query = "(?, %s, %s)" % (args.relation, args.head) if args.inverse else "(%s, %s, ?)" % (args.head, args.relation)
     print("%s: top %d%s" % (query, int(count[0]), "" if args.unfiltered else ", known answers left out"))

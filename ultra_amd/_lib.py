@@ -143,6 +143,8 @@ def _load():
                                                   ctypes.POINTER(UltraTombstones), ctypes.POINTER(UltraSampleKeys), vp]
     lib.ultra_rspmm_edit_rows_split.argtypes = [vp, i32, i32, i32, matp, matp, matp, vp, matp, ctypes.POINTER(UltraDelta),
                                                 ctypes.POINTER(UltraTombstones), ctypes.POINTER(UltraSampleKeys), i64, vp]
+    lib.ultra_rspmm_edit_rows_owned.argtypes = [vp, i32, i32, i32, matp, matp, matp, vp, matp, ctypes.POINTER(UltraDelta), vp,
+                                                ctypes.POINTER(UltraTombstones), i64, vp]
     lib.ultra_rspmm_hub_tile.restype = i32
     lib.ultra_rspmm_forward_onehot.argtypes = [vp, i32, vp, matp, matp, vp, matp, matp, vp]
     lib.ultra_rspmm_forward_point.argtypes = [vp, i32, i32, i32, vp, matp, matp, vp, matp, matp, vp]

@@ -25,6 +25,10 @@
 //   rspmm_edit_rows_kernel          <TOMBS = true,  KEYS = false>   plus RETRACTED facts, TOMBSTONES on the same plan.
 //   rspmm_edit_rows_samples_kernel  <TOMBS = true,  KEYS = true>    plus PER-SLICE dead keys.
 //
+// and the split launch has one more shell of its own:
+//   rspmm_edit_rows_owned_kernel    <TOMBS = true,  KEYS = false, OWNED = true>   delta edges that are live in ONE outer slice each
+//                                                                   (what-if facts assumed per query) beside those live in all.
+//
 // TOMBS: a removed edge changes the one row it points into, so the touched rows are the union of both kinds and the base cursor
 // gets one more cursor beside it: per touched row the distinct dead (col, type) keys, sorted; a base edge whose (col, type) is
 // among them takes no part (base edges of one col come in edge-id order, not type order: the keys of that col are scanned).  A
@@ -77,11 +81,21 @@ struct SampleParams : EditParams {
     int32_t per_sample;
 };
 
+struct OwnedParams : SampleParams {
+    const int32_t *d_owner;                              // per delta edge: -1 live in every outer slice, s in slice s alone
+};
+
+// OWNED: is the delta edge whose owner is `owner` live in outer slice `outer`?  (compared only, never used as an index: any
+// value but -1 and the slice's own number is live nowhere)
+__device__ __forceinline__ bool owner_live(int owner, int outer) { return owner == -1 || owner == outer; }
+
 // The walk of one (touched row, outer slice) by one 16-lane group.  (bi, bcol, btype) is always the next LIVE base edge of the
 // row, (dj, dcol, dtype) the next live delta edge.  TOMBS reads EditParams' tombstones, KEYS SampleParams' per-slice keys; with
 // KEYS a NULL t_ptr means "no tombstones".
 // SPLIT (rspmm_edit_rows_split_kernel): a row whose base length exceeds p.hub_len is left to hub_row_walk below.
-template <typename T, int SUM, int MUL, bool TOMBS, bool KEYS, bool SPLIT = false, typename Params>
+// OWNED (rspmm_edit_rows_owned_kernel; OwnedParams, a NULL t_ptr means "no tombstones"): a delta edge takes part in the slices
+// its owner names, and a (row, slice) with no tombstone key and no live delta edge is left as the base walk wrote it.
+template <typename T, int SUM, int MUL, bool TOMBS, bool KEYS, bool SPLIT = false, bool OWNED = false, typename Params>
 __device__ __forceinline__ void edit_rows_walk(const Params &p) {
     constexpr int VEC = 16 / (int)sizeof(T);      // elements per 16-byte chunk
     using P = Pack<T, VEC>;
@@ -98,12 +112,23 @@ __device__ __forceinline__ void edit_rows_walk(const Params &p) {
     const int je = min(max(p.d_ptr[k + 1], j), p.cap_edges);
     int q = 0, qe = 0;                            // (no tombstones: an empty key range)
     if constexpr (TOMBS) {                        // (two selects, not one branch: DESIGN.md 26 has the measurement)
-        q = (!KEYS || p.t_ptr) ? min(max(p.t_ptr[k], 0), p.cap_keys) : 0;
-        qe = (!KEYS || p.t_ptr) ? min(max(p.t_ptr[k + 1], q), p.cap_keys) : 0;
+        q = (!(KEYS || OWNED) || p.t_ptr) ? min(max(p.t_ptr[k], 0), p.cap_keys) : 0;
+        qe = (!(KEYS || OWNED) || p.t_ptr) ? min(max(p.t_ptr[k + 1], q), p.cap_keys) : 0;
     }
     if (i < 0 || ie < i || ie > p.num_edge) return;
     if constexpr (SPLIT)
         if (ie - i > p.hub_len) return;
+    if constexpr (OWNED) {
+        // the early-out (a contract: the row is NOT written): no tombstone key in the row and no delta edge live in this slice.
+        // The group's lanes share the row's delta range (bounded by the capacity) and OR their findings over the sixteen.
+        if (q == qe) {
+            int any = 0;
+            for (int dj = j + l16; dj < je; dj += 16) any |= owner_live(p.d_owner[dj], outer) ? 1 : 0;
+#pragma unroll
+            for (int m = 8; m >= 1; m >>= 1) any |= __shfl_xor(any, m, 16);
+            if (!any) return;
+        }
+    }
 
     // KEYS: this slice's keys that name this row (compared only, never used as an index), filtered into registers once per
     // group; a group with none takes one always-false branch per edge
@@ -172,6 +197,8 @@ __device__ __forceinline__ void edit_rows_walk(const Params &p) {
         // step to the next delta edge that carries none of the slice's keys (tombstones never apply to delta edges)
         const auto next_delta = [&]() {
             for (++dj; dj < je; ++dj) {
+                if constexpr (OWNED)
+                    if (!owner_live(p.d_owner[dj], outer)) continue;
                 dcol = p.d_col[dj], dtype = p.d_type[dj];
                 if constexpr (KEYS) {
                     if (!smask || !sample_dead(dcol, dtype)) return;
@@ -270,7 +297,7 @@ constexpr int HUB_DRAIN = 8;                                             // slot
 static_assert(HUB_TILE % HUB_DRAIN == 0, "the consumer's batches tile the tile");
 static_assert(HUB_SLOTS * HUB_GROUPS == HUB_TILE && HUB_TILE <= DELTA_THREADS - 64, "a producer thread per slot, whole rounds of groups");
 
-template <typename T, int SUM, int MUL, bool TOMBS, bool KEYS, typename Params>
+template <typename T, int SUM, int MUL, bool TOMBS, bool KEYS, bool OWNED = false, typename Params>
 __device__ __forceinline__ void hub_row_walk(const Params &p, const long long wg) {
     constexpr int VEC = 16 / (int)sizeof(T);
     using P = Pack<T, VEC>;
@@ -293,8 +320,17 @@ __device__ __forceinline__ void hub_row_walk(const Params &p, const long long wg
     const int je = min(max(p.d_ptr[k + 1], j), p.cap_edges);
     int q = 0, qe = 0;
     if constexpr (TOMBS) {
-        q = (!KEYS || p.t_ptr) ? min(max(p.t_ptr[k], 0), p.cap_keys) : 0;
-        qe = (!KEYS || p.t_ptr) ? min(max(p.t_ptr[k + 1], q), p.cap_keys) : 0;
+        q = (!(KEYS || OWNED) || p.t_ptr) ? min(max(p.t_ptr[k], 0), p.cap_keys) : 0;
+        qe = (!(KEYS || OWNED) || p.t_ptr) ? min(max(p.t_ptr[k + 1], q), p.cap_keys) : 0;
+    }
+    if constexpr (OWNED) {
+        // the early-out of edit_rows_walk, ahead of the first barrier: every thread scans the same range (bounded by the
+        // capacity) of the same workgroup-uniform addresses, so the whole workgroup returns or none of it does
+        if (q == qe) {
+            bool any = false;
+            for (int dj = j; dj < je; ++dj) any |= owner_live(p.d_owner[dj], outer);
+            if (!any) return;
+        }
     }
     const int ntiles = (n - 1) / HUB_TILE + 1;
 
@@ -335,6 +371,8 @@ __device__ __forceinline__ void hub_row_walk(const Params &p, const long long wg
         for (int e = 0; e < VEC; ++e) dmsg.v[e] = T(0), acc.v[e] = nary_zero<T, SUM>();
         const auto next_delta = [&]() {
             for (++dj; dj < je; ++dj) {
+                if constexpr (OWNED)
+                    if (!owner_live(p.d_owner[dj], outer)) continue;
                 dcol = p.d_col[dj];
                 int dtype = p.d_type[dj];
                 if constexpr (KEYS)
@@ -447,12 +485,12 @@ __device__ __forceinline__ void hub_row_walk(const Params &p, const long long wg
 
 // The split launch: blocks [0, small_blocks) walk the touched rows of at most hub_len base edges as the kernels above do,
 // block small_blocks + w is the workgroup of (touched row, outer slice) w and ends at once unless that row is a hub.
-template <typename T, int SUM, int MUL, bool TOMBS, bool KEYS, typename Params>
+template <typename T, int SUM, int MUL, bool TOMBS, bool KEYS, bool OWNED = false, typename Params>
 __device__ __forceinline__ void split_rows_roles(const Params &p, const unsigned small_blocks) {
     if (blockIdx.x < small_blocks)
-        edit_rows_walk<T, SUM, MUL, TOMBS, KEYS, true>(p);
+        edit_rows_walk<T, SUM, MUL, TOMBS, KEYS, true, OWNED>(p);
     else
-        hub_row_walk<T, SUM, MUL, TOMBS, KEYS>(p, (long long)(blockIdx.x - small_blocks));
+        hub_row_walk<T, SUM, MUL, TOMBS, KEYS, OWNED>(p, (long long)(blockIdx.x - small_blocks));
 }
 template <typename T, int SUM, int MUL>
 __global__ void __launch_bounds__(DELTA_THREADS) rspmm_delta_rows_split_kernel(const DeltaParams p, const unsigned small_blocks) {
@@ -465,6 +503,11 @@ __global__ void __launch_bounds__(DELTA_THREADS) rspmm_edit_rows_split_kernel(co
 template <typename T, int SUM, int MUL>
 __global__ void __launch_bounds__(DELTA_THREADS) rspmm_edit_rows_samples_split_kernel(const SampleParams p, const unsigned small_blocks) {
     split_rows_roles<T, SUM, MUL, true, true>(p, small_blocks);
+}
+// delta edges OWNED by outer slices (ultra_rspmm_edit_rows_owned): one launch, both roles
+template <typename T, int SUM, int MUL>
+__global__ void __launch_bounds__(DELTA_THREADS) rspmm_edit_rows_owned_kernel(const OwnedParams p, const unsigned small_blocks) {
+    split_rows_roles<T, SUM, MUL, true, false, true>(p, small_blocks);
 }
 
 // kernel K_'s instantiations by [dtype != ULTRA_F32][sum * 2 + mul]
@@ -494,6 +537,7 @@ static void (*const SAMPLES_KERNELS[2][6])(SampleParams) = ULTRA_ROWS_KERNELS(rs
 static void (*const DELTA_SPLIT_KERNELS[2][6])(DeltaParams, unsigned) = ULTRA_ROWS_KERNELS(rspmm_delta_rows_split_kernel);
 static void (*const EDIT_SPLIT_KERNELS[2][6])(EditParams, unsigned) = ULTRA_ROWS_KERNELS(rspmm_edit_rows_split_kernel);
 static void (*const SAMPLES_SPLIT_KERNELS[2][6])(SampleParams, unsigned) = ULTRA_ROWS_KERNELS(rspmm_edit_rows_samples_split_kernel);
+static void (*const OWNED_KERNELS[2][6])(OwnedParams, unsigned) = ULTRA_ROWS_KERNELS(rspmm_edit_rows_owned_kernel);
 #undef ULTRA_ROWS_KERNELS
 
 static int delta_invalid(const char *who, const std::string &msg) {
@@ -525,7 +569,8 @@ static bool delta_vec_ok(const ultra_mat *m, int64_t step) {
 static int delta_rows_impl(const char *who, ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const ultra_mat *relation,
                            const ultra_mat *input, const ultra_mat *boundary, const int64_t *point_rows_dev,
                            const ultra_mat *output, const ultra_delta *delta, const ultra_tombstones *removed, void *stream,
-                           const ultra_sample_keys *keys = nullptr, bool split = false, int64_t hub_len = INT32_MAX) {
+                           const ultra_sample_keys *keys = nullptr, bool split = false, int64_t hub_len = INT32_MAX,
+                           bool owned = false, const int32_t *owner_dev = nullptr) {
     if (!plan) return delta_invalid(who, "plan is NULL");
     if (sum < 0 || sum > 2) return delta_invalid(who, "unknown sum code");
     if (mul != ULTRA_MUL_MUL && mul != ULTRA_MUL_ADD && mul != ULTRA_MUL_ROTATE) return delta_invalid(who, "unknown mul code");
@@ -542,6 +587,7 @@ static int delta_rows_impl(const char *who, ultra_plan *plan, int32_t sum, int32
     if (n_outer == 0 || delta->capacity_rows == 0) return ULTRA_OK;
     if (!delta->row_dev || !delta->ptr_dev || !delta->col_dev || !delta->type_dev || !delta->count_dev)
         return delta_invalid(who, "delta: a NULL array");
+    if (owned && !owner_dev) return delta_invalid(who, "owner_dev is NULL");
     // (ptr_dev is read for every touched row; the key arrays only below a non-zero capacity)
     if (removed && (!removed->ptr_dev || (removed->capacity_keys > 0 && (!removed->col_dev || !removed->type_dev))))
         return delta_invalid(who, "removed: a NULL array");
@@ -566,7 +612,8 @@ static int delta_rows_impl(const char *who, ultra_plan *plan, int32_t sum, int32
     if (grid + (split ? groups : 0) >= (1ll << 31)) return delta_invalid(who, "capacity_rows * n_outer exceeds the launch grid");
     if ((rc = ultra_plan_upload(plan))) return rc;
 
-    SampleParams p;
+    OwnedParams p;
+    p.d_owner = owner_dev;
     p.row_ptr = plan->d.row_ptr, p.col = plan->d.col, p.type = plan->d.type;
     p.d_row = delta->row_dev, p.d_ptr = delta->ptr_dev, p.d_col = delta->col_dev, p.d_type = delta->type_dev;
     p.d_count = delta->count_dev;
@@ -591,6 +638,14 @@ static int delta_rows_impl(const char *who, ultra_plan *plan, int32_t sum, int32
     (void)hipGetLastError();   // drop any stale error left by other users of the HIP runtime
     const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool f32 = dtype == ULTRA_F32;
+    if (owned) {      // (always the split shape: both roles in one launch)
+        const hipError_t e = launch_split<OwnedParams>(OWNED_KERNELS, f32, sum, mul, p, (unsigned)grid, (unsigned)groups, s);
+        if (e != hipSuccess) {
+            set_error(std::string("rspmm_edit_rows_owned_kernel launch: ") + hipGetErrorString(e));
+            return ULTRA_ERR_HIP;
+        }
+        return ULTRA_OK;
+    }
     if (split) {
         const unsigned hubs = (unsigned)groups;
         const hipError_t e = keys      ? launch_split<SampleParams>(SAMPLES_SPLIT_KERNELS, f32, sum, mul, p, (unsigned)grid, hubs, s)
@@ -657,6 +712,15 @@ extern "C" int32_t ultra_rspmm_edit_rows_split(ultra_plan *plan, int32_t sum, in
     ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);
     return delta_rows_impl(who, plan, sum, mul, dtype, relation, input, boundary, point_rows_dev, output, delta, removed, stream, keys,
                            true, hub_len);
+}
+
+extern "C" int32_t ultra_rspmm_edit_rows_owned(ultra_plan *plan, int32_t sum, int32_t mul, int32_t dtype, const ultra_mat *relation,
+                                               const ultra_mat *input, const ultra_mat *boundary, const int64_t *point_rows_dev,
+                                               const ultra_mat *output, const ultra_delta *delta, const int32_t *owner_dev,
+                                               const ultra_tombstones *removed, int64_t hub_len, void *stream) {
+    ULTRA_DEVICE_SCOPE(stream, output ? output->ptr : nullptr);
+    return delta_rows_impl("ultra_rspmm_edit_rows_owned", plan, sum, mul, dtype, relation, input, boundary, point_rows_dev, output,
+                           delta, removed, stream, nullptr, true, hub_len, true, owner_dev);
 }
 
 extern "C" int32_t ultra_rspmm_hub_tile(void) { return HUB_TILE; }

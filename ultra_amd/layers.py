@@ -179,6 +179,7 @@ class GeneralizedRelationalConv(nn.Module):
             out = self._forward_impl(input, query, boundary, edge_index, edge_type, size, edge_weight, residual=False, delta=delta)
             if out is not None:
                 return out
+            # (an overlay of per-sample facts, rspmm.AssumedFacts, has no shared edge list: its edges() raises)
             extra_index, extra_type = delta.edges()
             edge_index, edge_type = delta.surviving(edge_index, edge_type)
             edge_index, edge_type = torch.cat([edge_index, extra_index], dim=1), torch.cat([edge_type, extra_type])
@@ -367,7 +368,13 @@ class GeneralizedRelationalConv(nn.Module):
         plan = rspmm.get_plan(edge_index, edge_type, num_node, relation.shape[1])
         sum = {"sum": "add", "mean": "add"}.get(self.aggregate_func, self.aggregate_func)
         mul = self.message2mul[self.message_func]
-        if rspmm.EDIT_ROWS_HUB_SPLIT and plan.has_hub_rows:      # (the same rows, the same bits: hub rows by a workgroup each)
+        if getattr(delta, "per_query_owned", False):
+            # an overlay of facts assumed per sample (rspmm.AssumedFacts): the owned entry, one launch with both
+            # roles, tombstones or none.  `mean` would need a per-sample degree: not served
+            if self.aggregate_func == "mean":
+                return None
+            fix_rows = plan.edit_rows_owned
+        elif rspmm.EDIT_ROWS_HUB_SPLIT and plan.has_hub_rows:      # (the same rows, the same bits: hub rows by a workgroup each)
             fix_rows = plan.edit_rows_split
         else:
             fix_rows = plan.edit_rows if delta.num_removed else plan.delta_rows

@@ -783,6 +783,10 @@ class EntityNBFNet(BaseNBFNet):
                     raise _DeltaRouteUnsupported()
                 return self._forward_delta(data, relation_representations, batch, prologue, delta)
             except _DeltaRouteUnsupported:
+                if getattr(delta, "per_query_owned", False):
+                    # (facts assumed per sample, rspmm.AssumedFacts: no shared materialised graph to fall back to)
+                    raise NotOnFusedPath("an overlay of assumed facts outside the engine route runs query by query "
+                                         "(predict.assume_reference's loop)")
                 return _materialized_forward(lambda graph: self.forward(graph, relation_representations, batch), data, delta,
                                              batch.is_cuda)
         if edge_keep is not None:

@@ -33,10 +33,10 @@ import math
 
 import torch
 
-from . import _lib, dense, models, selection, tasks
+from . import _lib, dense, models, rspmm, selection, tasks
 from .candidates import CandidateSets, span_rows
 from .graph import Capture, param_state
-from .live import LiveGraph, check_live, check_live_relations, check_not_retired, forwarded
+from .live import LiveGraph, check_live, check_live_relations, check_not_retired, forwarded, with_facts
 
 _select = selection.launch      # (the dispatcher, under the name and with the arguments it is called by here)
 
@@ -326,10 +326,11 @@ def filtered_above(pred, threshold, ptr=None, index=None, num_live=None, retired
     return out_ptr, ids, scores, size
 
 
-def known_answers(data, anchor, relation, mode="tail"):
+def known_answers(data, anchor, relation, mode="tail", extra=None):
     """(ptr (n + 1), index): per query the distinct tails of (anchor, relation, .) in `data` (mode="tail") or the distinct
     heads of (., relation, anchor) (mode="head"), ascending.  tasks.known_answers without the positive: for a true triple of
-    `data` the two agree."""
+    `data` the two agree.  extra (None, or (sample, ids) int64 vectors): ids[j] is one more known answer of query
+    sample[j] alone -- the answers a query's own assumed facts state."""
     if mode not in ("tail", "head"):
         raise ValueError("mode must be 'tail' or 'head', got %r" % (mode,))
     keyed, answer_row = (0, 1) if mode == "tail" else (1, 0)
@@ -339,7 +340,10 @@ def known_answers(data, anchor, relation, mode="tail"):
     truth = data.edge_index[answer_row, edge_id]
     sample = torch.arange(len(count), device=anchor.device).repeat_interleave(count)
     n = data.num_nodes
-    key = torch.unique(sample * n + truth)                     # sorted: grouped by query, ids ascending
+    key = sample * n + truth
+    if extra is not None:
+        key = torch.cat([key, extra[0].to(key.device) * n + extra[1].to(key.device)])
+    key = torch.unique(key)                                    # sorted: grouped by query, ids ascending
     ptr = torch.searchsorted(key, torch.arange(len(anchor) + 1, device=anchor.device) * n)
     return ptr, key % n
 
@@ -429,7 +433,8 @@ class _GraphedPredictStep(_IndexedStep):
         _IndexedStep.__init__(self, model, data, batch_size, index_capacity, delta, n_live, retired, among)
         dev = data.edge_index.device
         self.k, self.mode = k, mode
-        model_kwargs = {} if delta is None else {"delta": delta}
+        handed = self._model_delta(data, delta, batch_size)
+        model_kwargs = {} if handed is None else {"delta": handed}
         self.anchor = torch.zeros(batch_size, dtype=torch.long, device=dev)
         self.relation = torch.zeros(batch_size, dtype=torch.long, device=dev)
         self.ids = torch.empty(batch_size, k, dtype=torch.long, device=dev)
@@ -450,6 +455,11 @@ class _GraphedPredictStep(_IndexedStep):
             _select("ultra_filtered_topk", args, n_live, dev, retired, among=self.among_operand)
 
         self.record_step(step, warmup, (self.anchor, self.relation), (self.ids, self.scores, self.count))
+
+
+    def _model_delta(self, data, delta, batch_size):
+        """What the model is handed as `delta=` (None: nothing): the delta itself; _GraphedAssumeStep hands an overlay over it."""
+        return delta
 
 
 def _release(steps):
@@ -587,6 +597,156 @@ def verify_reference(model, data, filter_graph, h, r, t, mode="tail"):
     return score, rank, num_negative
 
 
+# ---- what-if queries: facts assumed per query ----
+def assume_supported(model):
+    """Does `model` answer what-if queries (tails(h, r, assuming=) ...) on the cached plan -- forward(delta=) with every entity
+    layer on ultra_rspmm_edit_rows_owned: sum / max / min aggregates with TransE / DistMult messages?  (`mean` would need a
+    per-sample degree; pna and RotatE have no delta route.)  Another model runs the per-query loop of assume_reference."""
+    try:
+        params = inspect.signature(getattr(model, "forward", model)).parameters
+    except (TypeError, ValueError):
+        return False
+    layers = getattr(_entity_model(model), "layers", None)
+    return ("delta" in params and layers is not None and len(layers) > 0
+            and all(getattr(layer, "aggregate_func", None) in ("sum", "max", "min")
+                    and getattr(layer, "message_func", None) in ("transe", "distmult") for layer in layers))
+
+
+def _assumed_lists(data, assuming, n, per_query=None, **live):
+    """`assuming` of a call with n queries as a list of n (m_i, 3) int64 (h, r, t) tensors on the graph's device: one (m, 3)
+    tensor is assumed by every query; a list or tuple holds one entry per query -- (m_i, 3) rows, or None / empty.  The facts
+    follow _check_facts (`live`: its num_live / num_direct / retired; h and t are ALWAYS bounded -- by num_live, else by
+    data.num_nodes -- so no id reaches a forward or another query's known-answer keys unchecked); ValueError for a wrong count,
+    a wrong shape, or more than per_query facts in one entry."""
+    dev = data.edge_index.device
+    if live.get("num_live") is None:        # (always bounded: without a reserve every row of the graph is an entity)
+        live = dict(live, num_live=int(data.num_nodes))
+    if torch.is_tensor(assuming):
+        entries = [assuming] * n
+    elif isinstance(assuming, (list, tuple)):
+        if len(assuming) != n:
+            raise ValueError("`assuming` is one (m, 3) tensor for every query or a list with one entry per query: got %d "
+                             "entries for %d queries" % (len(assuming), n))
+        entries = list(assuming)
+    else:
+        raise ValueError("`assuming` is one (m, 3) tensor or a list with one entry per query, got %r" % type(assuming).__name__)
+    out, checked = [], {}
+    for entry in entries:
+        if id(entry) not in checked:
+            facts = torch.zeros(0, 3, dtype=torch.long) if entry is None else torch.as_tensor(entry, dtype=torch.long)
+            if facts.numel() == 0:
+                facts = facts.reshape(0, 3)
+            if facts.dim() != 2 or facts.shape[1] != 3:
+                raise ValueError("assumed facts are (m, 3) rows (h, r, t), got shape %s" % (tuple(facts.shape),))
+            if per_query is not None and len(facts) > per_query:
+                raise ValueError("a query assumes at most assume_capacity = %d facts, got %d" % (per_query, len(facts)))
+            facts = facts.to(dev)
+            _check_facts(data, facts[:, 0], facts[:, 1], facts[:, 2], **live)
+            checked[id(entry)] = facts
+        out.append(checked[id(entry)])
+    return out
+
+
+def _assumed_known(assumed, anchor, relation, mode):
+    """The (sample, ids) `extra` of known_answers: the answers of query i that its own assumed facts state -- the tails t of its
+    facts (anchor[i], relation[i], t) (mode="tail") or the heads h of its facts (h, relation[i], anchor[i]) (mode="head")."""
+    keyed, answer = (0, 2) if mode == "tail" else (2, 0)
+    sample, ids = [], []
+    for i, facts in enumerate(assumed):
+        if len(facts):
+            hit = (facts[:, keyed] == anchor[i]) & (facts[:, 1] == relation[i])
+            ids.append(facts[hit, answer])
+            sample.append(torch.full_like(ids[-1], i))
+    if not ids:
+        empty = torch.zeros(0, dtype=torch.long, device=anchor.device)
+        return empty, empty
+    return torch.cat(sample), torch.cat(ids)
+
+
+def _assumed_graph(graph, facts):
+    """A copy of `graph` with the edges of `facts` (m, 3) = (h, r, t) appended -- direct, then inverse -- and everything else,
+    the relation graph included, kept."""
+    return with_facts(graph, facts[:, 0], facts[:, 1], facts[:, 2]) if len(facts) else graph
+
+
+@torch.no_grad()
+def assume_reference(model, data, filter_graph, anchor, relation, assuming, k=10, mode="tail", min_score=None, num_live=None,
+                     retired=None, among=None):
+    """What-if queries in plain terms, on any device -- the DEFINITION Predictor.tails / heads / tails_above / heads_above
+    (assuming=) are tested against.  Query i = (anchor[i], relation[i]) is answered on a COPY of `data` with its assumed facts
+    appended -- [data's edges ; its direct edges (h, t, r) in the given order ; their inverse edges], duplicates kept, the
+    relation graph kept as it is (the reference keeps it when a sample's edge set differs: remove_easy_edges) -- by one forward,
+    and filtered against `filter_graph` (None: no filter) plus its own assumed facts: filtered_topk_reference, or with
+    min_score filtered_above_reference.  No other query sees the facts; nothing is stated.  assuming: one (m, 3) tensor of
+    (h, r, t) rows for every query, or a list with one entry per query (rows, None or empty).  Returns (ids (n, k), scores
+    (n, k), count (n)), or with min_score (ptr (n + 1), ids, scores, size (n)).  One plan and one forward per query.
+    num_live, retired, among: those of the _reference selections -- among is one id vector for every query or a list of one
+    per query (the candidate set of `Predictor.tails(among=)`)."""
+    if mode not in ("tail", "head"):
+        raise ValueError("mode must be 'tail' or 'head', got %r" % (mode,))
+    dev = data.edge_index.device
+    anchor = torch.as_tensor(anchor, dtype=torch.long, device=dev).flatten()
+    relation = torch.as_tensor(relation, dtype=torch.long, device=dev).flatten()
+    assumed = _assumed_lists(data, assuming, len(anchor))
+    select = {} if num_live is None else {"num_live": num_live}
+    if retired is not None:
+        select["retired"] = retired
+    rows = []
+    with eval_mode(model):
+        for i, facts in enumerate(assumed):
+            a, r = anchor[i:i + 1], relation[i:i + 1]
+            graph = _assumed_graph(data, facts)
+            pred = model(graph, _candidates(graph, a, r, mode)).float()
+            ptr = index = None
+            if filter_graph is not None:
+                ptr, index = known_answers(_assumed_graph(filter_graph, facts), a, r, mode)
+            if among is not None:
+                select["among"] = [among[i] if isinstance(among, (list, tuple)) else among]
+            if min_score is None:
+                rows.append(filtered_topk_reference(pred, k, ptr, index, **select))
+            else:
+                rows.append(filtered_above_reference(pred, min_score, ptr, index, **select))
+    if min_score is None:
+        if not rows:
+            return (torch.zeros(0, k, dtype=torch.long, device=dev), torch.zeros(0, k, dtype=torch.float32, device=dev),
+                    torch.zeros(0, dtype=torch.long, device=dev))
+        return tuple(torch.cat([row[j] for row in rows]) for j in range(3))
+    return _join_above(rows, dev)
+
+
+def _join_above(parts, dev):
+    """The (ptr, ids, scores, size) of a whole call from those of its consecutive parts."""
+    out_ptr, at = [torch.zeros(1, dtype=torch.long, device=dev)], 0
+    for ptr, ids, _, _ in parts:
+        out_ptr.append(ptr[1:] + at)
+        at += ids.numel()
+    if not parts:
+        return (out_ptr[0], torch.zeros(0, dtype=torch.long, device=dev), torch.zeros(0, dtype=torch.float32, device=dev),
+                torch.zeros(0, dtype=torch.long, device=dev))
+    return (torch.cat(out_ptr),) + tuple(torch.cat([part[j] for part in parts]) for j in (1, 2, 3))
+
+
+def _assume_route(delta):
+    """What a captured what-if step remembers of the delta under its overlay: the relation-graph object alone (the owned entry
+    takes tombstones or none in the same launch, and an empty overlay is a launch that ends at once)."""
+    return None if delta is None else id(delta.relation_graph)
+
+
+class _GraphedAssumeStep(_GraphedPredictStep):
+    """_GraphedPredictStep for what-if queries: the model is handed `overlay` -- an rspmm.AssumedFacts over the
+    predictor's delta with room for `per_query` facts a query -- so every entity layer records ultra_rspmm_edit_rows_owned over
+    the overlay's buffers.  Between replays the host refills the overlay (`overlay.fill`); nothing is recorded again."""
+
+    def __init__(self, model, data, batch_size, k, mode, index_capacity, per_query, **kwargs):
+        self.per_query = per_query
+        _GraphedPredictStep.__init__(self, model, data, batch_size, k, mode, index_capacity, **kwargs)
+
+    def _model_delta(self, data, delta, batch_size):
+        self.route = _assume_route(delta)
+        self.overlay = rspmm.AssumedFacts(data, delta, batch_size, self.per_query)
+        return self.overlay
+
+
 class _GraphedVerifyStep(_IndexedStep):
     """One batch of stated facts of one direction as ONE hipGraph replay (a graph.Capture, like _GraphedPredictStep): the
     leave-one-out keep rows from the (bs, 3) triples (ultra_leave_one_out_keep into the step's (bs, num_edge) fp32 buffer), the
@@ -715,8 +875,14 @@ class Predictor(object):
     taken out of the candidate set.  A predictor that never retires calls exactly the entries it called before."""
 
     def __init__(self, model, data, k=10, batch_size=8, filtered_data=None, filtered=True, use_graph=True, delta_capacity=256,
-                 entity_capacity=0, relation_capacity=0, relation_bits_budget=256 << 20, live_relation_graph=False):
+                 entity_capacity=0, relation_capacity=0, relation_bits_budget=256 << 20, live_relation_graph=False,
+                 assume_capacity=8):
         check_k(k)
+        if isinstance(assume_capacity, bool) or not isinstance(assume_capacity, int) or assume_capacity < 1:
+            raise ValueError("assume_capacity must be a positive int (facts one query may assume), got %r" % (assume_capacity,))
+        self.assume_capacity = assume_capacity
+        self._assume_eager_only = False
+        self._assume_overlay = None         # (delta, overlay): the overlay of the eager what-if batches
         if not isinstance(live_relation_graph, bool):
             raise ValueError("live_relation_graph must be True or False, got %r" % (live_relation_graph,))
         if live_relation_graph:
@@ -859,30 +1025,40 @@ class Predictor(object):
         delta = self.delta      # (handed over whenever it exists, empty or not: the capture relies on it)
         return {} if delta is None else {"delta": delta}
 
-    def tails(self, h, r, among=None):
-        """among (None: every entity): the candidates of query i are the ids of a set -- a name (define_set), a 1-D
+    def tails(self, h, r, among=None, assuming=None):
+        """assuming (None: nothing): facts ASSUMED for this call only -- "if (a, r', b) were true, what would the
+        tails of (h, r, ?) be?".  One (m, 3) int64 tensor of (h, r, t) rows is assumed by every query; a list holds one entry
+        per query ((m_i, 3) rows, None or empty).  Query i is answered on [materialised served graph ; its direct edges in the
+        given order ; their inverse edges] with the served relation graph, and filtered against the filter graph plus its own
+        assumed facts: an assumed tail of (h[i], r[i], ?) is a known answer of query i only.  Nothing is stated -- materialized(),
+        the delta, the filter graph and the other routes' captures are untouched, and query j never sees query i's facts.  The
+        facts follow add_facts' rules (ValueError); at most `assume_capacity` a query (ValueError).  On the GPU a batch is one
+        replay of a captured step of its own (key (mode, "assume")) whose entity layers run ultra_rspmm_edit_rows_owned over
+        an overlay (rspmm.AssumedFacts) that the host refills between replays; a model outside assume_supported, and every
+        call off the GPU, runs assume_reference's loop.  A call whose assumptions are all empty is the call without them.
+        among (None: every entity): the candidates of query i are the ids of a set -- a name (define_set), a 1-D
         id vector or list (one set for every query) or a sequence of one name or vector per query (ValueError for a wrong
         count, KeyError for an unknown name, ValueError for an id outside [0, num_slots)) -- that are live, alive and not
         known: count[i] = min(k, how many there are).  The selection gathers the listed scores (ultra_filtered_topk_among): the
         same order and bits as the full ranking restricted to the set.  Captured under a key of its own; a later call whose
         sets fit the step's buffers records nothing."""
-        return self._run(*self._query(h, r), "tail", among)
+        return self._run(*self._query(h, r), "tail", among, assuming)
 
-    def heads(self, t, r, among=None):
-        return self._run(*self._query(t, r), "head", among)
+    def heads(self, t, r, among=None, assuming=None):
+        return self._run(*self._query(t, r), "head", among, assuming)
 
-    def tails_above(self, h, r, min_score, among=None):
+    def tails_above(self, h, r, min_score, among=None, assuming=None):
         """Every tail of (h[i], r[i], ?) whose logit exceeds `min_score` (a Python float: the threshold of
         filtered_above_reference), ranked: (ptr (n + 1) int64, ids, scores, size (n) int64) for the whole call, in query order
         -- the set of query i is ids[ptr[i] : ptr[i + 1]], best first; known answers are left out as in `tails`, while size[i]
         counts every entity above the threshold, known ones included.  The forward runs eagerly, batch by batch, and
         ultra_filtered_above selects on the device; the host reads one number per batch (the batch's total) to slice the
         batch's lists out of their full-capacity buffers.  Off the GPU the plain-torch restatement selects, as in `tails`."""
-        return self._run_above(h, r, min_score, "tail", among)
+        return self._run_above(h, r, min_score, "tail", among, assuming)
 
-    def heads_above(self, t, r, min_score, among=None):
+    def heads_above(self, t, r, min_score, among=None, assuming=None):
         """tails_above for the heads of (?, r[i], t[i])."""
-        return self._run_above(t, r, min_score, "head", among)
+        return self._run_above(t, r, min_score, "head", among, assuming)
 
     def explain_tails(self, h, r, chunk=16, compact=True, among=None):
         """tails(h, r) plus why: (ids, scores, count, explanations).  explanations[i][j], j < count[i], is the (paths, weights)
@@ -984,14 +1160,14 @@ class Predictor(object):
             check_live_relations(relation, self.num_direct_relations, "the relations of a query")
         return anchor, relation
 
-    def _step(self, key, need, build, among_need=None):
+    def _step(self, key, need, build, among_need=None, route=_delta_route):
         """The captured step `key` of `_steps`, (re)built -- build(capacity) -- when there is none, the weights changed, the known
         lists of the call (`need` ids; None: no filter) do not fit its buffer, the delta, its route or the retired pair changed.
         among_need ((ids in all, longest list) of a call with candidate sets; None: none): ... or the call's lists do not fit the
         step's buffer or its longest list its capacity -- build(capacity, (index capacity, list capacity)) then, both doubled."""
         step = self._steps.get(key)
         if step is not None and step.params == param_state(self.model) and (need is None or need <= step.capacity) \
-                and step.delta is self.delta and step.route == _delta_route(self.delta) and step.retired is self._live.retired_operand \
+                and step.delta is self.delta and step.route == route(self.delta) and step.retired is self._live.retired_operand \
                 and (among_need is None or step.among_fits(*among_need)):
             return step
         if step is not None:
@@ -1004,20 +1180,23 @@ class Predictor(object):
             step = self._steps[key] = build(capacity, (max(2 * among_need[0], 1 << 16), max(2 * among_need[1], _lib.TOPK_CHUNK)))
         return step
 
-    def _batched(self, key, build, rows, ptr, index, outs, eager, capturable=True, among=None):
+    def _batched(self, key, build, rows, ptr, index, outs, eager, capturable=True, among=None, route=_delta_route, before=None,
+                 eager_flag="_eager_only"):
         """The batch loop of tails / heads / verify_*, inside eval_mode: `rows` (the per-query tensors a step takes) in batches of
         batch_size into `outs`.  On the GPU with use_graph each batch is one replay of the captured step `key` (_step): a last
         batch that is short is padded with copies of its last row with no known list, `index` is loaded once, and the step's
         buffers are copied out, the padded rows dropped.  A model outside the fused inference path (models.NotOnFusedPath),
         and every other case: eager(lo) gives the outputs of the batch that starts at row lo.
         among (None, or the call's (span, index, longest) of CandidateSets.assemble): the step -- under a key of its own --
-        takes the call's lists once (load_among) and a batch's spans per replay; a padded row gets an empty span."""
+        takes the call's lists once (load_among) and a batch's spans per replay; a padded row gets an empty span.
+        route: what the step remembers of the delta (_step); before(step, lo): called ahead of the replay of the batch at lo;
+        eager_flag: the attribute that remembers "this route is not capturable here" -- every route owns its own."""
         n, bs = len(rows[0]), self.batch_size
         start = 0
-        if capturable and self.use_graph and outs[0].is_cuda and not self._eager_only:
+        if capturable and self.use_graph and outs[0].is_cuda and not getattr(self, eager_flag):
             try:
                 step = self._step(key, None if index is None else index.numel(), build,
-                                  None if among is None else (among[1].numel(), among[2]))
+                                  None if among is None else (among[1].numel(), among[2]), route=route)
                 pad = (-n) % bs
                 padded, ptr_p = rows, ptr
                 if pad:
@@ -1031,13 +1210,15 @@ class Predictor(object):
                 for lo in range(0, n, bs):
                     if among is not None:
                         step.among_span.copy_(span_p[lo:lo + bs], non_blocking=True)
+                    if before is not None:
+                        before(step, lo)
                     got = step(*(t[lo:lo + bs] for t in padded), None if ptr_p is None else ptr_p[lo:lo + bs + 1])
                     for out, b_out in zip(outs, got):
                         out[lo:lo + bs].copy_(b_out[:min(bs, n - lo)], non_blocking=True)
                 start = n
             except models.NotOnFusedPath:       # model outside the fused inference path: everything runs eagerly below
                 torch.cuda.synchronize()
-                self._eager_only = True
+                setattr(self, eager_flag, True)
         for lo in range(start, n, bs):
             for out, b_out in zip(outs, eager(lo)):
                 out[lo:lo + len(b_out)] = b_out
@@ -1103,24 +1284,68 @@ class Predictor(object):
             return {"among": (part, index), "among_capacity": max(1, longest)}
         return {"among": span_rows(part, index)}
 
+    # ---- what-if queries ----
+    def _assumed(self, assuming, n):
+        """`assuming` of a call with n queries: None where nothing is assumed (the plain route), else _assumed_lists under the
+        rules of add_facts and the capacity."""
+        if assuming is None:
+            return None
+        assumed = _assumed_lists(self.data, assuming, n, per_query=self.assume_capacity,
+                                 num_live=self.num_entities if self.entity_capacity else None,
+                                 num_direct=self.num_direct_relations if self.relation_capacity else None,
+                                 retired=self.retired_entities)
+        return assumed if any(len(facts) for facts in assumed) else None
+
+    def _assume_served(self):
+        """Does the engine route answer what-if queries here: a model in assume_supported, a delta to lay the overlay over, the GPU?"""
+        return (not self._assume_eager_only and self.delta is not None and self.data.edge_index.is_cuda
+                and assume_supported(self.model))
+
+    def _assume_scores(self, assumed, anchor, relation, mode, lo):
+        """The (rows, N) fp32 scores of the what-if batch that starts at query lo, eagerly: one forward over the overlay where
+        the engine serves it, else query by query on a copy of the materialised served graph with the query's facts appended
+        (assume_reference's loop)."""
+        data, bs = self.data, self.batch_size
+        part = assumed[lo:lo + bs]
+        if self._assume_served():
+            if self._assume_overlay is None or self._assume_overlay[0] is not self.delta:
+                self._assume_overlay = (self.delta, rspmm.AssumedFacts(data, self.delta, bs, self.assume_capacity))
+            overlay = self._assume_overlay[1]
+            overlay.fill(part + [None] * (bs - len(part)))
+            try:
+                return self.model(data, _candidates(data, anchor[lo:lo + bs], relation[lo:lo + bs], mode), delta=overlay).float()
+            except models.NotOnFusedPath:       # (a plan or a shape the owned entry does not serve)
+                self._assume_eager_only = True
+        full = self._live._probe().materialize(data)
+        rows = []
+        for i, facts in enumerate(part):
+            graph = _assumed_graph(full, facts)
+            rows.append(self.model(graph, _candidates(graph, anchor[lo + i:lo + i + 1], relation[lo + i:lo + i + 1], mode)).float())
+        return torch.cat(rows)
+
     @torch.no_grad()
-    def _run_above(self, anchor, relation, min_score, mode, among=None):
+    def _run_above(self, anchor, relation, min_score, mode, among=None, assuming=None):
         threshold = _fp32_threshold(min_score)
         data, bs, live, model_kwargs = self.data, self.batch_size, self._live, self._model_kwargs()
         dev = data.edge_index.device
         anchor, relation = self._query(anchor, relation)
         n = len(anchor)
+        assumed = self._assumed(assuming, n)
         if among is not None:
             among = self._sets.assemble(among, n, dev)
         out_ptr, ids, scores, size = [torch.zeros(1, dtype=torch.long, device=dev)], [], [], []
         with eval_mode(self.model):
             ptr = index = None
             if self.filtered and n:     # the known lists of the whole call, once
-                ptr, index = known_answers(self.filter_graph, anchor, relation, mode)
+                extra = None if assumed is None else _assumed_known(assumed, anchor, relation, mode)
+                ptr, index = known_answers(self.filter_graph, anchor, relation, mode, extra=extra)
             at = 0
             for lo in range(0, n, bs):
-                pred = self.model(data, _candidates(data, anchor[lo:lo + bs], relation[lo:lo + bs], mode),
-                                  **model_kwargs).float()
+                if assumed is not None:
+                    pred = self._assume_scores(assumed, anchor, relation, mode, lo)
+                else:
+                    pred = self.model(data, _candidates(data, anchor[lo:lo + bs], relation[lo:lo + bs], mode),
+                                      **model_kwargs).float()
                 b_ptr = None if ptr is None else ptr[lo:lo + len(pred) + 1]
                 if pred.is_cuda:
                     b_out, b_ids, b_scores, b_size = filtered_above(pred, threshold, b_ptr, index, **live.selection_for(pred.is_cuda),
@@ -1143,11 +1368,50 @@ class Predictor(object):
         return torch.cat(out_ptr), torch.cat(ids), torch.cat(scores), torch.cat(size)
 
     @torch.no_grad()
-    def _run(self, anchor, relation, mode, among=None):
-        """tails / heads of the queries (anchor, relation) as _query gives them; among: as the caller gave it."""
+    def _run_assume(self, anchor, relation, mode, among, assumed):
+        """_run for a call in which some query assumes facts (`assumed`: _assumed's list): the captured step (mode, "assume") --
+        its overlay refilled ahead of every replay -- or, where that does not apply, _assume_scores batch by batch."""
+        data, bs, k, live = self.data, self.batch_size, self.k, self._live
+        dev = data.edge_index.device
+        n = len(anchor)
+        outs = (torch.empty(n, k, dtype=torch.long, device=dev), torch.empty(n, k, dtype=torch.float32, device=dev),
+                torch.empty(n, dtype=torch.long, device=dev))       # (ids, scores, count)
+        if among is not None:
+            among = self._sets.assemble(among, n, dev)
+        with eval_mode(self.model):
+            ptr = index = None
+            if self.filtered:       # the known lists of the whole call, once: every query's own assumed answers among them
+                ptr, index = known_answers(self.filter_graph, anchor, relation, mode,
+                                           extra=_assumed_known(assumed, anchor, relation, mode))
+
+            def eager(lo):
+                pred = self._assume_scores(assumed, anchor, relation, mode, lo)
+                select = filtered_topk if pred.is_cuda else filtered_topk_reference
+                return select(pred, k, None if ptr is None else ptr[lo:lo + len(pred) + 1], index, **live.selection_for(pred.is_cuda),
+                              **self._among_for(among, lo, len(pred), pred.is_cuda))
+
+            def refill(step, lo):
+                part = assumed[lo:lo + bs]
+                step.overlay.fill(part + [None] * (bs - len(part)))
+
+            self._batched((mode, "assume") if among is None else (mode, "assume", "among"),
+                          lambda capacity, among_sizes=None: _GraphedAssumeStep(
+                              self.model, data, bs, k, mode, capacity, self.assume_capacity, delta=self.delta,
+                              n_live=self.live_count, retired=self._live.retired_operand,
+                              **({} if among_sizes is None else {"among": among_sizes})),
+                          (anchor, relation), ptr, index, outs, eager, capturable=self._assume_served(), among=among,
+                          route=_assume_route, before=refill, eager_flag="_assume_eager_only")
+        return outs
+
+    @torch.no_grad()
+    def _run(self, anchor, relation, mode, among=None, assuming=None):
+        """tails / heads of the queries (anchor, relation) as _query gives them; among, assuming: as the caller gave them."""
         data, bs, k, live, model_kwargs = self.data, self.batch_size, self.k, self._live, self._model_kwargs()
         dev = data.edge_index.device
         n = len(anchor)
+        assumed = self._assumed(assuming, n)
+        if assumed is not None:
+            return self._run_assume(anchor, relation, mode, among, assumed)
         outs = (torch.empty(n, k, dtype=torch.long, device=dev), torch.empty(n, k, dtype=torch.float32, device=dev),
                 torch.empty(n, dtype=torch.long, device=dev))       # (ids, scores, count)
         if among is not None:

@@ -400,7 +400,8 @@ class Plan(object):
     def _recompute_rows(self, entry, relation, input, out, delta, boundary, sum, mul, point, edits, on_gpu=(), tail=()):
         """The body of delta_rows, edit_rows, edit_rows_samples and edit_rows_split: the checks, the operands, one call of `entry`.
         `edits()` -- called once the checks have passed -- returns the entry's struct operands between `output` and `stream`, the
-        delta's first (None: a NULL pointer); `tail`: plain arguments that follow them; `on_gpu`: further tensors the entry reads."""
+        delta's first (None: a NULL pointer; an int: a device address, passed as it is); `tail`: plain arguments that follow them;
+        `on_gpu`: further tensors the entry reads."""
         if not self.exact:
             return None
         if (delta.num_nodes, delta.num_relations) != (self.num_node, self.num_relation) or self.num_in != self.num_node:
@@ -414,8 +415,8 @@ class Plan(object):
             raise RuntimeError("`out` must have unit stride along its last dimension")
         operands = edits()
         rc = entry(self._h, _lib.SUM_CODES[sum], _lib.MUL_CODES[mul], op.dtype, op.relation, op.input, op.boundary, op.rows,
-                   op.out_ref, *[None if operand is None else ctypes.byref(operand) for operand in operands], *tail,
-                   stream_of(input))
+                   op.out_ref, *[operand if operand is None or isinstance(operand, int) else ctypes.byref(operand)
+                                 for operand in operands], *tail, stream_of(input))
         if rc == _lib.ULTRA_ERR_UNSUPPORTED:
             return None
         check(rc)
@@ -460,6 +461,19 @@ class Plan(object):
 
         return self._recompute_rows(lib.ultra_rspmm_edit_rows_split, relation, input, out, delta, boundary, sum, mul, point,
                                     edits, on_gpu=keys or (), tail=(ctypes.c_int64(-1 if hub_len is None else int(hub_len)),))
+
+    def edit_rows_owned(self, relation, input, out, overlay, boundary=None, sum="add", mul="mul", point=None, hub_len=None):
+        """edit_rows_split for an OVERLAY (AssumedFacts) whose delta edges have an owner each: -1 -- live in every
+        outer slice, s -- live in slice s alone, anything else -- live nowhere (ultra_rspmm_edit_rows_owned).  Afterwards slice
+        s of every touched row that holds a tombstone key or an edge live in s is the forward on a fresh reference-order plan of
+        [surviving base edges ; shared edges ; slice s's edges], bit for bit; the other (row, slice) pairs are NOT written --
+        `out` came from forward() on this plan, which is right there.  One launch, both roles, sized by the overlay's capacity.
+        Returns `out`, or None exactly where edit_rows does."""
+        def edits():
+            return overlay.operand(), overlay.owner.data_ptr(), overlay.removed_operand()
+
+        return self._recompute_rows(lib.ultra_rspmm_edit_rows_owned, relation, input, out, overlay, boundary, sum, mul, point,
+                                    edits, on_gpu=(overlay.owner,), tail=(ctypes.c_int64(-1 if hub_len is None else int(hub_len)),))
 
     @staticmethod
     def _sample_keys_operand(keys, out):
@@ -1321,6 +1335,150 @@ class GraphDelta(object):
         """The tombstones as the engine takes them (ultra_tombstones); valid while this object lives."""
         return _lib.UltraTombstones(self.dead_ptr.data_ptr(), self.dead_col.data_ptr(), self.dead_type.data_ptr(),
                                     self.dead_col.numel())
+
+
+class AssumedFacts(object):
+    """The OVERLAY of one batch of what-if queries: the persistent delta's edges, live in every sample, then the
+    facts each query ASSUMES, live in that query's sample alone.  Nothing is stated: the delta, the graph and the filter graph
+    are only read.
+
+        overlay = AssumedFacts(data, delta, batch_size, per_query)      # delta: the served graph's GraphDelta, or None
+        overlay.fill([facts_0, None, facts_2, ...])                     # one (m_i, 3) int64 (h, r, t) tensor / list or None each
+
+    Sample i then runs on G_i = [delta.materialize(data) ; its assumed direct edges (h, t, r) in the given order ; their inverse
+    edges (t, h, r + num_relations / 2)], duplicates kept as edges.  Laid out the way GraphDelta._prepare lays a delta out, into
+    buffers that keep their address and have room for delta.capacity + batch_size * per_query facts -- fill() rewrites them, a
+    captured launch reads whatever they hold at replay:
+      col / type / owner  int32 (2 F)      the edges in the plan's direction, sorted by (row, col, insertion id); the delta's
+                                           edges carry the lowest ids and owner -1, query i's edges (direct, then inverse) owner i
+      rows        int32 (2 F)              the distinct rows an edge of the overlay or a tombstone key points into, ascending
+      ptr         int32 (2 F + 1)          the edges' ranges per touched row
+      dead_ptr    int32 (2 F + 1)          the delta's tombstone keys' ranges per touched row OF THIS LAYOUT; the keys themselves
+                                           are the delta's own dead_col / dead_type arrays (the tombstone operand shares them)
+      count       int32 (1)                the number of touched rows -- the same tensor for the overlay's life
+    The live subsequence of sample s in a row is the sorted row of G_s (Plan.edit_rows_owned).  It offers what
+    layers._propagate_delta and Ultra.forward(delta=) ask of a delta; it has no shared materialised edge list (`edges`,
+    `surviving` and `materialize` raise): a route that needs one runs predict.assume_reference's loop instead."""
+    per_query_owned = True
+
+    def __init__(self, data, delta, batch_size, per_query):
+        if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+            raise ValueError("batch_size must be a positive int, got %r" % (batch_size,))
+        if isinstance(per_query, bool) or not isinstance(per_query, int) or per_query < 1:
+            raise ValueError("per_query must be a positive int (facts one query may assume), got %r" % (per_query,))
+        self.base, self.delta, self.batch_size, self.per_query = data, delta, batch_size, per_query
+        self.num_nodes, self.num_relations = int(data.num_nodes), int(data.num_relations)
+        if delta is not None and (delta.num_nodes, delta.num_relations) != (self.num_nodes, self.num_relations):
+            raise ValueError("the delta was made for a graph of %d nodes and %d relations, the overlay's has %d and %d"
+                             % (delta.num_nodes, delta.num_relations, self.num_nodes, self.num_relations))
+        dev = self.device = data.edge_index.device
+        self.capacity = (0 if delta is None else delta.capacity) + batch_size * per_query
+        cap = 2 * self.capacity
+        self.col, self.type, self.owner, self.rows = (torch.zeros(cap, dtype=torch.int32, device=dev) for _ in range(4))
+        self.ptr = torch.zeros(cap + 1, dtype=torch.int32, device=dev)
+        self.dead_ptr = torch.zeros(cap + 1, dtype=torch.int32, device=dev)
+        self.count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._no_keys = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.num_edges = 0
+        self._shared_cache = None       # (delta.version, _shared()'s parts)
+        self.fill([None] * batch_size)
+
+    edited = True       # (handed to a model it always takes the delta route: an empty overlay is a launch that ends at once)
+
+    @property
+    def num_removed(self):
+        return 0 if self.delta is None else self.delta.num_removed
+
+    @property
+    def relation_graph(self):
+        """The served relation graph: the delta's, kept as it is (the reference keeps it when a sample's edge set differs)."""
+        return getattr(self.base, "relation_graph", None) if self.delta is None else self.delta.relation_graph
+
+    def live_view(self, data):
+        return data if self.delta is None else self.delta.live_view(data)
+
+    def check(self, assumed):
+        """`assumed` -- one entry per sample -- as a list of (m_i, 3) int64 (h, r, t) tensors on the overlay's device; ValueError
+        for a wrong count, a wrong shape, or more than per_query facts in one entry.  (Ids are the caller's to check.)"""
+        if len(assumed) != self.batch_size:
+            raise ValueError("one entry of assumed facts per sample: got %d for %d samples" % (len(assumed), self.batch_size))
+        out = []
+        for facts in assumed:
+            facts = torch.zeros(0, 3, dtype=torch.long) if facts is None else torch.as_tensor(facts, dtype=torch.long)
+            facts = facts.to(self.device).reshape(-1, 3) if facts.numel() == 0 else facts.to(self.device)
+            if facts.dim() != 2 or facts.shape[1] != 3:
+                raise ValueError("assumed facts are (m, 3) rows (h, r, t), got %s" % (tuple(facts.shape),))
+            if len(facts) > self.per_query:
+                raise ValueError("a query assumes at most %d facts, got %d" % (self.per_query, len(facts)))
+            out.append(facts)
+        return out
+
+    def _shared(self):
+        """(edge_index, edge_type, key_row) of the delta as it is now: its edges in materialised order and the rows of its
+        tombstone keys, built once per delta.version -- a refill between two replays does not walk the host list of keys again."""
+        version = None if self.delta is None else self.delta.version
+        hit = self._shared_cache
+        if hit is None or hit[0] != version:
+            dev = self.device
+            if self.delta is None:
+                parts = (torch.zeros(2, 0, dtype=torch.long, device=dev), torch.zeros(0, dtype=torch.long, device=dev),
+                         torch.zeros(0, dtype=torch.long, device=dev))
+            else:
+                keys = torch.tensor(self.delta.dead_keys, dtype=torch.long, device=dev)
+                parts = self.delta.edges() + (keys // (self.num_relations * self.num_nodes),)
+            hit = self._shared_cache = (version, parts)
+        return hit[1]
+
+    def fill(self, assumed):
+        """Lay out the delta's edges as they are now and the facts `assumed` (check) into the fixed buffers.  Returns the number
+        of edges held."""
+        assumed = self.check(assumed)
+        dev, n, half = self.device, self.num_nodes, self.num_relations // 2
+        rows, cols, kinds, owners = [], [], [], []
+        shared_index, shared_type, key_row = self._shared()
+        if len(shared_type):
+            rows.append(shared_index[0]), cols.append(shared_index[1]), kinds.append(shared_type)
+            owners.append(torch.full_like(shared_type, -1))
+        for s, facts in enumerate(assumed):
+            if len(facts):
+                h, r, t = facts.unbind(1)
+                rows.append(torch.cat([h, t])), cols.append(torch.cat([t, h])), kinds.append(torch.cat([r, r + half]))
+                owners.append(torch.full((2 * len(facts),), s, dtype=torch.long, device=dev))
+        empty = torch.zeros(0, dtype=torch.long, device=dev)
+        row, col, kind, owner = (torch.cat(v) if v else empty for v in (rows, cols, kinds, owners))
+        num_edge = len(row)
+        order = torch.argsort((row * n + col) * max(num_edge, 1) + torch.arange(num_edge, device=dev))
+        row, col, kind, owner = row[order], col[order], kind[order], owner[order]
+        touched = torch.unique(torch.cat([row, key_row]))      # (ascending; its length is the refill's one host read)
+        num_touched = len(touched)
+        self.col[:num_edge] = col.to(torch.int32)
+        self.type[:num_edge] = kind.to(torch.int32)
+        self.owner[:num_edge] = owner.to(torch.int32)
+        self.rows[:num_touched] = touched.to(torch.int32)
+        for ptr, of in ((self.ptr, row), (self.dead_ptr, key_row)):
+            counts = torch.bincount(torch.searchsorted(touched, of), minlength=num_touched)
+            ptr[1:num_touched + 1] = counts.cumsum(0).to(torch.int32)
+        self.count.fill_(num_touched)
+        self.num_edges = num_edge
+        return num_edge
+
+    def operand(self):
+        """The overlay's rows and edges as the engine takes a delta (ultra_delta); valid while this object lives."""
+        return _lib.UltraDelta(self.rows.data_ptr(), self.ptr.data_ptr(), self.col.data_ptr(), self.type.data_ptr(),
+                               self.count.data_ptr(), self.rows.numel(), self.col.numel())
+
+    def removed_operand(self):
+        """The delta's tombstone keys under this layout's row ranges (ultra_tombstones): the key arrays are the delta's own."""
+        if self.delta is None:
+            return _lib.UltraTombstones(self.dead_ptr.data_ptr(), self._no_keys.data_ptr(), self._no_keys.data_ptr(), 0)
+        return _lib.UltraTombstones(self.dead_ptr.data_ptr(), self.delta.dead_col.data_ptr(), self.delta.dead_type.data_ptr(),
+                                    self.delta.dead_col.numel())
+
+    def _no_shared_list(self, *args, **kwargs):
+        raise RuntimeError("an overlay of assumed facts has one edge list per sample, no shared one: the per-query loop "
+                           "(predict.assume_reference) serves what the engine route does not")
+
+    edges = surviving = materialize = _no_shared_list
 
 
 # ---- plan cache: the graph is static across the 12 rspmm calls of a forward and across batches ----
