@@ -435,6 +435,19 @@ typedef struct {
 int32_t ultra_symbolic_traversal_edit_rows(const int64_t *row_ptr, const int32_t *csr_src, const int32_t *csr_type,
                                            int64_t num_node, const ultra_traversal_edits *edits, const int64_t *r_index,
                                            int64_t batch, int32_t dtype, const void *h, void *t, void *stream);
+/* ultra_symbolic_traversal_edit_rows_owned: the same launch over an overlay of facts ASSUMED per sample.
+ *   owner_dev     int32 [capacity_edges]     parallel to add_src_dev: -1 = the edge is live in every sample; s in [0, batch) = in
+ *                                            sample s only; any other value = nowhere.  Only compared, never used as an index.
+ * Sample b's row is max(0, its live base edges, the added edges whose owner is -1 or b).  The dead keys apply to base edges only:
+ * a retracted base fact that one sample assumes again is live for that sample.  EARLY-OUT, a contract: a (touched tail, sample)
+ * pair is NOT written where the tail holds no dead key of relation r_index[b] and the relation's added range holds no edge live
+ * for b -- the output of ultra_symbolic_traversal stands there.  The wave decides it from one strided pass over the added range,
+ * before it reads the base segment.  Everything else -- the launch shape, the device-side count, the clamps, NULL dead_ptr_dev,
+ * the argument checks -- is ultra_symbolic_traversal_edit_rows'; a NULL owner_dev is ULTRA_ERR_INVALID. */
+int32_t ultra_symbolic_traversal_edit_rows_owned(const int64_t *row_ptr, const int32_t *csr_src, const int32_t *csr_type,
+                                                 int64_t num_node, const ultra_traversal_edits *edits, const int32_t *owner_dev,
+                                                 const int64_t *r_index, int64_t batch, int32_t dtype, const void *h, void *t,
+                                                 void *stream);
 
 /* ---- training UltraQuery ----
  * ultra_symbolic_traversal_keep: ultra_symbolic_traversal on the graph without its dropped edges; keep_slot (num_edge) fp32 in

@@ -3,7 +3,7 @@
     python tools/query_predict.py --data-root DIR [--ckpt FILE] --query "(('e1', ('r1',)), ('e2', ('r2', -2)))" [-k 10]
                                   [--logic product] [--unfiltered] [--above P] [--add-fact H R T]... [--remove-fact H R T]...
                                   [--entity-capacity M] [--add-entity NAME]... [--remove-entity NAME]...
-                                  [--among NAME [NAME ...]] [--among-file FILE]
+                                  [--among NAME [NAME ...]] [--among-file FILE] [--assume H R T]...
 
 DIR holds train.txt / valid.txt / test.txt (`head relation tail` per line) and optionally entities.dict / relations.dict
 (ultra_amd.data.load_triples_dir).  The query is a BetaE nested tuple (ultra_amd.ultraquery.Query.from_nested): a pair
@@ -35,6 +35,10 @@ in the query.
 --among NAME [NAME ...] and --among-file FILE (entity names, one per line; both may be given, the set is their union) restrict
 the candidates to a set (QueryPredictor.answers(among=)): only these entities are ranked, or listed by --above.
 An unknown name is an error that names it; a name introduced by --add-entity may be listed, a retired entity is simply absent.
+
+--assume H R T (repeatable) answers the query as if the fact were true WITHOUT stating it (QueryPredictor.answers(assuming=),
+DESIGN.md 33): the query's projections traverse it and the answers it entails are left out, while the graph served and its
+edits stay what they were.  The names are those known after every edit option; R is a relation of the dataset (not an inverse).
 """
 import argparse
 import ast
@@ -106,6 +110,8 @@ def main(argv=None):
                     help="retire an entity and retract its facts before the query; repeatable, applied in order with the other edits")
     ap.add_argument("--entity-capacity", type=int, default=None, metavar="M",
                     help="rows reserved for new entities (default: the number of --add-entity options)")
+    ap.add_argument("--assume", nargs=3, action="append", default=[], metavar=("H", "R", "T"),
+                    help="answer as if the fact (H, R, T) were true, without stating it; repeatable")
     ap.add_argument("--among", nargs="+", metavar="NAME", help="rank only these entities (a shortlist, a type)")
     ap.add_argument("--among-file", metavar="FILE", help="... the entity names of FILE, one per line")
     ap.set_defaults(edits=[])
@@ -144,6 +150,7 @@ def main(argv=None):
     if len(ent) > num_known and not reserve:
         sys.exit("--add-entity needs --entity-capacity above 0")
     nested = resolve(ast.literal_eval(args.query), ent, rel, gone)
+    assumed = [lookup_fact(fact, ent, rel, gone) for fact in args.assume]       # (the names known after every edit)
     among = {}
     if args.among or args.among_file:
         from ultra_amd.candidates import named_ids
@@ -162,7 +169,8 @@ def main(argv=None):
     else:
         print("no --ckpt: randomly initialised weights, the answers mean nothing")
     model = model.to(dev).eval()
-    qp = query_predict.QueryPredictor(model, data, k=args.k, batch_size=1, filtered=not args.unfiltered, entity_capacity=reserve)
+    qp = query_predict.QueryPredictor(model, data, k=args.k, batch_size=1, filtered=not args.unfiltered, entity_capacity=reserve,
+                                      assume_capacity=max(8, len(assumed)))
     at = 0
     while at < len(edits):        # (runs of one kind go in one call)
         if edits[at][0] is None:
@@ -197,6 +205,18 @@ def main(argv=None):
     print(ultraquery.Query.from_nested(nested).to_readable())
     if among:
         print("candidates: the %d listed entities" % len(set(among["among"])))
+    if assumed:
+        among["assuming"] = torch.tensor(assumed, dtype=torch.long, device=dev)
+        print("assuming %d fact(s) for this query only: nothing is stated" % len(assumed))
+    try:
+        return show(args, qp, nested, among, ent)
+    except ValueError as exc:
+        if not assumed:
+            raise
+        sys.exit(str(exc))      # (an assumed fact the predictor refuses: an inverse relation, a retired entity)
+
+
+def show(args, qp, nested, among, ent):
     if args.above is not None:
         ptr, ids, scores, size = qp.answer_sets([nested], probability=args.above, **among)
         print("%d answers with probability above %g%s; predicted size of the set %d"

@@ -222,6 +222,8 @@ def _load():
     lib.ultra_symbolic_traversal.argtypes = [vp, vp, vp, i64, vp, i64, i32, vp, vp, vp]
     lib.ultra_symbolic_traversal_edit_rows.argtypes = [vp, vp, vp, i64, ctypes.POINTER(UltraTraversalEdits), vp, i64, i32, vp,
                                                        vp, vp]
+    lib.ultra_symbolic_traversal_edit_rows_owned.argtypes = [vp, vp, vp, i64, ctypes.POINTER(UltraTraversalEdits), vp, vp, i64, i32,
+                                                             vp, vp, vp]
     lib.ultra_answer_ranking.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp]
     lib.ultra_strict_negatives.argtypes = [vp, i64, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp]
     lib.ultra_ranking_loss.argtypes = [vp, i64, i64, ctypes.c_float, ctypes.c_float, vp, vp, vp]

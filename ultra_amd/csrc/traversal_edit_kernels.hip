@@ -19,6 +19,14 @@
 // so a launch recorded into a hipGraph serves whatever the buffers hold at replay.  No atomics, no allocation, no memset, no host
 // synchronisation.  Every ptr value is clamped to its capacity, a key is only compared, a touched tail outside [0, num_node) is
 // not written and a source outside [0, num_node) is never dereferenced.
+//
+// Facts ASSUMED per query: ultra_symbolic_traversal_edit_rows_owned, the template flag OWNED.  An int32
+// owner per added edge names the one sample that sees it (-1: every sample; any other value outside [0, batch): none); an owner is
+// only compared.  The dead keys still apply to base edges only, so a retracted base fact that one sample assumes again is live
+// for that sample.  The added range is scanned FIRST, one strided pass that takes the edges live for b and notes whether there
+// was one; a (tail, sample) wave with no dead key of its relation and no live added edge ends there, before the base segment is
+// read, and writes nothing -- the base launch already wrote the right bits.  A hub tail touched by one query's hypothesis is so
+// scanned by one wave, not by `batch` waves.  Without the flag nothing changes: every touched pair is written.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -56,13 +64,13 @@ __device__ __forceinline__ int32_t clamp_ptr(int32_t p, int32_t lo, long long ca
     return p < lo ? lo : (p > cap ? cap : p);
 }
 
-template <typename T>
+template <typename T, bool OWNED = false>
 __global__ void __launch_bounds__(TRAVERSAL_EDIT_THREADS) symbolic_traversal_edit_rows_kernel(
     const int64_t *__restrict__ row_ptr, const int32_t *__restrict__ csr_src, const int32_t *__restrict__ csr_type,
     long long num_node, const int32_t *__restrict__ rows, const int32_t *__restrict__ count,
     const int32_t *__restrict__ add_ptr, const int32_t *__restrict__ add_src, const int32_t *__restrict__ add_type,
-    const int32_t *__restrict__ dead_ptr, const int32_t *__restrict__ dead_src, const int32_t *__restrict__ dead_type,
-    long long capacity_rows, long long capacity_edges, long long capacity_keys, const int64_t *__restrict__ r_index,
+    const int32_t *__restrict__ owner, const int32_t *__restrict__ dead_ptr, const int32_t *__restrict__ dead_src,
+    const int32_t *__restrict__ dead_type, long long capacity_rows, long long capacity_edges, long long capacity_keys, const int64_t *__restrict__ r_index,
     const T *__restrict__ h, T *__restrict__ t) {
     // (wave-uniform by construction: the searches below run once per wave)
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -86,6 +94,27 @@ __global__ void __launch_bounds__(TRAVERSAL_EDIT_THREADS) symbolic_traversal_edi
     }
 
     T best = T(0);      // max(0, ...), as in the base kernel
+    // added edges of relation r into v
+    const int32_t a0 = clamp_ptr(add_ptr[slot], 0, capacity_edges);
+    const int32_t a1 = clamp_ptr(add_ptr[slot + 1], a0, capacity_edges);
+    int32_t alo, ahi;
+    type_range<int32_t>(add_type, a0, a1, r, alo, ahi);
+    if constexpr (OWNED) {
+        // ... those live for sample b: this pass comes first, it decides whether the wave has anything to write
+        bool mine = false;
+        for (int32_t s = alo + lane; s < ahi; s += 64) {
+            const int32_t o = owner[s];
+            if (o == -1 || o == (int32_t)b) {
+                mine = true;
+                const int32_t u = add_src[s];
+                if (u >= 0 && u < num_node) {
+                    const T x = hb[u];
+                    best = x > best ? x : best;
+                }
+            }
+        }
+        if (klo == khi && __ballot(mine) == 0) return;      // (wave-uniform) the base launch's bits stand
+    }
     // live base edges of relation r into v
     long long lo, hi;
     type_range<long long>(csr_type, row_ptr[v], row_ptr[v + 1], r, lo, hi);
@@ -102,16 +131,13 @@ __global__ void __launch_bounds__(TRAVERSAL_EDIT_THREADS) symbolic_traversal_edi
             best = x > best ? x : best;
         }
     }
-    // added edges of relation r into v
-    const int32_t a0 = clamp_ptr(add_ptr[slot], 0, capacity_edges);
-    const int32_t a1 = clamp_ptr(add_ptr[slot + 1], a0, capacity_edges);
-    int32_t alo, ahi;
-    type_range<int32_t>(add_type, a0, a1, r, alo, ahi);
-    for (int32_t s = alo + lane; s < ahi; s += 64) {
-        const int32_t u = add_src[s];
-        if (u >= 0 && u < num_node) {
-            const T x = hb[u];
-            best = x > best ? x : best;
+    if constexpr (!OWNED) {
+        for (int32_t s = alo + lane; s < ahi; s += 64) {
+            const int32_t u = add_src[s];
+            if (u >= 0 && u < num_node) {
+                const T x = hb[u];
+                best = x > best ? x : best;
+            }
         }
     }
     for (int off = 32; off > 0; off >>= 1) {
@@ -123,51 +149,76 @@ __global__ void __launch_bounds__(TRAVERSAL_EDIT_THREADS) symbolic_traversal_edi
 
 }  // namespace ultra
 
-extern "C" int32_t ultra_symbolic_traversal_edit_rows(const int64_t *row_ptr, const int32_t *csr_src, const int32_t *csr_type,
-                                                      int64_t num_node, const ultra_traversal_edits *edits,
-                                                      const int64_t *r_index, int64_t batch, int32_t dtype, const void *h,
-                                                      void *t, void *stream) {
+namespace ultra {
+
+// Both entries: `name` prefixes the messages; owner_dev non-NULL selects the OWNED instantiation.
+static int32_t traversal_edit_rows(const char *name, const int64_t *row_ptr, const int32_t *csr_src, const int32_t *csr_type,
+                                   int64_t num_node, const ultra_traversal_edits *edits, const int32_t *owner_dev, bool owned,
+                                   const int64_t *r_index, int64_t batch, int32_t dtype, const void *h, void *t, void *stream) {
     // (every argument is judged before the first GPU call)
+    const std::string who(name);
     if (!row_ptr || !csr_src || !csr_type || !edits || !r_index || !h || !t || num_node <= 0 || num_node >= (1LL << 31) ||
         batch < 0 || batch > 65535) {
-        ultra::set_error("ultra_symbolic_traversal_edit_rows: NULL operand or batch / num_node out of range");
+        set_error(who + ": NULL operand or batch / num_node out of range");
+        return ULTRA_ERR_INVALID;
+    }
+    if (owned && !owner_dev) {
+        set_error(who + ": owner_dev is NULL (one int32 owner per added edge)");
         return ULTRA_ERR_INVALID;
     }
     if (dtype != 0 && dtype != 1) {
-        ultra::set_error("ultra_symbolic_traversal_edit_rows: dtype must be fp32 (0) or fp64 (1)");
+        set_error(who + ": dtype must be fp32 (0) or fp64 (1)");
         return ULTRA_ERR_INVALID;
     }
     if (edits->capacity_rows < 0 || edits->capacity_edges < 0 || edits->capacity_keys < 0 ||
-        edits->capacity_rows >= (1LL << 31) - ultra::TRAVERSAL_EDIT_WAVES) {
-        ultra::set_error("ultra_symbolic_traversal_edit_rows: capacities out of range");
+        edits->capacity_rows >= (1LL << 31) - TRAVERSAL_EDIT_WAVES) {
+        set_error(who + ": capacities out of range");
         return ULTRA_ERR_INVALID;
     }
     if (!edits->row_dev || !edits->count_dev || !edits->add_ptr_dev || !edits->add_src_dev || !edits->add_type_dev ||
         (edits->dead_ptr_dev && (!edits->dead_src_dev || !edits->dead_type_dev))) {
-        ultra::set_error("ultra_symbolic_traversal_edit_rows: NULL array in the edits (only dead_ptr_dev may be NULL)");
+        set_error(who + ": NULL array in the edits (only dead_ptr_dev may be NULL)");
         return ULTRA_ERR_INVALID;
     }
     if (edits->capacity_rows == 0 || batch == 0) return ULTRA_OK;
     ULTRA_DEVICE_SCOPE(stream, h);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)((edits->capacity_rows + ultra::TRAVERSAL_EDIT_WAVES - 1) / ultra::TRAVERSAL_EDIT_WAVES),
-                    (unsigned)batch);
+    const dim3 grid((unsigned)((edits->capacity_rows + TRAVERSAL_EDIT_WAVES - 1) / TRAVERSAL_EDIT_WAVES), (unsigned)batch);
     (void)hipGetLastError();
-    if (dtype == 0)
-        hipLaunchKernelGGL(ultra::symbolic_traversal_edit_rows_kernel<float>, grid, dim3(ultra::TRAVERSAL_EDIT_THREADS), 0, s,
-                           row_ptr, csr_src, csr_type, (long long)num_node, edits->row_dev, edits->count_dev, edits->add_ptr_dev,
-                           edits->add_src_dev, edits->add_type_dev, edits->dead_ptr_dev, edits->dead_src_dev,
-                           edits->dead_type_dev, (long long)edits->capacity_rows, (long long)edits->capacity_edges,
-                           (long long)edits->capacity_keys, r_index, (const float *)h, (float *)t);
-    else
-        hipLaunchKernelGGL(ultra::symbolic_traversal_edit_rows_kernel<double>, grid, dim3(ultra::TRAVERSAL_EDIT_THREADS), 0, s,
-                           row_ptr, csr_src, csr_type, (long long)num_node, edits->row_dev, edits->count_dev, edits->add_ptr_dev,
-                           edits->add_src_dev, edits->add_type_dev, edits->dead_ptr_dev, edits->dead_src_dev,
-                           edits->dead_type_dev, (long long)edits->capacity_rows, (long long)edits->capacity_edges,
-                           (long long)edits->capacity_keys, r_index, (const double *)h, (double *)t);
+#define ULTRA_TRAVERSAL_EDIT_LAUNCH(T, OWNED)                                                                                   \
+    hipLaunchKernelGGL((symbolic_traversal_edit_rows_kernel<T, OWNED>), grid, dim3(TRAVERSAL_EDIT_THREADS), 0, s, row_ptr,     \
+                       csr_src, csr_type, (long long)num_node, edits->row_dev, edits->count_dev, edits->add_ptr_dev,            \
+                       edits->add_src_dev, edits->add_type_dev, owner_dev, edits->dead_ptr_dev, edits->dead_src_dev,            \
+                       edits->dead_type_dev, (long long)edits->capacity_rows, (long long)edits->capacity_edges,                 \
+                       (long long)edits->capacity_keys, r_index, (const T *)h, (T *)t)
+    if (owned) {
+        if (dtype == 0) ULTRA_TRAVERSAL_EDIT_LAUNCH(float, true); else ULTRA_TRAVERSAL_EDIT_LAUNCH(double, true);
+    } else {
+        if (dtype == 0) ULTRA_TRAVERSAL_EDIT_LAUNCH(float, false); else ULTRA_TRAVERSAL_EDIT_LAUNCH(double, false);
+    }
+#undef ULTRA_TRAVERSAL_EDIT_LAUNCH
     if (hipGetLastError() != hipSuccess) {
-        ultra::set_error("symbolic_traversal_edit_rows_kernel launch failed");
+        set_error("symbolic_traversal_edit_rows_kernel launch failed");
         return ULTRA_ERR_HIP;
     }
     return ULTRA_OK;
+}
+
+}  // namespace ultra
+
+extern "C" int32_t ultra_symbolic_traversal_edit_rows(const int64_t *row_ptr, const int32_t *csr_src, const int32_t *csr_type,
+                                                      int64_t num_node, const ultra_traversal_edits *edits,
+                                                      const int64_t *r_index, int64_t batch, int32_t dtype, const void *h,
+                                                      void *t, void *stream) {
+    return ultra::traversal_edit_rows("ultra_symbolic_traversal_edit_rows", row_ptr, csr_src, csr_type, num_node, edits, nullptr,
+                                      false, r_index, batch, dtype, h, t, stream);
+}
+
+extern "C" int32_t ultra_symbolic_traversal_edit_rows_owned(const int64_t *row_ptr, const int32_t *csr_src,
+                                                            const int32_t *csr_type, int64_t num_node,
+                                                            const ultra_traversal_edits *edits, const int32_t *owner_dev,
+                                                            const int64_t *r_index, int64_t batch, int32_t dtype, const void *h,
+                                                            void *t, void *stream) {
+    return ultra::traversal_edit_rows("ultra_symbolic_traversal_edit_rows_owned", row_ptr, csr_src, csr_type, num_node, edits,
+                                      owner_dev, true, r_index, batch, dtype, h, t, stream);
 }

@@ -981,6 +981,10 @@ class QueryNBFNet(EntityNBFNet):
                 hiddens, _ = self._propagate_layers(data, node_features, query, node_features, delta=delta,
                                                     relations=self._project_relations_batched())
             except _DeltaRouteUnsupported:
+                if getattr(delta, "per_query_owned", False):
+                    # (facts assumed per sample, rspmm.AssumedFacts: no shared materialised graph to fall back to)
+                    raise NotOnFusedPath("an overlay of assumed facts outside the engine route runs query by query "
+                                         "(query_predict.assume_reference's loop)")
                 return _materialized_forward(lambda graph: self.forward(graph, node_features, relation_representations, query),
                                              data, delta, query.is_cuda)
             if dense.readout_supported(self, hiddens[-1]):

@@ -29,7 +29,7 @@ from collections import namedtuple
 
 import torch
 
-from . import _lib, selection
+from . import _lib, models, selection
 from .ultraquery import Query, UltraQuery, _logic
 
 PUSH_ENTITY, AND, OR, NOT = 0, 1, 2, 3
@@ -407,11 +407,28 @@ def projections(model, graph, delta=None):
     return call(model.model), call(model.symbolic_model)
 
 
+def in_lockstep(program):
+    """Does every projection of `program` cover all samples in ascending order -- row j of every projection is sample j?  True for
+    a batch of queries of one structure (QueryPredictor._programs)."""
+    every = list(range(program.batch))
+    return all(list(p.samples) == every for p in program.projections)
+
+
 def execute(model, graph, query_or_program, symbolic_traversal=True, executor=None, delta=None):
     """(logits (batch, num_nodes), final symbolic sets or None): `UltraQuery.forward` and the top of its symbolic stack,
     through the compiled program.  A CPU graph or model runs `run_reference` on the model's own projections.  delta
-    (rspmm.GraphDelta of `graph`): the same on delta.materialize(graph) (`projections`)."""
+    (rspmm.GraphDelta of `graph`): the same on delta.materialize(graph) (`projections`).  delta an rspmm.AssumedFacts (DESIGN.md
+    33): sample j on the materialised graph plus the facts it assumes -- the overlay names a sample by its row, so the program
+    must be in lockstep (`in_lockstep`) and no larger than the overlay's batch_size, on the GPU; models.NotOnFusedPath otherwise
+    (the caller runs query_predict.assume_reference's loop)."""
     program = _as_program(query_or_program, graph)
+    if getattr(delta, "per_query_owned", False):
+        if not _on_gpu(model, graph):
+            raise models.NotOnFusedPath("an overlay of assumed facts is served on the GPU only")
+        if not in_lockstep(program) or program.batch > delta.batch_size:
+            raise models.NotOnFusedPath("an overlay of assumed facts names a sample by its row: every projection of the program "
+                                        "must cover all %d samples in ascending order, at most %d of them"
+                                        % (program.batch, delta.batch_size))
     if model.training:
         raise ValueError("the compiled executor serves eval mode only: training keeps UltraQuery.execute, whose traversal "
                          "dropout draws per projection")

@@ -29,16 +29,113 @@ CANDIDATE sets: `answers(queries, among=)` / `answer_sets(queri
 candidates to a set -- a name (`define_set`), one id vector for every query, or one name or vector per query, which follows its
 query through the grouping into batches.  The entailed lists stay the deny list; the selection gathers the listed logits
 (ultra_filtered_topk_among / ultra_filtered_above_among) with the live count and the retired set as its optional operands.
+
+WHAT-IF queries: `answers(queries, assuming=)` / `answer_sets(queries, probability, assuming=)` -- facts a query
+ASSUMES for itself (the rules of predict.Predictor.tails(assuming=), §32): query i runs, neural and symbolic projection alike, on
+materialized() plus its own direct and inverse edges, so what it entails through a hypothesis is left out for that query alone.
+Nothing is stated.  `assume_reference` is the definition.
 """
 import contextlib
 import functools
 
 import torch
 
-from . import predict, query_exec
+from . import models, predict, query_exec, rspmm
 from .candidates import CandidateSets, span_rows
 from .live import LiveGraph, forwarded
 from .ultraquery import Query, _logic
+
+
+def _postfix_rows(queries):
+    """One postfix row (a list ending with stop) per query."""
+    if isinstance(queries, torch.Tensor):
+        if queries.dim() != 2:
+            raise ValueError("postfix queries come as (n, L) rows, got %s" % (tuple(queries.shape),))
+        return queries.as_subclass(torch.Tensor).cpu().tolist()
+    return [Query.nested_to_postfix(q) + [Query.stop] if isinstance(q, tuple) else
+            torch.as_tensor(q).as_subclass(torch.Tensor).flatten().tolist() for q in queries]
+
+
+def postfix_batch(queries):
+    """`queries` (nested tuples, lists or rows) as one (n, L) int64 batch of postfix rows, padded with stop."""
+    rows = _postfix_rows(queries)
+    width = max(len(row) for row in rows)
+    return torch.tensor([row + [Query.stop] * (width - len(row)) for row in rows], dtype=torch.long)
+
+
+def _entailed(sym, num_live=None, retired=None):
+    """(ptr (rows + 1), ids) of the final symbolic sets `sym` in plain torch: per row the non-zero ids below num_live that are not
+    retired (after a negation a reserved or a retired slot holds 1.0)."""
+    if num_live is not None:
+        sym = sym[:, :int(num_live)]
+    listed = sym != 0
+    if retired is not None and len(retired):
+        retired = torch.as_tensor(retired, dtype=torch.long, device=sym.device).flatten()
+        listed[:, retired[retired < sym.shape[1]]] = False
+    sample, known = listed.nonzero().t()
+    return torch.searchsorted(sample.contiguous(), torch.arange(sym.shape[0] + 1, device=sym.device)), known
+
+
+def assume_supported(model):
+    """Does the engine route answer what-if logical queries for `model` (an UltraQuery): predict.assume_supported of the Ultra
+    its projection holds -- sum / max / min with TransE / DistMult?"""
+    return predict.assume_supported(getattr(getattr(model, "model", None), "model", None))
+
+
+@torch.no_grad()
+def assume_reference(model, graph, queries, assuming, k=10, filtered=True, logic=None, probability=None, num_live=None,
+                     retired=None, among=None):
+    """What-if logical queries in plain terms, on any device -- the DEFINITION QueryPredictor.answers / answer_sets (assuming=)
+    are tested against.  Query i is answered on a COPY of `graph` with its assumed facts appended -- [graph's edges ; its direct
+    edges (h, t, r) in the given order ; their inverse edges], duplicates kept, the relation graph kept as it is
+    (predict._assumed_graph) -- by query_exec.execute on a batch of that one query: both projections, the neural and the
+    symbolic one, run on the copy, so the entailed answers left out (filtered=True: the non-zero ids of the final symbolic set)
+    are those the copy entails.  No other query sees the facts; nothing is stated.  The selection is
+    predict.filtered_topk_reference, or with `probability` filtered_above_reference at logit_threshold(probability).
+    assuming: one (m, 3) tensor of (h, r, t) rows for every query, or a list with one entry per query (rows, None or empty), under
+    predict._assumed_lists' rules.  logic: overrides model.logic.  num_live, retired (a sorted id vector): the ids that exist --
+    for the anchors, the facts, the entailed lists and the selection.  among: one id vector for every query or a list of one per
+    query.  Returns (ids (n, k), scores (n, k), count (n)), or with probability (ptr (n + 1), ids, scores, size (n))."""
+    rows = _postfix_rows(queries)
+    dev = graph.edge_index.device
+    live = {} if num_live is None else {"num_live": int(num_live)}
+    if retired is not None:
+        retired = torch.as_tensor(retired, dtype=torch.long).flatten()
+    assumed = predict._assumed_lists(graph, assuming, len(rows), retired=retired, **live)
+    select = dict(live)
+    compile_kwargs = dict(live)
+    if retired is not None and len(retired):
+        select["retired"] = retired.to(dev)
+        compile_kwargs["retired"] = frozenset(retired.tolist())
+    threshold = None if probability is None else predict.logit_threshold(probability)
+    n, r = int(graph.num_nodes), int(graph.num_relations)
+    programs = [query_exec.compile(torch.tensor([row], dtype=torch.long), n, r, **compile_kwargs) for row in rows]
+    out = []
+    was = model.logic
+    with predict.eval_mode(model):
+        if logic is not None:
+            _logic(logic)
+            model.logic = logic
+        try:
+            for i, (program, facts) in enumerate(zip(programs, assumed)):
+                logits, sym = query_exec.execute(model, predict._assumed_graph(graph, facts), program, symbolic_traversal=filtered)
+                ptr = known = None
+                if filtered:
+                    ptr, known = _entailed(sym, num_live, select.get("retired"))
+                if among is not None:
+                    select["among"] = [among[i] if isinstance(among, (list, tuple)) else among]
+                if threshold is None:
+                    out.append(predict.filtered_topk_reference(logits, k, ptr, known, **select))
+                else:
+                    out.append(predict.filtered_above_reference(logits, threshold, ptr, known, **select))
+        finally:
+            model.logic = was
+    if threshold is not None:
+        return predict._join_above(out, dev)
+    if not out:
+        return (torch.zeros(0, k, dtype=torch.long, device=dev), torch.zeros(0, k, dtype=torch.float32, device=dev),
+                torch.zeros(0, dtype=torch.long, device=dev))
+    return tuple(torch.cat([part[j] for part in out]) for j in range(3))
 
 
 class QueryPredictor(object):
@@ -58,10 +155,18 @@ class QueryPredictor(object):
     `retired_entities` -- with the retired ids taken out of the candidates and of the entailed lists.  A retired slot of an
     intermediate fuzzy or symbolic set is left as the logic leaves it: nothing is zeroed on the way, so every score keeps the
     bits of the fresh predictor's.  Until the first retirement every call reaches exactly the entries it reached before.  (The
-    method is not called remove_entities: see DESIGN.md §29, "The name".)"""
+    method is not called remove_entities: see DESIGN.md §29, "The name".)
 
-    def __init__(self, model, graph, k=10, batch_size=16, filtered=True, logic=None, delta_capacity=256, entity_capacity=0):
+    assume_capacity: the facts one query may assume (`answers(assuming=)`)."""
+
+    def __init__(self, model, graph, k=10, batch_size=16, filtered=True, logic=None, delta_capacity=256, entity_capacity=0,
+                 assume_capacity=8):
         predict.check_k(k)
+        if isinstance(assume_capacity, bool) or not isinstance(assume_capacity, int) or assume_capacity < 1:
+            raise ValueError("assume_capacity must be a positive int (facts one query may assume), got %r" % (assume_capacity,))
+        self.assume_capacity = assume_capacity
+        self._assume_loop_only = False      # (an engine route that did not serve this predictor once is not tried again)
+        self._assume_overlay = None         # (graph, delta, overlay): the overlay of the what-if batches
         if int(batch_size) < 1:
             raise ValueError("batch_size must be positive, got %r" % (batch_size,))
         if logic is not None:
@@ -169,12 +274,7 @@ class QueryPredictor(object):
 
     def _rows(self, queries):
         """One postfix row (a list ending with stop) per query."""
-        if isinstance(queries, torch.Tensor):
-            if queries.dim() != 2:
-                raise ValueError("postfix queries come as (n, L) rows, got %s" % (tuple(queries.shape),))
-            return queries.as_subclass(torch.Tensor).cpu().tolist()
-        return [Query.nested_to_postfix(q) + [Query.stop] if isinstance(q, tuple) else
-                torch.as_tensor(q).as_subclass(torch.Tensor).flatten().tolist() for q in queries]
+        return _postfix_rows(queries)
 
     def _programs(self, queries):
         """[(indices, Program)] of the batches of `answers`.  With a reserve the programs are compiled against the slot count
@@ -205,20 +305,27 @@ class QueryPredictor(object):
         return [index for index, _ in self._programs(queries)]
 
     @contextlib.contextmanager
-    def _batches(self, plan, among=None):
+    def _batches(self, plan, among=None, assumed=None):
         """The batches of `plan` (_programs) as answers and answer_sets run them: inside the block the model is in eval mode
         under this predictor's logic (both restored on the way out), and the value is an iterator of (index, logits, ptr, known,
         live) -- the batch's query indices, its logits from the compiled executor, the lists of its entailed answers (None, None
         unless filtered) and the kwargs of the selection: the live count and, once an entity was retired, the retired set
         (LiveGraph.selection_for) -- the lists take the same two.  among (the call's assembled (span, index, longest), or None):
         the kwargs gain the batch's candidate lists -- the spans of its queries, through `index` -- in the form the selection
-        of that device takes."""
+        of that device takes.  assumed (_assumed's list, or None; the engine route of what-if queries): a batch
+        in which a query assumes facts runs with the overlay -- filled for that batch, a short one padded -- as its delta;
+        models.NotOnFusedPath where the engine does not serve it."""
         graph, live_graph, delta_kwargs = self.graph, self._live, self._delta_kwargs()
 
         def run():
             for index, program in plan:
+                kwargs = delta_kwargs
+                if assumed is not None and any(len(assumed[i]) for i in index):
+                    overlay = self._overlay()
+                    overlay.fill([assumed[i] for i in index] + [None] * (self.batch_size - len(index)))
+                    kwargs = {"delta": overlay}
                 logits, sym = query_exec.execute(self.model, graph, program, symbolic_traversal=self.filtered,
-                                                 executor=self._executor, **delta_kwargs)
+                                                 executor=self._executor, **kwargs)
                 live = live_graph.selection_for(logits.is_cuda)
                 ptr = known = None
                 if self.filtered:
@@ -241,28 +348,84 @@ class QueryPredictor(object):
             finally:
                 self.model.logic = logic
 
+    # ---- what-if queries ----
+    def _assumed(self, assuming, n):
+        """`assuming` of a call with n queries: None where nothing is assumed (the plain route), else predict._assumed_lists under
+        the rules of add_facts and the capacity."""
+        if assuming is None:
+            return None
+        assumed = predict._assumed_lists(self.graph, assuming, n, per_query=self.assume_capacity,
+                                         num_live=self.num_entities if self.entity_capacity else None,
+                                         retired=self.retired_entities if self.num_retired else None)
+        return assumed if any(len(facts) for facts in assumed) else None
+
+    def _assume_served(self):
+        """Does the engine route answer what-if queries here: a model in assume_supported, on the GPU, not refused before?"""
+        return not self._assume_loop_only and query_exec._on_gpu(self.model, self.graph) and assume_supported(self.model)
+
+    def _overlay(self):
+        """The overlay of this predictor's what-if batches: one per (served graph, delta object) -- the delta is made at the first
+        edit, so a never-edited predictor lays its overlay over no delta."""
+        graph, delta = self.graph, self.delta
+        hit = self._assume_overlay
+        if hit is None or hit[0] is not graph or hit[1] is not delta:
+            hit = self._assume_overlay = (graph, delta, rspmm.AssumedFacts(graph, delta, self.batch_size, self.assume_capacity))
+        return hit[2]
+
+    def _assume_loop(self, queries, assumed, among, probability=None):
+        """The call query by query on copies of materialized() (assume_reference): exact and slow -- a model, a device or a
+        program the engine route does not serve."""
+        retired = self.retired_entities if self.num_retired else None
+        if among is not None:
+            among = span_rows(among[0], among[1])
+        return assume_reference(self.model, self.materialized(), queries, assumed, k=self.k, filtered=self.filtered,
+                                logic=self.logic, probability=probability, retired=retired, among=among)
+
+    def _what_if(self, run, queries, assumed, among, probability=None):
+        """`run(assumed)` -- the batches of the call, with the overlay where a query assumes facts -- where the engine serves the
+        call, else (remembered per predictor) _assume_loop."""
+        if assumed is None:
+            return run(None)
+        if self._assume_served():
+            try:
+                return run(assumed)
+            except models.NotOnFusedPath:       # (a plan, a shape or a program the owned entries do not serve)
+                self._assume_loop_only = True
+        return self._assume_loop(queries, assumed, among, probability)
+
     @torch.no_grad()
-    def answers(self, queries, among=None):
+    def answers(self, queries, among=None, assuming=None):
         """among (None: every entity): a candidate set per query -- a name, one id vector for all, or one name or vector per
-        query, in input order (CandidateSets.resolve) -- count[i] = min(k, its ids that are live, alive and not entailed)."""
+        query, in input order (CandidateSets.resolve) -- count[i] = min(k, its ids that are live, alive and not entailed).
+        assuming (None: nothing): facts the queries assume -- one (m, 3) int64 tensor of (h, r, t) rows for every
+        query, or a list with one entry per query in input order (rows, None or empty), which follows its query through the
+        grouping into batches; the rules of add_facts, at most assume_capacity a query (ValueError, before anything runs).
+        Query i is answered on materialized() plus its own direct and inverse edges, the served relation graph kept: both
+        projections see them, so an answer the hypothesis entails is left out (filtered=True) for that query alone.  Nothing is
+        stated.  Every answer equals assume_reference's.  A call whose assumptions are all empty is the call without them."""
         dev = self.graph.edge_index.device
         plan = self._programs(queries)
         n, k = sum(len(index) for index, _ in plan), self.k
+        assumed = self._assumed(assuming, n)
         if among is not None:
             among = self._sets.assemble(among, n, dev)
-        ids = torch.empty(n, k, dtype=torch.long, device=dev)
-        scores = torch.empty(n, k, dtype=torch.float32, device=dev)
-        count = torch.empty(n, dtype=torch.long, device=dev)
-        with self._batches(plan, among) as batches:
-            for index, logits, ptr, known, live in batches:
-                select = predict.filtered_topk if logits.is_cuda else predict.filtered_topk_reference
-                got = select(logits, k, ptr, known, **live)
-                where = torch.tensor(index, dtype=torch.long).to(dev, non_blocking=True)
-                ids[where], scores[where], count[where] = got
-        return ids, scores, count
+
+        def run(assumed):
+            ids = torch.empty(n, k, dtype=torch.long, device=dev)
+            scores = torch.empty(n, k, dtype=torch.float32, device=dev)
+            count = torch.empty(n, dtype=torch.long, device=dev)
+            with self._batches(plan, among, assumed) as batches:
+                for index, logits, ptr, known, live in batches:
+                    select = predict.filtered_topk if logits.is_cuda else predict.filtered_topk_reference
+                    got = select(logits, k, ptr, known, **live)
+                    where = torch.tensor(index, dtype=torch.long).to(dev, non_blocking=True)
+                    ids[where], scores[where], count[where] = got
+            return ids, scores, count
+
+        return self._what_if(run, queries, assumed, among)
 
     @torch.no_grad()
-    def answer_sets(self, queries, probability=0.5, among=None):
+    def answer_sets(self, queries, probability=0.5, among=None, assuming=None):
         """The answer SET of every query, ranked: (ptr (n + 1) int64, ids, scores, size (n) int64) in INPUT order -- the set of
         query i is ids[ptr[i] : ptr[i + 1]], best first.  An entity belongs to the set iff its logit exceeds
         predict.logit_threshold(probability) (predict.filtered_above_reference: the rule is on the logit, so a positive logit
@@ -271,17 +434,23 @@ class QueryPredictor(object):
         the entailed answers are left out of the lists exactly as in `answers`.  The batches are those of `answers`, through
         the same executor call; ultra_filtered_above selects on the device and the host reads one number per batch (the
         batch's total) to slice the batch's lists.  among: as in `answers` -- only the set's ids can be members, in the lists
-        and in size."""
+        and in size.  assuming: as in `answers` -- the sets of the what-if queries, assume_reference(probability=)'s."""
         threshold = predict.logit_threshold(probability)
         dev = self.graph.edge_index.device
         plan = self._programs(queries)
         n = sum(len(index) for index, _ in plan)
+        assumed = self._assumed(assuming, n)
         if among is not None:
             among = self._sets.assemble(among, n, dev)
+        return self._what_if(lambda assumed: self._answer_sets(plan, n, threshold, among, assumed), queries, assumed, among,
+                             probability)
+
+    def _answer_sets(self, plan, n, threshold, among, assumed):
+        dev = self.graph.edge_index.device
         length = torch.zeros(n, dtype=torch.long, device=dev)
         size = torch.zeros(n, dtype=torch.long, device=dev)
         done = []
-        with self._batches(plan, among) as batches:
+        with self._batches(plan, among, assumed) as batches:
             for index, logits, ptr, known, live in batches:
                 if logits.is_cuda:
                     b_ptr, b_ids, b_scores, b_size = predict.filtered_above(logits, threshold, ptr, known, **live)

@@ -789,6 +789,7 @@ def dense_layer0_adjacency(adjacency, num_node, relation, src_rows, src_values, 
 
 
 TraversalLayout = namedtuple("TraversalLayout", "rows count add_ptr add_src add_type dead_ptr dead_src dead_type")
+OwnedTraversalLayout = namedtuple("OwnedTraversalLayout", "rows count add_ptr add_src add_type owner dead_ptr")
 ExplainLayout = namedtuple("ExplainLayout", "rows count add_ptr add_src add_dst add_type add_j dead_ptr dead_src dead_type "
                                             "src_rows src_count src_ptr src_dst src_type src_j")
 
@@ -1381,6 +1382,8 @@ class AssumedFacts(object):
         self._no_keys = torch.zeros(1, dtype=torch.int32, device=dev)
         self.num_edges = 0
         self._shared_cache = None       # (delta.version, _shared()'s parts)
+        self.traversal = None           # the layout in the symbolic traversal's direction: laid out when first asked for
+        self._filled = None             # (src, dst, type, owner) of the last fill, in insertion order
         self.fill([None] * batch_size)
 
     edited = True       # (handed to a model it always takes the delta route: an empty overlay is a launch that ends at once)
@@ -1414,18 +1417,20 @@ class AssumedFacts(object):
         return out
 
     def _shared(self):
-        """(edge_index, edge_type, key_row) of the delta as it is now: its edges in materialised order and the rows of its
-        tombstone keys, built once per delta.version -- a refill between two replays does not walk the host list of keys again."""
+        """(edge_index, edge_type, key_row, key_tail) of the delta as it is now: its edges in materialised order and the rows
+        (edge_index[0]) and the tails (edge_index[1]) of its tombstone keys, built once per delta.version -- a refill between two
+        replays does not walk the host list of keys again."""
         version = None if self.delta is None else self.delta.version
         hit = self._shared_cache
         if hit is None or hit[0] != version:
             dev = self.device
             if self.delta is None:
-                parts = (torch.zeros(2, 0, dtype=torch.long, device=dev), torch.zeros(0, dtype=torch.long, device=dev),
-                         torch.zeros(0, dtype=torch.long, device=dev))
+                parts = (torch.zeros(2, 0, dtype=torch.long, device=dev),) + tuple(
+                    torch.zeros(0, dtype=torch.long, device=dev) for _ in range(3))
             else:
                 keys = torch.tensor(self.delta.dead_keys, dtype=torch.long, device=dev)
-                parts = self.delta.edges() + (keys // (self.num_relations * self.num_nodes),)
+                parts = self.delta.edges() + (keys // (self.num_relations * self.num_nodes),
+                                              (keys // self.num_relations) % self.num_nodes)
             hit = self._shared_cache = (version, parts)
         return hit[1]
 
@@ -1435,7 +1440,7 @@ class AssumedFacts(object):
         assumed = self.check(assumed)
         dev, n, half = self.device, self.num_nodes, self.num_relations // 2
         rows, cols, kinds, owners = [], [], [], []
-        shared_index, shared_type, key_row = self._shared()
+        shared_index, shared_type, key_row, _ = self._shared()
         if len(shared_type):
             rows.append(shared_index[0]), cols.append(shared_index[1]), kinds.append(shared_type)
             owners.append(torch.full_like(shared_type, -1))
@@ -1447,6 +1452,7 @@ class AssumedFacts(object):
         empty = torch.zeros(0, dtype=torch.long, device=dev)
         row, col, kind, owner = (torch.cat(v) if v else empty for v in (rows, cols, kinds, owners))
         num_edge = len(row)
+        self._filled = (row, col, kind, owner)
         order = torch.argsort((row * n + col) * max(num_edge, 1) + torch.arange(num_edge, device=dev))
         row, col, kind, owner = row[order], col[order], kind[order], owner[order]
         touched = torch.unique(torch.cat([row, key_row]))      # (ascending; its length is the refill's one host read)
@@ -1460,7 +1466,65 @@ class AssumedFacts(object):
             ptr[1:num_touched + 1] = counts.cumsum(0).to(torch.int32)
         self.count.fill_(num_touched)
         self.num_edges = num_edge
+        if self.traversal is not None:
+            self._prepare_traversal()
         return num_edge
+
+    def _prepare_traversal(self):
+        """The last fill keyed by the TAIL an edge points into, as GraphDelta._prepare_traversal lays a delta out,
+        into buffers allocated at the first call and rewritten in place by every later fill():
+          rows       int32 (2 F)       the distinct tails an edge of the overlay or a dead key of the delta points into, ascending
+          count      int32 (1)         their number -- the same tensor for the overlay's life
+          add_ptr    int32 (2 F + 1)   the edges' ranges per touched tail
+          add_src / add_type / owner   int32 (2 F)   the edges (source, relation, owner: -1 the delta's, i query i's), sorted by
+                                       (tail, relation, source) -- a stable sort: equal edges stay in insertion order
+          dead_ptr   int32 (2 F + 1)   the delta's dead keys' ranges per touched tail OF THIS LAYOUT; the keys themselves are the
+                                       delta's own traversal arrays (dead_src / dead_type, sorted by tail first)"""
+        dev, cap = self.device, 2 * self.capacity
+        if self.traversal is None:
+            buf = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
+            self.traversal = OwnedTraversalLayout(rows=buf(cap), count=buf(1), add_ptr=buf(cap + 1), add_src=buf(cap),
+                                                  add_type=buf(cap), owner=buf(cap), dead_ptr=buf(cap + 1))
+        lay = self.traversal
+        if self.delta is not None and self.delta.traversal is None:
+            self.delta._prepare_traversal()      # (its dead_src / dead_type: kept current by the delta from here on)
+        src, dst, kind, owner = self._filled
+        key_dst = self._shared()[3]
+        order = torch.sort((dst * self.num_relations + kind) * self.num_nodes + src, stable=True).indices
+        src, dst, kind, owner = src[order], dst[order], kind[order], owner[order]
+        touched = torch.unique(torch.cat([dst, key_dst]))      # (ascending)
+        num_touched, num_edge = len(touched), len(src)
+        lay.add_src[:num_edge] = src.to(torch.int32)
+        lay.add_type[:num_edge] = kind.to(torch.int32)
+        lay.owner[:num_edge] = owner.to(torch.int32)
+        lay.rows[:num_touched] = touched.to(torch.int32)
+        for ptr, of in ((lay.add_ptr, dst), (lay.dead_ptr, key_dst)):
+            counts = torch.bincount(torch.searchsorted(touched, of), minlength=num_touched)
+            ptr[1:num_touched + 1] = counts.cumsum(0).to(torch.int32)
+        lay.count.fill_(num_touched)
+
+    def traversal_operand(self):
+        """The overlay in the traversal's direction as the engine takes it (ultra_traversal_edits), beside `traversal_owner`;
+        valid while this object lives.  The first call lays the buffers out; from then on fill() keeps them current.  Without a
+        delta the dead arrays are NULL: no tombstones."""
+        if self.traversal is None:
+            self._prepare_traversal()
+        lay = self.traversal
+        if self.delta is None:
+            dead = (None, None, None, 0)
+        else:
+            keys = self.delta.traversal
+            dead = (lay.dead_ptr.data_ptr(), keys.dead_src.data_ptr(), keys.dead_type.data_ptr(), keys.dead_src.numel())
+        return _lib.UltraTraversalEdits(lay.rows.data_ptr(), lay.count.data_ptr(), lay.add_ptr.data_ptr(), lay.add_src.data_ptr(),
+                                        lay.add_type.data_ptr(), dead[0], dead[1], dead[2], lay.rows.numel(),
+                                        lay.add_src.numel(), dead[3])
+
+    @property
+    def traversal_owner(self):
+        """int32 (2 F): the owner of every edge of the traversal layout, parallel to its add_src (laid out when first asked for)."""
+        if self.traversal is None:
+            self._prepare_traversal()
+        return self.traversal.owner
 
     def operand(self):
         """The overlay's rows and edges as the engine takes a delta (ultra_delta); valid while this object lives."""

@@ -440,7 +440,9 @@ def symbolic_traversal(edge_index, edge_type, num_node, h_prob, r_index, edge_ke
     edge_keep (num_edge, 0/1) over the edges whose keep is not 0 only (ultra_symbolic_traversal_keep).  delta (an edited
     rspmm.GraphDelta whose base graph the edge list is; not with edge_keep): the traversal of delta.materialize(...) -- the base
     launch on the cached CSR of the base graph, then one launch that recomputes the tails an added or a removed edge points
-    into (ultra_symbolic_traversal_edit_rows).  The same bits: a max has no order."""
+    into (ultra_symbolic_traversal_edit_rows).  The same bits: a max has no order.  delta an rspmm.AssumedFacts
+    (`per_query_owned`): row b is the traversal of the materialised graph plus the facts sample b assumes
+    (ultra_symbolic_traversal_edit_rows_owned) -- row b is sample b, at most the overlay's batch_size rows."""
     if delta is not None and not delta.edited:
         delta = None
     if delta is not None:
@@ -449,6 +451,9 @@ def symbolic_traversal(edge_index, edge_type, num_node, h_prob, r_index, edge_ke
         if delta.num_nodes != int(num_node) or delta.device != edge_index.device:
             raise ValueError("the delta was made for a graph of %d nodes on %s, the traversal runs over %d nodes on %s"
                              % (delta.num_nodes, delta.device, num_node, edge_index.device))
+        if getattr(delta, "per_query_owned", False) and h_prob.shape[0] > delta.batch_size:
+            raise ValueError("the overlay of assumed facts was laid out for %d samples, the traversal has %d rows"
+                             % (delta.batch_size, h_prob.shape[0]))
     if h_prob.dtype not in (torch.float32, torch.float64):
         raise TypeError("the symbolic traversal takes fp32 or fp64 fuzzy sets, got %s" % h_prob.dtype)
     if h_prob.dim() != 2 or h_prob.shape[1] != num_node or r_index.shape != (h_prob.shape[0],):
@@ -471,7 +476,14 @@ def symbolic_traversal(edge_index, edge_type, num_node, h_prob, r_index, edge_ke
     check(lib.ultra_symbolic_traversal(csr.row_ptr.data_ptr(), csr.src.data_ptr(), csr.type.data_ptr(), csr.num_node,
                                        r.data_ptr(), h.shape[0], 0 if h.dtype == torch.float32 else 1, h.data_ptr(),
                                        t.data_ptr(), stream))
-    if delta is not None:
+    if delta is not None and getattr(delta, "per_query_owned", False):
+        # facts assumed per sample (rspmm.AssumedFacts): row b sees the delta's edges and sample b's own
+        edits, owner = delta.traversal_operand(), delta.traversal_owner
+        check(lib.ultra_symbolic_traversal_edit_rows_owned(csr.row_ptr.data_ptr(), csr.src.data_ptr(), csr.type.data_ptr(),
+                                                           csr.num_node, ctypes.byref(edits), owner.data_ptr(), r.data_ptr(),
+                                                           h.shape[0], 0 if h.dtype == torch.float32 else 1, h.data_ptr(),
+                                                           t.data_ptr(), stream))
+    elif delta is not None:
         edits = delta.traversal_operand()
         check(lib.ultra_symbolic_traversal_edit_rows(csr.row_ptr.data_ptr(), csr.src.data_ptr(), csr.type.data_ptr(),
                                                      csr.num_node, ctypes.byref(edits), r.data_ptr(), h.shape[0],
