@@ -676,6 +676,37 @@ int32_t ultra_filtered_rank_among(const void *score, const int64_t *pos_index, c
                                   int64_t n_cand, int64_t among_capacity, int64_t *rank_out, int64_t *num_negative_out,
                                   const int64_t *n_live, const uint32_t *retired_bits, const int64_t *n_retired, void *stream);
 
+/*
+ * The best k (query, id, score) records over MANY queries: ultra_topk_pairs_merge folds the row-wise
+ * answers of one batch into the running list of a whole call, in place.  All operands on the DEVICE:
+ *   ids (batch, k_row) int64 and scores (batch, k_row) fp32, contiguous, as any ultra_filtered_topk* entry writes them: a slot
+ *     with id < 0 is ABSENT; a slot with id >= 0 and score -inf is a genuine candidate.
+ *   query_base (one int64): row b is query *query_base + b of the call.
+ *   n_rows (one int64, or NULL: batch): read at run time and clamped to [0, batch]; rows at and beyond it are never loaded.
+ *   min_score (one fp32, or NULL): a slot is a MEMBER iff score > *min_score as an fp32 comparison -- strict, a NaN is never
+ *     a member (the rule of ultra_filtered_above).  NULL: every present slot is a member, NaNs included.  The rule is applied
+ *     to the records of the running list as well as to the batch's.
+ *   best_query (k) int64, best_id (k) int64, best_score (k) fp32, best_count (one int64): the running list.  On entry its first
+ *     *best_count records (clamped to [0, k]) are present and nothing beyond them is read; on return it holds the first
+ *     m = min(k, #members) members of [running list ; row 0 ; row 1 ; ...] in the order below, slots [m, k) hold -1 / -1 / -inf and
+ *     *best_count = m.  best_score holds STORED bits (-0.0 and NaN payloads survive).  The running list must not overlap ids or
+ *     scores.
+ * Order: score descending, then query ascending, then id ascending; every NaN above every number (NaNs tie), -0.0 == +0.0 --
+ * the stable descending torch.sort of the call's row lists laid end to end in query order.  The CALLER guarantees
+ *   (1) every query of the batch (*query_base + b) is larger than every query in the running list, and
+ *   (2) rows ascend within the batch (they do: row b is query *query_base + b), each row in the (score, id) order its
+ *       selection wrote;
+ * the position in [running list ; rows] then breaks every tie of scores the way (query, id) does, and the kernel ranks by
+ * (score, position) alone.
+ * One workgroup, one launch; no allocation, no memset, no global atomics, no host wait: a recorded call reads query_base,
+ * n_rows, min_score and the count when it is replayed.  Exact and reproducible.
+ * k or k_row outside [1, ULTRA_TOPK_MAX] or batch outside [0, 65535]: ULTRA_ERR_UNSUPPORTED; a NULL ids, scores, query_base or
+ * running-list pointer: ULTRA_ERR_INVALID; both decided before any pointer is looked at.  batch == 0: ULTRA_OK, nothing is
+ * launched (the running list is left as it is). */
+int32_t ultra_topk_pairs_merge(const int64_t *ids, const void *scores, int64_t batch, int32_t k_row, const int64_t *query_base,
+                               const int64_t *n_rows, const float *min_score, int64_t *best_query, int64_t *best_id,
+                               void *best_score, int64_t *best_count, int32_t k, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

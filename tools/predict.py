@@ -5,6 +5,7 @@
                             [--relation-capacity K] [--add-relation NAME]... [--live-relation-graph] [--remove-entity NAME]...
                             [--among NAME [NAME ...]] [--among-file FILE] [--assume H R T]...
     python tools/predict.py --data-root DIR [--ckpt FILE] --verify (--head NAME --relation NAME --tail NAME | --triples FILE) [--inverse]
+    python tools/predict.py --data-root DIR [--ckpt FILE] --propose RELATION [--propose-k K] [--min-score X] [--among-file FILE] [--inverse]
 
 DIR holds train.txt / valid.txt / test.txt (`head relation tail` per line) and optionally entities.dict / relations.dict
 (ultra_amd.data.load_triples_dir).  The query is (NAME, relation, ?); with --inverse it is (?, relation, NAME) and heads are
@@ -46,6 +47,13 @@ of a type -- and with --verify the fact is ranked among them.  An unknown name i
 32): the graph served, the delta and the known answers of later queries stay what they were; an assumed tail of the query's own
 (head, relation) is left out of its answers.  The names are those known after every edit option.  Not with --verify / --explain.
 
+--propose RELATION asks which facts of RELATION are most likely MISSING (Predictor.propose_tails): every entity in
+use is a head, and the --propose-k (default 10) best triples (head, RELATION, tail) that the dataset does not state are printed
+with their scores, best first; equal scores in the order of (head, tail) ids.  --min-score X keeps only triples whose logit
+exceeds X; --among / --among-file restrict the TAILS to a set; the edit options apply first, as for a query.  With --inverse the
+heads are ranked for every tail (Predictor.propose_heads).  Not with --verify / --explain / --assume, and --head / --relation /
+--tail / --triples / -k are refused beside it.
+
 --verify judges facts the dataset may already state: every (head, relation, tail) -- one from the command line, or the
 `head relation tail` lines of FILE -- is scored on the graph WITHOUT itself and its inverse edge (Predictor.verify_tails; with
 --inverse the head is the answer judged, Predictor.verify_heads) and printed with its score, its filtered rank and the number
@@ -81,7 +89,7 @@ def main(argv=None):
     ap.add_argument("--tail", help="--verify: the tail of the fact")
     ap.add_argument("--triples", help="--verify: a file of `head relation tail` lines")
     ap.add_argument("--inverse", action="store_true", help="predict heads of (?, relation, NAME)")
-    ap.add_argument("-k", type=int, default=10)
+    ap.add_argument("-k", type=int, default=None, help="answers of the query (default 10)")
     ap.add_argument("--unfiltered", action="store_true")
     ap.add_argument("--explain", action="store_true", help="print the top paths behind every answer")
     ap.add_argument("--no-compact", action="store_true",
@@ -114,11 +122,26 @@ def main(argv=None):
                     help="keep the relation graph current in place: no relation-graph plan, no new capture for an edit")
     ap.add_argument("--assume", nargs=3, action="append", default=[], metavar=("H", "R", "T"),
                     help="answer as if the fact (H, R, T) were true, without stating it; repeatable")
+    ap.add_argument("--propose", metavar="RELATION", help="the most likely missing facts of RELATION, over all heads")
+    ap.add_argument("--propose-k", type=int, default=10, metavar="K", help="--propose: how many triples")
+    ap.add_argument("--min-score", type=float, default=None, metavar="X", help="--propose: only triples whose logit exceeds X")
     ap.add_argument("--among", nargs="+", metavar="NAME", help="rank only these entities (a shortlist, a type)")
     ap.add_argument("--among-file", metavar="FILE", help="... the entity names of FILE, one per line")
     ap.set_defaults(edits=[])
     args = ap.parse_args(argv)
-    if args.verify:
+    if args.k is None and not args.propose:
+        args.k = 10
+    if args.propose:
+        if args.verify or args.explain or args.assume:
+            ap.error("--propose goes alone: not with --verify, --explain or --assume")
+        given = [name for name, value in (("--head", args.head), ("--relation", args.relation), ("--tail", args.tail),
+                                          ("--triples", args.triples), ("-k", args.k)) if value is not None]
+        if given:
+            ap.error("--propose takes no %s: every entity in use is a head, the relation is --propose's and the number of "
+                     "triples is --propose-k" % " / ".join(given))
+        if not 1 <= args.propose_k <= 256:
+            ap.error("--propose-k must lie in [1, 256]")
+    elif args.verify:
         if not (args.triples or (args.head and args.relation and args.tail)):
             ap.error("--verify takes --head, --relation and --tail, or --triples FILE")
     elif not (args.head and args.relation):
@@ -158,8 +181,12 @@ def main(argv=None):
             known.discard(value)
         else:
             checks.append((value, set(known)))
-    for triple in (facts if facts is not None else [(args.head, args.relation, args.head)]):
-        checks.append((triple, known))
+    if args.propose:
+        if args.propose not in rel:
+            sys.exit("unknown relation %r" % args.propose)
+    else:
+        for triple in (facts if facts is not None else [(args.head, args.relation, args.head)]):
+            checks.append((triple, known))
     if args.assume and (args.verify or args.explain):
         sys.exit("--assume goes with the plain query: not with --verify or --explain")
     for triple in args.assume:          # (judged against the names known after every edit)
@@ -182,6 +209,10 @@ def main(argv=None):
     if facts is not None:
         predictor = predict.Predictor(model, data, batch_size=min(8, len(facts)), entity_capacity=reserve,
                                       relation_capacity=rel_reserve, live_relation_graph=args.live_relation_graph)
+    elif args.propose:
+        predictor = predict.Predictor(model, data, k=args.propose_k, batch_size=8, filtered=not args.unfiltered,
+                                      entity_capacity=reserve, relation_capacity=rel_reserve,
+                                      live_relation_graph=args.live_relation_graph)
     else:
         predictor = predict.Predictor(model, data, k=args.k, batch_size=1, filtered=not args.unfiltered, entity_capacity=reserve,
                                       relation_capacity=rel_reserve, live_relation_graph=args.live_relation_graph,
@@ -240,6 +271,19 @@ def main(argv=None):
               % ("heads" if args.inverse else "tails"))
         for f, s, k, n in zip(facts, score.tolist(), rank.tolist(), num_negative.tolist()):
             print("%-28s %-24s %-28s %12.6g  %6d / %d" % (f[0], f[1], f[2], s, k, n + 1))
+        return
+    if args.propose:
+        propose = predictor.propose_heads if args.inverse else predictor.propose_tails
+        try:
+            heads, tails, scores, count = propose(rel.index(args.propose), min_score=args.min_score, **among)
+        except ValueError as exc:
+            sys.exit("--propose: %s" % exc)
+        print("(?, %s, ?): the %d most likely missing facts over all %s%s%s"
+              % (args.propose, int(count), "tails" if args.inverse else "heads",
+                 "" if args.unfiltered else ", stated facts left out",
+                 "" if args.min_score is None else ", logit above %g" % args.min_score))
+        for i in range(int(count)):
+            print("%3d  %-28s %-24s %-28s %.6g" % (i + 1, ent[int(heads[i])], args.propose, ent[int(tails[i])], float(scores[i])))
         return
     anchor = torch.tensor([ent.index(args.head)], device=dev)
     relation = torch.tensor([rel.index(args.relation)], device=dev)

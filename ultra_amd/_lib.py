@@ -37,6 +37,7 @@ RANKING_LDS_ANSWERS = 2048   # ULTRA_RANKING_LDS_ANSWERS
 TOPK_MAX = 256               # ULTRA_TOPK_MAX
 TOPK_CHUNK = 4096            # ULTRA_TOPK_CHUNK
 ABOVE_MAX_BATCH = 65535      # the most rows ultra_filtered_above takes
+PAIRS_MAX_BATCH = 65535      # the most rows ultra_topk_pairs_merge takes (csrc/pairs_kernels.hip PAIRS_MAX_BATCH)
 ARR_DENSE = 7
 ARR_DENSE_ORDER = 8
 # the layer update's flag bits: ULTRA_CONV_* and, for ultra_nbf_layer0 alone, ULTRA_LAYER0_* (include/ultra_nbfnet.h)
@@ -206,6 +207,9 @@ def _load():
     lib.ultra_filtered_above_among.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, ctypes.c_float, vp, vp, vp, i64, vp, vp, i64,
                                                vp, vp, vp, vp]
     lib.ultra_filtered_rank_among.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp]
+    # the best k (query, id, score) records over many queries: (ids, scores, batch, k_row, query_base, n_rows or
+    # None, min_score or None, best_query, best_id, best_score, best_count, k, stream)
+    lib.ultra_topk_pairs_merge.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]
     lib.ultra_query_segment.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, vp, vp, i64, vp, i64, vp, vp, vp, vp]
     lib.ultra_nonzero_lists.argtypes = [vp, i64, i64, vp, vp, vp, i64, vp]
     # ... over the live ids of rows of n slots: the device pointer to the int64 live count before the stream

@@ -13,6 +13,10 @@ and relation, leaving out the ones the graph already states?
   known_answers             the ragged lists of ids to leave out, from the filter graph (no positive is added)
   Predictor                 .tails(h, r) / .heads(t, r): candidate construction, the forward and the selection as one
                             hipGraph replay per batch; .tails_above(h, r, min_score) / .heads_above(t, r, min_score): the sets
+  merge_pairs_reference     the best k (query, id, score) records of a running list and one more batch, in plain torch
+  merge_pairs               csrc/pairs_kernels.hip (ultra_topk_pairs_merge): the running list updated in place on the device
+  best_reference            the best k (query, answer) pairs over all queries of a call: one forward per query, one stable sort
+  Predictor.best_tails / best_heads / propose_tails / propose_heads    ... the same as captured steps: link discovery
   verify_reference          leave-one-out verification of stated facts in plain torch: per triple a filtered copy of the graph
   Predictor.verify_tails    ... the same for a batch of facts as one hipGraph replay: per-sample keep masks over the cached plan
     / .verify_heads         of the full graph
@@ -326,6 +330,107 @@ def filtered_above(pred, threshold, ptr=None, index=None, num_live=None, retired
     return out_ptr, ids, scores, size
 
 
+# ---- the best k (query, id) pairs over many queries ----
+def empty_pairs(k, device=None):
+    """An empty running list of k slots -- (query (k) int64, id (k) int64, score (k) fp32, count (1) int64), every slot
+    -1 / -1 / -inf -- for merge_pairs_reference / merge_pairs to fold batches into."""
+    check_k(k)
+    return (torch.full((k,), -1, dtype=torch.long, device=device), torch.full((k,), -1, dtype=torch.long, device=device),
+            torch.full((k,), float("-inf"), dtype=torch.float32, device=device), torch.zeros(1, dtype=torch.long, device=device))
+
+
+def _pairs_operands(name, best, ids, scores):
+    """The running list and the batch of `name` (merge_pairs / merge_pairs_reference), checked: (k, batch, k_row)."""
+    if len(best) != 4:
+        raise ValueError("%s: the running list is (query (k), id (k), score (k), count (1))" % name)
+    query, best_id, best_score, count = best
+    k = int(query.numel())
+    check_k(k)
+    if (query.shape != (k,) or best_id.shape != (k,) or best_score.shape != (k,) or count.numel() != 1
+            or query.dtype != torch.long or best_id.dtype != torch.long or count.dtype != torch.long):
+        raise ValueError("%s: the running list is (query (k), id (k), score (k), count (1)), the scores apart int64" % name)
+    if ids.dim() != 2 or ids.shape != scores.shape or ids.dtype != torch.long or scores.dtype != best_score.dtype:
+        raise TypeError("%s takes (batch, k_row) int64 ids and scores of the running list's dtype, got %s %s and %s %s"
+                        % (name, tuple(ids.shape), ids.dtype, tuple(scores.shape), scores.dtype))
+    batch, k_row = ids.shape
+    if not 1 <= k_row <= _lib.TOPK_MAX or batch > _lib.PAIRS_MAX_BATCH:
+        raise ValueError("%s takes at most %d rows of 1 to %d slots, got %s" % (name, _lib.PAIRS_MAX_BATCH, _lib.TOPK_MAX,
+                                                                               tuple(ids.shape)))
+    return k, batch, k_row
+
+
+def merge_pairs_reference(best, ids, scores, query_base, n_rows=None, min_score=None):
+    """The best k (query, id, score) records of a running list and one more batch of row-wise answers, in plain torch on any
+    device -- the DEFINITION ultra_topk_pairs_merge is tested against.
+
+    best: the running list (query (k), id (k), score (k), count (1)) -- empty_pairs(k) at first --, its first `count` records
+    present.  ids, scores (batch, k_row): what a filtered_topk* call returned; row b is query query_base + b of the call; a
+    slot with id < 0 is absent, a slot with id >= 0 and score -inf is a genuine candidate.  n_rows (None: batch): only the
+    rows below it (clamped to [0, batch]) exist -- whatever the others hold.  min_score (None, or a Python float, finite or
+    -inf): a record is a MEMBER iff score > min_score in fp32 -- strict, a NaN never is (filtered_above_reference's rule);
+    None: every present record is a member, NaNs included.  The rule covers the running list's records too.
+
+    [running list ; row 0 ; row 1 ; ...] is concatenated, absent slots and non-members are dropped, and the first k of ONE
+    stable descending sort by score stay: score descending, NaN on top, -0.0 == +0.0, equal scores in the order they were laid
+    out -- which is (query, id) ascending where every query of the batch is larger than every query of the running list (the
+    caller's contract).  Returns a NEW running list, the slots beyond its count -1 / -1 / -inf; query_base, n_rows: ints or
+    one-element tensors."""
+    k, batch, k_row = _pairs_operands("merge_pairs_reference", best, ids, scores)
+    best_query, best_id, best_score, count = best
+    dev = ids.device
+    old = min(max(int(count), 0), k)
+    rows = batch if n_rows is None else min(max(int(n_rows), 0), batch)
+    query = torch.cat([best_query[:old], (int(query_base) + torch.arange(rows, device=dev)).repeat_interleave(k_row)])
+    answer = torch.cat([best_id[:old], ids[:rows].reshape(-1)])
+    score = torch.cat([best_score[:old], scores[:rows].reshape(-1)])
+    member = torch.cat([torch.ones(old, dtype=torch.bool, device=dev), ids[:rows].reshape(-1) >= 0])
+    if min_score is not None:
+        member &= score.float() > torch.tensor(_fp32_threshold(min_score), dtype=torch.float32, device=dev)
+    query, answer, score = query[member], answer[member], score[member]
+    order = torch.sort(score, descending=True, stable=True).indices[:k]
+    m = order.numel()
+    out = empty_pairs(k, dev)
+    out = (out[0], out[1], out[2].to(best_score.dtype), out[3])
+    out[0][:m], out[1][:m], out[2][:m] = query[order], answer[order], score[order]
+    out[3].fill_(m)
+    return out
+
+
+def _device_scalar(name, what, value, dtype, dev):
+    """`value` of merge_pairs' operand `what` as one `dtype` element on `dev`: a tensor is taken as it is (the kernel reads it
+    when it runs), a Python number is copied there."""
+    if torch.is_tensor(value):
+        if value.numel() != 1 or value.dtype != dtype or value.device != dev:
+            raise ValueError("%s: `%s` is a Python number or one %s on the scores' device" % (name, what, dtype))
+        return value
+    return torch.tensor([value], dtype=dtype, device=dev)
+
+
+def merge_pairs(best, ids, scores, query_base, n_rows=None, min_score=None):
+    """merge_pairs_reference through the HIP kernel (csrc/pairs_kernels.hip, ultra_topk_pairs_merge): everything fp32 / int64
+    and contiguous on one GPU.  The running list `best` is updated IN PLACE and returned.  query_base, n_rows (int64) and
+    min_score (fp32) may be one-element device tensors, which the kernel reads when it runs -- a recorded call serves new
+    values --, or Python numbers (min_score then finite or -inf)."""
+    name = "merge_pairs"
+    if not scores.is_cuda:
+        raise RuntimeError("ultra_amd.predict.%s: expected a GPU tensor; the MI355X engine has no CPU path" % name)
+    k, batch, k_row = _pairs_operands(name, best, ids, scores)
+    dev = scores.device
+    if scores.dtype != torch.float32 or any(t.device != dev or not t.is_contiguous() for t in tuple(best) + (ids, scores)):
+        raise TypeError("%s takes fp32 scores, everything contiguous on the scores' device" % name)
+    if batch == 0:
+        return best
+    base = _device_scalar(name, "query_base", query_base, torch.long, dev)       # (referenced until the launch is enqueued)
+    rows = None if n_rows is None else _device_scalar(name, "n_rows", n_rows, torch.long, dev)
+    if min_score is not None and not torch.is_tensor(min_score):
+        min_score = _fp32_threshold(min_score)
+    low = None if min_score is None else _device_scalar(name, "min_score", min_score, torch.float32, dev)
+    _lib.check(_lib.lib.ultra_topk_pairs_merge(ids.data_ptr(), scores.data_ptr(), batch, k_row, base.data_ptr(), _lib.ptr(rows),
+                                               _lib.ptr(low), best[0].data_ptr(), best[1].data_ptr(), best[2].data_ptr(),
+                                               best[3].data_ptr(), k, _lib.stream_of(scores)))
+    return best
+
+
 def known_answers(data, anchor, relation, mode="tail", extra=None):
     """(ptr (n + 1), index): per query the distinct tails of (anchor, relation, .) in `data` (mode="tail") or the distinct
     heads of (., relation, anchor) (mode="head"), ascending.  tasks.known_answers without the positive: for a true triple of
@@ -453,6 +558,7 @@ class _GraphedPredictStep(_IndexedStep):
                     self.index.data_ptr() if self.filtered else None, batch_size, n, k, self.ids.data_ptr(),
                     self.scores.data_ptr(), self.count.data_ptr(), self.ws.data_ptr(), self.ws.numel() * 8)
             _select("ultra_filtered_topk", args, n_live, dev, retired, among=self.among_operand)
+            self._after_selection()
 
         self.record_step(step, warmup, (self.anchor, self.relation), (self.ids, self.scores, self.count))
 
@@ -460,6 +566,9 @@ class _GraphedPredictStep(_IndexedStep):
     def _model_delta(self, data, delta, batch_size):
         """What the model is handed as `delta=` (None: nothing): the delta itself; _GraphedAssumeStep hands an overlay over it."""
         return delta
+
+    def _after_selection(self):
+        """What the step records behind its selection: nothing; _GraphedBestStep folds the batch into its running list."""
 
 
 def _release(steps):
@@ -714,6 +823,63 @@ def assume_reference(model, data, filter_graph, anchor, relation, assuming, k=10
     return _join_above(rows, dev)
 
 
+def _check_per_query(per_query, k, name="per_query"):
+    if per_query is not None and (isinstance(per_query, bool) or not isinstance(per_query, int) or not 1 <= per_query <= k):
+        raise ValueError("%s must be None or an int in [1, k = %d], got %r" % (name, k, per_query))
+
+
+@torch.no_grad()
+def best_reference(model, data, filter_graph, anchor, relation, k, mode="tail", min_score=None, per_query=None, among=None,
+                   num_live=None, retired=None):
+    """The best k (query, answer) pairs over ALL the queries (anchor[i], relation[i]) in plain terms, on any device -- the
+    DEFINITION Predictor.best_tails / best_heads / propose_tails / propose_heads are tested against.  Query i
+    is answered by one forward on `data` and filtered against `filter_graph` (None: no filter): its list is the first
+    `per_query or k` answers of filtered_topk_reference.  All lists are laid end to end in query order, the pads are dropped,
+    with min_score every pair whose score is not > min_score in fp32 is dropped (a NaN is), and ONE stable descending sort
+    ranks the rest: score descending, then query ascending, then id ascending, NaN on top, -0.0 == +0.0.  Returns (query (k)
+    int64 -- positions in `anchor` --, ids (k) int64, scores (k) fp32, count (0-d int64)), -1 / -1 / -inf beyond count.
+    num_live, retired, among: those of filtered_topk_reference -- among is one id vector for every query or a list of one per
+    query.  Nothing here goes batch by batch or through merge_pairs_reference."""
+    if mode not in ("tail", "head"):
+        raise ValueError("mode must be 'tail' or 'head', got %r" % (mode,))
+    check_k(k)
+    _check_per_query(per_query, k)
+    dev = data.edge_index.device
+    anchor = torch.as_tensor(anchor, dtype=torch.long, device=dev).flatten()
+    relation = torch.as_tensor(relation, dtype=torch.long, device=dev).flatten()
+    select = {} if num_live is None else {"num_live": num_live}
+    if retired is not None:
+        select["retired"] = retired
+    query, answer, score = [], [], []
+    with eval_mode(model):
+        for i in range(len(anchor)):
+            a, r = anchor[i:i + 1], relation[i:i + 1]
+            pred = model(data, _candidates(data, a, r, mode)).float()
+            ptr = index = None
+            if filter_graph is not None:
+                ptr, index = known_answers(filter_graph, a, r, mode)
+            if among is not None:
+                select["among"] = [among[i] if isinstance(among, (list, tuple)) else among]
+            ids, scores, count = filtered_topk_reference(pred, per_query or k, ptr, index, **select)
+            m = int(count[0])
+            query.append(torch.full((m,), i, dtype=torch.long, device=dev))
+            answer.append(ids[0, :m])
+            score.append(scores[0, :m])
+    out = (torch.full((k,), -1, dtype=torch.long, device=dev), torch.full((k,), -1, dtype=torch.long, device=dev),
+           torch.full((k,), float("-inf"), dtype=torch.float32, device=dev), torch.zeros((), dtype=torch.long, device=dev))
+    if not query:
+        return out
+    query, answer, score = torch.cat(query), torch.cat(answer), torch.cat(score)
+    if min_score is not None:
+        member = score > torch.tensor(_fp32_threshold(min_score), dtype=torch.float32, device=dev)
+        query, answer, score = query[member], answer[member], score[member]
+    order = torch.sort(score, descending=True, stable=True).indices[:k]
+    m = order.numel()
+    out[0][:m], out[1][:m], out[2][:m] = query[order], answer[order], score[order]
+    out[3].fill_(m)
+    return out
+
+
 def _join_above(parts, dev):
     """The (ptr, ids, scores, size) of a whole call from those of its consecutive parts."""
     out_ptr, at = [torch.zeros(1, dtype=torch.long, device=dev)], 0
@@ -745,6 +911,25 @@ class _GraphedAssumeStep(_GraphedPredictStep):
         self.route = _assume_route(delta)
         self.overlay = rspmm.AssumedFacts(data, delta, batch_size, self.per_query)
         return self.overlay
+
+
+class _GraphedBestStep(_GraphedPredictStep):
+    """_GraphedPredictStep for the best pairs over many queries: the predict step with k_row answers a query,
+    followed in the same capture by ultra_topk_pairs_merge into the step's own running list of `k_best` slots (`best`).  The
+    merge reads at replay `where` = (query_base, n_rows) -- the batch's first query and how many of its rows are no padding --
+    and, for a step made `with_floor`, the one float `min_score`; the host rewrites them between replays and zeroes the count
+    (best[3]) ahead of a call's first batch.  Nothing is recorded again for another call of the same shape."""
+
+    def __init__(self, model, data, batch_size, k_best, k_row, mode, index_capacity, with_floor, **kwargs):
+        dev = data.edge_index.device
+        self.k_best, self.k_row, self.with_floor = k_best, k_row, with_floor
+        self.best = empty_pairs(k_best, dev)
+        self.where = torch.zeros(2, dtype=torch.long, device=dev)
+        self.min_score = torch.full((1,), float("-inf"), dtype=torch.float32, device=dev)
+        _GraphedPredictStep.__init__(self, model, data, batch_size, k_row, mode, index_capacity, **kwargs)
+
+    def _after_selection(self):
+        merge_pairs(self.best, self.ids, self.scores, self.where[0:1], self.where[1:2], self.min_score if self.with_floor else None)
 
 
 class _GraphedVerifyStep(_IndexedStep):
@@ -1060,6 +1245,115 @@ class Predictor(object):
         """tails_above for the heads of (?, r[i], t[i])."""
         return self._run_above(t, r, min_score, "head", among, assuming)
 
+    # ---- the best pairs over many queries: link discovery (DESIGN.md 34) ----
+    def best_tails(self, h, r, k=None, among=None, min_score=None, per_query=None):
+        """The best k (default: the predictor's k) (query, tail) pairs over ALL the queries (h[i], r[i], ?) of the call:
+        (query (k) int64 -- positions in h --, ids (k) int64, scores (k) fp32, count (0-d int64)); slots beyond count hold
+        -1 / -1 / -inf.  Order: score descending, then query ascending, then id ascending, NaN on top, -0.0 == +0.0 -- the
+        stable descending sort of the queries' row-wise lists laid end to end (best_reference is the definition).  Known answers
+        are left out and `among` restricts the candidates as in `tails`; min_score (a Python float, finite or -inf) keeps only
+        pairs whose logit exceeds it, as in `tails_above`; per_query (an int in [1, k]) caps how many pairs one query may
+        contribute.  On the GPU every batch is one replay of a captured step of its own (key (mode, "best", k, k_row) ...): the predict
+        step with per_query or k answers a row, then ultra_topk_pairs_merge into a running list on the device, which is read
+        once after the last replay -- no per-batch copy-out.  A second call with the same k / per_query records nothing, whatever
+        the queries and min_score.  Off the GPU, without use_graph and for a model outside the fused path: filtered_topk and
+        merge_pairs (or their _reference twins) batch by batch."""
+        return self._run_best(*self._query(h, r), "tail", k, among, min_score, per_query)
+
+    def best_heads(self, t, r, k=None, among=None, min_score=None, per_query=None):
+        """best_tails for the heads of (?, r[i], t[i]): `ids` are heads, `query` positions in t."""
+        return self._run_best(*self._query(t, r), "head", k, among, min_score, per_query)
+
+    def propose_tails(self, r, heads=None, k=None, among=None, min_score=None, per_head=None):
+        """Which facts of the direct relation `r` are most likely MISSING from the graph?  The best k triples (head, r, tail)
+        over the heads `heads` -- None: every entity in use (below the live count, not retired); the name of a set
+        (define_set: its ids that are in use); or an id vector (entities in use, ValueError otherwise) --, de-duplicated and
+        ascending, that the filter graph does not state: (heads (k), tails (k), scores (k), count), -1 / -1 / -inf beyond count,
+        ordered by (score descending, head ascending, tail ascending).  best_tails over those heads: k, among (the tails'
+        candidate set), min_score as there; per_head caps the proposals of one head.  Added and retracted facts, new and
+        retired entities and relations are served as `tails` serves them -- the step is the predict step."""
+        heads, relation = self._proposers(r, heads, "heads")
+        query, ids, scores, count = self._run_best(heads, relation, "tail", k, among, min_score, per_head, "per_head")
+        return torch.where(query >= 0, heads[query.clamp(min=0)] if len(heads) else query, query), ids, scores, count
+
+    def propose_heads(self, r, tails=None, k=None, among=None, min_score=None, per_tail=None):
+        """propose_tails from the other side: the best k triples (head, r, tail) over the tails `tails`, the heads ranked by
+        best_heads -- (heads (k), tails (k), scores (k), count), ordered by (score descending, tail ascending, head ascending)."""
+        tails, relation = self._proposers(r, tails, "tails")
+        query, ids, scores, count = self._run_best(tails, relation, "head", k, among, min_score, per_tail, "per_tail")
+        return ids, torch.where(query >= 0, tails[query.clamp(min=0)] if len(tails) else query, query), scores, count
+
+    def _proposers(self, r, which, what):
+        """(anchors, relation) of propose_*: the entities `which` (None, a set's name or ids) ascending and distinct, and `r`
+        -- one direct relation in use -- once for each."""
+        dev = self.data.edge_index.device
+        if isinstance(r, bool) or (torch.is_tensor(r) and r.numel() != 1) or not (torch.is_tensor(r) or isinstance(r, int)):
+            raise ValueError("propose takes ONE direct relation (an int), got %r" % (r,))
+        r = int(r)
+        if not 0 <= r < self.num_direct_relations:
+            raise ValueError("propose takes a direct relation in use (0 <= r < %d), got %d" % (self.num_direct_relations, r))
+        if which is None or isinstance(which, str):
+            ids = torch.arange(self.num_entities, device=dev) if which is None else self._sets.resolve(which, 1)[0][1].to(dev)
+            keep = ids < self.num_entities
+            keep[torch.isin(ids, self.retired_entities.to(dev))] = False
+            ids = ids[keep]
+        else:
+            ids = torch.unique(torch.as_tensor(which, dtype=torch.long, device=dev).flatten())
+            if len(ids) and (int(ids[0]) < 0 or int(ids[-1]) >= self.num_slots):
+                raise ValueError("the %s of a proposal are entity ids in [0, %d)" % (what, self.num_slots))
+        anchors, relation = self._query(ids, torch.full_like(ids, r))
+        return anchors, relation
+
+    @torch.no_grad()
+    def _run_best(self, anchor, relation, mode, k, among, min_score, per_query, per_name="per_query"):
+        """best_tails / best_heads of the queries (anchor, relation) as _query gives them."""
+        k = self.k if k is None else k
+        check_k(k)
+        _check_per_query(per_query, k, per_name)
+        k_row = per_query or k
+        floor = None if min_score is None else _fp32_threshold(min_score)
+        data, bs, live, model_kwargs = self.data, self.batch_size, self._live, self._model_kwargs()
+        dev = data.edge_index.device
+        n = len(anchor)
+        if among is not None:
+            among = self._sets.assemble(among, n, dev)
+        state = {"best": empty_pairs(k, dev), "step": None}      # the eager route's list; the captured step that served the call
+        if n:
+            with eval_mode(self.model):
+                ptr = index = None
+                if self.filtered:       # the known lists of the whole call, once
+                    ptr, index = known_answers(self.filter_graph, anchor, relation, mode)
+
+                def eager(lo):
+                    pred = self.model(data, _candidates(data, anchor[lo:lo + bs], relation[lo:lo + bs], mode), **model_kwargs).float()
+                    on_gpu = pred.is_cuda
+                    ids, scores, _ = (filtered_topk if on_gpu else filtered_topk_reference)(
+                        pred, k_row, None if ptr is None else ptr[lo:lo + len(pred) + 1], index, **live.selection_for(on_gpu),
+                        **self._among_for(among, lo, len(pred), on_gpu))
+                    state["best"] = (merge_pairs if on_gpu else merge_pairs_reference)(state["best"], ids, scores, lo, None, floor)
+                    state["step"] = None
+                    return ()
+
+                starts = torch.arange(0, n, bs, device=dev)
+                where = torch.stack([starts, (n - starts).clamp(max=bs)], dim=1)      # (query_base, n_rows) of every batch
+
+                def before(step, lo):
+                    if lo == 0:     # a new call: the running list is empty, the floor is this call's
+                        step.best[3].fill_(0)
+                        if floor is not None:
+                            step.min_score.fill_(floor)
+                    step.where.copy_(where[lo // bs], non_blocking=True)
+                    state["step"] = step
+
+                # (k and k_row are part of the key: a caller who alternates two values keeps both captures)
+                key = (mode, "best", k, k_row) + (() if floor is None else ("floor",)) + (() if among is None else ("among",))
+                self._batched(key, lambda capacity, among_sizes=None: _GraphedBestStep(
+                    self.model, data, bs, k, k_row, mode, capacity, floor is not None, delta=self.delta, n_live=self.live_count,
+                    retired=self._live.retired_operand, **({} if among_sizes is None else {"among": among_sizes})),
+                    (anchor, relation), ptr, index, state["best"][:1], eager, among=among, before=before, copy_out=False)
+        query, ids, scores, count = (t.clone() for t in (state["best"] if state["step"] is None else state["step"].best))
+        return query, ids, scores, count.reshape(())
+
     def explain_tails(self, h, r, chunk=16, compact=True, among=None):
         """tails(h, r) plus why: (ids, scores, count, explanations).  explanations[i][j], j < count[i], is the (paths, weights)
         of model.visualize_batch for the triple (h[i], ids[i, j], r[i]) -- answer j of query i -- so every path runs from
@@ -1181,7 +1475,7 @@ class Predictor(object):
         return step
 
     def _batched(self, key, build, rows, ptr, index, outs, eager, capturable=True, among=None, route=_delta_route, before=None,
-                 eager_flag="_eager_only"):
+                 eager_flag="_eager_only", copy_out=True):
         """The batch loop of tails / heads / verify_*, inside eval_mode: `rows` (the per-query tensors a step takes) in batches of
         batch_size into `outs`.  On the GPU with use_graph each batch is one replay of the captured step `key` (_step): a last
         batch that is short is padded with copies of its last row with no known list, `index` is loaded once, and the step's
@@ -1190,7 +1484,9 @@ class Predictor(object):
         among (None, or the call's (span, index, longest) of CandidateSets.assemble): the step -- under a key of its own --
         takes the call's lists once (load_among) and a batch's spans per replay; a padded row gets an empty span.
         route: what the step remembers of the delta (_step); before(step, lo): called ahead of the replay of the batch at lo;
-        eager_flag: the attribute that remembers "this route is not capturable here" -- every route owns its own."""
+        eager_flag: the attribute that remembers "this route is not capturable here" -- every route owns its own.
+        copy_out=False (the best pairs): a step that keeps its result itself -- nothing is copied out of its buffers
+        per batch, `outs` only tells the device, and eager(lo) keeps its own result and returns ()."""
         n, bs = len(rows[0]), self.batch_size
         start = 0
         if capturable and self.use_graph and outs[0].is_cuda and not getattr(self, eager_flag):
@@ -1213,7 +1509,7 @@ class Predictor(object):
                     if before is not None:
                         before(step, lo)
                     got = step(*(t[lo:lo + bs] for t in padded), None if ptr_p is None else ptr_p[lo:lo + bs + 1])
-                    for out, b_out in zip(outs, got):
+                    for out, b_out in zip(outs, got if copy_out else ()):
                         out[lo:lo + bs].copy_(b_out[:min(bs, n - lo)], non_blocking=True)
                 start = n
             except models.NotOnFusedPath:       # model outside the fused inference path: everything runs eagerly below
